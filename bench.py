@@ -4,8 +4,15 @@
 uniform-random policy, synthetic deals).
 
     python bench.py --gpus 1 --steps 100 --warmup 10          (the defaults)
+    python bench.py --full                                   (+ repeats, side measurements, CPU baseline)
+    python bench.py --dump-outputs DIR                       (+ the last timed step's outputs as DIR/*.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the --steps launches of the headline and prints the line; everything
+else it can measure runs only with --full.  --dump-outputs DIR writes, after the timed launches and outside
+the clock, what the last one computed (dump_outputs: a fixed, seeded sample of the games); the inputs depend
+only on the arguments, so two builds can be compared array for array.
 
 One bench "step" = one pass of the hot path over the batch = ONE launch of
 tarok_krog_random: `--cards-per-launch` (default 128 = thirty-two tricks) lock-steps of every
@@ -22,11 +29,11 @@ graph, so that the capture is untimed, and to ~25 ms of launches, so that the GP
 idle clocks: `warmup` reports what ran).  Weak scaling: each rank
 owns its own 65,536 games (global game indices rank*65536...), no collective in the env path.
 
-BASELINE.md's protocol: `value` is the first timed region (seed 0: the contract's number); the further
+BASELINE.md's protocol (--full): `value` is the first timed region (seed 0: the contract's number); the further
 regions of --repeats rotate the seeds {0, 1, 2} (one env per seed, each warmed up and graph-captured untimed)
 and are reported as a spread and per seed.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (all but roofline and issue_roofline, which read committed profiles, need --full):
   roofline           the dominant kernel (k_play_wide: tarok_krog_random) against HBM peak.  `achieved` =
                      HBM bytes per launch / launch duration (HIP events on the launch stream
                      over the timed region / launches).  For launches of several cards the
@@ -181,6 +188,46 @@ def cpu_baseline(n_games_chunk, mix, min_seconds=10.0, max_seconds=25.0):
             "single_core_value": r1["total_steps"] / dt1}
 
 
+DUMP_GAMES = 4096               # --dump-outputs: games of the fixed sample (seed DUMP_SEED), all cards of the last launch
+DUMP_SEED = 0
+
+
+def dump_outputs(env, cards, out_dir):
+    """--dump-outputs: what the last timed launch handed its caller, for a fixed, seeded sample of the games.
+    Rows are the launch's cards ([cards, games]; one row in the one-card modes):
+      game_index  the sampled game slots (sorted)
+      action      the card played (u8 -> float32)
+      done        1 iff the game finished on that card (multi-card launches: the done rows the path writes)
+      reward      [rows, games, 4] scores by seat where the game finished, 0 elsewhere (the library writes them
+                  only there; i16 -> float32)
+      obs_lo/hi   the observation word's bits [31:0] / [63:32] (u64 -> two float64, exact)
+    At most 192 x 4,096 x 40 B = 31 MB in all.  -> {"dir", "games", "rows", "files"}"""
+    import numpy as np
+    import torch
+    if cards >= 2:
+        kb = env._krog_bufs(cards)             # the buffers tarok_run_random wrote (no new allocation: same cards)
+        rows = dict(action=kb["action"], done=kb["done"], reward=kb["reward"], obs=kb["obs"])
+    else:                                      # (the one-card legs leave the done row out: bit 62 of the word says it)
+        rows = dict(action=env.action[None], reward=env.reward[None], obs=env.obs_words[None])
+    n = rows["obs"].shape[1]
+    games = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_GAMES), replace=False))
+    idx = torch.from_numpy(games).to(rows["obs"].device)
+    pick = {k: v.index_select(1, idx) for k, v in rows.items()}
+    words = pick["obs"]
+    finished = pick["done"] != 0 if "done" in pick else ((words >> 62) & 1) != 0
+    arrays = {"game_index": games.astype(np.float64),
+              "action": pick["action"].to(torch.float32).cpu().numpy(),
+              "reward": torch.where(finished[..., None], pick["reward"], torch.zeros_like(pick["reward"])).to(torch.float32).cpu().numpy(),
+              "obs_lo": (words & 0xFFFFFFFF).to(torch.float64).cpu().numpy(),
+              "obs_hi": ((words >> 32) & 0xFFFFFFFF).to(torch.float64).cpu().numpy()}
+    if "done" in pick:
+        arrays["done"] = pick["done"].to(torch.float32).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "games": int(games.size), "rows": int(words.shape[0]), "files": sorted(k + ".npy" for k in arrays)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -188,19 +235,27 @@ def main():
                     help="timed passes of the hot path = kernel launches of --cards-per-launch lock-steps each "
                          "(default 100 x 128 = 12,800 lock-steps, ~350 games per slot)")
     ap.add_argument("--warmup", type=int, default=10, help="untimed passes (raised to one whole graph)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps passes in all, reported as a spread")
+    ap.add_argument("--full", action="store_true",
+                    help="also the seed repeats, the side measurements (other launch modes, sizes and configurations, "
+                         "self-play) and the CPU baseline; a plain run times the headline region only")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps passes in all, reported as a spread (default 5 with --full, else 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--games", type=int, default=65536, help="games per GPU")
     ap.add_argument("--graph-chunk", type=int, default=4096, help="at most this many lock-steps per replayed hipGraph (0 = eager)")
     ap.add_argument("--cards-per-launch", type=int, default=128,
                     help="headline mode: cards of every game per launch (4 = one trick = one pass of the reference's krog; "
                          "48 = twelve tricks = the longest game; 128 = thirty-two tricks, where the time between launches "
                          "stops mattering at 65,536 games; 1 = one card per launch), at most 192")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the side measurements")
     ap.add_argument("--strict", action="store_true", help="exit 1 (after printing the line) when a side leg failed")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0 or not (1 <= args.cards_per_launch <= 192):
         ap.error("--steps >= 1, --warmup >= 0, 1 <= --cards-per-launch <= 192")
+    repeats = args.repeats if args.repeats is not None else (5 if args.full else 1)
+    extras = args.full and not args.no_extras
 
     import torch
     from tarok_amd import TarokVecEnv, karte as K, sharding
@@ -278,11 +333,13 @@ def main():
     pg = sharding.group_info()
     env_steps = n * plan["lock_steps"] * world_size
     value = env_steps / dt
-    # 5 repeats over the seeds {0, 1, 2}, median (min-max).  `value` stays the first region (seed 0: the
-    # contract's one); every further seed gets its own env, warmed up and graph-captured like the first
+    # (before the repeats: the fourth region runs on this env again)
+    dumped = dump_outputs(env, cards, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    # 5 repeats over the seeds {0, 1, 2}, median (min-max).  `value` stays the first region (seed 0:
+    # the contract's one); every further seed gets its own env, warmed up and graph-captured like the first
     seed_envs = {SEEDS[0]: env}
     spread, per_seed = [value], {str(SEEDS[0]): [value]}
-    for k in range(1, max(1, args.repeats)):
+    for k in range(1, max(1, repeats)):
         sd = SEEDS[k % len(SEEDS)]
         if sd not in seed_envs:
             e2 = TarokVecEnv(n, device=local_rank, seed=sd, mix=K.MIX_ALL, game_offset=offset)
@@ -324,6 +381,8 @@ def main():
                     "note": "region k runs seed k mod 3 (its own env and graph); `value` is region 0"},
         "kernel_src_sha": sha,
     }
+    if dumped:
+        out["dump_outputs"] = dumped
 
     if rank == 0:
         # ---- roofline of the dominant kernel (k_play_wide): HIP events on the launch stream around the
@@ -398,7 +457,7 @@ def main():
                 iss["play_role_wave_time_waiting_frac"] = po["SQ_WAIT_ANY"]["mean"] / po["SQ_WAVE_CYCLES"]["mean"]
             out["issue_roofline"] = iss
 
-    if not args.no_extras:
+    if extras:
         # ---- side measurements (not `value`); lock-steps per region = the headline's, capped
         side_steps = min(plan["lock_steps"], SIDE_LOCK_STEPS_CAP)
         # (a) the C-ABI surface an external policy drives: tarok_policy_random writes the action array,
@@ -544,7 +603,7 @@ def main():
             errors.append("selfplay_ppo: " + repr(ex))
             print("bench.py: the self-play side leg FAILED: %r" % (ex,), file=sys.stderr)
 
-    if rank == 0 and world_size == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world_size == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(1 << 20, K.MIX_ALL)
     out["side_leg_errors"] = errors
 

@@ -86,6 +86,22 @@ class FakeEnv:
     def close(self):
         pass
 
+    def _krog_bufs(self, cards):
+        """The [cards, N] output rows of the multi-card launches: seeded noise, every bit of the word in play."""
+        if getattr(self, "_kb_cards", 0) != cards:
+            g = torch.Generator().manual_seed(cards)
+            self._kb = dict(action=torch.randint(0, 255, (cards, self.n), dtype=torch.uint8, generator=g),
+                            reward=torch.randint(-500, 500, (cards, self.n, 4), dtype=torch.int16, generator=g),
+                            done=torch.randint(0, 2, (cards, self.n), dtype=torch.uint8, generator=g),
+                            obs=torch.randint(-2 ** 63, 2 ** 63 - 1, (cards, self.n), dtype=torch.int64, generator=g))
+            self._kb_cards = cards
+        return self._kb
+
+    # the one-card modes' [N] buffers (only the dump reads them)
+    action = property(lambda self: self._krog_bufs(1)["action"][0])
+    reward = property(lambda self: self._krog_bufs(1)["reward"][0])
+    obs_words = property(lambda self: self._krog_bufs(1)["obs"][0])
+
 
 class FakeEvent:
     def __init__(self, enable_timing=False):
@@ -123,7 +139,7 @@ def fake_gpu(monkeypatch):
                                   ["--steps", "1", "--warmup", "0"], ["--steps", "47", "--cards-per-launch", "5"],
                                   ["--steps", "3", "--cards-per-launch", "1"], []])
 def test_bench_line_on_a_fake_env(fake_gpu, monkeypatch, capsys, argv):
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--no-cpu-baseline"] + argv)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"] + argv)
     bench.main()
     out = capsys.readouterr()
     line = json.loads(out.out.strip().splitlines()[-1])
@@ -163,11 +179,70 @@ def test_bench_line_on_a_fake_env(fake_gpu, monkeypatch, capsys, argv):
 
 
 def test_bench_strict_exits_nonzero_after_printing(fake_gpu, monkeypatch, capsys):
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--no-cpu-baseline", "--strict", "--steps", "2"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline", "--strict", "--steps", "2"])
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert e.value.code == 1
     assert json.loads(capsys.readouterr().out.strip().splitlines()[-1])["side_leg_errors"]
+
+
+@pytest.mark.parametrize("argv", [["--gpus", "1", "--steps", "20", "--warmup", "5"], ["--steps", "3", "--cards-per-launch", "1"]])
+def test_plain_bench_runs_the_headline_only(fake_gpu, monkeypatch, capsys, argv):
+    """Without --full: one env, reset, the warm-up, ONE timed region of exactly --steps launches, the line —
+    no repeats, no side legs, no CPU baseline."""
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: pytest.fail("a plain run timed the CPU baseline"))
+    bench.main()
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    a = dict(zip(argv[::2], argv[1::2]))
+    steps, cards = int(a["--steps"]), int(a.get("--cards-per-launch", 128))
+    assert line["steps"] == line["steps_requested"] == steps == line["config"]["launch_plan"]["launches"]
+    assert line["metric"] == bench.baseline_metric() and line["unit"] == "env steps/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "u64" and line["value"] > 0
+    assert line["ms_per_step"] == pytest.approx(line["timed_region"]["wall_ms_max_over_ranks"] / steps)
+    assert len(FakeEnv.instances) == 1
+    p = line["config"]["launch_plan"]
+    assert FakeEnv.instances[0].calls == [("reset",), ("run", line["warmup"] * max(1, cards), cards, p["graph_chunk"]),
+                                          ("run", p["lock_steps"], cards, p["graph_chunk"])]
+    for k in ("api_two_kernel", "roofline_step_api", "config2", "one_trick_per_launch", "one_card_per_launch",
+              "fused_rollout", "selfplay_ppo", "cpu_baseline", "dump_outputs"):
+        assert k not in line
+    assert line["repeats"]["n"] == 1 and line["side_leg_errors"] == []
+
+
+@pytest.mark.parametrize("cards", [128, 5, 1])
+def test_dump_outputs_writes_the_last_timed_launch(fake_gpu, monkeypatch, capsys, tmp_path, cards):
+    """--dump-outputs DIR: the rows of the last timed launch for a fixed, seeded sample of the games, float32 /
+    float64 only, reward zeroed where the library leaves it unwritten, the word split exactly; the same files
+    on a second run, and with --full (the dump is taken before the repeats reuse the env)."""
+    import numpy as np
+    dumps = []
+    for extra in ([], [], ["--full", "--no-cpu-baseline"]):
+        d = tmp_path / ("d%d" % len(dumps))
+        FakeEnv.instances.clear()
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--cards-per-launch", str(cards), "--dump-outputs", str(d)] + extra)
+        bench.main()
+        line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+        rows = cards if cards >= 2 else 1
+        names = ["action", "game_index", "obs_hi", "obs_lo", "reward"] + (["done"] if cards >= 2 else [])
+        assert line["dump_outputs"] == {"dir": str(d), "games": bench.DUMP_GAMES, "rows": rows, "files": sorted(k + ".npy" for k in names)}
+        arrs = {k: np.load(d / (k + ".npy")) for k in names}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        dumps.append(arrs)
+    kb = FakeEnv.instances[0]._krog_bufs(cards if cards >= 2 else 1)
+    arrs = dumps[0]
+    g = arrs["game_index"].astype(np.int64)
+    assert g.size == bench.DUMP_GAMES and (np.diff(g) > 0).all() and 0 <= g[0] and g[-1] < 65536
+    words = kb["obs"].numpy()[:, g].view(np.uint64)
+    assert (arrs["obs_lo"].astype(np.uint64) | (arrs["obs_hi"].astype(np.uint64) << np.uint64(32)) == words).all()
+    assert (arrs["action"] == kb["action"].numpy()[:, g]).all()
+    fin = kb["done"].numpy()[:, g] != 0 if cards >= 2 else (words >> np.uint64(62)) & np.uint64(1) != 0
+    assert (arrs["reward"] == np.where(fin[..., None], kb["reward"].numpy()[:, g], 0)).all() and fin.any() and (~fin).any()
+    if cards >= 2:
+        assert (arrs["done"] == kb["done"].numpy()[:, g]).all()
+    for other in dumps[1:]:
+        assert all((other[k] == arrs[k]).all() for k in arrs)
 
 
 def test_the_mode_string_names_the_library_constant():

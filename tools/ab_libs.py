@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Diagnostic (GPU box): same-box A/B of libraries under tools/ab/ (each built by hand with its -D flags):
-bench.py --no-extras --no-cpu-baseline per library and batch size, medians of the repeats.
+bench.py --full --no-extras --no-cpu-baseline per library and batch size, medians of the repeats.
 
     python tools/ab_libs.py base.so,prio3.so 65536,1048576 [steps]"""
 import json, os, subprocess, sys
@@ -13,7 +13,7 @@ for n in sizes:
     row = []
     for lib in libs:
         env = dict(os.environ, TAROK_LIB=os.path.join(HERE, "ab", lib))
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-extras", "--no-cpu-baseline", "--games", str(n), "--steps", steps],
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-extras", "--no-cpu-baseline", "--games", str(n), "--steps", steps],
                              env=env, capture_output=True, text=True, timeout=600)
         if out.returncode != 0:
             print(lib, n, "FAILED", out.stderr[-400:]); sys.exit(1)

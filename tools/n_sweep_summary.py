@@ -15,7 +15,7 @@ for n in (65536, 1048576, 4194304, 16777216):
     rows.append({"games": n, "value_env_steps_per_s": d["value"], "us_per_lock_step": d["us_per_lock_step"],
                  "launch_us": d["roofline"]["launch_us"], "cards_per_launch": d["config"]["cards_per_launch"], "steps": d["steps"],
                  "warmup": d["warmup"], "algorithmic_54B_GBps": algo["achieved"], "algorithmic_frac": algo["frac"], "repeats": d["repeats"]})
-json.dump({"source": "python bench.py --games N --steps 8 --warmup 4 --no-cpu-baseline --no-extras (tools/profile_round.sh)",
+json.dump({"source": "python bench.py --full --games N --steps 8 --warmup 4 --no-cpu-baseline --no-extras (tools/profile_round.sh)",
            "kernel_src_sha": sha, "rows": rows}, open(out, "w"), indent=1)
 for r in rows:
     print(r["games"], "%.1f G steps/s (median %.1f)" % (r["value_env_steps_per_s"] / 1e9, r["repeats"]["median"] / 1e9), "launch %.1f us" % r["launch_us"])

@@ -8,25 +8,25 @@ CARDS=${2:-128}          # the bench's default cards per launch
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python3 bench.py > $OUT/bench_line.json 2> $OUT/bench.err || exit 1
+python3 bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err || exit 1
 echo "bench done"; cut -c1-300 $OUT/bench_line.json
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_line_driver_command.json 2>> $OUT/bench.err || exit 1
 echo "driver-command bench done"; cut -c1-300 $OUT/bench_line_driver_command.json
 # headline mode only: every k_play dispatch in this trace is a launch of the timed mode
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --no-cpu-baseline --no-extras > $OUT/stats_bench.json 2> $OUT/stats.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --full --no-cpu-baseline --no-extras > $OUT/stats_bench.json 2> $OUT/stats.err || exit 1
 # all modes (one trick / one card per launch, two-kernel path, rollout, self-play side measurements)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_all -- python3 bench.py --no-cpu-baseline > $OUT/stats_all_bench.json 2> $OUT/stats_all.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_all -- python3 bench.py --full --no-cpu-baseline > $OUT/stats_all_bench.json 2> $OUT/stats_all.err || exit 1
 echo "stats done"
 # HBM traffic: separate passes per counter; headline only, then with the side legs (the step API's kernels)
 for C in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/pmc_headline_$C -- python3 bench.py --steps 20 --warmup 4 --repeats 2 --no-cpu-baseline --no-extras > $OUT/pmc_headline_$C.json 2> $OUT/pmc_headline_$C.err || exit 1
-  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/pmc_all_$C -- python3 bench.py --steps 20 --warmup 4 --repeats 2 --no-cpu-baseline > $OUT/pmc_all_$C.json 2> $OUT/pmc_all_$C.err || exit 1
+  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/pmc_all_$C -- python3 bench.py --full --steps 20 --warmup 4 --repeats 2 --no-cpu-baseline > $OUT/pmc_all_$C.json 2> $OUT/pmc_all_$C.err || exit 1
 done
 echo "pmc done"
 python3 tools/pmc_summary.py $OUT/pmc_headline_FETCH_SIZE $OUT/pmc_headline_WRITE_SIZE $CARDS 65536 $OUT/pmc_fetch_write_65536.json
 python3 tools/pmc_summary.py $OUT/pmc_all_FETCH_SIZE $OUT/pmc_all_WRITE_SIZE $CARDS 65536 $OUT/pmc_fetch_write_all_modes_65536.json
 for N in 65536 1048576 4194304 16777216; do
-  python3 bench.py --games $N --steps 8 --warmup 4 --no-cpu-baseline --no-extras > $OUT/bench_N$N.json 2>> $OUT/nsweep.err || exit 1
+  python3 bench.py --full --games $N --steps 8 --warmup 4 --no-cpu-baseline --no-extras > $OUT/bench_N$N.json 2>> $OUT/nsweep.err || exit 1
   cut -c1-200 $OUT/bench_N$N.json
 done
 bash tools/sq_counters.sh 65536 $TAG/sq64k > /dev/null 2>&1 && cp gpurun_out/$TAG/sq64k/sq_counters.json $OUT/sq_counters.json

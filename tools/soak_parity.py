@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Diagnostic (GPU box): a run of the size and shape of the default bench run (49,152 warm-up + 5 x 12,800 timed
+"""Diagnostic (on an MI355X): a run of the size and shape of a `bench.py --full` run (49,152 warm-up + 5 x 12,800 timed
 lock-steps, 128 cards per launch, graphs of 25 launches, 65,536 games, auto-reset) compared with the CPU oracle
 at the end: episode numbers, score sums, canonical state, observation words (the oracle replays the 113,152
 lock-steps of all 65,536 slots on the host cores)."""
