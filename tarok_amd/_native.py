@@ -12,7 +12,7 @@ SRC = os.path.join(HERE, "csrc", "tarok_env.hip")
 DEPS = [SRC, os.path.join(HERE, "csrc", "tarok_device.h"), os.path.join(HERE, "csrc", "deal_network.inc"),
         os.path.join(HERE, "csrc", "tarok_learner.inc"),
         os.path.join(ROOT, "include", "tarok_env.h")]
-LIB_PATH = os.environ.get("TAROK_LIB") or os.path.join(HERE, "libtarokenv.so")   # TAROK_LIB: A/B diagnostics only
+LIB_PATH = os.path.join(HERE, "libtarokenv.so")
 ARCH = "gfx950"
 
 SYMBOLS = [
@@ -37,10 +37,6 @@ def hipcc_path():
 
 
 def needs_build():
-    if os.environ.get("TAROK_LIB"):          # an A/B library is whatever its builder made it: never rebuilt over
-        if not os.path.exists(LIB_PATH):
-            raise FileNotFoundError("TAROK_LIB=%s does not exist" % LIB_PATH)
-        return False
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
@@ -126,8 +122,7 @@ def lib():
     L.tarok_create.restype = i32; L.tarok_create.argtypes = [C.POINTER(vp), i32, i64, u64, u64, i32, i32]
     L.tarok_destroy.restype = None; L.tarok_destroy.argtypes = [vp]
     L.tarok_num_games.restype = i64; L.tarok_num_games.argtypes = [vp]
-    if hasattr(L, "tarok_set_option"):      # (absent from older libraries loaded through TAROK_LIB for A/B runs)
-        L.tarok_set_option.restype = i32; L.tarok_set_option.argtypes = [vp, i32, i32]
+    L.tarok_set_option.restype = i32; L.tarok_set_option.argtypes = [vp, i32, i32]
     L.tarok_reset.restype = i32; L.tarok_reset.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, i32, vp]
     L.tarok_exchange.restype = i32; L.tarok_exchange.argtypes = [vp, vp, vp, vp]
     L.tarok_legal_actions.restype = i32; L.tarok_legal_actions.argtypes = [vp, vp, vp, vp]
@@ -146,24 +141,20 @@ def lib():
     L.tarok_expand_features.restype = i32; L.tarok_expand_features.argtypes = [vp, i64, vp, vp, vp, vp]
     f32 = C.c_float
     L.tarok_ppo_loss.restype = i32; L.tarok_ppo_loss.argtypes = [vp, i64] + [vp] * 7 + [f32] * 3 + [vp] * 4
-    if hasattr(L, "tarok_targets_ref"):
-        L.tarok_targets_ref.restype = i32; L.tarok_targets_ref.argtypes = [vp, i32] + [vp] * 6 + [f32] + [vp] * 3
-    if hasattr(L, "tarok_learn_chain"):
-        L.tarok_learn_returns.restype = i32; L.tarok_learn_returns.argtypes = [vp, i32] + [vp] * 6 + [f32] + [vp] * 4
-        L.tarok_learn_chain.restype = i32; L.tarok_learn_chain.argtypes = [vp, i64] + [vp] * 4 + [f32] * 3 + [vp] * 18
-        L.tarok_learn_workspace_bytes.restype = i64; L.tarok_learn_workspace_bytes.argtypes = [vp]
-        L.tarok_learn_dw.restype = i32; L.tarok_learn_dw.argtypes = [vp, i64] + [vp] * 10
-        L.tarok_learn_adam.restype = i32; L.tarok_learn_adam.argtypes = [vp] * 6 + [f32] * 5 + [vp] * 6 + [i32, vp]
+    L.tarok_targets_ref.restype = i32; L.tarok_targets_ref.argtypes = [vp, i32] + [vp] * 6 + [f32] + [vp] * 3
+    L.tarok_learn_returns.restype = i32; L.tarok_learn_returns.argtypes = [vp, i32] + [vp] * 6 + [f32] + [vp] * 4
+    L.tarok_learn_chain.restype = i32; L.tarok_learn_chain.argtypes = [vp, i64] + [vp] * 4 + [f32] * 3 + [vp] * 18
+    L.tarok_learn_workspace_bytes.restype = i64; L.tarok_learn_workspace_bytes.argtypes = [vp]
+    L.tarok_learn_dw.restype = i32; L.tarok_learn_dw.argtypes = [vp, i64] + [vp] * 10
+    L.tarok_learn_adam.restype = i32; L.tarok_learn_adam.argtypes = [vp] * 6 + [f32] * 5 + [vp] * 6 + [i32, vp]
     L.tarok_observe_ref.restype = i32; L.tarok_observe_ref.argtypes = [vp, vp, vp, vp]
     L.tarok_observe_exchange_ref.restype = i32; L.tarok_observe_exchange_ref.argtypes = [vp, vp, vp]
     L.tarok_observe_hands_ref.restype = i32; L.tarok_observe_hands_ref.argtypes = [vp, vp, vp]
     L.tarok_get_history.restype = i32; L.tarok_get_history.argtypes = [vp, vp, vp]
     L.tarok_set_history.restype = i32; L.tarok_set_history.argtypes = [vp, vp, vp]
     L.tarok_debug_stamps.restype = i32; L.tarok_debug_stamps.argtypes = [vp, vp]
-    if hasattr(L, "tarok_debug_stamps_sized"):      # (absent from older libraries loaded through TAROK_LIB for A/B runs)
-        L.tarok_debug_stamps_sized.restype = i32; L.tarok_debug_stamps_sized.argtypes = [vp, vp, i64]
-    if hasattr(L, "tarok_debug_refill_selftest"):
-        L.tarok_debug_refill_selftest.restype = i32; L.tarok_debug_refill_selftest.argtypes = [vp, i32, i32, u32, i32, i32, vp]
+    L.tarok_debug_stamps_sized.restype = i32; L.tarok_debug_stamps_sized.argtypes = [vp, vp, i64]
+    L.tarok_debug_refill_selftest.restype = i32; L.tarok_debug_refill_selftest.argtypes = [vp, i32, i32, u32, i32, i32, vp]
     L.tarok_set_state.restype = i32; L.tarok_set_state.argtypes = [vp, vp, vp]
     L.tarok_get_counters.restype = i32; L.tarok_get_counters.argtypes = [vp, vp, vp, vp]
     _lib = L

@@ -38,9 +38,7 @@
 
 #include "../../include/tarok_env.h"
 
-#ifndef TK_BLOCK
-#define TK_BLOCK 256               // (512 / 1024: diagnostics builds only, tools/ab_build.sh — more play waves per SIMD on fewer CUs)
-#endif
+#define TK_BLOCK 256               // game slots per play workgroup (the MLP and learner kernels are laid out for 256)
 #define TK_PF_SLOTS (4 * TK_BLOCK)
 #define TK_GRAPH_CACHE 16          // instantiated graphs kept per env (tarok_run_random)
 #define TK_REFILL_CAP (TK_BLOCK * TK_AHEAD) // refill-list entries per play workgroup and launch (<= TK_AHEAD per slot)
@@ -48,23 +46,15 @@
 // list lengths: one 128-byte line per (play workgroup, parity) — neighbouring workgroups run on
 // different XCDs, whose L2s are not coherent: two of them must never write into one line
 #define TK_RC(group, k) ((((size_t)(group)) * 4 + (k)) * 32)     // k = 0, 1: the per-launch lists by parity; 2, 3: the one-card step's stretch lists
-#ifndef TK_BULK_EVERY
 #define TK_BULK_EVERY 32u          // one-card launches per stretch (a power of two; see launch_count): the stretch lists are dealt in bulk this often
-#endif
 #define TK_BULK_CAP ((TK_BULK_EVERY / 4) * TK_BLOCK)  // entries of a stretch list: a game is at least four cards long, one card per launch
 
-#ifndef TK_AHEAD
 #define TK_AHEAD TAROK_GAMES_AHEAD  // next-game lines per slot (<= 15: epar and cprev are 4 bits each)
-#endif
 #define TK_LINE(episode) ((u32)(episode) % (u32)TK_AHEAD)
 #define TK_FINQ 128                 // entries of a play wave's finished-games ring (a power of two >= 128)
 // The per-card outputs are written once and never read back by the kernels: non-temporal stores, so that
 // they stream out during the launch instead of piling up as dirty L2 lines for the write-back at its end
-#ifndef TK_NO_STREAM_STORES
 #define TK_STREAM_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#else
-#define TK_STREAM_STORE(ptr, val) (*(ptr) = (val))
-#endif
 // s_waitcnt vmcnt(0) (gfx9 encoding: expcnt and lgkmcnt left at their maxima)
 #define TK_WAIT_LOADS() __builtin_amdgcn_s_waitcnt(0x0F70)
 // wave-uniform branches of the card loop (play_role): a taken branch costs a lone wave ~25 cycles, one that falls
@@ -555,7 +545,7 @@ __device__ __forceinline__ void play_role(
     // Deferred scoring (the multi-card kernel): a game that ends leaves its final state in a per-wave LDS ring
     // (9 dwords) instead of being scored on the spot — with ~10 % of the slots finishing per trick the
     // scoring code (both contract families, ~250 instructions) ran for every wave on every trick with 7 of 64
-    // lanes active: a third of a play wave's time at 65,536 games (tools/card_probe.py).  Whenever 64 entries
+    // lanes active: a third of a play wave's time at 65,536 games (profiles/r02_card_probe_before.txt).  Whenever 64 entries
     // wait they are scored in ONE pass on full lanes (drain_finished); the rest at the end of the launch.  The
     // scores go to their reward row from there and are summed per slot in LDS (sacc) for the slot's score_sum.
     __shared__ u32 finq[TK_BLOCK / 64][9][TK_FINQ];
@@ -647,16 +637,6 @@ __device__ __forceinline__ void play_role(
     launch_counted<1>(epoch);
     g.cprev = 0;
     u32 consumed = 0;                       // games swapped in / dealt during this launch
-#ifdef TK_EVENT_STAMPS                      // diagnostics build (tools/ev_probe.py): per-wave event counts
-    u32 ev_deal = 0, ev_lazy = 0, ev_renew = 0, ev_early = 0;
-#endif
-#ifdef TK_CARD_STAMPS
-    u32 cs_012 = 0, cs_3 = 0, cs_seg[4] = {0, 0, 0, 0};      // cs_seg: the 4th card's rules | scoring queue | renewal | outputs
-    u64 cs_t = 0;
-#define TK_SEG(k) do { if constexpr (ALL && NT == 3) { u64 t_ = __builtin_amdgcn_s_memtime(); cs_seg[k] += (u32)(t_ - cs_t); cs_t = t_; } } while (0)
-#else
-#define TK_SEG(k) do { } while (0)
-#endif
     bool resync = false;                    // a line that should have been usable was not: refill them all
     bool blocked = false;                   // a game was dealt in place: no more swap-ins in this launch
     bool acc_dirty = false, seats_dirty = false, touched = false;
@@ -705,9 +685,6 @@ __device__ __forceinline__ void play_role(
             // a scalar test here, not a vote on per-lane conditions at every trick.  Which lane holds which line
             // is read off the tags: a lane holds the line of its next game if nep1 is that game's number.)
             if (TK_RARE(pending != 0)) {
-#ifdef TK_EVENT_STAMPS
-                ev_early++;
-#endif
                 pending = 0;
                 bool base = spec && blocked_v == 0 && consumed >= 1;
                 bool lacks = base && nep1 != cur_ep + 1 && consumed < allowed;
@@ -717,9 +694,6 @@ __device__ __forceinline__ void play_role(
         }
         const bool v = ALL ? true : valid;
         const bool play = ALL ? true : (valid && g.phase == TK_PHASE_PLAY);
-#ifdef TK_CARD_STAMPS
-        if constexpr (ALL && NT == 3) cs_t = __builtin_amdgcn_s_memtime();
-#endif
         u32 a = play ? policy_action(key, g.trick_no * 4 + g.nt, legal) : 255u;
         u64 scores = 0;
         u32 trick_info = 0;
@@ -743,7 +717,6 @@ __device__ __forceinline__ void play_role(
             if (STD || action_out) TK_STREAM_STORE(&action_out[row], (uint8_t)a);
             if (!STD && trick) TK_STREAM_STORE(&trick[row], (uint16_t)trick_info);
         }
-        TK_SEG(0);
         // (cards 0..2 of a trick cannot end a game: no finish / renewal code in their copies)
         constexpr bool CAN_END = !(ALL && NT >= 0 && NT < 3);
         // the trick-aligned loop: queue + renewal of the finishing lanes in one exec region, every per-lane fact
@@ -773,9 +746,6 @@ __device__ __forceinline__ void play_role(
         auto deal_in_place = [&](bool deal_here, Game &gd, u64 &kd) __attribute__((always_inline)) {
             u64 pend = __ballot(deal_here);
             if (TK_RARE(pend != 0)) {
-#ifdef TK_EVENT_STAMPS
-                ev_deal += (u32)__popcll(pend);
-#endif
                 u64 dkey = 0;
                 if (deal_here) dkey = game_key(seed, offset + (u64)i, cur_ep + 1);
                 u64 h0 = 0, h1 = 0, h2 = 0, h3 = 0, tal = 0;
@@ -809,9 +779,6 @@ __device__ __forceinline__ void play_role(
             // inside a divergent region, and every compare -> mask -> select hop stalls a lone wave: tools/valu_issue.)
             u64 fm = __ballot(fin);
             if (TK_USUAL(fm != 0)) {                                      // (wave uniform)
-#ifdef TK_EVENT_STAMPS
-                ev_renew++;
-#endif
                 if (TK_RARE(fq_n >= 64)) drain_finished(64);              // room for 64 more: fewer than 64 wait now
                 const u32 slot0 = fq_head + fq_n;                         // (scalar bookkeeping outside the exec region)
                 fq_n += (u32)__popcll(fm);
@@ -840,13 +807,9 @@ __device__ __forceinline__ void play_role(
                 fq_n += (u32)__popcll(fm);
             }
         }
-        TK_SEG(1);
         if (CAN_END && !FAST_RENEW && (ALL || autoreset)) {  // (ALL implies auto-reset, and every lane was in play: done = just finished)
             bool renew = ALL ? fin : (v && g.phase == TK_PHASE_DONE);
             if (TK_USUAL(__ballot(renew) != 0)) {
-#ifdef TK_EVENT_STAMPS
-                ev_renew++;
-#endif
                 // Loops that are not trick-aligned: a third or later game of a launch (the two preloaded lines
                 // are used up) is fetched on the spot: a memory round trip (~550 cycles) that nothing hides.  So
                 // when one lane has to, EVERY lane that has used its lines up takes its next games' lines along —
@@ -854,9 +817,6 @@ __device__ __forceinline__ void play_role(
                 if constexpr (TOP_UP_LATE) {
                     bool lacks = spec && !blocked && !ok1 && consumed >= 1 && consumed < allowed;
                     if (TK_RARE(__ballot(renew && lacks) != 0)) {
-#ifdef TK_EVENT_STAMPS
-                        ev_lazy++;
-#endif
                         bool lacks2 = spec && !blocked && !ok2 && consumed >= 1 && consumed + 1 < allowed;
                         fetch_lines(lacks, lacks2);
                         TK_WAIT_LOADS();
@@ -877,7 +837,6 @@ __device__ __forceinline__ void play_role(
                 if (renew) { cur_ep++; consumed++; seats_dirty = true; }
             }
         }
-        TK_SEG(2);
         // (ALL: a finished game has been replaced just above, so every lane is in play again)
         legal = (ALL || (v && g.phase == TK_PHASE_PLAY)) ? legal_now(g) : 0;
         if (v) {
@@ -886,7 +845,6 @@ __device__ __forceinline__ void play_role(
             TK_STREAM_STORE(&obs[row], obs_word_with<true>(g, false, legal) | ((u64)(ALL ? fin01 : ((fin || g.phase == TK_PHASE_DONE) ? 1u : 0u)) << 62));
             if (STD || done) TK_STREAM_STORE(&done[row], (uint8_t)fin01);
         }
-        TK_SEG(3);
     };
     // With auto-reset a lane that is in play stays in play (a finished game is replaced within the
     // same card), so "every lane of the wave valid and in play" decided HERE holds for the whole
@@ -900,20 +858,10 @@ __device__ __forceinline__ void play_role(
             auto tricks = [&](auto std_tag) __attribute__((always_inline)) {
                 touched = true; seats_dirty = true;          // (cards >= 4: every lane plays a whole trick)
                 for (int c = 0; c < cards; c += 4) {
-#ifdef TK_CARD_STAMPS                       // diagnostics build (tools/card_probe.py): cycles of cards 0-2 vs the trick's 4th card
-                    u64 ts_a = __builtin_amdgcn_s_memtime();
-#endif
                     play_card(std::true_type{}, std::integral_constant<int, 0>{}, std_tag, row, c); row += stride;
                     play_card(std::true_type{}, std::integral_constant<int, 1>{}, std_tag, row, c + 1); row += stride;
                     play_card(std::true_type{}, std::integral_constant<int, 2>{}, std_tag, row, c + 2); row += stride;
-#ifdef TK_CARD_STAMPS
-                    u64 ts_b = __builtin_amdgcn_s_memtime();
-#endif
                     play_card(std::true_type{}, std::integral_constant<int, 3>{}, std_tag, row, c + 3); row += stride;
-#ifdef TK_CARD_STAMPS
-                    u64 ts_c = __builtin_amdgcn_s_memtime();
-                    cs_012 += (u32)(ts_b - ts_a); cs_3 += (u32)(ts_c - ts_b);
-#endif
                 }
             };
             if (action_out && done && !trick) tricks(std::true_type{});
@@ -959,14 +907,6 @@ __device__ __forceinline__ void play_role(
         stamps[3 * w + 0] = t_real0;
         stamps[3 * w + 1] = __builtin_amdgcn_s_memrealtime();
         stamps[3 * w + 2] = ((__builtin_amdgcn_s_memtime() - t_cyc0) << 32) | (t_play & 0xFFFFFFFFULL);
-#ifdef TK_CARD_STAMPS
-        stamps[3 * w + 0] = ((u64)cs_012 << 32) | (u64)cs_3;
-        stamps[3 * w + 1] = ((u64)cs_seg[0] << 32) | (u64)cs_seg[1];
-        stamps[3 * w + 2] = (stamps[3 * w + 2] & 0xFFFFFFFFULL) | ((u64)cs_seg[2] << 32);      // (cs_seg[3] = cs_3 - the others)
-#endif
-#ifdef TK_EVENT_STAMPS                      // (replaces the entry time stamp)
-        stamps[3 * w + 0] = ((u64)ev_deal << 48) | ((u64)ev_lazy << 32) | ((u64)ev_renew << 16) | (u64)ev_early;
-#endif
     }
 }
 
@@ -990,9 +930,6 @@ TK_KERNEL(TK_BLOCK, 168) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_play_
     if (blockIdx.x >= play_groups)
         refill_role<false>(blockIdx.x - play_groups, threadIdx.x, TK_BLOCK, seed, offset, mix, play_groups, count, epoch, fan, false, aux, rlist, rcount, nullptr);
     else {
-#ifdef TK_PLAY_PRIO                          // diagnostics build: wave priority of the play role (no effect: profiles/r02_ab_lone_wave_rewrite.txt)
-        __builtin_amdgcn_s_setprio(TK_PLAY_PRIO);
-#endif
         play_role<HIST>(blockIdx.x, threadIdx.x, n, seed, offset, mix, flags, cards, stride, count, epoch, play_groups, fan,
                         action_out, reward, done, trick, obs, hist, s01, s23, aux, cnt, gkey, rlist, rcount, stamps);
     }
@@ -1221,27 +1158,13 @@ __device__ __forceinline__ void step_role(
         uint8_t *__restrict__ done, uint16_t *__restrict__ trick, u64 *__restrict__ obs, uint8_t *__restrict__ hist,              \
         ulonglong2 *__restrict__ s01, ulonglong2 *__restrict__ s23, Aux *aux, Counters *__restrict__ cnt,                         \
         u64 *__restrict__ gkey, u64 *rlist, u32 *rcount, u64 *elist
-#ifndef TK_STEP_WAVES
-#define TK_STEP_WAVES 4            // waves per SIMD the one-card kernel is compiled for (diagnostic builds: 5, 6, 8)
-#endif
-#if TK_STEP_WAVES == 4             // (the kernel's VGPR bucket and its last register: TK_KERNEL / TK_VGPR_TOP, tarok_device.h)
-#define TK_STEP_VGPRS 128
-#define TK_STEP_VTOP 127
-#elif TK_STEP_WAVES == 5
-#define TK_STEP_VGPRS 96
-#define TK_STEP_VTOP 95
-#elif TK_STEP_WAVES == 6
-#define TK_STEP_VGPRS 80
-#define TK_STEP_VTOP 79
-#else
-#define TK_STEP_VGPRS 64
-#define TK_STEP_VTOP 63
-#endif
+// The one-card kernel is compiled for four waves per SIMD: a 128-VGPR bucket, v127 its last register (TK_KERNEL /
+// TK_VGPR_TOP, tarok_device.h).
 // LAZY: the env deals the lines its one-card launches empty in bulk (TAROK_OPT_LAZY_REFILL, refill_role<true>); the other
 // instantiation carries none of that — where the batch streams, a dozen instructions per step wave are 3 % of a launch
 template <bool RANDOM, bool LAZY>
-TK_KERNEL(TK_BLOCK, TK_STEP_VGPRS) __attribute__((amdgpu_waves_per_eu(TK_STEP_WAVES))) void k_step(TK_STEP_ARGS) {
-    TK_VGPR_TOP(TK_STEP_VGPRS, TK_STEP_VTOP);
+TK_KERNEL(TK_BLOCK, 128) __attribute__((amdgpu_waves_per_eu(4))) void k_step(TK_STEP_ARGS) {
+    TK_VGPR_TOP(128, 127);
     TkCount count = launch_count<LAZY ? 0 : 1>(epoch, play_groups);
     __shared__ u32 finq[FINQ_WORDS][TK_BLOCK];
     if (LAZY) {
@@ -1851,7 +1774,6 @@ TK_KERNEL(TK_BLOCK, 256) void k_ppo_loss(int64_t n, const uint4 *__restrict__ ou
 // stores).  Layers 1-2: wave w owns features [64w, 64w+64) x all 128 games (2 x 4 tiles, 128 MFMAs,
 // the weight slab streamed from L2 four k-steps ahead); layer 3 (64 outputs = 54 card logits, value
 // in column 54): wave w owns games [32w, 32w+32).
-#if TK_BLOCK == 256                // the MLP kernels are laid out for 256-slot groups
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -2174,8 +2096,6 @@ __global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_
                            count, epoch, play_groups, fan, nullptr, nullptr, reward, done, trick, obs_out, hist, s01, s23, aux, cnt, gkey, rlist, rcount, nullptr,
                            reinterpret_cast<u32 (*)[TK_BLOCK]>(lds));
 }
-
-#endif  // TK_BLOCK == 256
 
 // ---------------------------------------------------------------------------
 // The reference agent's transition targets in its own form: what Nevronski_igralec.rezultat_stiha
@@ -2731,9 +2651,6 @@ int tarok_debug_stamps(tarok_env *e, uint64_t *stamps) {      // the step kernel
 
 int tarok_debug_refill_selftest(tarok_env *e, int kind, int per_slot, uint32_t episode0, int order, int reps, uint64_t *report_out) {
     if (!e || kind < 0 || kind > 3 || per_slot < 1 || per_slot > TK_AHEAD || order < 0 || order > 2 || reps < 1 || !report_out) return TAROK_EINVAL;
-#if TK_BLOCK != 256
-    return TAROK_EINVAL;
-#else
     HIPCHK(hipSetDevice(e->device));
     const int64_t n = e->n;
     const size_t rows = 4;
@@ -2769,7 +2686,6 @@ int tarok_debug_refill_selftest(tarok_env *e, int kind, int per_slot, uint32_t e
     (void)hipFree(buf); (void)hipFree(rep);
     if (r != hipSuccess) { g_last_hip = (int)r; return TAROK_EHIP; }
     return TAROK_OK;
-#endif
 }
 
 int tarok_observe(tarok_env *e, void *features_out, void *stream) {
@@ -2837,9 +2753,6 @@ int tarok_policy_mlp(tarok_env *e, const void *w1, const float *b1, const void *
                      const float *b3, const uint64_t *obs, uint8_t *action_out, float *logp_out, float *value_out,
                      void *features_out, uint64_t *feature_words_out, void *stream) {
     if (!e || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !obs || !action_out) return TAROK_EINVAL;
-#if TK_BLOCK != 256
-    return TAROK_EINVAL;
-#else
     HIPCHK(hipSetDevice(e->device));
     dim3 grid((unsigned)((e->n + PM_M - 1) / PM_M));
     hipLaunchKernelGGL(k_policy_mlp, grid, dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->s01, e->s23, (const u64 *)obs,
@@ -2847,7 +2760,6 @@ int tarok_policy_mlp(tarok_env *e, const void *w1, const float *b1, const void *
                        value_out, (uint4 *)features_out, (ulonglong2 *)feature_words_out, stamps_for(e, 8 * (size_t)grid.x));
     HIPCHK(hipGetLastError());
     return TAROK_OK;
-#endif
 }
 
 int tarok_policy_step(tarok_env *e, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
@@ -2855,9 +2767,6 @@ int tarok_policy_step(tarok_env *e, const void *w1, const float *b1, const void 
                       uint64_t *feature_words_out, int16_t *reward_out, uint8_t *done_out, uint16_t *trick_out,
                       uint64_t *obs_out, int flags, void *stream) {
     if (!e || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !obs || !action_out || !obs_out) return TAROK_EINVAL;
-#if TK_BLOCK != 256
-    return TAROK_EINVAL;
-#else
     HIPCHK(hipSetDevice(e->device));
     u32 groups = (u32)((e->n + TK_BLOCK - 1) / TK_BLOCK);
     u32 fan = e->refill_fan;
@@ -2869,7 +2778,6 @@ int tarok_policy_step(tarok_env *e, const void *w1, const float *b1, const void 
                        (u64 *)obs_out, e->hist, e->s01, e->s23, e->aux, e->cnt, e->gkey, e->rlist, e->rcount);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
-#endif
 }
 
 int tarok_expand_features(tarok_env *e, int64_t n_samples, const uint64_t *feature_words, const int64_t *index,
@@ -2908,7 +2816,6 @@ int tarok_targets_ref(tarok_env *e, int T, const uint64_t *obs_before, const uin
     return TAROK_OK;
 }
 
-#if TK_BLOCK == 256
 int tarok_learn_returns(tarok_env *e, int T, const uint8_t *done, const int16_t *reward, const uint64_t *obs, const float *logp,
                         const float *value, const uint8_t *action, float reward_scale, float *rec_out, float *stats_out,
                         float *scratch, void *stream) {
@@ -2959,9 +2866,7 @@ static inline void learn_chunks(tarok_env *e, u32 &c2, u32 &c1, u32 &c3) {
         e->n_cus = hipGetDeviceProperties(&pr, e->device) == hipSuccess && pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
     }
     u32 total = (u32)e->n_cus < 8 ? 8 : (u32)e->n_cus;
-    u32 s2 = 96, s1 = 108;
-    if (const char *f = getenv("TAROK_DW_SHARES")) { unsigned a = 0, b = 0; if (sscanf(f, "%u,%u", &a, &b) == 2 && a >= 8 && b >= 8 && a + b <= 248) { s2 = a; s1 = b; } }   // diagnostics (A/B runs)
-    c2 = total * s2 / 256; c1 = total * s1 / 256; c3 = total - c2 - c1;
+    c2 = total * 96 / 256; c1 = total * 108 / 256; c3 = total - c2 - c1;
 }
 
 int64_t tarok_learn_workspace_bytes(tarok_env *e) {
@@ -3004,18 +2909,6 @@ int tarok_learn_adam(tarok_env *e, float *param, const float *grad, float *m, fl
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }
-#else
-int tarok_learn_returns(tarok_env *, int, const uint8_t *, const int16_t *, const uint64_t *, const float *, const float *, const uint8_t *,
-                        float, float *, float *, float *, void *) { return TAROK_EINVAL; }
-int tarok_learn_chain(tarok_env *, int64_t, const uint64_t *, const int64_t *, const float *, const float *, float, float, float,
-                      const void *, const float *, const void *, const float *, const void *, const float *, const void *, const void *,
-                      uint64_t *, void *, void *, void *, void *, void *, float *, float *, float *, void *) { return TAROK_EINVAL; }
-int64_t tarok_learn_workspace_bytes(tarok_env *) { return 0; }
-int tarok_learn_dw(tarok_env *, int64_t, const uint64_t *, const void *, const void *, const void *, const void *,
-                   const void *, const float *, void *, float *, void *) { return TAROK_EINVAL; }
-int tarok_learn_adam(tarok_env *, float *, const float *, float *, float *, int32_t *, float, float, float, float, float, void *, void *,
-                     void *, void *, void *, float *, int, void *) { return TAROK_EINVAL; }
-#endif
 
 int tarok_get_state(tarok_env *e, uint64_t *lanes_out, void *stream) {
     if (!e || !lanes_out) return TAROK_EINVAL;

@@ -20,8 +20,6 @@
 //   k_learn_adam   gradient-norm clip + Adam on flat parameter / state vectors, and the bf16 fragment-order
 //                  copies of the weights (and of their transposes, for the backward chain) that the next
 //                  minibatch's kernels and the rollout read.  One workgroup.
-#if TK_BLOCK == 256
-
 #define LN_M 96                    // samples per tile of k_learn_chain: three 32-sample MFMA tiles — 75 KB of LDS, so that TWO
                                    // workgroups share a CU and one's epilogues, loss and gather run under the other's MFMAs
                                    // (128 samples: 100 KB, one workgroup per CU, 17 % of the MFMA rate)
@@ -160,9 +158,7 @@ typedef __attribute__((ext_vector_type(4))) unsigned int ln_u32x4;
 // Cache policy of the stores k_learn_chain leaves for k_learn_dw (buffer stores: the policy bits are an immediate of the
 // builtin — 0 plain, 2 non-temporal, 16 `sc1` = write-through).  Same box, us per minibatch, k_learn_chain | k_learn_dw:
 // non-temporal 276 | 182, plain 278 | 202, write-through 281 | 200 (profiles/r04_learner_steps.txt).
-#ifndef LN_STORE_AUX
 #define LN_STORE_AUX 2
-#endif
 // rows [row0, row0 + valid) x `row_bytes` of a row-major array as a raw buffer: a store past `valid` rows is dropped by the
 // bounds check of the buffer instruction (no row test in the code)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t chain_rows(void *first_row, int64_t row0, int64_t nrows, u32 row_bytes) {
@@ -245,14 +241,7 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                                                                        // vector-memory load (behind the tile stores in flight: below)
     const int64_t base = (int64_t)blockIdx.x * LN_M;
     const u32 tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-#define LN_STAMP_AT(k) do { if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#ifdef LN_FINE_STAMPS               // diagnostics build (tools/chain_stamps.py fine): layers 1-2 split into GEMM | epilogue | tile store
-#define LN_STAMP(k) do { if ((k) < 2) LN_STAMP_AT(k); } while (0)
-#define LN_FINE(k) LN_STAMP_AT(k)
-#else
-#define LN_STAMP(k) LN_STAMP_AT(k)
-#define LN_FINE(k) do { } while (0)
-#endif
+#define LN_STAMP(k) do { if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
     LN_STAMP(0);
     for (u32 k = threadIdx.x; k < 580; k += TK_BLOCK)
         bias_s[k] = k < 256 ? a.b1[k] : k < 512 ? a.b2[k - 256] : k < 576 ? a.b3[k - 512] : reinterpret_cast<const float *>(a.stats)[k - 576];
@@ -293,7 +282,6 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     // nothing behind them is a vector-memory load until the next layer's weights (the biases come from LDS).
     auto hidden = [&](const __bf16 *w, const float *bias, bool keep_mask, auto tail) __attribute__((always_inline)) {
         chain_gemm<16>(acc, X, PM_LD, w, wave, tail);
-        if (keep_mask) LN_FINE(2); else LN_FINE(5);
         __syncthreads();                                   // every wave has read its last X fragment
 #pragma unroll
         for (int ft = 0; ft < 2; ft++)
@@ -315,13 +303,9 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         __syncthreads();
     };
     hidden(a.w1, bias_s, true, ChainNoTail());
-    LN_FINE(3);
     LN_STAMP(2);
-    LN_FINE(4);
     hidden(a.w2, bias_s + 256, false, [&]() __attribute__((always_inline)) { chain_store_tile(X, a.H1, base, a.B, tid); });
-    LN_FINE(6);
     LN_STAMP(3);
-    LN_FINE(7);
     // ---- layer 3 (64 outputs: 54 card logits, value in column 54) for samples [32 wave, 32 wave + 32), and the loss
     // in its accumulators: lane (r, h) holds outputs 32 ft + 8 q + 4 h + j of sample 32 wave + r, its partner lane ^ 32
     // the other half.  (Waves 0 .. LN_GT - 1: the fourth compute wave has no samples in this phase.)
@@ -509,8 +493,6 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     }
     LN_STAMP(6);
 #undef LN_STAMP
-#undef LN_STAMP_AT
-#undef LN_FINE
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -524,12 +506,8 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 // WORDS: the H operand is the network input, expanded on the fly from the minibatch's feature words (layer 1; in
 // minibatch order, as k_learn_chain wrote them: no index, no dependent load).
 // Bias gradient: thread t sums column t of the staged dH tile.
-#ifndef DW_KT
 #define DW_KT 32                    // samples per staged tile (k-steps of 16)
-#endif
-#ifndef DW_ST
 #define DW_ST 4                     // register stages: tiles in flight behind the one being computed
-#endif
 template <class F, int... I> __device__ __forceinline__ void static_for_impl(F &f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
 template <int N, class F> __device__ __forceinline__ void static_for(F &&f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 #define DW_LD 288                   // LDS row stride, bf16 elements
@@ -849,5 +827,3 @@ TK_KERNEL(LN_ADAM_BLOCK, 64) void k_learn_adam(AdamArgs a) {
         if (a.w3t) frag_store(a.w3t, 4, e & 255, e >> 8, w);
     }
 }
-
-#endif  // TK_BLOCK == 256

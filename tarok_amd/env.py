@@ -71,15 +71,7 @@ class TarokVecEnv:
         _native.check(L.tarok_create(C.byref(h), self.device_index, self.n, self.game_offset, self.seed, self.mix,
                                      K.HISTORY if history else 0))
         self._h = h
-        import os
-        if refill_fan is None and os.environ.get("TAROK_REFILL_FAN"):      # diagnostics (tools/: A/B runs of whole scripts)
-            refill_fan = int(os.environ["TAROK_REFILL_FAN"])
-        if refill_fan is not None:
-            _native.check(L.tarok_set_option(h, K.OPT_REFILL_FAN, int(refill_fan)))
-        if lazy_refill is None and os.environ.get("TAROK_LAZY_REFILL"):
-            lazy_refill = int(os.environ["TAROK_LAZY_REFILL"])
-        if lazy_refill is not None:
-            _native.check(L.tarok_set_option(h, K.OPT_LAZY_REFILL, int(lazy_refill)))
+        self.set_option(refill_fan, lazy_refill)
         with torch.cuda.device(self.device):
             self.obs_words = torch.zeros(self.n, dtype=torch.int64, device=self.device)
             self.reward = torch.zeros((self.n, 4), dtype=torch.int16, device=self.device)

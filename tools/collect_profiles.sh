@@ -15,7 +15,7 @@ cp $S/play_only_counters.json $P/${TAG}_play_only_counters.json
 cp $S/valu_issue_raw.json $P/${TAG}_valu_issue_raw.json
 python3 tools/valu_issue_summary.py $S/valu_issue_raw.json $P/${TAG}_valu_issue.json > /dev/null
 python3 tools/n_sweep_summary.py $S $P/${TAG}_n_sweep.json
-for f in first_launches.txt wave_stamps_65536.txt card_probe_65536.txt policy_mlp_times.txt observe_ref_times.txt; do grep -v amdgpu.ids $S/$f > $P/${TAG}_$f; done
+for f in first_launches.txt wave_stamps_65536.txt policy_mlp_times.txt observe_ref_times.txt; do grep -v amdgpu.ids $S/$f > $P/${TAG}_$f; done
 grep -v amdgpu.ids $X/step_api_n_sweep.txt > $P/${TAG}_step_api_n_sweep.txt
 cp $X/step_durations_final.txt $P/${TAG}_step_durations.txt
 cp $X/step_sq.txt $P/${TAG}_step_sq.txt

@@ -35,7 +35,6 @@ bash tools/play_only_counters.sh 65536 $TAG/play_only > /dev/null 2>&1 && cp gpu
 timeout -k 10 600 ./tools/valu_issue 1500 > $OUT/valu_issue_raw.json 2> $OUT/valu_issue.err
 python3 tools/first_launches.py 65536 $CARDS > $OUT/first_launches.txt 2>&1
 python3 tools/krog_stamps.py 65536 $CARDS > $OUT/wave_stamps_65536.txt 2>&1
-python3 tools/card_probe.py 65536 $CARDS > $OUT/card_probe_65536.txt 2>&1
 python3 tools/mlp_time.py 65536 > $OUT/policy_mlp_times.txt 2>&1
 python3 tools/observe_ref_time.py > $OUT/observe_ref_times.txt 2>&1
 # keep only the summaries of the rocprof directories (the raw traces are large)

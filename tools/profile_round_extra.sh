@@ -13,7 +13,7 @@ for m in random two; do
   python3 tools/step_durations.py $OUT/dur_$m 4194304 >> $OUT/step_durations_final.txt
   rm -rf $OUT/dur_$m
 done
-# 65,536 games: the one-card step deals in bulk every sixteenth launch there (period 16: launch number mod 16, 0 = the bulk launch)
+# 65,536 games: the one-card step deals in bulk every thirty-second launch there (period 32: launch number mod 32, 0 = the bulk launch)
 rocprofv3 --kernel-trace --output-format csv -d $OUT/dur_small -- python3 tools/step_ledger.py 65536 two d 0 1 224 > $OUT/dur_small.log 2>&1
 echo "65,536 games, by launch number mod 32:" >> $OUT/step_durations_final.txt
 python3 tools/step_durations.py $OUT/dur_small 65536 32 >> $OUT/step_durations_final.txt

@@ -48,7 +48,7 @@ def main():
         tot = sum(r[k][0] for k in r) - extra / 4.0
         return tot, r["stepR"][0] + r["stepW"][0] - extra / 4.0
     print("step-API traffic ledger, %d games, MIX_ALL, auto-reset; bytes per env step (mean | cards 0-2 | 4th card)" % n)
-    print("R = FETCH_SIZE x 2, W = WRITE_SIZE; step = the step kernel (k_step<..>, r02: k_play<false,true> / k_play_wide<true,false>)")
+    print("R = FETCH_SIZE x 2, W = WRITE_SIZE; step = the step kernel (k_step<..>)")
     for v in variants:
         r = table[v]
         cells = []
@@ -91,9 +91,6 @@ def main():
         print("  4th card on top of cards 0-2:         R %.2f  W %.2f per 4th-card launch (seat pair 16 W; Counters, next-game line, key, list entry of the games that end)"
               % (r["stepR"][2] - r["stepR"][1], r["stepW"][2] - r["stepW"][1]))
         print("  cards 0-2 (play pair 16 R + 16 W, seat pair 16 R, card 1 R, observation 8 W = 33 R + 24 W): R %.2f  W %.2f" % (r["stepR"][1], r["stepW"][1]))
-    if "two_r02" in table:
-        print("  round-2 kernel (k_play<false,true>, 64 B/lane of scratch) minus this one:  R %.2f  W %.2f   (cards 0-2: R %.2f  W %.2f)"
-              % (d("two_r02", "two_base", "stepR"), d("two_r02", "two_base", "stepW"), d("two_r02", "two_base", "stepR", 1), d("two_r02", "two_base", "stepW", 1)))
 
 if __name__ == "__main__":
     main()

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Diagnostic (GPU box): three self-play iterations (rollout + update) — run under rocprofv3 --kernel-trace --stats for
+"""Diagnostic (GPU box): four self-play iterations (rollout + update) — run under rocprofv3 --kernel-trace --stats for
 the per-kernel times of the update (profiles/r03_update_kernel_stats.csv), or plainly for the wall times."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
