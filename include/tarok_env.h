@@ -365,7 +365,7 @@ int tarok_targets_ref(tarok_env *env, int T, const uint64_t *obs_before, const u
 #define TAROK_MLP_PARAMS 148032
 #define TAROK_LEARN_PAD 256 /* padding rows of the activation arrays of tarok_learn_chain / tarok_learn_dw */
 #define TAROK_LEARN_MAX_BATCH 4194048 /* samples per minibatch of tarok_learn_dw (its arrays are addressed through 32-bit
-                                       * byte offsets: (B + TAROK_LEARN_PAD) * 512 < 2^31); larger: TAROK_EINVAL */
+                                       * byte offsets: (B + 255) * 512 < 2^31); larger: TAROK_EINVAL */
 
 /* Returns of a rollout of T lock-steps (rows [T,N] as written by tarok_policy_step): every card is credited with
  * its seat's final score of the game it belongs to, times reward_scale.

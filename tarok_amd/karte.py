@@ -49,6 +49,7 @@ GAMES_AHEAD = 14          # TAROK_GAMES_AHEAD: games every slot keeps dealt ahea
 # the flat parameter vector of the 256-256-256-64 policy (include/tarok_env.h TAROK_MLP_*)
 MLP_W1, MLP_B1, MLP_W2, MLP_B2, MLP_W3, MLP_B3, MLP_PARAMS = 0, 65536, 65792, 131328, 131584, 147968, 148032
 LEARN_PAD = 256           # TAROK_LEARN_PAD: padding rows of the fused learner's activation arrays
+LEARN_MAX_BATCH = 4194048  # TAROK_LEARN_MAX_BATCH: samples per tarok_learn_dw launch (SelfPlay.update_fused splits larger minibatches)
 
 # the reference-layout observation record (include/tarok_env.h TAROK_REF_*)
 REF_ROWS = 56

@@ -128,6 +128,26 @@ def assign_returns(done, reward, seat):
     return ret, known
 
 
+def dw_ranges(B, cap=K.LEARN_MAX_BATCH):
+    """The row ranges [(r0, r1), ...] over which update_fused computes the weight gradients of a minibatch of B
+    samples: tarok_learn_dw takes at most `cap` samples per launch (32-bit buffer offsets), so a larger minibatch is
+    split into ceil(B / cap) consecutive ranges of nearly equal size.  Exact: the gradient is linear in the samples
+    and every range is scaled by the whole minibatch's 1 / sum w (terms[3])."""
+    k = max(1, -(-B // cap))
+    per = -(-B // k)
+    return [(r0, min(r0 + per, B)) for r0 in range(0, B, per)]
+
+
+def learn_dw_ranges(env, B, acts, terms, work, grad, gpart, cap=K.LEARN_MAX_BATCH):
+    """env.learn_dw of a minibatch of B samples, one launch per row range of dw_ranges(B, cap): acts = (Xw, H1, H2, dOut,
+    dH2, dH1) of the minibatch, passed as row-offset views; the first range writes `grad`, every later one `gpart`
+    [MLP_PARAMS] f32 (unused when B <= cap), which is then added in, in range order."""
+    for k, (r0, r1) in enumerate(dw_ranges(B, cap)):
+        env.learn_dw(r1 - r0, *[a[r0:] if r0 else a for a in acts], terms, work, grad if k == 0 else gpart)
+        if k:
+            grad += gpart
+
+
 def allreduce_flat(flat):
     """Average ONE flat gradient vector over all ranks in place (the fused learner's gradients already are one
     buffer: no gather, no scatter).  No-op without an initialised process group / with one rank."""
@@ -382,6 +402,7 @@ class SelfPlay:
             f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
             act = lambda k: torch.zeros((B + K.LEARN_PAD, k), dtype=torch.bfloat16, device=dev)
             lb = dict(M=M, B=B, rec=f32(M, 4), stats=f32(4), scratch=f32(max((self.env.n + 255) // 256, (B + 95) // 96), 4),
+                      gpart=f32(K.MLP_PARAMS) if B > K.LEARN_MAX_BATCH else None,
                       H1=act(256), H2=act(256), dH2=act(256), dH1=act(256), dOut=act(64), terms=f32(4),
                       Xw=torch.zeros((B + K.LEARN_PAD, 4), dtype=torch.int64, device=dev),
                       running=torch.zeros(4, dtype=torch.float32, device=dev),
@@ -407,8 +428,9 @@ class SelfPlay:
     def update_fused(self, buf, epochs=2, minibatches=8):
         """The update as fused launches (include/tarok_env.h tarok_learn_*): per rollout one returns kernel; per
         minibatch the forward + loss + backward chain (activations in LDS, bf16 MFMA), the three weight gradients
-        as one split-K launch, ONE flat gradient all-reduce, and clip + Adam + weight-copy refresh in one launch.
-        No host synchronisation until the statistics are read at the end."""
+        as one split-K launch (one per row range of dw_ranges past TAROK_LEARN_MAX_BATCH samples), ONE flat gradient
+        all-reduce, and clip + Adam + weight-copy refresh in one launch.  No host synchronisation until the statistics
+        are read at the end."""
         env = self.env
         T, n = buf["act"].shape
         M = T * n
@@ -426,7 +448,8 @@ class SelfPlay:
                 b = idx.numel()
                 env.learn_chain(b, words, idx, lb["rec"], lb["stats"], self.clip, self.vf_coef, self.ent_coef, self._wf, bias,
                                 lb["Xw"], lb["H1"], lb["H2"], lb["dOut"], lb["dH2"], lb["dH1"], lb["scratch"], lb["terms"], lb["running"])
-                env.learn_dw(b, lb["Xw"], lb["H1"], lb["H2"], lb["dOut"], lb["dH2"], lb["dH1"], lb["terms"], lb["work"], self.gflat)
+                learn_dw_ranges(env, b, [lb[a] for a in ("Xw", "H1", "H2", "dOut", "dH2", "dH1")], lb["terms"], lb["work"],
+                                self.gflat, lb["gpart"])
                 nbytes = allreduce_flat(self.gflat)
                 env.learn_adam(self.flat, self.gflat, self.adam_m, self.adam_v, self.adam_step, self._wf, lr=self.lr,
                                max_norm=self.max_grad_norm)

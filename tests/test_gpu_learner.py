@@ -1,6 +1,6 @@
 """GPU tests of the fused learner (tarok_learn_*: returns, forward + loss + backward chain on MFMA, split-K
-weight gradients through transposed LDS reads, clip + Adam on flat vectors) against float32 torch — autograd
-for every gradient.  Build-owned code (the reference has no policy-gradient learner): these are numerics
+weight gradients through transposed LDS reads, clip + Adam on flat vectors) against torch — float64 autograd
+for every gradient of the chain.  Build-owned code (the reference has no policy-gradient learner): these are numerics
 tests of kernels, with bf16 tolerances written where they apply.
 
 Run on the GPU box:  python -m pytest tests -m gpu -x -q
@@ -108,23 +108,29 @@ def _rollout_words(T, env, net_w, steps):
     return torch.cat(fws), torch.cat(ows)
 
 
-@pytest.mark.parametrize("B", [5000, 128, 333])
-def test_learn_chain_and_dw_vs_torch_autograd(T, B):
-    """tarok_learn_chain + tarok_learn_dw on a ragged minibatch (gathered through an index) vs float32 torch
-    autograd of the same network on the same bf16 weights, with the kernel's bf16 roundings of H1 / H2 written
-    into the reference (a dtype cast is transparent to autograd): activations, loss terms, d loss / d output,
-    the hidden gradients and every weight and bias gradient."""
+SENTINEL_BF16 = 0x7FC1                        # a NaN payload no kernel writes: padding rows a store must not touch
+SENTINEL_WORD = 0x5A5A5A5A5A5A5A5A
+
+
+def _chain_vs_autograd(T, B, n=2048, steps=3, indexed=True, known_p=0.8, wscale=2.0):
+    """tarok_learn_chain + tarok_learn_dw on a minibatch of B samples of a rollout of n games x `steps` observations vs
+    float64 torch autograd of the same network on the same bf16 weights, with the kernel's bf16 roundings of H1 / H2
+    written into the reference (a dtype cast is transparent to autograd): activations, loss terms, d loss / d output, the
+    hidden gradients and every weight and bias gradient.  indexed: the samples are gathered through a random index
+    (else index NULL: sample j = row j); known_p: share of samples whose game ended (weight 1); wscale: the factor on
+    torch's initial weights (10: near one-hot softmax, ratios clipped on both sides).  The padding rows of every array
+    the chain writes hold a sentinel that must survive the launch (its tile stores are bounds-checked per row)."""
     import torch
     import torch.nn.functional as F
     from tarok_amd import selfplay as SP
     K = T.karte
-    n = 2048
+    f64 = torch.float64
     env = T.TarokVecEnv(n, seed=5, mix=K.MIX_ALL)
     torch.manual_seed(1)
     net = SP.PolicyNet(256).cuda()
     with torch.no_grad():
         for p in net.parameters():
-            p.mul_(2.0)
+            p.mul_(wscale)
     ps = [net.fc1.weight, net.fc1.bias, net.fc2.weight, net.fc2.bias, net.head.weight, net.head.bias]
     flat = torch.cat([p.detach().reshape(-1) for p in ps]).contiguous()
     bf = lambda k: torch.empty(k, dtype=torch.bfloat16, device="cuda")
@@ -132,42 +138,43 @@ def test_learn_chain_and_dw_vs_torch_autograd(T, B):
     env.learn_adam(flat, None, None, None, None, wf, apply=False)
     bias = (flat[K.MLP_B1:K.MLP_B1 + 256], flat[K.MLP_B2:K.MLP_B2 + 256], flat[K.MLP_B3:K.MLP_B3 + 64])
     roll_w = [wf["w1"].view(256, 256), bias[0], wf["w2"].view(256, 256), bias[1], wf["w3"].view(64, 256), bias[2]]
-    words, obs_words = _rollout_words(T, env, roll_w, 3)
+    words, obs_words = _rollout_words(T, env, roll_w, steps)
     M = words.shape[0]
+    assert M >= B
     g = torch.Generator(device="cuda"); g.manual_seed(7)
-    idx = torch.randperm(M, device="cuda", generator=g)[:B].contiguous()
+    idx = torch.randperm(M, device="cuda", generator=g)[:B].contiguous() if indexed else torch.arange(B, device="cuda")
     legal_all = SP.legal_matrix(obs_words & K.OBS_MASK)
     assert torch.equal(words[:, 1] & K.OBS_MASK, obs_words & K.OBS_MASK)             # feature word 1 = the legal cards
     act_all = torch.multinomial(legal_all.float(), 1, generator=g).squeeze(1)
-    Wq = [p.detach().to(torch.bfloat16).float().requires_grad_(True) if p.dim() == 2 else p.detach().clone().requires_grad_(True) for p in ps]
+    Wq = [p.detach().to(torch.bfloat16).to(f64).requires_grad_(True) if p.dim() == 2 else p.detach().to(f64).requires_grad_(True) for p in ps]
 
     def forward(x):
         z1 = x @ Wq[0].T + Wq[1]
         z1.retain_grad()                                       # (the kernel's dH is the gradient at the PRE-activation)
-        h1 = torch.relu(z1).to(torch.bfloat16).float()
+        h1 = torch.relu(z1).to(torch.bfloat16).to(f64)
         z2 = h1 @ Wq[2].T + Wq[3]
         z2.retain_grad()
-        h2 = torch.relu(z2).to(torch.bfloat16).float()
+        h2 = torch.relu(z2).to(torch.bfloat16).to(f64)
         out = h2 @ Wq[4].T + Wq[5]
         out.retain_grad()
         return h1, h2, out, z1, z2
-    x = env.expand_feature_words(words[idx], torch.float32)
+    x = env.expand_feature_words(words[idx], f64)
     h1, h2, out, z1, z2 = forward(x)
     legal = legal_all[idx]
     with torch.no_grad():
         lp_now = F.log_softmax(out[:, :54].masked_fill(~legal, float("-inf")), -1).gather(1, act_all[idx][:, None]).squeeze(1)
     rec = torch.zeros((M, 4), device="cuda")
-    rec[idx, 0] = lp_now + 0.4 * torch.randn(B, device="cuda", generator=g)       # ratios on both sides of the clip range
+    rec[idx, 0] = (lp_now + 0.4 * torch.randn(B, device="cuda", generator=g, dtype=f64)).float()   # ratios on both sides of the clip range
     rec[:, 1] = torch.randn(M, device="cuda", generator=g)
     rec[:, 2] = 0.5 * torch.randn(M, device="cuda", generator=g)
-    known = torch.rand(M, device="cuda", generator=g) < 0.8
+    known = torch.rand(M, device="cuda", generator=g) < known_p
     rec[:, 3] = (act_all.to(torch.int32) | (known.to(torch.int32) << 8)).view(torch.float32)
     stats = torch.tensor([0.1, 0.9, 0.8, 0.0], device="cuda")
     clip, vf, ent_c = 0.2, 0.5, 0.01
     # ---- reference loss
-    r = rec[idx]
-    adv = (r[:, 1] - r[:, 2] - stats[0]) * stats[1]
-    w = known[idx].float()
+    r = rec[idx].to(f64)
+    adv = (r[:, 1] - r[:, 2] - stats[0].to(f64)) * stats[1].to(f64)
+    w = known[idx].to(f64)
     wsum = w.sum().clamp(min=1)
     lg = out[:, :54].masked_fill(~legal, float("-inf"))
     logp_all = F.log_softmax(lg, dim=-1)
@@ -178,44 +185,89 @@ def test_learn_chain_and_dw_vs_torch_autograd(T, B):
     p = logp_all.exp()
     H = (-(p * torch.where(legal, logp_all, torch.zeros_like(logp_all))).sum(-1) * w).sum() / wsum
     (pi + vf * vl - ent_c * H).backward()
-    # ---- kernels
+    del x, lg, logp_all, p, ratio
+    # ---- kernels: the padding rows of every output array hold a sentinel before the chain runs
     act_t = lambda k: torch.zeros((B + K.LEARN_PAD, k), dtype=torch.bfloat16, device="cuda")
     H1, H2, dH2, dH1, dOut = act_t(256), act_t(256), act_t(256), act_t(256), act_t(64)
     scratch = torch.empty(((B + 95) // 96, 4), device="cuda")
     terms = torch.empty(4, device="cuda"); running = torch.zeros(4, device="cuda")
     Xw = torch.zeros((B + K.LEARN_PAD, 4), dtype=torch.int64, device="cuda")
-    env.learn_chain(B, words, idx, rec, stats, clip, vf, ent_c, wf, bias, Xw, H1, H2, dOut, dH2, dH1, scratch, terms, running)
+    Xw[B:] = SENTINEL_WORD
+    for t_ in (H1, H2, dH2, dH1, dOut):
+        t_[B:].view(torch.int16).fill_(SENTINEL_BF16)
+    env.learn_chain(B, words, idx if indexed else None, rec, stats, clip, vf, ent_c, wf, bias, Xw, H1, H2, dOut, dH2, dH1, scratch,
+                    terms, running)
+    assert (Xw[B:] == SENTINEL_WORD).all().item(), "tarok_learn_chain wrote a padding row of Xw"
+    for t_, name in ((H1, "H1"), (H2, "H2"), (dH2, "dH2"), (dH1, "dH1"), (dOut, "dOut")):
+        assert (t_[B:].view(torch.int16) == SENTINEL_BF16).all().item(), "tarok_learn_chain wrote a padding row of " + name
     assert torch.equal(Xw[:B], words[idx])                       # the feature words in minibatch order
     # activations: equal to the reference up to a bf16 ulp where the f32 sums round differently
     for got, want, name in ((H1, h1, "H1"), (H2, h2, "H2")):
-        d = (got[:B].float() - want.detach()).abs()
+        d = (got[:B].to(f64) - want.detach()).abs()
         assert d.max().item() <= 0.02 * (1 + want.abs().max().item()), name
         assert (d > 0.004 * (1 + want.detach().abs())).float().mean().item() < 0.01, name
+        del d
     ref_terms = torch.stack([pi, vl, H]).detach()
-    assert torch.allclose(terms[:3], ref_terms, rtol=5e-3, atol=5e-4), (terms, ref_terms)
+    assert torch.allclose(terms[:3].to(f64), ref_terms, rtol=5e-3, atol=5e-4), (terms, ref_terms)
     assert abs(terms[3].item() - 1.0 / wsum.item()) < 1e-9 and running[3].item() == 1.0
     # gradients w.r.t. the outputs and the hidden activations (kernel: unscaled, i.e. times the weight sum)
     for got, want, name, tol in ((dOut, out.grad, "dOut", 0.01), (dH2, z2.grad, "dH2", 0.02), (dH1, z1.grad, "dH1", 0.03)):
         want = want * wsum
-        err = (got[:B].float() - want).abs()
+        err = (got[:B].to(f64) - want).abs()
         scale = want.abs().max().item()
         assert err.max().item() < tol * scale + 1e-9, (name, err.max().item(), scale)
+        del err, want
     assert (dOut[:B, 55:] == 0).all().item() and (dOut[:B, :54][~legal] == 0).all().item()
-    Xw[B:] = -1
-    for t_ in (H1, H2, dH2, dH1, dOut):
-        t_[B:].uniform_(-3, 3)                                # (the padding rows may hold anything: tarok_learn_dw ignores them)
-    # weight and bias gradients
+    # weight and bias gradients (the padding rows still hold the sentinel: tarok_learn_dw must not read them)
     work = torch.empty(env.learn_workspace_bytes(), dtype=torch.uint8, device="cuda")
     grad = torch.zeros(K.MLP_PARAMS, device="cuda")
     env.learn_dw(B, Xw, H1, H2, dOut, dH2, dH1, terms, work, grad)
     off = 0
     for q, name in zip(Wq, ("W1", "b1", "W2", "b2", "W3", "b3")):
-        gk = grad[off:off + q.numel()].view_as(q)
+        gk = grad[off:off + q.numel()].view_as(q).to(f64)
         off += q.numel()
         rel = (gk - q.grad).norm().item() / (q.grad.norm().item() + 1e-12)
         assert rel < 0.02, (name, rel)
         assert (gk - q.grad).abs().max().item() < 0.03 * q.grad.abs().max().item() + 1e-9, name
+    out_ = dict(terms=terms.clone(), grad=grad.clone(), dOut=dOut[:B].clone(), dH2=dH2[:B].clone(), dH1=dH1[:B].clone())
     env.close()
+    del H1, H2, dH2, dH1, dOut, Xw, work, h1, h2, out, z1, z2, Wq
+    torch.cuda.empty_cache()
+    return out_
+
+
+@pytest.mark.parametrize("B", [5000, 128, 333])
+def test_learn_chain_and_dw_vs_torch_autograd(T, B):
+    """tarok_learn_chain + tarok_learn_dw on a ragged minibatch (gathered through an index) vs float64 torch autograd
+    (_chain_vs_autograd)."""
+    _chain_vs_autograd(T, B)
+
+
+def test_learn_chain_and_dw_at_the_bench_minibatch(T):
+    """The same at the benchmark's minibatch, 393,216 samples (48 x 65,536 / 8) drawn from a rollout of 65,536 games:
+    k_learn_chain runs 4,096 tiles, every chunk of k_learn_dw walks 90-237 tiles through its register ring."""
+    _chain_vs_autograd(T, 393216, n=65536, steps=8)
+
+
+def test_learn_chain_without_an_index(T):
+    """index NULL: sample j is row j of the feature words and records (a ragged last tile of 5000 = 52 x 96 + 8)."""
+    _chain_vs_autograd(T, 5000, indexed=False)
+
+
+def test_learn_chain_with_no_known_sample(T):
+    """A minibatch in which no game ended: every weight is 0, so the loss terms are {0, 0, 0, 1 / max(0, 1)}, d loss / d
+    output and the hidden gradients are exactly zero, and so is every weight and bias gradient."""
+    r = _chain_vs_autograd(T, 5000, known_p=0.0)
+    assert r["terms"].tolist() == [0.0, 0.0, 0.0, 1.0]
+    for k in ("dOut", "dH2", "dH1"):
+        assert (r[k] == 0).all().item(), k
+    assert (r["grad"] == 0).all().item()
+
+
+def test_learn_chain_with_saturated_logits(T):
+    """Weights five times the usual scale: the softmax is nearly one-hot on most samples and the ratios clip on both
+    sides (the chain's exp / log of the loss phase at their extremes) — against float64 autograd as above."""
+    _chain_vs_autograd(T, 5000, wscale=10.0)
 
 
 def test_selfplay_fused_learner_matches_the_torch_update(T):

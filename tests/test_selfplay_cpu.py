@@ -167,3 +167,30 @@ def test_split_k_linear_gives_the_plain_gradients():
     assert torch.equal(o1, o0)
     for a, b in zip(g1, g0):
         assert torch.allclose(a, b, rtol=1e-4, atol=1e-7)
+
+
+def test_learn_max_batch_mirrors_the_header():
+    """karte.LEARN_MAX_BATCH is the TAROK_LEARN_MAX_BATCH the library refuses past, and it keeps the largest byte offset
+    k_learn_dw forms, (B + 255) * 512, below 2^31."""
+    import re
+    from tarok_amd import karte
+    hdr = open(os.path.join(ROOT, "include", "tarok_env.h")).read()
+    assert int(re.search(r"#define TAROK_LEARN_MAX_BATCH (\d+)", hdr).group(1)) == karte.LEARN_MAX_BATCH
+    assert int(re.search(r"#define TAROK_LEARN_PAD (\d+)", hdr).group(1)) == karte.LEARN_PAD
+    assert (karte.LEARN_MAX_BATCH + 255) * 512 < 2 ** 31 <= (karte.LEARN_MAX_BATCH + 1 + 255) * 512
+
+
+def test_dw_ranges_cover_the_minibatch():
+    """update_fused's weight-gradient ranges: [0, B) in order, without gaps or overlaps, each at most the limit, as few
+    as the limit allows; one range (the plain launch) up to it.  B of 2^20 and 2^22 games at T = 48 and 8
+    minibatches (past the limit), and sizes up to it."""
+    from tarok_amd import karte
+    cap = karte.LEARN_MAX_BATCH
+    for B, cap_ in [(-(-48 * (1 << 20) // 8), cap), (-(-48 * (1 << 22) // 8), cap), (cap + 1, cap), (2 * cap, cap), (8 << 20, cap),
+                    (5000, 1000), (5001, 1000), (1, cap), (393216, cap), (cap, cap)]:
+        r = SP.dw_ranges(B, cap_)
+        assert r[0][0] == 0 and r[-1][1] == B and all(a[1] == b[0] for a, b in zip(r, r[1:])), (B, r)
+        assert all(0 < r1 - r0 <= cap_ for r0, r1 in r), (B, r)
+        assert len(r) == -(-B // cap_)
+    assert SP.dw_ranges(393216) == [(0, 393216)] and SP.dw_ranges(cap) == [(0, cap)]
+    assert len(SP.dw_ranges(48 * (1 << 20) // 8)) == 2 and len(SP.dw_ranges(48 * (1 << 22) // 8)) == 7
