@@ -312,6 +312,20 @@ int tarok_policy_step(tarok_env *env, const void *w1, const float *b1, const voi
                       float *logp_out, float *value_out, uint64_t *feature_words_out, int16_t *reward_out,
                       uint8_t *done_out, uint16_t *trick_out, uint64_t *obs_out, int flags, void *stream);
 
+/* tarok_policy_step with the network on some seats and the Bot (tarok_step_random's card) on the others: the launch
+ * of a mixed table, e.g. for playing the same deals with the network on one seat at a time (tarok_amd/evaluate.py).
+ *   seats           4-bit set used for every game when seats_per_game is NULL (bit s: seat s plays the network)
+ *   seats_per_game  [N] u8 (device) or NULL: the set of each game (bits 4..7 are ignored)
+ * The other arguments are tarok_policy_step's.  Rows whose mover is a Bot seat: action_out = the Bot's card,
+ * logp_out = 0; value_out and feature_words_out are written for every game.  seats = 15 gives exactly
+ * tarok_policy_step; seats = 0 gives the cards, state and outputs of tarok_step_random.  TAROK_EINVAL (before any
+ * HIP call) for a NULL env, seats outside 0..15, a missing required array or obs == obs_out. */
+int tarok_policy_step_seats(tarok_env *env, int seats, const uint8_t *seats_per_game, const void *w1, const float *b1,
+                            const void *w2, const float *b2, const void *w3, const float *b3, const uint64_t *obs,
+                            uint8_t *action_out, float *logp_out, float *value_out, uint64_t *feature_words_out,
+                            int16_t *reward_out, uint8_t *done_out, uint16_t *trick_out, uint64_t *obs_out, int flags,
+                            void *stream);
+
 /* The learner's network input for a minibatch: features_out[j] [256] bf16 (0.0 / 1.0) = the bits
  * of feature_words[index[j]] (feature_words [M,4] u64 as written by feature_words_out; index
  * [n_samples] i64 sample numbers, or NULL for samples 0..n_samples-1).  Gather + expansion in one

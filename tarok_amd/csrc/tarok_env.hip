@@ -1864,14 +1864,18 @@ __device__ __forceinline__ void mlp_hidden(__bf16 *__restrict__ X, const __bf16 
 // The policy step of 128 * TILES games by a workgroup of 256 * TILES threads (tile t = waves
 // 4t..4t+3 and rows 128t.. of X).  TILES = 1: tarok_policy_mlp; TILES = 2: the first half of
 // tarok_policy_step, which then needs the sampled cards of its 256 games in LDS (act_s).
-template <int TILES>
+// MIXED (tarok_policy_step_seats): a game whose seat to move is not in its seat set (seat_sets[i], or `seats` for every
+// game) takes the Bot's card — k_policy's, i.e. what tarok_step_random plays — and the log-probability 0; the network
+// is evaluated for every game all the same (the seat to move differs from lane to lane: nothing wave-uniform to skip).
+template <int TILES, bool MIXED = false>
 __device__ __forceinline__ void policy_body(
     int64_t n, const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23, const u64 *__restrict__ obs,
     const u64 *__restrict__ gkey, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
     const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3,
     const float *__restrict__ b3, uint8_t *__restrict__ action, float *__restrict__ logp, float *__restrict__ value,
     uint4 *__restrict__ features_out, ulonglong2 *__restrict__ feature_words_out, u64 *__restrict__ stamps,
-    uint8_t *__restrict__ act_s, u32 **lds_after = nullptr /* the activation buffer: free once every thread has returned */) {
+    uint8_t *__restrict__ act_s, u32 **lds_after = nullptr /* the activation buffer: free once every thread has returned */,
+    u32 seats = 15, const uint8_t *__restrict__ seat_sets = nullptr) {
     constexpr int GAMES = PM_M * TILES;
     u64 ts[7];
 #define PM_STAMP(k) if (stamps) ts[k] = __builtin_amdgcn_s_memtime();
@@ -2019,7 +2023,9 @@ __device__ __forceinline__ void policy_body(
         for (int c = 0; c < 27; c++) sum += l[c];
         float sum_sw = PM_SWAP_F(sum);
         sum = half ? sum : sum_sw;                             // total over cards 0..53, from the high lane
-        u32 rr = rng32(gkey[i], 192u + ((u32)(o >> TAROK_OBS_STEP_SHIFT) & 63u));
+        const u64 key = gkey[i];
+        const u32 played = (u32)(o >> TAROK_OBS_STEP_SHIFT) & 63u;      // cards played so far in this game
+        u32 rr = rng32(key, 192u + played);
         float u = ((float)(rr >> 8) + 0.5f) * (1.0f / 16777216.0f) * sum;
         float acc = start, pe = 0.f;
         int pickc = -1;
@@ -2042,10 +2048,16 @@ __device__ __forceinline__ void policy_body(
             int pk = pickc >= 0 ? pickc : (pick_o >= 0 ? pick_o + 27 : last);
             float pp = pickc >= 0 ? pe : (pick_o >= 0 ? pe_o : (last < 27 ? pl : pl_o));
             if (value) value[i] = v54;
+            bool bot = false;
+            if (MIXED) {
+                u32 set = seat_sets ? seat_sets[i] : seats;
+                bot = ((set >> ((u32)(o >> TAROK_OBS_SEAT_SHIFT) & 3u)) & 1u) == 0;
+                if (bot && m) pk = (int)policy_action(key, played, m);
+            }
             if (!m) { action[i] = 255; if (logp) logp[i] = 0.f; }
             else {
                 action[i] = (uint8_t)pk;
-                if (logp) logp[i] = __logf(pp / sum);
+                if (logp) logp[i] = (MIXED && bot) ? 0.f : __logf(pp / sum);
             }
             if (act_s) act_s[gi] = m ? (uint8_t)pk : (uint8_t)255;
         }
@@ -2091,6 +2103,35 @@ __global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_
     policy_body<2>(n, s01, s23, obs_in, gkey, w1, b1, w2, b2, w3, b3, action, logp, value, nullptr, feature_words_out, nullptr,
                    act_s, &lds);
     __syncthreads();                          // (the policy's LDS is free from here on: the step's scoring list goes there)
+    u32 tid = threadIdx.x;
+    step_role<false, false>(blockIdx.x, tid & (TK_BLOCK - 1), tid < TK_BLOCK, act_s[tid & (TK_BLOCK - 1)], false, n, seed, offset, mix, flags,
+                           count, epoch, play_groups, fan, nullptr, nullptr, reward, done, trick, obs_out, hist, s01, s23, aux, cnt, gkey, rlist, rcount, nullptr,
+                           reinterpret_cast<u32 (*)[TK_BLOCK]>(lds));
+}
+
+// tarok_policy_step_seats: the same launch with the network on the seats of a 4-bit set and the Bot on the others
+// (policy_body<2, true>).  Written out beside k_policy_step, not as a shared body: that kernel's code stays as it was,
+// instruction for instruction.  The set and the per-game sets come LAST: the preloaded kernel arguments are the same.
+__global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_step_seats(
+    int64_t n, u64 seed, u64 offset, int mix, int flags, u32 play_groups, u32 *epoch, u32 fan,
+    const u64 *__restrict__ obs_in, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3,
+    const float *__restrict__ b3, uint8_t *__restrict__ action, float *__restrict__ logp, float *__restrict__ value,
+    ulonglong2 *__restrict__ feature_words_out, int16_t *__restrict__ reward, uint8_t *__restrict__ done,
+    uint16_t *__restrict__ trick, u64 *__restrict__ obs_out, uint8_t *__restrict__ hist,
+    ulonglong2 *__restrict__ s01, ulonglong2 *__restrict__ s23, Aux *aux, Counters *__restrict__ cnt,
+    u64 *__restrict__ gkey, u64 *rlist, u32 *rcount, u32 seats, const uint8_t *__restrict__ seat_sets) {
+    TK_VGPR_TOP(256, 255);
+    TkCount count = launch_count<1>(epoch, play_groups);
+    if (blockIdx.x >= play_groups) {
+        refill_role<false>(blockIdx.x - play_groups, threadIdx.x, 2 * TK_BLOCK, seed, offset, mix, play_groups, count, epoch, fan, false, aux, rlist, rcount, nullptr);
+        return;
+    }
+    __shared__ uint8_t act_s[2 * PM_M];
+    u32 *lds = nullptr;
+    policy_body<2, true>(n, s01, s23, obs_in, gkey, w1, b1, w2, b2, w3, b3, action, logp, value, nullptr, feature_words_out, nullptr,
+                         act_s, &lds, seats, seat_sets);
+    __syncthreads();
     u32 tid = threadIdx.x;
     step_role<false, false>(blockIdx.x, tid & (TK_BLOCK - 1), tid < TK_BLOCK, act_s[tid & (TK_BLOCK - 1)], false, n, seed, offset, mix, flags,
                            count, epoch, play_groups, fan, nullptr, nullptr, reward, done, trick, obs_out, hist, s01, s23, aux, cnt, gkey, rlist, rcount, nullptr,
@@ -2776,6 +2817,25 @@ int tarok_policy_step(tarok_env *e, const void *w1, const float *b1, const void 
                        groups, e->epoch, fan, (const u64 *)obs, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3,
                        action_out, logp_out, value_out, (ulonglong2 *)feature_words_out, reward_out, done_out, trick_out,
                        (u64 *)obs_out, e->hist, e->s01, e->s23, e->aux, e->cnt, e->gkey, e->rlist, e->rcount);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int tarok_policy_step_seats(tarok_env *e, int seats, const uint8_t *seats_per_game, const void *w1, const float *b1, const void *w2,
+                            const float *b2, const void *w3, const float *b3, const uint64_t *obs, uint8_t *action_out, float *logp_out,
+                            float *value_out, uint64_t *feature_words_out, int16_t *reward_out, uint8_t *done_out, uint16_t *trick_out,
+                            uint64_t *obs_out, int flags, void *stream) {
+    if (!e || seats < 0 || seats > 15) return TAROK_EINVAL;       // (before the env is looked at, before any HIP call)
+    if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !obs || !action_out || !obs_out || obs == obs_out) return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    u32 groups = (u32)((e->n + TK_BLOCK - 1) / TK_BLOCK);
+    u32 fan = e->refill_fan;
+    dim3 grid(groups + (groups + fan - 1) / fan);
+    e->launched = 1;
+    hipLaunchKernelGGL(k_policy_step_seats, grid, dim3(2 * TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, e->mix, flags,
+                       groups, e->epoch, fan, (const u64 *)obs, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3,
+                       action_out, logp_out, value_out, (ulonglong2 *)feature_words_out, reward_out, done_out, trick_out,
+                       (u64 *)obs_out, e->hist, e->s01, e->s23, e->aux, e->cnt, e->gkey, e->rlist, e->rcount, (u32)seats, seats_per_game);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }

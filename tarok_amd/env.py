@@ -372,16 +372,31 @@ class TarokVecEnv:
         return action_out, logp_out, value_out
 
     def policy_step(self, weights, obs_words, obs_out, action_out, logp_out=None, value_out=None, feature_words_out=None,
-                    reward_out=None, done_out=None, auto_reset=True):
+                    reward_out=None, done_out=None, auto_reset=True, seats=None, seats_per_game=None, tricks=None):
         """policy_mlp + step in one launch (tarok_policy_step): samples a card per game from the MLP
-        policy on `obs_words` and plays it; obs_out receives the next observation words."""
+        policy on `obs_words` and plays it; obs_out receives the next observation words.
+        seats (a 4-bit set, bit s: seat s plays the network) or seats_per_game ([N] uint8 device tensor of such sets):
+        the mixed table of tarok_policy_step_seats — the other seats play the Bot's card (step_random's) with
+        logp 0.  tricks: a [N] int16 device tensor that receives trick_out (see step())."""
         w1, b1, w2, b2, w3, b3 = weights
+        flags = K.AUTO_RESET if auto_reset else 0
         with torch.cuda.device(self.device):
-            _native.check(self.L.tarok_policy_step(self._h, self._p(w1), self._p(b1), self._p(w2), self._p(b2), self._p(w3),
-                                                   self._p(b3), self._p(obs_words), self._p(action_out), self._p(logp_out),
-                                                   self._p(value_out), self._p(feature_words_out), self._p(reward_out),
-                                                   self._p(done_out), None, self._p(obs_out),
-                                                   K.AUTO_RESET if auto_reset else 0, self._stream()))
+            if seats is None and seats_per_game is None:
+                _native.check(self.L.tarok_policy_step(self._h, self._p(w1), self._p(b1), self._p(w2), self._p(b2), self._p(w3),
+                                                       self._p(b3), self._p(obs_words), self._p(action_out), self._p(logp_out),
+                                                       self._p(value_out), self._p(feature_words_out), self._p(reward_out),
+                                                       self._p(done_out), self._p(tricks), self._p(obs_out), flags, self._stream()))
+                return action_out
+            if seats_per_game is not None:
+                spg = seats_per_game
+                if not (torch.is_tensor(spg) and spg.device == self.device and spg.dtype == torch.uint8 and spg.is_contiguous()
+                        and tuple(spg.shape) == (self.n,)):
+                    raise ValueError("seats_per_game: a contiguous uint8 tensor [N] on the env's device")
+            _native.check(self.L.tarok_policy_step_seats(self._h, 15 if seats is None else int(seats), self._p(seats_per_game),
+                                                         self._p(w1), self._p(b1), self._p(w2), self._p(b2), self._p(w3),
+                                                         self._p(b3), self._p(obs_words), self._p(action_out), self._p(logp_out),
+                                                         self._p(value_out), self._p(feature_words_out), self._p(reward_out),
+                                                         self._p(done_out), self._p(tricks), self._p(obs_out), flags, self._stream()))
         return action_out
 
     def ppo_loss(self, out, obs_words, action, logp_old, advantage, ret, weight, clip, vf_coef, ent_coef):

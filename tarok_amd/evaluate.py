@@ -1,0 +1,84 @@
+"""How well does a policy play?  Duplicate evaluation of the learned policy against the Bot.
+
+The same deals are played five times: once with the Bot (Bot_igralec, Igralec.py:148-171: a uniformly random legal
+card) on all four seats, and once with the network on each single seat and the Bot on the other three
+(tarok_policy_step_seats).  Deals, contracts and the Bot's draws are functions of (seed, game index, episode, cards
+played) alone, so the five tables of a deal differ only through the cards the network chose, and the score the
+network's seat made is compared with the score the Bot made on that very seat of that very deal:
+
+    advantage = mean over deals d and seats k of  score(network on k)[d, k] - score(Bot everywhere)[d, k]
+
+in game points per game.  The four differences of a deal share its cards, so the standard error is taken over deals:
+stderr = std over d of (mean over k of the difference) / sqrt(deals).
+"""
+import numpy as np
+import torch
+
+from . import karte as K
+from .env import TarokVecEnv
+
+PASS_SEATS = (0, 1, 2, 4, 8)      # the seat set of pass p: Bot everywhere, then the network on seat p - 1 alone
+GAME_CARDS = 48
+
+
+def duplicate_advantage(scores):
+    """scores [5, D, 4] (numpy array or torch tensor): the final scores by seat of deal d in pass p — pass 0 the Bot on
+    every seat, pass 1 + k the network on seat k only.  Returns a dict:
+      policy_mean  mean over d, k of scores[1 + k, d, k]     bot_mean  the same entries of pass 0
+      advantage    mean of the paired differences            by_seat   [4] the same per seat k
+      stderr       sample standard deviation (n - 1) over deals of each deal's mean-over-k difference, divided by
+                   sqrt(D); nan for a single deal
+      deals        D"""
+    if torch.is_tensor(scores):
+        scores = scores.detach().cpu().numpy()
+    s = np.asarray(scores, dtype=np.float64)
+    if s.ndim != 3 or s.shape[0] != 5 or s.shape[2] != 4 or s.shape[1] < 1:
+        raise ValueError("scores must be [5, deals, 4], got %s" % (s.shape,))
+    k = np.arange(4)
+    own = s[1 + k, :, k].T                    # [D, 4]: the network's seat in its pass
+    bot = s[0][:, k]                          # [D, 4]: that seat with the Bot on it
+    diff = own - bot
+    deals = s.shape[1]
+    per_deal = diff.mean(axis=1)
+    stderr = float(per_deal.std(ddof=1) / np.sqrt(deals)) if deals > 1 else float("nan")
+    return dict(policy_mean=float(own.mean()), bot_mean=float(bot.mean()), advantage=float(diff.mean()), stderr=stderr,
+                by_seat=[float(x) for x in diff.mean(axis=0)], deals=int(deals))
+
+
+def _play_passes(weights, n_games, episodes, seed, mix, device, inspect=None):
+    """The five passes of every episode on an env of its own; returns scores [5, episodes * n_games, 4] i32.
+    inspect (tests): a list that receives one dict per pass — episode, seats, start (the canonical lanes after the
+    reset), actions [48, N] u8 and scores [N, 4] host arrays — at the price of a second synchronisation per pass."""
+    n = int(n_games)
+    scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
+    env = TarokVecEnv(n, device=device, seed=seed, mix=mix)
+    try:
+        with torch.cuda.device(env.device):
+            # the observation words go back and forth between the env's own buffer (reset() leaves the first ones there)
+            # and a second one: the step's input and output may not alias
+            words = [env.obs_words, torch.empty(n, dtype=torch.int64, device=env.device)]
+            actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
+        for e in range(int(episodes)):
+            for p, seats in enumerate(PASS_SEATS):
+                env.reset(episode=e, clear_counters=True)
+                start = env.state() if inspect is not None else None
+                for t in range(GAME_CARDS):
+                    env.policy_step(weights, words[t & 1], words[(t + 1) & 1], actions[t], auto_reset=False, seats=seats)
+                _, ss = env.counters()                # (the pass's one synchronisation)
+                scores[p, e * n:(e + 1) * n] = ss
+                if inspect is not None:
+                    inspect.append(dict(episode=e, seats=seats, start=start, actions=actions.cpu().numpy(), scores=ss.copy()))
+    finally:
+        env.close()
+    return scores
+
+
+def evaluate_vs_bot(weights, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0):
+    """Duplicate evaluation of `weights` (w1, b1, w2, b2, w3, b3 as tarok_policy_step takes them, on `device`)
+    over n_games * episodes deals; returns duplicate_advantage's dict.  Deal e * n_games + i is game i of episode e
+    of an env with this seed and game offset 0: the same arguments always play the same deals.
+
+    Runs on an env of its own (a training env, its state and its captured graph are never touched).  Per episode and
+    pass: reset with the score counters cleared, 48 one-card launches without auto-reset (a finished game ignores its
+    card; a Berac may end early), then ONE host synchronisation to read the slots' score sums."""
+    return duplicate_advantage(_play_passes(weights, n_games, episodes, seed, mix, device))

@@ -261,6 +261,20 @@ class SelfPlay:
                 for d, (p, dt) in zip(self._w, src):
                     d.copy_(conv(p, dt))              # in place: the captured graph reads these tensors
 
+    @torch.no_grad()
+    def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT):
+        """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
+        weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
+        and on the SAME deals on every rank (seed 0, game offset 0, whatever the training env's are): the figures of
+        one run are comparable from call to call, and ranks holding the same weights return the same numbers —
+        averaging them over ranks adds nothing."""
+        if not self.fused:
+            raise RuntimeError("evaluate() plays tarok_policy_step_seats, which is built for hidden = 256")
+        from .evaluate import evaluate_vs_bot
+        if self._w is None or not self.fused_learner:
+            self._refresh_rollout_weights()
+        return evaluate_vs_bot(self._w, n_games, episodes, mix=mix, device=self.env.device_index)
+
     def _alloc(self, T):
         n, dev = self.env.n, self.device
         self._T = T
