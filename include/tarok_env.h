@@ -326,6 +326,26 @@ int tarok_policy_step_seats(tarok_env *env, int seats, const uint8_t *seats_per_
                             int16_t *reward_out, uint8_t *done_out, uint16_t *trick_out, uint64_t *obs_out, int flags,
                             void *stream);
 
+/* tarok_policy_step_seats with a second network in the Bot's place: two weight sets at one table, e.g. the current
+ * checkpoint against an earlier one on the same deals (tarok_amd/evaluate.py, evaluate_vs_policy).
+ *   seats, seats_per_game   as in tarok_policy_step_seats: bit s set = seat s plays network A; every other seat
+ *                           plays network B
+ *   w1 .. b3                network A, v1 .. c3 network B: both in tarok_policy_mlp's layouts
+ * The other arguments are tarok_policy_step's.  The mover's network is chosen by the seat field of obs[i] and the
+ * game's set, live game or not; action_out, logp_out and value_out of a game are that network's, bit for bit what
+ * tarok_policy_mlp with its weights writes on the same observation words (both networks draw with the same spec RNG
+ * draw, 192 + cards played, and only one plays: a network's card on a position does not depend on the opponent).
+ * action_out = 255 and logp_out = 0 where nothing is to be played; feature_words_out and everything the env half
+ * writes are tarok_policy_step's.  seats = 15 gives exactly tarok_policy_step with A, seats = 0 with B.
+ * TAROK_EINVAL (before any HIP call) for a NULL env, seats outside 0..15, a missing weight, bias or required array,
+ * or obs == obs_out. */
+int tarok_policy_step_versus(tarok_env *env, int seats, const uint8_t *seats_per_game, const void *w1, const float *b1,
+                             const void *w2, const float *b2, const void *w3, const float *b3, const void *v1,
+                             const float *c1, const void *v2, const float *c2, const void *v3, const float *c3,
+                             const uint64_t *obs, uint8_t *action_out, float *logp_out, float *value_out,
+                             uint64_t *feature_words_out, int16_t *reward_out, uint8_t *done_out, uint16_t *trick_out,
+                             uint64_t *obs_out, int flags, void *stream);
+
 /* The learner's network input for a minibatch: features_out[j] [256] bf16 (0.0 / 1.0) = the bits
  * of feature_words[index[j]] (feature_words [M,4] u64 as written by feature_words_out; index
  * [n_samples] i64 sample numbers, or NULL for samples 0..n_samples-1).  Gather + expansion in one

@@ -2138,6 +2138,222 @@ __global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_
                            reinterpret_cast<u32 (*)[TK_BLOCK]>(lds));
 }
 
+// tarok_policy_step_versus: two networks at one table.  A second body beside policy_body<2> (whose instantiations stay
+// as they compile): the feature words are built once into ext, then the activation buffer is expanded from ext and
+// run through layers 1-3 and the sampler ONCE PER NETWORK (pass 0: A, pass 1: B; the logits of a pass overwrite the
+// activations, and no second buffer fits in LDS).  Each pass is policy_body's code — mlp_prefetch, mlp_hidden, the
+// same layer 3 and sampler in the same order of accumulation — so a network's card, log-probability and value are the
+// bits of tarok_policy_mlp with its weights; a game's candidate of pass A waits in the registers of its half == 0
+// lane, and the seat to move (obs bits 55:54) against the game's seat set picks the one that is written and played.
+__device__ __forceinline__ void policy_versus_body(
+    int64_t n, const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23, const u64 *__restrict__ obs,
+    const u64 *__restrict__ gkey, const __bf16 *__restrict__ w1a, const float *__restrict__ b1a, const __bf16 *__restrict__ w2a,
+    const float *__restrict__ b2a, const __bf16 *__restrict__ w3a, const float *__restrict__ b3a,
+    const __bf16 *__restrict__ w1b, const float *__restrict__ b1b, const __bf16 *__restrict__ w2b,
+    const float *__restrict__ b2b, const __bf16 *__restrict__ w3b, const float *__restrict__ b3b, uint8_t *__restrict__ action,
+    float *__restrict__ logp, float *__restrict__ value, ulonglong2 *__restrict__ feature_words_out,
+    uint8_t *__restrict__ act_s, u32 **lds_after, u32 seats, const uint8_t *__restrict__ seat_sets) {
+    constexpr int GAMES = PM_M * 2;
+    __shared__ __attribute__((aligned(16))) __bf16 X[GAMES * PM_LD];
+    __shared__ u64 ext[GAMES][4];
+    int64_t base = (int64_t)blockIdx.x * GAMES;
+    u32 tid = threadIdx.x, wave4 = (tid >> 6) & 3, tile = tid >> 8;
+    __bf16 *Xt = X + tile * PM_M * PM_LD;
+    *lds_after = reinterpret_cast<u32 *>(X);
+    bf16x8 wq[4][2];
+    mlp_prefetch(wq, w1a, wave4 * 2);          // lands while the features are built
+    // ---- the four 64-bit feature words of each game (policy_body's; kept in ext for both passes)
+    if (tid < GAMES) {
+        int64_t i = base + tid < n ? base + tid : n - 1;
+        Game g;
+        load_game(g, s01, s23, i);
+        u32 seat = (g.leader + g.nt) & 3;
+        bool live = g.phase == TK_PHASE_PLAY;
+        u64 on_table = 0;
+        for (u32 j = 0; j < g.nt; j++) on_table |= 1ULL << ((g.trick >> (6 * j)) & 63);
+        u64 f1 = (u64)(1u << ((g.declarer - seat) & 3)) | ((u64)(1u << g.nt) << 4) | ((u64)((g.team >> seat) & 1) << 8) |
+                 ((u64)(has_king(g.contract) ? 1u : 0u) << 9);
+        u64 f2 = (has_king(g.contract) ? (u64)(1u << g.king) : 0) | ((u64)g.trick_no << 4);
+        ext[tid][0] = hand_of(g, seat) | ((u64)(1u << g.contract) << 54);
+        ext[tid][1] = (live ? legal_now(g) : 0) | (f1 << 54);
+        ext[tid][2] = on_table | (f2 << 54);
+        ext[tid][3] = (g.C & ~talon_unowned(g) & ~on_table) | ((u64)(live ? 1u : 0u) << 54);
+        if (feature_words_out && base + tid < n) {
+            feature_words_out[i * 2] = make_ulonglong2(ext[tid][0], ext[tid][1]);
+            feature_words_out[i * 2 + 1] = make_ulonglong2(ext[tid][2], ext[tid][3]);
+        }
+    }
+    // the sampler's per-game inputs, the same for both passes (two lanes per game)
+    const u32 gi = tid >> 1, half = tid & 1;
+    const bool in_range = base + gi < n;
+    const int64_t i = in_range ? base + gi : n - 1;
+    const u64 o = obs[i];
+    const u64 m = o & TAROK_OBS_MASK;
+    const u64 key = gkey[i];
+    const u32 played = (u32)(o >> TAROK_OBS_STEP_SHIFT) & 63u;
+    const u32 set = seat_sets ? seat_sets[i] : seats;
+    const bool is_a = ((set >> ((u32)(o >> TAROK_OBS_SEAT_SHIFT) & 3u)) & 1u) != 0;
+    int pk = 0;                                    // the mover's network's candidate (held by the game's half == 0 lane)
+    float pp = 0.f, psum = 1.f, pv = 0.f;
+#pragma unroll 1
+    for (int net = 0; net < 2; net++) {
+        const bool mine = (net == 0) == is_a;
+        const __bf16 *w1 = net ? w1b : w1a, *w2 = net ? w2b : w2a, *w3 = net ? w3b : w3a;
+        const float *b1 = net ? b1b : b1a, *b2 = net ? b2b : b2a, *b3 = net ? b3b : b3a;
+        // (pass 1: every lane has read its logits of pass 0 before the activations go back over them)
+        __syncthreads();
+        if (net) mlp_prefetch(wq, w1, wave4 * 2);
+        {   // expand ext to bf16 0.0 / 1.0 (policy_body's expansion)
+            u32 gme = tid >> 1, par = tid & 1;
+            const uint4 *row = reinterpret_cast<const uint4 *>(&ext[gme][0]);
+            uint4 r0 = row[0], r1 = row[1];
+            u32 wd[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                u32 chunk = 2 * j + par;
+                u32 byte = (wd[j >> 1] >> (8 * ((2 * (j & 1)) + par))) & 255u;
+                *reinterpret_cast<uint4 *>(X + gme * PM_LD + 8 * chunk) = tk_expand_byte(byte);
+            }
+        }
+        __syncthreads();
+        mlp_hidden(Xt, w1, b1, wq, wave4);
+        mlp_prefetch(wq, w2, wave4 * 2);
+        mlp_hidden(Xt, w2, b2, wq, wave4);
+        // ---- layer 3 (policy_body's): f32 logits to LDS [256][68] over the activation buffer
+        float *L = reinterpret_cast<float *>(X);
+        {
+            u32 lane = __lane_id(), wave = wave4, r = lane & 31, h = lane >> 5;
+            const bf16x8 *wf = reinterpret_cast<const bf16x8 *>(w3) + lane;
+            f32x16 acc[2];
+#pragma unroll
+            for (int ft = 0; ft < 2; ft++)
+#pragma unroll
+                for (int j = 0; j < 16; j++) acc[ft][j] = 0.f;
+            bf16x8 wq[4][2];
+#pragma unroll
+            for (int d = 0; d < 4; d++)
+#pragma unroll
+                for (int ft = 0; ft < 2; ft++) wq[d][ft] = wf[(ft * 16 + d) * 64];
+            bf16x8 xn = *reinterpret_cast<const bf16x8 *>(Xt + (32 * wave + r) * PM_LD + 8 * h);
+#pragma unroll
+            for (int kk = 0; kk < 16; kk++) {
+                bf16x8 x = xn;
+                bf16x8 wc[2] = {wq[kk & 3][0], wq[kk & 3][1]};
+                if (kk + 4 < 16) {
+#pragma unroll
+                    for (int ft = 0; ft < 2; ft++) wq[kk & 3][ft] = wf[(ft * 16 + kk + 4) * 64];
+                }
+                if (kk < 15) xn = *reinterpret_cast<const bf16x8 *>(Xt + (32 * wave + r) * PM_LD + 16 * (kk + 1) + 8 * h);
+#pragma unroll
+                for (int ft = 0; ft < 2; ft++) acc[ft] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wc[ft], x, acc[ft], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __syncthreads();                           // all waves are done with X: the logits may overwrite it
+#pragma unroll
+            for (int ft = 0; ft < 2; ft++)
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    u32 f0 = 32 * ft + 8 * q + 4 * h;
+                    float4 bv = *reinterpret_cast<const float4 *>(b3 + f0);
+                    float4 ov = make_float4(acc[ft][4 * q + 0] + bv.x, acc[ft][4 * q + 1] + bv.y, acc[ft][4 * q + 2] + bv.z, acc[ft][4 * q + 3] + bv.w);
+                    *reinterpret_cast<float4 *>(L + (PM_M * tile + 32 * wave + r) * PM_LL + f0) = ov;
+                }
+        }
+        __syncthreads();
+        // ---- masked categorical sample (policy_body's: same draw, same order of additions), two lanes per game
+        {
+#define PM_SWAP_F(x) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, true))   /* quad_perm [1,0,3,2] */
+#define PM_SWAP_I(x) __builtin_amdgcn_update_dpp(0, (int)(x), 0xB1, 0xF, 0xF, true)
+            float l[27];
+#pragma unroll
+            for (int c = 0; c < 27; c++) l[c] = L[gi * PM_LL + 27 * half + c];
+            float v54 = L[gi * PM_LL + 54];
+            u32 mh = (u32)(m >> (27 * half)) & 0x7FFFFFFu;
+            float mx = -3.0e38f;
+#pragma unroll
+            for (int c = 0; c < 27; c++) mx = ((mh >> c) & 1) ? fmaxf(mx, l[c]) : mx;
+            mx = fmaxf(mx, PM_SWAP_F(mx));
+#pragma unroll
+            for (int c = 0; c < 27; c++) l[c] = ((mh >> c) & 1) ? __expf(l[c] - mx) : 0.f;
+            float s = 0.f;
+#pragma unroll
+            for (int c = 0; c < 27; c++) s += l[c];
+            float s_sw = PM_SWAP_F(s);                         // (DPP reads need the source lane active: never inside a select)
+            float s_low = half ? s_sw : s;
+            float start = half ? s_low : 0.f;
+            float sum = start;
+#pragma unroll
+            for (int c = 0; c < 27; c++) sum += l[c];
+            float sum_sw = PM_SWAP_F(sum);
+            sum = half ? sum : sum_sw;
+            u32 rr = rng32(key, 192u + played);
+            float u = ((float)(rr >> 8) + 0.5f) * (1.0f / 16777216.0f) * sum;
+            float acc = start, pe = 0.f;
+            int pickc = -1;
+#pragma unroll
+            for (int c = 0; c < 27; c++) {
+                bool legal = (mh >> c) & 1;
+                acc += l[c];
+                bool take = legal && pickc < 0 && acc > u;
+                pe = take ? l[c] : pe;
+                pickc = take ? c : pickc;
+            }
+            int last = m ? 63 - __clzll(m) : 0;
+            float pl = 0.f;
+#pragma unroll
+            for (int c = 0; c < 27; c++) pl = (c + 27 * (int)half == last) ? l[c] : pl;
+            int pick_o = PM_SWAP_I(pickc);
+            float pe_o = PM_SWAP_F(pe), pl_o = PM_SWAP_F(pl);
+            int pk_n = pickc >= 0 ? pickc : (pick_o >= 0 ? pick_o + 27 : last);
+            float pp_n = pickc >= 0 ? pe : (pick_o >= 0 ? pe_o : (last < 27 ? pl : pl_o));
+            pk = mine ? pk_n : pk;
+            pp = mine ? pp_n : pp;
+            psum = mine ? sum : psum;
+            pv = mine ? v54 : pv;
+#undef PM_SWAP_F
+#undef PM_SWAP_I
+        }
+    }
+    if (half == 0 && in_range) {
+        if (value) value[i] = pv;
+        if (!m) { action[i] = 255; if (logp) logp[i] = 0.f; }
+        else {
+            action[i] = (uint8_t)pk;
+            if (logp) logp[i] = __logf(pp / psum);
+        }
+        act_s[gi] = m ? (uint8_t)pk : (uint8_t)255;
+    }
+}
+
+// (the twelve weight pointers, the set and the per-game sets come LAST: the preloaded kernel arguments are its siblings')
+__global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_step_versus(
+    int64_t n, u64 seed, u64 offset, int mix, int flags, u32 play_groups, u32 *epoch, u32 fan,
+    const u64 *__restrict__ obs_in, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3,
+    const float *__restrict__ b3, uint8_t *__restrict__ action, float *__restrict__ logp, float *__restrict__ value,
+    ulonglong2 *__restrict__ feature_words_out, int16_t *__restrict__ reward, uint8_t *__restrict__ done,
+    uint16_t *__restrict__ trick, u64 *__restrict__ obs_out, uint8_t *__restrict__ hist,
+    ulonglong2 *__restrict__ s01, ulonglong2 *__restrict__ s23, Aux *aux, Counters *__restrict__ cnt,
+    u64 *__restrict__ gkey, u64 *rlist, u32 *rcount, u32 seats, const uint8_t *__restrict__ seat_sets,
+    const __bf16 *__restrict__ v1, const float *__restrict__ c1, const __bf16 *__restrict__ v2,
+    const float *__restrict__ c2, const __bf16 *__restrict__ v3, const float *__restrict__ c3) {
+    TK_VGPR_TOP(256, 255);
+    TkCount count = launch_count<1>(epoch, play_groups);
+    if (blockIdx.x >= play_groups) {
+        refill_role<false>(blockIdx.x - play_groups, threadIdx.x, 2 * TK_BLOCK, seed, offset, mix, play_groups, count, epoch, fan, false, aux, rlist, rcount, nullptr);
+        return;
+    }
+    __shared__ uint8_t act_s[2 * PM_M];
+    u32 *lds = nullptr;
+    policy_versus_body(n, s01, s23, obs_in, gkey, w1, b1, w2, b2, w3, b3, v1, c1, v2, c2, v3, c3, action, logp, value, feature_words_out, act_s, &lds,
+                       seats, seat_sets);
+    __syncthreads();
+    u32 tid = threadIdx.x;
+    step_role<false, false>(blockIdx.x, tid & (TK_BLOCK - 1), tid < TK_BLOCK, act_s[tid & (TK_BLOCK - 1)], false, n, seed, offset, mix, flags,
+                           count, epoch, play_groups, fan, nullptr, nullptr, reward, done, trick, obs_out, hist, s01, s23, aux, cnt, gkey, rlist, rcount, nullptr,
+                           reinterpret_cast<u32 (*)[TK_BLOCK]>(lds));
+}
+
 // ---------------------------------------------------------------------------
 // The reference agent's transition targets in its own form: what Nevronski_igralec.rezultat_stiha
 // builds per trick and rezultat_igre completes (Igralec.py:387-446), for every (trick, game, seat) of a recorded
@@ -2836,6 +3052,28 @@ int tarok_policy_step_seats(tarok_env *e, int seats, const uint8_t *seats_per_ga
                        groups, e->epoch, fan, (const u64 *)obs, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3,
                        action_out, logp_out, value_out, (ulonglong2 *)feature_words_out, reward_out, done_out, trick_out,
                        (u64 *)obs_out, e->hist, e->s01, e->s23, e->aux, e->cnt, e->gkey, e->rlist, e->rcount, (u32)seats, seats_per_game);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int tarok_policy_step_versus(tarok_env *e, int seats, const uint8_t *seats_per_game, const void *w1, const float *b1, const void *w2,
+                             const float *b2, const void *w3, const float *b3, const void *v1, const float *c1, const void *v2,
+                             const float *c2, const void *v3, const float *c3, const uint64_t *obs, uint8_t *action_out,
+                             float *logp_out, float *value_out, uint64_t *feature_words_out, int16_t *reward_out, uint8_t *done_out,
+                             uint16_t *trick_out, uint64_t *obs_out, int flags, void *stream) {
+    if (!e || seats < 0 || seats > 15) return TAROK_EINVAL;       // (before the env is looked at, before any HIP call)
+    if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !v1 || !c1 || !v2 || !c2 || !v3 || !c3) return TAROK_EINVAL;
+    if (!obs || !action_out || !obs_out || obs == obs_out) return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    u32 groups = (u32)((e->n + TK_BLOCK - 1) / TK_BLOCK);
+    u32 fan = e->refill_fan;
+    dim3 grid(groups + (groups + fan - 1) / fan);
+    e->launched = 1;
+    hipLaunchKernelGGL(k_policy_step_versus, grid, dim3(2 * TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, e->mix, flags,
+                       groups, e->epoch, fan, (const u64 *)obs, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3,
+                       action_out, logp_out, value_out, (ulonglong2 *)feature_words_out, reward_out, done_out, trick_out,
+                       (u64 *)obs_out, e->hist, e->s01, e->s23, e->aux, e->cnt, e->gkey, e->rlist, e->rcount, (u32)seats, seats_per_game,
+                       (const __bf16 *)v1, c1, (const __bf16 *)v2, c2, (const __bf16 *)v3, c3);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }

@@ -347,17 +347,23 @@ class TarokVecEnv:
         assert weight.shape[1] == 256 and out % 32 == 0
         return weight.detach().to(torch.bfloat16).view(out // 32, 32, 16, 2, 8).permute(0, 2, 3, 1, 4).contiguous().view(out, 256)
 
+    @staticmethod
+    def check_mlp_weights(weights):
+        """(w1, b1, w2, b2, w3, b3) as the policy kernels read them, or an AssertionError / ValueError."""
+        w1, b1, w2, b2, w3, b3 = weights
+        for w, shp in ((w1, (256, 256)), (w2, (256, 256)), (w3, (64, 256))):
+            assert w.dtype == torch.bfloat16 and w.is_contiguous() and tuple(w.shape) == shp
+        for b, k in ((b1, 256), (b2, 256), (b3, 64)):
+            assert b.dtype == torch.float32 and b.is_contiguous() and tuple(b.shape) == (k,)
+        return w1, b1, w2, b2, w3, b3
+
     def policy_mlp(self, weights, obs_words, action_out=None, logp_out=None, value_out=None, features_out=None,
                    feature_words_out=None):
         """Fused learned-policy step (tarok_policy_mlp).  weights = (w1, b1, w2, b2, w3, b3): w* bf16 in
         mfma_weight_order() ([256,256], [256,256], [64,256]), b* f32; returns (action u8 [N], logp f32 [N],
         value f32 [N]).  features_out [N,256] bf16 and/or feature_words_out [N,4] int64 (the same features
         as bits: expand_feature_words) receive the network input for the learner."""
-        w1, b1, w2, b2, w3, b3 = weights
-        for w, shp in ((w1, (256, 256)), (w2, (256, 256)), (w3, (64, 256))):
-            assert w.dtype == torch.bfloat16 and w.is_contiguous() and tuple(w.shape) == shp
-        for b, k in ((b1, 256), (b2, 256), (b3, 64)):
-            assert b.dtype == torch.float32 and b.is_contiguous() and tuple(b.shape) == (k,)
+        w1, b1, w2, b2, w3, b3 = self.check_mlp_weights(weights)
         with torch.cuda.device(self.device):
             if action_out is None:
                 action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
@@ -372,16 +378,19 @@ class TarokVecEnv:
         return action_out, logp_out, value_out
 
     def policy_step(self, weights, obs_words, obs_out, action_out, logp_out=None, value_out=None, feature_words_out=None,
-                    reward_out=None, done_out=None, auto_reset=True, seats=None, seats_per_game=None, tricks=None):
+                    reward_out=None, done_out=None, auto_reset=True, seats=None, seats_per_game=None, tricks=None, opponent=None):
         """policy_mlp + step in one launch (tarok_policy_step): samples a card per game from the MLP
         policy on `obs_words` and plays it; obs_out receives the next observation words.
         seats (a 4-bit set, bit s: seat s plays the network) or seats_per_game ([N] uint8 device tensor of such sets):
         the mixed table of tarok_policy_step_seats — the other seats play the Bot's card (step_random's) with
-        logp 0.  tricks: a [N] int16 device tensor that receives trick_out (see step())."""
+        logp 0.  tricks: a [N] int16 device tensor that receives trick_out (see step()).
+        opponent (six tensors like `weights`): a second network in the Bot's place (tarok_policy_step_versus) — the
+        seats of the set play `weights`, the others `opponent`, each with its own card, logp and value; without
+        seats / seats_per_game the set is 15."""
         w1, b1, w2, b2, w3, b3 = weights
         flags = K.AUTO_RESET if auto_reset else 0
         with torch.cuda.device(self.device):
-            if seats is None and seats_per_game is None:
+            if opponent is None and seats is None and seats_per_game is None:
                 _native.check(self.L.tarok_policy_step(self._h, self._p(w1), self._p(b1), self._p(w2), self._p(b2), self._p(w3),
                                                        self._p(b3), self._p(obs_words), self._p(action_out), self._p(logp_out),
                                                        self._p(value_out), self._p(feature_words_out), self._p(reward_out),
@@ -392,6 +401,14 @@ class TarokVecEnv:
                 if not (torch.is_tensor(spg) and spg.device == self.device and spg.dtype == torch.uint8 and spg.is_contiguous()
                         and tuple(spg.shape) == (self.n,)):
                     raise ValueError("seats_per_game: a contiguous uint8 tensor [N] on the env's device")
+            if opponent is not None:
+                w1, b1, w2, b2, w3, b3 = self.check_mlp_weights(weights)
+                _native.check(self.L.tarok_policy_step_versus(
+                    self._h, 15 if seats is None else int(seats), self._p(seats_per_game), self._p(w1), self._p(b1), self._p(w2),
+                    self._p(b2), self._p(w3), self._p(b3), *[self._p(t) for t in self.check_mlp_weights(opponent)],
+                    self._p(obs_words), self._p(action_out), self._p(logp_out), self._p(value_out), self._p(feature_words_out),
+                    self._p(reward_out), self._p(done_out), self._p(tricks), self._p(obs_out), flags, self._stream()))
+                return action_out
             _native.check(self.L.tarok_policy_step_seats(self._h, 15 if seats is None else int(seats), self._p(seats_per_game),
                                                          self._p(w1), self._p(b1), self._p(w2), self._p(b2), self._p(w3),
                                                          self._p(b3), self._p(obs_words), self._p(action_out), self._p(logp_out),

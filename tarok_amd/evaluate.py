@@ -1,4 +1,5 @@
-"""How well does a policy play?  Duplicate evaluation of the learned policy against the Bot.
+"""How well does a policy play?  Duplicate evaluation of the learned policy against the Bot (evaluate_vs_bot) or
+against a second network, such as an earlier checkpoint (evaluate_vs_policy: read "the Bot" below as that network).
 
 The same deals are played five times: once with the Bot (Bot_igralec, Igralec.py:148-171: a uniformly random legal
 card) on all four seats, and once with the network on each single seat and the Bot on the other three
@@ -45,8 +46,10 @@ def duplicate_advantage(scores):
                 by_seat=[float(x) for x in diff.mean(axis=0)], deals=int(deals))
 
 
-def _play_passes(weights, n_games, episodes, seed, mix, device, inspect=None):
+def _play_passes(weights, n_games, episodes, seed, mix, device, inspect=None, opponent=None):
     """The five passes of every episode on an env of its own; returns scores [5, episodes * n_games, 4] i32.
+    opponent: six tensors like `weights`, the network that takes the Bot's place on every seat outside the pass's set
+    (tarok_policy_step_versus; None: the Bot, tarok_policy_step_seats).
     inspect (tests): a list that receives one dict per pass — episode, seats, start (the canonical lanes after the
     reset), actions [48, N] u8 and scores [N, 4] host arrays — at the price of a second synchronisation per pass."""
     n = int(n_games)
@@ -63,7 +66,8 @@ def _play_passes(weights, n_games, episodes, seed, mix, device, inspect=None):
                 env.reset(episode=e, clear_counters=True)
                 start = env.state() if inspect is not None else None
                 for t in range(GAME_CARDS):
-                    env.policy_step(weights, words[t & 1], words[(t + 1) & 1], actions[t], auto_reset=False, seats=seats)
+                    env.policy_step(weights, words[t & 1], words[(t + 1) & 1], actions[t], auto_reset=False, seats=seats,
+                                    opponent=opponent)
                 _, ss = env.counters()                # (the pass's one synchronisation)
                 scores[p, e * n:(e + 1) * n] = ss
                 if inspect is not None:
@@ -82,3 +86,18 @@ def evaluate_vs_bot(weights, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0)
     pass: reset with the score counters cleared, 48 one-card launches without auto-reset (a finished game ignores its
     card; a Berac may end early), then ONE host synchronisation to read the slots' score sums."""
     return duplicate_advantage(_play_passes(weights, n_games, episodes, seed, mix, device))
+
+
+def evaluate_vs_policy(weights, opponent, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0):
+    """Duplicate evaluation of `weights` against a second network, `opponent` (both as tarok_policy_step takes them, on
+    `device`): evaluate_vs_bot with `opponent` in the Bot's place, one tarok_policy_step_versus launch per lock-step.
+    Pass 0 plays `opponent` on all four seats, pass 1 + k `weights` on seat k alone and `opponent` on the other three,
+    on the deals evaluate_vs_bot plays with the same arguments.  Returns duplicate_advantage's dict, unchanged:
+    `bot_mean` is then the mean of the BASELINE policy (`opponent` on the seat in pass 0), `policy_mean` that of
+    `weights`, and `advantage` is points per game of `weights` over `opponent` — exactly 0.0 for a network against
+    itself, since a network's card on a position does not depend on who else sits at the table."""
+    for name, ws in (("weights", weights), ("opponent", opponent)):
+        if not isinstance(ws, (tuple, list)) or len(ws) != 6 or not all(torch.is_tensor(t) for t in ws):
+            raise ValueError("%s: six tensors (w1, b1, w2, b2, w3, b3)" % name)
+        TarokVecEnv.check_mlp_weights(ws)
+    return duplicate_advantage(_play_passes(weights, n_games, episodes, seed, mix, device, opponent=opponent))

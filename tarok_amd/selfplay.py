@@ -262,17 +262,31 @@ class SelfPlay:
                     d.copy_(conv(p, dt))              # in place: the captured graph reads these tensors
 
     @torch.no_grad()
-    def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT):
+    def snapshot(self):
+        """A detached copy of the current policy as the kernels read it (w1, b1, w2, b2, w3, b3: what evaluate()
+        plays), safe to keep across later updates: evaluate(opponent=...) takes it."""
+        if not self.fused:
+            raise RuntimeError("snapshot() copies the weights of the fused policy, which is built for hidden = 256")
+        if self._w is None or not self.fused_learner:
+            self._refresh_rollout_weights()
+        return tuple(t.detach().clone().contiguous() for t in self._w)
+
+    @torch.no_grad()
+    def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None):
         """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
         weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
         and on the SAME deals on every rank (seed 0, game offset 0, whatever the training env's are): the figures of
         one run are comparable from call to call, and ranks holding the same weights return the same numbers —
-        averaging them over ranks adds nothing."""
+        averaging them over ranks adds nothing.
+        opponent (a snapshot()): points per game against that network instead (evaluate.evaluate_vs_policy: `bot_mean`
+        is then the opponent's mean), on the same deals."""
         if not self.fused:
             raise RuntimeError("evaluate() plays tarok_policy_step_seats, which is built for hidden = 256")
-        from .evaluate import evaluate_vs_bot
+        from .evaluate import evaluate_vs_bot, evaluate_vs_policy
         if self._w is None or not self.fused_learner:
             self._refresh_rollout_weights()
+        if opponent is not None:
+            return evaluate_vs_policy(self._w, opponent, n_games, episodes, mix=mix, device=self.env.device_index)
         return evaluate_vs_bot(self._w, n_games, episodes, mix=mix, device=self.env.device_index)
 
     def _alloc(self, T):

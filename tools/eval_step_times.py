@@ -6,7 +6,8 @@ usage: python tools/eval_step_times.py [--evaluate] LIB LABEL OUT [KIND ...]
          without tarok_policy_step_seats can be timed too)
   LABEL  goes in front of every line
   OUT    the lines are appended to this file
-  KIND   "plain" (tarok_policy_step) or a seat set 0..15 (tarok_policy_step_seats)"""
+  KIND   "plain" (tarok_policy_step), a seat set 0..15 (tarok_policy_step_seats) or "versus:<set>"
+         (tarok_policy_step_versus: two different weight sets, PolicyNet(256) of torch seeds 0 and 1, parameters x 3)"""
 import ctypes as C
 import os
 import sys
@@ -27,6 +28,8 @@ L.tarok_legal_actions.restype = i32; L.tarok_legal_actions.argtypes = [vp, vp, v
 L.tarok_policy_step.restype = i32; L.tarok_policy_step.argtypes = [vp] * 16 + [i32, vp]
 if hasattr(L, "tarok_policy_step_seats"):
     L.tarok_policy_step_seats.restype = i32; L.tarok_policy_step_seats.argtypes = [vp, i32, vp] + [vp] * 15 + [i32, vp]
+if hasattr(L, "tarok_policy_step_versus"):
+    L.tarok_policy_step_versus.restype = i32; L.tarok_policy_step_versus.argtypes = [vp, i32, vp] + [vp] * 21 + [i32, vp]
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tarok_amd import karte as K, selfplay as SP
@@ -36,7 +39,20 @@ net = SP.PolicyNet(256).cuda()
 order = TarokVecEnv.mfma_weight_order
 bf = lambda w: order(w.detach().to(torch.bfloat16).contiguous())
 fl = lambda b: b.detach().float().contiguous()
-W = [bf(net.fc1.weight), fl(net.fc1.bias), bf(net.fc2.weight), fl(net.fc2.bias), bf(net.head.weight), fl(net.head.bias)]
+pack = lambda net: [bf(net.fc1.weight), fl(net.fc1.bias), bf(net.fc2.weight), fl(net.fc2.bias), bf(net.head.weight), fl(net.head.bias)]
+W = pack(net)
+
+
+def scaled(seed):
+    torch.manual_seed(seed)
+    m = SP.PolicyNet(256).cuda()
+    with torch.no_grad():
+        for q in m.parameters():
+            q.mul_(3.0)
+    return pack(m)
+
+
+VS = [scaled(0), scaled(1)] if any(k.startswith("versus:") for k in kinds) else None
 p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
 dev = torch.device("cuda", 0)
 lines = []
@@ -54,8 +70,13 @@ for kind in kinds:
     def body(stream):
         s = C.c_void_p(stream.cuda_stream)
         for t in range(T):
-            a = [p(x) for x in W] + [p(words[t % 2]), p(act[t]), p(logp[t]), p(val[t]), p(fw[t]), p(rew[t]), p(done[t]), None, p(words[(t + 1) % 2]), K.AUTO_RESET, s]
-            rc = L.tarok_policy_step(h, *a) if kind == "plain" else L.tarok_policy_step_seats(h, int(kind), None, *a)
+            a = ([p(x) for x in VS[0] + VS[1]] if kind.startswith("versus:") else [p(x) for x in W]) + [p(words[t % 2]), p(act[t]), p(logp[t]), p(val[t]), p(fw[t]), p(rew[t]), p(done[t]), None, p(words[(t + 1) % 2]), K.AUTO_RESET, s]
+            if kind == "plain":
+                rc = L.tarok_policy_step(h, *a)
+            elif kind.startswith("versus:"):
+                rc = L.tarok_policy_step_versus(h, int(kind[7:]), None, *a)
+            else:
+                rc = L.tarok_policy_step_seats(h, int(kind), None, *a)
             assert rc == 0, rc
 
     cur = torch.cuda.current_stream(dev)
@@ -84,7 +105,7 @@ for kind in kinds:
         one.append(e0.elapsed_time(e1) * 1e3)
         many.append(e1.elapsed_time(e2) * 1e3 / INNER)
     lines.append("%-8s %-22s one replay of 48 launches, us: %s | mean of %d back-to-back replays, us: %s" % (
-        label, "tarok_policy_step" if kind == "plain" else "policy_step_seats=%s" % kind,
+        label, "tarok_policy_step" if kind == "plain" else "policy_step_versus=%s" % kind[7:] if kind.startswith("versus:") else "policy_step_seats=%s" % kind,
         " ".join("%.1f" % x for x in one), INNER, " ".join("%.1f" % x for x in many)))
     L.tarok_destroy(h)
     del g
