@@ -1249,7 +1249,24 @@ TK_KERNEL(TK_BLOCK, 96) void k_rollout(int64_t n, u64 seed, u64 offset, u32 epis
 //                                   the table one-hot (4), mover is on the declarer's team, Tri/Dve/Ena
 //   [128,192) cards on the table  | called-king suit one-hot (4), trick number in binary (4), 0, 0
 //   [192,256) cards already taken | game live, 0 ...
-// Each thread builds the four 64-bit words of its own game; then the wave writes one game per
+// The four 64-bit feature words of a game, for the seat to move (the regions above: a 54-bit card set, ten flag bits
+// from bit 54): what the fused policy kernels feed their network and write to feature_words_out.
+// (k_observe restates it: through this function that tuned kernel compiles to another instruction stream.)
+__device__ __forceinline__ void policy_feature_words(const Game &g, u64 (&e)[4]) {
+    u32 seat = (g.leader + g.nt) & 3;
+    bool live = g.phase == TK_PHASE_PLAY;
+    u64 on_table = 0;
+    for (u32 j = 0; j < g.nt; j++) on_table |= 1ULL << ((g.trick >> (6 * j)) & 63);
+    u64 f1 = (u64)(1u << ((g.declarer - seat) & 3)) | ((u64)(1u << g.nt) << 4) | ((u64)((g.team >> seat) & 1) << 8) |
+             ((u64)(has_king(g.contract) ? 1u : 0u) << 9);
+    u64 f2 = (has_king(g.contract) ? (u64)(1u << g.king) : 0) | ((u64)g.trick_no << 4);
+    e[0] = hand_of(g, seat) | ((u64)(1u << g.contract) << 54);
+    e[1] = (live ? legal_now(g) : 0) | (f1 << 54);
+    e[2] = on_table | (f2 << 54);
+    e[3] = (g.C & ~talon_unowned(g) & ~on_table) | ((u64)(live ? 1u : 0u) << 54);
+}
+
+// k_observe: each thread builds the four 64-bit words of its own game; then the wave writes one game per
 // iteration: lane L expands bits 4L..4L+3 into 4 bf16 and the 64 lanes store one contiguous
 // 512-byte row (v_readlane broadcasts the words), so the 33 MB/step of features leave as full lines.
 TK_KERNEL(TK_BLOCK, 64) void k_observe(int64_t n, const ulonglong2 *__restrict__ s01,
@@ -1861,21 +1878,170 @@ __device__ __forceinline__ void mlp_hidden(__bf16 *__restrict__ X, const __bf16 
     __syncthreads();
 }
 
-// The policy step of 128 * TILES games by a workgroup of 256 * TILES threads (tile t = waves
-// 4t..4t+3 and rows 128t.. of X).  TILES = 1: tarok_policy_mlp; TILES = 2: the first half of
-// tarok_policy_step, which then needs the sampled cards of its 256 games in LDS (act_s).
-// MIXED (tarok_policy_step_seats): a game whose seat to move is not in its seat set (seat_sets[i], or `seats` for every
-// game) takes the Bot's card — k_policy's, i.e. what tarok_step_random plays — and the log-probability 0; the network
-// is evaluated for every game all the same (the seat to move differs from lane to lane: nothing wave-uniform to skip).
-template <int TILES, bool MIXED = false>
+// The weights of one network, as tarok_policy_mlp takes them (bf16 in MFMA fragment order, f32 biases).
+struct PolicyWeights {
+    const __bf16 *w1; const float *b1; const __bf16 *w2; const float *b2; const __bf16 *w3; const float *b3;
+};
+
+// The feature words ext[game][4] expanded to bf16 0.0 / 1.0 into X, one 16-byte chunk (8 features = one byte of a
+// feature word) at a time.  Two threads per game (tid < 2 * games), thread parity p takes the odd / even bytes of the
+// game's 32: ONE 32-byte LDS read per thread up front instead of a dependent byte read per chunk, and the pair's
+// 16-byte stores fall into different banks.  (A 256-entry LDS table byte -> 8 bf16 was tried: no faster than the selects.)
+// (k_learn_chain restates it: through this function that tuned kernel compiles to another instruction stream.)
+__device__ __forceinline__ void policy_expand(__bf16 *X, const u64 (*ext)[4], u32 tid) {
+    u32 gme = tid >> 1, par = tid & 1;
+    const uint4 *row = reinterpret_cast<const uint4 *>(&ext[gme][0]);
+    uint4 r0 = row[0], r1 = row[1];
+    u32 wd[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+        u32 chunk = 2 * j + par;                       // byte `chunk` of the row = byte (2j + par) & 3 of word j / 2
+        u32 byte = (wd[j >> 1] >> (8 * ((2 * (j & 1)) + par))) & 255u;
+        *reinterpret_cast<uint4 *>(X + gme * PM_LD + 8 * chunk) = tk_expand_byte(byte);
+    }
+}
+
+// Layer 3: 64 outputs; wave w of the tile takes games [32w, 32w+32), both 32-feature tiles; f32 logits to LDS
+// [games][PM_LL] OVER the activation buffer (Xt: this tile's rows of it, L: all of it as floats — the same memory,
+// hence the barrier between the last read and the first store, and no __restrict__ on either).
+__device__ __forceinline__ void mlp_head(const __bf16 *Xt, float *L, const __bf16 *__restrict__ w3, const float *__restrict__ b3,
+                                         u32 wave, u32 tile) {
+    u32 lane = __lane_id(), r = lane & 31, h = lane >> 5;
+    const bf16x8 *wf = reinterpret_cast<const bf16x8 *>(w3) + lane;
+    f32x16 acc[2];
+#pragma unroll
+    for (int ft = 0; ft < 2; ft++)
+#pragma unroll
+        for (int j = 0; j < 16; j++) acc[ft][j] = 0.f;
+    bf16x8 wq[4][2];
+#pragma unroll
+    for (int d = 0; d < 4; d++)
+#pragma unroll
+        for (int ft = 0; ft < 2; ft++) wq[d][ft] = wf[(ft * 16 + d) * 64];
+    bf16x8 xn = *reinterpret_cast<const bf16x8 *>(Xt + (32 * wave + r) * PM_LD + 8 * h);
+#pragma unroll
+    for (int kk = 0; kk < 16; kk++) {
+        bf16x8 x = xn;
+        bf16x8 wc[2] = {wq[kk & 3][0], wq[kk & 3][1]};
+        if (kk + 4 < 16) {
+#pragma unroll
+            for (int ft = 0; ft < 2; ft++) wq[kk & 3][ft] = wf[(ft * 16 + kk + 4) * 64];
+        }
+        if (kk < 15) xn = *reinterpret_cast<const bf16x8 *>(Xt + (32 * wave + r) * PM_LD + 16 * (kk + 1) + 8 * h);
+#pragma unroll
+        for (int ft = 0; ft < 2; ft++) acc[ft] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wc[ft], x, acc[ft], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    __syncthreads();                                   // all waves are done with X: the logits may overwrite it
+#pragma unroll
+    for (int ft = 0; ft < 2; ft++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            u32 f0 = 32 * ft + 8 * q + 4 * h;
+            float4 bv = *reinterpret_cast<const float4 *>(b3 + f0);
+            float4 o = make_float4(acc[ft][4 * q + 0] + bv.x, acc[ft][4 * q + 1] + bv.y, acc[ft][4 * q + 2] + bv.z, acc[ft][4 * q + 3] + bv.w);
+            *reinterpret_cast<float4 *>(L + (PM_M * tile + 32 * wave + r) * PM_LL + f0) = o;
+        }
+}
+
+// The masked categorical sampler of the fused kernels (same draw, same order of additions as k_sample), two lanes per
+// game: lane pair (2g, 2g+1) takes cards 0..26 / 27..53 (half = 0 / 1), partner values through DPP.  In two parts, so
+// that a kernel with two networks reads a game's inputs once and samples once per network.
+
+// the pair partner's value (quad_perm [1,0,3,2]; DPP reads need the source lane active: never inside a select)
+__device__ __forceinline__ float pm_swap(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, true)); }
+__device__ __forceinline__ int pm_swap(int x) { return __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true); }
+
+struct PolicySampleIn {
+    u64 o, m, key;            // the game's observation word, its legal cards, its draw key
+    u32 played, mh;           // cards played so far in this game; the legality bits of this lane's cards
+    int last;                 // the last legal card
+};
+struct PolicyPick { int pk; float pp, sum, v54; };      // card, its exp(logit - max), the sum of those, the state value
+
+__device__ __forceinline__ PolicySampleIn policy_sample_inputs(const u64 *__restrict__ obs, const u64 *__restrict__ gkey, int64_t i, u32 half) {
+    PolicySampleIn in;
+    in.o = obs[i];
+    in.m = in.o & TAROK_OBS_MASK;
+    in.key = gkey[i];
+    in.played = (u32)(in.o >> TAROK_OBS_STEP_SHIFT) & 63u;
+    in.mh = (u32)(in.m >> (27 * half)) & 0x7FFFFFFu;
+    in.last = in.m ? 63 - __clzll(in.m) : 0;
+    return in;
+}
+
+// one draw from logits row gi of L: the candidate is whole on the game's half == 0 lane
+__device__ __forceinline__ PolicyPick policy_sample(const float *L, u32 gi, u32 half, const PolicySampleIn &in) {
+    float l[27];
+#pragma unroll
+    for (int c = 0; c < 27; c++) l[c] = L[gi * PM_LL + 27 * half + c];
+    float v54 = L[gi * PM_LL + 54];
+    const u32 mh = in.mh;
+    float mx = -3.0e38f;
+#pragma unroll
+    for (int c = 0; c < 27; c++) mx = ((mh >> c) & 1) ? fmaxf(mx, l[c]) : mx;
+    mx = fmaxf(mx, pm_swap(mx));
+#pragma unroll
+    for (int c = 0; c < 27; c++) l[c] = ((mh >> c) & 1) ? __expf(l[c] - mx) : 0.f;
+    // running sums in card order: the low half from 0, then the high half from the low half's total
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < 27; c++) s += l[c];
+    float s_sw = pm_swap(s);
+    float s_low = half ? s_sw : s;                         // sum over cards 0..26 (in both lanes)
+    float start = half ? s_low : 0.f;
+    float sum = start;
+#pragma unroll
+    for (int c = 0; c < 27; c++) sum += l[c];
+    float sum_sw = pm_swap(sum);
+    sum = half ? sum : sum_sw;                             // total over cards 0..53, from the high lane
+    u32 rr = rng32(in.key, 192u + in.played);
+    float u = ((float)(rr >> 8) + 0.5f) * (1.0f / 16777216.0f) * sum;
+    float acc = start, pe = 0.f;
+    int pickc = -1;
+#pragma unroll
+    for (int c = 0; c < 27; c++) {
+        bool legal = (mh >> c) & 1;
+        acc += l[c];
+        bool take = legal && pickc < 0 && acc > u;
+        pe = take ? l[c] : pe;
+        pickc = take ? c : pickc;
+    }
+    // rounding at the top end: the last legal card (its lane supplies the probability)
+    const int last = in.last;
+    float pl = 0.f;
+#pragma unroll
+    for (int c = 0; c < 27; c++) pl = (c + 27 * (int)half == last) ? l[c] : pl;
+    int pick_o = pm_swap(pickc);
+    float pe_o = pm_swap(pe), pl_o = pm_swap(pl);
+    PolicyPick p;
+    p.pk = pickc >= 0 ? pickc : (pick_o >= 0 ? pick_o + 27 : last);
+    p.pp = pickc >= 0 ? pe : (pick_o >= 0 ? pe_o : (last < 27 ? pl : pl_o));
+    p.sum = sum;
+    p.v54 = v54;
+    return p;
+}
+
+// The policy step of 128 * TILES games by a workgroup of 256 * TILES threads (tile t = waves 4t..4t+3 and rows 128t..
+// of X): the ONE forward and sampler of tarok_policy_mlp (TILES = 1) and of the three tarok_policy_step launches
+// (TILES = 2, which then need the sampled cards of their 256 games in LDS: act_s).  The feature words are built once
+// into ext; then, ONCE PER NETWORK, the activation buffer is expanded from ext and run through layers 1-3 and the
+// sampler (the logits of a pass overwrite the activations, and no second buffer fits in LDS); one block writes out.
+// NETS = 2 (tarok_policy_step_versus): nets[0] plays the seats of a game's seat set (seat_sets[i], or `seats` for every
+// game), nets[1] the others; both are evaluated for every game (the seat to move differs from lane to lane: nothing
+// wave-uniform to skip), the mover's network's candidate waits in the registers of the game's half == 0 lane.  Every
+// pass is the same code in the same order of accumulation, so a network's card, log-probability and value are the bits
+// of tarok_policy_mlp with its weights.  With NETS = 1 the loop and the selects fold away.
+// MIXED (tarok_policy_step_seats): a game whose seat to move is not in its seat set takes the Bot's card — k_policy's,
+// i.e. what tarok_step_random plays — and the log-probability 0; the network is evaluated for every game all the same.
+template <int TILES, int NETS = 1, bool MIXED = false>
 __device__ __forceinline__ void policy_body(
     int64_t n, const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23, const u64 *__restrict__ obs,
-    const u64 *__restrict__ gkey, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
-    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3,
-    const float *__restrict__ b3, uint8_t *__restrict__ action, float *__restrict__ logp, float *__restrict__ value,
-    uint4 *__restrict__ features_out, ulonglong2 *__restrict__ feature_words_out, u64 *__restrict__ stamps,
-    uint8_t *__restrict__ act_s, u32 **lds_after = nullptr /* the activation buffer: free once every thread has returned */,
-    u32 seats = 15, const uint8_t *__restrict__ seat_sets = nullptr) {
+    const u64 *__restrict__ gkey, const PolicyWeights (&nets)[NETS], uint8_t *__restrict__ action, float *__restrict__ logp,
+    float *__restrict__ value, uint4 *__restrict__ features_out, ulonglong2 *__restrict__ feature_words_out,
+    u64 *__restrict__ stamps, uint8_t *__restrict__ act_s,
+    u32 **lds_after = nullptr /* the activation buffer: free once every thread has returned */, u32 seats = 15,
+    const uint8_t *__restrict__ seat_sets = nullptr) {
     constexpr int GAMES = PM_M * TILES;
     u64 ts[7];
 #define PM_STAMP(k) if (stamps) ts[k] = __builtin_amdgcn_s_memtime();
@@ -1885,186 +2051,96 @@ __device__ __forceinline__ void policy_body(
     int64_t base = (int64_t)blockIdx.x * GAMES;
     u32 tid = threadIdx.x, wave4 = (tid >> 6) & 3, tile = tid >> 8;
     __bf16 *Xt = X + tile * PM_M * PM_LD;
+    float *L = reinterpret_cast<float *>(X);
     if (lds_after) *lds_after = reinterpret_cast<u32 *>(X);
     bf16x8 wq[4][2];
-    mlp_prefetch(wq, w1, wave4 * 2);           // lands while the features are built
-    // ---- the four 64-bit feature words of each game (same definition as k_observe)
+    mlp_prefetch(wq, nets[0].w1, wave4 * 2);   // lands while the features are built
     if (tid < GAMES) {
         int64_t i = base + tid < n ? base + tid : n - 1;
         Game g;
         load_game(g, s01, s23, i);
-        u32 seat = (g.leader + g.nt) & 3;
-        bool live = g.phase == TK_PHASE_PLAY;
-        u64 on_table = 0;
-        for (u32 j = 0; j < g.nt; j++) on_table |= 1ULL << ((g.trick >> (6 * j)) & 63);
-        u64 f1 = (u64)(1u << ((g.declarer - seat) & 3)) | ((u64)(1u << g.nt) << 4) | ((u64)((g.team >> seat) & 1) << 8) |
-                 ((u64)(has_king(g.contract) ? 1u : 0u) << 9);
-        u64 f2 = (has_king(g.contract) ? (u64)(1u << g.king) : 0) | ((u64)g.trick_no << 4);
-        ext[tid][0] = hand_of(g, seat) | ((u64)(1u << g.contract) << 54);
-        ext[tid][1] = (live ? legal_now(g) : 0) | (f1 << 54);
-        ext[tid][2] = on_table | (f2 << 54);
-        ext[tid][3] = (g.C & ~talon_unowned(g) & ~on_table) | ((u64)(live ? 1u : 0u) << 54);
+        policy_feature_words(g, ext[tid]);
         if (feature_words_out && base + tid < n) {
             feature_words_out[i * 2] = make_ulonglong2(ext[tid][0], ext[tid][1]);
             feature_words_out[i * 2 + 1] = make_ulonglong2(ext[tid][2], ext[tid][3]);
         }
     }
-    __syncthreads();
-    PM_STAMP(6)
-    // expand to bf16 0.0 / 1.0, one 16-byte chunk (8 features = one byte of a feature word) at a time.
-    // Two threads per game, thread parity p takes the odd / even bytes of the game's 32: ONE 32-byte
-    // LDS read per thread up front instead of a dependent byte read per chunk, and the pair's
-    // 16-byte stores fall into different banks.  (A 256-entry LDS table byte -> 8 bf16 was tried:
-    // no faster than the selects.)
-    {
-        u32 gme = tid >> 1, par = tid & 1;
-        const uint4 *row = reinterpret_cast<const uint4 *>(&ext[gme][0]);
-        uint4 r0 = row[0], r1 = row[1];
-        u32 wd[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            u32 chunk = 2 * j + par;                       // byte `chunk` of the row = byte (2j + par) & 3 of word j / 2
-            u32 byte = (wd[j >> 1] >> (8 * ((2 * (j & 1)) + par))) & 255u;
-            *reinterpret_cast<uint4 *>(X + gme * PM_LD + 8 * chunk) = tk_expand_byte(byte);
-        }
+    // the sampler's game (two lanes per game) and whether its seat to move is in its seat set
+    const u32 gi = tid >> 1, half = tid & 1;
+    const bool in_range = base + gi < n;
+    const int64_t i = in_range ? base + gi : n - 1;
+    auto in_set = [&](u64 o) {
+        u32 set = seat_sets ? seat_sets[i] : seats;
+        return ((set >> ((u32)(o >> TAROK_OBS_SEAT_SHIFT) & 3u)) & 1u) != 0;
+    };
+    PolicySampleIn in;
+    bool is_a = true;
+    if constexpr (NETS > 1) {                      // (the same for both passes)
+        in = policy_sample_inputs(obs, gkey, i, half);
+        is_a = in_set(in.o);
     }
-    if (features_out) {                                    // optional global copy: full 512-byte rows per 32 lanes
+    PolicyPick pick = {0, 0.f, 1.f, 0.f};          // the mover's network's candidate
+    auto pass = [&](int net) __attribute__((always_inline)) {
+        PolicyWeights w = nets[0];
+        if constexpr (NETS > 1) { if (net) w = nets[1]; }
+        // (the feature words are in ext; pass 1: every lane has read its logits of pass 0 before the activations go
+        // back over them)
         __syncthreads();
+        PM_STAMP(6)
+        if (net) mlp_prefetch(wq, w.w1, wave4 * 2);
+        policy_expand(X, ext, tid);
+        if (features_out) {                                    // optional global copy: full 512-byte rows per 32 lanes
+            __syncthreads();
 #pragma unroll
-        for (int it = 0; it < 16; it++) {
-            u32 gme = it * (8 * TILES) + (tid >> 5), chunk = tid & 31;
-            if (base + gme < n) features_out[(base + gme) * 32 + chunk] = *reinterpret_cast<const uint4 *>(X + gme * PM_LD + 8 * chunk);
-        }
-    }
-    __syncthreads();
-    PM_STAMP(1)
-    mlp_hidden(Xt, w1, b1, wq, wave4);
-    PM_STAMP(2)
-    mlp_prefetch(wq, w2, wave4 * 2);
-    mlp_hidden(Xt, w2, b2, wq, wave4);
-    PM_STAMP(3)
-    // ---- layer 3: 64 outputs; wave w takes games [32w, 32w+32), both 32-feature tiles; f32
-    // logits to LDS [128][68] over the activation buffer
-    float *L = reinterpret_cast<float *>(X);
-    {
-        u32 lane = __lane_id(), wave = wave4, r = lane & 31, h = lane >> 5;
-        const bf16x8 *wf = reinterpret_cast<const bf16x8 *>(w3) + lane;
-        f32x16 acc[2];
-#pragma unroll
-        for (int ft = 0; ft < 2; ft++)
-#pragma unroll
-            for (int j = 0; j < 16; j++) acc[ft][j] = 0.f;
-        bf16x8 wq[4][2];
-#pragma unroll
-        for (int d = 0; d < 4; d++)
-#pragma unroll
-            for (int ft = 0; ft < 2; ft++) wq[d][ft] = wf[(ft * 16 + d) * 64];
-        bf16x8 xn = *reinterpret_cast<const bf16x8 *>(Xt + (32 * wave + r) * PM_LD + 8 * h);
-#pragma unroll
-        for (int kk = 0; kk < 16; kk++) {
-            bf16x8 x = xn;
-            bf16x8 wc[2] = {wq[kk & 3][0], wq[kk & 3][1]};
-            if (kk + 4 < 16) {
-#pragma unroll
-                for (int ft = 0; ft < 2; ft++) wq[kk & 3][ft] = wf[(ft * 16 + kk + 4) * 64];
+            for (int it = 0; it < 16; it++) {
+                u32 gme = it * (8 * TILES) + (tid >> 5), chunk = tid & 31;
+                if (base + gme < n) features_out[(base + gme) * 32 + chunk] = *reinterpret_cast<const uint4 *>(X + gme * PM_LD + 8 * chunk);
             }
-            if (kk < 15) xn = *reinterpret_cast<const bf16x8 *>(Xt + (32 * wave + r) * PM_LD + 16 * (kk + 1) + 8 * h);
-#pragma unroll
-            for (int ft = 0; ft < 2; ft++) acc[ft] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wc[ft], x, acc[ft], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
         }
-        __syncthreads();                               // all waves are done with X: the logits may overwrite it
-#pragma unroll
-        for (int ft = 0; ft < 2; ft++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                u32 f0 = 32 * ft + 8 * q + 4 * h;
-                float4 bv = *reinterpret_cast<const float4 *>(b3 + f0);
-                float4 o = make_float4(acc[ft][4 * q + 0] + bv.x, acc[ft][4 * q + 1] + bv.y, acc[ft][4 * q + 2] + bv.z, acc[ft][4 * q + 3] + bv.w);
-                *reinterpret_cast<float4 *>(L + (PM_M * tile + 32 * wave + r) * PM_LL + f0) = o;
-            }
-    }
-    __syncthreads();
-    PM_STAMP(4)
-    if (stamps && tid == 0) {
-        for (int k = 0; k < 5; k++) stamps[blockIdx.x * 8 + k] = ts[k];
-        stamps[blockIdx.x * 8 + 6] = ts[6];
-    }
-    // ---- masked categorical sample (same draw, same order of additions as k_sample), two lanes
-    // per game: lane pair (2g, 2g+1) takes cards 0..26 / 27..53, partner values through DPP
-    {
-#define PM_SWAP_F(x) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, true))   /* quad_perm [1,0,3,2] */
-#define PM_SWAP_I(x) __builtin_amdgcn_update_dpp(0, (int)(x), 0xB1, 0xF, 0xF, true)
-        u32 gi = tid >> 1, half = tid & 1;
-        bool in_range = base + gi < n;
-        int64_t i = in_range ? base + gi : n - 1;
-        float l[27];
-#pragma unroll
-        for (int c = 0; c < 27; c++) l[c] = L[gi * PM_LL + 27 * half + c];
-        float v54 = L[gi * PM_LL + 54];
-        u64 o = obs[i];
-        u64 m = o & TAROK_OBS_MASK;
-        u32 mh = (u32)(m >> (27 * half)) & 0x7FFFFFFu;         // the legality bits of this lane's cards
-        float mx = -3.0e38f;
-#pragma unroll
-        for (int c = 0; c < 27; c++) mx = ((mh >> c) & 1) ? fmaxf(mx, l[c]) : mx;
-        mx = fmaxf(mx, PM_SWAP_F(mx));
-#pragma unroll
-        for (int c = 0; c < 27; c++) l[c] = ((mh >> c) & 1) ? __expf(l[c] - mx) : 0.f;
-        // running sums in card order: the low half from 0, then the high half from the low half's total
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < 27; c++) s += l[c];
-        float s_sw = PM_SWAP_F(s);                             // (DPP reads need the source lane active: never inside a select)
-        float s_low = half ? s_sw : s;                         // sum over cards 0..26 (in both lanes)
-        float start = half ? s_low : 0.f;
-        float sum = start;
-#pragma unroll
-        for (int c = 0; c < 27; c++) sum += l[c];
-        float sum_sw = PM_SWAP_F(sum);
-        sum = half ? sum : sum_sw;                             // total over cards 0..53, from the high lane
-        const u64 key = gkey[i];
-        const u32 played = (u32)(o >> TAROK_OBS_STEP_SHIFT) & 63u;      // cards played so far in this game
-        u32 rr = rng32(key, 192u + played);
-        float u = ((float)(rr >> 8) + 0.5f) * (1.0f / 16777216.0f) * sum;
-        float acc = start, pe = 0.f;
-        int pickc = -1;
-#pragma unroll
-        for (int c = 0; c < 27; c++) {
-            bool legal = (mh >> c) & 1;
-            acc += l[c];
-            bool take = legal && pickc < 0 && acc > u;
-            pe = take ? l[c] : pe;
-            pickc = take ? c : pickc;
+        __syncthreads();
+        PM_STAMP(1)
+        mlp_hidden(Xt, w.w1, w.b1, wq, wave4);
+        PM_STAMP(2)
+        mlp_prefetch(wq, w.w2, wave4 * 2);
+        mlp_hidden(Xt, w.w2, w.b2, wq, wave4);
+        PM_STAMP(3)
+        mlp_head(Xt, L, w.w3, w.b3, wave4, tile);
+        __syncthreads();
+        PM_STAMP(4)
+        if (stamps && tid == 0) {
+            for (int k = 0; k < 5; k++) stamps[blockIdx.x * 8 + k] = ts[k];
+            stamps[blockIdx.x * 8 + 6] = ts[6];
         }
-        // rounding at the top end: the last legal card (its lane supplies the probability)
-        int last = m ? 63 - __clzll(m) : 0;
-        float pl = 0.f;
-#pragma unroll
-        for (int c = 0; c < 27; c++) pl = (c + 27 * (int)half == last) ? l[c] : pl;
-        int pick_o = PM_SWAP_I(pickc);
-        float pe_o = PM_SWAP_F(pe), pl_o = PM_SWAP_F(pl);
-        if (half == 0 && in_range) {
-            int pk = pickc >= 0 ? pickc : (pick_o >= 0 ? pick_o + 27 : last);
-            float pp = pickc >= 0 ? pe : (pick_o >= 0 ? pe_o : (last < 27 ? pl : pl_o));
-            if (value) value[i] = v54;
-            bool bot = false;
-            if (MIXED) {
-                u32 set = seat_sets ? seat_sets[i] : seats;
-                bot = ((set >> ((u32)(o >> TAROK_OBS_SEAT_SHIFT) & 3u)) & 1u) == 0;
-                if (bot && m) pk = (int)policy_action(key, played, m);
-            }
-            if (!m) { action[i] = 255; if (logp) logp[i] = 0.f; }
-            else {
-                action[i] = (uint8_t)pk;
-                if (logp) logp[i] = (MIXED && bot) ? 0.f : __logf(pp / sum);
-            }
-            if (act_s) act_s[gi] = m ? (uint8_t)pk : (uint8_t)255;
-        }
-#undef PM_SWAP_F
-#undef PM_SWAP_I
-        if (stamps && tid == 0) stamps[blockIdx.x * 8 + 5] = __builtin_amdgcn_s_memtime();
+        if constexpr (NETS == 1) in = policy_sample_inputs(obs, gkey, i, half);
+        PolicyPick c = policy_sample(L, gi, half, in);
+        const bool mine = NETS == 1 || (net == 0) == is_a;
+        pick.pk = mine ? c.pk : pick.pk;
+        pick.pp = mine ? c.pp : pick.pp;
+        pick.sum = mine ? c.sum : pick.sum;
+        pick.v54 = mine ? c.v54 : pick.v54;
+    };
+    if constexpr (NETS == 1) pass(0);              // (no loop at all: nothing of the sampler is hoisted over the layers)
+    else {
+#pragma unroll 1
+        for (int net = 0; net < NETS; net++) pass(net);
     }
+    if (half == 0 && in_range) {
+        const u64 m = in.m;
+        if (value) value[i] = pick.v54;
+        bool bot = false;
+        if constexpr (MIXED) {
+            bot = !in_set(in.o);
+            if (bot && m) pick.pk = (int)policy_action(in.key, in.played, m);
+        }
+        if (!m) { action[i] = 255; if (logp) logp[i] = 0.f; }
+        else {
+            action[i] = (uint8_t)pick.pk;
+            if (logp) logp[i] = bot ? 0.f : __logf(pick.pp / pick.sum);
+        }
+        if (act_s) act_s[gi] = m ? (uint8_t)pick.pk : (uint8_t)255;
+    }
+    if (stamps && tid == 0) stamps[blockIdx.x * 8 + 5] = __builtin_amdgcn_s_memtime();
+#undef PM_STAMP
 }
 
 __global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_mlp(
@@ -2074,8 +2150,8 @@ __global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_mlp(
     const float *__restrict__ b3, uint8_t *__restrict__ action, float *__restrict__ logp, float *__restrict__ value,
     uint4 *__restrict__ features_out, ulonglong2 *__restrict__ feature_words_out, u64 *__restrict__ stamps) {
     TK_VGPR_TOP(256, 255);
-    policy_body<1>(n, s01, s23, obs, gkey, w1, b1, w2, b2, w3, b3, action, logp, value, features_out, feature_words_out, stamps,
-                   nullptr);
+    const PolicyWeights nets[1] = {{w1, b1, w2, b2, w3, b3}};
+    policy_body<1>(n, s01, s23, obs, gkey, nets, action, logp, value, features_out, feature_words_out, stamps, nullptr);
 }
 
 // tarok_policy_step: tarok_policy_mlp and tarok_step in ONE launch.  A play workgroup (512
@@ -2083,16 +2159,25 @@ __global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_mlp(
 // as two 128-game tiles side by side, leaves the sampled cards in LDS and then runs the step
 // kernel's play role on them (threads 0..255; same refill lists, same launch-parity protocol as
 // k_play); the workgroups after the play groups run the refill role.
-__global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_step(
-    int64_t n, u64 seed, u64 offset, int mix, int flags, u32 play_groups, u32 *epoch, u32 fan,
-    const u64 *__restrict__ obs_in, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
-    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3,
-    const float *__restrict__ b3, uint8_t *__restrict__ action, float *__restrict__ logp, float *__restrict__ value,
-    ulonglong2 *__restrict__ feature_words_out, int16_t *__restrict__ reward, uint8_t *__restrict__ done,
-    uint16_t *__restrict__ trick, u64 *__restrict__ obs_out, uint8_t *__restrict__ hist,
-    ulonglong2 *__restrict__ s01, ulonglong2 *__restrict__ s23, Aux *aux, Counters *__restrict__ cnt,
-    u64 *__restrict__ gkey, u64 *rlist, u32 *rcount) {
-    TK_VGPR_TOP(256, 255);
+// tarok_policy_step_seats (MIXED) and tarok_policy_step_versus (NETS = 2) are the same launch around another
+// instantiation of policy_body; what they take more comes LAST in their kernels' parameters (the set and the per-game
+// sets, then the second network's six pointers): the preloaded kernel arguments are the same for the three.
+#define TK_POLICY_STEP_ARGS                                                                                                       \
+    int64_t n, u64 seed, u64 offset, int mix, int flags, u32 play_groups, u32 *epoch, u32 fan,                                    \
+        const u64 *__restrict__ obs_in, const __bf16 *__restrict__ w1, const float *__restrict__ b1,                              \
+        const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3,                               \
+        const float *__restrict__ b3, uint8_t *__restrict__ action, float *__restrict__ logp, float *__restrict__ value,          \
+        ulonglong2 *__restrict__ feature_words_out, int16_t *__restrict__ reward, uint8_t *__restrict__ done,                     \
+        uint16_t *__restrict__ trick, u64 *__restrict__ obs_out, uint8_t *__restrict__ hist,                                      \
+        ulonglong2 *__restrict__ s01, ulonglong2 *__restrict__ s23, Aux *aux, Counters *__restrict__ cnt,                         \
+        u64 *__restrict__ gkey, u64 *rlist, u32 *rcount
+#define TK_POLICY_STEP_NAMES                                                                                                      \
+    n, seed, offset, mix, flags, play_groups, epoch, fan, obs_in, w1, b1, w2, b2, w3, b3, action, logp, value,                    \
+        feature_words_out, reward, done, trick, obs_out, hist, s01, s23, aux, cnt, gkey, rlist, rcount
+
+template <int NETS, bool MIXED>
+__device__ __forceinline__ void policy_step_shell(TK_POLICY_STEP_ARGS, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                  const PolicyWeights &second) {
     TkCount count = launch_count<1>(epoch, play_groups);          // (in flight under the policy's first loads)
     if (blockIdx.x >= play_groups) {
         refill_role<false>(blockIdx.x - play_groups, threadIdx.x, 2 * TK_BLOCK, seed, offset, mix, play_groups, count, epoch, fan, false, aux, rlist, rcount, nullptr);
@@ -2100,8 +2185,10 @@ __global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_
     }
     __shared__ uint8_t act_s[2 * PM_M];
     u32 *lds = nullptr;
-    policy_body<2>(n, s01, s23, obs_in, gkey, w1, b1, w2, b2, w3, b3, action, logp, value, nullptr, feature_words_out, nullptr,
-                   act_s, &lds);
+    PolicyWeights nets[NETS] = {{w1, b1, w2, b2, w3, b3}};
+    if constexpr (NETS > 1) nets[1] = second;
+    policy_body<2, NETS, MIXED>(n, s01, s23, obs_in, gkey, nets, action, logp, value, nullptr, feature_words_out, nullptr, act_s, &lds,
+                                seats, seat_sets);
     __syncthreads();                          // (the policy's LDS is free from here on: the step's scoring list goes there)
     u32 tid = threadIdx.x;
     step_role<false, false>(blockIdx.x, tid & (TK_BLOCK - 1), tid < TK_BLOCK, act_s[tid & (TK_BLOCK - 1)], false, n, seed, offset, mix, flags,
@@ -2109,249 +2196,23 @@ __global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_
                            reinterpret_cast<u32 (*)[TK_BLOCK]>(lds));
 }
 
-// tarok_policy_step_seats: the same launch with the network on the seats of a 4-bit set and the Bot on the others
-// (policy_body<2, true>).  Written out beside k_policy_step, not as a shared body: that kernel's code stays as it was,
-// instruction for instruction.  The set and the per-game sets come LAST: the preloaded kernel arguments are the same.
+__global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_step(TK_POLICY_STEP_ARGS) {
+    TK_VGPR_TOP(256, 255);
+    policy_step_shell<1, false>(TK_POLICY_STEP_NAMES, 15, nullptr, PolicyWeights{});
+}
+
 __global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_step_seats(
-    int64_t n, u64 seed, u64 offset, int mix, int flags, u32 play_groups, u32 *epoch, u32 fan,
-    const u64 *__restrict__ obs_in, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
-    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3,
-    const float *__restrict__ b3, uint8_t *__restrict__ action, float *__restrict__ logp, float *__restrict__ value,
-    ulonglong2 *__restrict__ feature_words_out, int16_t *__restrict__ reward, uint8_t *__restrict__ done,
-    uint16_t *__restrict__ trick, u64 *__restrict__ obs_out, uint8_t *__restrict__ hist,
-    ulonglong2 *__restrict__ s01, ulonglong2 *__restrict__ s23, Aux *aux, Counters *__restrict__ cnt,
-    u64 *__restrict__ gkey, u64 *rlist, u32 *rcount, u32 seats, const uint8_t *__restrict__ seat_sets) {
+    TK_POLICY_STEP_ARGS, u32 seats, const uint8_t *__restrict__ seat_sets) {
     TK_VGPR_TOP(256, 255);
-    TkCount count = launch_count<1>(epoch, play_groups);
-    if (blockIdx.x >= play_groups) {
-        refill_role<false>(blockIdx.x - play_groups, threadIdx.x, 2 * TK_BLOCK, seed, offset, mix, play_groups, count, epoch, fan, false, aux, rlist, rcount, nullptr);
-        return;
-    }
-    __shared__ uint8_t act_s[2 * PM_M];
-    u32 *lds = nullptr;
-    policy_body<2, true>(n, s01, s23, obs_in, gkey, w1, b1, w2, b2, w3, b3, action, logp, value, nullptr, feature_words_out, nullptr,
-                         act_s, &lds, seats, seat_sets);
-    __syncthreads();
-    u32 tid = threadIdx.x;
-    step_role<false, false>(blockIdx.x, tid & (TK_BLOCK - 1), tid < TK_BLOCK, act_s[tid & (TK_BLOCK - 1)], false, n, seed, offset, mix, flags,
-                           count, epoch, play_groups, fan, nullptr, nullptr, reward, done, trick, obs_out, hist, s01, s23, aux, cnt, gkey, rlist, rcount, nullptr,
-                           reinterpret_cast<u32 (*)[TK_BLOCK]>(lds));
+    policy_step_shell<1, true>(TK_POLICY_STEP_NAMES, seats, seat_sets, PolicyWeights{});
 }
 
-// tarok_policy_step_versus: two networks at one table.  A second body beside policy_body<2> (whose instantiations stay
-// as they compile): the feature words are built once into ext, then the activation buffer is expanded from ext and
-// run through layers 1-3 and the sampler ONCE PER NETWORK (pass 0: A, pass 1: B; the logits of a pass overwrite the
-// activations, and no second buffer fits in LDS).  Each pass is policy_body's code — mlp_prefetch, mlp_hidden, the
-// same layer 3 and sampler in the same order of accumulation — so a network's card, log-probability and value are the
-// bits of tarok_policy_mlp with its weights; a game's candidate of pass A waits in the registers of its half == 0
-// lane, and the seat to move (obs bits 55:54) against the game's seat set picks the one that is written and played.
-__device__ __forceinline__ void policy_versus_body(
-    int64_t n, const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23, const u64 *__restrict__ obs,
-    const u64 *__restrict__ gkey, const __bf16 *__restrict__ w1a, const float *__restrict__ b1a, const __bf16 *__restrict__ w2a,
-    const float *__restrict__ b2a, const __bf16 *__restrict__ w3a, const float *__restrict__ b3a,
-    const __bf16 *__restrict__ w1b, const float *__restrict__ b1b, const __bf16 *__restrict__ w2b,
-    const float *__restrict__ b2b, const __bf16 *__restrict__ w3b, const float *__restrict__ b3b, uint8_t *__restrict__ action,
-    float *__restrict__ logp, float *__restrict__ value, ulonglong2 *__restrict__ feature_words_out,
-    uint8_t *__restrict__ act_s, u32 **lds_after, u32 seats, const uint8_t *__restrict__ seat_sets) {
-    constexpr int GAMES = PM_M * 2;
-    __shared__ __attribute__((aligned(16))) __bf16 X[GAMES * PM_LD];
-    __shared__ u64 ext[GAMES][4];
-    int64_t base = (int64_t)blockIdx.x * GAMES;
-    u32 tid = threadIdx.x, wave4 = (tid >> 6) & 3, tile = tid >> 8;
-    __bf16 *Xt = X + tile * PM_M * PM_LD;
-    *lds_after = reinterpret_cast<u32 *>(X);
-    bf16x8 wq[4][2];
-    mlp_prefetch(wq, w1a, wave4 * 2);          // lands while the features are built
-    // ---- the four 64-bit feature words of each game (policy_body's; kept in ext for both passes)
-    if (tid < GAMES) {
-        int64_t i = base + tid < n ? base + tid : n - 1;
-        Game g;
-        load_game(g, s01, s23, i);
-        u32 seat = (g.leader + g.nt) & 3;
-        bool live = g.phase == TK_PHASE_PLAY;
-        u64 on_table = 0;
-        for (u32 j = 0; j < g.nt; j++) on_table |= 1ULL << ((g.trick >> (6 * j)) & 63);
-        u64 f1 = (u64)(1u << ((g.declarer - seat) & 3)) | ((u64)(1u << g.nt) << 4) | ((u64)((g.team >> seat) & 1) << 8) |
-                 ((u64)(has_king(g.contract) ? 1u : 0u) << 9);
-        u64 f2 = (has_king(g.contract) ? (u64)(1u << g.king) : 0) | ((u64)g.trick_no << 4);
-        ext[tid][0] = hand_of(g, seat) | ((u64)(1u << g.contract) << 54);
-        ext[tid][1] = (live ? legal_now(g) : 0) | (f1 << 54);
-        ext[tid][2] = on_table | (f2 << 54);
-        ext[tid][3] = (g.C & ~talon_unowned(g) & ~on_table) | ((u64)(live ? 1u : 0u) << 54);
-        if (feature_words_out && base + tid < n) {
-            feature_words_out[i * 2] = make_ulonglong2(ext[tid][0], ext[tid][1]);
-            feature_words_out[i * 2 + 1] = make_ulonglong2(ext[tid][2], ext[tid][3]);
-        }
-    }
-    // the sampler's per-game inputs, the same for both passes (two lanes per game)
-    const u32 gi = tid >> 1, half = tid & 1;
-    const bool in_range = base + gi < n;
-    const int64_t i = in_range ? base + gi : n - 1;
-    const u64 o = obs[i];
-    const u64 m = o & TAROK_OBS_MASK;
-    const u64 key = gkey[i];
-    const u32 played = (u32)(o >> TAROK_OBS_STEP_SHIFT) & 63u;
-    const u32 set = seat_sets ? seat_sets[i] : seats;
-    const bool is_a = ((set >> ((u32)(o >> TAROK_OBS_SEAT_SHIFT) & 3u)) & 1u) != 0;
-    int pk = 0;                                    // the mover's network's candidate (held by the game's half == 0 lane)
-    float pp = 0.f, psum = 1.f, pv = 0.f;
-#pragma unroll 1
-    for (int net = 0; net < 2; net++) {
-        const bool mine = (net == 0) == is_a;
-        const __bf16 *w1 = net ? w1b : w1a, *w2 = net ? w2b : w2a, *w3 = net ? w3b : w3a;
-        const float *b1 = net ? b1b : b1a, *b2 = net ? b2b : b2a, *b3 = net ? b3b : b3a;
-        // (pass 1: every lane has read its logits of pass 0 before the activations go back over them)
-        __syncthreads();
-        if (net) mlp_prefetch(wq, w1, wave4 * 2);
-        {   // expand ext to bf16 0.0 / 1.0 (policy_body's expansion)
-            u32 gme = tid >> 1, par = tid & 1;
-            const uint4 *row = reinterpret_cast<const uint4 *>(&ext[gme][0]);
-            uint4 r0 = row[0], r1 = row[1];
-            u32 wd[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-#pragma unroll
-            for (int j = 0; j < 16; j++) {
-                u32 chunk = 2 * j + par;
-                u32 byte = (wd[j >> 1] >> (8 * ((2 * (j & 1)) + par))) & 255u;
-                *reinterpret_cast<uint4 *>(X + gme * PM_LD + 8 * chunk) = tk_expand_byte(byte);
-            }
-        }
-        __syncthreads();
-        mlp_hidden(Xt, w1, b1, wq, wave4);
-        mlp_prefetch(wq, w2, wave4 * 2);
-        mlp_hidden(Xt, w2, b2, wq, wave4);
-        // ---- layer 3 (policy_body's): f32 logits to LDS [256][68] over the activation buffer
-        float *L = reinterpret_cast<float *>(X);
-        {
-            u32 lane = __lane_id(), wave = wave4, r = lane & 31, h = lane >> 5;
-            const bf16x8 *wf = reinterpret_cast<const bf16x8 *>(w3) + lane;
-            f32x16 acc[2];
-#pragma unroll
-            for (int ft = 0; ft < 2; ft++)
-#pragma unroll
-                for (int j = 0; j < 16; j++) acc[ft][j] = 0.f;
-            bf16x8 wq[4][2];
-#pragma unroll
-            for (int d = 0; d < 4; d++)
-#pragma unroll
-                for (int ft = 0; ft < 2; ft++) wq[d][ft] = wf[(ft * 16 + d) * 64];
-            bf16x8 xn = *reinterpret_cast<const bf16x8 *>(Xt + (32 * wave + r) * PM_LD + 8 * h);
-#pragma unroll
-            for (int kk = 0; kk < 16; kk++) {
-                bf16x8 x = xn;
-                bf16x8 wc[2] = {wq[kk & 3][0], wq[kk & 3][1]};
-                if (kk + 4 < 16) {
-#pragma unroll
-                    for (int ft = 0; ft < 2; ft++) wq[kk & 3][ft] = wf[(ft * 16 + kk + 4) * 64];
-                }
-                if (kk < 15) xn = *reinterpret_cast<const bf16x8 *>(Xt + (32 * wave + r) * PM_LD + 16 * (kk + 1) + 8 * h);
-#pragma unroll
-                for (int ft = 0; ft < 2; ft++) acc[ft] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wc[ft], x, acc[ft], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            __syncthreads();                           // all waves are done with X: the logits may overwrite it
-#pragma unroll
-            for (int ft = 0; ft < 2; ft++)
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    u32 f0 = 32 * ft + 8 * q + 4 * h;
-                    float4 bv = *reinterpret_cast<const float4 *>(b3 + f0);
-                    float4 ov = make_float4(acc[ft][4 * q + 0] + bv.x, acc[ft][4 * q + 1] + bv.y, acc[ft][4 * q + 2] + bv.z, acc[ft][4 * q + 3] + bv.w);
-                    *reinterpret_cast<float4 *>(L + (PM_M * tile + 32 * wave + r) * PM_LL + f0) = ov;
-                }
-        }
-        __syncthreads();
-        // ---- masked categorical sample (policy_body's: same draw, same order of additions), two lanes per game
-        {
-#define PM_SWAP_F(x) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, true))   /* quad_perm [1,0,3,2] */
-#define PM_SWAP_I(x) __builtin_amdgcn_update_dpp(0, (int)(x), 0xB1, 0xF, 0xF, true)
-            float l[27];
-#pragma unroll
-            for (int c = 0; c < 27; c++) l[c] = L[gi * PM_LL + 27 * half + c];
-            float v54 = L[gi * PM_LL + 54];
-            u32 mh = (u32)(m >> (27 * half)) & 0x7FFFFFFu;
-            float mx = -3.0e38f;
-#pragma unroll
-            for (int c = 0; c < 27; c++) mx = ((mh >> c) & 1) ? fmaxf(mx, l[c]) : mx;
-            mx = fmaxf(mx, PM_SWAP_F(mx));
-#pragma unroll
-            for (int c = 0; c < 27; c++) l[c] = ((mh >> c) & 1) ? __expf(l[c] - mx) : 0.f;
-            float s = 0.f;
-#pragma unroll
-            for (int c = 0; c < 27; c++) s += l[c];
-            float s_sw = PM_SWAP_F(s);                         // (DPP reads need the source lane active: never inside a select)
-            float s_low = half ? s_sw : s;
-            float start = half ? s_low : 0.f;
-            float sum = start;
-#pragma unroll
-            for (int c = 0; c < 27; c++) sum += l[c];
-            float sum_sw = PM_SWAP_F(sum);
-            sum = half ? sum : sum_sw;
-            u32 rr = rng32(key, 192u + played);
-            float u = ((float)(rr >> 8) + 0.5f) * (1.0f / 16777216.0f) * sum;
-            float acc = start, pe = 0.f;
-            int pickc = -1;
-#pragma unroll
-            for (int c = 0; c < 27; c++) {
-                bool legal = (mh >> c) & 1;
-                acc += l[c];
-                bool take = legal && pickc < 0 && acc > u;
-                pe = take ? l[c] : pe;
-                pickc = take ? c : pickc;
-            }
-            int last = m ? 63 - __clzll(m) : 0;
-            float pl = 0.f;
-#pragma unroll
-            for (int c = 0; c < 27; c++) pl = (c + 27 * (int)half == last) ? l[c] : pl;
-            int pick_o = PM_SWAP_I(pickc);
-            float pe_o = PM_SWAP_F(pe), pl_o = PM_SWAP_F(pl);
-            int pk_n = pickc >= 0 ? pickc : (pick_o >= 0 ? pick_o + 27 : last);
-            float pp_n = pickc >= 0 ? pe : (pick_o >= 0 ? pe_o : (last < 27 ? pl : pl_o));
-            pk = mine ? pk_n : pk;
-            pp = mine ? pp_n : pp;
-            psum = mine ? sum : psum;
-            pv = mine ? v54 : pv;
-#undef PM_SWAP_F
-#undef PM_SWAP_I
-        }
-    }
-    if (half == 0 && in_range) {
-        if (value) value[i] = pv;
-        if (!m) { action[i] = 255; if (logp) logp[i] = 0.f; }
-        else {
-            action[i] = (uint8_t)pk;
-            if (logp) logp[i] = __logf(pp / psum);
-        }
-        act_s[gi] = m ? (uint8_t)pk : (uint8_t)255;
-    }
-}
-
-// (the twelve weight pointers, the set and the per-game sets come LAST: the preloaded kernel arguments are its siblings')
 __global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_step_versus(
-    int64_t n, u64 seed, u64 offset, int mix, int flags, u32 play_groups, u32 *epoch, u32 fan,
-    const u64 *__restrict__ obs_in, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
-    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3,
-    const float *__restrict__ b3, uint8_t *__restrict__ action, float *__restrict__ logp, float *__restrict__ value,
-    ulonglong2 *__restrict__ feature_words_out, int16_t *__restrict__ reward, uint8_t *__restrict__ done,
-    uint16_t *__restrict__ trick, u64 *__restrict__ obs_out, uint8_t *__restrict__ hist,
-    ulonglong2 *__restrict__ s01, ulonglong2 *__restrict__ s23, Aux *aux, Counters *__restrict__ cnt,
-    u64 *__restrict__ gkey, u64 *rlist, u32 *rcount, u32 seats, const uint8_t *__restrict__ seat_sets,
-    const __bf16 *__restrict__ v1, const float *__restrict__ c1, const __bf16 *__restrict__ v2,
-    const float *__restrict__ c2, const __bf16 *__restrict__ v3, const float *__restrict__ c3) {
+    TK_POLICY_STEP_ARGS, u32 seats, const uint8_t *__restrict__ seat_sets, const __bf16 *__restrict__ v1,
+    const float *__restrict__ c1, const __bf16 *__restrict__ v2, const float *__restrict__ c2, const __bf16 *__restrict__ v3,
+    const float *__restrict__ c3) {
     TK_VGPR_TOP(256, 255);
-    TkCount count = launch_count<1>(epoch, play_groups);
-    if (blockIdx.x >= play_groups) {
-        refill_role<false>(blockIdx.x - play_groups, threadIdx.x, 2 * TK_BLOCK, seed, offset, mix, play_groups, count, epoch, fan, false, aux, rlist, rcount, nullptr);
-        return;
-    }
-    __shared__ uint8_t act_s[2 * PM_M];
-    u32 *lds = nullptr;
-    policy_versus_body(n, s01, s23, obs_in, gkey, w1, b1, w2, b2, w3, b3, v1, c1, v2, c2, v3, c3, action, logp, value, feature_words_out, act_s, &lds,
-                       seats, seat_sets);
-    __syncthreads();
-    u32 tid = threadIdx.x;
-    step_role<false, false>(blockIdx.x, tid & (TK_BLOCK - 1), tid < TK_BLOCK, act_s[tid & (TK_BLOCK - 1)], false, n, seed, offset, mix, flags,
-                           count, epoch, play_groups, fan, nullptr, nullptr, reward, done, trick, obs_out, hist, s01, s23, aux, cnt, gkey, rlist, rcount, nullptr,
-                           reinterpret_cast<u32 (*)[TK_BLOCK]>(lds));
+    policy_step_shell<2, false>(TK_POLICY_STEP_NAMES, seats, seat_sets, PolicyWeights{v1, c1, v2, c2, v3, c3});
 }
 
 // ---------------------------------------------------------------------------
@@ -3019,22 +2880,38 @@ int tarok_policy_mlp(tarok_env *e, const void *w1, const float *b1, const void *
     return TAROK_OK;
 }
 
-int tarok_policy_step(tarok_env *e, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
-                      const float *b3, const uint64_t *obs, uint8_t *action_out, float *logp_out, float *value_out,
-                      uint64_t *feature_words_out, int16_t *reward_out, uint8_t *done_out, uint16_t *trick_out,
-                      uint64_t *obs_out, int flags, void *stream) {
-    if (!e || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !obs || !action_out || !obs_out) return TAROK_EINVAL;
+// The launch of the three policy-step kinds (0: k_policy_step, 1: k_policy_step_seats, 2: k_policy_step_versus), the
+// arguments checked by the caller: one grid (the play groups, then their refill workgroups), one argument list.
+static int launch_policy_step(tarok_env *e, int kind, u32 seats, const uint8_t *seat_sets, const PolicyWeights &a,
+                              const PolicyWeights &b, const uint64_t *obs, uint8_t *action_out, float *logp_out, float *value_out,
+                              uint64_t *feature_words_out, int16_t *reward_out, uint8_t *done_out, uint16_t *trick_out,
+                              uint64_t *obs_out, int flags, void *stream) {
     HIPCHK(hipSetDevice(e->device));
     u32 groups = (u32)((e->n + TK_BLOCK - 1) / TK_BLOCK);
     u32 fan = e->refill_fan;
     dim3 grid(groups + (groups + fan - 1) / fan);
     e->launched = 1;
-    hipLaunchKernelGGL(k_policy_step, grid, dim3(2 * TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, e->mix, flags,
-                       groups, e->epoch, fan, (const u64 *)obs, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3,
-                       action_out, logp_out, value_out, (ulonglong2 *)feature_words_out, reward_out, done_out, trick_out,
-                       (u64 *)obs_out, e->hist, e->s01, e->s23, e->aux, e->cnt, e->gkey, e->rlist, e->rcount);
+#define TK_LAUNCH_POLICY_STEP(K, ...)                                                                                      \
+    hipLaunchKernelGGL(K, grid, dim3(2 * TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, e->mix, flags, groups,  \
+                       e->epoch, fan, (const u64 *)obs, a.w1, a.b1, a.w2, a.b2, a.w3, a.b3, action_out, logp_out, value_out,  \
+                       (ulonglong2 *)feature_words_out, reward_out, done_out, trick_out, (u64 *)obs_out, e->hist, e->s01,     \
+                       e->s23, e->aux, e->cnt, e->gkey, e->rlist, e->rcount, ##__VA_ARGS__)
+    if (kind == 0) TK_LAUNCH_POLICY_STEP(k_policy_step);
+    else if (kind == 1) TK_LAUNCH_POLICY_STEP(k_policy_step_seats, seats, seat_sets);
+    else TK_LAUNCH_POLICY_STEP(k_policy_step_versus, seats, seat_sets, b.w1, b.b1, b.w2, b.b2, b.w3, b.b3);
+#undef TK_LAUNCH_POLICY_STEP
     HIPCHK(hipGetLastError());
     return TAROK_OK;
+}
+#define TK_WEIGHTS(w1, b1, w2, b2, w3, b3) PolicyWeights{(const __bf16 *)(w1), b1, (const __bf16 *)(w2), b2, (const __bf16 *)(w3), b3}
+
+int tarok_policy_step(tarok_env *e, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
+                      const float *b3, const uint64_t *obs, uint8_t *action_out, float *logp_out, float *value_out,
+                      uint64_t *feature_words_out, int16_t *reward_out, uint8_t *done_out, uint16_t *trick_out,
+                      uint64_t *obs_out, int flags, void *stream) {
+    if (!e || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !obs || !action_out || !obs_out) return TAROK_EINVAL;
+    return launch_policy_step(e, 0, 15, nullptr, TK_WEIGHTS(w1, b1, w2, b2, w3, b3), PolicyWeights{}, obs, action_out, logp_out, value_out,
+                              feature_words_out, reward_out, done_out, trick_out, obs_out, flags, stream);
 }
 
 int tarok_policy_step_seats(tarok_env *e, int seats, const uint8_t *seats_per_game, const void *w1, const float *b1, const void *w2,
@@ -3043,17 +2920,8 @@ int tarok_policy_step_seats(tarok_env *e, int seats, const uint8_t *seats_per_ga
                             uint64_t *obs_out, int flags, void *stream) {
     if (!e || seats < 0 || seats > 15) return TAROK_EINVAL;       // (before the env is looked at, before any HIP call)
     if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !obs || !action_out || !obs_out || obs == obs_out) return TAROK_EINVAL;
-    HIPCHK(hipSetDevice(e->device));
-    u32 groups = (u32)((e->n + TK_BLOCK - 1) / TK_BLOCK);
-    u32 fan = e->refill_fan;
-    dim3 grid(groups + (groups + fan - 1) / fan);
-    e->launched = 1;
-    hipLaunchKernelGGL(k_policy_step_seats, grid, dim3(2 * TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, e->mix, flags,
-                       groups, e->epoch, fan, (const u64 *)obs, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3,
-                       action_out, logp_out, value_out, (ulonglong2 *)feature_words_out, reward_out, done_out, trick_out,
-                       (u64 *)obs_out, e->hist, e->s01, e->s23, e->aux, e->cnt, e->gkey, e->rlist, e->rcount, (u32)seats, seats_per_game);
-    HIPCHK(hipGetLastError());
-    return TAROK_OK;
+    return launch_policy_step(e, 1, (u32)seats, seats_per_game, TK_WEIGHTS(w1, b1, w2, b2, w3, b3), PolicyWeights{}, obs, action_out, logp_out,
+                              value_out, feature_words_out, reward_out, done_out, trick_out, obs_out, flags, stream);
 }
 
 int tarok_policy_step_versus(tarok_env *e, int seats, const uint8_t *seats_per_game, const void *w1, const float *b1, const void *w2,
@@ -3064,19 +2932,10 @@ int tarok_policy_step_versus(tarok_env *e, int seats, const uint8_t *seats_per_g
     if (!e || seats < 0 || seats > 15) return TAROK_EINVAL;       // (before the env is looked at, before any HIP call)
     if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !v1 || !c1 || !v2 || !c2 || !v3 || !c3) return TAROK_EINVAL;
     if (!obs || !action_out || !obs_out || obs == obs_out) return TAROK_EINVAL;
-    HIPCHK(hipSetDevice(e->device));
-    u32 groups = (u32)((e->n + TK_BLOCK - 1) / TK_BLOCK);
-    u32 fan = e->refill_fan;
-    dim3 grid(groups + (groups + fan - 1) / fan);
-    e->launched = 1;
-    hipLaunchKernelGGL(k_policy_step_versus, grid, dim3(2 * TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, e->mix, flags,
-                       groups, e->epoch, fan, (const u64 *)obs, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3,
-                       action_out, logp_out, value_out, (ulonglong2 *)feature_words_out, reward_out, done_out, trick_out,
-                       (u64 *)obs_out, e->hist, e->s01, e->s23, e->aux, e->cnt, e->gkey, e->rlist, e->rcount, (u32)seats, seats_per_game,
-                       (const __bf16 *)v1, c1, (const __bf16 *)v2, c2, (const __bf16 *)v3, c3);
-    HIPCHK(hipGetLastError());
-    return TAROK_OK;
+    return launch_policy_step(e, 2, (u32)seats, seats_per_game, TK_WEIGHTS(w1, b1, w2, b2, w3, b3), TK_WEIGHTS(v1, c1, v2, c2, v3, c3), obs,
+                              action_out, logp_out, value_out, feature_words_out, reward_out, done_out, trick_out, obs_out, flags, stream);
 }
+#undef TK_WEIGHTS
 
 int tarok_expand_features(tarok_env *e, int64_t n_samples, const uint64_t *feature_words, const int64_t *index,
                           void *features_out, void *stream) {

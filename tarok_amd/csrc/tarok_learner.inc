@@ -258,7 +258,7 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         recs[tid] = rc;
     }
     __syncthreads();
-    if (tid < 2 * LN_M) {   // expansion to bf16 0.0 / 1.0 (policy_body): two threads per sample, odd / even bytes
+    if (tid < 2 * LN_M) {   // expansion to bf16 0.0 / 1.0 (policy_expand, restated): two threads per sample, odd / even bytes
         u32 gme = tid >> 1, par = tid & 1;
         const uint4 *row = reinterpret_cast<const uint4 *>(&ext[gme][0]);
         uint4 r0 = row[0], r1 = row[1];
