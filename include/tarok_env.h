@@ -411,6 +411,26 @@ int tarok_learn_returns(tarok_env *env, int T, const uint8_t *done, const int16_
                         const float *logp, const float *value, const uint8_t *action, float reward_scale,
                         float *rec_out, float *stats_out, float *scratch, void *stream);
 
+/* The same record with returns by GAE(gamma, lambda) per seat, bootstrapped from the value of the SAME seat's next
+ * decision inside the rollout (arrays as tarok_learn_returns).  Per slot, backwards over t = T-1 .. 0, with a state per
+ * seat s (have[s] = false at first):
+ *   done[t]:  for every seat s: pend_r[s] = reward[t][s] * reward_scale, next_v[s] = next_adv[s] = 0, have[s] = true
+ *   s = the seat to move in obs[t], v = value[t];
+ *     have[s]:   delta = pend_r[s] + gamma * next_v[s] - v,  A = delta + gamma * lambda * next_adv[s],  known = 1
+ *     otherwise: A = 0, known = 0
+ *   return = A + v;  then next_v[s] = v, next_adv[s] = A, pend_r[s] = 0, have[s] = true
+ * gamma discounts per decision of the seat (its cards lie four lock-steps apart), not per lock-step.  With gamma =
+ * lambda = 1 the return of every sample tarok_learn_returns knows equals that one's (up to f32 rounding of the sum).
+ *   known = the seat moves again, or its game ends, inside the rollout: only a seat's LAST decision of a game still
+ *           unfinished at the end of the rollout is unknown (weight 0; it still serves as the bootstrap of the seat's
+ *           earlier decisions) — at most 4 samples per slot, so stats_out[2] >= 1 - 4 / T for rollouts whose slots
+ *           are never idle (auto-reset).
+ *   stats_out: over the known samples, of A.  Bit-reproducible from call to call (fixed summation order).
+ * gamma or lambda outside [0, 1] or NaN: TAROK_EINVAL. */
+int tarok_learn_returns_gae(tarok_env *env, int T, const uint8_t *done, const int16_t *reward, const uint64_t *obs,
+                            const float *logp, const float *value, const uint8_t *action, float reward_scale, float gamma,
+                            float lambda, float *rec_out, float *stats_out, float *scratch, void *stream);
+
 /* Forward, loss and backward chain of one minibatch of B samples (sample j = row index[j] of feature_words [M,4] /
  * rec [M,4]; index NULL: row j): feature gather + expansion -> layers 1-3 -> the loss of tarok_ppo_loss (advantage
  * = (return - value - stats[0]) * stats[1], weight = known) -> dH2, dH1.  Weights: the bf16 fragment-order copies

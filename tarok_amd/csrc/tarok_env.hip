@@ -2987,6 +2987,21 @@ int tarok_learn_returns(tarok_env *e, int T, const uint8_t *done, const int16_t 
     return TAROK_OK;
 }
 
+int tarok_learn_returns_gae(tarok_env *e, int T, const uint8_t *done, const int16_t *reward, const uint64_t *obs, const float *logp,
+                            const float *value, const uint8_t *action, float reward_scale, float gamma, float lambda, float *rec_out,
+                            float *stats_out, float *scratch, void *stream) {
+    if (!e || T < 1 || !done || !reward || !obs || !logp || !value || !action || !rec_out || !stats_out || !scratch) return TAROK_EINVAL;
+    if (!(gamma >= 0.f && gamma <= 1.f) || !(lambda >= 0.f && lambda <= 1.f)) return TAROK_EINVAL;      // (NaN fails both)
+    HIPCHK(hipSetDevice(e->device));
+    dim3 grid = grid_for(e->n);
+    hipLaunchKernelGGL(k_returns_gae, grid, dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, T, done, reward, (const u64 *)obs, logp,
+                       value, action, reward_scale, gamma, gamma * lambda, (float4 *)rec_out, (float4 *)scratch);
+    hipLaunchKernelGGL(k_adv_stats, dim3(1), dim3(TK_BLOCK), 0, (hipStream_t)stream, (int)grid.x, (int64_t)T * e->n,
+                       (const float4 *)scratch, (float4 *)stats_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
 int tarok_learn_chain(tarok_env *e, int64_t B, const uint64_t *feature_words, const int64_t *index, const float *rec,
                       const float *stats, float clip, float vf_coef, float ent_coef, const void *w1, const float *b1,
                       const void *w2, const float *b2, const void *w3, const float *b3, const void *w3t, const void *w2t,

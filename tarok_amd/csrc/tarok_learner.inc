@@ -7,6 +7,7 @@
 //
 //   k_returns      per slot, backwards over the rollout: every card is credited with its seat's final score of
 //                  its game; packs the per-sample record the update gathers; sums for the advantage statistics
+//   k_returns_gae  the same walk with per-seat GAE(gamma, lambda) returns bootstrapped from the seat's next decision
 //   k_learn_chain  one 128-sample tile per workgroup, activations in LDS: feature gather + expansion ->
 //                  layer 1, 2, 3 (bf16 MFMA, f32 accumulate) -> clipped-surrogate / value / entropy loss and its
 //                  gradient in the layer-3 accumulators -> dH2 = (dOut W3) . relu' -> dH1 = (dH2 W2) . relu'.
@@ -59,6 +60,66 @@ TK_KERNEL(TK_BLOCK, 64) void k_returns(int64_t n, int T, const uint8_t *__restri
             float v = val[j];
             rec[j] = make_float4(logp[j], r, v, __uint_as_float((u32)act[j] | (have ? 256u : 0u)));
             if (have) { float a = r - v; s_n += 1.f; s_a += a; s_q += a * a; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { s_n += __shfl_xor(s_n, o); s_a += __shfl_xor(s_a, o); s_q += __shfl_xor(s_q, o); }
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s_n; red[1][threadIdx.x >> 6] = s_a; red[2][threadIdx.x >> 6] = s_q; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+        for (int k = 0; k < TK_BLOCK / 64; k++) { a0 += red[0][k]; a1 += red[1][k]; a2 += red[2][k]; }
+        part[blockIdx.x] = make_float4(a0, a1, a2, 0.f);
+    }
+}
+
+// Returns by GAE(gamma, lambda), per seat.  Arrays and rec / part as k_returns; the walk keeps, for each of the four seats,
+// what the seat's NEXT decision inside the rollout left behind: have (there is one, or the game ended), next_v (its
+// value), next_adv (its advantage) and pend_r (the seat's scaled final score if its game ended in between, else 0).
+// At lock-step t, seat s to move, v = val[t]:
+//     done[t]:   for every seat pend_r = reward[t][seat] * scale, next_v = next_adv = 0, have = true
+//                (the steps after t belong to the slot's next game and are behind us)
+//     have[s]:   delta = pend_r[s] + gamma * next_v[s] - v,  A = delta + gamma * lambda * next_adv[s],  known
+//     else:      A = 0, not known: the seat's last decision of a game that is unfinished when the rollout ends
+//     rec[t].y = A + v;  then next_v[s] = v, next_adv[s] = A, pend_r[s] = 0, have[s] = true (an unknown tail sample is
+//                still the bootstrap of the seat's earlier decisions)
+// gamma discounts per DECISION OF THE SEAT (its next card is one step away, four lock-steps later), not per lock-step.
+// At most one sample per seat and slot stays unknown: stats[2] >= 1 - 4 / T.  gl = gamma * lambda (f32 product).
+// The seat's state is picked by compare / select over four named registers (a runtime-indexed array would live in
+// scratch memory), and the scores are loaded as four shorts: no 64-bit shift by a variable amount (DESIGN.md section 3).
+TK_KERNEL(TK_BLOCK, 64) void k_returns_gae(int64_t n, int T, const uint8_t *__restrict__ done, const int16_t *__restrict__ reward,
+                                                         const u64 *__restrict__ words, const float *__restrict__ logp,
+                                                         const float *__restrict__ val, const uint8_t *__restrict__ act, float scale,
+                                                         float gamma, float gl, float4 *__restrict__ rec, float4 *__restrict__ part) {
+    TK_VGPR_TOP(64, 63);
+    __shared__ float red[3][TK_BLOCK / 64];
+    int64_t i = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
+    float s_n = 0.f, s_a = 0.f, s_q = 0.f;
+    if (i < n) {
+        float nv[4] = {0.f, 0.f, 0.f, 0.f}, na[4] = {0.f, 0.f, 0.f, 0.f}, pr[4] = {0.f, 0.f, 0.f, 0.f};   // (constant indices only)
+        u32 have = 0;                                        // bit s: seat s
+#pragma unroll 4                                             // (four lock-steps' loads in flight: the walk is latency bound)
+        for (int t = T - 1; t >= 0; t--) {
+            int64_t j = (int64_t)t * n + i;
+            if (done[j]) {
+                short4 rw = reinterpret_cast<const short4 *>(reward)[j];
+                pr[0] = (float)rw.x * scale; pr[1] = (float)rw.y * scale; pr[2] = (float)rw.z * scale; pr[3] = (float)rw.w * scale;
+#pragma unroll
+                for (int k = 0; k < 4; k++) { nv[k] = 0.f; na[k] = 0.f; }
+                have = 15u;
+            }
+            u32 seat = (u32)(words[j] >> TAROK_OBS_SEAT_SHIFT) & 3u;
+            float v = val[j];
+            float p = pr[3], nvs = nv[3], nas = na[3];
+#pragma unroll
+            for (int k = 0; k < 3; k++) { bool m = seat == (u32)k; p = m ? pr[k] : p; nvs = m ? nv[k] : nvs; nas = m ? na[k] : nas; }
+            bool known = (have >> seat) & 1u;
+            float a = known ? (p + gamma * nvs - v) + gl * nas : 0.f;
+            rec[j] = make_float4(logp[j], a + v, v, __uint_as_float((u32)act[j] | (known ? 256u : 0u)));
+#pragma unroll
+            for (int k = 0; k < 4; k++) { bool m = seat == (u32)k; pr[k] = m ? 0.f : pr[k]; nv[k] = m ? v : nv[k]; na[k] = m ? a : na[k]; }
+            have |= 1u << seat;
+            if (known) { s_n += 1.f; s_a += a; s_q += a * a; }
         }
     }
 #pragma unroll

@@ -457,6 +457,13 @@ class TarokVecEnv:
                                                      self._p(val), self._p(act), float(reward_scale), self._p(rec), self._p(stats),
                                                      self._p(scratch), self._stream()))
 
+    def learn_returns_gae(self, T, done, reward, words, logp, val, act, reward_scale, gamma, lam, rec, stats, scratch):
+        """tarok_learn_returns_gae: the record of learn_returns with per-seat GAE(gamma, lam) returns."""
+        with torch.cuda.device(self.device):
+            _native.check(self.L.tarok_learn_returns_gae(self._h, int(T), self._p(done), self._p(reward), self._p(words), self._p(logp),
+                                                         self._p(val), self._p(act), float(reward_scale), float(gamma), float(lam),
+                                                         self._p(rec), self._p(stats), self._p(scratch), self._stream()))
+
     def learn_chain(self, B, words, index, rec, stats, clip, vf_coef, ent_coef, wf, bias, Xw, H1, H2, dOut, dH2, dH1, scratch, terms,
                     running=None):
         """wf: dict of the bf16 fragment-order weight copies (w1, w2, w3, w3t, w2t: learn_adam), bias: (b1, b2, b3) f32."""

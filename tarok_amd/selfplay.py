@@ -12,7 +12,8 @@ Shape of the loop (per rank, one env shard each; games need no communication):
     env.step(a, auto_reset=True)                                          (HIP kernel)
     ... T steps ...
     returns: every card is credited with its seat's final score of that game (Monte-Carlo,
-    gamma = 1); clipped-surrogate PPO update; gradients summed over ranks in ONE flattened
+    gamma = 1), or, with SelfPlay(gamma=..., gae_lambda=...), per-seat GAE bootstrapped from the
+    seat's next decision; clipped-surrogate PPO update; gradients summed over ranks in ONE flattened
     all-reduce per minibatch (a few hundred KB: latency-bound, so one bucket, not many).
 """
 import time
@@ -128,6 +129,43 @@ def assign_returns(done, reward, seat):
     return ret, known
 
 
+def assign_gae(done, reward, seat, val, gamma, lam, reward_scale):
+    """Returns by GAE(gamma, lam) per seat, bootstrapped from the value of the same seat's next decision inside the
+    rollout: the plain torch statement of tarok_learn_returns_gae (include/tarok_env.h), the counterpart of
+    assign_returns.
+
+    done, reward, seat as in assign_returns, val [T,N]: the value at play time.  Per seat s the backward walk keeps what
+    the seat's next decision left: nv (its value), na (its advantage), pr (the seat's final score * reward_scale if its
+    game ended in between, else 0), have (there is such a decision, or the game ended).  gamma discounts per decision of
+    the seat, not per lock-step.  Returns (ret [T,N] f32 = advantage + value, already scaled; known [T,N] bool):
+    `known` is False only for a seat's last decision of a game still unfinished when the rollout ends.  The walk itself
+    runs in float64 (this is the reference statement, not the hot path), so `ret` is the recursion's value rounded once."""
+    T, N = done.shape
+    dev = done.device
+    ret = torch.zeros((T, N), dtype=torch.float32, device=dev)
+    known = torch.zeros((T, N), dtype=torch.bool, device=dev)
+    nv = torch.zeros((N, 4), dtype=torch.float64, device=dev)
+    na, pr = torch.zeros_like(nv), torch.zeros_like(nv)
+    have = torch.zeros((N, 4), dtype=torch.bool, device=dev)
+    seats = torch.arange(4, device=dev)
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    for t in range(T - 1, -1, -1):
+        d = done[t].bool().unsqueeze(-1)
+        pr = torch.where(d, reward[t].double() * reward_scale, pr)
+        nv, na = torch.where(d, zero, nv), torch.where(d, zero, na)
+        have = have | d
+        s = seat[t].long().unsqueeze(-1)
+        pick = lambda x: x.gather(-1, s).squeeze(-1)
+        v = val[t].double()
+        h = pick(have)
+        a = torch.where(h, (pick(pr) + gamma * pick(nv) - v) + gamma * lam * pick(na), zero)
+        ret[t], known[t] = (a + v).float(), h
+        mine = seats == s
+        nv, na, pr = torch.where(mine, v.unsqueeze(-1), nv), torch.where(mine, a.unsqueeze(-1), na), torch.where(mine, zero, pr)
+        have = have | mine
+    return ret, known
+
+
 def dw_ranges(B, cap=K.LEARN_MAX_BATCH):
     """The row ranges [(r0, r1), ...] over which update_fused computes the weight gradients of a minibatch of B
     samples: tarok_learn_dw takes at most `cap` samples per launch (32-bit buffer offsets), so a larger minibatch is
@@ -187,8 +225,15 @@ class SelfPlay:
     hidden size the policy runs as tarok_observe -> torch GEMMs -> tarok_sample_policy."""
 
     def __init__(self, env, hidden=256, lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.01, reward_scale=1.0 / 70.0, seed=0,
-                 use_graph=True, fused=None, fused_loss=None, fused_step=None, fused_learner=None, max_grad_norm=1.0):
+                 use_graph=True, fused=None, fused_loss=None, fused_step=None, fused_learner=None, max_grad_norm=1.0,
+                 gamma=None, gae_lambda=None):
         self.env = env
+        # returns: both None = every card credited with its seat's final score (Monte-Carlo: assign_returns /
+        # tarok_learn_returns); either set = per-seat GAE(gamma, lambda), the other defaulting to 1.0 (assign_gae /
+        # tarok_learn_returns_gae)
+        self.gae = gamma is not None or gae_lambda is not None
+        self.gamma = 1.0 if gamma is None else float(gamma)
+        self.gae_lambda = 1.0 if gae_lambda is None else float(gae_lambda)
         self.device = env.device
         torch.manual_seed(seed)                       # same initial weights on every rank
         self.net = PolicyNet(hidden).to(self.device)
@@ -365,8 +410,11 @@ class SelfPlay:
         T, n = buf["act"].shape
         words_t = buf["words"][:T]
         seat = (words_t >> K.OBS_SEAT_SHIFT) & 3
-        ret, known = assign_returns(buf["done"].bool(), buf["reward"], seat)
-        ret = ret * self.reward_scale
+        if self.gae:
+            ret, known = assign_gae(buf["done"].bool(), buf["reward"], seat, buf["val"], self.gamma, self.gae_lambda, self.reward_scale)
+        else:
+            ret, known = assign_returns(buf["done"].bool(), buf["reward"], seat)
+            ret = ret * self.reward_scale
         flat = lambda x: x.reshape(T * n, *x.shape[2:])
         obs, words, act, logp0 = flat(buf["obs"]), flat(words_t), flat(buf["act"]).long(), flat(buf["logp"])
         val0 = flat(buf["val"]).float()
@@ -464,8 +512,12 @@ class SelfPlay:
         M = T * n
         B = -(-M // minibatches)
         lb = self._learn_bufs(M, B)
-        env.learn_returns(T, buf["done"], buf["reward"], buf["words"][:T], buf["logp"], buf["val"], buf["act"], self.reward_scale,
-                          lb["rec"], lb["stats"], lb["scratch"])
+        if self.gae:
+            env.learn_returns_gae(T, buf["done"], buf["reward"], buf["words"][:T], buf["logp"], buf["val"], buf["act"],
+                                  self.reward_scale, self.gamma, self.gae_lambda, lb["rec"], lb["stats"], lb["scratch"])
+        else:
+            env.learn_returns(T, buf["done"], buf["reward"], buf["words"][:T], buf["logp"], buf["val"], buf["act"], self.reward_scale,
+                              lb["rec"], lb["stats"], lb["scratch"])
         words = buf["obs"].view(M, 4)
         lb["running"].zero_()
         nbytes = 0
