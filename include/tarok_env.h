@@ -431,6 +431,41 @@ int tarok_learn_returns_gae(tarok_env *env, int T, const uint8_t *done, const in
                             const float *logp, const float *value, const uint8_t *action, float reward_scale, float gamma,
                             float lambda, float *rec_out, float *stats_out, float *scratch, void *stream);
 
+/* tarok_learn_returns (gae = 0; gamma and lambda are ignored) or tarok_learn_returns_gae (gae = 1; its checks of gamma
+ * and lambda) for a rollout in which only some seats are the learner's: training against a frozen opponent seated by
+ * tarok_policy_step_versus.
+ *   seats, seats_per_game   exactly as in tarok_policy_step_versus: `seats` is a 4-bit set used for every slot when
+ *                           seats_per_game is NULL, seats_per_game [N] u8 one set per slot (bits 4..7 ignored); bit s
+ *                           set = seat s is the learner's.  A slot keeps its set through the auto-resets.
+ * The record differs in `known` alone: the unmasked walk's known AND (the seat to move in obs[t] is in the slot's set).
+ * logp, return, value and the card byte are written for every sample as before, and the per-seat GAE state is updated
+ * for every seat as before: a seat's chain only ever reads that seat's own values, so a learner seat's returns equal
+ * the unmasked ones.
+ *   stats_out = {mean, 1 / std of the advantages over the known samples, known / (T N), 0}, in the fixed summation
+ *   order of the kernels it extends (bit-reproducible).  No known sample at all: {0, 1e6, 0, 0}.
+ * With seats = 15 and seats_per_game = NULL, rec_out and stats_out are byte for byte those of tarok_learn_returns
+ * (gae = 0) / tarok_learn_returns_gae (gae = 1).  rec_out, stats_out, scratch as in tarok_learn_returns.
+ * TAROK_EINVAL (before any HIP call) for a NULL env or required array, T < 1, seats outside 0..15, gae outside {0, 1}
+ * and, with gae = 1, gamma or lambda outside [0, 1] or NaN. */
+int tarok_learn_returns_seats(tarok_env *env, int T, const uint8_t *done, const int16_t *reward, const uint64_t *obs,
+                              const float *logp, const float *value, const uint8_t *action, float reward_scale, int gae,
+                              float gamma, float lambda, int seats, const uint8_t *seats_per_game, float *rec_out,
+                              float *stats_out, float *scratch, void *stream);
+
+/* Stable compaction of the known samples of a record: index_out[0 .. count) = the sample numbers j in [0, M) whose
+ * known bit (bit 8 of rec[j].w) is set, in ascending order, count_out[0] (device) = how many there are.  Entries of
+ * index_out at and beyond count are NOT written.  Deterministic: the same input gives the same bytes.  The list is what
+ * tarok_learn_chain takes as `index`: minibatches drawn from it hold known samples only, so a learner that owns one
+ * seat of four does not run the forward, loss and backward of the other three (they would carry weight 0).
+ *   rec [M,4] f32 (tarok_learn_returns*), index_out [M] i64, scratch: tarok_learn_select_scratch_bytes(M) bytes,
+ *   16-byte aligned.  M up to 2^28 and beyond: sample numbers and byte offsets are 64 bit.
+ * Three small stream-ordered launches (count per tile of TAROK_LEARN_SELECT_TILE samples, scan of the tile counts,
+ * scatter); no workgroup waits for another.  TAROK_EINVAL for a NULL env or pointer, or M < 1. */
+#define TAROK_LEARN_SELECT_TILE 2048 /* samples one workgroup of the scatter launch handles */
+int64_t tarok_learn_select_scratch_bytes(int64_t M);
+int tarok_learn_select(tarok_env *env, int64_t M, const float *rec, int64_t *index_out, int64_t *count_out,
+                       void *scratch, void *stream);
+
 /* Forward, loss and backward chain of one minibatch of B samples (sample j = row index[j] of feature_words [M,4] /
  * rec [M,4]; index NULL: row j): feature gather + expansion -> layers 1-3 -> the loss of tarok_ppo_loss (advantage
  * = (return - value - stats[0]) * stats[1], weight = known) -> dH2, dH1.  Weights: the bf16 fragment-order copies

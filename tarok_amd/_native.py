@@ -20,7 +20,8 @@ SYMBOLS = [
     "tarok_create", "tarok_destroy", "tarok_num_games", "tarok_set_option", "tarok_reset", "tarok_exchange",
     "tarok_legal_actions", "tarok_step", "tarok_prefetch", "tarok_policy_random", "tarok_step_random",
     "tarok_run_random", "tarok_krog_random", "tarok_rollout_random", "tarok_get_state", "tarok_set_state", "tarok_get_counters", "tarok_debug_stamps", "tarok_debug_stamps_sized", "tarok_debug_refill_selftest", "tarok_observe", "tarok_sample_policy", "tarok_policy_mlp", "tarok_policy_step", "tarok_policy_step_seats", "tarok_policy_step_versus", "tarok_expand_features", "tarok_ppo_loss",
-    "tarok_targets_ref", "tarok_learn_returns", "tarok_learn_returns_gae", "tarok_learn_chain", "tarok_learn_workspace_bytes", "tarok_learn_dw", "tarok_learn_adam",
+    "tarok_targets_ref", "tarok_learn_returns", "tarok_learn_returns_gae", "tarok_learn_returns_seats", "tarok_learn_select_scratch_bytes", "tarok_learn_select",
+    "tarok_learn_chain", "tarok_learn_workspace_bytes", "tarok_learn_dw", "tarok_learn_adam",
     "tarok_observe_ref", "tarok_observe_exchange_ref", "tarok_observe_hands_ref", "tarok_get_history", "tarok_set_history",
 ]
 
@@ -146,6 +147,10 @@ def lib():
     L.tarok_targets_ref.restype = i32; L.tarok_targets_ref.argtypes = [vp, i32] + [vp] * 6 + [f32] + [vp] * 3
     L.tarok_learn_returns.restype = i32; L.tarok_learn_returns.argtypes = [vp, i32] + [vp] * 6 + [f32] + [vp] * 4
     L.tarok_learn_returns_gae.restype = i32; L.tarok_learn_returns_gae.argtypes = [vp, i32] + [vp] * 6 + [f32] * 3 + [vp] * 4
+    L.tarok_learn_returns_seats.restype = i32
+    L.tarok_learn_returns_seats.argtypes = [vp, i32] + [vp] * 6 + [f32, i32, f32, f32, i32] + [vp] * 5
+    L.tarok_learn_select_scratch_bytes.restype = i64; L.tarok_learn_select_scratch_bytes.argtypes = [i64]
+    L.tarok_learn_select.restype = i32; L.tarok_learn_select.argtypes = [vp, i64] + [vp] * 5
     L.tarok_learn_chain.restype = i32; L.tarok_learn_chain.argtypes = [vp, i64] + [vp] * 4 + [f32] * 3 + [vp] * 18
     L.tarok_learn_workspace_bytes.restype = i64; L.tarok_learn_workspace_bytes.argtypes = [vp]
     L.tarok_learn_dw.restype = i32; L.tarok_learn_dw.argtypes = [vp, i64] + [vp] * 10

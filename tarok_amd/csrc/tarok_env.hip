@@ -3002,6 +3002,49 @@ int tarok_learn_returns_gae(tarok_env *e, int T, const uint8_t *done, const int1
     return TAROK_OK;
 }
 
+int tarok_learn_returns_seats(tarok_env *e, int T, const uint8_t *done, const int16_t *reward, const uint64_t *obs, const float *logp,
+                              const float *value, const uint8_t *action, float reward_scale, int gae, float gamma, float lambda,
+                              int seats, const uint8_t *seats_per_game, float *rec_out, float *stats_out, float *scratch, void *stream) {
+    if (!e || T < 1 || !done || !reward || !obs || !logp || !value || !action || !rec_out || !stats_out || !scratch) return TAROK_EINVAL;
+    if (seats < 0 || seats > 15 || (gae != 0 && gae != 1)) return TAROK_EINVAL;
+    if (gae && (!(gamma >= 0.f && gamma <= 1.f) || !(lambda >= 0.f && lambda <= 1.f))) return TAROK_EINVAL;      // (NaN fails both)
+    HIPCHK(hipSetDevice(e->device));
+    dim3 grid = grid_for(e->n);
+    if (gae)
+        hipLaunchKernelGGL(k_returns_gae_seats, grid, dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, T, done, reward, (const u64 *)obs, logp,
+                           value, action, reward_scale, gamma, gamma * lambda, (u32)seats, seats_per_game, (float4 *)rec_out,
+                           (float4 *)scratch);
+    else
+        hipLaunchKernelGGL(k_returns_seats, grid, dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, T, done, reward, (const u64 *)obs, logp,
+                           value, action, reward_scale, (u32)seats, seats_per_game, (float4 *)rec_out, (float4 *)scratch);
+    hipLaunchKernelGGL(k_adv_stats, dim3(1), dim3(TK_BLOCK), 0, (hipStream_t)stream, (int)grid.x, (int64_t)T * e->n,
+                       (const float4 *)scratch, (float4 *)stats_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+// scratch of tarok_learn_select: tile_off [tiles] i64, then tile_cnt [tiles] u32 (rounded up to 16 bytes)
+static inline int64_t select_tiles(int64_t M) { return (M + TAROK_LEARN_SELECT_TILE - 1) / TAROK_LEARN_SELECT_TILE; }
+int64_t tarok_learn_select_scratch_bytes(int64_t M) {
+    if (M < 1) return 0;
+    return (select_tiles(M) * 12 + 15) / 16 * 16;
+}
+
+int tarok_learn_select(tarok_env *e, int64_t M, const float *rec, int64_t *index_out, int64_t *count_out, void *scratch, void *stream) {
+    if (!e || M < 1 || !rec || !index_out || !count_out || !scratch) return TAROK_EINVAL;
+    const int64_t tiles = select_tiles(M);
+    if (tiles > 0x7FFFFFFF) return TAROK_EINVAL;              // (one workgroup per tile: the grid's first dimension)
+    HIPCHK(hipSetDevice(e->device));
+    int64_t *tile_off = (int64_t *)scratch;
+    u32 *tile_cnt = (u32 *)(tile_off + tiles);
+    hipLaunchKernelGGL(k_select_count, dim3((unsigned)tiles), dim3(TK_BLOCK), 0, (hipStream_t)stream, M, (const float4 *)rec, tile_cnt);
+    hipLaunchKernelGGL(k_select_scan, dim3(1), dim3(TK_BLOCK), 0, (hipStream_t)stream, tiles, (const u32 *)tile_cnt, tile_off, count_out);
+    hipLaunchKernelGGL(k_select_scatter, dim3((unsigned)tiles), dim3(TK_BLOCK), 0, (hipStream_t)stream, M, (const float4 *)rec,
+                       (const int64_t *)tile_off, index_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
 int tarok_learn_chain(tarok_env *e, int64_t B, const uint64_t *feature_words, const int64_t *index, const float *rec,
                       const float *stats, float clip, float vf_coef, float ent_coef, const void *w1, const float *b1,
                       const void *w2, const float *b2, const void *w3, const float *b3, const void *w3t, const void *w2t,

@@ -8,6 +8,10 @@
 //   k_returns      per slot, backwards over the rollout: every card is credited with its seat's final score of
 //                  its game; packs the per-sample record the update gathers; sums for the advantage statistics
 //   k_returns_gae  the same walk with per-seat GAE(gamma, lambda) returns bootstrapped from the seat's next decision
+//   k_returns_seats, k_returns_gae_seats   the two walks with `known` masked by the learner's seats of the slot (training
+//                  against a frozen opponent: the other seats' samples are somebody else's cards)
+//   k_select_*     stable compaction of the known samples into an index list (count per tile, scan, scatter): the
+//                  minibatches of k_learn_chain then hold the learner's samples only
 //   k_learn_chain  one 128-sample tile per workgroup, activations in LDS: feature gather + expansion ->
 //                  layer 1, 2, 3 (bf16 MFMA, f32 accumulate) -> clipped-surrogate / value / entropy loss and its
 //                  gradient in the layer-3 accumulators -> dH2 = (dOut W3) . relu' -> dH1 = (dH2 W2) . relu'.
@@ -40,17 +44,23 @@ static_assert(LN_P == TAROK_MLP_PARAMS, "flat parameter vector");
 // logp / val [T,N] f32 from the rollout, act [T,N] u8.  rec [T,N] float4 = {logp_old, ret * scale, val, bits:
 // card | known << 8} where known = the game the card belongs to ended inside the rollout.  part [blocks][4] =
 // {sum known, sum adv, sum adv^2, 0} with adv = ret - val (f32, fixed order inside a block).
-TK_KERNEL(TK_BLOCK, 64) void k_returns(int64_t n, int T, const uint8_t *__restrict__ done, const int16_t *__restrict__ reward,
-                                                     const u64 *__restrict__ words, const float *__restrict__ logp,
-                                                     const float *__restrict__ val, const uint8_t *__restrict__ act, float scale,
-                                                     float4 *__restrict__ rec, float4 *__restrict__ part) {
-    TK_VGPR_TOP(64, 63);
+// MASK (k_returns_seats): known = that AND the seat to move is one of the learner's seats of the slot (`seat_sets[i]`, or
+// `seats` for every slot: 4-bit sets as in tarok_policy_step_versus, bits 4..7 ignored).  The set is read once per slot
+// and tested by a 32-bit shift; everything else of the record is written as without the mask.
+#define TK_RETURNS_ARGS int64_t n, int T, const uint8_t *__restrict__ done, const int16_t *__restrict__ reward,                  \
+                        const u64 *__restrict__ words, const float *__restrict__ logp, const float *__restrict__ val,        \
+                        const uint8_t *__restrict__ act, float scale
+#define TK_RETURNS_NAMES n, T, done, reward, words, logp, val, act, scale
+template <bool MASK>
+__device__ __forceinline__ void returns_walk(TK_RETURNS_ARGS, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                             float4 *__restrict__ rec, float4 *__restrict__ part) {
     __shared__ float red[3][TK_BLOCK / 64];
     int64_t i = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
     float s_n = 0.f, s_a = 0.f, s_q = 0.f;
     if (i < n) {
         u64 cur = 0;
         bool have = false;
+        const u32 set = MASK ? (seat_sets ? (u32)seat_sets[i] : seats) : 15u;
 #pragma unroll 4                                             // (four lock-steps' loads in flight: the walk is latency bound)
         for (int t = T - 1; t >= 0; t--) {
             int64_t j = (int64_t)t * n + i;
@@ -58,8 +68,9 @@ TK_KERNEL(TK_BLOCK, 64) void k_returns(int64_t n, int T, const uint8_t *__restri
             u32 seat = (u32)(words[j] >> TAROK_OBS_SEAT_SHIFT) & 3u;
             float r = (float)(int16_t)((cur >> (16 * seat)) & 0xFFFF) * scale;
             float v = val[j];
-            rec[j] = make_float4(logp[j], r, v, __uint_as_float((u32)act[j] | (have ? 256u : 0u)));
-            if (have) { float a = r - v; s_n += 1.f; s_a += a; s_q += a * a; }
+            const bool known = MASK ? have && ((set >> seat) & 1u) : have;
+            rec[j] = make_float4(logp[j], r, v, __uint_as_float((u32)act[j] | (known ? 256u : 0u)));
+            if (known) { float a = r - v; s_n += 1.f; s_a += a; s_q += a * a; }
         }
     }
 #pragma unroll
@@ -71,6 +82,15 @@ TK_KERNEL(TK_BLOCK, 64) void k_returns(int64_t n, int T, const uint8_t *__restri
         for (int k = 0; k < TK_BLOCK / 64; k++) { a0 += red[0][k]; a1 += red[1][k]; a2 += red[2][k]; }
         part[blockIdx.x] = make_float4(a0, a1, a2, 0.f);
     }
+}
+TK_KERNEL(TK_BLOCK, 64) void k_returns(TK_RETURNS_ARGS, float4 *__restrict__ rec, float4 *__restrict__ part) {
+    TK_VGPR_TOP(64, 63);
+    returns_walk<false>(TK_RETURNS_NAMES, 15u, nullptr, rec, part);
+}
+TK_KERNEL(TK_BLOCK, 64) void k_returns_seats(TK_RETURNS_ARGS, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                           float4 *__restrict__ rec, float4 *__restrict__ part) {
+    TK_VGPR_TOP(64, 63);
+    returns_walk<true>(TK_RETURNS_NAMES, seats, seat_sets, rec, part);
 }
 
 // Returns by GAE(gamma, lambda), per seat.  Arrays and rec / part as k_returns; the walk keeps, for each of the four seats,
@@ -87,15 +107,17 @@ TK_KERNEL(TK_BLOCK, 64) void k_returns(int64_t n, int T, const uint8_t *__restri
 // At most one sample per seat and slot stays unknown: stats[2] >= 1 - 4 / T.  gl = gamma * lambda (f32 product).
 // The seat's state is picked by compare / select over four named registers (a runtime-indexed array would live in
 // scratch memory), and the scores are loaded as four shorts: no 64-bit shift by a variable amount (DESIGN.md section 3).
-TK_KERNEL(TK_BLOCK, 64) void k_returns_gae(int64_t n, int T, const uint8_t *__restrict__ done, const int16_t *__restrict__ reward,
-                                                         const u64 *__restrict__ words, const float *__restrict__ logp,
-                                                         const float *__restrict__ val, const uint8_t *__restrict__ act, float scale,
-                                                         float gamma, float gl, float4 *__restrict__ rec, float4 *__restrict__ part) {
-    TK_VGPR_TOP(64, 63);
+// MASK (k_returns_gae_seats): the record's known bit and the sums are ANDed with the learner's seat set of the slot as in
+// returns_walk; the walk's own state (A, have, next_v, next_adv, pend_r of every seat) is kept as without the mask — a
+// seat's chain reads that seat's values only, so a learner seat's returns are the unmasked ones.
+template <bool MASK>
+__device__ __forceinline__ void returns_gae_walk(TK_RETURNS_ARGS, float gamma, float gl, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                 float4 *__restrict__ rec, float4 *__restrict__ part) {
     __shared__ float red[3][TK_BLOCK / 64];
     int64_t i = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
     float s_n = 0.f, s_a = 0.f, s_q = 0.f;
     if (i < n) {
+        const u32 set = MASK ? (seat_sets ? (u32)seat_sets[i] : seats) : 15u;
         float nv[4] = {0.f, 0.f, 0.f, 0.f}, na[4] = {0.f, 0.f, 0.f, 0.f}, pr[4] = {0.f, 0.f, 0.f, 0.f};   // (constant indices only)
         u32 have = 0;                                        // bit s: seat s
 #pragma unroll 4                                             // (four lock-steps' loads in flight: the walk is latency bound)
@@ -115,11 +137,12 @@ TK_KERNEL(TK_BLOCK, 64) void k_returns_gae(int64_t n, int T, const uint8_t *__re
             for (int k = 0; k < 3; k++) { bool m = seat == (u32)k; p = m ? pr[k] : p; nvs = m ? nv[k] : nvs; nas = m ? na[k] : nas; }
             bool known = (have >> seat) & 1u;
             float a = known ? (p + gamma * nvs - v) + gl * nas : 0.f;
-            rec[j] = make_float4(logp[j], a + v, v, __uint_as_float((u32)act[j] | (known ? 256u : 0u)));
+            const bool mine = MASK ? known && ((set >> seat) & 1u) : known;
+            rec[j] = make_float4(logp[j], a + v, v, __uint_as_float((u32)act[j] | (mine ? 256u : 0u)));
 #pragma unroll
             for (int k = 0; k < 4; k++) { bool m = seat == (u32)k; pr[k] = m ? 0.f : pr[k]; nv[k] = m ? v : nv[k]; na[k] = m ? a : na[k]; }
             have |= 1u << seat;
-            if (known) { s_n += 1.f; s_a += a; s_q += a * a; }
+            if (mine) { s_n += 1.f; s_a += a; s_q += a * a; }
         }
     }
 #pragma unroll
@@ -131,6 +154,15 @@ TK_KERNEL(TK_BLOCK, 64) void k_returns_gae(int64_t n, int T, const uint8_t *__re
         for (int k = 0; k < TK_BLOCK / 64; k++) { a0 += red[0][k]; a1 += red[1][k]; a2 += red[2][k]; }
         part[blockIdx.x] = make_float4(a0, a1, a2, 0.f);
     }
+}
+TK_KERNEL(TK_BLOCK, 64) void k_returns_gae(TK_RETURNS_ARGS, float gamma, float gl, float4 *__restrict__ rec, float4 *__restrict__ part) {
+    TK_VGPR_TOP(64, 63);
+    returns_gae_walk<false>(TK_RETURNS_NAMES, gamma, gl, 15u, nullptr, rec, part);
+}
+TK_KERNEL(TK_BLOCK, 64) void k_returns_gae_seats(TK_RETURNS_ARGS, float gamma, float gl, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                               float4 *__restrict__ rec, float4 *__restrict__ part) {
+    TK_VGPR_TOP(64, 63);
+    returns_gae_walk<true>(TK_RETURNS_NAMES, gamma, gl, seats, seat_sets, rec, part);
 }
 
 // stats = {mean, 1 / std, known fraction, 0} of the advantages from k_returns' block sums (one workgroup)
@@ -152,6 +184,95 @@ TK_KERNEL(TK_BLOCK, 64) void k_adv_stats(int blocks, int64_t total, const float4
         double sd = sqrt(var > 0 ? var : 0);
         if (sd < 1e-6) sd = 1e-6;
         stats[0] = make_float4((float)mean, (float)(1.0 / sd), (float)(red[0][0] / (double)(total < 1 ? 1 : total)), 0.f);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Compaction of the known samples (tarok_learn_select): index_out[0 .. count) = the sample numbers j whose record has the
+// known bit (bit 8 of rec[j].w), ascending.  Three stream-ordered launches and no workgroup that waits for another:
+//   k_select_count    one workgroup per tile of TAROK_LEARN_SELECT_TILE samples: how many of them are known
+//   k_select_scan     ONE workgroup: exclusive prefix sums of the tile counts (64 bit) and the total
+//   k_select_scatter  one workgroup per tile: the known samples' numbers to index_out from the tile's prefix on
+// A tile is SEL_ROUNDS rounds of 64 consecutive samples for each of the workgroup's four waves (wave w: samples
+// [SEL_WAVE w, SEL_WAVE (w + 1)) of the tile), lane l of a round its l-th sample: the rank of a known sample inside its
+// round is the number of known lanes below it (ballot + mbcnt), in front of it the wave's earlier rounds (popcounts of
+// their ballots, the same in every lane), the tile's earlier waves (LDS) and the earlier tiles (the scan).  Both passes
+// evaluate the same predicate on the same records, so every rank lies below the total.  Samples at or past M are not
+// known.  Sample numbers and the byte offsets made of them are 64 bit throughout (rec of 2^28 samples is 4 GiB).
+#define SEL_ROUNDS (TAROK_LEARN_SELECT_TILE / TK_BLOCK)
+#define SEL_WAVE (64 * SEL_ROUNDS)
+static_assert(TK_BLOCK == 256 && TAROK_LEARN_SELECT_TILE % TK_BLOCK == 0, "a tile is whole rounds of the four waves");
+// the ballots of the wave's rounds (all loads in flight at once) and, bit r of `mine`, whether the lane's own sample of
+// round r is known; returns how many of the wave's samples are known
+__device__ __forceinline__ u32 select_ballots(int64_t M, const float4 *__restrict__ rec, int64_t wave0, u64 (&b)[SEL_ROUNDS], u32 &mine) {
+    const u32 lane = threadIdx.x & 63;
+    u32 w[SEL_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < SEL_ROUNDS; r++) {
+        int64_t j = wave0 + 64 * r + lane;
+        w[r] = j < M ? reinterpret_cast<const u32 *>(rec + j)[3] : 0u;
+    }
+    u32 total = 0;
+    mine = 0;
+#pragma unroll
+    for (int r = 0; r < SEL_ROUNDS; r++) {
+        const u32 k = (w[r] >> 8) & 1u;
+        mine |= k << r;
+        b[r] = __ballot(k != 0u);
+        total += (u32)__popcll(b[r]);
+    }
+    return total;
+}
+TK_KERNEL(TK_BLOCK, 64) void k_select_count(int64_t M, const float4 *__restrict__ rec, u32 *__restrict__ tile_cnt) {
+    TK_VGPR_TOP(64, 63);
+    __shared__ u32 wtot[TK_BLOCK / 64];
+    const u32 wave = threadIdx.x >> 6;
+    u64 b[SEL_ROUNDS];
+    u32 mine;
+    u32 total = select_ballots(M, rec, (int64_t)blockIdx.x * TAROK_LEARN_SELECT_TILE + (int64_t)wave * SEL_WAVE, b, mine);
+    if ((threadIdx.x & 63) == 0) wtot[wave] = total;
+    __syncthreads();
+    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = (wtot[0] + wtot[1]) + (wtot[2] + wtot[3]);
+}
+// thread t owns tiles [per t, per (t + 1)): their sum, an exclusive scan of the 256 sums in LDS, then the prefixes
+TK_KERNEL(TK_BLOCK, 64) void k_select_scan(int64_t tiles, const u32 *__restrict__ tile_cnt, int64_t *__restrict__ tile_off,
+                                                         int64_t *__restrict__ count_out) {
+    TK_VGPR_TOP(64, 63);
+    __shared__ int64_t sums[TK_BLOCK];
+    const int64_t per = (tiles + TK_BLOCK - 1) / TK_BLOCK;
+    const int64_t k0 = per * threadIdx.x < tiles ? per * threadIdx.x : tiles, k1 = k0 + per < tiles ? k0 + per : tiles;
+    int64_t s = 0;
+    for (int64_t k = k0; k < k1; k++) s += tile_cnt[k];
+    sums[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t run = 0;
+        for (int k = 0; k < TK_BLOCK; k++) { int64_t c = sums[k]; sums[k] = run; run += c; }
+        count_out[0] = run;
+    }
+    __syncthreads();
+    int64_t run = sums[threadIdx.x];
+    for (int64_t k = k0; k < k1; k++) { tile_off[k] = run; run += tile_cnt[k]; }
+}
+TK_KERNEL(TK_BLOCK, 64) void k_select_scatter(int64_t M, const float4 *__restrict__ rec, const int64_t *__restrict__ tile_off,
+                                                            int64_t *__restrict__ index_out) {
+    TK_VGPR_TOP(64, 63);
+    __shared__ u32 wtot[TK_BLOCK / 64];
+    const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t wave0 = (int64_t)blockIdx.x * TAROK_LEARN_SELECT_TILE + (int64_t)wave * SEL_WAVE;
+    u64 b[SEL_ROUNDS];
+    u32 mine;
+    u32 total = select_ballots(M, rec, wave0, b, mine);
+    if (lane == 0) wtot[wave] = total;
+    __syncthreads();
+    int64_t at = tile_off[blockIdx.x];
+#pragma unroll
+    for (u32 k = 0; k < TK_BLOCK / 64 - 1; k++) at += k < wave ? wtot[k] : 0u;
+#pragma unroll
+    for (int r = 0; r < SEL_ROUNDS; r++) {
+        const u32 below = __builtin_amdgcn_mbcnt_hi((u32)(b[r] >> 32), __builtin_amdgcn_mbcnt_lo((u32)b[r], 0u));
+        if ((mine >> r) & 1u) index_out[at + below] = wave0 + 64 * r + lane;
+        at += (u32)__popcll(b[r]);
     }
 }
 

@@ -464,6 +464,32 @@ class TarokVecEnv:
                                                          self._p(val), self._p(act), float(reward_scale), float(gamma), float(lam),
                                                          self._p(rec), self._p(stats), self._p(scratch), self._stream()))
 
+    def learn_returns_seats(self, T, done, reward, words, logp, val, act, reward_scale, rec, stats, scratch, gae=False, gamma=1.0,
+                            lam=1.0, seats=15, seats_per_game=None):
+        """tarok_learn_returns_seats: the record of learn_returns (gae=False) or learn_returns_gae (gae=True) with `known`
+        masked by the learner's seats: seats (a 4-bit set for every slot) or seats_per_game ([N] uint8 device tensor of
+        sets), as in policy_step."""
+        if seats_per_game is not None:
+            spg = seats_per_game
+            if not (torch.is_tensor(spg) and spg.device == self.device and spg.dtype == torch.uint8 and spg.is_contiguous()
+                    and tuple(spg.shape) == (self.n,)):
+                raise ValueError("seats_per_game: a contiguous uint8 tensor [N] on the env's device")
+        with torch.cuda.device(self.device):
+            _native.check(self.L.tarok_learn_returns_seats(self._h, int(T), self._p(done), self._p(reward), self._p(words), self._p(logp),
+                                                           self._p(val), self._p(act), float(reward_scale), 1 if gae else 0, float(gamma),
+                                                           float(lam), int(seats), self._p(seats_per_game), self._p(rec), self._p(stats),
+                                                           self._p(scratch), self._stream()))
+
+    def learn_select_scratch_bytes(self, M):
+        return int(self.L.tarok_learn_select_scratch_bytes(int(M)))
+
+    def learn_select(self, M, rec, index_out, count_out, scratch):
+        """tarok_learn_select: index_out[:count] (int64 [M]) = the numbers of the known samples of rec [M,4], ascending;
+        count_out int64 [1] on the device; scratch: learn_select_scratch_bytes(M) bytes.  No host synchronisation."""
+        with torch.cuda.device(self.device):
+            _native.check(self.L.tarok_learn_select(self._h, int(M), self._p(rec), self._p(index_out), self._p(count_out),
+                                                    self._p(scratch), self._stream()))
+
     def learn_chain(self, B, words, index, rec, stats, clip, vf_coef, ent_coef, wf, bias, Xw, H1, H2, dOut, dH2, dH1, scratch, terms,
                     running=None):
         """wf: dict of the bf16 fragment-order weight copies (w1, w2, w3, w3t, w2t: learn_adam), bias: (b1, b2, b3) f32."""

@@ -15,6 +15,9 @@ Shape of the loop (per rank, one env shard each; games need no communication):
     gamma = 1), or, with SelfPlay(gamma=..., gae_lambda=...), per-seat GAE bootstrapped from the
     seat's next decision; clipped-surrogate PPO update; gradients summed over ranks in ONE flattened
     all-reduce per minibatch (a few hundred KB: latency-bound, so one bucket, not many).
+
+SelfPlay(env, opponent=snapshot) trains against a frozen opponent instead: per slot some seats are the learner's, the
+others play the snapshot (tarok_policy_step_versus), and only the learner's samples reach the update.
 """
 import time
 
@@ -109,12 +112,20 @@ def sample_masked(logits, legal, generator=None):
     return torch.where(none, torch.full_like(action, 255), action), torch.where(none, torch.zeros_like(logp), logp)
 
 
-def assign_returns(done, reward, seat):
+def learner_moves(seat, learner):
+    """bool [T,N]: the seat that played at t is one of the learner's seats of its slot.  seat [T,N]; learner [N] uint8:
+    one 4-bit seat set per slot (bit s: seat s is the learner's; bits 4..7 are ignored)."""
+    return ((learner.to(device=seat.device, dtype=torch.int64).unsqueeze(0) >> seat.long()) & 1).bool()
+
+
+def assign_returns(done, reward, seat, learner=None):
     """Credit every transition with its seat's final score of the game it belongs to.
 
     done [T,N] bool: the card played at t finished a game; reward [T,N,4]: scores by seat,
     valid where done; seat [T,N]: who played at t.  Returns (ret [T,N] f32, known [T,N] bool):
-    `known` is False for the cards of games still unfinished when the rollout ends."""
+    `known` is False for the cards of games still unfinished when the rollout ends.
+    learner ([N] uint8 seat sets, learner_moves): `known` is also False where another seat than the learner's played
+    (tarok_learn_returns_seats); the returns are the same."""
     T, N = done.shape
     ret = torch.zeros((T, N), dtype=torch.float32, device=done.device)
     known = torch.zeros((T, N), dtype=torch.bool, device=done.device)
@@ -126,6 +137,8 @@ def assign_returns(done, reward, seat):
         have = have | d
         ret[t] = cur.gather(-1, seat[t].long().unsqueeze(-1)).squeeze(-1)
         known[t] = have
+    if learner is not None:
+        known &= learner_moves(seat, learner)
     return ret, known
 
 
@@ -163,6 +176,16 @@ def assign_gae(done, reward, seat, val, gamma, lam, reward_scale):
         mine = seats == s
         nv, na, pr = torch.where(mine, v.unsqueeze(-1), nv), torch.where(mine, a.unsqueeze(-1), na), torch.where(mine, zero, pr)
         have = have | mine
+    return ret, known
+
+
+def assign_gae_seats(done, reward, seat, val, gamma, lam, reward_scale, learner=None):
+    """assign_gae with `known` masked by the learner's seats (learner [N] uint8 seat sets as in assign_returns; None:
+    assign_gae itself): the plain torch statement of tarok_learn_returns_seats with gae = 1.  The walk is assign_gae's
+    for every seat — a seat's chain reads that seat's values only — so the returns are the same."""
+    ret, known = assign_gae(done, reward, seat, val, gamma, lam, reward_scale)
+    if learner is not None:
+        known &= learner_moves(seat, learner)
     return ret, known
 
 
@@ -222,11 +245,28 @@ class SelfPlay:
     launched on torch's capture stream) and replayed: per lock-step ONE tarok_policy_mlp launch
     (features -> MLP on the matrix cores -> masked sample, hidden = 256) and one tarok_step
     launch, both writing straight into their rows of static rollout buffers.  With another
-    hidden size the policy runs as tarok_observe -> torch GEMMs -> tarok_sample_policy."""
+    hidden size the policy runs as tarok_observe -> torch GEMMs -> tarok_sample_policy.
+
+    opponent (a snapshot()): train against that frozen network instead of against oneself.  Per slot the seats of
+    `learner_seats` play and learn the current weights, the others play the opponent (tarok_policy_step_versus: needs
+    the fused policy and the fused step); only the learner's samples are `known` to the update
+    (tarok_learn_returns_seats), and the fused update compacts them (tarok_learn_select) so that its minibatches hold
+    nothing else.  learner_seats: an int 0..15 (one seat set for every slot) or a [N] uint8 tensor of sets; default:
+    slot g owns the single seat (game_offset + g) % 4, so a sharded run seats the same games the same way.
+    set_opponent() swaps the opponent's weights without a new graph capture."""
 
     def __init__(self, env, hidden=256, lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.01, reward_scale=1.0 / 70.0, seed=0,
                  use_graph=True, fused=None, fused_loss=None, fused_step=None, fused_learner=None, max_grad_norm=1.0,
-                 gamma=None, gae_lambda=None):
+                 gamma=None, gae_lambda=None, opponent=None, learner_seats=None):
+        if opponent is None and learner_seats is not None:
+            raise ValueError("learner_seats says which seats learn against an opponent: pass opponent= (a snapshot()) as well")
+        if opponent is not None:
+            is_fused = (hidden == 256) if fused is None else bool(fused)
+            if not is_fused or not (is_fused if fused_step is None else bool(fused_step)):
+                raise RuntimeError("an opponent is seated by tarok_policy_step_versus, which needs the fused policy (hidden = 256) "
+                                   "and the fused step")
+            if isinstance(learner_seats, int) and not 0 <= learner_seats <= 15:
+                raise ValueError("learner_seats: a seat set 0..15 or a [N] uint8 tensor of sets")
         self.env = env
         # returns: both None = every card credited with its seat's final score (Monte-Carlo: assign_returns /
         # tarok_learn_returns); either set = per-seat GAE(gamma, lambda), the other defaulting to 1.0 (assign_gae /
@@ -270,6 +310,18 @@ class SelfPlay:
         assert not self.fused_learner or self.fused, "the fused learner is built for the fused policy (hidden = 256)"
         self._graph, self._buf, self._T = None, None, 0
         self._w = None                                # rollout copies of the weights (bf16) / biases (f32)
+        # opponent mode: copies of the opponent's six tensors that belong to this object (the captured rollout reads them,
+        # set_opponent writes them, no update ever does) and the learner's seat set of every slot
+        self._opp, self._seats = None, None
+        if opponent is not None:
+            self._opp = [t.detach().to(self.device).clone().contiguous() for t in env.check_mlp_weights(opponent)]
+            if learner_seats is None:
+                learner_seats = (1 << ((torch.arange(env.n, dtype=torch.int64) + env.game_offset) % 4)).to(torch.uint8)
+            elif not torch.is_tensor(learner_seats):
+                learner_seats = torch.full((env.n,), int(learner_seats), dtype=torch.uint8)
+            if learner_seats.dtype != torch.uint8 or tuple(learner_seats.shape) != (env.n,):
+                raise ValueError("learner_seats: a seat set 0..15 or a [N] uint8 tensor of sets")
+            self._seats = learner_seats.detach().to(self.device).clone().contiguous()
         self._learn = None                            # the fused learner's buffers
         if self.fused_learner:
             dev = self.device
@@ -317,6 +369,15 @@ class SelfPlay:
         return tuple(t.detach().clone().contiguous() for t in self._w)
 
     @torch.no_grad()
+    def set_opponent(self, weights):
+        """Replace the frozen opponent by `weights` (a snapshot()): copied IN PLACE into the tensors the captured rollout
+        graph reads, so the next collect() plays the new opponent without a new capture."""
+        if self._opp is None:
+            raise RuntimeError("set_opponent() needs a SelfPlay made with opponent=")
+        for dst, src in zip(self._opp, self.env.check_mlp_weights(weights)):
+            dst.copy_(src)
+
+    @torch.no_grad()
     def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None):
         """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
         weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
@@ -353,6 +414,11 @@ class SelfPlay:
     def _rollout_body(self, T):
         env, buf, w = self.env, self._buf, self._w
         for t in range(T):
+            if self._opp is not None:                 # the learner's seats play w, the others the frozen opponent
+                env.policy_step(w, buf["words"][t], buf["words"][t + 1], buf["act"][t], buf["logp"][t], buf["val"][t],
+                                feature_words_out=buf["obs"][t], reward_out=buf["reward"][t], done_out=buf["done"][t],
+                                opponent=self._opp, seats_per_game=self._seats)
+                continue
             if self.fused and self.fused_step:
                 env.policy_step(w, buf["words"][t], buf["words"][t + 1], buf["act"][t], buf["logp"][t], buf["val"][t],
                                 feature_words_out=buf["obs"][t], reward_out=buf["reward"][t], done_out=buf["done"][t])
@@ -411,9 +477,10 @@ class SelfPlay:
         words_t = buf["words"][:T]
         seat = (words_t >> K.OBS_SEAT_SHIFT) & 3
         if self.gae:
-            ret, known = assign_gae(buf["done"].bool(), buf["reward"], seat, buf["val"], self.gamma, self.gae_lambda, self.reward_scale)
+            ret, known = assign_gae_seats(buf["done"].bool(), buf["reward"], seat, buf["val"], self.gamma, self.gae_lambda, self.reward_scale,
+                                          learner=self._seats)
         else:
-            ret, known = assign_returns(buf["done"].bool(), buf["reward"], seat)
+            ret, known = assign_returns(buf["done"].bool(), buf["reward"], seat, learner=self._seats)
             ret = ret * self.reward_scale
         flat = lambda x: x.reshape(T * n, *x.shape[2:])
         obs, words, act, logp0 = flat(buf["obs"]), flat(words_t), flat(buf["act"]).long(), flat(buf["logp"])
@@ -425,6 +492,8 @@ class SelfPlay:
         std = (((adv - mean) ** 2 * m).sum() / m.sum().clamp(min=1)).sqrt().clamp(min=1e-6)
         adv = (adv - mean) / std
         stats = dict(loss=0.0, pi_loss=0.0, v_loss=0.0, entropy=0.0, allreduce_bytes=0, known_frac=float(m.mean()))
+        if self._opp is not None:                     # (the weights m carry the seat mask: the opponent's samples count for nothing)
+            stats["learner_samples"] = int(known.sum())
         sums = torch.zeros(4, dtype=torch.float32, device=self.device)     # loss terms summed on the device: no host sync per minibatch
         params = [p for p in self.net.parameters()]
         count = 0
@@ -506,13 +575,31 @@ class SelfPlay:
         minibatch the forward + loss + backward chain (activations in LDS, bf16 MFMA), the three weight gradients
         as one split-K launch (one per row range of dw_ranges past TAROK_LEARN_MAX_BATCH samples), ONE flat gradient
         all-reduce, and clip + Adam + weight-copy refresh in one launch.  No host synchronisation until the statistics
-        are read at the end."""
+        are read at the end.
+        Opponent mode: tarok_learn_returns_seats knows the learner's samples only, tarok_learn_select compacts their
+        numbers into a list, and ONE host read of the list's length follows — the single synchronisation opponent mode
+        adds, per update: the epoch permutation runs over that many entries (not over M), and every minibatch's index
+        is a run of it mapped through the list, so no launch computes an opponent's sample."""
         env = self.env
         T, n = buf["act"].shape
         M = T * n
         B = -(-M // minibatches)
         lb = self._learn_bufs(M, B)
-        if self.gae:
+        sel, count = None, M
+        if self._opp is not None:
+            env.learn_returns_seats(T, buf["done"], buf["reward"], buf["words"][:T], buf["logp"], buf["val"], buf["act"],
+                                    self.reward_scale, lb["rec"], lb["stats"], lb["scratch"], gae=self.gae, gamma=self.gamma,
+                                    lam=self.gae_lambda, seats_per_game=self._seats)
+            if "sel" not in lb:
+                lb["sel"] = torch.empty(M, dtype=torch.int64, device=self.device)
+                lb["sel_count"] = torch.zeros(1, dtype=torch.int64, device=self.device)
+                lb["sel_scratch"] = torch.empty(env.learn_select_scratch_bytes(M), dtype=torch.uint8, device=self.device)
+            env.learn_select(M, lb["rec"], lb["sel"], lb["sel_count"], lb["sel_scratch"])
+            count = int(lb["sel_count"].item())       # the one host read
+            sel = lb["sel"]
+            if count == 0:                            # nothing of the learner's: no launch, no step
+                return dict(loss=0.0, pi_loss=0.0, v_loss=0.0, entropy=0.0, allreduce_bytes=0, known_frac=0.0, learner_samples=0)
+        elif self.gae:
             env.learn_returns_gae(T, buf["done"], buf["reward"], buf["words"][:T], buf["logp"], buf["val"], buf["act"],
                                   self.reward_scale, self.gamma, self.gae_lambda, lb["rec"], lb["stats"], lb["scratch"])
         else:
@@ -523,8 +610,10 @@ class SelfPlay:
         nbytes = 0
         bias = (self._w[1], self._w[3], self._w[5])
         for _ in range(epochs):
-            perm = self._epoch_permutation(M)
+            perm = self._epoch_permutation(count)
             for idx in perm.chunk(minibatches):
+                if sel is not None:
+                    idx = sel[idx]
                 b = idx.numel()
                 env.learn_chain(b, words, idx, lb["rec"], lb["stats"], self.clip, self.vf_coef, self.ent_coef, self._wf, bias,
                                 lb["Xw"], lb["H1"], lb["H2"], lb["dOut"], lb["dH2"], lb["dH1"], lb["scratch"], lb["terms"], lb["running"])
@@ -536,8 +625,11 @@ class SelfPlay:
         run = lb["running"].tolist()
         cnt = max(1.0, run[3])
         pi, v, ent = run[0] / cnt, run[1] / cnt, run[2] / cnt
-        return dict(loss=pi + self.vf_coef * v - self.ent_coef * ent, pi_loss=pi, v_loss=v, entropy=ent, allreduce_bytes=nbytes,
-                    known_frac=float(lb["stats"][2]))
+        stats = dict(loss=pi + self.vf_coef * v - self.ent_coef * ent, pi_loss=pi, v_loss=v, entropy=ent, allreduce_bytes=nbytes,
+                     known_frac=float(lb["stats"][2]))
+        if sel is not None:
+            stats["learner_samples"] = count
+        return stats
 
     def iterate(self, T=48, epochs=2, minibatches=8):
         """One rollout + one update, timed.  Returns stats incl. env steps/s of the rollout and of the whole
@@ -554,4 +646,8 @@ class SelfPlay:
                      rollout_steps_per_s=T * self.env.n / (t1 - t0), iteration_steps_per_s=T * self.env.n / (t2 - t0),
                      mean_score=float(buf["reward"].float().sum() / buf["done"].float().sum().clamp(min=1) / 4),
                      env_errors=int((buf["words"] < 0).any()))
+        if self._opp is not None:                     # mean final score over the learner's seats of the games that ended
+            mine = ((self._seats.long().unsqueeze(-1) >> torch.arange(4, device=self.device)) & 1).float()      # [N,4]
+            w = buf["done"].float().unsqueeze(-1) * mine
+            stats["learner_mean_score"] = float((buf["reward"].float() * w).sum() / w.sum().clamp(min=1))
         return stats
