@@ -119,7 +119,9 @@ def _chain_vs_autograd(T, B, n=2048, steps=3, indexed=True, known_p=0.8, wscale=
     hidden gradients and every weight and bias gradient.  indexed: the samples are gathered through a random index
     (else index NULL: sample j = row j); known_p: share of samples whose game ended (weight 1); wscale: the factor on
     torch's initial weights (10: near one-hot softmax, ratios clipped on both sides).  The padding rows of every array
-    the chain writes hold a sentinel that must survive the launch (its tile stores are bounds-checked per row)."""
+    the chain writes hold a sentinel that must survive the launch (its tile stores are bounds-checked per row).
+    The bounds on dOut, dH2 and dH1 here are one number per array, scaled by the array's largest entry; the per-element
+    statement (every term of the loss gradient, every ReLU mask) lives in tests/test_gpu_loss_exact.py."""
     import torch
     import torch.nn.functional as F
     from tarok_amd import selfplay as SP

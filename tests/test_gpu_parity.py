@@ -780,7 +780,9 @@ def test_policy_step_kernel_equals_policy_then_step(T, S):
 
 def test_ppo_loss_kernel_vs_torch(T, S):
     """tarok_ppo_loss (clipped surrogate + value loss - entropy over the legal cards, forward and
-    gradient in one pass) vs the same loss written with torch ops and differentiated by autograd."""
+    gradient in one pass) vs the same loss written with torch ops and differentiated by autograd.
+    The bound on dout is one number for the array, scaled by its largest entry; the per-element statement (policy,
+    entropy and value gradient each on its own) lives in tests/test_gpu_loss_exact.py."""
     import torch
     import torch.nn.functional as F
     from tarok_amd import selfplay as SP
