@@ -14,6 +14,12 @@ DEPS = [SRC, os.path.join(HERE, "csrc", "tarok_device.h"), os.path.join(HERE, "c
         os.path.join(ROOT, "include", "tarok_env.h")]
 LIB_PATH = os.path.join(HERE, "libtarokenv.so")
 ARCH = "gfx950"
+# -amdgpu-kernarg-preload-count: the first kernel arguments arrive in scalar registers with the dispatch
+# instead of behind a scalar load at the top of the kernel (0.1-0.2 us of every latency-bound launch:
+# profiles/r04_ab_step.txt); firmware without the feature runs the kernels' own load prologue
+# (tools that disassemble the library's source — tools/trick_loop_isa.py — compile with these flags too)
+COMPILE_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-mllvm", "-amdgpu-kernarg-preload-count=16",
+                 "-I", os.path.join(ROOT, "include")]
 
 SYMBOLS = [
     "tarok_strerror", "tarok_abi_version", "tarok_device_count", "tarok_last_hip_error",
@@ -58,12 +64,7 @@ def build(force=False, verbose=False):
         try:
             if force or needs_build():
                 tmp = "%s.tmp.%d" % (LIB_PATH, os.getpid())
-                # -amdgpu-kernarg-preload-count: the first kernel arguments arrive in scalar registers with the dispatch
-                # instead of behind a scalar load at the top of the kernel (0.1-0.2 us of every latency-bound launch:
-                # profiles/r04_ab_step.txt); firmware without the feature runs the kernels' own load prologue
-                cmd = [hipcc_path(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-shared", "-fPIC",
-                       "-mllvm", "-amdgpu-kernarg-preload-count=16",
-                       "-I", os.path.join(ROOT, "include"), "-o", tmp, SRC]
+                cmd = [hipcc_path()] + COMPILE_FLAGS + ["-shared", "-fPIC", "-o", tmp, SRC]
                 if verbose:
                     print(" ".join(cmd))
                 try:

@@ -97,6 +97,9 @@ __device__ __forceinline__ void unpack_fresh(Game &g, u64 x0, u64 x1, u64 y0, u6
     g.team = m3 & 15; g.epar = (m3 >> 4) & 15; g.cprev = 0;
 }
 
+// (g.C must be a clean plane here, bits 54-63 zero: the trick-aligned card loops keep TK_C_PAD set in their working
+// copy — hand_of<true> — and take it off before the plane reaches pack_play / store_game or, through the finished-games
+// ring, score_game.  A padded plane would be or-ed over nt, leader, trick_no and phase.)
 __device__ __forceinline__ void pack_play(const Game &g, u64 &x0, u64 &x1) {
     x0 = g.C | ((u64)(g.nt | (g.leader << 2) | (g.trick_no << 4) | (g.phase << 8)) << 54);
     x1 = g.talon | ((u64)g.trick << 36) | ((u64)g.tl << 60) | ((u64)g.error << 63);
@@ -129,12 +132,17 @@ __device__ __forceinline__ u64 seat_cards(const Game &g, u32 s) {
 }
 // hand of seat s = ~C & (A == s&1) & (B == s>>1): with ma / mb = all-ones when the seat bit is
 // set, (A xnor ma) & (B xnor mb) & ~C is two v_bitop3 per 32-bit half
+// C_PADDED: the caller keeps the ten bits above the deck of the C plane's high word set (TK_C_PAD; the trick-aligned
+// card loops do, from their first card to their last): ~C then clears them in every hand, without the mask
+#define TK_C_PAD (0xFFC00000ULL << 32)
+template <bool C_PADDED = false>
 __device__ __forceinline__ u64 hand_of(const Game &g, u32 s) {
     u32 ma = (u32)((int)(s << 31) >> 31), mb = (u32)((int)(s << 30) >> 31);
     u32 tl = TK_BITOP3(TK_LO(g.A), ma, TK_LO(g.C), ~c_ & ~(a_ ^ b_));
     u32 th = TK_BITOP3(TK_HI(g.A), ma, TK_HI(g.C), ~c_ & ~(a_ ^ b_));
     u32 hl = TK_BITOP3(tl, TK_LO(g.B), mb, a_ & ~(b_ ^ c_));
-    u32 hh = TK_BITOP3(th, TK_HI(g.B), mb, a_ & ~(b_ ^ c_)) & 0x3FFFFFu;
+    u32 hh = TK_BITOP3(th, TK_HI(g.B), mb, a_ & ~(b_ ^ c_));
+    if (!C_PADDED) hh &= 0x3FFFFFu;
     return TK_U64(hl, hh);
 }
 // won pile of seat S (incl. whatever is parked in its pile bits): C & (A == S&1) & (B == S>>1)
@@ -208,6 +216,26 @@ __device__ __forceinline__ u64 legal_mask(u64 hand, bool has_lead, u32 lead, u32
     u32 bh = hh & zs;
     u32 kf = (0x281u >> contract) & 1u;                 // Klop, Berac, Odprti berac: the pagat only when nothing else goes
     u32 only_pagat = tk_zero_mask(bl | (bh & ~1u));
+    return TK_U64(bl, TK_BITOP3(bh, kf, only_pagat, a_ & ~(b_ & ~c_)));
+}
+
+// The same rule for a seat that FOLLOWS (somebody has led).  Then all legal cards lie in one word: cards of the suit
+// led or, without taroks, the whole hand — the low word; taroks, when the seat has no card of the suit (the pagat rule
+// only ever clears bit 0 of them) — the high word.  hi_sel: all ones when it is the high word, else zero.
+__device__ __forceinline__ u64 legal_mask_follow(u64 hand, u32 lead, u32 contract, u32 &hi_sel) {
+    u32 hl = TK_LO(hand), hh = TK_HI(hand);
+    u32 tarok_led = (u32)((int)(lead << 26) >> 31);
+    u32 s = TK_BITOP3(hl, 0xFFu << (lead & 24), tarok_led, a_ & b_ & ~c_);
+    u32 zs = tk_zero_mask(s);                           // no card of the suit led
+    u32 zt = tk_zero_mask(hh);                          // no taroks
+    u32 bl = s | TK_BITOP3(hl, zs, zt, a_ & b_ & c_);
+    u32 bh = hh & zs;
+    u32 kf = (0x281u >> contract) & 1u;
+    u32 only_pagat = tk_zero_mask(bl | (bh & ~1u));
+    // zs & ~zt, as one opaque bit operation and pinned as a word: left to itself the compiler recognises the two sign
+    // smears behind it and rebuilds this line, or the pick's last step hi_sel & 32, as a compare and a select — the
+    // pair this rule code is written to avoid (see above)
+    hi_sel = TK_BITOP3(zs, zt, zt, a_ & ~b_);           TK_KEEP_VGPR(hi_sel);
     return TK_U64(bl, TK_BITOP3(bh, kf, only_pagat, a_ & ~(b_ & ~c_)));
 }
 
@@ -488,9 +516,27 @@ __device__ __forceinline__ u32 kth_bit(u64 m, u32 k) {
     return p | (s0 & 32u);
 }
 
+// kth_bit for a mask that lies in one word (legal_mask_follow): w = low word | high word, hi_sel = all ones when
+// it is the high one.  No first level — nothing to count to tell the words apart; the five levels on w as above.
+__device__ __forceinline__ u32 kth_bit_word(u32 w, u32 hi_sel, u32 k) {
+    u32 nk = ~k;
+    u32 p = ((u32)__popc(w & 0xFFFFu) + nk) >> 31;
+#pragma unroll
+    for (int s = 3; s >= 0; s--) {
+        u32 q = (p << (s + 1)) | (1u << s);
+        u32 d = (u32)__popc(__builtin_amdgcn_ubfe(w, 0, q)) + nk;
+        p = (p << 1) | (d >> 31);
+    }
+    return p | (hi_sel & 32u);
+}
+
 // uniform card among the legal ones (Bot_igralec.igraj_karto, Igralec.py:158-159)
 __device__ __forceinline__ u32 policy_action(u64 key, u32 step, u64 mask) {
     return kth_bit(mask, pick(rng32(key, 128 + step), (u32)popc64(mask)));
+}
+// the same draw from a follower's one-word mask: one popcount, one-word pick
+__device__ __forceinline__ u32 policy_action_follow(u64 key, u32 step, u32 w, u32 hi_sel) {
+    return kth_bit_word(w, hi_sel, pick(rng32(key, 128 + step), (u32)__popc(w)));
 }
 
 // One bidding round between four Bot players (TAROK_MIX_BOT): the control flow of

@@ -561,7 +561,8 @@ __device__ __forceinline__ void play_role(
         if (lane < cnt_) {
             u32 e = (fq_head + lane) & (TK_FINQ - 1);
             Game f;
-            f.A = TK_U64(fq[0][e], fq[1][e]); f.B = TK_U64(fq[2][e], fq[3][e]); f.C = TK_U64(fq[4][e], fq[5][e]);
+            // (the trick-aligned loops push their C plane as they keep it, TK_C_PAD set: cleaned here, once per 64 games)
+            f.A = TK_U64(fq[0][e], fq[1][e]); f.B = TK_U64(fq[2][e], fq[3][e]); f.C = TK_U64(fq[4][e], fq[5][e] & 0x3FFFFFu);
             u32 m = fq[7][e], ri = fq[8][e];
             f.talon = TK_U64(fq[6][e], (m >> 24) & 15u);
             f.contract = m & 15; f.declarer = (m >> 4) & 3; f.king = (m >> 6) & 3; f.team = (m >> 8) & 15;
@@ -644,6 +645,7 @@ __device__ __forceinline__ void play_role(
     // card c+1: computed once per card, carried in a register
     u64 legal = (valid && g.phase == TK_PHASE_PLAY) ? legal_now(g) : 0;
     u64 c_lead = 0;
+    u32 legal_hi = 0;                        // trick-aligned loops, cards 1..3: which word of `legal` holds the cards (legal_mask_follow)
     u64 pending = 0;                         // (wave uniform) lanes that came out of a swap without a line for their next game
     u32 blocked_v = 0, resync_v = 0;         // `blocked` / `resync` of the fast-renewal loop, as numbers (a bool carried through a loop is a
                                              // lane mask, merged with three scalar instructions at every join, used or not)
@@ -694,7 +696,11 @@ __device__ __forceinline__ void play_role(
         }
         const bool v = ALL ? true : valid;
         const bool play = ALL ? true : (valid && g.phase == TK_PHASE_PLAY);
-        u32 a = play ? policy_action(key, g.trick_no * 4 + g.nt, legal) : 255u;
+        // (trick-aligned loops: g.C carries TK_C_PAD from the first card to the last, see tricks() below)
+        constexpr bool ALIGNED = ALL && NT >= 0;
+        u32 a;
+        if constexpr (ALL && NT >= 1) a = policy_action_follow(key, g.trick_no * 4 + g.nt, TK_LO(legal) | TK_HI(legal), legal_hi);
+        else a = play ? policy_action(key, g.trick_no * 4 + g.nt, legal) : 255u;
         u64 scores = 0;
         u32 trick_info = 0;
         int res = -2;
@@ -738,6 +744,7 @@ __device__ __forceinline__ void play_role(
         };
         auto swap_in = [&]() __attribute__((always_inline)) {                   // (lanes that hold their next game's line)
             unpack_fresh(g, na.x, na.y, nb.x, nb.y);  // carries epar of the new game
+            if constexpr (ALIGNED) g.C |= TK_C_PAD;
             key = nkey;
             na = na2; nb = nb2; nkey = nkey2;
             nep1 = nep2;
@@ -838,7 +845,9 @@ __device__ __forceinline__ void play_role(
             }
         }
         // (ALL: a finished game has been replaced just above, so every lane is in play again)
-        legal = (ALL || (v && g.phase == TK_PHASE_PLAY)) ? legal_now(g) : 0;
+        if constexpr (ALIGNED && NT < 3) legal = legal_mask_follow(hand_of<true>(g, (g.leader + g.nt) & 3), g.trick & 63, g.contract, legal_hi);
+        else if constexpr (ALIGNED) legal = legal_mask(hand_of<true>(g, g.leader), false, 0u, g.contract);
+        else legal = (ALL || (v && g.phase == TK_PHASE_PLAY)) ? legal_now(g) : 0;
         if (v) {
             // (ALL: res is 0 or 1 — the number itself goes into the observation's bit 62 and the done row, no selects)
             const u32 fin01 = ALL ? (u32)res : (fin ? 1u : 0u);
@@ -857,12 +866,17 @@ __device__ __forceinline__ void play_role(
         if ((cards & 3) == 0 && __ballot(g.nt != 0) == 0) {
             auto tricks = [&](auto std_tag) __attribute__((always_inline)) {
                 touched = true; seats_dirty = true;          // (cards >= 4: every lane plays a whole trick)
+                // the C plane's high word keeps the ten bits above the deck set for the length of the loop: every hand
+                // comes out of ~C without them (hand_of<true>).  The trick's cards are the plane's gain (c_lead carries
+                // the bits too); the plane is cleaned where it leaves: below, and where a finished game is scored.
+                g.C |= TK_C_PAD;
                 for (int c = 0; c < cards; c += 4) {
                     play_card(std::true_type{}, std::integral_constant<int, 0>{}, std_tag, row, c); row += stride;
                     play_card(std::true_type{}, std::integral_constant<int, 1>{}, std_tag, row, c + 1); row += stride;
                     play_card(std::true_type{}, std::integral_constant<int, 2>{}, std_tag, row, c + 2); row += stride;
                     play_card(std::true_type{}, std::integral_constant<int, 3>{}, std_tag, row, c + 3); row += stride;
                 }
+                g.C &= TK_DECK;
             };
             if (action_out && done && !trick) tricks(std::true_type{});
             else tricks(std::false_type{});
