@@ -29,6 +29,7 @@
 #include "tarok_device.h"
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -608,29 +609,47 @@ __device__ __forceinline__ void play_role(
     u32 allowed = TK_AHEAD - min(cprev0, (u32)TK_AHEAD);
     int4 acc = make_int4(0, 0, 0, 0);
     u32 cur_ep = 0;
-    // (na, nb, nkey, nep1): the line of the next game (episode cur_ep + 1), (na2, nb2, nkey2, nep2): of the
-    // one after it.  ok1 / ok2: the line has been requested (and was one this launch may take); its episode tag
-    // is compared when it is taken, so that nothing waits for the load where it is issued (line_tag).  Both
-    // are loaded here, before the loop, and topped up at the first card of a trick (below) — never across the
-    // loop's back edge: a load in flight there would make every iteration wait for the previous iteration's
-    // stores (vmcnt counts both, in order)
+    // (na, nb, nkey, nep1): the line of the next game (episode cur_ep + 1).  The trick-aligned loops hold this ONE
+    // line: a lane that takes it fetches the next at the first card of the following trick (below), and whether a
+    // lane holds its line is read off the tag (nep1 == cur_ep + 1).  The loops that are not trick-aligned have no
+    // such place to fetch from and keep a second line, (na2, nb2, nkey2, nep2): the game after the next, with
+    // ok1 / ok2: the line has been requested (and was one this launch may take).  A tag is compared when the line
+    // is taken, so that nothing waits for the load where it is issued (line_tag).  The lines are loaded here,
+    // before the loop, and inside it at a trick's first card, to be taken at its 4th.  Across the loop's back edge
+    // the rule is: the TAG has landed (the 4th card votes on it on every trick), so the next trick's compare of it
+    // waits for nothing.  The two pair loads issued behind the tag's are waited for only where a lane takes them;
+    // after a trick in which no lane of the wave finished they are formally still in flight at the back edge and
+    // are waited for inside the next fetch, whose registers they write — behind the twelve stores of a trick
+    // (vmcnt counts loads and stores in order), ~1,400 cycles after they were issued: nothing stalls there.  What
+    // must not happen is a load ISSUED late in a trick and consumed early in the next: every iteration would
+    // wait for the previous iteration's stores
     ulonglong2 na = make_ulonglong2(0, 0), nb = na, na2 = na, nb2 = na;
     u64 nkey = 0, nkey2 = 0;
     u32 nep1 = 0, nep2 = 0;
     bool ok1 = false, ok2 = false;
     auto line_tag = [&](bool &ok, u32 &nep, u32 tag) __attribute__((always_inline)) { nep = tag; ok = true; };
+    // a line in three loads: the two packed pairs, and the key with the tag behind it — twelve bytes of the line's
+    // third 16, in three registers (a 16-byte load's fourth register is dead from the start: the allocator hands it
+    // to the next instruction that needs one, which then waits for the load to land — at the card that issued it)
+    static_assert(offsetof(AuxLine, nkey) == 32 && offsetof(AuxLine, nep) == 40, "key and tag share the line's third 16 bytes");
+    auto load_line = [&](const AuxLine *ln, ulonglong2 &a, ulonglong2 &b, u64 &k, bool &ok, u32 &nep) __attribute__((always_inline)) {
+        a = ln->n01; b = ln->n23;
+        uint3 kt = *reinterpret_cast<const uint3 *>(__builtin_assume_aligned(&ln->nkey, 16));
+        k = TK_U64(kt.x, kt.y);
+        line_tag(ok, nep, kt.z);
+    };
+    // With auto-reset a lane that is in play stays in play (a finished game is replaced within the same card), and
+    // games are whole tricks long: a wave whose lanes all start a launch of whole tricks at a trick boundary plays
+    // the trick-aligned loop (below) — known here, where it decides how many lines are loaded ahead.
+    const bool all_play = autoreset && __ballot(valid && g.phase == TK_PHASE_PLAY) == ~0ULL;
+    const bool aligned = all_play && (cards & 3) == 0 && __ballot(g.nt != 0) == 0;
     if (spec) {
         acc = cnt[i].score_sum;
         cur_ep = cnt[i].episode;
         if (autoreset && allowed > 0) {
-            const AuxLine *ln = &aux[i].line[TK_LINE(g.epar + 1)];
-            na = ln->n01; nb = ln->n23; nkey = ln->nkey;
-            line_tag(ok1, nep1, ln->nep);
-            if (allowed > 1 && cards > 4) {          // a Berac can be over after 4 cards
-                const AuxLine *l2 = &aux[i].line[TK_LINE(g.epar + 2)];
-                na2 = l2->n01; nb2 = l2->n23; nkey2 = l2->nkey;
-                line_tag(ok2, nep2, l2->nep);
-            }
+            load_line(&aux[i].line[TK_LINE(g.epar + 1)], na, nb, nkey, ok1, nep1);
+            if (!aligned && allowed > 1 && cards > 4)          // a Berac can be over after 4 cards
+                load_line(&aux[i].line[TK_LINE(g.epar + 2)], na2, nb2, nkey2, ok2, nep2);
         }
     }
     TK_WAIT_LOADS();                        // nothing in flight when the loop starts (see above)
@@ -646,21 +665,16 @@ __device__ __forceinline__ void play_role(
     u64 legal = (valid && g.phase == TK_PHASE_PLAY) ? legal_now(g) : 0;
     u64 c_lead = 0;
     u32 legal_hi = 0;                        // trick-aligned loops, cards 1..3: which word of `legal` holds the cards (legal_mask_follow)
-    u64 pending = 0;                         // (wave uniform) lanes that came out of a swap without a line for their next game
-    u32 blocked_v = 0, resync_v = 0;         // `blocked` / `resync` of the fast-renewal loop, as numbers (a bool carried through a loop is a
+    u32 resync_v = 0;                        // `resync` of the fast-renewal loop, as a number (a bool carried through a loop is a
                                              // lane mask, merged with three scalar instructions at every join, used or not)
+    // the fast-renewal loop's `allowed` and `blocked` in one number: how many games of this launch the lane may take
+    // from lines — none for a lane that cannot finish in this launch (its counters are not loaded), none any more
+    // once a game was dealt in place
+    u32 lim = spec ? allowed : 0u;
     // fill the line buffers of the lanes that lack them (lacks: the next game's, lacks2: the one after it)
     auto fetch_lines = [&](bool lacks, bool lacks2) __attribute__((always_inline)) {
-        if (lacks) {
-            const AuxLine *ln = &aux[i].line[TK_LINE(cur_ep + 1)];
-            na = ln->n01; nb = ln->n23; nkey = ln->nkey;
-            line_tag(ok1, nep1, ln->nep);
-        }
-        if (lacks2) {
-            const AuxLine *l2 = &aux[i].line[TK_LINE(cur_ep + 2)];
-            na2 = l2->n01; nb2 = l2->n23; nkey2 = l2->nkey;
-            line_tag(ok2, nep2, l2->nep);
-        }
+        if (lacks) load_line(&aux[i].line[TK_LINE(cur_ep + 1)], na, nb, nkey, ok1, nep1);
+        if (lacks2) load_line(&aux[i].line[TK_LINE(cur_ep + 2)], na2, nb2, nkey2, ok2, nep2);
     };
     auto play_card = [&](auto all_tag, auto nt_tag, auto std_tag, int64_t row, int ci) __attribute__((always_inline)) {
         // ALL: every lane of the wave is a valid slot with a game in play (wave uniform, see below):
@@ -673,25 +687,29 @@ __device__ __forceinline__ void play_role(
         constexpr int NT = decltype(nt_tag)::value;
         constexpr bool STD = decltype(std_tag)::value;
         if constexpr (NT >= 0) g.nt = (u32)NT;
-        // Trick-aligned loops: the lines of the next games are topped
-        // up HERE, at the first card of a trick, as soon as one lane has used its two up — three cards (~1,400
-        // cycles) before a game can end and take one: the memory round trip hides behind the rules, and the
-        // compiler's wait at the first use counts past the stores issued since.  (A lane's `consumed` only moves
-        // at a 4th card, so a lane that still lacks a line at the 4th card could not have fetched one: no fetch
-        // on the spot in these loops.)  With four waves on a SIMD the other waves hide the round trip of a
-        // fetch on the spot, and the earlier, more frequent top-ups only cost instructions (4 M games: -11 %).
+        // Trick-aligned loops: a lane that took its line at a 4th card fetches the line of its next game HERE, at the
+        // first card of the following trick — three cards (~1,400 cycles) before a game can end and take it, even a
+        // Berac that is over after one trick: the memory round trip hides behind the rules, and the compiler's
+        // wait at the first use counts past the stores issued since.  One line is therefore enough: a second,
+        // buffered one would be fetched at the same card and waited for at the same place.  (A lane's `consumed`
+        // only moves at a 4th card, so a lane that still lacks a line at the 4th card could not have fetched one:
+        // no fetch on the spot in these loops.)  With four waves on a SIMD the other waves hide the round trip of
+        // a fetch on the spot, and the earlier, more frequent fetches only cost instructions (4 M games: -11 %).
         constexpr bool TOP_UP_EARLY = ALL && NT == 0;
         constexpr bool TOP_UP_LATE = !(ALL && NT == 3);
         if constexpr (TOP_UP_EARLY) {
-            // (`pending`: set at a 4th card when a finishing lane came out of its swap without the next line —
-            // a scalar test here, not a vote on per-lane conditions at every trick.  Which lane holds which line
-            // is read off the tags: a lane holds the line of its next game if nep1 is that game's number.)
-            if (TK_RARE(pending != 0)) {
-                pending = 0;
-                bool base = spec && blocked_v == 0 && consumed >= 1;
-                bool lacks = base && nep1 != cur_ep + 1 && consumed < allowed;
-                bool lacks2 = base && nep2 != cur_ep + 2 && consumed + 1 < allowed;
-                fetch_lines(lacks, lacks2);
+            // (Which lane holds its line is read off the tag: nep1 is the number of the lane's next game, or the lane
+            // has no line.  No wave-uniform "somebody swapped" flag in front: with ~10 % of the slots finishing per
+            // trick it is set on nearly every trick.  The line's index follows the game's epar = TK_LINE(cur_ep): a
+            // compare, not a division by fourteen.  No `consumed >= 1` in the condition: it would only keep a lane whose
+            // PRELOADED line carries a stale tag — after one-card launches or a change of the refill fan, a handful of
+            // launches in an env's life — from asking for that line again, three loads per trick under its own exec
+            // bit until it finishes, deals in place and drops to lim = 0.  The tag stays stale (this launch's refill
+            // workgroups write only lines that `lim` excludes), so results are the same; the compare and its mask
+            // would be paid by every wave on every trick of every launch.)
+            if (nep1 != cur_ep + 1 && consumed < lim) {
+                u32 off = g.epar + 1 >= (u32)TK_AHEAD ? 0u : (g.epar + 1) * (u32)sizeof(AuxLine);
+                load_line(reinterpret_cast<const AuxLine *>(reinterpret_cast<const char *>(aux[i].line) + off), na, nb, nkey, ok1, nep1);
             }
         }
         const bool v = ALL ? true : valid;
@@ -746,8 +764,12 @@ __device__ __forceinline__ void play_role(
             unpack_fresh(g, na.x, na.y, nb.x, nb.y);  // carries epar of the new game
             if constexpr (ALIGNED) g.C |= TK_C_PAD;
             key = nkey;
-            na = na2; nb = nb2; nkey = nkey2;
-            nep1 = nep2;
+            // (trick-aligned loops: nothing moves up — the tag left behind is the game just taken, so the lane
+            // reads as being without a line until the next trick's first card has fetched one)
+            if constexpr (!ALIGNED) {
+                na = na2; nb = nb2; nkey = nkey2;
+                nep1 = nep2;
+            }
         };
         // a game dealt here and now, for the lanes with deal_here (all 64 lanes must come along: deal_wave)
         auto deal_in_place = [&](bool deal_here, Game &gd, u64 &kd) __attribute__((always_inline)) {
@@ -785,24 +807,28 @@ __device__ __forceinline__ void play_role(
             // on vector registers.  (Per-lane flags kept as lane masks cost three scalar instructions per update
             // inside a divergent region, and every compare -> mask -> select hop stalls a lone wave: tools/valu_issue.)
             u64 fm = __ballot(fin);
+            // (voted on every trick, not only where a game ends: the tag of a line fetched at the first card has then
+            // landed before the loop's back edge whether or not a lane finishes, and the next trick's compare of it
+            // waits for nothing.  The line's pairs are waited for where a lane takes them; after a trick without a
+            // finish they cross the back edge and are waited for at the next fetch — behind the twelve stores of a
+            // trick, which have long gone: the relaxed back-edge rule stated at the line registers above.)
+            const u64 nol = __ballot(nep1 != cur_ep + 1);
             if (TK_USUAL(fm != 0)) {                                      // (wave uniform)
                 if (TK_RARE(fq_n >= 64)) drain_finished(64);              // room for 64 more: fewer than 64 wait now
                 const u32 slot0 = fq_head + fq_n;                         // (scalar bookkeeping outside the exec region)
                 fq_n += (u32)__popcll(fm);
                 // (a vote on ONE compare, and-ed with the finishing lanes as a scalar: see apply_step's last lines)
-                if (TK_RARE((fm & __ballot(nep1 != cur_ep + 1)) != 0)) {
+                if (TK_RARE((fm & nol) != 0)) {
                     bool lineless = fin && nep1 != cur_ep + 1;
                     // ran out of usable lines (the next ones are being re-dealt right now: the usual
                     // bookkeeping stays valid) vs a line that should have been there and is not
-                    resync_v |= (lineless && consumed < allowed) ? 1u : 0u;
-                    blocked_v |= lineless ? 1u : 0u;                      // (no more fetches for this lane in this launch)
+                    resync_v |= (lineless && consumed < lim) ? 1u : 0u;
+                    lim = lineless ? 0u : lim;                            // (no more fetches for this lane in this launch)
                     Game d = g;
                     u64 dk = key;
                     deal_in_place(lineless, d, dk);
                     if (lineless) { pack(d, na.x, na.y, nb.x, nb.y); nkey = dk; nep1 = cur_ep + 1; }
                 }
-                // (who comes out of the swap without the next line: what the swap moves up is the second buffer)
-                pending |= fm & __ballot(nep2 != cur_ep + 2);
                 if (fin) { push_finished(fm, slot0); swap_in(); cur_ep++; consumed++; }
             }
         }
@@ -855,15 +881,13 @@ __device__ __forceinline__ void play_role(
             if (STD || done) TK_STREAM_STORE(&done[row], (uint8_t)fin01);
         }
     };
-    // With auto-reset a lane that is in play stays in play (a finished game is replaced within the
-    // same card), so "every lane of the wave valid and in play" decided HERE holds for the whole
-    // launch: one of two separate loops (a choice per card made the loop body slower than either).
-    // Games are whole tricks long, so lanes that start a launch of whole tricks at a trick boundary
-    // stay trick-aligned too: third loop, four specialised cards per trick.
+    // "Every lane of the wave valid and in play" (all_play, above) holds for the whole launch: one of two
+    // separate loops (a choice per card made the loop body slower than either).  Lanes that start a launch of
+    // whole tricks at a trick boundary stay trick-aligned too (aligned): third loop, four specialised cards per trick.
     int64_t row = i;
     typedef std::integral_constant<int, -1> nt_any;
-    if (autoreset && __ballot(valid && g.phase == TK_PHASE_PLAY) == ~0ULL) {
-        if ((cards & 3) == 0 && __ballot(g.nt != 0) == 0) {
+    if (all_play) {
+        if (aligned) {
             auto tricks = [&](auto std_tag) __attribute__((always_inline)) {
                 touched = true; seats_dirty = true;          // (cards >= 4: every lane plays a whole trick)
                 // the C plane's high word keeps the ten bits above the deck set for the length of the loop: every hand
@@ -2403,19 +2427,23 @@ TK_KERNEL(TK_BLOCK, 64) void k_set_state(int64_t n, const u64 *__restrict__ in,
 // kernel of its own.  Round 3's corruption was a dealt-ahead game WRITTEN wrong by the refill loop of one build (a gfx950
 // erratum, see TK_VGPR_TOP); no test looked at the lines themselves, and only lists of several hundred entries — four
 // passes of the loop on full waves — showed it.  This is that test (tests/test_gpu_parity.py), for any build.
-__global__ __launch_bounds__(TK_BLOCK) TK_VGPR_BUDGET(64) void k_dbg_fill_lists(u64 *rlist, u32 *rcount, u32 per_slot, u32 ep0, u32 order) {
+__global__ __launch_bounds__(TK_BLOCK) TK_VGPR_BUDGET(64) void k_dbg_fill_lists(u64 *rlist, u32 *rcount, int64_t n, u32 per_slot, u32 ep0, u32 order) {
     TK_VGPR_TOP(64, 63);
     u32 g = blockIdx.x;
-    for (u32 idx = threadIdx.x; idx < per_slot * TK_BLOCK; idx += TK_BLOCK) {
-        u32 k = idx / TK_BLOCK, t = idx % TK_BLOCK;
-        if (order == 1) t = TK_BLOCK - 1 - t;
-        if (order == 2) t = (t * 37u + 11u) % TK_BLOCK;
+    // the slots the group has: a partial last group lists only those (the refill role deals what it is told to, and a
+    // line of a slot >= n lies behind the end of the lines' allocation)
+    const u32 have = (u32)min((int64_t)TK_BLOCK, n - (int64_t)g * TK_BLOCK);
+    if (order == 2 && have % 37u == 0) order = 1;                // (t * 37 + 11 mod `have` must stay a permutation)
+    for (u32 idx = threadIdx.x; idx < per_slot * have; idx += TK_BLOCK) {
+        u32 k = idx / have, t = idx % have;
+        if (order == 1) t = have - 1 - t;
+        if (order == 2) t = (t * 37u + 11u) % have;
         u64 en = ((u64)(ep0 + 1 + k) << 32) | t;
         rlist[((int64_t)g * 2 + 0) * TK_REFILL_CAP + idx] = en;
         rlist[((int64_t)g * 2 + 1) * TK_REFILL_CAP + idx] = en;
     }
     if (threadIdx.x == 0) {
-        rcount[TK_RC(g, 0)] = per_slot * TK_BLOCK; rcount[TK_RC(g, 1)] = per_slot * TK_BLOCK;
+        rcount[TK_RC(g, 0)] = per_slot * have; rcount[TK_RC(g, 1)] = per_slot * have;
         rcount[TK_RC(g, 2)] = 0; rcount[TK_RC(g, 3)] = 0;
     }
 }
@@ -2798,7 +2826,7 @@ int tarok_debug_refill_selftest(tarok_env *e, int kind, int per_slot, uint32_t e
     u32 groups = (u32)((n + TK_BLOCK - 1) / TK_BLOCK);
     for (int it = 0; it < reps; it++) {
         hipLaunchKernelGGL(k_dbg_clear_lines, grid_for(n), dim3(TK_BLOCK), 0, 0, e->aux, n);
-        hipLaunchKernelGGL(k_dbg_fill_lists, dim3(groups), dim3(TK_BLOCK), 0, 0, e->rlist, e->rcount, (u32)per_slot, episode0, (u32)order);
+        hipLaunchKernelGGL(k_dbg_fill_lists, dim3(groups), dim3(TK_BLOCK), 0, 0, e->rlist, e->rcount, n, (u32)per_slot, episode0, (u32)order);
         if (kind == 0) launch_play(e, true, 1, n, nullptr, action, reward, done, nullptr, obs, TAROK_AUTO_RESET, 0);            // k_step, Bot policy
         else if (kind == 1) {                                                                                                  // k_step, cards given
             hipLaunchKernelGGL(k_legal, grid_for(n), dim3(TK_BLOCK), 0, 0, n, e->s01, e->s23, (u64 *)obs, (int8_t *)nullptr);
