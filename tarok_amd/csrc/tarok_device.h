@@ -257,6 +257,19 @@ __device__ __forceinline__ u64 obs_word_with(const Game &g, bool finished_now, u
     return o;
 }
 
+// The seat and position bits of the observation word (54..61) for a caller that plays a game card by card, as ONE
+// carried word: the position (cards played, 0..47) in bits 0..5 and the seat to play in bits 30..31, so that one add
+// of TK_OBS_CARD moves both — the seat's carry falls off the top of the word instead of into the position.  Turned
+// right by eight bits it is the observation's high word: position at bit 24, seat at bit 22.  After a trick's 4th
+// card the seat is the trick's winner, not the next one round: the word is rebuilt there (obs_carry).
+#define TK_OBS_CARD ((1u << 30) + 1u)
+__device__ __forceinline__ u32 obs_carry(u32 seat, u32 pos) { return (seat << 30) | pos; }
+__device__ __forceinline__ u32 obs_carry_hi(u32 carry) { return (carry >> 8) | (carry << 24); }
+// the observation word of a game in play from the carried word (fin01: the game ended with this card, 0 / 1)
+__device__ __forceinline__ u64 obs_word_with(u32 carry, u32 error, u32 fin01, u64 legal) {
+    return legal | ((u64)(obs_carry_hi(carry) | (fin01 << 30) | (error << 31)) << 32);
+}
+
 // observation word (tarok_env.h TAROK_OBS_*)
 __device__ __forceinline__ u64 obs_word(const Game &g, bool finished_now) {
     bool play = g.phase == TK_PHASE_PLAY;
@@ -482,15 +495,21 @@ __device__ __forceinline__ u64 game_key(u64 seed, u64 gidx, u64 episode) {
     u64 a = gidx * 0x9E3779B97F4A7C15ULL + episode * 0xD1B54A32D192ED03ULL + 0x2545F4914F6CDD1DULL;
     return mix64(seed ^ mix64(a));
 }
-__device__ __forceinline__ u32 rng32(u32 lo, u32 hi, u32 i) {
-    u32 x = lo ^ (i * 0x9E3779B1u);
+// draw i's counter word, premultiplied: a caller that draws i, i + 1, ... carries it and adds TK_RNG_STEP per draw
+#define TK_RNG_STEP 0x9E3779B1u
+struct RngCtr { u32 v; };
+__device__ __forceinline__ RngCtr rng_ctr(u32 i) { return RngCtr{i * TK_RNG_STEP}; }
+__device__ __forceinline__ u32 rng32(u32 lo, u32 hi, RngCtr c) {
+    u32 x = lo ^ c.v;
     x ^= x >> 16; x *= 0x85EBCA6Bu;
     x ^= x >> 13; x *= 0xC2B2AE35u;
     x ^= x >> 16; x ^= hi;
     x *= 0x27D4EB2Fu; x ^= x >> 15;
     return x;
 }
+__device__ __forceinline__ u32 rng32(u32 lo, u32 hi, u32 i) { return rng32(lo, hi, rng_ctr(i)); }
 __device__ __forceinline__ u32 rng32(u64 key, u32 i) { return rng32((u32)key, (u32)(key >> 32), i); }
+__device__ __forceinline__ u32 rng32(u64 key, RngCtr c) { return rng32((u32)key, (u32)(key >> 32), c); }
 __device__ __forceinline__ u32 pick(u32 r, u32 n) { return __umulhi(r, n); }
 
 // index of the k-th (0-based) set bit, k < popcount(m): the smallest p with more than k set bits at or below
@@ -537,6 +556,14 @@ __device__ __forceinline__ u32 policy_action(u64 key, u32 step, u64 mask) {
 // the same draw from a follower's one-word mask: one popcount, one-word pick
 __device__ __forceinline__ u32 policy_action_follow(u64 key, u32 step, u32 w, u32 hi_sel) {
     return kth_bit_word(w, hi_sel, pick(rng32(key, 128 + step), (u32)__popc(w)));
+}
+
+// the same two draws for a caller that carries the counter of card `step`: c = rng_ctr(128 + step)
+__device__ __forceinline__ u32 policy_action(u64 key, RngCtr c, u64 mask) {
+    return kth_bit(mask, pick(rng32(key, c), (u32)popc64(mask)));
+}
+__device__ __forceinline__ u32 policy_action_follow(u64 key, RngCtr c, u32 w, u32 hi_sel) {
+    return kth_bit_word(w, hi_sel, pick(rng32(key, c), (u32)__popc(w)));
 }
 
 // One bidding round between four Bot players (TAROK_MIX_BOT): the control flow of

@@ -665,6 +665,9 @@ __device__ __forceinline__ void play_role(
     u64 legal = (valid && g.phase == TK_PHASE_PLAY) ? legal_now(g) : 0;
     u64 c_lead = 0;
     u32 legal_hi = 0;                        // trick-aligned loops, cards 1..3: which word of `legal` holds the cards (legal_mask_follow)
+    // trick-aligned loops, carried from card to card: the RNG counter of the card to play (rng_ctr(128 + cards played)) and
+    // the seat / position half of the observation word (obs_carry) — each moves by a constant per card
+    u32 rctr = 0, ocar = 0;
     u32 resync_v = 0;                        // `resync` of the fast-renewal loop, as a number (a bool carried through a loop is a
                                              // lane mask, merged with three scalar instructions at every join, used or not)
     // the fast-renewal loop's `allowed` and `blocked` in one number: how many games of this launch the lane may take
@@ -717,8 +720,11 @@ __device__ __forceinline__ void play_role(
         // (trick-aligned loops: g.C carries TK_C_PAD from the first card to the last, see tricks() below)
         constexpr bool ALIGNED = ALL && NT >= 0;
         u32 a;
-        if constexpr (ALL && NT >= 1) a = policy_action_follow(key, g.trick_no * 4 + g.nt, TK_LO(legal) | TK_HI(legal), legal_hi);
+        // (trick-aligned loops: the card's RNG counter is carried, one add per card, not rebuilt from trick_no and nt)
+        if constexpr (ALL && NT >= 1) a = policy_action_follow(key, RngCtr{rctr}, TK_LO(legal) | TK_HI(legal), legal_hi);
+        else if constexpr (ALIGNED) a = policy_action(key, RngCtr{rctr}, legal);
         else a = play ? policy_action(key, g.trick_no * 4 + g.nt, legal) : 255u;
+        if constexpr (ALIGNED) rctr += TK_RNG_STEP;       // (the 4th card's renewal region resets it for a fresh game)
         u64 scores = 0;
         u32 trick_info = 0;
         int res = -2;
@@ -829,7 +835,7 @@ __device__ __forceinline__ void play_role(
                     deal_in_place(lineless, d, dk);
                     if (lineless) { pack(d, na.x, na.y, nb.x, nb.y); nkey = dk; nep1 = cur_ep + 1; }
                 }
-                if (fin) { push_finished(fm, slot0); swap_in(); cur_ep++; consumed++; }
+                if (fin) { push_finished(fm, slot0); swap_in(); cur_ep++; consumed++; rctr = rng_ctr(128u).v; }
             }
         }
         if constexpr (CAN_END && !FAST_RENEW) {
@@ -877,7 +883,15 @@ __device__ __forceinline__ void play_role(
         if (v) {
             // (ALL: res is 0 or 1 — the number itself goes into the observation's bit 62 and the done row, no selects)
             const u32 fin01 = ALL ? (u32)res : (fin ? 1u : 0u);
-            TK_STREAM_STORE(&obs[row], obs_word_with<true>(g, false, legal) | ((u64)(ALL ? fin01 : ((fin || g.phase == TK_PHASE_DONE) ? 1u : 0u)) << 62));
+            if constexpr (ALIGNED) {
+                // (the seat and position bits are carried: one add per card; after the 4th card the seat to play is the
+                // trick's winner, or a fresh game's leader: rebuilt there, two instructions)
+                if constexpr (NT < 3) ocar += TK_OBS_CARD;
+                else ocar = obs_carry(g.leader, g.trick_no << 2);
+                TK_STREAM_STORE(&obs[row], obs_word_with(ocar, g.error, fin01, legal));
+            } else {
+                TK_STREAM_STORE(&obs[row], obs_word_with<true>(g, false, legal) | ((u64)(ALL ? fin01 : ((fin || g.phase == TK_PHASE_DONE) ? 1u : 0u)) << 62));
+            }
             if (STD || done) TK_STREAM_STORE(&done[row], (uint8_t)fin01);
         }
     };
@@ -894,6 +908,8 @@ __device__ __forceinline__ void play_role(
                 // comes out of ~C without them (hand_of<true>).  The trick's cards are the plane's gain (c_lead carries
                 // the bits too); the plane is cleaned where it leaves: below, and where a finished game is scored.
                 g.C |= TK_C_PAD;
+                rctr = rng_ctr(128u + g.trick_no * 4).v;
+                ocar = obs_carry(g.leader, g.trick_no << 2);
                 for (int c = 0; c < cards; c += 4) {
                     play_card(std::true_type{}, std::integral_constant<int, 0>{}, std_tag, row, c); row += stride;
                     play_card(std::true_type{}, std::integral_constant<int, 1>{}, std_tag, row, c + 1); row += stride;
