@@ -277,6 +277,31 @@ int tarok_observe_hands_ref(tarok_env *env, uint8_t *out, void *stream);
 int tarok_get_history(tarok_env *env, uint8_t *hist_out, void *stream);
 int tarok_set_history(tarok_env *env, const uint8_t *hist_in, void *stream);
 
+/* The play mode of an env: HOW the five launches below that turn the network's logits into a card — tarok_sample_policy,
+ * tarok_policy_mlp, tarok_policy_step, tarok_policy_step_seats, tarok_policy_step_versus — choose it.  Two numbers,
+ * temperature T >= 0 and epsilon in [0, 1]; a new env has (1, 0): one draw from the softmax over the legal cards, as
+ * described at those functions.  For a game with k > 0 legal cards, logits l_c and `played` cards so far:
+ *   T > 0   the draw is made from p_T(c) ~ exp((l_c - max over the legal cards) * (1.0f / T)): the same spec RNG draw,
+ *           192 + played, the same order of additions, the same last-legal-card rule at the top of the CDF;
+ *   T = 0   greedy: the lowest-numbered legal card whose logit equals the maximum over the legal cards (p_T is 1 there);
+ *           the logits are the float32 values the sampler reads (bf16 widened for tarok_sample_policy);
+ *   epsilon with thr = floor(epsilon * 2^24) > 0 a coin is drawn, spec RNG draw 256 + played (the draw indices in use
+ *           before end at 255), and iff (coin >> 8) < thr the game plays the Bot's card instead: draw 128 + played, the
+ *           card tarok_step_random plays there.  This is Igralec.igraj_karto's arg-max / random_card selection
+ *           (Igralec.py:344-355) at T = 0.
+ * logp_out is the log of the probability with which the MODE plays the card that was played, explored or not:
+ * log((1 - e) p_T(card) + e / k), e = thr / 2^24 — exactly 0 for (0, 0), today's value for (1, 0).  value_out, the
+ * features, rows with nothing to play (255, logp 0) and a mixed table's Bot seats (the Bot's card, logp 0) do not depend
+ * on the mode; both networks of tarok_policy_step_versus play the env's one mode.
+ * The mode is read when a launch is ISSUED: at (1, 0) the launches are the kernels they have always been, otherwise
+ * their play-mode twins with the mode's values as kernel arguments.  A graph a caller captured around these launches
+ * therefore keeps the mode that was in force at capture, whatever is set later: capture again after a change.
+ * tarok_set_play_mode returns TAROK_EINVAL, before any HIP call and leaving the mode as it was, for a NULL env, a NaN,
+ * epsilon outside [0, 1], T < 0, 0 < T < 1e-6 or T > 1e6 (1 / T and its products with logit differences stay finite).
+ * tarok_get_play_mode returns the two numbers as they were set (either pointer may be NULL). */
+int tarok_set_play_mode(tarok_env *env, float temperature, float epsilon);
+int tarok_get_play_mode(const tarok_env *env, float *temperature_out, float *epsilon_out);
+
 /* A learned player's igraj_karto (cf. Igralec.py:344-355): sample one LEGAL card per game from
  * policy logits.  logits [N,64] bf16 (card c in column c, columns 54..63 ignored), obs [N] the
  * observation words (legal mask + cards played), softmax over the legal cards only, draw from the

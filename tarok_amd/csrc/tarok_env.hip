@@ -29,6 +29,7 @@
 #include "tarok_device.h"
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -115,6 +116,10 @@ struct tarok_env {
     float *adam_sumsq;       // k_learn_gnorm's partial sums
     u64 *stamps;             // diagnostics only (tarok_debug_stamps)
     size_t stamps_words;     // its capacity: a kernel that would write more gets no stamps pointer
+    float temperature, epsilon;   // the play mode as given (tarok_set_play_mode); (1, 0): the MODE = 0 kernels, untouched
+    float inv_t, eps_p;      // what the MODE = 1 kernels take: 1 / temperature (1 when greedy), thr / 2^24 ...
+    uint32_t explore_thr;    // ... thr = floor(epsilon * 2^24) ...
+    int greedy, mode_on;     // ... temperature == 0; mode_on: the mode is not (1, 0)
     int launched;            // a step launch has been issued (tarok_set_option: a change of the grid must restart the launch counters)
     hipStream_t cap_stream;  // capture-only stream for tarok_run_random's graphs
     // tarok_run_random's instantiated graphs.  An exec is NEVER destroyed while launches of it may still be queued (round 3
@@ -1637,10 +1642,18 @@ TK_KERNEL(TK_BLOCK, 64) void k_observe_hands_ref(int64_t n, const ulonglong2 *__
 // (bit-expand mask, masked_fill, log_softmax, multinomial, gather) with one pass over 8 MB.
 __device__ __forceinline__ float bf16_to_f32(u32 h) { return __uint_as_float(h << 16); }
 
-TK_KERNEL(TK_BLOCK, 256) void k_sample(int64_t n, const uint4 *__restrict__ logits /* [N,64] bf16 */,
-                                                    const u64 *__restrict__ obs, const u64 *__restrict__ gkey,
-                                                    uint8_t *__restrict__ action, float *__restrict__ logp) {
-    TK_VGPR_TOP(256, 255);
+// The play mode of the MODE = 1 kernels (tarok_set_play_mode; include/tarok_env.h): the tempered softmax
+// exp((l - max) * inv_t), or with `greedy` the lowest-numbered legal card at the maximum; with thr > 0 a coin — spec
+// RNG draw 256 + cards played, explore iff (coin >> 8) < thr — sends the game to the Bot's card (policy_action, draw
+// 128 + cards played); eps = thr / 2^24, the probability of that.  The log-probability is that of the card played under
+// the whole mode: log((1 - eps) p_T(card) + eps / k), k legal cards.  MODE = 0 is the plain draw at (1, 0) and takes none
+// of this: everything a mode adds sits behind `if constexpr (MODE)`.
+struct PlayMode { float inv_t; int greedy; u32 thr; float eps; };
+#define TK_DRAW_EXPLORE 256u
+
+template <int MODE>
+__device__ __forceinline__ void sample_body(int64_t n, const uint4 *logits /* [N,64] bf16 */, const u64 *obs, const u64 *gkey,
+                                            uint8_t *action, float *logp, const PlayMode pm = PlayMode{}) {
     int64_t i = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
     if (i >= n) return;
     u64 o = obs[i];
@@ -1660,10 +1673,22 @@ TK_KERNEL(TK_BLOCK, 256) void k_sample(int64_t n, const uint4 *__restrict__ logi
     float mx = -3.0e38f;
 #pragma unroll
     for (int c = 0; c < 54; c++) mx = ((m >> c) & 1) ? fmaxf(mx, l[c]) : mx;
+    int best = -1;                     // MODE: the lowest-numbered legal card at the maximum (strictly greater moves it)
+    if constexpr (MODE) {
+        float bm = -3.0e38f;
+#pragma unroll
+        for (int c = 0; c < 54; c++) {
+            bool up = ((m >> c) & 1) && (best < 0 || l[c] > bm);
+            bm = up ? l[c] : bm;
+            best = up ? c : best;
+        }
+    }
     float sum = 0.f;
 #pragma unroll
     for (int c = 0; c < 54; c++) {
-        float e = ((m >> c) & 1) ? __expf(l[c] - mx) : 0.f;
+        float e;
+        if constexpr (MODE) e = ((m >> c) & 1) ? __expf((l[c] - mx) * pm.inv_t) : 0.f;
+        else e = ((m >> c) & 1) ? __expf(l[c] - mx) : 0.f;
         l[c] = e;                      // keep exp() for the draw
         sum += e;
     }
@@ -1685,8 +1710,35 @@ TK_KERNEL(TK_BLOCK, 256) void k_sample(int64_t n, const uint4 *__restrict__ logi
 #pragma unroll
         for (int c = 0; c < 54; c++) pe = (c == pickc) ? l[c] : pe;
     }
+    if constexpr (MODE) {
+        const u32 played = (u32)(o >> TAROK_OBS_STEP_SHIFT) & 63u;
+        const int bc = (int)policy_action(gkey[i], played, m);      // the Bot's card here
+        float pb = 0.f;
+#pragma unroll
+        for (int c = 0; c < 54; c++) pb = (c == bc) ? l[c] : pb;
+        if (pm.greedy) { pickc = best; pe = 1.f; sum = 1.f; pb = bc == best ? 1.f : 0.f; }
+        if (pm.thr && (rng32(gkey[i], TK_DRAW_EXPLORE + played) >> 8) < pm.thr) { pickc = bc; pe = pb; }
+        action[i] = (uint8_t)pickc;
+        if (logp) logp[i] = __logf((1.f - pm.eps) * (pe / sum) + pm.eps / (float)popc64(m));
+        return;
+    }
     action[i] = (uint8_t)pickc;
     if (logp) logp[i] = __logf(pe / sum);
+}
+
+TK_KERNEL(TK_BLOCK, 256) void k_sample(int64_t n, const uint4 *__restrict__ logits /* [N,64] bf16 */,
+                                                    const u64 *__restrict__ obs, const u64 *__restrict__ gkey,
+                                                    uint8_t *__restrict__ action, float *__restrict__ logp) {
+    TK_VGPR_TOP(256, 255);
+    sample_body<0>(n, logits, obs, gkey, action, logp);
+}
+
+TK_KERNEL(TK_BLOCK, 256) void k_sample_mode(int64_t n, const uint4 *__restrict__ logits /* [N,64] bf16 */,
+                                                         const u64 *__restrict__ obs, const u64 *__restrict__ gkey,
+                                                         uint8_t *__restrict__ action, float *__restrict__ logp,
+                                                         float inv_t, int greedy, u32 thr, float eps) {
+    TK_VGPR_TOP(256, 255);
+    sample_body<1>(n, logits, obs, gkey, action, logp, PlayMode{inv_t, greedy, thr, eps});
 }
 
 
@@ -2011,7 +2063,10 @@ struct PolicySampleIn {
     u32 played, mh;           // cards played so far in this game; the legality bits of this lane's cards
     int last;                 // the last legal card
 };
-struct PolicyPick { int pk; float pp, sum, v54; };      // card, its exp(logit - max), the sum of those, the state value
+struct PolicyPick {
+    int pk; float pp, sum, v54;      // card, its exp(logit - max), the sum of those, the state value
+    int bc; float pb;                // MODE only: the Bot's card on this position and its exp (PlayMode: an exploring game plays it)
+};
 
 __device__ __forceinline__ PolicySampleIn policy_sample_inputs(const u64 *__restrict__ obs, const u64 *__restrict__ gkey, int64_t i, u32 half) {
     PolicySampleIn in;
@@ -2025,7 +2080,8 @@ __device__ __forceinline__ PolicySampleIn policy_sample_inputs(const u64 *__rest
 }
 
 // one draw from logits row gi of L: the candidate is whole on the game's half == 0 lane
-__device__ __forceinline__ PolicyPick policy_sample(const float *L, u32 gi, u32 half, const PolicySampleIn &in) {
+template <int MODE = 0>
+__device__ __forceinline__ PolicyPick policy_sample(const float *L, u32 gi, u32 half, const PolicySampleIn &in, const PlayMode &pm = PlayMode{}) {
     float l[27];
 #pragma unroll
     for (int c = 0; c < 27; c++) l[c] = L[gi * PM_LL + 27 * half + c];
@@ -2035,8 +2091,23 @@ __device__ __forceinline__ PolicyPick policy_sample(const float *L, u32 gi, u32 
 #pragma unroll
     for (int c = 0; c < 27; c++) mx = ((mh >> c) & 1) ? fmaxf(mx, l[c]) : mx;
     mx = fmaxf(mx, pm_swap(mx));
+    // MODE: this lane's arg-max over its 27 cards (strictly greater moves it: the lowest index stays), before the logits
+    // turn into exps
+    int am = -1;
+    float bm = -3.0e38f;
+    if constexpr (MODE) {
 #pragma unroll
-    for (int c = 0; c < 27; c++) l[c] = ((mh >> c) & 1) ? __expf(l[c] - mx) : 0.f;
+        for (int c = 0; c < 27; c++) {
+            bool up = ((mh >> c) & 1) && (am < 0 || l[c] > bm);
+            bm = up ? l[c] : bm;
+            am = up ? c : am;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 27; c++) {
+        if constexpr (MODE) l[c] = ((mh >> c) & 1) ? __expf((l[c] - mx) * pm.inv_t) : 0.f;
+        else l[c] = ((mh >> c) & 1) ? __expf(l[c] - mx) : 0.f;
+    }
     // running sums in card order: the low half from 0, then the high half from the low half's total
     float s = 0.f;
 #pragma unroll
@@ -2073,6 +2144,20 @@ __device__ __forceinline__ PolicyPick policy_sample(const float *L, u32 gi, u32 
     p.pp = pickc >= 0 ? pe : (pick_o >= 0 ? pe_o : (last < 27 ? pl : pl_o));
     p.sum = sum;
     p.v54 = v54;
+    if constexpr (MODE) {
+        // the Bot's card of the position (the same in both lanes: whole on the half == 0 lane) and its exp from the lane
+        // that holds it; the pair's arg-max, the low half winning ties.  Every partner read is made before any select.
+        const int bc = (int)policy_action(in.key, in.played, in.m);
+        float pb = 0.f;
+#pragma unroll
+        for (int c = 0; c < 27; c++) pb = (c + 27 * (int)half == bc) ? l[c] : pb;
+        const float pb_o = pm_swap(pb), bm_o = pm_swap(bm);
+        const int am_o = pm_swap(am);
+        const int best = (am >= 0 && (am_o < 0 || bm >= bm_o)) ? am : am_o + 27;
+        p.bc = bc;
+        p.pb = bc < 27 ? pb : pb_o;
+        if (pm.greedy) { p.pk = best; p.pp = 1.f; p.sum = 1.f; p.pb = bc == best ? 1.f : 0.f; }
+    }
     return p;
 }
 
@@ -2088,14 +2173,16 @@ __device__ __forceinline__ PolicyPick policy_sample(const float *L, u32 gi, u32 
 // of tarok_policy_mlp with its weights.  With NETS = 1 the loop and the selects fold away.
 // MIXED (tarok_policy_step_seats): a game whose seat to move is not in its seat set takes the Bot's card — k_policy's,
 // i.e. what tarok_step_random plays — and the log-probability 0; the network is evaluated for every game all the same.
-template <int TILES, int NETS = 1, bool MIXED = false>
+// MODE = 1 (the *_mode kernels): the env's play mode, PlayMode — tempered or greedy card, the exploration coin and the
+// mode's log-probability at the write-out, on the half == 0 lane; a Bot seat of a mixed table is the Bot's all the same.
+template <int TILES, int NETS = 1, bool MIXED = false, int MODE = 0>
 __device__ __forceinline__ void policy_body(
     int64_t n, const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23, const u64 *__restrict__ obs,
     const u64 *__restrict__ gkey, const PolicyWeights (&nets)[NETS], uint8_t *__restrict__ action, float *__restrict__ logp,
     float *__restrict__ value, uint4 *__restrict__ features_out, ulonglong2 *__restrict__ feature_words_out,
     u64 *__restrict__ stamps, uint8_t *__restrict__ act_s,
     u32 **lds_after = nullptr /* the activation buffer: free once every thread has returned */, u32 seats = 15,
-    const uint8_t *__restrict__ seat_sets = nullptr) {
+    const uint8_t *__restrict__ seat_sets = nullptr, const PlayMode pmode = PlayMode{}) {
     constexpr int GAMES = PM_M * TILES;
     u64 ts[7];
 #define PM_STAMP(k) if (stamps) ts[k] = __builtin_amdgcn_s_memtime();
@@ -2133,7 +2220,7 @@ __device__ __forceinline__ void policy_body(
         in = policy_sample_inputs(obs, gkey, i, half);
         is_a = in_set(in.o);
     }
-    PolicyPick pick = {0, 0.f, 1.f, 0.f};          // the mover's network's candidate
+    PolicyPick pick = {0, 0.f, 1.f, 0.f, 0, 0.f};  // the mover's network's candidate
     auto pass = [&](int net) __attribute__((always_inline)) {
         PolicyWeights w = nets[0];
         if constexpr (NETS > 1) { if (net) w = nets[1]; }
@@ -2166,12 +2253,16 @@ __device__ __forceinline__ void policy_body(
             stamps[blockIdx.x * 8 + 6] = ts[6];
         }
         if constexpr (NETS == 1) in = policy_sample_inputs(obs, gkey, i, half);
-        PolicyPick c = policy_sample(L, gi, half, in);
+        PolicyPick c = policy_sample<MODE>(L, gi, half, in, pmode);
         const bool mine = NETS == 1 || (net == 0) == is_a;
         pick.pk = mine ? c.pk : pick.pk;
         pick.pp = mine ? c.pp : pick.pp;
         pick.sum = mine ? c.sum : pick.sum;
         pick.v54 = mine ? c.v54 : pick.v54;
+        if constexpr (MODE) {
+            pick.bc = c.bc;                        // (the position's, whichever network)
+            pick.pb = mine ? c.pb : pick.pb;
+        }
     };
     if constexpr (NETS == 1) pass(0);              // (no loop at all: nothing of the sampler is hoisted over the layers)
     else {
@@ -2186,10 +2277,23 @@ __device__ __forceinline__ void policy_body(
             bot = !in_set(in.o);
             if (bot && m) pick.pk = (int)policy_action(in.key, in.played, m);
         }
-        if (!m) { action[i] = 255; if (logp) logp[i] = 0.f; }
-        else {
-            action[i] = (uint8_t)pick.pk;
-            if (logp) logp[i] = bot ? 0.f : __logf(pick.pp / pick.sum);
+        if constexpr (MODE) {
+            // the coin of an exploring mode (a network seat's only); the card's probability under the whole mode
+            if (m && !bot && pmode.thr && (rng32(in.key, TK_DRAW_EXPLORE + in.played) >> 8) < pmode.thr) {
+                pick.pk = pick.bc;
+                pick.pp = pick.pb;
+            }
+            if (!m) { action[i] = 255; if (logp) logp[i] = 0.f; }
+            else {
+                action[i] = (uint8_t)pick.pk;
+                if (logp) logp[i] = bot ? 0.f : __logf((1.f - pmode.eps) * (pick.pp / pick.sum) + pmode.eps / (float)popc64(m));
+            }
+        } else {
+            if (!m) { action[i] = 255; if (logp) logp[i] = 0.f; }
+            else {
+                action[i] = (uint8_t)pick.pk;
+                if (logp) logp[i] = bot ? 0.f : __logf(pick.pp / pick.sum);
+            }
         }
         if (act_s) act_s[gi] = m ? (uint8_t)pick.pk : (uint8_t)255;
     }
@@ -2206,6 +2310,19 @@ __global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_mlp(
     TK_VGPR_TOP(256, 255);
     const PolicyWeights nets[1] = {{w1, b1, w2, b2, w3, b3}};
     policy_body<1>(n, s01, s23, obs, gkey, nets, action, logp, value, features_out, feature_words_out, stamps, nullptr);
+}
+
+__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_mlp_mode(
+    int64_t n, const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23, const u64 *__restrict__ obs,
+    const u64 *__restrict__ gkey, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3,
+    const float *__restrict__ b3, uint8_t *__restrict__ action, float *__restrict__ logp, float *__restrict__ value,
+    uint4 *__restrict__ features_out, ulonglong2 *__restrict__ feature_words_out, u64 *__restrict__ stamps,
+    float inv_t, int greedy, u32 thr, float eps) {
+    TK_VGPR_TOP(256, 255);
+    const PolicyWeights nets[1] = {{w1, b1, w2, b2, w3, b3}};
+    policy_body<1, 1, false, 1>(n, s01, s23, obs, gkey, nets, action, logp, value, features_out, feature_words_out, stamps, nullptr,
+                                nullptr, 15, nullptr, PlayMode{inv_t, greedy, thr, eps});
 }
 
 // tarok_policy_step: tarok_policy_mlp and tarok_step in ONE launch.  A play workgroup (512
@@ -2229,9 +2346,9 @@ __global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_mlp(
     n, seed, offset, mix, flags, play_groups, epoch, fan, obs_in, w1, b1, w2, b2, w3, b3, action, logp, value,                    \
         feature_words_out, reward, done, trick, obs_out, hist, s01, s23, aux, cnt, gkey, rlist, rcount
 
-template <int NETS, bool MIXED>
+template <int NETS, bool MIXED, int MODE = 0>
 __device__ __forceinline__ void policy_step_shell(TK_POLICY_STEP_ARGS, u32 seats, const uint8_t *__restrict__ seat_sets,
-                                                  const PolicyWeights &second) {
+                                                  const PolicyWeights &second, const PlayMode pmode = PlayMode{}) {
     TkCount count = launch_count<1>(epoch, play_groups);          // (in flight under the policy's first loads)
     if (blockIdx.x >= play_groups) {
         refill_role<false>(blockIdx.x - play_groups, threadIdx.x, 2 * TK_BLOCK, seed, offset, mix, play_groups, count, epoch, fan, false, aux, rlist, rcount, nullptr);
@@ -2241,8 +2358,8 @@ __device__ __forceinline__ void policy_step_shell(TK_POLICY_STEP_ARGS, u32 seats
     u32 *lds = nullptr;
     PolicyWeights nets[NETS] = {{w1, b1, w2, b2, w3, b3}};
     if constexpr (NETS > 1) nets[1] = second;
-    policy_body<2, NETS, MIXED>(n, s01, s23, obs_in, gkey, nets, action, logp, value, nullptr, feature_words_out, nullptr, act_s, &lds,
-                                seats, seat_sets);
+    policy_body<2, NETS, MIXED, MODE>(n, s01, s23, obs_in, gkey, nets, action, logp, value, nullptr, feature_words_out, nullptr, act_s, &lds,
+                                      seats, seat_sets, pmode);
     __syncthreads();                          // (the policy's LDS is free from here on: the step's scoring list goes there)
     u32 tid = threadIdx.x;
     step_role<false, false>(blockIdx.x, tid & (TK_BLOCK - 1), tid < TK_BLOCK, act_s[tid & (TK_BLOCK - 1)], false, n, seed, offset, mix, flags,
@@ -2267,6 +2384,28 @@ __global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_
     const float *__restrict__ c3) {
     TK_VGPR_TOP(256, 255);
     policy_step_shell<2, false>(TK_POLICY_STEP_NAMES, seats, seat_sets, PolicyWeights{v1, c1, v2, c2, v3, c3});
+}
+
+// The same three launches under a play mode (MODE = 1): the mode's four values come LAST, after whatever the kind takes.
+#define TK_PLAY_MODE_ARGS float inv_t, int greedy, u32 thr, float eps
+#define TK_PLAY_MODE_NAMES PlayMode{inv_t, greedy, thr, eps}
+__global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_step_mode(TK_POLICY_STEP_ARGS, TK_PLAY_MODE_ARGS) {
+    TK_VGPR_TOP(256, 255);
+    policy_step_shell<1, false, 1>(TK_POLICY_STEP_NAMES, 15, nullptr, PolicyWeights{}, TK_PLAY_MODE_NAMES);
+}
+
+__global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_step_seats_mode(
+    TK_POLICY_STEP_ARGS, u32 seats, const uint8_t *__restrict__ seat_sets, TK_PLAY_MODE_ARGS) {
+    TK_VGPR_TOP(256, 255);
+    policy_step_shell<1, true, 1>(TK_POLICY_STEP_NAMES, seats, seat_sets, PolicyWeights{}, TK_PLAY_MODE_NAMES);
+}
+
+__global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_step_versus_mode(
+    TK_POLICY_STEP_ARGS, u32 seats, const uint8_t *__restrict__ seat_sets, const __bf16 *__restrict__ v1,
+    const float *__restrict__ c1, const __bf16 *__restrict__ v2, const float *__restrict__ c2, const __bf16 *__restrict__ v3,
+    const float *__restrict__ c3, TK_PLAY_MODE_ARGS) {
+    TK_VGPR_TOP(256, 255);
+    policy_step_shell<2, false, 1>(TK_POLICY_STEP_NAMES, seats, seat_sets, PolicyWeights{v1, c1, v2, c2, v3, c3}, TK_PLAY_MODE_NAMES);
 }
 
 // ---------------------------------------------------------------------------
@@ -2542,6 +2681,7 @@ int tarok_create(tarok_env **out, int device, int64_t n_games, uint64_t game_off
     // games: -8 % per lock-step, 262,144: -7 %); where the batch streams the deals' instructions add to the launch
     // wherever they run, and a whole stretch of launches' worth at once cost what they cost one trick at a time (profiles/r03_ab_step.txt (e))
     e->lazy_refill = n_games < (1 << 20) ? 1 : 0;
+    e->temperature = 1.f; e->inv_t = 1.f;      // play mode (1, 0): epsilon, thr, greedy and mode_on are 0
     size_t stale_bytes = (size_t)((n_games + TK_PF_SLOTS - 1) / TK_PF_SLOTS) * TK_PF_SLOTS * sizeof(uint16_t);
     hipError_t r = hipMalloc((void **)&e->s01, (size_t)n_games * sizeof(ulonglong2));
     if (r == hipSuccess) r = hipMalloc((void **)&e->s23, (size_t)n_games * sizeof(ulonglong2));
@@ -2614,6 +2754,26 @@ int tarok_set_option(tarok_env *e, int option, int value) {
         e->lazy_refill = (uint32_t)value;
     } else return TAROK_EINVAL;
     return TAROK_OK;      // (graphs instantiated for the old tuning stay cached under their own key: tarok_run_random)
+}
+
+int tarok_set_play_mode(tarok_env *e, float temperature, float epsilon) {
+    if (!e || temperature != temperature || epsilon != epsilon) return TAROK_EINVAL;
+    if (!(epsilon >= 0.f && epsilon <= 1.f)) return TAROK_EINVAL;
+    if (temperature < 0.f || (temperature > 0.f && temperature < 1e-6f) || temperature > 1e6f) return TAROK_EINVAL;
+    e->temperature = temperature; e->epsilon = epsilon;
+    e->greedy = temperature == 0.f;
+    e->inv_t = e->greedy ? 1.f : 1.0f / temperature;
+    e->explore_thr = (uint32_t)floor((double)epsilon * 16777216.0);
+    e->eps_p = (float)e->explore_thr * (1.0f / 16777216.0f);      // (exact: thr <= 2^24)
+    e->mode_on = !(temperature == 1.f && epsilon == 0.f);
+    return TAROK_OK;      // (no HIP call: the next launch reads it; a caller's captured graph keeps the kernel and the values it captured)
+}
+
+int tarok_get_play_mode(const tarok_env *e, float *temperature_out, float *epsilon_out) {
+    if (!e) return TAROK_EINVAL;
+    if (temperature_out) *temperature_out = e->temperature;
+    if (epsilon_out) *epsilon_out = e->epsilon;
+    return TAROK_OK;
 }
 
 static inline void launch_prefetch(tarok_env *e, hipStream_t s) {
@@ -2919,8 +3079,12 @@ int tarok_sample_policy(tarok_env *e, const void *logits_bf16, const uint64_t *o
                         float *logp_out, void *stream) {
     if (!e || !logits_bf16 || !obs || !action_out) return TAROK_EINVAL;
     HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_sample, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, (const uint4 *)logits_bf16,
-                       (const u64 *)obs, e->gkey, action_out, logp_out);
+    if (!e->mode_on)
+        hipLaunchKernelGGL(k_sample, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, (const uint4 *)logits_bf16,
+                           (const u64 *)obs, e->gkey, action_out, logp_out);
+    else
+        hipLaunchKernelGGL(k_sample_mode, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, (const uint4 *)logits_bf16,
+                           (const u64 *)obs, e->gkey, action_out, logp_out, e->inv_t, e->greedy, e->explore_thr, e->eps_p);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }
@@ -2931,9 +3095,15 @@ int tarok_policy_mlp(tarok_env *e, const void *w1, const float *b1, const void *
     if (!e || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !obs || !action_out) return TAROK_EINVAL;
     HIPCHK(hipSetDevice(e->device));
     dim3 grid((unsigned)((e->n + PM_M - 1) / PM_M));
-    hipLaunchKernelGGL(k_policy_mlp, grid, dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->s01, e->s23, (const u64 *)obs,
-                       e->gkey, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3, action_out, logp_out,
-                       value_out, (uint4 *)features_out, (ulonglong2 *)feature_words_out, stamps_for(e, 8 * (size_t)grid.x));
+    if (!e->mode_on)
+        hipLaunchKernelGGL(k_policy_mlp, grid, dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->s01, e->s23, (const u64 *)obs,
+                           e->gkey, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3, action_out, logp_out,
+                           value_out, (uint4 *)features_out, (ulonglong2 *)feature_words_out, stamps_for(e, 8 * (size_t)grid.x));
+    else
+        hipLaunchKernelGGL(k_policy_mlp_mode, grid, dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->s01, e->s23, (const u64 *)obs,
+                           e->gkey, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3, action_out, logp_out,
+                           value_out, (uint4 *)features_out, (ulonglong2 *)feature_words_out, stamps_for(e, 8 * (size_t)grid.x),
+                           e->inv_t, e->greedy, e->explore_thr, e->eps_p);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }
@@ -2954,9 +3124,17 @@ static int launch_policy_step(tarok_env *e, int kind, u32 seats, const uint8_t *
                        e->epoch, fan, (const u64 *)obs, a.w1, a.b1, a.w2, a.b2, a.w3, a.b3, action_out, logp_out, value_out,  \
                        (ulonglong2 *)feature_words_out, reward_out, done_out, trick_out, (u64 *)obs_out, e->hist, e->s01,     \
                        e->s23, e->aux, e->cnt, e->gkey, e->rlist, e->rcount, ##__VA_ARGS__)
-    if (kind == 0) TK_LAUNCH_POLICY_STEP(k_policy_step);
-    else if (kind == 1) TK_LAUNCH_POLICY_STEP(k_policy_step_seats, seats, seat_sets);
-    else TK_LAUNCH_POLICY_STEP(k_policy_step_versus, seats, seat_sets, b.w1, b.b1, b.w2, b.b2, b.w3, b.b3);
+    if (!e->mode_on) {                    // play mode (1, 0): the launches as they always were
+        if (kind == 0) TK_LAUNCH_POLICY_STEP(k_policy_step);
+        else if (kind == 1) TK_LAUNCH_POLICY_STEP(k_policy_step_seats, seats, seat_sets);
+        else TK_LAUNCH_POLICY_STEP(k_policy_step_versus, seats, seat_sets, b.w1, b.b1, b.w2, b.b2, b.w3, b.b3);
+    } else {
+#define TK_MODE_VALUES e->inv_t, e->greedy, e->explore_thr, e->eps_p
+        if (kind == 0) TK_LAUNCH_POLICY_STEP(k_policy_step_mode, TK_MODE_VALUES);
+        else if (kind == 1) TK_LAUNCH_POLICY_STEP(k_policy_step_seats_mode, seats, seat_sets, TK_MODE_VALUES);
+        else TK_LAUNCH_POLICY_STEP(k_policy_step_versus_mode, seats, seat_sets, b.w1, b.b1, b.w2, b.b2, b.w3, b.b3, TK_MODE_VALUES);
+#undef TK_MODE_VALUES
+    }
 #undef TK_LAUNCH_POLICY_STEP
     HIPCHK(hipGetLastError());
     return TAROK_OK;

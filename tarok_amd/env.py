@@ -88,6 +88,21 @@ class TarokVecEnv:
         if lazy_refill is not None:
             _native.check(self.L.tarok_set_option(self._h, K.OPT_LAZY_REFILL, int(lazy_refill)))
 
+    def set_play_mode(self, temperature=1.0, epsilon=0.0):
+        """How sample_policy, policy_mlp and policy_step choose the card from the logits (tarok_set_play_mode): a draw
+        from the softmax at `temperature` (0: greedy, the lowest-numbered legal card at the maximum), and with probability
+        `epsilon` the Bot's uniformly random legal card instead — (0, random_card) is Igralec.igraj_karto's selection.
+        (1, 0), a new env's mode, is the plain draw.  logp_out is the log-probability of the played card under the whole
+        mode.  Read when a launch is issued: a graph captured around launches keeps the mode it was captured with."""
+        _native.check(self.L.tarok_set_play_mode(self._h, float(temperature), float(epsilon)))
+
+    @property
+    def play_mode(self):
+        """(temperature, epsilon) as set (tarok_get_play_mode)."""
+        t, e = C.c_float(), C.c_float()
+        _native.check(self.L.tarok_get_play_mode(self._h, C.byref(t), C.byref(e)))
+        return t.value, e.value
+
     def refill_selftest(self, kind, per_slot, episode0=100, order=0, reps=1):
         """tarok_debug_refill_selftest (tests only; reset() afterwards): (wrong lines, [first records])."""
         import numpy as np

@@ -47,15 +47,23 @@ def duplicate_advantage(scores):
 
 
 def _play_passes(weights, n_games, episodes, seed, mix, device, inspect=None, opponent=None):
+    """_play_passes_mode at the play mode (1, 0): every network card one draw from its softmax."""
+    return _play_passes_mode(weights, n_games, episodes, seed, mix, device, inspect=inspect, opponent=opponent)
+
+
+def _play_passes_mode(weights, n_games, episodes, seed, mix, device, inspect=None, opponent=None, temperature=1.0, epsilon=0.0):
     """The five passes of every episode on an env of its own; returns scores [5, episodes * n_games, 4] i32.
     opponent: six tensors like `weights`, the network that takes the Bot's place on every seat outside the pass's set
     (tarok_policy_step_versus; None: the Bot, tarok_policy_step_seats).
+    temperature, epsilon: the play mode of the env (TarokVecEnv.set_play_mode) — of every network seat, `opponent`'s
+    too; the Bot's seats, hence the whole of evaluate_vs_bot's pass 0, do not depend on it.
     inspect (tests): a list that receives one dict per pass — episode, seats, start (the canonical lanes after the
     reset), actions [48, N] u8 and scores [N, 4] host arrays — at the price of a second synchronisation per pass."""
     n = int(n_games)
     scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
     env = TarokVecEnv(n, device=device, seed=seed, mix=mix)
     try:
+        env.set_play_mode(temperature, epsilon)
         with torch.cuda.device(env.device):
             # the observation words go back and forth between the env's own buffer (reset() leaves the first ones there)
             # and a second one: the step's input and output may not alias
@@ -77,27 +85,36 @@ def _play_passes(weights, n_games, episodes, seed, mix, device, inspect=None, op
     return scores
 
 
-def evaluate_vs_bot(weights, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0):
+def evaluate_vs_bot(weights, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, temperature=1.0, epsilon=0.0):
     """Duplicate evaluation of `weights` (w1, b1, w2, b2, w3, b3 as tarok_policy_step takes them, on `device`)
     over n_games * episodes deals; returns duplicate_advantage's dict.  Deal e * n_games + i is game i of episode e
     of an env with this seed and game offset 0: the same arguments always play the same deals.
 
     Runs on an env of its own (a training env, its state and its captured graph are never touched).  Per episode and
     pass: reset with the score counters cleared, 48 one-card launches without auto-reset (a finished game ignores its
-    card; a Berac may end early), then ONE host synchronisation to read the slots' score sums."""
-    return duplicate_advantage(_play_passes(weights, n_games, episodes, seed, mix, device))
+    card; a Berac may end early), then ONE host synchronisation to read the slots' score sums.
+
+    temperature, epsilon: how the network's card is chosen (TarokVecEnv.set_play_mode, on the evaluation's own env).  The
+    default (1, 0) samples the softmax, so the figure is that of the policy plus its sampling noise; temperature=0 plays
+    the network's best card — the arg-max of Igralec.igraj_karto — and epsilon its random_card.  The Bot-everywhere pass
+    is the same whatever the mode."""
+    return duplicate_advantage(_play_passes_mode(weights, n_games, episodes, seed, mix, device, temperature=temperature,
+                                                 epsilon=epsilon))
 
 
-def evaluate_vs_policy(weights, opponent, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0):
+def evaluate_vs_policy(weights, opponent, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, temperature=1.0, epsilon=0.0):
     """Duplicate evaluation of `weights` against a second network, `opponent` (both as tarok_policy_step takes them, on
     `device`): evaluate_vs_bot with `opponent` in the Bot's place, one tarok_policy_step_versus launch per lock-step.
     Pass 0 plays `opponent` on all four seats, pass 1 + k `weights` on seat k alone and `opponent` on the other three,
     on the deals evaluate_vs_bot plays with the same arguments.  Returns duplicate_advantage's dict, unchanged:
     `bot_mean` is then the mean of the BASELINE policy (`opponent` on the seat in pass 0), `policy_mean` that of
     `weights`, and `advantage` is points per game of `weights` over `opponent` — exactly 0.0 for a network against
-    itself, since a network's card on a position does not depend on who else sits at the table."""
+    itself, since a network's card on a position does not depend on who else sits at the table.
+    temperature, epsilon: the play mode of BOTH networks (evaluate_vs_bot); a network against itself stays at 0.0 in
+    every mode, the coin and the Bot's card being functions of the position too."""
     for name, ws in (("weights", weights), ("opponent", opponent)):
         if not isinstance(ws, (tuple, list)) or len(ws) != 6 or not all(torch.is_tensor(t) for t in ws):
             raise ValueError("%s: six tensors (w1, b1, w2, b2, w3, b3)" % name)
         TarokVecEnv.check_mlp_weights(ws)
-    return duplicate_advantage(_play_passes(weights, n_games, episodes, seed, mix, device, opponent=opponent))
+    return duplicate_advantage(_play_passes_mode(weights, n_games, episodes, seed, mix, device, opponent=opponent,
+                                                 temperature=temperature, epsilon=epsilon))

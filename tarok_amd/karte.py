@@ -60,6 +60,11 @@ REF_RECORD_BYTES = 12544
 REF_EXCHANGE_BYTES = 400
 REF_TYPES = ("Klop", "Navadna_igra", "Solo", "Berac")    # meta[:, 1] (Nevronski_igralec.Tipi_NN, Igralec.py:174-178)
 
+# spec RNG draw indices of the play launches (oracle/tarok_spec.py has those of the deal): index + cards played
+DRAW_POLICY = 128         # the Bot's uniform legal card (tarok_step_random, tarok_policy_random)
+DRAW_SAMPLE = 192         # the learned policy's inverse-CDF draw (tarok_sample_policy and the fused launches)
+DRAW_EXPLORE = 256        # the exploration coin of a play mode with epsilon > 0 (tarok_set_play_mode)
+
 # observation word
 OBS_MASK = DECK
 OBS_SEAT_SHIFT = 54

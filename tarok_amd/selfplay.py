@@ -378,22 +378,30 @@ class SelfPlay:
             dst.copy_(src)
 
     @torch.no_grad()
-    def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None):
+    def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None, greedy=False, temperature=None, epsilon=0.0):
         """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
         weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
         and on the SAME deals on every rank (seed 0, game offset 0, whatever the training env's are): the figures of
         one run are comparable from call to call, and ranks holding the same weights return the same numbers —
         averaging them over ranks adds nothing.
         opponent (a snapshot()): points per game against that network instead (evaluate.evaluate_vs_policy: `bot_mean`
-        is then the opponent's mean), on the same deals."""
+        is then the opponent's mean), on the same deals.
+        greedy=True plays the network's best card (temperature 0) instead of a draw from its softmax, temperature a
+        tempered draw, epsilon the Bot's card with that probability (TarokVecEnv.set_play_mode, on the evaluation's env
+        only: the rollout keeps sampling at (1, 0))."""
+        if greedy and temperature:
+            raise ValueError("greedy=True is temperature 0: give one of the two")
+        temperature = 0.0 if greedy else (1.0 if temperature is None else float(temperature))
         if not self.fused:
             raise RuntimeError("evaluate() plays tarok_policy_step_seats, which is built for hidden = 256")
         from .evaluate import evaluate_vs_bot, evaluate_vs_policy
         if self._w is None or not self.fused_learner:
             self._refresh_rollout_weights()
         if opponent is not None:
-            return evaluate_vs_policy(self._w, opponent, n_games, episodes, mix=mix, device=self.env.device_index)
-        return evaluate_vs_bot(self._w, n_games, episodes, mix=mix, device=self.env.device_index)
+            return evaluate_vs_policy(self._w, opponent, n_games, episodes, mix=mix, device=self.env.device_index,
+                                      temperature=temperature, epsilon=epsilon)
+        return evaluate_vs_bot(self._w, n_games, episodes, mix=mix, device=self.env.device_index, temperature=temperature,
+                               epsilon=epsilon)
 
     def _alloc(self, T):
         n, dev = self.env.n, self.device

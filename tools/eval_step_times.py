@@ -7,7 +7,9 @@ usage: python tools/eval_step_times.py [--evaluate] LIB LABEL OUT [KIND ...]
   LABEL  goes in front of every line
   OUT    the lines are appended to this file
   KIND   "plain" (tarok_policy_step), a seat set 0..15 (tarok_policy_step_seats) or "versus:<set>"
-         (tarok_policy_step_versus: two different weight sets, PolicyNet(256) of torch seeds 0 and 1, parameters x 3)"""
+         (tarok_policy_step_versus: two different weight sets, PolicyNet(256) of torch seeds 0 and 1, parameters x 3)
+         or "mode:<temperature>:<epsilon>" (tarok_policy_step after tarok_set_play_mode: profiles/play_mode_step_times.txt;
+         the graph is captured with the mode set, so it replays the mode's kernel)"""
 import ctypes as C
 import os
 import sys
@@ -30,6 +32,9 @@ if hasattr(L, "tarok_policy_step_seats"):
     L.tarok_policy_step_seats.restype = i32; L.tarok_policy_step_seats.argtypes = [vp, i32, vp] + [vp] * 15 + [i32, vp]
 if hasattr(L, "tarok_policy_step_versus"):
     L.tarok_policy_step_versus.restype = i32; L.tarok_policy_step_versus.argtypes = [vp, i32, vp] + [vp] * 21 + [i32, vp]
+
+if hasattr(L, "tarok_set_play_mode"):
+    L.tarok_set_play_mode.restype = i32; L.tarok_set_play_mode.argtypes = [vp, C.c_float, C.c_float]
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tarok_amd import karte as K, selfplay as SP
@@ -59,6 +64,8 @@ lines = []
 for kind in kinds:
     h = vp()
     assert L.tarok_create(C.byref(h), 0, N, 0, 0, 0, 0) == 0
+    if kind.startswith("mode:"):
+        assert L.tarok_set_play_mode(h, float(kind.split(":")[1]), float(kind.split(":")[2])) == 0
     words = torch.zeros((2, N), dtype=torch.int64, device=dev)       # the observation words go back and forth
     act = torch.zeros((T, N), dtype=torch.uint8, device=dev)
     logp = torch.zeros((T, N), dtype=torch.float32, device=dev)
@@ -71,7 +78,7 @@ for kind in kinds:
         s = C.c_void_p(stream.cuda_stream)
         for t in range(T):
             a = ([p(x) for x in VS[0] + VS[1]] if kind.startswith("versus:") else [p(x) for x in W]) + [p(words[t % 2]), p(act[t]), p(logp[t]), p(val[t]), p(fw[t]), p(rew[t]), p(done[t]), None, p(words[(t + 1) % 2]), K.AUTO_RESET, s]
-            if kind == "plain":
+            if kind == "plain" or kind.startswith("mode:"):
                 rc = L.tarok_policy_step(h, *a)
             elif kind.startswith("versus:"):
                 rc = L.tarok_policy_step_versus(h, int(kind[7:]), None, *a)
@@ -105,7 +112,7 @@ for kind in kinds:
         one.append(e0.elapsed_time(e1) * 1e3)
         many.append(e1.elapsed_time(e2) * 1e3 / INNER)
     lines.append("%-8s %-22s one replay of 48 launches, us: %s | mean of %d back-to-back replays, us: %s" % (
-        label, "tarok_policy_step" if kind == "plain" else "policy_step_versus=%s" % kind[7:] if kind.startswith("versus:") else "policy_step_seats=%s" % kind,
+        label, "tarok_policy_step" if kind == "plain" else "policy_step (%s, %s)" % tuple(kind.split(":")[1:]) if kind.startswith("mode:") else "policy_step_versus=%s" % kind[7:] if kind.startswith("versus:") else "policy_step_seats=%s" % kind,
         " ".join("%.1f" % x for x in one), INNER, " ".join("%.1f" % x for x in many)))
     L.tarok_destroy(h)
     del g
