@@ -1765,6 +1765,22 @@ TK_KERNEL(TK_BLOCK, 64) void k_expand_features(int64_t n, const u64 *__restrict_
     out[j * 32 + chunk] = v;
 }
 
+// Block sum of three per-thread terms: part[blockIdx.x] = {sum s0, sum s1, sum s2, 0} over the workgroup, in a fixed
+// order (wave butterfly 32 .. 1, then the four waves in index order by thread 0): the result does not depend on the
+// schedule.  Every thread of the workgroup calls it.  Used by k_ppo_loss and the returns kernels (tarok_learner.inc).
+__device__ __forceinline__ void block_sum3(float s0, float s1, float s2, float4 *__restrict__ part) {
+    __shared__ float red[3][TK_BLOCK / 64];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { s0 += __shfl_xor(s0, o); s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s0; red[1][threadIdx.x >> 6] = s1; red[2][threadIdx.x >> 6] = s2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+        for (int k = 0; k < TK_BLOCK / 64; k++) { a0 += red[0][k]; a1 += red[1][k]; a2 += red[2][k]; }
+        part[blockIdx.x] = make_float4(a0, a1, a2, 0.f);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Learner side of the policy step: the clipped-surrogate policy-gradient loss
 // over the LEGAL cards, forward and gradient in one pass over the head outputs.  Replaces ~40
@@ -1783,7 +1799,6 @@ TK_KERNEL(TK_BLOCK, 256) void k_ppo_loss(int64_t n, const uint4 *__restrict__ ou
                                                       float ent_coef, const float *__restrict__ inv_wsum_p, uint4 *__restrict__ dout,
                                                       float4 *__restrict__ part) {
     TK_VGPR_TOP(256, 255);
-    __shared__ float red[3][TK_BLOCK / 64];
     float inv_wsum = *inv_wsum_p;
     int64_t i = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
     float s_pi = 0.f, s_v = 0.f, s_h = 0.f;
@@ -1862,18 +1877,7 @@ TK_KERNEL(TK_BLOCK, 256) void k_ppo_loss(int64_t n, const uint4 *__restrict__ ou
             dout[i * 8 + q] = v;
         }
     }
-    // block sums of the three loss terms (fixed order: the result does not depend on the schedule)
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        s_pi += __shfl_xor(s_pi, o); s_v += __shfl_xor(s_v, o); s_h += __shfl_xor(s_h, o);
-    }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s_pi; red[1][threadIdx.x >> 6] = s_v; red[2][threadIdx.x >> 6] = s_h; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-        for (int k = 0; k < TK_BLOCK / 64; k++) { a0 += red[0][k]; a1 += red[1][k]; a2 += red[2][k]; }
-        part[blockIdx.x] = make_float4(a0, a1, a2, 0.f);
-    }
+    block_sum3(s_pi, s_v, s_h, part);
 }
 
 // ---------------------------------------------------------------------------
@@ -3209,54 +3213,52 @@ int tarok_targets_ref(tarok_env *e, int T, const uint64_t *obs_before, const uin
     return TAROK_OK;
 }
 
+// The one launch of the returns front end: a returns kernel (Monte-Carlo or GAE, seat-masked or not) and k_adv_stats on
+// its block sums.  The masked kernel only where a mask can show: with the set 15 and no per-game sets it writes the
+// bytes of the unmasked one.
+static int launch_returns(tarok_env *e, int T, const uint8_t *done, const int16_t *reward, const uint64_t *obs, const float *logp,
+                          const float *value, const uint8_t *action, float scale, int gae, float gamma, float lambda, int seats,
+                          const uint8_t *seat_sets, float *rec, float *stats, float *scratch, void *stream) {
+    if (!e || T < 1 || !done || !reward || !obs || !logp || !value || !action || !rec || !stats || !scratch) return TAROK_EINVAL;
+    if (seats < 0 || seats > 15 || (gae != 0 && gae != 1)) return TAROK_EINVAL;
+    if (gae && (!(gamma >= 0.f && gamma <= 1.f) || !(lambda >= 0.f && lambda <= 1.f))) return TAROK_EINVAL;      // (NaN fails both)
+    HIPCHK(hipSetDevice(e->device));
+    const dim3 grid = grid_for(e->n), block(TK_BLOCK);
+    const hipStream_t st = (hipStream_t)stream;
+    const u64 *w = (const u64 *)obs;
+    float4 *r = (float4 *)rec, *part = (float4 *)scratch;
+    const bool mask = seat_sets || seats != 15;
+    if (gae && mask)
+        hipLaunchKernelGGL(k_returns_gae_seats, grid, block, 0, st, e->n, T, done, reward, w, logp, value, action, scale, gamma,
+                           gamma * lambda, (u32)seats, seat_sets, r, part);
+    else if (gae)
+        hipLaunchKernelGGL(k_returns_gae, grid, block, 0, st, e->n, T, done, reward, w, logp, value, action, scale, gamma, gamma * lambda, r, part);
+    else if (mask)
+        hipLaunchKernelGGL(k_returns_seats, grid, block, 0, st, e->n, T, done, reward, w, logp, value, action, scale, (u32)seats, seat_sets, r, part);
+    else
+        hipLaunchKernelGGL(k_returns, grid, block, 0, st, e->n, T, done, reward, w, logp, value, action, scale, r, part);
+    hipLaunchKernelGGL(k_adv_stats, dim3(1), block, 0, st, (int)grid.x, (int64_t)T * e->n, (const float4 *)part, (float4 *)stats);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
 int tarok_learn_returns(tarok_env *e, int T, const uint8_t *done, const int16_t *reward, const uint64_t *obs, const float *logp,
                         const float *value, const uint8_t *action, float reward_scale, float *rec_out, float *stats_out,
                         float *scratch, void *stream) {
-    if (!e || T < 1 || !done || !reward || !obs || !logp || !value || !action || !rec_out || !stats_out || !scratch) return TAROK_EINVAL;
-    HIPCHK(hipSetDevice(e->device));
-    dim3 grid = grid_for(e->n);
-    hipLaunchKernelGGL(k_returns, grid, dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, T, done, reward, (const u64 *)obs, logp, value,
-                       action, reward_scale, (float4 *)rec_out, (float4 *)scratch);
-    hipLaunchKernelGGL(k_adv_stats, dim3(1), dim3(TK_BLOCK), 0, (hipStream_t)stream, (int)grid.x, (int64_t)T * e->n,
-                       (const float4 *)scratch, (float4 *)stats_out);
-    HIPCHK(hipGetLastError());
-    return TAROK_OK;
+    return launch_returns(e, T, done, reward, obs, logp, value, action, reward_scale, 0, 1.f, 1.f, 15, nullptr, rec_out, stats_out, scratch, stream);
 }
 
 int tarok_learn_returns_gae(tarok_env *e, int T, const uint8_t *done, const int16_t *reward, const uint64_t *obs, const float *logp,
                             const float *value, const uint8_t *action, float reward_scale, float gamma, float lambda, float *rec_out,
                             float *stats_out, float *scratch, void *stream) {
-    if (!e || T < 1 || !done || !reward || !obs || !logp || !value || !action || !rec_out || !stats_out || !scratch) return TAROK_EINVAL;
-    if (!(gamma >= 0.f && gamma <= 1.f) || !(lambda >= 0.f && lambda <= 1.f)) return TAROK_EINVAL;      // (NaN fails both)
-    HIPCHK(hipSetDevice(e->device));
-    dim3 grid = grid_for(e->n);
-    hipLaunchKernelGGL(k_returns_gae, grid, dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, T, done, reward, (const u64 *)obs, logp,
-                       value, action, reward_scale, gamma, gamma * lambda, (float4 *)rec_out, (float4 *)scratch);
-    hipLaunchKernelGGL(k_adv_stats, dim3(1), dim3(TK_BLOCK), 0, (hipStream_t)stream, (int)grid.x, (int64_t)T * e->n,
-                       (const float4 *)scratch, (float4 *)stats_out);
-    HIPCHK(hipGetLastError());
-    return TAROK_OK;
+    return launch_returns(e, T, done, reward, obs, logp, value, action, reward_scale, 1, gamma, lambda, 15, nullptr, rec_out, stats_out, scratch, stream);
 }
 
 int tarok_learn_returns_seats(tarok_env *e, int T, const uint8_t *done, const int16_t *reward, const uint64_t *obs, const float *logp,
                               const float *value, const uint8_t *action, float reward_scale, int gae, float gamma, float lambda,
                               int seats, const uint8_t *seats_per_game, float *rec_out, float *stats_out, float *scratch, void *stream) {
-    if (!e || T < 1 || !done || !reward || !obs || !logp || !value || !action || !rec_out || !stats_out || !scratch) return TAROK_EINVAL;
-    if (seats < 0 || seats > 15 || (gae != 0 && gae != 1)) return TAROK_EINVAL;
-    if (gae && (!(gamma >= 0.f && gamma <= 1.f) || !(lambda >= 0.f && lambda <= 1.f))) return TAROK_EINVAL;      // (NaN fails both)
-    HIPCHK(hipSetDevice(e->device));
-    dim3 grid = grid_for(e->n);
-    if (gae)
-        hipLaunchKernelGGL(k_returns_gae_seats, grid, dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, T, done, reward, (const u64 *)obs, logp,
-                           value, action, reward_scale, gamma, gamma * lambda, (u32)seats, seats_per_game, (float4 *)rec_out,
-                           (float4 *)scratch);
-    else
-        hipLaunchKernelGGL(k_returns_seats, grid, dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, T, done, reward, (const u64 *)obs, logp,
-                           value, action, reward_scale, (u32)seats, seats_per_game, (float4 *)rec_out, (float4 *)scratch);
-    hipLaunchKernelGGL(k_adv_stats, dim3(1), dim3(TK_BLOCK), 0, (hipStream_t)stream, (int)grid.x, (int64_t)T * e->n,
-                       (const float4 *)scratch, (float4 *)stats_out);
-    HIPCHK(hipGetLastError());
-    return TAROK_OK;
+    return launch_returns(e, T, done, reward, obs, logp, value, action, reward_scale, gae, gamma, lambda, seats, seats_per_game, rec_out,
+                          stats_out, scratch, stream);
 }
 
 // scratch of tarok_learn_select: tile_off [tiles] i64, then tile_cnt [tiles] u32 (rounded up to 16 bytes)

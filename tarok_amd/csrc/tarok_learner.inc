@@ -54,7 +54,6 @@ static_assert(LN_P == TAROK_MLP_PARAMS, "flat parameter vector");
 template <bool MASK>
 __device__ __forceinline__ void returns_walk(TK_RETURNS_ARGS, u32 seats, const uint8_t *__restrict__ seat_sets,
                                              float4 *__restrict__ rec, float4 *__restrict__ part) {
-    __shared__ float red[3][TK_BLOCK / 64];
     int64_t i = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
     float s_n = 0.f, s_a = 0.f, s_q = 0.f;
     if (i < n) {
@@ -73,15 +72,7 @@ __device__ __forceinline__ void returns_walk(TK_RETURNS_ARGS, u32 seats, const u
             if (known) { float a = r - v; s_n += 1.f; s_a += a; s_q += a * a; }
         }
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { s_n += __shfl_xor(s_n, o); s_a += __shfl_xor(s_a, o); s_q += __shfl_xor(s_q, o); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s_n; red[1][threadIdx.x >> 6] = s_a; red[2][threadIdx.x >> 6] = s_q; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-        for (int k = 0; k < TK_BLOCK / 64; k++) { a0 += red[0][k]; a1 += red[1][k]; a2 += red[2][k]; }
-        part[blockIdx.x] = make_float4(a0, a1, a2, 0.f);
-    }
+    block_sum3(s_n, s_a, s_q, part);
 }
 TK_KERNEL(TK_BLOCK, 64) void k_returns(TK_RETURNS_ARGS, float4 *__restrict__ rec, float4 *__restrict__ part) {
     TK_VGPR_TOP(64, 63);
@@ -113,7 +104,6 @@ TK_KERNEL(TK_BLOCK, 64) void k_returns_seats(TK_RETURNS_ARGS, u32 seats, const u
 template <bool MASK>
 __device__ __forceinline__ void returns_gae_walk(TK_RETURNS_ARGS, float gamma, float gl, u32 seats, const uint8_t *__restrict__ seat_sets,
                                                  float4 *__restrict__ rec, float4 *__restrict__ part) {
-    __shared__ float red[3][TK_BLOCK / 64];
     int64_t i = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
     float s_n = 0.f, s_a = 0.f, s_q = 0.f;
     if (i < n) {
@@ -145,15 +135,7 @@ __device__ __forceinline__ void returns_gae_walk(TK_RETURNS_ARGS, float gamma, f
             if (mine) { s_n += 1.f; s_a += a; s_q += a * a; }
         }
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { s_n += __shfl_xor(s_n, o); s_a += __shfl_xor(s_a, o); s_q += __shfl_xor(s_q, o); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s_n; red[1][threadIdx.x >> 6] = s_a; red[2][threadIdx.x >> 6] = s_q; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-        for (int k = 0; k < TK_BLOCK / 64; k++) { a0 += red[0][k]; a1 += red[1][k]; a2 += red[2][k]; }
-        part[blockIdx.x] = make_float4(a0, a1, a2, 0.f);
-    }
+    block_sum3(s_n, s_a, s_q, part);
 }
 TK_KERNEL(TK_BLOCK, 64) void k_returns_gae(TK_RETURNS_ARGS, float gamma, float gl, float4 *__restrict__ rec, float4 *__restrict__ part) {
     TK_VGPR_TOP(64, 63);
@@ -165,18 +147,34 @@ TK_KERNEL(TK_BLOCK, 64) void k_returns_gae_seats(TK_RETURNS_ARGS, float gamma, f
     returns_gae_walk<true>(TK_RETURNS_NAMES, gamma, gl, seats, seat_sets, rec, part);
 }
 
-// stats = {mean, 1 / std, known fraction, 0} of the advantages from k_returns' block sums (one workgroup)
+// Column sums of `blocks` float4 partials by one workgroup, in double and in a fixed order (strided accumulate per thread,
+// LDS tree): afterwards red[c][0] = the sum of column c, for thread 0.
+template <int C>
+__device__ __forceinline__ void part_column_sums(int blocks, const float4 *__restrict__ part, double (&red)[C][TK_BLOCK]) {
+    double a[C] = {};
+    for (int k = threadIdx.x; k < blocks; k += TK_BLOCK) {
+        float4 p = part[k];
+        const float col[4] = {p.x, p.y, p.z, p.w};
+#pragma unroll
+        for (int c = 0; c < C; c++) a[c] += col[c];
+    }
+#pragma unroll
+    for (int c = 0; c < C; c++) red[c][threadIdx.x] = a[c];
+    __syncthreads();
+    for (int s = TK_BLOCK / 2; s >= 1; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+#pragma unroll
+            for (int c = 0; c < C; c++) red[c][threadIdx.x] += red[c][threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+}
+
+// stats = {mean, 1 / std, known fraction, 0} of the advantages from the returns kernels' block sums (one workgroup)
 TK_KERNEL(TK_BLOCK, 64) void k_adv_stats(int blocks, int64_t total, const float4 *__restrict__ part, float4 *__restrict__ stats) {
     TK_VGPR_TOP(64, 63);
     __shared__ double red[3][TK_BLOCK];
-    double a = 0, b = 0, c = 0;
-    for (int k = threadIdx.x; k < blocks; k += TK_BLOCK) { float4 p = part[k]; a += p.x; b += p.y; c += p.z; }
-    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b; red[2][threadIdx.x] = c;
-    __syncthreads();
-    for (int s = TK_BLOCK / 2; s >= 1; s >>= 1) {
-        if ((int)threadIdx.x < s) { red[0][threadIdx.x] += red[0][threadIdx.x + s]; red[1][threadIdx.x] += red[1][threadIdx.x + s]; red[2][threadIdx.x] += red[2][threadIdx.x + s]; }
-        __syncthreads();
-    }
+    part_column_sums<3>(blocks, part, red);
     if (threadIdx.x == 0) {
         double cnt = red[0][0] < 1.0 ? 1.0 : red[0][0];
         double mean = red[1][0] / cnt;
@@ -895,15 +893,7 @@ TK_KERNEL(TK_BLOCK, 64) void k_learn_terms(int blocks, const float4 *__restrict_
                                                          float4 *__restrict__ running /* or NULL: += the terms (epoch statistics) */) {
     TK_VGPR_TOP(64, 63);
     __shared__ double red[4][TK_BLOCK];
-    double a = 0, b = 0, c = 0, d = 0;
-    for (int k = threadIdx.x; k < blocks; k += TK_BLOCK) { float4 p = part[k]; a += p.x; b += p.y; c += p.z; d += p.w; }
-    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b; red[2][threadIdx.x] = c; red[3][threadIdx.x] = d;
-    __syncthreads();
-    for (int s = TK_BLOCK / 2; s >= 1; s >>= 1) {
-        if ((int)threadIdx.x < s)
-            for (int k = 0; k < 4; k++) red[k][threadIdx.x] += red[k][threadIdx.x + s];
-        __syncthreads();
-    }
+    part_column_sums<4>(blocks, part, red);
     if (threadIdx.x == 0) {
         double inv = 1.0 / (red[3][0] < 1.0 ? 1.0 : red[3][0]);
         float4 t = make_float4((float)(red[0][0] * inv), (float)(red[1][0] * inv), (float)(red[2][0] * inv), (float)inv);

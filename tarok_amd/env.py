@@ -402,34 +402,24 @@ class TarokVecEnv:
         opponent (six tensors like `weights`): a second network in the Bot's place (tarok_policy_step_versus) — the
         seats of the set play `weights`, the others `opponent`, each with its own card, logp and value; without
         seats / seats_per_game the set is 15."""
-        w1, b1, w2, b2, w3, b3 = weights
         flags = K.AUTO_RESET if auto_reset else 0
+        plain = opponent is None and seats is None and seats_per_game is None
+        sets = () if plain else (15 if seats is None else int(seats), self._p(self._seat_sets(seats_per_game)))
+        nets = [weights] if opponent is None else [self.check_mlp_weights(weights), self.check_mlp_weights(opponent)]
+        fn = self.L.tarok_policy_step if plain else self.L.tarok_policy_step_seats if opponent is None else self.L.tarok_policy_step_versus
         with torch.cuda.device(self.device):
-            if opponent is None and seats is None and seats_per_game is None:
-                _native.check(self.L.tarok_policy_step(self._h, self._p(w1), self._p(b1), self._p(w2), self._p(b2), self._p(w3),
-                                                       self._p(b3), self._p(obs_words), self._p(action_out), self._p(logp_out),
-                                                       self._p(value_out), self._p(feature_words_out), self._p(reward_out),
-                                                       self._p(done_out), self._p(tricks), self._p(obs_out), flags, self._stream()))
-                return action_out
-            if seats_per_game is not None:
-                spg = seats_per_game
-                if not (torch.is_tensor(spg) and spg.device == self.device and spg.dtype == torch.uint8 and spg.is_contiguous()
-                        and tuple(spg.shape) == (self.n,)):
-                    raise ValueError("seats_per_game: a contiguous uint8 tensor [N] on the env's device")
-            if opponent is not None:
-                w1, b1, w2, b2, w3, b3 = self.check_mlp_weights(weights)
-                _native.check(self.L.tarok_policy_step_versus(
-                    self._h, 15 if seats is None else int(seats), self._p(seats_per_game), self._p(w1), self._p(b1), self._p(w2),
-                    self._p(b2), self._p(w3), self._p(b3), *[self._p(t) for t in self.check_mlp_weights(opponent)],
-                    self._p(obs_words), self._p(action_out), self._p(logp_out), self._p(value_out), self._p(feature_words_out),
-                    self._p(reward_out), self._p(done_out), self._p(tricks), self._p(obs_out), flags, self._stream()))
-                return action_out
-            _native.check(self.L.tarok_policy_step_seats(self._h, 15 if seats is None else int(seats), self._p(seats_per_game),
-                                                         self._p(w1), self._p(b1), self._p(w2), self._p(b2), self._p(w3),
-                                                         self._p(b3), self._p(obs_words), self._p(action_out), self._p(logp_out),
-                                                         self._p(value_out), self._p(feature_words_out), self._p(reward_out),
-                                                         self._p(done_out), self._p(tricks), self._p(obs_out), flags, self._stream()))
+            _native.check(fn(self._h, *sets, *[self._p(t) for net in nets for t in net], self._p(obs_words), self._p(action_out),
+                             self._p(logp_out), self._p(value_out), self._p(feature_words_out), self._p(reward_out), self._p(done_out),
+                             self._p(tricks), self._p(obs_out), flags, self._stream()))
         return action_out
+
+    def _seat_sets(self, seats_per_game):
+        """seats_per_game as the C entry points take it: None, or a contiguous uint8 tensor [N] on the env's device."""
+        spg = seats_per_game
+        if spg is not None and not (torch.is_tensor(spg) and spg.device == self.device and spg.dtype == torch.uint8
+                                    and spg.is_contiguous() and tuple(spg.shape) == (self.n,)):
+            raise ValueError("seats_per_game: a contiguous uint8 tensor [N] on the env's device")
+        return spg
 
     def ppo_loss(self, out, obs_words, action, logp_old, advantage, ret, weight, clip, vf_coef, ent_coef):
         """tarok_ppo_loss: (loss terms f32 [3] = weighted means of the policy loss, the squared value
@@ -466,34 +456,27 @@ class TarokVecEnv:
         return dy, meta
 
     # ---- the fused learner (include/tarok_env.h tarok_learn_*; driven by tarok_amd.selfplay.SelfPlay.update_fused)
-    def learn_returns(self, T, done, reward, words, logp, val, act, reward_scale, rec, stats, scratch):
+    def _learn_returns(self, T, done, reward, words, logp, val, act, reward_scale, rec, stats, scratch, gae, gamma, lam, seats, seats_per_game):
         with torch.cuda.device(self.device):
-            _native.check(self.L.tarok_learn_returns(self._h, int(T), self._p(done), self._p(reward), self._p(words), self._p(logp),
-                                                     self._p(val), self._p(act), float(reward_scale), self._p(rec), self._p(stats),
-                                                     self._p(scratch), self._stream()))
+            _native.check(self.L.tarok_learn_returns_seats(self._h, int(T), self._p(done), self._p(reward), self._p(words), self._p(logp),
+                                                           self._p(val), self._p(act), float(reward_scale), 1 if gae else 0, float(gamma),
+                                                           float(lam), int(seats), self._p(self._seat_sets(seats_per_game)), self._p(rec),
+                                                           self._p(stats), self._p(scratch), self._stream()))
+
+    def learn_returns(self, T, done, reward, words, logp, val, act, reward_scale, rec, stats, scratch):
+        """The record and advantage statistics of tarok_learn_returns: every card credited with its seat's final score."""
+        self._learn_returns(T, done, reward, words, logp, val, act, reward_scale, rec, stats, scratch, False, 1.0, 1.0, 15, None)
 
     def learn_returns_gae(self, T, done, reward, words, logp, val, act, reward_scale, gamma, lam, rec, stats, scratch):
-        """tarok_learn_returns_gae: the record of learn_returns with per-seat GAE(gamma, lam) returns."""
-        with torch.cuda.device(self.device):
-            _native.check(self.L.tarok_learn_returns_gae(self._h, int(T), self._p(done), self._p(reward), self._p(words), self._p(logp),
-                                                         self._p(val), self._p(act), float(reward_scale), float(gamma), float(lam),
-                                                         self._p(rec), self._p(stats), self._p(scratch), self._stream()))
+        """The record of learn_returns with per-seat GAE(gamma, lam) returns (tarok_learn_returns_gae)."""
+        self._learn_returns(T, done, reward, words, logp, val, act, reward_scale, rec, stats, scratch, True, gamma, lam, 15, None)
 
     def learn_returns_seats(self, T, done, reward, words, logp, val, act, reward_scale, rec, stats, scratch, gae=False, gamma=1.0,
                             lam=1.0, seats=15, seats_per_game=None):
         """tarok_learn_returns_seats: the record of learn_returns (gae=False) or learn_returns_gae (gae=True) with `known`
         masked by the learner's seats: seats (a 4-bit set for every slot) or seats_per_game ([N] uint8 device tensor of
-        sets), as in policy_step."""
-        if seats_per_game is not None:
-            spg = seats_per_game
-            if not (torch.is_tensor(spg) and spg.device == self.device and spg.dtype == torch.uint8 and spg.is_contiguous()
-                    and tuple(spg.shape) == (self.n,)):
-                raise ValueError("seats_per_game: a contiguous uint8 tensor [N] on the env's device")
-        with torch.cuda.device(self.device):
-            _native.check(self.L.tarok_learn_returns_seats(self._h, int(T), self._p(done), self._p(reward), self._p(words), self._p(logp),
-                                                           self._p(val), self._p(act), float(reward_scale), 1 if gae else 0, float(gamma),
-                                                           float(lam), int(seats), self._p(seats_per_game), self._p(rec), self._p(stats),
-                                                           self._p(scratch), self._stream()))
+        sets), as in policy_step.  The set 15 without seats_per_game masks nothing: the unmasked kernel runs."""
+        self._learn_returns(T, done, reward, words, logp, val, act, reward_scale, rec, stats, scratch, gae, gamma, lam, seats, seats_per_game)
 
     def learn_select_scratch_bytes(self, M):
         return int(self.L.tarok_learn_select_scratch_bytes(int(M)))

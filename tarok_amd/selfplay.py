@@ -142,7 +142,7 @@ def assign_returns(done, reward, seat, learner=None):
     return ret, known
 
 
-def assign_gae(done, reward, seat, val, gamma, lam, reward_scale):
+def assign_gae(done, reward, seat, val, gamma, lam, reward_scale, learner=None):
     """Returns by GAE(gamma, lam) per seat, bootstrapped from the value of the same seat's next decision inside the
     rollout: the plain torch statement of tarok_learn_returns_gae (include/tarok_env.h), the counterpart of
     assign_returns.
@@ -152,7 +152,10 @@ def assign_gae(done, reward, seat, val, gamma, lam, reward_scale):
     game ended in between, else 0), have (there is such a decision, or the game ended).  gamma discounts per decision of
     the seat, not per lock-step.  Returns (ret [T,N] f32 = advantage + value, already scaled; known [T,N] bool):
     `known` is False only for a seat's last decision of a game still unfinished when the rollout ends.  The walk itself
-    runs in float64 (this is the reference statement, not the hot path), so `ret` is the recursion's value rounded once."""
+    runs in float64 (this is the reference statement, not the hot path), so `ret` is the recursion's value rounded once.
+    learner ([N] uint8 seat sets as in assign_returns): `known` is also False where another seat than the learner's
+    played (tarok_learn_returns_seats with gae = 1).  The walk is the same for every seat — a seat's chain reads that
+    seat's values only — so the returns are the same."""
     T, N = done.shape
     dev = done.device
     ret = torch.zeros((T, N), dtype=torch.float32, device=dev)
@@ -176,17 +179,14 @@ def assign_gae(done, reward, seat, val, gamma, lam, reward_scale):
         mine = seats == s
         nv, na, pr = torch.where(mine, v.unsqueeze(-1), nv), torch.where(mine, a.unsqueeze(-1), na), torch.where(mine, zero, pr)
         have = have | mine
+    if learner is not None:
+        known &= learner_moves(seat, learner)
     return ret, known
 
 
 def assign_gae_seats(done, reward, seat, val, gamma, lam, reward_scale, learner=None):
-    """assign_gae with `known` masked by the learner's seats (learner [N] uint8 seat sets as in assign_returns; None:
-    assign_gae itself): the plain torch statement of tarok_learn_returns_seats with gae = 1.  The walk is assign_gae's
-    for every seat — a seat's chain reads that seat's values only — so the returns are the same."""
-    ret, known = assign_gae(done, reward, seat, val, gamma, lam, reward_scale)
-    if learner is not None:
-        known &= learner_moves(seat, learner)
-    return ret, known
+    """assign_gae under its earlier name for the seat-masked call."""
+    return assign_gae(done, reward, seat, val, gamma, lam, reward_scale, learner=learner)
 
 
 def dw_ranges(B, cap=K.LEARN_MAX_BATCH):
@@ -485,8 +485,8 @@ class SelfPlay:
         words_t = buf["words"][:T]
         seat = (words_t >> K.OBS_SEAT_SHIFT) & 3
         if self.gae:
-            ret, known = assign_gae_seats(buf["done"].bool(), buf["reward"], seat, buf["val"], self.gamma, self.gae_lambda, self.reward_scale,
-                                          learner=self._seats)
+            ret, known = assign_gae(buf["done"].bool(), buf["reward"], seat, buf["val"], self.gamma, self.gae_lambda, self.reward_scale,
+                                    learner=self._seats)
         else:
             ret, known = assign_returns(buf["done"].bool(), buf["reward"], seat, learner=self._seats)
             ret = ret * self.reward_scale
@@ -594,10 +594,10 @@ class SelfPlay:
         B = -(-M // minibatches)
         lb = self._learn_bufs(M, B)
         sel, count = None, M
+        env.learn_returns_seats(T, buf["done"], buf["reward"], buf["words"][:T], buf["logp"], buf["val"], buf["act"], self.reward_scale,
+                                lb["rec"], lb["stats"], lb["scratch"], gae=self.gae, gamma=self.gamma, lam=self.gae_lambda,
+                                seats_per_game=self._seats)      # (None outside opponent mode: the unmasked kernel)
         if self._opp is not None:
-            env.learn_returns_seats(T, buf["done"], buf["reward"], buf["words"][:T], buf["logp"], buf["val"], buf["act"],
-                                    self.reward_scale, lb["rec"], lb["stats"], lb["scratch"], gae=self.gae, gamma=self.gamma,
-                                    lam=self.gae_lambda, seats_per_game=self._seats)
             if "sel" not in lb:
                 lb["sel"] = torch.empty(M, dtype=torch.int64, device=self.device)
                 lb["sel_count"] = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -607,12 +607,6 @@ class SelfPlay:
             sel = lb["sel"]
             if count == 0:                            # nothing of the learner's: no launch, no step
                 return dict(loss=0.0, pi_loss=0.0, v_loss=0.0, entropy=0.0, allreduce_bytes=0, known_frac=0.0, learner_samples=0)
-        elif self.gae:
-            env.learn_returns_gae(T, buf["done"], buf["reward"], buf["words"][:T], buf["logp"], buf["val"], buf["act"],
-                                  self.reward_scale, self.gamma, self.gae_lambda, lb["rec"], lb["stats"], lb["scratch"])
-        else:
-            env.learn_returns(T, buf["done"], buf["reward"], buf["words"][:T], buf["logp"], buf["val"], buf["act"], self.reward_scale,
-                              lb["rec"], lb["stats"], lb["scratch"])
         words = buf["obs"].view(M, 4)
         lb["running"].zero_()
         nbytes = 0

@@ -79,4 +79,5 @@ def test_unknown_samples_are_the_last_decision_of_each_seat_of_the_unfinished_ga
 def test_selfplay_arguments_default_to_none():
     sig = inspect.signature(SP.SelfPlay.__init__).parameters
     assert sig["gamma"].default is None and sig["gae_lambda"].default is None
-    assert list(inspect.signature(SP.assign_gae).parameters) == ["done", "reward", "seat", "val", "gamma", "lam", "reward_scale"]
+    assert list(inspect.signature(SP.assign_gae).parameters) == ["done", "reward", "seat", "val", "gamma", "lam", "reward_scale", "learner"]
+    assert inspect.signature(SP.assign_gae).parameters["learner"].default is None
