@@ -647,7 +647,10 @@ __device__ __forceinline__ void play_role(
     // games are whole tricks long: a wave whose lanes all start a launch of whole tricks at a trick boundary plays
     // the trick-aligned loop (below) — known here, where it decides how many lines are loaded ahead.
     const bool all_play = autoreset && __ballot(valid && g.phase == TK_PHASE_PLAY) == ~0ULL;
-    const bool aligned = all_play && (cards & 3) == 0 && __ballot(g.nt != 0) == 0;
+    // (the trick-aligned loops address the action and done rows by a 32-bit element offset, see out_b below: a launch whose
+    // last row would not fit one plays the loop that is not trick-aligned — more than twenty million games at 192 cards)
+    const bool aligned = all_play && (cards & 3) == 0 && __ballot(g.nt != 0) == 0 &&
+                         (u64)stride <= 0xFFFFFFFFull && (u64)stride * (u32)cards + (u64)n <= 0xFFFFFFFFull;
     if (spec) {
         acc = cnt[i].score_sum;
         cur_ep = cnt[i].episode;
@@ -679,6 +682,12 @@ __device__ __forceinline__ void play_role(
     // from lines — none for a lane that cannot finish in this launch (its counters are not loaded), none any more
     // once a game was dealt in place
     u32 lim = spec ? allowed : 0u;
+    // trick-aligned loops: where the card's output rows go.  The action and done rows share ONE 32-bit element offset per
+    // lane (scalar base + 32-bit lane offset: the store forms its address itself), one add per card for both; the
+    // observation row keeps a 64-bit pointer (eight times the offset passes 2^32 at four million games), one add per card.
+    // Eight address instructions per trick for its twelve stores, not fourteen
+    u32 out_b = (u32)i;
+    u64 *out_obs = obs + i;
     // fill the line buffers of the lanes that lack them (lacks: the next game's, lacks2: the one after it)
     auto fetch_lines = [&](bool lacks, bool lacks2) __attribute__((always_inline)) {
         if (lacks) load_line(&aux[i].line[TK_LINE(cur_ep + 1)], na, nb, nkey, ok1, nep1);
@@ -748,7 +757,10 @@ __device__ __forceinline__ void play_role(
             touched = touched || res != -2;
             seats_dirty = seats_dirty || (res >= 0 && g.nt == 0);
         }
-        if (v) {
+        if constexpr (ALIGNED) {
+            if (STD || action_out) TK_STREAM_STORE(&action_out[out_b], (uint8_t)a);
+            if (!STD && trick) TK_STREAM_STORE(&trick[out_b], (uint16_t)trick_info);
+        } else if (v) {
             if (STD || action_out) TK_STREAM_STORE(&action_out[row], (uint8_t)a);
             if (!STD && trick) TK_STREAM_STORE(&trick[row], (uint16_t)trick_info);
         }
@@ -885,18 +897,18 @@ __device__ __forceinline__ void play_role(
         if constexpr (ALIGNED && NT < 3) legal = legal_mask_follow(hand_of<true>(g, (g.leader + g.nt) & 3), g.trick & 63, g.contract, legal_hi);
         else if constexpr (ALIGNED) legal = legal_mask(hand_of<true>(g, g.leader), false, 0u, g.contract);
         else legal = (ALL || (v && g.phase == TK_PHASE_PLAY)) ? legal_now(g) : 0;
-        if (v) {
-            // (ALL: res is 0 or 1 — the number itself goes into the observation's bit 62 and the done row, no selects)
-            const u32 fin01 = ALL ? (u32)res : (fin ? 1u : 0u);
-            if constexpr (ALIGNED) {
-                // (the seat and position bits are carried: one add per card; after the 4th card the seat to play is the
-                // trick's winner, or a fresh game's leader: rebuilt there, two instructions)
-                if constexpr (NT < 3) ocar += TK_OBS_CARD;
-                else ocar = obs_carry(g.leader, g.trick_no << 2);
-                TK_STREAM_STORE(&obs[row], obs_word_with(ocar, g.error, fin01, legal));
-            } else {
-                TK_STREAM_STORE(&obs[row], obs_word_with<true>(g, false, legal) | ((u64)(ALL ? fin01 : ((fin || g.phase == TK_PHASE_DONE) ? 1u : 0u)) << 62));
-            }
+        // (ALL: res is 0 or 1 — the number itself goes into the observation's bit 62 and the done row, no selects)
+        const u32 fin01 = ALL ? (u32)res : (fin ? 1u : 0u);
+        if constexpr (ALIGNED) {
+            // (the seat and position bits are carried: one add per card; after the 4th card the seat to play is the
+            // trick's winner, or a fresh game's leader: rebuilt there, two instructions)
+            if constexpr (NT < 3) ocar += TK_OBS_CARD;
+            else ocar = obs_carry(g.leader, g.trick_no << 2);
+            TK_STREAM_STORE(out_obs, obs_word_with(ocar, g.error, fin01, legal));
+            if (STD || done) TK_STREAM_STORE(&done[out_b], (uint8_t)fin01);
+            out_b += (u32)stride; out_obs += stride;          // (the card's last stores: on to the next card's row)
+        } else if (v) {
+            TK_STREAM_STORE(&obs[row], obs_word_with<true>(g, false, legal) | ((u64)(ALL ? fin01 : ((fin || g.phase == TK_PHASE_DONE) ? 1u : 0u)) << 62));
             if (STD || done) TK_STREAM_STORE(&done[row], (uint8_t)fin01);
         }
     };
@@ -915,11 +927,12 @@ __device__ __forceinline__ void play_role(
                 g.C |= TK_C_PAD;
                 rctr = rng_ctr(128u + g.trick_no * 4).v;
                 ocar = obs_carry(g.leader, g.trick_no << 2);
+                // (these copies address their rows by out_b / out_obs, advanced inside the card: `row` is not read)
                 for (int c = 0; c < cards; c += 4) {
-                    play_card(std::true_type{}, std::integral_constant<int, 0>{}, std_tag, row, c); row += stride;
-                    play_card(std::true_type{}, std::integral_constant<int, 1>{}, std_tag, row, c + 1); row += stride;
-                    play_card(std::true_type{}, std::integral_constant<int, 2>{}, std_tag, row, c + 2); row += stride;
-                    play_card(std::true_type{}, std::integral_constant<int, 3>{}, std_tag, row, c + 3); row += stride;
+                    play_card(std::true_type{}, std::integral_constant<int, 0>{}, std_tag, row, c);
+                    play_card(std::true_type{}, std::integral_constant<int, 1>{}, std_tag, row, c + 1);
+                    play_card(std::true_type{}, std::integral_constant<int, 2>{}, std_tag, row, c + 2);
+                    play_card(std::true_type{}, std::integral_constant<int, 3>{}, std_tag, row, c + 3);
                 }
                 g.C &= TK_DECK;
             };
