@@ -211,6 +211,37 @@ int tarok_run_random(tarok_env *env, int64_t n_steps, int cards_per_launch, int 
 int tarok_rollout_random(tarok_env *env, uint32_t episode, int16_t *scores_out, int16_t *nsteps_out,
                          int8_t *seats_out, uint64_t *masks_out, uint8_t *actions_out, void *stream);
 
+/* Open-hand Monte-Carlo playouts from the env's CURRENT positions: what is each legal card of the seat to move worth?
+ * Every legal card is tried and the game played out to its end `samples` times by the Bot (a uniformly random legal card
+ * on every seat); the final scores are summed.  The playouts use the TRUE hidden hands — perfect information, no
+ * re-dealing of the unseen cards — so the result is an upper-side yardstick and a teacher signal, NOT a fair player.
+ *
+ * Terms: s = the seat to move, legal = its legal mask, played = trick number * 4 + cards on the table, ep = the slot's
+ * episode number, gidx = game_offset + g.  A game TAKES PART iff it is in the play phase and s is in its seat set:
+ * `seats`, or seats_per_game[g] & 15 when that array is given (as in tarok_policy_step_seats).
+ * For a game that takes part, every rank j < popcount(legal) — c = the j-th lowest legal card — and sample k < samples:
+ * copy the game, play c, then play to the end with the Bot: at q cards played the card is the uniform legal card of
+ * spec RNG draw 128 + q under the playout key
+ *     pkey = game_key(seed ^ salt, gidx, E),   E = 1 << 63 | (u64)ep << 28 | played << 22 | c << 16 | k
+ * (bit 63 keeps E apart from every episode number a deal is keyed by), and add the four final scores to
+ * sum_out[g][j][0..3].  A card that ends the game outright adds `samples` times that score; a Berac that ends early is
+ * scored where it ends.
+ *   sum_out     [N,12,4] i32, 16-byte aligned, or NULL.  EVERY row is written: zeros for ranks at or beyond the number
+ *               of legal cards and for games that do not take part (a Bot seat to move, a finished game, a game
+ *               waiting for the exchange).  sum[j][s] / samples is the card's mean score for the mover.
+ *   action_out  [N] u8 or NULL: for a game that takes part the legal card of the smallest rank j that maximises
+ *               sum[j][s]; for a game in play whose mover is outside the set the Bot's card (tarok_policy_random's);
+ *               255 for any other game.
+ * seats = 15: every seat is the Monte-Carlo player; seats = 0: tarok_policy_random's cards, no playout is run.
+ * Read-only on the env: the state, the next-game lines and refill lists, the launch counters, the history, the score
+ * sums and the play mode are untouched, and the result is a function of the arguments and the state alone.
+ * TAROK_EINVAL (before any HIP call) for a NULL env, samples outside 1..TAROK_PLAYOUT_MAX_SAMPLES, seats outside 0..15
+ * or both outputs NULL. */
+#define TAROK_PLAYOUT_RANKS 12          /* a hand in play never holds more than 12 cards */
+#define TAROK_PLAYOUT_MAX_SAMPLES 1024
+int tarok_playout_cards(tarok_env *env, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                        int32_t *sum_out, uint8_t *action_out, void *stream);
+
 /* Observation features of the seat to move for a policy network: features_out [N,256] bf16,
  * every entry 0.0 or 1.0 (feature set documented at k_observe — the build's own,
  * the reference's encoder is part of its LSTM agent, Igralec.py:453-543):

@@ -8,11 +8,11 @@ without a GPU; creating an environment does not (no CPU fallback)."""
 from . import karte
 from ._native import TarokNativeError, build
 
-__all__ = ["karte", "build", "TarokNativeError", "TarokVecEnv", "Obs"]
+__all__ = ["karte", "build", "TarokNativeError", "TarokVecEnv", "Obs", "playout_values"]
 
 
 def __getattr__(name):
-    if name in ("TarokVecEnv", "Obs"):
+    if name in ("TarokVecEnv", "Obs", "playout_values"):
         from . import env
         return getattr(env, name)
     raise AttributeError(name)

@@ -1312,6 +1312,102 @@ TK_KERNEL(TK_BLOCK, 96) void k_rollout(int64_t n, u64 seed, u64 offset, u32 epis
     if (nsteps_out) nsteps_out[i] = (int16_t)played;
 }
 
+// tarok_playout_cards: open-hand Monte-Carlo playouts from the env's CURRENT positions (the true hidden hands: perfect
+// information, not a fair player).  Read-only on the env.  A team of 2^lg lanes (4 .. 256, the host picks it from
+// `samples`) owns one game; the game's work items (rank j of a legal card, sample k), nlegal * samples of them, are dealt
+// round-robin over the team's lanes, so a follower's two legal cards keep as many lanes busy as a leader's twelve.  All
+// lanes of a team play the same game on from the same card count: their playouts have the same length (a Berac may end
+// early in some of them), and the loops below branch on team-uniform values.  The four scores of a playout are added to
+// the team's [12][4] row block in LDS (integer adds: the result does not depend on the lane layout), which one pass
+// writes to sum_out as 16-byte rows and reads for the card.  A game that does not take part runs no playout: zero rows.
+#define TK_PO_MIN_LG 2
+#define TK_PO_MAX_LG 8
+TK_KERNEL(TK_BLOCK, 128) void k_playout(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 samples, u32 lg, u32 seats,
+                                       const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                       const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                       const u64 *__restrict__ gkey, int4 *__restrict__ sum_out, uint8_t *__restrict__ action_out) {
+    TK_VGPR_TOP(128, 127);
+    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> TK_PO_MIN_LG) * TAROK_PLAYOUT_RANKS * 4];
+    const u32 tid = threadIdx.x, team = tid >> lg, L = 1u << lg, lane = tid & (L - 1u), teams = (u32)TK_BLOCK >> lg;
+    const int64_t g = (int64_t)blockIdx.x * teams + team;
+    for (u32 w = tid; w < teams * (TAROK_PLAYOUT_RANKS * 4); w += TK_BLOCK) sums[w] = 0;
+    __syncthreads();
+    int *row = sums + team * (TAROK_PLAYOUT_RANKS * 4);
+    u64 legal = 0;
+    u32 mover = 0, played = 0, nlegal = 0;
+    bool in_play = false, takes_part = false;
+    if (g < n) {
+        const ulonglong2 a = s01[g], b = s23[g];
+        Game g0;
+        unpack(g0, a.x, a.y, b.x, b.y);
+        in_play = g0.phase == TK_PHASE_PLAY;
+        if (in_play) {
+            legal = legal_now(g0);
+            mover = (g0.leader + g0.nt) & 3;
+            played = g0.trick_no * 4 + g0.nt;
+            u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+            takes_part = (set >> mover) & 1u;
+        }
+        if (takes_part) {
+            nlegal = (u32)popc64(legal);
+            const u64 ebase = (1ULL << 63) | ((u64)cnt[g].episode << 28) | ((u64)played << 22);
+            const u32 items = nlegal * samples;
+            for (u32 i = lane; i < items; i += L) {
+                u32 j = i / samples, k = i - j * samples;
+                u32 c = kth_bit(legal, j);
+                u64 pkey = game_key(pseed, offset + (u64)g, ebase | ((u64)c << 16) | (u64)k);
+                Game h;
+                unpack(h, a.x, a.y, b.x, b.y);
+                u64 scores = 0;
+                u32 ti, q = played + 1;
+                int fin = apply_step<true>(h, c, scores, ti, false);
+                // the rest of the trick the position stands in: its place in the trick is a run-time value
+                while (!fin && h.nt != 0) {
+                    u32 card = policy_action(pkey, q, legal_now(h));
+                    fin = apply_step<true>(h, card, scores, ti, false);
+                    q++;
+                }
+                // whole tricks from the boundary on: the place in the trick is a compile-time constant (k_rollout)
+                auto one = [&](auto nt_tag) __attribute__((always_inline)) {
+                    h.nt = (u32)decltype(nt_tag)::value;
+                    u32 card = policy_action(pkey, q, legal_now(h));
+                    q++;
+                    return apply_step<true>(h, card, scores, ti, false);
+                };
+                while (!fin) {
+                    one(std::integral_constant<int, 0>{});
+                    one(std::integral_constant<int, 1>{});
+                    one(std::integral_constant<int, 2>{});
+                    fin = one(std::integral_constant<int, 3>{});
+                }
+                atomicAdd(row + j * 4 + 0, (int)(int16_t)scores);
+                atomicAdd(row + j * 4 + 1, (int)(int16_t)(scores >> 16));
+                atomicAdd(row + j * 4 + 2, (int)(int16_t)(scores >> 32));
+                atomicAdd(row + j * 4 + 3, (int)(int16_t)(scores >> 48));
+            }
+        }
+    }
+    __syncthreads();
+    if (g >= n) return;
+    if (sum_out)
+        for (u32 r = lane; r < TAROK_PLAYOUT_RANKS; r += L) sum_out[g * TAROK_PLAYOUT_RANKS + r] = reinterpret_cast<const int4 *>(row)[r];
+    if (action_out && lane == 0) {
+        u32 act = 255;
+        if (takes_part) {                            // the smallest rank at the maximum of the mover's sums
+            u32 best = 0;
+            int top = row[mover];
+            for (u32 j = 1; j < nlegal; j++) {
+                int v = row[j * 4 + mover];
+                if (v > top) { top = v; best = j; }
+            }
+            act = kth_bit(legal, best);
+        } else if (in_play) {
+            act = policy_action(gkey[g], played, legal);
+        }
+        action_out[g] = (uint8_t)act;
+    }
+}
+
 // Observation features for the seat to move, 256 x bf16 per game (0.0 / 1.0), for a policy
 // network (the feature set is the build's own: the reference's encoder belongs
 // to its LSTM agent, Igralec.py:453-543).  Four 64-wide regions, each a 54-bit card set followed
@@ -2986,6 +3082,21 @@ int tarok_rollout_random(tarok_env *e, uint32_t episode, int16_t *scores_out, in
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_rollout, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset,
                        episode, e->mix, scores_out, nsteps_out, seats_out, (u64 *)masks_out, actions_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int tarok_playout_cards(tarok_env *e, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game, int32_t *sum_out,
+                        uint8_t *action_out, void *stream) {
+    if (!e || samples < 1 || samples > TAROK_PLAYOUT_MAX_SAMPLES || seats < 0 || seats > 15 || (!sum_out && !action_out)) return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    // lanes per game: a power of two near four per sample (a mover has 1..12 legal cards, followers few), 4 .. 256
+    u32 lg = TK_PO_MIN_LG;
+    while (lg < TK_PO_MAX_LG && (1 << lg) < 4 * samples) lg++;
+    int64_t teams = TK_BLOCK >> lg;
+    hipLaunchKernelGGL(k_playout, dim3((unsigned)((e->n + teams - 1) / teams)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
+                       e->seed ^ (u64)salt, e->offset, (u32)samples, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, e->gkey,
+                       reinterpret_cast<int4 *>(sum_out), action_out);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }

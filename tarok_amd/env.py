@@ -53,6 +53,21 @@ class Obs:
         return _u64(self.mask)
 
 
+def playout_values(sum, words, samples):
+    """TarokVecEnv.playout_cards' sums as per-card values: [N,54] float32, for every legal card of the seat to move (the
+    legal mask and seat of the observation words `words` [N] int64 the playouts started from) the mean final score of
+    that seat over the `samples` open-hand playouts, -inf elsewhere.  Rank j of `sum` [N,12,4] is the j-th lowest legal
+    card.  Pure torch, on whatever device the inputs are; the values inherit the playouts' perfect information."""
+    cards = torch.arange(54, device=words.device, dtype=torch.int64)
+    legal = ((words.to(torch.int64).unsqueeze(1) >> cards) & 1).bool()                  # [N,54]
+    rank = (torch.cumsum(legal.to(torch.int64), dim=1) - 1).clamp_(0, K.PLAYOUT_RANKS - 1)
+    seat = ((words.to(torch.int64) >> K.OBS_SEAT_SHIFT) & 3).view(-1, 1, 1).expand(-1, K.PLAYOUT_RANKS, 1)
+    # the correctly rounded float32 quotient on every device: a float32 division by a scalar may be carried out as a
+    # multiplication by its reciprocal, which is an ulp off for some sums; in float64 either way rounds to the same float32
+    own = (torch.gather(sum, 2, seat).squeeze(2).to(torch.float64) / float(samples)).to(torch.float32)      # [N,12]
+    return torch.where(legal, torch.gather(own, 1, rank), torch.full((), float("-inf"), device=words.device))
+
+
 class TarokVecEnv:
     def __init__(self, n_games, device=0, seed=0, mix=K.MIX_ALL, game_offset=0, history=False, refill_fan=None, lazy_refill=None):
         """refill_fan, lazy_refill: launch tuning (tarok_set_option; None = the library's default for the batch size);
@@ -292,6 +307,24 @@ class TarokVecEnv:
                                                       self._p(out.get("seats")), self._p(out.get("masks")),
                                                       self._p(out.get("actions")), self._stream()))
         return out
+
+    def playout_cards(self, samples, salt=0, seats=15, seats_per_game=None, sum_out=None, action_out=None):
+        """Open-hand Monte-Carlo value of every legal card of the seat to move (tarok_playout_cards): each legal card is
+        played and the game finished `samples` times by the Bot, from the env's current positions.  The playouts see the
+        TRUE hidden hands (perfect information): an upper-side yardstick and a teacher signal, not a fair player.
+        Returns (sum [N,12,4] int32 — row j: the four final scores summed over the playouts of the j-th lowest legal card,
+        zero rows beyond the legal cards and for games that do not take part — and action [N] uint8: the first card at
+        the maximum of the mover's sums, the Bot's card where the mover is outside `seats` / `seats_per_game` (as in
+        policy_step), 255 where nothing is to be played).  Read-only on the env; `salt` varies the playouts' draws."""
+        with torch.cuda.device(self.device):
+            if sum_out is None:
+                sum_out = torch.empty((self.n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=self.device)
+            if action_out is None:
+                action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
+            _native.check(self.L.tarok_playout_cards(self._h, int(samples), int(salt) & ((1 << 64) - 1), int(seats),
+                                                     self._p(self._seat_sets(seats_per_game)), self._p(sum_out),
+                                                     self._p(action_out), self._stream()))
+        return sum_out, action_out
 
     def observe(self, out=None):
         """[N,256] bf16 features of the seat to move (include/tarok_env.h tarok_observe)."""

@@ -118,3 +118,41 @@ def evaluate_vs_policy(weights, opponent, n_games, episodes, seed=0, mix=K.MIX_B
         TarokVecEnv.check_mlp_weights(ws)
     return duplicate_advantage(_play_passes_mode(weights, n_games, episodes, seed, mix, device, opponent=opponent,
                                                  temperature=temperature, epsilon=epsilon))
+
+
+def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None):
+    """_play_passes_mode with the open-hand Monte-Carlo player (TarokVecEnv.playout_cards) in the network's place: per
+    lock-step one tarok_playout_cards launch with the pass's seat set, whose action_out holds the playout player's card
+    on its seats and the Bot's on the others, and one tarok_step that plays it.  inspect: as in _play_passes_mode."""
+    n = int(n_games)
+    scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
+    env = TarokVecEnv(n, device=device, seed=seed, mix=mix)
+    try:
+        with torch.cuda.device(env.device):
+            actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
+            sums = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=env.device)
+        for e in range(int(episodes)):
+            for p, seats in enumerate(PASS_SEATS):
+                env.reset(episode=e, clear_counters=True)
+                start = env.state() if inspect is not None else None
+                for t in range(GAME_CARDS):
+                    env.playout_cards(samples, salt=salt, seats=seats, sum_out=sums, action_out=actions[t])
+                    env.step(actions[t], auto_reset=False)
+                _, ss = env.counters()                # (the pass's one synchronisation)
+                scores[p, e * n:(e + 1) * n] = ss
+                if inspect is not None:
+                    inspect.append(dict(episode=e, seats=seats, start=start, actions=actions.cpu().numpy(), scores=ss.copy()))
+    finally:
+        env.close()
+    return scores
+
+
+def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None):
+    """evaluate_vs_bot with the open-hand Monte-Carlo player in the network's place: a strong reference player that needs
+    no training.  On its seat it plays, at every move, the legal card with the best summed score over `samples` Bot
+    playouts of each legal card (tarok_playout_cards; `salt` varies their draws).  The playouts see the TRUE hidden
+    hands — perfect information — so the figure is an upper-side yardstick for a policy's own evaluate_vs_bot figure on
+    the same deals (same seed, mix and sizes), not the strength of a fair player.
+    The same five duplicate passes (PASS_SEATS) on an env of its own; returns duplicate_advantage's dict, `policy_mean`
+    being the playout player's.  inspect (tests): a list that receives one dict per pass, as in _play_passes_mode."""
+    return duplicate_advantage(_playout_passes(samples, n_games, episodes, seed, mix, device, salt=salt, inspect=inspect))

@@ -65,6 +65,10 @@ DRAW_POLICY = 128         # the Bot's uniform legal card (tarok_step_random, tar
 DRAW_SAMPLE = 192         # the learned policy's inverse-CDF draw (tarok_sample_policy and the fused launches)
 DRAW_EXPLORE = 256        # the exploration coin of a play mode with epsilon > 0 (tarok_set_play_mode)
 
+# tarok_playout_cards (include/tarok_env.h TAROK_PLAYOUT_*)
+PLAYOUT_RANKS = 12        # rows of sum_out per game: a hand in play never holds more than 12 cards
+PLAYOUT_MAX_SAMPLES = 1024
+
 # observation word
 OBS_MASK = DECK
 OBS_SEAT_SHIFT = 54

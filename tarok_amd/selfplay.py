@@ -378,7 +378,8 @@ class SelfPlay:
             dst.copy_(src)
 
     @torch.no_grad()
-    def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None, greedy=False, temperature=None, epsilon=0.0):
+    def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None, greedy=False, temperature=None, epsilon=0.0,
+                 versus_playout=None):
         """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
         weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
         and on the SAME deals on every rank (seed 0, game offset 0, whatever the training env's are): the figures of
@@ -388,7 +389,12 @@ class SelfPlay:
         is then the opponent's mean), on the same deals.
         greedy=True plays the network's best card (temperature 0) instead of a draw from its softmax, temperature a
         tempered draw, epsilon the Bot's card with that probability (TarokVecEnv.set_play_mode, on the evaluation's env
-        only: the rollout keeps sampling at (1, 0))."""
+        only: the rollout keeps sampling at (1, 0)).
+        versus_playout=samples: returns TWO dicts, (the policy's advantage over the Bot, the open-hand Monte-Carlo
+        player's over the Bot on the same deals: evaluate.evaluate_playout_vs_bot with `samples` playouts per card).  The
+        playout player sees the true hidden hands, so its figure is an upper-side yardstick, not a fair player's."""
+        if versus_playout is not None and opponent is not None:
+            raise ValueError("versus_playout compares against the Bot: give it without opponent=")
         if greedy and temperature:
             raise ValueError("greedy=True is temperature 0: give one of the two")
         temperature = 0.0 if greedy else (1.0 if temperature is None else float(temperature))
@@ -400,8 +406,12 @@ class SelfPlay:
         if opponent is not None:
             return evaluate_vs_policy(self._w, opponent, n_games, episodes, mix=mix, device=self.env.device_index,
                                       temperature=temperature, epsilon=epsilon)
-        return evaluate_vs_bot(self._w, n_games, episodes, mix=mix, device=self.env.device_index, temperature=temperature,
-                               epsilon=epsilon)
+        own = evaluate_vs_bot(self._w, n_games, episodes, mix=mix, device=self.env.device_index, temperature=temperature,
+                              epsilon=epsilon)
+        if versus_playout is None:
+            return own
+        from .evaluate import evaluate_playout_vs_bot
+        return own, evaluate_playout_vs_bot(int(versus_playout), n_games, episodes, mix=mix, device=self.env.device_index)
 
     def _alloc(self, T):
         n, dev = self.env.n, self.device
