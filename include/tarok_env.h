@@ -242,6 +242,44 @@ int tarok_rollout_random(tarok_env *env, uint32_t episode, int16_t *scores_out, 
 int tarok_playout_cards(tarok_env *env, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
                         int32_t *sum_out, uint8_t *action_out, void *stream);
 
+/* Determinized Monte-Carlo playouts (perfect-information Monte-Carlo over sampled worlds): tarok_playout_cards for a
+ * FAIR player.  The playouts of world w run on a uniform re-deal of the cards the seat to move cannot see, so the result
+ * is a function of that seat's information set alone: its own hand, the table, the four won piles, the talon ids and
+ * `tl`, the contract, the declarer and the called suit.  Terms (s, legal, played, ep, gidx, "takes part", rank j, card
+ * c) as above.
+ *
+ * Unseen pool: P = the union of the hands of the three other seats (the cards with C = 0 that s does not hold).
+ * Everything else is the same in every world, and with it the mover's legal cards and their ranks.
+ * World w < worlds, under the world key
+ *     wkey = game_key(seed ^ salt, gidx, W),   W = 7 << 61 | (u64)ep << 28 | played << 22 | w:
+ * let o0 < o1 < o2 be the other seats in seat order and cap_i the size of o_i's true hand.  The cards of P are walked in
+ * ascending card number; the i-th card of the walk (i from 0) draws r = pick(rng32(wkey, i), cap0 + cap1 + cap2) on the
+ * capacities as they stand at that moment and goes to o0 if r < cap0, to o1 if r < cap0 + cap1, to o2 otherwise; the
+ * capacity of the seat that receives it drops by one.  This is uniform over all deals that keep the hand sizes.
+ * Team: when the contract has a called king (Tri, Dve, Ena) and the king card 8 * king + 7 lies in P, nobody at s's seat
+ * knows the partner, and the world's team is 1 << declarer | 1 << (the seat that received the king).  In every other
+ * case — the king in s's hand, played, in the talon, or a contract without one — the team stays.
+ * Playouts: in world w, for rank j (card c) and sample k < samples: play c, then the Bot's cards to the end exactly as
+ * tarok_playout_cards does (draw 128 + q) under
+ *     pkey = game_key(seed ^ salt, gidx, D),   D = 3 << 62 | (u64)ep << 28 | played << 22 | c << 16 | w << 10 | k,
+ * and add the four final scores to sum_out[g][j][0..3], taken over all worlds x samples: sum[j][s] / (worlds * samples)
+ * is the card's mean score for the mover.  Bits 62 and 61 keep both keys apart from E (bit 63 alone) and from every
+ * deal.  World w and sample k depend on neither `worlds` nor `samples`: a launch at (W', S') sums a subset of the
+ * playouts of a launch at (W >= W', S >= S').
+ * sum_out, action_out, seats / seats_per_game, the games that do not take part and the read-only contract: as for
+ * tarok_playout_cards.
+ *
+ * Known leaks (information the re-deal does not use, or uses though the seat could not have it):
+ *   - a void that another seat has shown by not following suit does not constrain the re-deal;
+ *   - Klop's face-down talon keeps its true cards in every world;
+ *   - the declarer's discards lie in the declarer's pile and so count as seen.
+ * TAROK_EINVAL (before any HIP call) for a NULL env, worlds outside 1..TAROK_PLAYOUT_MAX_WORLDS, samples outside
+ * 1..TAROK_PLAYOUT_MAX_SAMPLES, seats outside 0..15 or both outputs NULL.  (65,536 playouts of |int16| scores fit the
+ * int32 sums.) */
+#define TAROK_PLAYOUT_MAX_WORLDS 64
+int tarok_playout_cards_det(tarok_env *env, int worlds, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                            int32_t *sum_out, uint8_t *action_out, void *stream);
+
 /* Observation features of the seat to move for a policy network: features_out [N,256] bf16,
  * every entry 0.0 or 1.0 (feature set documented at k_observe — the build's own,
  * the reference's encoder is part of its LSTM agent, Igralec.py:453-543):

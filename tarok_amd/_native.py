@@ -29,7 +29,7 @@ SYMBOLS = [
     "tarok_targets_ref", "tarok_learn_returns", "tarok_learn_returns_gae", "tarok_learn_returns_seats", "tarok_learn_select_scratch_bytes", "tarok_learn_select",
     "tarok_learn_chain", "tarok_learn_workspace_bytes", "tarok_learn_dw", "tarok_learn_adam",
     "tarok_observe_ref", "tarok_observe_exchange_ref", "tarok_observe_hands_ref", "tarok_get_history", "tarok_set_history",
-    "tarok_set_play_mode", "tarok_get_play_mode", "tarok_playout_cards",
+    "tarok_set_play_mode", "tarok_get_play_mode", "tarok_playout_cards", "tarok_playout_cards_det",
 ]
 
 
@@ -165,6 +165,7 @@ def lib():
     L.tarok_set_play_mode.restype = i32; L.tarok_set_play_mode.argtypes = [vp, f32, f32]
     L.tarok_get_play_mode.restype = i32; L.tarok_get_play_mode.argtypes = [vp, C.POINTER(f32), C.POINTER(f32)]
     L.tarok_playout_cards.restype = i32; L.tarok_playout_cards.argtypes = [vp, i32, u64, i32, vp, vp, vp, vp]
+    L.tarok_playout_cards_det.restype = i32; L.tarok_playout_cards_det.argtypes = [vp, i32, i32, u64, i32, vp, vp, vp, vp]
     L.tarok_debug_stamps.restype = i32; L.tarok_debug_stamps.argtypes = [vp, vp]
     L.tarok_debug_stamps_sized.restype = i32; L.tarok_debug_stamps_sized.argtypes = [vp, vp, i64]
     L.tarok_debug_refill_selftest.restype = i32; L.tarok_debug_refill_selftest.argtypes = [vp, i32, i32, u32, i32, i32, vp]

@@ -566,6 +566,48 @@ __device__ __forceinline__ u32 policy_action_follow(u64 key, RngCtr c, u32 w, u3
     return kth_bit_word(w, hi_sel, pick(rng32(key, c), (u32)__popc(w)));
 }
 
+// Determinization (tarok_playout_cards_det, include/tarok_env.h): one WORLD of the seat `mover` — the cards it cannot
+// see, P = the hands of the three other seats, are dealt afresh among those seats, uniformly over the deals that keep
+// the hand sizes.  The cards of P are walked in ascending card number; card i of the walk draws
+// r = pick(rng32(wkey, i), cap0 + cap1 + cap2) on the capacities left at that moment and goes to the other seat
+// o0 < o1 < o2 whose interval [0, cap0) / [cap0, cap0 + cap1) / the rest r falls into.  Only the A/B planes of P change:
+// the mover's hand, the table, the won piles, the talon ids and tl, the contract, the declarer and the called suit stay.
+// TEAM: with a called king that lies in P the mover's seat does not know the partner, so the world's team is the
+// declarer and whoever received the king; otherwise (king in the mover's hand, played, in the talon, or a contract
+// without one) it stays.  A new team moves the un-owned talon cards, which setup_game parked in the pile bits of the
+// lowest seat outside the team and score_game counts there, to the lowest seat outside the NEW team.
+// Selects only: the one loop runs popcount(P) <= 36 times, the same count on every lane that deals a world of one game.
+__device__ __forceinline__ void redeal_unseen(Game &g, u32 mover, u64 wkey) {
+    const u32 o0 = mover == 0 ? 1u : 0u, o1 = mover <= 1 ? 2u : 1u, o2 = mover == 3 ? 2u : 3u;
+    const u64 h0 = hand_of(g, o0), h1 = hand_of(g, o1), h2 = hand_of(g, o2);
+    const u64 P = h0 | h1 | h2;
+    u32 cap0 = (u32)popc64(h0), cap1 = (u32)popc64(h1), total = (u32)popc64(P);
+    u64 m0 = 0, m1 = 0, rest = P;
+    const u32 klo = (u32)wkey, khi = (u32)(wkey >> 32), n = total;
+    for (u32 i = 0; i < n; i++) {
+        u64 bit = rest & (0ULL - rest);
+        u32 r = pick(rng32(klo, khi, i), total);
+        u32 t0 = r < cap0 ? 1u : 0u, t1 = (r >= cap0 && r < cap0 + cap1) ? 1u : 0u;
+        m0 |= t0 ? bit : 0ULL;
+        m1 |= t1 ? bit : 0ULL;
+        cap0 -= t0; cap1 -= t1; total--;
+        rest ^= bit;
+    }
+    const u64 m2 = P & ~(m0 | m1);
+    u64 sa = ((o0 & 1) ? m0 : 0ULL) | ((o1 & 1) ? m1 : 0ULL) | ((o2 & 1) ? m2 : 0ULL);
+    u64 sb = ((o0 & 2) ? m0 : 0ULL) | ((o1 & 2) ? m1 : 0ULL) | ((o2 & 2) ? m2 : 0ULL);
+    u64 A = (g.A & ~P) | sa, B = (g.B & ~P) | sb;
+    const u64 kb = 1ULL << (g.king * 8 + 7);
+    const bool hidden = has_king(g.contract) && (P & kb) != 0;           // the partner is not known at the mover's seat
+    const u32 got = (m0 & kb) ? o0 : ((m1 & kb) ? o1 : o2);
+    const u32 team = hidden ? ((1u << g.declarer) | (1u << got)) : g.team;
+    const u64 un = hidden ? talon_unowned(g) : 0ULL;                     // (a team of a called king: one or two seats)
+    const u32 park = (u32)__builtin_ctz((~team & 15u) | 16u);
+    g.A = (A & ~un) | ((park & 1) ? un : 0ULL);
+    g.B = (B & ~un) | ((park & 2) ? un : 0ULL);
+    g.team = team;
+}
+
 // One bidding round between four Bot players (TAROK_MIX_BOT): the control flow of
 // Igra.licitacija (Igra.py:75-114) with Bot_igralec.licitiram (Igralec.py:148-152)
 // behind the player-side filter (Igralec.py:58-74).  Bids are int(Tip_igre)

@@ -1312,6 +1312,34 @@ TK_KERNEL(TK_BLOCK, 96) void k_rollout(int64_t n, u64 seed, u64 offset, u32 epis
     if (nsteps_out) nsteps_out[i] = (int16_t)played;
 }
 
+// One playout, shared by k_playout and k_playout_det: card c on the position h (`played` cards into its game), then the
+// Bot's cards to the end under pkey (draw 128 + q at q cards played).  Returns the four final scores, packed.
+__device__ __forceinline__ u64 playout_from(Game &h, u32 c, u64 pkey, u32 played) {
+    u64 scores = 0;
+    u32 ti, q = played + 1;
+    int fin = apply_step<true>(h, c, scores, ti, false);
+    // the rest of the trick the position stands in: its place in the trick is a run-time value
+    while (!fin && h.nt != 0) {
+        u32 card = policy_action(pkey, q, legal_now(h));
+        fin = apply_step<true>(h, card, scores, ti, false);
+        q++;
+    }
+    // whole tricks from the boundary on: the place in the trick is a compile-time constant (k_rollout)
+    auto one = [&](auto nt_tag) __attribute__((always_inline)) {
+        h.nt = (u32)decltype(nt_tag)::value;
+        u32 card = policy_action(pkey, q, legal_now(h));
+        q++;
+        return apply_step<true>(h, card, scores, ti, false);
+    };
+    while (!fin) {
+        one(std::integral_constant<int, 0>{});
+        one(std::integral_constant<int, 1>{});
+        one(std::integral_constant<int, 2>{});
+        fin = one(std::integral_constant<int, 3>{});
+    }
+    return scores;
+}
+
 // tarok_playout_cards: open-hand Monte-Carlo playouts from the env's CURRENT positions (the true hidden hands: perfect
 // information, not a fair player).  Read-only on the env.  A team of 2^lg lanes (4 .. 256, the host picks it from
 // `samples`) owns one game; the game's work items (rank j of a legal card, sample k), nlegal * samples of them, are dealt
@@ -1358,33 +1386,98 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout(int64_t n, u64 pseed /* seed ^ salt */, 
                 u64 pkey = game_key(pseed, offset + (u64)g, ebase | ((u64)c << 16) | (u64)k);
                 Game h;
                 unpack(h, a.x, a.y, b.x, b.y);
-                u64 scores = 0;
-                u32 ti, q = played + 1;
-                int fin = apply_step<true>(h, c, scores, ti, false);
-                // the rest of the trick the position stands in: its place in the trick is a run-time value
-                while (!fin && h.nt != 0) {
-                    u32 card = policy_action(pkey, q, legal_now(h));
-                    fin = apply_step<true>(h, card, scores, ti, false);
-                    q++;
-                }
-                // whole tricks from the boundary on: the place in the trick is a compile-time constant (k_rollout)
-                auto one = [&](auto nt_tag) __attribute__((always_inline)) {
-                    h.nt = (u32)decltype(nt_tag)::value;
-                    u32 card = policy_action(pkey, q, legal_now(h));
-                    q++;
-                    return apply_step<true>(h, card, scores, ti, false);
-                };
-                while (!fin) {
-                    one(std::integral_constant<int, 0>{});
-                    one(std::integral_constant<int, 1>{});
-                    one(std::integral_constant<int, 2>{});
-                    fin = one(std::integral_constant<int, 3>{});
-                }
+                u64 scores = playout_from(h, c, pkey, played);
                 atomicAdd(row + j * 4 + 0, (int)(int16_t)scores);
                 atomicAdd(row + j * 4 + 1, (int)(int16_t)(scores >> 16));
                 atomicAdd(row + j * 4 + 2, (int)(int16_t)(scores >> 32));
                 atomicAdd(row + j * 4 + 3, (int)(int16_t)(scores >> 48));
             }
+        }
+    }
+    __syncthreads();
+    if (g >= n) return;
+    if (sum_out)
+        for (u32 r = lane; r < TAROK_PLAYOUT_RANKS; r += L) sum_out[g * TAROK_PLAYOUT_RANKS + r] = reinterpret_cast<const int4 *>(row)[r];
+    if (action_out && lane == 0) {
+        u32 act = 255;
+        if (takes_part) {                            // the smallest rank at the maximum of the mover's sums
+            u32 best = 0;
+            int top = row[mover];
+            for (u32 j = 1; j < nlegal; j++) {
+                int v = row[j * 4 + mover];
+                if (v > top) { top = v; best = j; }
+            }
+            act = kth_bit(legal, best);
+        } else if (in_play) {
+            act = policy_action(gkey[g], played, legal);
+        }
+        action_out[g] = (uint8_t)act;
+    }
+}
+
+// tarok_playout_cards_det: determinized playouts — k_playout's sibling for a FAIR player.  The playouts of world w run on
+// a re-deal of the cards the mover cannot see (redeal_unseen under the world key), so the result is a function of the
+// mover's information set alone.  A team of 2^lg lanes owns one game (lg from worlds * samples by k_playout's rule, so
+// teams * worlds <= TK_PO_WORLD_SLOTS).  A world is dealt ONCE: lanes w = lane, lane + L, ... of the team each deal one
+// world and leave its (A plane, B plane, team) in LDS, 20 bytes; after one barrier the work items (rank j, world w,
+// sample k), nlegal * worlds * samples of them, go round-robin over the team: each builds its candidate game from the
+// position's packed words and its world's planes and runs playout_from.  Sums, rows and the card are k_playout's.
+// Nothing of the env is written; no global atomics.
+#define TK_PO_WORLD_SLOTS 64
+TK_KERNEL(TK_BLOCK, 128) void k_playout_det(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 samples, u32 lg,
+                                           u32 seats, const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                           const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                           const u64 *__restrict__ gkey, int4 *__restrict__ sum_out, uint8_t *__restrict__ action_out) {
+    TK_VGPR_TOP(128, 127);
+    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> TK_PO_MIN_LG) * TAROK_PLAYOUT_RANKS * 4];
+    __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS];
+    __shared__ u32 world_team[TK_PO_WORLD_SLOTS];
+    const u32 tid = threadIdx.x, team = tid >> lg, L = 1u << lg, lane = tid & (L - 1u), teams = (u32)TK_BLOCK >> lg;
+    const int64_t g = (int64_t)blockIdx.x * teams + team;
+    for (u32 w = tid; w < teams * (TAROK_PLAYOUT_RANKS * 4); w += TK_BLOCK) sums[w] = 0;
+    int *row = sums + team * (TAROK_PLAYOUT_RANKS * 4);
+    const u32 slot0 = team * worlds;                 // the team's worlds: slots slot0 .. slot0 + worlds - 1
+    ulonglong2 a = {0, 0}, b = {0, 0};
+    u64 legal = 0, ebase = 0;
+    u32 mover = 0, played = 0, nlegal = 0;
+    bool in_play = false, takes_part = false;
+    if (g < n) {
+        a = s01[g]; b = s23[g];
+        Game g0;
+        unpack(g0, a.x, a.y, b.x, b.y);
+        in_play = g0.phase == TK_PHASE_PLAY;
+        if (in_play) {
+            legal = legal_now(g0);
+            mover = (g0.leader + g0.nt) & 3;
+            played = g0.trick_no * 4 + g0.nt;
+            u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+            takes_part = (set >> mover) & 1u;
+        }
+        if (takes_part) {
+            nlegal = (u32)popc64(legal);
+            ebase = ((u64)cnt[g].episode << 28) | ((u64)played << 22);
+            for (u32 w = lane; w < worlds; w += L) {
+                Game d = g0;
+                redeal_unseen(d, mover, game_key(pseed, offset + (u64)g, (7ULL << 61) | ebase | (u64)w));
+                world_a[slot0 + w] = d.A; world_b[slot0 + w] = d.B; world_team[slot0 + w] = d.team;
+            }
+        }
+    }
+    __syncthreads();
+    if (takes_part) {
+        const u32 per_card = worlds * samples, items = nlegal * per_card;
+        for (u32 i = lane; i < items; i += L) {
+            u32 j = i / per_card, rem = i - j * per_card, w = rem / samples, k = rem - w * samples;
+            u32 c = kth_bit(legal, j);
+            u64 pkey = game_key(pseed, offset + (u64)g, (3ULL << 62) | ebase | ((u64)c << 16) | ((u64)w << 10) | (u64)k);
+            Game h;
+            unpack(h, a.x, a.y, b.x, b.y);
+            h.A = world_a[slot0 + w]; h.B = world_b[slot0 + w]; h.team = world_team[slot0 + w];
+            u64 scores = playout_from(h, c, pkey, played);
+            atomicAdd(row + j * 4 + 0, (int)(int16_t)scores);
+            atomicAdd(row + j * 4 + 1, (int)(int16_t)(scores >> 16));
+            atomicAdd(row + j * 4 + 2, (int)(int16_t)(scores >> 32));
+            atomicAdd(row + j * 4 + 3, (int)(int16_t)(scores >> 48));
         }
     }
     __syncthreads();
@@ -3097,6 +3190,25 @@ int tarok_playout_cards(tarok_env *e, int samples, uint64_t salt, int seats, con
     hipLaunchKernelGGL(k_playout, dim3((unsigned)((e->n + teams - 1) / teams)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
                        e->seed ^ (u64)salt, e->offset, (u32)samples, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, e->gkey,
                        reinterpret_cast<int4 *>(sum_out), action_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int tarok_playout_cards_det(tarok_env *e, int worlds, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                            int32_t *sum_out, uint8_t *action_out, void *stream) {
+    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || samples < 1 || samples > TAROK_PLAYOUT_MAX_SAMPLES || seats < 0 ||
+        seats > 15 || (!sum_out && !action_out))
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    // lanes per game: tarok_playout_cards' rule on worlds * samples playouts per card; 4 * worlds <= lanes, so the worlds
+    // of a workgroup's teams fit its TK_PO_WORLD_SLOTS slots
+    static_assert(TAROK_PLAYOUT_MAX_WORLDS * 4 <= TK_BLOCK && TK_PO_WORLD_SLOTS * 4 == TK_BLOCK, "teams * worlds <= TK_PO_WORLD_SLOTS");
+    u32 lg = TK_PO_MIN_LG;
+    while (lg < TK_PO_MAX_LG && (1 << lg) < 4 * worlds * samples) lg++;
+    int64_t teams = TK_BLOCK >> lg;
+    hipLaunchKernelGGL(k_playout_det, dim3((unsigned)((e->n + teams - 1) / teams)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
+                       e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)samples, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt,
+                       e->gkey, reinterpret_cast<int4 *>(sum_out), action_out);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }

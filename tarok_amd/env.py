@@ -57,7 +57,9 @@ def playout_values(sum, words, samples):
     """TarokVecEnv.playout_cards' sums as per-card values: [N,54] float32, for every legal card of the seat to move (the
     legal mask and seat of the observation words `words` [N] int64 the playouts started from) the mean final score of
     that seat over the `samples` open-hand playouts, -inf elsewhere.  Rank j of `sum` [N,12,4] is the j-th lowest legal
-    card.  Pure torch, on whatever device the inputs are; the values inherit the playouts' perfect information."""
+    card.  Pure torch, on whatever device the inputs are; the values inherit the playouts' perfect information.
+    `samples` is the divisor, the number of playouts per card: for the sums of a determinized launch
+    (playout_cards_det) pass worlds * samples; those values use the mover's own information only."""
     cards = torch.arange(54, device=words.device, dtype=torch.int64)
     legal = ((words.to(torch.int64).unsqueeze(1) >> cards) & 1).bool()                  # [N,54]
     rank = (torch.cumsum(legal.to(torch.int64), dim=1) - 1).clamp_(0, K.PLAYOUT_RANKS - 1)
@@ -312,6 +314,7 @@ class TarokVecEnv:
         """Open-hand Monte-Carlo value of every legal card of the seat to move (tarok_playout_cards): each legal card is
         played and the game finished `samples` times by the Bot, from the env's current positions.  The playouts see the
         TRUE hidden hands (perfect information): an upper-side yardstick and a teacher signal, not a fair player.
+        The fair sibling is playout_cards_det.
         Returns (sum [N,12,4] int32 — row j: the four final scores summed over the playouts of the j-th lowest legal card,
         zero rows beyond the legal cards and for games that do not take part — and action [N] uint8: the first card at
         the maximum of the mover's sums, the Bot's card where the mover is outside `seats` / `seats_per_game` (as in
@@ -324,6 +327,24 @@ class TarokVecEnv:
             _native.check(self.L.tarok_playout_cards(self._h, int(samples), int(salt) & ((1 << 64) - 1), int(seats),
                                                      self._p(self._seat_sets(seats_per_game)), self._p(sum_out),
                                                      self._p(action_out), self._stream()))
+        return sum_out, action_out
+
+    def playout_cards_det(self, worlds, samples, salt=0, seats=15, seats_per_game=None, sum_out=None, action_out=None):
+        """Determinized Monte-Carlo value of every legal card of the seat to move (tarok_playout_cards_det): the FAIR
+        sibling of playout_cards.  The cards the mover cannot see are re-dealt `worlds` times (1..64) among the other
+        seats, hand sizes kept, and every legal card is played out `samples` times by the Bot in every world, so the sums
+        are over worlds * samples playouts (playout_values' divisor) and depend on the mover's information set alone:
+        its hand, the table, the won piles, the talon ids, the contract, the declarer and the called suit.  Where a
+        called king is among the unseen cards the world's team is the declarer and whoever was dealt it.
+        Outputs, `seats` / `seats_per_game`, `salt` and the read-only contract: as for playout_cards."""
+        with torch.cuda.device(self.device):
+            if sum_out is None:
+                sum_out = torch.empty((self.n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=self.device)
+            if action_out is None:
+                action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
+            _native.check(self.L.tarok_playout_cards_det(self._h, int(worlds), int(samples), int(salt) & ((1 << 64) - 1),
+                                                         int(seats), self._p(self._seat_sets(seats_per_game)),
+                                                         self._p(sum_out), self._p(action_out), self._stream()))
         return sum_out, action_out
 
     def observe(self, out=None):

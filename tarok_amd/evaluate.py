@@ -120,10 +120,12 @@ def evaluate_vs_policy(weights, opponent, n_games, episodes, seed=0, mix=K.MIX_B
                                                  temperature=temperature, epsilon=epsilon))
 
 
-def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None):
-    """_play_passes_mode with the open-hand Monte-Carlo player (TarokVecEnv.playout_cards) in the network's place: per
-    lock-step one tarok_playout_cards launch with the pass's seat set, whose action_out holds the playout player's card
-    on its seats and the Bot's on the others, and one tarok_step that plays it.  inspect: as in _play_passes_mode."""
+def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None):
+    """_play_passes_mode with the Monte-Carlo player (TarokVecEnv.playout_cards) in the network's place: per lock-step
+    one playout launch with the pass's seat set — tarok_playout_cards (open hands) for worlds=None,
+    tarok_playout_cards_det (the fair player: `worlds` re-deals of the unseen cards) otherwise — whose action_out holds
+    the playout player's card on its seats and the Bot's on the others, and one tarok_step that plays it.
+    inspect: as in _play_passes_mode."""
     n = int(n_games)
     scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
     env = TarokVecEnv(n, device=device, seed=seed, mix=mix)
@@ -136,7 +138,10 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
                 env.reset(episode=e, clear_counters=True)
                 start = env.state() if inspect is not None else None
                 for t in range(GAME_CARDS):
-                    env.playout_cards(samples, salt=salt, seats=seats, sum_out=sums, action_out=actions[t])
+                    if worlds is None:
+                        env.playout_cards(samples, salt=salt, seats=seats, sum_out=sums, action_out=actions[t])
+                    else:
+                        env.playout_cards_det(worlds, samples, salt=salt, seats=seats, sum_out=sums, action_out=actions[t])
                     env.step(actions[t], auto_reset=False)
                 _, ss = env.counters()                # (the pass's one synchronisation)
                 scores[p, e * n:(e + 1) * n] = ss
@@ -147,12 +152,16 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     return scores
 
 
-def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None):
+def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None):
     """evaluate_vs_bot with the open-hand Monte-Carlo player in the network's place: a strong reference player that needs
     no training.  On its seat it plays, at every move, the legal card with the best summed score over `samples` Bot
     playouts of each legal card (tarok_playout_cards; `salt` varies their draws).  The playouts see the TRUE hidden
     hands — perfect information — so the figure is an upper-side yardstick for a policy's own evaluate_vs_bot figure on
     the same deals (same seed, mix and sizes), not the strength of a fair player.
+    worlds=W is the FAIR player: determinized playouts (tarok_playout_cards_det), W re-deals of the cards its seat cannot
+    see and `samples` playouts of every legal card in each.  It uses only what its seat may know, so it is the honest
+    fixed opponent to hold a learned policy against and a teacher the network could in principle reach.
     The same five duplicate passes (PASS_SEATS) on an env of its own; returns duplicate_advantage's dict, `policy_mean`
     being the playout player's.  inspect (tests): a list that receives one dict per pass, as in _play_passes_mode."""
-    return duplicate_advantage(_playout_passes(samples, n_games, episodes, seed, mix, device, salt=salt, inspect=inspect))
+    return duplicate_advantage(_playout_passes(samples, n_games, episodes, seed, mix, device, salt=salt, inspect=inspect,
+                                               worlds=worlds))

@@ -68,6 +68,7 @@ DRAW_EXPLORE = 256        # the exploration coin of a play mode with epsilon > 0
 # tarok_playout_cards (include/tarok_env.h TAROK_PLAYOUT_*)
 PLAYOUT_RANKS = 12        # rows of sum_out per game: a hand in play never holds more than 12 cards
 PLAYOUT_MAX_SAMPLES = 1024
+PLAYOUT_MAX_WORLDS = 64   # tarok_playout_cards_det: re-deals of the unseen cards per launch
 
 # observation word
 OBS_MASK = DECK

@@ -379,7 +379,7 @@ class SelfPlay:
 
     @torch.no_grad()
     def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None, greedy=False, temperature=None, epsilon=0.0,
-                 versus_playout=None):
+                 versus_playout=None, playout_worlds=None):
         """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
         weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
         and on the SAME deals on every rank (seed 0, game offset 0, whatever the training env's are): the figures of
@@ -392,7 +392,12 @@ class SelfPlay:
         only: the rollout keeps sampling at (1, 0)).
         versus_playout=samples: returns TWO dicts, (the policy's advantage over the Bot, the open-hand Monte-Carlo
         player's over the Bot on the same deals: evaluate.evaluate_playout_vs_bot with `samples` playouts per card).  The
-        playout player sees the true hidden hands, so its figure is an upper-side yardstick, not a fair player's."""
+        playout player sees the true hidden hands, so its figure is an upper-side yardstick, not a fair player's.
+        playout_worlds=W (with versus_playout): the second dict is the determinized player's instead (W re-deals of the
+        cards its seat cannot see, `samples` playouts per card in each).  Of the two, that one is the FAIR player: it uses
+        only its seat's information, so its figure is one a policy can be held against."""
+        if playout_worlds is not None and versus_playout is None:
+            raise ValueError("playout_worlds goes with versus_playout=samples")
         if versus_playout is not None and opponent is not None:
             raise ValueError("versus_playout compares against the Bot: give it without opponent=")
         if greedy and temperature:
@@ -411,7 +416,8 @@ class SelfPlay:
         if versus_playout is None:
             return own
         from .evaluate import evaluate_playout_vs_bot
-        return own, evaluate_playout_vs_bot(int(versus_playout), n_games, episodes, mix=mix, device=self.env.device_index)
+        return own, evaluate_playout_vs_bot(int(versus_playout), n_games, episodes, mix=mix, device=self.env.device_index,
+                                            worlds=playout_worlds)
 
     def _alloc(self, T):
         n, dev = self.env.n, self.device

@@ -9,7 +9,11 @@ exactly 48 cards and the cards a launch plays follow from the positions alone, o
 (each playout plays its candidate card and then the game to its end); tarok_rollout_random plays 48 * games.
 Each figure is the median of `runs` launches, each between two device events, after two untimed ones.
 
-usage: playout_time.py [out.txt = profiles/playout_times.txt] [games = 65536] [samples = 16]"""
+--worlds W adds, at every position and in the same process, the determinized launch tarok_playout_cards_det at
+(W, samples) beside the open-hand launch at W * samples playouts per card — the same number of playouts and of cards —
+and prints the ratio of the two times (default output then: profiles/playout_det_times.txt).
+
+usage: playout_time.py [out.txt = profiles/playout_times.txt] [games = 65536] [samples = 16] [--worlds W]"""
 import json
 import os
 import statistics
@@ -21,9 +25,16 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from tarok_amd import TarokVecEnv, karte as K  # noqa: E402
 
-out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "playout_times.txt")
-n = int(sys.argv[2]) if len(sys.argv) > 2 else 65536
-samples = int(sys.argv[3]) if len(sys.argv) > 3 else 16
+argv = list(sys.argv)
+worlds = None
+if "--worlds" in argv:
+    at = argv.index("--worlds")
+    worlds = int(argv[at + 1])
+    del argv[at:at + 2]
+out_path = argv[1] if len(argv) > 1 else os.path.join(ROOT, "profiles", "playout_det_times.txt" if worlds else "playout_times.txt")
+n = int(argv[2]) if len(argv) > 2 else 65536
+per_world = int(argv[3]) if len(argv) > 3 else (1 if worlds else 16)
+samples = per_world * (worlds or 1)          # playouts per card of both launches
 RUNS = 9
 assert torch.cuda.is_available(), "this tool measures on the GPU"
 
@@ -71,6 +82,11 @@ with torch.cuda.device(env.device):
         lines.append("  %-28s %10.1f us (%.1f, %.1f)   %12d cards   %8.2f G cards/s   %.2f x rollout_random   (%.2f legal cards per game)"
                      % ("playouts after %2d cards" % cards, med, lo, hi, total, rate / 1e9, rate / rate_rollout, legal.mean()))
         result["after_%d" % cards] = dict(us=med, cards=total, cards_per_s=rate, legal_mean=float(legal.mean()))
+        if worlds:
+            dmed, dlo, dhi = timed_us(lambda: env.playout_cards_det(worlds, per_world, sum_out=sums, action_out=acts))
+            lines.append("  %-28s %10.1f us (%.1f, %.1f)   %12d cards   %8.2f G cards/s   %.3f x the open-hand time"
+                         % ("  determinized (%d, %d)" % (worlds, per_world), dmed, dlo, dhi, total, total / (dmed * 1e-6) / 1e9, dmed / med))
+            result["after_%d" % cards].update(det_us=dmed, det_over_open=dmed / med, worlds=worlds, samples_per_world=per_world)
 text = "\n".join(lines) + "\n"
 os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
 with open(out_path, "w") as f:
