@@ -280,6 +280,31 @@ int tarok_playout_cards(tarok_env *env, int samples, uint64_t salt, int seats, c
 int tarok_playout_cards_det(tarok_env *env, int worlds, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
                             int32_t *sum_out, uint8_t *action_out, void *stream);
 
+/* A playout launch's sums as a teacher's target distribution: one row of 64 bf16 per game, for the learner's distillation
+ * term (tarok_learn_chain_distill).  Per game g the kernel reads obs[g], the observation word the playouts started from:
+ * legal = its 54-bit mask, s = its seat bits, nl = min(popcount(legal), TAROK_PLAYOUT_RANKS).
+ * The game HAS A TEACHER iff legal != 0 and s is in the game's seat set (`seats`, or seats_per_game[g] & 15 when that array
+ * is given, exactly as in tarok_playout_cards).  On the words the env writes this is the playout launches' "takes part":
+ * a word carries legal cards iff its game is in the play phase (a finished game without TAROK_AUTO_RESET and a game
+ * waiting for the exchange have legal = 0).  TAROK_OBS_DONE and TAROK_OBS_ERROR are NOT part of the rule, because they do
+ * not tell such games apart: with TAROK_AUTO_RESET the word that describes a slot's NEXT game keeps TAROK_OBS_DONE (the
+ * first card of every game of a rollout), and the error bit is sticky while its game plays on — the playout launches play
+ * both, and both get their teacher's row.  The word tells every case apart; nothing else is passed.
+ *   with a teacher:  z_j = (sums[g][j][s] - max_k sums[g][k][s]) / (playouts * tau) for the ranks j, k < nl (the difference
+ *                    in integers, the rest in float32; the divisor is the float32 product), and
+ *                    target[g][c] = bf16(exp(z_j) / sum_k exp(z_k)), round to nearest even, at the j-th lowest legal card
+ *                    c; 0 in every other column 0..63.  tau = 0: 1.0 at the card of the smallest rank that maximises
+ *                    sums[g][j][s] — the card action_out of the playout launch names — and 0 elsewhere.
+ *   without:         all 64 columns 0.
+ * EVERY row is written.  Nothing of the env is read but its size and device: the result is a function of the arguments.
+ * sums [N,12,4] i32 (16-byte aligned), obs [N] u64, playouts = the playouts behind every sum (samples, or worlds *
+ * samples), target_out [N,64] bf16 (16-byte aligned).
+ * TAROK_EINVAL (before any HIP call) for a NULL env or array (seats_per_game may be NULL), playouts < 1, tau < 0, NaN or
+ * infinite, a tau > 0 whose float32 product playouts * tau overflows or is not a normal number (below 2^-126), seats
+ * outside 0..15. */
+int tarok_playout_targets(tarok_env *env, const int32_t *sums, const uint64_t *obs, int playouts, float tau, int seats,
+                          const uint8_t *seats_per_game, void *target_out, void *stream);
+
 /* Observation features of the seat to move for a policy network: features_out [N,256] bf16,
  * every entry 0.0 or 1.0 (feature set documented at k_observe — the build's own,
  * the reference's encoder is part of its LSTM agent, Igralec.py:453-543):
@@ -574,6 +599,28 @@ int tarok_learn_chain(tarok_env *env, int64_t B, const uint64_t *feature_words, 
                       const void *w2, const float *b2, const void *w3, const float *b3, const void *w3t, const void *w2t,
                       uint64_t *Xw, void *H1, void *H2, void *dOut, void *dH2, void *dH1, float *scratch, float *terms_out,
                       float *running, void *stream);
+
+/* tarok_learn_chain with a distillation term: the cross-entropy of the policy against a target row per sample (the
+ * playout teacher's: tarok_playout_targets), beside the clipped surrogate, the value loss and the entropy bonus.
+ * target [M,64] bf16, row = sample number as for rec (gathered through index).  Per sample i, weight w_i (the known bit):
+ * p = the masked softmax of the loss, q_c = the row's value at legal card c — columns of illegal cards and 54..63 are
+ * dropped by a select (a NaN there reaches no output), a sample without a legal card has none —, S_i = sum_c q_c:
+ *     ce_i = -sum_c q_c log p_c
+ *     loss            += distill_coef * sum_i w_i ce_i / max(sum w, 1)
+ *     d loss / d logit_c += distill_coef * w_i (S_i p_c - q_c)   on the legal cards; unscaled in dOut like the other parts
+ * S_i p_c - q_c is the exact gradient of ce_i for q as stored (bf16 rows do not sum to exactly 1).  A zero row adds nothing.
+ *   distill_scratch [ceil(B/96),2] f32; distill_out [2] f32 = {sum w ce, sum w S} / max(sum w, 1), summed in a fixed
+ *   order (bit-reproducible); distill_running [2] f32 or NULL: += distill_out.
+ * Every other argument and output as in tarok_learn_chain: H1, H2 and terms_out are those of tarok_learn_chain on the
+ * same inputs, and distill_coef = 0 leaves dOut equal to its dOut.  tarok_learn_dw / tarok_learn_adam read dOut and
+ * terms[3] as before.  TAROK_EINVAL as tarok_learn_chain, and for a NULL target, distill_scratch or distill_out or a
+ * distill_coef that is NaN or infinite. */
+int tarok_learn_chain_distill(tarok_env *env, int64_t B, const uint64_t *feature_words, const int64_t *index, const float *rec,
+                              const float *stats, float clip, float vf_coef, float ent_coef, const void *w1, const float *b1,
+                              const void *w2, const float *b2, const void *w3, const float *b3, const void *w3t,
+                              const void *w2t, uint64_t *Xw, void *H1, void *H2, void *dOut, void *dH2, void *dH1,
+                              float *scratch, float *terms_out, float *running, const void *target, float distill_coef,
+                              float *distill_scratch, float *distill_out, float *distill_running, void *stream);
 
 /* The weight and bias gradients of that minibatch: grad_out [TAROK_MLP_PARAMS] f32 = terms[3] * (dH^T H per layer,
  * column sums of dH), in the flat parameter order.  workspace: tarok_learn_workspace_bytes(env) bytes.

@@ -1501,6 +1501,69 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_det(int64_t n, u64 pseed /* seed ^ salt 
     }
 }
 
+// tarok_playout_targets: a playout launch's sums -> one target row of 64 bf16 per game (include/tarok_env.h).  One lane per
+// game builds its row in LDS — eight zero pieces, then at most twelve 2-byte values at the legal cards' columns — and the
+// workgroup writes its 256 rows, 32 KB in a row of memory, as 16-byte pieces in lane order.  The mover's column of the twelve
+// sums is picked by compare / select (no run-time register index), the row maximum is subtracted in integers (exact), the
+// exponential is expf and the quotient a division: one float32 softmax, rounded once to bf16.
+TK_KERNEL(TK_BLOCK, 128) void k_playout_targets(int64_t n, const int4 *__restrict__ sums, const u64 *__restrict__ obs, float den /* playouts * tau */,
+                                              u32 seats, const uint8_t *__restrict__ seat_sets, uint4 *__restrict__ out) {
+    TK_VGPR_TOP(128, 127);                          // (the twelve 16-byte loads in flight and the twelve exponentials: 80 registers)
+    __shared__ __attribute__((aligned(16))) uint16_t rows[TK_BLOCK * 64];
+    const u32 tid = threadIdx.x;
+    const int64_t g0 = (int64_t)blockIdx.x * TK_BLOCK, g = g0 + tid;
+    uint4 *rows4 = reinterpret_cast<uint4 *>(rows);
+#pragma unroll
+    for (u32 i = 0; i < 8; i++) rows4[i * TK_BLOCK + tid] = make_uint4(0u, 0u, 0u, 0u);
+    __syncthreads();
+    if (g < n) {
+        const u64 word = obs[g], legal = word & TAROK_OBS_MASK;
+        const u32 s = (u32)(word >> TAROK_OBS_SEAT_SHIFT) & 3u;
+        const u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+        if (legal != 0 && ((set >> s) & 1u)) {
+            u32 nl = (u32)popc64(legal);
+            nl = nl < TAROK_PLAYOUT_RANKS ? nl : TAROK_PLAYOUT_RANKS;
+            int v[TAROK_PLAYOUT_RANKS];
+#pragma unroll
+            for (u32 j = 0; j < TAROK_PLAYOUT_RANKS; j++) {
+                int4 q = sums[g * TAROK_PLAYOUT_RANKS + j];
+                v[j] = s == 0 ? q.x : s == 1 ? q.y : s == 2 ? q.z : q.w;
+            }
+            int top = v[0];
+            u32 best = 0;                                // the smallest rank at the maximum: the playout launch's card
+#pragma unroll
+            for (u32 j = 1; j < TAROK_PLAYOUT_RANKS; j++) {
+                bool up = j < nl && v[j] > top;
+                top = up ? v[j] : top;
+                best = up ? j : best;
+            }
+            float e[TAROK_PLAYOUT_RANKS], sum = 0.f;
+#pragma unroll
+            for (u32 j = 0; j < TAROK_PLAYOUT_RANKS; j++) {
+                float x = den > 0.f ? expf((float)((int64_t)v[j] - (int64_t)top) / den) : (j == best ? 1.f : 0.f);
+                e[j] = j < nl ? x : 0.f;
+                sum += e[j];
+            }
+            u64 rest = legal;
+#pragma unroll
+            for (u32 j = 0; j < TAROK_PLAYOUT_RANKS; j++) {
+                if (j < nl) {
+                    u32 c = (u32)__builtin_ctzll(rest);
+                    rest &= rest - 1;
+                    rows[tid * 64 + c] = __builtin_bit_cast(uint16_t, (__bf16)(e[j] / sum));
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const u32 pieces = (u32)(n - g0 < TK_BLOCK ? n - g0 : TK_BLOCK) * 8u;
+#pragma unroll
+    for (u32 i = 0; i < 8; i++) {
+        u32 p = i * TK_BLOCK + tid;
+        if (p < pieces) out[g0 * 8 + p] = rows4[p];
+    }
+}
+
 // Observation features for the seat to move, 256 x bf16 per game (0.0 / 1.0), for a policy
 // network (the feature set is the build's own: the reference's encoder belongs
 // to its LSTM agent, Igralec.py:453-543).  Four 64-wide regions, each a 54-bit card set followed
@@ -3213,6 +3276,18 @@ int tarok_playout_cards_det(tarok_env *e, int worlds, int samples, uint64_t salt
     return TAROK_OK;
 }
 
+int tarok_playout_targets(tarok_env *e, const int32_t *sums, const uint64_t *obs, int playouts, float tau, int seats,
+                          const uint8_t *seats_per_game, void *target_out, void *stream) {
+    if (!e || !sums || !obs || !target_out || playouts < 1 || !(tau >= 0.f) || tau > 3.0e38f || seats < 0 || seats > 15) return TAROK_EINVAL;
+    const float den = (float)playouts * tau;      // the kernel's divisor: a normal float32 number, or 0 with tau = 0
+    if (tau > 0.f && !(den >= 1.17549435e-38f && den <= 3.0e38f)) return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    hipLaunchKernelGGL(k_playout_targets, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, reinterpret_cast<const int4 *>(sums),
+                       (const u64 *)obs, den, (u32)seats, seats_per_game, reinterpret_cast<uint4 *>(target_out));
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
 int tarok_debug_stamps_sized(tarok_env *e, uint64_t *stamps, int64_t n_words) {
     if (!e || n_words < 0 || (stamps && n_words == 0)) return TAROK_EINVAL;
     e->stamps = (u64 *)stamps;
@@ -3519,16 +3594,22 @@ int tarok_learn_select(tarok_env *e, int64_t M, const float *rec, int64_t *index
     return TAROK_OK;
 }
 
-int tarok_learn_chain(tarok_env *e, int64_t B, const uint64_t *feature_words, const int64_t *index, const float *rec,
-                      const float *stats, float clip, float vf_coef, float ent_coef, const void *w1, const float *b1,
-                      const void *w2, const float *b2, const void *w3, const float *b3, const void *w3t, const void *w2t,
-                      uint64_t *Xw, void *H1, void *H2, void *dOut, void *dH2, void *dH1, float *scratch, float *terms_out,
-                      float *running, void *stream) {
+// tarok_learn_chain and tarok_learn_chain_distill: one launcher, the kernel's instantiation chosen by DISTILL
+extern "C++" {
+template <bool DISTILL>
+static int launch_learn_chain(tarok_env *e, int64_t B, const uint64_t *feature_words, const int64_t *index, const float *rec,
+                              const float *stats, float clip, float vf_coef, float ent_coef, const void *w1, const float *b1,
+                              const void *w2, const float *b2, const void *w3, const float *b3, const void *w3t, const void *w2t,
+                              uint64_t *Xw, void *H1, void *H2, void *dOut, void *dH2, void *dH1, float *scratch, float *terms_out,
+                              float *running, const void *target, float distill_coef, float *distill_scratch, float *distill_out,
+                              float *distill_running, void *stream) {
     if (!e || B < 1 || !feature_words || !rec || !stats || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w3t || !w2t || !Xw || !H1 || !H2 ||
         !dOut || !dH2 || !dH1 || !scratch || !terms_out)
         return TAROK_EINVAL;
+    if (DISTILL && (!target || !distill_scratch || !distill_out || !(distill_coef == distill_coef) || distill_coef > 3.0e38f || distill_coef < -3.0e38f))
+        return TAROK_EINVAL;
     HIPCHK(hipSetDevice(e->device));
-    LearnArgs a;
+    std::conditional_t<DISTILL, LearnArgsDistill, LearnArgs> a;
     a.B = B; a.words = (const u64 *)feature_words; a.index = index; a.rec = (const float4 *)rec; a.stats = (const float4 *)stats;
     a.clip = clip; a.vf_coef = vf_coef; a.ent_coef = ent_coef;
     a.w1 = (const __bf16 *)w1; a.w2 = (const __bf16 *)w2; a.w3 = (const __bf16 *)w3; a.w3t = (const __bf16 *)w3t; a.w2t = (const __bf16 *)w2t;
@@ -3538,11 +3619,38 @@ int tarok_learn_chain(tarok_env *e, int64_t B, const uint64_t *feature_words, co
     a.part = (float4 *)scratch;
     unsigned blocks = (unsigned)((B + LN_M - 1) / LN_M);
     a.stamps = stamps_for(e, 8 * (size_t)blocks);       // (eight stamps per workgroup: a buffer sized for the step kernels gets none)
-    hipLaunchKernelGGL(k_learn_chain, dim3(blocks), dim3(LN_CHAIN_THREADS), 0, (hipStream_t)stream, a);
-    hipLaunchKernelGGL(k_learn_terms, dim3(1), dim3(TK_BLOCK), 0, (hipStream_t)stream, (int)blocks, (const float4 *)scratch,
-                       (float4 *)terms_out, (float4 *)running);
+    if constexpr (DISTILL) { a.target = (const uint2 *)target; a.distill_coef = distill_coef; a.dpart = (float2 *)distill_scratch; }
+    hipLaunchKernelGGL(k_learn_chain<DISTILL>, dim3(blocks), dim3(LN_CHAIN_THREADS), 0, (hipStream_t)stream, a);
+    if constexpr (DISTILL)
+        hipLaunchKernelGGL(k_learn_terms_distill, dim3(1), dim3(TK_BLOCK), 0, (hipStream_t)stream, (int)blocks, (const float4 *)scratch,
+                           (const float2 *)distill_scratch, (float4 *)terms_out, (float4 *)running, (float2 *)distill_out,
+                           (float2 *)distill_running);
+    else
+        hipLaunchKernelGGL(k_learn_terms, dim3(1), dim3(TK_BLOCK), 0, (hipStream_t)stream, (int)blocks, (const float4 *)scratch,
+                           (float4 *)terms_out, (float4 *)running);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
+}
+}  // extern "C++"
+
+int tarok_learn_chain(tarok_env *e, int64_t B, const uint64_t *feature_words, const int64_t *index, const float *rec,
+                      const float *stats, float clip, float vf_coef, float ent_coef, const void *w1, const float *b1,
+                      const void *w2, const float *b2, const void *w3, const float *b3, const void *w3t, const void *w2t,
+                      uint64_t *Xw, void *H1, void *H2, void *dOut, void *dH2, void *dH1, float *scratch, float *terms_out,
+                      float *running, void *stream) {
+    return launch_learn_chain<false>(e, B, feature_words, index, rec, stats, clip, vf_coef, ent_coef, w1, b1, w2, b2, w3, b3, w3t, w2t, Xw,
+                                     H1, H2, dOut, dH2, dH1, scratch, terms_out, running, nullptr, 0.f, nullptr, nullptr, nullptr, stream);
+}
+
+int tarok_learn_chain_distill(tarok_env *e, int64_t B, const uint64_t *feature_words, const int64_t *index, const float *rec,
+                              const float *stats, float clip, float vf_coef, float ent_coef, const void *w1, const float *b1,
+                              const void *w2, const float *b2, const void *w3, const float *b3, const void *w3t, const void *w2t,
+                              uint64_t *Xw, void *H1, void *H2, void *dOut, void *dH2, void *dH1, float *scratch, float *terms_out,
+                              float *running, const void *target, float distill_coef, float *distill_scratch, float *distill_out,
+                              float *distill_running, void *stream) {
+    return launch_learn_chain<true>(e, B, feature_words, index, rec, stats, clip, vf_coef, ent_coef, w1, b1, w2, b2, w3, b3, w3t, w2t, Xw,
+                                    H1, H2, dOut, dH2, dH1, scratch, terms_out, running, target, distill_coef, distill_scratch, distill_out,
+                                    distill_running, stream);
 }
 
 // chunks per layer of k_learn_dw: one workgroup per CU in all.  A tile costs a workgroup about the same in every

@@ -149,22 +149,26 @@ TK_KERNEL(TK_BLOCK, 64) void k_returns_gae_seats(TK_RETURNS_ARGS, float gamma, f
 
 // Column sums of `blocks` float4 partials by one workgroup, in double and in a fixed order (strided accumulate per thread,
 // LDS tree): afterwards red[c][0] = the sum of column c, for thread 0.
-template <int C>
-__device__ __forceinline__ void part_column_sums(int blocks, const float4 *__restrict__ part, double (&red)[C][TK_BLOCK]) {
-    double a[C] = {};
+// (E = 2: two more columns, C and C + 1, from a second array of float2 partials: the distillation term's)
+template <int C, int E = 0>
+__device__ __forceinline__ void part_column_sums(int blocks, const float4 *__restrict__ part, double (&red)[C + E][TK_BLOCK],
+                                                 const float2 *__restrict__ extra = nullptr) {
+    static_assert(E == 0 || E == 2, "no extra columns, or one float2 per block");
+    double a[C + E] = {};
     for (int k = threadIdx.x; k < blocks; k += TK_BLOCK) {
         float4 p = part[k];
         const float col[4] = {p.x, p.y, p.z, p.w};
 #pragma unroll
         for (int c = 0; c < C; c++) a[c] += col[c];
+        if constexpr (E == 2) { float2 x = extra[k]; a[C] += x.x; a[C + 1] += x.y; }
     }
 #pragma unroll
-    for (int c = 0; c < C; c++) red[c][threadIdx.x] = a[c];
+    for (int c = 0; c < C + E; c++) red[c][threadIdx.x] = a[c];
     __syncthreads();
     for (int s = TK_BLOCK / 2; s >= 1; s >>= 1) {
         if ((int)threadIdx.x < s) {
 #pragma unroll
-            for (int c = 0; c < C; c++) red[c][threadIdx.x] += red[c][threadIdx.x + s];
+            for (int c = 0; c < C + E; c++) red[c][threadIdx.x] += red[c][threadIdx.x + s];
         }
         __syncthreads();
     }
@@ -398,14 +402,32 @@ struct LearnArgs {
     float4 *part;                                // [blocks] {sum w pi, sum w v, sum w H, sum w}
     u64 *stamps;                                 // diagnostics (tarok_debug_stamps): [blocks][8] shader-clock stamps of the phases, or NULL
 };
+// tarok_learn_chain_distill: the same and the playout teacher's target rows.  A struct of its own, so that the kernel
+// arguments of the instantiation without the term are LearnArgs, byte for byte
+struct LearnArgsDistill : LearnArgs {
+    const uint2 *target;                         // [M][64] bf16 as 16 x 8 bytes per row; row = sample number, as for rec
+    float distill_coef;
+    float2 *dpart;                               // [blocks] {sum w ce, sum w S}
+};
 
 // Two workgroups share a CU (75 KB of LDS, 186 VGPRs: two waves per SIMD): one's gather, epilogues, loss and tile
 // stores run under the other's MFMAs.  (A fifth, store-only wave per workgroup was tried — on gfx9 `vmcnt` counts loads
 // and stores together, in order, so a wave that has just stored a tile waits for those stores at its next weight
 // fragment — but five waves of 186 registers leave room for ONE workgroup per CU: 552 us against 499 us per
 // minibatch, profiles/r03_learner_steps.txt.)
+// DISTILL (tarok_learn_chain_distill): the cross-entropy of the policy against a target row q per sample, beside the other
+// three terms: ce = -sum_c q_c log p_c over the LEGAL cards c (q of every other column is dropped by a select: a NaN there
+// reaches nothing), S = sum_c q_c, d ce / d logit_c = S p_c - q_c.  The lane that holds outputs 32 ft + 8 q + 4 h .. + 3 of a
+// sample loads exactly those eight 8-byte pieces of the sample's target row — the layout of its D store — in the gather
+// phase: the row number comes from `index` by a load at the kernel's top, the eight loads leave behind the gather's own and
+// in front of every tile store, and the first weight fragment of layer 1, which the wave waits for anyway, retires them
+// (vmcnt counts in order): the loss phase, two layers later, never waits for them.  Sixteen registers held until then.
+// Everything of the term sits under `if constexpr (DISTILL)`; tarok_learn_chain launches k_learn_chain<false>.  (That
+// instantiation has the registers, LDS bytes and matrix / memory instructions of the kernel before the term existed, but not
+// its exact instruction stream: figures and the timing that goes with them in DESIGN.md section 8.5.)
 #define LN_CHAIN_THREADS TK_BLOCK
-TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_learn_chain(LearnArgs a) {
+template <bool DISTILL>
+TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_learn_chain(std::conditional_t<DISTILL, LearnArgsDistill, LearnArgs> a) {
     TK_VGPR_TOP(256, 255);
     __shared__ __attribute__((aligned(16))) __bf16 X[LN_M * PM_LD];
     __shared__ __attribute__((aligned(16))) __bf16 D[LN_M * LN_LDD];
@@ -416,13 +438,21 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     // put them 64 bytes apart — an eight-way bank conflict on every one of the 24 byte stores of a lane: k_learn_chain
     // 320 -> 302 us per minibatch, profiles/r04_learner_steps.txt)
     __shared__ uint8_t mask1[64][LN_M];
-    __shared__ float red[4][TK_BLOCK / 64];
+    __shared__ float red[DISTILL ? 6 : 4][TK_BLOCK / 64];
     __shared__ __attribute__((aligned(16))) float bias_s[580];        // b1 | b2 | b3 | stats: read from LDS, so that no epilogue waits for a
                                                                        // vector-memory load (behind the tile stores in flight: below)
     const int64_t base = (int64_t)blockIdx.x * LN_M;
     const u32 tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
 #define LN_STAMP(k) do { if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
     LN_STAMP(0);
+    int64_t tsrc = 0;                                        // DISTILL: the target row of the lane's sample of the loss phase
+    uint2 tq[DISTILL ? 8 : 1];
+    if constexpr (DISTILL) {
+        if (wave < LN_GT) {
+            int64_t j = base + 32 * wave + r < a.B ? base + 32 * wave + r : a.B - 1;
+            tsrc = a.index ? a.index[j] : j;
+        }
+    }
     for (u32 k = threadIdx.x; k < 580; k += TK_BLOCK)
         bias_s[k] = k < 256 ? a.b1[k] : k < 512 ? a.b2[k - 256] : k < 576 ? a.b3[k - 512] : reinterpret_cast<const float *>(a.stats)[k - 576];
     // ---- gather: feature words and records of the tile's samples
@@ -436,6 +466,13 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         float4 rc = a.rec[src];
         if (base + tid >= a.B) rc.w = __uint_as_float(__float_as_uint(rc.w) & 0xFFu);       // (padding rows: weight 0)
         recs[tid] = rc;
+    }
+    if constexpr (DISTILL) {
+        if (wave < LN_GT) {
+            const uint2 *trow = a.target + tsrc * 16 + h;
+#pragma unroll
+            for (int k = 0; k < 8; k++) tq[k] = trow[2 * k];              // columns 32 ft + 8 q + 4 h .. + 3 at k = 4 ft + q
+        }
     }
     __syncthreads();
     if (tid < 2 * LN_M) {   // expansion to bf16 0.0 / 1.0 (policy_expand, restated): two threads per sample, odd / even bytes
@@ -489,7 +526,7 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     // ---- layer 3 (64 outputs: 54 card logits, value in column 54) for samples [32 wave, 32 wave + 32), and the loss
     // in its accumulators: lane (r, h) holds outputs 32 ft + 8 q + 4 h + j of sample 32 wave + r, its partner lane ^ 32
     // the other half.  (Waves 0 .. LN_GT - 1: the fourth compute wave has no samples in this phase.)
-    float s_pi = 0.f, s_v = 0.f, s_h = 0.f, s_w = 0.f;
+    float s_pi = 0.f, s_v = 0.f, s_h = 0.f, s_w = 0.f, s_ce = 0.f, s_q = 0.f;
     if (wave < LN_GT) {
         const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16 *>(a.w3), 0, 2 * 16 * 1024, 0x00020000);
         auto wfrag = [&](int f) __attribute__((always_inline)) {
@@ -527,6 +564,7 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         u64 m = ext[gi][1] & TAROK_OBS_MASK;                 // feature word 1 = the legal cards
         u32 meta = __float_as_uint(rc.w);
         float w = (meta & 256u) ? 1.f : 0.f;
+        const bool has_card = m != 0;
         if (!m) { m = 1; w = 0.f; }                          // nothing to play: no contribution, finite arithmetic
         u32 act = meta & 255u;
         act = act < 54 ? act : 53u;
@@ -595,9 +633,29 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         float g = (first || inside) ? -A * ratio : 0.f;
         float dv = value - rc.y;
         if (h == 0) { s_pi = w * (-fminf(s1, s2)); s_v = w * dv * dv; s_h = w * H; s_w = w; }
+        // DISTILL: the lane's 32 target values in the order of l[] / p_[], 0 where the card is not legal (select), ce and S
+        float tqf[DISTILL ? 32 : 1], S = 0.f;
+        if constexpr (DISTILL) {
+            const u32 legal_q = has_card ? legal : 0u;
+            float ce = 0.f;
+#pragma unroll
+            for (int k = 0; k < 32; k++) {
+                const u32 pair = (k & 2) ? tq[k >> 2].y : tq[k >> 2].x;
+                const float qv = __uint_as_float((k & 1) ? (pair & 0xFFFF0000u) : (pair << 16));
+                const float qk = ((legal_q >> k) & 1) ? qv : 0.f;
+                tqf[k] = qk;
+                S += qk;
+                ce -= qk * l[k];
+            }
+            S += __shfl_xor(S, 32);
+            ce += __shfl_xor(ce, 32);
+            if (h == 0) { s_ce = w * ce; s_q = w * S; }
+        }
         // d loss / d output (unscaled: k_learn_reduce divides by the sum of the weights) -> D[sample][output], bf16; the sample's
         // weight folded into the two coefficients
         const float gw = g * w, ew = a.ent_coef * w, dval = w * a.vf_coef * 2.0f * dv;
+        float cw = 0.f;
+        if constexpr (DISTILL) cw = a.distill_coef * w;
 #pragma unroll
         for (int ft = 0; ft < 2; ft++)
 #pragma unroll
@@ -609,6 +667,7 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                     float p = p_[k];
                     float t = (act_h == (u32)(32 * ft + 8 * q + j)) ? 1.0f - p : -p;
                     d4[j] = gw * t + ew * p * (l[k] + H);
+                    if constexpr (DISTILL) d4[j] += cw * (S * p - tqf[k]);
                     if (ft == 1 && q == 2 && j == 2) d4[j] = (h == 1) ? dval : d4[j];      // output 54: the value
                 }
                 *reinterpret_cast<uint2 *>(D + gi * LN_LDD + 32 * ft + 8 * q + 4 * h) = make_uint2(ln_bf16x2_of(d4[0], d4[1]), ln_bf16x2_of(d4[2], d4[3]));
@@ -619,6 +678,11 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     // block sums of the loss terms (fixed order)
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) { s_pi += __shfl_xor(s_pi, o); s_v += __shfl_xor(s_v, o); s_h += __shfl_xor(s_h, o); s_w += __shfl_xor(s_w, o); }
+    if constexpr (DISTILL) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { s_ce += __shfl_xor(s_ce, o); s_q += __shfl_xor(s_q, o); }
+        if (lane == 0) { red[4][wave] = s_ce; red[5][wave] = s_q; }
+    }
     if (lane == 0) { red[0][wave] = s_pi; red[1][wave] = s_v; red[2][wave] = s_h; red[3][wave] = s_w; }
     __syncthreads();                                         // D complete; every wave is done with X (= H2) as an operand
     LN_STAMP(4);
@@ -670,6 +734,11 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
         for (int k = 0; k < TK_BLOCK / 64; k++) { a0 += red[0][k]; a1 += red[1][k]; a2 += red[2][k]; a3 += red[3][k]; }
         a.part[blockIdx.x] = make_float4(a0, a1, a2, a3);
+        if constexpr (DISTILL) {
+            float c0 = 0.f, c1 = 0.f;
+            for (int k = 0; k < TK_BLOCK / 64; k++) { c0 += red[4][k]; c1 += red[5][k]; }
+            a.dpart[blockIdx.x] = make_float2(c0, c1);
+        }
     }
     LN_STAMP(6);
 #undef LN_STAMP
@@ -899,6 +968,25 @@ TK_KERNEL(TK_BLOCK, 64) void k_learn_terms(int blocks, const float4 *__restrict_
         float4 t = make_float4((float)(red[0][0] * inv), (float)(red[1][0] * inv), (float)(red[2][0] * inv), (float)inv);
         terms[0] = t;
         if (running) { float4 q = running[0]; running[0] = make_float4(q.x + t.x, q.y + t.y, q.z + t.z, q.w + 1.f); }
+    }
+}
+
+// k_learn_terms for tarok_learn_chain_distill, in its place: the same four terms by the same arithmetic (the same bits) and,
+// from the chain's second array of block sums, dout = {sum w ce, sum w S} / max(sum w, 1): one reducer, one launch
+TK_KERNEL(TK_BLOCK, 64) void k_learn_terms_distill(int blocks, const float4 *__restrict__ part, const float2 *__restrict__ dpart,
+                                                   float4 *__restrict__ terms, float4 *__restrict__ running /* or NULL */,
+                                                   float2 *__restrict__ dout, float2 *__restrict__ drunning /* or NULL: += dout */) {
+    TK_VGPR_TOP(64, 63);
+    __shared__ double red[6][TK_BLOCK];
+    part_column_sums<4, 2>(blocks, part, red, dpart);
+    if (threadIdx.x == 0) {
+        double inv = 1.0 / (red[3][0] < 1.0 ? 1.0 : red[3][0]);
+        float4 t = make_float4((float)(red[0][0] * inv), (float)(red[1][0] * inv), (float)(red[2][0] * inv), (float)inv);
+        terms[0] = t;
+        if (running) { float4 q = running[0]; running[0] = make_float4(q.x + t.x, q.y + t.y, q.z + t.z, q.w + 1.f); }
+        float2 d = make_float2((float)(red[4][0] * inv), (float)(red[5][0] * inv));
+        dout[0] = d;
+        if (drunning) { float2 q = drunning[0]; drunning[0] = make_float2(q.x + d.x, q.y + d.y); }
     }
 }
 

@@ -347,6 +347,20 @@ class TarokVecEnv:
                                                          self._p(sum_out), self._p(action_out), self._stream()))
         return sum_out, action_out
 
+    def playout_targets(self, sums, obs_words, playouts, tau, seats=15, seats_per_game=None, target_out=None):
+        """A playout launch's sums as a teacher's target rows (tarok_playout_targets): target [N,64] bf16, for a game with
+        a teacher the softmax over its legal cards of (the mover's sum) / (playouts * tau) at the cards' columns (tau = 0:
+        1.0 at the playout launch's card), 0 everywhere else; a zero row for a game without one.  sums [N,12,4] int32
+        (playout_cards / playout_cards_det), obs_words [N] the observation words the playouts started from, playouts =
+        samples (x worlds), seats / seats_per_game as given to the playout launch.  Stream-ordered; allocates nothing when
+        target_out is given."""
+        with torch.cuda.device(self.device):
+            if target_out is None:
+                target_out = torch.empty((self.n, 64), dtype=torch.bfloat16, device=self.device)
+            _native.check(self.L.tarok_playout_targets(self._h, self._p(sums), self._p(obs_words), int(playouts), float(tau), int(seats),
+                                                       self._p(self._seat_sets(seats_per_game)), self._p(target_out), self._stream()))
+        return target_out
+
     def observe(self, out=None):
         """[N,256] bf16 features of the seat to move (include/tarok_env.h tarok_observe)."""
         with torch.cuda.device(self.device):
@@ -552,6 +566,19 @@ class TarokVecEnv:
                                                    self._p(wf["w3t"]), self._p(wf["w2t"]), self._p(Xw), self._p(H1), self._p(H2), self._p(dOut),
                                                    self._p(dH2), self._p(dH1), self._p(scratch), self._p(terms), self._p(running),
                                                    self._stream()))
+
+    def learn_chain_distill(self, B, words, index, rec, stats, clip, vf_coef, ent_coef, wf, bias, Xw, H1, H2, dOut, dH2, dH1, scratch, terms,
+                            running, target, distill_coef, distill_scratch, distill_out, distill_running=None):
+        """learn_chain with the distillation term (tarok_learn_chain_distill): target [M,64] bf16 rows by sample number (as
+        rec), distill_scratch [ceil(B/96),2] f32, distill_out [2] f32 = {weighted mean cross-entropy, weighted mean of the
+        rows' sums}, distill_running [2] f32 or None: += distill_out."""
+        with torch.cuda.device(self.device):
+            _native.check(self.L.tarok_learn_chain_distill(
+                self._h, int(B), self._p(words), self._p(index), self._p(rec), self._p(stats), float(clip), float(vf_coef),
+                float(ent_coef), self._p(wf["w1"]), self._p(bias[0]), self._p(wf["w2"]), self._p(bias[1]), self._p(wf["w3"]),
+                self._p(bias[2]), self._p(wf["w3t"]), self._p(wf["w2t"]), self._p(Xw), self._p(H1), self._p(H2), self._p(dOut),
+                self._p(dH2), self._p(dH1), self._p(scratch), self._p(terms), self._p(running), self._p(target), float(distill_coef),
+                self._p(distill_scratch), self._p(distill_out), self._p(distill_running), self._stream()))
 
     def learn_workspace_bytes(self):
         return int(self.L.tarok_learn_workspace_bytes(self._h))

@@ -253,11 +253,21 @@ class SelfPlay:
     (tarok_learn_returns_seats), and the fused update compacts them (tarok_learn_select) so that its minibatches hold
     nothing else.  learner_seats: an int 0..15 (one seat set for every slot) or a [N] uint8 tensor of sets; default:
     slot g owns the single seat (game_offset + g) % 4, so a sharded run seats the same games the same way.
-    set_opponent() swaps the opponent's weights without a new graph capture."""
+    set_opponent() swaps the opponent's weights without a new graph capture.
+
+    teacher = dict(worlds=W, samples=S, tau=tau, every=k, salt=...): learn from the playout teacher as well (expert
+    iteration).  Before the policy launch of every k-th lock-step (every: default 1) the rollout runs one playout launch
+    on the learner's seats — tarok_playout_cards_det with W worlds, or the open-hand tarok_playout_cards with worlds=0 —
+    and one tarok_playout_targets on the words the policy is about to choose its cards on, into buf["teach"] [T,N,64] bf16
+    (rows of the other lock-steps stay zero).  Both are stream-ordered and read-only on the env: they sit inside the one
+    captured rollout graph and the rollout's own bytes do not change.  The update then adds distill_coef x the
+    cross-entropy of the policy against those rows (tarok_learn_chain_distill; on the torch paths in torch) and the stats
+    gain distill_ce and teacher_frac (the weighted mean of the rows' sums: about the share of weighted samples with a
+    teacher).  distill_coef = 0 with a teacher measures the term without acting on it.  teacher=None: nothing changes."""
 
     def __init__(self, env, hidden=256, lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.01, reward_scale=1.0 / 70.0, seed=0,
                  use_graph=True, fused=None, fused_loss=None, fused_step=None, fused_learner=None, max_grad_norm=1.0,
-                 gamma=None, gae_lambda=None, opponent=None, learner_seats=None):
+                 gamma=None, gae_lambda=None, opponent=None, learner_seats=None, teacher=None, distill_coef=0.0):
         if opponent is None and learner_seats is not None:
             raise ValueError("learner_seats says which seats learn against an opponent: pass opponent= (a snapshot()) as well")
         if opponent is not None:
@@ -267,6 +277,20 @@ class SelfPlay:
                                    "and the fused step")
             if isinstance(learner_seats, int) and not 0 <= learner_seats <= 15:
                 raise ValueError("learner_seats: a seat set 0..15 or a [N] uint8 tensor of sets")
+        self.teacher, self.distill_coef = None, float(distill_coef)
+        if teacher is not None:
+            unknown = set(teacher) - {"worlds", "samples", "tau", "every", "salt"}
+            if unknown or "samples" not in teacher:
+                raise ValueError("teacher: dict(worlds=W, samples=S, tau=tau, every=k, salt=...), samples required; unknown keys %s" % sorted(unknown))
+            t = dict(worlds=int(teacher.get("worlds", 0)), samples=int(teacher["samples"]), tau=float(teacher.get("tau", 1.0)),
+                     every=int(teacher.get("every", 1)), salt=int(teacher.get("salt", 0)))
+            if not (0 <= t["worlds"] <= K.PLAYOUT_MAX_WORLDS and 1 <= t["samples"] <= K.PLAYOUT_MAX_SAMPLES and t["every"] >= 1
+                    and 0.0 <= t["tau"] < float("inf")):
+                raise ValueError("teacher: worlds 0..%d, samples 1..%d, tau >= 0 and finite, every >= 1"
+                                 % (K.PLAYOUT_MAX_WORLDS, K.PLAYOUT_MAX_SAMPLES))
+            self.teacher = t
+        elif distill_coef:
+            raise ValueError("distill_coef weighs the playout teacher's term: pass teacher= as well")
         self.env = env
         # returns: both None = every card credited with its seat's final score (Monte-Carlo: assign_returns /
         # tarok_learn_returns); either set = per-seat GAE(gamma, lambda), the other defaulting to 1.0 (assign_gae /
@@ -433,11 +457,30 @@ class SelfPlay:
                          val=torch.empty((T, n), dtype=torch.float32, device=dev),
                          done=torch.empty((T, n), dtype=torch.uint8, device=dev),
                          reward=torch.zeros((T, n, 4), dtype=torch.int16, device=dev))   # written only where done
+        if self.teacher is not None:                  # the teacher's target rows, and the playout launch's own outputs
+            self._buf["teach"] = torch.zeros((T, n, 64), dtype=torch.bfloat16, device=dev)
+            self._teach_sums = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=dev)
+            self._teach_act = torch.empty(n, dtype=torch.uint8, device=dev)
         self._graph = None
+
+    def _teach(self, t):
+        """The teacher's rows of lock-step t: one playout launch on the learner's seats from the env's current positions,
+        one tarok_playout_targets on the words of that lock-step.  Stream-ordered, read-only on the env, no allocation."""
+        env, buf, tc = self.env, self._buf, self.teacher
+        if tc["worlds"]:
+            env.playout_cards_det(tc["worlds"], tc["samples"], salt=tc["salt"], seats_per_game=self._seats, sum_out=self._teach_sums,
+                                  action_out=self._teach_act)
+        else:
+            env.playout_cards(tc["samples"], salt=tc["salt"], seats_per_game=self._seats, sum_out=self._teach_sums,
+                              action_out=self._teach_act)
+        env.playout_targets(self._teach_sums, buf["words"][t], max(1, tc["worlds"]) * tc["samples"], tc["tau"],
+                            seats_per_game=self._seats, target_out=buf["teach"][t])
 
     def _rollout_body(self, T):
         env, buf, w = self.env, self._buf, self._w
         for t in range(T):
+            if self.teacher is not None and t % self.teacher["every"] == 0:
+                self._teach(t)
             if self._opp is not None:                 # the learner's seats play w, the others the frozen opponent
                 env.policy_step(w, buf["words"][t], buf["words"][t + 1], buf["act"][t], buf["logp"][t], buf["val"][t],
                                 feature_words_out=buf["obs"][t], reward_out=buf["reward"][t], done_out=buf["done"][t],
@@ -516,6 +559,8 @@ class SelfPlay:
         std = (((adv - mean) ** 2 * m).sum() / m.sum().clamp(min=1)).sqrt().clamp(min=1e-6)
         adv = (adv - mean) / std
         stats = dict(loss=0.0, pi_loss=0.0, v_loss=0.0, entropy=0.0, allreduce_bytes=0, known_frac=float(m.mean()))
+        teach = flat(buf["teach"]) if self.teacher is not None else None
+        dsums = torch.zeros(2, dtype=torch.float32, device=self.device) if teach is not None else None
         if self._opp is not None:                     # (the weights m carry the seat mask: the opponent's samples count for nothing)
             stats["learner_samples"] = int(known.sum())
         sums = torch.zeros(4, dtype=torch.float32, device=self.device)     # loss terms summed on the device: no host sync per minibatch
@@ -535,6 +580,19 @@ class SelfPlay:
                                                     self.clip, self.vf_coef, self.ent_coef)
                     pi_loss, v_loss, ent = terms[0], terms[1], terms[2]
                     loss = pi_loss + self.vf_coef * v_loss - self.ent_coef * ent
+                    if teach is not None:                 # tarok_ppo_loss knows no teacher: the term in torch, added to dout
+                        legal = legal_matrix(words[idx] & K.OBS_MASK)
+                        lp = F.log_softmax(out[:, :54].float().masked_fill(~legal, float("-inf")), dim=-1)
+                        lp = torch.where(legal, lp, torch.zeros_like(lp))
+                        q = torch.where(legal, teach[idx][:, :54].float(), torch.zeros_like(lp))
+                        S = q.sum(-1)
+                        wsum = w.sum().clamp(min=1)
+                        ce = (-(q * lp).sum(-1) * w).sum() / wsum
+                        dsums += torch.stack([ce, (S * w).sum() / wsum])
+                        loss = loss + self.distill_coef * ce
+                        dd = torch.zeros_like(dout, dtype=torch.float32)
+                        dd[:, :54] = (self.distill_coef * w / wsum).unsqueeze(-1) * (S.unsqueeze(-1) * lp.exp() * legal - q)
+                        dout = (dout.float() + dd).to(torch.bfloat16)
                     self.opt.zero_grad(set_to_none=True)
                     out.backward(dout)
                 else:
@@ -551,6 +609,11 @@ class SelfPlay:
                     p = logp_all.exp()
                     ent = (-(p * torch.where(legal, logp_all, torch.zeros_like(logp_all))).sum(-1) * w).sum() / wsum
                     loss = pi_loss + self.vf_coef * v_loss - self.ent_coef * ent
+                    if teach is not None:
+                        q = torch.where(legal, teach[idx][:, :54].float(), torch.zeros_like(logp_all))
+                        ce = (-(q * torch.where(legal, logp_all, torch.zeros_like(logp_all))).sum(-1) * w).sum() / wsum
+                        dsums += torch.stack([ce.detach(), (q.sum(-1) * w).sum() / wsum])
+                        loss = loss + self.distill_coef * ce
                     self.opt.zero_grad(set_to_none=True)
                     loss.backward()
                 stats["allreduce_bytes"] = allreduce_gradients(params)
@@ -560,6 +623,8 @@ class SelfPlay:
                 sums += torch.stack([loss.detach().float(), pi_loss.detach().float(), v_loss.detach().float(), ent.detach().float()])
         for k, v in zip(("loss", "pi_loss", "v_loss", "entropy"), sums.tolist()):
             stats[k] = v / max(1, count)
+        if teach is not None:
+            stats["distill_ce"], stats["teacher_frac"] = (v / max(1, count) for v in dsums.tolist())
         return stats
 
     def _learn_bufs(self, M, B):
@@ -576,6 +641,8 @@ class SelfPlay:
                       Xw=torch.zeros((B + K.LEARN_PAD, 4), dtype=torch.int64, device=dev),
                       running=torch.zeros(4, dtype=torch.float32, device=dev),
                       work=torch.empty(self.env.learn_workspace_bytes(), dtype=torch.uint8, device=dev))
+            if self.teacher is not None:
+                lb.update(dscratch=f32((B + 95) // 96, 2), dterms=f32(2), drunning=torch.zeros(2, dtype=torch.float32, device=dev))
             self._learn = lb
         return lb
 
@@ -622,9 +689,16 @@ class SelfPlay:
             count = int(lb["sel_count"].item())       # the one host read
             sel = lb["sel"]
             if count == 0:                            # nothing of the learner's: no launch, no step
-                return dict(loss=0.0, pi_loss=0.0, v_loss=0.0, entropy=0.0, allreduce_bytes=0, known_frac=0.0, learner_samples=0)
+                none = dict(loss=0.0, pi_loss=0.0, v_loss=0.0, entropy=0.0, allreduce_bytes=0, known_frac=0.0, learner_samples=0)
+                if self.teacher is not None:
+                    none.update(distill_ce=0.0, teacher_frac=0.0)
+                return none
         words = buf["obs"].view(M, 4)
         lb["running"].zero_()
+        teach = None
+        if self.teacher is not None:
+            teach = buf["teach"].view(M, 64)
+            lb["drunning"].zero_()
         nbytes = 0
         bias = (self._w[1], self._w[3], self._w[5])
         for _ in range(epochs):
@@ -633,8 +707,12 @@ class SelfPlay:
                 if sel is not None:
                     idx = sel[idx]
                 b = idx.numel()
-                env.learn_chain(b, words, idx, lb["rec"], lb["stats"], self.clip, self.vf_coef, self.ent_coef, self._wf, bias,
-                                lb["Xw"], lb["H1"], lb["H2"], lb["dOut"], lb["dH2"], lb["dH1"], lb["scratch"], lb["terms"], lb["running"])
+                chain_args = (b, words, idx, lb["rec"], lb["stats"], self.clip, self.vf_coef, self.ent_coef, self._wf, bias,
+                              lb["Xw"], lb["H1"], lb["H2"], lb["dOut"], lb["dH2"], lb["dH1"], lb["scratch"], lb["terms"], lb["running"])
+                if teach is None:
+                    env.learn_chain(*chain_args)
+                else:
+                    env.learn_chain_distill(*chain_args, teach, self.distill_coef, lb["dscratch"], lb["dterms"], lb["drunning"])
                 learn_dw_ranges(env, b, [lb[a] for a in ("Xw", "H1", "H2", "dOut", "dH2", "dH1")], lb["terms"], lb["work"],
                                 self.gflat, lb["gpart"])
                 nbytes = allreduce_flat(self.gflat)
@@ -647,6 +725,9 @@ class SelfPlay:
                      known_frac=float(lb["stats"][2]))
         if sel is not None:
             stats["learner_samples"] = count
+        if teach is not None:
+            ce, frac = (v / cnt for v in lb["drunning"].tolist())
+            stats.update(distill_ce=ce, teacher_frac=frac, loss=stats["loss"] + self.distill_coef * ce)
         return stats
 
     def iterate(self, T=48, epochs=2, minibatches=8):
