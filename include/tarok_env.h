@@ -270,7 +270,8 @@ int tarok_playout_cards(tarok_env *env, int samples, uint64_t salt, int seats, c
  * tarok_playout_cards.
  *
  * Known leaks (information the re-deal does not use, or uses though the seat could not have it):
- *   - a void that another seat has shown by not following suit does not constrain the re-deal;
+ *   - a void that another seat has shown by not following suit does not constrain the re-deal (it does in
+ *     tarok_playout_cards_voids below);
  *   - Klop's face-down talon keeps its true cards in every world;
  *   - the declarer's discards lie in the declarer's pile and so count as seen.
  * TAROK_EINVAL (before any HIP call) for a NULL env, worlds outside 1..TAROK_PLAYOUT_MAX_WORLDS, samples outside
@@ -279,6 +280,67 @@ int tarok_playout_cards(tarok_env *env, int samples, uint64_t salt, int seats, c
 #define TAROK_PLAYOUT_MAX_WORLDS 64
 int tarok_playout_cards_det(tarok_env *env, int worlds, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
                             int32_t *sum_out, uint8_t *action_out, void *stream);
+
+/* Shown voids: what the play so far has told the whole table about who is out of which class of cards.  Needs an env
+ * created with TAROK_HISTORY.
+ *   voids_out [N] u32, one word per game: bit 5 * seat + class is set iff that seat has shown in this game that it holds
+ *   no card of that class; class(card) = min(card >> 3, 4): 0..3 the suits, 4 the taroks (cards 32..53).  Bits 20..31
+ *   are 0.  EVERY row is written: 0 for a game that is not in the play phase.
+ * Rule, for a game in play with `played` cards so far: history entries 0 .. played - 1 are walked (entries at or beyond
+ * `played` are stale and are not read).  Tricks are entries 4t .. 4t + 3; the first leader (the declarer of a Berac, else
+ * seat 0) and the winner of every complete trick are replayed from the cards, as tarok_observe_ref replays them.  For
+ * card j >= 1 of a trick, complete or on the table, played by seat (lead + j) & 3, with L = the class of the trick's
+ * first card and K = the class of this card: if K != L the seat is void in L; if moreover K != 4 and L != 4 it is void in
+ * taroks too (it could neither follow suit nor trump; Navadna_igra.py:158-168, Klop.py:96-133).  Klop's talon gift is not
+ * a history entry and plays no part.  The rule is sound for every contract: a seat's true hand never holds a card of a
+ * class its bits mark void (tests/test_playout_voids_cpu.py plays every contract on the oracle and checks after each card).
+ * Read-only on the env, stream-ordered, capturable.
+ * TAROK_EINVAL (before any HIP call) for a NULL env or array, or an env without TAROK_HISTORY. */
+int tarok_shown_voids(tarok_env *env, uint32_t *voids_out, void *stream);
+
+/* Void-aware determinized playouts: tarok_playout_cards_det whose worlds honour a void word per game.  World w of game g
+ * is a re-deal of the unseen pool P that keeps the hand sizes AND gives no other seat a card of a class voids[g] marks it
+ * void in, uniform over all such deals, under the SAME world key wkey as tarok_playout_cards_det — but w names another
+ * deal than there, unless the game falls back.  The playout keys pkey, the sums, the card rule, "takes part", the
+ * read-only contract and the outputs are tarok_playout_cards_det's.  Terms as there: o0 < o1 < o2 the other seats, c_i
+ * their true hand sizes.
+ *
+ * For a card x of P the allowed set is S(x) = { i : bit 5 * o_i + class(x) of the word is clear }; the mover's own bits
+ * are ignored.  Groups: F_i = the cards with S = {i} (forced to o_i), G01 / G02 / G12 = those with two allowed seats
+ * (sizes n01, n02, n12), Q = those with all three (size q), E = those with none.
+ * Fallback: the world is exactly tarok_playout_cards_det's (the same draws, hands, team and parking) when the bits of
+ * the three other seats are all zero, when E is not empty, when some r_i = c_i - |F_i| is negative, or when Total below
+ * is 0.  The last three arise only with a word that is not the game's own (a hand-built state, a stale history, a
+ * caller's array).
+ * Counting: for a = 0..n01 (cards of G01 that go to o0) and b = 0..n02 (cards of G02 that go to o0):
+ *     s0 = r0 - a - b,  r1' = r1 - (n01 - a),  r2' = r2 - (n02 - b),
+ *     T(a, b) = C(n01, a) * C(n02, b) * C(q, s0) * C(n12 + q - s0, r1'),
+ * and T(a, b) = 0 unless 0 <= s0 <= q, r1' >= 0, r2' >= 0 (then r1' + r2' = n12 + q - s0).  The last factor sums, by
+ * Vandermonde, over how G12 and the rest of Q split between o1 and o2.  T(a, b) is the number of consistent deals with
+ * those counts and Total = sum of T the number of all consistent deals; every partial product is a count of partial
+ * deals <= 3^36 < 2^58, so 64-bit words hold them.
+ * Drawing (a, b): R = (u64)rng32(wkey, 64) << 32 | rng32(wkey, 65), u = the high 64 bits of R * Total; (a, b) is the
+ * first pair whose running sum of T exceeds u, a ascending in the outer loop, b ascending in the inner one.  (The pool
+ * has at most 36 cards: draws 0..35 and 128..163 are the walks', 64 and 65 are free.)
+ * Walks, all in ascending card number; i is the card's index in the ascending walk of ALL of P:
+ *   F_i  the card goes to o_i; no draw.
+ *   G01  running capacities (capA, capB) = (a, n01 - a): r = pick(rng32(wkey, i), capA + capB); to o0 iff r < capA, else
+ *        to o1; the receiver's capacity drops by one.          G02  the same with (b, n02 - b), to o0 or o2.
+ *   Q    stage 1, which s0 of its cards go to o0: running (k0, kq) = (s0, q): r = pick(rng32(wkey, i), kq); to o0 iff
+ *        r < k0; kq drops at every Q card, k0 when o0 takes the card.
+ *   G12 and the Q cards that did not go to o0, as ONE ascending walk: running (k1, k2) = (r1', r2'):
+ *        r = pick(rng32(wkey, 128 + i), k1 + k2); to o1 iff r < k1, else to o2.
+ * Each stage is the sequential form of a uniform subset choice given (a, b), and (a, b) is drawn in proportion to the
+ * number of deals behind it: the world is uniform over the deals that keep the hand sizes and the voids, up to the 2^-64
+ * and 2^-32 biases of the two multiply-high picks.  The team of a called king in P is 1 << declarer | 1 << (the seat that
+ * received the king), and the un-owned talon is re-parked, as in tarok_playout_cards_det.
+ *   voids  [N] u32, required: tarok_shown_voids' words, or any words of the caller's.  With every word 0 both outputs are
+ *          byte for byte those of tarok_playout_cards_det.
+ * Known leaks left: Klop's face-down talon keeps its true cards in every world; the declarer's discards count as seen.
+ * TAROK_EINVAL (before any HIP call) for a NULL env or voids array, worlds outside 1..TAROK_PLAYOUT_MAX_WORLDS, samples
+ * outside 1..TAROK_PLAYOUT_MAX_SAMPLES, seats outside 0..15 or both outputs NULL. */
+int tarok_playout_cards_voids(tarok_env *env, int worlds, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                              const uint32_t *voids, int32_t *sum_out, uint8_t *action_out, void *stream);
 
 /* A playout launch's sums as a teacher's target distribution: one row of 64 bf16 per game, for the learner's distillation
  * term (tarok_learn_chain_distill).  Per game g the kernel reads obs[g], the observation word the playouts started from:

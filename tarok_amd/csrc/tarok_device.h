@@ -608,6 +608,145 @@ __device__ __forceinline__ void redeal_unseen(Game &g, u32 mover, u64 wkey) {
     g.team = team;
 }
 
+// The trick leaders of a game replayed from its cards alone (k_observe_ref phase 1, k_shown_voids): nobody stores who
+// led trick t.  first_leader: Berac.py:15, Klop.py:26, Navadna_igra.py:70.  next_leader: the seat that led the complete
+// trick c0..c3 in, the seat that took it out — pobere_stih (Klop.py:81-94): a challenger beats the best card so far with a
+// higher card of its class, or as a tarok against a suit card (class = min(card >> 3, 4): suits 0..3, taroks 4).
+__device__ __forceinline__ u32 first_leader(u32 contract, u32 declarer) {
+    bool berac = contract == TK_BERAC || contract == TK_ODPRTI_BERAC;
+    return berac ? declarer : 0u;
+}
+__device__ __forceinline__ u32 next_leader(u32 lead, const u32 (&c)[4]) {
+    u32 w = 0, cw = c[0];
+#pragma unroll
+    for (u32 j = 1; j < 4; j++) {
+        u32 sw = min(cw >> 3, 4u), si = min(c[j] >> 3, 4u);
+        bool beats = (sw == si) ? (cw < c[j]) : (si == 4);
+        w = beats ? j : w;
+        cw = beats ? c[j] : cw;
+    }
+    return (lead + w) & 3;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Void-aware determinization (tarok_playout_cards_voids, include/tarok_env.h).
+// A void word holds bit 5 * seat + class for every (seat, class) the play so far has shown empty (k_shown_voids).
+// redeal_voids deals the unseen pool P among the other seats o0 < o1 < o2 uniformly over the deals that keep the hand
+// sizes AND give no seat a card of a class it is void in.  Every card of P has an allowed set S of seats: the cards with
+// one allowed seat are forced (F_i), those with two form G01, G02, G12, those with three Q.  The number of deals with a
+// cards of G01 and b cards of G02 on o0 is
+//     T(a, b) = C(n01, a) C(n02, b) C(q, s0) C(n12 + q - s0, r1'),   s0 = r0 - a - b,  r1' = r1 - (n01 - a),
+// r_i = c_i - |F_i| (the last factor: how G12 and the rest of Q split between o1 and o2, summed over by Vandermonde).
+// (a, b) is drawn in proportion to T from draws 64 and 65 of the world key, and each group is then dealt by the
+// sequential form of a uniform subset choice: draw i of the world key for card i of the ascending walk of P (G01, G02
+// and Q's share of o0), draw 128 + i for the split of G12 and the rest of Q between o1 and o2.
+// Binomials C(n, k), n, k <= 36, from a table in constant memory (k > n reads 0): no run-time-indexed register array.
+// The game falls back to redeal_unseen's world — the same draws, hands, team and parking — when the three other seats
+// show no void, when a card of P has no allowed seat, when some r_i < 0 or when no consistent deal exists (Total = 0);
+// the last three happen only with a void word that is not the game's own.
+// Weights are recomputed per world in registers (two passes over (a, b): Total, then the pick): no LDS.
+struct TkBinom {
+    u64 c[37][37];
+    constexpr TkBinom() : c{} {
+        for (int n = 0; n < 37; n++)
+            for (int k = 0; k <= n; k++) c[n][k] = (k == 0 || k == n) ? 1ULL : c[n - 1][k - 1] + c[n - 1][k];
+    }
+};
+#ifdef __HIPCC__
+static __constant__ const TkBinom tk_binom = TkBinom();
+__device__ __forceinline__ u64 tk_mulhi64(u64 a, u64 b) { return __umul64hi(a, b); }
+#else
+static const TkBinom tk_binom = TkBinom();
+__device__ __forceinline__ u64 tk_mulhi64(u64 a, u64 b) { return (u64)(((unsigned __int128)a * b) >> 64); }
+#endif
+// the cards of the classes whose bits are set in v (5 bits: suits 0..3, taroks)
+__device__ __forceinline__ u64 class_cards(u32 v) {
+    u32 lo = ((v & 1u) ? 0xFFu : 0u) | ((v & 2u) ? 0xFF00u : 0u) | ((v & 4u) ? 0xFF0000u : 0u) | ((v & 8u) ? 0xFF000000u : 0u);
+    u32 hi = (v & 16u) ? 0x3FFFFFu : 0u;
+    return TK_U64(lo, hi);
+}
+// T(a, b) as above; 0 outside its support.  All table indices are clamped into the table.
+__device__ __forceinline__ u64 voids_weight(u64 c01a, int n02, int n12, int q, int r0, int r1, int r2, int n01, int a, int b) {
+    int s0 = r0 - a - b, r1p = r1 - (n01 - a), r2p = r2 - (n02 - b);
+    bool ok = s0 >= 0 && s0 <= q && r1p >= 0 && r2p >= 0;
+    int s0c = ok ? s0 : 0, r1c = ok ? r1p : 0;
+    u64 t = c01a * tk_binom.c[n02][b];
+    t *= tk_binom.c[q][s0c];
+    t *= tk_binom.c[n12 + q - s0c][r1c];
+    return ok ? t : 0ULL;
+}
+__device__ __forceinline__ void redeal_voids(Game &g, u32 mover, u64 wkey, u32 voids) {
+    const u32 o0 = mover == 0 ? 1u : 0u, o1 = mover <= 1 ? 2u : 1u, o2 = mover == 3 ? 2u : 3u;
+    const u32 v0 = (voids >> (5 * o0)) & 31u, v1 = (voids >> (5 * o1)) & 31u, v2 = (voids >> (5 * o2)) & 31u;
+    const u64 h0 = hand_of(g, o0), h1 = hand_of(g, o1), h2 = hand_of(g, o2);
+    const u64 P = h0 | h1 | h2;
+    const u64 a0 = P & ~class_cards(v0), a1 = P & ~class_cards(v1), a2 = P & ~class_cards(v2);   // what each seat may hold
+    const u64 Q = a0 & a1 & a2, G01 = a0 & a1 & ~a2, G02 = a0 & a2 & ~a1, G12 = a1 & a2 & ~a0;
+    const u64 F0 = a0 & ~(a1 | a2), F1 = a1 & ~(a0 | a2), E = P & ~(a0 | a1 | a2);
+    const int n01 = popc64(G01), n02 = popc64(G02), n12 = popc64(G12), q = popc64(Q);
+    const int r0 = popc64(h0) - popc64(F0), r1 = popc64(h1) - popc64(F1), r2 = popc64(h2) - popc64(a2 & ~(a0 | a1));
+    bool plain = (v0 | v1 | v2) == 0 || E != 0 || r0 < 0 || r1 < 0 || r2 < 0 || popc64(P) > 36;  // (36: the table's last row)
+    u64 total = 0;
+    if (!plain) {
+        for (int a = 0; a <= n01; a++) {
+            const u64 ca = tk_binom.c[n01][a];
+            for (int b = 0; b <= n02; b++) total += voids_weight(ca, n02, n12, q, r0, r1, r2, n01, a, b);
+        }
+    }
+    if (plain || total == 0) { redeal_unseen(g, mover, wkey); return; }
+    const u32 klo = (u32)wkey, khi = (u32)(wkey >> 32);
+    const u64 u = tk_mulhi64(((u64)rng32(klo, khi, 64u) << 32) | (u64)rng32(klo, khi, 65u), total);
+    int sa = 0, sb = 0;
+    {   // the first (a, b), a outer and b inner, whose running sum of T exceeds u (u < Total: there is one)
+        u64 run = 0;
+        bool found = false;
+        for (int a = 0; a <= n01; a++) {
+            const u64 ca = tk_binom.c[n01][a];
+            for (int b = 0; b <= n02; b++) {
+                run += voids_weight(ca, n02, n12, q, r0, r1, r2, n01, a, b);
+                bool hit = !found && run > u;
+                sa = hit ? a : sa; sb = hit ? b : sb;
+                found = found || hit;
+            }
+        }
+    }
+    // running capacities: G01 (o0, o1), G02 (o0, o2), Q's first stage (o0's share, Q cards left), the o1 / o2 split
+    u32 c01a = (u32)sa, c01b = (u32)(n01 - sa), c02a = (u32)sb, c02b = (u32)(n02 - sb);
+    u32 k0 = (u32)(r0 - sa - sb), kq = (u32)q, k1 = (u32)(r1 - (n01 - sa)), k2 = (u32)(r2 - (n02 - sb));
+    u64 m0 = F0, m1 = F1, rest = P;
+    const u32 n = (u32)popc64(P);
+    for (u32 i = 0; i < n; i++) {
+        const u64 bit = rest & (0ULL - rest);
+        const bool g01 = (bit & G01) != 0, g02 = (bit & G02) != 0, g12 = (bit & G12) != 0, inq = (bit & Q) != 0;
+        const u32 cap = g01 ? c01a + c01b : (g02 ? c02a + c02b : kq), thr = g01 ? c01a : (g02 ? c02a : k0);
+        const bool to0 = (g01 || g02 || inq) && pick(rng32(klo, khi, i), cap) < thr;
+        const bool split = g12 || (inq && !to0);                         // the card is o1's or o2's by the second draw
+        const bool low = pick(rng32(klo, khi, 128u + i), k1 + k2) < k1;
+        const bool to1 = (g01 && !to0) || (split && low);
+        m0 |= to0 ? bit : 0ULL;
+        m1 |= to1 ? bit : 0ULL;
+        c01a -= (g01 && to0) ? 1u : 0u; c01b -= (g01 && !to0) ? 1u : 0u;
+        c02a -= (g02 && to0) ? 1u : 0u; c02b -= (g02 && !to0) ? 1u : 0u;
+        kq -= inq ? 1u : 0u; k0 -= (inq && to0) ? 1u : 0u;
+        k1 -= (split && low) ? 1u : 0u; k2 -= (split && !low) ? 1u : 0u;
+        rest ^= bit;
+    }
+    // the planes, the team of a hidden called king and the re-parked talon: redeal_unseen's
+    const u64 m2 = P & ~(m0 | m1);
+    u64 pa = ((o0 & 1) ? m0 : 0ULL) | ((o1 & 1) ? m1 : 0ULL) | ((o2 & 1) ? m2 : 0ULL);
+    u64 pb = ((o0 & 2) ? m0 : 0ULL) | ((o1 & 2) ? m1 : 0ULL) | ((o2 & 2) ? m2 : 0ULL);
+    u64 A = (g.A & ~P) | pa, B = (g.B & ~P) | pb;
+    const u64 kb = 1ULL << (g.king * 8 + 7);
+    const bool hidden = has_king(g.contract) && (P & kb) != 0;
+    const u32 got = (m0 & kb) ? o0 : ((m1 & kb) ? o1 : o2);
+    const u32 team = hidden ? ((1u << g.declarer) | (1u << got)) : g.team;
+    const u64 un = hidden ? talon_unowned(g) : 0ULL;
+    const u32 park = (u32)__builtin_ctz((~team & 15u) | 16u);
+    g.A = (A & ~un) | ((park & 1) ? un : 0ULL);
+    g.B = (B & ~un) | ((park & 2) ? un : 0ULL);
+    g.team = team;
+}
+
 // One bidding round between four Bot players (TAROK_MIX_BOT): the control flow of
 // Igra.licitacija (Igra.py:75-114) with Bot_igralec.licitiram (Igralec.py:148-152)
 // behind the player-side filter (Igralec.py:58-74).  Bids are int(Tip_igre)

@@ -347,6 +347,39 @@ class TarokVecEnv:
                                                          self._p(sum_out), self._p(action_out), self._stream()))
         return sum_out, action_out
 
+    def shown_voids(self, out=None):
+        """[N] int32 device tensor (tarok_shown_voids; the bits of a u32): bit 5 * seat + class of a game's word is set
+        iff the play so far has shown that seat to hold no card of that class (class = min(card >> 3, 4): the four suits,
+        the taroks); 0 for a game that is not in play.  Needs TarokVecEnv(history=True).  Read-only, stream-ordered."""
+        if not self.history:
+            raise ValueError("shown_voids reads the play history: TarokVecEnv(history=True)")
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.empty(self.n, dtype=torch.int32, device=self.device)
+            _native.check(self.L.tarok_shown_voids(self._h, self._p(out), self._stream()))
+        return out
+
+    def playout_cards_voids(self, worlds, samples, salt=0, seats=15, seats_per_game=None, voids=None, sum_out=None, action_out=None):
+        """playout_cards_det whose worlds honour shown voids (tarok_playout_cards_voids): every world is uniform over the
+        re-deals that keep the hand sizes and give no other seat a card of a class `voids` marks it void in.
+        voids: [N] int32 words as shown_voids() returns them (any words of the caller's are accepted; all zero gives
+        playout_cards_det's bytes); None: shown_voids() of the current positions.  Needs TarokVecEnv(history=True).
+        Everything else as for playout_cards_det; world w is another deal than there unless the game shows no void."""
+        if not self.history:
+            raise ValueError("playout_cards_voids goes with the play history: TarokVecEnv(history=True)")
+        if voids is None:
+            voids = self.shown_voids()
+        with torch.cuda.device(self.device):
+            if sum_out is None:
+                sum_out = torch.empty((self.n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=self.device)
+            if action_out is None:
+                action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
+            _native.check(self.L.tarok_playout_cards_voids(self._h, int(worlds), int(samples), int(salt) & ((1 << 64) - 1),
+                                                           int(seats), self._p(self._seat_sets(seats_per_game)),
+                                                           self._p(self._dev(voids, torch.int32, (self.n,))), self._p(sum_out),
+                                                           self._p(action_out), self._stream()))
+        return sum_out, action_out
+
     def playout_targets(self, sums, obs_words, playouts, tau, seats=15, seats_per_game=None, target_out=None):
         """A playout launch's sums as a teacher's target rows (tarok_playout_targets): target [N,64] bf16, for a game with
         a teacher the softmax over its legal cards of (the mover's sum) / (playouts * tau) at the cards' columns (tau = 0:

@@ -120,19 +120,24 @@ def evaluate_vs_policy(weights, opponent, n_games, episodes, seed=0, mix=K.MIX_B
                                                  temperature=temperature, epsilon=epsilon))
 
 
-def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None):
+def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None, voids=False):
     """_play_passes_mode with the Monte-Carlo player (TarokVecEnv.playout_cards) in the network's place: per lock-step
     one playout launch with the pass's seat set — tarok_playout_cards (open hands) for worlds=None,
     tarok_playout_cards_det (the fair player: `worlds` re-deals of the unseen cards) otherwise — whose action_out holds
     the playout player's card on its seats and the Bot's on the others, and one tarok_step that plays it.
+    voids=True (with worlds): the env keeps the play history and every lock-step runs tarok_shown_voids and
+    tarok_playout_cards_voids in tarok_playout_cards_det's place.
     inspect: as in _play_passes_mode."""
+    if voids and worlds is None:
+        raise ValueError("voids=True constrains the re-deals: give worlds= as well")
     n = int(n_games)
     scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
-    env = TarokVecEnv(n, device=device, seed=seed, mix=mix)
+    env = TarokVecEnv(n, device=device, seed=seed, mix=mix, history=bool(voids))
     try:
         with torch.cuda.device(env.device):
             actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
             sums = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=env.device)
+            words = torch.empty(n, dtype=torch.int32, device=env.device) if voids else None
         for e in range(int(episodes)):
             for p, seats in enumerate(PASS_SEATS):
                 env.reset(episode=e, clear_counters=True)
@@ -140,6 +145,9 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
                 for t in range(GAME_CARDS):
                     if worlds is None:
                         env.playout_cards(samples, salt=salt, seats=seats, sum_out=sums, action_out=actions[t])
+                    elif voids:
+                        env.playout_cards_voids(worlds, samples, salt=salt, seats=seats, voids=env.shown_voids(words), sum_out=sums,
+                                                action_out=actions[t])
                     else:
                         env.playout_cards_det(worlds, samples, salt=salt, seats=seats, sum_out=sums, action_out=actions[t])
                     env.step(actions[t], auto_reset=False)
@@ -152,7 +160,8 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     return scores
 
 
-def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None):
+def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None,
+                            voids=False):
     """evaluate_vs_bot with the open-hand Monte-Carlo player in the network's place: a strong reference player that needs
     no training.  On its seat it plays, at every move, the legal card with the best summed score over `samples` Bot
     playouts of each legal card (tarok_playout_cards; `salt` varies their draws).  The playouts see the TRUE hidden
@@ -161,7 +170,9 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
     worlds=W is the FAIR player: determinized playouts (tarok_playout_cards_det), W re-deals of the cards its seat cannot
     see and `samples` playouts of every legal card in each.  It uses only what its seat may know, so it is the honest
     fixed opponent to hold a learned policy against and a teacher the network could in principle reach.
+    voids=True (with worlds=W): the fair player also uses the voids the table has seen — its worlds give no seat a card
+    of a class it has shown to be out of (tarok_shown_voids, tarok_playout_cards_voids; the env keeps the history).
     The same five duplicate passes (PASS_SEATS) on an env of its own; returns duplicate_advantage's dict, `policy_mean`
     being the playout player's.  inspect (tests): a list that receives one dict per pass, as in _play_passes_mode."""
     return duplicate_advantage(_playout_passes(samples, n_games, episodes, seed, mix, device, salt=salt, inspect=inspect,
-                                               worlds=worlds))
+                                               worlds=worlds, voids=voids))

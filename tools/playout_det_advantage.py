@@ -4,7 +4,10 @@ alone — tests/playout_det_model.replay_pass on the CPU oracle over the five pa
 TAROK_MIX_BOT, episode 0) — so the figure in DESIGN 8.4 does not come from the code it describes.  The deals are spread
 over worker processes; the result is a function of the arguments alone.
 
-usage: playout_det_advantage.py [deals = 512] [worlds = 8] [samples = 2] [processes = 8]"""
+--voids: the void-aware player instead (tests/playout_voids_model.replay_pass: worlds that honour the voids shown so far,
+DESIGN 8.6), and beside its own figure the paired difference to the determinized player on the same deals.
+
+usage: playout_det_advantage.py [deals = 512] [worlds = 8] [samples = 2] [processes = 8] [--voids]"""
 import json
 import multiprocessing
 import os
@@ -25,22 +28,39 @@ def one_deal(args):
     return [DM.replay_pass(SEED, MIX_BOT, i, 0, seats, worlds, samples)[1] for seats in PASS_SEATS]
 
 
-def main():
-    deals = int(sys.argv[1]) if len(sys.argv) > 1 else 512
-    worlds = int(sys.argv[2]) if len(sys.argv) > 2 else 8
-    samples = int(sys.argv[3]) if len(sys.argv) > 3 else 2
-    procs = int(sys.argv[4]) if len(sys.argv) > 4 else 8
-    from oracle import oracle as O
-    O.build()
-    with multiprocessing.Pool(procs) as pool:
-        rows = pool.map(one_deal, [(i, worlds, samples) for i in range(deals)], chunksize=4)
+def one_deal_voids(args):
+    import playout_voids_model as VM
+    i, worlds, samples = args
+    return [VM.replay_pass(SEED, MIX_BOT, i, 0, seats, worlds, samples)[1] for seats in PASS_SEATS]
+
+
+def figures(rows, deals):
     scores = np.asarray(rows, np.int64).transpose(1, 0, 2)               # [5, deals, 4]
     k = np.arange(4)
     diff = scores[1 + k, :, k].T - scores[0][:, k]                       # evaluate.duplicate_advantage, in integers
     per_deal = diff.mean(axis=1)
-    out = dict(deals=deals, worlds=worlds, samples=samples, diff_sum=int(diff.sum()), advantage=float(diff.mean()),
-               stderr=float(per_deal.std(ddof=1) / np.sqrt(deals)), policy_mean=float(scores[1 + k, :, k].mean()),
-               bot_mean=float(scores[0][:, k].mean()))
+    return diff, dict(diff_sum=int(diff.sum()), advantage=float(diff.mean()), stderr=float(per_deal.std(ddof=1) / np.sqrt(deals)),
+                      policy_mean=float(scores[1 + k, :, k].mean()), bot_mean=float(scores[0][:, k].mean()))
+
+
+def main():
+    argv = [a for a in sys.argv if a != "--voids"]
+    voids = len(argv) != len(sys.argv)
+    deals = int(argv[1]) if len(argv) > 1 else 512
+    worlds = int(argv[2]) if len(argv) > 2 else 8
+    samples = int(argv[3]) if len(argv) > 3 else 2
+    procs = int(argv[4]) if len(argv) > 4 else 8
+    from oracle import oracle as O
+    O.build()
+    work = [(i, worlds, samples) for i in range(deals)]
+    with multiprocessing.Pool(procs) as pool:
+        diff, out = figures(pool.map(one_deal, work, chunksize=4), deals)
+        out = dict(dict(deals=deals, worlds=worlds, samples=samples), **out)
+        if voids:
+            vdiff, vout = figures(pool.map(one_deal_voids, work, chunksize=4), deals)
+            paired = (vdiff - diff).mean(axis=1)                         # per deal: void-aware minus determinized
+            out = dict(deals=deals, worlds=worlds, samples=samples, voids=vout, determinized=out,
+                       paired_difference=float(paired.mean()), paired_stderr=float(paired.std(ddof=1) / np.sqrt(deals)))
     print(json.dumps(out))
 
 

@@ -13,7 +13,12 @@ Each figure is the median of `runs` launches, each between two device events, af
 (W, samples) beside the open-hand launch at W * samples playouts per card — the same number of playouts and of cards —
 and prints the ratio of the two times (default output then: profiles/playout_det_times.txt).
 
-usage: playout_time.py [out.txt = profiles/playout_times.txt] [games = 65536] [samples = 16] [--worlds W]"""
+--voids (with --worlds W): the env keeps the play history, and at every position the void-aware launch
+tarok_playout_cards_voids at (W, samples) on tarok_shown_voids' words is timed beside tarok_playout_cards_det at the same
+sizes, with the ratio of the two, and tarok_shown_voids alone (default output then: profiles/playout_voids_times.txt).  On a
+fresh deal every word is 0 and every game falls back: that ratio is the overhead of the path alone.
+
+usage: playout_time.py [out.txt = profiles/playout_times.txt] [games = 65536] [samples = 16] [--worlds W] [--voids]"""
 import json
 import os
 import statistics
@@ -26,19 +31,24 @@ import torch  # noqa: E402
 from tarok_amd import TarokVecEnv, karte as K  # noqa: E402
 
 argv = list(sys.argv)
+voids = "--voids" in argv
+if voids:
+    argv.remove("--voids")
 worlds = None
 if "--worlds" in argv:
     at = argv.index("--worlds")
     worlds = int(argv[at + 1])
     del argv[at:at + 2]
-out_path = argv[1] if len(argv) > 1 else os.path.join(ROOT, "profiles", "playout_det_times.txt" if worlds else "playout_times.txt")
+out_path = argv[1] if len(argv) > 1 else os.path.join(
+    ROOT, "profiles", "playout_voids_times.txt" if voids else ("playout_det_times.txt" if worlds else "playout_times.txt"))
+assert worlds or not voids, "--voids goes with --worlds W"
 n = int(argv[2]) if len(argv) > 2 else 65536
 per_world = int(argv[3]) if len(argv) > 3 else (1 if worlds else 16)
 samples = per_world * (worlds or 1)          # playouts per card of both launches
 RUNS = 9
 assert torch.cuda.is_available(), "this tool measures on the GPU"
 
-env = TarokVecEnv(n, seed=0, mix=K.MIX_BOT)
+env = TarokVecEnv(n, seed=0, mix=K.MIX_BOT, history=voids)
 
 
 def timed_us(fn):
@@ -87,6 +97,16 @@ with torch.cuda.device(env.device):
             lines.append("  %-28s %10.1f us (%.1f, %.1f)   %12d cards   %8.2f G cards/s   %.3f x the open-hand time"
                          % ("  determinized (%d, %d)" % (worlds, per_world), dmed, dlo, dhi, total, total / (dmed * 1e-6) / 1e9, dmed / med))
             result["after_%d" % cards].update(det_us=dmed, det_over_open=dmed / med, worlds=worlds, samples_per_world=per_world)
+        if voids:
+            vw = torch.empty(n, dtype=torch.int32, device=env.device)
+            smed, slo, shi = timed_us(lambda: env.shown_voids(vw))
+            torch.cuda.synchronize()
+            shown = int((vw != 0).sum().item())
+            vmed, vlo, vhi = timed_us(lambda: env.playout_cards_voids(worlds, per_world, voids=vw, sum_out=sums, action_out=acts))
+            lines.append("  %-28s %10.1f us (%.1f, %.1f)   %12d cards   %8.2f G cards/s   %.3f x the determinized time   (%d games show a void)"
+                         % ("  void-aware (%d, %d)" % (worlds, per_world), vmed, vlo, vhi, total, total / (vmed * 1e-6) / 1e9, vmed / dmed, shown))
+            lines.append("  %-28s %10.1f us (%.1f, %.1f)" % ("  tarok_shown_voids", smed, slo, shi))
+            result["after_%d" % cards].update(voids_us=vmed, voids_over_det=vmed / dmed, shown_voids_us=smed, games_with_a_void=shown)
 text = "\n".join(lines) + "\n"
 os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
 with open(out_path, "w") as f:
