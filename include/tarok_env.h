@@ -281,6 +281,50 @@ int tarok_playout_cards(tarok_env *env, int samples, uint64_t salt, int seats, c
 int tarok_playout_cards_det(tarok_env *env, int worlds, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
                             int32_t *sum_out, uint8_t *action_out, void *stream);
 
+/* Playout-valued talon exchange: the declarer's one decision before the first card of a Tri, Dve, Ena or Solo contract —
+ * which talon group to pick up, which cards to lay down (menjaj_iz_talona: Navadna_igra.py:36-66, Igralec.py:161-171) —
+ * valued by determinized playouts.  At this moment the opened talon is shown to the whole table and the discards are
+ * the declarer's own, so the only hidden cards are the three other hands: none of tarok_playout_cards_det's leaks
+ * applies.  Exact and integer.
+ *
+ * A game TAKES PART if it waits for the exchange (TAROK_DEFER_EXCHANGE) and its declarer is in the seat set: `seats`,
+ * or seats_per_game[g] & 15 when that array is given.  For such a game: gs = the contract's group size (3, 2, 1 for
+ * Tri / Solo_tri, Dve / Solo_dve, Ena / Solo_ena), ngroups = 6 / gs, D = discard_sets, ep = the slot's episode, gidx the
+ * global game index.
+ * Candidate (i, d), i < ngroups, d < D: group i (talon cards i * gs .. i * gs + gs - 1) is picked up and the discards
+ * are the Bot's own sampler on the declarer's hand with the group: draws 68 + j, j < gs, of
+ *     ckey = game_key(seed ^ salt, gidx, 5 << 61 | (u64)ep << 28 | i << 6 | d),
+ * each among the discardable cards left (suit cards below the king, taroks II..VII), among the whole hand if fewer than
+ * gs are discardable.  Two candidates may hold the same set; they stay separate candidates.
+ * World w < worlds: the three other hands re-dealt by tarok_playout_cards_det's walk with the DECLARER as the viewer, on
+ * the game as it waits, under
+ *     wkey = game_key(seed ^ salt, gidx, 7 << 61 | (u64)ep << 28 | 63 << 22 | w)
+ * (63 in the cards-played field is never a card count: these are not the streams a card launch draws at 0 cards played).
+ * The team rule is that launch's: a called king among the three hands makes the world's team the declarer and the seat
+ * that received it; with the king in the declarer's hand or in the talon the team stays.  The whole talon, which nobody
+ * owns yet, is re-parked with the world's opponents.  The worlds do not depend on the candidate.
+ * Playout (i, d, w, k), k < samples: the candidate's exchange is applied to world w and the game played from its first
+ * card to the end by the Bot on every seat (draw 128 + q at q cards played) under
+ *     pkey = game_key(seed ^ salt, gidx, 3 << 62 | (u64)ep << 28 | 63 << 22 | (8 * i + d) << 16 | w << 10 | k);
+ * the four final scores are summed over (w, k) into sum_out[g][i * D + d][0..3].  Key tags, bits 63..61: 101 candidates,
+ * 111 worlds, 110 playouts, 100 the open-hand playouts, 000 deals.  Neither d, w nor k depends on the launch's sizes
+ * except through the row index: a launch at (W', S', D') sums a corner of one at (W >= W', S >= S', D >= D').
+ *   sum_out      [N, 6 * D, 4] i32, 16-byte aligned, or NULL.  EVERY row is written: zeros for groups >= ngroups and
+ *                for games that do not take part.
+ *   choice_out   [N] i8 and discards_out [N,3] u8 (255 beyond gs), each or NULL, EVERY row written: for a game that
+ *                takes part the candidate with the largest sum[declarer], the smallest (i, d) on ties; for a game that
+ *                waits with its declarer outside the set exactly the Bot's exchange (group 0, the sampler under the
+ *                game's own key: what tarok_exchange does without arrays); -1 and 255, 255, 255 for any other game.
+ *                tarok_exchange(choice_out, discards_out) therefore serves a mixed table in one call.
+ * Read-only on the env (as tarok_playout_cards), stream-ordered, capturable.
+ * TAROK_EINVAL (before any HIP call) for a NULL env, worlds outside 1..TAROK_PLAYOUT_MAX_WORLDS, samples outside
+ * 1..TAROK_PLAYOUT_MAX_SAMPLES, discard_sets outside 1..TAROK_EXCHANGE_MAX_SETS or seats outside 0..15.  With all three
+ * outputs NULL nothing is launched. */
+#define TAROK_EXCHANGE_MAX_SETS 8
+#define TAROK_EXCHANGE_ROWS 48          /* 6 groups x TAROK_EXCHANGE_MAX_SETS: the most rows a game's sums can have */
+int tarok_playout_exchange(tarok_env *env, int worlds, int samples, int discard_sets, uint64_t salt, int seats,
+                           const uint8_t *seats_per_game, int32_t *sum_out, int8_t *choice_out, uint8_t *discards_out, void *stream);
+
 /* Shown voids: what the play so far has told the whole table about who is out of which class of cards.  Needs an env
  * created with TAROK_HISTORY.
  *   voids_out [N] u32, one word per game: bit 5 * seat + class is set iff that seat has shown in this game that it holds

@@ -833,6 +833,27 @@ __device__ __forceinline__ void bot_exchange(Game &g, u64 key) {
     apply_exchange(g, 0, dpk & 255, (dpk >> 8) & 255, (dpk >> 16) & 255);
 }
 
+// The discards of an exchange CANDIDATE (tarok_playout_exchange, include/tarok_env.h): talon group `group` is picked up
+// and the Bot's sampler — draws 68 + j of `ckey` on the discardable cards of hand | group, the whole of it if there are
+// too few — lays down group_size cards.  Returns them packed, 8 bits each, 255 beyond group_size: what apply_exchange and
+// discards_out take.  Under the game's own key and group 0 these are bot_exchange's discards; bot_exchange keeps its own
+// copy of the loop so that every kernel that calls it compiles as before.  For a game waiting for the exchange.
+__device__ __forceinline__ u32 exchange_discards(const Game &g, u32 group, u64 ckey) {
+    u32 gs = group_size(g.contract);
+    u64 h = hand_of(g, g.declarer) | ids_mask(g.talon, (int)(group * gs), (int)gs);
+    u64 cand = h & TK_DISCARDABLE;
+    if ((u32)popc64(cand) < gs) cand = h;
+    u32 dpk = 0xFFFFFF;
+#pragma unroll
+    for (u32 j = 0; j < 3; j++)
+        if (j < gs) {
+            u32 c = kth_bit(cand, pick(rng32(ckey, 68 + j), (u32)popc64(cand)));
+            dpk = (dpk & ~(255u << (8 * j))) | (c << (8 * j));
+            cand &= ~(1ULL << c);
+        }
+    return dpk;
+}
+
 // The deal: sort the 54 cards by (random key | card id); position p of the
 // sorted order is Igra.razdeli's karte[p] (Igra.py:65-73).
 // Per-thread form: 54 keys in registers through a fixed sorting network.

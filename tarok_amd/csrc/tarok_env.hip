@@ -1501,6 +1501,116 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_det(int64_t n, u64 pseed /* seed ^ salt 
     }
 }
 
+// tarok_playout_exchange: the declarer's talon exchange valued by determinized playouts — k_playout_det's structure one
+// decision earlier.  A team of 2^lg lanes owns one game that waits for the exchange (lg >= TK_PX_MIN_LG, by k_playout's
+// rule on worlds * samples, so teams <= 16 and teams * worlds <= TK_PO_WORLD_SLOTS).  The viewer of every world is the
+// DECLARER: redeal_unseen runs on the game as it waits — plane C holds the whole talon there, so no talon card is in a
+// hand, the pool is the three other hands, and a new team re-parks all six talon cards; apply_exchange afterwards moves
+// the chosen group to the declarer and leaves the rest where the world parked it.  Dealing lanes leave (A, B, team) of
+// each world in LDS and the packed discards of each candidate (group i, set d) beside them; after ONE barrier the items
+// (i, d, w, k), ngroups * sets * worlds * samples of them, go round-robin over the team: unpack, the world's planes, the
+// candidate's exchange, the Bot's first card, playout_from.  Sums go into the team's [48][4] rows by integer LDS adds; a
+// last pass writes 6 * sets 16-byte rows and lane 0 scans for the choice.  Nothing of the env is written; no global atomics.
+#define TK_PX_MIN_LG 4
+#define TK_PX_ROWS 48                                // 6 groups x 8 discard sets
+TK_KERNEL(TK_BLOCK, 128) void k_playout_exchange(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 samples, u32 sets,
+                                                u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
+                                                const Counters *__restrict__ cnt, const u64 *__restrict__ gkey,
+                                                int4 *__restrict__ sum_out, int8_t *__restrict__ choice_out,
+                                                uint8_t *__restrict__ discards_out) {
+    TK_VGPR_TOP(128, 127);
+    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> TK_PX_MIN_LG) * TK_PX_ROWS * 4];
+    __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS];
+    __shared__ u32 world_team[TK_PO_WORLD_SLOTS];
+    __shared__ u32 cand_dpk[(TK_BLOCK >> TK_PX_MIN_LG) * TK_PX_ROWS];
+    const u32 tid = threadIdx.x, team = tid >> lg, L = 1u << lg, lane = tid & (L - 1u), teams = (u32)TK_BLOCK >> lg;
+    const int64_t g = (int64_t)blockIdx.x * teams + team;
+    for (u32 w = tid; w < teams * (TK_PX_ROWS * 4); w += TK_BLOCK) sums[w] = 0;
+    int *row = sums + team * (TK_PX_ROWS * 4);
+    u32 *cand = cand_dpk + team * TK_PX_ROWS;
+    const u32 slot0 = team * worlds;                 // the team's worlds: slots slot0 .. slot0 + worlds - 1
+    ulonglong2 a = {0, 0}, b = {0, 0};
+    u64 ebase = 0;
+    u32 declarer = 0, ncand = 0;
+    bool waiting = false, takes_part = false;
+    if (g < n) {
+        a = s01[g]; b = s23[g];
+        Game g0;
+        unpack(g0, a.x, a.y, b.x, b.y);
+        waiting = g0.phase == TK_PHASE_EXCHANGE;
+        declarer = g0.declarer;
+        if (waiting) {
+            u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+            takes_part = (set >> declarer) & 1u;
+        }
+        if (takes_part) {
+            const u32 gs = group_size(g0.contract);
+            ncand = (gs == 3 ? 2u : (gs == 2 ? 3u : 6u)) * sets;
+            ebase = (u64)cnt[g].episode << 28;
+            for (u32 w = lane; w < worlds; w += L) {
+                Game d = g0;
+                redeal_unseen(d, declarer, game_key(pseed, offset + (u64)g, (7ULL << 61) | ebase | (63ULL << 22) | (u64)w));
+                world_a[slot0 + w] = d.A; world_b[slot0 + w] = d.B; world_team[slot0 + w] = d.team;
+            }
+            for (u32 r = lane; r < ncand; r += L) {
+                u32 i = r / sets, d = r - i * sets;
+                cand[r] = exchange_discards(g0, i, game_key(pseed, offset + (u64)g, (5ULL << 61) | ebase | ((u64)i << 6) | (u64)d));
+            }
+        }
+    }
+    __syncthreads();
+    if (takes_part) {
+        const u32 per_cand = worlds * samples, items = ncand * per_cand;
+        for (u32 it = lane; it < items; it += L) {
+            u32 r = it / per_cand, rem = it - r * per_cand, w = rem / samples, k = rem - w * samples;
+            u32 i = r / sets, d = r - i * sets;
+            u64 pkey = game_key(pseed, offset + (u64)g,
+                                (3ULL << 62) | ebase | (63ULL << 22) | ((u64)(8u * i + d) << 16) | ((u64)w << 10) | (u64)k);
+            Game h;
+            unpack(h, a.x, a.y, b.x, b.y);
+            h.A = world_a[slot0 + w]; h.B = world_b[slot0 + w]; h.team = world_team[slot0 + w];
+            const u32 dpk = cand[r];
+            apply_exchange(h, i, dpk & 255, (dpk >> 8) & 255, (dpk >> 16) & 255);
+            u32 c = policy_action(pkey, 0u, legal_now(h));
+            u64 scores = playout_from(h, c, pkey, 0u);
+            atomicAdd(row + r * 4 + 0, (int)(int16_t)scores);
+            atomicAdd(row + r * 4 + 1, (int)(int16_t)(scores >> 16));
+            atomicAdd(row + r * 4 + 2, (int)(int16_t)(scores >> 32));
+            atomicAdd(row + r * 4 + 3, (int)(int16_t)(scores >> 48));
+        }
+    }
+    __syncthreads();
+    if (g >= n) return;
+    const u32 nrows = 6u * sets;                     // rows at or beyond ncand stay zero: groups the contract does not have
+    if (sum_out)
+        for (u32 r = lane; r < nrows; r += L) sum_out[g * nrows + r] = reinterpret_cast<const int4 *>(row)[r];
+    if ((choice_out || discards_out) && lane == 0) {
+        int ch = -1;
+        u32 dpk = 0xFFFFFFu;
+        if (takes_part) {                            // the first candidate at the maximum of the declarer's sums
+            u32 best = 0;
+            int top = row[declarer];
+            for (u32 r = 1; r < ncand; r++) {
+                int v = row[r * 4 + declarer];
+                if (v > top) { top = v; best = r; }
+            }
+            ch = (int)(best / sets);
+            dpk = cand[best];
+        } else if (waiting) {                        // the Bot's own exchange: group 0, its sampler under the game's key
+            Game g0;
+            unpack(g0, a.x, a.y, b.x, b.y);
+            ch = 0;
+            dpk = exchange_discards(g0, 0u, gkey[g]);
+        }
+        if (choice_out) choice_out[g] = (int8_t)ch;
+        if (discards_out) {
+            discards_out[g * 3 + 0] = (uint8_t)dpk; discards_out[g * 3 + 1] = (uint8_t)(dpk >> 8);
+            discards_out[g * 3 + 2] = (uint8_t)(dpk >> 16);
+        }
+    }
+}
+
 // tarok_shown_voids: the voids the play of every game has shown so far, one word per game (bit 5 * seat + class).  One lane
 // per game: the history bytes 0 .. played - 1 (nothing at or beyond `played` is read: those entries are stale), the trick
 // leaders replayed from the cards (first_leader / next_leader, as k_observe_ref does), and per follower card of another
@@ -3376,6 +3486,27 @@ int tarok_playout_cards_det(tarok_env *e, int worlds, int samples, uint64_t salt
     hipLaunchKernelGGL(k_playout_det, dim3((unsigned)((e->n + teams - 1) / teams)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
                        e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)samples, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt,
                        e->gkey, reinterpret_cast<int4 *>(sum_out), action_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int tarok_playout_exchange(tarok_env *e, int worlds, int samples, int discard_sets, uint64_t salt, int seats,
+                           const uint8_t *seats_per_game, int32_t *sum_out, int8_t *choice_out, uint8_t *discards_out, void *stream) {
+    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || samples < 1 || samples > TAROK_PLAYOUT_MAX_SAMPLES ||
+        discard_sets < 1 || discard_sets > TAROK_EXCHANGE_MAX_SETS || seats < 0 || seats > 15)
+        return TAROK_EINVAL;
+    if (!sum_out && !choice_out && !discards_out) return TAROK_OK;
+    HIPCHK(hipSetDevice(e->device));
+    // lanes per game: tarok_playout_cards_det's rule on worlds * samples playouts per candidate, and never fewer than 16:
+    // at most 16 teams per workgroup, whose 48 rows each are the 12 KiB the card launches use; 4 * worlds <= lanes, so
+    // the worlds of a workgroup's teams fit its TK_PO_WORLD_SLOTS slots
+    static_assert(TAROK_EXCHANGE_ROWS == TK_PX_ROWS && TAROK_EXCHANGE_MAX_SETS * 6 == TK_PX_ROWS, "6 groups x 8 sets");
+    u32 lg = TK_PX_MIN_LG;
+    while (lg < TK_PO_MAX_LG && (1 << lg) < 4 * worlds * samples) lg++;
+    int64_t teams = TK_BLOCK >> lg;
+    hipLaunchKernelGGL(k_playout_exchange, dim3((unsigned)((e->n + teams - 1) / teams)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
+                       e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)samples, (u32)discard_sets, lg, (u32)seats, seats_per_game,
+                       e->s01, e->s23, e->cnt, e->gkey, reinterpret_cast<int4 *>(sum_out), choice_out, discards_out);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }

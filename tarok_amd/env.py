@@ -347,6 +347,30 @@ class TarokVecEnv:
                                                          self._p(sum_out), self._p(action_out), self._stream()))
         return sum_out, action_out
 
+    def playout_exchange(self, worlds, samples, discard_sets=4, salt=0, seats=15, seats_per_game=None, sum_out=None,
+                         choice_out=None, discards_out=None):
+        """The declarer's talon exchange valued by determinized playouts (tarok_playout_exchange), for the games that
+        wait for it (reset(defer_exchange=True)) with their declarer in `seats` / `seats_per_game`.  Candidate (i, d):
+        talon group i with the d-th of `discard_sets` (1..8) draws of the Bot's discard sampler; every candidate is
+        played to the end `samples` times by the Bot in each of `worlds` (1..64) re-deals of the three hands the
+        declarer cannot see.  Returns (sum [N, 6 * discard_sets, 4] int32 — row i * discard_sets + d, zero rows for
+        groups the contract does not have and for games that do not take part —, choice [N] int8 and discards [N,3]
+        uint8: the first candidate at the maximum of the declarer's sums; the Bot's own exchange where a game waits
+        with its declarer outside the set; -1 and 255s elsewhere).  exchange(choice, discards) applies them — a mixed
+        table in one call.  Read-only on the env; `salt` varies the draws."""
+        with torch.cuda.device(self.device):
+            if sum_out is None:
+                sum_out = torch.empty((self.n, 6 * int(discard_sets), 4), dtype=torch.int32, device=self.device)
+            if choice_out is None:
+                choice_out = torch.empty(self.n, dtype=torch.int8, device=self.device)
+            if discards_out is None:
+                discards_out = torch.empty((self.n, 3), dtype=torch.uint8, device=self.device)
+            _native.check(self.L.tarok_playout_exchange(self._h, int(worlds), int(samples), int(discard_sets),
+                                                        int(salt) & ((1 << 64) - 1), int(seats),
+                                                        self._p(self._seat_sets(seats_per_game)), self._p(sum_out),
+                                                        self._p(choice_out), self._p(discards_out), self._stream()))
+        return sum_out, choice_out, discards_out
+
     def shown_voids(self, out=None):
         """[N] int32 device tensor (tarok_shown_voids; the bits of a u32): bit 5 * seat + class of a game's word is set
         iff the play so far has shown that seat to hold no card of that class (class = min(card >> 3, 4): the four suits,

@@ -120,16 +120,40 @@ def evaluate_vs_policy(weights, opponent, n_games, episodes, seed=0, mix=K.MIX_B
                                                  temperature=temperature, epsilon=epsilon))
 
 
-def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None, voids=False):
+def _exchange_front(env, episode, worlds, samples, exchange, salt, seats, bufs):
+    """The front end of a pass whose playout player also makes the talon exchange: reset with the exchange deferred, ONE
+    tarok_playout_exchange with the pass's seat set — its rows are the Bot's own exchange for a declarer outside the
+    set — and one tarok_exchange that applies them.  Returns the canonical lanes before the exchange if asked for."""
+    sums, choice, discards, want_start = bufs
+    env.reset(episode=episode, clear_counters=True, defer_exchange=True)
+    start = env.state() if want_start else None
+    env.playout_exchange(worlds, samples, exchange, salt=salt, seats=seats, sum_out=sums, choice_out=choice, discards_out=discards)
+    env.exchange(choice, discards)
+    return start
+
+
+def _exchange_bufs(env, n, exchange, want_start):
+    with torch.cuda.device(env.device):
+        return (torch.empty((n, 6 * int(exchange), 4), dtype=torch.int32, device=env.device),
+                torch.empty(n, dtype=torch.int8, device=env.device),
+                torch.empty((n, 3), dtype=torch.uint8, device=env.device), want_start)
+
+
+def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None, voids=False, exchange=None):
     """_play_passes_mode with the Monte-Carlo player (TarokVecEnv.playout_cards) in the network's place: per lock-step
     one playout launch with the pass's seat set — tarok_playout_cards (open hands) for worlds=None,
     tarok_playout_cards_det (the fair player: `worlds` re-deals of the unseen cards) otherwise — whose action_out holds
     the playout player's card on its seats and the Bot's on the others, and one tarok_step that plays it.
     voids=True (with worlds): the env keeps the play history and every lock-step runs tarok_shown_voids and
     tarok_playout_cards_voids in tarok_playout_cards_det's place.
+    exchange=D (with worlds): every pass starts with _exchange_front at (worlds, samples, D) — the playout player makes
+    its seat's talon exchange too; the inspected dicts then also hold choice [N] i8 and discards [N,3] u8, and `start`
+    is the state BEFORE the exchange.  None: the reset's own Bot exchange, the code path as it was.
     inspect: as in _play_passes_mode."""
     if voids and worlds is None:
         raise ValueError("voids=True constrains the re-deals: give worlds= as well")
+    if exchange is not None and worlds is None:
+        raise ValueError("exchange=D is the fair player's front end: give worlds= as well")
     n = int(n_games)
     scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
     env = TarokVecEnv(n, device=device, seed=seed, mix=mix, history=bool(voids))
@@ -138,10 +162,14 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
             actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
             sums = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=env.device)
             words = torch.empty(n, dtype=torch.int32, device=env.device) if voids else None
+        xb = _exchange_bufs(env, n, exchange, inspect is not None) if exchange is not None else None
         for e in range(int(episodes)):
             for p, seats in enumerate(PASS_SEATS):
-                env.reset(episode=e, clear_counters=True)
-                start = env.state() if inspect is not None else None
+                if xb is not None:
+                    start = _exchange_front(env, e, worlds, samples, exchange, salt, seats, xb)
+                else:
+                    env.reset(episode=e, clear_counters=True)
+                    start = env.state() if inspect is not None else None
                 for t in range(GAME_CARDS):
                     if worlds is None:
                         env.playout_cards(samples, salt=salt, seats=seats, sum_out=sums, action_out=actions[t])
@@ -155,13 +183,15 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
                 scores[p, e * n:(e + 1) * n] = ss
                 if inspect is not None:
                     inspect.append(dict(episode=e, seats=seats, start=start, actions=actions.cpu().numpy(), scores=ss.copy()))
+                    if xb is not None:
+                        inspect[-1].update(choice=xb[1].cpu().numpy(), discards=xb[2].cpu().numpy())
     finally:
         env.close()
     return scores
 
 
 def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None,
-                            voids=False):
+                            voids=False, exchange=None):
     """evaluate_vs_bot with the open-hand Monte-Carlo player in the network's place: a strong reference player that needs
     no training.  On its seat it plays, at every move, the legal card with the best summed score over `samples` Bot
     playouts of each legal card (tarok_playout_cards; `salt` varies their draws).  The playouts see the TRUE hidden
@@ -172,7 +202,51 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
     fixed opponent to hold a learned policy against and a teacher the network could in principle reach.
     voids=True (with worlds=W): the fair player also uses the voids the table has seen — its worlds give no seat a card
     of a class it has shown to be out of (tarok_shown_voids, tarok_playout_cards_voids; the env keeps the history).
+    exchange=D (with worlds=W): the fair player makes BOTH of its seat's decisions — before the first card of a game it
+    declared it picks the talon group and the discards by playouts over D discard sets per group
+    (tarok_playout_exchange at (W, samples, D)); the other declarers exchange as the Bot does.  None (the default): every
+    declarer exchanges as the Bot does, as before.
     The same five duplicate passes (PASS_SEATS) on an env of its own; returns duplicate_advantage's dict, `policy_mean`
     being the playout player's.  inspect (tests): a list that receives one dict per pass, as in _play_passes_mode."""
     return duplicate_advantage(_playout_passes(samples, n_games, episodes, seed, mix, device, salt=salt, inspect=inspect,
-                                               worlds=worlds, voids=voids))
+                                               worlds=worlds, voids=voids, exchange=exchange))
+
+
+def _exchange_passes(worlds, samples, discard_sets, n_games, episodes, seed, mix, device, salt=0, inspect=None):
+    """The five passes with the playout player making the talon exchange of its seat ONLY: _exchange_front, then the
+    Bot's card on every seat at every move (tarok_playout_cards with the empty seat set — no playout is run — and one
+    tarok_step: the card loop of evaluate_playout_vs_bot's pass 0).  inspect: one dict per pass — episode, seats, start
+    (the lanes before the exchange), choice, discards, actions, scores."""
+    n = int(n_games)
+    scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
+    env = TarokVecEnv(n, device=device, seed=seed, mix=mix)
+    try:
+        with torch.cuda.device(env.device):
+            actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
+            zeros = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=env.device)
+        xb = _exchange_bufs(env, n, discard_sets, inspect is not None)
+        for e in range(int(episodes)):
+            for p, seats in enumerate(PASS_SEATS):
+                start = _exchange_front(env, e, worlds, samples, discard_sets, salt, seats, xb)
+                for t in range(GAME_CARDS):
+                    env.playout_cards(1, seats=0, sum_out=zeros, action_out=actions[t])
+                    env.step(actions[t], auto_reset=False)
+                _, ss = env.counters()                # (the pass's one synchronisation)
+                scores[p, e * n:(e + 1) * n] = ss
+                if inspect is not None:
+                    inspect.append(dict(episode=e, seats=seats, start=start, choice=xb[1].cpu().numpy(), discards=xb[2].cpu().numpy(),
+                                        actions=actions.cpu().numpy(), scores=ss.copy()))
+    finally:
+        env.close()
+    return scores
+
+
+def evaluate_exchange_vs_bot(worlds, samples, discard_sets, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None):
+    """What is the talon exchange alone worth?  The five duplicate passes with the Bot playing EVERY card on every seat;
+    in pass 1 + k the games seat k declared get their exchange from tarok_playout_exchange at (worlds, samples,
+    discard_sets) — the talon group and discards with the best summed score over determinized playouts — and every
+    other declarer exchanges as the Bot does (group 0, random discards).  Pass 0 is the Bot everywhere: the scores of
+    evaluate_vs_bot's and evaluate_playout_vs_bot's pass 0 on the same deals.  Returns duplicate_advantage's dict,
+    `policy_mean` being that of the seat whose exchanges the playouts chose."""
+    return duplicate_advantage(_exchange_passes(worlds, samples, discard_sets, n_games, episodes, seed, mix, device, salt=salt,
+                                                inspect=inspect))

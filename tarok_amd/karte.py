@@ -69,6 +69,7 @@ DRAW_EXPLORE = 256        # the exploration coin of a play mode with epsilon > 0
 PLAYOUT_RANKS = 12        # rows of sum_out per game: a hand in play never holds more than 12 cards
 PLAYOUT_MAX_SAMPLES = 1024
 PLAYOUT_MAX_WORLDS = 64   # tarok_playout_cards_det: re-deals of the unseen cards per launch
+EXCHANGE_MAX_SETS = 8     # tarok_playout_exchange: discard sets per talon group; sum_out has 6 * discard_sets rows per game
 # tarok_shown_voids: bit VOID_SEAT_BITS * seat + class of a game's word; class = min(card >> 3, VOID_TAROK)
 VOID_SEAT_BITS = 5
 VOID_TAROK = 4            # classes 0..3 are the suits

@@ -410,7 +410,7 @@ class SelfPlay:
 
     @torch.no_grad()
     def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None, greedy=False, temperature=None, epsilon=0.0,
-                 versus_playout=None, playout_worlds=None, playout_voids=False):
+                 versus_playout=None, playout_worlds=None, playout_voids=False, playout_exchange=None):
         """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
         weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
         and on the SAME deals on every rank (seed 0, game offset 0, whatever the training env's are): the figures of
@@ -427,7 +427,11 @@ class SelfPlay:
         playout_worlds=W (with versus_playout): the second dict is the determinized player's instead (W re-deals of the
         cards its seat cannot see, `samples` playouts per card in each).  Of the two, that one is the FAIR player: it uses
         only its seat's information, so its figure is one a policy can be held against.
-        playout_voids=True (with playout_worlds): its worlds also honour the voids the table has seen."""
+        playout_voids=True (with playout_worlds): its worlds also honour the voids the table has seen.
+        playout_exchange=D (with playout_worlds): the fair player also makes its seat's talon exchange, valued by
+        playouts over D discard sets per group (evaluate_playout_vs_bot(exchange=D))."""
+        if playout_exchange is not None and playout_worlds is None:
+            raise ValueError("playout_exchange goes with playout_worlds=W")
         if playout_worlds is not None and versus_playout is None:
             raise ValueError("playout_worlds goes with versus_playout=samples")
         if playout_voids and playout_worlds is None:
@@ -451,7 +455,7 @@ class SelfPlay:
             return own
         from .evaluate import evaluate_playout_vs_bot
         return own, evaluate_playout_vs_bot(int(versus_playout), n_games, episodes, mix=mix, device=self.env.device_index,
-                                            worlds=playout_worlds, voids=bool(playout_voids))
+                                            worlds=playout_worlds, voids=bool(playout_voids), exchange=playout_exchange)
 
     def _alloc(self, T):
         n, dev = self.env.n, self.device
