@@ -386,6 +386,54 @@ int tarok_shown_voids(tarok_env *env, uint32_t *voids_out, void *stream);
 int tarok_playout_cards_voids(tarok_env *env, int worlds, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
                               const uint32_t *voids, int32_t *sum_out, uint8_t *action_out, void *stream);
 
+/* The cards of the play history as a set.  Needs an env created with TAROK_HISTORY.
+ *   played_out [N] u64, one word per game: bit c is set iff card c is among history entries 0 .. played - 1 of the slot's
+ *   current game — every card played so far, the cards of the trick on the table included; a finished game that has not
+ *   been re-dealt keeps the cards of its whole play.  Klop's talon gifts and the declarer's discards are not history
+ *   entries.  Bits 54..63 are 0.  EVERY row is written: 0 for a game that waits for the exchange, and for a slot whose
+ *   finished game has been re-dealt (its new game has played nothing; the stale entries are not read).
+ * What it is for: the packed state cannot tell the declarer's discards from the declarer's won tricks; the discards are
+ * (the declarer's pile) & ~word.
+ * Read-only on the env, stream-ordered, capturable.
+ * TAROK_EINVAL (before any HIP call) for a NULL env or array, or an env without TAROK_HISTORY. */
+int tarok_played_cards(tarok_env *env, uint64_t *played_out, void *stream);
+
+/* Determinized playouts whose worlds hide what only other seats have seen: tarok_playout_cards_det without its last two
+ * leaks.  World w of game g is drawn under the SAME world key wkey as there; the playout keys pkey, the sums, the card
+ * rule, "takes part", the read-only contract and the outputs are tarok_playout_cards_det's.  Terms as there: s the seat
+ * to move, o0 < o1 < o2 the other seats, cap_i their true hand sizes, P the union of their hands.  Three cases:
+ *
+ * Klop with tl > 0 talon cards not yet given away (they lie face down in slots 0 .. tl - 1; the winner of the next trick
+ *   gets slot tl - 1).  The pool is P plus those tl cards, walked in ascending card number; card i draws
+ *   r = pick(rng32(wkey, i), cap0 + cap1 + cap2 + capT) on the capacities left, capT = tl at the start, and goes to o0,
+ *   o1, o2 or the talon by the interval r falls into, in that order.  Then the cards that landed in the talon, in
+ *   ascending order: the j-th takes the pick(rng32(wkey, 320 + j), free slots left)-th free slot, counted from slot 0,
+ *   among slots 0 .. tl - 1.  The world is uniform over the deals that keep the three hand sizes and tl, and over the
+ *   orders of the talon's cards.  The ids of slots >= tl (given away, seen) stay.
+ * Tri, Dve, Ena, Solo_tri, Solo_dve, Solo_ena in play with s != declarer.  D = (the declarer's pile) & ~played[g]: the
+ *   cards the declarer laid down, which only the declarer saw.  If popcount(D) != the contract's group size gs, or D holds
+ *   a card that is not discardable (a king, a tarok I, XXI or the skis: the reference lays those down only when the hand
+ *   has too few others), the discards stay seen and the world is tarok_playout_cards_det's.  Otherwise the pool is
+ *   P' = P | D and E = its discardable cards; D' is a uniform gs-subset of E by the sequential form: E is walked in
+ *   ascending card number, card i draws pick(rng32(wkey, 256 + i), cards of E left, this one included) and is taken iff
+ *   the draw is below the number still to take.  P' - D' is then dealt to o0, o1, o2 by tarok_playout_cards_det's walk
+ *   (draws 0, 1, .. in ascending card order over P' - D', the true hand sizes).  In the world D' lies in the declarer's
+ *   pile.  Every D' has the same number of completions, so the world is uniform over all (discards, hands) that keep the
+ *   sizes and lay down discardable cards only.
+ * Every other game (s == declarer, Klop with tl == 0, Berac, Odprti berac, Solo_brez): the world is exactly
+ *   tarok_playout_cards_det's — the same draws, the same bytes of both outputs.
+ * Team: as in tarok_playout_cards_det (a called king is never discardable: it is in P' - D' iff it is in P).
+ * Draws under a world key: 0..41 the walk, 256..294 the discards, 320..325 the talon slots (the void-aware walk uses
+ * 0..35, 64, 65 and 128..163).
+ *   played [N] u64, required: tarok_played_cards' words (or the caller's own).
+ * Not honoured, by this launch or by tarok_playout_cards_det: the table has seen the picked-up talon group, so those
+ * cards are known to be in the declarer's hand or discards; the worlds may deal them to anybody.  That makes the worlds
+ * too wide, not too informed.  Shown voids are not combined with this launch.
+ * TAROK_EINVAL (before any HIP call) for a NULL env or played array, worlds outside 1..TAROK_PLAYOUT_MAX_WORLDS, samples
+ * outside 1..TAROK_PLAYOUT_MAX_SAMPLES, seats outside 0..15 or both outputs NULL. */
+int tarok_playout_cards_hidden(tarok_env *env, int worlds, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                               const uint64_t *played, int32_t *sum_out, uint8_t *action_out, void *stream);
+
 /* A playout launch's sums as a teacher's target distribution: one row of 64 bf16 per game, for the learner's distillation
  * term (tarok_learn_chain_distill).  Per game g the kernel reads obs[g], the observation word the playouts started from:
  * legal = its 54-bit mask, s = its seat bits, nl = min(popcount(legal), TAROK_PLAYOUT_RANKS).

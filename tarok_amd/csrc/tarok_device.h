@@ -747,6 +747,92 @@ __device__ __forceinline__ void redeal_voids(Game &g, u32 mover, u64 wkey, u32 v
     g.team = team;
 }
 
+// Determinization that also hides what only others have seen (tarok_playout_cards_hidden, include/tarok_env.h): one
+// world of the seat `mover` in which, beyond the three other hands,
+//   Klop with tl > 0: the tl talon cards nobody has been given yet join the pool, and the pool is dealt to the other
+//     seats o0 < o1 < o2 and back into the talon by one ascending walk — card i on draw i of wkey, four running
+//     capacities (the hand sizes, tl) — after which the j-th card that landed in the talon, ascending, takes the
+//     pick(rng32(wkey, 320 + j), free slots left)-th free slot of slots 0 .. tl - 1.  The ids of those slots, and the A/B/C
+//     bits of every card that moved, are rewritten (a Klop's talon card is C = 1, A = B = 0: setup_game);
+//   Tri .. Solo_ena after the exchange, mover != declarer: D = the declarer's pile without the cards of the play history
+//     (`played`: tarok_played_cards' word) are the discards.  With popcount(D) = group_size and D all discardable, the pool
+//     is P' = the three hands | D; D' = a uniform group_size-subset of E = P' & TK_DISCARDABLE by the sequential form
+//     (card i of E's ascending walk on draw 256 + i); P' - D' is dealt to o0, o1, o2 by redeal_unseen's walk (draws 0, 1,
+//     ..).  D' gets C = 1 and the declarer's A/B bits.  Otherwise the discards stay seen.
+// In every other case the pool is redeal_unseen's and so are the draws and the bytes: the one walk below with no talon
+// capacity and no discards IS that walk.  Team rule and re-parking: redeal_unseen's (the called king is never
+// discardable, so it is in P' - D' exactly when it is in a hand).  Selects only; all trip counts depend on the game alone.
+__device__ __forceinline__ void redeal_hidden(Game &g, u32 mover, u64 wkey, u64 played) {
+    const u32 o0 = mover == 0 ? 1u : 0u, o1 = mover <= 1 ? 2u : 1u, o2 = mover == 3 ? 2u : 3u;
+    const u64 h0 = hand_of(g, o0), h1 = hand_of(g, o1), h2 = hand_of(g, o2);
+    const u64 P = h0 | h1 | h2;
+    const u32 klo = (u32)wkey, khi = (u32)(wkey >> 32);
+    const u32 d = g.declarer, gs = group_size(g.contract);
+    // the discards, where they are hidden from the mover
+    const u64 dpile = seat_cards(g, d) & g.C & ~played;
+    const bool exch = has_exchange(g.contract) && g.tl != 7 && mover != d && (u32)popc64(dpile) == gs && (dpile & ~TK_DISCARDABLE) == 0;
+    const u64 D = exch ? dpile : 0ULL;
+    u64 Dn = 0;
+    {   // D': gs of the cards of E, each taken with probability (still needed) / (cards of E left)
+        u64 rest = exch ? ((P | D) & TK_DISCARDABLE) : 0ULL;
+        u32 left = (u32)popc64(rest), need = gs;
+        const u32 n = left;
+        for (u32 i = 0; i < n; i++) {
+            u64 bit = rest & (0ULL - rest);
+            u32 take = pick(rng32(klo, khi, 256u + i), left) < need ? 1u : 0u;
+            Dn |= take ? bit : 0ULL;
+            need -= take; left--;
+            rest ^= bit;
+        }
+    }
+    // Klop's talon cards that nobody owns yet
+    const u32 ntal = g.contract == TK_KLOP ? g.tl : 0u;
+    const u64 T = ids_mask(g.talon, 0, (int)ntal);
+    const u64 pool = ((P | D) & ~Dn) | T;
+    u32 cap0 = (u32)popc64(h0), cap1 = (u32)popc64(h1), cap2 = (u32)popc64(h2), total = cap0 + cap1 + cap2 + ntal;
+    u64 m0 = 0, m1 = 0, m2 = 0, rest = pool;
+    const u32 n = total;
+    for (u32 i = 0; i < n; i++) {
+        u64 bit = rest & (0ULL - rest);
+        u32 r = pick(rng32(klo, khi, i), total);
+        u32 t0 = r < cap0 ? 1u : 0u, t1 = (r >= cap0 && r < cap0 + cap1) ? 1u : 0u;
+        u32 t2 = (r >= cap0 + cap1 && r < cap0 + cap1 + cap2) ? 1u : 0u;
+        m0 |= t0 ? bit : 0ULL;
+        m1 |= t1 ? bit : 0ULL;
+        m2 |= t2 ? bit : 0ULL;
+        cap0 -= t0; cap1 -= t1; cap2 -= t2; total--;
+        rest ^= bit;
+    }
+    const u64 mT = pool & ~(m0 | m1 | m2);
+    {   // the talon's new cards take its free slots 0 .. ntal - 1
+        u64 tr = mT, ids = g.talon;
+        u32 fm = (1u << ntal) - 1u;
+        for (u32 j = 0; j < ntal; j++) {
+            u64 bit = tr & (0ULL - tr);
+            u32 card = (u32)__builtin_ctzll(bit | (1ULL << 63));
+            u32 slot = kth_bit((u64)fm, pick(rng32(klo, khi, 320u + j), (u32)__popc(fm)));
+            ids = (ids & ~(63ULL << (6 * slot))) | ((u64)card << (6 * slot));
+            fm &= ~(1u << slot);
+            tr ^= bit;
+        }
+        g.talon = ids;
+    }
+    const u64 U = P | D | T;                                             // every card whose bits may change
+    u64 sa = ((o0 & 1) ? m0 : 0ULL) | ((o1 & 1) ? m1 : 0ULL) | ((o2 & 1) ? m2 : 0ULL) | ((d & 1) ? Dn : 0ULL);
+    u64 sb = ((o0 & 2) ? m0 : 0ULL) | ((o1 & 2) ? m1 : 0ULL) | ((o2 & 2) ? m2 : 0ULL) | ((d & 2) ? Dn : 0ULL);
+    u64 A = (g.A & ~U) | sa, B = (g.B & ~U) | sb;
+    g.C = (g.C & ~U) | Dn | mT;
+    const u64 kb = 1ULL << (g.king * 8 + 7);
+    const bool hidden = has_king(g.contract) && (P & kb) != 0;           // the partner is not known at the mover's seat
+    const u32 got = (m0 & kb) ? o0 : ((m1 & kb) ? o1 : o2);
+    const u32 team = hidden ? ((1u << d) | (1u << got)) : g.team;
+    const u64 un = hidden ? talon_unowned(g) : 0ULL;
+    const u32 park = (u32)__builtin_ctz((~team & 15u) | 16u);
+    g.A = (A & ~un) | ((park & 1) ? un : 0ULL);
+    g.B = (B & ~un) | ((park & 2) ? un : 0ULL);
+    g.team = team;
+}
+
 // One bidding round between four Bot players (TAROK_MIX_BOT): the control flow of
 // Igra.licitacija (Igra.py:75-114) with Bot_igralec.licitiram (Igralec.py:148-152)
 // behind the player-side filter (Igralec.py:58-74).  Bids are int(Tip_igre)

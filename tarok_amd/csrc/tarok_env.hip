@@ -1726,6 +1726,110 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_voids(int64_t n, u64 pseed /* seed ^ sal
     }
 }
 
+// tarok_played_cards: the cards of every game's play history as one word per game (bit c: card c has been played, the
+// cards on the table included).  One lane per game: the history bytes 0 .. played - 1 (those at or beyond `played` are
+// stale and are not read).  The packed state cannot tell the declarer's discards from the declarer's won tricks — both
+// are C-plane bits with the declarer's owner bits; pile_of(declarer) & ~word are the discards.  Read-only; every row
+// written, 0 for a game that waits for the exchange.
+TK_KERNEL(TK_BLOCK, 64) void k_played_cards(int64_t n, const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
+                                           const uint8_t *__restrict__ hist, u64 *__restrict__ played_out) {
+    TK_VGPR_TOP(64, 63);
+    const int64_t i = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    Game g;
+    load_game(g, s01, s23, i);
+    const u32 plays = g.phase >= TK_PHASE_PLAY ? min(g.trick_no * 4 + g.nt, 48u) : 0u;
+    u64 m = 0;
+    for (u32 p = 0; p < plays; p++) m |= 1ULL << ((u32)hist[(int64_t)p * n + i] & 63u);
+    played_out[i] = m & TK_DECK;
+}
+
+// tarok_playout_cards_hidden: k_playout_det with worlds that also hide what only other seats have seen — Klop's face-down
+// talon and the declarer's discards (redeal_hidden under the same world key; played[g] tells the discards from the won
+// tricks).  The same structure: the dealing lanes leave one world each in LDS, one barrier, the items run playout_from.
+// A world's record is (A, B, C, talon ids, team), 36 bytes: the C plane changes where a discard or a talon card changes
+// places with a hand card, and a Klop's gifts are read from the world's ids (apply_step).
+TK_KERNEL(TK_BLOCK, 128) void k_playout_hidden(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 samples, u32 lg,
+                                              u32 seats, const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                              const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                              const u64 *__restrict__ gkey, const u64 *__restrict__ played_words,
+                                              int4 *__restrict__ sum_out, uint8_t *__restrict__ action_out) {
+    TK_VGPR_TOP(128, 127);
+    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> TK_PO_MIN_LG) * TAROK_PLAYOUT_RANKS * 4];
+    __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS], world_c[TK_PO_WORLD_SLOTS], world_ids[TK_PO_WORLD_SLOTS];
+    __shared__ u32 world_team[TK_PO_WORLD_SLOTS];
+    const u32 tid = threadIdx.x, team = tid >> lg, L = 1u << lg, lane = tid & (L - 1u), teams = (u32)TK_BLOCK >> lg;
+    const int64_t g = (int64_t)blockIdx.x * teams + team;
+    for (u32 w = tid; w < teams * (TAROK_PLAYOUT_RANKS * 4); w += TK_BLOCK) sums[w] = 0;
+    int *row = sums + team * (TAROK_PLAYOUT_RANKS * 4);
+    const u32 slot0 = team * worlds;                 // the team's worlds: slots slot0 .. slot0 + worlds - 1
+    ulonglong2 a = {0, 0}, b = {0, 0};
+    u64 legal = 0, ebase = 0;
+    u32 mover = 0, played = 0, nlegal = 0;
+    bool in_play = false, takes_part = false;
+    if (g < n) {
+        a = s01[g]; b = s23[g];
+        Game g0;
+        unpack(g0, a.x, a.y, b.x, b.y);
+        in_play = g0.phase == TK_PHASE_PLAY;
+        if (in_play) {
+            legal = legal_now(g0);
+            mover = (g0.leader + g0.nt) & 3;
+            played = g0.trick_no * 4 + g0.nt;
+            u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+            takes_part = (set >> mover) & 1u;
+        }
+        if (takes_part) {
+            nlegal = (u32)popc64(legal);
+            ebase = ((u64)cnt[g].episode << 28) | ((u64)played << 22);
+            const u64 pw = played_words[g];
+            for (u32 w = lane; w < worlds; w += L) {
+                Game d = g0;
+                redeal_hidden(d, mover, game_key(pseed, offset + (u64)g, (7ULL << 61) | ebase | (u64)w), pw);
+                world_a[slot0 + w] = d.A; world_b[slot0 + w] = d.B; world_c[slot0 + w] = d.C; world_ids[slot0 + w] = d.talon;
+                world_team[slot0 + w] = d.team;
+            }
+        }
+    }
+    __syncthreads();
+    if (takes_part) {
+        const u32 per_card = worlds * samples, items = nlegal * per_card;
+        for (u32 i = lane; i < items; i += L) {
+            u32 j = i / per_card, rem = i - j * per_card, w = rem / samples, k = rem - w * samples;
+            u32 c = kth_bit(legal, j);
+            u64 pkey = game_key(pseed, offset + (u64)g, (3ULL << 62) | ebase | ((u64)c << 16) | ((u64)w << 10) | (u64)k);
+            Game h;
+            unpack(h, a.x, a.y, b.x, b.y);
+            h.A = world_a[slot0 + w]; h.B = world_b[slot0 + w]; h.C = world_c[slot0 + w]; h.talon = world_ids[slot0 + w];
+            h.team = world_team[slot0 + w];
+            u64 scores = playout_from(h, c, pkey, played);
+            atomicAdd(row + j * 4 + 0, (int)(int16_t)scores);
+            atomicAdd(row + j * 4 + 1, (int)(int16_t)(scores >> 16));
+            atomicAdd(row + j * 4 + 2, (int)(int16_t)(scores >> 32));
+            atomicAdd(row + j * 4 + 3, (int)(int16_t)(scores >> 48));
+        }
+    }
+    __syncthreads();
+    if (g >= n) return;
+    if (sum_out)
+        for (u32 r = lane; r < TAROK_PLAYOUT_RANKS; r += L) sum_out[g * TAROK_PLAYOUT_RANKS + r] = reinterpret_cast<const int4 *>(row)[r];
+    if (action_out && lane == 0) {
+        u32 act = 255;
+        if (takes_part) {                            // the smallest rank at the maximum of the mover's sums
+            u32 best = 0;
+            int top = row[mover];
+            for (u32 j = 1; j < nlegal; j++) {
+                int v = row[j * 4 + mover];
+                if (v > top) { top = v; best = j; }
+            }
+            act = kth_bit(legal, best);
+        } else if (in_play) {
+            act = policy_action(gkey[g], played, legal);
+        }
+        action_out[g] = (uint8_t)act;
+    }
+}
+
 // tarok_playout_targets: a playout launch's sums -> one target row of 64 bf16 per game (include/tarok_env.h).  One lane per
 // game builds its row in LDS — eight zero pieces, then at most twelve 2-byte values at the legal cards' columns — and the
 // workgroup writes its 256 rows, 32 KB in a row of memory, as 16-byte pieces in lane order.  The mover's column of the twelve
@@ -3531,6 +3635,31 @@ int tarok_playout_cards_voids(tarok_env *e, int worlds, int samples, uint64_t sa
     hipLaunchKernelGGL(k_playout_voids, dim3((unsigned)((e->n + teams - 1) / teams)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
                        e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)samples, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt,
                        e->gkey, voids, reinterpret_cast<int4 *>(sum_out), action_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int tarok_played_cards(tarok_env *e, uint64_t *played_out, void *stream) {
+    if (!e || !played_out || !e->hist) return TAROK_EINVAL;             // needs a TAROK_HISTORY env
+    HIPCHK(hipSetDevice(e->device));
+    hipLaunchKernelGGL(k_played_cards, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->s01, e->s23, e->hist,
+                       (u64 *)played_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int tarok_playout_cards_hidden(tarok_env *e, int worlds, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                               const uint64_t *played, int32_t *sum_out, uint8_t *action_out, void *stream) {
+    if (!e || !played || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || samples < 1 || samples > TAROK_PLAYOUT_MAX_SAMPLES ||
+        seats < 0 || seats > 15 || (!sum_out && !action_out))
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    u32 lg = TK_PO_MIN_LG;                           // lanes per game: tarok_playout_cards_det's rule
+    while (lg < TK_PO_MAX_LG && (1 << lg) < 4 * worlds * samples) lg++;
+    int64_t teams = TK_BLOCK >> lg;
+    hipLaunchKernelGGL(k_playout_hidden, dim3((unsigned)((e->n + teams - 1) / teams)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
+                       e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)samples, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt,
+                       e->gkey, (const u64 *)played, reinterpret_cast<int4 *>(sum_out), action_out);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }

@@ -404,6 +404,39 @@ class TarokVecEnv:
                                                            self._p(action_out), self._stream()))
         return sum_out, action_out
 
+    def played_cards(self, out=None):
+        """[N] int64 device tensor (tarok_played_cards; the bits of a u64): bit c of a game's word is set iff card c is in
+        the play history of the slot's current game, the cards on the table included; 0 for a game that waits for the
+        exchange or has just been re-dealt.  Needs TarokVecEnv(history=True).  Read-only, stream-ordered."""
+        if not self.history:
+            raise ValueError("played_cards reads the play history: TarokVecEnv(history=True)")
+        with torch.cuda.device(self.device):
+            if out is None:
+                out = torch.empty(self.n, dtype=torch.int64, device=self.device)
+            _native.check(self.L.tarok_played_cards(self._h, self._p(out), self._stream()))
+        return out
+
+    def playout_cards_hidden(self, worlds, samples, salt=0, seats=15, seats_per_game=None, played=None, sum_out=None, action_out=None):
+        """playout_cards_det whose worlds also re-deal what only other seats have seen (tarok_playout_cards_hidden): in a
+        Klop the face-down talon cards not yet given away, in Tri .. Solo_ena the declarer's discards when another seat
+        is to move.  Where nothing more is hidden the bytes are playout_cards_det's.
+        played: [N] int64 words as played_cards() returns them; None: played_cards() of the current positions.  Needs
+        TarokVecEnv(history=True).  Everything else as for playout_cards_det."""
+        if not self.history:
+            raise ValueError("playout_cards_hidden goes with the play history: TarokVecEnv(history=True)")
+        if played is None:
+            played = self.played_cards()
+        with torch.cuda.device(self.device):
+            if sum_out is None:
+                sum_out = torch.empty((self.n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=self.device)
+            if action_out is None:
+                action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
+            _native.check(self.L.tarok_playout_cards_hidden(self._h, int(worlds), int(samples), int(salt) & ((1 << 64) - 1),
+                                                            int(seats), self._p(self._seat_sets(seats_per_game)),
+                                                            self._p(self._dev(played, torch.int64, (self.n,))), self._p(sum_out),
+                                                            self._p(action_out), self._stream()))
+        return sum_out, action_out
+
     def playout_targets(self, sums, obs_words, playouts, tau, seats=15, seats_per_game=None, target_out=None):
         """A playout launch's sums as a teacher's target rows (tarok_playout_targets): target [N,64] bf16, for a game with
         a teacher the softmax over its legal cards of (the mover's sum) / (playouts * tau) at the cards' columns (tau = 0:

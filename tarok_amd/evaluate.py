@@ -139,29 +139,37 @@ def _exchange_bufs(env, n, exchange, want_start):
                 torch.empty((n, 3), dtype=torch.uint8, device=env.device), want_start)
 
 
-def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None, voids=False, exchange=None):
+def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None, voids=False, exchange=None,
+                    hidden=False):
     """_play_passes_mode with the Monte-Carlo player (TarokVecEnv.playout_cards) in the network's place: per lock-step
     one playout launch with the pass's seat set — tarok_playout_cards (open hands) for worlds=None,
     tarok_playout_cards_det (the fair player: `worlds` re-deals of the unseen cards) otherwise — whose action_out holds
     the playout player's card on its seats and the Bot's on the others, and one tarok_step that plays it.
     voids=True (with worlds): the env keeps the play history and every lock-step runs tarok_shown_voids and
     tarok_playout_cards_voids in tarok_playout_cards_det's place.
+    hidden=True (with worlds, not with voids): the env keeps the play history and every lock-step runs tarok_played_cards
+    and tarok_playout_cards_hidden in tarok_playout_cards_det's place.
     exchange=D (with worlds): every pass starts with _exchange_front at (worlds, samples, D) — the playout player makes
     its seat's talon exchange too; the inspected dicts then also hold choice [N] i8 and discards [N,3] u8, and `start`
     is the state BEFORE the exchange.  None: the reset's own Bot exchange, the code path as it was.
     inspect: as in _play_passes_mode."""
     if voids and worlds is None:
         raise ValueError("voids=True constrains the re-deals: give worlds= as well")
+    if hidden and worlds is None:
+        raise ValueError("hidden=True widens the re-deals: give worlds= as well")
+    if hidden and voids:
+        raise ValueError("hidden=True is not built together with voids=True: give one of the two")
     if exchange is not None and worlds is None:
         raise ValueError("exchange=D is the fair player's front end: give worlds= as well")
     n = int(n_games)
     scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
-    env = TarokVecEnv(n, device=device, seed=seed, mix=mix, history=bool(voids))
+    env = TarokVecEnv(n, device=device, seed=seed, mix=mix, history=bool(voids or hidden))
     try:
         with torch.cuda.device(env.device):
             actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
             sums = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=env.device)
             words = torch.empty(n, dtype=torch.int32, device=env.device) if voids else None
+            pwords = torch.empty(n, dtype=torch.int64, device=env.device) if hidden else None
         xb = _exchange_bufs(env, n, exchange, inspect is not None) if exchange is not None else None
         for e in range(int(episodes)):
             for p, seats in enumerate(PASS_SEATS):
@@ -176,6 +184,9 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
                     elif voids:
                         env.playout_cards_voids(worlds, samples, salt=salt, seats=seats, voids=env.shown_voids(words), sum_out=sums,
                                                 action_out=actions[t])
+                    elif hidden:
+                        env.playout_cards_hidden(worlds, samples, salt=salt, seats=seats, played=env.played_cards(pwords),
+                                                 sum_out=sums, action_out=actions[t])
                     else:
                         env.playout_cards_det(worlds, samples, salt=salt, seats=seats, sum_out=sums, action_out=actions[t])
                     env.step(actions[t], auto_reset=False)
@@ -191,7 +202,7 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
 
 
 def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None,
-                            voids=False, exchange=None):
+                            voids=False, exchange=None, hidden=False):
     """evaluate_vs_bot with the open-hand Monte-Carlo player in the network's place: a strong reference player that needs
     no training.  On its seat it plays, at every move, the legal card with the best summed score over `samples` Bot
     playouts of each legal card (tarok_playout_cards; `salt` varies their draws).  The playouts see the TRUE hidden
@@ -202,6 +213,9 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
     fixed opponent to hold a learned policy against and a teacher the network could in principle reach.
     voids=True (with worlds=W): the fair player also uses the voids the table has seen — its worlds give no seat a card
     of a class it has shown to be out of (tarok_shown_voids, tarok_playout_cards_voids; the env keeps the history).
+    hidden=True (with worlds=W, not with voids=True): the fair player's worlds also re-deal what only other seats have
+    seen — Klop's face-down talon and the declarer's discards (tarok_played_cards, tarok_playout_cards_hidden; the env
+    keeps the history).  It composes with exchange=D, which runs before the first card.
     exchange=D (with worlds=W): the fair player makes BOTH of its seat's decisions — before the first card of a game it
     declared it picks the talon group and the discards by playouts over D discard sets per group
     (tarok_playout_exchange at (W, samples, D)); the other declarers exchange as the Bot does.  None (the default): every
@@ -209,7 +223,7 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
     The same five duplicate passes (PASS_SEATS) on an env of its own; returns duplicate_advantage's dict, `policy_mean`
     being the playout player's.  inspect (tests): a list that receives one dict per pass, as in _play_passes_mode."""
     return duplicate_advantage(_playout_passes(samples, n_games, episodes, seed, mix, device, salt=salt, inspect=inspect,
-                                               worlds=worlds, voids=voids, exchange=exchange))
+                                               worlds=worlds, voids=voids, exchange=exchange, hidden=hidden))
 
 
 def _exchange_passes(worlds, samples, discard_sets, n_games, episodes, seed, mix, device, salt=0, inspect=None):

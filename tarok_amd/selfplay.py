@@ -266,7 +266,10 @@ class SelfPlay:
     teacher).  distill_coef = 0 with a teacher measures the term without acting on it.  teacher=None: nothing changes.
     teacher = dict(..., worlds=W >= 1, voids=True): the rows come from the void-aware worlds — tarok_shown_voids, then
     tarok_playout_cards_voids, then tarok_playout_targets, still one stream-ordered chain inside the captured rollout.
-    The env must keep the play history (TarokVecEnv(history=True))."""
+    The env must keep the play history (TarokVecEnv(history=True)).
+    teacher = dict(..., worlds=W >= 1, hidden=True): the rows come from worlds that also re-deal Klop's face-down talon and
+    the declarer's discards — tarok_played_cards, then tarok_playout_cards_hidden, then tarok_playout_targets, recorded
+    the same way.  Needs the play history too; not together with voids=True."""
 
     def __init__(self, env, hidden=256, lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.01, reward_scale=1.0 / 70.0, seed=0,
                  use_graph=True, fused=None, fused_loss=None, fused_step=None, fused_learner=None, max_grad_norm=1.0,
@@ -282,11 +285,12 @@ class SelfPlay:
                 raise ValueError("learner_seats: a seat set 0..15 or a [N] uint8 tensor of sets")
         self.teacher, self.distill_coef = None, float(distill_coef)
         if teacher is not None:
-            unknown = set(teacher) - {"worlds", "samples", "tau", "every", "salt", "voids"}
+            unknown = set(teacher) - {"worlds", "samples", "tau", "every", "salt", "voids", "hidden"}
             if unknown or "samples" not in teacher:
                 raise ValueError("teacher: dict(worlds=W, samples=S, tau=tau, every=k, salt=...), samples required; unknown keys %s" % sorted(unknown))
             t = dict(worlds=int(teacher.get("worlds", 0)), samples=int(teacher["samples"]), tau=float(teacher.get("tau", 1.0)),
-                     every=int(teacher.get("every", 1)), salt=int(teacher.get("salt", 0)), voids=bool(teacher.get("voids", False)))
+                     every=int(teacher.get("every", 1)), salt=int(teacher.get("salt", 0)), voids=bool(teacher.get("voids", False)),
+                     hidden=bool(teacher.get("hidden", False)))
             if not (0 <= t["worlds"] <= K.PLAYOUT_MAX_WORLDS and 1 <= t["samples"] <= K.PLAYOUT_MAX_SAMPLES and t["every"] >= 1
                     and 0.0 <= t["tau"] < float("inf")):
                 raise ValueError("teacher: worlds 0..%d, samples 1..%d, tau >= 0 and finite, every >= 1"
@@ -295,6 +299,12 @@ class SelfPlay:
                 raise ValueError("teacher: voids=True constrains the re-deals, so it goes with worlds >= 1")
             if t["voids"] and not env.history:
                 raise ValueError("teacher: voids=True reads the play history: TarokVecEnv(history=True)")
+            if t["hidden"] and not t["worlds"]:
+                raise ValueError("teacher: hidden=True widens the re-deals, so it goes with worlds >= 1")
+            if t["hidden"] and t["voids"]:
+                raise ValueError("teacher: hidden=True is not built together with voids=True: give one of the two")
+            if t["hidden"] and not env.history:
+                raise ValueError("teacher: hidden=True reads the play history: TarokVecEnv(history=True)")
             self.teacher = t
         elif distill_coef:
             raise ValueError("distill_coef weighs the playout teacher's term: pass teacher= as well")
@@ -410,7 +420,8 @@ class SelfPlay:
 
     @torch.no_grad()
     def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None, greedy=False, temperature=None, epsilon=0.0,
-                 versus_playout=None, playout_worlds=None, playout_voids=False, playout_exchange=None):
+                 versus_playout=None, playout_worlds=None, playout_voids=False, playout_exchange=None,
+                 playout_hidden=False):
         """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
         weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
         and on the SAME deals on every rank (seed 0, game offset 0, whatever the training env's are): the figures of
@@ -428,6 +439,8 @@ class SelfPlay:
         cards its seat cannot see, `samples` playouts per card in each).  Of the two, that one is the FAIR player: it uses
         only its seat's information, so its figure is one a policy can be held against.
         playout_voids=True (with playout_worlds): its worlds also honour the voids the table has seen.
+        playout_hidden=True (with playout_worlds, not with playout_voids): its worlds also re-deal Klop's face-down talon
+        and the declarer's discards (evaluate_playout_vs_bot(hidden=True)).
         playout_exchange=D (with playout_worlds): the fair player also makes its seat's talon exchange, valued by
         playouts over D discard sets per group (evaluate_playout_vs_bot(exchange=D))."""
         if playout_exchange is not None and playout_worlds is None:
@@ -436,6 +449,10 @@ class SelfPlay:
             raise ValueError("playout_worlds goes with versus_playout=samples")
         if playout_voids and playout_worlds is None:
             raise ValueError("playout_voids goes with playout_worlds=W")
+        if playout_hidden and playout_worlds is None:
+            raise ValueError("playout_hidden goes with playout_worlds=W")
+        if playout_hidden and playout_voids:
+            raise ValueError("playout_hidden is not built together with playout_voids: give one of the two")
         if versus_playout is not None and opponent is not None:
             raise ValueError("versus_playout compares against the Bot: give it without opponent=")
         if greedy and temperature:
@@ -455,7 +472,8 @@ class SelfPlay:
             return own
         from .evaluate import evaluate_playout_vs_bot
         return own, evaluate_playout_vs_bot(int(versus_playout), n_games, episodes, mix=mix, device=self.env.device_index,
-                                            worlds=playout_worlds, voids=bool(playout_voids), exchange=playout_exchange)
+                                            worlds=playout_worlds, voids=bool(playout_voids), exchange=playout_exchange,
+                                            hidden=bool(playout_hidden))
 
     def _alloc(self, T):
         n, dev = self.env.n, self.device
@@ -476,6 +494,7 @@ class SelfPlay:
             self._teach_sums = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=dev)
             self._teach_act = torch.empty(n, dtype=torch.uint8, device=dev)
             self._teach_voids = torch.empty(n, dtype=torch.int32, device=dev) if self.teacher["voids"] else None
+            self._teach_played = torch.empty(n, dtype=torch.int64, device=dev) if self.teacher["hidden"] else None
         self._graph = None
 
     def _teach(self, t):
@@ -485,6 +504,9 @@ class SelfPlay:
         if tc["voids"]:
             env.playout_cards_voids(tc["worlds"], tc["samples"], salt=tc["salt"], seats_per_game=self._seats,
                                     voids=env.shown_voids(self._teach_voids), sum_out=self._teach_sums, action_out=self._teach_act)
+        elif tc["hidden"]:
+            env.playout_cards_hidden(tc["worlds"], tc["samples"], salt=tc["salt"], seats_per_game=self._seats,
+                                     played=env.played_cards(self._teach_played), sum_out=self._teach_sums, action_out=self._teach_act)
         elif tc["worlds"]:
             env.playout_cards_det(tc["worlds"], tc["samples"], salt=tc["salt"], seats_per_game=self._seats, sum_out=self._teach_sums,
                                   action_out=self._teach_act)

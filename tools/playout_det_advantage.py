@@ -7,7 +7,10 @@ over worker processes; the result is a function of the arguments alone.
 --voids: the void-aware player instead (tests/playout_voids_model.replay_pass: worlds that honour the voids shown so far,
 DESIGN 8.6), and beside its own figure the paired difference to the determinized player on the same deals.
 
-usage: playout_det_advantage.py [deals = 512] [worlds = 8] [samples = 2] [processes = 8] [--voids]"""
+--hidden: the player whose worlds also re-deal Klop's face-down talon and the declarer's discards instead
+(tests/playout_hidden_model.replay_pass), with the same paired difference.
+
+usage: playout_det_advantage.py [deals = 512] [worlds = 8] [samples = 2] [processes = 8] [--voids | --hidden]"""
 import json
 import multiprocessing
 import os
@@ -34,6 +37,12 @@ def one_deal_voids(args):
     return [VM.replay_pass(SEED, MIX_BOT, i, 0, seats, worlds, samples)[1] for seats in PASS_SEATS]
 
 
+def one_deal_hidden(args):
+    import playout_hidden_model as HM
+    i, worlds, samples = args
+    return [HM.replay_pass(SEED, MIX_BOT, i, 0, seats, worlds, samples)[1] for seats in PASS_SEATS]
+
+
 def figures(rows, deals):
     scores = np.asarray(rows, np.int64).transpose(1, 0, 2)               # [5, deals, 4]
     k = np.arange(4)
@@ -44,8 +53,9 @@ def figures(rows, deals):
 
 
 def main():
-    argv = [a for a in sys.argv if a != "--voids"]
-    voids = len(argv) != len(sys.argv)
+    argv = [a for a in sys.argv if a not in ("--voids", "--hidden")]
+    voids, hidden = "--voids" in sys.argv, "--hidden" in sys.argv
+    assert not (voids and hidden), "--voids or --hidden, not both"
     deals = int(argv[1]) if len(argv) > 1 else 512
     worlds = int(argv[2]) if len(argv) > 2 else 8
     samples = int(argv[3]) if len(argv) > 3 else 2
@@ -60,6 +70,11 @@ def main():
             vdiff, vout = figures(pool.map(one_deal_voids, work, chunksize=4), deals)
             paired = (vdiff - diff).mean(axis=1)                         # per deal: void-aware minus determinized
             out = dict(deals=deals, worlds=worlds, samples=samples, voids=vout, determinized=out,
+                       paired_difference=float(paired.mean()), paired_stderr=float(paired.std(ddof=1) / np.sqrt(deals)))
+        if hidden:
+            hdiff, hout = figures(pool.map(one_deal_hidden, work, chunksize=4), deals)
+            paired = (hdiff - diff).mean(axis=1)                         # per deal: hidden-aware minus determinized
+            out = dict(deals=deals, worlds=worlds, samples=samples, hidden=hout, determinized=out,
                        paired_difference=float(paired.mean()), paired_stderr=float(paired.std(ddof=1) / np.sqrt(deals)))
     print(json.dumps(out))
 

@@ -18,7 +18,11 @@ tarok_playout_cards_voids at (W, samples) on tarok_shown_voids' words is timed b
 sizes, with the ratio of the two, and tarok_shown_voids alone (default output then: profiles/playout_voids_times.txt).  On a
 fresh deal every word is 0 and every game falls back: that ratio is the overhead of the path alone.
 
-usage: playout_time.py [out.txt = profiles/playout_times.txt] [games = 65536] [samples = 16] [--worlds W] [--voids]"""
+--hidden (with --worlds W): the env keeps the play history, and at every position tarok_playout_cards_hidden at
+(W, samples) on tarok_played_cards' words is timed beside tarok_playout_cards_det, with the ratio, and tarok_played_cards
+alone (default output then: profiles/playout_hidden_times.txt).
+
+usage: playout_time.py [out.txt = profiles/playout_times.txt] [games = 65536] [samples = 16] [--worlds W] [--voids | --hidden]"""
 import json
 import os
 import statistics
@@ -34,21 +38,25 @@ argv = list(sys.argv)
 voids = "--voids" in argv
 if voids:
     argv.remove("--voids")
+hidden = "--hidden" in argv
+if hidden:
+    argv.remove("--hidden")
 worlds = None
 if "--worlds" in argv:
     at = argv.index("--worlds")
     worlds = int(argv[at + 1])
     del argv[at:at + 2]
 out_path = argv[1] if len(argv) > 1 else os.path.join(
-    ROOT, "profiles", "playout_voids_times.txt" if voids else ("playout_det_times.txt" if worlds else "playout_times.txt"))
-assert worlds or not voids, "--voids goes with --worlds W"
+    ROOT, "profiles", "playout_hidden_times.txt" if hidden else "playout_voids_times.txt" if voids else ("playout_det_times.txt" if worlds else "playout_times.txt"))
+assert worlds or not (voids or hidden), "--voids and --hidden go with --worlds W"
+assert not (voids and hidden), "--voids or --hidden, not both"
 n = int(argv[2]) if len(argv) > 2 else 65536
 per_world = int(argv[3]) if len(argv) > 3 else (1 if worlds else 16)
 samples = per_world * (worlds or 1)          # playouts per card of both launches
 RUNS = 9
 assert torch.cuda.is_available(), "this tool measures on the GPU"
 
-env = TarokVecEnv(n, seed=0, mix=K.MIX_BOT, history=voids)
+env = TarokVecEnv(n, seed=0, mix=K.MIX_BOT, history=voids or hidden)
 
 
 def timed_us(fn):
@@ -107,6 +115,14 @@ with torch.cuda.device(env.device):
                          % ("  void-aware (%d, %d)" % (worlds, per_world), vmed, vlo, vhi, total, total / (vmed * 1e-6) / 1e9, vmed / dmed, shown))
             lines.append("  %-28s %10.1f us (%.1f, %.1f)" % ("  tarok_shown_voids", smed, slo, shi))
             result["after_%d" % cards].update(voids_us=vmed, voids_over_det=vmed / dmed, shown_voids_us=smed, games_with_a_void=shown)
+        if hidden:
+            pw = torch.empty(n, dtype=torch.int64, device=env.device)
+            smed, slo, shi = timed_us(lambda: env.played_cards(pw))
+            hmed, hlo, hhi = timed_us(lambda: env.playout_cards_hidden(worlds, per_world, played=pw, sum_out=sums, action_out=acts))
+            lines.append("  %-28s %10.1f us (%.1f, %.1f)   %12d cards   %8.2f G cards/s   %.3f x the determinized time"
+                         % ("  hidden-aware (%d, %d)" % (worlds, per_world), hmed, hlo, hhi, total, total / (hmed * 1e-6) / 1e9, hmed / dmed))
+            lines.append("  %-28s %10.1f us (%.1f, %.1f)" % ("  tarok_played_cards", smed, slo, shi))
+            result["after_%d" % cards].update(hidden_us=hmed, hidden_over_det=hmed / dmed, played_cards_us=smed)
 text = "\n".join(lines) + "\n"
 os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
 with open(out_path, "w") as f:
