@@ -434,6 +434,62 @@ int tarok_played_cards(tarok_env *env, uint64_t *played_out, void *stream);
 int tarok_playout_cards_hidden(tarok_env *env, int worlds, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
                                const uint64_t *played, int32_t *sum_out, uint8_t *action_out, void *stream);
 
+/* Playout-valued bidding, part 1: every bid of every seat valued by determinized playouts, BEFORE tarok_reset.  Read-only
+ * on the env; the env's games are not read at all.  The game valued is the one tarok_reset(env, episode, deals, ...)
+ * would deal: row g of deals [N,54] (validated as tarok_reset validates it; an invalid row gives all-zero sums) or, with
+ * deals == NULL, the device's own deal under game_key(seed, gidx, episode), gidx = game_offset + g.
+ *
+ * Rows (TAROK_BID_ROWS = 20 per viewer): 0 Klop; 1 + 4 (c - 1) + k for contract c = Tri 1, Dve 2, Ena 3 with the king of
+ * suit k = 0..3 called (rows 1..12); 13, 14, 15 Solo_tri, Solo_dve, Solo_ena; 16 Berac; 17 Solo_brez; 18 Odprti_berac;
+ * 19 reserved, always 0.  A row is played iff bit `code` of `contracts` is set (the contract codes above; int(Tip_igre) /
+ * 10); a row that is not played holds 0.
+ * Viewers: seat v takes part in game g iff bit v of the seat set is set (`seats`, or seats_per_game[g] & 15).
+ * World (v, w), w < worlds: the 42 cards v does not hold are dealt again.  o0 < o1 < o2 the other seats; capacities 12,
+ *   12, 12 and 6 for the talon.  The pool is walked in ascending card number; card i draws pick(rng32(wkey, i), cap0 +
+ *   cap1 + cap2 + capT) on the capacities as they stand and goes to o0 / o1 / o2 / the talon by its interval.  The talon's
+ *   cards then take slots: the j-th of them, ascending, takes the pick(rng32(wkey, 320 + j), free slots left)-th free slot
+ *   of 0..5 (tarok_playout_cards_hidden's Klop walk at tl = 6).
+ *     wkey = game_key(seed ^ salt, gidx, 2 << 61 | (u64)episode << 28 | v << 6 | w)
+ *   Worlds depend on neither the row nor the launch's sizes.
+ * Playout (v, r, w, k), k < samples: the game of world w's four hands and talon with the row's contract, declarer v (Klop:
+ *   declarer 0) and the row's king; partner and parking seat by the WORLD's hands (a called king in the talon or in v's
+ *   hand: v plays alone).  For Tri .. Solo_ena the Bot's exchange under the playout key (group 0, draws 68 + j); then all
+ *   cards by the Bot on every seat, draw 128 + q at q cards played; a Berac that ends early is scored where it ends.
+ *     pkey = game_key(seed ^ salt, gidx, 3 << 61 | (u64)episode << 28 | v << 26 | r << 21 | w << 15 | k)
+ *   The VIEWER's final score is added to sum_out[g][v][r].
+ * sum_out [N,4,TAROK_BID_ROWS] i32, 16-byte aligned; EVERY row is written (zeros for seats outside the set, rows outside
+ * `contracts` and row 19).  A launch at (W', S') sums a corner of one at (W >= W', S >= S').  With sum_out == NULL nothing
+ * is launched.  The first call allocates 40 bytes per game, which the env keeps (not capturable in a graph; later calls
+ * are).
+ * TAROK_EINVAL (before any HIP call) for a NULL env, worlds outside 1..TAROK_PLAYOUT_MAX_WORLDS, samples outside
+ * 1..TAROK_PLAYOUT_MAX_SAMPLES, contracts outside 1..TAROK_BID_ALL_CONTRACTS or seats outside 0..15. */
+#define TAROK_BID_ROWS 20
+#define TAROK_BID_DEFAULT_CONTRACTS 0x00F /* Klop, Tri, Dve, Ena: the Bot's own range */
+#define TAROK_BID_ALL_CONTRACTS 0x3FF
+int tarok_playout_bids(tarok_env *env, uint32_t episode, const uint8_t *deals, int worlds, int samples, int contracts, uint64_t salt,
+                       int seats, const uint8_t *seats_per_game, int32_t *sum_out, void *stream);
+
+/* Playout-valued bidding, part 2: the bidding round (Igra.licitacija, Igra.py:75-114) of every game on the device, under
+ * key = game_key(seed, gidx, episode): seats 1, 2, 3 over a floor of Tri; seat 0's forced call (nobody bid: at least Klop)
+ * or priority call; re-bidding rounds with seat 0 asked last and the holder allowed to stand, cut after 8 rounds.  Every
+ * call licitiram(seat, min_igra, obvezno, prednost) increments the call counter n.
+ * A seat OUTSIDE the set answers as the Bot: draw 72 + n (Naprej 1/2, Tri / Dve / Ena 1/6 each) behind the player-side
+ *   filter.
+ * A seat v INSIDE the set answers from S(r) = sums[g][v][r] (tarok_playout_bids' rows), bids b = 10 * code:
+ *   candidates = the rows of the contracts in `contracts` with b >= 10 and b > min_igra (b >= min_igra with prednost);
+ *   best = the candidate with the largest S, the lowest row on ties.
+ *   Without obvezno: b(best) if a candidate exists and S(best) > (int64) threshold * playouts, else Naprej.
+ *   With obvezno = o: stand = the largest S over the rows of contract o / 10; b(best) if a candidate exists, S(best) > stand
+ *   and S(best) > threshold * playouts, else o.
+ * contract_out / declarer_out / king_out [N] i8 are what tarok_reset takes, EVERY row written: the final contract, the
+ * holder (0 for Klop), and for Tri / Dve / Ena the king: the suit of the declarer's largest S among that contract's four
+ * rows (lowest suit on ties) for a declarer in the set, pick(rng32(key, 67), 4) for a Bot declarer; 0 for every other
+ * contract.  With seats = 0 and no seats_per_game the outputs are exactly TAROK_MIX_BOT's, and sums may be NULL.
+ * TAROK_EINVAL (before any HIP call) for a NULL env, playouts < 1, contracts outside 1..TAROK_BID_ALL_CONTRACTS, seats
+ * outside 0..15, sums == NULL with a non-empty set, or all three outputs NULL. */
+int tarok_bid_round(tarok_env *env, uint32_t episode, const int32_t *sums, int playouts, int threshold, int contracts, int seats,
+                    const uint8_t *seats_per_game, int8_t *contract_out, int8_t *declarer_out, int8_t *king_out, void *stream);
+
 /* A playout launch's sums as a teacher's target distribution: one row of 64 bf16 per game, for the learner's distillation
  * term (tarok_learn_chain_distill).  Per game g the kernel reads obs[g], the observation word the playouts started from:
  * legal = its 54-bit mask, s = its seat bits, nl = min(popcount(legal), TAROK_PLAYOUT_RANKS).

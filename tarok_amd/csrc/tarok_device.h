@@ -987,3 +987,121 @@ __device__ __forceinline__ void deal_wave(u32 klo, u32 khi, u64 &h0, u64 &h1, u6
     }
     talon36 = t;
 }
+
+// ---------------------------------------------------------------------------
+// Playout-valued bidding (tarok_playout_bids / tarok_bid_round, include/tarok_env.h)
+// ---------------------------------------------------------------------------
+// A viewer's 19 options, one row each: 0 Klop; 1 + 4 (c - 1) + k contract c = Tri, Dve, Ena with suit k called; 13 .. 18
+// Solo_tri .. Odprti_berac; row 19 is padding.
+#define TK_BID_ROWS 20
+#define TK_BID_OPTIONS 19
+__device__ __forceinline__ u32 bid_row_contract(u32 r) { return r == 0 ? 0u : (r <= 12 ? 1u + ((r - 1u) >> 2) : r - 9u); }
+__device__ __forceinline__ u32 bid_row_king(u32 r) { return (r >= 1 && r <= 12) ? ((r - 1u) & 3u) : 0u; }
+// the rows a contract mask (bit code) plays, as a 19-bit word
+__device__ __forceinline__ u32 bid_row_mask(u32 contracts) {
+    u32 m = contracts & 1u;
+    m |= (contracts & 2u) ? 0xFu << 1 : 0u;
+    m |= (contracts & 4u) ? 0xFu << 5 : 0u;
+    m |= (contracts & 8u) ? 0xFu << 9 : 0u;
+    return m | (((contracts >> 4) & 0x3Fu) << 13);
+}
+
+// World wkey of a bidder: seat `viewer` holds its twelve cards and has seen nothing else, so the other 42 are dealt
+// again — redeal_hidden's four-capacity walk (12, 12, 12 and the talon's 6, then the talon's slot order) on the deal set
+// up as a Klop, where all six talon cards are un-owned.  The world is (A plane, B plane, talon ids); its C plane is the
+// mask of the ids and a talon card has A = B = 0.
+__device__ __forceinline__ void bid_world(u64 h0, u64 h1, u64 h2, u64 h3, u64 talon36, u32 viewer, u64 wkey, u64 &A, u64 &B, u64 &ids) {
+    Game g;
+    setup_game(g, h0, h1, h2, h3, talon36, TK_KLOP, 0, 0);
+    g.epar = 0; g.cprev = 0;
+    redeal_hidden(g, viewer, wkey, 0ULL);
+    A = g.A; B = g.B; ids = g.talon;
+}
+// The game of row r on a world: the row's contract and king with the viewer as the declarer (Klop: seat 0); partner and
+// parking seat by setup_game's own rule on the WORLD's hands.  Left waiting for the exchange where the contract has one.
+__device__ __forceinline__ void bid_game(Game &h, u64 A, u64 B, u64 ids, u32 r, u32 viewer) {
+    const u64 in_hand = ~ids_mask(ids, 0, 6) & TK_DECK;
+    const u32 c = bid_row_contract(r);
+    setup_game(h, in_hand & ~A & ~B, in_hand & A & ~B, in_hand & ~A & B, in_hand & A & B, ids, c, c == TK_KLOP ? 0u : viewer, bid_row_king(r));
+    h.epar = 0; h.cprev = 0;
+}
+
+// The answer of a playout bidder to licitiram(min_igra, obvezno, prednost) from its row of sums S[0 .. 18]: the candidates
+// are the rows of the contracts in `contracts` from Tri up that beat (prednost: at least match) min_igra; the best is the
+// largest S, the lowest row on ties.  It is bid when S exceeds thr = threshold * playouts and, for a seat that may stand
+// on `obvezno` (-100: none), the largest S of that contract's rows; else the seat answers obvezno, or Naprej (-10).
+__device__ __forceinline__ int bid_answer(const int32_t *S, int min_igra, int obvezno, bool prednost, long long thr, u32 contracts) {
+    int best = -1, bs = 0;
+    for (u32 r = 1; r < TK_BID_OPTIONS; r++) {
+        const u32 c = bid_row_contract(r);
+        const int b = 10 * (int)c, s = S[r];
+        const bool cand = ((contracts >> c) & 1u) && (prednost ? b >= min_igra : b > min_igra);
+        if (cand && (best < 0 || s > bs)) { best = (int)r; bs = s; }
+    }
+    bool bid = best >= 0 && (long long)bs > thr;
+    if (obvezno != -100) {
+        const u32 oc = (u32)(obvezno / 10);
+        bool any = false;
+        int stand = 0;
+        for (u32 r = 0; r < TK_BID_OPTIONS; r++)
+            if (bid_row_contract(r) == oc) { stand = (!any || S[r] > stand) ? S[r] : stand; any = true; }
+        bid = bid && bs > stand;
+    }
+    return bid ? 10 * (int)bid_row_contract((u32)best) : (obvezno == -100 ? -10 : obvezno);
+}
+
+// One bidding round at a mixed table: bot_bidding's control flow (Igra.licitacija, Igra.py:75-114) with a playout bidder
+// on the seats of `set` (sums [4][TK_BID_ROWS], read only for those seats) and the Bot's draw 72 + n elsewhere; every call
+// counts in n.  With set = 0 this is sample_setup(key, mix = 2).  The king: the declarer's best row of the contract (the
+// lowest suit on ties) for a playout declarer, draw 67 for the Bot, 0 for a contract without one.
+struct BidTable { BidCtx b; const int32_t *sums; long long thr; u32 contracts, set; };
+__device__ __forceinline__ int bid_ask(BidTable &t, u32 seat, int min_igra, int obvezno, bool prednost) {
+    if (!((t.set >> seat) & 1u)) return bot_ask(t.b, min_igra, obvezno, prednost);
+    t.b.calls++;
+    return bid_answer(t.sums + seat * TK_BID_ROWS, min_igra, obvezno, prednost, t.thr, t.contracts);
+}
+__device__ __forceinline__ void bid_round(u64 key, const int32_t *sums, int playouts, int threshold, u32 contracts, u32 set,
+                                          u32 &contract, u32 &declarer, u32 &king) {
+    BidTable t = {{key, 0}, sums, (long long)threshold * (long long)playouts, contracts, set};
+    u32 still = 0, holder = 0;
+    int top = 10;
+    bool open = true;
+    for (u32 seat = 1; seat <= 3; seat++) {
+        int v = bid_ask(t, seat, top, -100, false);
+        if (v != -10) still |= 1u << seat;
+        top = max(top, v);
+    }
+    if (top == 10) {                                 // nobody bid: seat 0 plays at least Klop
+        top = bid_ask(t, 0, -10, 0, false);
+        open = false;
+    }
+    if (open) {
+        int v = bid_ask(t, 0, top, -100, true);      // seat 0 may match (priority)
+        if (v != -10) still |= 1u;
+        top = max(top, v);
+        holder = (u32)__builtin_ctz(still);
+        for (int rounds = 0; __popc(still) != 1 && rounds < 8; rounds++) {
+            u32 nxt = 0;
+            for (u32 k = 0; k < 4; k++) {
+                u32 seat = (k + 1) & 3;              // 1, 2, 3, 0: seat 0 is asked last
+                if ((still >> seat) & 1) {
+                    v = bid_ask(t, seat, top, seat == holder ? top : -100, false);
+                    if (v != -10) { nxt |= 1u << seat; holder = seat; top = v; }
+                }
+            }
+            still = nxt;
+        }
+    }
+    declarer = top == 0 ? 0u : holder;
+    contract = (u32)(top / 10);
+    u32 kg = 0;
+    if (has_king(contract)) {
+        if ((set >> declarer) & 1u) {
+            const int32_t *S = sums + declarer * TK_BID_ROWS + 1u + 4u * (contract - 1u);
+            for (u32 k = 1; k < 4; k++) kg = S[k] > S[kg] ? k : kg;
+        } else {
+            kg = pick(rng32(key, 67), 4);
+        }
+    }
+    king = kg;
+}

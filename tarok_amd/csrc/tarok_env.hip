@@ -114,6 +114,7 @@ struct tarok_env {
     uint32_t lazy_refill;    // the one-card step lists emptied lines for a bulk deal every TK_BULK_EVERY launches (refill_role)
     int n_cus;               // compute units of the device (k_learn_dw's grid), 0 = not asked yet
     float *adam_sumsq;       // k_learn_gnorm's partial sums
+    u64 *bid_deal;           // tarok_playout_bids: the deal being bid on, [5][n] (k_bid_deal); allocated by its first call
     u64 *stamps;             // diagnostics only (tarok_debug_stamps)
     size_t stamps_words;     // its capacity: a kernel that would write more gets no stamps pointer
     float temperature, epsilon;   // the play mode as given (tarok_set_play_mode); (1, 0): the MODE = 0 kernels, untouched
@@ -1830,6 +1831,108 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_hidden(int64_t n, u64 pseed /* seed ^ sa
     }
 }
 
+// tarok_playout_bids, first launch: the deal tarok_reset(env, episode, deals, ...) would make, one lane per game, left as
+// (h0, h1, h2, h3, talon ids) in the env's bidding buffer [5][n] — the 54-key sorting network has a kernel of its own so
+// that the playout kernel keeps its registers.  A deals row that k_reset would flag leaves five zeros: no viewer, zero sums.
+TK_KERNEL(TK_BLOCK, 80) void k_bid_deal(int64_t n, u64 seed, u64 offset, u32 episode, const uint8_t *__restrict__ deals,
+                                       u64 *__restrict__ out) {
+    TK_VGPR_TOP(80, 79);
+    int64_t i = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    u64 h0 = 0, h1 = 0, h2 = 0, h3 = 0, tal = 0;
+    if (deals) {
+        const uint8_t *p = deals + i * 54;
+        u64 h[4] = {0, 0, 0, 0};
+        u64 seen = 0;
+        bool bad = false;
+        for (int k = 0; k < 48; k++) { u32 c = p[k]; bad |= c >= 54; c &= 63; seen |= 1ULL << c; h[k / 12] |= 1ULL << c; }
+        for (int k = 0; k < 6; k++) { u32 c = p[48 + k]; bad |= c >= 54; c &= 63; seen |= 1ULL << c; tal |= (u64)c << (6 * k); }
+        bad |= seen != TK_DECK;
+        h0 = bad ? 0ULL : h[0]; h1 = bad ? 0ULL : h[1]; h2 = bad ? 0ULL : h[2]; h3 = bad ? 0ULL : h[3]; tal = bad ? 0ULL : tal;
+    } else {
+        deal_thread(game_key(seed, offset + (u64)i, episode), h0, h1, h2, h3, tal);
+    }
+    out[i] = h0; out[n + i] = h1; out[2 * n + i] = h2; out[3 * n + i] = h3; out[4 * n + i] = tal;
+}
+
+// tarok_playout_bids: every bid valued by determinized playouts — k_playout_exchange's structure one decision earlier
+// still.  A team of 2^lg lanes owns one game (lg >= TK_PB_MIN_LG by k_playout's rule on worlds * samples, so teams <= 16
+// and teams * worlds <= TK_PO_WORLD_SLOTS).  The four viewers are taken one after the other and share the team's world
+// slots: for viewer v the dealing lanes leave (A, B, talon ids) of each world in LDS (bid_world), a barrier, then the
+// items (row r of the rows played, world w, sample k) go round-robin over the team: bid_game, the Bot's exchange under
+// the playout key where the contract has one, the Bot's first card, playout_from.  The VIEWER's score goes into the
+// team's [4][20] block by integer LDS adds; a last pass writes it as twenty 16-byte pieces.  The viewer loop's barriers
+// are outside every test of the game's seat set: each workgroup passes nine.  The env's games are not read.
+#define TK_PB_MIN_LG 4
+TK_KERNEL(TK_BLOCK, 128) void k_playout_bids(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 episode, u32 worlds, u32 samples,
+                                            u32 lg, u32 contracts, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                            const u64 *__restrict__ deal, int4 *__restrict__ sum_out) {
+    TK_VGPR_TOP(128, 127);
+    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> TK_PB_MIN_LG) * 4 * TAROK_BID_ROWS];
+    __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS], world_ids[TK_PO_WORLD_SLOTS];
+    const u32 tid = threadIdx.x, team = tid >> lg, L = 1u << lg, lane = tid & (L - 1u), teams = (u32)TK_BLOCK >> lg;
+    const int64_t g = (int64_t)blockIdx.x * teams + team;
+    for (u32 w = tid; w < teams * (4 * TAROK_BID_ROWS); w += TK_BLOCK) sums[w] = 0;
+    int *row = sums + team * (4 * TAROK_BID_ROWS);
+    const u32 slot0 = team * worlds;                 // the team's worlds: slots slot0 .. slot0 + worlds - 1
+    u64 h0 = 0, h1 = 0, h2 = 0, h3 = 0, tal = 0;
+    u32 set = 0;
+    if (g < n) {
+        h0 = deal[g]; h1 = deal[n + g]; h2 = deal[2 * n + g]; h3 = deal[3 * n + g]; tal = deal[4 * n + g];
+        set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+        if ((h0 | h1 | h2 | h3) == 0) set = 0;       // an invalid deal row
+    }
+    const u32 rowmask = bid_row_mask(contracts), nrows = (u32)__popc(rowmask);
+    const u32 per_row = worlds * samples, items = nrows * per_row;
+    const u64 ebase = (u64)episode << 28;
+#pragma unroll 1
+    for (u32 v = 0; v < 4; v++) {
+        const bool part = (set >> v) & 1u;
+        __syncthreads();                             // the rows are zero; the last viewer's items have read their worlds
+        if (part) {
+            for (u32 w = lane; w < worlds; w += L) {
+                u64 A, B, ids;
+                bid_world(h0, h1, h2, h3, tal, v, game_key(pseed, offset + (u64)g, (2ULL << 61) | ebase | ((u64)v << 6) | (u64)w), A, B, ids);
+                world_a[slot0 + w] = A; world_b[slot0 + w] = B; world_ids[slot0 + w] = ids;
+            }
+        }
+        __syncthreads();
+        if (part) {
+            for (u32 it = lane; it < items; it += L) {
+                u32 j = it / per_row, rem = it - j * per_row, w = rem / samples, k = rem - w * samples;
+                u32 r = kth_bit((u64)rowmask, j);
+                u64 pkey = game_key(pseed, offset + (u64)g,
+                                    (3ULL << 61) | ebase | ((u64)v << 26) | ((u64)r << 21) | ((u64)w << 15) | (u64)k);
+                Game h;
+                bid_game(h, world_a[slot0 + w], world_b[slot0 + w], world_ids[slot0 + w], r, v);
+                if (h.phase == TK_PHASE_EXCHANGE) bot_exchange(h, pkey);
+                u32 c = policy_action(pkey, 0u, legal_now(h));
+                u64 scores = playout_from(h, c, pkey, 0u);
+                atomicAdd(row + v * TAROK_BID_ROWS + r, (int)(int16_t)(scores >> (16 * v)));
+            }
+        }
+    }
+    __syncthreads();
+    if (g >= n) return;
+    for (u32 r = lane; r < TAROK_BID_ROWS; r += L) sum_out[g * TAROK_BID_ROWS + r] = reinterpret_cast<const int4 *>(row)[r];
+}
+
+// tarok_bid_round: one bidding round per game on one lane (bid_round, tarok_device.h): the control flow of bot_bidding
+// with playout-valued answers on the seats of the set.  Every row of the three outputs is written.
+TK_KERNEL(TK_BLOCK, 64) void k_bid_round(int64_t n, u64 seed, u64 offset, u32 episode, const int32_t *__restrict__ sums, int playouts,
+                                        int threshold, u32 contracts, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                        int8_t *__restrict__ contract_out, int8_t *__restrict__ declarer_out, int8_t *__restrict__ king_out) {
+    TK_VGPR_TOP(64, 63);
+    int64_t i = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const u32 set = seat_sets ? (u32)seat_sets[i] & 15u : seats;
+    u32 c, d, k;
+    bid_round(game_key(seed, offset + (u64)i, episode), sums + i * (4 * TAROK_BID_ROWS), playouts, threshold, contracts, set, c, d, k);
+    if (contract_out) contract_out[i] = (int8_t)c;
+    if (declarer_out) declarer_out[i] = (int8_t)d;
+    if (king_out) king_out[i] = (int8_t)k;
+}
+
 // tarok_playout_targets: a playout launch's sums -> one target row of 64 bf16 per game (include/tarok_env.h).  One lane per
 // game builds its row in LDS — eight zero pieces, then at most twelve 2-byte values at the legal cards' columns — and the
 // workgroup writes its 256 rows, 32 KB in a row of memory, as 16-byte pieces in lane order.  The mover's column of the twelve
@@ -3315,6 +3418,7 @@ void tarok_destroy(tarok_env *e) {
     if (e->cap_stream) (void)hipStreamDestroy(e->cap_stream);
     (void)hipFree(e->s01); (void)hipFree(e->s23); (void)hipFree(e->aux); (void)hipFree(e->cnt); (void)hipFree(e->nstale); (void)hipFree(e->gkey);
     (void)hipFree(e->rlist); (void)hipFree(e->rcount); (void)hipFree(e->elist); (void)hipFree(e->epoch); (void)hipFree(e->hist); (void)hipFree(e->adam_sumsq);
+    (void)hipFree(e->bid_deal);
     delete e;
 }
 
@@ -3660,6 +3764,41 @@ int tarok_playout_cards_hidden(tarok_env *e, int worlds, int samples, uint64_t s
     hipLaunchKernelGGL(k_playout_hidden, dim3((unsigned)((e->n + teams - 1) / teams)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
                        e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)samples, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt,
                        e->gkey, (const u64 *)played, reinterpret_cast<int4 *>(sum_out), action_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int tarok_playout_bids(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int samples, int contracts, uint64_t salt,
+                       int seats, const uint8_t *seats_per_game, int32_t *sum_out, void *stream) {
+    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || samples < 1 || samples > TAROK_PLAYOUT_MAX_SAMPLES || contracts < 1 ||
+        contracts > TAROK_BID_ALL_CONTRACTS || seats < 0 || seats > 15)
+        return TAROK_EINVAL;
+    if (!sum_out) return TAROK_OK;
+    HIPCHK(hipSetDevice(e->device));
+    if (!e->bid_deal) HIPCHK(hipMalloc((void **)&e->bid_deal, (size_t)e->n * 5 * sizeof(u64)));   // on the first call; tarok_destroy frees it
+    hipLaunchKernelGGL(k_bid_deal, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, episode, deals, e->bid_deal);
+    // lanes per game: tarok_playout_exchange's rule — 16 or more, so a workgroup's at most 16 teams keep their 80 sums each
+    // in 5 KiB, and 4 * worlds <= lanes, so their worlds fit its TK_PO_WORLD_SLOTS slots
+    static_assert(TAROK_BID_ROWS == TK_BID_ROWS && TAROK_BID_ROWS % 4 == 0, "a viewer's rows are whole 16-byte pieces");
+    u32 lg = TK_PB_MIN_LG;
+    while (lg < TK_PO_MAX_LG && (1 << lg) < 4 * worlds * samples) lg++;
+    int64_t teams = TK_BLOCK >> lg;
+    hipLaunchKernelGGL(k_playout_bids, dim3((unsigned)((e->n + teams - 1) / teams)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
+                       e->seed ^ (u64)salt, e->offset, episode, (u32)worlds, (u32)samples, lg, (u32)contracts, (u32)seats, seats_per_game,
+                       e->bid_deal, reinterpret_cast<int4 *>(sum_out));
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int tarok_bid_round(tarok_env *e, uint32_t episode, const int32_t *sums, int playouts, int threshold, int contracts, int seats,
+                    const uint8_t *seats_per_game, int8_t *contract_out, int8_t *declarer_out, int8_t *king_out, void *stream) {
+    if (!e || playouts < 1 || contracts < 1 || contracts > TAROK_BID_ALL_CONTRACTS || seats < 0 || seats > 15 ||
+        (!sums && (seats != 0 || seats_per_game)) || (!contract_out && !declarer_out && !king_out))
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    hipLaunchKernelGGL(k_bid_round, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, episode, sums, playouts,
+                       threshold, (u32)contracts, (u32)(sums ? seats : 0), sums ? seats_per_game : nullptr, contract_out, declarer_out,
+                       king_out);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }

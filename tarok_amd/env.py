@@ -371,6 +371,39 @@ class TarokVecEnv:
                                                         self._p(choice_out), self._p(discards_out), self._stream()))
         return sum_out, choice_out, discards_out
 
+    def playout_bids(self, episode, worlds, samples, contracts=K.BID_DEFAULT_CONTRACTS, deals=None, salt=0, seats=15,
+                     seats_per_game=None, sum_out=None):
+        """Every bid of every seat valued by determinized playouts (tarok_playout_bids), BEFORE reset(): the game valued
+        is the one reset(episode, deals) would deal.  For every viewer seat in `seats` / `seats_per_game` and each of
+        `worlds` (1..64) re-deals of the 42 cards it does not hold, every option in `contracts` (bit code: Klop 0 ..
+        Odprti_berac 9) — each of Tri / Dve / Ena with each of the four kings — is played to the end `samples` times by
+        the Bot with the viewer as declarer.  Returns sum [N, 4, K.BID_ROWS] int32: the viewer's summed score per row
+        (karte.bid_row), zeros for seats outside the set, options outside `contracts` and row 19.  bid_round() turns the
+        sums into a contract, a declarer and a king.  Does not read or write the env's games; `salt` varies the draws."""
+        deals = self._dev(deals, torch.uint8, (self.n, 54))
+        with torch.cuda.device(self.device):
+            if sum_out is None:
+                sum_out = torch.empty((self.n, 4, K.BID_ROWS), dtype=torch.int32, device=self.device)
+            _native.check(self.L.tarok_playout_bids(self._h, int(episode), self._p(deals), int(worlds), int(samples), int(contracts),
+                                                    int(salt) & ((1 << 64) - 1), int(seats),
+                                                    self._p(self._seat_sets(seats_per_game)), self._p(sum_out), self._stream()))
+        return sum_out
+
+    def bid_round(self, episode, sums, playouts, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, seats=15, seats_per_game=None):
+        """The bidding round of every game on the device (tarok_bid_round; Igra.licitacija's control flow): the seats of
+        `seats` / `seats_per_game` answer from playout_bids()' sums — the best-valued contract that beats the standing
+        bid, if its sum exceeds threshold * playouts (playouts = worlds * samples of the launch that made the sums) and,
+        for the holder, the sum of standing — and the other seats as the Bot does.  Returns (contract, declarer,
+        king_suit), three [N] int8 device tensors that reset(episode, deals, contract=, declarer=, king_suit=) takes
+        unchanged.  seats=0 is the Bot's own round (K.MIX_BOT's contract, declarer and king); sums may then be None."""
+        sums = self._dev(sums, torch.int32, (self.n, 4, K.BID_ROWS))
+        with torch.cuda.device(self.device):
+            out = [torch.empty(self.n, dtype=torch.int8, device=self.device) for _ in range(3)]
+            _native.check(self.L.tarok_bid_round(self._h, int(episode), self._p(sums), int(playouts), int(threshold), int(contracts),
+                                                 int(seats), self._p(self._seat_sets(seats_per_game)), self._p(out[0]),
+                                                 self._p(out[1]), self._p(out[2]), self._stream()))
+        return tuple(out)
+
     def shown_voids(self, out=None):
         """[N] int32 device tensor (tarok_shown_voids; the bits of a u32): bit 5 * seat + class of a game's word is set
         iff the play so far has shown that seat to hold no card of that class (class = min(card >> 3, 4): the four suits,

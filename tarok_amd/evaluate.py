@@ -120,12 +120,32 @@ def evaluate_vs_policy(weights, opponent, n_games, episodes, seed=0, mix=K.MIX_B
                                                  temperature=temperature, epsilon=epsilon))
 
 
-def _exchange_front(env, episode, worlds, samples, exchange, salt, seats, bufs):
+def _bid_front(env, episode, bidding, salt, seats, threshold, contracts, sums):
+    """The front end of a pass whose playout player also bids: ONE tarok_playout_bids at bidding = (worlds, samples) with
+    the pass's seat set, ONE tarok_bid_round — the Bot's own answers outside the set, so the empty set gives
+    K.MIX_BOT's contract, declarer and king — and the keyword arguments reset() takes them as."""
+    worlds, samples = bidding
+    env.playout_bids(episode, worlds, samples, contracts=contracts, salt=salt, seats=seats, sum_out=sums)
+    c, d, k = env.bid_round(episode, sums, int(worlds) * int(samples), threshold=threshold, contracts=contracts, seats=seats)
+    return dict(contract=c, declarer=d, king_suit=k)
+
+
+def _bid_args(bidding, mix):
+    if bidding is None:
+        return None
+    if mix != K.MIX_BOT:
+        raise ValueError("bidding=(worlds, samples) replaces the Bot's bidding round: it goes with mix=K.MIX_BOT")
+    worlds, samples = bidding
+    return int(worlds), int(samples)
+
+
+def _exchange_front(env, episode, worlds, samples, exchange, salt, seats, bufs, setup=None):
     """The front end of a pass whose playout player also makes the talon exchange: reset with the exchange deferred, ONE
     tarok_playout_exchange with the pass's seat set — its rows are the Bot's own exchange for a declarer outside the
-    set — and one tarok_exchange that applies them.  Returns the canonical lanes before the exchange if asked for."""
+    set — and one tarok_exchange that applies them.  setup: _bid_front's contract, declarer and king for the reset.
+    Returns the canonical lanes before the exchange if asked for."""
     sums, choice, discards, want_start = bufs
-    env.reset(episode=episode, clear_counters=True, defer_exchange=True)
+    env.reset(episode=episode, clear_counters=True, defer_exchange=True, **(setup or {}))
     start = env.state() if want_start else None
     env.playout_exchange(worlds, samples, exchange, salt=salt, seats=seats, sum_out=sums, choice_out=choice, discards_out=discards)
     env.exchange(choice, discards)
@@ -140,7 +160,7 @@ def _exchange_bufs(env, n, exchange, want_start):
 
 
 def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None, voids=False, exchange=None,
-                    hidden=False):
+                    hidden=False, bidding=None, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS):
     """_play_passes_mode with the Monte-Carlo player (TarokVecEnv.playout_cards) in the network's place: per lock-step
     one playout launch with the pass's seat set — tarok_playout_cards (open hands) for worlds=None,
     tarok_playout_cards_det (the fair player: `worlds` re-deals of the unseen cards) otherwise — whose action_out holds
@@ -152,6 +172,8 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     exchange=D (with worlds): every pass starts with _exchange_front at (worlds, samples, D) — the playout player makes
     its seat's talon exchange too; the inspected dicts then also hold choice [N] i8 and discards [N,3] u8, and `start`
     is the state BEFORE the exchange.  None: the reset's own Bot exchange, the code path as it was.
+    bidding=(W, S) (with worlds): every pass starts with _bid_front at (W, S) — the playout player bids for its seat too;
+    the inspected dicts then also hold contract, declarer and king_suit [N] i8.  None: the mix's own contracts.
     inspect: as in _play_passes_mode."""
     if voids and worlds is None:
         raise ValueError("voids=True constrains the re-deals: give worlds= as well")
@@ -161,6 +183,9 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
         raise ValueError("hidden=True is not built together with voids=True: give one of the two")
     if exchange is not None and worlds is None:
         raise ValueError("exchange=D is the fair player's front end: give worlds= as well")
+    if bidding is not None and worlds is None:
+        raise ValueError("bidding=(W, S) is the fair player's front end: give worlds= as well")
+    bidding = _bid_args(bidding, mix)
     n = int(n_games)
     scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
     env = TarokVecEnv(n, device=device, seed=seed, mix=mix, history=bool(voids or hidden))
@@ -171,12 +196,14 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
             words = torch.empty(n, dtype=torch.int32, device=env.device) if voids else None
             pwords = torch.empty(n, dtype=torch.int64, device=env.device) if hidden else None
         xb = _exchange_bufs(env, n, exchange, inspect is not None) if exchange is not None else None
+        bsums = _bid_bufs(env, n) if bidding is not None else None
         for e in range(int(episodes)):
             for p, seats in enumerate(PASS_SEATS):
+                setup = _bid_front(env, e, bidding, salt, seats, threshold, contracts, bsums) if bidding is not None else {}
                 if xb is not None:
-                    start = _exchange_front(env, e, worlds, samples, exchange, salt, seats, xb)
+                    start = _exchange_front(env, e, worlds, samples, exchange, salt, seats, xb, setup)
                 else:
-                    env.reset(episode=e, clear_counters=True)
+                    env.reset(episode=e, clear_counters=True, **setup)
                     start = env.state() if inspect is not None else None
                 for t in range(GAME_CARDS):
                     if worlds is None:
@@ -196,13 +223,21 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
                     inspect.append(dict(episode=e, seats=seats, start=start, actions=actions.cpu().numpy(), scores=ss.copy()))
                     if xb is not None:
                         inspect[-1].update(choice=xb[1].cpu().numpy(), discards=xb[2].cpu().numpy())
+                    if bidding is not None:
+                        inspect[-1].update({k: v.cpu().numpy() for k, v in setup.items()})
     finally:
         env.close()
     return scores
 
 
+def _bid_bufs(env, n):
+    with torch.cuda.device(env.device):
+        return torch.empty((n, 4, K.BID_ROWS), dtype=torch.int32, device=env.device)
+
+
 def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None,
-                            voids=False, exchange=None, hidden=False):
+                            voids=False, exchange=None, hidden=False, bidding=None, threshold=0,
+                            contracts=K.BID_DEFAULT_CONTRACTS):
     """evaluate_vs_bot with the open-hand Monte-Carlo player in the network's place: a strong reference player that needs
     no training.  On its seat it plays, at every move, the legal card with the best summed score over `samples` Bot
     playouts of each legal card (tarok_playout_cards; `salt` varies their draws).  The playouts see the TRUE hidden
@@ -220,10 +255,15 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
     declared it picks the talon group and the discards by playouts over D discard sets per group
     (tarok_playout_exchange at (W, samples, D)); the other declarers exchange as the Bot does.  None (the default): every
     declarer exchanges as the Bot does, as before.
+    bidding=(Wb, Sb) (with worlds=W and mix=K.MIX_BOT): the fair player also BIDS for its seat — tarok_playout_bids at
+    (Wb, Sb) over `contracts` and tarok_bid_round with `threshold` decide contract, declarer and called king before the
+    reset; the other seats bid as the Bot does, so pass 0 is unchanged.  It composes with exchange=D.  None (the default):
+    the Bot's bidding round on every seat, as before.
     The same five duplicate passes (PASS_SEATS) on an env of its own; returns duplicate_advantage's dict, `policy_mean`
     being the playout player's.  inspect (tests): a list that receives one dict per pass, as in _play_passes_mode."""
     return duplicate_advantage(_playout_passes(samples, n_games, episodes, seed, mix, device, salt=salt, inspect=inspect,
-                                               worlds=worlds, voids=voids, exchange=exchange, hidden=hidden))
+                                               worlds=worlds, voids=voids, exchange=exchange, hidden=hidden, bidding=bidding,
+                                               threshold=threshold, contracts=contracts))
 
 
 def _exchange_passes(worlds, samples, discard_sets, n_games, episodes, seed, mix, device, salt=0, inspect=None):
@@ -264,3 +304,45 @@ def evaluate_exchange_vs_bot(worlds, samples, discard_sets, n_games, episodes, s
     `policy_mean` being that of the seat whose exchanges the playouts chose."""
     return duplicate_advantage(_exchange_passes(worlds, samples, discard_sets, n_games, episodes, seed, mix, device, salt=salt,
                                                 inspect=inspect))
+
+
+def _bidding_passes(worlds, samples, n_games, episodes, seed, device, salt=0, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS,
+                    inspect=None):
+    """The five passes with the playout player making the BID of its seat only: _bid_front, a reset that takes its
+    contract, declarer and king (the Bot's exchange), then the Bot's card on every seat at every move, as in
+    _exchange_passes.  inspect: one dict per pass — episode, seats, contract, declarer, king_suit, start, actions, scores."""
+    n = int(n_games)
+    scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
+    env = TarokVecEnv(n, device=device, seed=seed, mix=K.MIX_BOT)
+    try:
+        with torch.cuda.device(env.device):
+            actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
+            zeros = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=env.device)
+        bsums = _bid_bufs(env, n)
+        for e in range(int(episodes)):
+            for p, seats in enumerate(PASS_SEATS):
+                setup = _bid_front(env, e, (worlds, samples), salt, seats, threshold, contracts, bsums)
+                env.reset(episode=e, clear_counters=True, **setup)
+                start = env.state() if inspect is not None else None
+                for t in range(GAME_CARDS):
+                    env.playout_cards(1, seats=0, sum_out=zeros, action_out=actions[t])
+                    env.step(actions[t], auto_reset=False)
+                _, ss = env.counters()                # (the pass's one synchronisation)
+                scores[p, e * n:(e + 1) * n] = ss
+                if inspect is not None:
+                    inspect.append(dict(episode=e, seats=seats, start=start, actions=actions.cpu().numpy(), scores=ss.copy(),
+                                        **{k: v.cpu().numpy() for k, v in setup.items()}))
+    finally:
+        env.close()
+    return scores
+
+
+def evaluate_bidding_vs_bot(worlds, samples, n_games, episodes, seed=0, device=0, salt=0, threshold=0,
+                            contracts=K.BID_DEFAULT_CONTRACTS, inspect=None):
+    """What is the bid alone worth?  The five duplicate passes on K.MIX_BOT's deals with the Bot making EVERY exchange and
+    playing EVERY card; in pass 1 + k seat k bids by playouts — tarok_playout_bids at (worlds, samples) over `contracts`,
+    then tarok_bid_round with `threshold` — against three Bot bidders, and calls its king by the same sums.  Pass 0 is the
+    Bot's own bidding round on every seat: the scores of evaluate_vs_bot's pass 0 on the same deals.  Returns
+    duplicate_advantage's dict, `policy_mean` being that of the seat that bid by playouts."""
+    return duplicate_advantage(_bidding_passes(worlds, samples, n_games, episodes, seed, device, salt=salt, threshold=threshold,
+                                               contracts=contracts, inspect=inspect))

@@ -70,6 +70,24 @@ PLAYOUT_RANKS = 12        # rows of sum_out per game: a hand in play never holds
 PLAYOUT_MAX_SAMPLES = 1024
 PLAYOUT_MAX_WORLDS = 64   # tarok_playout_cards_det: re-deals of the unseen cards per launch
 EXCHANGE_MAX_SETS = 8     # tarok_playout_exchange: discard sets per talon group; sum_out has 6 * discard_sets rows per game
+BID_ROWS = 20             # tarok_playout_bids: rows of sum_out per viewer seat (19 options and one of padding)
+BID_DEFAULT_CONTRACTS = 0x00F   # Klop, Tri, Dve, Ena: the Bot's own range
+BID_ALL_CONTRACTS = 0x3FF
+
+
+def bid_row(code, king=0):
+    """The row of tarok_playout_bids' sums that holds contract `code` (0 Klop .. 9 Odprti_berac; for Tri, Dve, Ena with the
+    king of suit `king` called)."""
+    code = int(code)
+    return 0 if code == 0 else (1 + 4 * (code - 1) + int(king) if code <= 3 else 9 + code)
+
+
+def bid_row_option(row):
+    """(contract code, called suit or -1) of row 0..18: the inverse of bid_row."""
+    row = int(row)
+    if row == 0:
+        return 0, -1
+    return (1 + (row - 1) // 4, (row - 1) % 4) if row <= 12 else (row - 9, -1)
 # tarok_shown_voids: bit VOID_SEAT_BITS * seat + class of a game's word; class = min(card >> 3, VOID_TAROK)
 VOID_SEAT_BITS = 5
 VOID_TAROK = 4            # classes 0..3 are the suits

@@ -1,7 +1,10 @@
 """Host-side bidding round — the control flow of `Igra.licitacija` (Igra.py:75-114).
 
-One call per game and policy-driven, so it stays on the host; the
-GPU env takes its outcome (declarer seat, contract) as `tarok_reset` inputs.
+`licitacija()` is the host form: one call per game with any `licitiram` callback; the GPU env
+takes its outcome (declarer seat, contract) as `tarok_reset` inputs.  The device runs the same
+round for every game at once in `tarok_bid_round` (`TarokVecEnv.bid_round`), with the Bot's
+answers or with the playout bidder's, whose rule `playout_answer` states here as a pure host
+function on `tarok_playout_bids`' sums.
 
 Bids are the reference's `int(Tip_igre)` values (Tip_igre.py:4-15) so that the `>` / `>=`
 comparisons of the player-side filter (Igralec.py:58-74) mean the same thing.
@@ -65,3 +68,35 @@ def licitacija(licitiram, max_rounds=64):
                 top = b
         still_in = nxt
     return holder, top
+
+
+BID_OPTIONS = 19                                 # rows of a viewer in tarok_playout_bids' sums (row 19 is padding)
+
+
+def row_bid(row):
+    """int(Tip_igre) of row 0..18 of tarok_playout_bids' sums: Klop; Tri, Dve, Ena x four kings; the six others."""
+    return 0 if row == 0 else (10 * (1 + (row - 1) // 4) if row <= 12 else 10 * (row - 9))
+
+
+def playout_answer(S_row, min_igra, obvezno, prednost, playouts, threshold=0, contracts=0x00F):
+    """The answer of a playout bidder to licitiram(min_igra, obvezno, prednost), as tarok_bid_round gives it, from the
+    seat's row of tarok_playout_bids' sums (S_row[r], r < 19; any integer sequence).
+    Candidates: the rows of the contracts in `contracts` (bit int(Tip_igre) / 10) from Tri up that beat min_igra (at least
+    match it with prednost); best = the largest sum, the lowest row on ties.  Without obvezno: the best row's bid if its
+    sum exceeds threshold * playouts, else Naprej.  With obvezno = o: the best row's bid if its sum also exceeds the
+    largest sum among the rows of o itself, else o.
+    As the callback of licitacija():  lambda seat, m, o, p: playout_answer(S[seat], m, o, p, playouts)."""
+    best = None
+    for r in range(1, BID_OPTIONS):
+        b = row_bid(r)
+        if not (int(contracts) >> (b // 10)) & 1:
+            continue
+        if not (b >= min_igra if prednost else b > min_igra):
+            continue
+        if best is None or int(S_row[r]) > int(S_row[best]):
+            best = r
+    bid = best is not None and int(S_row[best]) > int(threshold) * int(playouts)
+    if obvezno is None:
+        return row_bid(best) if bid else NAPREJ
+    stand = max(int(S_row[r]) for r in range(BID_OPTIONS) if row_bid(r) == obvezno)
+    return row_bid(best) if bid and int(S_row[best]) > stand else obvezno

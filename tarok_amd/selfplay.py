@@ -421,7 +421,7 @@ class SelfPlay:
     @torch.no_grad()
     def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None, greedy=False, temperature=None, epsilon=0.0,
                  versus_playout=None, playout_worlds=None, playout_voids=False, playout_exchange=None,
-                 playout_hidden=False):
+                 playout_hidden=False, playout_bidding=None):
         """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
         weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
         and on the SAME deals on every rank (seed 0, game offset 0, whatever the training env's are): the figures of
@@ -442,7 +442,11 @@ class SelfPlay:
         playout_hidden=True (with playout_worlds, not with playout_voids): its worlds also re-deal Klop's face-down talon
         and the declarer's discards (evaluate_playout_vs_bot(hidden=True)).
         playout_exchange=D (with playout_worlds): the fair player also makes its seat's talon exchange, valued by
-        playouts over D discard sets per group (evaluate_playout_vs_bot(exchange=D))."""
+        playouts over D discard sets per group (evaluate_playout_vs_bot(exchange=D)).
+        playout_bidding=(W, S) (with playout_worlds and mix=K.MIX_BOT): the fair player also bids for its seat, every
+        contract valued by playouts (evaluate_playout_vs_bot(bidding=(W, S)))."""
+        if playout_bidding is not None and playout_worlds is None:
+            raise ValueError("playout_bidding goes with playout_worlds=W")
         if playout_exchange is not None and playout_worlds is None:
             raise ValueError("playout_exchange goes with playout_worlds=W")
         if playout_worlds is not None and versus_playout is None:
@@ -473,7 +477,7 @@ class SelfPlay:
         from .evaluate import evaluate_playout_vs_bot
         return own, evaluate_playout_vs_bot(int(versus_playout), n_games, episodes, mix=mix, device=self.env.device_index,
                                             worlds=playout_worlds, voids=bool(playout_voids), exchange=playout_exchange,
-                                            hidden=bool(playout_hidden))
+                                            hidden=bool(playout_hidden), bidding=playout_bidding)
 
     def _alloc(self, T):
         n, dev = self.env.n, self.device
