@@ -490,6 +490,37 @@ int tarok_playout_bids(tarok_env *env, uint32_t episode, const uint8_t *deals, i
 int tarok_bid_round(tarok_env *env, uint32_t episode, const int32_t *sums, int playouts, int threshold, int contracts, int seats,
                     const uint8_t *seats_per_game, int8_t *contract_out, int8_t *declarer_out, int8_t *king_out, void *stream);
 
+/* The bidding head: a network that writes tarok_playout_bids' array from the twelve cards of each hand, in that launch's
+ * place in front of tarok_bid_round.  Read-only on the env; the env's games are not read at all.  The game valued is the
+ * one tarok_reset(env, episode, deals, ...) would deal, exactly as tarok_playout_bids defines it (row g of deals, an
+ * invalid row giving all-zero rows, or the device's own deal under game_key(seed, gidx, episode)).
+ *
+ * Row (g, v), v = 0..3, has the 256 0/1 features F(hand of seat v, v), feature f = bit f % 64 of word f / 64:
+ *   word 0  bits 0..53 the hand; bit 54 + v (one-hot seat: the seat decides the bidding order, seat 0's forced call and
+ *           priority).
+ *   word 1  bit j, j < 12: the hand holds more than j taroks; bit 16 + 8 k + j, k < 4, j < 8: more than j cards of suit
+ *           k; bit 48 + k: the king of suit k; bits 52, 53, 54: pagat, mond, skis.
+ *   words 2, 3  zero (reserved).
+ * The row goes through tarok_policy_mlp's network — 256 -> 256 -> 256 -> 64, ReLU, bf16 MFMA with f32 accumulate, both
+ * hidden layers stored as bf16 — with w1, b1, w2, b2, w3, b3 in that call's layouts.  Output o < 19 is y of bid row o
+ * (the rows of tarok_playout_bids); outputs 19..63 are ignored.
+ *   value_out [N,4,TAROK_BID_ROWS] i32, 16-byte aligned, may be NULL:
+ *       (int32) rintf(fminf(fmaxf(y * scale, -2^30), 2^30))     (ties to even; a NaN becomes -2^30 by fmaxf)
+ *     and 0 for a seat outside the game's set (`seats`, or seats_per_game[g] & 15), a row whose contract bit is not in
+ *     `contracts`, row 19 and an invalid deal: tarok_playout_bids' zeros, so the array is interchangeable with its
+ *     sum_out as tarok_bid_round's `sums` (playouts then being the caller's own divisor: scale = playouts / the unit
+ *     of y in points).  EVERY row is written.
+ *   raw_out [N,4,TAROK_BID_ROWS] f32, 16-byte aligned, may be NULL: y before scaling, with the same zeros.
+ *   feature_words_out [N,4,4] u64, 16-byte aligned, may be NULL: the four feature words of every seat, in the set or not
+ *     (an invalid deal: F(0, v)) — what a learner of the head trains on.
+ * Two launches (the deal, then the head); the first call allocates tarok_playout_bids' 40 bytes per game, which the env
+ * keeps (not capturable in a graph; later calls are).
+ * TAROK_EINVAL (before any HIP call) for a NULL env, weight or bias, a scale that is not finite, <= 0 or > 2^20,
+ * contracts outside 1..TAROK_BID_ALL_CONTRACTS, seats outside 0..15 or all three outputs NULL. */
+int tarok_bid_values(tarok_env *env, uint32_t episode, const uint8_t *deals, const void *w1, const float *b1, const void *w2,
+                     const float *b2, const void *w3, const float *b3, float scale, int contracts, int seats,
+                     const uint8_t *seats_per_game, int32_t *value_out, float *raw_out, uint64_t *feature_words_out, void *stream);
+
 /* A playout launch's sums as a teacher's target distribution: one row of 64 bf16 per game, for the learner's distillation
  * term (tarok_learn_chain_distill).  Per game g the kernel reads obs[g], the observation word the playouts started from:
  * legal = its 54-bit mask, s = its seat bits, nl = min(popcount(legal), TAROK_PLAYOUT_RANKS).

@@ -1,0 +1,118 @@
+"""The bidding head's learner: a network that values every bid from the twelve cards of a hand.
+
+The teacher is TarokVecEnv.playout_bids (tarok_playout_bids): 52-76 determinized playout sets per game, too slow for a
+self-play loop.  The head is a PolicyNet — the policy's 256 -> 256 -> 256 -> 64 network, so the rollout side is
+tarok_bid_values, the policy's own MFMA forward — whose outputs 0..18 regress on the teacher's mean score per row, in
+units of `reward_scale` points (1 / 70, as the policy's returns).  TarokVecEnv.bid_values then writes the array
+TarokVecEnv.bid_round reads, in the teacher's place.
+
+The update is plain torch autograd with Adam on purpose: an iteration is dominated by the teacher's launch, not by a
+regression on 4 rows per game, and everything but collect() / round() runs on CPU tensors as well (BidLearner(None)).
+"""
+import torch
+import torch.nn.functional as F
+
+from . import karte as K
+from .env import TarokVecEnv
+from .selfplay import PolicyNet
+
+BID_OPTIONS = K.BID_ROWS - 1          # rows 0..18 are options, row 19 is padding
+
+
+def row_mask(contracts, device=None):
+    """[BID_OPTIONS] bool: the rows whose contract's bit is set in `contracts` (karte.bid_row_option)."""
+    return torch.tensor([bool((int(contracts) >> K.bid_row_option(r)[0]) & 1) for r in range(BID_OPTIONS)], dtype=torch.bool,
+                        device=device)
+
+
+def bid_loss(out, sums, playouts, reward_scale, contracts):
+    """The head's loss from network outputs `out` [M, >= 19] and the teacher's sums [M, K.BID_ROWS] (int): target =
+    sums / playouts * reward_scale, Huber loss (delta 1) over the rows whose contract is in `contracts`, averaged over
+    those entries.  The other columns enter neither the value nor the gradient."""
+    rows = row_mask(contracts, out.device)
+    target = sums[:, :BID_OPTIONS].to(torch.float32) * (float(reward_scale) / float(playouts))
+    return F.huber_loss(out[:, :BID_OPTIONS].float()[:, rows], target[:, rows], reduction="mean", delta=1.0)
+
+
+def pack_weights(net):
+    """A PolicyNet as tarok_bid_values / tarok_policy_mlp read it: (w1, b1, w2, b2, w3, b3), the weights bf16 in MFMA
+    fragment order (TarokVecEnv.mfma_weight_order), the biases float32 — SelfPlay.snapshot()'s shape."""
+    with torch.no_grad():
+        order = TarokVecEnv.mfma_weight_order
+        f = lambda b: b.detach().to(torch.float32).contiguous().clone()
+        return (order(net.fc1.weight), f(net.fc1.bias), order(net.fc2.weight), f(net.fc2.bias), order(net.head.weight), f(net.head.bias))
+
+
+class BidLearner:
+    """Regresses a PolicyNet on the playout teacher's bid values.
+
+    env: a TarokVecEnv (never reset by the learner: both launches come before reset()), or None for a learner on the
+    CPU that is fed batches by hand (loss / step).  worlds, samples: the teacher's launch (playout_bids).  contracts: the
+    rows learned and bid.  playouts_equiv: the `playouts` bid_round() is told for the head's values, which are scaled to
+    sums over that many playouts, so `threshold` stays in points per game as for the teacher."""
+
+    def __init__(self, env, worlds=8, samples=2, contracts=K.BID_DEFAULT_CONTRACTS, lr=1e-3, reward_scale=1.0 / 70.0,
+                 playouts_equiv=16, seed=0):
+        if not 1 <= int(contracts) <= K.BID_ALL_CONTRACTS:
+            raise ValueError("contracts: a bit set within 1..0x3FF")
+        if not (reward_scale > 0 and int(playouts_equiv) >= 1):
+            raise ValueError("reward_scale > 0 and playouts_equiv >= 1")
+        self.env = env
+        self.device = env.device if env is not None else torch.device("cpu")
+        self.worlds, self.samples, self.contracts = int(worlds), int(samples), int(contracts)
+        self.reward_scale, self.playouts_equiv = float(reward_scale), int(playouts_equiv)
+        self.scale = self.playouts_equiv / self.reward_scale        # tarok_bid_values' scale: outputs -> sums over playouts_equiv
+        if not self.scale <= 2.0 ** 20:
+            raise ValueError("playouts_equiv / reward_scale exceeds tarok_bid_values' largest scale, 2**20")
+        with torch.random.fork_rng(devices=[]):       # the initial weights are a function of `seed` alone
+            torch.manual_seed(int(seed))
+            self.net = PolicyNet(256)
+        self.net.to(self.device)
+        self.opt = torch.optim.Adam(self.net.parameters(), lr=float(lr))
+        self.episode = 0
+        self.salt = int(seed)
+
+    # ---- the regression (any device)
+    def outputs(self, feature_words):
+        """The module's float outputs [M, 64] on feature words [M, 4] int64 (bid_values(feature_words=True) rows)."""
+        x = TarokVecEnv.expand_feature_words(feature_words.reshape(-1, 4), torch.float32)
+        return self.net.forward_raw(x)
+
+    def loss(self, feature_words, sums, playouts):
+        """bid_loss of the network on feature words [..., 4] and the teacher's sums [..., K.BID_ROWS] at `playouts`."""
+        return bid_loss(self.outputs(feature_words), sums.reshape(-1, K.BID_ROWS), playouts, self.reward_scale, self.contracts)
+
+    def step(self, feature_words, sums, playouts):
+        """One Adam step on one batch; returns the loss before the step (a float)."""
+        self.opt.zero_grad(set_to_none=True)
+        loss = self.loss(feature_words, sums, playouts)
+        loss.backward()
+        self.opt.step()
+        return float(loss.detach())
+
+    # ---- the launches (need the env)
+    @torch.no_grad()
+    def weights(self):
+        return pack_weights(self.net)
+
+    @torch.no_grad()
+    def collect(self, episode):
+        """(feature_words [N,4,4] int64, sums [N,4,K.BID_ROWS] int32, playouts) of episode `episode`: the teacher's launch
+        on every seat and the head's launch for its input rows."""
+        sums = self.env.playout_bids(episode, self.worlds, self.samples, contracts=self.contracts, salt=self.salt)
+        _, _, fw = self.env.bid_values(episode, self.weights(), self.scale, contracts=self.contracts, feature_words=True)
+        return fw, sums, self.worlds * self.samples
+
+    def iterate(self):
+        """collect() on a fresh episode and one step(); returns the loss before the step."""
+        fw, sums, playouts = self.collect(self.episode)
+        self.episode += 1
+        return self.step(fw, sums, playouts)
+
+    @torch.no_grad()
+    def round(self, episode, seats=15, threshold=0, deals=None, seats_per_game=None):
+        """The bidding round with the head on `seats`: (contract, declarer, king_suit) as reset() takes them."""
+        values = self.env.bid_values(episode, self.weights(), self.scale, contracts=self.contracts, deals=deals, seats=seats,
+                                     seats_per_game=seats_per_game)
+        return self.env.bid_round(episode, values, self.playouts_equiv, threshold=threshold, contracts=self.contracts, seats=seats,
+                                  seats_per_game=seats_per_game)

@@ -1105,3 +1105,32 @@ __device__ __forceinline__ void bid_round(u64 key, const int32_t *sums, int play
     }
     king = kg;
 }
+
+// ---------------------------------------------------------------------------
+// The bidding head (tarok_bid_values, include/tarok_env.h)
+// ---------------------------------------------------------------------------
+// The 256 0/1 features of a bidder, seat `seat` holding `hand`, in the policy's layout (feature f = bit f % 64 of word
+// f / 64).  Word 0: the hand (bits 0..53), the seat one-hot (54..57).  Word 1: thermometers — bit j (j < 12) iff the hand
+// holds more than j taroks, bit 16 + 8k + j (j < 8) iff more than j cards of suit k — then king of suit k held (48 + k)
+// and pagat, mond, skis held (52, 53, 54).  Words 2 and 3 are zero (reserved: the layer stays the policy's 256 inputs).
+// The kings and the trula are the cards of TK_V5: the suit cards among them, and its lowest, middle and highest tarok.
+__device__ __forceinline__ void bid_feature_words(u64 hand, u32 seat, u64 out[4]) {
+    constexpr u64 kings = TK_V5 & ~TK_TAROK, trula = TK_V5 & TK_TAROK;
+    constexpr u64 skis = 1ULL << (63 - __builtin_clzll(trula)), mond = trula & ~TK_PAGAT & ~skis;
+    hand &= TK_DECK;
+    const u32 nt = (u32)popc64(hand & TK_TAROK);
+    u64 w = (1ULL << (nt < 12u ? nt : 12u)) - 1ULL;
+#pragma unroll
+    for (u32 k = 0; k < 4; k++) {
+        const u64 suit = 0xFFULL << (8 * k);
+        w |= ((1ULL << (u32)popc64(hand & suit)) - 1ULL) << (16 + 8 * k);
+        w |= (u64)((hand & kings & suit) != 0) << (48 + k);
+    }
+    w |= (u64)((hand & TK_PAGAT) != 0) << 52;
+    w |= (u64)((hand & mond) != 0) << 53;
+    w |= (u64)((hand & skis) != 0) << 54;
+    out[0] = hand | (1ULL << (54 + (seat & 3u)));
+    out[1] = w;
+    out[2] = 0;
+    out[3] = 0;
+}

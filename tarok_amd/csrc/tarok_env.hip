@@ -3015,6 +3015,68 @@ __global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_mlp_
                                 nullptr, 15, nullptr, PlayMode{inv_t, greedy, thr, eps});
 }
 
+// tarok_bid_values: the bidding head — k_policy_mlp's forward (TILES = 1, the shared functions unchanged) on the twelve
+// cards of a hand.  A workgroup takes 32 games = 128 rows, row = 4 * local game + seat: threads below 128 build ext[row] =
+// bid_feature_words(the seat's hand, from k_bid_deal's buffer) under w1's prefetch; after the head, two lanes per row
+// (lane parity p: pieces p, p + 2, p + 4 of the row's five) turn outputs 0..18 into the row's twenty values — scaled,
+// clamped to +-2^30 (fmaxf first: a NaN becomes -2^30) and rounded to even — with tarok_playout_bids' zeros: a seat
+// outside the game's set, a row outside `contracts`, row 19, an invalid deal (all four hands zero).  A ragged last
+// workgroup's rows read game n - 1 and store nothing.  The env's games are not read.
+__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_bid_values(
+    int64_t n, const u64 *__restrict__ deal, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3,
+    const float *__restrict__ b3, float scale, u32 contracts, u32 seats, const uint8_t *__restrict__ seat_sets,
+    int4 *__restrict__ value_out, float4 *__restrict__ raw_out, ulonglong2 *__restrict__ feature_words_out) {
+    TK_VGPR_TOP(256, 255);
+    static_assert(TK_BLOCK == 2 * PM_M && PM_M % 4 == 0 && TK_BID_ROWS == 20 && TK_BID_ROWS <= 64, "two lanes per row, five pieces per row");
+    __shared__ __attribute__((aligned(16))) __bf16 X[PM_M * PM_LD];
+    __shared__ u64 ext[PM_M][4];
+    const int64_t base = (int64_t)blockIdx.x * (PM_M / 4);
+    const u32 tid = threadIdx.x, wave = tid >> 6;
+    float *L = reinterpret_cast<float *>(X);
+    bf16x8 wq[4][2];
+    mlp_prefetch(wq, w1, wave * 2);                // lands while the features are built
+    if (tid < PM_M) {
+        const u32 v = tid & 3u;
+        const int64_t gq = base + (tid >> 2), g = gq < n ? gq : n - 1;
+        bid_feature_words(deal[(int64_t)v * n + g], v, ext[tid]);
+        if (feature_words_out && gq < n) {
+            feature_words_out[(g * 4 + v) * 2] = make_ulonglong2(ext[tid][0], ext[tid][1]);
+            feature_words_out[(g * 4 + v) * 2 + 1] = make_ulonglong2(ext[tid][2], ext[tid][3]);
+        }
+    }
+    __syncthreads();
+    policy_expand(X, ext, tid);
+    __syncthreads();
+    mlp_hidden(X, w1, b1, wq, wave);
+    mlp_prefetch(wq, w2, wave * 2);
+    mlp_hidden(X, w2, b2, wq, wave);
+    mlp_head(X, L, w3, b3, wave, 0);
+    __syncthreads();
+    const u32 row = tid >> 1, v = row & 3u;
+    const int64_t g = base + (row >> 2);
+    if (g >= n) return;
+    const u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+    const bool live = ((set >> v) & 1u) && deal[(int64_t)v * n + g] != 0;     // (a valid deal's hand holds twelve cards)
+    const u32 rowmask = live ? bid_row_mask(contracts) : 0u;                  // (19 bits: row 19 is never set)
+#pragma unroll
+    for (u32 p = tid & 1u; p < TK_BID_ROWS / 4; p += 2) {
+        const float4 y = *reinterpret_cast<const float4 *>(L + row * PM_LL + 4 * p);
+        const float yy[4] = {y.x, y.y, y.z, y.w};
+        float rw[4];
+        int vl[4];
+#pragma unroll
+        for (u32 j = 0; j < 4; j++) {
+            const bool keep = (rowmask >> (4 * p + j)) & 1u;
+            rw[j] = keep ? yy[j] : 0.f;
+            vl[j] = keep ? (int)rintf(fminf(fmaxf(yy[j] * scale, -1073741824.f), 1073741824.f)) : 0;
+        }
+        const int64_t o = (g * 4 + v) * (TK_BID_ROWS / 4) + p;
+        if (value_out) value_out[o] = make_int4(vl[0], vl[1], vl[2], vl[3]);
+        if (raw_out) raw_out[o] = make_float4(rw[0], rw[1], rw[2], rw[3]);
+    }
+}
+
 // tarok_policy_step: tarok_policy_mlp and tarok_step in ONE launch.  A play workgroup (512
 // threads, 256 games = the 256 slots of step group blockIdx.x) evaluates the policy for its games
 // as two 128-game tiles side by side, leaves the sampled cards in LDS and then runs the step
@@ -3799,6 +3861,24 @@ int tarok_bid_round(tarok_env *e, uint32_t episode, const int32_t *sums, int pla
     hipLaunchKernelGGL(k_bid_round, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, episode, sums, playouts,
                        threshold, (u32)contracts, (u32)(sums ? seats : 0), sums ? seats_per_game : nullptr, contract_out, declarer_out,
                        king_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int tarok_bid_values(tarok_env *e, uint32_t episode, const uint8_t *deals, const void *w1, const float *b1, const void *w2,
+                     const float *b2, const void *w3, const float *b3, float scale, int contracts, int seats,
+                     const uint8_t *seats_per_game, int32_t *value_out, float *raw_out, uint64_t *feature_words_out, void *stream) {
+    if (!e || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !(scale > 0.f) || scale > 1048576.f || contracts < 1 ||
+        contracts > TAROK_BID_ALL_CONTRACTS || seats < 0 || seats > 15 || (!value_out && !raw_out && !feature_words_out))
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    if (!e->bid_deal) HIPCHK(hipMalloc((void **)&e->bid_deal, (size_t)e->n * 5 * sizeof(u64)));   // tarok_playout_bids' buffer
+    hipLaunchKernelGGL(k_bid_deal, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, episode, deals, e->bid_deal);
+    const int64_t games = PM_M / 4;                  // per workgroup: one 128-row tile
+    hipLaunchKernelGGL(k_bid_values, dim3((unsigned)((e->n + games - 1) / games)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
+                       e->bid_deal, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3, scale, (u32)contracts,
+                       (u32)seats, seats_per_game, reinterpret_cast<int4 *>(value_out), reinterpret_cast<float4 *>(raw_out),
+                       reinterpret_cast<ulonglong2 *>(feature_words_out));
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }

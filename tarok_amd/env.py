@@ -404,6 +404,33 @@ class TarokVecEnv:
                                                  self._p(out[1]), self._p(out[2]), self._stream()))
         return tuple(out)
 
+    def bid_values(self, episode, weights, scale, contracts=K.BID_DEFAULT_CONTRACTS, deals=None, seats=15, seats_per_game=None,
+                   value_out=None, raw=False, feature_words=False):
+        """The bidding head (tarok_bid_values): playout_bids()' array written by a network from the twelve cards of each
+        hand, BEFORE reset(), for the game reset(episode, deals) would deal.  weights = (w1, b1, w2, b2, w3, b3) as
+        policy_mlp takes them; the input row of seat v is the hand, the one-hot seat and the tarok / suit-length / king /
+        trula features of include/tarok_env.h, and output o < 19 of the network is bid row o (karte.bid_row).  Returns
+        value [N, 4, K.BID_ROWS] int32 = the outputs times `scale` (0 < scale <= 2**20), clamped to +-2**30 and rounded to
+        even, with playout_bids()' zeros (seats outside `seats` / `seats_per_game`, options outside `contracts`, row 19,
+        an invalid deal): bid_round(episode, value, playouts, ...) takes it as its sums.  raw=True also returns the
+        unscaled float32 outputs [N, 4, K.BID_ROWS] (same zeros), feature_words=True the input rows as bits
+        [N, 4, 4] int64 (expand_feature_words; every seat, in the set or not): (value, raw, feature_words), None for what
+        was not asked for.  Does not read or write the env's games."""
+        w1, b1, w2, b2, w3, b3 = self.check_mlp_weights(weights)
+        deals = self._dev(deals, torch.uint8, (self.n, 54))
+        with torch.cuda.device(self.device):
+            if value_out is None:
+                value_out = torch.empty((self.n, 4, K.BID_ROWS), dtype=torch.int32, device=self.device)
+            raw_out = torch.empty((self.n, 4, K.BID_ROWS), dtype=torch.float32, device=self.device) if raw else None
+            fw_out = torch.empty((self.n, 4, 4), dtype=torch.int64, device=self.device) if feature_words else None
+            _native.check(self.L.tarok_bid_values(self._h, int(episode), self._p(deals), self._p(w1), self._p(b1), self._p(w2),
+                                                  self._p(b2), self._p(w3), self._p(b3), float(scale), int(contracts), int(seats),
+                                                  self._p(self._seat_sets(seats_per_game)), self._p(value_out), self._p(raw_out),
+                                                  self._p(fw_out), self._stream()))
+        if not raw and not feature_words:
+            return value_out
+        return value_out, raw_out, fw_out
+
     def shown_voids(self, out=None):
         """[N] int32 device tensor (tarok_shown_voids; the bits of a u32): bit 5 * seat + class of a game's word is set
         iff the play so far has shown that seat to hold no card of that class (class = min(card >> 3, 4): the four suits,

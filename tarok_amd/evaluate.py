@@ -346,3 +346,53 @@ def evaluate_bidding_vs_bot(worlds, samples, n_games, episodes, seed=0, device=0
     duplicate_advantage's dict, `policy_mean` being that of the seat that bid by playouts."""
     return duplicate_advantage(_bidding_passes(worlds, samples, n_games, episodes, seed, device, salt=salt, threshold=threshold,
                                                contracts=contracts, inspect=inspect))
+
+
+def _bidnet_passes(bid_weights, n_games, episodes, seed, device, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, playouts_equiv=16,
+                   reward_scale=1.0 / 70.0, inspect=None):
+    """_bidding_passes with the bidding head in the playout teacher's place: per pass ONE tarok_bid_values at scale =
+    playouts_equiv / reward_scale with the pass's seat set and ONE tarok_bid_round at playouts = playouts_equiv, a reset
+    that takes their contract, declarer and king (the Bot's exchange), then the Bot's card on every seat at every move.
+    inspect: one dict per pass — episode, seats, contract, declarer, king_suit, values [N,4,K.BID_ROWS] i32, start,
+    actions, scores."""
+    n = int(n_games)
+    weights = TarokVecEnv.check_mlp_weights(bid_weights)
+    scale = float(int(playouts_equiv) / float(reward_scale))
+    scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
+    env = TarokVecEnv(n, device=device, seed=seed, mix=K.MIX_BOT)
+    try:
+        with torch.cuda.device(env.device):
+            actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
+            zeros = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=env.device)
+        values = _bid_bufs(env, n)
+        for e in range(int(episodes)):
+            for p, seats in enumerate(PASS_SEATS):
+                env.bid_values(e, weights, scale, contracts=contracts, seats=seats, value_out=values)
+                c, d, k = env.bid_round(e, values, int(playouts_equiv), threshold=threshold, contracts=contracts, seats=seats)
+                setup = dict(contract=c, declarer=d, king_suit=k)
+                env.reset(episode=e, clear_counters=True, **setup)
+                start = env.state() if inspect is not None else None
+                for t in range(GAME_CARDS):
+                    env.playout_cards(1, seats=0, sum_out=zeros, action_out=actions[t])
+                    env.step(actions[t], auto_reset=False)
+                _, ss = env.counters()                # (the pass's one synchronisation)
+                scores[p, e * n:(e + 1) * n] = ss
+                if inspect is not None:
+                    inspect.append(dict(episode=e, seats=seats, start=start, actions=actions.cpu().numpy(), scores=ss.copy(),
+                                        values=values.cpu().numpy(), **{k_: v.cpu().numpy() for k_, v in setup.items()}))
+    finally:
+        env.close()
+    return scores
+
+
+def evaluate_bidnet_vs_bot(bid_weights, n_games, episodes, seed=0, device=0, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS,
+                           playouts_equiv=16, reward_scale=1.0 / 70.0, inspect=None):
+    """What is the bidding head's bid worth?  evaluate_bidding_vs_bot with tarok_bid_values in tarok_playout_bids' place:
+    the five duplicate passes on K.MIX_BOT's deals with the Bot making EVERY exchange and playing EVERY card; in pass
+    1 + k seat k bids from the network's values — bid_weights = (w1, b1, w2, b2, w3, b3) as tarok_bid_values takes them
+    (bidding.BidLearner.weights()), scaled to sums over `playouts_equiv` playouts of `reward_scale` points, so that
+    `threshold` is in points per game as for the teacher — against three Bot bidders.  Pass 0 is the Bot's own round on
+    every seat: evaluate_bidding_vs_bot's pass 0 on the same deals.  Returns duplicate_advantage's dict, `policy_mean`
+    being that of the seat the head bid for."""
+    return duplicate_advantage(_bidnet_passes(bid_weights, n_games, episodes, seed, device, threshold=threshold, contracts=contracts,
+                                              playouts_equiv=playouts_equiv, reward_scale=reward_scale, inspect=inspect))
