@@ -1313,7 +1313,7 @@ TK_KERNEL(TK_BLOCK, 96) void k_rollout(int64_t n, u64 seed, u64 offset, u32 epis
     if (nsteps_out) nsteps_out[i] = (int16_t)played;
 }
 
-// One playout, shared by k_playout and k_playout_det: card c on the position h (`played` cards into its game), then the
+// One playout, shared by every playout kernel: card c on the position h (`played` cards into its game), then the
 // Bot's cards to the end under pkey (draw 128 + q at q cards played).  Returns the four final scores, packed.
 __device__ __forceinline__ u64 playout_from(Game &h, u32 c, u64 pkey, u32 played) {
     u64 scores = 0;
@@ -1341,165 +1341,210 @@ __device__ __forceinline__ u64 playout_from(Game &h, u32 c, u64 pkey, u32 played
     return scores;
 }
 
-// tarok_playout_cards: open-hand Monte-Carlo playouts from the env's CURRENT positions (the true hidden hands: perfect
-// information, not a fair player).  Read-only on the env.  A team of 2^lg lanes (4 .. 256, the host picks it from
-// `samples`) owns one game; the game's work items (rank j of a legal card, sample k), nlegal * samples of them, are dealt
-// round-robin over the team's lanes, so a follower's two legal cards keep as many lanes busy as a leader's twelve.  All
-// lanes of a team play the same game on from the same card count: their playouts have the same length (a Berac may end
-// early in some of them), and the loops below branch on team-uniform values.  The four scores of a playout are added to
-// the team's [12][4] row block in LDS (integer adds: the result does not depend on the lane layout), which one pass
-// writes to sum_out as 16-byte rows and reads for the card.  A game that does not take part runs no playout: zero rows.
+// ---- The playout launches (k_playout, _det, _voids, _hidden, _exchange, _bids): their shared pieces ----
 #define TK_PO_MIN_LG 2
 #define TK_PO_MAX_LG 8
+#define TK_PO_WORLD_SLOTS 64
+
+// A team of 2^lg lanes (4 .. 256, the host picks lg from the playouts per row) owns game g; a workgroup holds `teams` of
+// them.  With worlds, the team's world records are slots slot0 .. slot0 + worlds - 1 of the workgroup's TK_PO_WORLD_SLOTS.
+struct PlayoutTeam {
+    u32 team, L, lane, teams;
+    int64_t g;
+    u32 slot0;
+    __device__ __forceinline__ PlayoutTeam(u32 lg, u32 worlds = 0)
+        : team(threadIdx.x >> lg), L(1u << lg), lane(threadIdx.x & (L - 1u)), teams((u32)TK_BLOCK >> lg),
+          g((int64_t)blockIdx.x * teams + team), slot0(team * worlds) {}
+    // zeroes the workgroup's row blocks of INTS sums per team (no barrier: the caller's next one covers it) -> the team's block
+    template <u32 INTS> __device__ __forceinline__ int *zero_rows(int *sums) const {
+        for (u32 w = threadIdx.x; w < teams * INTS; w += TK_BLOCK) sums[w] = 0;
+        return sums + team * INTS;
+    }
+};
+
+// The four scores of one playout into row j of a team's block: integer LDS adds, so the sums do not depend on the lane layout.
+__device__ __forceinline__ void add_scores(int *row, u32 j, u64 scores) {
+    atomicAdd(row + j * 4 + 0, (int)(int16_t)scores);
+    atomicAdd(row + j * 4 + 1, (int)(int16_t)(scores >> 16));
+    atomicAdd(row + j * 4 + 2, (int)(int16_t)(scores >> 32));
+    atomicAdd(row + j * 4 + 3, (int)(int16_t)(scores >> 48));
+}
+
+// The smallest of rows 0 .. count - 1 at the maximum of `seat`'s sums.
+__device__ __forceinline__ u32 best_row(const int *row, u32 count, u32 seat) {
+    u32 best = 0;
+    int top = row[seat];
+    for (u32 j = 1; j < count; j++) {
+        int v = row[j * 4 + seat];
+        if (v > top) { top = v; best = j; }
+    }
+    return best;
+}
+
+// The position a card launch plays from.  All zero for a game that is not in play.
+struct CardPosition {
+    u64 legal = 0;
+    u32 mover = 0, played = 0;
+    bool in_play = false, takes_part = false;        // takes_part: in play with the mover in the game's seat set
+};
+__device__ __forceinline__ CardPosition card_position(const Game &g0, const uint8_t *__restrict__ seat_sets, u32 seats, int64_t g) {
+    CardPosition p;
+    p.in_play = g0.phase == TK_PHASE_PLAY;
+    if (p.in_play) {
+        p.legal = legal_now(g0);
+        p.mover = (g0.leader + g0.nt) & 3;
+        p.played = g0.trick_no * 4 + g0.nt;
+        u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+        p.takes_part = (set >> p.mover) & 1u;
+    }
+    return p;
+}
+
+// A card launch's outputs for game t.g (t.g < n): the team's twelve 16-byte rows, and on lane 0 the card — the smallest
+// rank at the maximum of the mover's sums, the Bot's card where the mover is outside the seat set, 255 where nothing is
+// to be played.
+__device__ __forceinline__ void card_epilogue(const PlayoutTeam &t, const int *row, const CardPosition &p, u32 nlegal,
+                                              const u64 *__restrict__ gkey, int4 *__restrict__ sum_out, uint8_t *__restrict__ action_out) {
+    if (sum_out)
+        for (u32 r = t.lane; r < TAROK_PLAYOUT_RANKS; r += t.L) sum_out[t.g * TAROK_PLAYOUT_RANKS + r] = reinterpret_cast<const int4 *>(row)[r];
+    if (action_out && t.lane == 0) {
+        u32 act = 255;
+        if (p.takes_part) act = kth_bit(p.legal, best_row(row, nlegal, p.mover));
+        else if (p.in_play) act = policy_action(gkey[t.g], p.played, p.legal);
+        action_out[t.g] = (uint8_t)act;
+    }
+}
+
+// What a dealt world leaves in LDS for the items that play in it: one record per world slot, as separate arrays.
+struct WorldAB {                                     // (A plane, B plane, team), 20 bytes a world: _det, _voids, _exchange
+    u64 a[TK_PO_WORLD_SLOTS], b[TK_PO_WORLD_SLOTS];
+    u32 team[TK_PO_WORLD_SLOTS];
+    __device__ __forceinline__ void store(u32 slot, const Game &d) { a[slot] = d.A; b[slot] = d.B; team[slot] = d.team; }
+    __device__ __forceinline__ void load(u32 slot, Game &h) const { h.A = a[slot]; h.B = b[slot]; h.team = team[slot]; }
+};
+struct WorldABCT {                                   // (A, B, C, talon ids, team), 36 bytes a world: _hidden, whose re-deal
+    u64 a[TK_PO_WORLD_SLOTS], b[TK_PO_WORLD_SLOTS], c[TK_PO_WORLD_SLOTS], ids[TK_PO_WORLD_SLOTS];   // moves C-plane and talon cards
+    u32 team[TK_PO_WORLD_SLOTS];
+    __device__ __forceinline__ void store(u32 slot, const Game &d) {
+        a[slot] = d.A; b[slot] = d.B; c[slot] = d.C; ids[slot] = d.talon; team[slot] = d.team;
+    }
+    __device__ __forceinline__ void load(u32 slot, Game &h) const {
+        h.A = a[slot]; h.B = b[slot]; h.C = c[slot]; h.talon = ids[slot]; h.team = team[slot];
+    }
+};
+struct NoWorlds {                                    // the open-hand launch: the position itself is the one world
+    __device__ __forceinline__ void store(u32, const Game &) {}
+    __device__ __forceinline__ void load(u32, Game &) const {}
+};
+
+// The dealers of the card launches: which worlds the playouts run in.  Extra is the dealer's per-game word (NoWord: none),
+// deal() turns a copy of the position into world `key`'s, and the tags are the top bits of the game_key counters.
+struct NoWord {};
+template <class T> __device__ __forceinline__ T game_word(const T *__restrict__ words, int64_t g) {
+    if constexpr (std::is_empty<T>::value) return T{}; else return words[g];
+}
+struct DealOpen {                                    // k_playout: the true hands
+    static constexpr bool has_worlds = false;
+    using Record = NoWorlds;
+    using Extra = NoWord;
+    static constexpr u64 world_tag = 0, item_tag = 1ULL << 63;
+    __device__ static __forceinline__ void deal(Game &, u32, u64, NoWord) {}
+};
+template <class R, class X> struct DealWorlds {
+    static constexpr bool has_worlds = true;
+    using Record = R;
+    using Extra = X;
+    static constexpr u64 world_tag = 7ULL << 61, item_tag = 3ULL << 62;
+};
+struct DealUnseen : DealWorlds<WorldAB, NoWord> {    // k_playout_det: the cards the mover cannot see, re-dealt
+    __device__ static __forceinline__ void deal(Game &d, u32 mover, u64 key, NoWord) { redeal_unseen(d, mover, key); }
+};
+struct DealVoids : DealWorlds<WorldAB, u32> {        // k_playout_voids: ... and no seat a card of a class it has shown void in
+    __device__ static __forceinline__ void deal(Game &d, u32 mover, u64 key, u32 voids) { redeal_voids(d, mover, key, voids); }
+};
+struct DealHidden : DealWorlds<WorldABCT, u64> {     // k_playout_hidden: ... and Klop's talon and the declarer's discards too
+    __device__ static __forceinline__ void deal(Game &d, u32 mover, u64 key, u64 played) { redeal_hidden(d, mover, key, played); }
+};
+
+// The card launches' one body: Monte-Carlo playouts from the env's CURRENT positions, read-only on the env.  A team owns
+// one game.  With worlds, a world is dealt ONCE: lanes w = lane, lane + L, ... of the team each deal one world under the
+// world key and leave its record in LDS (teams * worlds <= TK_PO_WORLD_SLOTS by the host's lg); without, the position's
+// true hands are the one world.  After one barrier the game's work items (rank j of a legal card, world w, sample k),
+// nlegal * worlds * samples of them, go round-robin over the team's lanes, so a follower's two legal cards keep as many
+// lanes busy as a leader's twelve: each unpacks the position, loads its world and runs playout_from under the item key.
+// All lanes of a team play the same game on from the same card count: their playouts have the same length (a Berac may
+// end early in some of them), and the loops branch on team-uniform values.  The four scores go into the team's [12][4]
+// row block in LDS; after a second barrier card_epilogue writes the rows and the card.  A game that does not take part
+// runs no playout: zero rows.  Nothing of the env is written; no global atomics.
+template <class Dealer>
+__device__ __forceinline__ void playout_cards_body(int64_t n, u64 pseed, u64 offset, u32 worlds, u32 samples, u32 lg, u32 seats,
+                                                   const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                                   const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                                   const u64 *__restrict__ gkey, const typename Dealer::Extra *__restrict__ extra,
+                                                   int4 *__restrict__ sum_out, uint8_t *__restrict__ action_out) {
+    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> TK_PO_MIN_LG) * TAROK_PLAYOUT_RANKS * 4];
+    __shared__ typename Dealer::Record world;
+    const PlayoutTeam t(lg, worlds);
+    const int64_t g = t.g;
+    int *row = t.zero_rows<TAROK_PLAYOUT_RANKS * 4>(sums);
+    ulonglong2 a = {0, 0}, b = {0, 0};
+    CardPosition p;
+    u64 ebase = 0;
+    u32 nlegal = 0;
+    if (g < n) {
+        a = s01[g]; b = s23[g];
+        Game g0;
+        unpack(g0, a.x, a.y, b.x, b.y);
+        p = card_position(g0, seat_sets, seats, g);
+        if (p.takes_part) {
+            nlegal = (u32)popc64(p.legal);
+            ebase = ((u64)cnt[g].episode << 28) | ((u64)p.played << 22);
+            if constexpr (Dealer::has_worlds) {
+                const typename Dealer::Extra word = game_word(extra, g);
+                for (u32 w = t.lane; w < worlds; w += t.L) {
+                    Game d = g0;
+                    Dealer::deal(d, p.mover, game_key(pseed, offset + (u64)g, Dealer::world_tag | ebase | (u64)w), word);
+                    world.store(t.slot0 + w, d);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (p.takes_part) {
+        const u32 per_card = Dealer::has_worlds ? worlds * samples : samples, items = nlegal * per_card;
+        for (u32 i = t.lane; i < items; i += t.L) {
+            u32 j = i / per_card, k = i - j * per_card, w = 0;
+            if constexpr (Dealer::has_worlds) { w = k / samples; k -= w * samples; }
+            u32 c = kth_bit(p.legal, j);
+            u64 pkey = game_key(pseed, offset + (u64)g, Dealer::item_tag | ebase | ((u64)c << 16) | ((u64)w << 10) | (u64)k);
+            Game h;
+            unpack(h, a.x, a.y, b.x, b.y);
+            world.load(t.slot0 + w, h);
+            add_scores(row, j, playout_from(h, c, pkey, p.played));
+        }
+    }
+    __syncthreads();
+    if (g < n) card_epilogue(t, row, p, nlegal, gkey, sum_out, action_out);
+}
+
+// tarok_playout_cards: the open-hand launch — the playouts see the true hidden hands (perfect information, not a fair player).
 TK_KERNEL(TK_BLOCK, 128) void k_playout(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 samples, u32 lg, u32 seats,
                                        const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
                                        const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
                                        const u64 *__restrict__ gkey, int4 *__restrict__ sum_out, uint8_t *__restrict__ action_out) {
     TK_VGPR_TOP(128, 127);
-    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> TK_PO_MIN_LG) * TAROK_PLAYOUT_RANKS * 4];
-    const u32 tid = threadIdx.x, team = tid >> lg, L = 1u << lg, lane = tid & (L - 1u), teams = (u32)TK_BLOCK >> lg;
-    const int64_t g = (int64_t)blockIdx.x * teams + team;
-    for (u32 w = tid; w < teams * (TAROK_PLAYOUT_RANKS * 4); w += TK_BLOCK) sums[w] = 0;
-    __syncthreads();
-    int *row = sums + team * (TAROK_PLAYOUT_RANKS * 4);
-    u64 legal = 0;
-    u32 mover = 0, played = 0, nlegal = 0;
-    bool in_play = false, takes_part = false;
-    if (g < n) {
-        const ulonglong2 a = s01[g], b = s23[g];
-        Game g0;
-        unpack(g0, a.x, a.y, b.x, b.y);
-        in_play = g0.phase == TK_PHASE_PLAY;
-        if (in_play) {
-            legal = legal_now(g0);
-            mover = (g0.leader + g0.nt) & 3;
-            played = g0.trick_no * 4 + g0.nt;
-            u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
-            takes_part = (set >> mover) & 1u;
-        }
-        if (takes_part) {
-            nlegal = (u32)popc64(legal);
-            const u64 ebase = (1ULL << 63) | ((u64)cnt[g].episode << 28) | ((u64)played << 22);
-            const u32 items = nlegal * samples;
-            for (u32 i = lane; i < items; i += L) {
-                u32 j = i / samples, k = i - j * samples;
-                u32 c = kth_bit(legal, j);
-                u64 pkey = game_key(pseed, offset + (u64)g, ebase | ((u64)c << 16) | (u64)k);
-                Game h;
-                unpack(h, a.x, a.y, b.x, b.y);
-                u64 scores = playout_from(h, c, pkey, played);
-                atomicAdd(row + j * 4 + 0, (int)(int16_t)scores);
-                atomicAdd(row + j * 4 + 1, (int)(int16_t)(scores >> 16));
-                atomicAdd(row + j * 4 + 2, (int)(int16_t)(scores >> 32));
-                atomicAdd(row + j * 4 + 3, (int)(int16_t)(scores >> 48));
-            }
-        }
-    }
-    __syncthreads();
-    if (g >= n) return;
-    if (sum_out)
-        for (u32 r = lane; r < TAROK_PLAYOUT_RANKS; r += L) sum_out[g * TAROK_PLAYOUT_RANKS + r] = reinterpret_cast<const int4 *>(row)[r];
-    if (action_out && lane == 0) {
-        u32 act = 255;
-        if (takes_part) {                            // the smallest rank at the maximum of the mover's sums
-            u32 best = 0;
-            int top = row[mover];
-            for (u32 j = 1; j < nlegal; j++) {
-                int v = row[j * 4 + mover];
-                if (v > top) { top = v; best = j; }
-            }
-            act = kth_bit(legal, best);
-        } else if (in_play) {
-            act = policy_action(gkey[g], played, legal);
-        }
-        action_out[g] = (uint8_t)act;
-    }
+    playout_cards_body<DealOpen>(n, pseed, offset, 0u, samples, lg, seats, seat_sets, s01, s23, cnt, gkey, nullptr, sum_out, action_out);
 }
 
 // tarok_playout_cards_det: determinized playouts — k_playout's sibling for a FAIR player.  The playouts of world w run on
 // a re-deal of the cards the mover cannot see (redeal_unseen under the world key), so the result is a function of the
-// mover's information set alone.  A team of 2^lg lanes owns one game (lg from worlds * samples by k_playout's rule, so
-// teams * worlds <= TK_PO_WORLD_SLOTS).  A world is dealt ONCE: lanes w = lane, lane + L, ... of the team each deal one
-// world and leave its (A plane, B plane, team) in LDS, 20 bytes; after one barrier the work items (rank j, world w,
-// sample k), nlegal * worlds * samples of them, go round-robin over the team: each builds its candidate game from the
-// position's packed words and its world's planes and runs playout_from.  Sums, rows and the card are k_playout's.
-// Nothing of the env is written; no global atomics.
-#define TK_PO_WORLD_SLOTS 64
+// mover's information set alone.
 TK_KERNEL(TK_BLOCK, 128) void k_playout_det(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 samples, u32 lg,
                                            u32 seats, const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
                                            const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
                                            const u64 *__restrict__ gkey, int4 *__restrict__ sum_out, uint8_t *__restrict__ action_out) {
     TK_VGPR_TOP(128, 127);
-    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> TK_PO_MIN_LG) * TAROK_PLAYOUT_RANKS * 4];
-    __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS];
-    __shared__ u32 world_team[TK_PO_WORLD_SLOTS];
-    const u32 tid = threadIdx.x, team = tid >> lg, L = 1u << lg, lane = tid & (L - 1u), teams = (u32)TK_BLOCK >> lg;
-    const int64_t g = (int64_t)blockIdx.x * teams + team;
-    for (u32 w = tid; w < teams * (TAROK_PLAYOUT_RANKS * 4); w += TK_BLOCK) sums[w] = 0;
-    int *row = sums + team * (TAROK_PLAYOUT_RANKS * 4);
-    const u32 slot0 = team * worlds;                 // the team's worlds: slots slot0 .. slot0 + worlds - 1
-    ulonglong2 a = {0, 0}, b = {0, 0};
-    u64 legal = 0, ebase = 0;
-    u32 mover = 0, played = 0, nlegal = 0;
-    bool in_play = false, takes_part = false;
-    if (g < n) {
-        a = s01[g]; b = s23[g];
-        Game g0;
-        unpack(g0, a.x, a.y, b.x, b.y);
-        in_play = g0.phase == TK_PHASE_PLAY;
-        if (in_play) {
-            legal = legal_now(g0);
-            mover = (g0.leader + g0.nt) & 3;
-            played = g0.trick_no * 4 + g0.nt;
-            u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
-            takes_part = (set >> mover) & 1u;
-        }
-        if (takes_part) {
-            nlegal = (u32)popc64(legal);
-            ebase = ((u64)cnt[g].episode << 28) | ((u64)played << 22);
-            for (u32 w = lane; w < worlds; w += L) {
-                Game d = g0;
-                redeal_unseen(d, mover, game_key(pseed, offset + (u64)g, (7ULL << 61) | ebase | (u64)w));
-                world_a[slot0 + w] = d.A; world_b[slot0 + w] = d.B; world_team[slot0 + w] = d.team;
-            }
-        }
-    }
-    __syncthreads();
-    if (takes_part) {
-        const u32 per_card = worlds * samples, items = nlegal * per_card;
-        for (u32 i = lane; i < items; i += L) {
-            u32 j = i / per_card, rem = i - j * per_card, w = rem / samples, k = rem - w * samples;
-            u32 c = kth_bit(legal, j);
-            u64 pkey = game_key(pseed, offset + (u64)g, (3ULL << 62) | ebase | ((u64)c << 16) | ((u64)w << 10) | (u64)k);
-            Game h;
-            unpack(h, a.x, a.y, b.x, b.y);
-            h.A = world_a[slot0 + w]; h.B = world_b[slot0 + w]; h.team = world_team[slot0 + w];
-            u64 scores = playout_from(h, c, pkey, played);
-            atomicAdd(row + j * 4 + 0, (int)(int16_t)scores);
-            atomicAdd(row + j * 4 + 1, (int)(int16_t)(scores >> 16));
-            atomicAdd(row + j * 4 + 2, (int)(int16_t)(scores >> 32));
-            atomicAdd(row + j * 4 + 3, (int)(int16_t)(scores >> 48));
-        }
-    }
-    __syncthreads();
-    if (g >= n) return;
-    if (sum_out)
-        for (u32 r = lane; r < TAROK_PLAYOUT_RANKS; r += L) sum_out[g * TAROK_PLAYOUT_RANKS + r] = reinterpret_cast<const int4 *>(row)[r];
-    if (action_out && lane == 0) {
-        u32 act = 255;
-        if (takes_part) {                            // the smallest rank at the maximum of the mover's sums
-            u32 best = 0;
-            int top = row[mover];
-            for (u32 j = 1; j < nlegal; j++) {
-                int v = row[j * 4 + mover];
-                if (v > top) { top = v; best = j; }
-            }
-            act = kth_bit(legal, best);
-        } else if (in_play) {
-            act = policy_action(gkey[g], played, legal);
-        }
-        action_out[g] = (uint8_t)act;
-    }
+    playout_cards_body<DealUnseen>(n, pseed, offset, worlds, samples, lg, seats, seat_sets, s01, s23, cnt, gkey, nullptr, sum_out, action_out);
 }
 
 // tarok_playout_exchange: the declarer's talon exchange valued by determinized playouts — k_playout_det's structure one
@@ -1522,15 +1567,13 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_exchange(int64_t n, u64 pseed /* seed ^ 
                                                 uint8_t *__restrict__ discards_out) {
     TK_VGPR_TOP(128, 127);
     __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> TK_PX_MIN_LG) * TK_PX_ROWS * 4];
-    __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS];
-    __shared__ u32 world_team[TK_PO_WORLD_SLOTS];
+    __shared__ WorldAB world;
     __shared__ u32 cand_dpk[(TK_BLOCK >> TK_PX_MIN_LG) * TK_PX_ROWS];
-    const u32 tid = threadIdx.x, team = tid >> lg, L = 1u << lg, lane = tid & (L - 1u), teams = (u32)TK_BLOCK >> lg;
-    const int64_t g = (int64_t)blockIdx.x * teams + team;
-    for (u32 w = tid; w < teams * (TK_PX_ROWS * 4); w += TK_BLOCK) sums[w] = 0;
-    int *row = sums + team * (TK_PX_ROWS * 4);
-    u32 *cand = cand_dpk + team * TK_PX_ROWS;
-    const u32 slot0 = team * worlds;                 // the team's worlds: slots slot0 .. slot0 + worlds - 1
+    const PlayoutTeam t(lg, worlds);
+    const u32 L = t.L, lane = t.lane;
+    const int64_t g = t.g;
+    int *row = t.zero_rows<TK_PX_ROWS * 4>(sums);
+    u32 *cand = cand_dpk + t.team * TK_PX_ROWS;
     ulonglong2 a = {0, 0}, b = {0, 0};
     u64 ebase = 0;
     u32 declarer = 0, ncand = 0;
@@ -1552,7 +1595,7 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_exchange(int64_t n, u64 pseed /* seed ^ 
             for (u32 w = lane; w < worlds; w += L) {
                 Game d = g0;
                 redeal_unseen(d, declarer, game_key(pseed, offset + (u64)g, (7ULL << 61) | ebase | (63ULL << 22) | (u64)w));
-                world_a[slot0 + w] = d.A; world_b[slot0 + w] = d.B; world_team[slot0 + w] = d.team;
+                world.store(t.slot0 + w, d);
             }
             for (u32 r = lane; r < ncand; r += L) {
                 u32 i = r / sets, d = r - i * sets;
@@ -1570,15 +1613,11 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_exchange(int64_t n, u64 pseed /* seed ^ 
                                 (3ULL << 62) | ebase | (63ULL << 22) | ((u64)(8u * i + d) << 16) | ((u64)w << 10) | (u64)k);
             Game h;
             unpack(h, a.x, a.y, b.x, b.y);
-            h.A = world_a[slot0 + w]; h.B = world_b[slot0 + w]; h.team = world_team[slot0 + w];
+            world.load(t.slot0 + w, h);
             const u32 dpk = cand[r];
             apply_exchange(h, i, dpk & 255, (dpk >> 8) & 255, (dpk >> 16) & 255);
             u32 c = policy_action(pkey, 0u, legal_now(h));
-            u64 scores = playout_from(h, c, pkey, 0u);
-            atomicAdd(row + r * 4 + 0, (int)(int16_t)scores);
-            atomicAdd(row + r * 4 + 1, (int)(int16_t)(scores >> 16));
-            atomicAdd(row + r * 4 + 2, (int)(int16_t)(scores >> 32));
-            atomicAdd(row + r * 4 + 3, (int)(int16_t)(scores >> 48));
+            add_scores(row, r, playout_from(h, c, pkey, 0u));
         }
     }
     __syncthreads();
@@ -1590,12 +1629,7 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_exchange(int64_t n, u64 pseed /* seed ^ 
         int ch = -1;
         u32 dpk = 0xFFFFFFu;
         if (takes_part) {                            // the first candidate at the maximum of the declarer's sums
-            u32 best = 0;
-            int top = row[declarer];
-            for (u32 r = 1; r < ncand; r++) {
-                int v = row[r * 4 + declarer];
-                if (v > top) { top = v; best = r; }
-            }
+            const u32 best = best_row(row, ncand, declarer);
             ch = (int)(best / sets);
             dpk = cand[best];
         } else if (waiting) {                        // the Bot's own exchange: group 0, its sampler under the game's key
@@ -1645,8 +1679,7 @@ TK_KERNEL(TK_BLOCK, 64) void k_shown_voids(int64_t n, const ulonglong2 *__restri
 }
 
 // tarok_playout_cards_voids: k_playout_det with worlds that honour shown voids — world w is redeal_voids(..., voids[g])
-// under the same world key; a game whose word shows no void of another seat gets redeal_unseen's worlds.  The same
-// structure: the dealing lanes leave one world each in LDS, one barrier, the items run playout_from.  The binomials come
+// under the same world key; a game whose word shows no void of another seat gets redeal_unseen's worlds.  The binomials come
 // from constant memory (tk_binom); the (a, b) weights are recomputed per world in registers, so the LDS is k_playout_det's.
 TK_KERNEL(TK_BLOCK, 128) void k_playout_voids(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 samples, u32 lg,
                                              u32 seats, const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
@@ -1654,77 +1687,7 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_voids(int64_t n, u64 pseed /* seed ^ sal
                                              const u64 *__restrict__ gkey, const u32 *__restrict__ voids,
                                              int4 *__restrict__ sum_out, uint8_t *__restrict__ action_out) {
     TK_VGPR_TOP(128, 127);
-    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> TK_PO_MIN_LG) * TAROK_PLAYOUT_RANKS * 4];
-    __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS];
-    __shared__ u32 world_team[TK_PO_WORLD_SLOTS];
-    const u32 tid = threadIdx.x, team = tid >> lg, L = 1u << lg, lane = tid & (L - 1u), teams = (u32)TK_BLOCK >> lg;
-    const int64_t g = (int64_t)blockIdx.x * teams + team;
-    for (u32 w = tid; w < teams * (TAROK_PLAYOUT_RANKS * 4); w += TK_BLOCK) sums[w] = 0;
-    int *row = sums + team * (TAROK_PLAYOUT_RANKS * 4);
-    const u32 slot0 = team * worlds;                 // the team's worlds: slots slot0 .. slot0 + worlds - 1
-    ulonglong2 a = {0, 0}, b = {0, 0};
-    u64 legal = 0, ebase = 0;
-    u32 mover = 0, played = 0, nlegal = 0;
-    bool in_play = false, takes_part = false;
-    if (g < n) {
-        a = s01[g]; b = s23[g];
-        Game g0;
-        unpack(g0, a.x, a.y, b.x, b.y);
-        in_play = g0.phase == TK_PHASE_PLAY;
-        if (in_play) {
-            legal = legal_now(g0);
-            mover = (g0.leader + g0.nt) & 3;
-            played = g0.trick_no * 4 + g0.nt;
-            u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
-            takes_part = (set >> mover) & 1u;
-        }
-        if (takes_part) {
-            nlegal = (u32)popc64(legal);
-            ebase = ((u64)cnt[g].episode << 28) | ((u64)played << 22);
-            const u32 vw = voids[g];
-            for (u32 w = lane; w < worlds; w += L) {
-                Game d = g0;
-                redeal_voids(d, mover, game_key(pseed, offset + (u64)g, (7ULL << 61) | ebase | (u64)w), vw);
-                world_a[slot0 + w] = d.A; world_b[slot0 + w] = d.B; world_team[slot0 + w] = d.team;
-            }
-        }
-    }
-    __syncthreads();
-    if (takes_part) {
-        const u32 per_card = worlds * samples, items = nlegal * per_card;
-        for (u32 i = lane; i < items; i += L) {
-            u32 j = i / per_card, rem = i - j * per_card, w = rem / samples, k = rem - w * samples;
-            u32 c = kth_bit(legal, j);
-            u64 pkey = game_key(pseed, offset + (u64)g, (3ULL << 62) | ebase | ((u64)c << 16) | ((u64)w << 10) | (u64)k);
-            Game h;
-            unpack(h, a.x, a.y, b.x, b.y);
-            h.A = world_a[slot0 + w]; h.B = world_b[slot0 + w]; h.team = world_team[slot0 + w];
-            u64 scores = playout_from(h, c, pkey, played);
-            atomicAdd(row + j * 4 + 0, (int)(int16_t)scores);
-            atomicAdd(row + j * 4 + 1, (int)(int16_t)(scores >> 16));
-            atomicAdd(row + j * 4 + 2, (int)(int16_t)(scores >> 32));
-            atomicAdd(row + j * 4 + 3, (int)(int16_t)(scores >> 48));
-        }
-    }
-    __syncthreads();
-    if (g >= n) return;
-    if (sum_out)
-        for (u32 r = lane; r < TAROK_PLAYOUT_RANKS; r += L) sum_out[g * TAROK_PLAYOUT_RANKS + r] = reinterpret_cast<const int4 *>(row)[r];
-    if (action_out && lane == 0) {
-        u32 act = 255;
-        if (takes_part) {                            // the smallest rank at the maximum of the mover's sums
-            u32 best = 0;
-            int top = row[mover];
-            for (u32 j = 1; j < nlegal; j++) {
-                int v = row[j * 4 + mover];
-                if (v > top) { top = v; best = j; }
-            }
-            act = kth_bit(legal, best);
-        } else if (in_play) {
-            act = policy_action(gkey[g], played, legal);
-        }
-        action_out[g] = (uint8_t)act;
-    }
+    playout_cards_body<DealVoids>(n, pseed, offset, worlds, samples, lg, seats, seat_sets, s01, s23, cnt, gkey, voids, sum_out, action_out);
 }
 
 // tarok_played_cards: the cards of every game's play history as one word per game (bit c: card c has been played, the
@@ -1747,88 +1710,15 @@ TK_KERNEL(TK_BLOCK, 64) void k_played_cards(int64_t n, const ulonglong2 *__restr
 
 // tarok_playout_cards_hidden: k_playout_det with worlds that also hide what only other seats have seen — Klop's face-down
 // talon and the declarer's discards (redeal_hidden under the same world key; played[g] tells the discards from the won
-// tricks).  The same structure: the dealing lanes leave one world each in LDS, one barrier, the items run playout_from.
-// A world's record is (A, B, C, talon ids, team), 36 bytes: the C plane changes where a discard or a talon card changes
-// places with a hand card, and a Klop's gifts are read from the world's ids (apply_step).
+// tricks).  A world's record is WorldABCT: the C plane changes where a discard or a talon card changes places with a hand
+// card, and a Klop's gifts are read from the world's ids (apply_step).
 TK_KERNEL(TK_BLOCK, 128) void k_playout_hidden(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 samples, u32 lg,
                                               u32 seats, const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
                                               const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
                                               const u64 *__restrict__ gkey, const u64 *__restrict__ played_words,
                                               int4 *__restrict__ sum_out, uint8_t *__restrict__ action_out) {
     TK_VGPR_TOP(128, 127);
-    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> TK_PO_MIN_LG) * TAROK_PLAYOUT_RANKS * 4];
-    __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS], world_c[TK_PO_WORLD_SLOTS], world_ids[TK_PO_WORLD_SLOTS];
-    __shared__ u32 world_team[TK_PO_WORLD_SLOTS];
-    const u32 tid = threadIdx.x, team = tid >> lg, L = 1u << lg, lane = tid & (L - 1u), teams = (u32)TK_BLOCK >> lg;
-    const int64_t g = (int64_t)blockIdx.x * teams + team;
-    for (u32 w = tid; w < teams * (TAROK_PLAYOUT_RANKS * 4); w += TK_BLOCK) sums[w] = 0;
-    int *row = sums + team * (TAROK_PLAYOUT_RANKS * 4);
-    const u32 slot0 = team * worlds;                 // the team's worlds: slots slot0 .. slot0 + worlds - 1
-    ulonglong2 a = {0, 0}, b = {0, 0};
-    u64 legal = 0, ebase = 0;
-    u32 mover = 0, played = 0, nlegal = 0;
-    bool in_play = false, takes_part = false;
-    if (g < n) {
-        a = s01[g]; b = s23[g];
-        Game g0;
-        unpack(g0, a.x, a.y, b.x, b.y);
-        in_play = g0.phase == TK_PHASE_PLAY;
-        if (in_play) {
-            legal = legal_now(g0);
-            mover = (g0.leader + g0.nt) & 3;
-            played = g0.trick_no * 4 + g0.nt;
-            u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
-            takes_part = (set >> mover) & 1u;
-        }
-        if (takes_part) {
-            nlegal = (u32)popc64(legal);
-            ebase = ((u64)cnt[g].episode << 28) | ((u64)played << 22);
-            const u64 pw = played_words[g];
-            for (u32 w = lane; w < worlds; w += L) {
-                Game d = g0;
-                redeal_hidden(d, mover, game_key(pseed, offset + (u64)g, (7ULL << 61) | ebase | (u64)w), pw);
-                world_a[slot0 + w] = d.A; world_b[slot0 + w] = d.B; world_c[slot0 + w] = d.C; world_ids[slot0 + w] = d.talon;
-                world_team[slot0 + w] = d.team;
-            }
-        }
-    }
-    __syncthreads();
-    if (takes_part) {
-        const u32 per_card = worlds * samples, items = nlegal * per_card;
-        for (u32 i = lane; i < items; i += L) {
-            u32 j = i / per_card, rem = i - j * per_card, w = rem / samples, k = rem - w * samples;
-            u32 c = kth_bit(legal, j);
-            u64 pkey = game_key(pseed, offset + (u64)g, (3ULL << 62) | ebase | ((u64)c << 16) | ((u64)w << 10) | (u64)k);
-            Game h;
-            unpack(h, a.x, a.y, b.x, b.y);
-            h.A = world_a[slot0 + w]; h.B = world_b[slot0 + w]; h.C = world_c[slot0 + w]; h.talon = world_ids[slot0 + w];
-            h.team = world_team[slot0 + w];
-            u64 scores = playout_from(h, c, pkey, played);
-            atomicAdd(row + j * 4 + 0, (int)(int16_t)scores);
-            atomicAdd(row + j * 4 + 1, (int)(int16_t)(scores >> 16));
-            atomicAdd(row + j * 4 + 2, (int)(int16_t)(scores >> 32));
-            atomicAdd(row + j * 4 + 3, (int)(int16_t)(scores >> 48));
-        }
-    }
-    __syncthreads();
-    if (g >= n) return;
-    if (sum_out)
-        for (u32 r = lane; r < TAROK_PLAYOUT_RANKS; r += L) sum_out[g * TAROK_PLAYOUT_RANKS + r] = reinterpret_cast<const int4 *>(row)[r];
-    if (action_out && lane == 0) {
-        u32 act = 255;
-        if (takes_part) {                            // the smallest rank at the maximum of the mover's sums
-            u32 best = 0;
-            int top = row[mover];
-            for (u32 j = 1; j < nlegal; j++) {
-                int v = row[j * 4 + mover];
-                if (v > top) { top = v; best = j; }
-            }
-            act = kth_bit(legal, best);
-        } else if (in_play) {
-            act = policy_action(gkey[g], played, legal);
-        }
-        action_out[g] = (uint8_t)act;
-    }
+    playout_cards_body<DealHidden>(n, pseed, offset, worlds, samples, lg, seats, seat_sets, s01, s23, cnt, gkey, played_words, sum_out, action_out);
 }
 
 // tarok_playout_bids, first launch: the deal tarok_reset(env, episode, deals, ...) would make, one lane per game, left as
@@ -1870,6 +1760,8 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_bids(int64_t n, u64 pseed /* seed ^ salt
     TK_VGPR_TOP(128, 127);
     __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> TK_PB_MIN_LG) * 4 * TAROK_BID_ROWS];
     __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS], world_ids[TK_PO_WORLD_SLOTS];
+    // (PlayoutTeam's fields written out: through the struct this kernel compiles to six more instructions and its 19-row
+    // launch measured 0.2 % slower, outside the parent's band — DESIGN 8.3)
     const u32 tid = threadIdx.x, team = tid >> lg, L = 1u << lg, lane = tid & (L - 1u), teams = (u32)TK_BLOCK >> lg;
     const int64_t g = (int64_t)blockIdx.x * teams + team;
     for (u32 w = tid; w < teams * (4 * TAROK_BID_ROWS); w += TK_BLOCK) sums[w] = 0;
@@ -3726,57 +3618,66 @@ int tarok_rollout_random(tarok_env *e, uint32_t episode, int16_t *scores_out, in
     return TAROK_OK;
 }
 
-int tarok_playout_cards(tarok_env *e, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game, int32_t *sum_out,
-                        uint8_t *action_out, void *stream) {
-    if (!e || samples < 1 || samples > TAROK_PLAYOUT_MAX_SAMPLES || seats < 0 || seats > 15 || (!sum_out && !action_out)) return TAROK_EINVAL;
+extern "C++" {
+// Lanes per game of a playout launch, as lg: a power of two near four per playout of a row (a mover has 1..12 legal cards,
+// followers few), 2^min_lg .. 256.  4 * worlds <= lanes, so the worlds of a workgroup's teams fit its TK_PO_WORLD_SLOTS slots.
+static_assert(TAROK_PLAYOUT_MAX_WORLDS * 4 <= TK_BLOCK && TK_PO_WORLD_SLOTS * 4 == TK_BLOCK, "teams * worlds <= TK_PO_WORLD_SLOTS");
+static inline u32 playout_lg(u32 min_lg, int playouts) {
+    u32 lg = min_lg;
+    while (lg < TK_PO_MAX_LG && (1 << lg) < 4 * playouts) lg++;
+    return lg;
+}
+static inline dim3 playout_grid(const tarok_env *e, u32 lg) {
+    const int64_t teams = TK_BLOCK >> lg;
+    return dim3((unsigned)((e->n + teams - 1) / teams));
+}
+
+// The arguments every playout launch takes (an open-hand launch has one world).
+static inline bool playout_args_ok(const tarok_env *e, int worlds, int samples, int seats) {
+    return e && worlds >= 1 && worlds <= TAROK_PLAYOUT_MAX_WORLDS && samples >= 1 && samples <= TAROK_PLAYOUT_MAX_SAMPLES && seats >= 0 &&
+           seats <= 15;
+}
+
+// One card launch.  WORLDS: the kernel takes (worlds, samples); else samples alone, and `worlds` is 1.  `words`: the
+// dealer's per-game words, where it has any.
+template <bool WORLDS, class Kernel, class... Words>
+static int launch_playout_cards(Kernel kernel, tarok_env *e, int worlds, int samples, uint64_t salt, int seats,
+                                const uint8_t *seats_per_game, int32_t *sum_out, uint8_t *action_out, void *stream, Words... words) {
+    if (!playout_args_ok(e, worlds, samples, seats) || (!sum_out && !action_out) || (... || !words)) return TAROK_EINVAL;
     HIPCHK(hipSetDevice(e->device));
-    // lanes per game: a power of two near four per sample (a mover has 1..12 legal cards, followers few), 4 .. 256
-    u32 lg = TK_PO_MIN_LG;
-    while (lg < TK_PO_MAX_LG && (1 << lg) < 4 * samples) lg++;
-    int64_t teams = TK_BLOCK >> lg;
-    hipLaunchKernelGGL(k_playout, dim3((unsigned)((e->n + teams - 1) / teams)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
-                       e->seed ^ (u64)salt, e->offset, (u32)samples, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, e->gkey,
-                       reinterpret_cast<int4 *>(sum_out), action_out);
+    const u32 lg = playout_lg(TK_PO_MIN_LG, worlds * samples);
+    auto launch = [&](auto... counts) {
+        hipLaunchKernelGGL(kernel, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
+                           counts..., lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, e->gkey, words...,
+                           reinterpret_cast<int4 *>(sum_out), action_out);
+    };
+    if constexpr (WORLDS) launch((u32)worlds, (u32)samples); else launch((u32)samples);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
+}
+}
+
+int tarok_playout_cards(tarok_env *e, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game, int32_t *sum_out,
+                        uint8_t *action_out, void *stream) {
+    return launch_playout_cards<false>(k_playout, e, 1, samples, salt, seats, seats_per_game, sum_out, action_out, stream);
 }
 
 int tarok_playout_cards_det(tarok_env *e, int worlds, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
                             int32_t *sum_out, uint8_t *action_out, void *stream) {
-    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || samples < 1 || samples > TAROK_PLAYOUT_MAX_SAMPLES || seats < 0 ||
-        seats > 15 || (!sum_out && !action_out))
-        return TAROK_EINVAL;
-    HIPCHK(hipSetDevice(e->device));
-    // lanes per game: tarok_playout_cards' rule on worlds * samples playouts per card; 4 * worlds <= lanes, so the worlds
-    // of a workgroup's teams fit its TK_PO_WORLD_SLOTS slots
-    static_assert(TAROK_PLAYOUT_MAX_WORLDS * 4 <= TK_BLOCK && TK_PO_WORLD_SLOTS * 4 == TK_BLOCK, "teams * worlds <= TK_PO_WORLD_SLOTS");
-    u32 lg = TK_PO_MIN_LG;
-    while (lg < TK_PO_MAX_LG && (1 << lg) < 4 * worlds * samples) lg++;
-    int64_t teams = TK_BLOCK >> lg;
-    hipLaunchKernelGGL(k_playout_det, dim3((unsigned)((e->n + teams - 1) / teams)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
-                       e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)samples, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt,
-                       e->gkey, reinterpret_cast<int4 *>(sum_out), action_out);
-    HIPCHK(hipGetLastError());
-    return TAROK_OK;
+    return launch_playout_cards<true>(k_playout_det, e, worlds, samples, salt, seats, seats_per_game, sum_out, action_out, stream);
 }
 
 int tarok_playout_exchange(tarok_env *e, int worlds, int samples, int discard_sets, uint64_t salt, int seats,
                            const uint8_t *seats_per_game, int32_t *sum_out, int8_t *choice_out, uint8_t *discards_out, void *stream) {
-    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || samples < 1 || samples > TAROK_PLAYOUT_MAX_SAMPLES ||
-        discard_sets < 1 || discard_sets > TAROK_EXCHANGE_MAX_SETS || seats < 0 || seats > 15)
-        return TAROK_EINVAL;
+    if (!playout_args_ok(e, worlds, samples, seats) || discard_sets < 1 || discard_sets > TAROK_EXCHANGE_MAX_SETS) return TAROK_EINVAL;
     if (!sum_out && !choice_out && !discards_out) return TAROK_OK;
     HIPCHK(hipSetDevice(e->device));
-    // lanes per game: tarok_playout_cards_det's rule on worlds * samples playouts per candidate, and never fewer than 16:
-    // at most 16 teams per workgroup, whose 48 rows each are the 12 KiB the card launches use; 4 * worlds <= lanes, so
-    // the worlds of a workgroup's teams fit its TK_PO_WORLD_SLOTS slots
+    // never fewer than 16 lanes per game: at most 16 teams per workgroup, whose 48 rows each are the 12 KiB the card launches use
     static_assert(TAROK_EXCHANGE_ROWS == TK_PX_ROWS && TAROK_EXCHANGE_MAX_SETS * 6 == TK_PX_ROWS, "6 groups x 8 sets");
-    u32 lg = TK_PX_MIN_LG;
-    while (lg < TK_PO_MAX_LG && (1 << lg) < 4 * worlds * samples) lg++;
-    int64_t teams = TK_BLOCK >> lg;
-    hipLaunchKernelGGL(k_playout_exchange, dim3((unsigned)((e->n + teams - 1) / teams)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
-                       e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)samples, (u32)discard_sets, lg, (u32)seats, seats_per_game,
-                       e->s01, e->s23, e->cnt, e->gkey, reinterpret_cast<int4 *>(sum_out), choice_out, discards_out);
+    const u32 lg = playout_lg(TK_PX_MIN_LG, worlds * samples);
+    hipLaunchKernelGGL(k_playout_exchange, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
+                       (u32)worlds, (u32)samples, (u32)discard_sets, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, e->gkey,
+                       reinterpret_cast<int4 *>(sum_out), choice_out, discards_out);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }
@@ -3791,18 +3692,7 @@ int tarok_shown_voids(tarok_env *e, uint32_t *voids_out, void *stream) {
 
 int tarok_playout_cards_voids(tarok_env *e, int worlds, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
                               const uint32_t *voids, int32_t *sum_out, uint8_t *action_out, void *stream) {
-    if (!e || !voids || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || samples < 1 || samples > TAROK_PLAYOUT_MAX_SAMPLES ||
-        seats < 0 || seats > 15 || (!sum_out && !action_out))
-        return TAROK_EINVAL;
-    HIPCHK(hipSetDevice(e->device));
-    u32 lg = TK_PO_MIN_LG;                           // lanes per game: tarok_playout_cards_det's rule
-    while (lg < TK_PO_MAX_LG && (1 << lg) < 4 * worlds * samples) lg++;
-    int64_t teams = TK_BLOCK >> lg;
-    hipLaunchKernelGGL(k_playout_voids, dim3((unsigned)((e->n + teams - 1) / teams)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
-                       e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)samples, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt,
-                       e->gkey, voids, reinterpret_cast<int4 *>(sum_out), action_out);
-    HIPCHK(hipGetLastError());
-    return TAROK_OK;
+    return launch_playout_cards<true>(k_playout_voids, e, worlds, samples, salt, seats, seats_per_game, sum_out, action_out, stream, voids);
 }
 
 int tarok_played_cards(tarok_env *e, uint64_t *played_out, void *stream) {
@@ -3816,37 +3706,21 @@ int tarok_played_cards(tarok_env *e, uint64_t *played_out, void *stream) {
 
 int tarok_playout_cards_hidden(tarok_env *e, int worlds, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
                                const uint64_t *played, int32_t *sum_out, uint8_t *action_out, void *stream) {
-    if (!e || !played || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || samples < 1 || samples > TAROK_PLAYOUT_MAX_SAMPLES ||
-        seats < 0 || seats > 15 || (!sum_out && !action_out))
-        return TAROK_EINVAL;
-    HIPCHK(hipSetDevice(e->device));
-    u32 lg = TK_PO_MIN_LG;                           // lanes per game: tarok_playout_cards_det's rule
-    while (lg < TK_PO_MAX_LG && (1 << lg) < 4 * worlds * samples) lg++;
-    int64_t teams = TK_BLOCK >> lg;
-    hipLaunchKernelGGL(k_playout_hidden, dim3((unsigned)((e->n + teams - 1) / teams)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
-                       e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)samples, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt,
-                       e->gkey, (const u64 *)played, reinterpret_cast<int4 *>(sum_out), action_out);
-    HIPCHK(hipGetLastError());
-    return TAROK_OK;
+    return launch_playout_cards<true>(k_playout_hidden, e, worlds, samples, salt, seats, seats_per_game, sum_out, action_out, stream,
+                                      (const u64 *)played);
 }
 
 int tarok_playout_bids(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int samples, int contracts, uint64_t salt,
                        int seats, const uint8_t *seats_per_game, int32_t *sum_out, void *stream) {
-    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || samples < 1 || samples > TAROK_PLAYOUT_MAX_SAMPLES || contracts < 1 ||
-        contracts > TAROK_BID_ALL_CONTRACTS || seats < 0 || seats > 15)
-        return TAROK_EINVAL;
+    if (!playout_args_ok(e, worlds, samples, seats) || contracts < 1 || contracts > TAROK_BID_ALL_CONTRACTS) return TAROK_EINVAL;
     if (!sum_out) return TAROK_OK;
     HIPCHK(hipSetDevice(e->device));
     if (!e->bid_deal) HIPCHK(hipMalloc((void **)&e->bid_deal, (size_t)e->n * 5 * sizeof(u64)));   // on the first call; tarok_destroy frees it
     hipLaunchKernelGGL(k_bid_deal, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, episode, deals, e->bid_deal);
-    // lanes per game: tarok_playout_exchange's rule — 16 or more, so a workgroup's at most 16 teams keep their 80 sums each
-    // in 5 KiB, and 4 * worlds <= lanes, so their worlds fit its TK_PO_WORLD_SLOTS slots
+    // 16 lanes per game or more, so a workgroup's at most 16 teams keep their 80 sums each in 5 KiB
     static_assert(TAROK_BID_ROWS == TK_BID_ROWS && TAROK_BID_ROWS % 4 == 0, "a viewer's rows are whole 16-byte pieces");
-    u32 lg = TK_PB_MIN_LG;
-    while (lg < TK_PO_MAX_LG && (1 << lg) < 4 * worlds * samples) lg++;
-    int64_t teams = TK_BLOCK >> lg;
-    hipLaunchKernelGGL(k_playout_bids, dim3((unsigned)((e->n + teams - 1) / teams)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
-                       e->seed ^ (u64)salt, e->offset, episode, (u32)worlds, (u32)samples, lg, (u32)contracts, (u32)seats, seats_per_game,
+    const u32 lg = playout_lg(TK_PB_MIN_LG, worlds * samples);
+    hipLaunchKernelGGL(k_playout_bids, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset, episode, (u32)worlds, (u32)samples, lg, (u32)contracts, (u32)seats, seats_per_game,
                        e->bid_deal, reinterpret_cast<int4 *>(sum_out));
     HIPCHK(hipGetLastError());
     return TAROK_OK;

@@ -310,6 +310,36 @@ class TarokVecEnv:
                                                       self._p(out.get("actions")), self._stream()))
         return out
 
+    def _playout_cards(self, fn, counts, salt, seats, seats_per_game, words, sum_out, action_out):
+        """One card launch: the native entry point `fn` with `counts` ((samples,) or (worlds, samples)) and the dealer's
+        per-game `words` (a tuple: empty, or one device tensor).  Returns (sum_out, action_out), allocated where None."""
+        with torch.cuda.device(self.device):
+            if sum_out is None:
+                sum_out = torch.empty((self.n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=self.device)
+            if action_out is None:
+                action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
+            _native.check(fn(self._h, *[int(c) for c in counts], int(salt) & ((1 << 64) - 1), int(seats),
+                             self._p(self._seat_sets(seats_per_game)), *[self._p(w) for w in words], self._p(sum_out),
+                             self._p(action_out), self._stream()))
+        return sum_out, action_out
+
+    def playout_cards_fair(self, worlds, samples, *, voids=False, hidden=False, words=None, salt=0, seats=15, seats_per_game=None,
+                           sum_out=None, action_out=None):
+        """The card launch a player's settings name: worlds None / 0 -> playout_cards (open hands); voids=True ->
+        playout_cards_voids on shown_voids(words); hidden=True -> playout_cards_hidden on played_cards(words); otherwise
+        playout_cards_det.  words: the caller's scratch tensor for the voids / played words ([N] int32 / int64; None: a
+        new one per call), so that a captured rollout allocates nothing.  Everything else as for the launch chosen."""
+        if voids and hidden:
+            raise ValueError("hidden=True is not built together with voids=True: give one of the two")
+        out = dict(salt=salt, seats=seats, seats_per_game=seats_per_game, sum_out=sum_out, action_out=action_out)
+        if not worlds:
+            return self.playout_cards(samples, **out)
+        if voids:
+            return self.playout_cards_voids(worlds, samples, voids=self.shown_voids(words), **out)
+        if hidden:
+            return self.playout_cards_hidden(worlds, samples, played=self.played_cards(words), **out)
+        return self.playout_cards_det(worlds, samples, **out)
+
     def playout_cards(self, samples, salt=0, seats=15, seats_per_game=None, sum_out=None, action_out=None):
         """Open-hand Monte-Carlo value of every legal card of the seat to move (tarok_playout_cards): each legal card is
         played and the game finished `samples` times by the Bot, from the env's current positions.  The playouts see the
@@ -319,15 +349,7 @@ class TarokVecEnv:
         zero rows beyond the legal cards and for games that do not take part — and action [N] uint8: the first card at
         the maximum of the mover's sums, the Bot's card where the mover is outside `seats` / `seats_per_game` (as in
         policy_step), 255 where nothing is to be played).  Read-only on the env; `salt` varies the playouts' draws."""
-        with torch.cuda.device(self.device):
-            if sum_out is None:
-                sum_out = torch.empty((self.n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=self.device)
-            if action_out is None:
-                action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
-            _native.check(self.L.tarok_playout_cards(self._h, int(samples), int(salt) & ((1 << 64) - 1), int(seats),
-                                                     self._p(self._seat_sets(seats_per_game)), self._p(sum_out),
-                                                     self._p(action_out), self._stream()))
-        return sum_out, action_out
+        return self._playout_cards(self.L.tarok_playout_cards, (samples,), salt, seats, seats_per_game, (), sum_out, action_out)
 
     def playout_cards_det(self, worlds, samples, salt=0, seats=15, seats_per_game=None, sum_out=None, action_out=None):
         """Determinized Monte-Carlo value of every legal card of the seat to move (tarok_playout_cards_det): the FAIR
@@ -337,15 +359,7 @@ class TarokVecEnv:
         its hand, the table, the won piles, the talon ids, the contract, the declarer and the called suit.  Where a
         called king is among the unseen cards the world's team is the declarer and whoever was dealt it.
         Outputs, `seats` / `seats_per_game`, `salt` and the read-only contract: as for playout_cards."""
-        with torch.cuda.device(self.device):
-            if sum_out is None:
-                sum_out = torch.empty((self.n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=self.device)
-            if action_out is None:
-                action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
-            _native.check(self.L.tarok_playout_cards_det(self._h, int(worlds), int(samples), int(salt) & ((1 << 64) - 1),
-                                                         int(seats), self._p(self._seat_sets(seats_per_game)),
-                                                         self._p(sum_out), self._p(action_out), self._stream()))
-        return sum_out, action_out
+        return self._playout_cards(self.L.tarok_playout_cards_det, (worlds, samples), salt, seats, seats_per_game, (), sum_out, action_out)
 
     def playout_exchange(self, worlds, samples, discard_sets=4, salt=0, seats=15, seats_per_game=None, sum_out=None,
                          choice_out=None, discards_out=None):
@@ -453,16 +467,8 @@ class TarokVecEnv:
             raise ValueError("playout_cards_voids goes with the play history: TarokVecEnv(history=True)")
         if voids is None:
             voids = self.shown_voids()
-        with torch.cuda.device(self.device):
-            if sum_out is None:
-                sum_out = torch.empty((self.n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=self.device)
-            if action_out is None:
-                action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
-            _native.check(self.L.tarok_playout_cards_voids(self._h, int(worlds), int(samples), int(salt) & ((1 << 64) - 1),
-                                                           int(seats), self._p(self._seat_sets(seats_per_game)),
-                                                           self._p(self._dev(voids, torch.int32, (self.n,))), self._p(sum_out),
-                                                           self._p(action_out), self._stream()))
-        return sum_out, action_out
+        return self._playout_cards(self.L.tarok_playout_cards_voids, (worlds, samples), salt, seats, seats_per_game,
+                                   (self._dev(voids, torch.int32, (self.n,)),), sum_out, action_out)
 
     def played_cards(self, out=None):
         """[N] int64 device tensor (tarok_played_cards; the bits of a u64): bit c of a game's word is set iff card c is in
@@ -486,16 +492,8 @@ class TarokVecEnv:
             raise ValueError("playout_cards_hidden goes with the play history: TarokVecEnv(history=True)")
         if played is None:
             played = self.played_cards()
-        with torch.cuda.device(self.device):
-            if sum_out is None:
-                sum_out = torch.empty((self.n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=self.device)
-            if action_out is None:
-                action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
-            _native.check(self.L.tarok_playout_cards_hidden(self._h, int(worlds), int(samples), int(salt) & ((1 << 64) - 1),
-                                                            int(seats), self._p(self._seat_sets(seats_per_game)),
-                                                            self._p(self._dev(played, torch.int64, (self.n,))), self._p(sum_out),
-                                                            self._p(action_out), self._stream()))
-        return sum_out, action_out
+        return self._playout_cards(self.L.tarok_playout_cards_hidden, (worlds, samples), salt, seats, seats_per_game,
+                                   (self._dev(played, torch.int64, (self.n,)),), sum_out, action_out)
 
     def playout_targets(self, sums, obs_words, playouts, tau, seats=15, seats_per_game=None, target_out=None):
         """A playout launch's sums as a teacher's target rows (tarok_playout_targets): target [N,64] bf16, for a game with

@@ -193,8 +193,7 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
         with torch.cuda.device(env.device):
             actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
             sums = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=env.device)
-            words = torch.empty(n, dtype=torch.int32, device=env.device) if voids else None
-            pwords = torch.empty(n, dtype=torch.int64, device=env.device) if hidden else None
+            words = torch.empty(n, dtype=torch.int32 if voids else torch.int64, device=env.device) if voids or hidden else None
         xb = _exchange_bufs(env, n, exchange, inspect is not None) if exchange is not None else None
         bsums = _bid_bufs(env, n) if bidding is not None else None
         for e in range(int(episodes)):
@@ -206,16 +205,8 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
                     env.reset(episode=e, clear_counters=True, **setup)
                     start = env.state() if inspect is not None else None
                 for t in range(GAME_CARDS):
-                    if worlds is None:
-                        env.playout_cards(samples, salt=salt, seats=seats, sum_out=sums, action_out=actions[t])
-                    elif voids:
-                        env.playout_cards_voids(worlds, samples, salt=salt, seats=seats, voids=env.shown_voids(words), sum_out=sums,
-                                                action_out=actions[t])
-                    elif hidden:
-                        env.playout_cards_hidden(worlds, samples, salt=salt, seats=seats, played=env.played_cards(pwords),
-                                                 sum_out=sums, action_out=actions[t])
-                    else:
-                        env.playout_cards_det(worlds, samples, salt=salt, seats=seats, sum_out=sums, action_out=actions[t])
+                    env.playout_cards_fair(worlds, samples, voids=voids, hidden=hidden, words=words, salt=salt, seats=seats, sum_out=sums,
+                                           action_out=actions[t])
                     env.step(actions[t], auto_reset=False)
                 _, ss = env.counters()                # (the pass's one synchronisation)
                 scores[p, e * n:(e + 1) * n] = ss

@@ -497,26 +497,17 @@ class SelfPlay:
             self._buf["teach"] = torch.zeros((T, n, 64), dtype=torch.bfloat16, device=dev)
             self._teach_sums = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=dev)
             self._teach_act = torch.empty(n, dtype=torch.uint8, device=dev)
-            self._teach_voids = torch.empty(n, dtype=torch.int32, device=dev) if self.teacher["voids"] else None
-            self._teach_played = torch.empty(n, dtype=torch.int64, device=dev) if self.teacher["hidden"] else None
+            tc = self.teacher                         # the voids / played words of the teacher's worlds
+            self._teach_words = (torch.empty(n, dtype=torch.int32 if tc["voids"] else torch.int64, device=dev)
+                                 if tc["voids"] or tc["hidden"] else None)
         self._graph = None
 
     def _teach(self, t):
         """The teacher's rows of lock-step t: one playout launch on the learner's seats from the env's current positions,
         one tarok_playout_targets on the words of that lock-step.  Stream-ordered, read-only on the env, no allocation."""
         env, buf, tc = self.env, self._buf, self.teacher
-        if tc["voids"]:
-            env.playout_cards_voids(tc["worlds"], tc["samples"], salt=tc["salt"], seats_per_game=self._seats,
-                                    voids=env.shown_voids(self._teach_voids), sum_out=self._teach_sums, action_out=self._teach_act)
-        elif tc["hidden"]:
-            env.playout_cards_hidden(tc["worlds"], tc["samples"], salt=tc["salt"], seats_per_game=self._seats,
-                                     played=env.played_cards(self._teach_played), sum_out=self._teach_sums, action_out=self._teach_act)
-        elif tc["worlds"]:
-            env.playout_cards_det(tc["worlds"], tc["samples"], salt=tc["salt"], seats_per_game=self._seats, sum_out=self._teach_sums,
-                                  action_out=self._teach_act)
-        else:
-            env.playout_cards(tc["samples"], salt=tc["salt"], seats_per_game=self._seats, sum_out=self._teach_sums,
-                              action_out=self._teach_act)
+        env.playout_cards_fair(tc["worlds"], tc["samples"], voids=tc["voids"], hidden=tc["hidden"], words=self._teach_words,
+                               salt=tc["salt"], seats_per_game=self._seats, sum_out=self._teach_sums, action_out=self._teach_act)
         env.playout_targets(self._teach_sums, buf["words"][t], max(1, tc["worlds"]) * tc["samples"], tc["tau"],
                             seats_per_game=self._seats, target_out=buf["teach"][t])
 
