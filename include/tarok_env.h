@@ -521,6 +521,55 @@ int tarok_bid_values(tarok_env *env, uint32_t episode, const uint8_t *deals, con
                      const float *b2, const void *w3, const float *b3, float scale, int contracts, int seats,
                      const uint8_t *seats_per_game, int32_t *value_out, float *raw_out, uint64_t *feature_words_out, void *stream);
 
+/* The exchange head: a network that picks the talon group and the discards, in tarok_playout_exchange's place in front of
+ * tarok_exchange.  Read-only on the env, stream-ordered, capturable.  A game TAKES PART exactly as in
+ * tarok_playout_exchange: it waits for the exchange (TAROK_DEFER_EXCHANGE) and its declarer is in the seat set (`seats`, or
+ * seats_per_game[g] & 15).
+ *
+ * Notation: gs the group size, ngroups = 6 / gs, d the declarer, H its hand, T the six talon cards, T_i group i (talon
+ * cards i gs .. i gs + gs - 1), P_i = H | T_i what the declarer holds after picking group i up.
+ * Rows: eight per game, row (g, i), i < 8, "pick up group i"; LIVE iff the game takes part and i < ngroups.  A live row
+ * has 256 0/1 features, feature f = bit f % 64 of word f / 64:
+ *   word 0  bits 0..53 P_i; bit 54 + d; bits 58, 59, 60: gs = 3, 2, 1; bit 61: the contract is a Solo.
+ *   word 1  bits 0..53 T & ~T_i (what stays with the opponents); bit 54 + k: called-king suit k (Tri / Dve / Ena only);
+ *           bit 58 + i.
+ *   word 2  bits 0..53 T_i; bits 54, 55, 56: the called king lies in T_i, in H, in T & ~T_i (Tri / Dve / Ena only).
+ *   word 3  on P_i: bit j, j < 16: more than j taroks; bit 16 + 8 k + j, j < 8: more than j cards of suit k; bit 48 + k:
+ *           the king of suit k; bits 52, 53, 54: pagat, mond, skis (tarok_bid_values' word 1 with sixteen tarok bits).
+ * A row that is not live has four zero words.
+ * The row goes through tarok_policy_mlp's network — 256 -> 256 -> 256 -> 64, ReLU, bf16 MFMA with f32 accumulate, both
+ * hidden layers stored as bf16 — with w1 .. b3 in that call's layouts.  Output c < 54 is the discard score of card c,
+ * output 54 the value of the group (the policy's own layout: 54 logits and the value column); 55..63 are ignored.
+ * clean(y) = fmaxf(y, -inf): a NaN becomes -inf, so a broken network still yields a valid exchange.
+ * The decision of a game that takes part:
+ *   choice    i* = the i < ngroups with the largest clean(y_i[54]), the lowest i on ties;
+ *   cand      P_i* & the discardable cards (suit ranks 1..7 and taroks 2..7, as for the Bot), all of P_i* if those
+ *             are fewer than gs: the Bot's own rule;
+ *   discards  gs times the card of cand with the largest clean(y_i*[c]), the lowest card on ties, removed once taken.
+ * Outputs, each may be NULL, EVERY row written:
+ *   raw_out [N,8,64] f32, 16-byte aligned: the 64 outputs of a live row, zeros for every other row.
+ *   choice_out [N] i8, discards_out [N,3] u8 (255 beyond gs, the cards in the order taken): tarok_playout_exchange's three
+ *     cases — the decision above; the Bot's exchange (group 0, its sampler under the game's own key) for a game that
+ *     waits with its declarer outside the set; -1 and 255, 255, 255 for any other game — so tarok_exchange(choice_out,
+ *     discards_out) serves a mixed table in one call.
+ *   feature_words_out [N,8,4] u64, 16-byte aligned: the four words of every row (zero where not live) — what a learner
+ *     of the head trains on.
+ * With all four outputs NULL nothing is launched.
+ * TAROK_EINVAL (before any HIP call) for a NULL env, weight or bias, or seats outside 0..15. */
+int tarok_exchange_values(tarok_env *env, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
+                          const float *b3, int seats, const uint8_t *seats_per_game, float *raw_out, int8_t *choice_out,
+                          uint8_t *discards_out, uint64_t *feature_words_out, void *stream);
+
+/* What tarok_playout_exchange's candidates laid down: its sum_out says what candidate (i, d) was worth, this launch which
+ * cards it discarded — what a learner of the exchange head's discard scores needs.  Read-only, stream-ordered.
+ *   cand_out [N, 6 * discard_sets, 3] u8: row i * discard_sets + d holds the discards of group i under
+ *     ckey = game_key(seed ^ salt, gidx, 5 << 61 | (u64)episode << 28 | i << 6 | d), tarok_playout_exchange's to the bit,
+ *     255 beyond gs; 255, 255, 255 for groups >= ngroups and for games that do not take part.  EVERY row is written.
+ * With cand_out == NULL nothing is launched.  TAROK_EINVAL (before any HIP call) for a NULL env, discard_sets outside
+ * 1..TAROK_EXCHANGE_MAX_SETS or seats outside 0..15. */
+int tarok_exchange_candidates(tarok_env *env, int discard_sets, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                              uint8_t *cand_out, void *stream);
+
 /* A playout launch's sums as a teacher's target distribution: one row of 64 bf16 per game, for the learner's distillation
  * term (tarok_learn_chain_distill).  Per game g the kernel reads obs[g], the observation word the playouts started from:
  * legal = its 54-bit mask, s = its seat bits, nl = min(popcount(legal), TAROK_PLAYOUT_RANKS).

@@ -32,7 +32,7 @@ SYMBOLS = [
     "tarok_set_play_mode", "tarok_get_play_mode", "tarok_playout_cards", "tarok_playout_cards_det",
     "tarok_playout_targets", "tarok_learn_chain_distill", "tarok_shown_voids", "tarok_playout_cards_voids",
     "tarok_playout_exchange", "tarok_played_cards", "tarok_playout_cards_hidden", "tarok_playout_bids", "tarok_bid_round",
-    "tarok_bid_values",
+    "tarok_bid_values", "tarok_exchange_values", "tarok_exchange_candidates",
 ]
 
 
@@ -177,6 +177,8 @@ def lib():
     L.tarok_playout_bids.restype = i32; L.tarok_playout_bids.argtypes = [vp, u32, vp, i32, i32, i32, u64, i32, vp, vp, vp]
     L.tarok_bid_round.restype = i32; L.tarok_bid_round.argtypes = [vp, u32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.tarok_bid_values.restype = i32; L.tarok_bid_values.argtypes = [vp, u32, vp] + [vp] * 6 + [f32, i32, i32] + [vp] * 5
+    L.tarok_exchange_values.restype = i32; L.tarok_exchange_values.argtypes = [vp] + [vp] * 6 + [i32] + [vp] * 6
+    L.tarok_exchange_candidates.restype = i32; L.tarok_exchange_candidates.argtypes = [vp, i32, u64, i32, vp, vp, vp]
     L.tarok_playout_targets.restype = i32; L.tarok_playout_targets.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp]
     L.tarok_learn_chain_distill.restype = i32
     L.tarok_learn_chain_distill.argtypes = [vp, i64] + [vp] * 4 + [f32] * 3 + [vp] * 17 + [vp, f32, vp, vp, vp, vp]

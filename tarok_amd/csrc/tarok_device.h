@@ -1134,3 +1134,78 @@ __device__ __forceinline__ void bid_feature_words(u64 hand, u32 seat, u64 out[4]
     out[2] = 0;
     out[3] = 0;
 }
+
+// ---------------------------------------------------------------------------
+// The exchange head (tarok_exchange_values, include/tarok_env.h)
+// ---------------------------------------------------------------------------
+// The 256 0/1 features of row i, "the declarer picks up talon group i", of a game that waits for the exchange, in the
+// policy's layout.  With gs = group_size, d the declarer, H its hand, T the six talon cards, T_i group i and P = H | T_i:
+//   word 0  P; bit 54 + d; bits 58, 59, 60: gs = 3, 2, 1; bit 61: a Solo contract.
+//   word 1  T & ~T_i (what stays with the opponents); bit 54 + k: the called suit (Tri / Dve / Ena); bit 58 + i.
+//   word 2  T_i; bits 54, 55, 56: the called king lies in T_i, in H, in T & ~T_i.
+//   word 3  bid_feature_words' word 1 of P — that function's text, called, not restated — with the tarok thermometer
+//           carried on to sixteen bits (P holds up to fifteen cards).
+// A row the contract does not have (i >= 6 / gs) is four zero words.
+__device__ __forceinline__ void exchange_feature_words(const Game &g, u32 i, u64 out[4]) {
+    const u32 gs = group_size(g.contract), d = g.declarer;
+    const bool live = i * gs < 6u;
+    const u64 H = hand_of(g, d), T = talon_all(g), Ti = live ? ids_mask(g.talon, (int)(i * gs), (int)gs) : 0ULL;
+    const u64 P = H | Ti, R = T & ~Ti;
+    const u64 kb = has_king(g.contract) ? 1ULL << (8 * g.king + 7) : 0ULL;
+    const u64 w0 = P | (1ULL << (54 + d)) | (1ULL << (61 - gs)) | ((u64)(g.contract >= TK_SOLO_TRI) << 61);
+    const u64 w1 = R | ((kb ? 1ULL : 0ULL) << (54 + g.king)) | ((1ULL << 58) << (i & 7u));
+    const u64 w2 = Ti | ((u64)((Ti & kb) != 0) << 54) | ((u64)((H & kb) != 0) << 55) | ((u64)((R & kb) != 0) << 56);
+    u64 shape[4];
+    bid_feature_words(P, 0u, shape);
+    const u32 nt = (u32)popc64(P & TK_TAROK);
+    const u64 w3 = shape[1] | ((1ULL << (nt < 16u ? nt : 16u)) - 1ULL);
+    out[0] = live ? w0 : 0ULL;
+    out[1] = live ? w1 : 0ULL;
+    out[2] = live ? w2 : 0ULL;
+    out[3] = live ? w3 : 0ULL;
+}
+
+// A network output as the exchange head reads it: a NaN counts as -inf (fmaxf returns its other operand), so a broken
+// network still yields a valid exchange.  (The builtin: the header needs no <math.h> where g++ compiles it.)
+__device__ __forceinline__ float exchange_clean(float y) { return __builtin_fmaxf(y, -__builtin_inff()); }
+
+// The exchange head's discards from one row of 64 outputs: gs times the card of `cand` with the largest clean score, the
+// lowest card on ties, removed once taken.  Packed as exchange_discards packs them: 8 bits a card in the order taken, 255
+// beyond gs (and where cand runs out, which a candidate mask of an exchange never does).
+__device__ __forceinline__ u32 exchange_select(const float *y, u64 cand, u32 gs) {
+    u32 dpk = 0xFFFFFFu;
+    cand &= TK_DECK;
+#pragma unroll
+    for (u32 j = 0; j < 3; j++) {
+        if (j >= gs) break;
+        u32 best = 255u;
+        float bv = 0.f;
+#pragma unroll
+        for (u32 c = 0; c < 54; c++) {
+            const float v = exchange_clean(y[c]);
+            const bool take = ((cand >> c) & 1ULL) && (best == 255u || v > bv);
+            best = take ? c : best;
+            bv = take ? v : bv;
+        }
+        if (best != 255u) {
+            dpk = (dpk & ~(255u << (8 * j))) | (best << (8 * j));
+            cand &= ~(1ULL << best);
+        }
+    }
+    return dpk;
+}
+
+// The exchange head's group from the rows of a game (row i at y + i * stride): the i < ngroups with the largest clean
+// output 54, the lowest i on ties.
+__device__ __forceinline__ u32 exchange_choice(const float *y, u32 stride, u32 ngroups) {
+    u32 best = 0;
+    float bv = exchange_clean(y[54]);
+#pragma unroll
+    for (u32 i = 1; i < 6; i++) {
+        const float v = exchange_clean(y[(i < ngroups ? i : 0u) * stride + 54]);
+        const bool take = i < ngroups && v > bv;
+        best = take ? i : best;
+        bv = take ? v : bv;
+    }
+    return best;
+}

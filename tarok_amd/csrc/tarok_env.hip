@@ -2969,6 +2969,119 @@ __global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_bid_values(
     }
 }
 
+// tarok_exchange_values: the exchange head — k_bid_values' forward on the declarer's pick-up.  A workgroup takes 16 games
+// = 128 rows, row = 8 * local game + i, "pick up talon group i": threads below 128 decode their game's 32-byte state and
+// build ext[row] = exchange_feature_words(game, i) under w1's prefetch — four zero words for a row that is not live (the
+// game does not take part, or i >= ngroups), so ext[row][0] != 0 says "live" to the end of the kernel (word 0 of a live row
+// holds the declarer's bit).  After the head the f32 rows in LDS feed the raw_out stores (all 256 threads, 16-byte pieces,
+// the workgroup's 32 KiB contiguous), and one thread per game takes the value comparison across the game's rows
+// (exchange_choice) and the discards of the winning row (exchange_select on P & TK_DISCARDABLE, the Bot's fallback to
+// all of P), or, for a game outside the set, tarok_playout_exchange's other two cases.  A ragged last workgroup's rows
+// read game n - 1 and store nothing.  Nothing of the env is written.
+__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_exchange_values(
+    int64_t n, const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23, const u64 *__restrict__ gkey,
+    const __bf16 *__restrict__ w1, const float *__restrict__ b1, const __bf16 *__restrict__ w2, const float *__restrict__ b2,
+    const __bf16 *__restrict__ w3, const float *__restrict__ b3, u32 seats, const uint8_t *__restrict__ seat_sets,
+    float4 *__restrict__ raw_out, int8_t *__restrict__ choice_out, uint8_t *__restrict__ discards_out,
+    ulonglong2 *__restrict__ feature_words_out) {
+    TK_VGPR_TOP(256, 255);
+    constexpr u32 ROWS = 8, GAMES = PM_M / ROWS;     // rows per game, games per workgroup
+    static_assert(TK_BLOCK == 2 * PM_M && PM_M % ROWS == 0 && 64 * PM_M / 4 % TK_BLOCK == 0, "one tile, whole raw pieces per thread");
+    __shared__ __attribute__((aligned(16))) __bf16 X[PM_M * PM_LD];
+    __shared__ u64 ext[PM_M][4];
+    const int64_t base = (int64_t)blockIdx.x * GAMES;
+    const u32 tid = threadIdx.x, wave = tid >> 6;
+    float *L = reinterpret_cast<float *>(X);
+    bf16x8 wq[4][2];
+    mlp_prefetch(wq, w1, wave * 2);                // lands while the features are built
+    if (tid < PM_M) {
+        const u32 i = tid & (ROWS - 1);
+        const int64_t gq = base + (tid / ROWS), g = gq < n ? gq : n - 1;
+        Game gm;
+        load_game(gm, s01, s23, g);
+        const u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+        const bool part = gm.phase == TK_PHASE_EXCHANGE && ((set >> gm.declarer) & 1u);
+        u64 w[4];
+        exchange_feature_words(gm, i, w);
+#pragma unroll
+        for (u32 j = 0; j < 4; j++) ext[tid][j] = part ? w[j] : 0ULL;
+        if (feature_words_out && gq < n) {
+            feature_words_out[(g * ROWS + i) * 2] = make_ulonglong2(ext[tid][0], ext[tid][1]);
+            feature_words_out[(g * ROWS + i) * 2 + 1] = make_ulonglong2(ext[tid][2], ext[tid][3]);
+        }
+    }
+    __syncthreads();
+    policy_expand(X, ext, tid);
+    __syncthreads();
+    mlp_hidden(X, w1, b1, wq, wave);
+    mlp_prefetch(wq, w2, wave * 2);
+    mlp_hidden(X, w2, b2, wq, wave);
+    mlp_head(X, L, w3, b3, wave, 0);
+    __syncthreads();
+    if (raw_out) {
+#pragma unroll
+        for (u32 k = 0; k < 64 * PM_M / 4 / TK_BLOCK; k++) {
+            const u32 p = tid + TK_BLOCK * k, row = p >> 4, q = p & 15u;
+            if (base + (row / ROWS) < n) {
+                const float4 y = *reinterpret_cast<const float4 *>(L + row * PM_LL + 4 * q);
+                raw_out[base * (ROWS * 16) + p] = ext[row][0] ? y : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+    }
+    const int64_t g = base + tid;
+    if (tid >= GAMES || g >= n || (!choice_out && !discards_out)) return;
+    int ch = -1;
+    u32 dpk = 0xFFFFFFu;
+    const u64 w0 = ext[tid * ROWS][0];
+    if (w0) {                                        // the game takes part: row 0 is live
+        const u32 gs = 3u - (u32)__builtin_ctz((u32)(w0 >> 58) & 7u), ngroups = 6u / gs;
+        const float *y = L + tid * ROWS * PM_LL;
+        ch = (int)exchange_choice(y, PM_LL, ngroups);
+        const u64 P = ext[tid * ROWS + (u32)ch][0] & TK_DECK;
+        u64 cand = P & TK_DISCARDABLE;
+        if ((u32)popc64(cand) < gs) cand = P;
+        dpk = exchange_select(y + (u32)ch * PM_LL, cand, gs);
+    } else {
+        Game gm;
+        load_game(gm, s01, s23, g);
+        if (gm.phase == TK_PHASE_EXCHANGE) {         // the Bot's own exchange: group 0, its sampler under the game's key
+            ch = 0;
+            dpk = exchange_discards(gm, 0u, gkey[g]);
+        }
+    }
+    if (choice_out) choice_out[g] = (int8_t)ch;
+    if (discards_out) {
+        discards_out[g * 3 + 0] = (uint8_t)dpk; discards_out[g * 3 + 1] = (uint8_t)(dpk >> 8);
+        discards_out[g * 3 + 2] = (uint8_t)(dpk >> 16);
+    }
+}
+
+// tarok_exchange_candidates: the discards of every candidate (i, d) of tarok_playout_exchange, one thread per game —
+// exchange_discards under that launch's ckey, 255s for groups the contract does not have and for games that do not take
+// part.  Read-only; every row written.
+TK_KERNEL(TK_BLOCK, 128) void k_exchange_candidates(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 sets, u32 seats,
+                                                   const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                                   const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                                   uint8_t *__restrict__ cand_out) {
+    TK_VGPR_TOP(128, 127);
+    const int64_t g = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
+    if (g >= n) return;
+    Game g0;
+    load_game(g0, s01, s23, g);
+    const u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+    const bool part = g0.phase == TK_PHASE_EXCHANGE && ((set >> g0.declarer) & 1u);
+    const u32 ngroups = part ? 6u / group_size(g0.contract) : 0u;
+    const u64 ebase = (u64)cnt[g].episode << 28;
+    uint8_t *out = cand_out + g * (int64_t)(18u * sets);
+    for (u32 i = 0; i < 6; i++)
+        for (u32 d = 0; d < sets; d++) {
+            u32 dpk = 0xFFFFFFu;
+            if (i < ngroups) dpk = exchange_discards(g0, i, game_key(pseed, offset + (u64)g, (5ULL << 61) | ebase | ((u64)i << 6) | (u64)d));
+            uint8_t *o = out + 3u * (i * sets + d);
+            o[0] = (uint8_t)dpk; o[1] = (uint8_t)(dpk >> 8); o[2] = (uint8_t)(dpk >> 16);
+        }
+}
+
 // tarok_policy_step: tarok_policy_mlp and tarok_step in ONE launch.  A play workgroup (512
 // threads, 256 games = the 256 slots of step group blockIdx.x) evaluates the policy for its games
 // as two 128-game tiles side by side, leaves the sampled cards in LDS and then runs the step
@@ -3753,6 +3866,32 @@ int tarok_bid_values(tarok_env *e, uint32_t episode, const uint8_t *deals, const
                        e->bid_deal, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3, scale, (u32)contracts,
                        (u32)seats, seats_per_game, reinterpret_cast<int4 *>(value_out), reinterpret_cast<float4 *>(raw_out),
                        reinterpret_cast<ulonglong2 *>(feature_words_out));
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int tarok_exchange_values(tarok_env *e, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
+                          const float *b3, int seats, const uint8_t *seats_per_game, float *raw_out, int8_t *choice_out,
+                          uint8_t *discards_out, uint64_t *feature_words_out, void *stream) {
+    if (!e || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || seats < 0 || seats > 15) return TAROK_EINVAL;
+    if (!raw_out && !choice_out && !discards_out && !feature_words_out) return TAROK_OK;
+    HIPCHK(hipSetDevice(e->device));
+    const int64_t games = PM_M / 8;                  // per workgroup: one 128-row tile, eight rows a game
+    hipLaunchKernelGGL(k_exchange_values, dim3((unsigned)((e->n + games - 1) / games)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
+                       e->s01, e->s23, e->gkey, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3, (u32)seats,
+                       seats_per_game, reinterpret_cast<float4 *>(raw_out), choice_out, discards_out,
+                       reinterpret_cast<ulonglong2 *>(feature_words_out));
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int tarok_exchange_candidates(tarok_env *e, int discard_sets, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                              uint8_t *cand_out, void *stream) {
+    if (!e || discard_sets < 1 || discard_sets > TAROK_EXCHANGE_MAX_SETS || seats < 0 || seats > 15) return TAROK_EINVAL;
+    if (!cand_out) return TAROK_OK;
+    HIPCHK(hipSetDevice(e->device));
+    hipLaunchKernelGGL(k_exchange_candidates, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
+                       (u32)discard_sets, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, cand_out);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }

@@ -445,6 +445,46 @@ class TarokVecEnv:
             return value_out
         return value_out, raw_out, fw_out
 
+    def exchange_values(self, weights, seats=15, seats_per_game=None, raw=False, feature_words=False, choice_out=None,
+                        discards_out=None):
+        """The exchange head (tarok_exchange_values): playout_exchange()'s choice and discards from a network, for the
+        games that wait for the exchange (reset(defer_exchange=True)) with their declarer in `seats` / `seats_per_game`.
+        weights = (w1, b1, w2, b2, w3, b3) as policy_mlp takes them.  Row i < 8 of a game is "pick up talon group i" (the
+        features of include/tarok_env.h: what the declarer would hold, what stays in the talon, the group, the called
+        king's whereabouts, the shape of the new hand); output 54 of the network is the group's value, output c < 54 the
+        discard score of card c.  Returns choice [N] int8 and discards [N, 3] uint8 as playout_exchange() does — the
+        group of the largest value and its best-scored discardable cards; the Bot's own exchange where a game waits with
+        its declarer outside the set; -1 and 255s elsewhere — so exchange(choice, discards) applies them.  raw=True also
+        returns the float32 outputs [N, 8, 64] (zeros for rows that are not live), feature_words=True the input rows as
+        bits [N, 8, 4] int64 (expand_feature_words; zeros where not live): (choice, discards, raw, feature_words), None
+        for what was not asked for.  Read-only on the env."""
+        w1, b1, w2, b2, w3, b3 = self.check_mlp_weights(weights)
+        with torch.cuda.device(self.device):
+            if choice_out is None:
+                choice_out = torch.empty(self.n, dtype=torch.int8, device=self.device)
+            if discards_out is None:
+                discards_out = torch.empty((self.n, 3), dtype=torch.uint8, device=self.device)
+            raw_out = torch.empty((self.n, 8, 64), dtype=torch.float32, device=self.device) if raw else None
+            fw_out = torch.empty((self.n, 8, 4), dtype=torch.int64, device=self.device) if feature_words else None
+            _native.check(self.L.tarok_exchange_values(self._h, self._p(w1), self._p(b1), self._p(w2), self._p(b2), self._p(w3),
+                                                       self._p(b3), int(seats), self._p(self._seat_sets(seats_per_game)),
+                                                       self._p(raw_out), self._p(choice_out), self._p(discards_out),
+                                                       self._p(fw_out), self._stream()))
+        if not raw and not feature_words:
+            return choice_out, discards_out
+        return choice_out, discards_out, raw_out, fw_out
+
+    def exchange_candidates(self, discard_sets=4, salt=0, seats=15, seats_per_game=None):
+        """The cards playout_exchange()'s candidates laid down (tarok_exchange_candidates): [N, 6 * discard_sets, 3] uint8,
+        row i * discard_sets + d the discards of candidate (i, d) of a launch with the same discard_sets, salt and seat set
+        (255 beyond the group size; 255s for groups the contract does not have and games that do not take part).
+        Read-only on the env."""
+        with torch.cuda.device(self.device):
+            out = torch.empty((self.n, 6 * int(discard_sets), 3), dtype=torch.uint8, device=self.device)
+            _native.check(self.L.tarok_exchange_candidates(self._h, int(discard_sets), int(salt) & ((1 << 64) - 1), int(seats),
+                                                           self._p(self._seat_sets(seats_per_game)), self._p(out), self._stream()))
+        return out
+
     def shown_voids(self, out=None):
         """[N] int32 device tensor (tarok_shown_voids; the bits of a u32): bit 5 * seat + class of a game's word is set
         iff the play so far has shown that seat to hold no card of that class (class = min(card >> 3, 4): the four suits,

@@ -297,6 +297,50 @@ def evaluate_exchange_vs_bot(worlds, samples, discard_sets, n_games, episodes, s
                                                 inspect=inspect))
 
 
+def _exchangenet_passes(weights, n_games, episodes, seed, mix, device, inspect=None):
+    """_exchange_passes with the exchange head in the playout teacher's place: per pass a reset with the exchange
+    deferred, ONE tarok_exchange_values with the pass's seat set — its rows are the Bot's own exchange for a declarer
+    outside the set — and one tarok_exchange that applies them, then the Bot's card on every seat at every move.
+    inspect: one dict per pass — episode, seats, start (the lanes before the exchange), choice, discards, actions, scores."""
+    n = int(n_games)
+    weights = TarokVecEnv.check_mlp_weights(weights)
+    scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
+    env = TarokVecEnv(n, device=device, seed=seed, mix=mix)
+    try:
+        with torch.cuda.device(env.device):
+            actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
+            zeros = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=env.device)
+            choice = torch.empty(n, dtype=torch.int8, device=env.device)
+            discards = torch.empty((n, 3), dtype=torch.uint8, device=env.device)
+        for e in range(int(episodes)):
+            for p, seats in enumerate(PASS_SEATS):
+                env.reset(episode=e, clear_counters=True, defer_exchange=True)
+                start = env.state() if inspect is not None else None
+                env.exchange_values(weights, seats=seats, choice_out=choice, discards_out=discards)
+                env.exchange(choice, discards)
+                for t in range(GAME_CARDS):
+                    env.playout_cards(1, seats=0, sum_out=zeros, action_out=actions[t])
+                    env.step(actions[t], auto_reset=False)
+                _, ss = env.counters()                # (the pass's one synchronisation)
+                scores[p, e * n:(e + 1) * n] = ss
+                if inspect is not None:
+                    inspect.append(dict(episode=e, seats=seats, start=start, choice=choice.cpu().numpy(), discards=discards.cpu().numpy(),
+                                        actions=actions.cpu().numpy(), scores=ss.copy()))
+    finally:
+        env.close()
+    return scores
+
+
+def evaluate_exchangenet_vs_bot(weights, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, inspect=None):
+    """What is the exchange head's exchange worth?  evaluate_exchange_vs_bot with tarok_exchange_values in
+    tarok_playout_exchange's place: the five duplicate passes with the Bot playing EVERY card on every seat; in pass
+    1 + k the games seat k declared get their talon group and discards from the network — weights = (w1, b1, w2, b2, w3,
+    b3) as tarok_exchange_values takes them (exchange.ExchangeLearner.weights()) — and every other declarer exchanges as
+    the Bot does.  Pass 0 is the Bot's own exchange everywhere: evaluate_exchange_vs_bot's pass 0 on the same deals.
+    Returns duplicate_advantage's dict, `policy_mean` being that of the seat whose exchanges the head chose."""
+    return duplicate_advantage(_exchangenet_passes(weights, n_games, episodes, seed, mix, device, inspect=inspect))
+
+
 def _bidding_passes(worlds, samples, n_games, episodes, seed, device, salt=0, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS,
                     inspect=None):
     """The five passes with the playout player making the BID of its seat only: _bid_front, a reset that takes its
