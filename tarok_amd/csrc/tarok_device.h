@@ -145,6 +145,16 @@ __device__ __forceinline__ u64 hand_of(const Game &g, u32 s) {
     if (!C_PADDED) hh &= 0x3FFFFFu;
     return TK_U64(hl, hh);
 }
+// the same from the seat's two smears, for a caller that carries them from card to card
+template <bool C_PADDED = false>
+__device__ __forceinline__ u64 hand_of(const Game &g, u32 ma, u32 mb) {
+    u32 tl = TK_BITOP3(TK_LO(g.A), ma, TK_LO(g.C), ~c_ & ~(a_ ^ b_));
+    u32 th = TK_BITOP3(TK_HI(g.A), ma, TK_HI(g.C), ~c_ & ~(a_ ^ b_));
+    u32 hl = TK_BITOP3(tl, TK_LO(g.B), mb, a_ & ~(b_ ^ c_));
+    u32 hh = TK_BITOP3(th, TK_HI(g.B), mb, a_ & ~(b_ ^ c_));
+    if (!C_PADDED) hh &= 0x3FFFFFu;
+    return TK_U64(hl, hh);
+}
 // won pile of seat S (incl. whatever is parked in its pile bits): C & (A == S&1) & (B == S>>1)
 template <int S> __device__ __forceinline__ u64 pile_of(const Game &g) {
     u32 l, h;
@@ -239,6 +249,47 @@ __device__ __forceinline__ u64 legal_mask_follow(u64 hand, u32 lead, u32 contrac
     return TK_U64(bl, TK_BITOP3(bh, kf, only_pagat, a_ & ~(b_ & ~c_)));
 }
 
+// CARRIED WORDS.  A caller that plays a game card by card (the trick-aligned card loops) rebuilds nothing that only
+// changes with the game or with the trick: it keeps the words below and hands them to the overloads that follow.
+//   FamilyWord, once per game: the three facts of the contract the rules ask for, in ONE word read off a constant by
+//   the contract's number (two instructions where a game is taken): bit 0 = Klop, Berac or Odprti berac (the pagat
+//   rule; the legal masks and it as it is, for the high word of a hand has nothing above bit 21 and so bits 22 and 31
+//   clear nothing there), bit 22 = Berac or Odprti berac (the game ends with the declarer's first trick), bit 31 = Klop
+//   (the talon's gifts).  The constant: bits 0, 7, 9 | bits 22 + 7, 22 + 9 | bit 31, and nothing else within ten
+//   bits above any of the three places.
+//   LeadWord, once per trick: the byte of the suit led within a hand's low word, or zero where a tarok was led.
+#define TK_FAM_LUT 0xA0000281u
+#define TK_FAM_MASK 0x80400001u
+struct FamilyWord { u32 w; };
+struct LeadWord { u32 m; };
+__device__ __forceinline__ FamilyWord family_word(u32 contract) {
+    u32 w = (TK_FAM_LUT >> contract) & TK_FAM_MASK;     TK_KEEP_VGPR(w);
+    return FamilyWord{w};
+}
+__device__ __forceinline__ LeadWord lead_word(u32 lead) {
+    // (the smear pinned as a word: left to itself the compiler tests bit 5 of the id with a compare and selects)
+    u32 tarok_led = (u32)((int)(lead << 26) >> 31);     TK_KEEP_VGPR(tarok_led);
+    return LeadWord{(0xFFu << (lead & 24)) & ~tarok_led};
+}
+// legal_mask for the seat that LEADS (nobody has led: the hand, less the pagat where the rule holds)
+__device__ __forceinline__ u64 legal_mask(u64 hand, FamilyWord fam) {
+    u32 hl = TK_LO(hand), hh = TK_HI(hand);
+    u32 only_pagat = tk_zero_mask(hl | (hh & ~1u));
+    return TK_U64(hl, TK_BITOP3(hh, fam.w, only_pagat, a_ & ~(b_ & ~c_)));
+}
+// legal_mask_follow from the trick's LeadWord
+__device__ __forceinline__ u64 legal_mask_follow(u64 hand, LeadWord lead, FamilyWord fam, u32 &hi_sel) {
+    u32 hl = TK_LO(hand), hh = TK_HI(hand);
+    u32 s = hl & lead.m;
+    u32 zs = tk_zero_mask(s);                           // no card of the suit led
+    u32 zt = tk_zero_mask(hh);                          // no taroks
+    u32 bl = s | TK_BITOP3(hl, zs, zt, a_ & b_ & c_);
+    u32 bh = hh & zs;
+    u32 only_pagat = tk_zero_mask(bl | (bh & ~1u));
+    hi_sel = TK_BITOP3(zs, zt, zt, a_ & ~b_);           TK_KEEP_VGPR(hi_sel);      // (see legal_mask_follow above)
+    return TK_U64(bl, TK_BITOP3(bh, fam.w, only_pagat, a_ & ~(b_ & ~c_)));
+}
+
 __device__ __forceinline__ u64 legal_now(const Game &g) {
     u32 seat = (g.leader + g.nt) & 3;
     return legal_mask(hand_of(g, seat), g.nt != 0, g.trick & 63, g.contract);
@@ -268,6 +319,17 @@ __device__ __forceinline__ u32 obs_carry_hi(u32 carry) { return (carry >> 8) | (
 // the observation word of a game in play from the carried word (fin01: the game ended with this card, 0 / 1)
 __device__ __forceinline__ u64 obs_word_with(u32 carry, u32 error, u32 fin01, u64 legal) {
     return legal | ((u64)(obs_carry_hi(carry) | (fin01 << 30) | (error << 31)) << 32);
+}
+
+// The same with the game's error bit carried IN the word, already shifted: bit 7 of the carried word is bit 31 of the
+// observation's high word after the turn (and bit 6, which the position never reaches — 47 cards at the most — is
+// where the turn takes bit 30 from: it stays clear).  The error bit only changes where a game is taken: no shift and
+// no or per card.  The seat's two smears (hand_of) are read off the same word.
+__device__ __forceinline__ u32 obs_carry(u32 seat, u32 pos, u32 error) { return (error << 7) | obs_carry(seat, pos); }
+__device__ __forceinline__ u32 obs_carry_ma(u32 carry) { return (u32)((int)(carry << 1) >> 31); }
+__device__ __forceinline__ u32 obs_carry_mb(u32 carry) { return (u32)((int)carry >> 31); }
+__device__ __forceinline__ u64 obs_word_with(u32 carry_with_error, u32 fin01, u64 legal) {
+    return legal | ((u64)(obs_carry_hi(carry_with_error) | (fin01 << 30)) << 32);
 }
 
 // observation word (tarok_env.h TAROK_OBS_*)
@@ -348,8 +410,11 @@ __device__ __forceinline__ u64 berac_scores(const Game &g) {
 // together, on dense lanes).  want_tv = false skips the trick value (nobody asked for trick_info).
 // c_lead: where the caller kept the C plane of the moment the trick's first card was played (the trick-aligned
 // card loops), the trick's cards are the bits that plane has gained since; otherwise they come from the ids.
-template <bool TRUSTED = false, bool DEFER = false>
-__device__ __forceinline__ int apply_step(Game &g, u32 a, u64 &scores, u32 &trick_info, bool want_tv = true, const u64 *c_lead = nullptr) {
+// CARRIED: the caller keeps the game's FamilyWord and the trick's LeadWord (above) and hands them in: the suit led,
+// the Berac test and the Klop test are read off them, not rebuilt from g.trick and g.contract.
+template <bool TRUSTED = false, bool DEFER = false, bool CARRIED = false>
+__device__ __forceinline__ int apply_step(Game &g, u32 a, u64 &scores, u32 &trick_info, bool want_tv = true, const u64 *c_lead = nullptr,
+                                          FamilyWord fam = FamilyWord{0u}, LeadWord lead = LeadWord{0u}) {
     if (!TRUSTED) {
         u64 legal = legal_now(g);
         bool ok = a < 54 && ((legal >> (a & 63)) & 1);
@@ -370,7 +435,8 @@ __device__ __forceinline__ int apply_step(Game &g, u32 a, u64 &scores, u32 &tric
         u32 c0 = g.trick & 63, c1 = (g.trick >> 6) & 63, c2 = (g.trick >> 12) & 63, c3 = (g.trick >> 18) & 63;
         tm = (1ULL << c0) | (1ULL << c1) | (1ULL << c2) | (1ULL << c3);
     }
-    u32 th = TK_HI(tm), tl_ = TK_LO(tm) & (0xFFu << (g.trick & 24));     // taroks played; cards of the suit led
+    // taroks played; cards of the suit led (CARRIED: none where a tarok was led — th is not zero then, and the word is not read)
+    u32 th = TK_HI(tm), tl_ = TK_LO(tm) & (CARRIED ? lead.m : (0xFFu << (g.trick & 24)));
     // The winning card is the top bit of the tarok word, or of the suit word when no tarok was played (the card led
     // is a tarok or of its own suit: the chosen word is never zero), and WHO played it is still written in the
     // owner planes at that bit — played cards keep their player's seat bits until the trick changes hands just
@@ -380,7 +446,8 @@ __device__ __forceinline__ int apply_step(Game &g, u32 a, u64 &scores, u32 &tric
     u32 aw = TK_BITOP3(TK_HI(g.A), TK_LO(g.A), zt, (a_ & ~c_) | (b_ & c_)), bw = TK_BITOP3(TK_HI(g.B), TK_LO(g.B), zt, (a_ & ~c_) | (b_ & c_));
     u32 ws = __builtin_amdgcn_ubfe(aw, wbit, 1) | (__builtin_amdgcn_ubfe(bw, wbit, 1) << 1);
     {   // talon gift, Klop.py:67-71: talon.pop() joins the trick after the winner is known
-        u32 gift = tk_zero_mask(g.contract) & ((g.tl + 7u) >> 3);         // 1: a Klop with talon cards left
+        // 1: a Klop with talon cards left (CARRIED: the Klop bit is the word's top bit, and min(tl, 1) is "cards left")
+        u32 gift = CARRIED ? min(g.tl, fam.w >> 31) : (tk_zero_mask(g.contract) & ((g.tl + 7u) >> 3));
         g.tl -= gift;
         u64 gb = 1ULL << ((u32)(g.talon >> (6 * g.tl)) & 63u);
         u32 gm = 0u - gift;
@@ -403,7 +470,7 @@ __device__ __forceinline__ int apply_step(Game &g, u32 a, u64 &scores, u32 &tric
     // straight-line selects: lanes of one wave sit in every combination of these cases
     // (as a 0 / 1 number made of plain vector instructions: the caller's test of it is then ONE compare, which a
     // wave vote can use as it is; a vote on a compound condition goes compare -> scalar and -> select -> compare)
-    u32 berac01 = (0x280u >> g.contract) & 1u;                           // TK_BERAC = 7, TK_ODPRTI_BERAC = 9
+    u32 berac01 = CARRIED ? __builtin_amdgcn_ubfe(fam.w, 22u, 1u) : ((0x280u >> g.contract) & 1u);    // TK_BERAC = 7, TK_ODPRTI_BERAC = 9
     u32 over01 = ((g.trick_no + 4u) >> 4) | (berac01 & tk_zero_mask(ws ^ g.declarer));      // (trick_no <= 12)
     if (!DEFER) {
         if (over01) scores = berac01 ? berac_scores(g) : score_game(g);

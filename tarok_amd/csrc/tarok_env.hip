@@ -677,7 +677,12 @@ __device__ __forceinline__ void play_role(
     // trick-aligned loops, carried from card to card: the RNG counter of the card to play (rng_ctr(128 + cards played)) and
     // the seat / position half of the observation word (obs_carry) — each moves by a constant per card
     u32 rctr = 0, ocar = 0;
-    u32 resync_v = 0;                        // `resync` of the fast-renewal loop, as a number (a bool carried through a loop is a
+    // trick-aligned loops, carried too: what the rules ask of the contract (FamilyWord: set where a game is taken, as rctr is) and
+    // of the card led (LeadWord: set at a trick's first card; with it g.trick is not read in these loops).  The game's error
+    // bit rides in ocar, already shifted (obs_carry), and the smears of the seat to play are read off ocar's top bits
+    FamilyWord fam = FamilyWord{0u};
+    LeadWord led = LeadWord{0u};
+    u32 resync_v = 0;                       // `resync` of the fast-renewal loop, as a number (a bool carried through a loop is a
                                              // lane mask, merged with three scalar instructions at every join, used or not)
     // the fast-renewal loop's `allowed` and `blocked` in one number: how many games of this launch the lane may take
     // from lines — none for a lane that cannot finish in this launch (its counters are not loaded), none any more
@@ -747,7 +752,9 @@ __device__ __forceinline__ void play_role(
         // (trick-aligned loops: the C plane as the trick's first card finds it — what it gains until the 4th card is the trick)
         if constexpr (ALL && NT == 0) c_lead = g.C;
         const u64 *lead_plane = (ALL && NT >= 0) ? &c_lead : nullptr;
-        if (play) res = apply_step<true, true>(g, a, scores, trick_info, !STD && trick != nullptr, lead_plane);
+        if constexpr (ALL && NT == 0) led = lead_word(a);
+        if constexpr (ALIGNED) res = apply_step<true, true, true>(g, a, scores, trick_info, !STD && trick != nullptr, lead_plane, fam, led);
+        else if (play) res = apply_step<true, true>(g, a, scores, trick_info, !STD && trick != nullptr, lead_plane);
         bool fin = res == 1;
         // the play history (zgodovina, Klop.py:63 / Navadna_igra.py:127): card `pos` of the game, one byte,
         // write-only here; only the reference-layout observation (k_observe_ref) reads it
@@ -853,7 +860,7 @@ __device__ __forceinline__ void play_role(
                     deal_in_place(lineless, d, dk);
                     if (lineless) { pack(d, na.x, na.y, nb.x, nb.y); nkey = dk; nep1 = cur_ep + 1; }
                 }
-                if (fin) { push_finished(fm, slot0); swap_in(); cur_ep++; consumed++; rctr = rng_ctr(128u).v; }
+                if (fin) { push_finished(fm, slot0); swap_in(); cur_ep++; consumed++; rctr = rng_ctr(128u).v; fam = family_word(g.contract); }
             }
         }
         if constexpr (CAN_END && !FAST_RENEW) {
@@ -895,17 +902,18 @@ __device__ __forceinline__ void play_role(
             }
         }
         // (ALL: a finished game has been replaced just above, so every lane is in play again)
-        if constexpr (ALIGNED && NT < 3) legal = legal_mask_follow(hand_of<true>(g, (g.leader + g.nt) & 3), g.trick & 63, g.contract, legal_hi);
-        else if constexpr (ALIGNED) legal = legal_mask(hand_of<true>(g, g.leader), false, 0u, g.contract);
+        // (trick-aligned loops: the seat and position bits are carried, one add per card; after the 4th card the seat to play
+        // is the trick's winner, or a fresh game's leader, and the error bit may be a fresh game's: rebuilt there.  The hand
+        // to play next is the hand of the seat in the word's top bits)
+        if constexpr (ALIGNED && NT < 3) ocar += TK_OBS_CARD;
+        else if constexpr (ALIGNED) ocar = obs_carry(g.leader, g.trick_no << 2, g.error);
+        if constexpr (ALIGNED && NT < 3) legal = legal_mask_follow(hand_of<true>(g, obs_carry_ma(ocar), obs_carry_mb(ocar)), led, fam, legal_hi);
+        else if constexpr (ALIGNED) legal = legal_mask(hand_of<true>(g, obs_carry_ma(ocar), obs_carry_mb(ocar)), fam);
         else legal = (ALL || (v && g.phase == TK_PHASE_PLAY)) ? legal_now(g) : 0;
         // (ALL: res is 0 or 1 — the number itself goes into the observation's bit 62 and the done row, no selects)
         const u32 fin01 = ALL ? (u32)res : (fin ? 1u : 0u);
         if constexpr (ALIGNED) {
-            // (the seat and position bits are carried: one add per card; after the 4th card the seat to play is the
-            // trick's winner, or a fresh game's leader: rebuilt there, two instructions)
-            if constexpr (NT < 3) ocar += TK_OBS_CARD;
-            else ocar = obs_carry(g.leader, g.trick_no << 2);
-            TK_STREAM_STORE(out_obs, obs_word_with(ocar, g.error, fin01, legal));
+            TK_STREAM_STORE(out_obs, obs_word_with(ocar, fin01, legal));
             if (STD || done) TK_STREAM_STORE(&done[out_b], (uint8_t)fin01);
             out_b += (u32)stride; out_obs += stride;          // (the card's last stores: on to the next card's row)
         } else if (v) {
@@ -927,7 +935,8 @@ __device__ __forceinline__ void play_role(
                 // the bits too); the plane is cleaned where it leaves: below, and where a finished game is scored.
                 g.C |= TK_C_PAD;
                 rctr = rng_ctr(128u + g.trick_no * 4).v;
-                ocar = obs_carry(g.leader, g.trick_no << 2);
+                ocar = obs_carry(g.leader, g.trick_no << 2, g.error);
+                fam = family_word(g.contract);
                 // (these copies address their rows by out_b / out_obs, advanced inside the card: `row` is not read)
                 for (int c = 0; c < cards; c += 4) {
                     play_card(std::true_type{}, std::integral_constant<int, 0>{}, std_tag, row, c);
