@@ -614,12 +614,15 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         sum += __shfl_xor(sum, 32);
         za += __shfl_xor(za, 32);                            // (one of the pair holds the played card, which is legal)
         float ls = __logf(sum), inv = 1.0f / sum;
+        // (the entropy's sum is written out like the gradient below, "ONE ROUNDING SEQUENCE": H - p log p with the product
+        // rounded, but one fma in k = 26 and 27, the forms k_learn_chain<false> has had)
         float H = 0.f;
 #pragma unroll
         for (int k = 0; k < 32; k++) {
+#pragma clang fp contract(off)
             float p = p_[k] * inv;
             float lp = l[k] - ls;                            // log p (finite where p = 0: p log p = 0)
-            H -= p * lp;
+            H = (k == 26 || k == 27) ? __builtin_fmaf(-p, lp, H) : H - p * lp;
             p_[k] = p;
             l[k] = lp;
         }
@@ -653,6 +656,17 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         }
         // d loss / d output (unscaled: k_learn_reduce divides by the sum of the weights) -> D[sample][output], bf16; the sample's
         // weight folded into the two coefficients
+        // ONE ROUNDING SEQUENCE, WRITTEN OUT.  Both instantiations compute the three terms' part of an element by the same
+        // float32 operations, so that tarok_learn_chain_distill at coefficient 0 gives tarok_learn_chain's bytes: no
+        // contraction is left to the compiler here (it chose differently for <false> and <true> in the two columns beside
+        // the value's select: DESIGN.md section 8.5).  e = (ew p) (log p + H) rounds twice; then
+        //     every column but the two below:   fma(gw, t, e)
+        //     k = 26 (outputs 50 | 54):         gw t + e, both products rounded
+        //     k = 27 (outputs 51 | 55):         fma(ew p, log p + H, gw t)
+        // — the forms k_learn_chain<false> has had since the term was added: a plain launch computes what it always did.
+        // DISTILL: + cw y, y = fma(S, p, -q), as one more fma, taken only where cw != 0 and y != 0: at coefficient 0, in every
+        // row of weight 0, in a row without a teacher (64 zeros) and in the column of an illegal card the element keeps its
+        // bytes (x + 0 would turn a -0 into +0, and 0 x a non-finite target is a NaN).
         const float gw = g * w, ew = a.ent_coef * w, dval = w * a.vf_coef * 2.0f * dv;
         float cw = 0.f;
         if constexpr (DISTILL) cw = a.distill_coef * w;
@@ -663,11 +677,18 @@ TK_KERNEL(LN_CHAIN_THREADS, 256) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                 float d4[4];
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
+#pragma clang fp contract(off)
                     int k = 16 * ft + 4 * q + j;
                     float p = p_[k];
                     float t = (act_h == (u32)(32 * ft + 8 * q + j)) ? 1.0f - p : -p;
-                    d4[j] = gw * t + ew * p * (l[k] + H);
-                    if constexpr (DISTILL) d4[j] += cw * (S * p - tqf[k]);
+                    const float ep = ew * p, lh = l[k] + H;
+                    if (k == 26) d4[j] = gw * t + ep * lh;
+                    else if (k == 27) d4[j] = __builtin_fmaf(ep, lh, gw * t);
+                    else d4[j] = __builtin_fmaf(gw, t, ep * lh);
+                    if constexpr (DISTILL) {
+                        const float y = __builtin_fmaf(S, p, -tqf[k]);
+                        d4[j] = (cw != 0.f && y != 0.f) ? __builtin_fmaf(cw, y, d4[j]) : d4[j];
+                    }
                     if (ft == 1 && q == 2 && j == 2) d4[j] = (h == 1) ? dval : d4[j];      // output 54: the value
                 }
                 *reinterpret_cast<uint2 *>(D + gi * LN_LDD + 32 * ft + 8 * q + 4 * h) = make_uint2(ln_bf16x2_of(d4[0], d4[1]), ln_bf16x2_of(d4[2], d4[3]));

@@ -78,7 +78,9 @@ def restate32(logits, legal, w, q, coef, mutant=None):
     Sg = np.ones_like(Ssum) if mutant == "noS" else Ssum
     cw = (f(coef) * (np.ones_like(w) if mutant == "unweighted" else w)).astype(f)
     d = np.zeros((n, 64), f)
-    d[:, :54] = cw[:, None] * (Sg[:, None] * p - qs)
+    with np.errstate(invalid="ignore"):                        # the kernel's order: fma(cw, fma(S, p, -q), the other terms = 0)
+        inner = (Sg[:, None].astype(np.float64) * p.astype(np.float64) - qs.astype(np.float64)).astype(f)
+        d[:, :54] = np.where(cw[:, None] != 0, cw[:, None] * inner, f(0))
     wsum = max(float(w.sum()), 1.0)
     means = np.array([float((w * ce).sum(dtype=f)) / wsum, float((w * Ssum).sum(dtype=f)) / wsum])
     return torch.from_numpy(d).to(torch.bfloat16).double().numpy(), means
@@ -114,6 +116,20 @@ def test_float32_restatement_within_the_bounds_and_mutants_rejected():
         assert msgs or bad_means.any(), "the comparator lets the mutant '%s' through" % mutant
         if mutant == "all54":
             assert bad_means.any()
+
+
+def test_target_rows_random_is_target_rows_without_the_loop():
+    """The generator for large sample sets against the row-by-row one: rows without a card, one-card rows, full rows."""
+    rnd = np.random.RandomState(3)
+    legal = rnd.rand(4096, 54) < rnd.rand(4096, 1) * 0.4
+    legal[::97] = False
+    legal[1::97] = False
+    legal[1::97, 5] = True
+    legal[2::97] = True
+    for seed in (0, 7):
+        a, b = DM.target_rows(legal, "random", seed=seed), DM.target_rows_random(legal, seed=seed)
+        assert a.shape == b.shape == (4096, 64) and np.array_equal(a, b)
+    assert (b[::97] == 0).all() and (b[1::97, 5] == 1).all() and (b[:, 54:] == 0).all() and (b[~np.pad(legal, ((0, 0), (0, 10)))] == 0).all()
 
 
 def test_target_rows_model_on_hand_made_sums():

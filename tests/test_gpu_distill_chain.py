@@ -68,6 +68,8 @@ def test_distill_term_element_by_element(T):
             idx = torch.from_numpy(rows).cuda().contiguous() if indexed else None
             what0 = "set %s, B = %d, %s" % (name, B, "through an index" if indexed else "index NULL")
             plain = learner.chain(B, words, idx, rec, stats, mode)
+            # its dOut as 16-bit words (the float64 copy of a bf16 number converts back exactly, the sign of a zero included)
+            plain_raw = torch.from_numpy(plain["dOut"]).to(torch.bfloat16).view(torch.int16).numpy()
             ref = subset_reference(cases, logits, logp_old, rows)
             dead = ref["w"] == 0
             for kind in KINDS:
@@ -80,7 +82,7 @@ def test_distill_term_element_by_element(T):
                 for k in ("H1", "H2"):
                     assert np.array_equal(got[k], plain[k]), (what, k)
                 assert np.array_equal(got["terms"].view(np.uint32), plain["terms"].view(np.uint32)), what
-                assert (got["dOut"][dead] == plain["dOut"][dead]).all(), what + ": dOut of a row of weight 0 is not the no-teacher dOut"
+                assert np.array_equal(got["raw"]["dOut"][dead], plain_raw[dead]), what + ": dOut of a row of weight 0 is not the no-teacher dOut"
                 d = DM.distill_reference(ref, q[rows])
                 part = DM.distill_gradient(d, COEF)
                 ratio, msgs = L.violations(got["dOut"], d["w"][:, None] * part, DM.distill_bound(d, part, d["w"], COEF), "dOut, " + what)
@@ -93,7 +95,7 @@ def test_distill_term_element_by_element(T):
                 if not (merr <= mb).all():
                     fails.append("distill_out, %s: kernel %r, reference %r, bound %r" % (what, got["distill"], means, mb))
                 if kind == "zero":
-                    assert (got["dOut"] == plain["dOut"]).all() and (got["distill"] == 0).all(), what
+                    assert np.array_equal(got["raw"]["dOut"], plain_raw) and (got["distill"] == 0).all(), what
                 if kind == "random":
                     # NaN in every column the term must not look at changes no byte; a second launch gives the same bytes;
                     # coef = 0 gives the plain launch's dOut; distill_running accumulates
@@ -107,7 +109,7 @@ def test_distill_term_element_by_element(T):
                     assert np.array_equal(nan["distill"].view(np.uint32), got["distill"].view(np.uint32)), what
                     running = torch.tensor([1.0, 2.0], device="cuda")
                     zero = chain_distill(learner, B, words, idx, rec, stats, mode, tdev(q), 0.0, running)
-                    assert (zero["dOut"] == plain["dOut"]).all(), what + ": coef = 0 changed dOut"
+                    assert np.array_equal(zero["raw"]["dOut"], plain_raw), what + ": coef = 0 changed dOut"
                     assert np.array_equal(zero["distill"].view(np.uint32), got["distill"].view(np.uint32))
                     assert np.array_equal(running.cpu().numpy(), np.array([1.0, 2.0], np.float32) + zero["distill"]), what
         learner.close()

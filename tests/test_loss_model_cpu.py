@@ -36,6 +36,13 @@ def f32_exp(x):
         return np.exp2((x.astype(F) * LOG2E).astype(F)).astype(F)
 
 
+def fma32(a, b, c):
+    """fmaf on float32 arrays: the product of two float32 numbers is exact in float64, so only the sum rounds — to float64
+    and then to float32, which differs from fmaf's single rounding on about 2^-29 of all inputs (a tie after the first)."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(F)
+
+
 def f32_loss(logits, legal, act, logp_old, A, ret, scale, clip, vf, ent, mutant=0):
     """The loss phase of k_learn_chain in numpy float32, all 64 outputs of a sample at once; returns the bf16 output as
     float64 [n,64].  mutant 1..6, 8: the wrong kernels of test_the_comparator_reports_every_mutant."""
@@ -84,7 +91,13 @@ def f32_loss(logits, legal, act, logp_old, A, ret, scale, clip, vf, ent, mutant=
         elif mutant == 3:
             d = gw[:, None] * t
         else:
-            d = gw[:, None] * t + ew[:, None] * p * (lp + H[:, None])
+            # the kernel's written-out order (tarok_learner.inc, "ONE ROUNDING SEQUENCE"): e = (ew p)(log p + H) rounds twice,
+            # then fma(gw, t, e) — but gw t + e with both products rounded in output 50 and fma(ew p, log p + H, gw t) in 51
+            ep, lh = (ew[:, None] * p).astype(F), (lp + H[:, None]).astype(F)
+            e_, gt = (ep * lh).astype(F), (gw[:, None] * t).astype(F)
+            d = fma32(np.broadcast_to(gw[:, None], t.shape), t, e_)
+            d[:, 50] = (gt + e_).astype(F)[:, 50]
+            d[:, 51] = fma32(ep, lh, gt)[:, 51]
     d = d.astype(F)
     d[:, 54] = dval
     assert np.isfinite(d).all()
