@@ -521,6 +521,48 @@ int tarok_bid_values(tarok_env *env, uint32_t episode, const uint8_t *deals, con
                      const float *b2, const void *w3, const float *b3, float scale, int contracts, int seats,
                      const uint8_t *seats_per_game, int32_t *value_out, float *raw_out, uint64_t *feature_words_out, void *stream);
 
+/* The value of a pass: what a seat expects to score when ANOTHER seat declares.  Three entries beside tarok_playout_bids,
+ * tarok_bid_values and tarok_bid_round, which keep their bytes (row 19 written and read as zero).  Here row
+ * TAROK_BID_PASS_ROW = 19 of the [N,4,TAROK_BID_ROWS] array is the pass.  Exact and integer.
+ *
+ * Pass playout (v, w, k), w < worlds, k < samples, for a viewer v of the game's seat set.  World w of viewer v is
+ *   tarok_playout_bids' world, under the same wkey: the pass is valued on the re-deals the nineteen options are valued on.
+ *   The playout key is that launch's pkey with r = 19 (it fits the row field's five bits; no other playout uses it):
+ *     pkey = game_key(seed ^ salt, gidx, 3 << 61 | (u64)episode << 28 | v << 26 | 19 << 21 | w << 15 | k)
+ *   The playout is a TAROK_MIX_BOT game under pkey on the world's hands.  Its bidding round is tarok_bid_round's control
+ *   flow (Igra.licitacija) under pkey; every licitiram call counts in n.  The three other seats answer as the Bot does,
+ *   draw 72 + n of pkey behind the player-side filter.  Seat v gives its least answer on every call: Naprej, or obvezno
+ *   where it has one — seat 0's forced Klop when the three Bots passed, the only way v ends as the declarer.  The king of
+ *   a Tri / Dve / Ena is pick(rng32(pkey, 67), 4).  The game is then set up on the WORLD's hands and talon with that
+ *   contract, declarer and king: the partner follows from the world, and v may turn out to be the called partner.  The
+ *   Bot's exchange (group 0, draws 68 + j of pkey) where the contract has one; every card by the Bot, draw 128 + q at q
+ *   cards played.  The VIEWER's final score is added to sum_out[g][v][19].
+ *   The three other seats bid as Bots here even where the real table has more seats in the set: row 19 is the seat's
+ *   expectation against the Bot's round, not a solution of the bidding game.  It does not depend on `contracts` (a pass is
+ *   always an option; the Bots bid in their own range whatever the mask), on the standing bid or on who else is in the set.
+ *
+ * tarok_playout_bids_pass: tarok_playout_bids' arguments, TAROK_EINVAL conditions and NULL-output rule.  Rows 0..18 of
+ *   sum_out are byte for byte tarok_playout_bids' at equal arguments; row 19 is the sum of the worlds * samples pass playouts
+ *   of the viewer, 0 for a seat outside the set and for an invalid deal.  A launch at (W', S') sums a corner of one at
+ *   (W >= W', S >= S'), row 19 included.
+ * tarok_bid_values_pass: tarok_bid_values' arguments, TAROK_EINVAL conditions and outputs.  Rows 0..18 of value_out and
+ *   raw_out are byte for byte tarok_bid_values'; row 19 is output 19 of the network, scaled, clamped and rounded as the
+ *   other rows are (raw_out: unscaled), 0 for a seat outside the set and for an invalid deal, whatever `contracts` holds.
+ * tarok_bid_round_pass: tarok_bid_round with a bar of the seat's own in the constant one's place.  A seat v inside the set
+ *   answers by tarok_bid_round's rule with
+ *     thr(v) = (int64) S(19) + (int64) margin * playouts
+ *   where that rule has threshold * playouts; candidates, the best row, ties, standing on obvezno and the king by the
+ *   declarer's best row are unchanged.  `margin` is in points per game, as `threshold` is.  With row 19 all zero the
+ *   outputs are tarok_bid_round's at threshold = margin.  tarok_bid_round's TAROK_EINVAL conditions. */
+#define TAROK_BID_PASS_ROW 19
+int tarok_playout_bids_pass(tarok_env *env, uint32_t episode, const uint8_t *deals, int worlds, int samples, int contracts, uint64_t salt,
+                            int seats, const uint8_t *seats_per_game, int32_t *sum_out, void *stream);
+int tarok_bid_values_pass(tarok_env *env, uint32_t episode, const uint8_t *deals, const void *w1, const float *b1, const void *w2,
+                          const float *b2, const void *w3, const float *b3, float scale, int contracts, int seats,
+                          const uint8_t *seats_per_game, int32_t *value_out, float *raw_out, uint64_t *feature_words_out, void *stream);
+int tarok_bid_round_pass(tarok_env *env, uint32_t episode, const int32_t *sums, int playouts, int margin, int contracts, int seats,
+                         const uint8_t *seats_per_game, int8_t *contract_out, int8_t *declarer_out, int8_t *king_out, void *stream);
+
 /* The exchange head: a network that picks the talon group and the discards, in tarok_playout_exchange's place in front of
  * tarok_exchange.  Read-only on the env, stream-ordered, capturable.  A game TAKES PART exactly as in
  * tarok_playout_exchange: it waits for the exchange (TAROK_DEFER_EXCHANGE) and its declarer is in the seat set (`seats`, or

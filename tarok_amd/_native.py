@@ -33,6 +33,7 @@ SYMBOLS = [
     "tarok_playout_targets", "tarok_learn_chain_distill", "tarok_shown_voids", "tarok_playout_cards_voids",
     "tarok_playout_exchange", "tarok_played_cards", "tarok_playout_cards_hidden", "tarok_playout_bids", "tarok_bid_round",
     "tarok_bid_values", "tarok_exchange_values", "tarok_exchange_candidates",
+    "tarok_playout_bids_pass", "tarok_bid_round_pass", "tarok_bid_values_pass",
 ]
 
 
@@ -177,6 +178,8 @@ def lib():
     L.tarok_playout_bids.restype = i32; L.tarok_playout_bids.argtypes = [vp, u32, vp, i32, i32, i32, u64, i32, vp, vp, vp]
     L.tarok_bid_round.restype = i32; L.tarok_bid_round.argtypes = [vp, u32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.tarok_bid_values.restype = i32; L.tarok_bid_values.argtypes = [vp, u32, vp] + [vp] * 6 + [f32, i32, i32] + [vp] * 5
+    for twin in ("tarok_playout_bids", "tarok_bid_round", "tarok_bid_values"):      # the _pass entries take their siblings' arguments
+        getattr(L, twin + "_pass").restype = i32; getattr(L, twin + "_pass").argtypes = getattr(L, twin).argtypes
     L.tarok_exchange_values.restype = i32; L.tarok_exchange_values.argtypes = [vp] + [vp] * 6 + [i32] + [vp] * 6
     L.tarok_exchange_candidates.restype = i32; L.tarok_exchange_candidates.argtypes = [vp, i32, u64, i32, vp, vp, vp]
     L.tarok_playout_targets.restype = i32; L.tarok_playout_targets.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp]

@@ -25,13 +25,19 @@ def row_mask(contracts, device=None):
                         device=device)
 
 
-def bid_loss(out, sums, playouts, reward_scale, contracts):
+def bid_loss(out, sums, playouts, reward_scale, contracts, pass_value=False):
     """The head's loss from network outputs `out` [M, >= 19] and the teacher's sums [M, K.BID_ROWS] (int): target =
     sums / playouts * reward_scale, Huber loss (delta 1) over the rows whose contract is in `contracts`, averaged over
-    those entries.  The other columns enter neither the value nor the gradient."""
-    rows = row_mask(contracts, out.device)
-    target = sums[:, :BID_OPTIONS].to(torch.float32) * (float(reward_scale) / float(playouts))
-    return F.huber_loss(out[:, :BID_OPTIONS].float()[:, rows], target[:, rows], reduction="mean", delta=1.0)
+    those entries.  The other columns enter neither the value nor the gradient.
+    pass_value=True (out [M, >= 20], sums from playout_bids(pass_value=True)): row K.BID_PASS_ROW joins those rows — output
+    19 regresses on the value of a pass, same target, same loss."""
+    if not pass_value:
+        rows = row_mask(contracts, out.device)
+        target = sums[:, :BID_OPTIONS].to(torch.float32) * (float(reward_scale) / float(playouts))
+        return F.huber_loss(out[:, :BID_OPTIONS].float()[:, rows], target[:, rows], reduction="mean", delta=1.0)
+    rows = torch.cat([row_mask(contracts, out.device), torch.ones(1, dtype=torch.bool, device=out.device)])
+    target = sums[:, :K.BID_ROWS].to(torch.float32) * (float(reward_scale) / float(playouts))
+    return F.huber_loss(out[:, :K.BID_ROWS].float()[:, rows], target[:, rows], reduction="mean", delta=1.0)
 
 
 def pack_weights(net):
@@ -49,10 +55,12 @@ class BidLearner:
     env: a TarokVecEnv (never reset by the learner: both launches come before reset()), or None for a learner on the
     CPU that is fed batches by hand (loss / step).  worlds, samples: the teacher's launch (playout_bids).  contracts: the
     rows learned and bid.  playouts_equiv: the `playouts` bid_round() is told for the head's values, which are scaled to
-    sums over that many playouts, so `threshold` stays in points per game as for the teacher."""
+    sums over that many playouts, so `threshold` stays in points per game as for the teacher.  pass_value=True: the teacher
+    also values a pass (playout_bids(pass_value=True)), output 19 regresses on it, and round() holds every bid against the
+    seat's own pass (bid_values / bid_round with pass_value=True; `threshold` is then the margin over the pass)."""
 
     def __init__(self, env, worlds=8, samples=2, contracts=K.BID_DEFAULT_CONTRACTS, lr=1e-3, reward_scale=1.0 / 70.0,
-                 playouts_equiv=16, seed=0):
+                 playouts_equiv=16, seed=0, pass_value=False):
         if not 1 <= int(contracts) <= K.BID_ALL_CONTRACTS:
             raise ValueError("contracts: a bit set within 1..0x3FF")
         if not (reward_scale > 0 and int(playouts_equiv) >= 1):
@@ -61,6 +69,7 @@ class BidLearner:
         self.device = env.device if env is not None else torch.device("cpu")
         self.worlds, self.samples, self.contracts = int(worlds), int(samples), int(contracts)
         self.reward_scale, self.playouts_equiv = float(reward_scale), int(playouts_equiv)
+        self.pass_value = bool(pass_value)
         self.scale = self.playouts_equiv / self.reward_scale        # tarok_bid_values' scale: outputs -> sums over playouts_equiv
         if not self.scale <= 2.0 ** 20:
             raise ValueError("playouts_equiv / reward_scale exceeds tarok_bid_values' largest scale, 2**20")
@@ -80,7 +89,8 @@ class BidLearner:
 
     def loss(self, feature_words, sums, playouts):
         """bid_loss of the network on feature words [..., 4] and the teacher's sums [..., K.BID_ROWS] at `playouts`."""
-        return bid_loss(self.outputs(feature_words), sums.reshape(-1, K.BID_ROWS), playouts, self.reward_scale, self.contracts)
+        return bid_loss(self.outputs(feature_words), sums.reshape(-1, K.BID_ROWS), playouts, self.reward_scale, self.contracts,
+                        pass_value=self.pass_value)
 
     def step(self, feature_words, sums, playouts):
         """One Adam step on one batch; returns the loss before the step (a float)."""
@@ -99,7 +109,8 @@ class BidLearner:
     def collect(self, episode):
         """(feature_words [N,4,4] int64, sums [N,4,K.BID_ROWS] int32, playouts) of episode `episode`: the teacher's launch
         on every seat and the head's launch for its input rows."""
-        sums = self.env.playout_bids(episode, self.worlds, self.samples, contracts=self.contracts, salt=self.salt)
+        sums = self.env.playout_bids(episode, self.worlds, self.samples, contracts=self.contracts, salt=self.salt,
+                                     pass_value=self.pass_value)
         _, _, fw = self.env.bid_values(episode, self.weights(), self.scale, contracts=self.contracts, feature_words=True)
         return fw, sums, self.worlds * self.samples
 
@@ -113,6 +124,6 @@ class BidLearner:
     def round(self, episode, seats=15, threshold=0, deals=None, seats_per_game=None):
         """The bidding round with the head on `seats`: (contract, declarer, king_suit) as reset() takes them."""
         values = self.env.bid_values(episode, self.weights(), self.scale, contracts=self.contracts, deals=deals, seats=seats,
-                                     seats_per_game=seats_per_game)
+                                     seats_per_game=seats_per_game, pass_value=self.pass_value)
         return self.env.bid_round(episode, values, self.playouts_equiv, threshold=threshold, contracts=self.contracts, seats=seats,
-                                  seats_per_game=seats_per_game)
+                                  seats_per_game=seats_per_game, pass_value=self.pass_value)

@@ -1276,3 +1276,108 @@ __device__ __forceinline__ u32 exchange_choice(const float *y, u32 stride, u32 n
     }
     return best;
 }
+
+// ---------------------------------------------------------------------------
+// The value of a pass (tarok_playout_bids_pass / tarok_bid_round_pass, include/tarok_env.h)
+// ---------------------------------------------------------------------------
+#define TK_BID_PASS_ROW 19
+// The bar a bid has to clear at a seat whose row 19 holds the summed score of passing: the pass itself plus `margin`
+// points per game.  Stated once: the kernel, the host program and (tests/playout_pass_model.py) the model's own line.
+__device__ __forceinline__ long long pass_bar(int s19, int margin, int playouts) {
+    return (long long)s19 + (long long)margin * (long long)playouts;
+}
+
+// Igra.licitacija's control flow (Igra.py:75-114) once more, as bid_round walks it, with the answers behind
+// ask(seat, min_igra, obvezno, prednost); bid_round and bot_bidding keep their own copies so that every kernel that calls
+// them compiles as before.  Leaves the final bid and its holder (0 where seat 0 was forced).
+template <class Ask> __device__ __forceinline__ void bid_flow(Ask &ask, int &top_out, u32 &holder_out) {
+    u32 still = 0, holder = 0;
+    int top = 10;
+    for (u32 seat = 1; seat <= 3; seat++) {
+        int v = ask(seat, top, -100, false);
+        if (v != -10) still |= 1u << seat;
+        top = max(top, v);
+    }
+    if (top == 10) {                                 // nobody bid: seat 0 plays at least Klop
+        top = ask(0u, -10, 0, false);
+    } else {
+        int v = ask(0u, top, -100, true);            // seat 0 may match (priority)
+        if (v != -10) still |= 1u;
+        top = max(top, v);
+        holder = (u32)__builtin_ctz(still);
+        for (int rounds = 0; __popc(still) != 1 && rounds < 8; rounds++) {
+            u32 nxt = 0;
+            for (u32 k = 0; k < 4; k++) {
+                u32 seat = (k + 1) & 3;              // 1, 2, 3, 0: seat 0 is asked last
+                if ((still >> seat) & 1) {
+                    v = ask(seat, top, seat == holder ? top : -100, false);
+                    if (v != -10) { nxt |= 1u << seat; holder = seat; top = v; }
+                }
+            }
+            still = nxt;
+        }
+    }
+    top_out = top;
+    holder_out = top == 0 ? 0u : holder;
+}
+
+// The round of a pass playout: three Bots bid under `pkey` (draw 72 + n, every call counted) and seat `viewer` gives its
+// least answer on every call — Naprej, or obvezno where it has one (seat 0's forced Klop, the only way it ends as the
+// declarer).  The king of a Tri / Dve / Ena is draw 67 of pkey.
+struct PassAsk {
+    BidCtx b; u32 viewer;
+    __device__ __forceinline__ int operator()(u32 seat, int min_igra, int obvezno, bool prednost) {
+        if (seat != viewer) return bot_ask(b, min_igra, obvezno, prednost);
+        b.calls++;
+        return obvezno == -100 ? -10 : obvezno;
+    }
+};
+__device__ __forceinline__ void pass_round(u64 pkey, u32 viewer, u32 &contract, u32 &declarer, u32 &king) {
+    PassAsk ask = {{pkey, 0}, viewer};
+    int top;
+    bid_flow(ask, top, declarer);
+    contract = (u32)(top / 10);
+    king = has_king(contract) ? pick(rng32(pkey, 67), 4) : 0u;
+}
+
+// bid_game with the contract, declarer and king given: the game a pass playout plays on a world.
+__device__ __forceinline__ void bid_game_as(Game &h, u64 A, u64 B, u64 ids, u32 contract, u32 declarer, u32 king) {
+    const u64 in_hand = ~ids_mask(ids, 0, 6) & TK_DECK;
+    setup_game(h, in_hand & ~A & ~B, in_hand & A & ~B, in_hand & ~A & B, in_hand & A & B, ids, contract, declarer, king);
+    h.epar = 0; h.cprev = 0;
+}
+
+// bid_answer with the seat's own bar: thr = pass_bar(S[19], margin, playouts).  Nothing else of the rule changes.
+__device__ __forceinline__ int bid_answer(const int32_t *S, int min_igra, int obvezno, bool prednost, int margin, int playouts,
+                                          u32 contracts) {
+    return bid_answer(S, min_igra, obvezno, prednost, pass_bar(S[TK_BID_PASS_ROW], margin, playouts), contracts);
+}
+
+// bid_round with that answer on the seats of `set` (the trailing tag picks the overload): with row 19 all zero it is
+// bid_round at threshold = margin.  The king as there: the declarer's best row, draw 67 for a Bot.
+struct BidPassBar {};
+struct BidPassAsk {
+    BidCtx b; const int32_t *sums; int margin, playouts; u32 contracts, set;
+    __device__ __forceinline__ int operator()(u32 seat, int min_igra, int obvezno, bool prednost) {
+        if (!((set >> seat) & 1u)) return bot_ask(b, min_igra, obvezno, prednost);
+        b.calls++;
+        return bid_answer(sums + seat * TK_BID_ROWS, min_igra, obvezno, prednost, margin, playouts, contracts);
+    }
+};
+__device__ __forceinline__ void bid_round(u64 key, const int32_t *sums, int playouts, int margin, u32 contracts, u32 set, BidPassBar,
+                                          u32 &contract, u32 &declarer, u32 &king) {
+    BidPassAsk ask = {{key, 0}, sums, margin, playouts, contracts, set};
+    int top;
+    bid_flow(ask, top, declarer);
+    contract = (u32)(top / 10);
+    u32 kg = 0;
+    if (has_king(contract)) {
+        if ((set >> declarer) & 1u) {
+            const int32_t *S = sums + declarer * TK_BID_ROWS + 1u + 4u * (contract - 1u);
+            for (u32 k = 1; k < 4; k++) kg = S[k] > S[kg] ? k : kg;
+        } else {
+            kg = pick(rng32(key, 67), 4);
+        }
+    }
+    king = kg;
+}

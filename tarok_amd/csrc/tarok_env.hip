@@ -1818,6 +1818,67 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_bids(int64_t n, u64 pseed /* seed ^ salt
     for (u32 r = lane; r < TAROK_BID_ROWS; r += L) sum_out[g * TAROK_BID_ROWS + r] = reinterpret_cast<const int4 *>(row)[r];
 }
 
+// tarok_playout_bids_pass: k_playout_bids with one more kind of item per viewer, (19, w, k), the pass playout: three Bots
+// bid under the item's key with the viewer muted (pass_round), the game of their contract and declarer is set up on the
+// world, and the item goes on as a row's does.  Its sum is the viewer's row 19; rows 0..18 are k_playout_bids' to the byte.
+// A kernel of its own, k_playout_bids' text with the item changed: as one templated body the parent's kernel compiled to
+// four more instructions.  The barriers stand outside every test of the seat set as there.
+TK_KERNEL(TK_BLOCK, 128) void k_playout_bids_pass(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 episode, u32 worlds, u32 samples,
+                                                 u32 lg, u32 contracts, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                 const u64 *__restrict__ deal, int4 *__restrict__ sum_out) {
+    TK_VGPR_TOP(128, 127);
+    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> TK_PB_MIN_LG) * 4 * TAROK_BID_ROWS];
+    __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS], world_ids[TK_PO_WORLD_SLOTS];
+    const u32 tid = threadIdx.x, team = tid >> lg, L = 1u << lg, lane = tid & (L - 1u), teams = (u32)TK_BLOCK >> lg;
+    const int64_t g = (int64_t)blockIdx.x * teams + team;
+    for (u32 w = tid; w < teams * (4 * TAROK_BID_ROWS); w += TK_BLOCK) sums[w] = 0;
+    int *row = sums + team * (4 * TAROK_BID_ROWS);
+    const u32 slot0 = team * worlds;                 // the team's worlds: slots slot0 .. slot0 + worlds - 1
+    u64 h0 = 0, h1 = 0, h2 = 0, h3 = 0, tal = 0;
+    u32 set = 0;
+    if (g < n) {
+        h0 = deal[g]; h1 = deal[n + g]; h2 = deal[2 * n + g]; h3 = deal[3 * n + g]; tal = deal[4 * n + g];
+        set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+        if ((h0 | h1 | h2 | h3) == 0) set = 0;       // an invalid deal row
+    }
+    const u32 rowmask = bid_row_mask(contracts), nrows = (u32)__popc(rowmask);
+    const u32 per_row = worlds * samples, items = (nrows + 1u) * per_row;
+    const u64 ebase = (u64)episode << 28;
+#pragma unroll 1
+    for (u32 v = 0; v < 4; v++) {
+        const bool part = (set >> v) & 1u;
+        __syncthreads();                             // the rows are zero; the last viewer's items have read their worlds
+        if (part) {
+            for (u32 w = lane; w < worlds; w += L) {
+                u64 A, B, ids;
+                bid_world(h0, h1, h2, h3, tal, v, game_key(pseed, offset + (u64)g, (2ULL << 61) | ebase | ((u64)v << 6) | (u64)w), A, B, ids);
+                world_a[slot0 + w] = A; world_b[slot0 + w] = B; world_ids[slot0 + w] = ids;
+            }
+        }
+        __syncthreads();
+        if (part) {
+            for (u32 it = lane; it < items; it += L) {
+                u32 j = it / per_row, rem = it - j * per_row, w = rem / samples, k = rem - w * samples;
+                u32 r = j == nrows ? (u32)TK_BID_PASS_ROW : kth_bit((u64)rowmask, j);
+                u64 pkey = game_key(pseed, offset + (u64)g,
+                                    (3ULL << 61) | ebase | ((u64)v << 26) | ((u64)r << 21) | ((u64)w << 15) | (u64)k);
+                Game h;
+                // one setup for both kinds of item, so a pass item rejoins its wave's row items in front of the exchange
+                u32 ct = bid_row_contract(r), d = ct == TK_KLOP ? 0u : v, kg = bid_row_king(r);
+                if (r == TK_BID_PASS_ROW) pass_round(pkey, v, ct, d, kg);
+                bid_game_as(h, world_a[slot0 + w], world_b[slot0 + w], world_ids[slot0 + w], ct, d, kg);
+                if (h.phase == TK_PHASE_EXCHANGE) bot_exchange(h, pkey);
+                u32 c = policy_action(pkey, 0u, legal_now(h));
+                u64 scores = playout_from(h, c, pkey, 0u);
+                atomicAdd(row + v * TAROK_BID_ROWS + r, (int)(int16_t)(scores >> (16 * v)));
+            }
+        }
+    }
+    __syncthreads();
+    if (g >= n) return;
+    for (u32 r = lane; r < TAROK_BID_ROWS; r += L) sum_out[g * TAROK_BID_ROWS + r] = reinterpret_cast<const int4 *>(row)[r];
+}
+
 // tarok_bid_round: one bidding round per game on one lane (bid_round, tarok_device.h): the control flow of bot_bidding
 // with playout-valued answers on the seats of the set.  Every row of the three outputs is written.
 TK_KERNEL(TK_BLOCK, 64) void k_bid_round(int64_t n, u64 seed, u64 offset, u32 episode, const int32_t *__restrict__ sums, int playouts,
@@ -1829,6 +1890,21 @@ TK_KERNEL(TK_BLOCK, 64) void k_bid_round(int64_t n, u64 seed, u64 offset, u32 ep
     const u32 set = seat_sets ? (u32)seat_sets[i] & 15u : seats;
     u32 c, d, k;
     bid_round(game_key(seed, offset + (u64)i, episode), sums + i * (4 * TAROK_BID_ROWS), playouts, threshold, contracts, set, c, d, k);
+    if (contract_out) contract_out[i] = (int8_t)c;
+    if (declarer_out) declarer_out[i] = (int8_t)d;
+    if (king_out) king_out[i] = (int8_t)k;
+}
+
+// tarok_bid_round_pass: k_bid_round whose seats take their bar from row 19 of their own sums (bid_round's BidPassBar overload).
+TK_KERNEL(TK_BLOCK, 64) void k_bid_round_pass(int64_t n, u64 seed, u64 offset, u32 episode, const int32_t *__restrict__ sums, int playouts,
+                                             int margin, u32 contracts, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                             int8_t *__restrict__ contract_out, int8_t *__restrict__ declarer_out, int8_t *__restrict__ king_out) {
+    TK_VGPR_TOP(64, 63);
+    int64_t i = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const u32 set = seat_sets ? (u32)seat_sets[i] & 15u : seats;
+    u32 c, d, k;
+    bid_round(game_key(seed, offset + (u64)i, episode), sums + i * (4 * TAROK_BID_ROWS), playouts, margin, contracts, set, BidPassBar{}, c, d, k);
     if (contract_out) contract_out[i] = (int8_t)c;
     if (declarer_out) declarer_out[i] = (int8_t)d;
     if (king_out) king_out[i] = (int8_t)k;
@@ -2978,6 +3054,65 @@ __global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_bid_values(
     }
 }
 
+// tarok_bid_values_pass: k_bid_values whose row 19 is output 19, the value of a pass: scaled, clamped and rounded as rows
+// 0..18 are, with the same zeros for a seat outside the set and an invalid deal, and whatever `contracts` holds.  A kernel
+// of its own, k_bid_values' text with the row mask changed: as one templated body the parent's kernel did not keep its
+// instruction count.
+__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_bid_values_pass(
+    int64_t n, const u64 *__restrict__ deal, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3,
+    const float *__restrict__ b3, float scale, u32 contracts, u32 seats, const uint8_t *__restrict__ seat_sets,
+    int4 *__restrict__ value_out, float4 *__restrict__ raw_out, ulonglong2 *__restrict__ feature_words_out) {
+    TK_VGPR_TOP(256, 255);
+    static_assert(TK_BLOCK == 2 * PM_M && PM_M % 4 == 0 && TK_BID_ROWS == 20 && TK_BID_ROWS <= 64, "two lanes per row, five pieces per row");
+    __shared__ __attribute__((aligned(16))) __bf16 X[PM_M * PM_LD];
+    __shared__ u64 ext[PM_M][4];
+    const int64_t base = (int64_t)blockIdx.x * (PM_M / 4);
+    const u32 tid = threadIdx.x, wave = tid >> 6;
+    float *L = reinterpret_cast<float *>(X);
+    bf16x8 wq[4][2];
+    mlp_prefetch(wq, w1, wave * 2);                // lands while the features are built
+    if (tid < PM_M) {
+        const u32 v = tid & 3u;
+        const int64_t gq = base + (tid >> 2), g = gq < n ? gq : n - 1;
+        bid_feature_words(deal[(int64_t)v * n + g], v, ext[tid]);
+        if (feature_words_out && gq < n) {
+            feature_words_out[(g * 4 + v) * 2] = make_ulonglong2(ext[tid][0], ext[tid][1]);
+            feature_words_out[(g * 4 + v) * 2 + 1] = make_ulonglong2(ext[tid][2], ext[tid][3]);
+        }
+    }
+    __syncthreads();
+    policy_expand(X, ext, tid);
+    __syncthreads();
+    mlp_hidden(X, w1, b1, wq, wave);
+    mlp_prefetch(wq, w2, wave * 2);
+    mlp_hidden(X, w2, b2, wq, wave);
+    mlp_head(X, L, w3, b3, wave, 0);
+    __syncthreads();
+    const u32 row = tid >> 1, v = row & 3u;
+    const int64_t g = base + (row >> 2);
+    if (g >= n) return;
+    const u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+    const bool live = ((set >> v) & 1u) && deal[(int64_t)v * n + g] != 0;     // (a valid deal's hand holds twelve cards)
+    const u32 rowmask = live ? bid_row_mask(contracts) | 1u << TK_BID_PASS_ROW : 0u;      // (row 19 whatever `contracts` holds)
+#pragma unroll
+    for (u32 p = tid & 1u; p < TK_BID_ROWS / 4; p += 2) {
+        const float4 y = *reinterpret_cast<const float4 *>(L + row * PM_LL + 4 * p);
+        const float yy[4] = {y.x, y.y, y.z, y.w};
+        float rw[4];
+        int vl[4];
+#pragma unroll
+        for (u32 j = 0; j < 4; j++) {
+            const bool keep = (rowmask >> (4 * p + j)) & 1u;
+            rw[j] = keep ? yy[j] : 0.f;
+            vl[j] = keep ? (int)rintf(fminf(fmaxf(yy[j] * scale, -1073741824.f), 1073741824.f)) : 0;
+        }
+        const int64_t o = (g * 4 + v) * (TK_BID_ROWS / 4) + p;
+        if (value_out) value_out[o] = make_int4(vl[0], vl[1], vl[2], vl[3]);
+        if (raw_out) raw_out[o] = make_float4(rw[0], rw[1], rw[2], rw[3]);
+    }
+}
+
 // tarok_exchange_values: the exchange head — k_bid_values' forward on the declarer's pick-up.  A workgroup takes 16 games
 // = 128 rows, row = 8 * local game + i, "pick up talon group i": threads below 128 decode their game's 32-byte state and
 // build ext[row] = exchange_feature_words(game, i) under w1's prefetch — four zero words for a row that is not live (the
@@ -3832,8 +3967,11 @@ int tarok_playout_cards_hidden(tarok_env *e, int worlds, int samples, uint64_t s
                                       (const u64 *)played);
 }
 
-int tarok_playout_bids(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int samples, int contracts, uint64_t salt,
-                       int seats, const uint8_t *seats_per_game, int32_t *sum_out, void *stream) {
+extern "C++" {
+// tarok_playout_bids and its _pass twin: the deal, then the playout kernel given
+template <class Kernel>
+static int launch_playout_bids(Kernel kernel, tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int samples, int contracts,
+                               uint64_t salt, int seats, const uint8_t *seats_per_game, int32_t *sum_out, void *stream) {
     if (!playout_args_ok(e, worlds, samples, seats) || contracts < 1 || contracts > TAROK_BID_ALL_CONTRACTS) return TAROK_EINVAL;
     if (!sum_out) return TAROK_OK;
     HIPCHK(hipSetDevice(e->device));
@@ -3841,29 +3979,59 @@ int tarok_playout_bids(tarok_env *e, uint32_t episode, const uint8_t *deals, int
     hipLaunchKernelGGL(k_bid_deal, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, episode, deals, e->bid_deal);
     // 16 lanes per game or more, so a workgroup's at most 16 teams keep their 80 sums each in 5 KiB
     static_assert(TAROK_BID_ROWS == TK_BID_ROWS && TAROK_BID_ROWS % 4 == 0, "a viewer's rows are whole 16-byte pieces");
+    static_assert(TAROK_BID_PASS_ROW == TK_BID_PASS_ROW && TK_BID_PASS_ROW == TK_BID_OPTIONS && TK_BID_PASS_ROW < 32, "row 19, in the key's five bits");
     const u32 lg = playout_lg(TK_PB_MIN_LG, worlds * samples);
-    hipLaunchKernelGGL(k_playout_bids, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset, episode, (u32)worlds, (u32)samples, lg, (u32)contracts, (u32)seats, seats_per_game,
+    hipLaunchKernelGGL(kernel, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset, episode, (u32)worlds, (u32)samples, lg, (u32)contracts, (u32)seats, seats_per_game,
                        e->bid_deal, reinterpret_cast<int4 *>(sum_out));
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }
+}
 
-int tarok_bid_round(tarok_env *e, uint32_t episode, const int32_t *sums, int playouts, int threshold, int contracts, int seats,
-                    const uint8_t *seats_per_game, int8_t *contract_out, int8_t *declarer_out, int8_t *king_out, void *stream) {
+int tarok_playout_bids(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int samples, int contracts, uint64_t salt,
+                       int seats, const uint8_t *seats_per_game, int32_t *sum_out, void *stream) {
+    return launch_playout_bids(k_playout_bids, e, episode, deals, worlds, samples, contracts, salt, seats, seats_per_game, sum_out, stream);
+}
+
+int tarok_playout_bids_pass(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int samples, int contracts, uint64_t salt,
+                            int seats, const uint8_t *seats_per_game, int32_t *sum_out, void *stream) {
+    return launch_playout_bids(k_playout_bids_pass, e, episode, deals, worlds, samples, contracts, salt, seats, seats_per_game, sum_out, stream);
+}
+
+extern "C++" {
+template <class Kernel>
+static int launch_bid_round(Kernel kernel, tarok_env *e, uint32_t episode, const int32_t *sums, int playouts, int threshold, int contracts,
+                            int seats, const uint8_t *seats_per_game, int8_t *contract_out, int8_t *declarer_out, int8_t *king_out,
+                            void *stream) {
     if (!e || playouts < 1 || contracts < 1 || contracts > TAROK_BID_ALL_CONTRACTS || seats < 0 || seats > 15 ||
         (!sums && (seats != 0 || seats_per_game)) || (!contract_out && !declarer_out && !king_out))
         return TAROK_EINVAL;
     HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_bid_round, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, episode, sums, playouts,
+    hipLaunchKernelGGL(kernel, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, episode, sums, playouts,
                        threshold, (u32)contracts, (u32)(sums ? seats : 0), sums ? seats_per_game : nullptr, contract_out, declarer_out,
                        king_out);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }
+}
 
-int tarok_bid_values(tarok_env *e, uint32_t episode, const uint8_t *deals, const void *w1, const float *b1, const void *w2,
-                     const float *b2, const void *w3, const float *b3, float scale, int contracts, int seats,
-                     const uint8_t *seats_per_game, int32_t *value_out, float *raw_out, uint64_t *feature_words_out, void *stream) {
+int tarok_bid_round(tarok_env *e, uint32_t episode, const int32_t *sums, int playouts, int threshold, int contracts, int seats,
+                    const uint8_t *seats_per_game, int8_t *contract_out, int8_t *declarer_out, int8_t *king_out, void *stream) {
+    return launch_bid_round(k_bid_round, e, episode, sums, playouts, threshold, contracts, seats, seats_per_game, contract_out, declarer_out,
+                            king_out, stream);
+}
+
+int tarok_bid_round_pass(tarok_env *e, uint32_t episode, const int32_t *sums, int playouts, int margin, int contracts, int seats,
+                         const uint8_t *seats_per_game, int8_t *contract_out, int8_t *declarer_out, int8_t *king_out, void *stream) {
+    return launch_bid_round(k_bid_round_pass, e, episode, sums, playouts, margin, contracts, seats, seats_per_game, contract_out,
+                            declarer_out, king_out, stream);
+}
+
+extern "C++" {
+template <class Kernel>
+static int launch_bid_values(Kernel kernel, tarok_env *e, uint32_t episode, const uint8_t *deals, const void *w1, const float *b1,
+                             const void *w2, const float *b2, const void *w3, const float *b3, float scale, int contracts, int seats,
+                             const uint8_t *seats_per_game, int32_t *value_out, float *raw_out, uint64_t *feature_words_out, void *stream) {
     if (!e || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !(scale > 0.f) || scale > 1048576.f || contracts < 1 ||
         contracts > TAROK_BID_ALL_CONTRACTS || seats < 0 || seats > 15 || (!value_out && !raw_out && !feature_words_out))
         return TAROK_EINVAL;
@@ -3871,12 +4039,27 @@ int tarok_bid_values(tarok_env *e, uint32_t episode, const uint8_t *deals, const
     if (!e->bid_deal) HIPCHK(hipMalloc((void **)&e->bid_deal, (size_t)e->n * 5 * sizeof(u64)));   // tarok_playout_bids' buffer
     hipLaunchKernelGGL(k_bid_deal, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, episode, deals, e->bid_deal);
     const int64_t games = PM_M / 4;                  // per workgroup: one 128-row tile
-    hipLaunchKernelGGL(k_bid_values, dim3((unsigned)((e->n + games - 1) / games)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((e->n + games - 1) / games)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
                        e->bid_deal, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3, scale, (u32)contracts,
                        (u32)seats, seats_per_game, reinterpret_cast<int4 *>(value_out), reinterpret_cast<float4 *>(raw_out),
                        reinterpret_cast<ulonglong2 *>(feature_words_out));
     HIPCHK(hipGetLastError());
     return TAROK_OK;
+}
+}
+
+int tarok_bid_values(tarok_env *e, uint32_t episode, const uint8_t *deals, const void *w1, const float *b1, const void *w2,
+                     const float *b2, const void *w3, const float *b3, float scale, int contracts, int seats,
+                     const uint8_t *seats_per_game, int32_t *value_out, float *raw_out, uint64_t *feature_words_out, void *stream) {
+    return launch_bid_values(k_bid_values, e, episode, deals, w1, b1, w2, b2, w3, b3, scale, contracts, seats, seats_per_game, value_out,
+                             raw_out, feature_words_out, stream);
+}
+
+int tarok_bid_values_pass(tarok_env *e, uint32_t episode, const uint8_t *deals, const void *w1, const float *b1, const void *w2,
+                          const float *b2, const void *w3, const float *b3, float scale, int contracts, int seats,
+                          const uint8_t *seats_per_game, int32_t *value_out, float *raw_out, uint64_t *feature_words_out, void *stream) {
+    return launch_bid_values(k_bid_values_pass, e, episode, deals, w1, b1, w2, b2, w3, b3, scale, contracts, seats, seats_per_game,
+                             value_out, raw_out, feature_words_out, stream);
 }
 
 int tarok_exchange_values(tarok_env *e, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,

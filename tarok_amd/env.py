@@ -386,40 +386,48 @@ class TarokVecEnv:
         return sum_out, choice_out, discards_out
 
     def playout_bids(self, episode, worlds, samples, contracts=K.BID_DEFAULT_CONTRACTS, deals=None, salt=0, seats=15,
-                     seats_per_game=None, sum_out=None):
+                     seats_per_game=None, sum_out=None, pass_value=False):
         """Every bid of every seat valued by determinized playouts (tarok_playout_bids), BEFORE reset(): the game valued
         is the one reset(episode, deals) would deal.  For every viewer seat in `seats` / `seats_per_game` and each of
         `worlds` (1..64) re-deals of the 42 cards it does not hold, every option in `contracts` (bit code: Klop 0 ..
         Odprti_berac 9) — each of Tri / Dve / Ena with each of the four kings — is played to the end `samples` times by
         the Bot with the viewer as declarer.  Returns sum [N, 4, K.BID_ROWS] int32: the viewer's summed score per row
         (karte.bid_row), zeros for seats outside the set, options outside `contracts` and row 19.  bid_round() turns the
-        sums into a contract, a declarer and a king.  Does not read or write the env's games; `salt` varies the draws."""
+        sums into a contract, a declarer and a king.  Does not read or write the env's games; `salt` varies the draws.
+        pass_value=True (tarok_playout_bids_pass): row K.BID_PASS_ROW also holds the viewer's summed score of PASSING, over
+        the same worlds: three Bots bid with the viewer silent (seat 0 is left the forced Klop when all pass), and the game
+        they arrive at is played out by the Bot.  Rows 0..18 are the same bytes either way."""
         deals = self._dev(deals, torch.uint8, (self.n, 54))
+        launch = self.L.tarok_playout_bids_pass if pass_value else self.L.tarok_playout_bids
         with torch.cuda.device(self.device):
             if sum_out is None:
                 sum_out = torch.empty((self.n, 4, K.BID_ROWS), dtype=torch.int32, device=self.device)
-            _native.check(self.L.tarok_playout_bids(self._h, int(episode), self._p(deals), int(worlds), int(samples), int(contracts),
-                                                    int(salt) & ((1 << 64) - 1), int(seats),
-                                                    self._p(self._seat_sets(seats_per_game)), self._p(sum_out), self._stream()))
+            _native.check(launch(self._h, int(episode), self._p(deals), int(worlds), int(samples), int(contracts),
+                                 int(salt) & ((1 << 64) - 1), int(seats),
+                                 self._p(self._seat_sets(seats_per_game)), self._p(sum_out), self._stream()))
         return sum_out
 
-    def bid_round(self, episode, sums, playouts, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, seats=15, seats_per_game=None):
+    def bid_round(self, episode, sums, playouts, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, seats=15, seats_per_game=None,
+                  pass_value=False):
         """The bidding round of every game on the device (tarok_bid_round; Igra.licitacija's control flow): the seats of
         `seats` / `seats_per_game` answer from playout_bids()' sums — the best-valued contract that beats the standing
         bid, if its sum exceeds threshold * playouts (playouts = worlds * samples of the launch that made the sums) and,
         for the holder, the sum of standing — and the other seats as the Bot does.  Returns (contract, declarer,
         king_suit), three [N] int8 device tensors that reset(episode, deals, contract=, declarer=, king_suit=) takes
-        unchanged.  seats=0 is the Bot's own round (K.MIX_BOT's contract, declarer and king); sums may then be None."""
+        unchanged.  seats=0 is the Bot's own round (K.MIX_BOT's contract, declarer and king); sums may then be None.
+        pass_value=True (tarok_bid_round_pass): a seat's bar is the value of its own pass, sums[g, seat, K.BID_PASS_ROW] +
+        threshold * playouts: `threshold` is then the margin, in points per game, a bid has to beat the pass by."""
         sums = self._dev(sums, torch.int32, (self.n, 4, K.BID_ROWS))
+        launch = self.L.tarok_bid_round_pass if pass_value else self.L.tarok_bid_round
         with torch.cuda.device(self.device):
             out = [torch.empty(self.n, dtype=torch.int8, device=self.device) for _ in range(3)]
-            _native.check(self.L.tarok_bid_round(self._h, int(episode), self._p(sums), int(playouts), int(threshold), int(contracts),
-                                                 int(seats), self._p(self._seat_sets(seats_per_game)), self._p(out[0]),
-                                                 self._p(out[1]), self._p(out[2]), self._stream()))
+            _native.check(launch(self._h, int(episode), self._p(sums), int(playouts), int(threshold), int(contracts),
+                                 int(seats), self._p(self._seat_sets(seats_per_game)), self._p(out[0]),
+                                 self._p(out[1]), self._p(out[2]), self._stream()))
         return tuple(out)
 
     def bid_values(self, episode, weights, scale, contracts=K.BID_DEFAULT_CONTRACTS, deals=None, seats=15, seats_per_game=None,
-                   value_out=None, raw=False, feature_words=False):
+                   value_out=None, raw=False, feature_words=False, pass_value=False):
         """The bidding head (tarok_bid_values): playout_bids()' array written by a network from the twelve cards of each
         hand, BEFORE reset(), for the game reset(episode, deals) would deal.  weights = (w1, b1, w2, b2, w3, b3) as
         policy_mlp takes them; the input row of seat v is the hand, the one-hot seat and the tarok / suit-length / king /
@@ -429,18 +437,21 @@ class TarokVecEnv:
         an invalid deal): bid_round(episode, value, playouts, ...) takes it as its sums.  raw=True also returns the
         unscaled float32 outputs [N, 4, K.BID_ROWS] (same zeros), feature_words=True the input rows as bits
         [N, 4, 4] int64 (expand_feature_words; every seat, in the set or not): (value, raw, feature_words), None for what
-        was not asked for.  Does not read or write the env's games."""
+        was not asked for.  Does not read or write the env's games.
+        pass_value=True (tarok_bid_values_pass): row K.BID_PASS_ROW of value and raw is output 19, the value of a pass,
+        scaled, clamped and rounded as the other rows and whatever `contracts` holds; rows 0..18 are the same bytes."""
         w1, b1, w2, b2, w3, b3 = self.check_mlp_weights(weights)
         deals = self._dev(deals, torch.uint8, (self.n, 54))
+        launch = self.L.tarok_bid_values_pass if pass_value else self.L.tarok_bid_values
         with torch.cuda.device(self.device):
             if value_out is None:
                 value_out = torch.empty((self.n, 4, K.BID_ROWS), dtype=torch.int32, device=self.device)
             raw_out = torch.empty((self.n, 4, K.BID_ROWS), dtype=torch.float32, device=self.device) if raw else None
             fw_out = torch.empty((self.n, 4, 4), dtype=torch.int64, device=self.device) if feature_words else None
-            _native.check(self.L.tarok_bid_values(self._h, int(episode), self._p(deals), self._p(w1), self._p(b1), self._p(w2),
-                                                  self._p(b2), self._p(w3), self._p(b3), float(scale), int(contracts), int(seats),
-                                                  self._p(self._seat_sets(seats_per_game)), self._p(value_out), self._p(raw_out),
-                                                  self._p(fw_out), self._stream()))
+            _native.check(launch(self._h, int(episode), self._p(deals), self._p(w1), self._p(b1), self._p(w2),
+                                 self._p(b2), self._p(w3), self._p(b3), float(scale), int(contracts), int(seats),
+                                 self._p(self._seat_sets(seats_per_game)), self._p(value_out), self._p(raw_out),
+                                 self._p(fw_out), self._stream()))
         if not raw and not feature_words:
             return value_out
         return value_out, raw_out, fw_out

@@ -120,13 +120,15 @@ def evaluate_vs_policy(weights, opponent, n_games, episodes, seed=0, mix=K.MIX_B
                                                  temperature=temperature, epsilon=epsilon))
 
 
-def _bid_front(env, episode, bidding, salt, seats, threshold, contracts, sums):
+def _bid_front(env, episode, bidding, salt, seats, threshold, contracts, sums, pass_value=False):
     """The front end of a pass whose playout player also bids: ONE tarok_playout_bids at bidding = (worlds, samples) with
     the pass's seat set, ONE tarok_bid_round — the Bot's own answers outside the set, so the empty set gives
-    K.MIX_BOT's contract, declarer and king — and the keyword arguments reset() takes them as."""
+    K.MIX_BOT's contract, declarer and king — and the keyword arguments reset() takes them as.  pass_value: both launches'
+    _pass twins (the pass valued by playouts; `threshold` the margin over it)."""
     worlds, samples = bidding
-    env.playout_bids(episode, worlds, samples, contracts=contracts, salt=salt, seats=seats, sum_out=sums)
-    c, d, k = env.bid_round(episode, sums, int(worlds) * int(samples), threshold=threshold, contracts=contracts, seats=seats)
+    env.playout_bids(episode, worlds, samples, contracts=contracts, salt=salt, seats=seats, sum_out=sums, pass_value=pass_value)
+    c, d, k = env.bid_round(episode, sums, int(worlds) * int(samples), threshold=threshold, contracts=contracts, seats=seats,
+                            pass_value=pass_value)
     return dict(contract=c, declarer=d, king_suit=k)
 
 
@@ -160,7 +162,7 @@ def _exchange_bufs(env, n, exchange, want_start):
 
 
 def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None, voids=False, exchange=None,
-                    hidden=False, bidding=None, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS):
+                    hidden=False, bidding=None, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False):
     """_play_passes_mode with the Monte-Carlo player (TarokVecEnv.playout_cards) in the network's place: per lock-step
     one playout launch with the pass's seat set — tarok_playout_cards (open hands) for worlds=None,
     tarok_playout_cards_det (the fair player: `worlds` re-deals of the unseen cards) otherwise — whose action_out holds
@@ -198,7 +200,7 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
         bsums = _bid_bufs(env, n) if bidding is not None else None
         for e in range(int(episodes)):
             for p, seats in enumerate(PASS_SEATS):
-                setup = _bid_front(env, e, bidding, salt, seats, threshold, contracts, bsums) if bidding is not None else {}
+                setup = _bid_front(env, e, bidding, salt, seats, threshold, contracts, bsums, pass_value) if bidding is not None else {}
                 if xb is not None:
                     start = _exchange_front(env, e, worlds, samples, exchange, salt, seats, xb, setup)
                 else:
@@ -228,7 +230,7 @@ def _bid_bufs(env, n):
 
 def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None,
                             voids=False, exchange=None, hidden=False, bidding=None, threshold=0,
-                            contracts=K.BID_DEFAULT_CONTRACTS):
+                            contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False):
     """evaluate_vs_bot with the open-hand Monte-Carlo player in the network's place: a strong reference player that needs
     no training.  On its seat it plays, at every move, the legal card with the best summed score over `samples` Bot
     playouts of each legal card (tarok_playout_cards; `salt` varies their draws).  The playouts see the TRUE hidden
@@ -249,12 +251,13 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
     bidding=(Wb, Sb) (with worlds=W and mix=K.MIX_BOT): the fair player also BIDS for its seat — tarok_playout_bids at
     (Wb, Sb) over `contracts` and tarok_bid_round with `threshold` decide contract, declarer and called king before the
     reset; the other seats bid as the Bot does, so pass 0 is unchanged.  It composes with exchange=D.  None (the default):
-    the Bot's bidding round on every seat, as before.
+    the Bot's bidding round on every seat, as before.  pass_value=True (with bidding): the pass is valued by playouts too
+    and is the bar a bid has to clear (tarok_playout_bids_pass, tarok_bid_round_pass; `threshold` the margin over it).
     The same five duplicate passes (PASS_SEATS) on an env of its own; returns duplicate_advantage's dict, `policy_mean`
     being the playout player's.  inspect (tests): a list that receives one dict per pass, as in _play_passes_mode."""
     return duplicate_advantage(_playout_passes(samples, n_games, episodes, seed, mix, device, salt=salt, inspect=inspect,
                                                worlds=worlds, voids=voids, exchange=exchange, hidden=hidden, bidding=bidding,
-                                               threshold=threshold, contracts=contracts))
+                                               threshold=threshold, contracts=contracts, pass_value=pass_value))
 
 
 def _exchange_passes(worlds, samples, discard_sets, n_games, episodes, seed, mix, device, salt=0, inspect=None):
@@ -342,7 +345,7 @@ def evaluate_exchangenet_vs_bot(weights, n_games, episodes, seed=0, mix=K.MIX_BO
 
 
 def _bidding_passes(worlds, samples, n_games, episodes, seed, device, salt=0, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS,
-                    inspect=None):
+                    inspect=None, pass_value=False):
     """The five passes with the playout player making the BID of its seat only: _bid_front, a reset that takes its
     contract, declarer and king (the Bot's exchange), then the Bot's card on every seat at every move, as in
     _exchange_passes.  inspect: one dict per pass — episode, seats, contract, declarer, king_suit, start, actions, scores."""
@@ -356,7 +359,7 @@ def _bidding_passes(worlds, samples, n_games, episodes, seed, device, salt=0, th
         bsums = _bid_bufs(env, n)
         for e in range(int(episodes)):
             for p, seats in enumerate(PASS_SEATS):
-                setup = _bid_front(env, e, (worlds, samples), salt, seats, threshold, contracts, bsums)
+                setup = _bid_front(env, e, (worlds, samples), salt, seats, threshold, contracts, bsums, pass_value)
                 env.reset(episode=e, clear_counters=True, **setup)
                 start = env.state() if inspect is not None else None
                 for t in range(GAME_CARDS):
@@ -373,18 +376,20 @@ def _bidding_passes(worlds, samples, n_games, episodes, seed, device, salt=0, th
 
 
 def evaluate_bidding_vs_bot(worlds, samples, n_games, episodes, seed=0, device=0, salt=0, threshold=0,
-                            contracts=K.BID_DEFAULT_CONTRACTS, inspect=None):
+                            contracts=K.BID_DEFAULT_CONTRACTS, inspect=None, pass_value=False):
     """What is the bid alone worth?  The five duplicate passes on K.MIX_BOT's deals with the Bot making EVERY exchange and
     playing EVERY card; in pass 1 + k seat k bids by playouts — tarok_playout_bids at (worlds, samples) over `contracts`,
     then tarok_bid_round with `threshold` — against three Bot bidders, and calls its king by the same sums.  Pass 0 is the
     Bot's own bidding round on every seat: the scores of evaluate_vs_bot's pass 0 on the same deals.  Returns
-    duplicate_advantage's dict, `policy_mean` being that of the seat that bid by playouts."""
+    duplicate_advantage's dict, `policy_mean` being that of the seat that bid by playouts.  pass_value=True: the seat's
+    pass is valued by playouts as well (tarok_playout_bids_pass) and is the bar its bids have to clear
+    (tarok_bid_round_pass, `threshold` the margin over it); pass 0 is unchanged."""
     return duplicate_advantage(_bidding_passes(worlds, samples, n_games, episodes, seed, device, salt=salt, threshold=threshold,
-                                               contracts=contracts, inspect=inspect))
+                                               contracts=contracts, inspect=inspect, pass_value=pass_value))
 
 
 def _bidnet_passes(bid_weights, n_games, episodes, seed, device, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, playouts_equiv=16,
-                   reward_scale=1.0 / 70.0, inspect=None):
+                   reward_scale=1.0 / 70.0, inspect=None, pass_value=False):
     """_bidding_passes with the bidding head in the playout teacher's place: per pass ONE tarok_bid_values at scale =
     playouts_equiv / reward_scale with the pass's seat set and ONE tarok_bid_round at playouts = playouts_equiv, a reset
     that takes their contract, declarer and king (the Bot's exchange), then the Bot's card on every seat at every move.
@@ -402,8 +407,9 @@ def _bidnet_passes(bid_weights, n_games, episodes, seed, device, threshold=0, co
         values = _bid_bufs(env, n)
         for e in range(int(episodes)):
             for p, seats in enumerate(PASS_SEATS):
-                env.bid_values(e, weights, scale, contracts=contracts, seats=seats, value_out=values)
-                c, d, k = env.bid_round(e, values, int(playouts_equiv), threshold=threshold, contracts=contracts, seats=seats)
+                env.bid_values(e, weights, scale, contracts=contracts, seats=seats, value_out=values, pass_value=pass_value)
+                c, d, k = env.bid_round(e, values, int(playouts_equiv), threshold=threshold, contracts=contracts, seats=seats,
+                                        pass_value=pass_value)
                 setup = dict(contract=c, declarer=d, king_suit=k)
                 env.reset(episode=e, clear_counters=True, **setup)
                 start = env.state() if inspect is not None else None
@@ -421,13 +427,15 @@ def _bidnet_passes(bid_weights, n_games, episodes, seed, device, threshold=0, co
 
 
 def evaluate_bidnet_vs_bot(bid_weights, n_games, episodes, seed=0, device=0, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS,
-                           playouts_equiv=16, reward_scale=1.0 / 70.0, inspect=None):
+                           playouts_equiv=16, reward_scale=1.0 / 70.0, inspect=None, pass_value=False):
     """What is the bidding head's bid worth?  evaluate_bidding_vs_bot with tarok_bid_values in tarok_playout_bids' place:
     the five duplicate passes on K.MIX_BOT's deals with the Bot making EVERY exchange and playing EVERY card; in pass
     1 + k seat k bids from the network's values — bid_weights = (w1, b1, w2, b2, w3, b3) as tarok_bid_values takes them
     (bidding.BidLearner.weights()), scaled to sums over `playouts_equiv` playouts of `reward_scale` points, so that
     `threshold` is in points per game as for the teacher — against three Bot bidders.  Pass 0 is the Bot's own round on
     every seat: evaluate_bidding_vs_bot's pass 0 on the same deals.  Returns duplicate_advantage's dict, `policy_mean`
-    being that of the seat the head bid for."""
+    being that of the seat the head bid for.  pass_value=True: output 19 is the seat's value of a pass and the bar its bids
+    have to clear (tarok_bid_values_pass, tarok_bid_round_pass; a head trained by BidLearner(pass_value=True))."""
     return duplicate_advantage(_bidnet_passes(bid_weights, n_games, episodes, seed, device, threshold=threshold, contracts=contracts,
-                                              playouts_equiv=playouts_equiv, reward_scale=reward_scale, inspect=inspect))
+                                              playouts_equiv=playouts_equiv, reward_scale=reward_scale, inspect=inspect,
+                                              pass_value=pass_value))

@@ -73,6 +73,7 @@ EXCHANGE_MAX_SETS = 8     # tarok_playout_exchange: discard sets per talon group
 BID_ROWS = 20             # tarok_playout_bids: rows of sum_out per viewer seat (19 options and one of padding)
 BID_DEFAULT_CONTRACTS = 0x00F   # Klop, Tri, Dve, Ena: the Bot's own range
 BID_ALL_CONTRACTS = 0x3FF
+BID_PASS_ROW = 19         # tarok_playout_bids_pass / tarok_bid_values_pass: the row that holds the value of a pass
 
 
 def bid_row(code, king=0):

@@ -71,6 +71,7 @@ def licitacija(licitiram, max_rounds=64):
 
 
 BID_OPTIONS = 19                                 # rows of a viewer in tarok_playout_bids' sums (row 19 is padding)
+BID_PASS_ROW = 19                                # ... or, from tarok_playout_bids_pass, the summed score of passing
 
 
 def row_bid(row):
@@ -78,13 +79,15 @@ def row_bid(row):
     return 0 if row == 0 else (10 * (1 + (row - 1) // 4) if row <= 12 else 10 * (row - 9))
 
 
-def playout_answer(S_row, min_igra, obvezno, prednost, playouts, threshold=0, contracts=0x00F):
+def playout_answer(S_row, min_igra, obvezno, prednost, playouts, threshold=0, contracts=0x00F, pass_value=False):
     """The answer of a playout bidder to licitiram(min_igra, obvezno, prednost), as tarok_bid_round gives it, from the
     seat's row of tarok_playout_bids' sums (S_row[r], r < 19; any integer sequence).
     Candidates: the rows of the contracts in `contracts` (bit int(Tip_igre) / 10) from Tri up that beat min_igra (at least
     match it with prednost); best = the largest sum, the lowest row on ties.  Without obvezno: the best row's bid if its
     sum exceeds threshold * playouts, else Naprej.  With obvezno = o: the best row's bid if its sum also exceeds the
     largest sum among the rows of o itself, else o.
+    pass_value=True (tarok_bid_round_pass): the bar is S_row[19] + threshold * playouts, the seat's own value of a pass
+    plus a margin of `threshold` points per game; nothing else changes.
     As the callback of licitacija():  lambda seat, m, o, p: playout_answer(S[seat], m, o, p, playouts)."""
     best = None
     for r in range(1, BID_OPTIONS):
@@ -95,7 +98,8 @@ def playout_answer(S_row, min_igra, obvezno, prednost, playouts, threshold=0, co
             continue
         if best is None or int(S_row[r]) > int(S_row[best]):
             best = r
-    bid = best is not None and int(S_row[best]) > int(threshold) * int(playouts)
+    bar = (int(S_row[BID_PASS_ROW]) if pass_value else 0) + int(threshold) * int(playouts)
+    bid = best is not None and int(S_row[best]) > bar
     if obvezno is None:
         return row_bid(best) if bid else NAPREJ
     stand = max(int(S_row[r]) for r in range(BID_OPTIONS) if row_bid(r) == obvezno)

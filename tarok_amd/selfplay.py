@@ -421,7 +421,7 @@ class SelfPlay:
     @torch.no_grad()
     def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None, greedy=False, temperature=None, epsilon=0.0,
                  versus_playout=None, playout_worlds=None, playout_voids=False, playout_exchange=None,
-                 playout_hidden=False, playout_bidding=None):
+                 playout_hidden=False, playout_bidding=None, pass_value=False):
         """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
         weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
         and on the SAME deals on every rank (seed 0, game offset 0, whatever the training env's are): the figures of
@@ -444,7 +444,9 @@ class SelfPlay:
         playout_exchange=D (with playout_worlds): the fair player also makes its seat's talon exchange, valued by
         playouts over D discard sets per group (evaluate_playout_vs_bot(exchange=D)).
         playout_bidding=(W, S) (with playout_worlds and mix=K.MIX_BOT): the fair player also bids for its seat, every
-        contract valued by playouts (evaluate_playout_vs_bot(bidding=(W, S)))."""
+        contract valued by playouts (evaluate_playout_vs_bot(bidding=(W, S))).
+        pass_value=True (with playout_bidding): its pass is valued by playouts too and is the bar its bids have to clear
+        (evaluate_playout_vs_bot(pass_value=True))."""
         if playout_bidding is not None and playout_worlds is None:
             raise ValueError("playout_bidding goes with playout_worlds=W")
         if playout_exchange is not None and playout_worlds is None:
@@ -477,7 +479,8 @@ class SelfPlay:
         from .evaluate import evaluate_playout_vs_bot
         return own, evaluate_playout_vs_bot(int(versus_playout), n_games, episodes, mix=mix, device=self.env.device_index,
                                             worlds=playout_worlds, voids=bool(playout_voids), exchange=playout_exchange,
-                                            hidden=bool(playout_hidden), bidding=playout_bidding)
+                                            hidden=bool(playout_hidden), bidding=playout_bidding,
+                                            pass_value=pass_value)
 
     def _alloc(self, T):
         n, dev = self.env.n, self.device
