@@ -797,6 +797,34 @@ int tarok_policy_step_versus(tarok_env *env, int seats, const uint8_t *seats_per
                              uint64_t *feature_words_out, int16_t *reward_out, uint8_t *done_out, uint16_t *trick_out,
                              uint64_t *obs_out, int flags, void *stream);
 
+/* Policy-network playouts: tarok_playout_cards_det whose playouts are played by a policy network — the determinized
+ * player with the learned policy inside, a teacher that improves with its student, and (by the choice of net_seats) a
+ * best response to a known table.  "Takes part", the worlds and the world key wkey, sum_out [N,12,4] i32, action_out
+ * [N] u8, seats / seats_per_game and the read-only contract are exactly tarok_playout_cards_det's.  There is no
+ * `samples`: ONE playout per (legal card of rank j, world w < worlds), under the det launch's item key with sample 0,
+ *     pkey = game_key(seed ^ salt, gidx, D),   D = 3 << 62 | (u64)ep << 28 | played << 22 | c << 16 | w << 10.
+ * Inside a playout, after the candidate card c, the seat to move (absolute seat number) plays
+ *   - if its bit is set in net_seats (0..15): the network's GREEDY card — the lowest-numbered legal card at the maximum
+ *     of the 54 card logits that tarok_policy_mlp's forward gives (bit for bit) on the feature words of the playout's
+ *     own position; the rule of the greedy play mode (tarok_set_play_mode, temperature 0).  The env's own play mode is
+ *     not read;
+ *   - otherwise the Bot's card, policy_action(pkey, q, legal) at q cards played (spec RNG draw 128 + q), as in
+ *     tarok_playout_cards_det.
+ * Hence net_seats = 0 writes the bytes of tarok_playout_cards_det(worlds, samples = 1).
+ *   w1 .. b3   the network, in tarok_policy_mlp's layouts; read through the pointers when the launch RUNS, so a captured
+ *              graph replays with the weights that are in place then
+ *   scratch    device memory, 16-byte aligned, at least tarok_playout_net_scratch(env, worlds) bytes (48 bytes per
+ *              (game, rank, world)); nothing is allocated inside the call, and the call may be captured into a graph.
+ *              Its contents are undefined afterwards.
+ * tarok_playout_net_scratch returns TAROK_EINVAL for a NULL env or worlds outside 1..TAROK_PLAYOUT_MAX_WORLDS.
+ * TAROK_EINVAL (before any HIP call) for a NULL env, worlds outside 1..TAROK_PLAYOUT_MAX_WORLDS, seats or net_seats
+ * outside 0..15, a missing weight or bias, a NULL, misaligned or short scratch, or both outputs NULL. */
+int64_t tarok_playout_net_scratch(const tarok_env *env, int worlds);
+int tarok_playout_cards_net(tarok_env *env, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                            int net_seats, const void *w1, const float *b1, const void *w2, const float *b2,
+                            const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
+                            int32_t *sum_out, uint8_t *action_out, void *stream);
+
 /* The learner's network input for a minibatch: features_out[j] [256] bf16 (0.0 / 1.0) = the bits
  * of feature_words[index[j]] (feature_words [M,4] u64 as written by feature_words_out; index
  * [n_samples] i64 sample numbers, or NULL for samples 0..n_samples-1).  Gather + expansion in one

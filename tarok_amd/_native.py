@@ -34,6 +34,7 @@ SYMBOLS = [
     "tarok_playout_exchange", "tarok_played_cards", "tarok_playout_cards_hidden", "tarok_playout_bids", "tarok_bid_round",
     "tarok_bid_values", "tarok_exchange_values", "tarok_exchange_candidates",
     "tarok_playout_bids_pass", "tarok_bid_round_pass", "tarok_bid_values_pass",
+    "tarok_playout_net_scratch", "tarok_playout_cards_net",
 ]
 
 
@@ -170,6 +171,9 @@ def lib():
     L.tarok_get_play_mode.restype = i32; L.tarok_get_play_mode.argtypes = [vp, C.POINTER(f32), C.POINTER(f32)]
     L.tarok_playout_cards.restype = i32; L.tarok_playout_cards.argtypes = [vp, i32, u64, i32, vp, vp, vp, vp]
     L.tarok_playout_cards_det.restype = i32; L.tarok_playout_cards_det.argtypes = [vp, i32, i32, u64, i32, vp, vp, vp, vp]
+    L.tarok_playout_net_scratch.restype = i64; L.tarok_playout_net_scratch.argtypes = [vp, i32]
+    L.tarok_playout_cards_net.restype = i32
+    L.tarok_playout_cards_net.argtypes = [vp, i32, u64, i32, vp, i32] + [vp] * 6 + [vp, i64, vp, vp, vp]
     L.tarok_playout_exchange.restype = i32; L.tarok_playout_exchange.argtypes = [vp, i32, i32, i32, u64, i32, vp, vp, vp, vp, vp]
     L.tarok_shown_voids.restype = i32; L.tarok_shown_voids.argtypes = [vp, vp, vp]
     L.tarok_playout_cards_voids.restype = i32; L.tarok_playout_cards_voids.argtypes = [vp, i32, i32, u64, i32, vp, vp, vp, vp, vp]

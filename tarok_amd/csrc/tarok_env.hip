@@ -3310,6 +3310,208 @@ __global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_
 }
 
 // ---------------------------------------------------------------------------
+// tarok_playout_cards_net: tarok_playout_cards_det at one playout per (legal card, world), whose playouts are played by a
+// policy network on the seats of `net_seats` and by the Bot on the others.  Three launches on one stream
+// over the caller's scratch, one ITEM per (game, rank j, world w), item = (g * 12 + j) * worlds + w, four arrays:
+//   i01, i23 [items] the item's 32 state bytes (a live item's only), ikey [items] its playout key (a live item's only),
+//   ires [items] TK_PN_LIVE while the item is to be played, else its four final scores, packed (0: no such item).
+// No score is -32768, so TK_PN_LIVE is no result.
+#define TK_PN_LIVE 0x8000800080008000ULL
+#define TK_PN_ITEM_BYTES 48
+#define TK_PN_MAX_CARDS 48
+
+// First launch: k_playout_det's worlds (the same team layout, dealer and keys), the candidate card applied, the items
+// written.  An item whose candidate ends the game is written finished; the slots of absent ranks and of games that do
+// not take part get 0.
+TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,
+                                                const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                                const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                                ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,
+                                                u64 *__restrict__ ires) {
+    TK_VGPR_TOP(128, 127);
+    __shared__ WorldAB world;
+    const PlayoutTeam t(lg, worlds);
+    const int64_t g = t.g;
+    ulonglong2 a = {0, 0}, b = {0, 0};
+    CardPosition p;
+    u64 ebase = 0;
+    u32 nlegal = 0;
+    if (g < n) {
+        a = s01[g]; b = s23[g];
+        Game g0;
+        unpack(g0, a.x, a.y, b.x, b.y);
+        p = card_position(g0, seat_sets, seats, g);
+        if (p.takes_part) {
+            nlegal = (u32)popc64(p.legal);
+            ebase = ((u64)cnt[g].episode << 28) | ((u64)p.played << 22);
+            for (u32 w = t.lane; w < worlds; w += t.L) {
+                Game d = g0;
+                DealUnseen::deal(d, p.mover, game_key(pseed, offset + (u64)g, DealUnseen::world_tag | ebase | (u64)w), NoWord{});
+                world.store(t.slot0 + w, d);
+            }
+        }
+    }
+    __syncthreads();
+    if (g < n) {
+        const u32 slots = TAROK_PLAYOUT_RANKS * worlds;
+        for (u32 i = t.lane; i < slots; i += t.L) {
+            const int64_t it = g * (int64_t)slots + i;
+            const u32 j = i / worlds, w = i - j * worlds;
+            u64 res = 0;
+            if (j < nlegal) {                            // (nlegal = 0 for a game that does not take part)
+                const u32 c = kth_bit(p.legal, j);
+                Game h;
+                unpack(h, a.x, a.y, b.x, b.y);
+                world.load(t.slot0 + w, h);
+                u64 scores = 0;
+                u32 ti;
+                const int fin = apply_step<true>(h, c, scores, ti, false);
+                res = fin ? scores : TK_PN_LIVE;
+                if (!fin) {
+                    u64 x0, x1, y0, y1;
+                    pack(h, x0, x1, y0, y1);
+                    i01[it] = make_ulonglong2(x0, x1);
+                    i23[it] = make_ulonglong2(y0, y1);
+                    ikey[it] = game_key(pseed, offset + (u64)g, DealUnseen::item_tag | ebase | ((u64)c << 16) | ((u64)w << 10));
+                }
+            }
+            ires[it] = res;
+        }
+    }
+}
+
+// Second launch: the playouts.  A workgroup of 256 threads keeps one tile of PM_M = 128 items resident — their packed
+// states and keys in LDS, owned by threads 0..127 — and plays them card by card: feature words (policy_feature_words on
+// the item's own Game) -> policy_expand, mlp_hidden x 2, mlp_head, unchanged, so a row's logits are tarok_policy_mlp's
+// bits -> the greedy card of policy_sample<1> (two lanes per row) into act_s, or the Bot's card policy_action(key, q,
+// legal) for a seat outside net_seats -> apply_step<true>.  The forward is skipped in a card round in which no live
+// row's mover is a net seat.  LDS: X 67,584 + ext 4,096 + states 4,096 + keys 1,024 + cards and votes < 77 KB, two
+// workgroups per CU as k_policy_mlp, so one's integer work runs under the other's MFMAs.
+//
+// LOOP INVARIANTS (the card loop has workgroup barriers inside it):
+//   - the continuation test and the forward test read vote[parity][0..1], written by waves 0 and 1 before the round's
+//     first barrier and read by every thread after it: both are workgroup-uniform.  Two parities, because a round
+//     without a forward has no other barrier between this read and the next round's write;
+//   - the loop runs at most TK_PN_MAX_CARDS = 48 rounds (a game has 48 cards), whatever the items hold;
+//   - a live row with an empty legal mask is retired with result 0, not waited for;
+//   - a workgroup whose items are all dead leaves at the first round's test: it runs no forward;
+//   - a row still live after the last round (none can be) gets result 0: TK_PN_LIVE never reaches the third launch.
+__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net_play(
+    int64_t items, u32 net_seats, const ulonglong2 *__restrict__ i01, const ulonglong2 *__restrict__ i23,
+    const u64 *__restrict__ ikey, u64 *__restrict__ ires, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3, const float *__restrict__ b3) {
+    TK_VGPR_TOP(256, 255);
+    __shared__ __attribute__((aligned(16))) __bf16 X[PM_M * PM_LD];
+    __shared__ __attribute__((aligned(16))) u64 ext[PM_M][4];
+    __shared__ __attribute__((aligned(16))) u64 st[PM_M][4];
+    __shared__ u64 keys[PM_M];
+    __shared__ uint8_t act_s[PM_M];
+    __shared__ u32 vote[2][2];
+    const u32 tid = threadIdx.x, wave = tid >> 6;
+    const int64_t it = (int64_t)blockIdx.x * PM_M + tid;
+    float *L = reinterpret_cast<float *>(X);
+    bool live = false;
+    if (tid < PM_M && it < items && ires[it] == TK_PN_LIVE) {
+        live = true;
+        const ulonglong2 a = i01[it], b = i23[it];
+        st[tid][0] = a.x; st[tid][1] = a.y; st[tid][2] = b.x; st[tid][3] = b.y;
+        keys[tid] = ikey[it];
+    }
+#pragma unroll 1
+    for (u32 round = 0; round < TK_PN_MAX_CARDS; round++) {
+        if (tid < PM_M) {                                  // (waves 0 and 1, whole)
+            bool net = false;
+            if (live) {
+                Game h;
+                unpack(h, st[tid][0], st[tid][1], st[tid][2], st[tid][3]);
+                policy_feature_words(h, ext[tid]);
+                net = (net_seats >> ((h.leader + h.nt) & 3)) & 1u;
+            } else {
+                ext[tid][0] = 0; ext[tid][1] = 0; ext[tid][2] = 0; ext[tid][3] = 0;
+            }
+            const u64 any_live = __ballot(live), any_net = __ballot(live && net);
+            if (__lane_id() == 0) vote[round & 1][wave] = (any_live ? 1u : 0u) | (any_net ? 2u : 0u);
+        }
+        __syncthreads();
+        const u32 v = vote[round & 1][0] | vote[round & 1][1];
+        if (!(v & 1u)) break;
+        if (v & 2u) {
+            bf16x8 wq[4][2];
+            mlp_prefetch(wq, w1, wave * 2);
+            policy_expand(X, ext, tid);
+            __syncthreads();
+            mlp_hidden(X, w1, b1, wq, wave);
+            mlp_prefetch(wq, w2, wave * 2);
+            mlp_hidden(X, w2, b2, wq, wave);
+            mlp_head(X, L, w3, b3, wave, 0);
+            __syncthreads();
+            // the greedy card of row gi, two lanes per row: policy_sample<1> under a greedy mode (its draw, its exps and
+            // the Bot's card are not read: they fold away)
+            const u32 gi = tid >> 1, half = tid & 1;
+            PolicySampleIn in;
+            in.m = ext[gi][1] & TAROK_OBS_MASK;
+            in.o = in.m; in.key = 0; in.played = 0; in.last = 0;
+            in.mh = (u32)(in.m >> (27 * half)) & 0x7FFFFFFu;
+            const PolicyPick c = policy_sample<1>(L, gi, half, in, PlayMode{1.f, 1, 0u, 0.f});
+            if (half == 0) act_s[gi] = (uint8_t)c.pk;
+            __syncthreads();
+        }
+        if (live) {
+            Game h;
+            unpack(h, st[tid][0], st[tid][1], st[tid][2], st[tid][3]);
+            const u64 legal = ext[tid][1] & TAROK_OBS_MASK;
+            if (!legal) {
+                live = false;
+                ires[it] = 0;
+            } else {
+                const u32 seat = (h.leader + h.nt) & 3, q = h.trick_no * 4 + h.nt;
+                const u32 c = ((net_seats >> seat) & 1u) ? (u32)act_s[tid] : policy_action(keys[tid], q, legal);
+                u64 scores = 0;
+                u32 ti;
+                if (apply_step<true>(h, c, scores, ti, false)) {
+                    live = false;
+                    ires[it] = scores;
+                } else {
+                    pack(h, st[tid][0], st[tid][1], st[tid][2], st[tid][3]);
+                }
+            }
+        }
+    }
+    if (live) ires[it] = 0;
+}
+
+// Third launch: 16 lanes per game; lane r < 12 sums rank r's items over the worlds in integers, then card_epilogue's
+// write-out on the game's position, as the det launch.
+TK_KERNEL(TK_BLOCK, 64) void k_playout_net_sum(int64_t n, u32 worlds, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                              const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
+                                              const u64 *__restrict__ gkey, const u64 *__restrict__ ires,
+                                              int4 *__restrict__ sum_out, uint8_t *__restrict__ action_out) {
+    TK_VGPR_TOP(64, 63);
+    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> 4) * TAROK_PLAYOUT_RANKS * 4];
+    const PlayoutTeam t(4);
+    int *row = sums + t.team * (TAROK_PLAYOUT_RANKS * 4);
+    CardPosition p;
+    u32 nlegal = 0;
+    if (t.g < n) {
+        Game g0;
+        load_game(g0, s01, s23, t.g);
+        p = card_position(g0, seat_sets, seats, t.g);
+        if (p.takes_part) nlegal = (u32)popc64(p.legal);
+        if (t.lane < TAROK_PLAYOUT_RANKS) {
+            const u64 *r = ires + (t.g * TAROK_PLAYOUT_RANKS + t.lane) * (int64_t)worlds;
+            int4 s = make_int4(0, 0, 0, 0);
+            for (u32 w = 0; w < worlds; w++) {
+                const u64 sc = r[w];
+                s.x += (int)(int16_t)sc; s.y += (int)(int16_t)(sc >> 16); s.z += (int)(int16_t)(sc >> 32); s.w += (int)(int16_t)(sc >> 48);
+            }
+            reinterpret_cast<int4 *>(row)[t.lane] = s;
+        }
+    }
+    __syncthreads();
+    if (t.g < n) card_epilogue(t, row, p, nlegal, gkey, sum_out, action_out);
+}
+
+// ---------------------------------------------------------------------------
 // The reference agent's transition targets in its own form: what Nevronski_igralec.rezultat_stiha
 // builds per trick and rezultat_igre completes (Igralec.py:387-446), for every (trick, game, seat) of a recorded
 // rollout of whole tricks:  dy[54] = -70 on the cards that were not legal at the seat's decision (:392-393), on the
@@ -3922,6 +4124,33 @@ int tarok_playout_cards(tarok_env *e, int samples, uint64_t salt, int seats, con
 int tarok_playout_cards_det(tarok_env *e, int worlds, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
                             int32_t *sum_out, uint8_t *action_out, void *stream) {
     return launch_playout_cards<true>(k_playout_det, e, worlds, samples, salt, seats, seats_per_game, sum_out, action_out, stream);
+}
+
+int64_t tarok_playout_net_scratch(const tarok_env *e, int worlds) {
+    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS) return TAROK_EINVAL;
+    return e->n * TAROK_PLAYOUT_RANKS * (int64_t)worlds * TK_PN_ITEM_BYTES;
+}
+
+// tarok_playout_cards_net: the items, the playouts, the sums — three launches on `stream`, nothing allocated.
+int tarok_playout_cards_net(tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game, int net_seats,
+                            const void *w1, const float *b1, const void *w2, const float *b2, const void *w3, const float *b3,
+                            void *scratch, int64_t scratch_bytes, int32_t *sum_out, uint8_t *action_out, void *stream) {
+    if (!playout_args_ok(e, worlds, 1, seats) || net_seats < 0 || net_seats > 15 || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 ||
+        !scratch || ((uintptr_t)scratch & 15) || scratch_bytes < tarok_playout_net_scratch(e, worlds) || (!sum_out && !action_out))
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    const int64_t items = e->n * TAROK_PLAYOUT_RANKS * (int64_t)worlds;
+    ulonglong2 *i01 = reinterpret_cast<ulonglong2 *>(scratch), *i23 = i01 + items;
+    u64 *ikey = reinterpret_cast<u64 *>(i23 + items), *ires = ikey + items;
+    const u32 lg = playout_lg(TK_PO_MIN_LG, worlds);
+    hipLaunchKernelGGL(k_playout_net_deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
+                       (u32)worlds, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, i01, i23, ikey, ires);
+    hipLaunchKernelGGL(k_playout_net_play, dim3((unsigned)((items + PM_M - 1) / PM_M)), dim3(TK_BLOCK), 0, (hipStream_t)stream, items,
+                       (u32)net_seats, i01, i23, ikey, ires, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3);
+    hipLaunchKernelGGL(k_playout_net_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, (u32)worlds,
+                       (u32)seats, seats_per_game, e->s01, e->s23, e->gkey, ires, reinterpret_cast<int4 *>(sum_out), action_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
 }
 
 int tarok_playout_exchange(tarok_env *e, int worlds, int samples, int discard_sets, uint64_t salt, int seats,

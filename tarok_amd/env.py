@@ -88,6 +88,7 @@ class TarokVecEnv:
         _native.check(L.tarok_create(C.byref(h), self.device_index, self.n, self.game_offset, self.seed, self.mix,
                                      K.HISTORY if history else 0))
         self._h = h
+        self._net_scratch = {}          # playout_cards_net: worlds -> its scratch tensor
         self.set_option(refill_fan, lazy_refill)
         with torch.cuda.device(self.device):
             self.obs_words = torch.zeros(self.n, dtype=torch.int64, device=self.device)
@@ -360,6 +361,44 @@ class TarokVecEnv:
         called king is among the unseen cards the world's team is the declarer and whoever was dealt it.
         Outputs, `seats` / `seats_per_game`, `salt` and the read-only contract: as for playout_cards."""
         return self._playout_cards(self.L.tarok_playout_cards_det, (worlds, samples), salt, seats, seats_per_game, (), sum_out, action_out)
+
+    def playout_net_scratch(self, worlds):
+        """The scratch tensor of playout_cards_net at `worlds` (uint8, tarok_playout_net_scratch bytes), cached on the env
+        per `worlds`: a caller that captures the launch into a graph asks for it BEFORE the capture."""
+        worlds = int(worlds)
+        if not 1 <= worlds <= K.PLAYOUT_MAX_WORLDS:
+            raise ValueError("worlds: 1..%d" % K.PLAYOUT_MAX_WORLDS)
+        cache = self._net_scratch
+        if worlds not in cache:
+            size = int(self.L.tarok_playout_net_scratch(self._h, worlds))
+            if size < 0:
+                _native.check(size)
+            with torch.cuda.device(self.device):
+                cache[worlds] = torch.empty(size, dtype=torch.uint8, device=self.device)
+        return cache[worlds]
+
+    def playout_cards_net(self, weights, worlds, net_seats=15, salt=0, seats=15, seats_per_game=None, sum_out=None, action_out=None):
+        """playout_cards_det whose playouts are played by a policy network (tarok_playout_cards_net): one playout per
+        (legal card, world); after the candidate card the seats of `net_seats` (a 4-bit set of absolute seats) play the
+        GREEDY card of `weights` (policy_mlp's six tensors, read when the launch runs) on the playout's own position,
+        the other seats the Bot's card.  The sums are over `worlds` playouts (playout_values' divisor).  net_seats=15:
+        the learned policy with one ply of search on top; net_seats=0: playout_cards_det(worlds, 1) to the byte; one
+        seat: a best response to a table of Bots.  Worlds, outputs, `seats` / `seats_per_game`, `salt` and the
+        read-only contract: as for playout_cards_det.  The scratch is playout_net_scratch(worlds)."""
+        if not 0 <= int(net_seats) <= 15:
+            raise ValueError("net_seats: a 4-bit seat set, 0..15")
+        w = self.check_mlp_weights(weights)
+        scratch = self.playout_net_scratch(worlds)
+        with torch.cuda.device(self.device):
+            if sum_out is None:
+                sum_out = torch.empty((self.n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=self.device)
+            if action_out is None:
+                action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
+            _native.check(self.L.tarok_playout_cards_net(self._h, int(worlds), int(salt) & ((1 << 64) - 1), int(seats),
+                                                         self._p(self._seat_sets(seats_per_game)), int(net_seats),
+                                                         *[self._p(t) for t in w], self._p(scratch), scratch.numel(),
+                                                         self._p(sum_out), self._p(action_out), self._stream()))
+        return sum_out, action_out
 
     def playout_exchange(self, worlds, samples, discard_sets=4, salt=0, seats=15, seats_per_game=None, sum_out=None,
                          choice_out=None, discards_out=None):

@@ -162,7 +162,8 @@ def _exchange_bufs(env, n, exchange, want_start):
 
 
 def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None, voids=False, exchange=None,
-                    hidden=False, bidding=None, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False):
+                    hidden=False, bidding=None, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None,
+                    net_seats=15):
     """_play_passes_mode with the Monte-Carlo player (TarokVecEnv.playout_cards) in the network's place: per lock-step
     one playout launch with the pass's seat set — tarok_playout_cards (open hands) for worlds=None,
     tarok_playout_cards_det (the fair player: `worlds` re-deals of the unseen cards) otherwise — whose action_out holds
@@ -176,7 +177,20 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     is the state BEFORE the exchange.  None: the reset's own Bot exchange, the code path as it was.
     bidding=(W, S) (with worlds): every pass starts with _bid_front at (W, S) — the playout player bids for its seat too;
     the inspected dicts then also hold contract, declarer and king_suit [N] i8.  None: the mix's own contracts.
+    net=weights (with worlds, with nothing else): every lock-step runs tarok_playout_cards_net at `worlds` — the playouts
+    are played by the network's greedy card on the seats of net_seats (a 4-bit set, or "own": the pass's seat set) and by
+    the Bot elsewhere; `samples` is not taken.
     inspect: as in _play_passes_mode."""
+    if net is not None:
+        if worlds is None:
+            raise ValueError("net= plays the determinized player's playouts: give worlds= as well")
+        if samples is not None:
+            raise ValueError("net= runs one playout per (card, world): samples is not taken (pass None)")
+        if voids or hidden or exchange is not None or bidding is not None:
+            raise ValueError("net= composes with nothing else yet: no voids, hidden, exchange or bidding")
+        if net_seats != "own" and not (isinstance(net_seats, int) and 0 <= net_seats <= 15):
+            raise ValueError('net_seats: a 4-bit seat set, 0..15, or "own"')
+        net = TarokVecEnv.check_mlp_weights(net)
     if voids and worlds is None:
         raise ValueError("voids=True constrains the re-deals: give worlds= as well")
     if hidden and worlds is None:
@@ -207,8 +221,12 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
                     env.reset(episode=e, clear_counters=True, **setup)
                     start = env.state() if inspect is not None else None
                 for t in range(GAME_CARDS):
-                    env.playout_cards_fair(worlds, samples, voids=voids, hidden=hidden, words=words, salt=salt, seats=seats, sum_out=sums,
-                                           action_out=actions[t])
+                    if net is not None:
+                        env.playout_cards_net(net, worlds, net_seats=seats if net_seats == "own" else net_seats, salt=salt, seats=seats,
+                                              sum_out=sums, action_out=actions[t])
+                    else:
+                        env.playout_cards_fair(worlds, samples, voids=voids, hidden=hidden, words=words, salt=salt, seats=seats,
+                                               sum_out=sums, action_out=actions[t])
                     env.step(actions[t], auto_reset=False)
                 _, ss = env.counters()                # (the pass's one synchronisation)
                 scores[p, e * n:(e + 1) * n] = ss
@@ -230,7 +248,7 @@ def _bid_bufs(env, n):
 
 def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None,
                             voids=False, exchange=None, hidden=False, bidding=None, threshold=0,
-                            contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False):
+                            contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None, net_seats=15):
     """evaluate_vs_bot with the open-hand Monte-Carlo player in the network's place: a strong reference player that needs
     no training.  On its seat it plays, at every move, the legal card with the best summed score over `samples` Bot
     playouts of each legal card (tarok_playout_cards; `salt` varies their draws).  The playouts see the TRUE hidden
@@ -253,11 +271,16 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
     reset; the other seats bid as the Bot does, so pass 0 is unchanged.  It composes with exchange=D.  None (the default):
     the Bot's bidding round on every seat, as before.  pass_value=True (with bidding): the pass is valued by playouts too
     and is the bar a bid has to clear (tarok_playout_bids_pass, tarok_bid_round_pass; `threshold` the margin over it).
+    net=weights (with worlds=W; `samples` must be None; with none of voids, hidden, exchange, bidding): the fair player
+    whose playouts are played by a policy network (tarok_playout_cards_net) — weights = policy_mlp's six tensors.  Inside
+    the playouts the seats of net_seats (a 4-bit set; 15, the default: every seat) play the network's greedy card, the
+    others the Bot's; net_seats="own" makes the set the player's own seat, a best response to a table of Bots.
     The same five duplicate passes (PASS_SEATS) on an env of its own; returns duplicate_advantage's dict, `policy_mean`
     being the playout player's.  inspect (tests): a list that receives one dict per pass, as in _play_passes_mode."""
     return duplicate_advantage(_playout_passes(samples, n_games, episodes, seed, mix, device, salt=salt, inspect=inspect,
                                                worlds=worlds, voids=voids, exchange=exchange, hidden=hidden, bidding=bidding,
-                                               threshold=threshold, contracts=contracts, pass_value=pass_value))
+                                               threshold=threshold, contracts=contracts, pass_value=pass_value, net=net,
+                                               net_seats=net_seats))
 
 
 def _exchange_passes(worlds, samples, discard_sets, n_games, episodes, seed, mix, device, salt=0, inspect=None):

@@ -269,7 +269,13 @@ class SelfPlay:
     The env must keep the play history (TarokVecEnv(history=True)).
     teacher = dict(..., worlds=W >= 1, hidden=True): the rows come from worlds that also re-deal Klop's face-down talon and
     the declarer's discards — tarok_played_cards, then tarok_playout_cards_hidden, then tarok_playout_targets, recorded
-    the same way.  Needs the play history too; not together with voids=True."""
+    the same way.  Needs the play history too; not together with voids=True.
+    teacher = dict(worlds=W >= 1, net=True, net_seats=15, tau=..., every=..., salt=...): the playouts of the W worlds are
+    played by the LEARNER's own rollout weights — tarok_playout_cards_net on the weights the rollout plays with, the seats
+    of net_seats greedy, the others the Bot — so the teacher improves with its student.  One playout per
+    (card, world): `samples` is optional and must be 1; tarok_playout_targets divides by W.  Not together with voids or
+    hidden; needs the fused policy (hidden = 256).  The launch's scratch is allocated before the rollout is captured, and
+    a replayed graph reads the weights in place.  The launch is costly: `every` matters."""
 
     def __init__(self, env, hidden=256, lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.01, reward_scale=1.0 / 70.0, seed=0,
                  use_graph=True, fused=None, fused_loss=None, fused_step=None, fused_learner=None, max_grad_norm=1.0,
@@ -285,12 +291,26 @@ class SelfPlay:
                 raise ValueError("learner_seats: a seat set 0..15 or a [N] uint8 tensor of sets")
         self.teacher, self.distill_coef = None, float(distill_coef)
         if teacher is not None:
-            unknown = set(teacher) - {"worlds", "samples", "tau", "every", "salt", "voids", "hidden"}
-            if unknown or "samples" not in teacher:
+            unknown = set(teacher) - {"worlds", "samples", "tau", "every", "salt", "voids", "hidden", "net", "net_seats"}
+            net = bool(teacher.get("net", False))
+            if unknown or ("samples" not in teacher and not net):
                 raise ValueError("teacher: dict(worlds=W, samples=S, tau=tau, every=k, salt=...), samples required; unknown keys %s" % sorted(unknown))
-            t = dict(worlds=int(teacher.get("worlds", 0)), samples=int(teacher["samples"]), tau=float(teacher.get("tau", 1.0)),
+            t = dict(worlds=int(teacher.get("worlds", 0)), samples=int(teacher.get("samples", 1)), tau=float(teacher.get("tau", 1.0)),
                      every=int(teacher.get("every", 1)), salt=int(teacher.get("salt", 0)), voids=bool(teacher.get("voids", False)),
-                     hidden=bool(teacher.get("hidden", False)))
+                     hidden=bool(teacher.get("hidden", False)), net=net, net_seats=int(teacher.get("net_seats", 15)))
+            if "net_seats" in teacher and not net:
+                raise ValueError("teacher: net_seats names the network's seats inside the playouts: it goes with net=True")
+            if net:
+                if t["samples"] != 1:
+                    raise ValueError("teacher: net=True runs one playout per (card, world): samples is optional and must be 1")
+                if t["worlds"] < 1:
+                    raise ValueError("teacher: net=True plays the determinized worlds: worlds >= 1")
+                if t["voids"] or t["hidden"]:
+                    raise ValueError("teacher: net=True is not built together with voids=True or hidden=True")
+                if not 0 <= t["net_seats"] <= 15:
+                    raise ValueError("teacher: net_seats is a 4-bit seat set, 0..15")
+                if not ((hidden == 256) if fused is None else bool(fused)):
+                    raise ValueError("teacher: net=True plays tarok_playout_cards_net, which needs the fused policy (hidden = 256)")
             if not (0 <= t["worlds"] <= K.PLAYOUT_MAX_WORLDS and 1 <= t["samples"] <= K.PLAYOUT_MAX_SAMPLES and t["every"] >= 1
                     and 0.0 <= t["tau"] < float("inf")):
                 raise ValueError("teacher: worlds 0..%d, samples 1..%d, tau >= 0 and finite, every >= 1"
@@ -421,7 +441,7 @@ class SelfPlay:
     @torch.no_grad()
     def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None, greedy=False, temperature=None, epsilon=0.0,
                  versus_playout=None, playout_worlds=None, playout_voids=False, playout_exchange=None,
-                 playout_hidden=False, playout_bidding=None, pass_value=False):
+                 playout_hidden=False, playout_bidding=None, pass_value=False, playout_net=False, playout_net_seats=15):
         """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
         weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
         and on the SAME deals on every rank (seed 0, game offset 0, whatever the training env's are): the figures of
@@ -446,7 +466,17 @@ class SelfPlay:
         playout_bidding=(W, S) (with playout_worlds and mix=K.MIX_BOT): the fair player also bids for its seat, every
         contract valued by playouts (evaluate_playout_vs_bot(bidding=(W, S))).
         pass_value=True (with playout_bidding): its pass is valued by playouts too and is the bar its bids have to clear
-        (evaluate_playout_vs_bot(pass_value=True))."""
+        (evaluate_playout_vs_bot(pass_value=True)).
+        playout_net=True (with playout_worlds=W, versus_playout=1 and none of the other playout_ options): the second
+        dict is the determinized player whose playouts are played by THIS learner's current weights
+        (evaluate_playout_vs_bot(net=weights, net_seats=playout_net_seats)): one playout per (card, world)."""
+        if playout_net:
+            if playout_worlds is None:
+                raise ValueError("playout_net goes with playout_worlds=W")
+            if playout_voids or playout_hidden or playout_exchange is not None or playout_bidding is not None:
+                raise ValueError("playout_net composes with none of playout_voids, playout_hidden, playout_exchange, playout_bidding")
+            if versus_playout is not None and int(versus_playout) != 1:
+                raise ValueError("playout_net runs one playout per (card, world): versus_playout is 1")
         if playout_bidding is not None and playout_worlds is None:
             raise ValueError("playout_bidding goes with playout_worlds=W")
         if playout_exchange is not None and playout_worlds is None:
@@ -477,6 +507,9 @@ class SelfPlay:
         if versus_playout is None:
             return own
         from .evaluate import evaluate_playout_vs_bot
+        if playout_net:
+            return own, evaluate_playout_vs_bot(None, n_games, episodes, mix=mix, device=self.env.device_index, worlds=playout_worlds,
+                                                net=self._w, net_seats=playout_net_seats)
         return own, evaluate_playout_vs_bot(int(versus_playout), n_games, episodes, mix=mix, device=self.env.device_index,
                                             worlds=playout_worlds, voids=bool(playout_voids), exchange=playout_exchange,
                                             hidden=bool(playout_hidden), bidding=playout_bidding,
@@ -503,12 +536,20 @@ class SelfPlay:
             tc = self.teacher                         # the voids / played words of the teacher's worlds
             self._teach_words = (torch.empty(n, dtype=torch.int32 if tc["voids"] else torch.int64, device=dev)
                                  if tc["voids"] or tc["hidden"] else None)
+            if tc["net"]:                             # the net launch's scratch: allocated here, before any capture
+                self.env.playout_net_scratch(tc["worlds"])
         self._graph = None
 
     def _teach(self, t):
         """The teacher's rows of lock-step t: one playout launch on the learner's seats from the env's current positions,
         one tarok_playout_targets on the words of that lock-step.  Stream-ordered, read-only on the env, no allocation."""
         env, buf, tc = self.env, self._buf, self.teacher
+        if tc["net"]:                                 # the playouts are played by the learner's own rollout weights
+            env.playout_cards_net(self._w, tc["worlds"], net_seats=tc["net_seats"], salt=tc["salt"], seats_per_game=self._seats,
+                                  sum_out=self._teach_sums, action_out=self._teach_act)
+            env.playout_targets(self._teach_sums, buf["words"][t], tc["worlds"], tc["tau"], seats_per_game=self._seats,
+                                target_out=buf["teach"][t])
+            return
         env.playout_cards_fair(tc["worlds"], tc["samples"], voids=tc["voids"], hidden=tc["hidden"], words=self._teach_words,
                                salt=tc["salt"], seats_per_game=self._seats, sum_out=self._teach_sums, action_out=self._teach_act)
         env.playout_targets(self._teach_sums, buf["words"][t], max(1, tc["worlds"]) * tc["samples"], tc["tau"],
