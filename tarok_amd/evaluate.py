@@ -46,6 +46,165 @@ def duplicate_advantage(scores):
                 by_seat=[float(x) for x in diff.mean(axis=0)], deals=int(deals))
 
 
+def _empty(env, shape, dtype):
+    with torch.cuda.device(env.device):
+        return torch.empty(shape, dtype=dtype, device=env.device)
+
+
+def _passes(n_games, episodes, front, cards, inspect=None, **env_args):
+    """The duplicate-pass driver under every evaluate_* call: the five passes (PASS_SEATS) of every episode on an env of
+    its own, made with env_args (device, seed, mix, history); returns scores [5, episodes * n_games, 4] i32.
+    front, cards: who decides what, as makers that are called once with the env, before the first pass, where they
+    allocate their buffers.  They return
+      the front end    (env, episode, seats) -> (start, extras): the pass's reset and what goes before and after it (_front),
+      the card player  (env, t, seats, action_row): lock-step t's launches — they leave a card per game in action_row [N] u8
+                       and play it, without auto-reset (a finished game ignores its card; a Berac may end early).
+    Per pass: the front end, 48 lock-steps, then ONE host synchronisation to read the slots' score sums.
+    inspect (tests): a list that receives one dict per pass — episode, seats, start (the canonical lanes after the
+    reset), actions [48, N] u8 and scores [N, 4] host arrays, and the front end's extras as host arrays — at the price of
+    a second synchronisation per pass."""
+    n = int(n_games)
+    scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
+    env = TarokVecEnv(n, **env_args)
+    try:
+        actions = _empty(env, (GAME_CARDS, n), torch.uint8)
+        front, cards = front(env), cards(env)
+        for e in range(int(episodes)):
+            for p, seats in enumerate(PASS_SEATS):
+                start, extras = front(env, e, seats)
+                for t in range(GAME_CARDS):
+                    cards(env, t, seats, actions[t])
+                _, ss = env.counters()                # (the pass's one synchronisation)
+                scores[p, e * n:(e + 1) * n] = ss
+                if inspect is not None:
+                    inspect.append(dict(episode=e, seats=seats, start=start, actions=actions.cpu().numpy(), scores=ss.copy(),
+                                        **{k: v.cpu().numpy() for k, v in extras.items()}))
+    finally:
+        env.close()
+    return scores
+
+
+def _front(want_start, bid=None, exchange=None):
+    """The front end of a pass: the bid, if a maker of one is given (_bid_front, _bidnet_front), then the reset, which takes
+    the bid's contract, declarer and king — with the exchange deferred if a maker of one is given (_exchange_front,
+    _exchangenet_front), which then follows.  None: the mix's own contracts, the reset's own Bot exchange.
+    want_start: read the canonical lanes right after the reset — BEFORE a deferred exchange (a synchronisation)."""
+    def make(env):
+        bid_, exchange_ = bid and bid(env), exchange and exchange(env)        # (None stays None)
+
+        def front(env, episode, seats):
+            setup, extras = bid_(env, episode, seats) if bid_ else ({}, {})
+            env.reset(episode=episode, clear_counters=True, **setup, **({"defer_exchange": True} if exchange_ else {}))
+            start = env.state() if want_start else None
+            return start, dict(extras, **exchange_(env, seats)) if exchange_ else extras
+        return front
+    return make
+
+
+def _bid_front(bidding, salt, threshold, contracts, pass_value=False):
+    """The bid of a pass whose playout player bids: ONE tarok_playout_bids at bidding = (worlds, samples) with the pass's
+    seat set, ONE tarok_bid_round — the Bot's own answers outside the set, so the empty set gives K.MIX_BOT's contract,
+    declarer and king.  Returns them twice: as the keyword arguments reset() takes them as, and for `inspect`.  pass_value:
+    both launches' _pass twins (the pass valued by playouts; `threshold` the margin over it)."""
+    worlds, samples = bidding
+
+    def make(env):
+        sums = _empty(env, (env.n, 4, K.BID_ROWS), torch.int32)
+
+        def bid(env, episode, seats):
+            env.playout_bids(episode, worlds, samples, contracts=contracts, salt=salt, seats=seats, sum_out=sums, pass_value=pass_value)
+            c, d, k = env.bid_round(episode, sums, int(worlds) * int(samples), threshold=threshold, contracts=contracts, seats=seats,
+                                    pass_value=pass_value)
+            setup = dict(contract=c, declarer=d, king_suit=k)
+            return setup, setup
+        return bid
+    return make
+
+
+def _bidnet_front(weights, playouts_equiv, reward_scale, threshold, contracts, pass_value=False):
+    """_bid_front with the bidding head in the playout teacher's place: ONE tarok_bid_values at scale = playouts_equiv /
+    reward_scale with the pass's seat set and ONE tarok_bid_round at playouts = playouts_equiv; `inspect` also gets
+    values [N,4,K.BID_ROWS] i32."""
+    scale = float(int(playouts_equiv) / float(reward_scale))
+
+    def make(env):
+        values = _empty(env, (env.n, 4, K.BID_ROWS), torch.int32)
+
+        def bid(env, episode, seats):
+            env.bid_values(episode, weights, scale, contracts=contracts, seats=seats, value_out=values, pass_value=pass_value)
+            c, d, k = env.bid_round(episode, values, int(playouts_equiv), threshold=threshold, contracts=contracts, seats=seats,
+                                    pass_value=pass_value)
+            setup = dict(contract=c, declarer=d, king_suit=k)
+            return setup, dict(setup, values=values)
+        return bid
+    return make
+
+
+def _exchange_front(worlds, samples, discard_sets, salt):
+    """The talon exchange of a pass whose playout player makes it, after a reset that deferred it: ONE
+    tarok_playout_exchange with the pass's seat set — its rows are the Bot's own exchange for a declarer outside the set —
+    and one tarok_exchange that applies them.  Returns choice [N] i8 and discards [N,3] u8, for `inspect`."""
+    def make(env):
+        sums = _empty(env, (env.n, 6 * int(discard_sets), 4), torch.int32)
+        chosen = dict(choice=_empty(env, env.n, torch.int8), discards=_empty(env, (env.n, 3), torch.uint8))
+
+        def exchange(env, seats):
+            env.playout_exchange(worlds, samples, discard_sets, salt=salt, seats=seats, sum_out=sums, choice_out=chosen["choice"],
+                                 discards_out=chosen["discards"])
+            env.exchange(chosen["choice"], chosen["discards"])
+            return chosen
+        return exchange
+    return make
+
+
+def _exchangenet_front(weights):
+    """_exchange_front with the exchange head in the playout teacher's place: ONE tarok_exchange_values with the pass's
+    seat set and one tarok_exchange."""
+    def make(env):
+        chosen = dict(choice=_empty(env, env.n, torch.int8), discards=_empty(env, (env.n, 3), torch.uint8))
+
+        def exchange(env, seats):
+            env.exchange_values(weights, seats=seats, choice_out=chosen["choice"], discards_out=chosen["discards"])
+            env.exchange(chosen["choice"], chosen["discards"])
+            return chosen
+        return exchange
+    return make
+
+
+def _network_cards(weights, opponent, temperature, epsilon):
+    """The card player of the network: the play mode, set once, and one tarok_policy_step_seats (_versus with an
+    `opponent`) per lock-step."""
+    def make(env):
+        env.set_play_mode(temperature, epsilon)
+        # the observation words go back and forth between the env's own buffer (reset() leaves the first ones there)
+        # and a second one: the step's input and output may not alias
+        words = [env.obs_words, _empty(env, env.n, torch.int64)]
+
+        def cards(env, t, seats, row):
+            env.policy_step(weights, words[t & 1], words[(t + 1) & 1], row, auto_reset=False, seats=seats, opponent=opponent)
+        return cards
+    return make
+
+
+def _playout_cards(launch, words_dtype=None):
+    """A card player of two launches per lock-step: launch(env, seats, words, sums, row) — a playout launch that leaves
+    its player's card on the pass's seats and the Bot's on the others in `row` — and one tarok_step that plays it.
+    sums [N, K.PLAYOUT_RANKS, 4] i32 is the launch's sum_out; words [N], if a dtype is given, its history words."""
+    def make(env):
+        sums = _empty(env, (env.n, K.PLAYOUT_RANKS, 4), torch.int32)
+        words = _empty(env, env.n, words_dtype) if words_dtype is not None else None
+
+        def cards(env, t, seats, row):
+            launch(env, seats, words, sums, row)
+            env.step(row, auto_reset=False)
+        return cards
+    return make
+
+
+# the Bot's card on every seat: tarok_playout_cards with the empty seat set — no playout is run
+_bot_cards = _playout_cards(lambda env, seats, words, sums, row: env.playout_cards(1, seats=0, sum_out=sums, action_out=row))
+
+
 def _play_passes(weights, n_games, episodes, seed, mix, device, inspect=None, opponent=None):
     """_play_passes_mode at the play mode (1, 0): every network card one draw from its softmax."""
     return _play_passes_mode(weights, n_games, episodes, seed, mix, device, inspect=inspect, opponent=opponent)
@@ -59,30 +218,8 @@ def _play_passes_mode(weights, n_games, episodes, seed, mix, device, inspect=Non
     too; the Bot's seats, hence the whole of evaluate_vs_bot's pass 0, do not depend on it.
     inspect (tests): a list that receives one dict per pass — episode, seats, start (the canonical lanes after the
     reset), actions [48, N] u8 and scores [N, 4] host arrays — at the price of a second synchronisation per pass."""
-    n = int(n_games)
-    scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
-    env = TarokVecEnv(n, device=device, seed=seed, mix=mix)
-    try:
-        env.set_play_mode(temperature, epsilon)
-        with torch.cuda.device(env.device):
-            # the observation words go back and forth between the env's own buffer (reset() leaves the first ones there)
-            # and a second one: the step's input and output may not alias
-            words = [env.obs_words, torch.empty(n, dtype=torch.int64, device=env.device)]
-            actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
-        for e in range(int(episodes)):
-            for p, seats in enumerate(PASS_SEATS):
-                env.reset(episode=e, clear_counters=True)
-                start = env.state() if inspect is not None else None
-                for t in range(GAME_CARDS):
-                    env.policy_step(weights, words[t & 1], words[(t + 1) & 1], actions[t], auto_reset=False, seats=seats,
-                                    opponent=opponent)
-                _, ss = env.counters()                # (the pass's one synchronisation)
-                scores[p, e * n:(e + 1) * n] = ss
-                if inspect is not None:
-                    inspect.append(dict(episode=e, seats=seats, start=start, actions=actions.cpu().numpy(), scores=ss.copy()))
-    finally:
-        env.close()
-    return scores
+    return _passes(n_games, episodes, _front(inspect is not None), _network_cards(weights, opponent, temperature, epsilon), inspect,
+                   device=device, seed=seed, mix=mix)
 
 
 def evaluate_vs_bot(weights, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, temperature=1.0, epsilon=0.0):
@@ -120,18 +257,6 @@ def evaluate_vs_policy(weights, opponent, n_games, episodes, seed=0, mix=K.MIX_B
                                                  temperature=temperature, epsilon=epsilon))
 
 
-def _bid_front(env, episode, bidding, salt, seats, threshold, contracts, sums, pass_value=False):
-    """The front end of a pass whose playout player also bids: ONE tarok_playout_bids at bidding = (worlds, samples) with
-    the pass's seat set, ONE tarok_bid_round — the Bot's own answers outside the set, so the empty set gives
-    K.MIX_BOT's contract, declarer and king — and the keyword arguments reset() takes them as.  pass_value: both launches'
-    _pass twins (the pass valued by playouts; `threshold` the margin over it)."""
-    worlds, samples = bidding
-    env.playout_bids(episode, worlds, samples, contracts=contracts, salt=salt, seats=seats, sum_out=sums, pass_value=pass_value)
-    c, d, k = env.bid_round(episode, sums, int(worlds) * int(samples), threshold=threshold, contracts=contracts, seats=seats,
-                            pass_value=pass_value)
-    return dict(contract=c, declarer=d, king_suit=k)
-
-
 def _bid_args(bidding, mix):
     if bidding is None:
         return None
@@ -139,26 +264,6 @@ def _bid_args(bidding, mix):
         raise ValueError("bidding=(worlds, samples) replaces the Bot's bidding round: it goes with mix=K.MIX_BOT")
     worlds, samples = bidding
     return int(worlds), int(samples)
-
-
-def _exchange_front(env, episode, worlds, samples, exchange, salt, seats, bufs, setup=None):
-    """The front end of a pass whose playout player also makes the talon exchange: reset with the exchange deferred, ONE
-    tarok_playout_exchange with the pass's seat set — its rows are the Bot's own exchange for a declarer outside the
-    set — and one tarok_exchange that applies them.  setup: _bid_front's contract, declarer and king for the reset.
-    Returns the canonical lanes before the exchange if asked for."""
-    sums, choice, discards, want_start = bufs
-    env.reset(episode=episode, clear_counters=True, defer_exchange=True, **(setup or {}))
-    start = env.state() if want_start else None
-    env.playout_exchange(worlds, samples, exchange, salt=salt, seats=seats, sum_out=sums, choice_out=choice, discards_out=discards)
-    env.exchange(choice, discards)
-    return start
-
-
-def _exchange_bufs(env, n, exchange, want_start):
-    with torch.cuda.device(env.device):
-        return (torch.empty((n, 6 * int(exchange), 4), dtype=torch.int32, device=env.device),
-                torch.empty(n, dtype=torch.int8, device=env.device),
-                torch.empty((n, 3), dtype=torch.uint8, device=env.device), want_start)
 
 
 def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None, voids=False, exchange=None,
@@ -202,48 +307,16 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     if bidding is not None and worlds is None:
         raise ValueError("bidding=(W, S) is the fair player's front end: give worlds= as well")
     bidding = _bid_args(bidding, mix)
-    n = int(n_games)
-    scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
-    env = TarokVecEnv(n, device=device, seed=seed, mix=mix, history=bool(voids or hidden))
-    try:
-        with torch.cuda.device(env.device):
-            actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
-            sums = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=env.device)
-            words = torch.empty(n, dtype=torch.int32 if voids else torch.int64, device=env.device) if voids or hidden else None
-        xb = _exchange_bufs(env, n, exchange, inspect is not None) if exchange is not None else None
-        bsums = _bid_bufs(env, n) if bidding is not None else None
-        for e in range(int(episodes)):
-            for p, seats in enumerate(PASS_SEATS):
-                setup = _bid_front(env, e, bidding, salt, seats, threshold, contracts, bsums, pass_value) if bidding is not None else {}
-                if xb is not None:
-                    start = _exchange_front(env, e, worlds, samples, exchange, salt, seats, xb, setup)
-                else:
-                    env.reset(episode=e, clear_counters=True, **setup)
-                    start = env.state() if inspect is not None else None
-                for t in range(GAME_CARDS):
-                    if net is not None:
-                        env.playout_cards_net(net, worlds, net_seats=seats if net_seats == "own" else net_seats, salt=salt, seats=seats,
-                                              sum_out=sums, action_out=actions[t])
-                    else:
-                        env.playout_cards_fair(worlds, samples, voids=voids, hidden=hidden, words=words, salt=salt, seats=seats,
-                                               sum_out=sums, action_out=actions[t])
-                    env.step(actions[t], auto_reset=False)
-                _, ss = env.counters()                # (the pass's one synchronisation)
-                scores[p, e * n:(e + 1) * n] = ss
-                if inspect is not None:
-                    inspect.append(dict(episode=e, seats=seats, start=start, actions=actions.cpu().numpy(), scores=ss.copy()))
-                    if xb is not None:
-                        inspect[-1].update(choice=xb[1].cpu().numpy(), discards=xb[2].cpu().numpy())
-                    if bidding is not None:
-                        inspect[-1].update({k: v.cpu().numpy() for k, v in setup.items()})
-    finally:
-        env.close()
-    return scores
-
-
-def _bid_bufs(env, n):
-    with torch.cuda.device(env.device):
-        return torch.empty((n, 4, K.BID_ROWS), dtype=torch.int32, device=env.device)
+    if net is not None:
+        cards = _playout_cards(lambda env, seats, words, sums, row: env.playout_cards_net(
+            net, worlds, net_seats=seats if net_seats == "own" else net_seats, salt=salt, seats=seats, sum_out=sums, action_out=row))
+    else:
+        cards = _playout_cards(lambda env, seats, words, sums, row: env.playout_cards_fair(
+            worlds, samples, voids=voids, hidden=hidden, words=words, salt=salt, seats=seats, sum_out=sums, action_out=row),
+            words_dtype=(torch.int32 if voids else torch.int64) if voids or hidden else None)
+    front = _front(inspect is not None, bid=None if bidding is None else _bid_front(bidding, salt, threshold, contracts, pass_value),
+                   exchange=None if exchange is None else _exchange_front(worlds, samples, exchange, salt))
+    return _passes(n_games, episodes, front, cards, inspect, device=device, seed=seed, mix=mix, history=bool(voids or hidden))
 
 
 def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None,
@@ -283,35 +356,6 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
                                                net_seats=net_seats))
 
 
-def _exchange_passes(worlds, samples, discard_sets, n_games, episodes, seed, mix, device, salt=0, inspect=None):
-    """The five passes with the playout player making the talon exchange of its seat ONLY: _exchange_front, then the
-    Bot's card on every seat at every move (tarok_playout_cards with the empty seat set — no playout is run — and one
-    tarok_step: the card loop of evaluate_playout_vs_bot's pass 0).  inspect: one dict per pass — episode, seats, start
-    (the lanes before the exchange), choice, discards, actions, scores."""
-    n = int(n_games)
-    scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
-    env = TarokVecEnv(n, device=device, seed=seed, mix=mix)
-    try:
-        with torch.cuda.device(env.device):
-            actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
-            zeros = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=env.device)
-        xb = _exchange_bufs(env, n, discard_sets, inspect is not None)
-        for e in range(int(episodes)):
-            for p, seats in enumerate(PASS_SEATS):
-                start = _exchange_front(env, e, worlds, samples, discard_sets, salt, seats, xb)
-                for t in range(GAME_CARDS):
-                    env.playout_cards(1, seats=0, sum_out=zeros, action_out=actions[t])
-                    env.step(actions[t], auto_reset=False)
-                _, ss = env.counters()                # (the pass's one synchronisation)
-                scores[p, e * n:(e + 1) * n] = ss
-                if inspect is not None:
-                    inspect.append(dict(episode=e, seats=seats, start=start, choice=xb[1].cpu().numpy(), discards=xb[2].cpu().numpy(),
-                                        actions=actions.cpu().numpy(), scores=ss.copy()))
-    finally:
-        env.close()
-    return scores
-
-
 def evaluate_exchange_vs_bot(worlds, samples, discard_sets, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None):
     """What is the talon exchange alone worth?  The five duplicate passes with the Bot playing EVERY card on every seat;
     in pass 1 + k the games seat k declared get their exchange from tarok_playout_exchange at (worlds, samples,
@@ -319,42 +363,8 @@ def evaluate_exchange_vs_bot(worlds, samples, discard_sets, n_games, episodes, s
     other declarer exchanges as the Bot does (group 0, random discards).  Pass 0 is the Bot everywhere: the scores of
     evaluate_vs_bot's and evaluate_playout_vs_bot's pass 0 on the same deals.  Returns duplicate_advantage's dict,
     `policy_mean` being that of the seat whose exchanges the playouts chose."""
-    return duplicate_advantage(_exchange_passes(worlds, samples, discard_sets, n_games, episodes, seed, mix, device, salt=salt,
-                                                inspect=inspect))
-
-
-def _exchangenet_passes(weights, n_games, episodes, seed, mix, device, inspect=None):
-    """_exchange_passes with the exchange head in the playout teacher's place: per pass a reset with the exchange
-    deferred, ONE tarok_exchange_values with the pass's seat set — its rows are the Bot's own exchange for a declarer
-    outside the set — and one tarok_exchange that applies them, then the Bot's card on every seat at every move.
-    inspect: one dict per pass — episode, seats, start (the lanes before the exchange), choice, discards, actions, scores."""
-    n = int(n_games)
-    weights = TarokVecEnv.check_mlp_weights(weights)
-    scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
-    env = TarokVecEnv(n, device=device, seed=seed, mix=mix)
-    try:
-        with torch.cuda.device(env.device):
-            actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
-            zeros = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=env.device)
-            choice = torch.empty(n, dtype=torch.int8, device=env.device)
-            discards = torch.empty((n, 3), dtype=torch.uint8, device=env.device)
-        for e in range(int(episodes)):
-            for p, seats in enumerate(PASS_SEATS):
-                env.reset(episode=e, clear_counters=True, defer_exchange=True)
-                start = env.state() if inspect is not None else None
-                env.exchange_values(weights, seats=seats, choice_out=choice, discards_out=discards)
-                env.exchange(choice, discards)
-                for t in range(GAME_CARDS):
-                    env.playout_cards(1, seats=0, sum_out=zeros, action_out=actions[t])
-                    env.step(actions[t], auto_reset=False)
-                _, ss = env.counters()                # (the pass's one synchronisation)
-                scores[p, e * n:(e + 1) * n] = ss
-                if inspect is not None:
-                    inspect.append(dict(episode=e, seats=seats, start=start, choice=choice.cpu().numpy(), discards=discards.cpu().numpy(),
-                                        actions=actions.cpu().numpy(), scores=ss.copy()))
-    finally:
-        env.close()
-    return scores
+    front = _front(inspect is not None, exchange=_exchange_front(worlds, samples, discard_sets, salt))
+    return duplicate_advantage(_passes(n_games, episodes, front, _bot_cards, inspect, device=device, seed=seed, mix=mix))
 
 
 def evaluate_exchangenet_vs_bot(weights, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, inspect=None):
@@ -364,38 +374,8 @@ def evaluate_exchangenet_vs_bot(weights, n_games, episodes, seed=0, mix=K.MIX_BO
     b3) as tarok_exchange_values takes them (exchange.ExchangeLearner.weights()) — and every other declarer exchanges as
     the Bot does.  Pass 0 is the Bot's own exchange everywhere: evaluate_exchange_vs_bot's pass 0 on the same deals.
     Returns duplicate_advantage's dict, `policy_mean` being that of the seat whose exchanges the head chose."""
-    return duplicate_advantage(_exchangenet_passes(weights, n_games, episodes, seed, mix, device, inspect=inspect))
-
-
-def _bidding_passes(worlds, samples, n_games, episodes, seed, device, salt=0, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS,
-                    inspect=None, pass_value=False):
-    """The five passes with the playout player making the BID of its seat only: _bid_front, a reset that takes its
-    contract, declarer and king (the Bot's exchange), then the Bot's card on every seat at every move, as in
-    _exchange_passes.  inspect: one dict per pass — episode, seats, contract, declarer, king_suit, start, actions, scores."""
-    n = int(n_games)
-    scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
-    env = TarokVecEnv(n, device=device, seed=seed, mix=K.MIX_BOT)
-    try:
-        with torch.cuda.device(env.device):
-            actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
-            zeros = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=env.device)
-        bsums = _bid_bufs(env, n)
-        for e in range(int(episodes)):
-            for p, seats in enumerate(PASS_SEATS):
-                setup = _bid_front(env, e, (worlds, samples), salt, seats, threshold, contracts, bsums, pass_value)
-                env.reset(episode=e, clear_counters=True, **setup)
-                start = env.state() if inspect is not None else None
-                for t in range(GAME_CARDS):
-                    env.playout_cards(1, seats=0, sum_out=zeros, action_out=actions[t])
-                    env.step(actions[t], auto_reset=False)
-                _, ss = env.counters()                # (the pass's one synchronisation)
-                scores[p, e * n:(e + 1) * n] = ss
-                if inspect is not None:
-                    inspect.append(dict(episode=e, seats=seats, start=start, actions=actions.cpu().numpy(), scores=ss.copy(),
-                                        **{k: v.cpu().numpy() for k, v in setup.items()}))
-    finally:
-        env.close()
-    return scores
+    front = _front(inspect is not None, exchange=_exchangenet_front(TarokVecEnv.check_mlp_weights(weights)))
+    return duplicate_advantage(_passes(n_games, episodes, front, _bot_cards, inspect, device=device, seed=seed, mix=mix))
 
 
 def evaluate_bidding_vs_bot(worlds, samples, n_games, episodes, seed=0, device=0, salt=0, threshold=0,
@@ -407,46 +387,8 @@ def evaluate_bidding_vs_bot(worlds, samples, n_games, episodes, seed=0, device=0
     duplicate_advantage's dict, `policy_mean` being that of the seat that bid by playouts.  pass_value=True: the seat's
     pass is valued by playouts as well (tarok_playout_bids_pass) and is the bar its bids have to clear
     (tarok_bid_round_pass, `threshold` the margin over it); pass 0 is unchanged."""
-    return duplicate_advantage(_bidding_passes(worlds, samples, n_games, episodes, seed, device, salt=salt, threshold=threshold,
-                                               contracts=contracts, inspect=inspect, pass_value=pass_value))
-
-
-def _bidnet_passes(bid_weights, n_games, episodes, seed, device, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, playouts_equiv=16,
-                   reward_scale=1.0 / 70.0, inspect=None, pass_value=False):
-    """_bidding_passes with the bidding head in the playout teacher's place: per pass ONE tarok_bid_values at scale =
-    playouts_equiv / reward_scale with the pass's seat set and ONE tarok_bid_round at playouts = playouts_equiv, a reset
-    that takes their contract, declarer and king (the Bot's exchange), then the Bot's card on every seat at every move.
-    inspect: one dict per pass — episode, seats, contract, declarer, king_suit, values [N,4,K.BID_ROWS] i32, start,
-    actions, scores."""
-    n = int(n_games)
-    weights = TarokVecEnv.check_mlp_weights(bid_weights)
-    scale = float(int(playouts_equiv) / float(reward_scale))
-    scores = np.zeros((len(PASS_SEATS), int(episodes) * n, 4), np.int32)
-    env = TarokVecEnv(n, device=device, seed=seed, mix=K.MIX_BOT)
-    try:
-        with torch.cuda.device(env.device):
-            actions = torch.empty((GAME_CARDS, n), dtype=torch.uint8, device=env.device)
-            zeros = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=env.device)
-        values = _bid_bufs(env, n)
-        for e in range(int(episodes)):
-            for p, seats in enumerate(PASS_SEATS):
-                env.bid_values(e, weights, scale, contracts=contracts, seats=seats, value_out=values, pass_value=pass_value)
-                c, d, k = env.bid_round(e, values, int(playouts_equiv), threshold=threshold, contracts=contracts, seats=seats,
-                                        pass_value=pass_value)
-                setup = dict(contract=c, declarer=d, king_suit=k)
-                env.reset(episode=e, clear_counters=True, **setup)
-                start = env.state() if inspect is not None else None
-                for t in range(GAME_CARDS):
-                    env.playout_cards(1, seats=0, sum_out=zeros, action_out=actions[t])
-                    env.step(actions[t], auto_reset=False)
-                _, ss = env.counters()                # (the pass's one synchronisation)
-                scores[p, e * n:(e + 1) * n] = ss
-                if inspect is not None:
-                    inspect.append(dict(episode=e, seats=seats, start=start, actions=actions.cpu().numpy(), scores=ss.copy(),
-                                        values=values.cpu().numpy(), **{k_: v.cpu().numpy() for k_, v in setup.items()}))
-    finally:
-        env.close()
-    return scores
+    front = _front(inspect is not None, bid=_bid_front((worlds, samples), salt, threshold, contracts, pass_value))
+    return duplicate_advantage(_passes(n_games, episodes, front, _bot_cards, inspect, device=device, seed=seed, mix=K.MIX_BOT))
 
 
 def evaluate_bidnet_vs_bot(bid_weights, n_games, episodes, seed=0, device=0, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS,
@@ -459,6 +401,6 @@ def evaluate_bidnet_vs_bot(bid_weights, n_games, episodes, seed=0, device=0, thr
     every seat: evaluate_bidding_vs_bot's pass 0 on the same deals.  Returns duplicate_advantage's dict, `policy_mean`
     being that of the seat the head bid for.  pass_value=True: output 19 is the seat's value of a pass and the bar its bids
     have to clear (tarok_bid_values_pass, tarok_bid_round_pass; a head trained by BidLearner(pass_value=True))."""
-    return duplicate_advantage(_bidnet_passes(bid_weights, n_games, episodes, seed, device, threshold=threshold, contracts=contracts,
-                                              playouts_equiv=playouts_equiv, reward_scale=reward_scale, inspect=inspect,
-                                              pass_value=pass_value))
+    front = _front(inspect is not None, bid=_bidnet_front(TarokVecEnv.check_mlp_weights(bid_weights), playouts_equiv, reward_scale,
+                                                          threshold, contracts, pass_value))
+    return duplicate_advantage(_passes(n_games, episodes, front, _bot_cards, inspect, device=device, seed=seed, mix=K.MIX_BOT))
