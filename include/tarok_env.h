@@ -825,6 +825,39 @@ int tarok_playout_cards_net(tarok_env *env, int worlds, uint64_t salt, int seats
                             const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
                             int32_t *sum_out, uint8_t *action_out, void *stream);
 
+/* Net-played playouts for the exchange and the bid: tarok_playout_exchange and tarok_playout_bids at ONE playout per
+ * (candidate or option, world), played as tarok_playout_cards_net plays its playouts — the network's greedy card on the
+ * absolute seats of net_seats (one launch-wide 4-bit set), the Bot's card policy_action(pkey, q, legal) on the others.
+ * There is no `samples`: the playout of a row in world w runs under the Bot launch's pkey with k = 0.  Hence
+ * net_seats = 0 writes the bytes of tarok_playout_exchange(worlds, 1, discard_sets) and of tarok_playout_bids(worlds, 1).
+ * w1 .. b3, scratch (16-byte aligned, contents undefined afterwards), the read-only contract and the capture rule are
+ * tarok_playout_cards_net's: nothing is allocated inside either call, the weights are read when the launches RUN.
+ *
+ * tarok_playout_exchange_net: "waiting" and "takes part", the worlds (wkey), the candidates (ckey), sum_out
+ *   [N, 6 * discard_sets, 4] i32 (16-byte aligned), choice_out [N] i8 and discards_out [N,3] u8 — each or NULL, EVERY row
+ *   written, the Bot's own exchange for a waiting game outside the seat set, -1 / 255 for a game that does not wait —
+ *   are exactly tarok_playout_exchange's; the sums are over `worlds` playouts.  Three launches.  Scratch: 48 bytes per
+ *   item, item (g * 6 * discard_sets + r) * worlds + w.
+ * tarok_playout_bids_net: the deal (episode, deals), the viewers, the worlds (wkey), the rows of `contracts`, the Bot's
+ *   exchange under pkey and sum_out [N,4,TAROK_BID_ROWS] i32 — the viewer's own score; zeros for seats outside the set,
+ *   rows outside `contracts`, an invalid deal row and row 19: the pass is not valued here — are exactly
+ *   tarok_playout_bids'.  Four launches (the deal first).  Scratch: 48 bytes per item, item ((g * 4 + v) * TAROK_BID_ROWS
+ *   + r) * worlds + w, then the deal's 40 bytes per game: unlike tarok_playout_bids the first call allocates nothing.
+ * The _scratch functions return TAROK_EINVAL for a NULL env or a size argument out of range.
+ * TAROK_EINVAL (before any HIP call) for a NULL env, worlds outside 1..TAROK_PLAYOUT_MAX_WORLDS, discard_sets outside
+ * 1..TAROK_EXCHANGE_MAX_SETS, contracts outside 1..TAROK_BID_ALL_CONTRACTS, seats or net_seats outside 0..15, a missing
+ * weight or bias, a NULL, misaligned or short scratch, or every output NULL. */
+int64_t tarok_playout_exchange_net_scratch(const tarok_env *env, int worlds, int discard_sets);
+int tarok_playout_exchange_net(tarok_env *env, int worlds, int discard_sets, uint64_t salt, int seats,
+                               const uint8_t *seats_per_game, int net_seats, const void *w1, const float *b1, const void *w2,
+                               const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
+                               int32_t *sum_out, int8_t *choice_out, uint8_t *discards_out, void *stream);
+int64_t tarok_playout_bids_net_scratch(const tarok_env *env, int worlds);
+int tarok_playout_bids_net(tarok_env *env, uint32_t episode, const uint8_t *deals, int worlds, int contracts, uint64_t salt,
+                           int seats, const uint8_t *seats_per_game, int net_seats, const void *w1, const float *b1,
+                           const void *w2, const float *b2, const void *w3, const float *b3, void *scratch,
+                           int64_t scratch_bytes, int32_t *sum_out, void *stream);
+
 /* The learner's network input for a minibatch: features_out[j] [256] bf16 (0.0 / 1.0) = the bits
  * of feature_words[index[j]] (feature_words [M,4] u64 as written by feature_words_out; index
  * [n_samples] i64 sample numbers, or NULL for samples 0..n_samples-1).  Gather + expansion in one

@@ -35,6 +35,7 @@ SYMBOLS = [
     "tarok_bid_values", "tarok_exchange_values", "tarok_exchange_candidates",
     "tarok_playout_bids_pass", "tarok_bid_round_pass", "tarok_bid_values_pass",
     "tarok_playout_net_scratch", "tarok_playout_cards_net",
+    "tarok_playout_exchange_net_scratch", "tarok_playout_exchange_net", "tarok_playout_bids_net_scratch", "tarok_playout_bids_net",
 ]
 
 
@@ -174,6 +175,12 @@ def lib():
     L.tarok_playout_net_scratch.restype = i64; L.tarok_playout_net_scratch.argtypes = [vp, i32]
     L.tarok_playout_cards_net.restype = i32
     L.tarok_playout_cards_net.argtypes = [vp, i32, u64, i32, vp, i32] + [vp] * 6 + [vp, i64, vp, vp, vp]
+    L.tarok_playout_exchange_net_scratch.restype = i64; L.tarok_playout_exchange_net_scratch.argtypes = [vp, i32, i32]
+    L.tarok_playout_exchange_net.restype = i32
+    L.tarok_playout_exchange_net.argtypes = [vp, i32, i32, u64, i32, vp, i32] + [vp] * 6 + [vp, i64, vp, vp, vp, vp]
+    L.tarok_playout_bids_net_scratch.restype = i64; L.tarok_playout_bids_net_scratch.argtypes = [vp, i32]
+    L.tarok_playout_bids_net.restype = i32
+    L.tarok_playout_bids_net.argtypes = [vp, u32, vp, i32, i32, u64, i32, vp, i32] + [vp] * 6 + [vp, i64, vp, vp]
     L.tarok_playout_exchange.restype = i32; L.tarok_playout_exchange.argtypes = [vp, i32, i32, i32, u64, i32, vp, vp, vp, vp, vp]
     L.tarok_shown_voids.restype = i32; L.tarok_shown_voids.argtypes = [vp, vp, vp]
     L.tarok_playout_cards_voids.restype = i32; L.tarok_playout_cards_voids.argtypes = [vp, i32, i32, u64, i32, vp, vp, vp, vp, vp]

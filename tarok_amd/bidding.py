@@ -57,10 +57,23 @@ class BidLearner:
     rows learned and bid.  playouts_equiv: the `playouts` bid_round() is told for the head's values, which are scaled to
     sums over that many playouts, so `threshold` stays in points per game as for the teacher.  pass_value=True: the teacher
     also values a pass (playout_bids(pass_value=True)), output 19 regresses on it, and round() holds every bid against the
-    seat's own pass (bid_values / bid_round with pass_value=True; `threshold` is then the margin over the pass)."""
+    seat's own pass (bid_values / bid_round with pass_value=True; `threshold` is then the margin over the pass).  net: six
+    tensors (policy_mlp's weights, read live at every collect()) — the teacher is then playout_bids_net at `worlds` with the
+    network's greedy card on the seats of net_seats inside the playouts, playouts = worlds; `samples` must be 1 or left
+    unset, and pass_value=True does not go with it (the pass is not valued under the network)."""
 
-    def __init__(self, env, worlds=8, samples=2, contracts=K.BID_DEFAULT_CONTRACTS, lr=1e-3, reward_scale=1.0 / 70.0,
-                 playouts_equiv=16, seed=0, pass_value=False):
+    def __init__(self, env, worlds=8, samples=None, contracts=K.BID_DEFAULT_CONTRACTS, lr=1e-3, reward_scale=1.0 / 70.0,
+                 playouts_equiv=16, seed=0, pass_value=False, net=None, net_seats=15):
+        if net is not None:
+            if pass_value:
+                raise ValueError("net= does not value the pass: pass_value=True goes with the Bot's playouts only")
+            if samples not in (None, 1):
+                raise ValueError("net= runs one playout per (option, world): samples must be 1 or unset")
+            if not (isinstance(net_seats, int) and 0 <= net_seats <= 15):
+                raise ValueError("net_seats: a 4-bit seat set, 0..15")
+            net = TarokVecEnv.check_mlp_weights(net)
+        samples = (1 if net is not None else 2) if samples is None else samples
+        self.net_weights, self.net_seats = net, int(net_seats)
         if not 1 <= int(contracts) <= K.BID_ALL_CONTRACTS:
             raise ValueError("contracts: a bit set within 1..0x3FF")
         if not (reward_scale > 0 and int(playouts_equiv) >= 1):
@@ -109,8 +122,12 @@ class BidLearner:
     def collect(self, episode):
         """(feature_words [N,4,4] int64, sums [N,4,K.BID_ROWS] int32, playouts) of episode `episode`: the teacher's launch
         on every seat and the head's launch for its input rows."""
-        sums = self.env.playout_bids(episode, self.worlds, self.samples, contracts=self.contracts, salt=self.salt,
-                                     pass_value=self.pass_value)
+        if self.net_weights is not None:
+            sums = self.env.playout_bids_net(self.net_weights, episode, self.worlds, net_seats=self.net_seats, contracts=self.contracts,
+                                             salt=self.salt)
+        else:
+            sums = self.env.playout_bids(episode, self.worlds, self.samples, contracts=self.contracts, salt=self.salt,
+                                         pass_value=self.pass_value)
         _, _, fw = self.env.bid_values(episode, self.weights(), self.scale, contracts=self.contracts, feature_words=True)
         return fw, sums, self.worlds * self.samples
 

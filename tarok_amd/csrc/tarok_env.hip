@@ -3512,6 +3512,224 @@ TK_KERNEL(TK_BLOCK, 64) void k_playout_net_sum(int64_t n, u32 worlds, u32 seats,
 }
 
 // ---------------------------------------------------------------------------
+// tarok_playout_exchange_net / tarok_playout_bids_net: the exchange and the bid valued by playouts that
+// k_playout_net_play plays.  An exchange candidate in a world, or a bid option in a world, is an item at 0 cards played
+// under the key the Bot launch uses at sample 0; the scratch holds the four item arrays of tarok_playout_cards_net.
+
+// What decides whether a game takes part in an exchange launch, for both of its kernels.
+struct ExchangePosition {
+    u32 declarer = 0, ncand = 0;
+    bool waiting = false, takes_part = false;
+};
+__device__ __forceinline__ ExchangePosition exchange_position(const Game &g0, const uint8_t *__restrict__ seat_sets, u32 seats, u32 sets,
+                                                              int64_t g) {
+    ExchangePosition p;
+    p.waiting = g0.phase == TK_PHASE_EXCHANGE;
+    p.declarer = g0.declarer;
+    if (p.waiting) {
+        u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+        p.takes_part = (set >> p.declarer) & 1u;
+    }
+    if (p.takes_part) {
+        const u32 gs = group_size(g0.contract);
+        p.ncand = (gs == 3 ? 2u : (gs == 2 ? 3u : 6u)) * sets;
+    }
+    return p;
+}
+
+// Exchange, first launch: the front half of k_playout_exchange — its team layout, worlds, candidates and keys — and, where
+// that kernel plays an item, the game after apply_exchange packed and written with the item's key (k = 0) and TK_PN_LIVE.
+// Item (g * 6 * sets + r) * worlds + w; a row at or beyond ncand, or a game that takes no part, gets result 0 and
+// nothing else.
+TK_KERNEL(TK_BLOCK, 128) void k_playout_exchange_net_deal(int64_t n, int64_t items, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds,
+                                                         u32 sets, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                         const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
+                                                         const Counters *__restrict__ cnt, ulonglong2 *__restrict__ i01,
+                                                         ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
+    TK_VGPR_TOP(128, 127);
+    __shared__ WorldAB world;
+    __shared__ u32 cand_dpk[(TK_BLOCK >> TK_PX_MIN_LG) * TK_PX_ROWS];
+    const PlayoutTeam t(lg, worlds);
+    const u32 L = t.L, lane = t.lane;
+    const int64_t g = t.g;
+    u32 *cand = cand_dpk + t.team * TK_PX_ROWS;
+    ulonglong2 a = {0, 0}, b = {0, 0};
+    u64 ebase = 0;
+    ExchangePosition p;
+    if (g < n) {
+        a = s01[g]; b = s23[g];
+        Game g0;
+        unpack(g0, a.x, a.y, b.x, b.y);
+        p = exchange_position(g0, seat_sets, seats, sets, g);
+        if (p.takes_part) {
+            ebase = (u64)cnt[g].episode << 28;
+            for (u32 w = lane; w < worlds; w += L) {
+                Game d = g0;
+                redeal_unseen(d, p.declarer, game_key(pseed, offset + (u64)g, (7ULL << 61) | ebase | (63ULL << 22) | (u64)w));
+                world.store(t.slot0 + w, d);
+            }
+            for (u32 r = lane; r < p.ncand; r += L) {
+                u32 i = r / sets, d = r - i * sets;
+                cand[r] = exchange_discards(g0, i, game_key(pseed, offset + (u64)g, (5ULL << 61) | ebase | ((u64)i << 6) | (u64)d));
+            }
+        }
+    }
+    __syncthreads();
+    if (g >= n) return;
+    const u32 slots = 6u * sets * worlds;
+    for (u32 s = lane; s < slots; s += L) {
+        const int64_t it = g * (int64_t)slots + s;
+        if (it >= items) break;
+        const u32 r = s / worlds, w = s - r * worlds;
+        u64 res = 0;
+        if (r < p.ncand) {                               // (ncand = 0 for a game that does not take part)
+            const u32 i = r / sets, d = r - i * sets;
+            Game h;
+            unpack(h, a.x, a.y, b.x, b.y);
+            world.load(t.slot0 + w, h);
+            const u32 dpk = cand[r];
+            apply_exchange(h, i, dpk & 255, (dpk >> 8) & 255, (dpk >> 16) & 255);
+            u64 x0, x1, y0, y1;
+            pack(h, x0, x1, y0, y1);
+            i01[it] = make_ulonglong2(x0, x1);
+            i23[it] = make_ulonglong2(y0, y1);
+            ikey[it] = game_key(pseed, offset + (u64)g, (3ULL << 62) | ebase | (63ULL << 22) | ((u64)(8u * i + d) << 16) | ((u64)w << 10));
+            res = TK_PN_LIVE;
+        }
+        ires[it] = res;
+    }
+}
+
+// Exchange, third launch: 16 lanes per game; lane r, r + 16, r + 32 sum their rows' items over the worlds in integers,
+// then the tail of k_playout_exchange: 6 * sets 16-byte rows, and on lane 0 the choice — the first candidate at the
+// maximum of the declarer's sums with its discards drawn again under the candidate key, the Bot's own exchange for a
+// waiting game outside the set, -1 and 255s elsewhere.
+TK_KERNEL(TK_BLOCK, 64) void k_playout_exchange_net_sum(int64_t n, int64_t items, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds,
+                                                       u32 sets, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                       const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
+                                                       const Counters *__restrict__ cnt, const u64 *__restrict__ gkey,
+                                                       const u64 *__restrict__ ires, int4 *__restrict__ sum_out,
+                                                       int8_t *__restrict__ choice_out, uint8_t *__restrict__ discards_out) {
+    TK_VGPR_TOP(64, 63);
+    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> 4) * TK_PX_ROWS * 4];
+    const PlayoutTeam t(4);
+    const int64_t g = t.g;
+    int *row = sums + t.team * (TK_PX_ROWS * 4);
+    const u32 nrows = 6u * sets;
+    if (g < n) {
+        for (u32 r = t.lane; r < nrows; r += t.L) {
+            const int64_t first = (g * (int64_t)nrows + r) * (int64_t)worlds;
+            int4 s = make_int4(0, 0, 0, 0);
+            for (u32 w = 0; w < worlds; w++) {
+                const u64 sc = first + w < items ? ires[first + w] : 0ULL;
+                s.x += (int)(int16_t)sc; s.y += (int)(int16_t)(sc >> 16); s.z += (int)(int16_t)(sc >> 32); s.w += (int)(int16_t)(sc >> 48);
+            }
+            reinterpret_cast<int4 *>(row)[r] = s;
+        }
+    }
+    __syncthreads();
+    if (g >= n) return;
+    if (sum_out)
+        for (u32 r = t.lane; r < nrows; r += t.L) sum_out[g * nrows + r] = reinterpret_cast<const int4 *>(row)[r];
+    if ((choice_out || discards_out) && t.lane == 0) {
+        Game g0;
+        load_game(g0, s01, s23, g);
+        const ExchangePosition p = exchange_position(g0, seat_sets, seats, sets, g);
+        int ch = -1;
+        u32 dpk = 0xFFFFFFu;
+        if (p.takes_part) {                              // the first candidate at the maximum of the declarer's sums
+            const u32 best = best_row(row, p.ncand, p.declarer), i = best / sets, d = best - i * sets;
+            ch = (int)i;
+            dpk = exchange_discards(g0, i, game_key(pseed, offset + (u64)g, (5ULL << 61) | ((u64)cnt[g].episode << 28) | ((u64)i << 6) | (u64)d));
+        } else if (p.waiting) {                          // the Bot's own exchange: group 0, its sampler under the game's key
+            ch = 0;
+            dpk = exchange_discards(g0, 0u, gkey[g]);
+        }
+        if (choice_out) choice_out[g] = (int8_t)ch;
+        if (discards_out) {
+            discards_out[g * 3 + 0] = (uint8_t)dpk; discards_out[g * 3 + 1] = (uint8_t)(dpk >> 8);
+            discards_out[g * 3 + 2] = (uint8_t)(dpk >> 16);
+        }
+    }
+}
+
+// Bids, second launch (after k_bid_deal): k_playout_bids' viewer loop — its team layout, worlds and keys, its barriers
+// outside every test of the seat set — writing items where that kernel plays them: bid_game, the Bot's exchange under the
+// item's key (k = 0) where the contract has one, the game packed with the key and TK_PN_LIVE.  Item ((g * 4 + v) *
+// TAROK_BID_ROWS + r) * worlds + w; the slots of rows outside `contracts` (row 19 among them), of viewers outside the set
+// and of invalid deal rows get result 0 and nothing else.
+TK_KERNEL(TK_BLOCK, 128) void k_playout_bids_net_deal(int64_t n, int64_t items, u64 pseed /* seed ^ salt */, u64 offset, u32 episode,
+                                                     u32 worlds, u32 lg, u32 contracts, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                     const u64 *__restrict__ deal, ulonglong2 *__restrict__ i01,
+                                                     ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
+    TK_VGPR_TOP(128, 127);
+    __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS], world_ids[TK_PO_WORLD_SLOTS];
+    const PlayoutTeam t(lg, worlds);
+    const u32 L = t.L, lane = t.lane, slot0 = t.slot0;
+    const int64_t g = t.g;
+    u64 h0 = 0, h1 = 0, h2 = 0, h3 = 0, tal = 0;
+    u32 set = 0;
+    if (g < n) {
+        h0 = deal[g]; h1 = deal[n + g]; h2 = deal[2 * n + g]; h3 = deal[3 * n + g]; tal = deal[4 * n + g];
+        set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+        if ((h0 | h1 | h2 | h3) == 0) set = 0;           // an invalid deal row
+    }
+    const u32 rowmask = bid_row_mask(contracts), slots = (u32)TAROK_BID_ROWS * worlds;
+    const u64 ebase = (u64)episode << 28;
+#pragma unroll 1
+    for (u32 v = 0; v < 4; v++) {
+        const bool part = (set >> v) & 1u;
+        __syncthreads();                                 // the last viewer's items have read their worlds
+        if (part) {
+            for (u32 w = lane; w < worlds; w += L) {
+                u64 A, B, ids;
+                bid_world(h0, h1, h2, h3, tal, v, game_key(pseed, offset + (u64)g, (2ULL << 61) | ebase | ((u64)v << 6) | (u64)w), A, B, ids);
+                world_a[slot0 + w] = A; world_b[slot0 + w] = B; world_ids[slot0 + w] = ids;
+            }
+        }
+        __syncthreads();
+        if (g < n) {
+            for (u32 s = lane; s < slots; s += L) {
+                const int64_t it = (g * 4 + (int64_t)v) * (int64_t)slots + s;
+                if (it >= items) break;
+                const u32 r = s / worlds, w = s - r * worlds;
+                u64 res = 0;
+                if (part && ((rowmask >> r) & 1u)) {
+                    const u64 pkey = game_key(pseed, offset + (u64)g, (3ULL << 61) | ebase | ((u64)v << 26) | ((u64)r << 21) | ((u64)w << 15));
+                    Game h;
+                    bid_game(h, world_a[slot0 + w], world_b[slot0 + w], world_ids[slot0 + w], r, v);
+                    if (h.phase == TK_PHASE_EXCHANGE) bot_exchange(h, pkey);
+                    u64 x0, x1, y0, y1;
+                    pack(h, x0, x1, y0, y1);
+                    i01[it] = make_ulonglong2(x0, x1);
+                    i23[it] = make_ulonglong2(y0, y1);
+                    ikey[it] = pkey;
+                    res = TK_PN_LIVE;
+                }
+                ires[it] = res;
+            }
+        }
+    }
+}
+
+// Bids, fourth launch: one thread per (game, viewer, row); the VIEWER's 16 bits of the result words of its items,
+// summed over the worlds in integers.  Row 19 and every slot that held no item sum zeros.
+TK_KERNEL(TK_BLOCK, 64) void k_playout_bids_net_sum(int64_t rows /* n * 4 * TAROK_BID_ROWS */, int64_t items, u32 worlds,
+                                                   const u64 *__restrict__ ires, int *__restrict__ sum_out) {
+    TK_VGPR_TOP(64, 63);
+    const int64_t i = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
+    if (i >= rows) return;
+    const u32 v = (u32)((i / TAROK_BID_ROWS) & 3);
+    const int64_t first = i * (int64_t)worlds;
+    int s = 0;
+    for (u32 w = 0; w < worlds; w++) {
+        const u64 sc = first + w < items ? ires[first + w] : 0ULL;
+        s += (int)(int16_t)(sc >> (16 * v));
+    }
+    sum_out[i] = s;
+}
+
+// ---------------------------------------------------------------------------
 // The reference agent's transition targets in its own form: what Nevronski_igralec.rezultat_stiha
 // builds per trick and rezultat_igre completes (Igralec.py:387-446), for every (trick, game, seat) of a recorded
 // rollout of whole tricks:  dy[54] = -70 on the cards that were not legal at the seat's decision (:392-393), on the
@@ -4168,6 +4386,56 @@ int tarok_playout_exchange(tarok_env *e, int worlds, int samples, int discard_se
     return TAROK_OK;
 }
 
+extern "C++" {
+// The four item arrays of a net launch in its scratch (tarok_playout_cards_net's layout).
+struct NetItems {
+    ulonglong2 *i01, *i23;
+    u64 *ikey, *ires;
+    NetItems(void *scratch, int64_t items)
+        : i01(reinterpret_cast<ulonglong2 *>(scratch)), i23(i01 + items), ikey(reinterpret_cast<u64 *>(i23 + items)), ires(ikey + items) {}
+};
+static inline bool net_args_ok(int net_seats, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
+                               const float *b3, const void *scratch, int64_t scratch_bytes, int64_t need) {
+    return net_seats >= 0 && net_seats <= 15 && w1 && b1 && w2 && b2 && w3 && b3 && scratch && !((uintptr_t)scratch & 15) && need >= 0 &&
+           scratch_bytes >= need;
+}
+static inline void launch_net_play(int64_t items, int net_seats, const NetItems &it, const void *w1, const float *b1, const void *w2,
+                                   const float *b2, const void *w3, const float *b3, void *stream) {
+    hipLaunchKernelGGL(k_playout_net_play, dim3((unsigned)((items + PM_M - 1) / PM_M)), dim3(TK_BLOCK), 0, (hipStream_t)stream, items,
+                       (u32)net_seats, it.i01, it.i23, it.ikey, it.ires, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2,
+                       (const __bf16 *)w3, b3);
+}
+}
+
+int64_t tarok_playout_exchange_net_scratch(const tarok_env *e, int worlds, int discard_sets) {
+    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || discard_sets < 1 || discard_sets > TAROK_EXCHANGE_MAX_SETS) return TAROK_EINVAL;
+    return e->n * 6 * (int64_t)discard_sets * (int64_t)worlds * TK_PN_ITEM_BYTES;
+}
+
+// tarok_playout_exchange_net: the items, the playouts, the sums and the choice — three launches on `stream`, nothing allocated.
+int tarok_playout_exchange_net(tarok_env *e, int worlds, int discard_sets, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                               int net_seats, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
+                               const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out, int8_t *choice_out,
+                               uint8_t *discards_out, void *stream) {
+    if (!playout_args_ok(e, worlds, 1, seats) || discard_sets < 1 || discard_sets > TAROK_EXCHANGE_MAX_SETS ||
+        !net_args_ok(net_seats, w1, b1, w2, b2, w3, b3, scratch, scratch_bytes, tarok_playout_exchange_net_scratch(e, worlds, discard_sets)) ||
+        (!sum_out && !choice_out && !discards_out))
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    const int64_t items = e->n * 6 * (int64_t)discard_sets * (int64_t)worlds;
+    const NetItems it(scratch, items);
+    const u32 lg = playout_lg(TK_PX_MIN_LG, worlds);     // tarok_playout_exchange's teams at samples = 1
+    hipLaunchKernelGGL(k_playout_exchange_net_deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, items,
+                       e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)discard_sets, lg, (u32)seats, seats_per_game, e->s01, e->s23,
+                       e->cnt, it.i01, it.i23, it.ikey, it.ires);
+    launch_net_play(items, net_seats, it, w1, b1, w2, b2, w3, b3, stream);
+    hipLaunchKernelGGL(k_playout_exchange_net_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, items,
+                       e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)discard_sets, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt,
+                       e->gkey, it.ires, reinterpret_cast<int4 *>(sum_out), choice_out, discards_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
 int tarok_shown_voids(tarok_env *e, uint32_t *voids_out, void *stream) {
     if (!e || !voids_out || !e->hist) return TAROK_EINVAL;              // needs a TAROK_HISTORY env
     HIPCHK(hipSetDevice(e->device));
@@ -4225,6 +4493,34 @@ int tarok_playout_bids(tarok_env *e, uint32_t episode, const uint8_t *deals, int
 int tarok_playout_bids_pass(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int samples, int contracts, uint64_t salt,
                             int seats, const uint8_t *seats_per_game, int32_t *sum_out, void *stream) {
     return launch_playout_bids(k_playout_bids_pass, e, episode, deals, worlds, samples, contracts, salt, seats, seats_per_game, sum_out, stream);
+}
+
+// the items, then k_bid_deal's 40 bytes per game: the launch allocates nothing, the env's own bidding buffer is not used
+int64_t tarok_playout_bids_net_scratch(const tarok_env *e, int worlds) {
+    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS) return TAROK_EINVAL;
+    return e->n * 4 * TAROK_BID_ROWS * (int64_t)worlds * TK_PN_ITEM_BYTES + e->n * 5 * (int64_t)sizeof(u64);
+}
+
+// tarok_playout_bids_net: the deal, the items, the playouts, the sums — four launches on `stream`, nothing allocated.
+int tarok_playout_bids_net(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int contracts, uint64_t salt, int seats,
+                           const uint8_t *seats_per_game, int net_seats, const void *w1, const float *b1, const void *w2, const float *b2,
+                           const void *w3, const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out, void *stream) {
+    if (!playout_args_ok(e, worlds, 1, seats) || contracts < 1 || contracts > TAROK_BID_ALL_CONTRACTS ||
+        !net_args_ok(net_seats, w1, b1, w2, b2, w3, b3, scratch, scratch_bytes, tarok_playout_bids_net_scratch(e, worlds)) || !sum_out)
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    const int64_t rows = e->n * 4 * TAROK_BID_ROWS, items = rows * (int64_t)worlds;
+    const NetItems it(scratch, items);
+    u64 *deal = it.ires + items;
+    hipLaunchKernelGGL(k_bid_deal, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, episode, deals, deal);
+    const u32 lg = playout_lg(TK_PB_MIN_LG, worlds);     // tarok_playout_bids' teams at samples = 1
+    hipLaunchKernelGGL(k_playout_bids_net_deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, items, e->seed ^ (u64)salt,
+                       e->offset, episode, (u32)worlds, lg, (u32)contracts, (u32)seats, seats_per_game, deal, it.i01, it.i23, it.ikey, it.ires);
+    launch_net_play(items, net_seats, it, w1, b1, w2, b2, w3, b3, stream);
+    hipLaunchKernelGGL(k_playout_bids_net_sum, grid_for(rows), dim3(TK_BLOCK), 0, (hipStream_t)stream, rows, items, (u32)worlds, it.ires,
+                       sum_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
 }
 
 extern "C++" {

@@ -88,7 +88,7 @@ class TarokVecEnv:
         _native.check(L.tarok_create(C.byref(h), self.device_index, self.n, self.game_offset, self.seed, self.mix,
                                      K.HISTORY if history else 0))
         self._h = h
-        self._net_scratch = {}          # playout_cards_net: worlds -> its scratch tensor
+        self._net_scratch = {}          # playout_cards_net: worlds -> its scratch tensor; the _exchange_net / _bids_net launches: (name, shape)
         self.set_option(refill_fan, lazy_refill)
         with torch.cuda.device(self.device):
             self.obs_words = torch.zeros(self.n, dtype=torch.int64, device=self.device)
@@ -444,6 +444,84 @@ class TarokVecEnv:
             _native.check(launch(self._h, int(episode), self._p(deals), int(worlds), int(samples), int(contracts),
                                  int(salt) & ((1 << 64) - 1), int(seats),
                                  self._p(self._seat_sets(seats_per_game)), self._p(sum_out), self._stream()))
+        return sum_out
+
+    def _front_net_scratch(self, key, size_fn, *sizes):
+        """The cached scratch tensor of a front-end net launch: `key` names the launch and its shape in _net_scratch."""
+        cache = self._net_scratch
+        if key not in cache:
+            size = int(size_fn(self._h, *sizes))
+            if size < 0:
+                _native.check(size)
+            with torch.cuda.device(self.device):
+                cache[key] = torch.empty(size, dtype=torch.uint8, device=self.device)
+        return cache[key]
+
+    def playout_exchange_net_scratch(self, worlds, discard_sets=4):
+        """The scratch tensor of playout_exchange_net at (worlds, discard_sets) (uint8, tarok_playout_exchange_net_scratch
+        bytes), cached on the env per shape: a caller that captures the launch asks for it BEFORE the capture."""
+        worlds, discard_sets = int(worlds), int(discard_sets)
+        if not 1 <= worlds <= K.PLAYOUT_MAX_WORLDS:
+            raise ValueError("worlds: 1..%d" % K.PLAYOUT_MAX_WORLDS)
+        if not 1 <= discard_sets <= K.EXCHANGE_MAX_SETS:
+            raise ValueError("discard_sets: 1..%d" % K.EXCHANGE_MAX_SETS)
+        return self._front_net_scratch(("exchange", worlds, discard_sets), self.L.tarok_playout_exchange_net_scratch, worlds, discard_sets)
+
+    def playout_exchange_net(self, weights, worlds, discard_sets=4, net_seats=15, salt=0, seats=15, seats_per_game=None, sum_out=None,
+                             choice_out=None, discards_out=None):
+        """playout_exchange whose playouts are played by a policy network (tarok_playout_exchange_net): one playout per
+        (candidate, world), the seats of `net_seats` (a 4-bit set of absolute seats) playing the GREEDY card of `weights`
+        (policy_mlp's six tensors, read when the launch runs), the other seats the Bot's card.  The sums are over `worlds`
+        playouts.  net_seats=0: playout_exchange(worlds, 1, discard_sets) to the byte.  Candidates, worlds, the three
+        outputs, `seats` / `seats_per_game`, `salt` and the read-only contract: as for playout_exchange.  The scratch is
+        playout_exchange_net_scratch(worlds, discard_sets)."""
+        if not 0 <= int(net_seats) <= 15:
+            raise ValueError("net_seats: a 4-bit seat set, 0..15")
+        w = self.check_mlp_weights(weights)
+        scratch = self.playout_exchange_net_scratch(worlds, discard_sets)
+        with torch.cuda.device(self.device):
+            if sum_out is None:
+                sum_out = torch.empty((self.n, 6 * int(discard_sets), 4), dtype=torch.int32, device=self.device)
+            if choice_out is None:
+                choice_out = torch.empty(self.n, dtype=torch.int8, device=self.device)
+            if discards_out is None:
+                discards_out = torch.empty((self.n, 3), dtype=torch.uint8, device=self.device)
+            _native.check(self.L.tarok_playout_exchange_net(self._h, int(worlds), int(discard_sets), int(salt) & ((1 << 64) - 1),
+                                                            int(seats), self._p(self._seat_sets(seats_per_game)), int(net_seats),
+                                                            *[self._p(t) for t in w], self._p(scratch), scratch.numel(),
+                                                            self._p(sum_out), self._p(choice_out), self._p(discards_out),
+                                                            self._stream()))
+        return sum_out, choice_out, discards_out
+
+    def playout_bids_net_scratch(self, worlds):
+        """The scratch tensor of playout_bids_net at `worlds` (uint8, tarok_playout_bids_net_scratch bytes: 3,840 * worlds
+        + 40 per game), cached on the env per `worlds`: a caller that captures the launch asks for it BEFORE the capture."""
+        worlds = int(worlds)
+        if not 1 <= worlds <= K.PLAYOUT_MAX_WORLDS:
+            raise ValueError("worlds: 1..%d" % K.PLAYOUT_MAX_WORLDS)
+        return self._front_net_scratch(("bids", worlds), self.L.tarok_playout_bids_net_scratch, worlds)
+
+    def playout_bids_net(self, weights, episode, worlds, net_seats=15, contracts=K.BID_DEFAULT_CONTRACTS, deals=None, salt=0, seats=15,
+                         seats_per_game=None, sum_out=None):
+        """playout_bids whose playouts are played by a policy network (tarok_playout_bids_net): one playout per (viewer,
+        option, world), the seats of `net_seats` (a 4-bit set of absolute seats) playing the GREEDY card of `weights`, the
+        other seats the Bot's card; the exchange inside a playout stays the Bot's.  The sums are over `worlds` playouts.
+        net_seats=0: playout_bids(episode, worlds, 1) to the byte.  Row K.BID_PASS_ROW is 0: the pass is not valued here.
+        Everything else as for playout_bids.  The scratch is playout_bids_net_scratch(worlds); nothing is allocated by
+        the launch itself."""
+        if not 0 <= int(net_seats) <= 15:
+            raise ValueError("net_seats: a 4-bit seat set, 0..15")
+        w = self.check_mlp_weights(weights)
+        scratch = self.playout_bids_net_scratch(worlds)
+        deals = self._dev(deals, torch.uint8, (self.n, 54))
+        with torch.cuda.device(self.device):
+            if sum_out is None:
+                sum_out = torch.empty((self.n, 4, K.BID_ROWS), dtype=torch.int32, device=self.device)
+            _native.check(self.L.tarok_playout_bids_net(self._h, int(episode), self._p(deals), int(worlds), int(contracts),
+                                                        int(salt) & ((1 << 64) - 1), int(seats),
+                                                        self._p(self._seat_sets(seats_per_game)), int(net_seats),
+                                                        *[self._p(t) for t in w], self._p(scratch), scratch.numel(),
+                                                        self._p(sum_out), self._stream()))
         return sum_out
 
     def bid_round(self, episode, sums, playouts, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, seats=15, seats_per_game=None,

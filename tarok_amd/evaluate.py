@@ -121,6 +121,31 @@ def _bid_front(bidding, salt, threshold, contracts, pass_value=False):
     return make
 
 
+def _net_front_args(net, net_seats, samples, what):
+    """The checks of a front end whose playouts the network plays: net's six tensors, and the seat set to hand the launch
+    for a pass (a function of the pass's seats: "own" is the pass's own set)."""
+    if samples not in (None, 1):
+        raise ValueError("net= runs one playout per (%s, world): samples must be None or 1" % what)
+    if net_seats != "own" and not (isinstance(net_seats, int) and 0 <= net_seats <= 15):
+        raise ValueError('net_seats: a 4-bit seat set, 0..15, or "own"')
+    return TarokVecEnv.check_mlp_weights(net), (lambda seats: seats if net_seats == "own" else net_seats)
+
+
+def _bid_net_front(net, net_seats, worlds, salt, threshold, contracts):
+    """_bid_front whose playouts the network plays: ONE tarok_playout_bids_net at `worlds` with the pass's seat set —
+    net_seats inside the playouts, or the pass's own set for "own" — and ONE tarok_bid_round at playouts = worlds."""
+    def make(env):
+        sums = _empty(env, (env.n, 4, K.BID_ROWS), torch.int32)
+
+        def bid(env, episode, seats):
+            env.playout_bids_net(net, episode, worlds, net_seats=net_seats(seats), contracts=contracts, salt=salt, seats=seats, sum_out=sums)
+            c, d, k = env.bid_round(episode, sums, int(worlds), threshold=threshold, contracts=contracts, seats=seats)
+            setup = dict(contract=c, declarer=d, king_suit=k)
+            return setup, dict(setup, sums=sums)
+        return bid
+    return make
+
+
 def _bidnet_front(weights, playouts_equiv, reward_scale, threshold, contracts, pass_value=False):
     """_bid_front with the bidding head in the playout teacher's place: ONE tarok_bid_values at scale = playouts_equiv /
     reward_scale with the pass's seat set and ONE tarok_bid_round at playouts = playouts_equiv; `inspect` also gets
@@ -153,6 +178,22 @@ def _exchange_front(worlds, samples, discard_sets, salt):
                                  discards_out=chosen["discards"])
             env.exchange(chosen["choice"], chosen["discards"])
             return chosen
+        return exchange
+    return make
+
+
+def _exchange_net_front(net, net_seats, worlds, discard_sets, salt):
+    """_exchange_front whose playouts the network plays: ONE tarok_playout_exchange_net at (worlds, discard_sets) with the
+    pass's seat set — net_seats inside the playouts, or the pass's own set for "own" — and one tarok_exchange."""
+    def make(env):
+        sums = _empty(env, (env.n, 6 * int(discard_sets), 4), torch.int32)
+        chosen = dict(choice=_empty(env, env.n, torch.int8), discards=_empty(env, (env.n, 3), torch.uint8))
+
+        def exchange(env, seats):
+            env.playout_exchange_net(net, worlds, discard_sets, net_seats=net_seats(seats), salt=salt, seats=seats, sum_out=sums,
+                                     choice_out=chosen["choice"], discards_out=chosen["discards"])
+            env.exchange(chosen["choice"], chosen["discards"])
+            return dict(chosen, sums=sums)
         return exchange
     return make
 
@@ -356,15 +397,36 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
                                                net_seats=net_seats))
 
 
+def _front_cards(cards):
+    """The card player of the front-end evaluations: the Bot on every seat, or — cards=weights — the network's greedy card
+    (_network_cards at temperature 0) on the pass's seats in the Bot's place."""
+    return _bot_cards if cards is None else _network_cards(TarokVecEnv.check_mlp_weights(cards), None, 0.0, 0.0)
+
+
 def evaluate_exchange_vs_bot(worlds, samples, discard_sets, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None):
     """What is the talon exchange alone worth?  The five duplicate passes with the Bot playing EVERY card on every seat;
     in pass 1 + k the games seat k declared get their exchange from tarok_playout_exchange at (worlds, samples,
     discard_sets) — the talon group and discards with the best summed score over determinized playouts — and every
     other declarer exchanges as the Bot does (group 0, random discards).  Pass 0 is the Bot everywhere: the scores of
     evaluate_vs_bot's and evaluate_playout_vs_bot's pass 0 on the same deals.  Returns duplicate_advantage's dict,
-    `policy_mean` being that of the seat whose exchanges the playouts chose."""
+    `policy_mean` being that of the seat whose exchanges the playouts chose.  (The same with the playouts played by a
+    network: evaluate_exchange_net_vs_bot.)"""
     front = _front(inspect is not None, exchange=_exchange_front(worlds, samples, discard_sets, salt))
     return duplicate_advantage(_passes(n_games, episodes, front, _bot_cards, inspect, device=device, seed=seed, mix=mix))
+
+
+def evaluate_exchange_net_vs_bot(net, worlds, discard_sets, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None,
+                                 net_seats=15, cards=None):
+    """evaluate_exchange_vs_bot with the playouts played by a network: net = policy_mlp's six tensors; in pass 1 + k the
+    games seat k declared get their exchange from ONE tarok_playout_exchange_net at (worlds, discard_sets) — one playout
+    per (candidate, world), the network's greedy card on the seats of net_seats (a 4-bit set of absolute seats; "own":
+    the pass's seat set) inside them, the Bot's on the others — in tarok_playout_exchange's place; the inspected dicts
+    also hold the launch's sums.  cards=weights: the pass's seats also PLAY the network's greedy card, in the Bot's place.
+    Pass 0 is the Bot everywhere either way: evaluate_exchange_vs_bot's pass 0 on the same deals.  (A function of its own,
+    not arguments of evaluate_exchange_vs_bot: that call's parameter list is pinned as it stands.)"""
+    exchange = _exchange_net_front(*_net_front_args(net, net_seats, None, "candidate"), worlds, discard_sets, salt)
+    front = _front(inspect is not None, exchange=exchange)
+    return duplicate_advantage(_passes(n_games, episodes, front, _front_cards(cards), inspect, device=device, seed=seed, mix=mix))
 
 
 def evaluate_exchangenet_vs_bot(weights, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, inspect=None):
@@ -379,16 +441,27 @@ def evaluate_exchangenet_vs_bot(weights, n_games, episodes, seed=0, mix=K.MIX_BO
 
 
 def evaluate_bidding_vs_bot(worlds, samples, n_games, episodes, seed=0, device=0, salt=0, threshold=0,
-                            contracts=K.BID_DEFAULT_CONTRACTS, inspect=None, pass_value=False):
+                            contracts=K.BID_DEFAULT_CONTRACTS, inspect=None, pass_value=False, net=None, net_seats=15, cards=None):
     """What is the bid alone worth?  The five duplicate passes on K.MIX_BOT's deals with the Bot making EVERY exchange and
     playing EVERY card; in pass 1 + k seat k bids by playouts — tarok_playout_bids at (worlds, samples) over `contracts`,
     then tarok_bid_round with `threshold` — against three Bot bidders, and calls its king by the same sums.  Pass 0 is the
     Bot's own bidding round on every seat: the scores of evaluate_vs_bot's pass 0 on the same deals.  Returns
     duplicate_advantage's dict, `policy_mean` being that of the seat that bid by playouts.  pass_value=True: the seat's
     pass is valued by playouts as well (tarok_playout_bids_pass) and is the bar its bids have to clear
-    (tarok_bid_round_pass, `threshold` the margin over it); pass 0 is unchanged."""
-    front = _front(inspect is not None, bid=_bid_front((worlds, samples), salt, threshold, contracts, pass_value))
-    return duplicate_advantage(_passes(n_games, episodes, front, _bot_cards, inspect, device=device, seed=seed, mix=K.MIX_BOT))
+    (tarok_bid_round_pass, `threshold` the margin over it); pass 0 is unchanged.
+    net=weights (policy_mlp's six tensors; `samples` None or 1; not with pass_value=True): the playouts are played by the
+    network — one tarok_playout_bids_net at `worlds` in tarok_playout_bids' place, the network's greedy card on the seats
+    of net_seats (a 4-bit set of absolute seats; "own": the pass's seat set) inside them, and tarok_bid_round at playouts =
+    worlds; the inspected dicts then also hold the launch's sums.  cards=weights: the pass's seats also PLAY the network's
+    greedy card, in the Bot's place.  With the defaults the call issues the launches it always did."""
+    if net is None:
+        bid = _bid_front((worlds, samples), salt, threshold, contracts, pass_value)
+    else:
+        if pass_value:
+            raise ValueError("net= does not value the pass: pass_value=True goes with the Bot's playouts only")
+        bid = _bid_net_front(*_net_front_args(net, net_seats, samples, "option"), worlds, salt, threshold, contracts)
+    front = _front(inspect is not None, bid=bid)
+    return duplicate_advantage(_passes(n_games, episodes, front, _front_cards(cards), inspect, device=device, seed=seed, mix=K.MIX_BOT))
 
 
 def evaluate_bidnet_vs_bot(bid_weights, n_games, episodes, seed=0, device=0, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS,

@@ -65,11 +65,21 @@ class ExchangeLearner:
 
     env: a TarokVecEnv, which collect() RESETS with the exchange deferred (give the learner an env of its own), or None
     for a learner on the CPU that is fed batches by hand (loss / step).  worlds, samples, discard_sets: the teacher's
-    launch (playout_exchange)."""
+    launch (playout_exchange).  net: six tensors (policy_mlp's weights, read live at every collect()) — the teacher is then
+    playout_exchange_net at (worlds, discard_sets) with the network's greedy card on the seats of net_seats inside the
+    playouts, playouts = worlds; `samples` must be 1 or left unset."""
 
-    def __init__(self, env, worlds=8, samples=2, discard_sets=4, lr=1e-3, reward_scale=1.0 / 70.0, seed=0):
+    def __init__(self, env, worlds=8, samples=None, discard_sets=4, lr=1e-3, reward_scale=1.0 / 70.0, seed=0, net=None, net_seats=15):
         if not reward_scale > 0:
             raise ValueError("reward_scale > 0")
+        if net is not None:
+            if samples not in (None, 1):
+                raise ValueError("net= runs one playout per (candidate, world): samples must be 1 or unset")
+            if not (isinstance(net_seats, int) and 0 <= net_seats <= 15):
+                raise ValueError("net_seats: a 4-bit seat set, 0..15")
+            net = TarokVecEnv.check_mlp_weights(net)
+        samples = (1 if net is not None else 2) if samples is None else samples
+        self.net_weights, self.net_seats = net, int(net_seats)
         self.env = env
         self.device = env.device if env is not None else torch.device("cpu")
         self.worlds, self.samples, self.discard_sets = int(worlds), int(samples), int(discard_sets)
@@ -113,7 +123,11 @@ class ExchangeLearner:
         reset with the exchange deferred, the teacher's launch on every declarer, its candidates' discards and the head's
         launch for its input rows.  The games are left waiting for the exchange."""
         self.env.reset(episode=episode, defer_exchange=True)
-        sums, _, _ = self.env.playout_exchange(self.worlds, self.samples, self.discard_sets, salt=self.salt)
+        if self.net_weights is not None:
+            sums, _, _ = self.env.playout_exchange_net(self.net_weights, self.worlds, self.discard_sets, net_seats=self.net_seats,
+                                                       salt=self.salt)
+        else:
+            sums, _, _ = self.env.playout_exchange(self.worlds, self.samples, self.discard_sets, salt=self.salt)
         cands = self.env.exchange_candidates(self.discard_sets, salt=self.salt)
         _, _, _, fw = self.env.exchange_values(self.weights(), feature_words=True)
         return fw, sums, cands, self.worlds * self.samples
