@@ -38,6 +38,7 @@ extern "C" {
 #define TAROK_ABI_VERSION 5
 #define TAROK_MAX_CARDS_PER_LAUNCH 192 /* tarok_krog_random / tarok_run_random: cards of every game per launch */
 #define TAROK_GAMES_AHEAD 14           /* games every slot keeps dealt ahead for TAROK_AUTO_RESET (tarok_prefetch)  */
+#define TAROK_POOL_MAX 64              /* tarok_policy_step_pool: networks in one opponent pool                     */
 
 #define TAROK_OK 0
 #define TAROK_EINVAL (-1) /* bad argument                                  */
@@ -703,8 +704,9 @@ int tarok_observe_hands_ref(tarok_env *env, uint8_t *out, void *stream);
 int tarok_get_history(tarok_env *env, uint8_t *hist_out, void *stream);
 int tarok_set_history(tarok_env *env, const uint8_t *hist_in, void *stream);
 
-/* The play mode of an env: HOW the five launches below that turn the network's logits into a card — tarok_sample_policy,
- * tarok_policy_mlp, tarok_policy_step, tarok_policy_step_seats, tarok_policy_step_versus — choose it.  Two numbers,
+/* The play mode of an env: HOW the six launches below that turn the network's logits into a card — tarok_sample_policy,
+ * tarok_policy_mlp, tarok_policy_step, tarok_policy_step_seats, tarok_policy_step_versus, tarok_policy_step_pool —
+ * choose it.  Two numbers,
  * temperature T >= 0 and epsilon in [0, 1]; a new env has (1, 0): one draw from the softmax over the legal cards, as
  * described at those functions.  For a game with k > 0 legal cards, logits l_c and `played` cards so far:
  *   T > 0   the draw is made from p_T(c) ~ exp((l_c - max over the legal cards) * (1.0f / T)): the same spec RNG draw,
@@ -796,6 +798,32 @@ int tarok_policy_step_versus(tarok_env *env, int seats, const uint8_t *seats_per
                              const uint64_t *obs, uint8_t *action_out, float *logp_out, float *value_out,
                              uint64_t *feature_words_out, int16_t *reward_out, uint8_t *done_out, uint16_t *trick_out,
                              uint64_t *obs_out, int flags, void *stream);
+
+/* tarok_policy_step_versus against a POOL of frozen networks in one launch: the seats of a game's set play the learner
+ * (w1 .. b3), the others the network of the game's STEP GROUP — group g is slots 256 g .. 256 g + 255, the games one
+ * play workgroup owns; a slot stays in its group through auto-resets, so a group keeps its opponent from game to game.
+ *   seats, seats_per_game   as in tarok_policy_step_versus: bit s set = seat s plays the learner
+ *   pool_size               1 .. TAROK_POOL_MAX networks
+ *   p1 .. q3                the pool, six stacked arrays [pool_size, ...]: entry k of an array starts k * size elements
+ *                           after its base, size = 65,536 / 256 / 65,536 / 256 / 16,384 / 64 (w1, b1, w2, b2, w3, b3 of
+ *                           one network, each entry in tarok_policy_mlp's layout).  Read through the pointers when the
+ *                           launch RUNS: a captured graph sees an entry that was overwritten in place
+ *   group_net               [ceil(N / 256)] u8 (device) or NULL: the index k of each step group; NULL means
+ *                           k = g % pool_size.  ANY k >= pool_size means the learner itself: the group is plain
+ *                           self-play (both networks are w1 .. b3), and nothing outside the pool is read
+ * The other arguments are tarok_policy_step's.  action_out, logp_out and value_out of a game are its mover's network's,
+ * bit for bit what tarok_policy_mlp with that network's weights writes on the same observation words; everything else
+ * is tarok_policy_step_versus'.  The env's play mode applies to every network.  seats = 15 gives exactly
+ * tarok_policy_step with the learner, whatever the pool; pool_size = 1 with group_net = NULL gives
+ * tarok_policy_step_versus(..., pool entry 0) to the byte.
+ * TAROK_EINVAL (before any HIP call) for everything tarok_policy_step_versus refuses, pool_size outside
+ * 1..TAROK_POOL_MAX or a missing pool array. */
+int tarok_policy_step_pool(tarok_env *env, int seats, const uint8_t *seats_per_game, const void *w1, const float *b1,
+                           const void *w2, const float *b2, const void *w3, const float *b3, int pool_size,
+                           const void *p1, const float *q1, const void *p2, const float *q2, const void *p3,
+                           const float *q3, const uint8_t *group_net, const uint64_t *obs, uint8_t *action_out,
+                           float *logp_out, float *value_out, uint64_t *feature_words_out, int16_t *reward_out,
+                           uint8_t *done_out, uint16_t *trick_out, uint64_t *obs_out, int flags, void *stream);
 
 /* Policy-network playouts: tarok_playout_cards_det whose playouts are played by a policy network — the determinized
  * player with the learned policy inside, a teacher that improves with its student, and (by the choice of net_seats) a

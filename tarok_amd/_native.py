@@ -25,7 +25,7 @@ SYMBOLS = [
     "tarok_strerror", "tarok_abi_version", "tarok_device_count", "tarok_last_hip_error",
     "tarok_create", "tarok_destroy", "tarok_num_games", "tarok_set_option", "tarok_reset", "tarok_exchange",
     "tarok_legal_actions", "tarok_step", "tarok_prefetch", "tarok_policy_random", "tarok_step_random",
-    "tarok_run_random", "tarok_krog_random", "tarok_rollout_random", "tarok_get_state", "tarok_set_state", "tarok_get_counters", "tarok_debug_stamps", "tarok_debug_stamps_sized", "tarok_debug_refill_selftest", "tarok_observe", "tarok_sample_policy", "tarok_policy_mlp", "tarok_policy_step", "tarok_policy_step_seats", "tarok_policy_step_versus", "tarok_expand_features", "tarok_ppo_loss",
+    "tarok_run_random", "tarok_krog_random", "tarok_rollout_random", "tarok_get_state", "tarok_set_state", "tarok_get_counters", "tarok_debug_stamps", "tarok_debug_stamps_sized", "tarok_debug_refill_selftest", "tarok_observe", "tarok_sample_policy", "tarok_policy_mlp", "tarok_policy_step", "tarok_policy_step_seats", "tarok_policy_step_versus", "tarok_policy_step_pool", "tarok_expand_features", "tarok_ppo_loss",
     "tarok_targets_ref", "tarok_learn_returns", "tarok_learn_returns_gae", "tarok_learn_returns_seats", "tarok_learn_select_scratch_bytes", "tarok_learn_select",
     "tarok_learn_chain", "tarok_learn_workspace_bytes", "tarok_learn_dw", "tarok_learn_adam",
     "tarok_observe_ref", "tarok_observe_exchange_ref", "tarok_observe_hands_ref", "tarok_get_history", "tarok_set_history",
@@ -149,6 +149,7 @@ def lib():
     L.tarok_policy_step.restype = i32; L.tarok_policy_step.argtypes = [vp] * 16 + [i32, vp]
     L.tarok_policy_step_seats.restype = i32; L.tarok_policy_step_seats.argtypes = [vp, i32, vp] + [vp] * 15 + [i32, vp]
     L.tarok_policy_step_versus.restype = i32; L.tarok_policy_step_versus.argtypes = [vp, i32, vp] + [vp] * 21 + [i32, vp]
+    L.tarok_policy_step_pool.restype = i32; L.tarok_policy_step_pool.argtypes = [vp, i32, vp] + [vp] * 6 + [i32] + [vp] * 16 + [i32, vp]
     L.tarok_expand_features.restype = i32; L.tarok_expand_features.argtypes = [vp, i64, vp, vp, vp, vp]
     f32 = C.c_float
     L.tarok_ppo_loss.restype = i32; L.tarok_ppo_loss.argtypes = [vp, i64] + [vp] * 7 + [f32] * 3 + [vp] * 4

@@ -3247,9 +3247,15 @@ TK_KERNEL(TK_BLOCK, 128) void k_exchange_candidates(int64_t n, u64 pseed /* seed
     n, seed, offset, mix, flags, play_groups, epoch, fan, obs_in, w1, b1, w2, b2, w3, b3, action, logp, value,                    \
         feature_words_out, reward, done, trick, obs_out, hist, s01, s23, aux, cnt, gkey, rlist, rcount
 
-template <int NETS, bool MIXED, int MODE = 0>
+// `second` (NETS = 2) is the second network's weights, or a callable that gives them: it is called by a play workgroup
+// only, after the refill role has branched off (the pool kernels read their group's table entry in it).
+__device__ __forceinline__ PolicyWeights second_weights(const PolicyWeights &w) { return w; }
+template <class F>
+__device__ __forceinline__ PolicyWeights second_weights(const F &f) { return f(); }
+
+template <int NETS, bool MIXED, int MODE = 0, class SECOND = PolicyWeights>
 __device__ __forceinline__ void policy_step_shell(TK_POLICY_STEP_ARGS, u32 seats, const uint8_t *__restrict__ seat_sets,
-                                                  const PolicyWeights &second, const PlayMode pmode = PlayMode{}) {
+                                                  const SECOND &second, const PlayMode pmode = PlayMode{}) {
     TkCount count = launch_count<1>(epoch, play_groups);          // (in flight under the policy's first loads)
     if (blockIdx.x >= play_groups) {
         refill_role<false>(blockIdx.x - play_groups, threadIdx.x, 2 * TK_BLOCK, seed, offset, mix, play_groups, count, epoch, fan, false, aux, rlist, rcount, nullptr);
@@ -3258,7 +3264,7 @@ __device__ __forceinline__ void policy_step_shell(TK_POLICY_STEP_ARGS, u32 seats
     __shared__ uint8_t act_s[2 * PM_M];
     u32 *lds = nullptr;
     PolicyWeights nets[NETS] = {{w1, b1, w2, b2, w3, b3}};
-    if constexpr (NETS > 1) nets[1] = second;
+    if constexpr (NETS > 1) nets[1] = second_weights(second);
     policy_body<2, NETS, MIXED, MODE>(n, s01, s23, obs_in, gkey, nets, action, logp, value, nullptr, feature_words_out, nullptr, act_s, &lds,
                                       seats, seat_sets, pmode);
     __syncthreads();                          // (the policy's LDS is free from here on: the step's scoring list goes there)
@@ -3308,6 +3314,39 @@ __global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_
     TK_VGPR_TOP(256, 255);
     policy_step_shell<2, false, 1>(TK_POLICY_STEP_NAMES, seats, seat_sets, PolicyWeights{v1, c1, v2, c2, v3, c3}, TK_PLAY_MODE_NAMES);
 }
+
+// tarok_policy_step_pool: k_policy_step_versus whose second network is chosen PER PLAY WORKGROUP (= step group) from a
+// pool of pool_size networks, six stacked arrays with entry k at base + k * size.  The group's index k is
+// group_net[blockIdx.x], or blockIdx.x % pool_size without a table; k >= pool_size is the learner's own network (nets[1]
+// = nets[0]: plain self-play for the group, and no read outside the pool whatever the byte).  k is workgroup-uniform and
+// made so in the compiler's eyes (readfirstlane): the weights stay on scalar base registers, the tiles, the LDS and the
+// order of accumulation are the versus kernel's.  What the kind takes more comes last, as for the other kinds; a refill
+// workgroup never reads group_net.
+#define TK_POOL_ARGS                                                                                                              \
+    u32 pool_size, const __bf16 *__restrict__ p1, const float *__restrict__ q1, const __bf16 *__restrict__ p2,                    \
+        const float *__restrict__ q2, const __bf16 *__restrict__ p3, const float *__restrict__ q3,                                \
+        const uint8_t *__restrict__ group_net
+#define TK_POOL_SECOND                                                                                                            \
+    [&]() __attribute__((always_inline)) {                                                                                        \
+        u32 k = group_net ? (u32)group_net[blockIdx.x] : blockIdx.x % pool_size;                                                  \
+        k = (u32)__builtin_amdgcn_readfirstlane((int)k);                                                                          \
+        if (k >= pool_size) return PolicyWeights{w1, b1, w2, b2, w3, b3};                                                         \
+        return PolicyWeights{p1 + (size_t)k * 65536, q1 + (size_t)k * 256, p2 + (size_t)k * 65536, q2 + (size_t)k * 256,          \
+                             p3 + (size_t)k * 16384, q3 + (size_t)k * 64};                                                        \
+    }
+__global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_step_pool(
+    TK_POLICY_STEP_ARGS, u32 seats, const uint8_t *__restrict__ seat_sets, TK_POOL_ARGS) {
+    TK_VGPR_TOP(256, 255);
+    policy_step_shell<2, false>(TK_POLICY_STEP_NAMES, seats, seat_sets, TK_POOL_SECOND);
+}
+
+__global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_step_pool_mode(
+    TK_POLICY_STEP_ARGS, u32 seats, const uint8_t *__restrict__ seat_sets, TK_POOL_ARGS, TK_PLAY_MODE_ARGS) {
+    TK_VGPR_TOP(256, 255);
+    policy_step_shell<2, false, 1>(TK_POLICY_STEP_NAMES, seats, seat_sets, TK_POOL_SECOND, TK_PLAY_MODE_NAMES);
+}
+#undef TK_POOL_SECOND
+#undef TK_POOL_ARGS
 
 // ---------------------------------------------------------------------------
 // tarok_playout_cards_net: tarok_playout_cards_det at one playout per (legal card, world), whose playouts are played by a
@@ -4760,12 +4799,12 @@ int tarok_policy_mlp(tarok_env *e, const void *w1, const float *b1, const void *
     return TAROK_OK;
 }
 
-// The launch of the three policy-step kinds (0: k_policy_step, 1: k_policy_step_seats, 2: k_policy_step_versus), the
-// arguments checked by the caller: one grid (the play groups, then their refill workgroups), one argument list.
+// The launch of the four policy-step kinds (0: k_policy_step, 1: k_policy_step_seats, 2: k_policy_step_versus,
+// 3: k_policy_step_pool, whose `b` is the six stacked arrays of the pool), the arguments checked by the caller: one grid (the play groups, then their refill workgroups), one argument list.
 static int launch_policy_step(tarok_env *e, int kind, u32 seats, const uint8_t *seat_sets, const PolicyWeights &a,
                               const PolicyWeights &b, const uint64_t *obs, uint8_t *action_out, float *logp_out, float *value_out,
                               uint64_t *feature_words_out, int16_t *reward_out, uint8_t *done_out, uint16_t *trick_out,
-                              uint64_t *obs_out, int flags, void *stream) {
+                              uint64_t *obs_out, int flags, void *stream, u32 pool_size = 0, const uint8_t *group_net = nullptr) {
     HIPCHK(hipSetDevice(e->device));
     u32 groups = (u32)((e->n + TK_BLOCK - 1) / TK_BLOCK);
     u32 fan = e->refill_fan;
@@ -4779,12 +4818,15 @@ static int launch_policy_step(tarok_env *e, int kind, u32 seats, const uint8_t *
     if (!e->mode_on) {                    // play mode (1, 0): the launches as they always were
         if (kind == 0) TK_LAUNCH_POLICY_STEP(k_policy_step);
         else if (kind == 1) TK_LAUNCH_POLICY_STEP(k_policy_step_seats, seats, seat_sets);
-        else TK_LAUNCH_POLICY_STEP(k_policy_step_versus, seats, seat_sets, b.w1, b.b1, b.w2, b.b2, b.w3, b.b3);
+        else if (kind == 2) TK_LAUNCH_POLICY_STEP(k_policy_step_versus, seats, seat_sets, b.w1, b.b1, b.w2, b.b2, b.w3, b.b3);
+        else TK_LAUNCH_POLICY_STEP(k_policy_step_pool, seats, seat_sets, pool_size, b.w1, b.b1, b.w2, b.b2, b.w3, b.b3, group_net);
     } else {
 #define TK_MODE_VALUES e->inv_t, e->greedy, e->explore_thr, e->eps_p
         if (kind == 0) TK_LAUNCH_POLICY_STEP(k_policy_step_mode, TK_MODE_VALUES);
         else if (kind == 1) TK_LAUNCH_POLICY_STEP(k_policy_step_seats_mode, seats, seat_sets, TK_MODE_VALUES);
-        else TK_LAUNCH_POLICY_STEP(k_policy_step_versus_mode, seats, seat_sets, b.w1, b.b1, b.w2, b.b2, b.w3, b.b3, TK_MODE_VALUES);
+        else if (kind == 2) TK_LAUNCH_POLICY_STEP(k_policy_step_versus_mode, seats, seat_sets, b.w1, b.b1, b.w2, b.b2, b.w3, b.b3, TK_MODE_VALUES);
+        else TK_LAUNCH_POLICY_STEP(k_policy_step_pool_mode, seats, seat_sets, pool_size, b.w1, b.b1, b.w2, b.b2, b.w3, b.b3, group_net,
+                                   TK_MODE_VALUES);
 #undef TK_MODE_VALUES
     }
 #undef TK_LAUNCH_POLICY_STEP
@@ -4822,6 +4864,19 @@ int tarok_policy_step_versus(tarok_env *e, int seats, const uint8_t *seats_per_g
     if (!obs || !action_out || !obs_out || obs == obs_out) return TAROK_EINVAL;
     return launch_policy_step(e, 2, (u32)seats, seats_per_game, TK_WEIGHTS(w1, b1, w2, b2, w3, b3), TK_WEIGHTS(v1, c1, v2, c2, v3, c3), obs,
                               action_out, logp_out, value_out, feature_words_out, reward_out, done_out, trick_out, obs_out, flags, stream);
+}
+
+int tarok_policy_step_pool(tarok_env *e, int seats, const uint8_t *seats_per_game, const void *w1, const float *b1, const void *w2,
+                           const float *b2, const void *w3, const float *b3, int pool_size, const void *p1, const float *q1,
+                           const void *p2, const float *q2, const void *p3, const float *q3, const uint8_t *group_net,
+                           const uint64_t *obs, uint8_t *action_out, float *logp_out, float *value_out, uint64_t *feature_words_out,
+                           int16_t *reward_out, uint8_t *done_out, uint16_t *trick_out, uint64_t *obs_out, int flags, void *stream) {
+    if (!e || seats < 0 || seats > 15 || pool_size < 1 || pool_size > TAROK_POOL_MAX) return TAROK_EINVAL;   // (before any HIP call)
+    if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !p1 || !q1 || !p2 || !q2 || !p3 || !q3) return TAROK_EINVAL;
+    if (!obs || !action_out || !obs_out || obs == obs_out) return TAROK_EINVAL;
+    return launch_policy_step(e, 3, (u32)seats, seats_per_game, TK_WEIGHTS(w1, b1, w2, b2, w3, b3), TK_WEIGHTS(p1, q1, p2, q2, p3, q3), obs,
+                              action_out, logp_out, value_out, feature_words_out, reward_out, done_out, trick_out, obs_out, flags, stream,
+                              (u32)pool_size, group_net);
 }
 #undef TK_WEIGHTS
 

@@ -776,8 +776,44 @@ class TarokVecEnv:
                                                   self._stream()))
         return action_out, logp_out, value_out
 
+    POOL_MAX = K.POOL_MAX
+    POOL_SHAPES = ((256, 256), (256,), (256, 256), (256,), (64, 256), (64,))
+
+    @staticmethod
+    def check_pool_weights(pool):
+        """Six stacked tensors (w1 [K,256,256], b1 [K,256], w2 [K,256,256], b2 [K,256], w3 [K,64,256], b3 [K,64]), entry k
+        as check_mlp_weights takes one network, 1 <= K <= 64 — or a ValueError.  Returns (K, the six)."""
+        if not isinstance(pool, (list, tuple)) or len(pool) != 6 or not all(torch.is_tensor(t) for t in pool):
+            raise ValueError("opponent_pool: six stacked tensors (w1, b1, w2, b2, w3, b3), each with a leading K")
+        k = pool[0].shape[0] if pool[0].dim() else 0
+        if not 1 <= k <= TarokVecEnv.POOL_MAX:
+            raise ValueError("opponent_pool: 1..%d networks, got %d" % (TarokVecEnv.POOL_MAX, k))
+        for i, (t, shp) in enumerate(zip(pool, TarokVecEnv.POOL_SHAPES)):
+            want = torch.float32 if i & 1 else torch.bfloat16
+            if t.dtype != want or not t.is_contiguous() or tuple(t.shape) != (k,) + shp:
+                raise ValueError("opponent_pool[%d]: a contiguous %s tensor %s, got %s %s" % (i, want, (k,) + shp, t.dtype, tuple(t.shape)))
+        return k, tuple(pool)
+
+    @staticmethod
+    def stack_pool(weight_sets):
+        """A list of weight sets (each six tensors as check_mlp_weights takes them) -> the six stacked tensors of an
+        opponent pool, entry k = weight_sets[k] (new memory: the sets are copied)."""
+        sets = [TarokVecEnv.check_mlp_weights(w) for w in weight_sets]
+        if not 1 <= len(sets) <= TarokVecEnv.POOL_MAX:
+            raise ValueError("stack_pool: 1..%d weight sets, got %d" % (TarokVecEnv.POOL_MAX, len(sets)))
+        return tuple(torch.stack([s[i] for s in sets]).contiguous() for i in range(6))
+
+    def _group_net(self, group_net):
+        """group_net as tarok_policy_step_pool takes it: None, or a contiguous uint8 tensor [ceil(N / 256)] on the device."""
+        g = group_net
+        if g is not None and not (torch.is_tensor(g) and g.device == self.device and g.dtype == torch.uint8
+                                  and g.is_contiguous() and tuple(g.shape) == ((self.n + 255) // 256,)):
+            raise ValueError("group_net: a contiguous uint8 tensor [ceil(N / 256)] on the env's device")
+        return g
+
     def policy_step(self, weights, obs_words, obs_out, action_out, logp_out=None, value_out=None, feature_words_out=None,
-                    reward_out=None, done_out=None, auto_reset=True, seats=None, seats_per_game=None, tricks=None, opponent=None):
+                    reward_out=None, done_out=None, auto_reset=True, seats=None, seats_per_game=None, tricks=None, opponent=None,
+                    opponent_pool=None, group_net=None):
         """policy_mlp + step in one launch (tarok_policy_step): samples a card per game from the MLP
         policy on `obs_words` and plays it; obs_out receives the next observation words.
         seats (a 4-bit set, bit s: seat s plays the network) or seats_per_game ([N] uint8 device tensor of such sets):
@@ -785,9 +821,26 @@ class TarokVecEnv:
         logp 0.  tricks: a [N] int16 device tensor that receives trick_out (see step()).
         opponent (six tensors like `weights`): a second network in the Bot's place (tarok_policy_step_versus) — the
         seats of the set play `weights`, the others `opponent`, each with its own card, logp and value; without
-        seats / seats_per_game the set is 15."""
+        seats / seats_per_game the set is 15.
+        opponent_pool (six STACKED tensors, stack_pool()) instead of opponent: a pool of K frozen networks
+        (tarok_policy_step_pool) — the other seats of step group g (slots 256 g .. 256 g + 255) play pool entry
+        group_net[g] (a [ceil(N / 256)] uint8 device tensor; None: g % K); an index >= K is `weights` itself."""
         flags = K.AUTO_RESET if auto_reset else 0
-        plain = opponent is None and seats is None and seats_per_game is None
+        if opponent_pool is not None:
+            if opponent is not None:
+                raise ValueError("policy_step: opponent and opponent_pool exclude each other")
+            k, pool = TarokVecEnv.check_pool_weights(opponent_pool)      # (before the env is touched)
+            gn = self._group_net(group_net)
+            with torch.cuda.device(self.device):
+                _native.check(self.L.tarok_policy_step_pool(
+                    self._h, 15 if seats is None else int(seats), self._p(self._seat_sets(seats_per_game)),
+                    *[self._p(t) for t in self.check_mlp_weights(weights)], k, *[self._p(t) for t in pool], self._p(gn),
+                    self._p(obs_words), self._p(action_out), self._p(logp_out), self._p(value_out), self._p(feature_words_out),
+                    self._p(reward_out), self._p(done_out), self._p(tricks), self._p(obs_out), flags, self._stream()))
+            return action_out
+        if group_net is not None:
+            raise ValueError("policy_step: group_net needs opponent_pool")
+        plain =opponent is None and seats is None and seats_per_game is None
         sets = () if plain else (15 if seats is None else int(seats), self._p(self._seat_sets(seats_per_game)))
         nets = [weights] if opponent is None else [self.check_mlp_weights(weights), self.check_mlp_weights(opponent)]
         fn = self.L.tarok_policy_step if plain else self.L.tarok_policy_step_seats if opponent is None else self.L.tarok_policy_step_versus

@@ -298,6 +298,53 @@ def evaluate_vs_policy(weights, opponent, n_games, episodes, seed=0, mix=K.MIX_B
                                                  temperature=temperature, epsilon=epsilon))
 
 
+def _pool_cards(weights, pool, groups_per_block, temperature, epsilon):
+    """_network_cards against a pool: one tarok_policy_step_pool per lock-step, the six stacked tensors `pool` in the
+    opponent's place; step group g plays entry g // groups_per_block."""
+    def make(env):
+        env.set_play_mode(temperature, epsilon)
+        words = [env.obs_words, _empty(env, env.n, torch.int64)]
+        with torch.cuda.device(env.device):
+            group_net = (torch.arange((env.n + 255) // 256, device=env.device) // groups_per_block).to(torch.uint8)
+
+        def cards(env, t, seats, row):
+            env.policy_step(weights, words[t & 1], words[(t + 1) & 1], row, auto_reset=False, seats=seats, opponent_pool=pool,
+                            group_net=group_net)
+        return cards
+    return make
+
+
+def pool_block_scores(scores, k, n_games, pool_size):
+    """Block k's part of the scores of a pool evaluation ([5, episodes * pool_size * G, 4], G = n_games rounded up to a
+    multiple of 256: episode-major, then slot): the first n_games slots of block k = slots [k G, (k + 1) G) of every
+    episode, as [5, episodes * n_games, 4] in evaluate_vs_policy's order of deals."""
+    n = int(n_games)
+    G = -(-n // 256) * 256
+    s = np.asarray(scores)
+    return s.reshape(5, -1, int(pool_size), G, 4)[:, :, int(k), :n].reshape(5, -1, 4)
+
+
+def evaluate_vs_pool(weights, pool, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, temperature=1.0, epsilon=0.0, inspect=None):
+    """evaluate_vs_policy against every network of `pool` (a list of 1..64 weight sets) at once: ONE env of
+    len(pool) * G slots, G = n_games rounded up to a multiple of 256 (whole step groups), block k = slots [k G, (k + 1) G)
+    playing `weights` against pool[k] through tarok_policy_step_pool — one launch per lock-step for the whole pool, on
+    the same five duplicate passes.  Returns a list of duplicate_advantage dicts, dict k from the first n_games slots of
+    block k only (pool_block_scores).  Block k's deals are games k G .. of the seed: block 0's are evaluate_vs_policy's
+    with the same arguments, so a pool of one returns that call's dict; the other blocks play deals of their own.
+    temperature, epsilon: the play mode of every network.  inspect (tests): as in _play_passes_mode, over all slots."""
+    if not isinstance(weights, (tuple, list)) or len(weights) != 6 or not all(torch.is_tensor(t) for t in weights):
+        raise ValueError("weights: six tensors (w1, b1, w2, b2, w3, b3)")
+    weights = TarokVecEnv.check_mlp_weights(weights)
+    if not isinstance(pool, (tuple, list)) or not 1 <= len(pool) <= K.POOL_MAX:
+        raise ValueError("pool: a list of 1..%d weight sets" % K.POOL_MAX)
+    stacked = TarokVecEnv.stack_pool(pool)
+    k, n = len(pool), int(n_games)
+    G = -(-n // 256) * 256
+    scores = _passes(k * G, episodes, _front(inspect is not None), _pool_cards(weights, stacked, G // 256, temperature, epsilon),
+                     inspect, device=device, seed=seed, mix=mix)
+    return [duplicate_advantage(pool_block_scores(scores, j, n, k)) for j in range(k)]
+
+
 def _bid_args(bidding, mix):
     if bidding is None:
         return None

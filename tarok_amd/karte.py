@@ -51,6 +51,7 @@ MLP_W1, MLP_B1, MLP_W2, MLP_B2, MLP_W3, MLP_B3, MLP_PARAMS = 0, 65536, 65792, 13
 LEARN_PAD = 256           # TAROK_LEARN_PAD: padding rows of the fused learner's activation arrays
 LEARN_MAX_BATCH = 4194048  # TAROK_LEARN_MAX_BATCH: samples per tarok_learn_dw launch (SelfPlay.update_fused splits larger minibatches)
 
+POOL_MAX = 64             # TAROK_POOL_MAX: networks in one opponent pool of tarok_policy_step_pool
 LEARN_SELECT_TILE = 2048  # TAROK_LEARN_SELECT_TILE: samples per workgroup of tarok_learn_select's scatter launch
 
 # the reference-layout observation record (include/tarok_env.h TAROK_REF_*)

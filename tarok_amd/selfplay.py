@@ -254,6 +254,15 @@ class SelfPlay:
     nothing else.  learner_seats: an int 0..15 (one seat set for every slot) or a [N] uint8 tensor of sets; default:
     slot g owns the single seat (game_offset + g) % 4, so a sharded run seats the same games the same way.
     set_opponent() swaps the opponent's weights without a new graph capture.
+    opponent=[snapshot, ...] (a list or tuple of 1..64 snapshots): a POOL of K frozen opponents in the same rollout
+    (tarok_policy_step_pool, still one launch per lock-step in the one captured graph).  The object owns the six stacked
+    tensors and a group_net tensor: step group g (slots 256 g .. 256 g + 255 of this env) meets opponent g % K, game after
+    game.  self_play_groups = f in [0, 1] mixes plain self-play in: with P = max(1, round(1 / f)) every group with
+    g % P == 0 plays the learner on all four seats instead (pool index K; its slots' learner sets become 15, so all four
+    seats learn); the other groups keep opponent g % K; f = 0 (the default): no such group.  set_opponent(w, index=k)
+    overwrites entry k in place.  iterate() adds learner_mean_score_by_opponent (K floats: learner_mean_score over the
+    slots of each opponent's groups) and, with self-play groups, learner_mean_score_self.  A pool of K copies of one
+    snapshot trains to the bits of opponent=snapshot.
 
     teacher = dict(worlds=W, samples=S, tau=tau, every=k, salt=...): learn from the playout teacher as well (expert
     iteration).  Before the policy launch of every k-th lock-step (every: default 1) the rollout runs one playout launch
@@ -279,9 +288,16 @@ class SelfPlay:
 
     def __init__(self, env, hidden=256, lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.01, reward_scale=1.0 / 70.0, seed=0,
                  use_graph=True, fused=None, fused_loss=None, fused_step=None, fused_learner=None, max_grad_norm=1.0,
-                 gamma=None, gae_lambda=None, opponent=None, learner_seats=None, teacher=None, distill_coef=0.0):
+                 gamma=None, gae_lambda=None, opponent=None, learner_seats=None, teacher=None, distill_coef=0.0,
+                 self_play_groups=0.0):
         if opponent is None and learner_seats is not None:
             raise ValueError("learner_seats says which seats learn against an opponent: pass opponent= (a snapshot()) as well")
+        pool = self.is_pool(opponent)
+        if pool and not 1 <= len(opponent) <= K.POOL_MAX:
+            raise ValueError("opponent: a pool holds 1..%d snapshots, got %d" % (K.POOL_MAX, len(opponent)))
+        if self_play_groups and not pool:
+            raise ValueError("self_play_groups mixes plain self-play into an opponent POOL: pass opponent=[snapshot, ...] as well")
+        self.pool_period(self_play_groups)            # (a ValueError outside 0..1)
         if opponent is not None:
             is_fused = (hidden == 256) if fused is None else bool(fused)
             if not is_fused or not (is_fused if fused_step is None else bool(fused_step)):
@@ -373,9 +389,17 @@ class SelfPlay:
         self._w = None                                # rollout copies of the weights (bf16) / biases (f32)
         # opponent mode: copies of the opponent's six tensors that belong to this object (the captured rollout reads them,
         # set_opponent writes them, no update ever does) and the learner's seat set of every slot
-        self._opp, self._seats = None, None
+        # pool mode: _opp is the six STACKED tensors of the K opponents (tarok_policy_step_pool), _group_net the index of
+        # every step group, K for a self-play group
+        self._opp, self._seats, self._pool_k, self._group_net = None, None, 0, None
         if opponent is not None:
-            self._opp = [t.detach().to(self.device).clone().contiguous() for t in env.check_mlp_weights(opponent)]
+            if pool:
+                self._pool_k = len(opponent)
+                self._opp = [t.to(self.device) for t in env.stack_pool(opponent)]
+                index = self.pool_group_net((env.n + 255) // 256, self._pool_k, self_play_groups)
+                self._group_net = torch.tensor(index, dtype=torch.uint8, device=self.device)
+            else:
+                self._opp = [t.detach().to(self.device).clone().contiguous() for t in env.check_mlp_weights(opponent)]
             if learner_seats is None:
                 learner_seats = (1 << ((torch.arange(env.n, dtype=torch.int64) + env.game_offset) % 4)).to(torch.uint8)
             elif not torch.is_tensor(learner_seats):
@@ -383,7 +407,10 @@ class SelfPlay:
             if learner_seats.dtype != torch.uint8 or tuple(learner_seats.shape) != (env.n,):
                 raise ValueError("learner_seats: a seat set 0..15 or a [N] uint8 tensor of sets")
             self._seats = learner_seats.detach().to(self.device).clone().contiguous()
-        self._learn = None                            # the fused learner's buffers
+            if pool:                                  # a self-play group's four seats are all the learner's
+                own = (self._group_net.long() >= self._pool_k).repeat_interleave(256)[:env.n]
+                self._seats[own] = 15
+        self._learn = None                           # the fused learner's buffers
         if self.fused_learner:
             dev = self.device
             bf = lambda k: torch.empty(k, dtype=torch.bfloat16, device=dev)
@@ -429,12 +456,43 @@ class SelfPlay:
             self._refresh_rollout_weights()
         return tuple(t.detach().clone().contiguous() for t in self._w)
 
+    @staticmethod
+    def is_pool(opponent):
+        """opponent= is a POOL when it is a list or tuple whose entries are not tensors (snapshots, or nothing at all); a
+        single snapshot — six tensors — is today's one frozen opponent."""
+        return isinstance(opponent, (list, tuple)) and not (len(opponent) and torch.is_tensor(opponent[0]))
+
+    @staticmethod
+    def pool_period(self_play_groups):
+        """self_play_groups = f in [0, 1] -> the period P of the self-play groups: 0 (none) for f = 0, else
+        max(1, round(1 / f)) — every P-th step group plays itself."""
+        f = float(self_play_groups)
+        if not 0.0 <= f <= 1.0:
+            raise ValueError("self_play_groups: the share of step groups that play plain self-play, 0..1")
+        return 0 if f == 0.0 else max(1, round(1.0 / f))
+
+    @staticmethod
+    def pool_group_net(groups, k, self_play_groups=0.0):
+        """The pool index of every step group (group g = slots 256 g .. 256 g + 255), a list of `groups` ints: g % k,
+        except that with P = pool_period(self_play_groups) > 0 every group with g % P == 0 gets k — the learner itself."""
+        period = SelfPlay.pool_period(self_play_groups)
+        return [k if period and g % period == 0 else g % k for g in range(groups)]
+
     @torch.no_grad()
-    def set_opponent(self, weights):
+    def set_opponent(self, weights, index=None):
         """Replace the frozen opponent by `weights` (a snapshot()): copied IN PLACE into the tensors the captured rollout
-        graph reads, so the next collect() plays the new opponent without a new capture."""
+        graph reads, so the next collect() plays the new opponent without a new capture.  With a pool: entry `index`
+        (required) of it."""
         if self._opp is None:
             raise RuntimeError("set_opponent() needs a SelfPlay made with opponent=")
+        if self._pool_k:
+            if index is None or not 0 <= int(index) < self._pool_k:
+                raise ValueError("set_opponent() on a pool of %d needs index=0..%d" % (self._pool_k, self._pool_k - 1))
+            for dst, src in zip(self._opp, self.env.check_mlp_weights(weights)):
+                dst[int(index)].copy_(src)
+            return
+        if index is not None:
+            raise ValueError("set_opponent(index=) names an entry of an opponent pool: this SelfPlay has one opponent")
         for dst, src in zip(self._opp, self.env.check_mlp_weights(weights)):
             dst.copy_(src)
 
@@ -448,7 +506,8 @@ class SelfPlay:
         one run are comparable from call to call, and ranks holding the same weights return the same numbers —
         averaging them over ranks adds nothing.
         opponent (a snapshot()): points per game against that network instead (evaluate.evaluate_vs_policy: `bot_mean`
-        is then the opponent's mean), on the same deals.
+        is then the opponent's mean), on the same deals.  A LIST of snapshots: a list of such dicts, one per opponent,
+        from one env that plays them all at once (evaluate.evaluate_vs_pool).
         greedy=True plays the network's best card (temperature 0) instead of a draw from its softmax, temperature a
         tempered draw, epsilon the Bot's card with that probability (TarokVecEnv.set_play_mode, on the evaluation's env
         only: the rollout keeps sampling at (1, 0)).
@@ -499,6 +558,10 @@ class SelfPlay:
         from .evaluate import evaluate_vs_bot, evaluate_vs_policy
         if self._w is None or not self.fused_learner:
             self._refresh_rollout_weights()
+        if self.is_pool(opponent):                    # a list of snapshots: one dict per opponent, one launch per lock-step
+            from .evaluate import evaluate_vs_pool
+            return evaluate_vs_pool(self._w, opponent, n_games, episodes, mix=mix, device=self.env.device_index,
+                                    temperature=temperature, epsilon=epsilon)
         if opponent is not None:
             return evaluate_vs_policy(self._w, opponent, n_games, episodes, mix=mix, device=self.env.device_index,
                                       temperature=temperature, epsilon=epsilon)
@@ -560,6 +623,11 @@ class SelfPlay:
         for t in range(T):
             if self.teacher is not None and t % self.teacher["every"] == 0:
                 self._teach(t)
+            if self._pool_k:                          # ... the others their step group's entry of the frozen pool
+                env.policy_step(w, buf["words"][t], buf["words"][t + 1], buf["act"][t], buf["logp"][t], buf["val"][t],
+                                feature_words_out=buf["obs"][t], reward_out=buf["reward"][t], done_out=buf["done"][t],
+                                opponent_pool=self._opp, group_net=self._group_net, seats_per_game=self._seats)
+                continue
             if self._opp is not None:                 # the learner's seats play w, the others the frozen opponent
                 env.policy_step(w, buf["words"][t], buf["words"][t + 1], buf["act"][t], buf["logp"][t], buf["val"][t],
                                 feature_words_out=buf["obs"][t], reward_out=buf["reward"][t], done_out=buf["done"][t],
@@ -828,4 +896,14 @@ class SelfPlay:
             mine = ((self._seats.long().unsqueeze(-1) >> torch.arange(4, device=self.device)) & 1).float()      # [N,4]
             w = buf["done"].float().unsqueeze(-1) * mine
             stats["learner_mean_score"] = float((buf["reward"].float() * w).sum() / w.sum().clamp(min=1))
+            if self._pool_k:                          # ... and the same mean over the slots of each opponent's step groups
+                k = self._pool_k
+                net = self._group_net.long().clamp(max=k).repeat_interleave(256)[:self.env.n]              # [N], k = self
+                zero = lambda: torch.zeros(k + 1, dtype=torch.float64, device=self.device)     # (integer sums: exact)
+                num = zero().index_add_(0, net, (buf["reward"].double() * w.double()).sum((0, 2)))
+                den = zero().index_add_(0, net, w.double().sum((0, 2)))
+                mean = (num / den.clamp(min=1)).tolist()
+                stats["learner_mean_score_by_opponent"] = mean[:k]
+                if bool((self._group_net >= k).any()):
+                    stats["learner_mean_score_self"] = mean[k]
         return stats
