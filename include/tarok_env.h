@@ -613,6 +613,51 @@ int tarok_exchange_values(tarok_env *env, const void *w1, const float *b1, const
 int tarok_exchange_candidates(tarok_env *env, int discard_sets, uint64_t salt, int seats, const uint8_t *seats_per_game,
                               uint8_t *cand_out, void *stream);
 
+/* The bid and exchange heads on the games TAROK_AUTO_RESET deals ahead.  A slot keeps its next
+ * TAROK_GAMES_AHEAD games in next-game lines, each dealt, bid (the Bot's round of the env's mix) and exchanged (the Bot's)
+ * by a refill.  This call decides the front of every such game again that has not been fronted yet, in the lines, between
+ * two step launches: stream-ordered, capturable, nothing allocated, no host read.
+ *   Lines taken.  Line b of slot j (j < N) iff its episode tag nep lies in (episode[j], episode[j] + TAROK_GAMES_AHEAD] with
+ *     nep % TAROK_GAMES_AHEAD == b — the line is valid now, not one waiting on a refill list — and its front mark (a u32
+ *     at byte 44 of the 64-byte line, which no step kernel reads and no deal writes) differs from nep.  tarok_reset clears
+ *     the marks; a line dealt again carries another episode.
+ *   What is written, with key = game_key(seed, offset + j, nep) (the line's own key):
+ *     the deal of key;
+ *     with bid weights: the round of tarok_bid_round (pass_value != 0: tarok_bid_round_pass) under key, whose seats in
+ *       the slot's set (seats, or seats_per_game[j] & 15) answer from tarok_bid_values[_pass]' values of that deal at
+ *       (scale, contracts), held against threshold (margin) `margin` at `playouts`; the other seats are Bots.  Without:
+ *       the env's mix under key, as the line had it;
+ *     the game set up for episode nep;
+ *     where the contract has an exchange: with exchange weights and the declarer in the set, tarok_exchange_values'
+ *       choice and discards, applied; else the Bot's exchange under key;
+ *     the line's two packed pairs, and the mark = nep.  Key and tag keep their bytes.
+ *   With the empty set (seats = 0, no seats_per_game) every line taken keeps its first 44 bytes and gains the mark.
+ *   A line on a pending refill list has a stale tag and is skipped: the refill deals it unfronted, the next call takes it.
+ *   A slot that runs out of lines deals in place, the Bot's front.  With one-card launches (tarok_policy_step*) a line
+ *   dealt after a call belongs to a game at least thirteen games ahead: a call every 48 launches or oftener leaves no game
+ *   to start unfronted.
+ *   count_out [1] i64 (device, may be NULL): the lines this call fronted; contract_hist_out [10] i64 (device, may be
+ *   NULL): their contracts.  scratch: tarok_front_lines_scratch_bytes(N) bytes of device memory, 16-byte aligned, contents
+ *   irrelevant before and after (8-byte items behind a 128-byte header: the lines taken, compacted; the count stays on
+ *   the device).  Up to five launches.
+ * TAROK_EINVAL (before any HIP call) for a NULL env, a weight set given in part, both sets NULL, bid weights with scale
+ * outside (0, 2^20], playouts < 1, contracts outside 1..TAROK_BID_ALL_CONTRACTS or an env whose mix is not TAROK_MIX_BOT
+ * (the exchange weights alone go with any mix), seats outside 0..15, scratch NULL or scratch_bytes too small. */
+int64_t tarok_front_lines_scratch_bytes(int64_t n_games);
+int tarok_front_lines(tarok_env *env, const void *bid_w1, const float *bid_b1, const void *bid_w2, const float *bid_b2,
+                      const void *bid_w3, const float *bid_b3, float scale, int playouts, int margin, int contracts,
+                      int pass_value, const void *exchange_w1, const float *exchange_b1, const void *exchange_w2,
+                      const float *exchange_b2, const void *exchange_w3, const float *exchange_b3, int seats,
+                      const uint8_t *seats_per_game, void *scratch, int64_t scratch_bytes, int64_t *count_out,
+                      int64_t *contract_hist_out, void *stream);
+
+/* The next-game lines as they stand: what the tests of tarok_front_lines compare and what a checkpoint of a fronted env
+ * holds beside tarok_get_state.  Read-only, stream-ordered; either output may be NULL.
+ *   lines_out [N, TAROK_GAMES_AHEAD, 6] u64: the line's four packed words, its key, and nep | (u64)mark << 32.
+ *   lanes_out [10, N * TAROK_GAMES_AHEAD] u64: the line's game as tarok_get_state's lanes (line t = j * TAROK_GAMES_AHEAD + b);
+ *     meaningful for a line whose tag is valid. */
+int tarok_get_lines(tarok_env *env, uint64_t *lines_out, uint64_t *lanes_out, void *stream);
+
 /* A playout launch's sums as a teacher's target distribution: one row of 64 bf16 per game, for the learner's distillation
  * term (tarok_learn_chain_distill).  Per game g the kernel reads obs[g], the observation word the playouts started from:
  * legal = its 54-bit mask, s = its seat bits, nl = min(popcount(legal), TAROK_PLAYOUT_RANKS).
@@ -1071,7 +1116,8 @@ int tarok_debug_stamps_sized(tarok_env *env, uint64_t *stamps, int64_t n_words);
  * descending, 2 scattered) — `reps` step launches of `kind` (0 tarok_step_random, 1 tarok_policy_random + tarok_step,
  * 2 tarok_krog_random of 4 cards, 3 of 2 cards) work them off, and every line is compared with a re-deal by a kernel
  * of its own.  report_out (host, 49 u64): [0] lines that differ, then {slot, episode, play word read / expected, seat
- * word read / expected} of the first eight. */
+ * word read / expected} of the first eight.  It expects the Bot's lines: it is not meaningful on an env whose lines
+ * tarok_front_lines has rewritten. */
 int tarok_debug_refill_selftest(tarok_env *env, int kind, int per_slot, uint32_t episode0, int order, int reps, uint64_t *report_out);
 
 /* Canonical state for parity checks / checkpoints: lanes_out [10,N] u64. */

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "tarok_env.hip")
 DEPS = [SRC, os.path.join(HERE, "csrc", "tarok_device.h"), os.path.join(HERE, "csrc", "deal_network.inc"),
-        os.path.join(HERE, "csrc", "tarok_learner.inc"),
+        os.path.join(HERE, "csrc", "tarok_learner.inc"), os.path.join(HERE, "csrc", "tarok_front.inc"),
         os.path.join(ROOT, "include", "tarok_env.h")]
 LIB_PATH = os.path.join(HERE, "libtarokenv.so")
 ARCH = "gfx950"
@@ -36,6 +36,7 @@ SYMBOLS = [
     "tarok_playout_bids_pass", "tarok_bid_round_pass", "tarok_bid_values_pass",
     "tarok_playout_net_scratch", "tarok_playout_cards_net",
     "tarok_playout_exchange_net_scratch", "tarok_playout_exchange_net", "tarok_playout_bids_net_scratch", "tarok_playout_bids_net",
+    "tarok_front_lines_scratch_bytes", "tarok_front_lines", "tarok_get_lines",
 ]
 
 
@@ -197,6 +198,10 @@ def lib():
     L.tarok_playout_targets.restype = i32; L.tarok_playout_targets.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp]
     L.tarok_learn_chain_distill.restype = i32
     L.tarok_learn_chain_distill.argtypes = [vp, i64] + [vp] * 4 + [f32] * 3 + [vp] * 17 + [vp, f32, vp, vp, vp, vp]
+    L.tarok_front_lines_scratch_bytes.restype = i64; L.tarok_front_lines_scratch_bytes.argtypes = [i64]
+    L.tarok_front_lines.restype = i32
+    L.tarok_front_lines.argtypes = [vp] + [vp] * 6 + [f32, i32, i32, i32, i32] + [vp] * 6 + [i32, vp, vp, i64, vp, vp, vp]
+    L.tarok_get_lines.restype = i32; L.tarok_get_lines.argtypes = [vp, vp, vp, vp]
     L.tarok_debug_stamps.restype = i32; L.tarok_debug_stamps.argtypes = [vp, vp]
     L.tarok_debug_stamps_sized.restype = i32; L.tarok_debug_stamps_sized.argtypes = [vp, vp, i64]
     L.tarok_debug_refill_selftest.restype = i32; L.tarok_debug_refill_selftest.argtypes = [vp, i32, i32, u32, i32, i32, vp]

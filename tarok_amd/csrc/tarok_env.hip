@@ -180,7 +180,7 @@ TK_KERNEL(TK_BLOCK, 80) void k_reset(
     u64 h0 = 0, h1 = 0, h2 = 0, h3 = 0, tal = 0;
     bool bad = false;
 #pragma unroll
-    for (int b = 0; b < TK_AHEAD; b++) aux[i].line[b].nep = 0xFFFFFFFFu;   // all next-game lines: empty
+    for (int b = 0; b < TK_AHEAD; b++) { aux[i].line[b].nep = 0xFFFFFFFFu; aux[i].line[b].pad[0] = 0; }   // all next-game lines: empty, no front mark (tarok_front_lines; episode 0 is never dealt ahead)
     nstale[i] = (uint16_t)((1u << TK_AHEAD) - 1);
     if (deals) {
         const uint8_t *p = deals + i * 54;
@@ -3856,22 +3856,17 @@ TK_KERNEL(TK_BLOCK, 64) void k_counters(int64_t n, const Counters *__restrict__ 
     if (score_sum) score_sum[i] = cnt[i].score_sum;
 }
 
-// canonical lanes for parity checks: H0-3, P0-3, TAL, META (tarok_env.h)
-TK_KERNEL(TK_BLOCK, 64) void k_get_state(int64_t n, const ulonglong2 *__restrict__ s01,
-                                                       const ulonglong2 *__restrict__ s23, u64 *__restrict__ out) {
-    TK_VGPR_TOP(64, 63);
-    int64_t i = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    Game g;
-    load_game(g, s01, s23, i);
+// canonical lanes for parity checks: H0-3, P0-3, TAL, META (tarok_env.h); store(lane, value) takes the ten of one game
+template <class Store>
+__device__ __forceinline__ void state_lanes(const Game &g, Store store) {
     u64 on_table = 0;
     for (u32 j = 0; j < g.nt; j++) on_table |= 1ULL << ((g.trick >> (6 * j)) & 63);
     u64 won = g.C & ~talon_unowned(g) & ~on_table;
     for (u32 s = 0; s < 4; s++) {
-        out[(int64_t)s * n + i] = hand_of(g, s);
-        out[(int64_t)(4 + s) * n + i] = seat_cards(g, s) & won;
+        store((int)s, hand_of(g, s));
+        store((int)(4 + s), seat_cards(g, s) & won);
     }
-    out[8 * n + i] = g.talon;
+    store(8, g.talon);
     u64 m = g.trick;
     m |= (u64)g.nt << 24;
     m |= (u64)g.leader << 27;
@@ -3884,7 +3879,17 @@ TK_KERNEL(TK_BLOCK, 64) void k_get_state(int64_t n, const ulonglong2 *__restrict
     m |= (u64)(has_exchange(g.contract) ? g.tl : 7) << 49;
     m |= (u64)g.phase << 52;
     m |= (u64)g.error << 54;
-    out[9 * n + i] = m;
+    store(9, m);
+}
+
+TK_KERNEL(TK_BLOCK, 64) void k_get_state(int64_t n, const ulonglong2 *__restrict__ s01,
+                                                       const ulonglong2 *__restrict__ s23, u64 *__restrict__ out) {
+    TK_VGPR_TOP(64, 63);
+    int64_t i = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    Game g;
+    load_game(g, s01, s23, i);
+    state_lanes(g, [&](int lane, u64 v) { out[(int64_t)lane * n + i] = v; });
 }
 
 // inverse of k_get_state: rebuild the packed pairs from canonical lanes (checkpoint restore,
@@ -3934,6 +3939,8 @@ TK_KERNEL(TK_BLOCK, 64) void k_set_state(int64_t n, const u64 *__restrict__ in,
     g.C = piles | on_table | unowned;
     store_game(g, s01, s23, i);
 }
+
+#include "tarok_front.inc"
 
 
 // ---------------------------------------------------------------------------
@@ -4648,6 +4655,63 @@ int tarok_exchange_candidates(tarok_env *e, int discard_sets, uint64_t salt, int
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_exchange_candidates, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
                        (u32)discard_sets, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, cand_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int64_t tarok_front_lines_scratch_bytes(int64_t n_games) {
+    if (n_games <= 0 || n_games > (1LL << 31)) return TAROK_EINVAL;
+    return TK_FRONT_HEAD_BYTES + n_games * TK_AHEAD * (int64_t)sizeof(u64);
+}
+
+int tarok_front_lines(tarok_env *e, const void *bw1, const float *bb1, const void *bw2, const float *bb2, const void *bw3,
+                      const float *bb3, float scale, int playouts, int margin, int contracts, int pass_value, const void *xw1,
+                      const float *xb1, const void *xw2, const float *xb2, const void *xw3, const float *xb3, int seats,
+                      const uint8_t *seats_per_game, void *scratch, int64_t scratch_bytes, int64_t *count_out,
+                      int64_t *contract_hist_out, void *stream) {
+    if (!e) return TAROK_EINVAL;
+    const int nb = !!bw1 + !!bb1 + !!bw2 + !!bb2 + !!bw3 + !!bb3, nx = !!xw1 + !!xb1 + !!xw2 + !!xb2 + !!xw3 + !!xb3;
+    if ((nb != 0 && nb != 6) || (nx != 0 && nx != 6) || nb + nx == 0) return TAROK_EINVAL;
+    if (nb && (!(scale > 0.f) || scale > 1048576.f || playouts < 1 || contracts < 1 || contracts > TAROK_BID_ALL_CONTRACTS ||
+               e->mix != TAROK_MIX_BOT))
+        return TAROK_EINVAL;
+    if (seats < 0 || seats > 15 || !scratch || scratch_bytes < tarok_front_lines_scratch_bytes(e->n)) return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long *count = reinterpret_cast<unsigned long long *>(scratch);
+    u64 *items = reinterpret_cast<u64 *>((char *)scratch + TK_FRONT_HEAD_BYTES);
+    const int64_t cap = e->n * TK_AHEAD;
+    hipLaunchKernelGGL(k_front_zero, dim3(1), dim3(64), 0, s, count, reinterpret_cast<unsigned long long *>(contract_hist_out));
+    hipLaunchKernelGGL(k_front_select, grid_for(e->n), dim3(TK_BLOCK), 0, s, e->n, e->aux, e->cnt, count, items, cap);
+    if (nb) {
+        const dim3 grid((unsigned)((cap + PM_M / 4 - 1) / (PM_M / 4)));
+#define TK_LAUNCH_FRONT_BID(P)                                                                                                \
+        hipLaunchKernelGGL(k_front_bid<P>, grid, dim3(TK_BLOCK), 0, s, e->n, e->aux, count, items, (const __bf16 *)bw1, bb1,       \
+                           (const __bf16 *)bw2, bb2, (const __bf16 *)bw3, bb3, scale, playouts, margin, (u32)contracts, (u32)seats, \
+                           seats_per_game, nx ? 1 : 0)
+        if (pass_value) TK_LAUNCH_FRONT_BID(true); else TK_LAUNCH_FRONT_BID(false);
+#undef TK_LAUNCH_FRONT_BID
+    }
+    if (nx) {
+        const dim3 grid((unsigned)((cap + PM_M / 8 - 1) / (PM_M / 8)));
+#define TK_LAUNCH_FRONT_EXCHANGE(F)                                                                                           \
+        hipLaunchKernelGGL(k_front_exchange<F>, grid, dim3(TK_BLOCK), 0, s, e->n, e->mix, e->aux, count, items, (const __bf16 *)xw1, \
+                           xb1, (const __bf16 *)xw2, xb2, (const __bf16 *)xw3, xb3, (u32)seats, seats_per_game)
+        if (nb) TK_LAUNCH_FRONT_EXCHANGE(true); else TK_LAUNCH_FRONT_EXCHANGE(false);
+#undef TK_LAUNCH_FRONT_EXCHANGE
+    }
+    hipLaunchKernelGGL(k_front_mark, dim3((unsigned)((cap + TK_BLOCK - 1) / TK_BLOCK)), dim3(TK_BLOCK), 0, s, e->n, e->aux, count, items,
+                       count_out, reinterpret_cast<unsigned long long *>(contract_hist_out));
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int tarok_get_lines(tarok_env *e, uint64_t *lines_out, uint64_t *lanes_out, void *stream) {
+    if (!e) return TAROK_EINVAL;
+    if (!lines_out && !lanes_out) return TAROK_OK;
+    HIPCHK(hipSetDevice(e->device));
+    hipLaunchKernelGGL(k_get_lines, grid_for(e->n * TK_AHEAD), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->aux, (u64 *)lines_out,
+                       (u64 *)lanes_out);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }

@@ -602,6 +602,65 @@ class TarokVecEnv:
             return choice_out, discards_out
         return choice_out, discards_out, raw_out, fw_out
 
+    def front_lines_scratch(self):
+        """The scratch tensor of front_lines (uint8, tarok_front_lines_scratch_bytes), cached on the env: a caller that
+        captures the call asks for it BEFORE the capture."""
+        return self._front_net_scratch(("front_lines",), lambda h, n: self.L.tarok_front_lines_scratch_bytes(n), self.n)
+
+    def front_lines(self, bid=None, exchange=None, scale=None, contracts=K.BID_DEFAULT_CONTRACTS, margin=0, pass_value=False, seats=15,
+                    seats_per_game=None, count_out=None, hist_out=None, playouts=1):
+        """The bid and exchange heads on the games auto-reset has dealt ahead (tarok_front_lines): every next-game line
+        that is valid now and has not been fronted yet is decided again in place — the deal of its key, the bidding round
+        of bid_round(pass_value=) with the seats of `seats` / `seats_per_game` answering from bid_values(bid, scale,
+        contracts)' values at threshold `margin` and `playouts` (BidLearner.round's: scale = learner.scale, playouts =
+        learner.playouts_equiv), the game set up, and exchange_values(exchange)' choice and discards applied where the
+        declarer is in the set (the Bot's exchange elsewhere) — and marked.  bid, exchange: six tensors each as policy_mlp
+        takes them, read when the launches run; one of the two may be None (bid=None keeps the env's own contracts, and
+        only then may the env's mix be another than K.MIX_BOT).  With the empty set the lines keep their bytes and gain
+        the mark.  Stream-ordered and capturable between two step launches; lines on a pending refill list are left to
+        the next call.  count_out [1] int64 / hist_out [10] int64 device tensors, if given, receive the number of lines
+        fronted by this call and their contracts.  Returns (count_out, hist_out)."""
+        if bid is None and exchange is None:
+            raise ValueError("front_lines: give bid= or exchange= (six tensors as policy_mlp takes them), or both")
+        if not 0 <= int(seats) <= 15:
+            raise ValueError("seats: a 4-bit seat set, 0..15")
+        none = (None,) * 6
+        b = none
+        if bid is not None:
+            if scale is None or not 0.0 < float(scale) <= 2.0 ** 20:
+                raise ValueError("front_lines: bid= needs bid_values' scale, 0 < scale <= 2**20")
+            if not 1 <= int(contracts) <= K.BID_ALL_CONTRACTS:
+                raise ValueError("contracts: a bit set within 1..0x3FF")
+            if int(playouts) < 1:
+                raise ValueError("playouts: >= 1")
+            if self.mix != K.MIX_BOT:
+                raise ValueError("front_lines: bid= re-bids K.MIX_BOT's round: the env's mix must be K.MIX_BOT")
+            b = self.check_mlp_weights(bid)
+        x = none if exchange is None else self.check_mlp_weights(exchange)
+        spg = self._seat_sets(seats_per_game)
+        for name, t, k in (("count_out", count_out, 1), ("hist_out", hist_out, 10)):
+            if t is not None and not (torch.is_tensor(t) and t.device == self.device and t.dtype == torch.int64 and t.is_contiguous()
+                                      and t.numel() == k):
+                raise ValueError("%s: a contiguous int64 tensor of %d on the env's device" % (name, k))
+        scratch = self.front_lines_scratch()
+        with torch.cuda.device(self.device):
+            _native.check(self.L.tarok_front_lines(self._h, *[self._p(t) for t in b], float(scale) if bid is not None else 1.0,
+                                                   int(playouts), int(margin), int(contracts), int(bool(pass_value)),
+                                                   *[self._p(t) for t in x], int(seats), self._p(spg), self._p(scratch),
+                                                   scratch.numel(), self._p(count_out), self._p(hist_out), self._stream()))
+        return count_out, hist_out
+
+    def get_lines(self, lanes=False):
+        """The next-game lines (tarok_get_lines): a [N, K.GAMES_AHEAD, 6] uint64 numpy array — a line's four packed words,
+        its key, and episode tag | front mark << 32.  lanes=True: (lines, lanes [10, N, K.GAMES_AHEAD] uint64), each line's
+        game as state()'s ten lanes (meaningful where the tag is valid)."""
+        with torch.cuda.device(self.device):
+            out = torch.empty((self.n, K.GAMES_AHEAD, 6), dtype=torch.int64, device=self.device)
+            lan = torch.empty((10, self.n, K.GAMES_AHEAD), dtype=torch.int64, device=self.device) if lanes else None
+            _native.check(self.L.tarok_get_lines(self._h, self._p(out), self._p(lan), self._stream()))
+        lines = out.cpu().numpy().view("uint64")
+        return (lines, lan.cpu().numpy().view("uint64")) if lanes else lines
+
     def exchange_candidates(self, discard_sets=4, salt=0, seats=15, seats_per_game=None):
         """The cards playout_exchange()'s candidates laid down (tarok_exchange_candidates): [N, 6 * discard_sets, 3] uint8,
         row i * discard_sets + d the discards of candidate (i, d) of a launch with the same discard_sets, salt and seat set

@@ -284,12 +284,22 @@ class SelfPlay:
     of net_seats greedy, the others the Bot — so the teacher improves with its student.  One playout per
     (card, world): `samples` is optional and must be 1; tarok_playout_targets divides by W.  Not together with voids or
     hidden; needs the fused policy (hidden = 256).  The launch's scratch is allocated before the rollout is captured, and
-    a replayed graph reads the weights in place.  The launch is costly: `every` matters."""
+    a replayed graph reads the weights in place.  The launch is costly: `every` matters.
+
+    front = dict(bid=, exchange=, contracts=, margin=, pass_value=, every=1): the games auto-reset swaps in are bid and
+    exchanged by the heads instead of the Bot (TarokVecEnv.front_lines).  bid / exchange: six tensors each
+    (read in place) or a BidLearner / ExchangeLearner (its network, copied in place at the head of every rollout).  The
+    run's first games go through bid_values -> bid_round -> reset(defer_exchange=True) -> exchange_values -> exchange, then
+    prefetch and front_lines; every rollout then opens with one front_lines call inside the captured graph (every = k > 1:
+    before every k-th rollout, outside it).  The heads sit on the learner's seats in opponent and pool mode and on all four
+    in self-play.  T * every may not exceed FRONT_MAX_T = 48.  iterate() adds `fronted` (lines the rollout's call decided)
+    and `front_contract_share` (ten shares).  front=None: the launches are the ones issued without it."""
 
     def __init__(self, env, hidden=256, lr=3e-4, clip=0.2, vf_coef=0.5, ent_coef=0.01, reward_scale=1.0 / 70.0, seed=0,
                  use_graph=True, fused=None, fused_loss=None, fused_step=None, fused_learner=None, max_grad_norm=1.0,
                  gamma=None, gae_lambda=None, opponent=None, learner_seats=None, teacher=None, distill_coef=0.0,
-                 self_play_groups=0.0):
+                 self_play_groups=0.0, front=None):
+        self.front = self.check_front(front, env)
         if opponent is None and learner_seats is not None:
             raise ValueError("learner_seats says which seats learn against an opponent: pass opponent= (a snapshot()) as well")
         pool = self.is_pool(opponent)
@@ -410,6 +420,13 @@ class SelfPlay:
             if pool:                                  # a self-play group's four seats are all the learner's
                 own = (self._group_net.long() >= self._pool_k).repeat_interleave(256)[:env.n]
                 self._seats[own] = 15
+        if self.front is not None:                    # the first games through the heads' existing chain, the lines behind them
+            self._front_w = {k: ([t.detach().clone().contiguous() for t in self.front[k].weights()] if hasattr(self.front[k], "weights")
+                                 else self.front[k]) for k in ("bid", "exchange")}
+            self._front_count = torch.zeros(1, dtype=torch.int64, device=self.device)
+            self._front_hist = torch.zeros(10, dtype=torch.int64, device=self.device)
+            self._front_total = torch.zeros(11, dtype=torch.int64, device=self.device)     # lines and contracts over a rollout
+            self.obs_words = self._front_start().words.clone()
         self._learn = None                           # the fused learner's buffers
         if self.fused_learner:
             dev = self.device
@@ -425,6 +442,81 @@ class SelfPlay:
             # the rollout reads the learner's own copies: fragment-order weights, biases inside the flat vector
             self._w = [self._wf["w1"].view(256, 256), sl(K.MLP_B1, 256), self._wf["w2"].view(256, 256), sl(K.MLP_B2, 256),
                        self._wf["w3"].view(64, 256), sl(K.MLP_B3, 64)]
+
+    FRONT_MAX_T = 48          # one-card launches between two front_lines calls that leave no game to start unfronted
+
+    @staticmethod
+    def check_front(front, env):
+        """front=dict(bid=, exchange=, contracts=, margin=, pass_value=, every=) as SelfPlay keeps it, or a ValueError.  bid /
+        exchange: six tensors as policy_mlp takes them (read in place by every rollout) or a BidLearner / ExchangeLearner
+        (its network, copied into tensors of this object's at the head of every rollout); a BidLearner brings its scale,
+        playouts_equiv, contracts and pass_value along (scale= / playouts= for plain tensors)."""
+        if front is None:
+            return None
+        unknown = set(front) - {"bid", "exchange", "contracts", "margin", "pass_value", "every", "scale", "playouts"}
+        if unknown:
+            raise ValueError("front: dict(bid=, exchange=, contracts=, margin=, pass_value=, every=); unknown keys %s" % sorted(unknown))
+        bid, exchange = front.get("bid"), front.get("exchange")
+        if bid is None and exchange is None:
+            raise ValueError("front: give bid= or exchange= (weights or a learner), or both")
+        learner = hasattr(bid, "weights")
+        f = dict(bid=bid, exchange=exchange, margin=int(front.get("margin", 0)), every=int(front.get("every", 1)),
+                 contracts=int(front.get("contracts", bid.contracts if learner else K.BID_DEFAULT_CONTRACTS)),
+                 pass_value=bool(front.get("pass_value", bid.pass_value if learner else False)),
+                 scale=float(front.get("scale", bid.scale if learner else 0.0)),
+                 playouts=int(front.get("playouts", bid.playouts_equiv if learner else 1)))
+        if f["every"] < 1:
+            raise ValueError("front: every >= 1 (rollouts per front_lines call)")
+        if not 1 <= f["contracts"] <= K.BID_ALL_CONTRACTS:
+            raise ValueError("front: contracts is a bit set within 1..0x3FF")
+        if bid is not None and not 0.0 < f["scale"] <= 2.0 ** 20:
+            raise ValueError("front: bid= as plain tensors needs scale= (bid_values' scale, 0 < scale <= 2**20)")
+        if f["playouts"] < 1:
+            raise ValueError("front: playouts >= 1")
+        if bid is not None and env.mix != K.MIX_BOT:
+            raise ValueError("front: bid= re-bids K.MIX_BOT's round: the env's mix must be K.MIX_BOT")
+        for k in ("bid", "exchange"):
+            if f[k] is not None and not hasattr(f[k], "weights"):
+                f[k] = env.check_mlp_weights(f[k])
+        return f
+
+    def _front_args(self):
+        f = self.front
+        return dict(bid=self._front_w["bid"], exchange=self._front_w["exchange"], scale=f["scale"] if f["bid"] is not None else None,
+                    contracts=f["contracts"], margin=f["margin"], pass_value=f["pass_value"], playouts=f["playouts"],
+                    seats=15, seats_per_game=self._seats)
+
+    @torch.no_grad()
+    def _front_refresh(self):
+        for k in ("bid", "exchange"):
+            if hasattr(self.front[k], "weights"):
+                for dst, src in zip(self._front_w[k], self.front[k].weights()):
+                    dst.copy_(src)                    # in place: the captured rollout reads these tensors
+
+    @torch.no_grad()
+    def _front_start(self):
+        """The run's first games through the heads' own chain (bid_values -> bid_round -> reset(defer_exchange=True) ->
+        exchange_values -> exchange), then prefetch and the first front_lines: returns the first observation."""
+        env, a = self.env, self._front_args()
+        sets = dict(seats=a["seats"], seats_per_game=a["seats_per_game"])
+        setup = {}
+        if a["bid"] is not None:
+            values = env.bid_values(0, a["bid"], a["scale"], contracts=a["contracts"], pass_value=a["pass_value"], **sets)
+            c, d, k = env.bid_round(0, values, a["playouts"], threshold=a["margin"], contracts=a["contracts"], pass_value=a["pass_value"], **sets)
+            setup = dict(contract=c, declarer=d, king_suit=k)
+        env.reset(0, defer_exchange=True, **setup)
+        obs = env.exchange(*env.exchange_values(a["exchange"], **sets)) if a["exchange"] is not None else env.exchange()
+        env.prefetch()
+        env.front_lines_scratch()                     # allocated here, before any capture
+        env.front_lines(**a)
+        return obs
+
+    def _front_call(self):
+        """front_lines at the head of a rollout; its count and contracts are the rollout's _front_total."""
+        self._front_refresh()
+        self.env.front_lines(count_out=self._front_count, hist_out=self._front_hist, **self._front_args())
+        self._front_total[:1].copy_(self._front_count)
+        self._front_total[1:].copy_(self._front_hist)
 
     def sync_weights(self):
         """Rebuild the kernels' bf16 fragment-order weight copies from the flat parameter vector (after loading a
@@ -657,6 +749,8 @@ class SelfPlay:
         self._refresh_rollout_weights()
         buf["reward"].zero_()
         buf["words"][0].copy_(self.obs_words)
+        if self.front is not None and self.front["every"] == 1:
+            self._front_call()
         self._rollout_body(T)
         self.obs_words.copy_(buf["words"][T])
 
@@ -666,6 +760,14 @@ class SelfPlay:
         if self._buf is None or self._T != T:
             self._alloc(T)
         buf = self._buf
+        if self.front is not None:
+            if T * self.front["every"] > self.FRONT_MAX_T:
+                raise ValueError("front: T * every = %d launches between two front_lines calls; more than %d may start a game that "
+                                 "was never fronted" % (T * self.front["every"], self.FRONT_MAX_T))
+            self._front_total.zero_()
+            self._front_rollouts = getattr(self, "_front_rollouts", 0) + 1
+            if self.front["every"] > 1 and (self._front_rollouts - 1) % self.front["every"] == 0:
+                self._front_call()                    # (outside the captured rollout: the graph is the same for every rollout)
         if not self.use_graph:
             self._collect_body(T)
             return buf
@@ -892,8 +994,12 @@ class SelfPlay:
                      rollout_steps_per_s=T * self.env.n / (t1 - t0), iteration_steps_per_s=T * self.env.n / (t2 - t0),
                      mean_score=float(buf["reward"].float().sum() / buf["done"].float().sum().clamp(min=1) / 4),
                      env_errors=int((buf["words"] < 0).any()))
+        if self.front is not None:                    # the lines the rollout's front_lines call decided, and their contracts' shares
+            tot = self._front_total.tolist()
+            stats["fronted"] = tot[0]
+            stats["front_contract_share"] = [c / max(1, tot[0]) for c in tot[1:]]
         if self._opp is not None:                     # mean final score over the learner's seats of the games that ended
-            mine = ((self._seats.long().unsqueeze(-1) >> torch.arange(4, device=self.device)) & 1).float()      # [N,4]
+            mine =((self._seats.long().unsqueeze(-1) >> torch.arange(4, device=self.device)) & 1).float()      # [N,4]
             w = buf["done"].float().unsqueeze(-1) * mine
             stats["learner_mean_score"] = float((buf["reward"].float() * w).sum() / w.sum().clamp(min=1))
             if self._pool_k:                          # ... and the same mean over the slots of each opponent's step groups
