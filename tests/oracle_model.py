@@ -48,10 +48,13 @@ def reward_row(game, reward_ref):
 class SlotModel:
     """Slot `index` of an env (seed, mix): its current game, episode number, score sums and play history."""
 
-    def __init__(self, seed, index, mix, episode=0, game=None):
+    def __init__(self, seed, index, mix, episode=0, game=None, game_of=None):
         """game: an oracle Game to play instead of the slot's synthetic one (no spec RNG key: explicit cards only,
-        no auto-reset)."""
-        self.seed, self.i, self.mix = seed, index, mix
+        no auto-reset).
+        game_of(index, episode): the game the slot starts at `episode`, as (a fresh oracle Game, its key), or None for
+        the synthetic one — a next-game line that tarok_front_lines decided again (tests/front_lines_model.py).  The key
+        is the one the line carries, S.game_key(seed, index, episode): the Bot policy's draws stay on it."""
+        self.seed, self.i, self.mix, self.game_of = seed, index, mix, game_of
         self.sum = [0, 0, 0, 0]
         self.fin = False
         self.hist = [0] * 48
@@ -62,8 +65,12 @@ class SlotModel:
 
     def new_game(self, ep):
         self.ep = ep
-        self.g = O.Game.synth(self.seed, self.i, ep, self.mix)
-        self.key = S.game_key(self.seed, self.i, ep)
+        given = None if self.game_of is None else self.game_of(self.i, ep)
+        if given is None:
+            self.g, self.key = O.Game.synth(self.seed, self.i, ep, self.mix), S.game_key(self.seed, self.i, ep)
+        else:
+            self.g, self.key = given
+            assert int(self.key) == S.game_key(self.seed, self.i, ep), "a given game plays under the key its line carries"
         self.played = 0                               # rows [0, played) of the history belong to the current game
 
     def reset(self, ep):

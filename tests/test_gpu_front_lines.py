@@ -100,11 +100,11 @@ def valid_lines(env, nep):
     return (nep > ep[:, None]) & (nep <= ep[:, None] + AHEAD) & (nep % AHEAD == b)
 
 
-def twin_chain(T, episode, kw, mix=None, n=N):
+def twin_chain(T, episode, kw, mix=None, n=N, seed=SEED, offset=OFFSET):
     """(state lanes [10, n], keys) of a twin env taken through the existing chain at `episode`."""
     from tarok_amd import karte as K
     from oracle import tarok_spec as S
-    env = T.TarokVecEnv(n, seed=SEED, mix=K.MIX_BOT if mix is None else mix, game_offset=OFFSET)
+    env = T.TarokVecEnv(n, seed=seed, mix=K.MIX_BOT if mix is None else mix, game_offset=offset)
     sets = dict(seats=kw.get("seats", 15), seats_per_game=kw.get("seats_per_game"))
     setup = {}
     if kw.get("bid") is not None:
@@ -120,7 +120,7 @@ def twin_chain(T, episode, kw, mix=None, n=N):
         env.exchange()
     lanes = env.state()
     env.close()
-    keys = np.array([S.game_key(SEED, OFFSET + j, episode) for j in range(n)], np.uint64)
+    keys = np.array([S.game_key(seed, offset + j, episode) for j in range(n)], np.uint64)
     return lanes, keys
 
 

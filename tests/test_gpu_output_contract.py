@@ -16,7 +16,9 @@ CASES is a literal table, not a cross product: tests/test_oracle_model.py checks
 of two different axes that `allowed` admits occurs in at least one case.
 
 Not covered here: the numerical side of the learned policy (tarok_policy_step's card only has to be legal; logp and
-value are not judged), and slots of the 20,077-game cases that are not modelled (guards only).
+value are not judged), and slots of the 20,077-game cases that are not modelled (guards only).  Every next-game line
+consumed here is one deal_into_buffer wrote: the same rows on lines that tarok_front_lines decided again, and the
+tarok_policy_step_seats / _versus / _pool launches, are in tests/test_gpu_front_rows.py.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_output_contract.py -m gpu -q
 """

@@ -2,6 +2,8 @@
 
   * the per-slot model (tests/oracle_model.py) against the games RECORDED FROM THE REFERENCE
     (tests/golden/traces_v1.npz): its trick, done, reward and history rows are the reference run's;
+  * its game_of hook (a slot whose next game is a given one: tests/test_gpu_front_rows.py): nothing changes without it,
+    the Bot's line reproduces the synthetic run, a fronted game (tests/front_lines_model.py) changes it;
   * the guard-band checker (tests/guarded.py) reports a flipped byte in either guard and in a padding column;
   * the case table of the GPU file covers every allowed pair of values of two different axes.
 """
@@ -108,6 +110,77 @@ def test_model_auto_reset_starts_the_next_game_at_history_row_0():
                     assert row.obs == nxt.obs_word(True) and (row.obs >> 62) & 1 and (row.obs >> 56) & 63 == 0
                     assert m.card(None, auto=True).hist_pos == 0
             assert finished >= 3
+
+
+def _run_rows(m, cards=144, reward_ref=False):
+    """`cards` auto-reset cards of the Bot policy: every field of every row, and the model's state after each card."""
+    out = []
+    for _ in range(cards):
+        r = m.card(None, auto=True, reward_ref=reward_ref)
+        out.append((r.action, r.done, r.reward, r.trick, r.obs, r.hist_pos, r.rejected, m.ep, m.played, list(m.sum),
+                    [int(x) for x in m.g.lanes()]))
+    return out
+
+
+def test_model_without_a_hook_is_unchanged():
+    """game_of=None and a hook that always answers None: the synthetic games, row for row, and the hook is asked once
+    per game with the slot's index and the game's episode."""
+    for mix in (S.MIX_ALL, S.MIX_BOT):
+        for i in (0, 5, 9077):
+            asked = []
+            plain, hooked = SlotModel(9, i, mix), SlotModel(9, i, mix, game_of=lambda index, ep: asked.append((index, ep)))
+            assert _run_rows(plain) == _run_rows(hooked)
+            assert asked == [(i, e) for e in range(plain.ep + 1)] and plain.ep >= 3
+            assert plain.key == S.game_key(9, i, plain.ep) == hooked.key
+
+
+def test_model_hook_with_the_bot_line_is_the_synthetic_run():
+    """A hook that hands out front_lines_model.bot_line (what deal_into_buffer writes for MIX_BOT) with the line's key:
+    the run of the synthetic games, row for row, over three games and more."""
+    import front_lines_model as FM
+    for i in range(9000, 9012):
+        hook = lambda index, ep: (FM.bot_line(9, index, ep, S.MIX_BOT), S.game_key(9, index, ep)) if ep > 0 else None
+        plain, hooked = SlotModel(9, i, S.MIX_BOT), SlotModel(9, i, S.MIX_BOT, game_of=hook)
+        for reward_ref in (False, True):
+            assert _run_rows(plain, 96, reward_ref) == _run_rows(hooked, 96, reward_ref), i
+        assert plain.ep >= 3
+    with pytest.raises(AssertionError):                     # a game under another key than its line's is refused
+        SlotModel(9, 9000, S.MIX_BOT, game_of=lambda index, ep: (FM.bot_line(9, index, ep, S.MIX_BOT), S.game_key(9, index, ep + 1)))
+
+
+def test_model_hook_with_fronted_games_differs_from_the_bots():
+    """A hook that hands out front_lines_model.front_game on the integer weight sets of tests/test_front_lines_cpu.py:
+    each game starts as that game, and the run differs from the Bot's."""
+    import front_lines_model as FM
+    import test_front_lines_cpu as FC
+    bid = dict(W=FC.model_weights(1), scale=70.0, playouts=1, margin=0, contracts=0x3FF, pass_value=False)
+    Wx = FC.model_weights(2)
+    differ = 0
+    for i in (FC.GIDX, FC.GIDX + 1):
+        started = {}
+
+        def hook(index, ep):
+            if ep == 0:
+                return None
+            started[ep] = FM.front_game(FC.SEED, index, ep, 15, S.MIX_BOT, bid=bid, exchange=Wx).lanes()
+            return FM.front_game(FC.SEED, index, ep, 15, S.MIX_BOT, bid=bid, exchange=Wx), S.game_key(FC.SEED, index, ep)
+        plain, hooked = SlotModel(FC.SEED, i, S.MIX_BOT), SlotModel(FC.SEED, i, S.MIX_BOT, game_of=hook)
+        rows = []
+        for t in range(144):
+            ep = hooked.ep
+            r = hooked.card(None, auto=True)
+            rows.append(r)
+            if r.done:                                      # the finishing card's observation word describes the fronted game
+                g = O.Game.from_lanes(started[ep + 1])
+                assert hooked.ep == ep + 1 and hooked.played == 0 and (hooked.g.lanes() == started[ep + 1]).all()
+                assert r.obs == g.obs_word(True)
+        assert len(started) >= 3
+        mine = [(r.action, r.done, r.reward, r.trick, r.obs) for r in rows]
+        bots = [x[:5] for x in _run_rows(plain)]
+        first_game = next(t for t, r in enumerate(rows) if r.done)
+        assert mine[:first_game] == bots[:first_game], "episode 0 is the slot's own game under either"
+        differ += mine != bots
+    assert differ > 0
 
 
 def test_guard_checker_reports_one_flipped_byte():
