@@ -898,6 +898,32 @@ int tarok_playout_cards_net(tarok_env *env, int worlds, uint64_t salt, int seats
                             const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
                             int32_t *sum_out, uint8_t *action_out, void *stream);
 
+/* tarok_playout_cards_net in the two other fair world kinds: the network plays out worlds the table's knowledge allows.
+ * Everything is tarok_playout_cards_net's — "takes part", one playout per (legal card, world) under the same wkey and
+ * pkey, net_seats, w1 .. b3 (read when the launches RUN), scratch (tarok_playout_net_scratch(env, worlds) bytes, 16-byte
+ * aligned, contents undefined afterwards), sum_out, action_out, three launches on `stream`, nothing allocated, nothing
+ * read by the host, the env read-only — except the world that wkey deals:
+ *   tarok_playout_cards_net_voids   world w is tarok_playout_cards_voids' under voids[g]: uniform over the re-deals that
+ *                                   give no other seat a card of a class its word marks it void in (the fall-backs are
+ *                                   that launch's).  voids [N] u32 (device), tarok_shown_voids' words or the caller's
+ *                                   own; all-zero words give tarok_playout_cards_net's bytes.
+ *   tarok_playout_cards_net_hidden  world w is tarok_playout_cards_hidden's under played[g]: a Klop's face-down talon
+ *                                   and, for a mover who is not the declarer, the declarer's discards are re-dealt too.
+ *                                   played [N] u64 (device), tarok_played_cards' words.  Where nothing more is hidden the
+ *                                   bytes are tarok_playout_cards_net's.
+ * The words are an argument: the env needs no history for these calls, and they are read when the launches RUN.  Hence
+ * net_seats = 0 writes the bytes of tarok_playout_cards_voids(worlds, 1) / tarok_playout_cards_hidden(worlds, 1).  The
+ * two kinds do not compose (as for the Bot-played launches).
+ * TAROK_EINVAL (before any HIP call) for everything tarok_playout_cards_net refuses, and for a NULL word array. */
+int tarok_playout_cards_net_voids(tarok_env *env, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                                  const uint32_t *voids, int net_seats, const void *w1, const float *b1, const void *w2,
+                                  const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
+                                  int32_t *sum_out, uint8_t *action_out, void *stream);
+int tarok_playout_cards_net_hidden(tarok_env *env, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                                   const uint64_t *played, int net_seats, const void *w1, const float *b1, const void *w2,
+                                   const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
+                                   int32_t *sum_out, uint8_t *action_out, void *stream);
+
 /* Net-played playouts for the exchange and the bid: tarok_playout_exchange and tarok_playout_bids at ONE playout per
  * (candidate or option, world), played as tarok_playout_cards_net plays its playouts — the network's greedy card on the
  * absolute seats of net_seats (one launch-wide 4-bit set), the Bot's card policy_action(pkey, q, legal) on the others.

@@ -3359,16 +3359,17 @@ __global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_
 #define TK_PN_ITEM_BYTES 48
 #define TK_PN_MAX_CARDS 48
 
-// First launch: k_playout_det's worlds (the same team layout, dealer and keys), the candidate card applied, the items
-// written.  An item whose candidate ends the game is written finished; the slots of absent ranks and of games that do
-// not take part get 0.
-TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,
-                                                const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
-                                                const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
-                                                ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,
-                                                u64 *__restrict__ ires) {
-    TK_VGPR_TOP(128, 127);
-    __shared__ WorldAB world;
+// First launch: the card launches' worlds (playout_cards_body's team layout, dealers and keys: the dealer's Record in
+// LDS, its per-game word, Dealer::deal under the world key), the candidate card applied, the items written.  An item whose
+// candidate ends the game is written finished; the slots of absent ranks and of games that do not take part get 0.  A
+// hidden world's item is the packed Game whose C plane and talon ids moved: the second launch unpacks all of it.
+template <class Dealer>
+__device__ __forceinline__ void playout_net_deal_body(int64_t n, u64 pseed, u64 offset, u32 worlds, u32 lg, u32 seats,
+                                                      const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                                      const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                                      const typename Dealer::Extra *__restrict__ extra, ulonglong2 *__restrict__ i01,
+                                                      ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
+    __shared__ typename Dealer::Record world;
     const PlayoutTeam t(lg, worlds);
     const int64_t g = t.g;
     ulonglong2 a = {0, 0}, b = {0, 0};
@@ -3383,9 +3384,10 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal(int64_t n, u64 pseed /* seed ^ 
         if (p.takes_part) {
             nlegal = (u32)popc64(p.legal);
             ebase = ((u64)cnt[g].episode << 28) | ((u64)p.played << 22);
+            const typename Dealer::Extra word = game_word(extra, g);
             for (u32 w = t.lane; w < worlds; w += t.L) {
                 Game d = g0;
-                DealUnseen::deal(d, p.mover, game_key(pseed, offset + (u64)g, DealUnseen::world_tag | ebase | (u64)w), NoWord{});
+                Dealer::deal(d, p.mover, game_key(pseed, offset + (u64)g, Dealer::world_tag | ebase | (u64)w), word);
                 world.store(t.slot0 + w, d);
             }
         }
@@ -3411,12 +3413,43 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal(int64_t n, u64 pseed /* seed ^ 
                     pack(h, x0, x1, y0, y1);
                     i01[it] = make_ulonglong2(x0, x1);
                     i23[it] = make_ulonglong2(y0, y1);
-                    ikey[it] = game_key(pseed, offset + (u64)g, DealUnseen::item_tag | ebase | ((u64)c << 16) | ((u64)w << 10));
+                    ikey[it] = game_key(pseed, offset + (u64)g, Dealer::item_tag | ebase | ((u64)c << 16) | ((u64)w << 10));
                 }
             }
             ires[it] = res;
         }
     }
+}
+
+// tarok_playout_cards_net: redeal_unseen's worlds.
+TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,
+                                                const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                                const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                                ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,
+                                                u64 *__restrict__ ires) {
+    TK_VGPR_TOP(128, 127);
+    playout_net_deal_body<DealUnseen>(n, pseed, offset, worlds, lg, seats, seat_sets, s01, s23, cnt, nullptr, i01, i23, ikey, ires);
+}
+
+// tarok_playout_cards_net_voids: the worlds honour shown voids (redeal_voids under voids[g], as k_playout_voids).
+TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal_voids(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,
+                                                      const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                                      const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                                      const u32 *__restrict__ voids, ulonglong2 *__restrict__ i01,
+                                                      ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
+    TK_VGPR_TOP(128, 127);
+    playout_net_deal_body<DealVoids>(n, pseed, offset, worlds, lg, seats, seat_sets, s01, s23, cnt, voids, i01, i23, ikey, ires);
+}
+
+// tarok_playout_cards_net_hidden: the worlds also re-deal Klop's talon and the declarer's discards (redeal_hidden under
+// played[g], as k_playout_hidden; WorldABCT slots: 36 bytes x TK_PO_WORLD_SLOTS = 2,304 bytes of LDS).
+TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal_hidden(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,
+                                                       const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                                       const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                                       const u64 *__restrict__ played_words, ulonglong2 *__restrict__ i01,
+                                                       ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
+    TK_VGPR_TOP(128, 127);
+    playout_net_deal_body<DealHidden>(n, pseed, offset, worlds, lg, seats, seat_sets, s01, s23, cnt, played_words, i01, i23, ikey, ires);
 }
 
 // Second launch: the playouts.  A workgroup of 256 threads keeps one tile of PM_M = 128 items resident — their packed
@@ -4395,43 +4428,6 @@ int64_t tarok_playout_net_scratch(const tarok_env *e, int worlds) {
     return e->n * TAROK_PLAYOUT_RANKS * (int64_t)worlds * TK_PN_ITEM_BYTES;
 }
 
-// tarok_playout_cards_net: the items, the playouts, the sums — three launches on `stream`, nothing allocated.
-int tarok_playout_cards_net(tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game, int net_seats,
-                            const void *w1, const float *b1, const void *w2, const float *b2, const void *w3, const float *b3,
-                            void *scratch, int64_t scratch_bytes, int32_t *sum_out, uint8_t *action_out, void *stream) {
-    if (!playout_args_ok(e, worlds, 1, seats) || net_seats < 0 || net_seats > 15 || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 ||
-        !scratch || ((uintptr_t)scratch & 15) || scratch_bytes < tarok_playout_net_scratch(e, worlds) || (!sum_out && !action_out))
-        return TAROK_EINVAL;
-    HIPCHK(hipSetDevice(e->device));
-    const int64_t items = e->n * TAROK_PLAYOUT_RANKS * (int64_t)worlds;
-    ulonglong2 *i01 = reinterpret_cast<ulonglong2 *>(scratch), *i23 = i01 + items;
-    u64 *ikey = reinterpret_cast<u64 *>(i23 + items), *ires = ikey + items;
-    const u32 lg = playout_lg(TK_PO_MIN_LG, worlds);
-    hipLaunchKernelGGL(k_playout_net_deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
-                       (u32)worlds, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, i01, i23, ikey, ires);
-    hipLaunchKernelGGL(k_playout_net_play, dim3((unsigned)((items + PM_M - 1) / PM_M)), dim3(TK_BLOCK), 0, (hipStream_t)stream, items,
-                       (u32)net_seats, i01, i23, ikey, ires, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3);
-    hipLaunchKernelGGL(k_playout_net_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, (u32)worlds,
-                       (u32)seats, seats_per_game, e->s01, e->s23, e->gkey, ires, reinterpret_cast<int4 *>(sum_out), action_out);
-    HIPCHK(hipGetLastError());
-    return TAROK_OK;
-}
-
-int tarok_playout_exchange(tarok_env *e, int worlds, int samples, int discard_sets, uint64_t salt, int seats,
-                           const uint8_t *seats_per_game, int32_t *sum_out, int8_t *choice_out, uint8_t *discards_out, void *stream) {
-    if (!playout_args_ok(e, worlds, samples, seats) || discard_sets < 1 || discard_sets > TAROK_EXCHANGE_MAX_SETS) return TAROK_EINVAL;
-    if (!sum_out && !choice_out && !discards_out) return TAROK_OK;
-    HIPCHK(hipSetDevice(e->device));
-    // never fewer than 16 lanes per game: at most 16 teams per workgroup, whose 48 rows each are the 12 KiB the card launches use
-    static_assert(TAROK_EXCHANGE_ROWS == TK_PX_ROWS && TAROK_EXCHANGE_MAX_SETS * 6 == TK_PX_ROWS, "6 groups x 8 sets");
-    const u32 lg = playout_lg(TK_PX_MIN_LG, worlds * samples);
-    hipLaunchKernelGGL(k_playout_exchange, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
-                       (u32)worlds, (u32)samples, (u32)discard_sets, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, e->gkey,
-                       reinterpret_cast<int4 *>(sum_out), choice_out, discards_out);
-    HIPCHK(hipGetLastError());
-    return TAROK_OK;
-}
-
 extern "C++" {
 // The four item arrays of a net launch in its scratch (tarok_playout_cards_net's layout).
 struct NetItems {
@@ -4451,6 +4447,68 @@ static inline void launch_net_play(int64_t items, int net_seats, const NetItems 
                        (u32)net_seats, it.i01, it.i23, it.ikey, it.ires, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2,
                        (const __bf16 *)w3, b3);
 }
+
+// One net card launch: the items (`deal`, the dealer's kernel, with its per-game `words` where it has any), the playouts,
+// the sums — three launches on `stream`, nothing allocated.
+template <class Kernel, class... Words>
+static int launch_playout_cards_net(Kernel deal, tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                                    int net_seats, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
+                                    const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out, uint8_t *action_out,
+                                    void *stream, Words... words) {
+    if (!playout_args_ok(e, worlds, 1, seats) ||
+        !net_args_ok(net_seats, w1, b1, w2, b2, w3, b3, scratch, scratch_bytes, tarok_playout_net_scratch(e, worlds)) ||
+        (!sum_out && !action_out) || (... || !words))
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    const int64_t items = e->n * TAROK_PLAYOUT_RANKS * (int64_t)worlds;
+    const NetItems it(scratch, items);
+    const u32 lg = playout_lg(TK_PO_MIN_LG, worlds);
+    hipLaunchKernelGGL(deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
+                       (u32)worlds, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, words..., it.i01, it.i23, it.ikey, it.ires);
+    launch_net_play(items, net_seats, it, w1, b1, w2, b2, w3, b3, stream);
+    hipLaunchKernelGGL(k_playout_net_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, (u32)worlds,
+                       (u32)seats, seats_per_game, e->s01, e->s23, e->gkey, it.ires, reinterpret_cast<int4 *>(sum_out), action_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+}
+
+int tarok_playout_cards_net(tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game, int net_seats,
+                            const void *w1, const float *b1, const void *w2, const float *b2, const void *w3, const float *b3,
+                            void *scratch, int64_t scratch_bytes, int32_t *sum_out, uint8_t *action_out, void *stream) {
+    return launch_playout_cards_net(k_playout_net_deal, e, worlds, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3, scratch,
+                                    scratch_bytes, sum_out, action_out, stream);
+}
+
+int tarok_playout_cards_net_voids(tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                                  const uint32_t *voids, int net_seats, const void *w1, const float *b1, const void *w2, const float *b2,
+                                  const void *w3, const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out,
+                                  uint8_t *action_out, void *stream) {
+    return launch_playout_cards_net(k_playout_net_deal_voids, e, worlds, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3,
+                                    scratch, scratch_bytes, sum_out, action_out, stream, voids);
+}
+
+int tarok_playout_cards_net_hidden(tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                                   const uint64_t *played, int net_seats, const void *w1, const float *b1, const void *w2,
+                                   const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
+                                   int32_t *sum_out, uint8_t *action_out, void *stream) {
+    return launch_playout_cards_net(k_playout_net_deal_hidden, e, worlds, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3,
+                                    scratch, scratch_bytes, sum_out, action_out, stream, (const u64 *)played);
+}
+
+int tarok_playout_exchange(tarok_env *e, int worlds, int samples, int discard_sets, uint64_t salt, int seats,
+                           const uint8_t *seats_per_game, int32_t *sum_out, int8_t *choice_out, uint8_t *discards_out, void *stream) {
+    if (!playout_args_ok(e, worlds, samples, seats) || discard_sets < 1 || discard_sets > TAROK_EXCHANGE_MAX_SETS) return TAROK_EINVAL;
+    if (!sum_out && !choice_out && !discards_out) return TAROK_OK;
+    HIPCHK(hipSetDevice(e->device));
+    // never fewer than 16 lanes per game: at most 16 teams per workgroup, whose 48 rows each are the 12 KiB the card launches use
+    static_assert(TAROK_EXCHANGE_ROWS == TK_PX_ROWS && TAROK_EXCHANGE_MAX_SETS * 6 == TK_PX_ROWS, "6 groups x 8 sets");
+    const u32 lg = playout_lg(TK_PX_MIN_LG, worlds * samples);
+    hipLaunchKernelGGL(k_playout_exchange, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
+                       (u32)worlds, (u32)samples, (u32)discard_sets, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, e->gkey,
+                       reinterpret_cast<int4 *>(sum_out), choice_out, discards_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
 }
 
 int64_t tarok_playout_exchange_net_scratch(const tarok_env *e, int worlds, int discard_sets) {

@@ -377,27 +377,48 @@ class TarokVecEnv:
                 cache[worlds] = torch.empty(size, dtype=torch.uint8, device=self.device)
         return cache[worlds]
 
-    def playout_cards_net(self, weights, worlds, net_seats=15, salt=0, seats=15, seats_per_game=None, sum_out=None, action_out=None):
+    def playout_cards_net(self, weights, worlds, net_seats=15, salt=0, seats=15, seats_per_game=None, sum_out=None, action_out=None,
+                          voids=False, hidden=False, words=None):
         """playout_cards_det whose playouts are played by a policy network (tarok_playout_cards_net): one playout per
         (legal card, world); after the candidate card the seats of `net_seats` (a 4-bit set of absolute seats) play the
         GREEDY card of `weights` (policy_mlp's six tensors, read when the launch runs) on the playout's own position,
         the other seats the Bot's card.  The sums are over `worlds` playouts (playout_values' divisor).  net_seats=15:
         the learned policy with one ply of search on top; net_seats=0: playout_cards_det(worlds, 1) to the byte; one
         seat: a best response to a table of Bots.  Worlds, outputs, `seats` / `seats_per_game`, `salt` and the
-        read-only contract: as for playout_cards_det.  The scratch is playout_net_scratch(worlds)."""
+        read-only contract: as for playout_cards_det.  The scratch is playout_net_scratch(worlds).
+        voids=True: the worlds honour shown voids (tarok_playout_cards_net_voids on shown_voids(words)), so the network
+        never plays from a hand the table knows to be impossible; hidden=True: the worlds also re-deal Klop's face-down
+        talon and the declarer's discards (tarok_playout_cards_net_hidden on played_cards(words)).  Either needs
+        TarokVecEnv(history=True); a tensor in their place ([N] int32 / int64) is taken as the words themselves, as
+        playout_cards_voids(voids=...) takes them, and needs no history.  words: the caller's scratch tensor for the
+        env's own words (None: a new one per call), so that a captured launch allocates nothing.  Not both: the two
+        kinds do not compose.  The defaults issue tarok_playout_cards_net."""
+        given_v, given_h = (x is not None and not isinstance(x, (bool, int)) for x in (voids, hidden))   # a tensor or an array
+        want_v, want_h = given_v or bool(voids), given_h or bool(hidden)
+        if want_v and want_h:
+            raise ValueError("hidden=True is not built together with voids=True: give one of the two")
+        if (want_v and not given_v or want_h and not given_h) and not self.history:
+            raise ValueError("playout_cards_net(%s=True) goes with the play history: TarokVecEnv(history=True)"
+                             % ("voids" if want_v else "hidden"))
         if not 0 <= int(net_seats) <= 15:
             raise ValueError("net_seats: a 4-bit seat set, 0..15")
         w = self.check_mlp_weights(weights)
         scratch = self.playout_net_scratch(worlds)
+        fn, extra = self.L.tarok_playout_cards_net, ()
+        if want_v:
+            fn = self.L.tarok_playout_cards_net_voids
+            extra = (self._dev(voids if given_v else self.shown_voids(words), torch.int32, (self.n,)),)
+        elif want_h:
+            fn = self.L.tarok_playout_cards_net_hidden
+            extra = (self._dev(hidden if given_h else self.played_cards(words), torch.int64, (self.n,)),)
         with torch.cuda.device(self.device):
             if sum_out is None:
                 sum_out = torch.empty((self.n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=self.device)
             if action_out is None:
                 action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
-            _native.check(self.L.tarok_playout_cards_net(self._h, int(worlds), int(salt) & ((1 << 64) - 1), int(seats),
-                                                         self._p(self._seat_sets(seats_per_game)), int(net_seats),
-                                                         *[self._p(t) for t in w], self._p(scratch), scratch.numel(),
-                                                         self._p(sum_out), self._p(action_out), self._stream()))
+            _native.check(fn(self._h, int(worlds), int(salt) & ((1 << 64) - 1), int(seats), self._p(self._seat_sets(seats_per_game)),
+                             *[self._p(t) for t in extra], int(net_seats), *[self._p(t) for t in w], self._p(scratch),
+                             scratch.numel(), self._p(sum_out), self._p(action_out), self._stream()))
         return sum_out, action_out
 
     def playout_exchange(self, worlds, samples, discard_sets=4, salt=0, seats=15, seats_per_game=None, sum_out=None,

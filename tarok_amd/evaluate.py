@@ -345,6 +345,9 @@ def evaluate_vs_pool(weights, pool, n_games, episodes, seed=0, mix=K.MIX_BOT, de
     return [duplicate_advantage(pool_block_scores(scores, j, n, k)) for j in range(k)]
 
 
+NET_WORLDS = ("det", "voids", "hidden")           # the world kinds of the net-played card launch (net_worlds=)
+
+
 def _bid_args(bidding, mix):
     if bidding is None:
         return None
@@ -356,7 +359,7 @@ def _bid_args(bidding, mix):
 
 def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None, voids=False, exchange=None,
                     hidden=False, bidding=None, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None,
-                    net_seats=15):
+                    net_seats=15, net_worlds="det"):
     """_play_passes_mode with the Monte-Carlo player (TarokVecEnv.playout_cards) in the network's place: per lock-step
     one playout launch with the pass's seat set — tarok_playout_cards (open hands) for worlds=None,
     tarok_playout_cards_det (the fair player: `worlds` re-deals of the unseen cards) otherwise — whose action_out holds
@@ -373,7 +376,14 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     net=weights (with worlds, with nothing else): every lock-step runs tarok_playout_cards_net at `worlds` — the playouts
     are played by the network's greedy card on the seats of net_seats (a 4-bit set, or "own": the pass's seat set) and by
     the Bot elsewhere; `samples` is not taken.
+    net_worlds="voids" / "hidden" (with net): the env keeps the play history and every lock-step runs tarok_shown_voids and
+    tarok_playout_cards_net_voids / tarok_played_cards and tarok_playout_cards_net_hidden instead; "det" is the launch
+    above.  (voids=True / hidden=True together with net= keep raising: net_worlds is the way in.)
     inspect: as in _play_passes_mode."""
+    if net_worlds not in NET_WORLDS:
+        raise ValueError('net_worlds: one of "det", "voids", "hidden"')
+    if net is None and net_worlds != "det":
+        raise ValueError("net_worlds names the worlds of the network's playouts: it goes with net=weights")
     if net is not None:
         if worlds is None:
             raise ValueError("net= plays the determinized player's playouts: give worlds= as well")
@@ -395,7 +405,12 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     if bidding is not None and worlds is None:
         raise ValueError("bidding=(W, S) is the fair player's front end: give worlds= as well")
     bidding = _bid_args(bidding, mix)
-    if net is not None:
+    if net is not None and net_worlds != "det":
+        kind = {net_worlds: True}
+        cards = _playout_cards(lambda env, seats, words, sums, row: env.playout_cards_net(
+            net, worlds, net_seats=seats if net_seats == "own" else net_seats, salt=salt, seats=seats, sum_out=sums, action_out=row,
+            words=words, **kind), words_dtype=torch.int32 if net_worlds == "voids" else torch.int64)
+    elif net is not None:
         cards = _playout_cards(lambda env, seats, words, sums, row: env.playout_cards_net(
             net, worlds, net_seats=seats if net_seats == "own" else net_seats, salt=salt, seats=seats, sum_out=sums, action_out=row))
     else:
@@ -404,12 +419,13 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
             words_dtype=(torch.int32 if voids else torch.int64) if voids or hidden else None)
     front = _front(inspect is not None, bid=None if bidding is None else _bid_front(bidding, salt, threshold, contracts, pass_value),
                    exchange=None if exchange is None else _exchange_front(worlds, samples, exchange, salt))
-    return _passes(n_games, episodes, front, cards, inspect, device=device, seed=seed, mix=mix, history=bool(voids or hidden))
+    return _passes(n_games, episodes, front, cards, inspect, device=device, seed=seed, mix=mix,
+                   history=bool(voids or hidden or net_worlds != "det"))
 
 
 def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None,
                             voids=False, exchange=None, hidden=False, bidding=None, threshold=0,
-                            contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None, net_seats=15):
+                            contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None, net_seats=15, net_worlds="det"):
     """evaluate_vs_bot with the open-hand Monte-Carlo player in the network's place: a strong reference player that needs
     no training.  On its seat it plays, at every move, the legal card with the best summed score over `samples` Bot
     playouts of each legal card (tarok_playout_cards; `salt` varies their draws).  The playouts see the TRUE hidden
@@ -436,12 +452,16 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
     whose playouts are played by a policy network (tarok_playout_cards_net) — weights = policy_mlp's six tensors.  Inside
     the playouts the seats of net_seats (a 4-bit set; 15, the default: every seat) play the network's greedy card, the
     others the Bot's; net_seats="own" makes the set the player's own seat, a best response to a table of Bots.
+    net_worlds="voids" / "hidden" (with net=weights; "det", the default, is the call as it was): the network's playouts run
+    in the void-aware worlds (tarok_shown_voids, tarok_playout_cards_net_voids) or in the worlds that also re-deal Klop's
+    talon and the declarer's discards (tarok_played_cards, tarok_playout_cards_net_hidden); the env keeps the history.
+    The spellings net= with voids=True / hidden=True keep raising ValueError, as they always have: net_worlds is the way in.
     The same five duplicate passes (PASS_SEATS) on an env of its own; returns duplicate_advantage's dict, `policy_mean`
     being the playout player's.  inspect (tests): a list that receives one dict per pass, as in _play_passes_mode."""
     return duplicate_advantage(_playout_passes(samples, n_games, episodes, seed, mix, device, salt=salt, inspect=inspect,
                                                worlds=worlds, voids=voids, exchange=exchange, hidden=hidden, bidding=bidding,
                                                threshold=threshold, contracts=contracts, pass_value=pass_value, net=net,
-                                               net_seats=net_seats))
+                                               net_seats=net_seats, net_worlds=net_worlds))
 
 
 def _front_cards(cards):

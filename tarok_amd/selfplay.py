@@ -285,6 +285,12 @@ class SelfPlay:
     (card, world): `samples` is optional and must be 1; tarok_playout_targets divides by W.  Not together with voids or
     hidden; needs the fused policy (hidden = 256).  The launch's scratch is allocated before the rollout is captured, and
     a replayed graph reads the weights in place.  The launch is costly: `every` matters.
+    teacher = dict(..., net=True, net_worlds="voids" | "hidden"): the network's playouts run in the void-aware worlds
+    (tarok_shown_voids, then tarok_playout_cards_net_voids) or in the worlds that also re-deal Klop's talon and the
+    declarer's discards (tarok_played_cards, then tarok_playout_cards_net_hidden), so the net seats never answer a hand
+    the table knows to be impossible.  The words, the three launches and tarok_playout_targets are one
+    stream-ordered chain inside the captured rollout; the env must keep the play history.  "det" (the default) is the
+    launch above.  net=True with voids=True / hidden=True keeps raising, as it always has: net_worlds is the way in.
 
     front = dict(bid=, exchange=, contracts=, margin=, pass_value=, every=1): the games auto-reset swaps in are bid and
     exchanged by the heads instead of the Bot (TarokVecEnv.front_lines).  bid / exchange: six tensors each
@@ -317,15 +323,20 @@ class SelfPlay:
                 raise ValueError("learner_seats: a seat set 0..15 or a [N] uint8 tensor of sets")
         self.teacher, self.distill_coef = None, float(distill_coef)
         if teacher is not None:
-            unknown = set(teacher) - {"worlds", "samples", "tau", "every", "salt", "voids", "hidden", "net", "net_seats"}
+            unknown = set(teacher) - {"worlds", "samples", "tau", "every", "salt", "voids", "hidden", "net", "net_seats", "net_worlds"}
             net = bool(teacher.get("net", False))
             if unknown or ("samples" not in teacher and not net):
                 raise ValueError("teacher: dict(worlds=W, samples=S, tau=tau, every=k, salt=...), samples required; unknown keys %s" % sorted(unknown))
             t = dict(worlds=int(teacher.get("worlds", 0)), samples=int(teacher.get("samples", 1)), tau=float(teacher.get("tau", 1.0)),
                      every=int(teacher.get("every", 1)), salt=int(teacher.get("salt", 0)), voids=bool(teacher.get("voids", False)),
-                     hidden=bool(teacher.get("hidden", False)), net=net, net_seats=int(teacher.get("net_seats", 15)))
+                     hidden=bool(teacher.get("hidden", False)), net=net, net_seats=int(teacher.get("net_seats", 15)),
+                     net_worlds=teacher.get("net_worlds", "det"))
             if "net_seats" in teacher and not net:
                 raise ValueError("teacher: net_seats names the network's seats inside the playouts: it goes with net=True")
+            if t["net_worlds"] not in ("det", "voids", "hidden"):
+                raise ValueError('teacher: net_worlds is one of "det", "voids", "hidden"')
+            if "net_worlds" in teacher and not net:
+                raise ValueError("teacher: net_worlds names the worlds of the network's playouts: it goes with net=True")
             if net:
                 if t["samples"] != 1:
                     raise ValueError("teacher: net=True runs one playout per (card, world): samples is optional and must be 1")
@@ -337,6 +348,8 @@ class SelfPlay:
                     raise ValueError("teacher: net_seats is a 4-bit seat set, 0..15")
                 if not ((hidden == 256) if fused is None else bool(fused)):
                     raise ValueError("teacher: net=True plays tarok_playout_cards_net, which needs the fused policy (hidden = 256)")
+                if t["net_worlds"] != "det" and not env.history:
+                    raise ValueError("teacher: net_worlds=%r reads the play history: TarokVecEnv(history=True)" % t["net_worlds"])
             if not (0 <= t["worlds"] <= K.PLAYOUT_MAX_WORLDS and 1 <= t["samples"] <= K.PLAYOUT_MAX_SAMPLES and t["every"] >= 1
                     and 0.0 <= t["tau"] < float("inf")):
                 raise ValueError("teacher: worlds 0..%d, samples 1..%d, tau >= 0 and finite, every >= 1"
@@ -591,7 +604,8 @@ class SelfPlay:
     @torch.no_grad()
     def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None, greedy=False, temperature=None, epsilon=0.0,
                  versus_playout=None, playout_worlds=None, playout_voids=False, playout_exchange=None,
-                 playout_hidden=False, playout_bidding=None, pass_value=False, playout_net=False, playout_net_seats=15):
+                 playout_hidden=False, playout_bidding=None, pass_value=False, playout_net=False, playout_net_seats=15,
+                 playout_net_worlds="det"):
         """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
         weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
         and on the SAME deals on every rank (seed 0, game offset 0, whatever the training env's are): the figures of
@@ -620,7 +634,14 @@ class SelfPlay:
         (evaluate_playout_vs_bot(pass_value=True)).
         playout_net=True (with playout_worlds=W, versus_playout=1 and none of the other playout_ options): the second
         dict is the determinized player whose playouts are played by THIS learner's current weights
-        (evaluate_playout_vs_bot(net=weights, net_seats=playout_net_seats)): one playout per (card, world)."""
+        (evaluate_playout_vs_bot(net=weights, net_seats=playout_net_seats)): one playout per (card, world).
+        playout_net_worlds="voids" / "hidden" (with playout_net): those playouts run in the void-aware worlds or in the
+        worlds that also re-deal the talon and the discards (evaluate_playout_vs_bot(net_worlds=...)); "det": as before.
+        playout_net with playout_voids / playout_hidden keeps raising: playout_net_worlds is the way in."""
+        if playout_net_worlds not in ("det", "voids", "hidden"):
+            raise ValueError('playout_net_worlds: one of "det", "voids", "hidden"')
+        if playout_net_worlds != "det" and not playout_net:
+            raise ValueError("playout_net_worlds goes with playout_net=True")
         if playout_net:
             if playout_worlds is None:
                 raise ValueError("playout_net goes with playout_worlds=W")
@@ -664,7 +685,8 @@ class SelfPlay:
         from .evaluate import evaluate_playout_vs_bot
         if playout_net:
             return own, evaluate_playout_vs_bot(None, n_games, episodes, mix=mix, device=self.env.device_index, worlds=playout_worlds,
-                                                net=self._w, net_seats=playout_net_seats)
+                                                net=self._w, net_seats=playout_net_seats,
+                                                **({} if playout_net_worlds == "det" else dict(net_worlds=playout_net_worlds)))
         return own, evaluate_playout_vs_bot(int(versus_playout), n_games, episodes, mix=mix, device=self.env.device_index,
                                             worlds=playout_worlds, voids=bool(playout_voids), exchange=playout_exchange,
                                             hidden=bool(playout_hidden), bidding=playout_bidding,
@@ -689,8 +711,8 @@ class SelfPlay:
             self._teach_sums = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=dev)
             self._teach_act = torch.empty(n, dtype=torch.uint8, device=dev)
             tc = self.teacher                         # the voids / played words of the teacher's worlds
-            self._teach_words = (torch.empty(n, dtype=torch.int32 if tc["voids"] else torch.int64, device=dev)
-                                 if tc["voids"] or tc["hidden"] else None)
+            voids, hidden = tc["voids"] or tc["net_worlds"] == "voids", tc["hidden"] or tc["net_worlds"] == "hidden"
+            self._teach_words = torch.empty(n, dtype=torch.int32 if voids else torch.int64, device=dev) if voids or hidden else None
             if tc["net"]:                             # the net launch's scratch: allocated here, before any capture
                 self.env.playout_net_scratch(tc["worlds"])
         self._graph = None
@@ -700,8 +722,9 @@ class SelfPlay:
         one tarok_playout_targets on the words of that lock-step.  Stream-ordered, read-only on the env, no allocation."""
         env, buf, tc = self.env, self._buf, self.teacher
         if tc["net"]:                                 # the playouts are played by the learner's own rollout weights
+            kind = {} if tc["net_worlds"] == "det" else {tc["net_worlds"]: True, "words": self._teach_words}
             env.playout_cards_net(self._w, tc["worlds"], net_seats=tc["net_seats"], salt=tc["salt"], seats_per_game=self._seats,
-                                  sum_out=self._teach_sums, action_out=self._teach_act)
+                                  sum_out=self._teach_sums, action_out=self._teach_act, **kind)
             env.playout_targets(self._teach_sums, buf["words"][t], tc["worlds"], tc["tau"], seats_per_game=self._seats,
                                 target_out=buf["teach"][t])
             return
