@@ -924,6 +924,47 @@ int tarok_playout_cards_net_hidden(tarok_env *env, int worlds, uint64_t salt, in
                                    const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
                                    int32_t *sum_out, uint8_t *action_out, void *stream);
 
+/* Value-bootstrapped net playouts: the three launches above with every playout stopped at the VIEWER's depth-th next
+ * decision, where the network's value head stands in for the rest of the game.  "Takes part", the worlds, wkey and pkey,
+ * the item numbering, net_seats, w1 .. b3 (read when the launches RUN), the scratch and its size
+ * (tarok_playout_net_scratch(env, worlds), 16-byte aligned, contents undefined afterwards), sum_out, action_out, the
+ * read-only env, three launches on `stream`, nothing allocated and nothing read by the host are the existing kind's:
+ *   kind = TAROK_NET_WORLDS_DET     tarok_playout_cards_net's worlds;         words = NULL
+ *   kind = TAROK_NET_WORLDS_VOIDS   tarok_playout_cards_net_voids' worlds;    words = voids  [N] u32 (device)
+ *   kind = TAROK_NET_WORLDS_HIDDEN  tarok_playout_cards_net_hidden's worlds;  words = played [N] u64 (device)
+ * What is new:
+ *   - the VIEWER of an item is the seat to move in the env's position (the seat that plays the candidate card, the
+ *     seat the playouts are for);
+ *   - after the candidate, a live item counts the positions at which the viewer is to move.  At the depth-th such
+ *     position the item STOPS without playing a card.  (A seat plays once per trick: at depth = 1 an item plays at
+ *     most 6 cards after the candidate and stops in its 7th card round at the latest.)
+ *   - at the stop, tarok_policy_mlp's forward runs on that position's feature words with w1 .. b3, whether or not the
+ *     viewer is in net_seats; v is its output 54, bit for bit what tarok_policy_mlp writes to value_out there.  The
+ *     position is the viewer's own decision, so v depends on the world only through the cards played in it: own hand,
+ *     legal cards, table, taken cards, contract and team are what the viewer knows;
+ *   - the number written is computed in float32:  t = v * value_scale;  t = 0 if t is NaN;  t clamped to
+ *     [-32767, 32767];  V = (int)rintf(t), ties to even.  (value_scale = 1 / reward_scale turns a value head trained on
+ *     returns in reward_scale points back into points.)
+ *   - the stopped item's result is V in the viewer's column and 0 in the other three; an item whose game ends before
+ *     the stop keeps its four true scores, as in the existing launches.
+ * ONLY THE VIEWER'S COLUMN of sum_out is meaningful where items stopped: the other three columns sum true scores of the
+ * finished items and zeros of the stopped ones.  action_out keeps the card rule of the existing launches, which reads
+ * the mover's (= the viewer's) column alone.
+ * After its candidate the viewer has at most 11 decisions left, so depth = TAROK_PLAYOUT_MAX_DEPTH = 12 never stops an
+ * item and writes the bytes of the existing launch of the kind, for any weights and any value_scale.
+ * TAROK_EINVAL (before any HIP call) for everything the existing launch of the kind refuses, kind outside 0..2, words
+ * NULL for kind 1 or 2 or non-NULL for kind 0, depth outside 1..TAROK_PLAYOUT_MAX_DEPTH, value_scale not finite or
+ * not > 0. */
+#define TAROK_NET_WORLDS_DET 0
+#define TAROK_NET_WORLDS_VOIDS 1
+#define TAROK_NET_WORLDS_HIDDEN 2
+#define TAROK_PLAYOUT_MAX_DEPTH 12
+int tarok_playout_cards_net_value(tarok_env *env, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                                  int kind, const void *words, int net_seats, int depth, float value_scale,
+                                  const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
+                                  const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out,
+                                  uint8_t *action_out, void *stream);
+
 /* Net-played playouts for the exchange and the bid: tarok_playout_exchange and tarok_playout_bids at ONE playout per
  * (candidate or option, world), played as tarok_playout_cards_net plays its playouts — the network's greedy card on the
  * absolute seats of net_seats (one launch-wide 4-bit set), the Bot's card policy_action(pkey, q, legal) on the others.

@@ -35,6 +35,7 @@ SYMBOLS = [
     "tarok_bid_values", "tarok_exchange_values", "tarok_exchange_candidates",
     "tarok_playout_bids_pass", "tarok_bid_round_pass", "tarok_bid_values_pass",
     "tarok_playout_net_scratch", "tarok_playout_cards_net", "tarok_playout_cards_net_voids", "tarok_playout_cards_net_hidden",
+    "tarok_playout_cards_net_value",
     "tarok_playout_exchange_net_scratch", "tarok_playout_exchange_net", "tarok_playout_bids_net_scratch", "tarok_playout_bids_net",
     "tarok_front_lines_scratch_bytes", "tarok_front_lines", "tarok_get_lines",
 ]
@@ -180,6 +181,8 @@ def lib():
     for kind in ("voids", "hidden"):                 # the per-game words come before net_seats
         f = getattr(L, "tarok_playout_cards_net_" + kind)
         f.restype = i32; f.argtypes = [vp, i32, u64, i32, vp, vp, i32] + [vp] * 6 + [vp, i64, vp, vp, vp]
+    L.tarok_playout_cards_net_value.restype = i32    # (kind, words) before net_seats, (depth, value_scale) after it
+    L.tarok_playout_cards_net_value.argtypes = [vp, i32, u64, i32, vp, i32, vp, i32, i32, f32] + [vp] * 6 + [vp, i64, vp, vp, vp]
     L.tarok_playout_exchange_net_scratch.restype = i64; L.tarok_playout_exchange_net_scratch.argtypes = [vp, i32, i32]
     L.tarok_playout_exchange_net.restype = i32
     L.tarok_playout_exchange_net.argtypes = [vp, i32, i32, u64, i32, vp, i32] + [vp] * 6 + [vp, i64, vp, vp, vp, vp]

@@ -3363,7 +3363,9 @@ __global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_
 // LDS, its per-game word, Dealer::deal under the world key), the candidate card applied, the items written.  An item whose
 // candidate ends the game is written finished; the slots of absent ranks and of games that do not take part get 0.  A
 // hidden world's item is the packed Game whose C plane and talon ids moved: the second launch unpacks all of it.
-template <class Dealer>
+// VIEWER (tarok_playout_cards_net_value): a live item's marker carries the viewer — the seat to move in the env's position —
+// in its two low bits (lane 0 is -32768 + viewer: no score is near).
+template <class Dealer, bool VIEWER = false>
 __device__ __forceinline__ void playout_net_deal_body(int64_t n, u64 pseed, u64 offset, u32 worlds, u32 lg, u32 seats,
                                                       const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
                                                       const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
@@ -3407,7 +3409,7 @@ __device__ __forceinline__ void playout_net_deal_body(int64_t n, u64 pseed, u64 
                 u64 scores = 0;
                 u32 ti;
                 const int fin = apply_step<true>(h, c, scores, ti, false);
-                res = fin ? scores : TK_PN_LIVE;
+                res = fin ? scores : (VIEWER ? TK_PN_LIVE | (u64)p.mover : TK_PN_LIVE);
                 if (!fin) {
                     u64 x0, x1, y0, y1;
                     pack(h, x0, x1, y0, y1);
@@ -3452,6 +3454,34 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal_hidden(int64_t n, u64 pseed /* 
     playout_net_deal_body<DealHidden>(n, pseed, offset, worlds, lg, seats, seat_sets, s01, s23, cnt, played_words, i01, i23, ikey, ires);
 }
 
+// tarok_playout_cards_net_value's first launches: the three above with the viewer in a live item's marker.
+TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal_value(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,
+                                                      const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                                      const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                                      ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,
+                                                      u64 *__restrict__ ires) {
+    TK_VGPR_TOP(128, 127);
+    playout_net_deal_body<DealUnseen, true>(n, pseed, offset, worlds, lg, seats, seat_sets, s01, s23, cnt, nullptr, i01, i23, ikey, ires);
+}
+
+TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal_value_voids(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,
+                                                            const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                                            const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                                            const u32 *__restrict__ voids, ulonglong2 *__restrict__ i01,
+                                                            ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
+    TK_VGPR_TOP(128, 127);
+    playout_net_deal_body<DealVoids, true>(n, pseed, offset, worlds, lg, seats, seat_sets, s01, s23, cnt, voids, i01, i23, ikey, ires);
+}
+
+TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal_value_hidden(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,
+                                                             const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                                             const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                                             const u64 *__restrict__ played_words, ulonglong2 *__restrict__ i01,
+                                                             ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
+    TK_VGPR_TOP(128, 127);
+    playout_net_deal_body<DealHidden, true>(n, pseed, offset, worlds, lg, seats, seat_sets, s01, s23, cnt, played_words, i01, i23, ikey, ires);
+}
+
 // Second launch: the playouts.  A workgroup of 256 threads keeps one tile of PM_M = 128 items resident — their packed
 // states and keys in LDS, owned by threads 0..127 — and plays them card by card: feature words (policy_feature_words on
 // the item's own Game) -> policy_expand, mlp_hidden x 2, mlp_head, unchanged, so a row's logits are tarok_policy_mlp's
@@ -3468,29 +3498,48 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal_hidden(int64_t n, u64 pseed /* 
 //   - a live row with an empty legal mask is retired with result 0, not waited for;
 //   - a workgroup whose items are all dead leaves at the first round's test: it runs no forward;
 //   - a row still live after the last round (none can be) gets result 0: TK_PN_LIVE never reaches the third launch.
-__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net_play(
-    int64_t items, u32 net_seats, const ulonglong2 *__restrict__ i01, const ulonglong2 *__restrict__ i23,
-    const u64 *__restrict__ ikey, u64 *__restrict__ ires, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
-    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3, const float *__restrict__ b3) {
-    TK_VGPR_TOP(256, 255);
+//
+// VALUE (k_playout_net_play_value, tarok_playout_cards_net_value): a live item's marker carries its viewer
+// in the two low bits, and the owning thread counts down `depth` at every position with the viewer to move.  The row
+// that reaches 0 STOPS in that round: it plays no card, writes rint(clamp(v54 * value_scale)) into the viewer's column
+// (zeros in the other three) and dies.  What changes in the invariants above, and nothing else:
+//   - a THIRD vote bit (4): some live row stops this round.  It is written with the other two by waves 0 and 1 before
+//     the round's first barrier, so the forward test `v & 6` is workgroup-uniform as `v & 2` is; the two parities stay,
+//     and no barrier moved into a divergent branch;
+//   - the value reaches the owning thread as the card does: val_s[row], written next to act_s[row] by the row's
+//     half == 0 lane between the forward's last two barriers (512 bytes more LDS: 77,456 in all, still two per CU);
+//   - a stopping row is retired in its round whatever its legal mask holds; depth = TAROK_PLAYOUT_MAX_DEPTH never counts
+//     to 0 (a seat has at most 11 cards after its candidate), and every round is then the plain kernel's.
+template <bool VALUE>
+__device__ __forceinline__ void playout_net_play_body(int64_t items, u32 net_seats, u32 depth, float value_scale,
+                                                      const ulonglong2 *__restrict__ i01, const ulonglong2 *__restrict__ i23,
+                                                      const u64 *__restrict__ ikey, u64 *__restrict__ ires,
+                                                      const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+                                                      const __bf16 *__restrict__ w2, const float *__restrict__ b2,
+                                                      const __bf16 *__restrict__ w3, const float *__restrict__ b3) {
     __shared__ __attribute__((aligned(16))) __bf16 X[PM_M * PM_LD];
     __shared__ __attribute__((aligned(16))) u64 ext[PM_M][4];
     __shared__ __attribute__((aligned(16))) u64 st[PM_M][4];
     __shared__ u64 keys[PM_M];
     __shared__ uint8_t act_s[PM_M];
     __shared__ u32 vote[2][2];
+    __shared__ float val_s[VALUE ? PM_M : 1];
     const u32 tid = threadIdx.x, wave = tid >> 6;
     const int64_t it = (int64_t)blockIdx.x * PM_M + tid;
     float *L = reinterpret_cast<float *>(X);
     bool live = false;
-    if (tid < PM_M && it < items && ires[it] == TK_PN_LIVE) {
+    u32 viewer = 0, left = depth;
+    u64 mark = 0;
+    if (tid < PM_M && it < items && ((mark = ires[it]) & (VALUE ? ~3ULL : ~0ULL)) == TK_PN_LIVE) {
         live = true;
+        if constexpr (VALUE) viewer = (u32)mark & 3u;
         const ulonglong2 a = i01[it], b = i23[it];
         st[tid][0] = a.x; st[tid][1] = a.y; st[tid][2] = b.x; st[tid][3] = b.y;
         keys[tid] = ikey[it];
     }
 #pragma unroll 1
     for (u32 round = 0; round < TK_PN_MAX_CARDS; round++) {
+        bool stop = false;
         if (tid < PM_M) {                                  // (waves 0 and 1, whole)
             bool net = false;
             if (live) {
@@ -3498,16 +3547,24 @@ __global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net
                 unpack(h, st[tid][0], st[tid][1], st[tid][2], st[tid][3]);
                 policy_feature_words(h, ext[tid]);
                 net = (net_seats >> ((h.leader + h.nt) & 3)) & 1u;
+                if constexpr (VALUE) {
+                    if (((h.leader + h.nt) & 3) == viewer) stop = --left == 0;
+                }
             } else {
                 ext[tid][0] = 0; ext[tid][1] = 0; ext[tid][2] = 0; ext[tid][3] = 0;
             }
             const u64 any_live = __ballot(live), any_net = __ballot(live && net);
-            if (__lane_id() == 0) vote[round & 1][wave] = (any_live ? 1u : 0u) | (any_net ? 2u : 0u);
+            if constexpr (VALUE) {
+                const u64 any_stop = __ballot(stop);       // (every lane of the wave is here: tid < PM_M takes whole waves)
+                if (__lane_id() == 0) vote[round & 1][wave] = (any_live ? 1u : 0u) | (any_net ? 2u : 0u) | (any_stop ? 4u : 0u);
+            } else {
+                if (__lane_id() == 0) vote[round & 1][wave] = (any_live ? 1u : 0u) | (any_net ? 2u : 0u);
+            }
         }
         __syncthreads();
         const u32 v = vote[round & 1][0] | vote[round & 1][1];
         if (!(v & 1u)) break;
-        if (v & 2u) {
+        if (v & (VALUE ? 6u : 2u)) {
             bf16x8 wq[4][2];
             mlp_prefetch(wq, w1, wave * 2);
             policy_expand(X, ext, tid);
@@ -3525,14 +3582,23 @@ __global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net
             in.o = in.m; in.key = 0; in.played = 0; in.last = 0;
             in.mh = (u32)(in.m >> (27 * half)) & 0x7FFFFFFu;
             const PolicyPick c = policy_sample<1>(L, gi, half, in, PlayMode{1.f, 1, 0u, 0.f});
-            if (half == 0) act_s[gi] = (uint8_t)c.pk;
+            if (half == 0) {
+                act_s[gi] = (uint8_t)c.pk;
+                if constexpr (VALUE) val_s[gi] = c.v54;
+            }
             __syncthreads();
         }
         if (live) {
             Game h;
             unpack(h, st[tid][0], st[tid][1], st[tid][2], st[tid][3]);
             const u64 legal = ext[tid][1] & TAROK_OBS_MASK;
-            if (!legal) {
+            if (VALUE && stop) {                           // the viewer's depth-th decision: the value head's estimate, no card
+                float t = val_s[tid] * value_scale;
+                t = t != t ? 0.f : t;
+                t = fminf(fmaxf(t, -32767.f), 32767.f);
+                live = false;
+                ires[it] = (u64)(uint16_t)(int)rintf(t) << (16 * viewer);
+            } else if (!legal) {
                 live = false;
                 ires[it] = 0;
             } else {
@@ -3550,6 +3616,24 @@ __global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net
         }
     }
     if (live) ires[it] = 0;
+}
+
+__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net_play(
+    int64_t items, u32 net_seats, const ulonglong2 *__restrict__ i01, const ulonglong2 *__restrict__ i23,
+    const u64 *__restrict__ ikey, u64 *__restrict__ ires, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3, const float *__restrict__ b3) {
+    TK_VGPR_TOP(256, 255);
+    playout_net_play_body<false>(items, net_seats, 0, 0.f, i01, i23, ikey, ires, w1, b1, w2, b2, w3, b3);
+}
+
+// tarok_playout_cards_net_value's second launch: what the kind takes more comes last, as for the other kinds.
+__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net_play_value(
+    int64_t items, u32 net_seats, const ulonglong2 *__restrict__ i01, const ulonglong2 *__restrict__ i23,
+    const u64 *__restrict__ ikey, u64 *__restrict__ ires, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3, const float *__restrict__ b3,
+    u32 depth, float value_scale) {
+    TK_VGPR_TOP(256, 255);
+    playout_net_play_body<true>(items, net_seats, depth, value_scale, i01, i23, ikey, ires, w1, b1, w2, b2, w3, b3);
 }
 
 // Third launch: 16 lanes per game; lane r < 12 sums rank r's items over the worlds in integers, then card_epilogue's
@@ -4449,12 +4533,13 @@ static inline void launch_net_play(int64_t items, int net_seats, const NetItems 
 }
 
 // One net card launch: the items (`deal`, the dealer's kernel, with its per-game `words` where it has any), the playouts,
-// the sums — three launches on `stream`, nothing allocated.
+// the sums — three launches on `stream`, nothing allocated.  depth = 0: the playouts run to the last card; 1..12 (checked
+// by tarok_playout_cards_net_value, the only caller that gives one): they stop at the viewer's depth-th decision.
 template <class Kernel, class... Words>
 static int launch_playout_cards_net(Kernel deal, tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
                                     int net_seats, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
                                     const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out, uint8_t *action_out,
-                                    void *stream, Words... words) {
+                                    void *stream, int depth, float value_scale, Words... words) {
     if (!playout_args_ok(e, worlds, 1, seats) ||
         !net_args_ok(net_seats, w1, b1, w2, b2, w3, b3, scratch, scratch_bytes, tarok_playout_net_scratch(e, worlds)) ||
         (!sum_out && !action_out) || (... || !words))
@@ -4465,7 +4550,12 @@ static int launch_playout_cards_net(Kernel deal, tarok_env *e, int worlds, uint6
     const u32 lg = playout_lg(TK_PO_MIN_LG, worlds);
     hipLaunchKernelGGL(deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
                        (u32)worlds, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, words..., it.i01, it.i23, it.ikey, it.ires);
-    launch_net_play(items, net_seats, it, w1, b1, w2, b2, w3, b3, stream);
+    if (depth)                                            // (tarok_playout_cards_net_value: `deal` is a k_playout_net_deal_value*)
+        hipLaunchKernelGGL(k_playout_net_play_value, dim3((unsigned)((items + PM_M - 1) / PM_M)), dim3(TK_BLOCK), 0, (hipStream_t)stream,
+                           items, (u32)net_seats, it.i01, it.i23, it.ikey, it.ires, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2,
+                           (const __bf16 *)w3, b3, (u32)depth, value_scale);
+    else
+        launch_net_play(items, net_seats, it, w1, b1, w2, b2, w3, b3, stream);
     hipLaunchKernelGGL(k_playout_net_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, (u32)worlds,
                        (u32)seats, seats_per_game, e->s01, e->s23, e->gkey, it.ires, reinterpret_cast<int4 *>(sum_out), action_out);
     HIPCHK(hipGetLastError());
@@ -4477,7 +4567,7 @@ int tarok_playout_cards_net(tarok_env *e, int worlds, uint64_t salt, int seats, 
                             const void *w1, const float *b1, const void *w2, const float *b2, const void *w3, const float *b3,
                             void *scratch, int64_t scratch_bytes, int32_t *sum_out, uint8_t *action_out, void *stream) {
     return launch_playout_cards_net(k_playout_net_deal, e, worlds, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3, scratch,
-                                    scratch_bytes, sum_out, action_out, stream);
+                                    scratch_bytes, sum_out, action_out, stream, 0, 0.f);
 }
 
 int tarok_playout_cards_net_voids(tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
@@ -4485,7 +4575,7 @@ int tarok_playout_cards_net_voids(tarok_env *e, int worlds, uint64_t salt, int s
                                   const void *w3, const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out,
                                   uint8_t *action_out, void *stream) {
     return launch_playout_cards_net(k_playout_net_deal_voids, e, worlds, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3,
-                                    scratch, scratch_bytes, sum_out, action_out, stream, voids);
+                                    scratch, scratch_bytes, sum_out, action_out, stream, 0, 0.f, voids);
 }
 
 int tarok_playout_cards_net_hidden(tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
@@ -4493,7 +4583,24 @@ int tarok_playout_cards_net_hidden(tarok_env *e, int worlds, uint64_t salt, int 
                                    const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
                                    int32_t *sum_out, uint8_t *action_out, void *stream) {
     return launch_playout_cards_net(k_playout_net_deal_hidden, e, worlds, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3,
-                                    scratch, scratch_bytes, sum_out, action_out, stream, (const u64 *)played);
+                                    scratch, scratch_bytes, sum_out, action_out, stream, 0, 0.f, (const u64 *)played);
+}
+
+int tarok_playout_cards_net_value(tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game, int kind,
+                                  const void *words, int net_seats, int depth, float value_scale, const void *w1, const float *b1,
+                                  const void *w2, const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
+                                  int32_t *sum_out, uint8_t *action_out, void *stream) {
+    if (kind < TAROK_NET_WORLDS_DET || kind > TAROK_NET_WORLDS_HIDDEN || (kind == TAROK_NET_WORLDS_DET && words) || depth < 1 ||
+        depth > TAROK_PLAYOUT_MAX_DEPTH || !(value_scale > 0.f) || __builtin_isinf(value_scale))
+        return TAROK_EINVAL;
+    if (kind == TAROK_NET_WORLDS_VOIDS)
+        return launch_playout_cards_net(k_playout_net_deal_value_voids, e, worlds, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3,
+                                        b3, scratch, scratch_bytes, sum_out, action_out, stream, depth, value_scale, (const u32 *)words);
+    if (kind == TAROK_NET_WORLDS_HIDDEN)
+        return launch_playout_cards_net(k_playout_net_deal_value_hidden, e, worlds, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3,
+                                        b3, scratch, scratch_bytes, sum_out, action_out, stream, depth, value_scale, (const u64 *)words);
+    return launch_playout_cards_net(k_playout_net_deal_value, e, worlds, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3, scratch,
+                                    scratch_bytes, sum_out, action_out, stream, depth, value_scale);
 }
 
 int tarok_playout_exchange(tarok_env *e, int worlds, int samples, int discard_sets, uint64_t salt, int seats,

@@ -70,6 +70,46 @@ def playout_values(sum, words, samples):
     return torch.where(legal, torch.gather(own, 1, rank), torch.full((), float("-inf"), device=words.device))
 
 
+NET_WORLDS_DET, NET_WORLDS_VOIDS, NET_WORLDS_HIDDEN = 0, 1, 2      # tarok_playout_cards_net_value's `kind`
+
+
+def _playout_cards_net(self, weights, worlds, net_seats, salt, seats, seats_per_game, sum_out, action_out, voids, hidden, words,
+                       depth, value_scale):
+    """TarokVecEnv.playout_cards_net (depth None: the launch of the world kind) and .playout_cards_net_value (an integer
+    depth: tarok_playout_cards_net_value with the kind as a number) — one body, so that the two cannot drift."""
+    given_v, given_h = (x is not None and not isinstance(x, (bool, int)) for x in (voids, hidden))   # a tensor or an array
+    want_v, want_h = given_v or bool(voids), given_h or bool(hidden)
+    if want_v and want_h:
+        raise ValueError("hidden=True is not built together with voids=True: give one of the two")
+    if (want_v and not given_v or want_h and not given_h) and not self.history:
+        raise ValueError("playout_cards_net(%s=True) goes with the play history: TarokVecEnv(history=True)"
+                         % ("voids" if want_v else "hidden"))
+    if not 0 <= int(net_seats) <= 15:
+        raise ValueError("net_seats: a 4-bit seat set, 0..15")
+    w = self.check_mlp_weights(weights)
+    scratch = self.playout_net_scratch(worlds)
+    fn, kind, extra = self.L.tarok_playout_cards_net, NET_WORLDS_DET, ()
+    if want_v:
+        fn, kind = self.L.tarok_playout_cards_net_voids, NET_WORLDS_VOIDS
+        extra = (self._dev(voids if given_v else self.shown_voids(words), torch.int32, (self.n,)),)
+    elif want_h:
+        fn, kind = self.L.tarok_playout_cards_net_hidden, NET_WORLDS_HIDDEN
+        extra = (self._dev(hidden if given_h else self.played_cards(words), torch.int64, (self.n,)),)
+    head = [self._p(t) for t in extra] + [int(net_seats)]
+    if depth is not None:
+        fn = self.L.tarok_playout_cards_net_value
+        head = [kind, self._p(extra[0]) if extra else None, int(net_seats), int(depth), float(value_scale)]
+    with torch.cuda.device(self.device):
+        if sum_out is None:
+            sum_out = torch.empty((self.n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=self.device)
+        if action_out is None:
+            action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
+        _native.check(fn(self._h, int(worlds), int(salt) & ((1 << 64) - 1), int(seats), self._p(self._seat_sets(seats_per_game)),
+                         *head, *[self._p(t) for t in w], self._p(scratch), scratch.numel(), self._p(sum_out), self._p(action_out),
+                         self._stream()))
+    return sum_out, action_out
+
+
 class TarokVecEnv:
     def __init__(self, n_games, device=0, seed=0, mix=K.MIX_ALL, game_offset=0, history=False, refill_fan=None, lazy_refill=None):
         """refill_fan, lazy_refill: launch tuning (tarok_set_option; None = the library's default for the batch size);
@@ -393,33 +433,28 @@ class TarokVecEnv:
         playout_cards_voids(voids=...) takes them, and needs no history.  words: the caller's scratch tensor for the
         env's own words (None: a new one per call), so that a captured launch allocates nothing.  Not both: the two
         kinds do not compose.  The defaults issue tarok_playout_cards_net."""
-        given_v, given_h = (x is not None and not isinstance(x, (bool, int)) for x in (voids, hidden))   # a tensor or an array
-        want_v, want_h = given_v or bool(voids), given_h or bool(hidden)
-        if want_v and want_h:
-            raise ValueError("hidden=True is not built together with voids=True: give one of the two")
-        if (want_v and not given_v or want_h and not given_h) and not self.history:
-            raise ValueError("playout_cards_net(%s=True) goes with the play history: TarokVecEnv(history=True)"
-                             % ("voids" if want_v else "hidden"))
-        if not 0 <= int(net_seats) <= 15:
-            raise ValueError("net_seats: a 4-bit seat set, 0..15")
-        w = self.check_mlp_weights(weights)
-        scratch = self.playout_net_scratch(worlds)
-        fn, extra = self.L.tarok_playout_cards_net, ()
-        if want_v:
-            fn = self.L.tarok_playout_cards_net_voids
-            extra = (self._dev(voids if given_v else self.shown_voids(words), torch.int32, (self.n,)),)
-        elif want_h:
-            fn = self.L.tarok_playout_cards_net_hidden
-            extra = (self._dev(hidden if given_h else self.played_cards(words), torch.int64, (self.n,)),)
-        with torch.cuda.device(self.device):
-            if sum_out is None:
-                sum_out = torch.empty((self.n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=self.device)
-            if action_out is None:
-                action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
-            _native.check(fn(self._h, int(worlds), int(salt) & ((1 << 64) - 1), int(seats), self._p(self._seat_sets(seats_per_game)),
-                             *[self._p(t) for t in extra], int(net_seats), *[self._p(t) for t in w], self._p(scratch),
-                             scratch.numel(), self._p(sum_out), self._p(action_out), self._stream()))
-        return sum_out, action_out
+        return _playout_cards_net(self, weights, worlds, net_seats, salt, seats, seats_per_game, sum_out, action_out, voids, hidden,
+                                  words, None, 0.0)
+
+    def playout_cards_net_value(self, weights, worlds, depth, value_scale=70.0, net_seats=15, salt=0, seats=15, seats_per_game=None,
+                                sum_out=None, action_out=None, voids=False, hidden=False, words=None):
+        """playout_cards_net whose playouts stop at the VIEWER's `depth`-th next decision (tarok_playout_cards_net_value;
+        the viewer is the seat to move, the seat the playouts are for): there the value head of `weights` (output 54 of
+        policy_mlp's forward on the stop position's own features, whether or not the viewer is in net_seats) times
+        `value_scale`, rounded half-even into int16 range, is the viewer's result and the other three columns get 0; a
+        playout whose game ends first keeps its true scores.  Only the viewer's column of the sums is meaningful; the card
+        rule reads no other.  depth: 1..12 — depth 1 plays at most 6 cards per playout where a fresh deal takes 47; depth
+        12 never stops and gives playout_cards_net's bytes.  value_scale: points per unit of the value head (a learner
+        trained on returns * reward_scale wants 1 / reward_scale; 70 is SelfPlay's default reward_scale inverted).
+        Everything else — worlds, voids= / hidden= / words=, the scratch, the outputs — is playout_cards_net's; depth=None
+        IS playout_cards_net."""
+        if depth is not None:
+            if isinstance(depth, bool) or int(depth) != depth or not 1 <= int(depth) <= K.PLAYOUT_MAX_DEPTH:
+                raise ValueError("depth: None or 1..%d viewer decisions" % K.PLAYOUT_MAX_DEPTH)
+            if not (float(value_scale) > 0 and float(value_scale) < float("inf")):
+                raise ValueError("value_scale: finite and > 0")
+        return _playout_cards_net(self, weights, worlds, net_seats, salt, seats, seats_per_game, sum_out, action_out, voids, hidden,
+                                  words, depth, value_scale)
 
     def playout_exchange(self, worlds, samples, discard_sets=4, salt=0, seats=15, seats_per_game=None, sum_out=None,
                          choice_out=None, discards_out=None):

@@ -359,7 +359,7 @@ def _bid_args(bidding, mix):
 
 def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None, voids=False, exchange=None,
                     hidden=False, bidding=None, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None,
-                    net_seats=15, net_worlds="det"):
+                    net_seats=15, net_worlds="det", net_depth=None, net_value_scale=70.0):
     """_play_passes_mode with the Monte-Carlo player (TarokVecEnv.playout_cards) in the network's place: per lock-step
     one playout launch with the pass's seat set — tarok_playout_cards (open hands) for worlds=None,
     tarok_playout_cards_det (the fair player: `worlds` re-deals of the unseen cards) otherwise — whose action_out holds
@@ -379,7 +379,16 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     net_worlds="voids" / "hidden" (with net): the env keeps the play history and every lock-step runs tarok_shown_voids and
     tarok_playout_cards_net_voids / tarok_played_cards and tarok_playout_cards_net_hidden instead; "det" is the launch
     above.  (voids=True / hidden=True together with net= keep raising: net_worlds is the way in.)
+    net_depth=D (with net): the launch is playout_cards_net_value at depth D and net_value_scale in the same worlds — the
+    playouts stop at the player's D-th next decision and take the value head's estimate; None: the calls as they were.
     inspect: as in _play_passes_mode."""
+    if net_depth is not None:
+        if net is None:
+            raise ValueError("net_depth stops the network's playouts: it goes with net=weights")
+        if isinstance(net_depth, bool) or not isinstance(net_depth, int) or not 1 <= net_depth <= K.PLAYOUT_MAX_DEPTH:
+            raise ValueError("net_depth: None or 1..%d viewer decisions" % K.PLAYOUT_MAX_DEPTH)
+        if not 0 < float(net_value_scale) < float("inf"):
+            raise ValueError("net_value_scale: finite and > 0")
     if net_worlds not in NET_WORLDS:
         raise ValueError('net_worlds: one of "det", "voids", "hidden"')
     if net is None and net_worlds != "det":
@@ -405,14 +414,17 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     if bidding is not None and worlds is None:
         raise ValueError("bidding=(W, S) is the fair player's front end: give worlds= as well")
     bidding = _bid_args(bidding, mix)
+    def launch(env, seats, **kw):                     # net_depth=None: exactly the calls as they were
+        kw = dict(net_seats=seats if net_seats == "own" else net_seats, salt=salt, seats=seats, **kw)
+        if net_depth is None:
+            return env.playout_cards_net(net, worlds, **kw)
+        return env.playout_cards_net_value(net, worlds, net_depth, float(net_value_scale), **kw)
     if net is not None and net_worlds != "det":
         kind = {net_worlds: True}
-        cards = _playout_cards(lambda env, seats, words, sums, row: env.playout_cards_net(
-            net, worlds, net_seats=seats if net_seats == "own" else net_seats, salt=salt, seats=seats, sum_out=sums, action_out=row,
-            words=words, **kind), words_dtype=torch.int32 if net_worlds == "voids" else torch.int64)
+        cards = _playout_cards(lambda env, seats, words, sums, row: launch(env, seats, sum_out=sums, action_out=row, words=words, **kind),
+                               words_dtype=torch.int32 if net_worlds == "voids" else torch.int64)
     elif net is not None:
-        cards = _playout_cards(lambda env, seats, words, sums, row: env.playout_cards_net(
-            net, worlds, net_seats=seats if net_seats == "own" else net_seats, salt=salt, seats=seats, sum_out=sums, action_out=row))
+        cards = _playout_cards(lambda env, seats, words, sums, row: launch(env, seats, sum_out=sums, action_out=row))
     else:
         cards = _playout_cards(lambda env, seats, words, sums, row: env.playout_cards_fair(
             worlds, samples, voids=voids, hidden=hidden, words=words, salt=salt, seats=seats, sum_out=sums, action_out=row),
@@ -425,7 +437,8 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
 
 def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None,
                             voids=False, exchange=None, hidden=False, bidding=None, threshold=0,
-                            contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None, net_seats=15, net_worlds="det"):
+                            contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None, net_seats=15, net_worlds="det",
+                            net_depth=None, net_value_scale=70.0):
     """evaluate_vs_bot with the open-hand Monte-Carlo player in the network's place: a strong reference player that needs
     no training.  On its seat it plays, at every move, the legal card with the best summed score over `samples` Bot
     playouts of each legal card (tarok_playout_cards; `salt` varies their draws).  The playouts see the TRUE hidden
@@ -456,12 +469,17 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
     in the void-aware worlds (tarok_shown_voids, tarok_playout_cards_net_voids) or in the worlds that also re-deal Klop's
     talon and the declarer's discards (tarok_played_cards, tarok_playout_cards_net_hidden); the env keeps the history.
     The spellings net= with voids=True / hidden=True keep raising ValueError, as they always have: net_worlds is the way in.
+    net_depth=D (with net=weights; 1..12): the network's playouts stop at the player's D-th next decision and take the value
+    head's estimate times net_value_scale (points per unit of the head: 1 / the learner's reward_scale) for the rest of the
+    game (tarok_playout_cards_net_value, in the worlds of net_worlds) — at D = 1 at most 6 cards per playout where a fresh
+    deal takes 47.  None (the default): the playouts run to the last card, the calls as they were.
     The same five duplicate passes (PASS_SEATS) on an env of its own; returns duplicate_advantage's dict, `policy_mean`
     being the playout player's.  inspect (tests): a list that receives one dict per pass, as in _play_passes_mode."""
     return duplicate_advantage(_playout_passes(samples, n_games, episodes, seed, mix, device, salt=salt, inspect=inspect,
                                                worlds=worlds, voids=voids, exchange=exchange, hidden=hidden, bidding=bidding,
                                                threshold=threshold, contracts=contracts, pass_value=pass_value, net=net,
-                                               net_seats=net_seats, net_worlds=net_worlds))
+                                               net_seats=net_seats, net_worlds=net_worlds, net_depth=net_depth,
+                                               net_value_scale=net_value_scale))
 
 
 def _front_cards(cards):

@@ -291,6 +291,10 @@ class SelfPlay:
     the table knows to be impossible.  The words, the three launches and tarok_playout_targets are one
     stream-ordered chain inside the captured rollout; the env must keep the play history.  "det" (the default) is the
     launch above.  net=True with voids=True / hidden=True keeps raising, as it always has: net_worlds is the way in.
+    teacher = dict(..., net=True, depth=D): the network's playouts stop at the mover's D-th next decision (1..12) and take
+    the learner's own value head there, at value_scale = 1 / reward_scale — the head's unit turned back into points
+    (tarok_playout_cards_net_value in the worlds of net_worlds).  The call sits inside the captured rollout
+    on the live weights like the launch above; at D = 1 a playout is at most 6 cards long.  Without the key: as before.
 
     front = dict(bid=, exchange=, contracts=, margin=, pass_value=, every=1): the games auto-reset swaps in are bid and
     exchanged by the heads instead of the Bot (TarokVecEnv.front_lines).  bid / exchange: six tensors each
@@ -323,7 +327,7 @@ class SelfPlay:
                 raise ValueError("learner_seats: a seat set 0..15 or a [N] uint8 tensor of sets")
         self.teacher, self.distill_coef = None, float(distill_coef)
         if teacher is not None:
-            unknown = set(teacher) - {"worlds", "samples", "tau", "every", "salt", "voids", "hidden", "net", "net_seats", "net_worlds"}
+            unknown = set(teacher) - {"worlds", "samples", "tau", "every", "salt", "voids", "hidden", "net", "net_seats", "net_worlds", "depth"}
             net = bool(teacher.get("net", False))
             if unknown or ("samples" not in teacher and not net):
                 raise ValueError("teacher: dict(worlds=W, samples=S, tau=tau, every=k, salt=...), samples required; unknown keys %s" % sorted(unknown))
@@ -337,6 +341,15 @@ class SelfPlay:
                 raise ValueError('teacher: net_worlds is one of "det", "voids", "hidden"')
             if "net_worlds" in teacher and not net:
                 raise ValueError("teacher: net_worlds names the worlds of the network's playouts: it goes with net=True")
+            if teacher.get("depth") is not None:          # (the key is kept only where it was given: a teacher without it is unchanged)
+                d = teacher["depth"]
+                if not net:
+                    raise ValueError("teacher: depth stops the network's playouts at the mover's depth-th decision: it goes with net=True")
+                if isinstance(d, bool) or not isinstance(d, int) or not 1 <= d <= K.PLAYOUT_MAX_DEPTH:
+                    raise ValueError("teacher: depth is 1..%d viewer decisions" % K.PLAYOUT_MAX_DEPTH)
+                if not 0 < float(reward_scale) < float("inf"):
+                    raise ValueError("teacher: depth reads the value head in units of reward_scale, which must be finite and > 0")
+                t["depth"] = d
             if net:
                 if t["samples"] != 1:
                     raise ValueError("teacher: net=True runs one playout per (card, world): samples is optional and must be 1")
@@ -605,7 +618,7 @@ class SelfPlay:
     def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None, greedy=False, temperature=None, epsilon=0.0,
                  versus_playout=None, playout_worlds=None, playout_voids=False, playout_exchange=None,
                  playout_hidden=False, playout_bidding=None, pass_value=False, playout_net=False, playout_net_seats=15,
-                 playout_net_worlds="det"):
+                 playout_net_worlds="det", playout_net_depth=None):
         """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
         weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
         and on the SAME deals on every rank (seed 0, game offset 0, whatever the training env's are): the figures of
@@ -637,7 +650,15 @@ class SelfPlay:
         (evaluate_playout_vs_bot(net=weights, net_seats=playout_net_seats)): one playout per (card, world).
         playout_net_worlds="voids" / "hidden" (with playout_net): those playouts run in the void-aware worlds or in the
         worlds that also re-deal the talon and the discards (evaluate_playout_vs_bot(net_worlds=...)); "det": as before.
-        playout_net with playout_voids / playout_hidden keeps raising: playout_net_worlds is the way in."""
+        playout_net with playout_voids / playout_hidden keeps raising: playout_net_worlds is the way in.
+        playout_net_depth=D (with playout_net; 1..12): those playouts stop at the player's D-th next decision and take this
+        learner's value head there, in points (evaluate_playout_vs_bot(net_depth=D, net_value_scale=1 / reward_scale));
+        None: they run to the last card, as before."""
+        if playout_net_depth is not None:
+            if not playout_net:
+                raise ValueError("playout_net_depth goes with playout_net=True")
+            if isinstance(playout_net_depth, bool) or not isinstance(playout_net_depth, int) or not 1 <= playout_net_depth <= K.PLAYOUT_MAX_DEPTH:
+                raise ValueError("playout_net_depth: None or 1..%d viewer decisions" % K.PLAYOUT_MAX_DEPTH)
         if playout_net_worlds not in ("det", "voids", "hidden"):
             raise ValueError('playout_net_worlds: one of "det", "voids", "hidden"')
         if playout_net_worlds != "det" and not playout_net:
@@ -686,7 +707,9 @@ class SelfPlay:
         if playout_net:
             return own, evaluate_playout_vs_bot(None, n_games, episodes, mix=mix, device=self.env.device_index, worlds=playout_worlds,
                                                 net=self._w, net_seats=playout_net_seats,
-                                                **({} if playout_net_worlds == "det" else dict(net_worlds=playout_net_worlds)))
+                                                **({} if playout_net_worlds == "det" else dict(net_worlds=playout_net_worlds)),
+                                                **({} if playout_net_depth is None else
+                                                   dict(net_depth=playout_net_depth, net_value_scale=1.0 / self.reward_scale)))
         return own, evaluate_playout_vs_bot(int(versus_playout), n_games, episodes, mix=mix, device=self.env.device_index,
                                             worlds=playout_worlds, voids=bool(playout_voids), exchange=playout_exchange,
                                             hidden=bool(playout_hidden), bidding=playout_bidding,
@@ -723,8 +746,13 @@ class SelfPlay:
         env, buf, tc = self.env, self._buf, self.teacher
         if tc["net"]:                                 # the playouts are played by the learner's own rollout weights
             kind = {} if tc["net_worlds"] == "det" else {tc["net_worlds"]: True, "words": self._teach_words}
-            env.playout_cards_net(self._w, tc["worlds"], net_seats=tc["net_seats"], salt=tc["salt"], seats_per_game=self._seats,
-                                  sum_out=self._teach_sums, action_out=self._teach_act, **kind)
+            if "depth" in tc:                         # stopped at the mover's depth-th decision, the value head in points
+                env.playout_cards_net_value(self._w, tc["worlds"], tc["depth"], 1.0 / self.reward_scale, net_seats=tc["net_seats"],
+                                            salt=tc["salt"], seats_per_game=self._seats, sum_out=self._teach_sums,
+                                            action_out=self._teach_act, **kind)
+            else:
+                env.playout_cards_net(self._w, tc["worlds"], net_seats=tc["net_seats"], salt=tc["salt"], seats_per_game=self._seats,
+                                      sum_out=self._teach_sums, action_out=self._teach_act, **kind)
             env.playout_targets(self._teach_sums, buf["words"][t], tc["worlds"], tc["tau"], seats_per_game=self._seats,
                                 target_out=buf["teach"][t])
             return
