@@ -15,6 +15,7 @@ import torch
 
 from . import _native
 from . import karte as K
+from . import playout as P
 
 
 def _u64(t):
@@ -70,46 +71,6 @@ def playout_values(sum, words, samples):
     return torch.where(legal, torch.gather(own, 1, rank), torch.full((), float("-inf"), device=words.device))
 
 
-NET_WORLDS_DET, NET_WORLDS_VOIDS, NET_WORLDS_HIDDEN = 0, 1, 2      # tarok_playout_cards_net_value's `kind`
-
-
-def _playout_cards_net(self, weights, worlds, net_seats, salt, seats, seats_per_game, sum_out, action_out, voids, hidden, words,
-                       depth, value_scale):
-    """TarokVecEnv.playout_cards_net (depth None: the launch of the world kind) and .playout_cards_net_value (an integer
-    depth: tarok_playout_cards_net_value with the kind as a number) — one body, so that the two cannot drift."""
-    given_v, given_h = (x is not None and not isinstance(x, (bool, int)) for x in (voids, hidden))   # a tensor or an array
-    want_v, want_h = given_v or bool(voids), given_h or bool(hidden)
-    if want_v and want_h:
-        raise ValueError("hidden=True is not built together with voids=True: give one of the two")
-    if (want_v and not given_v or want_h and not given_h) and not self.history:
-        raise ValueError("playout_cards_net(%s=True) goes with the play history: TarokVecEnv(history=True)"
-                         % ("voids" if want_v else "hidden"))
-    if not 0 <= int(net_seats) <= 15:
-        raise ValueError("net_seats: a 4-bit seat set, 0..15")
-    w = self.check_mlp_weights(weights)
-    scratch = self.playout_net_scratch(worlds)
-    fn, kind, extra = self.L.tarok_playout_cards_net, NET_WORLDS_DET, ()
-    if want_v:
-        fn, kind = self.L.tarok_playout_cards_net_voids, NET_WORLDS_VOIDS
-        extra = (self._dev(voids if given_v else self.shown_voids(words), torch.int32, (self.n,)),)
-    elif want_h:
-        fn, kind = self.L.tarok_playout_cards_net_hidden, NET_WORLDS_HIDDEN
-        extra = (self._dev(hidden if given_h else self.played_cards(words), torch.int64, (self.n,)),)
-    head = [self._p(t) for t in extra] + [int(net_seats)]
-    if depth is not None:
-        fn = self.L.tarok_playout_cards_net_value
-        head = [kind, self._p(extra[0]) if extra else None, int(net_seats), int(depth), float(value_scale)]
-    with torch.cuda.device(self.device):
-        if sum_out is None:
-            sum_out = torch.empty((self.n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=self.device)
-        if action_out is None:
-            action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
-        _native.check(fn(self._h, int(worlds), int(salt) & ((1 << 64) - 1), int(seats), self._p(self._seat_sets(seats_per_game)),
-                         *head, *[self._p(t) for t in w], self._p(scratch), scratch.numel(), self._p(sum_out), self._p(action_out),
-                         self._stream()))
-    return sum_out, action_out
-
-
 class TarokVecEnv:
     def __init__(self, n_games, device=0, seed=0, mix=K.MIX_ALL, game_offset=0, history=False, refill_fan=None, lazy_refill=None):
         """refill_fan, lazy_refill: launch tuning (tarok_set_option; None = the library's default for the batch size);
@@ -128,7 +89,7 @@ class TarokVecEnv:
         _native.check(L.tarok_create(C.byref(h), self.device_index, self.n, self.game_offset, self.seed, self.mix,
                                      K.HISTORY if history else 0))
         self._h = h
-        self._net_scratch = {}          # playout_cards_net: worlds -> its scratch tensor; the _exchange_net / _bids_net launches: (name, shape)
+        self._net_scratch = {}          # the scratch tensors of the launches that take one, by (name, shape): _scratch
         self.set_option(refill_fan, lazy_refill)
         with torch.cuda.device(self.device):
             self.obs_words = torch.zeros(self.n, dtype=torch.int64, device=self.device)
@@ -200,6 +161,10 @@ class TarokVecEnv:
     def _p(t):
         return None if t is None else C.c_void_p(t.data_ptr())
 
+    def _empty(self, t, shape, dtype):
+        """An output the caller gave, or where it gave None a new uninitialised tensor on the env's device."""
+        return torch.empty(shape, dtype=dtype, device=self.device) if t is None else t
+
     # ------------------------------------------------------------------
     def reset(self, episode=0, deals=None, contract=None, declarer=None, king_suit=None,
               talon_choice=None, discards=None, defer_exchange=False, clear_counters=True):
@@ -261,10 +226,8 @@ class TarokVecEnv:
         """Masked categorical sample from bf16 logits [N,64] (tarok_sample_policy)."""
         assert logits.dtype == torch.bfloat16 and logits.is_contiguous() and tuple(logits.shape) == (self.n, 64)
         with torch.cuda.device(self.device):
-            if action_out is None:
-                action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
-            if logp_out is None:
-                logp_out = torch.empty(self.n, dtype=torch.float32, device=self.device)
+            action_out = self._empty(action_out, self.n, torch.uint8)
+            logp_out = self._empty(logp_out, self.n, torch.float32)
             _native.check(self.L.tarok_sample_policy(self._h, self._p(logits), self._p(obs_words), self._p(action_out),
                                                      self._p(logp_out), self._stream()))
         return action_out, logp_out
@@ -351,17 +314,39 @@ class TarokVecEnv:
                                                       self._p(out.get("actions")), self._stream()))
         return out
 
-    def _playout_cards(self, fn, counts, salt, seats, seats_per_game, words, sum_out, action_out):
-        """One card launch: the native entry point `fn` with `counts` ((samples,) or (worlds, samples)) and the dealer's
-        per-game `words` (a tuple: empty, or one device tensor).  Returns (sum_out, action_out), allocated where None."""
+    def _cards(self, worlds, samples, salt, seats, seats_per_game, sum_out, action_out, voids=False, hidden=False, words=None, net=None):
+        """The one card launch under the seven playout_cards* methods: picks the native entry point of the world kind —
+        worlds None: open hands; voids / hidden True: the env's own words, written into the caller's `words` tensor (None: a
+        new one); a tensor or an array in their place: the words themselves, which need no history — and of the player:
+        net None (the Bot, `samples` playouts per card and world) or (weights, net_seats, depth, value_scale), samples None.
+        Returns (sum_out, action_out), allocated where None."""
+        is_words = lambda x: x is not None and not isinstance(x, (bool, int))          # a tensor or an array
+        want_v, want_h = is_words(voids) or bool(voids), is_words(hidden) or bool(hidden)
+        P.one_world_kind(want_v, want_h)
+        kind = "open" if worlds is None else "voids" if want_v else "hidden" if want_h else "det"
+        given = voids if want_v else hidden
+        if kind in P.WORDS_DTYPE and not is_words(given) and not self.history:
+            raise ValueError("%s=True goes with the play history: TarokVecEnv(history=True)" % kind)
+        name = "tarok_playout_cards" + ("" if net is None else "_net") + ("" if kind == ("open" if net is None else "det") else "_" + kind)
+        if net is not None:
+            weights, net_seats, depth, value_scale = net
+            if not 0 <= int(net_seats) <= 15:
+                raise ValueError("net_seats: a 4-bit seat set, 0..15")
+            w, scratch = self.check_mlp_weights(weights), self.playout_net_scratch(worlds)
+        words = self._dev(given if is_words(given) else (self.shown_voids if want_v else self.played_cards)(words),
+                          P.WORDS_DTYPE[kind], (self.n,)) if kind in P.WORDS_DTYPE else None
+        mid = [] if words is None else [self._p(words)]
+        if net is not None:
+            mid.append(int(net_seats))
+            if depth is not None:
+                name, mid = "tarok_playout_cards_net_value", [P.WORLDS.index(kind), self._p(words), int(net_seats), int(depth), float(value_scale)]
+            mid += [self._p(t) for t in w] + [self._p(scratch), scratch.numel()]
         with torch.cuda.device(self.device):
-            if sum_out is None:
-                sum_out = torch.empty((self.n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=self.device)
-            if action_out is None:
-                action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
-            _native.check(fn(self._h, *[int(c) for c in counts], int(salt) & ((1 << 64) - 1), int(seats),
-                             self._p(self._seat_sets(seats_per_game)), *[self._p(w) for w in words], self._p(sum_out),
-                             self._p(action_out), self._stream()))
+            sum_out = self._empty(sum_out, (self.n, K.PLAYOUT_RANKS, 4), torch.int32)
+            action_out = self._empty(action_out, self.n, torch.uint8)
+            _native.check(getattr(self.L, name)(self._h, *[int(c) for c in (worlds, samples) if c is not None], int(salt) & ((1 << 64) - 1),
+                                                int(seats), self._p(self._seat_sets(seats_per_game)), *mid, self._p(sum_out),
+                                                self._p(action_out), self._stream()))
         return sum_out, action_out
 
     def playout_cards_fair(self, worlds, samples, *, voids=False, hidden=False, words=None, salt=0, seats=15, seats_per_game=None,
@@ -370,16 +355,7 @@ class TarokVecEnv:
         playout_cards_voids on shown_voids(words); hidden=True -> playout_cards_hidden on played_cards(words); otherwise
         playout_cards_det.  words: the caller's scratch tensor for the voids / played words ([N] int32 / int64; None: a
         new one per call), so that a captured rollout allocates nothing.  Everything else as for the launch chosen."""
-        if voids and hidden:
-            raise ValueError("hidden=True is not built together with voids=True: give one of the two")
-        out = dict(salt=salt, seats=seats, seats_per_game=seats_per_game, sum_out=sum_out, action_out=action_out)
-        if not worlds:
-            return self.playout_cards(samples, **out)
-        if voids:
-            return self.playout_cards_voids(worlds, samples, voids=self.shown_voids(words), **out)
-        if hidden:
-            return self.playout_cards_hidden(worlds, samples, played=self.played_cards(words), **out)
-        return self.playout_cards_det(worlds, samples, **out)
+        return self._cards(worlds or None, samples, salt, seats, seats_per_game, sum_out, action_out, bool(voids), bool(hidden), words)
 
     def playout_cards(self, samples, salt=0, seats=15, seats_per_game=None, sum_out=None, action_out=None):
         """Open-hand Monte-Carlo value of every legal card of the seat to move (tarok_playout_cards): each legal card is
@@ -390,7 +366,7 @@ class TarokVecEnv:
         zero rows beyond the legal cards and for games that do not take part — and action [N] uint8: the first card at
         the maximum of the mover's sums, the Bot's card where the mover is outside `seats` / `seats_per_game` (as in
         policy_step), 255 where nothing is to be played).  Read-only on the env; `salt` varies the playouts' draws."""
-        return self._playout_cards(self.L.tarok_playout_cards, (samples,), salt, seats, seats_per_game, (), sum_out, action_out)
+        return self._cards(None, samples, salt, seats, seats_per_game, sum_out, action_out)
 
     def playout_cards_det(self, worlds, samples, salt=0, seats=15, seats_per_game=None, sum_out=None, action_out=None):
         """Determinized Monte-Carlo value of every legal card of the seat to move (tarok_playout_cards_det): the FAIR
@@ -400,7 +376,7 @@ class TarokVecEnv:
         its hand, the table, the won piles, the talon ids, the contract, the declarer and the called suit.  Where a
         called king is among the unseen cards the world's team is the declarer and whoever was dealt it.
         Outputs, `seats` / `seats_per_game`, `salt` and the read-only contract: as for playout_cards."""
-        return self._playout_cards(self.L.tarok_playout_cards_det, (worlds, samples), salt, seats, seats_per_game, (), sum_out, action_out)
+        return self._cards(worlds, samples, salt, seats, seats_per_game, sum_out, action_out)
 
     def playout_net_scratch(self, worlds):
         """The scratch tensor of playout_cards_net at `worlds` (uint8, tarok_playout_net_scratch bytes), cached on the env
@@ -408,14 +384,7 @@ class TarokVecEnv:
         worlds = int(worlds)
         if not 1 <= worlds <= K.PLAYOUT_MAX_WORLDS:
             raise ValueError("worlds: 1..%d" % K.PLAYOUT_MAX_WORLDS)
-        cache = self._net_scratch
-        if worlds not in cache:
-            size = int(self.L.tarok_playout_net_scratch(self._h, worlds))
-            if size < 0:
-                _native.check(size)
-            with torch.cuda.device(self.device):
-                cache[worlds] = torch.empty(size, dtype=torch.uint8, device=self.device)
-        return cache[worlds]
+        return self._scratch(("cards", worlds), self.L.tarok_playout_net_scratch, worlds)
 
     def playout_cards_net(self, weights, worlds, net_seats=15, salt=0, seats=15, seats_per_game=None, sum_out=None, action_out=None,
                           voids=False, hidden=False, words=None):
@@ -433,8 +402,7 @@ class TarokVecEnv:
         playout_cards_voids(voids=...) takes them, and needs no history.  words: the caller's scratch tensor for the
         env's own words (None: a new one per call), so that a captured launch allocates nothing.  Not both: the two
         kinds do not compose.  The defaults issue tarok_playout_cards_net."""
-        return _playout_cards_net(self, weights, worlds, net_seats, salt, seats, seats_per_game, sum_out, action_out, voids, hidden,
-                                  words, None, 0.0)
+        return self._cards(worlds, None, salt, seats, seats_per_game, sum_out, action_out, voids, hidden, words, (weights, net_seats, None, 0.0))
 
     def playout_cards_net_value(self, weights, worlds, depth, value_scale=70.0, net_seats=15, salt=0, seats=15, seats_per_game=None,
                                 sum_out=None, action_out=None, voids=False, hidden=False, words=None):
@@ -449,12 +417,9 @@ class TarokVecEnv:
         Everything else — worlds, voids= / hidden= / words=, the scratch, the outputs — is playout_cards_net's; depth=None
         IS playout_cards_net."""
         if depth is not None:
-            if isinstance(depth, bool) or int(depth) != depth or not 1 <= int(depth) <= K.PLAYOUT_MAX_DEPTH:
-                raise ValueError("depth: None or 1..%d viewer decisions" % K.PLAYOUT_MAX_DEPTH)
-            if not (float(value_scale) > 0 and float(value_scale) < float("inf")):
-                raise ValueError("value_scale: finite and > 0")
-        return _playout_cards_net(self, weights, worlds, net_seats, salt, seats, seats_per_game, sum_out, action_out, voids, hidden,
-                                  words, depth, value_scale)
+            P.check_depth(depth, value_scale)
+        return self._cards(worlds, None, salt, seats, seats_per_game, sum_out, action_out, voids, hidden, words,
+                           (weights, net_seats, depth, value_scale))
 
     def playout_exchange(self, worlds, samples, discard_sets=4, salt=0, seats=15, seats_per_game=None, sum_out=None,
                          choice_out=None, discards_out=None):
@@ -468,12 +433,9 @@ class TarokVecEnv:
         with its declarer outside the set; -1 and 255s elsewhere).  exchange(choice, discards) applies them — a mixed
         table in one call.  Read-only on the env; `salt` varies the draws."""
         with torch.cuda.device(self.device):
-            if sum_out is None:
-                sum_out = torch.empty((self.n, 6 * int(discard_sets), 4), dtype=torch.int32, device=self.device)
-            if choice_out is None:
-                choice_out = torch.empty(self.n, dtype=torch.int8, device=self.device)
-            if discards_out is None:
-                discards_out = torch.empty((self.n, 3), dtype=torch.uint8, device=self.device)
+            sum_out = self._empty(sum_out, (self.n, 6 * int(discard_sets), 4), torch.int32)
+            choice_out = self._empty(choice_out, self.n, torch.int8)
+            discards_out = self._empty(discards_out, (self.n, 3), torch.uint8)
             _native.check(self.L.tarok_playout_exchange(self._h, int(worlds), int(samples), int(discard_sets),
                                                         int(salt) & ((1 << 64) - 1), int(seats),
                                                         self._p(self._seat_sets(seats_per_game)), self._p(sum_out),
@@ -495,15 +457,14 @@ class TarokVecEnv:
         deals = self._dev(deals, torch.uint8, (self.n, 54))
         launch = self.L.tarok_playout_bids_pass if pass_value else self.L.tarok_playout_bids
         with torch.cuda.device(self.device):
-            if sum_out is None:
-                sum_out = torch.empty((self.n, 4, K.BID_ROWS), dtype=torch.int32, device=self.device)
+            sum_out = self._empty(sum_out, (self.n, 4, K.BID_ROWS), torch.int32)
             _native.check(launch(self._h, int(episode), self._p(deals), int(worlds), int(samples), int(contracts),
                                  int(salt) & ((1 << 64) - 1), int(seats),
                                  self._p(self._seat_sets(seats_per_game)), self._p(sum_out), self._stream()))
         return sum_out
 
-    def _front_net_scratch(self, key, size_fn, *sizes):
-        """The cached scratch tensor of a front-end net launch: `key` names the launch and its shape in _net_scratch."""
+    def _scratch(self, key, size_fn, *sizes):
+        """The cached scratch tensor of a launch that takes one: `key` names the launch and its shape in _net_scratch."""
         cache = self._net_scratch
         if key not in cache:
             size = int(size_fn(self._h, *sizes))
@@ -521,7 +482,7 @@ class TarokVecEnv:
             raise ValueError("worlds: 1..%d" % K.PLAYOUT_MAX_WORLDS)
         if not 1 <= discard_sets <= K.EXCHANGE_MAX_SETS:
             raise ValueError("discard_sets: 1..%d" % K.EXCHANGE_MAX_SETS)
-        return self._front_net_scratch(("exchange", worlds, discard_sets), self.L.tarok_playout_exchange_net_scratch, worlds, discard_sets)
+        return self._scratch(("exchange", worlds, discard_sets), self.L.tarok_playout_exchange_net_scratch, worlds, discard_sets)
 
     def playout_exchange_net(self, weights, worlds, discard_sets=4, net_seats=15, salt=0, seats=15, seats_per_game=None, sum_out=None,
                              choice_out=None, discards_out=None):
@@ -536,12 +497,9 @@ class TarokVecEnv:
         w = self.check_mlp_weights(weights)
         scratch = self.playout_exchange_net_scratch(worlds, discard_sets)
         with torch.cuda.device(self.device):
-            if sum_out is None:
-                sum_out = torch.empty((self.n, 6 * int(discard_sets), 4), dtype=torch.int32, device=self.device)
-            if choice_out is None:
-                choice_out = torch.empty(self.n, dtype=torch.int8, device=self.device)
-            if discards_out is None:
-                discards_out = torch.empty((self.n, 3), dtype=torch.uint8, device=self.device)
+            sum_out = self._empty(sum_out, (self.n, 6 * int(discard_sets), 4), torch.int32)
+            choice_out = self._empty(choice_out, self.n, torch.int8)
+            discards_out = self._empty(discards_out, (self.n, 3), torch.uint8)
             _native.check(self.L.tarok_playout_exchange_net(self._h, int(worlds), int(discard_sets), int(salt) & ((1 << 64) - 1),
                                                             int(seats), self._p(self._seat_sets(seats_per_game)), int(net_seats),
                                                             *[self._p(t) for t in w], self._p(scratch), scratch.numel(),
@@ -555,7 +513,7 @@ class TarokVecEnv:
         worlds = int(worlds)
         if not 1 <= worlds <= K.PLAYOUT_MAX_WORLDS:
             raise ValueError("worlds: 1..%d" % K.PLAYOUT_MAX_WORLDS)
-        return self._front_net_scratch(("bids", worlds), self.L.tarok_playout_bids_net_scratch, worlds)
+        return self._scratch(("bids", worlds), self.L.tarok_playout_bids_net_scratch, worlds)
 
     def playout_bids_net(self, weights, episode, worlds, net_seats=15, contracts=K.BID_DEFAULT_CONTRACTS, deals=None, salt=0, seats=15,
                          seats_per_game=None, sum_out=None):
@@ -571,8 +529,7 @@ class TarokVecEnv:
         scratch = self.playout_bids_net_scratch(worlds)
         deals = self._dev(deals, torch.uint8, (self.n, 54))
         with torch.cuda.device(self.device):
-            if sum_out is None:
-                sum_out = torch.empty((self.n, 4, K.BID_ROWS), dtype=torch.int32, device=self.device)
+            sum_out = self._empty(sum_out, (self.n, 4, K.BID_ROWS), torch.int32)
             _native.check(self.L.tarok_playout_bids_net(self._h, int(episode), self._p(deals), int(worlds), int(contracts),
                                                         int(salt) & ((1 << 64) - 1), int(seats),
                                                         self._p(self._seat_sets(seats_per_game)), int(net_seats),
@@ -617,8 +574,7 @@ class TarokVecEnv:
         deals = self._dev(deals, torch.uint8, (self.n, 54))
         launch = self.L.tarok_bid_values_pass if pass_value else self.L.tarok_bid_values
         with torch.cuda.device(self.device):
-            if value_out is None:
-                value_out = torch.empty((self.n, 4, K.BID_ROWS), dtype=torch.int32, device=self.device)
+            value_out = self._empty(value_out, (self.n, 4, K.BID_ROWS), torch.int32)
             raw_out = torch.empty((self.n, 4, K.BID_ROWS), dtype=torch.float32, device=self.device) if raw else None
             fw_out = torch.empty((self.n, 4, 4), dtype=torch.int64, device=self.device) if feature_words else None
             _native.check(launch(self._h, int(episode), self._p(deals), self._p(w1), self._p(b1), self._p(w2),
@@ -644,10 +600,8 @@ class TarokVecEnv:
         for what was not asked for.  Read-only on the env."""
         w1, b1, w2, b2, w3, b3 = self.check_mlp_weights(weights)
         with torch.cuda.device(self.device):
-            if choice_out is None:
-                choice_out = torch.empty(self.n, dtype=torch.int8, device=self.device)
-            if discards_out is None:
-                discards_out = torch.empty((self.n, 3), dtype=torch.uint8, device=self.device)
+            choice_out = self._empty(choice_out, self.n, torch.int8)
+            discards_out = self._empty(discards_out, (self.n, 3), torch.uint8)
             raw_out = torch.empty((self.n, 8, 64), dtype=torch.float32, device=self.device) if raw else None
             fw_out = torch.empty((self.n, 8, 4), dtype=torch.int64, device=self.device) if feature_words else None
             _native.check(self.L.tarok_exchange_values(self._h, self._p(w1), self._p(b1), self._p(w2), self._p(b2), self._p(w3),
@@ -661,7 +615,7 @@ class TarokVecEnv:
     def front_lines_scratch(self):
         """The scratch tensor of front_lines (uint8, tarok_front_lines_scratch_bytes), cached on the env: a caller that
         captures the call asks for it BEFORE the capture."""
-        return self._front_net_scratch(("front_lines",), lambda h, n: self.L.tarok_front_lines_scratch_bytes(n), self.n)
+        return self._scratch(("front_lines",), lambda h, n: self.L.tarok_front_lines_scratch_bytes(n), self.n)
 
     def front_lines(self, bid=None, exchange=None, scale=None, contracts=K.BID_DEFAULT_CONTRACTS, margin=0, pass_value=False, seats=15,
                     seats_per_game=None, count_out=None, hist_out=None, playouts=1):
@@ -735,8 +689,7 @@ class TarokVecEnv:
         if not self.history:
             raise ValueError("shown_voids reads the play history: TarokVecEnv(history=True)")
         with torch.cuda.device(self.device):
-            if out is None:
-                out = torch.empty(self.n, dtype=torch.int32, device=self.device)
+            out = self._empty(out, self.n, torch.int32)
             _native.check(self.L.tarok_shown_voids(self._h, self._p(out), self._stream()))
         return out
 
@@ -748,10 +701,7 @@ class TarokVecEnv:
         Everything else as for playout_cards_det; world w is another deal than there unless the game shows no void."""
         if not self.history:
             raise ValueError("playout_cards_voids goes with the play history: TarokVecEnv(history=True)")
-        if voids is None:
-            voids = self.shown_voids()
-        return self._playout_cards(self.L.tarok_playout_cards_voids, (worlds, samples), salt, seats, seats_per_game,
-                                   (self._dev(voids, torch.int32, (self.n,)),), sum_out, action_out)
+        return self._cards(worlds, samples, salt, seats, seats_per_game, sum_out, action_out, voids=self.shown_voids() if voids is None else voids)
 
     def played_cards(self, out=None):
         """[N] int64 device tensor (tarok_played_cards; the bits of a u64): bit c of a game's word is set iff card c is in
@@ -760,8 +710,7 @@ class TarokVecEnv:
         if not self.history:
             raise ValueError("played_cards reads the play history: TarokVecEnv(history=True)")
         with torch.cuda.device(self.device):
-            if out is None:
-                out = torch.empty(self.n, dtype=torch.int64, device=self.device)
+            out = self._empty(out, self.n, torch.int64)
             _native.check(self.L.tarok_played_cards(self._h, self._p(out), self._stream()))
         return out
 
@@ -773,10 +722,7 @@ class TarokVecEnv:
         TarokVecEnv(history=True).  Everything else as for playout_cards_det."""
         if not self.history:
             raise ValueError("playout_cards_hidden goes with the play history: TarokVecEnv(history=True)")
-        if played is None:
-            played = self.played_cards()
-        return self._playout_cards(self.L.tarok_playout_cards_hidden, (worlds, samples), salt, seats, seats_per_game,
-                                   (self._dev(played, torch.int64, (self.n,)),), sum_out, action_out)
+        return self._cards(worlds, samples, salt, seats, seats_per_game, sum_out, action_out, hidden=self.played_cards() if played is None else played)
 
     def playout_targets(self, sums, obs_words, playouts, tau, seats=15, seats_per_game=None, target_out=None):
         """A playout launch's sums as a teacher's target rows (tarok_playout_targets): target [N,64] bf16, for a game with
@@ -786,8 +732,7 @@ class TarokVecEnv:
         samples (x worlds), seats / seats_per_game as given to the playout launch.  Stream-ordered; allocates nothing when
         target_out is given."""
         with torch.cuda.device(self.device):
-            if target_out is None:
-                target_out = torch.empty((self.n, 64), dtype=torch.bfloat16, device=self.device)
+            target_out = self._empty(target_out, (self.n, 64), torch.bfloat16)
             _native.check(self.L.tarok_playout_targets(self._h, self._p(sums), self._p(obs_words), int(playouts), float(tau), int(seats),
                                                        self._p(self._seat_sets(seats_per_game)), self._p(target_out), self._stream()))
         return target_out
@@ -795,8 +740,7 @@ class TarokVecEnv:
     def observe(self, out=None):
         """[N,256] bf16 features of the seat to move (include/tarok_env.h tarok_observe)."""
         with torch.cuda.device(self.device):
-            if out is None:
-                out = torch.empty((self.n, 256), dtype=torch.bfloat16, device=self.device)
+            out = self._empty(out, (self.n, 256), torch.bfloat16)
             _native.check(self.L.tarok_observe(self._h, self._p(out), self._stream()))
         return out
 
@@ -805,10 +749,8 @@ class TarokVecEnv:
         Igralec.py:453-533).  Returns (record [N, REF_RECORD_BYTES] u8, meta [N,4] i32 = T, type, rows
         used, seat); `ref_views` slices the record into the reference's tensors."""
         with torch.cuda.device(self.device):
-            if out is None:
-                out = torch.empty((self.n, K.REF_RECORD_BYTES), dtype=torch.uint8, device=self.device)
-            if meta is None:
-                meta = torch.empty((self.n, 4), dtype=torch.int32, device=self.device)
+            out = self._empty(out, (self.n, K.REF_RECORD_BYTES), torch.uint8)
+            meta = self._empty(meta, (self.n, 4), torch.int32)
             _native.check(self.L.tarok_observe_ref(self._h, self._p(out), self._p(meta), self._stream()))
         return out, meta
 
@@ -828,16 +770,14 @@ class TarokVecEnv:
         """menjaj_talon_v_vektor (Igralec.py:535-543) for the games waiting for the exchange:
         [N, REF_EXCHANGE_BYTES] u8 = roka 54 | talon (54,6) | igra 15 | pad."""
         with torch.cuda.device(self.device):
-            if out is None:
-                out = torch.empty((self.n, K.REF_EXCHANGE_BYTES), dtype=torch.uint8, device=self.device)
+            out = self._empty(out, (self.n, K.REF_EXCHANGE_BYTES), torch.uint8)
             _native.check(self.L.tarok_observe_exchange_ref(self._h, self._p(out), self._stream()))
         return out
 
     def observe_hands_ref(self, out=None):
         """The bidding input (Igralec.py:278-281): [N,4,54] u8, every seat's hand one-hot."""
         with torch.cuda.device(self.device):
-            if out is None:
-                out = torch.empty((self.n, 4, 54), dtype=torch.uint8, device=self.device)
+            out = self._empty(out, (self.n, 4, 54), torch.uint8)
             _native.check(self.L.tarok_observe_hands_ref(self._h, self._p(out), self._stream()))
         return out
 
@@ -879,12 +819,9 @@ class TarokVecEnv:
         as bits: expand_feature_words) receive the network input for the learner."""
         w1, b1, w2, b2, w3, b3 = self.check_mlp_weights(weights)
         with torch.cuda.device(self.device):
-            if action_out is None:
-                action_out = torch.empty(self.n, dtype=torch.uint8, device=self.device)
-            if logp_out is None:
-                logp_out = torch.empty(self.n, dtype=torch.float32, device=self.device)
-            if value_out is None:
-                value_out = torch.empty(self.n, dtype=torch.float32, device=self.device)
+            action_out = self._empty(action_out, self.n, torch.uint8)
+            logp_out = self._empty(logp_out, self.n, torch.float32)
+            value_out = self._empty(value_out, self.n, torch.float32)
             _native.check(self.L.tarok_policy_mlp(self._h, self._p(w1), self._p(b1), self._p(w2), self._p(b2), self._p(w3),
                                                   self._p(b3), self._p(obs_words), self._p(action_out), self._p(logp_out),
                                                   self._p(value_out), self._p(features_out), self._p(feature_words_out),
@@ -1086,8 +1023,7 @@ class TarokVecEnv:
         fw = feature_words.contiguous()
         B = fw.shape[0] if index is None else index.shape[0]
         with torch.cuda.device(self.device):
-            if out is None:
-                out = torch.empty((B, 256), dtype=torch.bfloat16, device=self.device)
+            out = self._empty(out, (B, 256), torch.bfloat16)
             idx = None if index is None else index.to(torch.int64).contiguous()
             _native.check(self.L.tarok_expand_features(self._h, int(B), self._p(fw), self._p(idx), self._p(out), self._stream()))
         return out

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import karte as K
+from . import playout
 from .env import TarokVecEnv
 
 PASS_SEATS = (0, 1, 2, 4, 8)      # the seat set of pass p: Bot everywhere, then the network on seat p - 1 alone
@@ -345,9 +346,6 @@ def evaluate_vs_pool(weights, pool, n_games, episodes, seed=0, mix=K.MIX_BOT, de
     return [duplicate_advantage(pool_block_scores(scores, j, n, k)) for j in range(k)]
 
 
-NET_WORLDS = ("det", "voids", "hidden")           # the world kinds of the net-played card launch (net_worlds=)
-
-
 def _bid_args(bidding, mix):
     if bidding is None:
         return None
@@ -382,57 +380,22 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     net_depth=D (with net): the launch is playout_cards_net_value at depth D and net_value_scale in the same worlds — the
     playouts stop at the player's D-th next decision and take the value head's estimate; None: the calls as they were.
     inspect: as in _play_passes_mode."""
-    if net_depth is not None:
-        if net is None:
-            raise ValueError("net_depth stops the network's playouts: it goes with net=weights")
-        if isinstance(net_depth, bool) or not isinstance(net_depth, int) or not 1 <= net_depth <= K.PLAYOUT_MAX_DEPTH:
-            raise ValueError("net_depth: None or 1..%d viewer decisions" % K.PLAYOUT_MAX_DEPTH)
-        if not 0 < float(net_value_scale) < float("inf"):
-            raise ValueError("net_value_scale: finite and > 0")
-    if net_worlds not in NET_WORLDS:
-        raise ValueError('net_worlds: one of "det", "voids", "hidden"')
-    if net is None and net_worlds != "det":
-        raise ValueError("net_worlds names the worlds of the network's playouts: it goes with net=weights")
+    player = playout.card_player(samples, worlds, voids, hidden, net is not None, net_seats, net_worlds, net_depth, net_value_scale, salt,
+                                 front=exchange is not None or bidding is not None)
     if net is not None:
-        if worlds is None:
-            raise ValueError("net= plays the determinized player's playouts: give worlds= as well")
         if samples is not None:
             raise ValueError("net= runs one playout per (card, world): samples is not taken (pass None)")
-        if voids or hidden or exchange is not None or bidding is not None:
-            raise ValueError("net= composes with nothing else yet: no voids, hidden, exchange or bidding")
-        if net_seats != "own" and not (isinstance(net_seats, int) and 0 <= net_seats <= 15):
-            raise ValueError('net_seats: a 4-bit seat set, 0..15, or "own"')
         net = TarokVecEnv.check_mlp_weights(net)
-    if voids and worlds is None:
-        raise ValueError("voids=True constrains the re-deals: give worlds= as well")
-    if hidden and worlds is None:
-        raise ValueError("hidden=True widens the re-deals: give worlds= as well")
-    if hidden and voids:
-        raise ValueError("hidden=True is not built together with voids=True: give one of the two")
     if exchange is not None and worlds is None:
         raise ValueError("exchange=D is the fair player's front end: give worlds= as well")
     if bidding is not None and worlds is None:
         raise ValueError("bidding=(W, S) is the fair player's front end: give worlds= as well")
     bidding = _bid_args(bidding, mix)
-    def launch(env, seats, **kw):                     # net_depth=None: exactly the calls as they were
-        kw = dict(net_seats=seats if net_seats == "own" else net_seats, salt=salt, seats=seats, **kw)
-        if net_depth is None:
-            return env.playout_cards_net(net, worlds, **kw)
-        return env.playout_cards_net_value(net, worlds, net_depth, float(net_value_scale), **kw)
-    if net is not None and net_worlds != "det":
-        kind = {net_worlds: True}
-        cards = _playout_cards(lambda env, seats, words, sums, row: launch(env, seats, sum_out=sums, action_out=row, words=words, **kind),
-                               words_dtype=torch.int32 if net_worlds == "voids" else torch.int64)
-    elif net is not None:
-        cards = _playout_cards(lambda env, seats, words, sums, row: launch(env, seats, sum_out=sums, action_out=row))
-    else:
-        cards = _playout_cards(lambda env, seats, words, sums, row: env.playout_cards_fair(
-            worlds, samples, voids=voids, hidden=hidden, words=words, salt=salt, seats=seats, sum_out=sums, action_out=row),
-            words_dtype=(torch.int32 if voids else torch.int64) if voids or hidden else None)
+    cards = _playout_cards(lambda env, seats, words, sums, row: player.launch(env, net, dict(seats=seats), words, sums, row),
+                           words_dtype=player.words_dtype)
     front = _front(inspect is not None, bid=None if bidding is None else _bid_front(bidding, salt, threshold, contracts, pass_value),
                    exchange=None if exchange is None else _exchange_front(worlds, samples, exchange, salt))
-    return _passes(n_games, episodes, front, cards, inspect, device=device, seed=seed, mix=mix,
-                   history=bool(voids or hidden or net_worlds != "det"))
+    return _passes(n_games, episodes, front, cards, inspect, device=device, seed=seed, mix=mix, history=player.needs_history)
 
 
 def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None,

@@ -1,0 +1,102 @@
+"""The playout card player, described once: what SelfPlay(teacher=dict(...)), SelfPlay.evaluate(playout_*=...) and
+evaluate.evaluate_playout_vs_bot(...) each spell in their own words.  card_player() holds every rule of the options and
+returns a CardPlayer; the CardPlayer knows what its launch needs (history, the words tensor, the net scratch, the divisor
+of tarok_playout_targets) and issues it through the env's public method of its kind.  A door keeps only the rules that
+are its own (tau and every; versus_playout; exchange and bidding) and names the options its way through spelling()."""
+import collections
+import numbers
+
+import torch
+
+from . import karte as K
+
+WORLDS = ("det", "voids", "hidden")               # the fair world kinds; the position is tarok_playout_cards_net_value's `kind`
+WORDS_DTYPE = dict(voids=torch.int32, hidden=torch.int64)      # the per-game words a kind reads: shown_voids() / played_cards()
+OPTIONS = ("samples", "worlds", "voids", "hidden", "exchange", "bidding", "net", "net_seats", "net_worlds", "net_depth", "net_value_scale")
+
+
+def spelling(prefix="", pattern="%s", **other):
+    """How a door words a refusal: `prefix`, then the text with every {option} of OPTIONS replaced by other[option] or
+    pattern % option.  The default is evaluate_playout_vs_bot's spelling."""
+    names = {k: other.get(k, pattern % k) for k in OPTIONS}
+    return lambda text: prefix + text.format(**names)
+
+
+def one_world_kind(voids, hidden, say=spelling()):
+    if voids and hidden:
+        raise ValueError(say("{hidden}=True is not built together with {voids}=True: give one of the two"))
+
+
+def check_depth(depth, value_scale, say=spelling(net_depth="depth", net_value_scale="value_scale")):
+    if isinstance(depth, bool) or not isinstance(depth, numbers.Integral) or not 1 <= depth <= K.PLAYOUT_MAX_DEPTH:
+        raise ValueError(say("{net_depth}: None or 1..%d viewer decisions" % K.PLAYOUT_MAX_DEPTH))
+    if not 0 < float(value_scale) < float("inf"):
+        raise ValueError(say("{net_value_scale}: finite and > 0"))
+
+
+class CardPlayer(collections.namedtuple("CardPlayer", "kind worlds samples net net_seats depth value_scale salt")):
+    """kind: "open" (the true hands) or one of WORLDS; worlds as the door gave it (None or 0 for "open"), samples per
+    (card, world); net: the playouts are played by a network on net_seats (a set 0..15, or "own": the launch's own seats),
+    stopped at the viewer's depth-th decision (None: never) with the value head at value_scale points per unit."""
+    __slots__ = ()
+
+    needs_history = property(lambda self: self.kind in WORDS_DTYPE)
+    words_dtype = property(lambda self: WORDS_DTYPE.get(self.kind))
+    playouts = property(lambda self: max(1, self.worlds or 0) * self.samples)       # tarok_playout_targets' divisor
+
+    def prepare(self, env):
+        """What has to exist before the launch is captured into a graph: the net launch's scratch."""
+        if self.net:
+            env.playout_net_scratch(self.worlds)
+
+    def launch(self, env, weights, sets, words, sum_out, action_out):
+        """The player's launch on `env`: sets = dict(seats=...) or dict(seats_per_game=...), words the caller's tensor of
+        words_dtype (None where there is none), weights the network's six tensors (net players only)."""
+        out = dict(salt=self.salt, sum_out=sum_out, action_out=action_out, **sets)
+        if not self.net:
+            return env.playout_cards_fair(self.worlds, self.samples, voids=self.kind == "voids", hidden=self.kind == "hidden", words=words, **out)
+        out.update(net_seats=sets["seats"] if self.net_seats == "own" else self.net_seats)
+        if self.needs_history:
+            out.update({self.kind: True, "words": words})
+        if self.depth is None:
+            return env.playout_cards_net(weights, self.worlds, **out)
+        return env.playout_cards_net_value(weights, self.worlds, self.depth, self.value_scale, **out)
+
+
+def card_player(samples=None, worlds=None, voids=False, hidden=False, net=False, net_seats=15, net_worlds="det", net_depth=None,
+                net_value_scale=70.0, salt=0, front=False, fused=True, history=None, own=True, say=spelling()):
+    """The one validator of a card player's options, in evaluate_playout_vs_bot's names: a CardPlayer, or a ValueError in
+    the door's words (say: spelling()).  samples None: 1.  front: the door also asked for a playout-valued exchange or
+    bidding.  fused: the door's policy is the fused one.  history: whether the env at hand keeps the play history (None:
+    the door makes its env as needs_history says).  own: the door takes net_seats="own"."""
+    if net_depth is not None:
+        if not net:
+            raise ValueError(say("{net_depth} stops the network's playouts: it goes with {net}="))
+        check_depth(net_depth, net_value_scale, say)
+    if net_worlds not in WORLDS:
+        raise ValueError(say("{net_worlds}: one of %s" % ", ".join('"%s"' % w for w in WORLDS)))
+    if net_worlds != "det" and not net:
+        raise ValueError(say("{net_worlds} names the worlds of the network's playouts: it goes with {net}="))
+    if net:
+        if not worlds:
+            raise ValueError(say("{net}= plays the determinized player's playouts: give {worlds}= as well"))
+        if samples not in (None, 1):
+            raise ValueError(say("{net}= runs one playout per (card, world): {samples} is optional and must be 1"))
+        if voids or hidden or front:
+            raise ValueError(say("{net}= composes with nothing else yet: no {voids}, {hidden}, {exchange} or {bidding}"))
+        if not (own and net_seats == "own") and not (isinstance(net_seats, int) and 0 <= net_seats <= 15):
+            raise ValueError(say("{net_seats}: a 4-bit seat set, 0..15" + ', or "own"' * own))
+        if not fused:
+            raise ValueError(say("{net}= plays tarok_playout_cards_net, which needs the fused policy (hidden = 256)"))
+    if voids and not worlds:
+        raise ValueError(say("{voids}=True constrains the re-deals: give {worlds}= as well"))
+    if hidden and not worlds:
+        raise ValueError(say("{hidden}=True widens the re-deals: give {worlds}= as well"))
+    one_world_kind(voids, hidden, say)
+    samples, worlds = 1 if samples is None else int(samples), None if worlds is None else int(worlds)
+    if not (0 <= (worlds or 0) <= K.PLAYOUT_MAX_WORLDS and 1 <= samples <= K.PLAYOUT_MAX_SAMPLES):
+        raise ValueError(say("{worlds} 0..%d, {samples} 1..%d" % (K.PLAYOUT_MAX_WORLDS, K.PLAYOUT_MAX_SAMPLES)))
+    kind = "open" if not worlds else "voids" if voids else "hidden" if hidden else net_worlds
+    if kind in WORDS_DTYPE and history is not None and not history:
+        raise ValueError(say("the %s worlds read the play history: TarokVecEnv(history=True)" % kind))
+    return CardPlayer(kind, worlds, samples, bool(net), net_seats, net_depth, float(net_value_scale), int(salt))

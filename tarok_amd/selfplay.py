@@ -26,6 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import karte as K
+from . import playout
 from . import sharding
 
 
@@ -325,59 +326,26 @@ class SelfPlay:
                                    "and the fused step")
             if isinstance(learner_seats, int) and not 0 <= learner_seats <= 15:
                 raise ValueError("learner_seats: a seat set 0..15 or a [N] uint8 tensor of sets")
-        self.teacher, self.distill_coef = None, float(distill_coef)
-        if teacher is not None:
+        self.teacher, self._player, self.distill_coef = None, None, float(distill_coef)
+        if teacher is not None:                       # the card player is playout.card_player's; tau and every are the teacher's own
             unknown = set(teacher) - {"worlds", "samples", "tau", "every", "salt", "voids", "hidden", "net", "net_seats", "net_worlds", "depth"}
             net = bool(teacher.get("net", False))
             if unknown or ("samples" not in teacher and not net):
                 raise ValueError("teacher: dict(worlds=W, samples=S, tau=tau, every=k, salt=...), samples required; unknown keys %s" % sorted(unknown))
-            t = dict(worlds=int(teacher.get("worlds", 0)), samples=int(teacher.get("samples", 1)), tau=float(teacher.get("tau", 1.0)),
-                     every=int(teacher.get("every", 1)), salt=int(teacher.get("salt", 0)), voids=bool(teacher.get("voids", False)),
-                     hidden=bool(teacher.get("hidden", False)), net=net, net_seats=int(teacher.get("net_seats", 15)),
-                     net_worlds=teacher.get("net_worlds", "det"))
             if "net_seats" in teacher and not net:
                 raise ValueError("teacher: net_seats names the network's seats inside the playouts: it goes with net=True")
-            if t["net_worlds"] not in ("det", "voids", "hidden"):
-                raise ValueError('teacher: net_worlds is one of "det", "voids", "hidden"')
-            if "net_worlds" in teacher and not net:
-                raise ValueError("teacher: net_worlds names the worlds of the network's playouts: it goes with net=True")
-            if teacher.get("depth") is not None:          # (the key is kept only where it was given: a teacher without it is unchanged)
-                d = teacher["depth"]
-                if not net:
-                    raise ValueError("teacher: depth stops the network's playouts at the mover's depth-th decision: it goes with net=True")
-                if isinstance(d, bool) or not isinstance(d, int) or not 1 <= d <= K.PLAYOUT_MAX_DEPTH:
-                    raise ValueError("teacher: depth is 1..%d viewer decisions" % K.PLAYOUT_MAX_DEPTH)
-                if not 0 < float(reward_scale) < float("inf"):
-                    raise ValueError("teacher: depth reads the value head in units of reward_scale, which must be finite and > 0")
-                t["depth"] = d
-            if net:
-                if t["samples"] != 1:
-                    raise ValueError("teacher: net=True runs one playout per (card, world): samples is optional and must be 1")
-                if t["worlds"] < 1:
-                    raise ValueError("teacher: net=True plays the determinized worlds: worlds >= 1")
-                if t["voids"] or t["hidden"]:
-                    raise ValueError("teacher: net=True is not built together with voids=True or hidden=True")
-                if not 0 <= t["net_seats"] <= 15:
-                    raise ValueError("teacher: net_seats is a 4-bit seat set, 0..15")
-                if not ((hidden == 256) if fused is None else bool(fused)):
-                    raise ValueError("teacher: net=True plays tarok_playout_cards_net, which needs the fused policy (hidden = 256)")
-                if t["net_worlds"] != "det" and not env.history:
-                    raise ValueError("teacher: net_worlds=%r reads the play history: TarokVecEnv(history=True)" % t["net_worlds"])
-            if not (0 <= t["worlds"] <= K.PLAYOUT_MAX_WORLDS and 1 <= t["samples"] <= K.PLAYOUT_MAX_SAMPLES and t["every"] >= 1
-                    and 0.0 <= t["tau"] < float("inf")):
-                raise ValueError("teacher: worlds 0..%d, samples 1..%d, tau >= 0 and finite, every >= 1"
-                                 % (K.PLAYOUT_MAX_WORLDS, K.PLAYOUT_MAX_SAMPLES))
-            if t["voids"] and not t["worlds"]:
-                raise ValueError("teacher: voids=True constrains the re-deals, so it goes with worlds >= 1")
-            if t["voids"] and not env.history:
-                raise ValueError("teacher: voids=True reads the play history: TarokVecEnv(history=True)")
-            if t["hidden"] and not t["worlds"]:
-                raise ValueError("teacher: hidden=True widens the re-deals, so it goes with worlds >= 1")
-            if t["hidden"] and t["voids"]:
-                raise ValueError("teacher: hidden=True is not built together with voids=True: give one of the two")
-            if t["hidden"] and not env.history:
-                raise ValueError("teacher: hidden=True reads the play history: TarokVecEnv(history=True)")
-            self.teacher = t
+            p = playout.card_player(int(teacher.get("samples", 1)), int(teacher.get("worlds", 0)), bool(teacher.get("voids", False)),
+                                    bool(teacher.get("hidden", False)), net, int(teacher.get("net_seats", 15)), teacher.get("net_worlds", "det"),
+                                    teacher.get("depth"), 1.0 / reward_scale if reward_scale else 0.0, int(teacher.get("salt", 0)),
+                                    fused=(hidden == 256) if fused is None else bool(fused), history=getattr(env, "history", False), own=False,
+                                    say=playout.spelling("teacher: ", net_depth="depth", net_value_scale="1 / reward_scale"))
+            tau, every = float(teacher.get("tau", 1.0)), int(teacher.get("every", 1))
+            if not (every >= 1 and 0.0 <= tau < float("inf")):
+                raise ValueError("teacher: tau >= 0 and finite, every >= 1")
+            self._player = p                          # self.teacher: the same player as the dict it has always been
+            self.teacher = dict(worlds=p.worlds, samples=p.samples, tau=tau, every=every, salt=p.salt, voids=p.kind == "voids" and not net,
+                                hidden=p.kind == "hidden" and not net, net=net, net_seats=p.net_seats, net_worlds=p.kind if net else "det",
+                                **({} if p.depth is None else dict(depth=p.depth)))
         elif distill_coef:
             raise ValueError("distill_coef weighs the playout teacher's term: pass teacher= as well")
         self.env = env
@@ -654,34 +622,15 @@ class SelfPlay:
         playout_net_depth=D (with playout_net; 1..12): those playouts stop at the player's D-th next decision and take this
         learner's value head there, in points (evaluate_playout_vs_bot(net_depth=D, net_value_scale=1 / reward_scale));
         None: they run to the last card, as before."""
-        if playout_net_depth is not None:
-            if not playout_net:
-                raise ValueError("playout_net_depth goes with playout_net=True")
-            if isinstance(playout_net_depth, bool) or not isinstance(playout_net_depth, int) or not 1 <= playout_net_depth <= K.PLAYOUT_MAX_DEPTH:
-                raise ValueError("playout_net_depth: None or 1..%d viewer decisions" % K.PLAYOUT_MAX_DEPTH)
-        if playout_net_worlds not in ("det", "voids", "hidden"):
-            raise ValueError('playout_net_worlds: one of "det", "voids", "hidden"')
-        if playout_net_worlds != "det" and not playout_net:
-            raise ValueError("playout_net_worlds goes with playout_net=True")
-        if playout_net:
-            if playout_worlds is None:
-                raise ValueError("playout_net goes with playout_worlds=W")
-            if playout_voids or playout_hidden or playout_exchange is not None or playout_bidding is not None:
-                raise ValueError("playout_net composes with none of playout_voids, playout_hidden, playout_exchange, playout_bidding")
-            if versus_playout is not None and int(versus_playout) != 1:
-                raise ValueError("playout_net runs one playout per (card, world): versus_playout is 1")
+        playout.card_player(versus_playout, playout_worlds, playout_voids, playout_hidden, bool(playout_net), playout_net_seats,
+                            playout_net_worlds, playout_net_depth, front=playout_exchange is not None or playout_bidding is not None,
+                            say=playout.spelling(pattern="playout_%s", samples="versus_playout"))
         if playout_bidding is not None and playout_worlds is None:
             raise ValueError("playout_bidding goes with playout_worlds=W")
         if playout_exchange is not None and playout_worlds is None:
             raise ValueError("playout_exchange goes with playout_worlds=W")
         if playout_worlds is not None and versus_playout is None:
             raise ValueError("playout_worlds goes with versus_playout=samples")
-        if playout_voids and playout_worlds is None:
-            raise ValueError("playout_voids goes with playout_worlds=W")
-        if playout_hidden and playout_worlds is None:
-            raise ValueError("playout_hidden goes with playout_worlds=W")
-        if playout_hidden and playout_voids:
-            raise ValueError("playout_hidden is not built together with playout_voids: give one of the two")
         if versus_playout is not None and opponent is not None:
             raise ValueError("versus_playout compares against the Bot: give it without opponent=")
         if greedy and temperature:
@@ -733,33 +682,17 @@ class SelfPlay:
             self._buf["teach"] = torch.zeros((T, n, 64), dtype=torch.bfloat16, device=dev)
             self._teach_sums = torch.empty((n, K.PLAYOUT_RANKS, 4), dtype=torch.int32, device=dev)
             self._teach_act = torch.empty(n, dtype=torch.uint8, device=dev)
-            tc = self.teacher                         # the voids / played words of the teacher's worlds
-            voids, hidden = tc["voids"] or tc["net_worlds"] == "voids", tc["hidden"] or tc["net_worlds"] == "hidden"
-            self._teach_words = torch.empty(n, dtype=torch.int32 if voids else torch.int64, device=dev) if voids or hidden else None
-            if tc["net"]:                             # the net launch's scratch: allocated here, before any capture
-                self.env.playout_net_scratch(tc["worlds"])
+            dtype = self._player.words_dtype            # the voids / played words of the teacher's worlds
+            self._teach_words = None if dtype is None else torch.empty(n, dtype=dtype, device=dev)
+            self._player.prepare(self.env)            # the net launch's scratch: allocated here, before any capture
         self._graph = None
 
     def _teach(self, t):
         """The teacher's rows of lock-step t: one playout launch on the learner's seats from the env's current positions,
         one tarok_playout_targets on the words of that lock-step.  Stream-ordered, read-only on the env, no allocation."""
-        env, buf, tc = self.env, self._buf, self.teacher
-        if tc["net"]:                                 # the playouts are played by the learner's own rollout weights
-            kind = {} if tc["net_worlds"] == "det" else {tc["net_worlds"]: True, "words": self._teach_words}
-            if "depth" in tc:                         # stopped at the mover's depth-th decision, the value head in points
-                env.playout_cards_net_value(self._w, tc["worlds"], tc["depth"], 1.0 / self.reward_scale, net_seats=tc["net_seats"],
-                                            salt=tc["salt"], seats_per_game=self._seats, sum_out=self._teach_sums,
-                                            action_out=self._teach_act, **kind)
-            else:
-                env.playout_cards_net(self._w, tc["worlds"], net_seats=tc["net_seats"], salt=tc["salt"], seats_per_game=self._seats,
-                                      sum_out=self._teach_sums, action_out=self._teach_act, **kind)
-            env.playout_targets(self._teach_sums, buf["words"][t], tc["worlds"], tc["tau"], seats_per_game=self._seats,
-                                target_out=buf["teach"][t])
-            return
-        env.playout_cards_fair(tc["worlds"], tc["samples"], voids=tc["voids"], hidden=tc["hidden"], words=self._teach_words,
-                               salt=tc["salt"], seats_per_game=self._seats, sum_out=self._teach_sums, action_out=self._teach_act)
-        env.playout_targets(self._teach_sums, buf["words"][t], max(1, tc["worlds"]) * tc["samples"], tc["tau"],
-                            seats_per_game=self._seats, target_out=buf["teach"][t])
+        self._player.launch(self.env, self._w, dict(seats_per_game=self._seats), self._teach_words, self._teach_sums, self._teach_act)
+        self.env.playout_targets(self._teach_sums, self._buf["words"][t], self._player.playouts, self.teacher["tau"], seats_per_game=self._seats,
+                                 target_out=self._buf["teach"][t])
 
     def _rollout_body(self, T):
         env, buf, w = self.env, self._buf, self._w

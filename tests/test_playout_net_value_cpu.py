@@ -215,6 +215,7 @@ def test_the_env_method_issues_the_value_launch():
         n, device, _h = 4, torch.device("cpu"), 77
         check_mlp_weights = staticmethod(TarokVecEnv.check_mlp_weights)
         shown_voids, played_cards, _dev = TarokVecEnv.shown_voids, TarokVecEnv.played_cards, TarokVecEnv._dev
+        _cards, _empty = TarokVecEnv._cards, TarokVecEnv._empty          # the one dispatcher under the public methods, its outputs
 
         def __init__(self, history):
             self.L, self.history, self.scratch = Calls(), history, torch.zeros(4 * 12 * 2 * 48, dtype=torch.uint8)

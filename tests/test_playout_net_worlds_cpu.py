@@ -130,7 +130,7 @@ def test_new_and_old_refusals():
             SP.SelfPlay.evaluate(object(), **kw)
     for env, kw in ((WithHistory, dict(voids=True, hidden=True)), (NoHistory, dict(voids=True)), (NoHistory, dict(hidden=True))):
         with pytest.raises(ValueError):
-            TarokVecEnv.playout_cards_net(env(), net, 2, **kw)
+            TarokVecEnv.playout_cards_net(type("Env", (env,), dict(_cards=TarokVecEnv._cards))(), net, 2, **kw)
 
 
 class Calls:
@@ -177,6 +177,7 @@ def test_the_env_method_issues_the_launch_of_the_kind():
         n, device, _h = 4, torch.device("cpu"), 77
         check_mlp_weights = staticmethod(TarokVecEnv.check_mlp_weights)
         shown_voids, played_cards, _dev = TarokVecEnv.shown_voids, TarokVecEnv.played_cards, TarokVecEnv._dev
+        _cards, _empty = TarokVecEnv._cards, TarokVecEnv._empty          # the one dispatcher under the public methods, its outputs
 
         def __init__(self, history):
             self.L, self.history, self.scratch = Calls(), history, torch.zeros(4 * 12 * 2 * 48, dtype=torch.uint8)
