@@ -689,7 +689,17 @@ int tarok_playout_targets(tarok_env *env, const int32_t *sums, const uint64_t *o
  *   [0,54) own hand, [54,64) contract one-hot;  [64,118) legal cards, [118,128) declarer
  *   relative seat (4) / cards on table count (4) / on declarer's team / contract calls a king;
  *   [128,182) cards on the table, [182,192) called-king suit (4) / trick number binary (4);
- *   [192,246) cards already taken, [246] game live. */
+ *   [192,246) cards already taken, [246] game live.
+ * The seat to move is (leader + cards on the table) % 4.  "Cards already taken" are the four piles: every seat's won
+ * tricks, Klop's gifted talon cards with the trick they went to, and the declarer's discards; talon cards that lie in
+ * nobody's pile (the groups not picked up, Klop's talon not yet gifted) are in no region.
+ * For a game that is NOT in play — waiting for the exchange (TAROK_DEFER_EXCHANGE) or finished without an auto-reset —
+ * the legal region and the live bit are 0 and every other region is what the game's state holds: for a waiting game
+ * the twelve dealt cards of seat 0, an empty table, trick number 0 and no card taken; for a finished game the cards
+ * left in the hand of the seat that took the last trick (none after twelve tricks), an empty table, the trick number
+ * at which it ended (12, or lower for a Berac lost earlier) and every pile.  The rows of such games are written like
+ * any other.  tests/observe_model.py states all of this on the CPU oracle; tests/test_gpu_observe_features.py holds
+ * tarok_observe and the fused policy launches' features_out / feature_words_out to it bit for bit. */
 #define TAROK_OBS_FEATURES 256
 int tarok_observe(tarok_env *env, void *features_out, void *stream);
 

@@ -1985,6 +1985,9 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_targets(int64_t n, const int4 *__restric
 // The four 64-bit feature words of a game, for the seat to move (the regions above: a 54-bit card set, ten flag bits
 // from bit 54): what the fused policy kernels feed their network and write to feature_words_out.
 // (k_observe restates it: through this function that tuned kernel compiles to another instruction stream.)
+// For a game that is not in play (waiting for the exchange, or finished) the legal region and the live bit are 0 and
+// every other region is what the game's state holds (include/tarok_env.h at tarok_observe); both streams are held to
+// tests/observe_model.py, the statement on the CPU oracle, by tests/test_gpu_observe_features.py.
 __device__ __forceinline__ void policy_feature_words(const Game &g, u64 (&e)[4]) {
     u32 seat = (g.leader + g.nt) & 3;
     bool live = g.phase == TK_PHASE_PLAY;

@@ -4,7 +4,7 @@ tarok_playout_cards_det at one playout per (legal card, world), with the cards a
 network on the seats of `net_seats` and by the Bot on the others.  The worlds and the keys are tests/playout_det_model.py's;
 the network's card is the lowest-numbered legal card at the maximum of the logits, and the logits are the float64 forward
 with the kernels' two bf16 stores written in (tests/test_gpu_policy_exact.reference) on the feature words of the playout's
-own position, restated here from the oracle's Game.  With the exactly summable weight sets of that test the float64
+own position, stated on the oracle's Game by tests/observe_model.py.  With the exactly summable weight sets of that test the float64
 logits ARE the kernel's float32 logits, so the comparison with the GPU is of integers.
 
 All playouts of a call run in lock-step, one forward per card round over the rows that need one; `pick` is the card rule
@@ -14,37 +14,11 @@ import numpy as np
 
 import playout_det_model as DM
 import playout_model as PM
+from observe_model import expand, feature_words  # noqa: F401  (the one statement of the feature words)
 from oracle import oracle as O
 
 RANKS = PM.RANKS
 DECK = (1 << 54) - 1
-
-
-def feature_words(game):
-    """The four 64-bit feature words of an oracle Game in play, for the seat to move (tarok_env.hip, "Observation features
-    for the seat to move": a 54-bit card set and ten flag bits per word)."""
-    g = game.g
-    seat, nt = game.seat(), int(g.n_in_trick)
-    has_king = int(g.king) >= 0
-    table = 0
-    for j in range(nt):
-        table |= 1 << int(g.trick[j])
-    f1 = (1 << ((int(g.declarer) - seat) & 3)) | (1 << (4 + nt)) | (((int(g.team) >> seat) & 1) << 8) | ((1 if has_king else 0) << 9)
-    f2 = ((1 << int(g.king)) if has_king else 0) | (int(g.trick_no) << 4)
-    piles = int(g.pile[0]) | int(g.pile[1]) | int(g.pile[2]) | int(g.pile[3])
-    return [int(g.hand[seat]) | (1 << (54 + int(g.contract))), game.legal() | (f1 << 54), table | (f2 << 54), piles | (1 << 54)]
-
-
-def expand(words):
-    """[m][4] feature words -> [m, 256] float64 0 / 1 (feature f = bit f % 64 of word f // 64)."""
-    x = np.zeros((len(words), 256))
-    for i, ws in enumerate(words):
-        for k, w in enumerate(ws):
-            for b in PM.cards_of(w & DECK):
-                x[i, 64 * k + b] = 1.0
-            for b in range(54, 64):
-                x[i, 64 * k + b] = (w >> b) & 1
-    return x
 
 
 def logits_of(words, W):
