@@ -6,6 +6,8 @@ and runs its mutants over them; the GPU test walks the same generators beside th
 """
 import ctypes as C
 
+import numpy as np
+
 from oracle import oracle as O
 from oracle import tarok_spec as S
 from oracle_model import SlotModel
@@ -63,5 +65,20 @@ def census_positions():
         for t in range(FINISH_STEPS + 1):
             play(slots, auto=False)
             out += [("to the finish", copy_of(s.g), None) for s in slots]
-        assert all(s.g.done for s in slots)
+        assert all(s.g.done for s in slots), "not true: all(s.g.done for s in slots)"
     return out
+
+
+def sample_games(tr, per_contract=24):
+    idx = []
+    for c in range(10):
+        w = np.where(tr["contract"] == c)[0]
+        idx += list(w[:: max(1, len(w) // per_contract)][:per_contract])
+    return np.array(sorted(idx))
+
+
+def reset_from_traces(env, tr, idx, **kw):
+    king = np.where(tr["king"][idx] < 0, 0, tr["king"][idx]).astype(np.int8)
+    choice = np.where(tr["choice"][idx] < 0, 0, tr["choice"][idx]).astype(np.int8)
+    return env.reset(deals=tr["deals"][idx], contract=tr["contract"][idx], declarer=tr["declarer"][idx], king_suit=king,
+                     talon_choice=choice, discards=tr["discards"][idx], **kw)

@@ -8,7 +8,7 @@ test is used.  No GPU in here.
 import numpy as np
 
 from oracle import tarok_spec as S
-from test_gpu_policy_exact import U, legal_matrix
+from policy_exact_ref import U, legal_matrix
 
 DRAW_BOT, DRAW_SAMPLE, DRAW_EXPLORE = S.DRAW_POLICY, 192, 256
 

@@ -24,7 +24,7 @@ DECK = (1 << 54) - 1
 def logits_of(words, W):
     """The 54 card logits of every row, float64 with the two bf16 stores."""
     import torch
-    from test_gpu_policy_exact import reference
+    from policy_exact_ref import reference
     return reference(torch.from_numpy(expand(words)), W)["out"][:, :54].numpy()
 
 

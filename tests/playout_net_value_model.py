@@ -42,7 +42,7 @@ def points(v, value_scale, half_even=True):
 def forward(games, W):
     """[m, 64] float64 outputs (card logits 0..53, value 54) on the feature words of every Game's own position."""
     import torch
-    from test_gpu_policy_exact import reference
+    from policy_exact_ref import reference
     return reference(torch.from_numpy(NM.expand([NM.feature_words(h) for h in games])), W)["out"].numpy()
 
 

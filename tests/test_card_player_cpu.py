@@ -10,8 +10,8 @@ package under other names, never from the code under test:
     mkdir /tmp/parent && for f in env selfplay evaluate; do git show 5509796:tarok_amd/$f.py > /tmp/parent/$f.py; done
     PYTHONPATH=. python tests/test_card_player_cpu.py /tmp/parent > tests/golden/card_player_calls_v1.json
 
-Calls are written as tests/test_evaluate_calls_cpu.py (the evaluation: Trace, stand_in, run_case, pack) and
-tests/test_playout_net_worlds_cpu.py (everything else: Calls — a tensor is its dtype and shape) write them."""
+Calls are written as tests/evaluate_calls_cases.py (the evaluation: Trace, stand_in, run_case, pack) and
+tests/playout_net_cases.py (everything else: Calls — a tensor is its dtype and shape) write them."""
 import contextlib
 import importlib.util
 import json
@@ -21,8 +21,8 @@ import sys
 import pytest
 import torch
 
-import test_evaluate_calls_cpu as EC
-from test_playout_net_worlds_cpu import Calls, no_device
+import evaluate_calls_cases as EC
+from playout_net_cases import Calls, no_device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "card_player_calls_v1.json")

@@ -3,7 +3,6 @@ declared C entry points, and the launch list of SelfPlay with and without front=
 import ctypes
 import os
 
-import numpy as np
 import pytest
 import torch
 
@@ -12,20 +11,9 @@ from oracle import tarok_spec as S
 from tarok_amd import _native, karte as K
 from tarok_amd import selfplay as SP
 from tarok_amd.env import TarokVecEnv
+from front_lines_cpu_cases import GIDX, SEED, model_weights, zero_weights
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED, GIDX = 3, 77
-
-
-def zero_weights():
-    return [torch.zeros((256, 256), dtype=torch.bfloat16), torch.zeros(256), torch.zeros((256, 256), dtype=torch.bfloat16),
-            torch.zeros(256), torch.zeros((64, 256), dtype=torch.bfloat16), torch.zeros(64)]
-
-
-def model_weights(seed):
-    g = torch.Generator().manual_seed(seed)
-    r = lambda *s: (torch.randint(-4, 5, s, generator=g).double() / 16)
-    return (r(256, 256), r(256), r(256, 256) / 16, r(256), r(64, 256) / 16, r(64))
 
 
 # ---- the model

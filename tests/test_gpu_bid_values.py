@@ -2,7 +2,7 @@
 of each hand) and the surface built on it, against tests/bid_head_model.py.  All outputs sit inside guard bands
 (tests/guarded.py); every row of value_out, raw_out and feature_words_out is compared.
 
-Why equality.  The weight sets are tests/test_gpu_policy_exact.py's: small integers times a power of two on 0/1
+Why equality.  The weight sets are tests/policy_exact_ref.py's: small integers times a power of two on 0/1
 features, so every partial sum of a layer is a multiple of one quantum below 2^24 quanta and float32 accumulation is
 exact in ANY order; the two bf16 stores are round-to-nearest-even, which the float64 model writes in.  Set R rounds a
 good share of H2 (many exact ties), the sets P walk the fragment order, and set H — a set P with integer W3 and b3 =
@@ -11,10 +11,12 @@ conditions are asserted on the launches' own inputs before any output is looked 
 
 Run on the GPU box:  python -m pytest tests/test_gpu_bid_values.py -m gpu -q
 """
-import os
 
 import numpy as np
 import pytest
+
+from gpu_harness import T  # noqa: F401  (the module fixture)
+from bid_values_cases import weight_sets
 
 pytestmark = pytest.mark.gpu
 
@@ -27,31 +29,8 @@ U = np.uint64
 
 
 @pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    from tarok_amd import _native
-    tarok_amd.build()
-    assert os.path.exists(_native.LIB_PATH), "libtarokenv.so missing: the HIP path is the product, no fallback"
-    assert hasattr(_native.lib(), "tarok_bid_values")
-    return tarok_amd
-
-
-def weight_sets():
-    """{name: float64 weight set}: R, two sets P and H (see the module's docstring)."""
-    import torch
-    import test_gpu_policy_exact as PE
-    g = torch.Generator(); g.manual_seed(5)
-    H = [t.clone() for t in PE.weights_p(0, 1, 0)]
-    H[4] = (H[4] * 8).round()
-    H[5] = torch.randint(-4, 5, (64,), generator=g).double() + 0.5
-    return dict(R=PE.weights_r(), P1=PE.weights_p(*PE.P_PARAMS[1]), P8=PE.weights_p(*PE.P_PARAMS[8]), H=H)
-
-
-@pytest.fixture(scope="module")
 def sets(T):
-    import test_gpu_policy_exact as PE
+    import policy_exact_ref as PE
     W = weight_sets()
     return W, {k: PE.kernel_weights(T, w) for k, w in W.items()}
 
@@ -100,7 +79,6 @@ def launch(env, kw, scale=SCALE, contracts=DEFAULT, deals=None, seats=15, per_ga
     return out
 
 
-
 def check(env, W, kw, perms, seats_of, tag, **kwargs):
     """One launch against the model: feature words, raw and value equal for every row."""
     import bid_head_model as HM
@@ -119,7 +97,7 @@ def test_the_inputs_meet_the_exactness_conditions():
     rounds at least 5 % of H2 with at least 1 % ties, H gives half-integers that tie both ways."""
     import torch
     import bid_head_model as HM
-    import test_gpu_policy_exact as PE
+    import policy_exact_ref as PE
     words = np.array([HM.game_words(p) for p in perms_of(100)], np.uint64).reshape(-1, 4)
     x = torch.from_numpy(HM.expand(words))
     assert 25 <= int(x.sum(1).min()) and int(x.sum(1).max()) <= 40
@@ -156,7 +134,7 @@ def test_the_clamp_and_the_nan_rule(T, sets):
     """b3 = +-1e30 and +inf end at +-2^30; a W3 row holding +inf and -inf makes NaN for every input (inf - inf, or
     0 x inf), which fmaxf turns into -2^30.  The other rows stay exact."""
     import torch
-    import test_gpu_policy_exact as PE
+    import policy_exact_ref as PE
     W = [t.clone() for t in sets[0]["P1"]]
     W[5][0], W[5][1], W[5][2] = 1e30, -1e30, float("inf")
     W[5] = W[5].float().double()
@@ -179,7 +157,7 @@ def test_random_bf16_weights_within_the_derived_bound(T):
     output) and the two bf16 stores; value_out equals the kernel's own raw_out pushed through the scaling in numpy."""
     import torch
     import bid_head_model as HM
-    import test_gpu_policy_exact as PE
+    import policy_exact_ref as PE
     g = torch.Generator(); g.manual_seed(17)
     bf = lambda t: t.to(torch.bfloat16).double()
     W = [bf(torch.randn(256, 256, generator=g) / 8), torch.randn(256, generator=g).float().double() / 4,

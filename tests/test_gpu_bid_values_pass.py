@@ -9,11 +9,11 @@ before any kernel output is looked at.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_bid_values_pass.py -m gpu -q
 """
-import ctypes as C
-import os
 
 import numpy as np
 import pytest
+
+from gpu_harness import T  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,23 +27,9 @@ PASS = 19
 
 
 @pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    from tarok_amd import _native
-    tarok_amd.build()
-    assert os.path.exists(_native.LIB_PATH), "libtarokenv.so missing: the HIP path is the product, no fallback"
-    lib = C.CDLL(_native.LIB_PATH)
-    for name in ("tarok_playout_bids_pass", "tarok_bid_round_pass", "tarok_bid_values_pass"):
-        assert hasattr(lib, name), "libtarokenv.so lacks %s" % name
-    return tarok_amd
-
-
-@pytest.fixture(scope="module")
 def sets(T):
-    import test_gpu_bid_values as BV
-    import test_gpu_policy_exact as PE
+    import bid_values_cases as BV
+    import policy_exact_ref as PE
     W = BV.weight_sets()
     return W, {k: PE.kernel_weights(T, w) for k, w in W.items()}
 
@@ -120,8 +106,8 @@ def test_the_inputs_meet_the_exactness_conditions():
     any order on all 64 outputs, so on output 19; set H makes output 19 a half-integer that ties both ways at scale 1."""
     import torch
     import bid_head_model as HM
-    import test_gpu_bid_values as BV
-    import test_gpu_policy_exact as PE
+    import bid_values_cases as BV
+    import policy_exact_ref as PE
     words = np.array([HM.game_words(p) for p in perms_of(160)], np.uint64).reshape(-1, 4)
     x = torch.from_numpy(HM.expand(words))
     W = BV.weight_sets()
@@ -153,7 +139,7 @@ def test_row_19_is_output_19_on_every_weight_set(T, sets, n):
 
 
 def test_a_nan_and_an_output_beyond_the_clamp_in_output_19(T, sets):
-    import test_gpu_policy_exact as PE
+    import policy_exact_ref as PE
     n = 33
     perms = perms_of(n)
     env = make_env(T, n)

@@ -5,24 +5,14 @@ state on every card.  Every row of every output, the final state and the counter
 
 Run on the GPU box:  python -m pytest tests/test_gpu_carried_words.py -m gpu -q
 """
-import os
 
 import pytest
+
+from gpu_harness import T  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
 
 N = 512                                                 # full waves only: a wave with an idle lane does not play the trick-aligned loop
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    from tarok_amd import _native
-    tarok_amd.build()
-    assert os.path.exists(_native.LIB_PATH), "libtarokenv.so missing: the HIP path is the product, no fallback"
-    return tarok_amd
 
 
 @pytest.fixture(scope="module")

@@ -10,8 +10,8 @@ import pytest
 
 import distill_model as DM
 import loss_model as L
-from test_gpu_loss_exact import (CONFIGS, M, SEED, SENTINEL_BF16, SENTINEL_WORD, SETS, Learner, T, features, forward_of,   # noqa: F401
-                                 subset_reference)
+from gpu_harness import T  # noqa: F401  (the module fixture)
+from learner_cases import CONFIGS, M, SEED, SENTINEL_BF16, SENTINEL_WORD, SETS, Learner, features, forward_of, subset_reference
 
 pytestmark = pytest.mark.gpu
 COEF = 0.75
@@ -127,7 +127,7 @@ def test_distill_chain_and_dw_vs_torch_autograd(T):
     import torch
     import torch.nn.functional as F
     from tarok_amd import selfplay as SP
-    from test_gpu_learner import _rollout_words
+    from learner_cases import _rollout_words
     K = T.karte
     f64 = torch.float64
     B, n, steps = 333, 2048, 3

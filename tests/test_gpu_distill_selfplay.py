@@ -5,7 +5,7 @@ Run on the GPU box:  python -m pytest tests/test_gpu_distill_selfplay.py -m gpu 
 import numpy as np
 import pytest
 
-from test_gpu_playout_det import T   # noqa: F401  (the module fixture)
+from gpu_harness import T  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
 N, STEPS = 512, 8

@@ -4,13 +4,17 @@ playout_cards_det(3, 2), which tests/test_gpu_playout_det.py pins: they are inpu
 
 Run on the GPU box:  python -m pytest tests/test_gpu_distill_targets.py -m gpu -q
 """
+import functools
 import numpy as np
 import pytest
 
 import distill_model as DM
-from test_gpu_playout_det import T, make_env   # noqa: F401  (T: the module fixture)
+import gpu_harness as H
+from gpu_harness import T  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
+SEED, OFFSET, EPISODE = 41, 1000, 3               # tests/test_gpu_playout_det.py's: the same games
+make_env = functools.partial(H.make_env, seed=SEED, offset=OFFSET, episode=EPISODE)
 U = np.uint64
 
 
@@ -58,7 +62,7 @@ def test_rows_on_real_env_states(T, cards):
     stand beside games in play from 22 cards on.  Seat sets 15, 0, 6 and a per-game cycle; tau in {0.5, 8, 64} within the
     bound, tau = 0 equal bytes and the launch's card.  The zero rows are exactly the games the playout launch left zero."""
     from oracle import tarok_spec as S
-    from test_gpu_playout_det import launch
+    from gpu_harness import launch_det as launch
     env = make_env(T, 773, S.MIX_ALL, cards)
     try:
         words = env.legal_actions().words.cpu().numpy().view(np.uint64)
@@ -92,7 +96,7 @@ def test_games_waiting_for_the_exchange_and_games_renewed_by_auto_reset(T):
     """Deferred exchange: every game that waits has a zero row and zero sums.  Auto-reset: a word that describes the slot's
     NEXT game keeps TAROK_OBS_DONE, the playout launch plays that game, and the row is its teacher's."""
     from oracle import tarok_spec as S
-    from test_gpu_playout_det import launch
+    from gpu_harness import launch_det as launch
     env = make_env(T, 300, S.MIX_ALL, 0, defer_exchange=True)
     try:
         words = env.legal_actions().words.cpu().numpy().view(np.uint64)

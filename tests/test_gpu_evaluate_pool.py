@@ -6,23 +6,16 @@ Run on the GPU box:  python -m pytest tests/test_gpu_evaluate_pool.py -m gpu -q
 import numpy as np
 import pytest
 
+from gpu_harness import T  # noqa: F401  (the module fixture)
+
 pytestmark = pytest.mark.gpu
 
 GAMES, EPISODES, SEED = 256, 1, 12
 
 
 @pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    tarok_amd.build()
-    return tarok_amd
-
-
-@pytest.fixture(scope="module")
 def nets(T):
-    from test_gpu_policy_step_versus import make_weights
+    from policy_step_cases import make_weights
     return [make_weights(T, s) for s in (0, 1, 2)]
 
 

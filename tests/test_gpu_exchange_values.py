@@ -6,17 +6,18 @@ The games come from a reset with the exchange deferred whose contract, declarer 
 contract codes x four declarers x four kings, so Klop, Berac and Solo_brez games sit between the waiting ones.  N = 1,
 16 (one workgroup), 17 (a ragged second) and 160 (the whole cycle).
 
-Why equality.  The weight sets are tests/test_gpu_policy_exact.py's: small integers times a power of two on 0/1
+Why equality.  The weight sets are tests/policy_exact_ref.py's: small integers times a power of two on 0/1
 features, so every partial sum of a layer is a multiple of one quantum below 2^24 quanta and float32 accumulation is
 exact in ANY order; the two bf16 stores are round-to-nearest-even, which the float64 model writes in.  The conditions are
 asserted on the launches' own inputs before any output is looked at.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_exchange_values.py -m gpu -q
 """
-import os
 
 import numpy as np
 import pytest
+
+from gpu_harness import T  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,23 +26,11 @@ NS = (1, 16, 17, 160)
 U = np.uint64
 
 
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    from tarok_amd import _native
-    tarok_amd.build()
-    assert os.path.exists(_native.LIB_PATH), "libtarokenv.so missing: the HIP path is the product, no fallback"
-    assert hasattr(_native.lib(), "tarok_exchange_values") and hasattr(_native.lib(), "tarok_exchange_candidates")
-    return tarok_amd
-
-
 def weight_sets():
-    """{name: float64 weight set}: R and two sets P of tests/test_gpu_policy_exact.py, and TIE — set P1 with the value
+    """{name: float64 weight set}: R and two sets P of tests/policy_exact_ref.py, and TIE — set P1 with the value
     row and the score rows of cards 0..19 and 32..39 cut down to their biases: every group ties at 1/4 (the lowest
     wins) and those cards tie at 1/2, above every other card of P1 only where the row says so."""
-    import test_gpu_policy_exact as PE
+    import policy_exact_ref as PE
     tie = [t.clone() for t in PE.weights_p(*PE.P_PARAMS[1])]
     tie[4][54] = 0
     tie[5][54] = 0.25
@@ -53,7 +42,7 @@ def weight_sets():
 
 @pytest.fixture(scope="module")
 def sets(T):
-    import test_gpu_policy_exact as PE
+    import policy_exact_ref as PE
     W = weight_sets()
     return W, {k: PE.kernel_weights(T, w) for k, w in W.items()}
 
@@ -134,7 +123,7 @@ def test_the_inputs_meet_the_exactness_conditions():
     holds what the tests lean on: all six exchange contracts, every declarer, and all three places of the called king."""
     import torch
     import exchange_head_model as EM
-    import test_gpu_policy_exact as PE
+    import policy_exact_ref as PE
     from oracle import oracle as O
     from oracle import tarok_spec as S
     c, d, k = setup_arrays(160)
@@ -187,7 +176,7 @@ def test_ties_in_value_and_in_score(T, sets):
 def test_nan_and_infinities_still_give_a_valid_exchange(T, sets):
     """b3[54] = NaN: every group's value is -inf after clean(), group 0 wins.  Score biases of +inf, -inf and a W3 row
     holding +inf and -inf (NaN for the rows that light both, else +-inf) still give the model's discards."""
-    import test_gpu_policy_exact as PE
+    import policy_exact_ref as PE
     env, lanes = make_env(T, 160)
     try:
         W = [t.clone() for t in sets[0]["P1"]]
@@ -217,7 +206,7 @@ def test_random_bf16_weights_within_the_derived_bound(T):
     model's selection."""
     import torch
     import exchange_head_model as EM
-    import test_gpu_policy_exact as PE
+    import policy_exact_ref as PE
     from oracle import oracle as O
     g = torch.Generator(); g.manual_seed(17)
     bf = lambda t: t.to(torch.bfloat16).double()

@@ -32,6 +32,8 @@ Run on the GPU box:  python -m pytest tests/test_gpu_front_rows.py -m gpu -q
 import numpy as np
 import pytest
 
+from gpu_harness import T  # noqa: F401  (the module fixture)
+
 pytestmark = pytest.mark.gpu
 
 STEPS = 144
@@ -65,21 +67,12 @@ def case_id(case):
 
 
 @pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    tarok_amd.build()
-    return tarok_amd
-
-
-@pytest.fixture(scope="module")
 def world(T):
     """The front_lines call of every case and what its lines must hold: twin[e] / bot[e] are the lanes [10, N] of the
     twin chain's and of the Bot's game of episode e = 1..14; differ[e], family[e] and xdiff[e] say per slot whether the
     two differ, the contract, and whether the exchange differs from the Bot's exchange of the same contract."""
     import front_lines_model as FM
-    import test_gpu_front_lines as FL
+    import front_lines_cases as FL
     from oracle import oracle as O
     from oracle import tarok_spec as S
     n = FL.N
@@ -108,7 +101,7 @@ def world(T):
 
 def game_of(w):
     """SlotModel's hook: the twin chain's game for the fourteen lines of the call, the synthetic one elsewhere."""
-    import test_gpu_front_lines as FL
+    import front_lines_cases as FL
     from oracle import oracle as O
 
     def hook(index, ep):
@@ -139,8 +132,8 @@ class Run:
 
     def __init__(self, T, kind, opt, n, offset, sets, hook, slots=None):
         import torch
-        import test_gpu_front_lines as FL
-        import test_gpu_output_contract as G
+        import front_lines_cases as FL
+        import output_contract_cases as G
         from oracle_model import SlotModel
         from tarok_amd import karte as K
         self.G, self.kind, self.part, self.n, self.sets = G, kind, kind.split(":"), n, sets
@@ -244,7 +237,7 @@ class Run:
 
 
 def front_once(env, kw):
-    import test_gpu_front_lines as FL
+    import front_lines_cases as FL
     count, _ = FL.front(env, **kw)
     assert count == FL.AHEAD * env.n
     _, _, nep, mark = FL.split(env.get_lines())
@@ -253,7 +246,7 @@ def front_once(env, kw):
 
 @pytest.mark.parametrize("case", CASES, ids=case_id)
 def test_rows_on_fronted_lines(T, world, case):
-    import test_gpu_front_lines as FL
+    import front_lines_cases as FL
     kind, opt = case
     n, offset, sets, base = FL.N, FL.OFFSET, world["sets"], 0
     if opt.get("one"):                   # one slot: the first whose set is 15 and whose first three lines all differ from the Bot's
@@ -276,12 +269,12 @@ def test_rows_on_fronted_lines(T, world, case):
 
 
 def test_rows_on_integer_weight_lines_against_the_cpu_model(T):
-    """krog:4 on the lines of a call with the integer weight sets of tests/test_gpu_policy_exact.py (sums exact in
+    """krog:4 on the lines of a call with the integer weight sets of tests/policy_exact_ref.py (sums exact in
     float32 in any order): the start of every game is tests/front_lines_model.front_game, no GPU in the reference at all.
     Every third slot is modelled; the others keep their guards."""
     import front_lines_model as FM
-    import test_gpu_front_lines as FL
-    import test_gpu_policy_exact as PE
+    import front_lines_cases as FL
+    import policy_exact_ref as PE
     from oracle import tarok_spec as S
     Wb, Wx = PE.weights_p(*PE.P_PARAMS[1]), PE.weights_p(*PE.P_PARAMS[8])
     sets = FL.sets_tensor(FL.N)
@@ -317,7 +310,7 @@ def test_rows_with_a_second_call_between_refills(T, world):
     (slot, episode) starts as the twin chain's of the call that marked its line, and as the Bot's if no call did (a line
     still on a refill list at the second call, or dealt after it).  With 80 lock-steps left a slot rarely gets past its
     fourteenth game: what the rows see of the second call is mostly that it left the lines ahead of the slots alone."""
-    import test_gpu_front_lines as FL
+    import front_lines_cases as FL
     from oracle import oracle as O
     from oracle import tarok_spec as S
     calls = [world["kw"], dict(world["kw"], bid=FL.random_weights(21, HEAD_GAIN), exchange=FL.random_weights(22, HEAD_GAIN))]

@@ -8,16 +8,10 @@ Run on the GPU box:  python -m pytest tests -m gpu -x -q
 import numpy as np
 import pytest
 
+from learner_cases import _rollout_words
+from gpu_harness import T  # noqa: F401  (the module fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    tarok_amd.build()
-    return tarok_amd
 
 
 def frag_order(w, ksteps):
@@ -92,20 +86,6 @@ def test_learn_returns_vs_torch(T):
     assert abs(stats[0].item() - mean) < 1e-4 and abs(stats[1].item() - 1.0 / std) < 1e-3 / std
     assert abs(stats[2].item() - known.float().mean().item()) < 1e-6
     env.close()
-
-
-def _rollout_words(T, env, net_w, steps):
-    """feature words [steps * n, 4] and observation words of real positions (policy_mlp on a stepped env)"""
-    import torch
-    obs = env.reset()
-    fws, ows = [], []
-    for t in range(steps):
-        for _ in range(3):
-            obs, _, _ = env.step(env.policy_random(obs), auto_reset=True)
-        fw = torch.zeros((env.n, 4), dtype=torch.int64, device="cuda")
-        env.policy_mlp(net_w, obs.words, feature_words_out=fw)
-        fws.append(fw); ows.append(obs.words.clone())
-    return torch.cat(fws), torch.cat(ows)
 
 
 SENTINEL_BF16 = 0x7FC1                        # a NaN payload no kernel writes: padding rows a store must not touch

@@ -4,7 +4,7 @@ the known samples) against np.flatnonzero and the numpy model of its three launc
 output between guard bands, and SelfPlay(opponent=...) end to end.  Build-owned code (the reference has no
 policy-gradient learner).
 
-Shapes of the returns tests: those of tests/test_gpu_learner_gae.py, whose arrays and slot patterns are reused — n = 300
+Shapes of the returns tests: those of tests/test_gpu_learner_gae.py, whose arrays and slot patterns (tests/gae_cases.py) are reused — n = 300
 slots (two workgroups, the second a ragged one of 44) at T = 12 and T = 13 (not a multiple of the walk's unroll of 4),
 one slot at T = 1; slots that never end a game, end one at t = 0 only, at t = T - 1, twice in a row, and slots where
 seat 2 never moves.
@@ -18,22 +18,14 @@ import numpy as np
 import pytest
 
 from select_model import known_patterns, rec_of, scratch_bytes, select_model
-from test_gpu_learner_gae import F32, SHAPES, arrays, check_bits, launch, model
-from test_opponent_cpu import monte_carlo_known, moves, seat_sets, SETS
+from gae_cases import F32, SHAPES, arrays, check_bits, launch, model
+from opponent_cases import SETS, monte_carlo_known, moves, seat_sets
+from gpu_harness import T  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
 MODES = [("mc", 1.0, 1.0), ("gae", 1.0, 0.5), ("gae", 0.5, 1.0)]          # exact inputs: gamma and lambda in {1, 1/2}
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    tarok_amd.build()
-    return tarok_amd
 
 
 @pytest.fixture(scope="module")
@@ -243,6 +235,7 @@ def test_returns_seats_rejects_bad_arguments(T, envs):
 
 # ---------------------------------------------------------------------------------------------------------------
 # compaction
+
 
 def select_launch(env, rec_np, spare=256):
     """One tarok_learn_select launch on a record (numpy [M,4] f32) with index_out, count_out and scratch between guard

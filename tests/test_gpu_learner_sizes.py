@@ -11,6 +11,8 @@ import re
 import numpy as np
 import pytest
 
+from gpu_harness import T  # noqa: F401  (the module fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # ---- a model of k_learn_dw's work split (tarok_env.hip learn_chunks, tarok_learner.inc dw_chunk / dw_layer)
@@ -94,15 +96,6 @@ def test_the_probe_sizes_cover_the_tiling_edges():
 
 
 # ---- GPU
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    tarok_amd.build()
-    return tarok_amd
-
-
 @pytest.fixture(scope="module")
 def env(T):
     e = T.TarokVecEnv(256, seed=1)

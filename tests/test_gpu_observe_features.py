@@ -21,21 +21,11 @@ import pytest
 import observe_cases as OC
 import observe_model as OM
 from guarded import Guarded, assert_guards_intact
+from gpu_harness import T  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
 
 MODEL = OM.Statement()
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    from tarok_amd import _native
-    tarok_amd.build()
-    assert os.path.exists(_native.LIB_PATH), "libtarokenv.so missing: the HIP path is the product, no fallback"
-    return tarok_amd
 
 
 @pytest.fixture(scope="module")
@@ -52,8 +42,8 @@ def S():
 
 @pytest.fixture(scope="module")
 def KW(T):
-    """An integer weight set of tests/test_gpu_policy_exact.py in the kernels' layout (the weights do not matter here)."""
-    from test_gpu_policy_exact import kernel_weights, weights_r
+    """An integer weight set of tests/policy_exact_ref.py in the kernels' layout (the weights do not matter here)."""
+    from policy_exact_ref import kernel_weights, weights_r
     return kernel_weights(T, weights_r())
 
 

@@ -10,16 +10,10 @@ import os
 import numpy as np
 import pytest
 
+from gpu_harness import T  # noqa: F401  (the module fixture)
+from observe_cases import reset_from_traces, sample_games
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    tarok_amd.build()
-    return tarok_amd
 
 
 @pytest.fixture(scope="module")
@@ -31,21 +25,6 @@ def E():
 @pytest.fixture(scope="module")
 def traces(golden_dir):
     return dict(np.load(os.path.join(golden_dir, "traces_v1.npz")))
-
-
-def sample_games(tr, per_contract=24):
-    idx = []
-    for c in range(10):
-        w = np.where(tr["contract"] == c)[0]
-        idx += list(w[:: max(1, len(w) // per_contract)][:per_contract])
-    return np.array(sorted(idx))
-
-
-def reset_from_traces(env, tr, idx, **kw):
-    king = np.where(tr["king"][idx] < 0, 0, tr["king"][idx]).astype(np.int8)
-    choice = np.where(tr["choice"][idx] < 0, 0, tr["choice"][idx]).astype(np.int8)
-    return env.reset(deals=tr["deals"][idx], contract=tr["contract"][idx], declarer=tr["declarer"][idx], king_suit=king,
-                     talon_choice=choice, discards=tr["discards"][idx], **kw)
 
 
 def expected_record(E, tr, i, t):

@@ -12,26 +12,16 @@ wave of valid and invalid lanes, which plays the loop with per-lane predicates a
 
 Run on the GPU box:  python -m pytest tests/test_gpu_one_line_renewal.py -m gpu -q
 """
-import os
 
 import numpy as np
 import pytest
+
+from gpu_harness import T  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
 
 SEED = 41            # all-Berac: slots that finish in consecutive tricks of one launch (asserted from the oracle below)
 SIZES = (256, 300, 320)
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    from tarok_amd import _native
-    tarok_amd.build()
-    assert os.path.exists(_native.LIB_PATH), "libtarokenv.so missing: the HIP path is the product, no fallback"
-    return tarok_amd
 
 
 @pytest.fixture(scope="module")

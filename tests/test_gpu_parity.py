@@ -11,18 +11,9 @@ import os
 import numpy as np
 import pytest
 
+from gpu_harness import T  # noqa: F401  (the module fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    from tarok_amd import _native
-    tarok_amd.build()
-    assert os.path.exists(_native.LIB_PATH), "libtarokenv.so missing: the HIP path is the product, no fallback"
-    return tarok_amd
 
 
 @pytest.fixture(scope="module")

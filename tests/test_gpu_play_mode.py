@@ -3,7 +3,7 @@ the float64 model of tests/play_mode_model.py, and the default mode (1, 0) again
 
 n = 300 games: two partial 128-game tiles of tarok_policy_mlp, and a second, partial 256-game workgroup of the step
 launches.  Positions come from a handful of step_random lock-steps with auto-reset (legal sets of 1 to 12 cards).  On the
-integer weight set R of tests/test_gpu_policy_exact.py the logits are known exactly (float32 values, ties among them),
+integer weight set R of tests/policy_exact_ref.py the logits are known exactly (float32 values, ties among them),
 so the arg-max has one right answer per row.
 
     python -m pytest tests/test_gpu_play_mode.py -m gpu -q
@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 import play_mode_model as PM
-from test_gpu_policy_exact import U, _u64, _played, _word, _zero_net, kernel_weights, reference, weights_r
+from policy_exact_ref import U, _played, _u64, _word, _zero_net, kernel_weights, reference, weights_r
+from gpu_harness import T  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -21,15 +22,6 @@ LEADS = (0, 1, 2, 3, 5, 14)
 NEAR = 1e-5            # the float32 rounding margin of a tempered draw, derived in test_temperature's docstring
 MASK54 = np.uint64((1 << 54) - 1)
 MODES = ((0.0, 0.0), (0.5, 0.0), (2.0, 0.0), (0.0, 1.0), (0.0, 0.25), (1.0, 0.25))      # (temperature, epsilon) of the fixture's launches
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    tarok_amd.build()
-    return tarok_amd
 
 
 def bits(t):

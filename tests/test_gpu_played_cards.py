@@ -7,9 +7,10 @@ Run on the GPU box:  python -m pytest tests/test_gpu_played_cards.py -m gpu -q
 import numpy as np
 import pytest
 
-from test_gpu_playout_det import EPISODE, OFFSET, SEED, T   # noqa: F401  (T: the module fixture)
+from gpu_harness import T  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
+SEED, OFFSET, EPISODE = 41, 1000, 3               # tests/test_gpu_playout_det.py's: the same games
 U = np.uint64
 POSITIONS = (0, 1, 4, 5, 47)
 

@@ -5,63 +5,25 @@ not written fails the test.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_playout.py -m gpu -q
 """
-import os
+import functools
 
 import numpy as np
 import pytest
+
+import gpu_harness as H
+from gpu_harness import T  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
 
 SEED = 41
 OFFSET = 1000                            # game offset of the envs: gidx = OFFSET + g
 EPISODE = 3                              # episode the envs are reset to: the key's episode field is not zero
-SENTINEL_I32 = np.array([0xA5A5A5A5], np.uint32).view(np.int32)[0]
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    from tarok_amd import _native
-    tarok_amd.build()
-    assert os.path.exists(_native.LIB_PATH), "libtarokenv.so missing: the HIP path is the product, no fallback"
-    return tarok_amd
-
-
-def make_env(T, n, mix, cards=0, history=False, seed=SEED, **reset):
-    """An env of n games at EPISODE after `cards` Bot cards without auto-reset."""
-    env = T.TarokVecEnv(n, seed=seed, mix=mix, game_offset=OFFSET, history=history)
-    env.reset(episode=EPISODE, **reset)
-    for _ in range(cards):
-        env.step_random(auto_reset=False)
-    return env
+make_env = functools.partial(H.make_env, seed=SEED, offset=OFFSET, episode=EPISODE)
 
 
 def launch(env, samples, salt=0, seats=15, per_game=None, want=("sum", "action")):
     """One tarok_playout_cards launch into guarded outputs: (sum [n,12,4] i32 or None, action [n] u8 or None)."""
-    import torch
-    from guarded import Guarded, assert_guards_intact
-    from tarok_amd import _native
-    n = env.n
-    g_sum = Guarded("sum_out", 1, n, np.int32, inner=(12, 4), device="cuda") if "sum" in want else None
-    g_act = Guarded("action_out", 1, n, np.uint8, device="cuda") if "action" in want else None
-    per_dev = None if per_game is None else torch.from_numpy(np.asarray(per_game, np.uint8)).cuda()
-    ptr = lambda a: None if a is None else a.ptr
-    with torch.cuda.device(env.device):
-        _native.check(env.L.tarok_playout_cards(env._h, int(samples), int(salt), int(seats), env._p(per_dev), ptr(g_sum), ptr(g_act),
-                                                env._stream()))
-        torch.cuda.synchronize()
-    assert_guards_intact([g_sum, g_act], (n, samples, seats))
-    sums = acts = None
-    if g_sum is not None:
-        sums = g_sum.host()[0][0]
-        assert (sums != SENTINEL_I32).all(), "a word of sum_out was not written"
-    if g_act is not None:
-        acts, written = g_act.host()
-        assert written.all(), "a byte of action_out was not written"
-        acts = acts[0]
-    return sums, acts
+    return H.launch_det(env, None, samples, salt, seats, per_game, want)
 
 
 def model_scores(env, salt, sets, samples, seed=SEED):
@@ -86,10 +48,7 @@ def expected(model, samples, seed=SEED):
 def check(env, model, samples, salt=0, seats=15, per_game=None, tag=None):
     want_sum, want_act = expected(model, samples)
     got_sum, got_act = launch(env, samples, salt, seats, per_game)
-    bad = np.nonzero((got_sum != want_sum).any(axis=(1, 2)))[0]
-    assert bad.size == 0, (tag, "sums differ", bad[:8], got_sum[bad[0]].tolist(), want_sum[bad[0]].tolist())
-    bad = np.nonzero(got_act != want_act)[0]
-    assert bad.size == 0, (tag, "cards differ", bad[:8], got_act[bad[:8]], want_act[bad[:8]])
+    H.assert_cards_equal(got_sum, want_sum, got_act, want_act, tag)
     return got_sum, got_act
 
 

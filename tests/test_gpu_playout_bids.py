@@ -9,88 +9,32 @@ the model's replay alone, and no sign is asserted.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_playout_bids.py -m gpu -q
 """
-import os
+import functools
 
 import numpy as np
 import pytest
+
+import gpu_harness as H
+from gpu_harness import T, U, dev_u8  # noqa: F401  (T: the module fixture)
 
 pytestmark = pytest.mark.gpu
 
 SEED = 2                                 # chosen on the CPU with the model alone: see test_the_default_mask_on_32_games
 OFFSET = 3000                            # game offset of the envs: gidx = OFFSET + g
 EPISODE = 4                              # the keys' episode field is not zero
-SENTINEL_I32 = np.array([0xA5A5A5A5], np.uint32).view(np.int32)[0]
-U = np.uint64
 DEFAULT, ALL = 0x00F, 0x3FF
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    from tarok_amd import _native
-    tarok_amd.build()
-    assert os.path.exists(_native.LIB_PATH), "libtarokenv.so missing: the HIP path is the product, no fallback"
-    assert hasattr(_native.lib(), "tarok_playout_bids") and hasattr(_native.lib(), "tarok_bid_round")
-    return tarok_amd
-
-
-def make_env(T, n, seed=SEED, offset=OFFSET, **kw):
-    """An env of n games that has NOT been reset: bidding comes first."""
-    from oracle import tarok_spec as S
-    return T.TarokVecEnv(n, seed=seed, mix=S.MIX_BOT, game_offset=offset, **kw)
-
-
-def dev_u8(a):
-    import torch
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.uint8)).cuda()
+make_env = functools.partial(H.make_bid_env, seed=SEED, offset=OFFSET)   # (T, n, **kw): NOT reset, bidding comes first
+perms_of = functools.partial(H.perms_of, seed=SEED, offset=OFFSET, episode=EPISODE)
 
 
 def launch_bids(env, worlds, samples, contracts=DEFAULT, deals=None, salt=0, seats=15, per_game=None, episode=EPISODE):
     """One tarok_playout_bids into a guarded sum_out: [n, 4, 20] i32."""
-    import torch
-    from guarded import Guarded, assert_guards_intact
-    from tarok_amd import _native
-    n = env.n
-    g_sum = Guarded("sum_out", 1, n, np.int32, inner=(4, 20), device="cuda")
-    d, p = dev_u8(deals), dev_u8(per_game)
-    with torch.cuda.device(env.device):
-        _native.check(env.L.tarok_playout_bids(env._h, int(episode), env._p(d), int(worlds), int(samples), int(contracts), int(salt),
-                                               int(seats), env._p(p), g_sum.ptr, env._stream()))
-        torch.cuda.synchronize()
-    assert_guards_intact([g_sum], (n, worlds, samples, contracts, seats))
-    assert g_sum.ptr.value % 16 == 0
-    sums = g_sum.host()[0][0]
-    assert (sums != SENTINEL_I32).all(), "a word of sum_out was not written"
-    return sums
+    return H.launch_bids(env, worlds, samples, contracts, deals, salt, seats, per_game, episode=episode, entry="tarok_playout_bids")
 
 
 def launch_round(env, sums, playouts, threshold=0, contracts=DEFAULT, seats=15, per_game=None, episode=EPISODE):
     """One tarok_bid_round into three guarded outputs: [n, 3] i8 (contract, declarer, king)."""
-    import torch
-    from guarded import Guarded, assert_guards_intact
-    from tarok_amd import _native
-    n = env.n
-    outs = [Guarded(name, 1, n, np.int8, device="cuda") for name in ("contract_out", "declarer_out", "king_out")]
-    s = None if sums is None else torch.from_numpy(np.ascontiguousarray(sums, np.int32)).cuda()
-    p = dev_u8(per_game)
-    with torch.cuda.device(env.device):
-        _native.check(env.L.tarok_bid_round(env._h, int(episode), env._p(s), int(playouts), int(threshold), int(contracts), int(seats),
-                                            env._p(p), outs[0].ptr, outs[1].ptr, outs[2].ptr, env._stream()))
-        torch.cuda.synchronize()
-    assert_guards_intact(outs, (n, playouts, threshold, contracts, seats))
-    cols = []
-    for o in outs:
-        vals, written = o.host()
-        assert written.all(), "a byte of %s was not written" % o.name
-        cols.append(vals[0])
-    return np.stack(cols, axis=1)
-
-
-def perms_of(n, seed=SEED, offset=OFFSET, episode=EPISODE):
-    from oracle import tarok_spec as S
-    return [S.deal(S.game_key(seed, offset + g, episode)) for g in range(n)]
+    return H.launch_round(env, sums, playouts, threshold, contracts, seats, per_game, episode=episode, entry="tarok_bid_round")
 
 
 def model_scores(perms, seats_of, worlds, samples, contracts, salt=0, seed=SEED, offset=OFFSET, episode=EPISODE):

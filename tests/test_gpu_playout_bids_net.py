@@ -8,46 +8,34 @@ env's state is untouched.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_playout_bids_net.py -m gpu -q
 """
+import functools
+
 import numpy as np
 import pytest
 
-from test_gpu_playout_bids import ALL, DEFAULT, EPISODE, OFFSET, SEED, SENTINEL_I32, T, U, dev_u8, make_env, perms_of  # noqa: F401
-from test_gpu_playout_bids import launch_bids as bot_launch
-from test_gpu_playout_exchange_net import item_arrays, replay_on_a_twin
-from test_gpu_playout_net import nets, random_net  # noqa: F401  (nets: the fixture)
+import gpu_harness as H
+from gpu_harness import T, U, dev_u8, item_arrays, nets, random_net  # noqa: F401  (T, nets: the module fixtures)
 
 pytestmark = pytest.mark.gpu
 
+SEED, OFFSET, EPISODE = 2, 3000, 4                # tests/test_gpu_playout_bids.py's: the same deals
+DEFAULT, ALL = 0x00F, 0x3FF
 LIVE = 0x8000800080008000
+make_env = functools.partial(H.make_bid_env, seed=SEED, offset=OFFSET)   # (T, n, **kw): NOT reset, bidding comes first
+perms_of = functools.partial(H.perms_of, seed=SEED, offset=OFFSET, episode=EPISODE)
+replay_on_a_twin = functools.partial(H.replay_on_a_twin, seed=43)        # (the twin's seed of tests/test_gpu_playout_exchange_net.py)
+
+
+def bot_launch(env, worlds, samples, contracts=DEFAULT, deals=None, salt=0, seats=15, per_game=None, episode=EPISODE):
+    """One tarok_playout_bids into a guarded sum_out: [n, 4, 20] i32."""
+    return H.launch_bids(env, worlds, samples, contracts, deals, salt, seats, per_game, episode=episode, entry="tarok_playout_bids")
 
 
 def net_launch(env, kw, worlds, net_seats, contracts=DEFAULT, deals=None, salt=0, seats=15, per_game=None, episode=EPISODE,
                scratch_out=None):
     """One launch into a guarded sum_out [n, 4, 20] i32 over a guarded scratch.  scratch_out: a list that receives the
     scratch's bytes after the launch."""
-    import torch
-    from guarded import Guarded, assert_guards_intact
-    from tarok_amd import _native
-    n = env.n
-    size = int(env.L.tarok_playout_bids_net_scratch(env._h, int(worlds)))
-    assert size == n * 80 * worlds * 48 + n * 40
-    g_scr = Guarded("scratch", 1, size, np.uint8, device="cuda")
-    g_sum = Guarded("sum_out", 1, n, np.int32, inner=(4, 20), device="cuda")
-    d, p = dev_u8(deals), dev_u8(per_game)
-    before = env.state().copy(), env.counters()
-    with torch.cuda.device(env.device):
-        _native.check(env.L.tarok_playout_bids_net(env._h, int(episode), env._p(d), int(worlds), int(contracts), int(salt), int(seats),
-                                                   env._p(p), int(net_seats), *[env._p(t) for t in kw], g_scr.ptr, size, g_sum.ptr,
-                                                   env._stream()))
-        torch.cuda.synchronize()
-    assert_guards_intact([g_scr, g_sum], (n, worlds, contracts, net_seats, seats))
-    after = env.state(), env.counters()
-    assert (before[0] == after[0]).all() and all((a == b).all() for a, b in zip(before[1], after[1])), "the env was written"
-    if scratch_out is not None:
-        scratch_out.append(g_scr.host()[0][0].copy())
-    sums = g_sum.host()[0][0]
-    assert (sums != SENTINEL_I32).all(), "a word of sum_out was not written"
-    return sums
+    return H.launch_bids_net(env, kw, worlds, net_seats, contracts, deals, salt, seats, per_game, episode, scratch_out)
 
 
 def deals_of(perms, per_game=None):

@@ -5,12 +5,16 @@ themselves compute is the business of tests/test_gpu_playout*.py.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_playout_dispatch.py -m gpu -q
 """
+import functools
 import numpy as np
 import pytest
 
-from test_gpu_playout_det import T, make_env   # noqa: F401
+import gpu_harness as H
+from gpu_harness import T  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
+SEED, OFFSET, EPISODE = 41, 1000, 3               # tests/test_gpu_playout_det.py's: the same games
+make_env = functools.partial(H.make_env, seed=SEED, offset=OFFSET, episode=EPISODE)
 N = 67                                   # at (1, 1) a workgroup holds 64 four-lane teams: the second workgroup is ragged
 CARDS = 5
 SIZES = ((1, 1), (3, 2))

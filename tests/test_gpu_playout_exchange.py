@@ -1,8 +1,8 @@
 """GPU: tarok_playout_exchange (the declarer's talon exchange valued by determinized playouts) and the surface built on
 it, checked exactly — integers against integers — against the per-game model of tests/playout_exchange_model.py, which
 deals every world, samples every candidate and plays every playout on the CPU oracle.  All three outputs sit inside
-guard bands (tests/guarded.py) and every row of each is compared.  The helpers have the shape of
-tests/test_gpu_playout_det.py's.
+guard bands (tests/guarded.py) and every row of each is compared.  The launch helpers are
+tests/gpu_harness.py's.
 
 The advantage: tools/playout_exchange_advantage.py (the model alone, 512 deals, (8, 2, 4)) gives evaluate_exchange_vs_bot
 +1.27 points per game with a standard error of 0.26 — 4.8 of them, short of five — so no sign is asserted here: the
@@ -11,73 +11,24 @@ evaluations are held to exact reproduction of the model's replay alone (DESIGN 8
 Run on the GPU box:  python -m pytest tests/test_gpu_playout_exchange.py -m gpu -q
 """
 import functools
-import os
 
 import numpy as np
 import pytest
+
+import gpu_harness as H
+from gpu_harness import T, U, launch_exchange_bot as launch  # noqa: F401  (T: the module fixture)
 
 pytestmark = pytest.mark.gpu
 
 SEED = 43
 OFFSET = 2000                            # game offset of the envs: gidx = OFFSET + g
 EPISODE = 5                              # episode the envs are reset to: the keys' episode field is not zero
-SENTINEL_I32 = np.array([0xA5A5A5A5], np.uint32).view(np.int32)[0]
-U = np.uint64
 EXCHANGE_CODES = (1, 2, 3, 4, 5, 6)      # Tri, Dve, Ena, Solo_tri, Solo_dve, Solo_ena
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    from tarok_amd import _native
-    tarok_amd.build()
-    assert os.path.exists(_native.LIB_PATH), "libtarokenv.so missing: the HIP path is the product, no fallback"
-    assert hasattr(_native.lib(), "tarok_playout_exchange")
-    return tarok_amd
 
 
 def make_env(T, n, mix, cards=0, defer=True, seed=SEED):
     """An env of n games at EPISODE, waiting for the exchange where the contract has one (defer), after `cards` Bot cards."""
-    env = T.TarokVecEnv(n, seed=seed, mix=mix, game_offset=OFFSET)
-    env.reset(episode=EPISODE, defer_exchange=defer)
-    for _ in range(cards):
-        env.step_random(auto_reset=False)
-    return env
-
-
-def launch(env, worlds, samples, sets, salt=0, seats=15, per_game=None, want=("sum", "choice", "discards")):
-    """One launch into guarded outputs: (sum [n, 6 * sets, 4] i32, choice [n] i8, discards [n, 3] u8), None where not asked."""
-    import torch
-    from guarded import Guarded, assert_guards_intact
-    from tarok_amd import _native
-    n = env.n
-    g_sum = Guarded("sum_out", 1, n, np.int32, inner=(6 * sets, 4), device="cuda") if "sum" in want else None
-    g_ch = Guarded("choice_out", 1, n, np.int8, device="cuda") if "choice" in want else None
-    g_di = Guarded("discards_out", 1, n, np.uint8, inner=(3,), device="cuda") if "discards" in want else None
-    per_dev = None if per_game is None else torch.from_numpy(np.asarray(per_game, np.uint8)).cuda()
-    ptr = lambda a: None if a is None else a.ptr
-    with torch.cuda.device(env.device):
-        rc = env.L.tarok_playout_exchange(env._h, int(worlds), int(samples), int(sets), int(salt), int(seats), env._p(per_dev),
-                                          ptr(g_sum), ptr(g_ch), ptr(g_di), env._stream())
-        _native.check(rc)
-        torch.cuda.synchronize()
-    assert_guards_intact([g_sum, g_ch, g_di], (n, worlds, samples, sets, seats))
-    sums = choice = disc = None
-    if g_sum is not None:
-        assert g_sum.ptr.value % 16 == 0
-        sums = g_sum.host()[0][0]
-        assert (sums != SENTINEL_I32).all(), "a word of sum_out was not written"
-    if g_ch is not None:
-        choice, written = g_ch.host()
-        assert written.all(), "a byte of choice_out was not written"
-        choice = choice[0]
-    if g_di is not None:
-        disc, _ = g_di.host()
-        disc = disc[0]
-        assert (disc != 0xA5).all(), "a byte of discards_out was not written"
-    return sums, choice, disc
+    return H.make_env(T, n, mix, cards, seed=seed, offset=OFFSET, episode=EPISODE, defer_exchange=defer)
 
 
 def model_scores(env, salt, sets_of_seats, worlds, samples, sets, seed=SEED):

@@ -8,62 +8,31 @@ that the env's state is untouched.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_playout_exchange_net.py -m gpu -q
 """
+import functools
+
 import numpy as np
 import pytest
 
-from test_gpu_playout_exchange import EPISODE, OFFSET, SEED, SENTINEL_I32, T, U, make_env  # noqa: F401  (T: the fixture)
-from test_gpu_playout_exchange import launch as bot_launch
-from test_gpu_playout_net import nets, random_net  # noqa: F401  (nets: the fixture)
+import gpu_harness as H
+from gpu_harness import T, U, item_arrays, nets, random_net  # noqa: F401  (T, nets: the module fixtures)
 
 pytestmark = pytest.mark.gpu
 
+SEED, OFFSET, EPISODE = 43, 2000, 5               # tests/test_gpu_playout_exchange.py's: the same games
 LIVE = 0x8000800080008000
+games_of = functools.partial(H.games_of, offset=OFFSET)
+replay_on_a_twin = functools.partial(H.replay_on_a_twin, seed=SEED)
+make_env = functools.partial(H.make_env, seed=SEED, offset=OFFSET, episode=EPISODE, defer_exchange=True)   # waiting for the exchange
+bot_launch = H.launch_exchange_bot
 
 
 def net_launch(env, kw, worlds, sets, net_seats, salt=0, seats=15, per_game=None, want=("sum", "choice", "discards"), scratch_out=None):
     """One launch into guarded outputs over a guarded scratch: (sum [n, 6 * sets, 4] i32, choice [n] i8, discards [n, 3] u8),
     None where not asked.  scratch_out: a list that receives the scratch's bytes after the launch."""
-    import torch
-    from guarded import Guarded, assert_guards_intact
-    from tarok_amd import _native
-    n = env.n
-    size = int(env.L.tarok_playout_exchange_net_scratch(env._h, int(worlds), int(sets)))
-    assert size == n * 6 * sets * worlds * 48
-    g_scr = Guarded("scratch", 1, size, np.uint8, device="cuda")
-    g_sum = Guarded("sum_out", 1, n, np.int32, inner=(6 * sets, 4), device="cuda") if "sum" in want else None
-    g_ch = Guarded("choice_out", 1, n, np.int8, device="cuda") if "choice" in want else None
-    g_di = Guarded("discards_out", 1, n, np.uint8, inner=(3,), device="cuda") if "discards" in want else None
-    per_dev = None if per_game is None else torch.from_numpy(np.asarray(per_game, np.uint8)).cuda()
-    ptr = lambda a: None if a is None else a.ptr
-    before = env.state().copy(), env.counters()
-    with torch.cuda.device(env.device):
-        _native.check(env.L.tarok_playout_exchange_net(env._h, int(worlds), int(sets), int(salt), int(seats), env._p(per_dev),
-                                                       int(net_seats), *[env._p(t) for t in kw], g_scr.ptr, size, ptr(g_sum),
-                                                       ptr(g_ch), ptr(g_di), env._stream()))
-        torch.cuda.synchronize()
-    assert_guards_intact([g_scr, g_sum, g_ch, g_di], (n, worlds, sets, net_seats, seats))
-    after = env.state(), env.counters()
-    assert (before[0] == after[0]).all() and all((a == b).all() for a, b in zip(before[1], after[1])), "the env was written"
-    if scratch_out is not None:
-        scratch_out.append(g_scr.host()[0][0].copy())
-    sums = choice = disc = None
-    if g_sum is not None:
-        sums = g_sum.host()[0][0]
-        assert (sums != SENTINEL_I32).all(), "a word of sum_out was not written"
-    if g_ch is not None:
-        choice, written = g_ch.host()
-        assert written.all(), "a byte of choice_out was not written"
-        choice = choice[0]
-    if g_di is not None:
-        disc = g_di.host()[0][0]
-        assert (disc != 0xA5).all(), "a byte of discards_out was not written"
-    return sums, choice, disc
-
-
-def games_of(env, per_game=None):
-    lanes = env.state()
-    ep, _ = env.counters()
-    return [(lanes[:, g].copy(), int(ep[g]), OFFSET + g, None if per_game is None else int(per_game[g]) & 15) for g in range(env.n)]
+    return H.launch_exchange(env, "tarok_playout_exchange_net",
+                             [int(worlds), int(sets), int(salt), int(seats), H.dev_u8(per_game), int(net_seats)] + list(kw), sets, want,
+                             scratch=("tarok_playout_exchange_net_scratch", (int(worlds), int(sets)), env.n * 6 * sets * worlds * 48),
+                             check_env_untouched=True, tag=(worlds, sets, net_seats, seats), scratch_out=scratch_out)
 
 
 def check_model(env, W, kw, worlds, sets, net_seats, salt=0, seats=15, per_game=None, tag=None):
@@ -140,41 +109,6 @@ def test_seat_sets_and_the_network_in_the_loop(T, nets):
         assert (sb != sr).any() and (sr != sp).any()
     finally:
         env.close()
-
-
-def replay_on_a_twin(T, kw, hs):
-    """The final scores [m, 4] of the oracle Games `hs` (at 0 cards played) put into a twin env through the canonical lanes
-    and played to their ends by the greedy tarok_policy_step on every seat."""
-    import torch
-    from oracle import tarok_spec as S
-    m = len(hs)
-    twin = T.TarokVecEnv(m, seed=SEED, mix=S.MIX_ALL)
-    try:
-        twin.reset()
-        twin.set_state(np.stack([h.lanes() for h in hs], axis=1))
-        twin.set_play_mode(0.0, 0.0)
-        words = [twin.legal_actions().words.clone(), torch.zeros(m, dtype=torch.int64, device="cuda")]
-        act = torch.zeros(m, dtype=torch.uint8, device="cuda")
-        rew, dn = torch.zeros((m, 4), dtype=torch.int16, device="cuda"), torch.zeros(m, dtype=torch.uint8, device="cuda")
-        final, finished = np.zeros((m, 4), np.int64), np.zeros(m, bool)
-        for t in range(48):
-            if finished.all():
-                break
-            twin.policy_step(kw, words[t & 1], words[(t + 1) & 1], act, reward_out=rew, done_out=dn, auto_reset=False)
-            d = dn.cpu().numpy().astype(bool) & ~finished
-            final[d] = rew.cpu().numpy()[d]
-            finished |= d
-        assert finished.all()
-    finally:
-        twin.close()
-    return final
-
-
-def item_arrays(scratch, items):
-    """(keys [items] u64, results [items, 4] i16 and as u64) of a launch's scratch bytes."""
-    keys = scratch[items * 32:items * 40].view(np.uint64)
-    res = scratch[items * 40:items * 48]
-    return keys, res.view(np.int16).reshape(items, 4), res.view(np.uint64)
 
 
 def test_random_weights_against_a_twin_replay(T):

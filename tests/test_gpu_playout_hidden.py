@@ -1,49 +1,31 @@
 """GPU: tarok_playout_cards_hidden (determinized playouts whose worlds also re-deal Klop's face-down talon and the
 declarer's discards) and the surface built on it, checked exactly — integers against integers — against the per-game
 model of tests/playout_hidden_model.py, which rebuilds every word of played cards from the history, deals every world
-and plays every playout on the CPU oracle.  Outputs sit inside guard bands (tests/guarded.py).  The helpers have the
-shape of tests/test_gpu_playout_det.py's.
+and plays every playout on the CPU oracle.  Outputs sit inside guard bands (tests/guarded.py).  The launch helpers are
+tests/gpu_harness.py's.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_playout_hidden.py -m gpu -q
 """
+import functools
+
 import numpy as np
 import pytest
 
-from test_gpu_playout_det import EPISODE, OFFSET, SEED, SENTINEL_I32, T, launch as launch_det, make_env   # noqa: F401
+import gpu_harness as H
+from gpu_harness import T, launch_det  # noqa: F401  (T: the module fixture)
 
 pytestmark = pytest.mark.gpu
 U = np.uint64
+SEED, OFFSET, EPISODE = 41, 1000, 3               # tests/test_gpu_playout_det.py's: the same games
 KLOP, DVE, BERAC, SOLO_BREZ = 0, 2, 7, 8
 HIDING = (0, 1, 2, 3, 4, 5, 6)                    # Klop and the six contracts with an exchange
+make_env = functools.partial(H.make_env, seed=SEED, offset=OFFSET, episode=EPISODE)
 
 
 def launch(env, worlds, samples, played=None, salt=0, seats=15, per_game=None, want=("sum", "action")):
     """One launch into guarded outputs: (sum [n,12,4] i32 or None, action [n] u8 or None).  played: [n] u64 host array;
     None: the env's own (TarokVecEnv.played_cards)."""
-    import torch
-    from guarded import Guarded, assert_guards_intact
-    from tarok_amd import _native
-    n = env.n
-    g_sum = Guarded("sum_out", 1, n, np.int32, inner=(12, 4), device="cuda") if "sum" in want else None
-    g_act = Guarded("action_out", 1, n, np.uint8, device="cuda") if "action" in want else None
-    ptr = lambda a: None if a is None else a.ptr
-    with torch.cuda.device(env.device):
-        per_dev = None if per_game is None else torch.from_numpy(np.asarray(per_game, np.uint8)).cuda()
-        words = env.played_cards() if played is None else torch.from_numpy(np.asarray(played, np.uint64).view(np.int64).copy()).cuda()
-        rc = env.L.tarok_playout_cards_hidden(env._h, int(worlds), int(samples), int(salt), int(seats), env._p(per_dev), env._p(words),
-                                              ptr(g_sum), ptr(g_act), env._stream())
-        _native.check(rc)
-        torch.cuda.synchronize()
-    assert_guards_intact([g_sum, g_act], (n, worlds, samples, seats))
-    sums = acts = None
-    if g_sum is not None:
-        sums = g_sum.host()[0][0]
-        assert (sums != SENTINEL_I32).all(), "a word of sum_out was not written"
-    if g_act is not None:
-        acts, written = g_act.host()
-        assert written.all(), "a byte of action_out was not written"
-        acts = acts[0]
-    return sums, acts
+    return H.launch_worlds("hidden", env, worlds, samples, played, salt, seats, per_game, want)
 
 
 def own_played(env):
@@ -70,10 +52,7 @@ def check(env, model, worlds, samples, played=None, salt=0, seats=15, per_game=N
     want_sum = np.stack([HM.sums_of(sc, worlds, samples) for _, _, _, sc in model])
     want_act = np.array([PM.card_of(lanes, seed, OFFSET + g, ep, s, want_sum[g]) for g, (lanes, ep, s, _) in enumerate(model)], np.uint8)
     got_sum, got_act = launch(env, worlds, samples, played, salt, seats, per_game)
-    bad = np.nonzero((got_sum != want_sum).any(axis=(1, 2)))[0]
-    assert bad.size == 0, (tag, "sums differ", bad[:8], got_sum[bad[0]].tolist(), want_sum[bad[0]].tolist())
-    bad = np.nonzero(got_act != want_act)[0]
-    assert bad.size == 0, (tag, "cards differ", bad[:8], got_act[bad[:8]], want_act[bad[:8]])
+    H.assert_cards_equal(got_sum, want_sum, got_act, want_act, tag)
     return got_sum, got_act
 
 

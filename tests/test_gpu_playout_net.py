@@ -7,78 +7,31 @@ that the env's state is untouched.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_playout_net.py -m gpu -q
 """
+import functools
+
 import numpy as np
 import pytest
 
-from test_gpu_playout_det import EPISODE, OFFSET, SEED, SENTINEL_I32, T, U, make_env  # noqa: F401  (T: the fixture)
-from test_gpu_playout_det import launch as det_launch
+import gpu_harness as H
+from gpu_harness import T, U, nets, random_net  # noqa: F401  (T, nets: the module fixtures)
+from gpu_harness import launch_det as det_launch
 
 pytestmark = pytest.mark.gpu
+SEED, OFFSET, EPISODE = 41, 1000, 3               # tests/test_gpu_playout_det.py's: the same games
+make_env = functools.partial(H.make_env, seed=SEED, offset=OFFSET, episode=EPISODE)
+games_of = functools.partial(H.games_of, offset=OFFSET)
 
 
 def net_launch(env, kw, worlds, net_seats, salt=0, seats=15, per_game=None, want=("sum", "action")):
     """One launch into guarded outputs over a guarded scratch: (sum [n,12,4] i32 or None, action [n] u8 or None)."""
-    import torch
-    from guarded import Guarded, assert_guards_intact
-    from tarok_amd import _native
-    n = env.n
-    size = int(env.L.tarok_playout_net_scratch(env._h, int(worlds)))
-    assert size == n * 12 * worlds * 48
-    g_scr = Guarded("scratch", 1, size, np.uint8, device="cuda")
-    g_sum = Guarded("sum_out", 1, n, np.int32, inner=(12, 4), device="cuda") if "sum" in want else None
-    g_act = Guarded("action_out", 1, n, np.uint8, device="cuda") if "action" in want else None
-    per_dev = None if per_game is None else torch.from_numpy(np.asarray(per_game, np.uint8)).cuda()
-    ptr = lambda a: None if a is None else a.ptr
-    before = env.state().copy(), env.counters()
-    with torch.cuda.device(env.device):
-        _native.check(env.L.tarok_playout_cards_net(env._h, int(worlds), int(salt), int(seats), env._p(per_dev), int(net_seats),
-                                                    *[env._p(t) for t in kw], g_scr.ptr, size, ptr(g_sum), ptr(g_act), env._stream()))
-        torch.cuda.synchronize()
-    assert_guards_intact([g_scr, g_sum, g_act], (n, worlds, net_seats, seats))
-    after = env.state(), env.counters()
-    assert (before[0] == after[0]).all() and all((a == b).all() for a, b in zip(before[1], after[1])), "the env was written"
-    sums = acts = None
-    if g_sum is not None:
-        sums = g_sum.host()[0][0]
-        assert (sums != SENTINEL_I32).all(), "a word of sum_out was not written"
-    if g_act is not None:
-        acts, written = g_act.host()
-        assert written.all(), "a byte of action_out was not written"
-        acts = acts[0]
-    return sums, acts
-
-
-@pytest.fixture(scope="module")
-def nets(T):
-    """The exactly summable weight sets of tests/test_gpu_policy_exact.py — R and one P — as (float64 set, kernel set)."""
-    import test_gpu_policy_exact as PE
-    WR, WP = PE.weights_r(), PE.weights_p(*PE.P_PARAMS[2])
-    return dict(R=(WR, PE.kernel_weights(T, WR)), P=(WP, PE.kernel_weights(T, WP)))
-
-
-def random_net(T, seed):
-    import torch
-    g = torch.Generator(); g.manual_seed(seed)
-    order = T.TarokVecEnv.mfma_weight_order
-    r = lambda *s: torch.randn(*s, generator=g)
-    return [order((r(256, 256) / 6).cuda()), (r(256) / 4).cuda(), order((r(256, 256) / 12).cuda()), (r(256) / 4).cuda(),
-            order((r(64, 256) / 12).cuda()), (r(64) / 4).cuda()]
-
-
-def games_of(env, per_game=None):
-    lanes = env.state()
-    ep, _ = env.counters()
-    return [(lanes[:, g].copy(), int(ep[g]), OFFSET + g, None if per_game is None else int(per_game[g]) & 15) for g in range(env.n)]
+    return H.launch_net("det", env, kw, worlds, net_seats, None, salt, seats, per_game, want)
 
 
 def check_model(env, W, kw, worlds, net_seats, salt=0, seats=15, per_game=None, tag=None):
     import playout_net_model as NM
     want_sum, want_act = NM.playout_cards(games_of(env, per_game), SEED, salt, seats, worlds, W, net_seats)
     got_sum, got_act = net_launch(env, kw, worlds, net_seats, salt, seats, per_game)
-    bad = np.nonzero((got_sum != want_sum).any(axis=(1, 2)))[0]
-    assert bad.size == 0, (tag, "sums differ", bad[:8], got_sum[bad[0]].tolist(), want_sum[bad[0]].tolist())
-    bad = np.nonzero(got_act != want_act)[0]
-    assert bad.size == 0, (tag, "cards differ", bad[:8], got_act[bad[:8]], want_act[bad[:8]])
+    H.assert_cards_equal(got_sum, want_sum, got_act, want_act, tag)
     return got_sum, got_act
 
 

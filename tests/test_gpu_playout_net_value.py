@@ -1,66 +1,44 @@
 """GPU: tarok_playout_cards_net_value (net playouts stopped at the viewer's depth-th decision, the value head's estimate
 in the viewer's column) checked exactly — integers against integers: depth 12 against the bytes of the three existing
 launches; exactly summable integer weights at depths 1..3 against the model of tests/playout_net_value_model.py, over the
-plan of tests/test_playout_net_value_cpu.py; random weights at net_seats = 0 against tarok_policy_mlp's value_out on the
+plan of tests/playout_net_value_cases.py; random weights at net_seats = 0 against tarok_policy_mlp's value_out on the
 model's stop positions; a captured graph after the weights changed in place; every TAROK_EINVAL; the teacher inside the
 captured rollout and the evaluation.  Every launch writes into guard bands (tests/guarded.py) over a guarded scratch and
 leaves the env, its counters and its history as they were.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_playout_net_value.py -m gpu -q
 """
+import functools
+
 import numpy as np
 import pytest
 
+import gpu_harness as H
+import playout_net_value_cases as PC
 import playout_net_value_model as VM
-import test_playout_net_value_cpu as PC
-from test_gpu_playout_det import EPISODE, OFFSET, SEED, T, U, make_env  # noqa: F401  (T: the fixture)
-from test_gpu_playout_net import games_of, random_net
-from test_gpu_playout_net import net_launch as det_net_launch
-from test_gpu_playout_net_worlds import host_words, model_words, outputs, read, words_of
-from test_gpu_playout_net_worlds import net_launch as worlds_net_launch
+from gpu_harness import T, U, host_words, model_words, random_net, words_of  # noqa: F401  (T: the module fixture)
 
 pytestmark = pytest.mark.gpu
+SEED, OFFSET, EPISODE = 41, 1000, 3               # tests/test_gpu_playout_det.py's: the same games
 SEEN = dict(tags=set(), moved=0, cases=set())
+make_env = functools.partial(H.make_env, seed=SEED, offset=OFFSET, episode=EPISODE)
+games_of = functools.partial(H.games_of, offset=OFFSET)
 
 
 @pytest.fixture(scope="module")
 def nets(T):
-    """R, P and V of tests/test_playout_net_value_cpu.weight_sets as (float64 set, kernel set)."""
-    import test_gpu_policy_exact as PE
+    """R, P and V of tests/playout_net_value_cases.weight_sets as (float64 set, kernel set)."""
+    import policy_exact_ref as PE
     return {k: (W, PE.kernel_weights(T, W)) for k, W in PC.weight_sets().items()}
 
 
 def value_launch(kind, env, kw, worlds, net_seats, depth, value_scale, words=None, salt=0, seats=15, per_game=None, want=("sum", "action")):
     """One launch of the kind into guarded outputs over a guarded scratch: (sum [n,12,4] i32 or None, action [n] u8 or None)."""
-    import torch
-    from guarded import Guarded, assert_guards_intact
-    from tarok_amd import _native
-    n = env.n
-    size = int(env.L.tarok_playout_net_scratch(env._h, int(worlds)))
-    assert size == n * 12 * worlds * 48
-    g_scr = Guarded("scratch", 1, size, np.uint8, device="cuda")
-    g_sum, g_act = outputs(n, want)
-    ptr = lambda a: None if a is None else a.ptr
-    snap = lambda: (env.state().copy(), env.counters(), env.get_history().cpu().numpy().copy())
-    before = snap()
-    with torch.cuda.device(env.device):
-        per_dev = None if per_game is None else torch.from_numpy(np.asarray(per_game, np.uint8)).cuda()
-        w = None if kind == "det" else words_of(kind, env, words)
-        _native.check(env.L.tarok_playout_cards_net_value(env._h, int(worlds), int(salt), int(seats), env._p(per_dev), VM.KINDS.index(kind),
-                                                          env._p(w), int(net_seats), int(depth), float(value_scale),
-                                                          *[env._p(t) for t in kw], g_scr.ptr, size, ptr(g_sum), ptr(g_act), env._stream()))
-        torch.cuda.synchronize()
-    assert_guards_intact([g_scr, g_sum, g_act], (kind, n, worlds, net_seats, depth, seats))
-    after = snap()
-    assert (before[0] == after[0]).all() and (before[2] == after[2]).all(), "the env was written"
-    assert all((a == b).all() for a, b in zip(before[1], after[1])), "the env's counters were written"
-    return read(g_sum, g_act)
+    return H.launch_net(kind, env, kw, worlds, net_seats, words, salt, seats, per_game, want, value=(depth, value_scale))
 
 
 def existing_launch(kind, env, kw, worlds, net_seats, salt, seats, per_game):
-    if kind == "det":
-        return det_net_launch(env, kw, worlds, net_seats, salt, seats, per_game)
-    return worlds_net_launch(kind, env, kw, worlds, net_seats, None, salt, seats, per_game)
+    return H.launch_net(kind, env, kw, worlds, net_seats, None, salt, seats, per_game)
 
 
 @pytest.mark.parametrize("kind", VM.KINDS)
@@ -110,10 +88,7 @@ def test_integer_weights_against_the_model(T, nets, kind, at):
                 want_act = np.array([PM.card_of(lanes, SEED, gidx, ep, 15, want_sum[g]) for g, (lanes, ep, gidx, _) in enumerate(games)], np.uint8)
                 got_sum, got_act = value_launch(kind, env, kw, worlds, net_seats, depth, scale, None, PC.SALT)
                 tag = (kind, cards, n, depth, name, net_seats, scale)
-                bad = np.nonzero((got_sum != want_sum).any(axis=(1, 2)))[0]
-                assert bad.size == 0, (tag, "sums differ", bad[:8], got_sum[bad[0]].tolist(), want_sum[bad[0]].tolist())
-                bad = np.nonzero(got_act != want_act)[0]
-                assert bad.size == 0, (tag, "cards differ", bad[:8], got_act[bad[:8]], want_act[bad[:8]])
+                H.assert_cards_equal(got_sum, want_sum, got_act, want_act, tag)
                 SEEN["tags"] |= VM.seen([(w, dict(d, V=VM.points(d["v"], scale) if d["stopped"] else None)) for w, d in info], scale)
                 if full is not None and scale == 1.0:
                     SEEN["moved"] += int((got_act != full).sum())

@@ -8,102 +8,29 @@ the env and its history as they were.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_playout_net_worlds.py -m gpu -q
 """
+import functools
+
 import numpy as np
 import pytest
 
-from test_gpu_playout_det import EPISODE, OFFSET, SEED, SENTINEL_I32, T, U, make_env  # noqa: F401  (T: the fixture)
-from test_gpu_playout_net import games_of, nets  # noqa: F401  (nets: the fixture)
-from test_gpu_playout_net import net_launch as det_net_launch
+import gpu_harness as H
+from gpu_harness import T, U, host_words, model_words, nets, words_of  # noqa: F401  (T, nets: the module fixtures)
 
 pytestmark = pytest.mark.gpu
+SEED, OFFSET, EPISODE = 41, 1000, 3               # tests/test_gpu_playout_det.py's: the same games
 KLOP, DVE, BERAC, SOLO_BREZ = 0, 2, 7, 8
 KINDS = ("voids", "hidden")
 NET_FN = dict(voids="tarok_playout_cards_net_voids", hidden="tarok_playout_cards_net_hidden")
-BOT_FN = dict(voids="tarok_playout_cards_voids", hidden="tarok_playout_cards_hidden")
-WORD = dict(voids=(np.uint32, np.int32), hidden=(np.uint64, np.int64))
 SHAPES = [(5, 3), (1, 1)]                         # 180 item slots: a full tile of 128 and a partial one; one partial tile
-
-
-def words_of(kind, env, words=None):
-    """The launch's word tensor: the env's own (shown_voids / played_cards), or a host array of the caller's."""
-    import torch
-    if words is None:
-        return env.shown_voids() if kind == "voids" else env.played_cards()
-    u, i = WORD[kind]
-    return torch.from_numpy(np.asarray(words, u).view(i).copy()).cuda()
-
-
-def host_words(kind, env):
-    return words_of(kind, env).cpu().numpy().view(WORD[kind][0])
-
-
-def model_words(kind, env):
-    """The env's words rebuilt on the oracle from its state and history."""
-    import playout_hidden_model as HM
-    import playout_voids_model as VM
-    lanes, hist = env.state(), env.get_history().cpu().numpy()
-    f = VM.voids_of_lanes if kind == "voids" else HM.played_of_lanes
-    return np.array([f(lanes[:, g], hist[:, g]) for g in range(env.n)], WORD[kind][0])
-
-
-def outputs(n, want):
-    from guarded import Guarded
-    g_sum = Guarded("sum_out", 1, n, np.int32, inner=(12, 4), device="cuda") if "sum" in want else None
-    g_act = Guarded("action_out", 1, n, np.uint8, device="cuda") if "action" in want else None
-    return g_sum, g_act
-
-
-def read(g_sum, g_act):
-    sums = acts = None
-    if g_sum is not None:
-        sums = g_sum.host()[0][0]
-        assert (sums != SENTINEL_I32).all(), "a word of sum_out was not written"
-    if g_act is not None:
-        acts, written = g_act.host()
-        assert written.all(), "a byte of action_out was not written"
-        acts = acts[0]
-    return sums, acts
-
-
-def net_launch(kind, env, kw, worlds, net_seats, words=None, salt=0, seats=15, per_game=None, want=("sum", "action")):
-    """One launch of the kind into guarded outputs over a guarded scratch: (sum [n,12,4] i32 or None, action [n] u8 or None)."""
-    import torch
-    from guarded import Guarded, assert_guards_intact
-    from tarok_amd import _native
-    n = env.n
-    size = int(env.L.tarok_playout_net_scratch(env._h, int(worlds)))
-    assert size == n * 12 * worlds * 48
-    g_scr = Guarded("scratch", 1, size, np.uint8, device="cuda")
-    g_sum, g_act = outputs(n, want)
-    ptr = lambda a: None if a is None else a.ptr
-    snap = lambda: (env.state().copy(), env.counters(), env.get_history().cpu().numpy().copy())
-    before = snap()
-    with torch.cuda.device(env.device):
-        per_dev = None if per_game is None else torch.from_numpy(np.asarray(per_game, np.uint8)).cuda()
-        w = words_of(kind, env, words)
-        _native.check(getattr(env.L, NET_FN[kind])(env._h, int(worlds), int(salt), int(seats), env._p(per_dev), env._p(w), int(net_seats),
-                                                   *[env._p(t) for t in kw], g_scr.ptr, size, ptr(g_sum), ptr(g_act), env._stream()))
-        torch.cuda.synchronize()
-    assert_guards_intact([g_scr, g_sum, g_act], (kind, n, worlds, net_seats, seats))
-    after = snap()
-    assert (before[0] == after[0]).all() and (before[2] == after[2]).all(), "the env was written"
-    assert all((a == b).all() for a, b in zip(before[1], after[1])), "the env's counters were written"
-    return read(g_sum, g_act)
+make_env = functools.partial(H.make_env, seed=SEED, offset=OFFSET, episode=EPISODE)
+games_of = functools.partial(H.games_of, offset=OFFSET)
+det_net_launch = functools.partial(H.launch_net, "det")
+net_launch = H.launch_net                         # (kind, env, kw, worlds, net_seats, words, salt, seats, per_game, want)
 
 
 def bot_launch(kind, env, worlds, salt=0, seats=15, per_game=None):
     """tarok_playout_cards_voids / _hidden at (worlds, 1) on the env's own words, into guarded outputs."""
-    import torch
-    from guarded import assert_guards_intact
-    from tarok_amd import _native
-    g_sum, g_act = outputs(env.n, ("sum", "action"))
-    with torch.cuda.device(env.device):
-        per_dev = None if per_game is None else torch.from_numpy(np.asarray(per_game, np.uint8)).cuda()
-        _native.check(getattr(env.L, BOT_FN[kind])(env._h, int(worlds), 1, int(salt), int(seats), env._p(per_dev),
-                                                   env._p(words_of(kind, env)), g_sum.ptr, g_act.ptr, env._stream()))
-        torch.cuda.synchronize()
-    assert_guards_intact([g_sum, g_act], (kind, env.n, worlds, seats))
-    return read(g_sum, g_act)
+    return H.launch_worlds(kind, env, worlds, 1, None, salt, seats, per_game)
 
 
 def check_model(kind, env, W, kw, worlds, net_seats, salt=0, seats=15, per_game=None, tag=None):
@@ -113,10 +40,7 @@ def check_model(kind, env, W, kw, worlds, net_seats, salt=0, seats=15, per_game=
     assert (host_words(kind, env) == words).all(), (tag, "the env's words are not the model's")
     want_sum, want_act = WM.playout_cards(kind, games_of(env, per_game), SEED, salt, seats, worlds, W, net_seats, [int(x) for x in words])
     got_sum, got_act = net_launch(kind, env, kw, worlds, net_seats, None, salt, seats, per_game)
-    bad = np.nonzero((got_sum != want_sum).any(axis=(1, 2)))[0]
-    assert bad.size == 0, (tag, "sums differ", bad[:8], got_sum[bad[0]].tolist(), want_sum[bad[0]].tolist())
-    bad = np.nonzero(got_act != want_act)[0]
-    assert bad.size == 0, (tag, "cards differ", bad[:8], got_act[bad[:8]], want_act[bad[:8]])
+    H.assert_cards_equal(got_sum, want_sum, got_act, want_act, tag)
     return got_sum, got_act
 
 

@@ -1,40 +1,28 @@
 """GPU: tarok_playout_cards_voids (determinized playouts whose worlds honour shown voids) and the surface built on it,
 checked exactly — integers against integers — against the per-game model of tests/playout_voids_model.py, which rebuilds
 every void word from the history, deals every world and plays every playout on the CPU oracle.  Outputs sit inside guard
-bands (tests/guarded.py).  The helpers have the shape of tests/test_gpu_playout_det.py's.
+bands (tests/guarded.py).  The launch helpers are tests/gpu_harness.py's.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_playout_voids.py -m gpu -q
 """
+import functools
+
 import numpy as np
 import pytest
 
-from test_gpu_playout_det import EPISODE, OFFSET, SEED, SENTINEL_I32, T, launch as launch_det, make_env   # noqa: F401
+import gpu_harness as H
+from gpu_harness import T, launch_det  # noqa: F401  (T: the module fixture)
 
 pytestmark = pytest.mark.gpu
 U = np.uint64
+SEED, OFFSET, EPISODE = 41, 1000, 3               # tests/test_gpu_playout_det.py's: the same games
+make_env = functools.partial(H.make_env, seed=SEED, offset=OFFSET, episode=EPISODE)
 
 
 def launch(env, worlds, samples, voids=None, salt=0, seats=15):
     """One launch into guarded outputs: (sum [n,12,4] i32, action [n] u8).  voids: [n] u32 host array; None: the env's own
     (TarokVecEnv.shown_voids)."""
-    import torch
-    from guarded import Guarded, assert_guards_intact
-    from tarok_amd import _native
-    n = env.n
-    g_sum = Guarded("sum_out", 1, n, np.int32, inner=(12, 4), device="cuda")
-    g_act = Guarded("action_out", 1, n, np.uint8, device="cuda")
-    with torch.cuda.device(env.device):
-        words = env.shown_voids() if voids is None else torch.from_numpy(np.asarray(voids, np.uint32).view(np.int32).copy()).cuda()
-        rc = env.L.tarok_playout_cards_voids(env._h, int(worlds), int(samples), int(salt), int(seats), None, env._p(words), g_sum.ptr,
-                                             g_act.ptr, env._stream())
-        _native.check(rc)
-        torch.cuda.synchronize()
-    assert_guards_intact([g_sum, g_act], (n, worlds, samples, seats))
-    sums = g_sum.host()[0][0]
-    assert (sums != SENTINEL_I32).all(), "a word of sum_out was not written"
-    acts, written = g_act.host()
-    assert written.all(), "a byte of action_out was not written"
-    return sums, acts[0]
+    return H.launch_worlds("voids", env, worlds, samples, voids, salt, seats)
 
 
 def own_voids(env):
@@ -57,10 +45,7 @@ def check(env, model, worlds, samples, voids, salt=0, tag=None, seed=SEED):
     want_sum = np.stack([VM.sums_of(sc, worlds, samples) for _, _, _, sc in model])
     want_act = np.array([PM.card_of(lanes, seed, OFFSET + g, ep, s, want_sum[g]) for g, (lanes, ep, s, _) in enumerate(model)], np.uint8)
     got_sum, got_act = launch(env, worlds, samples, voids, salt)
-    bad = np.nonzero((got_sum != want_sum).any(axis=(1, 2)))[0]
-    assert bad.size == 0, (tag, "sums differ", bad[:8], got_sum[bad[0]].tolist(), want_sum[bad[0]].tolist())
-    bad = np.nonzero(got_act != want_act)[0]
-    assert bad.size == 0, (tag, "cards differ", bad[:8], got_act[bad[:8]], want_act[bad[:8]])
+    H.assert_cards_equal(got_sum, want_sum, got_act, want_act, tag)
     return got_sum, got_act
 
 

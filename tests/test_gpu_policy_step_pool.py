@@ -9,10 +9,11 @@ that card through the per-slot model on the CPU oracle (tests/oracle_model.py).
 
 Run on the GPU box:  python -m pytest tests/test_gpu_policy_step_pool.py -m gpu -q
 """
-import os
 
 import numpy as np
 import pytest
+
+from gpu_harness import T  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -33,17 +34,6 @@ CASES = [
 
 
 @pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    from tarok_amd import _native
-    tarok_amd.build()
-    assert os.path.exists(_native.LIB_PATH), "libtarokenv.so missing: the HIP path is the product, no fallback"
-    return tarok_amd
-
-
-@pytest.fixture(scope="module")
 def S():
     from oracle import tarok_spec
     return tarok_spec
@@ -53,7 +43,7 @@ def S():
 def nets(T):
     """(the learner's weight set, [three pool weight sets], a fifth set): five different networks."""
     import torch
-    from test_gpu_policy_step_versus import make_weights
+    from policy_step_cases import make_weights
     sets = [make_weights(T, s) for s in range(5)]
     for a in range(5):
         for b in range(a):
@@ -80,8 +70,8 @@ def run_case(T, S, idx, case, nets):
     from guarded import Guarded, assert_guards_intact
     from oracle_model import SlotModel
     from tarok_amd import _native, karte as K
-    from test_gpu_output_contract import Outputs, check_against_models, modelled_slots
-    from test_gpu_policy_step_seats import bits, seat_sets
+    from output_contract_cases import Outputs, check_against_models, modelled_slots
+    from policy_step_cases import bits, seat_sets
     A, P, _ = nets
     c = dict(zip(FIELDS, case))
     n, auto, ref = N, bool(c["auto"]), bool(c["reward_ref"])
@@ -201,7 +191,7 @@ def twin_run(T, S, n, steps, launches, play_mode=None, seed=77):
     """One Twin env per launch function, `steps` lock-steps each; every output of every launch and the end state must be
     byte-equal to the first's."""
     import torch
-    from test_gpu_policy_step_seats import Twin
+    from policy_step_cases import Twin
     twins = [Twin(T, n, seed, S.MIX_ALL) for _ in launches]
     try:
         if play_mode is not None:
@@ -231,7 +221,7 @@ def twin_run(T, S, n, steps, launches, play_mode=None, seed=77):
 def launchers(T, flags):
     """Launch functions (env, outputs, words) of the three kinds, bound to their weights."""
     from tarok_amd import _native
-    from test_gpu_policy_step_versus import versus
+    from policy_step_cases import versus
 
     def outs(e, o):
         p = e._p

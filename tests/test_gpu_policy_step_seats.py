@@ -15,10 +15,12 @@ tarok_step_random covers those games the same way.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_policy_step_seats.py -m gpu -q
 """
-import os
 
 import numpy as np
 import pytest
+
+from gpu_harness import T  # noqa: F401  (the module fixture)
+from policy_step_cases import Twin, bits, seat_sets
 
 pytestmark = pytest.mark.gpu
 
@@ -39,17 +41,6 @@ CASES = [
     (20077, "all", 1, 0, 0, 0, "given", "given", "null", "given", "null", "given"),
     (20077, "all", 1, 1, 1, 15, "given", "null", "given", "null", "given", "null"),
 ]
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    from tarok_amd import _native
-    tarok_amd.build()
-    assert os.path.exists(_native.LIB_PATH), "libtarokenv.so missing: the HIP path is the product, no fallback"
-    return tarok_amd
 
 
 @pytest.fixture(scope="module")
@@ -74,25 +65,12 @@ def weights(T):
     return [bf(net.fc1.weight), fl(net.fc1.bias), bf(net.fc2.weight), fl(net.fc2.bias), bf(net.head.weight), fl(net.head.bias)]
 
 
-def seat_sets(spec, n):
-    """(the `seats` argument, the seats_per_game host array or None, the set of every game [n])."""
-    if spec == "cycle":
-        per = (np.arange(n) % 16).astype(np.uint8)
-        return 9, per, per               # (`seats` is ignored when the array is given: any valid value)
-    return int(spec), None, np.full(n, int(spec), np.uint8)
-
-
-def bits(x):
-    """f32 array -> its bit patterns."""
-    return np.ascontiguousarray(x).view(np.uint32)
-
-
 def run_case(T, S, idx, case, weights):
     import torch
     from guarded import Guarded, assert_guards_intact
     from oracle_model import SlotModel
     from tarok_amd import _native, karte as K
-    from test_gpu_output_contract import Outputs, check_against_models, modelled_slots
+    from output_contract_cases import Outputs, check_against_models, modelled_slots
     c = dict(zip(FIELDS, case))
     n, auto, ref = c["n"], bool(c["auto"]), bool(c["reward_ref"])
     seed, mix = 900 + idx, (S.MIX_ALL if c["mix"] == "all" else S.MIX_FIXED + 7)
@@ -192,26 +170,6 @@ def run_case(T, S, idx, case, weights):
 @pytest.mark.parametrize("idx", range(len(CASES)), ids=lambda i: "%02d-%s" % (i, "-".join(str(v) for v in CASES[i])))
 def test_every_row_of_a_mixed_launch_against_the_oracle(T, S, weights, idx):
     run_case(T, S, idx, CASES[idx], weights)
-
-
-class Twin:
-    """An env and one set of plain output tensors; `launch` is called with them."""
-
-    def __init__(self, T, n, seed, mix):
-        import torch
-        self.env = T.TarokVecEnv(n, seed=seed, mix=mix, history=True)
-        self.env.reset(episode=0)
-        z = lambda dt, *shape: torch.zeros(shape or (n,), dtype=dt, device="cuda")
-        self.o = dict(action=z(torch.uint8), logp=z(torch.float32), value=z(torch.float32), words=z(torch.int64, n, 4),
-                      reward=z(torch.int16, n, 4), done=z(torch.uint8), trick=z(torch.int16), obs=z(torch.int64))
-
-    def clear(self):
-        for k, v in self.o.items():
-            v.fill_(77)                               # (reward rows are written only where a game finished)
-
-    def end_state(self):
-        ep, ss = self.env.counters()
-        return self.env.state(), ep, ss, self.env.get_history().cpu().numpy(), self.env.legal_actions().words.cpu().numpy()
 
 
 @pytest.mark.parametrize("which", ["seats=15 is tarok_policy_step", "seats=0 is tarok_step_random"])

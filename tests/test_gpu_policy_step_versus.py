@@ -10,10 +10,12 @@ env half writes follows from that card through the per-slot model on the CPU ora
 Run on the GPU box:  python -m pytest tests/test_gpu_policy_step_versus.py -m gpu -q
 """
 import math
-import os
 
 import numpy as np
 import pytest
+
+from gpu_harness import T  # noqa: F401  (the module fixture)
+from policy_step_cases import make_weights, versus
 
 pytestmark = pytest.mark.gpu
 
@@ -32,35 +34,9 @@ CASES = [
 
 
 @pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    from tarok_amd import _native
-    tarok_amd.build()
-    assert os.path.exists(_native.LIB_PATH), "libtarokenv.so missing: the HIP path is the product, no fallback"
-    return tarok_amd
-
-
-@pytest.fixture(scope="module")
 def S():
     from oracle import tarok_spec
     return tarok_spec
-
-
-def make_weights(T, seed):
-    """selfplay.PolicyNet(256) of a torch seed, parameters x 3, in the kernels' fragment order."""
-    import torch
-    from tarok_amd import selfplay as SP
-    torch.manual_seed(seed)
-    net = SP.PolicyNet(256).cuda()
-    with torch.no_grad():
-        for p in net.parameters():
-            p.mul_(3.0)                  # spread the logits a little
-    order = T.TarokVecEnv.mfma_weight_order
-    bf = lambda w: order(w.detach().to(torch.bfloat16).contiguous())
-    fl = lambda b: b.detach().float().contiguous()
-    return [bf(net.fc1.weight), fl(net.fc1.bias), bf(net.fc2.weight), fl(net.fc2.bias), bf(net.head.weight), fl(net.head.bias)]
 
 
 @pytest.fixture(scope="module")
@@ -72,21 +48,13 @@ def nets(T):
     return A, B
 
 
-def versus(env, seats, per_game, A, B, obs, action, logp, value, words, reward, done, trick, obs_out, flags):
-    """One tarok_policy_step_versus launch through the C ABI (every argument a ctypes pointer or None)."""
-    from tarok_amd import _native
-    p = env._p
-    _native.check(env.L.tarok_policy_step_versus(env._h, seats, per_game, *[p(w) for w in A], *[p(w) for w in B], obs, action, logp, value,
-                                                 words, reward, done, trick, obs_out, flags, env._stream()))
-
-
 def run_case(T, S, idx, case, nets):
     import torch
     from guarded import Guarded, assert_guards_intact
     from oracle_model import SlotModel
     from tarok_amd import karte as K
-    from test_gpu_output_contract import Outputs, check_against_models, modelled_slots
-    from test_gpu_policy_step_seats import bits, seat_sets
+    from output_contract_cases import Outputs, check_against_models, modelled_slots
+    from policy_step_cases import bits, seat_sets
     A, B = nets
     c = dict(zip(FIELDS, case))
     n, auto, ref = c["n"], bool(c["auto"]), bool(c["reward_ref"])
@@ -205,7 +173,7 @@ def test_one_network_tables_reproduce_tarok_policy_step(T, S, nets, which):
     given as `seats` on one env and as a per-game array on a third ((A, A): the cycle i % 16 and the set 6)."""
     import torch
     from tarok_amd import _native, karte as K
-    from test_gpu_policy_step_seats import Twin
+    from policy_step_cases import Twin
     A, B = nets
     n, seed, flags = 20077, 77, K.AUTO_RESET | K.REWARD_REF
     a, b, c = (Twin(T, n, seed, S.MIX_ALL) for _ in range(3))

@@ -14,10 +14,11 @@ without a slot in play, which run the loop that is not trick-aligned beside it.
 
 Run on the GPU box:  python -m pytest tests/test_gpu_renewal_fetch.py -m gpu -q
 """
-import os
 
 import numpy as np
 import pytest
+
+from gpu_harness import T  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,17 +26,6 @@ BERAC_SEED = 41      # all-Berac: slots that finish in consecutive tricks of one
 SIZES = (256, 320)
 TAIL = 4             # cards played one by one after the compared run: they draw from the stored keys
 AHEAD = 14           # next-game lines per slot (TAROK_GAMES_AHEAD)
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    from tarok_amd import _native
-    tarok_amd.build()
-    assert os.path.exists(_native.LIB_PATH), "libtarokenv.so missing: the HIP path is the product, no fallback"
-    return tarok_amd
 
 
 @pytest.fixture(scope="module")

@@ -13,29 +13,18 @@ empty ones (the loops that are not trick-aligned, beside the changed one).
 
 Run on the GPU box:  python -m pytest tests/test_gpu_scalar_diet.py -m gpu -q
 """
-import os
 
 import numpy as np
 import pytest
 
 from guarded import Guarded, assert_guards_intact
+from gpu_harness import T  # noqa: F401  (the module fixture)
 
 pytestmark = pytest.mark.gpu
 
 SEED = 41
 LAUNCHES = 3
 PAD = 192            # row stride = games + PAD
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    from tarok_amd import _native
-    tarok_amd.build()
-    assert os.path.exists(_native.LIB_PATH), "libtarokenv.so missing: the HIP path is the product, no fallback"
-    return tarok_amd
 
 
 @pytest.fixture(scope="module")

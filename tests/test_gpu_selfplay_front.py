@@ -9,23 +9,16 @@ Run on the GPU box:  python -m pytest tests/test_gpu_selfplay_front.py -m gpu -q
 import numpy as np
 import pytest
 
+from gpu_harness import T  # noqa: F401  (the module fixture)
+
 pytestmark = pytest.mark.gpu
 
 N, T_STEPS, SEED = 512, 16, 5
 KEYS = ("obs", "words", "act", "logp", "val", "done", "reward")
 
 
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    tarok_amd.build()
-    return tarok_amd
-
-
 def heads():
-    from test_gpu_front_lines import random_weights
+    from front_lines_cases import random_weights
     return dict(bid=random_weights(11, 4.0), exchange=random_weights(12, 4.0), scale=70.0, contracts=0x3FF)
 
 
@@ -99,12 +92,12 @@ def test_statistics_are_a_recount_of_the_lines(T):
 # ---- front= composed with what it is trained with: an opponent pool with self-play groups, GAE, a teacher.  The rollout's
 # act / done / reward (and words) arrays are replayed on tests/oracle_model.SlotModel: the card is the network's and only has
 # to be accepted; every game — the first too — starts as the twin chain's game of its (slot, episode) under the seat sets
-# SelfPlay hands to front_lines (test_gpu_front_lines.twin_chain: neither front_lines nor a step kernel is in it).
+# SelfPlay hands to front_lines (front_lines_cases.twin_chain: neither front_lines nor a step kernel is in it).
 POOL = dict(self_play_groups=0.5, learner_seats=5)
 
 
 def pool():
-    from test_gpu_front_lines import random_weights
+    from front_lines_cases import random_weights
     return [random_weights(31), random_weights(32)]
 
 
@@ -137,7 +130,7 @@ def replay(T, sp, bufs):
     from oracle import oracle as O
     from oracle import tarok_spec as S
     from oracle_model import SlotModel
-    from test_gpu_front_lines import twin_chain
+    from front_lines_cases import twin_chain
     f = sp.front
     kw = dict(bid=sp._front_w["bid"], exchange=sp._front_w["exchange"], scale=f["scale"], contracts=f["contracts"], margin=f["margin"],
               playouts=f["playouts"], pass_value=f["pass_value"], seats_per_game=sp._seats)

@@ -6,18 +6,11 @@ Run on the GPU box:  python -m pytest tests/test_gpu_selfplay_pool.py -m gpu -q
 import numpy as np
 import pytest
 
+from gpu_harness import T  # noqa: F401  (the module fixture)
+
 pytestmark = pytest.mark.gpu
 
 N, TN, ITERS = 1024, 16, 2
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    tarok_amd.build()
-    return tarok_amd
 
 
 @pytest.fixture(scope="module")
@@ -29,7 +22,7 @@ def S():
 @pytest.fixture(scope="module")
 def snaps(T):
     """Two different frozen networks (make_weights of the versus test: PolicyNet(256), parameters x 3)."""
-    from test_gpu_policy_step_versus import make_weights
+    from policy_step_cases import make_weights
     return make_weights(T, 11), make_weights(T, 12)
 
 

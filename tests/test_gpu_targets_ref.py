@@ -10,22 +10,15 @@ import os
 import numpy as np
 import pytest
 
+from gpu_harness import T  # noqa: F401  (the module fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def T():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import tarok_amd
-    tarok_amd.build()
-    return tarok_amd
 
 
 def test_targets_ref_on_reference_games(T, golden_dir):
     import torch
     from oracle import encoder_spec as E
-    from test_gpu_observe_ref import reset_from_traces, sample_games
+    from observe_cases import reset_from_traces, sample_games
     tr = dict(np.load(os.path.join(golden_dir, "traces_v1.npz")))
     idx = sample_games(tr)
     n = len(idx)

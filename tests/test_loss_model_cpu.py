@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import loss_model as L
-from test_gpu_policy_exact import reference, synthetic_features, weights_p, weights_r
+from policy_exact_ref import reference, synthetic_features, weights_p, weights_r
 
 SEEDS = ((333, 17), (257, 18))            # (n, seed) of the case sets of tests/test_gpu_loss_exact.py
 F = np.float32

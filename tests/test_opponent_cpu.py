@@ -17,26 +17,10 @@ from gae_model import gae_model
 from select_model import known_of, known_patterns, rec_of, scratch_bytes, select_model
 from tarok_amd import karte as K
 from tarok_amd import selfplay as SP
-from test_gpu_learner_gae import arrays                        # the slot patterns of the GAE tests (numpy, no GPU)
+from gae_cases import arrays                                   # the slot patterns of the GAE tests (numpy, no GPU)
+from opponent_cases import SETS, monte_carlo_known, moves, seat_sets
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SETS = ["0", "1", "6", "15", "cycle"]
-
-
-def seat_sets(n, which):
-    """[n] uint8: the learner's seat set of every slot."""
-    if which == "cycle":
-        return (1 << (np.arange(n) % 4)).astype(np.uint8)
-    return np.full(n, int(which), np.uint8)
-
-
-def moves(seat, sets):
-    return ((sets[None, :].astype(np.int64) >> seat) & 1).astype(bool)
-
-
-def monte_carlo_known(done):
-    """known of the Monte-Carlo returns: a game ends at or after t inside the rollout."""
-    return np.flip(np.maximum.accumulate(np.flip(done.astype(bool), 0), 0), 0)
 
 
 def tt(a, *names):

@@ -13,7 +13,7 @@ import os
 import numpy as np
 import pytest
 
-import test_gpu_output_contract as G
+import output_contract_cases as G
 from guarded import SENTINEL_BYTE, Guarded, assert_guards_intact
 from oracle import encoder_spec as E
 from oracle import oracle as O
@@ -152,7 +152,7 @@ def test_model_hook_with_fronted_games_differs_from_the_bots():
     """A hook that hands out front_lines_model.front_game on the integer weight sets of tests/test_front_lines_cpu.py:
     each game starts as that game, and the run differs from the Bot's."""
     import front_lines_model as FM
-    import test_front_lines_cpu as FC
+    import front_lines_cpu_cases as FC
     bid = dict(W=FC.model_weights(1), scale=70.0, playouts=1, margin=0, contracts=0x3FF, pass_value=False)
     Wx = FC.model_weights(2)
     differ = 0
@@ -213,6 +213,44 @@ def test_guard_checker_reports_one_flipped_byte():
             a._host = None
             assert a.violations() == []
         assert torch.equal(a.raw[:gb], torch.full((gb,), SENTINEL_BYTE, dtype=torch.uint8))
+
+
+def test_card_output_readers_fail_on_an_unwritten_element_and_a_differing_row():
+    """tests/gpu_harness.py's readers on CPU buffers of n = 3 games: fully written outputs read back; one unwritten word of
+    sum_out or one unwritten byte of action_out fails; assert_cards_equal passes on equal arrays and fails on one differing
+    sum row and on one differing card."""
+    import gpu_harness as H
+    n = 3
+
+    def written(skip_word=None, skip_byte=None):
+        g_sum, g_act = H.card_outputs(n, ("sum", "action"), device="cpu")
+        words = g_sum.payload().view(n * 12 * 4, 4)
+        for w in range(n * 12 * 4):
+            if w != skip_word:
+                words[w] = 0
+        g_sum.payload()[0] = 7                                 # (game 0, card 0, seat 0: 7 points)
+        for g in range(n):
+            if g != skip_byte:
+                g_act.payload()[g] = 20 + g
+        g_sum._host = g_act._host = None
+        return g_sum, g_act
+    sums, acts = H.read_cards(*written())
+    assert sums.shape == (n, 12, 4) and sums.dtype == np.int32 and sums[0, 0, 0] == 7 and sums.sum() == 7
+    assert acts.dtype == np.uint8 and acts.tolist() == [20, 21, 22]
+    assert H.read_cards(written()[0], None)[1] is None and H.read_cards(None, written()[1])[0] is None
+    with pytest.raises(AssertionError, match="a word of sum_out was not written"):
+        H.read_cards(*written(skip_word=(1 * 12 + 5) * 4 + 2))
+    with pytest.raises(AssertionError, match="a byte of action_out was not written"):
+        H.read_cards(*written(skip_byte=2))
+    H.assert_cards_equal(sums, sums.copy(), acts, acts.copy(), "equal")
+    other = sums.copy()
+    other[2, 11, 3] += 1
+    with pytest.raises(AssertionError, match="sums differ"):
+        H.assert_cards_equal(other, sums, acts, acts, "one sum row")
+    card = acts.copy()
+    card[1] = 255
+    with pytest.raises(AssertionError, match="cards differ"):
+        H.assert_cards_equal(sums, sums, card, acts, "one card")
 
 
 def test_case_table_covers_every_allowed_pair():

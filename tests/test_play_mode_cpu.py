@@ -9,7 +9,7 @@ import pytest
 
 import play_mode_model as PM
 from oracle import tarok_spec as S
-from test_gpu_policy_exact import sampler_reference
+from policy_exact_ref import sampler_reference
 
 SEED = 17
 

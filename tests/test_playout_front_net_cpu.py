@@ -9,7 +9,7 @@ import playout_bids_model as BM
 import playout_exchange_model as XM
 import playout_front_net_model as FM
 from oracle import tarok_spec as S
-from test_playout_net_cpu import zero_net
+from playout_net_cases import zero_net
 
 SEED, EPISODE = 41, 3
 

@@ -9,17 +9,9 @@ import playout_model as PM
 import playout_net_model as NM
 from oracle import oracle as O
 from oracle import tarok_spec as S
+from playout_net_cases import zero_net
 
 SEED, EPISODE = 41, 3
-
-
-def zero_net(b3):
-    """A network whose 54 card logits are b3 on every position."""
-    import torch
-    z = lambda *s: torch.zeros(*s, dtype=torch.float64)
-    bias = z(64)
-    bias[:54] = torch.as_tensor(np.asarray(b3, np.float64))
-    return [z(256, 256), z(256), z(256, 256), z(256), z(64, 256), bias]
 
 
 def games(mix, n, cards, first=0):

@@ -2,8 +2,8 @@
 tests/playout_net_value_model.py against the models it extends (depth 12), its stop rule at depth 1, the mutants it must
 tell apart on the GPU tests' own positions, the guards against a vacuous GPU comparison on the model alone, every new
 ValueError, the launches the Python surface issues on stand-in envs, and the C entry point's argument checks, which come
-before any HIP call.  The plan of the GPU comparison (positions, weight sets, seat sets, depths) is defined here and
-imported by tests/test_gpu_playout_net_value.py.  No GPU in here."""
+before any HIP call.  The plan of the GPU comparison (positions, weight sets, seat sets, depths) is
+tests/playout_net_value_cases.py's, shared with tests/test_gpu_playout_net_value.py.  No GPU in here."""
 import ctypes
 import inspect
 
@@ -14,73 +14,8 @@ import playout_net_model as NM
 import playout_net_value_model as VM
 import playout_net_worlds_model as WM
 from oracle import tarok_spec as S
-from test_playout_net_cpu import zero_net
-from test_playout_net_worlds_cpu import Calls, NoHistory, WithHistory, no_device, weights
-
-SEED, EPISODE, OFFSET = 41, 3, 1000               # tests/test_gpu_playout_det.py's: the GPU tests' envs
-KLOP, DVE = 0, 2
-SALT = 3
-SCALES = (1.0, 0.5, 1e9)                          # 0.5: odd integer values land on ties; 1e9: every V is +-32767 or 0
-SHAPES = ((5, 3), (1, 1))                         # 180 item slots: a full tile of 128 and a partial one; one partial tile
-# the positions of the comparison with the GPU: (mix, cards).  voids and hidden: the constraining positions that
-# tests/test_gpu_playout_net_worlds.py builds come first
-POSITIONS = dict(det=[(S.MIX_ALL, c) for c in (0, 9, 24, 40, 44)],
-                 voids=[(S.MIX_ALL, c) for c in (5, 24, 44, 0, 9, 40)],
-                 hidden=[(S.MIX_FIXED + KLOP, 5), (S.MIX_FIXED + DVE, 24), (S.MIX_ALL, 44), (S.MIX_ALL, 0), (S.MIX_ALL, 9), (S.MIX_ALL, 40)])
-CASES = [(kind, at) for kind in VM.KINDS for at in range(len(POSITIONS[kind]))]
-
-
-def weight_sets():
-    """The exactly summable sets of tests/test_gpu_policy_exact.py, R and one P, and V: set R with row 54 of W3 and b3[54]
-    redrawn wider (W3[54] in {-8..8} 2^-10, b3[54] = 3.5), so that the value varies over the stop positions in sign and
-    size whatever R's own row gives."""
-    import torch
-    import test_gpu_policy_exact as PE
-    WR, WP = PE.weights_r(), PE.weights_p(*PE.P_PARAMS[2])
-    WV = [t.clone() for t in WR]
-    g = torch.Generator(); g.manual_seed(54)
-    WV[4][54] = torch.randint(-8, 9, (256,), generator=g).double() * 2.0 ** -10
-    WV[5][54] = 3.5
-    return dict(R=WR, P=WP, V=WV)
-
-
-def plan(kind, at):
-    """The launches of case (kind, at): [(n, worlds, depth, weight set name, net_seats or "no viewer")].  Over the cases
-    every depth meets every set and every seat choice."""
-    k = VM.KINDS.index(kind) + at
-    sets, seats = ("R", "P", "V"), (15, 0, "no viewer")
-    rows = [(5, 3, d, sets[(k + d) % 3], seats[(k + d // 2) % 3]) for d in (1, 2, 3)]
-    return rows + [(1, 1, 1 + k % 3, sets[k % 3], seats[(k + 1) % 3])]
-
-
-def games_at(kind, at, n):
-    mix, cards = POSITIONS[kind][at]
-    games, words, objs = WM.bot_games("voids" if kind == "det" else kind, SEED, EPISODE, mix, n, cards, first=OFFSET)
-    return games, (None if kind == "det" else words), objs
-
-
-def net_seats_of(choice, objs):
-    """"no viewer": every seat but game 0's mover — a set without (that game's) viewer."""
-    return 15 ^ (1 << objs[0].seat()) if choice == "no viewer" else choice
-
-
-def at_scale(n, worlds, info, value_scale, rule="spec"):
-    """The sums [n, 12, 4] of a model run re-formed at another value_scale: the playouts do not depend on it."""
-    sums = np.zeros((n, 12, 4), np.int64)
-    for (g, j, w), d in info:
-        if d["stopped"]:
-            V = VM.points(d["v"], value_scale, half_even=rule != "away")
-            sums[g, j, d["viewer"]] += V
-        else:
-            sums[g, j] += d["scores"]
-    return sums
-
-
-def model(kind, at, n, worlds, depth, W, choice, value_scale=1.0, rule="spec"):
-    games, words, objs = games_at(kind, at, n)
-    net_seats = net_seats_of(choice, objs)
-    sums, acts, info = VM.playout_cards(kind, games, SEED, SALT, 15, worlds, W, net_seats, depth, value_scale, words, rule=rule)
-    return games, words, net_seats, sums, acts, info
+from playout_net_cases import Calls, NoHistory, WithHistory, no_device, weights, zero_net
+from playout_net_value_cases import CASES, EPISODE, OFFSET, SALT, SCALES, SEED, model, plan, weight_sets
 
 
 def logits(k):
@@ -254,10 +189,10 @@ def test_the_env_method_issues_the_value_launch():
 
 
 def test_evaluate_issues_the_value_launch():
-    """evaluate_playout_vs_bot(net=, net_depth=) on the stand-in env of tests/test_evaluate_calls_cpu.py: None makes the
+    """evaluate_playout_vs_bot(net=, net_depth=) on the stand-in env of tests/evaluate_calls_cases.py: None makes the
     calls of the call without it; a depth makes the same calls with playout_cards_net_value(W, worlds, depth, scale, ...) in
     playout_cards_net's place, in the worlds of net_worlds."""
-    import test_evaluate_calls_cpu as EC
+    import evaluate_calls_cases as EC
     from tarok_amd import evaluate as EV
     new = dict(nd_none=("evaluate_playout_vs_bot", (None,), dict(worlds=2, net="W", net_seats=5), False),
                nd_off=("evaluate_playout_vs_bot", (None,), dict(worlds=2, net="W", net_seats=5, net_depth=None, net_value_scale=3.0), False),

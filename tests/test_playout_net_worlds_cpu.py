@@ -3,7 +3,6 @@
 the models it is made of where they must agree, the positions the GPU tests use (they do constrain the worlds), the
 ValueErrors old and new, the launches the three Python entry points issue on stand-in envs, and the C entry points'
 argument checks, which come before any HIP call.  No GPU in here."""
-import contextlib
 import ctypes
 import inspect
 
@@ -15,7 +14,7 @@ import playout_net_model as NM
 import playout_net_worlds_model as WM
 import playout_voids_model as VM
 from oracle import tarok_spec as S
-from test_playout_net_cpu import zero_net
+from playout_net_cases import Calls, NoHistory, WithHistory, no_device, weights, zero_net
 
 SEED, EPISODE, OFFSET = 41, 3, 1000               # tests/test_gpu_playout_det.py's: the GPU tests' envs
 KLOP, DVE = 0, 2
@@ -78,20 +77,6 @@ def test_the_gpu_tests_positions_constrain_the_worlds(kind):
     assert differ >= 3 and nets_differ >= 3
 
 
-def weights():
-    import torch
-    return [torch.zeros(256, 256, dtype=torch.bfloat16), torch.zeros(256), torch.zeros(256, 256, dtype=torch.bfloat16), torch.zeros(256),
-            torch.zeros(64, 256, dtype=torch.bfloat16), torch.zeros(64)]
-
-
-class NoHistory:
-    history = False
-
-
-class WithHistory:
-    history = True
-
-
 def test_new_and_old_refusals():
     """Every new ValueError, before any env is made or touched; and the old spellings keep raising (the pinned tests of
     tests/test_playout_net_cpu.py and tests/test_evaluate_calls_cpu.py are the authority on those)."""
@@ -131,39 +116,6 @@ def test_new_and_old_refusals():
     for env, kw in ((WithHistory, dict(voids=True, hidden=True)), (NoHistory, dict(voids=True)), (NoHistory, dict(hidden=True))):
         with pytest.raises(ValueError):
             TarokVecEnv.playout_cards_net(type("Env", (env,), dict(_cards=TarokVecEnv._cards))(), net, 2, **kw)
-
-
-class Calls:
-    """Records name(args) of everything called through it; tensors are shown by dtype and shape."""
-
-    def __init__(self):
-        self.calls = []
-
-    def show(self, x):
-        import torch
-        if torch.is_tensor(x):
-            return "%s%s" % (str(x.dtype).replace("torch.", ""), list(x.shape))
-        return repr(x)
-
-    def __getattr__(self, name):
-        if name.startswith("_"):
-            raise AttributeError(name)
-
-        def f(*args, **kwargs):
-            self.calls.append("%s(%s)" % (name, ", ".join([self.show(a) for a in args] + ["%s=%s" % (k, self.show(v)) for k, v in sorted(kwargs.items())])))
-            return 0
-        return f
-
-
-@contextlib.contextmanager
-def no_device():
-    import torch
-    saved = torch.cuda.device
-    torch.cuda.device = lambda d: contextlib.nullcontext()
-    try:
-        yield
-    finally:
-        torch.cuda.device = saved
 
 
 def test_the_env_method_issues_the_launch_of_the_kind():
@@ -212,11 +164,11 @@ def test_the_env_method_issues_the_launch_of_the_kind():
 
 
 def test_evaluate_issues_the_launch_of_the_kind():
-    """evaluate_playout_vs_bot(net=, net_worlds=) on the stand-in env of tests/test_evaluate_calls_cpu.py: "det" makes the
+    """evaluate_playout_vs_bot(net=, net_worlds=) on the stand-in env of tests/evaluate_calls_cases.py: "det" makes the
     calls of the call without it; "voids" / "hidden" make an env that keeps its history and hand every lock-step's
     playout_cards_net the kind and one words tensor of the kind's dtype, everything else the same."""
     import re
-    import test_evaluate_calls_cpu as EC
+    import evaluate_calls_cases as EC
     from tarok_amd import evaluate as EV
     EC.CASES.update(nw_none=("evaluate_playout_vs_bot", (None,), dict(worlds=2, net="W", net_seats=5), False),
                     nw_det=("evaluate_playout_vs_bot", (None,), dict(worlds=2, net="W", net_seats=5, net_worlds="det"), False),
