@@ -1008,6 +1008,43 @@ int tarok_playout_bids_net(tarok_env *env, uint32_t episode, const uint8_t *deal
                            const void *w2, const float *b2, const void *w3, const float *b3, void *scratch,
                            int64_t scratch_bytes, int32_t *sum_out, void *stream);
 
+/* Value-stopped net playouts for the exchange, the bid and the pass: the two launches above with every playout stopped
+ * at the VIEWER's depth-th decision, as tarok_playout_cards_net_value stops a card's playouts.  The worlds, candidates,
+ * rows, keys (k = 0), item numbering, the Bot's exchange inside a bid item, net_seats, "takes part", the outputs' shapes
+ * and rules, the scratch and its size (tarok_playout_exchange_net_scratch / tarok_playout_bids_net_scratch), the read-only
+ * env, three / four launches on `stream`, nothing allocated are the existing launches', word for word.  The stop, the
+ * forward at the stop, the float32 steps to V = rint(clamp(v54 * value_scale)) and the stopped item's result (V in the
+ * viewer's column, 0 in the other three; an item whose game ends first keeps its four true scores) are
+ * tarok_playout_cards_net_value's.  What is new:
+ *   - the VIEWER of an exchange item is the declarer; of a bid item, the seat v whose row it is — in the Klop row too,
+ *     where seat 0 declares, and in a pass item, where another seat declares.  choice_out / discards_out read the
+ *     declarer's column of the sums and sum_out of the bids holds the viewer's: both are the column V lands in;
+ *   - DEPTH RANGE 1..TAROK_PLAYOUT_FRONT_MAX_DEPTH = 13, not 12: an item starts at 0 cards played, so its viewer has all
+ *     12 decisions ahead (after a candidate card it has 11).  Depth 13 never stops an item and writes the bytes of the
+ *     existing launch for any weights and value_scale; depth 12 stops every item at the viewer's forced last card.  This
+ *     is the one place where the launches differ from tarok_playout_cards_net_value;
+ *   - pass_value = 1 (bids): slot (g, v, 19, w) is a live item for every viewer of the seat set — tarok_playout_bids_pass'
+ *     item under that launch's pkey with r = 19 and k = 0: three Bots bid with v muted, their contract, declarer and king
+ *     are set up on v's world, the Bot exchanges where the game has an exchange, and the item is played and stopped as a
+ *     row's item is.  sum_out[g][v][19] is then v's value of a pass; with depth 13 and net_seats = 0 the twenty rows are
+ *     tarok_playout_bids_pass(worlds, 1)'s bytes.  pass_value = 0: row 19 stays 0.
+ * At depth 1 with the viewer on lead the stop is at 0 cards played: no card is played, and V depends on the world only
+ * through what the viewer knows, so a candidate's (an option's) number is the same in every world.  That is correct and
+ * cheap; extra worlds add nothing there.
+ * TAROK_EINVAL (before any HIP call) for everything the existing launch refuses, depth outside
+ * 1..TAROK_PLAYOUT_FRONT_MAX_DEPTH, value_scale not finite or not > 0, pass_value outside 0..1. */
+#define TAROK_PLAYOUT_FRONT_MAX_DEPTH 13
+int tarok_playout_exchange_net_value(tarok_env *env, int worlds, int discard_sets, uint64_t salt, int seats,
+                                     const uint8_t *seats_per_game, int net_seats, int depth, float value_scale,
+                                     const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
+                                     const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out,
+                                     int8_t *choice_out, uint8_t *discards_out, void *stream);
+int tarok_playout_bids_net_value(tarok_env *env, uint32_t episode, const uint8_t *deals, int worlds, int contracts,
+                                 uint64_t salt, int seats, const uint8_t *seats_per_game, int net_seats, int depth,
+                                 float value_scale, int pass_value, const void *w1, const float *b1, const void *w2,
+                                 const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
+                                 int32_t *sum_out, void *stream);
+
 /* The learner's network input for a minibatch: features_out[j] [256] bf16 (0.0 / 1.0) = the bits
  * of feature_words[index[j]] (feature_words [M,4] u64 as written by feature_words_out; index
  * [n_samples] i64 sample numbers, or NULL for samples 0..n_samples-1).  Gather + expansion in one

@@ -37,6 +37,7 @@ SYMBOLS = [
     "tarok_playout_net_scratch", "tarok_playout_cards_net", "tarok_playout_cards_net_voids", "tarok_playout_cards_net_hidden",
     "tarok_playout_cards_net_value",
     "tarok_playout_exchange_net_scratch", "tarok_playout_exchange_net", "tarok_playout_bids_net_scratch", "tarok_playout_bids_net",
+    "tarok_playout_exchange_net_value", "tarok_playout_bids_net_value",
     "tarok_front_lines_scratch_bytes", "tarok_front_lines", "tarok_get_lines",
 ]
 
@@ -189,6 +190,10 @@ def lib():
     L.tarok_playout_bids_net_scratch.restype = i64; L.tarok_playout_bids_net_scratch.argtypes = [vp, i32]
     L.tarok_playout_bids_net.restype = i32
     L.tarok_playout_bids_net.argtypes = [vp, u32, vp, i32, i32, u64, i32, vp, i32] + [vp] * 6 + [vp, i64, vp, vp]
+    L.tarok_playout_exchange_net_value.restype = i32  # (depth, value_scale[, pass_value]) after net_seats
+    L.tarok_playout_exchange_net_value.argtypes = [vp, i32, i32, u64, i32, vp, i32, i32, f32] + [vp] * 6 + [vp, i64, vp, vp, vp, vp]
+    L.tarok_playout_bids_net_value.restype = i32
+    L.tarok_playout_bids_net_value.argtypes = [vp, u32, vp, i32, i32, u64, i32, vp, i32, i32, f32, i32] + [vp] * 6 + [vp, i64, vp, vp]
     L.tarok_playout_exchange.restype = i32; L.tarok_playout_exchange.argtypes = [vp, i32, i32, i32, u64, i32, vp, vp, vp, vp, vp]
     L.tarok_shown_voids.restype = i32; L.tarok_shown_voids.argtypes = [vp, vp, vp]
     L.tarok_playout_cards_voids.restype = i32; L.tarok_playout_cards_voids.argtypes = [vp, i32, i32, u64, i32, vp, vp, vp, vp, vp]

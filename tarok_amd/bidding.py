@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 from . import karte as K
+from . import playout as P
 from .env import TarokVecEnv
 from .selfplay import PolicyNet
 
@@ -60,13 +61,21 @@ class BidLearner:
     seat's own pass (bid_values / bid_round with pass_value=True; `threshold` is then the margin over the pass).  net: six
     tensors (policy_mlp's weights, read live at every collect()) — the teacher is then playout_bids_net at `worlds` with the
     network's greedy card on the seats of net_seats inside the playouts, playouts = worlds; `samples` must be 1 or left
-    unset, and pass_value=True does not go with it (the pass is not valued under the network)."""
+    unset.  net_depth: None, or 1..13 — the teacher is playout_bids_net_value, whose playouts stop at the viewer's
+    net_depth-th decision and read the value head of `net` there at net_value_scale points per unit (13 never stops).
+    pass_value=True goes with net= only together with net_depth: the value launch plays the pass item too, and output 19
+    regresses on its row 19; the plain net launch does not value the pass."""
 
     def __init__(self, env, worlds=8, samples=None, contracts=K.BID_DEFAULT_CONTRACTS, lr=1e-3, reward_scale=1.0 / 70.0,
-                 playouts_equiv=16, seed=0, pass_value=False, net=None, net_seats=15):
+                 playouts_equiv=16, seed=0, pass_value=False, net=None, net_seats=15, net_depth=None, net_value_scale=70.0):
+        if net_depth is not None:
+            if net is None:
+                raise ValueError("net_depth stops the network's playouts: it needs net=")
+            P.check_depth(net_depth, net_value_scale, P.spelling(), max_depth=K.PLAYOUT_FRONT_MAX_DEPTH)
         if net is not None:
-            if pass_value:
-                raise ValueError("net= does not value the pass: pass_value=True goes with the Bot's playouts only")
+            if pass_value and net_depth is None:
+                raise ValueError("net= without net_depth does not value the pass: pass_value=True goes with the Bot's playouts "
+                                 "or with net_depth")
             if samples not in (None, 1):
                 raise ValueError("net= runs one playout per (option, world): samples must be 1 or unset")
             if not (isinstance(net_seats, int) and 0 <= net_seats <= 15):
@@ -74,6 +83,7 @@ class BidLearner:
             net = TarokVecEnv.check_mlp_weights(net)
         samples = (1 if net is not None else 2) if samples is None else samples
         self.net_weights, self.net_seats = net, int(net_seats)
+        self.net_depth, self.net_value_scale = net_depth, float(net_value_scale)
         if not 1 <= int(contracts) <= K.BID_ALL_CONTRACTS:
             raise ValueError("contracts: a bit set within 1..0x3FF")
         if not (reward_scale > 0 and int(playouts_equiv) >= 1):
@@ -123,8 +133,9 @@ class BidLearner:
         """(feature_words [N,4,4] int64, sums [N,4,K.BID_ROWS] int32, playouts) of episode `episode`: the teacher's launch
         on every seat and the head's launch for its input rows."""
         if self.net_weights is not None:
-            sums = self.env.playout_bids_net(self.net_weights, episode, self.worlds, net_seats=self.net_seats, contracts=self.contracts,
-                                             salt=self.salt)
+            sums = self.env.playout_bids_net_value(self.net_weights, episode, self.worlds, self.net_depth, self.net_value_scale,
+                                                   pass_value=self.pass_value, net_seats=self.net_seats, contracts=self.contracts,
+                                                   salt=self.salt)
         else:
             sums = self.env.playout_bids(episode, self.worlds, self.samples, contracts=self.contracts, salt=self.salt,
                                          pass_value=self.pass_value)

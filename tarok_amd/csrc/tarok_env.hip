@@ -3759,6 +3759,68 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_exchange_net_deal(int64_t n, int64_t ite
     }
 }
 
+// tarok_playout_exchange_net_value's first launch: the kernel above with the VIEWER — the declarer, the seat the
+// candidates are valued for — in a live item's marker, as playout_net_deal_body<Dealer, true> writes the mover.  Text of its
+// own: as one templated body the kernel above compiled to other instructions than its parent's (seven operand orders).
+TK_KERNEL(TK_BLOCK, 128) void k_playout_exchange_net_deal_value(int64_t n, int64_t items, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds,
+                                                               u32 sets, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                               const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
+                                                               const Counters *__restrict__ cnt, ulonglong2 *__restrict__ i01,
+                                                               ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
+    TK_VGPR_TOP(128, 127);
+    __shared__ WorldAB world;
+    __shared__ u32 cand_dpk[(TK_BLOCK >> TK_PX_MIN_LG) * TK_PX_ROWS];
+    const PlayoutTeam t(lg, worlds);
+    const u32 L = t.L, lane = t.lane;
+    const int64_t g = t.g;
+    u32 *cand = cand_dpk + t.team * TK_PX_ROWS;
+    ulonglong2 a = {0, 0}, b = {0, 0};
+    u64 ebase = 0;
+    ExchangePosition p;
+    if (g < n) {
+        a = s01[g]; b = s23[g];
+        Game g0;
+        unpack(g0, a.x, a.y, b.x, b.y);
+        p = exchange_position(g0, seat_sets, seats, sets, g);
+        if (p.takes_part) {
+            ebase = (u64)cnt[g].episode << 28;
+            for (u32 w = lane; w < worlds; w += L) {
+                Game d = g0;
+                redeal_unseen(d, p.declarer, game_key(pseed, offset + (u64)g, (7ULL << 61) | ebase | (63ULL << 22) | (u64)w));
+                world.store(t.slot0 + w, d);
+            }
+            for (u32 r = lane; r < p.ncand; r += L) {
+                u32 i = r / sets, d = r - i * sets;
+                cand[r] = exchange_discards(g0, i, game_key(pseed, offset + (u64)g, (5ULL << 61) | ebase | ((u64)i << 6) | (u64)d));
+            }
+        }
+    }
+    __syncthreads();
+    if (g >= n) return;
+    const u32 slots = 6u * sets * worlds;
+    for (u32 s = lane; s < slots; s += L) {
+        const int64_t it = g * (int64_t)slots + s;
+        if (it >= items) break;
+        const u32 r = s / worlds, w = s - r * worlds;
+        u64 res = 0;
+        if (r < p.ncand) {                               // (ncand = 0 for a game that does not take part)
+            const u32 i = r / sets, d = r - i * sets;
+            Game h;
+            unpack(h, a.x, a.y, b.x, b.y);
+            world.load(t.slot0 + w, h);
+            const u32 dpk = cand[r];
+            apply_exchange(h, i, dpk & 255, (dpk >> 8) & 255, (dpk >> 16) & 255);
+            u64 x0, x1, y0, y1;
+            pack(h, x0, x1, y0, y1);
+            i01[it] = make_ulonglong2(x0, x1);
+            i23[it] = make_ulonglong2(y0, y1);
+            ikey[it] = game_key(pseed, offset + (u64)g, (3ULL << 62) | ebase | (63ULL << 22) | ((u64)(8u * i + d) << 16) | ((u64)w << 10));
+            res = TK_PN_LIVE | (u64)p.declarer;
+        }
+        ires[it] = res;
+    }
+}
+
 // Exchange, third launch: 16 lanes per game; lane r, r + 16, r + 32 sum their rows' items over the worlds in integers,
 // then the tail of k_playout_exchange: 6 * sets 16-byte rows, and on lane 0 the choice — the first candidate at the
 // maximum of the declarer's sums with its discards drawn again under the candidate key, the Bot's own exchange for a
@@ -3870,6 +3932,91 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_bids_net_deal(int64_t n, int64_t items, 
         }
     }
 }
+
+// tarok_playout_bids_net_value's second launch, text of its own — as one templated body the kernel above
+// compiled to other instructions than its parent's: the kernel above with the VIEWER in a live item's marker — v, the seat
+// whose row it is, in its two low bits — in the Klop row too, where seat 0 declares.  PASS: slot (g, v, 19, w) is a live
+// item as well, k_playout_bids_pass's item under that launch's key with r = 19 and k = 0: pass_round's contract, declarer
+// and king set up on the world by bid_game_as, then the Bot's exchange where the game has one; its viewer is v, whoever
+// declares.  The viewer loop's two barriers per viewer stand outside every test of the seat set, as in the kernel above.
+template <bool PASS>
+__device__ __forceinline__ void playout_bids_net_deal_value_body(int64_t n, int64_t items, u64 pseed, u64 offset, u32 episode, u32 worlds, u32 lg,
+                                                           u32 contracts, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                           const u64 *__restrict__ deal, ulonglong2 *__restrict__ i01,
+                                                           ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
+    __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS], world_ids[TK_PO_WORLD_SLOTS];
+    const PlayoutTeam t(lg, worlds);
+    const u32 L = t.L, lane = t.lane, slot0 = t.slot0;
+    const int64_t g = t.g;
+    u64 h0 = 0, h1 = 0, h2 = 0, h3 = 0, tal = 0;
+    u32 set = 0;
+    if (g < n) {
+        h0 = deal[g]; h1 = deal[n + g]; h2 = deal[2 * n + g]; h3 = deal[3 * n + g]; tal = deal[4 * n + g];
+        set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+        if ((h0 | h1 | h2 | h3) == 0) set = 0;           // an invalid deal row
+    }
+    const u32 rowmask = bid_row_mask(contracts), slots = (u32)TAROK_BID_ROWS * worlds;
+    const u64 ebase = (u64)episode << 28;
+#pragma unroll 1
+    for (u32 v = 0; v < 4; v++) {
+        const bool part = (set >> v) & 1u;
+        __syncthreads();                                 // the last viewer's items have read their worlds
+        if (part) {
+            for (u32 w = lane; w < worlds; w += L) {
+                u64 A, B, ids;
+                bid_world(h0, h1, h2, h3, tal, v, game_key(pseed, offset + (u64)g, (2ULL << 61) | ebase | ((u64)v << 6) | (u64)w), A, B, ids);
+                world_a[slot0 + w] = A; world_b[slot0 + w] = B; world_ids[slot0 + w] = ids;
+            }
+        }
+        __syncthreads();
+        if (g < n) {
+            for (u32 s = lane; s < slots; s += L) {
+                const int64_t it = (g * 4 + (int64_t)v) * (int64_t)slots + s;
+                if (it >= items) break;
+                const u32 r = s / worlds, w = s - r * worlds;
+                u64 res = 0;
+                if (part && (((rowmask >> r) & 1u) || (PASS && r == (u32)TK_BID_PASS_ROW))) {
+                    const u64 pkey = game_key(pseed, offset + (u64)g, (3ULL << 61) | ebase | ((u64)v << 26) | ((u64)r << 21) | ((u64)w << 15));
+                    Game h;
+                    if constexpr (PASS) {                // (k_playout_bids_pass's one setup for both kinds of item)
+                        u32 ct = bid_row_contract(r), d = ct == TK_KLOP ? 0u : v, kg = bid_row_king(r);
+                        if (r == (u32)TK_BID_PASS_ROW) pass_round(pkey, v, ct, d, kg);
+                        bid_game_as(h, world_a[slot0 + w], world_b[slot0 + w], world_ids[slot0 + w], ct, d, kg);
+                    } else {
+                        bid_game(h, world_a[slot0 + w], world_b[slot0 + w], world_ids[slot0 + w], r, v);
+                    }
+                    if (h.phase == TK_PHASE_EXCHANGE) bot_exchange(h, pkey);
+                    u64 x0, x1, y0, y1;
+                    pack(h, x0, x1, y0, y1);
+                    i01[it] = make_ulonglong2(x0, x1);
+                    i23[it] = make_ulonglong2(y0, y1);
+                    ikey[it] = pkey;
+                    res = TK_PN_LIVE | (u64)v;
+                }
+                ires[it] = res;
+            }
+        }
+    }
+}
+
+#define TK_BIDS_NET_DEAL_ARGS                                                                                                          \
+    int64_t n, int64_t items, u64 pseed /* seed ^ salt */, u64 offset, u32 episode, u32 worlds, u32 lg, u32 contracts, u32 seats,    \
+        const uint8_t *__restrict__ seat_sets, const u64 *__restrict__ deal, ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, \
+        u64 *__restrict__ ikey, u64 *__restrict__ ires
+#define TK_BIDS_NET_DEAL_NAMES n, items, pseed, offset, episode, worlds, lg, contracts, seats, seat_sets, deal, i01, i23, ikey, ires
+// tarok_playout_bids_net_value's second launch, without and with the pass item: two forms, not a launch argument, so the
+// launch without the pass carries no bidding round (DESIGN §8.19 has the instruction counts).
+TK_KERNEL(TK_BLOCK, 128) void k_playout_bids_net_deal_value(TK_BIDS_NET_DEAL_ARGS) {
+    TK_VGPR_TOP(128, 127);
+    playout_bids_net_deal_value_body<false>(TK_BIDS_NET_DEAL_NAMES);
+}
+
+TK_KERNEL(TK_BLOCK, 128) void k_playout_bids_net_deal_value_pass(TK_BIDS_NET_DEAL_ARGS) {
+    TK_VGPR_TOP(128, 127);
+    playout_bids_net_deal_value_body<true>(TK_BIDS_NET_DEAL_NAMES);
+}
+#undef TK_BIDS_NET_DEAL_NAMES
+#undef TK_BIDS_NET_DEAL_ARGS
 
 // Bids, fourth launch: one thread per (game, viewer, row); the VIEWER's 16 bits of the result words of its items,
 // summed over the worlds in integers.  Row 19 and every slot that held no item sum zeros.
@@ -4528,11 +4675,21 @@ static inline bool net_args_ok(int net_seats, const void *w1, const float *b1, c
     return net_seats >= 0 && net_seats <= 15 && w1 && b1 && w2 && b2 && w3 && b3 && scratch && !((uintptr_t)scratch & 15) && need >= 0 &&
            scratch_bytes >= need;
 }
+// The play launch over a net launch's items.  depth = 0: k_playout_net_play, to the last card; else k_playout_net_play_value,
+// whose live items carry their viewers (the caller's item kernel is the _value form).
 static inline void launch_net_play(int64_t items, int net_seats, const NetItems &it, const void *w1, const float *b1, const void *w2,
-                                   const float *b2, const void *w3, const float *b3, void *stream) {
-    hipLaunchKernelGGL(k_playout_net_play, dim3((unsigned)((items + PM_M - 1) / PM_M)), dim3(TK_BLOCK), 0, (hipStream_t)stream, items,
-                       (u32)net_seats, it.i01, it.i23, it.ikey, it.ires, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2,
-                       (const __bf16 *)w3, b3);
+                                   const float *b2, const void *w3, const float *b3, void *stream, int depth = 0, float value_scale = 0.f) {
+    const dim3 grid((unsigned)((items + PM_M - 1) / PM_M));
+    if (depth)
+        hipLaunchKernelGGL(k_playout_net_play_value, grid, dim3(TK_BLOCK), 0, (hipStream_t)stream, items, (u32)net_seats, it.i01, it.i23,
+                           it.ikey, it.ires, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3, (u32)depth, value_scale);
+    else
+        hipLaunchKernelGGL(k_playout_net_play, grid, dim3(TK_BLOCK), 0, (hipStream_t)stream, items, (u32)net_seats, it.i01, it.i23, it.ikey,
+                           it.ires, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3);
+}
+// What the _value entries take more: a depth in 1..max_depth and a finite value_scale > 0.
+static inline bool value_args_ok(int depth, int max_depth, float value_scale) {
+    return depth >= 1 && depth <= max_depth && value_scale > 0.f && !__builtin_isinf(value_scale);
 }
 
 // One net card launch: the items (`deal`, the dealer's kernel, with its per-game `words` where it has any), the playouts,
@@ -4553,12 +4710,7 @@ static int launch_playout_cards_net(Kernel deal, tarok_env *e, int worlds, uint6
     const u32 lg = playout_lg(TK_PO_MIN_LG, worlds);
     hipLaunchKernelGGL(deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
                        (u32)worlds, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, words..., it.i01, it.i23, it.ikey, it.ires);
-    if (depth)                                            // (tarok_playout_cards_net_value: `deal` is a k_playout_net_deal_value*)
-        hipLaunchKernelGGL(k_playout_net_play_value, dim3((unsigned)((items + PM_M - 1) / PM_M)), dim3(TK_BLOCK), 0, (hipStream_t)stream,
-                           items, (u32)net_seats, it.i01, it.i23, it.ikey, it.ires, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2,
-                           (const __bf16 *)w3, b3, (u32)depth, value_scale);
-    else
-        launch_net_play(items, net_seats, it, w1, b1, w2, b2, w3, b3, stream);
+    launch_net_play(items, net_seats, it, w1, b1, w2, b2, w3, b3, stream, depth, value_scale);   // (depth: `deal` is a k_playout_net_deal_value*)
     hipLaunchKernelGGL(k_playout_net_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, (u32)worlds,
                        (u32)seats, seats_per_game, e->s01, e->s23, e->gkey, it.ires, reinterpret_cast<int4 *>(sum_out), action_out);
     HIPCHK(hipGetLastError());
@@ -4626,11 +4778,13 @@ int64_t tarok_playout_exchange_net_scratch(const tarok_env *e, int worlds, int d
     return e->n * 6 * (int64_t)discard_sets * (int64_t)worlds * TK_PN_ITEM_BYTES;
 }
 
-// tarok_playout_exchange_net: the items, the playouts, the sums and the choice — three launches on `stream`, nothing allocated.
-int tarok_playout_exchange_net(tarok_env *e, int worlds, int discard_sets, uint64_t salt, int seats, const uint8_t *seats_per_game,
-                               int net_seats, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
-                               const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out, int8_t *choice_out,
-                               uint8_t *discards_out, void *stream) {
+// tarok_playout_exchange_net and its _value twin: the items, the playouts, the sums and the choice — three launches on `stream`,
+// nothing allocated.  depth = 0: the playouts run to the last card; 1..13 (checked by tarok_playout_exchange_net_value, the only
+// caller that gives one): they stop at the declarer's depth-th decision.
+static int launch_playout_exchange_net(tarok_env *e, int worlds, int discard_sets, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                                       int net_seats, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
+                                       const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out, int8_t *choice_out,
+                                       uint8_t *discards_out, void *stream, int depth, float value_scale) {
     if (!playout_args_ok(e, worlds, 1, seats) || discard_sets < 1 || discard_sets > TAROK_EXCHANGE_MAX_SETS ||
         !net_args_ok(net_seats, w1, b1, w2, b2, w3, b3, scratch, scratch_bytes, tarok_playout_exchange_net_scratch(e, worlds, discard_sets)) ||
         (!sum_out && !choice_out && !discards_out))
@@ -4639,15 +4793,32 @@ int tarok_playout_exchange_net(tarok_env *e, int worlds, int discard_sets, uint6
     const int64_t items = e->n * 6 * (int64_t)discard_sets * (int64_t)worlds;
     const NetItems it(scratch, items);
     const u32 lg = playout_lg(TK_PX_MIN_LG, worlds);     // tarok_playout_exchange's teams at samples = 1
-    hipLaunchKernelGGL(k_playout_exchange_net_deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, items,
-                       e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)discard_sets, lg, (u32)seats, seats_per_game, e->s01, e->s23,
-                       e->cnt, it.i01, it.i23, it.ikey, it.ires);
-    launch_net_play(items, net_seats, it, w1, b1, w2, b2, w3, b3, stream);
+    hipLaunchKernelGGL(depth ? k_playout_exchange_net_deal_value : k_playout_exchange_net_deal, playout_grid(e, lg), dim3(TK_BLOCK), 0,
+                       (hipStream_t)stream, e->n, items, e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)discard_sets, lg, (u32)seats,
+                       seats_per_game, e->s01, e->s23, e->cnt, it.i01, it.i23, it.ikey, it.ires);
+    launch_net_play(items, net_seats, it, w1, b1, w2, b2, w3, b3, stream, depth, value_scale);
     hipLaunchKernelGGL(k_playout_exchange_net_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, items,
                        e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)discard_sets, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt,
                        e->gkey, it.ires, reinterpret_cast<int4 *>(sum_out), choice_out, discards_out);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
+}
+
+int tarok_playout_exchange_net(tarok_env *e, int worlds, int discard_sets, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                               int net_seats, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
+                               const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out, int8_t *choice_out,
+                               uint8_t *discards_out, void *stream) {
+    return launch_playout_exchange_net(e, worlds, discard_sets, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3, scratch,
+                                       scratch_bytes, sum_out, choice_out, discards_out, stream, 0, 0.f);
+}
+
+int tarok_playout_exchange_net_value(tarok_env *e, int worlds, int discard_sets, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                                     int net_seats, int depth, float value_scale, const void *w1, const float *b1, const void *w2,
+                                     const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
+                                     int32_t *sum_out, int8_t *choice_out, uint8_t *discards_out, void *stream) {
+    if (!value_args_ok(depth, TAROK_PLAYOUT_FRONT_MAX_DEPTH, value_scale)) return TAROK_EINVAL;
+    return launch_playout_exchange_net(e, worlds, discard_sets, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3, scratch,
+                                       scratch_bytes, sum_out, choice_out, discards_out, stream, depth, value_scale);
 }
 
 int tarok_shown_voids(tarok_env *e, uint32_t *voids_out, void *stream) {
@@ -4715,10 +4886,13 @@ int64_t tarok_playout_bids_net_scratch(const tarok_env *e, int worlds) {
     return e->n * 4 * TAROK_BID_ROWS * (int64_t)worlds * TK_PN_ITEM_BYTES + e->n * 5 * (int64_t)sizeof(u64);
 }
 
-// tarok_playout_bids_net: the deal, the items, the playouts, the sums — four launches on `stream`, nothing allocated.
-int tarok_playout_bids_net(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int contracts, uint64_t salt, int seats,
-                           const uint8_t *seats_per_game, int net_seats, const void *w1, const float *b1, const void *w2, const float *b2,
-                           const void *w3, const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out, void *stream) {
+// tarok_playout_bids_net and its _value twin: the deal, the items, the playouts, the sums — four launches on `stream`, nothing
+// allocated.  depth = 0: the playouts run to the last card and `pass` is 0; 1..13 (checked by tarok_playout_bids_net_value, the only
+// caller that gives one): they stop at the viewer's depth-th decision, and pass = 1 makes row 19's slots items.
+static int launch_playout_bids_net(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int contracts, uint64_t salt, int seats,
+                                   const uint8_t *seats_per_game, int net_seats, const void *w1, const float *b1, const void *w2,
+                                   const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out,
+                                   void *stream, int depth, float value_scale, int pass) {
     if (!playout_args_ok(e, worlds, 1, seats) || contracts < 1 || contracts > TAROK_BID_ALL_CONTRACTS ||
         !net_args_ok(net_seats, w1, b1, w2, b2, w3, b3, scratch, scratch_bytes, tarok_playout_bids_net_scratch(e, worlds)) || !sum_out)
         return TAROK_EINVAL;
@@ -4728,13 +4902,30 @@ int tarok_playout_bids_net(tarok_env *e, uint32_t episode, const uint8_t *deals,
     u64 *deal = it.ires + items;
     hipLaunchKernelGGL(k_bid_deal, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, episode, deals, deal);
     const u32 lg = playout_lg(TK_PB_MIN_LG, worlds);     // tarok_playout_bids' teams at samples = 1
-    hipLaunchKernelGGL(k_playout_bids_net_deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, items, e->seed ^ (u64)salt,
-                       e->offset, episode, (u32)worlds, lg, (u32)contracts, (u32)seats, seats_per_game, deal, it.i01, it.i23, it.ikey, it.ires);
-    launch_net_play(items, net_seats, it, w1, b1, w2, b2, w3, b3, stream);
+    hipLaunchKernelGGL(!depth ? k_playout_bids_net_deal : (pass ? k_playout_bids_net_deal_value_pass : k_playout_bids_net_deal_value),
+                       playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, items, e->seed ^ (u64)salt, e->offset, episode,
+                       (u32)worlds, lg, (u32)contracts, (u32)seats, seats_per_game, deal, it.i01, it.i23, it.ikey, it.ires);
+    launch_net_play(items, net_seats, it, w1, b1, w2, b2, w3, b3, stream, depth, value_scale);
     hipLaunchKernelGGL(k_playout_bids_net_sum, grid_for(rows), dim3(TK_BLOCK), 0, (hipStream_t)stream, rows, items, (u32)worlds, it.ires,
                        sum_out);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
+}
+
+int tarok_playout_bids_net(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int contracts, uint64_t salt, int seats,
+                           const uint8_t *seats_per_game, int net_seats, const void *w1, const float *b1, const void *w2, const float *b2,
+                           const void *w3, const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out, void *stream) {
+    return launch_playout_bids_net(e, episode, deals, worlds, contracts, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3,
+                                   scratch, scratch_bytes, sum_out, stream, 0, 0.f, 0);
+}
+
+int tarok_playout_bids_net_value(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int contracts, uint64_t salt, int seats,
+                                 const uint8_t *seats_per_game, int net_seats, int depth, float value_scale, int pass_value, const void *w1,
+                                 const float *b1, const void *w2, const float *b2, const void *w3, const float *b3, void *scratch,
+                                 int64_t scratch_bytes, int32_t *sum_out, void *stream) {
+    if (!value_args_ok(depth, TAROK_PLAYOUT_FRONT_MAX_DEPTH, value_scale) || pass_value < 0 || pass_value > 1) return TAROK_EINVAL;
+    return launch_playout_bids_net(e, episode, deals, worlds, contracts, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3,
+                                   scratch, scratch_bytes, sum_out, stream, depth, value_scale, pass_value);
 }
 
 extern "C++" {

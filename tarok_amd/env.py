@@ -492,20 +492,43 @@ class TarokVecEnv:
         playouts.  net_seats=0: playout_exchange(worlds, 1, discard_sets) to the byte.  Candidates, worlds, the three
         outputs, `seats` / `seats_per_game`, `salt` and the read-only contract: as for playout_exchange.  The scratch is
         playout_exchange_net_scratch(worlds, discard_sets)."""
+        return TarokVecEnv._exchange_net(self, weights, worlds, discard_sets, net_seats, salt, seats, seats_per_game, sum_out, choice_out,
+                                         discards_out)
+
+    def _exchange_net(self, weights, worlds, discard_sets, net_seats, salt, seats, seats_per_game, sum_out, choice_out, discards_out,
+                      value=()):
+        """playout_exchange_net's call; value = (depth, value_scale): tarok_playout_exchange_net_value's."""
         if not 0 <= int(net_seats) <= 15:
             raise ValueError("net_seats: a 4-bit seat set, 0..15")
         w = self.check_mlp_weights(weights)
         scratch = self.playout_exchange_net_scratch(worlds, discard_sets)
+        launch = self.L.tarok_playout_exchange_net_value if value else self.L.tarok_playout_exchange_net
         with torch.cuda.device(self.device):
             sum_out = self._empty(sum_out, (self.n, 6 * int(discard_sets), 4), torch.int32)
             choice_out = self._empty(choice_out, self.n, torch.int8)
             discards_out = self._empty(discards_out, (self.n, 3), torch.uint8)
-            _native.check(self.L.tarok_playout_exchange_net(self._h, int(worlds), int(discard_sets), int(salt) & ((1 << 64) - 1),
-                                                            int(seats), self._p(self._seat_sets(seats_per_game)), int(net_seats),
-                                                            *[self._p(t) for t in w], self._p(scratch), scratch.numel(),
-                                                            self._p(sum_out), self._p(choice_out), self._p(discards_out),
-                                                            self._stream()))
+            _native.check(launch(self._h, int(worlds), int(discard_sets), int(salt) & ((1 << 64) - 1), int(seats),
+                                 self._p(self._seat_sets(seats_per_game)), int(net_seats), *value, *[self._p(t) for t in w],
+                                 self._p(scratch), scratch.numel(), self._p(sum_out), self._p(choice_out), self._p(discards_out),
+                                 self._stream()))
         return sum_out, choice_out, discards_out
+
+    def playout_exchange_net_value(self, weights, worlds, discard_sets, depth, value_scale=70.0, net_seats=15, salt=0, seats=15,
+                                   seats_per_game=None, sum_out=None, choice_out=None, discards_out=None):
+        """playout_exchange_net whose playouts stop at the DECLARER's `depth`-th decision (tarok_playout_exchange_net_value):
+        there the value head of `weights` times `value_scale`, rounded half-even into int16 range, is the declarer's result
+        and the other three columns get 0, as playout_cards_net_value stops a card's playouts; only the declarer's column of
+        the sums is meaningful, and the choice reads no other.  depth: 1..13 — a candidate is a game at 0 cards played, so
+        the declarer has 12 decisions ahead: 13 never stops and gives playout_exchange_net's bytes, 12 stops at the forced
+        last card, 1 runs at most 4 card rounds.  At depth 1 with the declarer on lead nothing is played and a candidate's
+        number is the same in every world.  Everything else, the scratch included, is playout_exchange_net's; depth=None IS
+        playout_exchange_net."""
+        value = ()
+        if depth is not None:
+            P.check_depth(depth, value_scale, max_depth=K.PLAYOUT_FRONT_MAX_DEPTH)
+            value = (int(depth), float(value_scale))
+        return TarokVecEnv._exchange_net(self, weights, worlds, discard_sets, net_seats, salt, seats, seats_per_game, sum_out, choice_out,
+                                         discards_out, value)
 
     def playout_bids_net_scratch(self, worlds):
         """The scratch tensor of playout_bids_net at `worlds` (uint8, tarok_playout_bids_net_scratch bytes: 3,840 * worlds
@@ -523,19 +546,40 @@ class TarokVecEnv:
         net_seats=0: playout_bids(episode, worlds, 1) to the byte.  Row K.BID_PASS_ROW is 0: the pass is not valued here.
         Everything else as for playout_bids.  The scratch is playout_bids_net_scratch(worlds); nothing is allocated by
         the launch itself."""
+        return TarokVecEnv._bids_net(self, weights, episode, worlds, net_seats, contracts, deals, salt, seats, seats_per_game, sum_out)
+
+    def _bids_net(self, weights, episode, worlds, net_seats, contracts, deals, salt, seats, seats_per_game, sum_out, value=()):
+        """playout_bids_net's call; value = (depth, value_scale, pass_value): tarok_playout_bids_net_value's."""
         if not 0 <= int(net_seats) <= 15:
             raise ValueError("net_seats: a 4-bit seat set, 0..15")
         w = self.check_mlp_weights(weights)
         scratch = self.playout_bids_net_scratch(worlds)
         deals = self._dev(deals, torch.uint8, (self.n, 54))
+        launch = self.L.tarok_playout_bids_net_value if value else self.L.tarok_playout_bids_net
         with torch.cuda.device(self.device):
             sum_out = self._empty(sum_out, (self.n, 4, K.BID_ROWS), torch.int32)
-            _native.check(self.L.tarok_playout_bids_net(self._h, int(episode), self._p(deals), int(worlds), int(contracts),
-                                                        int(salt) & ((1 << 64) - 1), int(seats),
-                                                        self._p(self._seat_sets(seats_per_game)), int(net_seats),
-                                                        *[self._p(t) for t in w], self._p(scratch), scratch.numel(),
-                                                        self._p(sum_out), self._stream()))
+            _native.check(launch(self._h, int(episode), self._p(deals), int(worlds), int(contracts), int(salt) & ((1 << 64) - 1),
+                                 int(seats), self._p(self._seat_sets(seats_per_game)), int(net_seats), *value,
+                                 *[self._p(t) for t in w], self._p(scratch), scratch.numel(), self._p(sum_out), self._stream()))
         return sum_out
+
+    def playout_bids_net_value(self, weights, episode, worlds, depth, value_scale=70.0, pass_value=False, net_seats=15,
+                               contracts=K.BID_DEFAULT_CONTRACTS, deals=None, salt=0, seats=15, seats_per_game=None, sum_out=None):
+        """playout_bids_net whose playouts stop at the VIEWER's `depth`-th decision (tarok_playout_bids_net_value; the viewer
+        is the seat whose row it is, in the Klop row too): there the value head of `weights` times `value_scale`, rounded
+        half-even into int16 range, is the viewer's result, as playout_cards_net_value stops a card's playouts.  depth:
+        1..13 — an option is a game at 0 cards played: 13 never stops and gives playout_bids_net's bytes, 12 stops at the
+        forced last card, 1 runs at most 4 card rounds.  pass_value=True: row K.BID_PASS_ROW also holds the viewer's value
+        of PASSING — playout_bids(pass_value=True)'s pass playout (three Bots bid with the viewer silent) at sample 0, played
+        and stopped like every other row; bid_round(pass_value=True) takes the sums.  Without it row 19 is 0.  Everything
+        else, the scratch included, is playout_bids_net's; depth=None IS playout_bids_net, where a pass is not valued."""
+        value = ()
+        if depth is not None:
+            P.check_depth(depth, value_scale, max_depth=K.PLAYOUT_FRONT_MAX_DEPTH)
+            value = (int(depth), float(value_scale), int(bool(pass_value)))
+        elif pass_value:
+            raise ValueError("pass_value=True needs a depth: the plain net launch does not value the pass")
+        return TarokVecEnv._bids_net(self, weights, episode, worlds, net_seats, contracts, deals, salt, seats, seats_per_game, sum_out, value)
 
     def bid_round(self, episode, sums, playouts, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, seats=15, seats_per_game=None,
                   pass_value=False):

@@ -122,9 +122,12 @@ def _bid_front(bidding, salt, threshold, contracts, pass_value=False):
     return make
 
 
-def _net_front_args(net, net_seats, samples, what):
+def _net_front_args(net, net_seats, samples, what, net_depth=None, net_value_scale=70.0):
     """The checks of a front end whose playouts the network plays: net's six tensors, and the seat set to hand the launch
-    for a pass (a function of the pass's seats: "own" is the pass's own set)."""
+    for a pass (a function of the pass's seats: "own" is the pass's own set).  net_depth: None, or the front launches'
+    1..13 with a finite net_value_scale > 0."""
+    if net_depth is not None:
+        playout.check_depth(net_depth, net_value_scale, playout.spelling(), max_depth=K.PLAYOUT_FRONT_MAX_DEPTH)
     if samples not in (None, 1):
         raise ValueError("net= runs one playout per (%s, world): samples must be None or 1" % what)
     if net_seats != "own" and not (isinstance(net_seats, int) and 0 <= net_seats <= 15):
@@ -132,15 +135,23 @@ def _net_front_args(net, net_seats, samples, what):
     return TarokVecEnv.check_mlp_weights(net), (lambda seats: seats if net_seats == "own" else net_seats)
 
 
-def _bid_net_front(net, net_seats, worlds, salt, threshold, contracts):
+def _bid_net_front(net, net_seats, worlds, salt, threshold, contracts, net_depth=None, net_value_scale=70.0, pass_value=False):
     """_bid_front whose playouts the network plays: ONE tarok_playout_bids_net at `worlds` with the pass's seat set —
-    net_seats inside the playouts, or the pass's own set for "own" — and ONE tarok_bid_round at playouts = worlds."""
+    net_seats inside the playouts, or the pass's own set for "own" — and ONE tarok_bid_round at playouts = worlds.
+    net_depth: tarok_playout_bids_net_value in its place; pass_value (with net_depth only): its pass item, and
+    tarok_bid_round_pass with `threshold` the margin over the pass, as for the Bot teacher."""
     def make(env):
         sums = _empty(env, (env.n, 4, K.BID_ROWS), torch.int32)
 
         def bid(env, episode, seats):
-            env.playout_bids_net(net, episode, worlds, net_seats=net_seats(seats), contracts=contracts, salt=salt, seats=seats, sum_out=sums)
-            c, d, k = env.bid_round(episode, sums, int(worlds), threshold=threshold, contracts=contracts, seats=seats)
+            if net_depth is None:
+                env.playout_bids_net(net, episode, worlds, net_seats=net_seats(seats), contracts=contracts, salt=salt, seats=seats, sum_out=sums)
+                c, d, k = env.bid_round(episode, sums, int(worlds), threshold=threshold, contracts=contracts, seats=seats)
+            else:
+                env.playout_bids_net_value(net, episode, worlds, net_depth, net_value_scale, pass_value=pass_value,
+                                           net_seats=net_seats(seats), contracts=contracts, salt=salt, seats=seats, sum_out=sums)
+                c, d, k = env.bid_round(episode, sums, int(worlds), threshold=threshold, contracts=contracts, seats=seats,
+                                        pass_value=pass_value)
             setup = dict(contract=c, declarer=d, king_suit=k)
             return setup, dict(setup, sums=sums)
         return bid
@@ -183,16 +194,21 @@ def _exchange_front(worlds, samples, discard_sets, salt):
     return make
 
 
-def _exchange_net_front(net, net_seats, worlds, discard_sets, salt):
+def _exchange_net_front(net, net_seats, worlds, discard_sets, salt, net_depth=None, net_value_scale=70.0):
     """_exchange_front whose playouts the network plays: ONE tarok_playout_exchange_net at (worlds, discard_sets) with the
-    pass's seat set — net_seats inside the playouts, or the pass's own set for "own" — and one tarok_exchange."""
+    pass's seat set — net_seats inside the playouts, or the pass's own set for "own" — and one tarok_exchange.  net_depth:
+    tarok_playout_exchange_net_value in its place."""
     def make(env):
         sums = _empty(env, (env.n, 6 * int(discard_sets), 4), torch.int32)
         chosen = dict(choice=_empty(env, env.n, torch.int8), discards=_empty(env, (env.n, 3), torch.uint8))
 
         def exchange(env, seats):
-            env.playout_exchange_net(net, worlds, discard_sets, net_seats=net_seats(seats), salt=salt, seats=seats, sum_out=sums,
-                                     choice_out=chosen["choice"], discards_out=chosen["discards"])
+            if net_depth is None:
+                env.playout_exchange_net(net, worlds, discard_sets, net_seats=net_seats(seats), salt=salt, seats=seats, sum_out=sums,
+                                         choice_out=chosen["choice"], discards_out=chosen["discards"])
+            else:
+                env.playout_exchange_net_value(net, worlds, discard_sets, net_depth, net_value_scale, net_seats=net_seats(seats), salt=salt,
+                                               seats=seats, sum_out=sums, choice_out=chosen["choice"], discards_out=chosen["discards"])
             env.exchange(chosen["choice"], chosen["discards"])
             return dict(chosen, sums=sums)
         return exchange
@@ -464,15 +480,18 @@ def evaluate_exchange_vs_bot(worlds, samples, discard_sets, n_games, episodes, s
 
 
 def evaluate_exchange_net_vs_bot(net, worlds, discard_sets, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None,
-                                 net_seats=15, cards=None):
+                                 net_seats=15, cards=None, net_depth=None, net_value_scale=70.0):
     """evaluate_exchange_vs_bot with the playouts played by a network: net = policy_mlp's six tensors; in pass 1 + k the
     games seat k declared get their exchange from ONE tarok_playout_exchange_net at (worlds, discard_sets) — one playout
     per (candidate, world), the network's greedy card on the seats of net_seats (a 4-bit set of absolute seats; "own":
     the pass's seat set) inside them, the Bot's on the others — in tarok_playout_exchange's place; the inspected dicts
     also hold the launch's sums.  cards=weights: the pass's seats also PLAY the network's greedy card, in the Bot's place.
     Pass 0 is the Bot everywhere either way: evaluate_exchange_vs_bot's pass 0 on the same deals.  (A function of its own,
-    not arguments of evaluate_exchange_vs_bot: that call's parameter list is pinned as it stands.)"""
-    exchange = _exchange_net_front(*_net_front_args(net, net_seats, None, "candidate"), worlds, discard_sets, salt)
+    not arguments of evaluate_exchange_vs_bot: that call's parameter list is pinned as it stands.)  net_depth: None, or
+    1..13 — tarok_playout_exchange_net_value: the playouts stop at the declarer's net_depth-th decision and read the value
+    head of `net` there at net_value_scale points per unit."""
+    exchange = _exchange_net_front(*_net_front_args(net, net_seats, None, "candidate", net_depth, net_value_scale), worlds, discard_sets,
+                                   salt, net_depth, net_value_scale)
     front = _front(inspect is not None, exchange=exchange)
     return duplicate_advantage(_passes(n_games, episodes, front, _front_cards(cards), inspect, device=device, seed=seed, mix=mix))
 
@@ -489,7 +508,8 @@ def evaluate_exchangenet_vs_bot(weights, n_games, episodes, seed=0, mix=K.MIX_BO
 
 
 def evaluate_bidding_vs_bot(worlds, samples, n_games, episodes, seed=0, device=0, salt=0, threshold=0,
-                            contracts=K.BID_DEFAULT_CONTRACTS, inspect=None, pass_value=False, net=None, net_seats=15, cards=None):
+                            contracts=K.BID_DEFAULT_CONTRACTS, inspect=None, pass_value=False, net=None, net_seats=15, cards=None,
+                            net_depth=None, net_value_scale=70.0):
     """What is the bid alone worth?  The five duplicate passes on K.MIX_BOT's deals with the Bot making EVERY exchange and
     playing EVERY card; in pass 1 + k seat k bids by playouts — tarok_playout_bids at (worlds, samples) over `contracts`,
     then tarok_bid_round with `threshold` — against three Bot bidders, and calls its king by the same sums.  Pass 0 is the
@@ -501,13 +521,20 @@ def evaluate_bidding_vs_bot(worlds, samples, n_games, episodes, seed=0, device=0
     network — one tarok_playout_bids_net at `worlds` in tarok_playout_bids' place, the network's greedy card on the seats
     of net_seats (a 4-bit set of absolute seats; "own": the pass's seat set) inside them, and tarok_bid_round at playouts =
     worlds; the inspected dicts then also hold the launch's sums.  cards=weights: the pass's seats also PLAY the network's
-    greedy card, in the Bot's place.  With the defaults the call issues the launches it always did."""
+    greedy card, in the Bot's place.  net_depth (with net): None, or 1..13 — tarok_playout_bids_net_value: the playouts stop
+    at the viewer's net_depth-th decision and read the value head of `net` there at net_value_scale points per unit; then
+    pass_value=True is allowed too — the launch plays the pass item, and tarok_bid_round_pass holds every bid against it as
+    for the Bot teacher.  With the defaults the call issues the launches it always did."""
     if net is None:
+        if net_depth is not None:
+            raise ValueError("net_depth stops the network's playouts: it needs net=")
         bid = _bid_front((worlds, samples), salt, threshold, contracts, pass_value)
     else:
-        if pass_value:
-            raise ValueError("net= does not value the pass: pass_value=True goes with the Bot's playouts only")
-        bid = _bid_net_front(*_net_front_args(net, net_seats, samples, "option"), worlds, salt, threshold, contracts)
+        if pass_value and net_depth is None:
+            raise ValueError("net= without net_depth does not value the pass: pass_value=True goes with the Bot's playouts or "
+                             "with net_depth")
+        bid = _bid_net_front(*_net_front_args(net, net_seats, samples, "option", net_depth, net_value_scale), worlds, salt, threshold,
+                             contracts, net_depth, net_value_scale, bool(pass_value))
     front = _front(inspect is not None, bid=bid)
     return duplicate_advantage(_passes(n_games, episodes, front, _front_cards(cards), inspect, device=device, seed=seed, mix=K.MIX_BOT))
 

@@ -14,6 +14,8 @@ everything but collect() / exchange() runs on CPU tensors as well (ExchangeLearn
 import torch
 import torch.nn.functional as F
 
+from . import karte as K
+from . import playout as P
 from .bidding import pack_weights
 from .env import TarokVecEnv
 from .selfplay import PolicyNet
@@ -67,11 +69,18 @@ class ExchangeLearner:
     for a learner on the CPU that is fed batches by hand (loss / step).  worlds, samples, discard_sets: the teacher's
     launch (playout_exchange).  net: six tensors (policy_mlp's weights, read live at every collect()) — the teacher is then
     playout_exchange_net at (worlds, discard_sets) with the network's greedy card on the seats of net_seats inside the
-    playouts, playouts = worlds; `samples` must be 1 or left unset."""
+    playouts, playouts = worlds; `samples` must be 1 or left unset.  net_depth: None, or 1..13 — the teacher is
+    playout_exchange_net_value, whose playouts stop at the declarer's net_depth-th decision and read the value head of `net`
+    there at net_value_scale points per unit (13 never stops)."""
 
-    def __init__(self, env, worlds=8, samples=None, discard_sets=4, lr=1e-3, reward_scale=1.0 / 70.0, seed=0, net=None, net_seats=15):
+    def __init__(self, env, worlds=8, samples=None, discard_sets=4, lr=1e-3, reward_scale=1.0 / 70.0, seed=0, net=None, net_seats=15,
+                 net_depth=None, net_value_scale=70.0):
         if not reward_scale > 0:
             raise ValueError("reward_scale > 0")
+        if net_depth is not None:
+            if net is None:
+                raise ValueError("net_depth stops the network's playouts: it needs net=")
+            P.check_depth(net_depth, net_value_scale, P.spelling(), max_depth=K.PLAYOUT_FRONT_MAX_DEPTH)
         if net is not None:
             if samples not in (None, 1):
                 raise ValueError("net= runs one playout per (candidate, world): samples must be 1 or unset")
@@ -80,6 +89,7 @@ class ExchangeLearner:
             net = TarokVecEnv.check_mlp_weights(net)
         samples = (1 if net is not None else 2) if samples is None else samples
         self.net_weights, self.net_seats = net, int(net_seats)
+        self.net_depth, self.net_value_scale = net_depth, float(net_value_scale)
         self.env = env
         self.device = env.device if env is not None else torch.device("cpu")
         self.worlds, self.samples, self.discard_sets = int(worlds), int(samples), int(discard_sets)
@@ -124,8 +134,8 @@ class ExchangeLearner:
         launch for its input rows.  The games are left waiting for the exchange."""
         self.env.reset(episode=episode, defer_exchange=True)
         if self.net_weights is not None:
-            sums, _, _ = self.env.playout_exchange_net(self.net_weights, self.worlds, self.discard_sets, net_seats=self.net_seats,
-                                                       salt=self.salt)
+            sums, _, _ = self.env.playout_exchange_net_value(self.net_weights, self.worlds, self.discard_sets, self.net_depth,
+                                                             self.net_value_scale, net_seats=self.net_seats, salt=self.salt)
         else:
             sums, _, _ = self.env.playout_exchange(self.worlds, self.samples, self.discard_sets, salt=self.salt)
         cands = self.env.exchange_candidates(self.discard_sets, salt=self.salt)

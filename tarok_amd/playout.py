@@ -27,9 +27,10 @@ def one_world_kind(voids, hidden, say=spelling()):
         raise ValueError(say("{hidden}=True is not built together with {voids}=True: give one of the two"))
 
 
-def check_depth(depth, value_scale, say=spelling(net_depth="depth", net_value_scale="value_scale")):
-    if isinstance(depth, bool) or not isinstance(depth, numbers.Integral) or not 1 <= depth <= K.PLAYOUT_MAX_DEPTH:
-        raise ValueError(say("{net_depth}: None or 1..%d viewer decisions" % K.PLAYOUT_MAX_DEPTH))
+def check_depth(depth, value_scale, say=spelling(net_depth="depth", net_value_scale="value_scale"), max_depth=K.PLAYOUT_MAX_DEPTH):
+    """max_depth: K.PLAYOUT_FRONT_MAX_DEPTH for the exchange and bid launches, whose items start at 0 cards played."""
+    if isinstance(depth, bool) or not isinstance(depth, numbers.Integral) or not 1 <= depth <= max_depth:
+        raise ValueError(say("{net_depth}: None or 1..%d viewer decisions" % max_depth))
     if not 0 < float(value_scale) < float("inf"):
         raise ValueError(say("{net_value_scale}: finite and > 0"))
 
