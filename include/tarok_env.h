@@ -975,6 +975,55 @@ int tarok_playout_cards_net_value(tarok_env *env, int worlds, uint64_t salt, int
                                   const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out,
                                   uint8_t *action_out, void *stream);
 
+/* Sequential-halving playouts: tarok_playout_cards_det / _voids / _hidden whose later worlds are played only by the
+ * leading cards.  One launch; exact and integer.  kind: TAROK_NET_WORLDS_DET / _VOIDS / _HIDDEN (the name is historical:
+ * here it names the Bot-played launch whose worlds are dealt); words: NULL, the voids [N] u32 or the played [N] u64, exactly
+ * as tarok_playout_cards_net_value takes them.  rounds: 1..TAROK_PLAYOUT_MAX_ROUNDS; round_worlds: a HOST array of
+ * `rounds` positive ints, read during the call; W = their sum <= TAROK_PLAYOUT_MAX_WORLDS; samples as in those launches.
+ *
+ * "Takes part", the position, wkey, pkey, ebase, the rank j of a legal card and the Bot's card for a mover outside the
+ * seat set are the existing card launches', word for word.  World w, w < W, is the world the existing launch of that kind
+ * deals under w.  With e_r the cumulative sum of round_worlds (e_{-1} = 0), round r covers the worlds e_{r-1} .. e_r - 1:
+ * every card ALIVE in round r is played `samples` times in each of them under the existing item key
+ * (c << 16 | w << 10 | k) and the four scores are added to the card's row.
+ *   Before round 0 every legal rank is alive.
+ *   After a round that is not the last, with k cards alive, the max(1, ceil(k / 2)) cards with the highest mover's sum
+ *   stay alive, ties to the lower rank.  (All alive cards have had the same number of playouts: comparing sums is
+ *   comparing means.)
+ *   A game with one card alive plays no further round.
+ *   sum_out    [N,12,4] i32, 16-byte aligned, or NULL: row j = the four scores summed over the playouts card j got; zero
+ *              rows beyond the legal cards and for games that do not take part.
+ *   count_out  [N,12] i32, 16-byte aligned, or NULL: entry j = the playouts behind row j, (worlds played) x samples; 0
+ *              beyond the legal cards and for games that do not take part.
+ *   action_out [N] u8 or NULL: among the cards alive after the last round played, the lowest rank at the maximum of the
+ *              mover's sum; the Bot's card or 255 under the existing rule.
+ * EVERY row of every given output is written.  Read-only on the env, stream-ordered, capturable: the rounds cost no
+ * launches, no global traffic and no host read.
+ * Consequences: rounds = 1 writes the bytes of tarok_playout_cards_det / _voids / _hidden(W, samples), and count =
+ * W * samples on the legal ranks; for any schedule a row whose count is e * samples equals that rank's row of the
+ * existing launch at worlds = e, e one of the cumulative ends (the keys depend on no launch size).
+ * TAROK_EINVAL (before any HIP call) for everything the existing launch of that kind refuses, rounds outside
+ * 1..TAROK_PLAYOUT_MAX_ROUNDS, a NULL round_worlds, an entry < 1, W > TAROK_PLAYOUT_MAX_WORLDS, a kind outside the three,
+ * words NULL for a kind that needs them or non-NULL for kind 0, all three outputs NULL. */
+#define TAROK_PLAYOUT_MAX_ROUNDS 4
+int tarok_playout_cards_halving(tarok_env *env, int kind, const void *words, int rounds, const int *round_worlds, int samples,
+                                uint64_t salt, int seats, const uint8_t *seats_per_game, int32_t *sum_out, int32_t *count_out,
+                                uint8_t *action_out, void *stream);
+
+/* tarok_playout_targets for sums with a count per card (a halving launch's sum_out and count_out).  The "has a teacher"
+ * rule and the row layout are tarok_playout_targets'.  With a teacher, nl as there:
+ *   m_j = float(sums[g][j][s]) / float(counts[g][j]), one float32 division, for the ranks j < nl with counts[g][j] > 0;
+ *   z_j = (m_j - max_k m_k) / tau over those ranks; target = bf16(exp(z_j) / sum_k exp(z_k)) at the rank's card.
+ *   A legal rank with count <= 0 gets target 0; a game all of whose legal ranks have count <= 0 gets a zero row.  (Neither
+ *   happens on a halving launch's own output, but the call is a function of its arguments.)
+ *   tau = 0: 1.0 at the lowest rank at the maximum of m AMONG THE RANKS OF MAXIMAL COUNT, compared exactly (equal counts:
+ *   the integer sums).  On a halving launch's output this is the launch's action_out.
+ * sums [N,12,4] i32 and counts [N,12] i32, both 16-byte aligned; obs, seats, seats_per_game, target_out as there.
+ * TAROK_EINVAL (before any HIP call) for a NULL env or array (seats_per_game may be NULL), tau < 0, NaN or infinite, a
+ * tau > 0 that is not a normal float32 number (below 2^-126), seats outside 0..15. */
+int tarok_playout_targets_counts(tarok_env *env, const int32_t *sums, const int32_t *counts, const uint64_t *obs, float tau,
+                                 int seats, const uint8_t *seats_per_game, void *target_out, void *stream);
+
 /* Net-played playouts for the exchange and the bid: tarok_playout_exchange and tarok_playout_bids at ONE playout per
  * (candidate or option, world), played as tarok_playout_cards_net plays its playouts — the network's greedy card on the
  * absolute seats of net_seats (one launch-wide 4-bit set), the Bot's card policy_action(pkey, q, legal) on the others.

@@ -633,6 +633,52 @@ __device__ __forceinline__ u32 policy_action_follow(u64 key, RngCtr c, u32 w, u3
     return kth_bit_word(w, hi_sel, pick(rng32(key, c), (u32)__popc(w)));
 }
 
+// Sequential halving (tarok_playout_cards_halving, include/tarok_env.h): the survivor rule after a round that is not the
+// last.  row: a game's [12][4] sums, alive: the ranks that played the round (bits 0..11, every one with the same number of
+// playouts behind its sums), seat: the mover.  Of k alive ranks the max(1, ceil(k / 2)) with the highest sum stay, ties
+// to the lower rank.  The twelve sums are read once (constant offsets: the reads pipeline, and every lane of a team reads
+// the same words, which LDS broadcasts); then `keep` times the best of the ranks left — the highest sum, the lowest rank at
+// it — is taken: a rolled loop of at most six passes over twelve registers.  (Rolled loops that re-read LDS for every pair
+// cost a launch more than its playouts: every lane of every team runs this; the unrolled 12 x 12 compare table took a
+// hundred registers.)  The kernel and tests/host_emu/halving_host.cpp share it.
+__device__ __forceinline__ u32 halve_alive(const int *row, u32 alive, u32 seat) {
+    int v[12];
+#pragma unroll
+    for (u32 j = 0; j < 12; j++) v[j] = row[j * 4 + seat];
+    u32 rest = alive, out = 0;
+#pragma nounroll
+    for (u32 n = ((u32)__popc(alive) + 1u) >> 1; n; n--) {
+        u32 best = 0;
+        int top = 0;
+        bool none = true;
+#pragma unroll
+        for (u32 j = 0; j < 12; j++) {
+            const bool up = ((rest >> j) & 1u) && (none || v[j] > top);
+            top = up ? v[j] : top;
+            best = up ? j : best;
+            none = none && !up;
+        }
+        out |= 1u << best;
+        rest &= ~(1u << best);
+    }
+    return out;
+}
+
+// The launch's card among the ranks alive after the last round played: the lowest rank at the maximum of seat's sums
+// (12 where none is alive).
+__device__ __forceinline__ u32 best_alive(const int *row, u32 alive, u32 seat) {
+    u32 best = 12;
+    int top = 0;
+#pragma unroll
+    for (u32 j = 0; j < 12; j++) {
+        const int v = row[j * 4 + seat];
+        const bool up = ((alive >> j) & 1u) && (best == 12 || v > top);
+        top = up ? v : top;
+        best = up ? j : best;
+    }
+    return best;
+}
+
 // Determinization (tarok_playout_cards_det, include/tarok_env.h): one WORLD of the seat `mover` — the cards it cannot
 // see, P = the hands of the three other seats, are dealt afresh among those seats, uniformly over the deals that keep
 // the hand sizes.  The cards of P are walked in ascending card number; card i of the walk draws

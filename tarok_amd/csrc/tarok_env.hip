@@ -1730,6 +1730,111 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_hidden(int64_t n, u64 pseed /* seed ^ sa
     playout_cards_body<DealHidden>(n, pseed, offset, worlds, samples, lg, seats, seat_sets, s01, s23, cnt, gkey, played_words, sum_out, action_out);
 }
 
+// tarok_playout_cards_halving: the card launches with sequential halving — playout_cards_body's team, dealers, keys and
+// playout_from, with a round loop around the item walk.  `ends`: the cumulative world counts e_0 .. e_{rounds-1}, a byte
+// each (e <= 64); the team deals all e_{rounds-1} worlds once.  Round r walks (ranks alive) x (worlds e_{r-1} .. e_r - 1) x
+// samples items round-robin over the team's lanes; after the barrier every lane of the team reads the team's rows and
+// computes the same new `alive` word (halve_alive), and a second barrier keeps a team of several waves from adding the
+// next round's scores to a row another of its waves still reads.  `ends` is launch-uniform, so every lane of the
+// workgroup meets the same 2 * rounds barriers whether or not its game still plays.  A team's block in LDS is its [12][4] sums and
+// behind them its twelve counts (48 bytes a team): after a round the ranks that played it get samples x the round's end.
+// No global traffic between the rounds, nothing of the env written.
+template <class Dealer>
+__device__ __forceinline__ void playout_halving_body(int64_t n, u64 pseed, u64 offset, u32 ends, u32 samples, u32 lg, u32 seats,
+                                                     const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                                     const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                                     const u64 *__restrict__ gkey, const typename Dealer::Extra *__restrict__ extra,
+                                                     int4 *__restrict__ sum_out, int4 *__restrict__ count_out, uint8_t *__restrict__ action_out) {
+    static_assert(Dealer::has_worlds, "halving runs in dealt worlds");
+    constexpr u32 INTS = TAROK_PLAYOUT_RANKS * 5;       // a team's block: [12][4] sums, [12] counts
+    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> TK_PO_MIN_LG) * INTS];
+    __shared__ typename Dealer::Record world;
+    // what only the epilogue needs waits in LDS — the launch's pointers and a flag byte per team (1: in play, 2: takes part):
+    // the item loop runs at the scalar registers' limit, and pointers and lane masks held across the rounds would spill
+    struct Epilogue { int4 *sum, *count; uint8_t *action; const u64 *gkey; int64_t n; };
+    __shared__ Epilogue epilogue;
+    __shared__ uint8_t flags[TK_BLOCK >> TK_PO_MIN_LG];
+    if (threadIdx.x == 0) epilogue = {sum_out, count_out, action_out, gkey, n};
+    const u32 worlds = ends >> 24 ? ends >> 24 : ends >> 16 ? ends >> 16 : ends >> 8 ? ends >> 8 : ends;      // the last round's end
+    const PlayoutTeam t(lg, worlds);
+    const int64_t g = t.g;
+    int *row = t.zero_rows<INTS>(sums);
+    ulonglong2 a = {0, 0}, b = {0, 0};
+    CardPosition p;
+    u64 ebase = 0;
+    u32 alive = 0;
+    if (g < n) {
+        a = s01[g]; b = s23[g];
+        Game g0;
+        unpack(g0, a.x, a.y, b.x, b.y);
+        p = card_position(g0, seat_sets, seats, g);
+        if (p.takes_part) {
+            alive = (1u << (u32)popc64(p.legal)) - 1u;
+            ebase = ((u64)cnt[g].episode << 28) | ((u64)p.played << 22);
+            const typename Dealer::Extra word = game_word(extra, g);
+            for (u32 w = t.lane; w < worlds; w += t.L) {
+                Game d = g0;
+                Dealer::deal(d, p.mover, game_key(pseed, offset + (u64)g, Dealer::world_tag | ebase | (u64)w), word);
+                world.store(t.slot0 + w, d);
+            }
+        }
+    }
+    if (t.lane == 0) flags[t.team] = (uint8_t)((u32)p.in_play | (u32)p.takes_part << 1);
+    __syncthreads();
+    u32 e0 = 0;
+    for (u32 rest = ends; rest; rest >>= 8) {           // one round per byte of `ends`: launch-uniform
+        const u32 e1 = rest & 255u;
+        const u32 on = (alive & (alive - 1u)) != 0u || e0 == 0u ? alive : 0u;      // a game with one card alive plays no further round
+        for (u32 j = t.lane; j < TAROK_PLAYOUT_RANKS; j += t.L)
+            if ((on >> j) & 1u) row[TAROK_PLAYOUT_RANKS * 4 + j] = (int)(e1 * samples);
+        const u32 per_card = (e1 - e0) * samples, items = (u32)__popc(on) * per_card;
+        for (u32 i = t.lane; i < items; i += t.L) {
+            u32 q = i / per_card, s = i - q * per_card, w = s / samples;
+            s -= w * samples;
+            w += e0;
+            const u32 j = kth_bit_word(on, 0u, q), c = kth_bit(p.legal, j);
+            u64 pkey = game_key(pseed, offset + (u64)g, Dealer::item_tag | ebase | ((u64)c << 16) | ((u64)w << 10) | (u64)s);
+            Game h;
+            unpack(h, a.x, a.y, b.x, b.y);
+            world.load(t.slot0 + w, h);
+            add_scores(row, j, playout_from(h, c, pkey, p.played));
+        }
+        __syncthreads();
+        if (rest >> 8) {                                // not the last round: the better half stays (one card stays one card)
+            alive = halve_alive(row, alive, p.mover);
+            __syncthreads();
+        }
+        e0 = e1;
+    }
+    const Epilogue o = epilogue;
+    if (g >= o.n) return;
+    if (o.sum)
+        for (u32 r = t.lane; r < TAROK_PLAYOUT_RANKS; r += t.L) o.sum[g * TAROK_PLAYOUT_RANKS + r] = reinterpret_cast<const int4 *>(row)[r];
+    if (o.count && t.lane < 3u) o.count[g * 3 + t.lane] = reinterpret_cast<const int4 *>(row)[TAROK_PLAYOUT_RANKS + t.lane];
+    if (o.action && t.lane == 0) {
+        const u32 f = flags[t.team];
+        u32 act = 255;
+        if (f & 2u) act = kth_bit(p.legal, best_alive(row, alive, p.mover));
+        else if (f & 1u) act = policy_action(o.gkey[g], p.played, p.legal);
+        o.action[g] = (uint8_t)act;
+    }
+}
+
+#define TK_HALVING_KERNEL(NAME, DEALER, WORDS_T)                                                                                   \
+    TK_KERNEL(TK_BLOCK, 128) void NAME(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 ends, u32 samples, u32 lg,          \
+                                      u32 seats, const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,         \
+                                      const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,                         \
+                                      const u64 *__restrict__ gkey, const WORDS_T *__restrict__ words, int4 *__restrict__ sum_out,  \
+                                      int4 *__restrict__ count_out, uint8_t *__restrict__ action_out) {                             \
+        TK_VGPR_TOP(128, 127);                                                                                                      \
+        playout_halving_body<DEALER>(n, pseed, offset, ends, samples, lg, seats, seat_sets, s01, s23, cnt, gkey, words, sum_out, \
+                                     count_out, action_out);                                                                        \
+    }
+TK_HALVING_KERNEL(k_playout_halving_det, DealUnseen, NoWord)         // words: nullptr
+TK_HALVING_KERNEL(k_playout_halving_voids, DealVoids, u32)
+TK_HALVING_KERNEL(k_playout_halving_hidden, DealHidden, u64)
+#undef TK_HALVING_KERNEL
+
 // tarok_playout_bids, first launch: the deal tarok_reset(env, episode, deals, ...) would make, one lane per game, left as
 // (h0, h1, h2, h3, talon ids) in the env's bidding buffer [5][n] — the 54-key sorting network has a kernel of its own so
 // that the playout kernel keeps its registers.  A deals row that k_reset would flag leaves five zeros: no viewer, zero sums.
@@ -1960,6 +2065,85 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_targets(int64_t n, const int4 *__restric
                     u32 c = (u32)__builtin_ctzll(rest);
                     rest &= rest - 1;
                     rows[tid * 64 + c] = __builtin_bit_cast(uint16_t, (__bf16)(e[j] / sum));
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const u32 pieces = (u32)(n - g0 < TK_BLOCK ? n - g0 : TK_BLOCK) * 8u;
+#pragma unroll
+    for (u32 i = 0; i < 8; i++) {
+        u32 p = i * TK_BLOCK + tid;
+        if (p < pieces) out[g0 * 8 + p] = rows4[p];
+    }
+}
+
+// tarok_playout_targets_counts: k_playout_targets for sums with a count per card (a halving launch's): the same lane per
+// game, LDS row and 16-byte stores.  m_j = float(sum) / float(count) is one float32 division, the maximum is taken over the
+// ranks with count > 0 and a rank without playouts gets 0.  tau = 0 compares the integer sums of the ranks of maximal count
+// (equal counts: comparing sums is comparing means, exactly), so on a halving launch's output it is that launch's card.
+TK_KERNEL(TK_BLOCK, 128) void k_playout_targets_counts(int64_t n, const int4 *__restrict__ sums, const int4 *__restrict__ counts,
+                                                     const u64 *__restrict__ obs, float tau, u32 seats,
+                                                     const uint8_t *__restrict__ seat_sets, uint4 *__restrict__ out) {
+    TK_VGPR_TOP(128, 127);
+    __shared__ __attribute__((aligned(16))) uint16_t rows[TK_BLOCK * 64];
+    const u32 tid = threadIdx.x;
+    const int64_t g0 = (int64_t)blockIdx.x * TK_BLOCK, g = g0 + tid;
+    uint4 *rows4 = reinterpret_cast<uint4 *>(rows);
+#pragma unroll
+    for (u32 i = 0; i < 8; i++) rows4[i * TK_BLOCK + tid] = make_uint4(0u, 0u, 0u, 0u);
+    __syncthreads();
+    if (g < n) {
+        const u64 word = obs[g], legal = word & TAROK_OBS_MASK;
+        const u32 s = (u32)(word >> TAROK_OBS_SEAT_SHIFT) & 3u;
+        const u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+        if (legal != 0 && ((set >> s) & 1u)) {
+            u32 nl = (u32)popc64(legal);
+            nl = nl < TAROK_PLAYOUT_RANKS ? nl : TAROK_PLAYOUT_RANKS;
+            int v[TAROK_PLAYOUT_RANKS], cn[TAROK_PLAYOUT_RANKS];
+#pragma unroll
+            for (u32 j = 0; j < TAROK_PLAYOUT_RANKS; j++) {
+                int4 q = sums[g * TAROK_PLAYOUT_RANKS + j];
+                v[j] = s == 0 ? q.x : s == 1 ? q.y : s == 2 ? q.z : q.w;
+            }
+#pragma unroll
+            for (u32 j = 0; j < TAROK_PLAYOUT_RANKS / 4; j++) {
+                int4 q = counts[g * (TAROK_PLAYOUT_RANKS / 4) + j];
+                cn[4 * j] = q.x; cn[4 * j + 1] = q.y; cn[4 * j + 2] = q.z; cn[4 * j + 3] = q.w;
+            }
+            int cmax = 0;
+#pragma unroll
+            for (u32 j = 0; j < TAROK_PLAYOUT_RANKS; j++) {
+                cn[j] = j < nl && cn[j] > 0 ? cn[j] : 0;
+                cmax = cn[j] > cmax ? cn[j] : cmax;
+            }
+            float m[TAROK_PLAYOUT_RANKS], mtop = 0.f;
+            int top = 0;
+            u32 best = TAROK_PLAYOUT_RANKS, any = 0;         // best: the smallest rank at the maximal sum among the ranks of maximal count
+#pragma unroll
+            for (u32 j = 0; j < TAROK_PLAYOUT_RANKS; j++) {
+                const bool on = cn[j] > 0;
+                m[j] = on ? (float)v[j] / (float)cn[j] : 0.f;
+                mtop = on && (!any || m[j] > mtop) ? m[j] : mtop;
+                any |= (u32)on;
+                const bool up = on && cn[j] == cmax && (best == TAROK_PLAYOUT_RANKS || v[j] > top);
+                top = up ? v[j] : top;
+                best = up ? j : best;
+            }
+            float e[TAROK_PLAYOUT_RANKS], sum = 0.f;
+#pragma unroll
+            for (u32 j = 0; j < TAROK_PLAYOUT_RANKS; j++) {
+                float x = tau > 0.f ? expf((m[j] - mtop) / tau) : (j == best ? 1.f : 0.f);
+                e[j] = cn[j] > 0 ? x : 0.f;
+                sum += e[j];
+            }
+            u64 rest = legal;
+#pragma unroll
+            for (u32 j = 0; j < TAROK_PLAYOUT_RANKS; j++) {
+                if (j < nl) {
+                    u32 c = (u32)__builtin_ctzll(rest);
+                    rest &= rest - 1;
+                    if (any) rows[tid * 64 + c] = __builtin_bit_cast(uint16_t, (__bf16)(e[j] / sum));
                 }
             }
         }
@@ -4645,6 +4829,31 @@ static int launch_playout_cards(Kernel kernel, tarok_env *e, int worlds, int sam
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }
+
+// One halving launch: the schedule is read here and goes to the kernel as its cumulative ends, a byte a round; lg is the
+// card launches' at (all worlds) x samples, so the team's worlds fit its slots.  `words`: the dealer's per-game words (a
+// typed null for the det kind).
+template <class Kernel, class Word>
+static int launch_playout_halving(Kernel kernel, tarok_env *e, int rounds, const int *round_worlds, int samples, uint64_t salt, int seats,
+                                  const uint8_t *seats_per_game, int32_t *sum_out, int32_t *count_out, uint8_t *action_out, void *stream,
+                                  const Word *words) {
+    if (rounds < 1 || rounds > TAROK_PLAYOUT_MAX_ROUNDS || !round_worlds) return TAROK_EINVAL;
+    int worlds = 0;
+    u32 ends = 0;
+    for (int r = 0; r < rounds; r++) {
+        if (round_worlds[r] < 1 || round_worlds[r] > TAROK_PLAYOUT_MAX_WORLDS - worlds) return TAROK_EINVAL;
+        worlds += round_worlds[r];
+        ends |= (u32)worlds << (8 * r);
+    }
+    if (!playout_args_ok(e, worlds, samples, seats) || (!sum_out && !count_out && !action_out)) return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    const u32 lg = playout_lg(TK_PO_MIN_LG, worlds * samples);
+    hipLaunchKernelGGL(kernel, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset, ends,
+                       (u32)samples, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, e->gkey, words,
+                       reinterpret_cast<int4 *>(sum_out), reinterpret_cast<int4 *>(count_out), action_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
 }
 
 int tarok_playout_cards(tarok_env *e, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game, int32_t *sum_out,
@@ -4847,6 +5056,20 @@ int tarok_playout_cards_hidden(tarok_env *e, int worlds, int samples, uint64_t s
                                const uint64_t *played, int32_t *sum_out, uint8_t *action_out, void *stream) {
     return launch_playout_cards<true>(k_playout_hidden, e, worlds, samples, salt, seats, seats_per_game, sum_out, action_out, stream,
                                       (const u64 *)played);
+}
+
+int tarok_playout_cards_halving(tarok_env *e, int kind, const void *words, int rounds, const int *round_worlds, int samples, uint64_t salt,
+                                int seats, const uint8_t *seats_per_game, int32_t *sum_out, int32_t *count_out, uint8_t *action_out,
+                                void *stream) {
+    if (kind < TAROK_NET_WORLDS_DET || kind > TAROK_NET_WORLDS_HIDDEN || (kind == TAROK_NET_WORLDS_DET) != !words) return TAROK_EINVAL;
+    if (kind == TAROK_NET_WORLDS_VOIDS)
+        return launch_playout_halving(k_playout_halving_voids, e, rounds, round_worlds, samples, salt, seats, seats_per_game, sum_out, count_out,
+                                      action_out, stream, (const u32 *)words);
+    if (kind == TAROK_NET_WORLDS_HIDDEN)
+        return launch_playout_halving(k_playout_halving_hidden, e, rounds, round_worlds, samples, salt, seats, seats_per_game, sum_out,
+                                      count_out, action_out, stream, (const u64 *)words);
+    return launch_playout_halving(k_playout_halving_det, e, rounds, round_worlds, samples, salt, seats, seats_per_game, sum_out, count_out,
+                                  action_out, stream, (const NoWord *)nullptr);
 }
 
 extern "C++" {
@@ -5083,6 +5306,18 @@ int tarok_playout_targets(tarok_env *e, const int32_t *sums, const uint64_t *obs
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_playout_targets, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, reinterpret_cast<const int4 *>(sums),
                        (const u64 *)obs, den, (u32)seats, seats_per_game, reinterpret_cast<uint4 *>(target_out));
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int tarok_playout_targets_counts(tarok_env *e, const int32_t *sums, const int32_t *counts, const uint64_t *obs, float tau, int seats,
+                                 const uint8_t *seats_per_game, void *target_out, void *stream) {
+    if (!e || !sums || !counts || !obs || !target_out || !(tau >= 0.f) || tau > 3.0e38f || seats < 0 || seats > 15) return TAROK_EINVAL;
+    if (tau > 0.f && tau < 1.17549435e-38f) return TAROK_EINVAL;      // the kernel's divisor: a normal float32 number, or 0
+    HIPCHK(hipSetDevice(e->device));
+    hipLaunchKernelGGL(k_playout_targets_counts, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
+                       reinterpret_cast<const int4 *>(sums), reinterpret_cast<const int4 *>(counts), (const u64 *)obs, tau, (u32)seats,
+                       seats_per_game, reinterpret_cast<uint4 *>(target_out));
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }

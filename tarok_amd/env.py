@@ -378,6 +378,31 @@ class TarokVecEnv:
         Outputs, `seats` / `seats_per_game`, `salt` and the read-only contract: as for playout_cards."""
         return self._cards(worlds, samples, salt, seats, seats_per_game, sum_out, action_out)
 
+    def playout_cards_halving(self, round_worlds, samples=1, *, voids=False, hidden=False, words=None, salt=0, seats=15, seats_per_game=None,
+                              sum_out=None, count_out=None, action_out=None):
+        """playout_cards_fair with sequential halving (tarok_playout_cards_halving), in one launch: round r plays the cards
+        still alive `samples` times in each of round_worlds[r] fresh worlds (1..4 rounds, sum(round_worlds) <= 64), and
+        after every round but the last the better half by the mover's sum stays alive, ties to the lower rank.  voids /
+        hidden / words: the worlds' kind and the caller's scratch tensor for its words, as in playout_cards_fair; the worlds
+        and the playouts' keys are that launch's, so round_worlds=(W,) gives its bytes.
+        Returns (sum [N,12,4] int32, count [N,12] int32 — the playouts behind every row, 0 beyond the legal cards and for
+        games that do not take part —, action [N] uint8: the first card at the maximum among the cards alive at the end)."""
+        P.one_world_kind(bool(voids), bool(hidden))
+        kind = "voids" if voids else "hidden" if hidden else "det"
+        schedule = P.check_halving(round_worlds)
+        if kind in P.WORDS_DTYPE and not self.history:
+            raise ValueError("%s=True goes with the play history: TarokVecEnv(history=True)" % kind)
+        words = (self.shown_voids if voids else self.played_cards)(words) if kind in P.WORDS_DTYPE else None
+        with torch.cuda.device(self.device):
+            sum_out = self._empty(sum_out, (self.n, K.PLAYOUT_RANKS, 4), torch.int32)
+            count_out = self._empty(count_out, (self.n, K.PLAYOUT_RANKS), torch.int32)
+            action_out = self._empty(action_out, self.n, torch.uint8)
+            _native.check(self.L.tarok_playout_cards_halving(self._h, P.WORLDS.index(kind), self._p(words), len(schedule),
+                                                             (C.c_int * len(schedule))(*schedule), int(samples), int(salt) & ((1 << 64) - 1),
+                                                             int(seats), self._p(self._seat_sets(seats_per_game)), self._p(sum_out),
+                                                             self._p(count_out), self._p(action_out), self._stream()))
+        return sum_out, count_out, action_out
+
     def playout_net_scratch(self, worlds):
         """The scratch tensor of playout_cards_net at `worlds` (uint8, tarok_playout_net_scratch bytes), cached on the env
         per `worlds`: a caller that captures the launch into a graph asks for it BEFORE the capture."""
@@ -779,6 +804,17 @@ class TarokVecEnv:
             target_out = self._empty(target_out, (self.n, 64), torch.bfloat16)
             _native.check(self.L.tarok_playout_targets(self._h, self._p(sums), self._p(obs_words), int(playouts), float(tau), int(seats),
                                                        self._p(self._seat_sets(seats_per_game)), self._p(target_out), self._stream()))
+        return target_out
+
+    def playout_targets_counts(self, sums, counts, obs_words, tau, seats=15, seats_per_game=None, target_out=None):
+        """playout_targets for sums with a count per card (tarok_playout_targets_counts): the softmax is over (the mover's
+        sum) / (the card's count) / tau on the cards with a count, 0 on a card without playouts; tau = 0: 1.0 at the first
+        card at the maximal mean among the cards of maximal count — on playout_cards_halving's (sum, count) that
+        launch's card.  counts [N,12] int32.  Stream-ordered; allocates nothing when target_out is given."""
+        with torch.cuda.device(self.device):
+            target_out = self._empty(target_out, (self.n, 64), torch.bfloat16)
+            _native.check(self.L.tarok_playout_targets_counts(self._h, self._p(sums), self._p(counts), self._p(obs_words), float(tau), int(seats),
+                                                              self._p(self._seat_sets(seats_per_game)), self._p(target_out), self._stream()))
         return target_out
 
     def observe(self, out=None):

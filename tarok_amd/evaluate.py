@@ -244,16 +244,18 @@ def _network_cards(weights, opponent, temperature, epsilon):
     return make
 
 
-def _playout_cards(launch, words_dtype=None):
+def _playout_cards(launch, words_dtype=None, counts=False):
     """A card player of two launches per lock-step: launch(env, seats, words, sums, row) — a playout launch that leaves
     its player's card on the pass's seats and the Bot's on the others in `row` — and one tarok_step that plays it.
-    sums [N, K.PLAYOUT_RANKS, 4] i32 is the launch's sum_out; words [N], if a dtype is given, its history words."""
+    sums [N, K.PLAYOUT_RANKS, 4] i32 is the launch's sum_out; words [N], if a dtype is given, its history words; counts:
+    the launch also takes count_out=[N, K.PLAYOUT_RANKS] i32 (a halving launch)."""
     def make(env):
         sums = _empty(env, (env.n, K.PLAYOUT_RANKS, 4), torch.int32)
         words = _empty(env, env.n, words_dtype) if words_dtype is not None else None
+        more = dict(count_out=_empty(env, (env.n, K.PLAYOUT_RANKS), torch.int32)) if counts else {}
 
         def cards(env, t, seats, row):
-            launch(env, seats, words, sums, row)
+            launch(env, seats, words, sums, row, **more)
             env.step(row, auto_reset=False)
         return cards
     return make
@@ -373,7 +375,7 @@ def _bid_args(bidding, mix):
 
 def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None, voids=False, exchange=None,
                     hidden=False, bidding=None, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None,
-                    net_seats=15, net_worlds="det", net_depth=None, net_value_scale=70.0):
+                    net_seats=15, net_worlds="det", net_depth=None, net_value_scale=70.0, halving=None):
     """_play_passes_mode with the Monte-Carlo player (TarokVecEnv.playout_cards) in the network's place: per lock-step
     one playout launch with the pass's seat set — tarok_playout_cards (open hands) for worlds=None,
     tarok_playout_cards_det (the fair player: `worlds` re-deals of the unseen cards) otherwise — whose action_out holds
@@ -395,9 +397,10 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     above.  (voids=True / hidden=True together with net= keep raising: net_worlds is the way in.)
     net_depth=D (with net): the launch is playout_cards_net_value at depth D and net_value_scale in the same worlds — the
     playouts stop at the player's D-th next decision and take the value head's estimate; None: the calls as they were.
+    halving=(w0, ..): the launch is tarok_playout_cards_halving with that schedule, in the worlds voids / hidden name.
     inspect: as in _play_passes_mode."""
     player = playout.card_player(samples, worlds, voids, hidden, net is not None, net_seats, net_worlds, net_depth, net_value_scale, salt,
-                                 front=exchange is not None or bidding is not None)
+                                 front=exchange is not None or bidding is not None, **({} if halving is None else dict(halving=halving)))
     if net is not None:
         if samples is not None:
             raise ValueError("net= runs one playout per (card, world): samples is not taken (pass None)")
@@ -407,8 +410,8 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     if bidding is not None and worlds is None:
         raise ValueError("bidding=(W, S) is the fair player's front end: give worlds= as well")
     bidding = _bid_args(bidding, mix)
-    cards = _playout_cards(lambda env, seats, words, sums, row: player.launch(env, net, dict(seats=seats), words, sums, row),
-                           words_dtype=player.words_dtype)
+    cards = _playout_cards(lambda env, seats, words, sums, row, **more: player.launch(env, net, dict(seats=seats), words, sums, row, **more),
+                           words_dtype=player.words_dtype, **({} if halving is None else dict(counts=True)))
     front = _front(inspect is not None, bid=None if bidding is None else _bid_front(bidding, salt, threshold, contracts, pass_value),
                    exchange=None if exchange is None else _exchange_front(worlds, samples, exchange, salt))
     return _passes(n_games, episodes, front, cards, inspect, device=device, seed=seed, mix=mix, history=player.needs_history)
@@ -417,7 +420,7 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
 def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None,
                             voids=False, exchange=None, hidden=False, bidding=None, threshold=0,
                             contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None, net_seats=15, net_worlds="det",
-                            net_depth=None, net_value_scale=70.0):
+                            net_depth=None, net_value_scale=70.0, halving=None):
     """evaluate_vs_bot with the open-hand Monte-Carlo player in the network's place: a strong reference player that needs
     no training.  On its seat it plays, at every move, the legal card with the best summed score over `samples` Bot
     playouts of each legal card (tarok_playout_cards; `salt` varies their draws).  The playouts see the TRUE hidden
@@ -452,13 +455,17 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
     head's estimate times net_value_scale (points per unit of the head: 1 / the learner's reward_scale) for the rest of the
     game (tarok_playout_cards_net_value, in the worlds of net_worlds) — at D = 1 at most 6 cards per playout where a fresh
     deal takes 47.  None (the default): the playouts run to the last card, the calls as they were.
+    halving=(w0, w1, ..) (1..4 positive world counts; `worlds` None or their sum; with voids / hidden as worlds=W is; not with
+    net=, exchange or bidding): the fair player spends its worlds by sequential halving (tarok_playout_cards_halving) —
+    every legal card in the first w0 worlds, then the better half in w1 fresh ones, and so on: the finalists are compared
+    over all the worlds at a fraction of the playouts.  None (the default): the calls as they were.
     The same five duplicate passes (PASS_SEATS) on an env of its own; returns duplicate_advantage's dict, `policy_mean`
     being the playout player's.  inspect (tests): a list that receives one dict per pass, as in _play_passes_mode."""
     return duplicate_advantage(_playout_passes(samples, n_games, episodes, seed, mix, device, salt=salt, inspect=inspect,
                                                worlds=worlds, voids=voids, exchange=exchange, hidden=hidden, bidding=bidding,
                                                threshold=threshold, contracts=contracts, pass_value=pass_value, net=net,
                                                net_seats=net_seats, net_worlds=net_worlds, net_depth=net_depth,
-                                               net_value_scale=net_value_scale))
+                                               net_value_scale=net_value_scale, **({} if halving is None else dict(halving=halving))))
 
 
 def _front_cards(cards):

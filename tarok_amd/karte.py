@@ -72,6 +72,7 @@ PLAYOUT_MAX_SAMPLES = 1024
 PLAYOUT_MAX_WORLDS = 64   # tarok_playout_cards_det: re-deals of the unseen cards per launch
 PLAYOUT_MAX_DEPTH = 12   # tarok_playout_cards_net_value: viewer decisions before the stop (12: never stops)
 PLAYOUT_FRONT_MAX_DEPTH = 13   # tarok_playout_exchange_net_value / _bids_net_value: an item starts at 0 cards (13: never stops)
+PLAYOUT_MAX_ROUNDS = 4    # tarok_playout_cards_halving: rounds of a sequential-halving schedule
 PLAYOUT_NET_ITEM_BYTES = 48   # tarok_playout_cards_net: scratch bytes per (game, rank, world) (tarok_playout_net_scratch)
 EXCHANGE_MAX_SETS = 8     # tarok_playout_exchange: discard sets per talon group; sum_out has 6 * discard_sets rows per game
 BID_ROWS = 20             # tarok_playout_bids: rows of sum_out per viewer seat (19 options and one of padding)

@@ -12,7 +12,8 @@ from . import karte as K
 
 WORLDS = ("det", "voids", "hidden")               # the fair world kinds; the position is tarok_playout_cards_net_value's `kind`
 WORDS_DTYPE = dict(voids=torch.int32, hidden=torch.int64)      # the per-game words a kind reads: shown_voids() / played_cards()
-OPTIONS = ("samples", "worlds", "voids", "hidden", "exchange", "bidding", "net", "net_seats", "net_worlds", "net_depth", "net_value_scale")
+OPTIONS = ("samples", "worlds", "voids", "hidden", "exchange", "bidding", "net", "net_seats", "net_worlds", "net_depth", "net_value_scale",
+           "halving")
 
 
 def spelling(prefix="", pattern="%s", **other):
@@ -35,11 +36,21 @@ def check_depth(depth, value_scale, say=spelling(net_depth="depth", net_value_sc
         raise ValueError(say("{net_value_scale}: finite and > 0"))
 
 
+def check_halving(halving, say=spelling()):
+    """A sequential-halving schedule as a tuple: 1..K.PLAYOUT_MAX_ROUNDS positive ints, at most K.PLAYOUT_MAX_WORLDS in all."""
+    ok = isinstance(halving, (tuple, list)) and 1 <= len(halving) <= K.PLAYOUT_MAX_ROUNDS and \
+        all(isinstance(w, numbers.Integral) and not isinstance(w, bool) and w >= 1 for w in halving)
+    if not ok or sum(halving) > K.PLAYOUT_MAX_WORLDS:
+        raise ValueError(say("{halving}: 1..%d positive world counts, one per round, at most %d in all" % (K.PLAYOUT_MAX_ROUNDS, K.PLAYOUT_MAX_WORLDS)))
+    return tuple(int(w) for w in halving)
+
+
 class CardPlayer(collections.namedtuple("CardPlayer", "kind worlds samples net net_seats depth value_scale salt")):
     """kind: "open" (the true hands) or one of WORLDS; worlds as the door gave it (None or 0 for "open"), samples per
     (card, world); net: the playouts are played by a network on net_seats (a set 0..15, or "own": the launch's own seats),
     stopped at the viewer's depth-th decision (None: never) with the value head at value_scale points per unit."""
     __slots__ = ()
+    halving = None                                    # (a HalvingPlayer's schedule)
 
     needs_history = property(lambda self: self.kind in WORDS_DTYPE)
     words_dtype = property(lambda self: WORDS_DTYPE.get(self.kind))
@@ -64,12 +75,40 @@ class CardPlayer(collections.namedtuple("CardPlayer", "kind worlds samples net n
         return env.playout_cards_net_value(weights, self.worlds, self.depth, self.value_scale, **out)
 
 
+class HalvingPlayer(collections.namedtuple("HalvingPlayer", CardPlayer._fields + ("halving",))):
+    """A CardPlayer of a fair kind played by the Bot whose launch is tarok_playout_cards_halving: halving = the worlds of
+    every round, worlds their sum.  Its rows have a count per card (count_out), not one divisor: the targets are
+    tarok_playout_targets_counts'."""
+    __slots__ = ()
+
+    needs_history, words_dtype = CardPlayer.needs_history, CardPlayer.words_dtype
+
+    def prepare(self, env):
+        pass
+
+    def launch(self, env, weights, sets, words, sum_out, action_out, count_out=None):
+        """As CardPlayer.launch; count_out: the caller's [N,12] int32 tensor (None: a new one per call).  Returns (sum,
+        count, action)."""
+        return env.playout_cards_halving(self.halving, self.samples, voids=self.kind == "voids", hidden=self.kind == "hidden", words=words,
+                                         salt=self.salt, sum_out=sum_out, count_out=count_out, action_out=action_out, **sets)
+
+
 def card_player(samples=None, worlds=None, voids=False, hidden=False, net=False, net_seats=15, net_worlds="det", net_depth=None,
-                net_value_scale=70.0, salt=0, front=False, fused=True, history=None, own=True, say=spelling()):
+                net_value_scale=70.0, salt=0, front=False, fused=True, history=None, own=True, say=spelling(), halving=None):
     """The one validator of a card player's options, in evaluate_playout_vs_bot's names: a CardPlayer, or a ValueError in
     the door's words (say: spelling()).  samples None: 1.  front: the door also asked for a playout-valued exchange or
     bidding.  fused: the door's policy is the fused one.  history: whether the env at hand keeps the play history (None:
-    the door makes its env as needs_history says).  own: the door takes net_seats="own"."""
+    the door makes its env as needs_history says).  own: the door takes net_seats="own".
+    halving: a tuple of 1..4 positive world counts, one per round of sequential halving (a HalvingPlayer): it names the worlds
+    itself — `worlds` None (or 0) or their sum —, goes with voids / hidden as worlds does, and is not built for net=, the
+    exchange, the bidding or open hands."""
+    if halving is not None:
+        halving = check_halving(halving, say)
+        if net or front:
+            raise ValueError(say("{halving}= is the Bot-played card launch's: no {net}, {exchange} or {bidding}"))
+        if worlds and int(worlds) != sum(halving):
+            raise ValueError(say("{halving}= names the worlds of every round: {worlds} is optional and must be their sum"))
+        worlds = sum(halving)
     if net_depth is not None:
         if not net:
             raise ValueError(say("{net_depth} stops the network's playouts: it goes with {net}="))
@@ -100,4 +139,5 @@ def card_player(samples=None, worlds=None, voids=False, hidden=False, net=False,
     kind = "open" if not worlds else "voids" if voids else "hidden" if hidden else net_worlds
     if kind in WORDS_DTYPE and history is not None and not history:
         raise ValueError(say("the %s worlds read the play history: TarokVecEnv(history=True)" % kind))
-    return CardPlayer(kind, worlds, samples, bool(net), net_seats, net_depth, float(net_value_scale), int(salt))
+    player = CardPlayer(kind, worlds, samples, bool(net), net_seats, net_depth, float(net_value_scale), int(salt))
+    return player if halving is None else HalvingPlayer(*player, halving)

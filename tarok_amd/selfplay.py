@@ -296,6 +296,10 @@ class SelfPlay:
     the learner's own value head there, at value_scale = 1 / reward_scale — the head's unit turned back into points
     (tarok_playout_cards_net_value in the worlds of net_worlds).  The call sits inside the captured rollout
     on the live weights like the launch above; at D = 1 a playout is at most 6 cards long.  Without the key: as before.
+    teacher = dict(halving=(w0, w1, ..), samples=S, tau=, every=, salt=, voids= | hidden=): the Bot-played worlds are spent by
+    sequential halving (tarok_playout_cards_halving: 1..4 rounds, `worlds` omitted or their sum, samples optional: 1) and the
+    rows come from tarok_playout_targets_counts on the launch's counts — both inside the captured rollout, the counts
+    buffer allocated before capture.  Not with net=True.
 
     front = dict(bid=, exchange=, contracts=, margin=, pass_value=, every=1): the games auto-reset swaps in are bid and
     exchanged by the heads instead of the Bot (TarokVecEnv.front_lines).  bid / exchange: six tensors each
@@ -328,24 +332,27 @@ class SelfPlay:
                 raise ValueError("learner_seats: a seat set 0..15 or a [N] uint8 tensor of sets")
         self.teacher, self._player, self.distill_coef = None, None, float(distill_coef)
         if teacher is not None:                       # the card player is playout.card_player's; tau and every are the teacher's own
-            unknown = set(teacher) - {"worlds", "samples", "tau", "every", "salt", "voids", "hidden", "net", "net_seats", "net_worlds", "depth"}
+            unknown = set(teacher) - {"worlds", "samples", "tau", "every", "salt", "voids", "hidden", "net", "net_seats", "net_worlds", "depth",
+                                      "halving"}
             net = bool(teacher.get("net", False))
-            if unknown or ("samples" not in teacher and not net):
-                raise ValueError("teacher: dict(worlds=W, samples=S, tau=tau, every=k, salt=...), samples required; unknown keys %s" % sorted(unknown))
+            if unknown or ("samples" not in teacher and not net and "halving" not in teacher):
+                raise ValueError("teacher: dict(worlds=W, samples=S, tau=tau, every=k, salt=...) or dict(halving=(w0, ..), ...): samples "
+                                 "required unless net=True or halving= is given; unknown keys %s" % sorted(unknown))
             if "net_seats" in teacher and not net:
                 raise ValueError("teacher: net_seats names the network's seats inside the playouts: it goes with net=True")
             p = playout.card_player(int(teacher.get("samples", 1)), int(teacher.get("worlds", 0)), bool(teacher.get("voids", False)),
                                     bool(teacher.get("hidden", False)), net, int(teacher.get("net_seats", 15)), teacher.get("net_worlds", "det"),
                                     teacher.get("depth"), 1.0 / reward_scale if reward_scale else 0.0, int(teacher.get("salt", 0)),
                                     fused=(hidden == 256) if fused is None else bool(fused), history=getattr(env, "history", False), own=False,
-                                    say=playout.spelling("teacher: ", net_depth="depth", net_value_scale="1 / reward_scale"))
+                                    say=playout.spelling("teacher: ", net_depth="depth", net_value_scale="1 / reward_scale"),
+                                    **({"halving": teacher["halving"]} if "halving" in teacher else {}))
             tau, every = float(teacher.get("tau", 1.0)), int(teacher.get("every", 1))
             if not (every >= 1 and 0.0 <= tau < float("inf")):
                 raise ValueError("teacher: tau >= 0 and finite, every >= 1")
             self._player = p                          # self.teacher: the same player as the dict it has always been
             self.teacher = dict(worlds=p.worlds, samples=p.samples, tau=tau, every=every, salt=p.salt, voids=p.kind == "voids" and not net,
                                 hidden=p.kind == "hidden" and not net, net=net, net_seats=p.net_seats, net_worlds=p.kind if net else "det",
-                                **({} if p.depth is None else dict(depth=p.depth)))
+                                **({} if p.depth is None else dict(depth=p.depth)), **({} if p.halving is None else dict(halving=p.halving)))
         elif distill_coef:
             raise ValueError("distill_coef weighs the playout teacher's term: pass teacher= as well")
         self.env = env
@@ -586,7 +593,7 @@ class SelfPlay:
     def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None, greedy=False, temperature=None, epsilon=0.0,
                  versus_playout=None, playout_worlds=None, playout_voids=False, playout_exchange=None,
                  playout_hidden=False, playout_bidding=None, pass_value=False, playout_net=False, playout_net_seats=15,
-                 playout_net_worlds="det", playout_net_depth=None):
+                 playout_net_worlds="det", playout_net_depth=None, playout_halving=None):
         """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
         weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
         and on the SAME deals on every rank (seed 0, game offset 0, whatever the training env's are): the figures of
@@ -621,10 +628,16 @@ class SelfPlay:
         playout_net with playout_voids / playout_hidden keeps raising: playout_net_worlds is the way in.
         playout_net_depth=D (with playout_net; 1..12): those playouts stop at the player's D-th next decision and take this
         learner's value head there, in points (evaluate_playout_vs_bot(net_depth=D, net_value_scale=1 / reward_scale));
-        None: they run to the last card, as before."""
+        None: they run to the last card, as before.
+        playout_halving=(w0, w1, ..) (with versus_playout=S; playout_worlds None or their sum; with playout_voids /
+        playout_hidden; not with playout_net, playout_exchange or playout_bidding): the fair player spends its worlds by
+        sequential halving (evaluate_playout_vs_bot(halving=...))."""
+        halving = {} if playout_halving is None else dict(halving=playout_halving)
         playout.card_player(versus_playout, playout_worlds, playout_voids, playout_hidden, bool(playout_net), playout_net_seats,
                             playout_net_worlds, playout_net_depth, front=playout_exchange is not None or playout_bidding is not None,
-                            say=playout.spelling(pattern="playout_%s", samples="versus_playout"))
+                            say=playout.spelling(pattern="playout_%s", samples="versus_playout"), **halving)
+        if playout_halving is not None and versus_playout is None:
+            raise ValueError("playout_halving goes with versus_playout=samples")
         if playout_bidding is not None and playout_worlds is None:
             raise ValueError("playout_bidding goes with playout_worlds=W")
         if playout_exchange is not None and playout_worlds is None:
@@ -662,7 +675,7 @@ class SelfPlay:
         return own, evaluate_playout_vs_bot(int(versus_playout), n_games, episodes, mix=mix, device=self.env.device_index,
                                             worlds=playout_worlds, voids=bool(playout_voids), exchange=playout_exchange,
                                             hidden=bool(playout_hidden), bidding=playout_bidding,
-                                            pass_value=pass_value)
+                                            pass_value=pass_value, **halving)
 
     def _alloc(self, T):
         n, dev = self.env.n, self.device
@@ -685,11 +698,19 @@ class SelfPlay:
             dtype = self._player.words_dtype            # the voids / played words of the teacher's worlds
             self._teach_words = None if dtype is None else torch.empty(n, dtype=dtype, device=dev)
             self._player.prepare(self.env)            # the net launch's scratch: allocated here, before any capture
+            if self._player.halving is not None:      # a halving teacher's playouts per card: its targets' divisors
+                self._teach_counts = torch.empty((n, K.PLAYOUT_RANKS), dtype=torch.int32, device=dev)
         self._graph = None
 
     def _teach(self, t):
         """The teacher's rows of lock-step t: one playout launch on the learner's seats from the env's current positions,
         one tarok_playout_targets on the words of that lock-step.  Stream-ordered, read-only on the env, no allocation."""
+        if self._player.halving is not None:          # one halving launch, one tarok_playout_targets_counts on its counts
+            self._player.launch(self.env, self._w, dict(seats_per_game=self._seats), self._teach_words, self._teach_sums, self._teach_act,
+                                count_out=self._teach_counts)
+            self.env.playout_targets_counts(self._teach_sums, self._teach_counts, self._buf["words"][t], self.teacher["tau"],
+                                            seats_per_game=self._seats, target_out=self._buf["teach"][t])
+            return
         self._player.launch(self.env, self._w, dict(seats_per_game=self._seats), self._teach_words, self._teach_sums, self._teach_act)
         self.env.playout_targets(self._teach_sums, self._buf["words"][t], self._player.playouts, self.teacher["tau"], seats_per_game=self._seats,
                                  target_out=self._buf["teach"][t])

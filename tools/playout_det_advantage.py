@@ -10,7 +10,12 @@ DESIGN 8.6), and beside its own figure the paired difference to the determinized
 --hidden: the player whose worlds also re-deal Klop's face-down talon and the declarer's discards instead
 (tests/playout_hidden_model.replay_pass), with the same paired difference.
 
-usage: playout_det_advantage.py [deals = 512] [worlds = 8] [samples = 2] [processes = 8] [--voids | --hidden]"""
+--halving a,b,c,d: the sequential-halving player instead (tests/playout_halving_model.replay_pass) at that
+schedule and `samples`, beside the uniform player at `worlds` (give the schedule's sum: the same finalists' worlds) and the
+uniform player at the nearest number of card-worlds (worlds = round(the schedule's items at twelve cards / 12)), with the
+paired differences halving minus each.
+
+usage: playout_det_advantage.py [deals = 512] [worlds = 8] [samples = 2] [processes = 8] [--voids | --hidden | --halving a,b,c,d]"""
 import json
 import multiprocessing
 import os
@@ -43,6 +48,12 @@ def one_deal_hidden(args):
     return [HM.replay_pass(SEED, MIX_BOT, i, 0, seats, worlds, samples)[1] for seats in PASS_SEATS]
 
 
+def one_deal_halving(args):
+    import playout_halving_model as HM
+    i, schedule, samples = args
+    return [HM.replay_pass(SEED, MIX_BOT, i, 0, seats, schedule, samples)[1] for seats in PASS_SEATS]
+
+
 def figures(rows, deals):
     scores = np.asarray(rows, np.int64).transpose(1, 0, 2)               # [5, deals, 4]
     k = np.arange(4)
@@ -53,7 +64,12 @@ def figures(rows, deals):
 
 
 def main():
-    argv = [a for a in sys.argv if a not in ("--voids", "--hidden")]
+    argv, schedule = list(sys.argv), None
+    if "--halving" in argv:
+        at = argv.index("--halving")
+        schedule = tuple(int(w) for w in argv[at + 1].split(","))
+        del argv[at:at + 2]
+    argv = [a for a in argv if a not in ("--voids", "--hidden")]
     voids, hidden = "--voids" in sys.argv, "--hidden" in sys.argv
     assert not (voids and hidden), "--voids or --hidden, not both"
     deals = int(argv[1]) if len(argv) > 1 else 512
@@ -76,6 +92,18 @@ def main():
             paired = (hdiff - diff).mean(axis=1)                         # per deal: hidden-aware minus determinized
             out = dict(deals=deals, worlds=worlds, samples=samples, hidden=hout, determinized=out,
                        paired_difference=float(paired.mean()), paired_stderr=float(paired.std(ddof=1) / np.sqrt(deals)))
+        if schedule:
+            assert sum(schedule) == worlds, "--halving: give worlds = the schedule's sum"
+            items, alive = 0, 12
+            for w in schedule:
+                items, alive = items + alive * w, max(1, (alive + 1) // 2)
+            near = max(1, round(items / 12.0))
+            hdiff, hout = figures(pool.map(one_deal_halving, [(i, schedule, samples) for i in range(deals)], chunksize=4), deals)
+            ndiff, nout = figures(pool.map(one_deal, [(i, near, samples) for i in range(deals)], chunksize=4), deals)
+            pair = lambda d: dict(paired_difference=float((hdiff - d).mean(axis=1).mean()),
+                                  paired_stderr=float((hdiff - d).mean(axis=1).std(ddof=1) / np.sqrt(deals)))
+            out = dict(deals=deals, samples=samples, halving=dict(schedule=list(schedule), card_worlds_at_12=items, **hout),
+                       uniform_full=dict(out, **pair(diff)), uniform_same_cost=dict(dict(worlds=near, card_worlds_at_12=12 * near), **nout, **pair(ndiff)))
     print(json.dumps(out))
 
 

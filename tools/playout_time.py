@@ -22,7 +22,16 @@ fresh deal every word is 0 and every game falls back: that ratio is the overhead
 (W, samples) on tarok_played_cards' words is timed beside tarok_playout_cards_det, with the ratio, and tarok_played_cards
 alone (default output then: profiles/playout_hidden_times.txt).
 
-usage: playout_time.py [out.txt = profiles/playout_times.txt] [games = 65536] [samples = 16] [--worlds W] [--voids | --hidden]"""
+--halving a,b,c,d[/a,b,c,d ...] (with --worlds W, W the schedules' sum): at every position tarok_playout_cards_halving at each
+schedule (the det kind, `samples` per world) is timed beside tarok_playout_cards_det at (W, samples), with the measured
+ratio next to the one the item count predicts for twelve legal cards (default output then:
+profiles/playout_halving_times.txt).  The dealing of all W worlds and the two barriers a round are not halved.
+--teacher (with --halving): also the rollout of DESIGN 8.5's table — SelfPlay.collect(48) at the same games, median of 5
+between device events — without a teacher, with teacher=dict(worlds=W, samples=...), with teacher=dict(halving=...) at
+every schedule, and the uniform teacher once more to show the session's spread.
+
+usage: playout_time.py [out.txt = profiles/playout_times.txt] [games = 65536] [samples = 16] [--worlds W] [--voids | --hidden]
+                       [--halving a,b,c,d[/...] [--teacher]]"""
 import json
 import os
 import statistics
@@ -41,15 +50,25 @@ if voids:
 hidden = "--hidden" in argv
 if hidden:
     argv.remove("--hidden")
+teacher = "--teacher" in argv
+if teacher:
+    argv.remove("--teacher")
+halving = []
+if "--halving" in argv:
+    at = argv.index("--halving")
+    halving = [tuple(int(w) for w in sch.split(",")) for sch in argv[at + 1].split("/")]
+    del argv[at:at + 2]
 worlds = None
 if "--worlds" in argv:
     at = argv.index("--worlds")
     worlds = int(argv[at + 1])
     del argv[at:at + 2]
 out_path = argv[1] if len(argv) > 1 else os.path.join(
-    ROOT, "profiles", "playout_hidden_times.txt" if hidden else "playout_voids_times.txt" if voids else ("playout_det_times.txt" if worlds else "playout_times.txt"))
+    ROOT, "profiles", "playout_halving_times.txt" if halving else "playout_hidden_times.txt" if hidden else "playout_voids_times.txt" if voids else ("playout_det_times.txt" if worlds else "playout_times.txt"))
 assert worlds or not (voids or hidden), "--voids and --hidden go with --worlds W"
 assert not (voids and hidden), "--voids or --hidden, not both"
+assert all(sum(sch) == worlds for sch in halving), "--halving goes with --worlds W, W the sum of every schedule"
+assert halving or not teacher, "--teacher goes with --halving"
 n = int(argv[2]) if len(argv) > 2 else 65536
 per_world = int(argv[3]) if len(argv) > 3 else (1 if worlds else 16)
 samples = per_world * (worlds or 1)          # playouts per card of both launches
@@ -105,6 +124,18 @@ with torch.cuda.device(env.device):
             lines.append("  %-28s %10.1f us (%.1f, %.1f)   %12d cards   %8.2f G cards/s   %.3f x the open-hand time"
                          % ("  determinized (%d, %d)" % (worlds, per_world), dmed, dlo, dhi, total, total / (dmed * 1e-6) / 1e9, dmed / med))
             result["after_%d" % cards].update(det_us=dmed, det_over_open=dmed / med, worlds=worlds, samples_per_world=per_world)
+        for sch in halving:
+            counts = torch.empty((n, K.PLAYOUT_RANKS), dtype=torch.int32, device=env.device)
+            hmed, hlo, hhi = timed_us(lambda: env.playout_cards_halving(sch, per_world, sum_out=sums, count_out=counts, action_out=acts))
+            torch.cuda.synchronize()
+            items, alive = 0, 12                        # the item count of twelve legal cards: what a fresh deal's leader plays
+            for w in sch:
+                items, alive = items + alive * w, max(1, (alive + 1) // 2)
+            done = int(counts.sum().item())             # the playouts the launch did run, over all games
+            lines.append("  %-28s %10.1f us (%.1f, %.1f)   %.3f x the determinized time   (items: %.3f predicted at 12 legal cards, %.3f run here)"
+                         % ("  halving %s" % ",".join(map(str, sch)), hmed, hlo, hhi, hmed / dmed, items / (12.0 * worlds),
+                            done / float((legal * samples).sum())))
+            result["after_%d" % cards]["halving_" + "_".join(map(str, sch))] = dict(us=hmed, over_det=hmed / dmed, items_over_det=done / float((legal * samples).sum()))
         if voids:
             vw = torch.empty(n, dtype=torch.int32, device=env.device)
             smed, slo, shi = timed_us(lambda: env.shown_voids(vw))
@@ -123,10 +154,33 @@ with torch.cuda.device(env.device):
                          % ("  hidden-aware (%d, %d)" % (worlds, per_world), hmed, hlo, hhi, total, total / (hmed * 1e-6) / 1e9, hmed / dmed))
             lines.append("  %-28s %10.1f us (%.1f, %.1f)" % ("  tarok_played_cards", smed, slo, shi))
             result["after_%d" % cards].update(hidden_us=hmed, hidden_over_det=hmed / dmed, played_cards_us=smed)
+env.close()
+if teacher:
+    from tarok_amd import selfplay as SP
+    T = 48
+    lines += ["", "rollout T = %d at %d games (SelfPlay.collect, hidden = 256, fused learner), median of 5 between device events (min, max)" % (T, n)]
+    uniform = dict(worlds=worlds, samples=per_world)
+    for label, tc in [("no teacher", None), ("teacher worlds = %d, samples = %d" % (worlds, per_world), uniform)] + \
+            [("teacher halving = (%s)" % ",".join(map(str, sch)), dict(halving=sch, samples=per_world)) for sch in halving] + \
+            [("teacher worlds = %d, samples = %d (again)" % (worlds, per_world), uniform)]:
+        tenv = TarokVecEnv(n, seed=0, mix=K.MIX_BOT)
+        sp = SP.SelfPlay(tenv, hidden=256, seed=0, fused_learner=True, teacher=tc)
+        sp.collect(T)
+        torch.cuda.synchronize()
+        us = []
+        for _ in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            sp.collect(T)
+            e1.record()
+            e1.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3)
+        lines.append("  %-44s %10.0f us (%.0f, %.0f)" % (label, statistics.median(us), min(us), max(us)))
+        result["rollout " + label] = statistics.median(us)
+        tenv.close()
 text = "\n".join(lines) + "\n"
 os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
 with open(out_path, "w") as f:
     f.write(text)
 print(text)
 print(json.dumps(result))
-env.close()
