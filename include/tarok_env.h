@@ -1024,6 +1024,49 @@ int tarok_playout_cards_halving(tarok_env *env, int kind, const void *words, int
 int tarok_playout_targets_counts(tarok_env *env, const int32_t *sums, const int32_t *counts, const uint64_t *obs, float tau,
                                  int seats, const uint8_t *seats_per_game, void *target_out, void *stream);
 
+/* Sequential-halving NET playouts on a compacted item list: tarok_playout_cards_halving's definition at samples = 1, its
+ * playouts played as tarok_playout_cards_net / _voids / _hidden / _value play theirs.  kind, words, rounds
+ * and round_worlds as tarok_playout_cards_halving takes them; salt, seats, seats_per_game, net_seats and w1 .. b3 (read
+ * when the launches RUN) as tarok_playout_cards_net.  World w and the item key (c << 16 | w << 10) are the existing net
+ * launch's; neither depends on a launch size.  With e0 / e1 the cumulative world counts before / after round r, the round
+ * plays every rank still alive once in each of the worlds e0 .. e1 - 1; after a round that is not the last the better half
+ * by the mover's column stays (the rule above); a game down to one alive card plays no further round.
+ *   depth      0 or TAROK_PLAYOUT_MAX_DEPTH: every playout runs to the last card.  1 .. TAROK_PLAYOUT_MAX_DEPTH - 1: it
+ *              stops at the viewer's depth-th decision with value_scale x the value head in the viewer's column, as
+ *              tarok_playout_cards_net_value stops it; only that column is meaningful, and the rule reads no other.
+ *   value_scale finite and > 0 (read only where depth stops a playout).
+ *   sum_out    [N,12,4] i32, count_out [N,12] i32 (both 16-byte aligned), action_out [N] u8: each optional, at least one
+ *              given.  count_out[g][j] is the cumulative end e1 of the last round rank j played (0: none); the card is
+ *              the lowest rank at the maximum of the mover's sum among the ranks alive at the end, the Bot's card for a
+ *              game in play that does not take part, 255 elsewhere.
+ * Consequences: rounds = 1, (W), writes the sum_out and action_out of the existing net launch of that kind and depth at
+ * worlds = W, byte for byte; a row whose count is e equals the existing launch's row at worlds = e.  net_seats = 0 writes
+ * tarok_playout_cards_halving(kind, schedule, samples = 1)'s three outputs.
+ *
+ * The launches (all on `stream`; no host read, no allocation, no synchronisation: capturable).  One init launch, then per
+ * round: three launches of an exclusive prefix sum over the games' item counts popc(on[g]) x W_r (on[g]: the ranks of
+ * game g that play the round), which give every game its first slot and the round's total in a device word; the items, in
+ * ascending (game, rank, world) order — the item of the q-th set bit of on[g] in world w is base[g] + q x W_r + (w - e0) —;
+ * the playouts, over a grid sized by the round's BOUND n x a_r x W_r (a_0 = 12, a_{r+1} = ceil(a_r / 2): 12, 6, 3, 2),
+ * whose workgroups past the total run nothing; the sums and the survivor rule.
+ *
+ * scratch: device memory, 16-byte aligned, contents undefined afterwards.  tarok_playout_net_halving_scratch_bytes:
+ *     B = max over the rounds of n x a_r x W_r                                (the largest round's item bound)
+ *     bytes = 48 x B + 252 x n + 4 x ceil(n / 256) + 4, rounded up to a multiple of 16
+ * — the four item arrays at B (48 bytes an item), per game the running [12][4] sums (192), [12] counts (48) and the words
+ * on, alive and base (12), the scan's partials (a word per 256 games) and the total word.
+ * tarok_playout_net_halving_scratch_bytes returns TAROK_EINVAL for a NULL env, rounds outside 1..TAROK_PLAYOUT_MAX_ROUNDS, a
+ * NULL round_worlds, an entry < 1, a sum above TAROK_PLAYOUT_MAX_WORLDS or a round whose bound reaches 2^31 items.
+ * TAROK_EINVAL (before any HIP call) for all of those, a kind outside the three, words NULL for a kind that needs them or
+ * non-NULL for kind 0, seats or net_seats outside 0..15, a NULL weight array, depth outside 0..TAROK_PLAYOUT_MAX_DEPTH,
+ * value_scale not finite or <= 0, a NULL or misaligned scratch or scratch_bytes below the size, all three outputs NULL. */
+int64_t tarok_playout_net_halving_scratch_bytes(const tarok_env *env, int rounds, const int *round_worlds);
+int tarok_playout_cards_net_halving(tarok_env *env, int kind, const void *words, int rounds, const int *round_worlds,
+                                    uint64_t salt, int seats, const uint8_t *seats_per_game, int net_seats, const void *w1,
+                                    const float *b1, const void *w2, const float *b2, const void *w3, const float *b3, int depth,
+                                    float value_scale, void *scratch, int64_t scratch_bytes, int32_t *sum_out,
+                                    int32_t *count_out, uint8_t *action_out, void *stream);
+
 /* Net-played playouts for the exchange and the bid: tarok_playout_exchange and tarok_playout_bids at ONE playout per
  * (candidate or option, world), played as tarok_playout_cards_net plays its playouts — the network's greedy card on the
  * absolute seats of net_seats (one launch-wide 4-bit set), the Bot's card policy_action(pkey, q, legal) on the others.

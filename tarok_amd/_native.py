@@ -40,6 +40,7 @@ SYMBOLS = [
     "tarok_playout_exchange_net_value", "tarok_playout_bids_net_value",
     "tarok_front_lines_scratch_bytes", "tarok_front_lines", "tarok_get_lines",
     "tarok_playout_cards_halving", "tarok_playout_targets_counts",
+    "tarok_playout_net_halving_scratch_bytes", "tarok_playout_cards_net_halving",
 ]
 
 
@@ -211,6 +212,9 @@ def lib():
     L.tarok_playout_cards_halving.restype = i32   # (kind, words, rounds, round_worlds: a host int array, samples, salt, ...)
     L.tarok_playout_cards_halving.argtypes = [vp, i32, vp, i32, vp, i32, u64, i32, vp, vp, vp, vp, vp]
     L.tarok_playout_targets_counts.restype = i32; L.tarok_playout_targets_counts.argtypes = [vp, vp, vp, vp, f32, i32, vp, vp, vp]
+    L.tarok_playout_net_halving_scratch_bytes.restype = i64; L.tarok_playout_net_halving_scratch_bytes.argtypes = [vp, i32, vp]
+    L.tarok_playout_cards_net_halving.restype = i32  # (kind, words, rounds, round_worlds), salt .. net_seats, w1 .. b3, (depth, value_scale)
+    L.tarok_playout_cards_net_halving.argtypes = [vp, i32, vp, i32, vp, u64, i32, vp, i32] + [vp] * 6 + [i32, f32, vp, i64, vp, vp, vp, vp]
     L.tarok_learn_chain_distill.restype = i32
     L.tarok_learn_chain_distill.argtypes = [vp, i64] + [vp] * 4 + [f32] * 3 + [vp] * 17 + [vp, f32, vp, vp, vp, vp]
     L.tarok_front_lines_scratch_bytes.restype = i64; L.tarok_front_lines_scratch_bytes.argtypes = [i64]

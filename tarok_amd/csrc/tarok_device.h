@@ -679,6 +679,31 @@ __device__ __forceinline__ u32 best_alive(const int *row, u32 alive, u32 seat) {
     return best;
 }
 
+// The compacted item list of tarok_playout_cards_net_halving (include/tarok_env.h): a round's items lie game after game,
+// in a game rank after rank of its `on` word, in a rank world after world of the round.  The kernels, the host launcher
+// and tests/host_emu/net_halving_host.cpp share these.
+//   net_list_slot    the item of the q-th set bit of a game's `on` word in the round's lw-th world (lw = w - e0 < round_worlds)
+//   net_list_count   a game's items in the round: the summand of the exclusive prefix sum that gives `base`
+//   net_list_alive   a_r, the most ranks a game can have alive in round r: a_0 = 12, a_{r+1} = ceil(a_r / 2) — 12, 6, 3, 2
+//   net_list_bound   the round's item bound n * a_r * round_worlds, which sizes the scratch and the play grid
+//   net_list_tiles   the play grid: the bound in tiles of `tile` rows, rounded up
+#ifdef __HIPCC__
+#define TK_HOST_DEVICE __host__ __device__
+#else
+#define TK_HOST_DEVICE
+#endif
+TK_HOST_DEVICE __forceinline__ u32 net_list_slot(u32 base, u32 q, u32 round_worlds, u32 lw) { return base + q * round_worlds + lw; }
+TK_HOST_DEVICE __forceinline__ u32 net_list_count(u32 on, u32 round_worlds) { return (u32)__builtin_popcount(on) * round_worlds; }
+TK_HOST_DEVICE __forceinline__ u32 net_list_alive(u32 round) {
+    u32 a = 12;
+    for (u32 r = 0; r < round; r++) a = (a + 1u) >> 1;
+    return a;
+}
+TK_HOST_DEVICE __forceinline__ int64_t net_list_bound(int64_t n, u32 round, u32 round_worlds) {
+    return n * (int64_t)net_list_alive(round) * (int64_t)round_worlds;
+}
+TK_HOST_DEVICE __forceinline__ int64_t net_list_tiles(int64_t bound, u32 tile) { return (bound + (int64_t)tile - 1) / (int64_t)tile; }
+
 // Determinization (tarok_playout_cards_det, include/tarok_env.h): one WORLD of the seat `mover` — the cards it cannot
 // see, P = the hands of the three other seats, are dealt afresh among those seats, uniformly over the deals that keep
 // the hand sizes.  The cards of P are walked in ascending card number; card i of the walk draws

@@ -3855,6 +3855,247 @@ TK_KERNEL(TK_BLOCK, 64) void k_playout_net_sum(int64_t n, u32 worlds, u32 seats,
 }
 
 // ---------------------------------------------------------------------------
+// tarok_playout_cards_net_halving: the net card launch with sequential halving on a COMPACTED item list.
+// Per game three words live in the scratch across the rounds — alive[g] (the ranks alive), on[g] (the ranks that play the
+// round: alive, or 0 for a game that does not take part or is down to one card after round 0) and base[g] (the game's first
+// item of the round: the exclusive prefix sum of net_list_count(on, W_r)) — beside its running [12][4] sums and [12]
+// counts.  A round is: the scan (three launches: no workgroup waits on another), the items, the playouts
+// (playout_net_play_body on the round's total, read from a device word), the sums and the survivor rule.  One stream, no
+// host read: the item arrays are sized by the host's bound n * a_r * W_r (net_list_bound).
+
+// k_playout_net_list_init: 16 lanes a game, as k_playout_net_sum: zero running sums and counts, alive and round 0's on.
+TK_KERNEL(TK_BLOCK, 64) void k_playout_net_list_init(int64_t n, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                    const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
+                                                    u32 *__restrict__ on, u32 *__restrict__ alive, int4 *__restrict__ rsum,
+                                                    int4 *__restrict__ rcnt) {
+    TK_VGPR_TOP(64, 63);
+    const PlayoutTeam t(4);
+    if (t.g >= n) return;
+    if (t.lane < TAROK_PLAYOUT_RANKS) rsum[t.g * TAROK_PLAYOUT_RANKS + t.lane] = make_int4(0, 0, 0, 0);
+    else if (t.lane < TAROK_PLAYOUT_RANKS + 3u) rcnt[t.g * 3 + (t.lane - TAROK_PLAYOUT_RANKS)] = make_int4(0, 0, 0, 0);
+    else if (t.lane == 15u) {
+        Game g0;
+        load_game(g0, s01, s23, t.g);
+        const CardPosition p = card_position(g0, seat_sets, seats, t.g);
+        const u32 a = p.takes_part ? (1u << (u32)popc64(p.legal)) - 1u : 0u;
+        alive[t.g] = a;
+        on[t.g] = a;
+    }
+}
+
+// The exclusive prefix sum of one value a thread over the workgroup's TK_BLOCK threads (Hillis-Steele in LDS; every thread
+// of the workgroup calls it) -> the sum of the values below the thread's; `total`: the workgroup's sum.
+__device__ __forceinline__ u32 block_exclusive_scan(u32 v, u32 *lds /* [TK_BLOCK] */, u32 &total) {
+    const u32 tid = threadIdx.x;
+    u32 x = v;
+    lds[tid] = x;
+    __syncthreads();
+#pragma unroll
+    for (u32 d = 1; d < TK_BLOCK; d <<= 1) {
+        const u32 y = tid >= d ? lds[tid - d] : 0u;
+        __syncthreads();
+        x += y;
+        lds[tid] = x;
+        __syncthreads();
+    }
+    total = lds[TK_BLOCK - 1];
+    __syncthreads();                                     // (the caller may scan again over the same words)
+    return x - v;
+}
+
+// The scan's first launch: a workgroup of TK_BLOCK games -> part[block], its items of the round.
+TK_KERNEL(TK_BLOCK, 64) void k_playout_net_list_totals(int64_t n, u32 round_worlds, const u32 *__restrict__ on, u32 *__restrict__ part) {
+    TK_VGPR_TOP(64, 63);
+    __shared__ u32 lds[TK_BLOCK];
+    const int64_t g = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
+    u32 total;
+    block_exclusive_scan(g < n ? net_list_count(on[g], round_worlds) : 0u, lds, total);
+    if (threadIdx.x == 0) part[blockIdx.x] = total;
+}
+
+// The second: ONE workgroup turns part[0 .. blocks - 1] into its exclusive prefix sums, TK_BLOCK words a pass with the
+// carry in a register, and writes the round's total.
+TK_KERNEL(TK_BLOCK, 64) void k_playout_net_list_scan(u32 blocks, u32 *__restrict__ part, u32 *__restrict__ total_out) {
+    TK_VGPR_TOP(64, 63);
+    __shared__ u32 lds[TK_BLOCK];
+    u32 carry = 0;
+    for (u32 b0 = 0; b0 < blocks; b0 += TK_BLOCK) {      // (launch-uniform: every thread meets the same barriers)
+        const u32 i = b0 + threadIdx.x;
+        u32 total;
+        const u32 x = block_exclusive_scan(i < blocks ? part[i] : 0u, lds, total);
+        if (i < blocks) part[i] = carry + x;
+        carry += total;
+    }
+    if (threadIdx.x == 0) *total_out = carry;
+}
+
+// The third: base[g] = the items of the workgroups before the game's + those of the games before it in its own.
+TK_KERNEL(TK_BLOCK, 64) void k_playout_net_list_base(int64_t n, u32 round_worlds, const u32 *__restrict__ on, const u32 *__restrict__ part,
+                                                    u32 *__restrict__ base) {
+    TK_VGPR_TOP(64, 63);
+    __shared__ u32 lds[TK_BLOCK];
+    const int64_t g = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
+    u32 total;
+    const u32 x = block_exclusive_scan(g < n ? net_list_count(on[g], round_worlds) : 0u, lds, total);
+    if (g < n) base[g] = part[blockIdx.x] + x;
+}
+
+// The round's items: playout_net_deal_body's team, dealer, keys and item words, for the ranks of on[g] in the round's worlds
+// e0 .. e0 + round_worlds - 1 alone — the team deals only those, into its world slots 0 .. round_worlds - 1, under their true
+// indices — each written to its compact slot net_list_slot(base[g], q, round_worlds, w - e0).  A game's items are
+// net_list_count(on[g]) <= a_r * round_worlds, so every slot written lies below the round's total and below the host's bound.
+template <class Dealer, bool VIEWER>
+__device__ __forceinline__ void playout_net_list_deal_body(int64_t n, u64 pseed, u64 offset, u32 e0, u32 round_worlds, u32 lg, u32 seats,
+                                                           const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                                           const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                                           const typename Dealer::Extra *__restrict__ extra, const u32 *__restrict__ on,
+                                                           const u32 *__restrict__ base, ulonglong2 *__restrict__ i01,
+                                                           ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
+    __shared__ typename Dealer::Record world;
+    const PlayoutTeam t(lg, round_worlds);
+    const int64_t g = t.g;
+    ulonglong2 a = {0, 0}, b = {0, 0};
+    CardPosition p;
+    u64 ebase = 0;
+    u32 o = 0, first = 0;
+    if (g < n && (o = on[g]) != 0u) {                    // (on: only games that take part)
+        first = base[g];
+        a = s01[g]; b = s23[g];
+        Game g0;
+        unpack(g0, a.x, a.y, b.x, b.y);
+        p = card_position(g0, seat_sets, seats, g);
+        ebase = ((u64)cnt[g].episode << 28) | ((u64)p.played << 22);
+        const typename Dealer::Extra word = game_word(extra, g);
+        for (u32 lw = t.lane; lw < round_worlds; lw += t.L) {
+            Game d = g0;
+            Dealer::deal(d, p.mover, game_key(pseed, offset + (u64)g, Dealer::world_tag | ebase | (u64)(e0 + lw)), word);
+            world.store(t.slot0 + lw, d);
+        }
+    }
+    __syncthreads();
+    const u32 count = net_list_count(o, round_worlds);
+    for (u32 i = t.lane; i < count; i += t.L) {
+        const u32 q = i / round_worlds, lw = i - q * round_worlds, w = e0 + lw;
+        const u32 it = net_list_slot(first, q, round_worlds, lw);
+        const u32 c = kth_bit(p.legal, kth_bit_word(o, 0u, q));
+        Game h;
+        unpack(h, a.x, a.y, b.x, b.y);
+        world.load(t.slot0 + lw, h);
+        u64 scores = 0;
+        u32 ti;
+        const int fin = apply_step<true>(h, c, scores, ti, false);
+        if (!fin) {
+            u64 x0, x1, y0, y1;
+            pack(h, x0, x1, y0, y1);
+            i01[it] = make_ulonglong2(x0, x1);
+            i23[it] = make_ulonglong2(y0, y1);
+            ikey[it] = game_key(pseed, offset + (u64)g, Dealer::item_tag | ebase | ((u64)c << 16) | ((u64)w << 10));
+        }
+        ires[it] = fin ? scores : (VIEWER ? TK_PN_LIVE | (u64)p.mover : TK_PN_LIVE);
+    }
+}
+
+#define TK_NET_LIST_DEAL(NAME, DEALER, VIEWER, WORDS_T)                                                                            \
+    TK_KERNEL(TK_BLOCK, 128) void NAME(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 e0, u32 round_worlds, u32 lg,        \
+                                      u32 seats, const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,         \
+                                      const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,                         \
+                                      const WORDS_T *__restrict__ words, const u32 *__restrict__ on, const u32 *__restrict__ base,  \
+                                      ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,           \
+                                      u64 *__restrict__ ires) {                                                                     \
+        TK_VGPR_TOP(128, 127);                                                                                                      \
+        playout_net_list_deal_body<DEALER, VIEWER>(n, pseed, offset, e0, round_worlds, lg, seats, seat_sets, s01, s23, cnt, words,  \
+                                                   on, base, i01, i23, ikey, ires);                                                 \
+    }
+TK_NET_LIST_DEAL(k_playout_net_list_deal, DealUnseen, false, NoWord)                  // words: nullptr
+TK_NET_LIST_DEAL(k_playout_net_list_deal_voids, DealVoids, false, u32)
+TK_NET_LIST_DEAL(k_playout_net_list_deal_hidden, DealHidden, false, u64)
+TK_NET_LIST_DEAL(k_playout_net_list_deal_value, DealUnseen, true, NoWord)
+TK_NET_LIST_DEAL(k_playout_net_list_deal_value_voids, DealVoids, true, u32)
+TK_NET_LIST_DEAL(k_playout_net_list_deal_value_hidden, DealHidden, true, u64)
+#undef TK_NET_LIST_DEAL
+
+// The round's playouts: k_playout_net_play / _value on the round's total, which no host knows — the grid is the bound's, and a
+// workgroup past the total has no live row and leaves at the first round's vote (playout_net_play_body's invariants).
+__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net_play_list(
+    const u32 *__restrict__ total, u32 net_seats, const ulonglong2 *__restrict__ i01, const ulonglong2 *__restrict__ i23,
+    const u64 *__restrict__ ikey, u64 *__restrict__ ires, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3, const float *__restrict__ b3) {
+    TK_VGPR_TOP(256, 255);
+    playout_net_play_body<false>((int64_t)*total, net_seats, 0, 0.f, i01, i23, ikey, ires, w1, b1, w2, b2, w3, b3);
+}
+
+__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net_play_list_value(
+    const u32 *__restrict__ total, u32 net_seats, const ulonglong2 *__restrict__ i01, const ulonglong2 *__restrict__ i23,
+    const u64 *__restrict__ ikey, u64 *__restrict__ ires, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3, const float *__restrict__ b3,
+    u32 depth, float value_scale) {
+    TK_VGPR_TOP(256, 255);
+    playout_net_play_body<true>((int64_t)*total, net_seats, depth, value_scale, i01, i23, ikey, ires, w1, b1, w2, b2, w3, b3);
+}
+
+// The round's sums and the survivor rule: 16 lanes a game, as k_playout_net_sum.  Lane j < 12 whose rank played the round adds
+// its round_worlds results, in integers, to the game's running sums and sets the rank's count to the round's end e1; the
+// team's block in LDS is playout_halving_body's ([12][4] sums, [12] counts).  After the barrier: not the last round ->
+// halve_alive on the mover's column, the new alive[g] and the next round's on[g]; the last -> the launch's three outputs,
+// the card by best_alive over the ranks alive, the Bot's for a game in play that does not take part.
+TK_KERNEL(TK_BLOCK, 128) void k_playout_net_list_sum(int64_t n, u32 e1, u32 round_worlds, u32 last, u32 seats,
+                                                    const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                                    const ulonglong2 *__restrict__ s23, const u64 *__restrict__ gkey,
+                                                    const u64 *__restrict__ ires, u32 *__restrict__ on, u32 *__restrict__ alive,
+                                                    const u32 *__restrict__ base, int4 *__restrict__ rsum, int *__restrict__ rcnt,
+                                                    int4 *__restrict__ sum_out, int4 *__restrict__ count_out,
+                                                    uint8_t *__restrict__ action_out) {
+    TK_VGPR_TOP(128, 127);
+    constexpr u32 INTS = TAROK_PLAYOUT_RANKS * 5;
+    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> 4) * INTS];
+    const PlayoutTeam t(4);
+    const int64_t g = t.g;
+    int *row = sums + t.team * INTS;
+    u32 o = 0, al = 0;
+    if (g < n) {
+        o = on[g]; al = alive[g];
+        if (t.lane < TAROK_PLAYOUT_RANKS) {
+            const u32 j = t.lane;
+            int4 s = rsum[g * TAROK_PLAYOUT_RANKS + j];
+            int c = rcnt[g * TAROK_PLAYOUT_RANKS + j];
+            if ((o >> j) & 1u) {
+                const u64 *r = ires + net_list_slot(base[g], (u32)__popc(o & ((1u << j) - 1u)), round_worlds, 0u);
+                for (u32 w = 0; w < round_worlds; w++) {
+                    const u64 sc = r[w];
+                    s.x += (int)(int16_t)sc; s.y += (int)(int16_t)(sc >> 16); s.z += (int)(int16_t)(sc >> 32); s.w += (int)(int16_t)(sc >> 48);
+                }
+                c = (int)e1;
+                rsum[g * TAROK_PLAYOUT_RANKS + j] = s;
+                rcnt[g * TAROK_PLAYOUT_RANKS + j] = c;
+            }
+            reinterpret_cast<int4 *>(row)[j] = s;
+            row[TAROK_PLAYOUT_RANKS * 4 + j] = c;
+        }
+    }
+    __syncthreads();
+    if (g >= n) return;
+    if (last) {
+        if (sum_out && t.lane < TAROK_PLAYOUT_RANKS) sum_out[g * TAROK_PLAYOUT_RANKS + t.lane] = reinterpret_cast<const int4 *>(row)[t.lane];
+        if (count_out && t.lane >= 12u && t.lane < 15u)
+            count_out[g * 3 + (t.lane - 12u)] = reinterpret_cast<const int4 *>(row)[TAROK_PLAYOUT_RANKS + (t.lane - 12u)];
+    }
+    if (t.lane != 15u || (last && !action_out)) return;
+    Game g0;
+    load_game(g0, s01, s23, g);
+    const CardPosition p = card_position(g0, seat_sets, seats, g);
+    if (!last) {
+        const u32 next = halve_alive(row, al, p.mover);
+        alive[g] = next;
+        on[g] = (next & (next - 1u)) != 0u ? next : 0u;     // a game down to one card plays no further round
+    } else {
+        u32 act = 255;
+        if (p.takes_part) act = kth_bit(p.legal, best_alive(row, al, p.mover));
+        else if (p.in_play) act = policy_action(gkey[g], p.played, p.legal);
+        action_out[g] = (uint8_t)act;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // tarok_playout_exchange_net / tarok_playout_bids_net: the exchange and the bid valued by playouts that
 // k_playout_net_play plays.  An exchange candidate in a world, or a bid option in a world, is an item at 0 cards played
 // under the key the Bot launch uses at sample 0; the scratch holds the four item arrays of tarok_playout_cards_net.
@@ -5070,6 +5311,103 @@ int tarok_playout_cards_halving(tarok_env *e, int kind, const void *words, int r
                                       count_out, action_out, stream, (const u64 *)words);
     return launch_playout_halving(k_playout_halving_det, e, rounds, round_worlds, samples, salt, seats, seats_per_game, sum_out, count_out,
                                   action_out, stream, (const NoWord *)nullptr);
+}
+
+extern "C++" {
+// A net halving launch's schedule as the host reads it: the cumulative ends, the largest round's item bound and the scratch.
+struct NetHalvingPlan {
+    int rounds = 0, worlds = 0;
+    int w[TAROK_PLAYOUT_MAX_ROUNDS] = {0, 0, 0, 0}, end[TAROK_PLAYOUT_MAX_ROUNDS] = {0, 0, 0, 0};
+    int64_t bound = 0, blocks = 0, bytes = 0;            // max_r net_list_bound; the scan's workgroups; the scratch
+};
+// false: a NULL env, rounds outside 1..TAROK_PLAYOUT_MAX_ROUNDS, a NULL schedule, a count < 1, a sum above
+// TAROK_PLAYOUT_MAX_WORLDS, or a round whose bound reaches 2^31 items (the list's slots are 32-bit words).
+static bool net_halving_plan(const tarok_env *e, int rounds, const int *round_worlds, NetHalvingPlan &p) {
+    if (!e || rounds < 1 || rounds > TAROK_PLAYOUT_MAX_ROUNDS || !round_worlds) return false;
+    p.rounds = rounds;
+    for (int r = 0; r < rounds; r++) {
+        if (round_worlds[r] < 1 || round_worlds[r] > TAROK_PLAYOUT_MAX_WORLDS - p.worlds) return false;
+        p.w[r] = round_worlds[r];
+        p.worlds += round_worlds[r];
+        p.end[r] = p.worlds;
+        const int64_t b = net_list_bound(e->n, (u32)r, (u32)round_worlds[r]);
+        if (b >= (1LL << 31)) return false;
+        p.bound = b > p.bound ? b : p.bound;
+    }
+    p.blocks = (e->n + TK_BLOCK - 1) / TK_BLOCK;
+    const int64_t raw = p.bound * TK_PN_ITEM_BYTES + e->n * 252 + p.blocks * 4 + 4;
+    p.bytes = (raw + 15) & ~(int64_t)15;
+    return true;
+}
+}
+
+int64_t tarok_playout_net_halving_scratch_bytes(const tarok_env *e, int rounds, const int *round_worlds) {
+    NetHalvingPlan p;
+    return net_halving_plan(e, rounds, round_worlds, p) ? p.bytes : (int64_t)TAROK_EINVAL;
+}
+
+extern "C++" {
+template <class Kernel, class Word>
+static void launch_net_list_deal(Kernel deal, tarok_env *e, u64 pseed, int e0, int w, int seats, const uint8_t *seats_per_game,
+                                 const Word *words, const u32 *on, const u32 *base, const NetItems &it, hipStream_t s) {
+    const u32 lg = playout_lg(TK_PO_MIN_LG, w);
+    hipLaunchKernelGGL(deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, s, e->n, pseed, e->offset, (u32)e0, (u32)w, lg, (u32)seats,
+                       seats_per_game, e->s01, e->s23, e->cnt, words, on, base, it.i01, it.i23, it.ikey, it.ires);
+}
+}
+
+int tarok_playout_cards_net_halving(tarok_env *e, int kind, const void *words, int rounds, const int *round_worlds, uint64_t salt,
+                                    int seats, const uint8_t *seats_per_game, int net_seats, const void *w1, const float *b1,
+                                    const void *w2, const float *b2, const void *w3, const float *b3, int depth, float value_scale,
+                                    void *scratch, int64_t scratch_bytes, int32_t *sum_out, int32_t *count_out, uint8_t *action_out,
+                                    void *stream) {
+    NetHalvingPlan p;
+    if (!e || kind < TAROK_NET_WORLDS_DET || kind > TAROK_NET_WORLDS_HIDDEN || (kind == TAROK_NET_WORLDS_DET) != !words ||
+        !net_halving_plan(e, rounds, round_worlds, p) || seats < 0 || seats > 15 ||
+        !net_args_ok(net_seats, w1, b1, w2, b2, w3, b3, scratch, scratch_bytes, p.bytes) || depth < 0 || depth > TAROK_PLAYOUT_MAX_DEPTH ||
+        !(value_scale > 0.f) || __builtin_isinf(value_scale) || (!sum_out && !count_out && !action_out))
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    if (depth == TAROK_PLAYOUT_MAX_DEPTH) depth = 0;     // never stops: the plain kernels' bytes (§8.18)
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = e->n;
+    const NetItems it(scratch, p.bound);
+    int4 *rsum = reinterpret_cast<int4 *>(it.ires + p.bound);
+    int *rcnt = reinterpret_cast<int *>(rsum + n * TAROK_PLAYOUT_RANKS);
+    u32 *on = reinterpret_cast<u32 *>(rcnt + n * TAROK_PLAYOUT_RANKS), *alive = on + n, *base = alive + n, *part = base + n,
+        *total = part + p.blocks;
+    const u64 pseed = e->seed ^ (u64)salt;
+    const dim3 per_game = grid_for(n), per_16((unsigned)((n + 15) / 16));
+    hipLaunchKernelGGL(k_playout_net_list_init, per_16, dim3(TK_BLOCK), 0, s, n, (u32)seats, seats_per_game, e->s01, e->s23, on, alive, rsum,
+                       reinterpret_cast<int4 *>(rcnt));
+    for (int r = 0; r < p.rounds; r++) {
+        const int e0 = p.end[r] - p.w[r];
+        hipLaunchKernelGGL(k_playout_net_list_totals, per_game, dim3(TK_BLOCK), 0, s, n, (u32)p.w[r], on, part);
+        hipLaunchKernelGGL(k_playout_net_list_scan, dim3(1), dim3(TK_BLOCK), 0, s, (u32)p.blocks, part, total);
+        hipLaunchKernelGGL(k_playout_net_list_base, per_game, dim3(TK_BLOCK), 0, s, n, (u32)p.w[r], on, part, base);
+        if (kind == TAROK_NET_WORLDS_VOIDS) {
+            if (depth) launch_net_list_deal(k_playout_net_list_deal_value_voids, e, pseed, e0, p.w[r], seats, seats_per_game, (const u32 *)words, on, base, it, s);
+            else launch_net_list_deal(k_playout_net_list_deal_voids, e, pseed, e0, p.w[r], seats, seats_per_game, (const u32 *)words, on, base, it, s);
+        } else if (kind == TAROK_NET_WORLDS_HIDDEN) {
+            if (depth) launch_net_list_deal(k_playout_net_list_deal_value_hidden, e, pseed, e0, p.w[r], seats, seats_per_game, (const u64 *)words, on, base, it, s);
+            else launch_net_list_deal(k_playout_net_list_deal_hidden, e, pseed, e0, p.w[r], seats, seats_per_game, (const u64 *)words, on, base, it, s);
+        } else {
+            if (depth) launch_net_list_deal(k_playout_net_list_deal_value, e, pseed, e0, p.w[r], seats, seats_per_game, (const NoWord *)nullptr, on, base, it, s);
+            else launch_net_list_deal(k_playout_net_list_deal, e, pseed, e0, p.w[r], seats, seats_per_game, (const NoWord *)nullptr, on, base, it, s);
+        }
+        const int64_t tiles = net_list_tiles(net_list_bound(n, (u32)r, (u32)p.w[r]), PM_M);
+        if (depth)
+            hipLaunchKernelGGL(k_playout_net_play_list_value, dim3((unsigned)tiles), dim3(TK_BLOCK), 0, s, total, (u32)net_seats, it.i01, it.i23,
+                               it.ikey, it.ires, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3, (u32)depth, value_scale);
+        else
+            hipLaunchKernelGGL(k_playout_net_play_list, dim3((unsigned)tiles), dim3(TK_BLOCK), 0, s, total, (u32)net_seats, it.i01, it.i23, it.ikey,
+                               it.ires, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3);
+        hipLaunchKernelGGL(k_playout_net_list_sum, per_16, dim3(TK_BLOCK), 0, s, n, (u32)p.end[r], (u32)p.w[r], (u32)(r == p.rounds - 1),
+                           (u32)seats, seats_per_game, e->s01, e->s23, e->gkey, it.ires, on, alive, base, rsum, rcnt,
+                           reinterpret_cast<int4 *>(sum_out), reinterpret_cast<int4 *>(count_out), action_out);
+    }
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
 }
 
 extern "C++" {

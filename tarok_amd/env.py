@@ -403,6 +403,51 @@ class TarokVecEnv:
                                                              self._p(count_out), self._p(action_out), self._stream()))
         return sum_out, count_out, action_out
 
+    def playout_net_halving_scratch(self, round_worlds):
+        """The scratch tensor of playout_cards_net_halving at a schedule (uint8, tarok_playout_net_halving_scratch_bytes: the
+        largest round's item arrays at its bound, the per-game words, the running sums and counts, the scan's partials), cached
+        on the env per schedule — the size depends on no world kind —: a caller that captures the launch asks for it BEFORE
+        the capture."""
+        schedule = P.check_halving(round_worlds)
+        return self._scratch(("cards_halving", schedule), self.L.tarok_playout_net_halving_scratch_bytes, len(schedule),
+                             (C.c_int * len(schedule))(*schedule))
+
+    def playout_cards_net_halving(self, weights, round_worlds, net_seats=15, voids=False, hidden=False, words=None, depth=None,
+                                  value_scale=70.0, salt=0, seats=15, seats_per_game=None, scratch=None, sum_out=None, count_out=None,
+                                  action_out=None):
+        """playout_cards_net / playout_cards_net_value with sequential halving on a compacted item list
+        (tarok_playout_cards_net_halving): round r plays the cards still alive once in each of round_worlds[r] fresh worlds,
+        the playouts played by `weights` on the seats of net_seats and by the Bot on the others, and after every round but
+        the last the better half by the mover's sum stays alive, ties to the lower rank.  A round's items are packed without
+        gaps, so its forward rows are its alive cards' alone; round_worlds=(W,) is playout_cards_net(weights, W) to the byte,
+        with no dead rows.  voids / hidden / words: the worlds' kind and the caller's scratch tensor for its words, as in
+        playout_cards_halving; depth / value_scale: playout_cards_net_value's stop (None: to the last card).  scratch: the
+        caller's uint8 tensor of at least playout_net_halving_scratch(round_worlds).numel() bytes (None: that cached one).
+        Returns (sum [N,12,4] int32, count [N,12] int32 — the worlds behind every row —, action [N] uint8: the first card
+        at the maximum among the cards alive at the end)."""
+        P.one_world_kind(bool(voids), bool(hidden))
+        kind = "voids" if voids else "hidden" if hidden else "det"
+        schedule = P.check_halving(round_worlds)
+        if not 0 <= int(net_seats) <= 15:
+            raise ValueError("net_seats: a 4-bit seat set, 0..15")
+        if depth is not None:
+            P.check_depth(depth, value_scale)
+        if kind in P.WORDS_DTYPE and not self.history:
+            raise ValueError("%s=True goes with the play history: TarokVecEnv(history=True)" % kind)
+        w = self.check_mlp_weights(weights)
+        scratch = self.playout_net_halving_scratch(schedule) if scratch is None else scratch
+        words = (self.shown_voids if voids else self.played_cards)(words) if kind in P.WORDS_DTYPE else None
+        with torch.cuda.device(self.device):
+            sum_out = self._empty(sum_out, (self.n, K.PLAYOUT_RANKS, 4), torch.int32)
+            count_out = self._empty(count_out, (self.n, K.PLAYOUT_RANKS), torch.int32)
+            action_out = self._empty(action_out, self.n, torch.uint8)
+            _native.check(self.L.tarok_playout_cards_net_halving(
+                self._h, P.WORLDS.index(kind), self._p(words), len(schedule), (C.c_int * len(schedule))(*schedule),
+                int(salt) & ((1 << 64) - 1), int(seats), self._p(self._seat_sets(seats_per_game)), int(net_seats), *[self._p(t) for t in w],
+                0 if depth is None else int(depth), float(value_scale), self._p(scratch), scratch.numel(), self._p(sum_out),
+                self._p(count_out), self._p(action_out), self._stream()))
+        return sum_out, count_out, action_out
+
     def playout_net_scratch(self, worlds):
         """The scratch tensor of playout_cards_net at `worlds` (uint8, tarok_playout_net_scratch bytes), cached on the env
         per `worlds`: a caller that captures the launch into a graph asks for it BEFORE the capture."""

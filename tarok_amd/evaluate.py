@@ -375,7 +375,7 @@ def _bid_args(bidding, mix):
 
 def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None, voids=False, exchange=None,
                     hidden=False, bidding=None, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None,
-                    net_seats=15, net_worlds="det", net_depth=None, net_value_scale=70.0, halving=None):
+                    net_seats=15, net_worlds="det", net_depth=None, net_value_scale=70.0, halving=None, net_halving=None):
     """_play_passes_mode with the Monte-Carlo player (TarokVecEnv.playout_cards) in the network's place: per lock-step
     one playout launch with the pass's seat set — tarok_playout_cards (open hands) for worlds=None,
     tarok_playout_cards_det (the fair player: `worlds` re-deals of the unseen cards) otherwise — whose action_out holds
@@ -398,9 +398,12 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     net_depth=D (with net): the launch is playout_cards_net_value at depth D and net_value_scale in the same worlds — the
     playouts stop at the player's D-th next decision and take the value head's estimate; None: the calls as they were.
     halving=(w0, ..): the launch is tarok_playout_cards_halving with that schedule, in the worlds voids / hidden name.
+    net_halving=(w0, ..) (with net): the launch is tarok_playout_cards_net_halving with that schedule, in the worlds of
+    net_worlds and at net_depth.
     inspect: as in _play_passes_mode."""
     player = playout.card_player(samples, worlds, voids, hidden, net is not None, net_seats, net_worlds, net_depth, net_value_scale, salt,
-                                 front=exchange is not None or bidding is not None, **({} if halving is None else dict(halving=halving)))
+                                 front=exchange is not None or bidding is not None, **({} if halving is None else dict(halving=halving)),
+                                 **({} if net_halving is None else dict(net_halving=net_halving)))
     if net is not None:
         if samples is not None:
             raise ValueError("net= runs one playout per (card, world): samples is not taken (pass None)")
@@ -411,7 +414,7 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
         raise ValueError("bidding=(W, S) is the fair player's front end: give worlds= as well")
     bidding = _bid_args(bidding, mix)
     cards = _playout_cards(lambda env, seats, words, sums, row, **more: player.launch(env, net, dict(seats=seats), words, sums, row, **more),
-                           words_dtype=player.words_dtype, **({} if halving is None else dict(counts=True)))
+                           words_dtype=player.words_dtype, **({} if player.halving is None else dict(counts=True)))
     front = _front(inspect is not None, bid=None if bidding is None else _bid_front(bidding, salt, threshold, contracts, pass_value),
                    exchange=None if exchange is None else _exchange_front(worlds, samples, exchange, salt))
     return _passes(n_games, episodes, front, cards, inspect, device=device, seed=seed, mix=mix, history=player.needs_history)
@@ -420,7 +423,7 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
 def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None,
                             voids=False, exchange=None, hidden=False, bidding=None, threshold=0,
                             contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None, net_seats=15, net_worlds="det",
-                            net_depth=None, net_value_scale=70.0, halving=None):
+                            net_depth=None, net_value_scale=70.0, halving=None, net_halving=None):
     """evaluate_vs_bot with the open-hand Monte-Carlo player in the network's place: a strong reference player that needs
     no training.  On its seat it plays, at every move, the legal card with the best summed score over `samples` Bot
     playouts of each legal card (tarok_playout_cards; `salt` varies their draws).  The playouts see the TRUE hidden
@@ -459,13 +462,17 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
     net=, exchange or bidding): the fair player spends its worlds by sequential halving (tarok_playout_cards_halving) —
     every legal card in the first w0 worlds, then the better half in w1 fresh ones, and so on: the finalists are compared
     over all the worlds at a fraction of the playouts.  None (the default): the calls as they were.
+    net_halving=(w0, w1, ..) (with net=weights; `worlds` None or their sum; with net_worlds and net_depth; not with exchange
+    or bidding): the network's playouts are spent by sequential halving on a compacted item list
+    (tarok_playout_cards_net_halving).  None (the default): the calls as they were.  halving= with net= keeps raising.
     The same five duplicate passes (PASS_SEATS) on an env of its own; returns duplicate_advantage's dict, `policy_mean`
     being the playout player's.  inspect (tests): a list that receives one dict per pass, as in _play_passes_mode."""
     return duplicate_advantage(_playout_passes(samples, n_games, episodes, seed, mix, device, salt=salt, inspect=inspect,
                                                worlds=worlds, voids=voids, exchange=exchange, hidden=hidden, bidding=bidding,
                                                threshold=threshold, contracts=contracts, pass_value=pass_value, net=net,
                                                net_seats=net_seats, net_worlds=net_worlds, net_depth=net_depth,
-                                               net_value_scale=net_value_scale, **({} if halving is None else dict(halving=halving))))
+                                               net_value_scale=net_value_scale, **({} if halving is None else dict(halving=halving)),
+                                               **({} if net_halving is None else dict(net_halving=net_halving))))
 
 
 def _front_cards(cards):

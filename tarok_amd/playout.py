@@ -13,7 +13,7 @@ from . import karte as K
 WORLDS = ("det", "voids", "hidden")               # the fair world kinds; the position is tarok_playout_cards_net_value's `kind`
 WORDS_DTYPE = dict(voids=torch.int32, hidden=torch.int64)      # the per-game words a kind reads: shown_voids() / played_cards()
 OPTIONS = ("samples", "worlds", "voids", "hidden", "exchange", "bidding", "net", "net_seats", "net_worlds", "net_depth", "net_value_scale",
-           "halving")
+           "halving", "net_halving")
 
 
 def spelling(prefix="", pattern="%s", **other):
@@ -36,12 +36,13 @@ def check_depth(depth, value_scale, say=spelling(net_depth="depth", net_value_sc
         raise ValueError(say("{net_value_scale}: finite and > 0"))
 
 
-def check_halving(halving, say=spelling()):
-    """A sequential-halving schedule as a tuple: 1..K.PLAYOUT_MAX_ROUNDS positive ints, at most K.PLAYOUT_MAX_WORLDS in all."""
+def check_halving(halving, say=spelling(), option="{halving}"):
+    """A sequential-halving schedule as a tuple: 1..K.PLAYOUT_MAX_ROUNDS positive ints, at most K.PLAYOUT_MAX_WORLDS in all.
+    option: the name the refusal gives it ("{net_halving}" for the net-played launch's)."""
     ok = isinstance(halving, (tuple, list)) and 1 <= len(halving) <= K.PLAYOUT_MAX_ROUNDS and \
         all(isinstance(w, numbers.Integral) and not isinstance(w, bool) and w >= 1 for w in halving)
     if not ok or sum(halving) > K.PLAYOUT_MAX_WORLDS:
-        raise ValueError(say("{halving}: 1..%d positive world counts, one per round, at most %d in all" % (K.PLAYOUT_MAX_ROUNDS, K.PLAYOUT_MAX_WORLDS)))
+        raise ValueError(say(option + ": 1..%d positive world counts, one per round, at most %d in all" % (K.PLAYOUT_MAX_ROUNDS, K.PLAYOUT_MAX_WORLDS)))
     return tuple(int(w) for w in halving)
 
 
@@ -93,15 +94,39 @@ class HalvingPlayer(collections.namedtuple("HalvingPlayer", CardPlayer._fields +
                                          salt=self.salt, sum_out=sum_out, count_out=count_out, action_out=action_out, **sets)
 
 
+class NetHalvingPlayer(collections.namedtuple("NetHalvingPlayer", CardPlayer._fields + ("halving",))):
+    """A CardPlayer of a fair kind played by the NETWORK whose launch is tarok_playout_cards_net_halving: halving = the worlds
+    of every round, worlds their sum, one playout per (card alive, world).  Its rows have a count per card, as a
+    HalvingPlayer's: the targets are tarok_playout_targets_counts'."""
+    __slots__ = ()
+
+    needs_history, words_dtype = CardPlayer.needs_history, CardPlayer.words_dtype
+
+    def prepare(self, env):
+        """The launch's scratch, before the launch is captured into a graph."""
+        env.playout_net_halving_scratch(self.halving)
+
+    def launch(self, env, weights, sets, words, sum_out, action_out, count_out=None):
+        """As HalvingPlayer.launch, on the network's six tensors.  Returns (sum, count, action)."""
+        return env.playout_cards_net_halving(weights, self.halving, sets["seats"] if self.net_seats == "own" else self.net_seats,
+                                             voids=self.kind == "voids", hidden=self.kind == "hidden", words=words, depth=self.depth,
+                                             value_scale=self.value_scale, salt=self.salt, sum_out=sum_out, count_out=count_out,
+                                             action_out=action_out, **sets)
+
+
 def card_player(samples=None, worlds=None, voids=False, hidden=False, net=False, net_seats=15, net_worlds="det", net_depth=None,
-                net_value_scale=70.0, salt=0, front=False, fused=True, history=None, own=True, say=spelling(), halving=None):
+                net_value_scale=70.0, salt=0, front=False, fused=True, history=None, own=True, say=spelling(), halving=None,
+                net_halving=None):
     """The one validator of a card player's options, in evaluate_playout_vs_bot's names: a CardPlayer, or a ValueError in
     the door's words (say: spelling()).  samples None: 1.  front: the door also asked for a playout-valued exchange or
     bidding.  fused: the door's policy is the fused one.  history: whether the env at hand keeps the play history (None:
     the door makes its env as needs_history says).  own: the door takes net_seats="own".
     halving: a tuple of 1..4 positive world counts, one per round of sequential halving (a HalvingPlayer): it names the worlds
     itself — `worlds` None (or 0) or their sum —, goes with voids / hidden as worlds does, and is not built for net=, the
-    exchange, the bidding or open hands."""
+    exchange, the bidding or open hands.
+    net_halving: such a tuple for the NET-played launch (a NetHalvingPlayer, tarok_playout_cards_net_halving): it requires
+    net=, names the worlds itself as halving does, goes with net_worlds and net_depth, and takes what net= takes — samples
+    None or 1, no exchange, no bidding.  halving= together with net= keeps raising."""
     if halving is not None:
         halving = check_halving(halving, say)
         if net or front:
@@ -109,6 +134,13 @@ def card_player(samples=None, worlds=None, voids=False, hidden=False, net=False,
         if worlds and int(worlds) != sum(halving):
             raise ValueError(say("{halving}= names the worlds of every round: {worlds} is optional and must be their sum"))
         worlds = sum(halving)
+    if net_halving is not None:
+        net_halving = check_halving(net_halving, say, "{net_halving}")
+        if not net:
+            raise ValueError(say("{net_halving}= spends the worlds of the network's playouts: it goes with {net}="))
+        if worlds and int(worlds) != sum(net_halving):
+            raise ValueError(say("{net_halving}= names the worlds of every round: {worlds} is optional and must be their sum"))
+        worlds = sum(net_halving)
     if net_depth is not None:
         if not net:
             raise ValueError(say("{net_depth} stops the network's playouts: it goes with {net}="))
@@ -140,4 +172,6 @@ def card_player(samples=None, worlds=None, voids=False, hidden=False, net=False,
     if kind in WORDS_DTYPE and history is not None and not history:
         raise ValueError(say("the %s worlds read the play history: TarokVecEnv(history=True)" % kind))
     player = CardPlayer(kind, worlds, samples, bool(net), net_seats, net_depth, float(net_value_scale), int(salt))
+    if net_halving is not None:
+        return NetHalvingPlayer(*player, net_halving)
     return player if halving is None else HalvingPlayer(*player, halving)

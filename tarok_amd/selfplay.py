@@ -300,6 +300,10 @@ class SelfPlay:
     sequential halving (tarok_playout_cards_halving: 1..4 rounds, `worlds` omitted or their sum, samples optional: 1) and the
     rows come from tarok_playout_targets_counts on the launch's counts — both inside the captured rollout, the counts
     buffer allocated before capture.  Not with net=True.
+    teacher = dict(net=True, net_halving=(w0, w1, ..), ...): the NETWORK's playouts are spent by sequential halving on a
+    compacted item list (tarok_playout_cards_net_halving, DESIGN 8.21: `worlds` omitted, None or their sum; with net_seats,
+    net_worlds and depth as above) and the rows come from tarok_playout_targets_counts.  The launch's scratch and the counts
+    buffer are allocated before capture; a replayed graph reads the live rollout weights.
 
     front = dict(bid=, exchange=, contracts=, margin=, pass_value=, every=1): the games auto-reset swaps in are bid and
     exchanged by the heads instead of the Bot (TarokVecEnv.front_lines).  bid / exchange: six tensors each
@@ -333,26 +337,27 @@ class SelfPlay:
         self.teacher, self._player, self.distill_coef = None, None, float(distill_coef)
         if teacher is not None:                       # the card player is playout.card_player's; tau and every are the teacher's own
             unknown = set(teacher) - {"worlds", "samples", "tau", "every", "salt", "voids", "hidden", "net", "net_seats", "net_worlds", "depth",
-                                      "halving"}
+                                      "halving", "net_halving"}
             net = bool(teacher.get("net", False))
             if unknown or ("samples" not in teacher and not net and "halving" not in teacher):
                 raise ValueError("teacher: dict(worlds=W, samples=S, tau=tau, every=k, salt=...) or dict(halving=(w0, ..), ...): samples "
                                  "required unless net=True or halving= is given; unknown keys %s" % sorted(unknown))
             if "net_seats" in teacher and not net:
                 raise ValueError("teacher: net_seats names the network's seats inside the playouts: it goes with net=True")
-            p = playout.card_player(int(teacher.get("samples", 1)), int(teacher.get("worlds", 0)), bool(teacher.get("voids", False)),
+            p = playout.card_player(int(teacher.get("samples", 1)), int(teacher.get("worlds") or 0), bool(teacher.get("voids", False)),
                                     bool(teacher.get("hidden", False)), net, int(teacher.get("net_seats", 15)), teacher.get("net_worlds", "det"),
                                     teacher.get("depth"), 1.0 / reward_scale if reward_scale else 0.0, int(teacher.get("salt", 0)),
                                     fused=(hidden == 256) if fused is None else bool(fused), history=getattr(env, "history", False), own=False,
                                     say=playout.spelling("teacher: ", net_depth="depth", net_value_scale="1 / reward_scale"),
-                                    **({"halving": teacher["halving"]} if "halving" in teacher else {}))
+                                    **({"halving": teacher["halving"]} if "halving" in teacher else {}),
+                                    **({"net_halving": teacher["net_halving"]} if teacher.get("net_halving") is not None else {}))
             tau, every = float(teacher.get("tau", 1.0)), int(teacher.get("every", 1))
             if not (every >= 1 and 0.0 <= tau < float("inf")):
                 raise ValueError("teacher: tau >= 0 and finite, every >= 1")
             self._player = p                          # self.teacher: the same player as the dict it has always been
             self.teacher = dict(worlds=p.worlds, samples=p.samples, tau=tau, every=every, salt=p.salt, voids=p.kind == "voids" and not net,
                                 hidden=p.kind == "hidden" and not net, net=net, net_seats=p.net_seats, net_worlds=p.kind if net else "det",
-                                **({} if p.depth is None else dict(depth=p.depth)), **({} if p.halving is None else dict(halving=p.halving)))
+                                **({} if p.depth is None else dict(depth=p.depth)), **({} if p.halving is None else {"net_halving" if net else "halving": p.halving}))
         elif distill_coef:
             raise ValueError("distill_coef weighs the playout teacher's term: pass teacher= as well")
         self.env = env
@@ -593,7 +598,7 @@ class SelfPlay:
     def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None, greedy=False, temperature=None, epsilon=0.0,
                  versus_playout=None, playout_worlds=None, playout_voids=False, playout_exchange=None,
                  playout_hidden=False, playout_bidding=None, pass_value=False, playout_net=False, playout_net_seats=15,
-                 playout_net_worlds="det", playout_net_depth=None, playout_halving=None):
+                 playout_net_worlds="det", playout_net_depth=None, playout_halving=None, playout_net_halving=None):
         """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
         weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
         and on the SAME deals on every rank (seed 0, game offset 0, whatever the training env's are): the figures of
@@ -631,8 +636,13 @@ class SelfPlay:
         None: they run to the last card, as before.
         playout_halving=(w0, w1, ..) (with versus_playout=S; playout_worlds None or their sum; with playout_voids /
         playout_hidden; not with playout_net, playout_exchange or playout_bidding): the fair player spends its worlds by
-        sequential halving (evaluate_playout_vs_bot(halving=...))."""
+        sequential halving (evaluate_playout_vs_bot(halving=...)).
+        playout_net_halving=(w0, w1, ..) (with playout_net; playout_worlds None or their sum; with playout_net_worlds and
+        playout_net_depth): the network's playouts are spent by sequential halving on a compacted item list
+        (evaluate_playout_vs_bot(net_halving=...)).  playout_halving with playout_net keeps raising."""
         halving = {} if playout_halving is None else dict(halving=playout_halving)
+        if playout_net_halving is not None:
+            halving = dict(halving, net_halving=playout_net_halving)
         playout.card_player(versus_playout, playout_worlds, playout_voids, playout_hidden, bool(playout_net), playout_net_seats,
                             playout_net_worlds, playout_net_depth, front=playout_exchange is not None or playout_bidding is not None,
                             say=playout.spelling(pattern="playout_%s", samples="versus_playout"), **halving)
@@ -671,7 +681,8 @@ class SelfPlay:
                                                 net=self._w, net_seats=playout_net_seats,
                                                 **({} if playout_net_worlds == "det" else dict(net_worlds=playout_net_worlds)),
                                                 **({} if playout_net_depth is None else
-                                                   dict(net_depth=playout_net_depth, net_value_scale=1.0 / self.reward_scale)))
+                                                   dict(net_depth=playout_net_depth, net_value_scale=1.0 / self.reward_scale)),
+                                                **({} if playout_net_halving is None else dict(net_halving=playout_net_halving)))
         return own, evaluate_playout_vs_bot(int(versus_playout), n_games, episodes, mix=mix, device=self.env.device_index,
                                             worlds=playout_worlds, voids=bool(playout_voids), exchange=playout_exchange,
                                             hidden=bool(playout_hidden), bidding=playout_bidding,
