@@ -1137,6 +1137,60 @@ int tarok_playout_bids_net_value(tarok_env *env, uint32_t episode, const uint8_t
                                  const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
                                  int32_t *sum_out, void *stream);
 
+/* The four launches above on a COMPACTED item list: the existing launches' definition, word for word —
+ * "waiting", "takes part", worlds, candidates, rows, keys (k = 0), the Bot's exchange inside a bid item and a pass item, the
+ * viewer, every output's shape, and the rule that every row is written — with the items laid without gaps, so a play tile's
+ * 128 forward rows are live items only.
+ *   depth      0 or TAROK_PLAYOUT_FRONT_MAX_DEPTH: every item is played to the last card.  1..12: an item stops at the
+ *              viewer's depth-th decision exactly as the _value launches stop it.
+ *   value_scale finite and > 0; read only where depth stops an item.
+ *   pass_value (bids) 0 or 1, at any depth; at depth 0 or 13 it is tarok_playout_bids_net_value(depth = 13, pass_value = 1).
+ * Consequences, for any weights: at depth 0 or 13 with pass_value = 0 the outputs are the bytes of tarok_playout_exchange_net /
+ * tarok_playout_bids_net; at every other (depth, pass_value) those of tarok_playout_exchange_net_value /
+ * tarok_playout_bids_net_value; hence net_seats = 0 gives tarok_playout_exchange(worlds, 1, sets) and
+ * tarok_playout_bids(worlds, 1) / tarok_playout_bids_pass(worlds, 1).
+ *
+ * The list.  A UNIT is one (game, talon group) for the exchange — 6 n units, unit g * 6 + i, whose live rows are the set
+ * indices d < discard_sets of a group the contract has in a game that takes part — and one (game, viewer) for the bids —
+ * 4 n units, unit g * 4 + v, whose live rows are the rows of `contracts`, plus row 19 with pass_value, for a viewer of the
+ * seat set with a valid deal row.  Each unit has a u32 `on` word of its live rows; the item of the q-th set bit in world w
+ * is base[u] + q x worlds + w, base the exclusive prefix sum of popc(on) x worlds over the units: the items ascend in
+ * (game, group or viewer, row, world).
+ *
+ * The launches (all on `stream`; no host read, no allocation, no synchronisation: capturable, the bids' first call
+ * included): for the bids the deal; the on words; the three launches of tarok_playout_cards_net_halving's prefix sum, over
+ * the units; the items, every slot below the list's total and none at or above it; the playouts, over a grid sized by the
+ * host's BOUND, whose workgroups past the total run nothing; the sums (and the exchange's choice).
+ *
+ * The bound B, which the host computes without reading the env:
+ *     exchange  B = n x 6 x discard_sets x worlds — every slot of the dense grid: the item arrays do NOT shrink (that would
+ *               need the contracts on the host); the gain is the playouts' time;
+ *     bids      B = n x U x R x worlds, U = popc(seats) without seats_per_game, else 4; R = the rows of `contracts` (1 for
+ *               Klop, 4 each for Tri / Dve / Ena, 1 for each contract above) + pass_value.
+ * scratch: device memory, 16-byte aligned, contents undefined afterwards.  With units = 6 n / 4 n:
+ *     bytes = 48 x B + [bids: 40 x n] + 8 x units + 4 x ceil(units / 256) + 4, rounded up to a multiple of 16
+ * — the four item arrays at B, the bids' deal, the units' on and base words, the scan's partials and the total word, in
+ * that order.  tarok_playout_bids_net_list_scratch takes the seat set the launch will get and per_game_seats = 1 where it
+ * will get a seats_per_game array.
+ * The _scratch entries return TAROK_EINVAL for a NULL env, worlds outside 1..TAROK_PLAYOUT_MAX_WORLDS, discard_sets outside
+ * 1..TAROK_EXCHANGE_MAX_SETS, contracts outside 1..TAROK_BID_ALL_CONTRACTS, seats outside 0..15, per_game_seats or pass_value
+ * outside 0..1, and a bound that reaches 2^31 items.  The launches: TAROK_EINVAL (before any HIP call) for all of those, for
+ * everything the existing launches refuse, depth outside 0..TAROK_PLAYOUT_FRONT_MAX_DEPTH, value_scale not finite or <= 0, a
+ * NULL or misaligned scratch or scratch_bytes below the size. */
+int64_t tarok_playout_exchange_net_list_scratch(const tarok_env *env, int worlds, int discard_sets);
+int tarok_playout_exchange_net_list(tarok_env *env, int worlds, int discard_sets, uint64_t salt, int seats,
+                                    const uint8_t *seats_per_game, int net_seats, int depth, float value_scale,
+                                    const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
+                                    const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out,
+                                    int8_t *choice_out, uint8_t *discards_out, void *stream);
+int64_t tarok_playout_bids_net_list_scratch(const tarok_env *env, int worlds, int contracts, int seats, int per_game_seats,
+                                            int pass_value);
+int tarok_playout_bids_net_list(tarok_env *env, uint32_t episode, const uint8_t *deals, int worlds, int contracts,
+                                uint64_t salt, int seats, const uint8_t *seats_per_game, int net_seats, int depth,
+                                float value_scale, int pass_value, const void *w1, const float *b1, const void *w2,
+                                const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
+                                int32_t *sum_out, void *stream);
+
 /* The learner's network input for a minibatch: features_out[j] [256] bf16 (0.0 / 1.0) = the bits
  * of feature_words[index[j]] (feature_words [M,4] u64 as written by feature_words_out; index
  * [n_samples] i64 sample numbers, or NULL for samples 0..n_samples-1).  Gather + expansion in one

@@ -64,16 +64,21 @@ class BidLearner:
     unset.  net_depth: None, or 1..13 — the teacher is playout_bids_net_value, whose playouts stop at the viewer's
     net_depth-th decision and read the value head of `net` there at net_value_scale points per unit (13 never stops).
     pass_value=True goes with net= only together with net_depth: the value launch plays the pass item too, and output 19
-    regresses on its row 19; the plain net launch does not value the pass."""
+    regresses on its row 19; the plain net launch does not value the pass.  net_list=True (with net=): the one teacher
+    launch is playout_bids_net_list, the same numbers from a compacted item list; it values the pass at any depth, so
+    pass_value=True then needs no net_depth.  Nothing else changes."""
 
     def __init__(self, env, worlds=8, samples=None, contracts=K.BID_DEFAULT_CONTRACTS, lr=1e-3, reward_scale=1.0 / 70.0,
-                 playouts_equiv=16, seed=0, pass_value=False, net=None, net_seats=15, net_depth=None, net_value_scale=70.0):
+                 playouts_equiv=16, seed=0, pass_value=False, net=None, net_seats=15, net_list=False, net_depth=None,
+                 net_value_scale=70.0):
+        if net_list and net is None:
+            raise ValueError("net_list packs the network's playouts: it needs net=")
         if net_depth is not None:
             if net is None:
                 raise ValueError("net_depth stops the network's playouts: it needs net=")
             P.check_depth(net_depth, net_value_scale, P.spelling(), max_depth=K.PLAYOUT_FRONT_MAX_DEPTH)
         if net is not None:
-            if pass_value and net_depth is None:
+            if pass_value and net_depth is None and not net_list:
                 raise ValueError("net= without net_depth does not value the pass: pass_value=True goes with the Bot's playouts "
                                  "or with net_depth")
             if samples not in (None, 1):
@@ -84,6 +89,7 @@ class BidLearner:
         samples = (1 if net is not None else 2) if samples is None else samples
         self.net_weights, self.net_seats = net, int(net_seats)
         self.net_depth, self.net_value_scale = net_depth, float(net_value_scale)
+        self.net_list = bool(net_list)
         if not 1 <= int(contracts) <= K.BID_ALL_CONTRACTS:
             raise ValueError("contracts: a bit set within 1..0x3FF")
         if not (reward_scale > 0 and int(playouts_equiv) >= 1):
@@ -132,7 +138,11 @@ class BidLearner:
     def collect(self, episode):
         """(feature_words [N,4,4] int64, sums [N,4,K.BID_ROWS] int32, playouts) of episode `episode`: the teacher's launch
         on every seat and the head's launch for its input rows."""
-        if self.net_weights is not None:
+        if self.net_list:
+            sums = self.env.playout_bids_net_list(self.net_weights, episode, self.worlds, self.net_depth, self.net_value_scale,
+                                                  pass_value=self.pass_value, net_seats=self.net_seats, contracts=self.contracts,
+                                                  salt=self.salt)
+        elif self.net_weights is not None:
             sums = self.env.playout_bids_net_value(self.net_weights, episode, self.worlds, self.net_depth, self.net_value_scale,
                                                    pass_value=self.pass_value, net_seats=self.net_seats, contracts=self.contracts,
                                                    salt=self.salt)

@@ -1136,12 +1136,38 @@ __device__ __forceinline__ void deal_wave(u32 klo, u32 khi, u64 &h0, u64 &h1, u6
 __device__ __forceinline__ u32 bid_row_contract(u32 r) { return r == 0 ? 0u : (r <= 12 ? 1u + ((r - 1u) >> 2) : r - 9u); }
 __device__ __forceinline__ u32 bid_row_king(u32 r) { return (r >= 1 && r <= 12) ? ((r - 1u) & 3u) : 0u; }
 // the rows a contract mask (bit code) plays, as a 19-bit word
-__device__ __forceinline__ u32 bid_row_mask(u32 contracts) {
+TK_HOST_DEVICE __forceinline__ u32 bid_row_mask(u32 contracts) {
     u32 m = contracts & 1u;
     m |= (contracts & 2u) ? 0xFu << 1 : 0u;
     m |= (contracts & 4u) ? 0xFu << 5 : 0u;
     m |= (contracts & 8u) ? 0xFu << 9 : 0u;
     return m | (((contracts >> 4) & 0x3Fu) << 13);
+}
+
+// The compacted item lists of tarok_playout_exchange_net_list / tarok_playout_bids_net_list (include/tarok_env.h, DESIGN
+// §8.22): net_list_slot / net_list_count over UNITS in the place of games.  A unit's `on` word holds its live rows; the
+// init, deal and sum kernels, the host's bounds and tests/host_emu/front_list_host.cpp share these statements.
+//   exchange: unit g * 6 + i is (game, talon group); its rows are the set indices d < sets of a group the contract has (2
+//             groups of three, 3 of two, 6 of one) in a game that takes part — row i * sets + d of the dense launch;
+//   bids:     unit g * 4 + v is (game, viewer); its rows are bid_row_mask(contracts), and row 19 with pass_value, for a
+//             viewer of the seat set with a valid deal row.
+TK_HOST_DEVICE __forceinline__ u32 exchange_list_groups(u32 contract) {
+    const u32 gs = 3u - ((contract - 1u) % 3u);          // group_size
+    return gs == 3u ? 2u : (gs == 2u ? 3u : 6u);
+}
+TK_HOST_DEVICE __forceinline__ u32 exchange_list_on(u32 contract, u32 group, u32 sets, bool takes_part) {
+    return takes_part && group < exchange_list_groups(contract) ? (1u << sets) - 1u : 0u;
+}
+TK_HOST_DEVICE __forceinline__ u32 bid_list_rows(u32 contracts, u32 pass_value) {
+    return bid_row_mask(contracts) | (pass_value ? 1u << 19 : 0u);
+}
+TK_HOST_DEVICE __forceinline__ u32 bid_list_on(u32 contracts, u32 pass_value, bool part) { return part ? bid_list_rows(contracts, pass_value) : 0u; }
+// The hosts' item bounds: every slot of the exchange's grid (the host cannot read the contracts), and for the bids the
+// viewers the seat set can hold (4 with per-game sets) x the rows of `contracts` x the worlds.
+TK_HOST_DEVICE __forceinline__ int64_t exchange_list_bound(int64_t n, u32 sets, u32 worlds) { return n * 6 * (int64_t)sets * (int64_t)worlds; }
+TK_HOST_DEVICE __forceinline__ int64_t bid_list_bound(int64_t n, u32 seats, bool per_game, u32 contracts, u32 pass_value, u32 worlds) {
+    const u32 viewers = per_game ? 4u : (u32)__builtin_popcount(seats & 15u);
+    return n * (int64_t)viewers * (int64_t)__builtin_popcount(bid_list_rows(contracts, pass_value)) * (int64_t)worlds;
 }
 
 // World wkey of a bidder: seat `viewer` holds its twelve cards and has seen nothing else, so the other 42 are dealt

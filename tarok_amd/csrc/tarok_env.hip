@@ -4461,6 +4461,264 @@ TK_KERNEL(TK_BLOCK, 64) void k_playout_bids_net_sum(int64_t rows /* n * 4 * TARO
 }
 
 // ---------------------------------------------------------------------------
+// tarok_playout_exchange_net_list / tarok_playout_bids_net_list: the two launches above on a COMPACTED item
+// list, §8.21's: a UNIT — (game, talon group) for the exchange, (game, viewer) for the bids — has an `on` word of its live
+// rows (exchange_list_on / bid_list_on, tarok_device.h) and, from k_playout_net_list_totals / _scan / _base run over the
+// units, a first slot base[u]; the item of the q-th set bit in world w is net_list_slot(base[u], q, worlds, w).  The deal
+// kernels are the dense kernels' teams, worlds, candidates, barriers and keys looping over live rows only; every slot they
+// write is tested against the host's bound, and every slot below the list's total is written.
+
+// Exchange, first launch: one thread a unit.
+TK_KERNEL(TK_BLOCK, 64) void k_playout_exchange_net_list_init(int64_t units, u32 sets, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                             const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
+                                                             u32 *__restrict__ on) {
+    TK_VGPR_TOP(64, 63);
+    const int64_t u = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
+    if (u >= units) return;
+    const int64_t g = u / 6;
+    Game g0;
+    load_game(g0, s01, s23, g);
+    const ExchangePosition p = exchange_position(g0, seat_sets, seats, sets, g);
+    on[u] = exchange_list_on(g0.contract, (u32)(u - g * 6), sets, p.takes_part);
+}
+
+// Exchange, the items: k_playout_exchange_net_deal (VIEWER: _deal_value) over the game's ncand * worlds live slots.  Row
+// r = i * sets + d is the d-th set bit of unit g * 6 + i, whose word is the low `sets` bits or 0.
+template <bool VIEWER>
+__device__ __forceinline__ void playout_exchange_net_list_deal_body(int64_t n, u32 bound, u64 pseed, u64 offset, u32 worlds, u32 sets, u32 lg,
+                                                                    u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                                    const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
+                                                                    const Counters *__restrict__ cnt, const u32 *__restrict__ on,
+                                                                    const u32 *__restrict__ base, ulonglong2 *__restrict__ i01,
+                                                                    ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
+    __shared__ WorldAB world;
+    __shared__ u32 cand_dpk[(TK_BLOCK >> TK_PX_MIN_LG) * TK_PX_ROWS];
+    const PlayoutTeam t(lg, worlds);
+    const u32 L = t.L, lane = t.lane;
+    const int64_t g = t.g;
+    u32 *cand = cand_dpk + t.team * TK_PX_ROWS;
+    ulonglong2 a = {0, 0}, b = {0, 0};
+    u64 ebase = 0;
+    ExchangePosition p;
+    if (g < n) {
+        a = s01[g]; b = s23[g];
+        Game g0;
+        unpack(g0, a.x, a.y, b.x, b.y);
+        p = exchange_position(g0, seat_sets, seats, sets, g);
+        if (p.takes_part) {
+            ebase = (u64)cnt[g].episode << 28;
+            for (u32 w = lane; w < worlds; w += L) {
+                Game d = g0;
+                redeal_unseen(d, p.declarer, game_key(pseed, offset + (u64)g, (7ULL << 61) | ebase | (63ULL << 22) | (u64)w));
+                world.store(t.slot0 + w, d);
+            }
+            for (u32 r = lane; r < p.ncand; r += L) {
+                u32 i = r / sets, d = r - i * sets;
+                cand[r] = exchange_discards(g0, i, game_key(pseed, offset + (u64)g, (5ULL << 61) | ebase | ((u64)i << 6) | (u64)d));
+            }
+        }
+    }
+    __syncthreads();
+    if (g >= n) return;
+    const u32 live = p.ncand * worlds;                   // (ncand = 0 for a game that does not take part)
+    for (u32 s = lane; s < live; s += L) {
+        const u32 r = s / worlds, w = s - r * worlds, i = r / sets, d = r - i * sets;
+        const int64_t u = g * 6 + (int64_t)i;
+        if (!((on[u] >> d) & 1u)) continue;              // (never: the unit's word is the init kernel's, by the same statement)
+        const u32 it = net_list_slot(base[u], d, worlds, w);
+        if (it >= bound) continue;
+        Game h;
+        unpack(h, a.x, a.y, b.x, b.y);
+        world.load(t.slot0 + w, h);
+        const u32 dpk = cand[r];
+        apply_exchange(h, i, dpk & 255, (dpk >> 8) & 255, (dpk >> 16) & 255);
+        u64 x0, x1, y0, y1;
+        pack(h, x0, x1, y0, y1);
+        i01[it] = make_ulonglong2(x0, x1);
+        i23[it] = make_ulonglong2(y0, y1);
+        ikey[it] = game_key(pseed, offset + (u64)g, (3ULL << 62) | ebase | (63ULL << 22) | ((u64)(8u * i + d) << 16) | ((u64)w << 10));
+        ires[it] = VIEWER ? TK_PN_LIVE | (u64)p.declarer : TK_PN_LIVE;
+    }
+}
+
+#define TK_EXCHANGE_NET_LIST_DEAL(NAME, VIEWER)                                                                                      \
+    TK_KERNEL(TK_BLOCK, 128) void NAME(int64_t n, u32 bound, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 sets, u32 lg,    \
+                                      u32 seats, const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,           \
+                                      const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,                           \
+                                      const u32 *__restrict__ on, const u32 *__restrict__ base, ulonglong2 *__restrict__ i01,         \
+                                      ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {                 \
+        TK_VGPR_TOP(128, 127);                                                                                                        \
+        playout_exchange_net_list_deal_body<VIEWER>(n, bound, pseed, offset, worlds, sets, lg, seats, seat_sets, s01, s23, cnt, on,   \
+                                                    base, i01, i23, ikey, ires);                                                      \
+    }
+TK_EXCHANGE_NET_LIST_DEAL(k_playout_exchange_net_list_deal, false)
+TK_EXCHANGE_NET_LIST_DEAL(k_playout_exchange_net_list_deal_value, true)
+#undef TK_EXCHANGE_NET_LIST_DEAL
+
+// Exchange, the sums and the choice: k_playout_exchange_net_sum reading compact slots; a row whose bit is off sums zeros.
+TK_KERNEL(TK_BLOCK, 64) void k_playout_exchange_net_list_sum(int64_t n, u32 bound, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds,
+                                                            u32 sets, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                            const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
+                                                            const Counters *__restrict__ cnt, const u64 *__restrict__ gkey,
+                                                            const u32 *__restrict__ on, const u32 *__restrict__ base,
+                                                            const u64 *__restrict__ ires, int4 *__restrict__ sum_out,
+                                                            int8_t *__restrict__ choice_out, uint8_t *__restrict__ discards_out) {
+    TK_VGPR_TOP(64, 63);
+    __shared__ __attribute__((aligned(16))) int sums[(TK_BLOCK >> 4) * TK_PX_ROWS * 4];
+    const PlayoutTeam t(4);
+    const int64_t g = t.g;
+    int *row = sums + t.team * (TK_PX_ROWS * 4);
+    const u32 nrows = 6u * sets;
+    if (g < n) {
+        for (u32 r = t.lane; r < nrows; r += t.L) {
+            const u32 i = r / sets, d = r - i * sets, o = on[g * 6 + i];
+            int4 s = make_int4(0, 0, 0, 0);
+            if ((o >> d) & 1u) {
+                const u32 first = net_list_slot(base[g * 6 + i], (u32)__popc(o & ((1u << d) - 1u)), worlds, 0u);
+                for (u32 w = 0; w < worlds; w++) {
+                    const u64 sc = first + w < bound ? ires[first + w] : 0ULL;
+                    s.x += (int)(int16_t)sc; s.y += (int)(int16_t)(sc >> 16); s.z += (int)(int16_t)(sc >> 32); s.w += (int)(int16_t)(sc >> 48);
+                }
+            }
+            reinterpret_cast<int4 *>(row)[r] = s;
+        }
+    }
+    __syncthreads();
+    if (g >= n) return;
+    if (sum_out)
+        for (u32 r = t.lane; r < nrows; r += t.L) sum_out[g * nrows + r] = reinterpret_cast<const int4 *>(row)[r];
+    if ((choice_out || discards_out) && t.lane == 0) {
+        Game g0;
+        load_game(g0, s01, s23, g);
+        const ExchangePosition p = exchange_position(g0, seat_sets, seats, sets, g);
+        int ch = -1;
+        u32 dpk = 0xFFFFFFu;
+        if (p.takes_part) {                              // the first candidate at the maximum of the declarer's sums
+            const u32 best = best_row(row, p.ncand, p.declarer), i = best / sets, d = best - i * sets;
+            ch = (int)i;
+            dpk = exchange_discards(g0, i, game_key(pseed, offset + (u64)g, (5ULL << 61) | ((u64)cnt[g].episode << 28) | ((u64)i << 6) | (u64)d));
+        } else if (p.waiting) {                          // the Bot's own exchange: group 0, its sampler under the game's key
+            ch = 0;
+            dpk = exchange_discards(g0, 0u, gkey[g]);
+        }
+        if (choice_out) choice_out[g] = (int8_t)ch;
+        if (discards_out) {
+            discards_out[g * 3 + 0] = (uint8_t)dpk; discards_out[g * 3 + 1] = (uint8_t)(dpk >> 8);
+            discards_out[g * 3 + 2] = (uint8_t)(dpk >> 16);
+        }
+    }
+}
+
+// Bids, second launch (after k_bid_deal): one thread a unit.
+TK_KERNEL(TK_BLOCK, 64) void k_playout_bids_net_list_init(int64_t n, u32 contracts, u32 pass_value, u32 seats,
+                                                         const uint8_t *__restrict__ seat_sets, const u64 *__restrict__ deal,
+                                                         u32 *__restrict__ on) {
+    TK_VGPR_TOP(64, 63);
+    const int64_t u = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
+    if (u >= n * 4) return;
+    const int64_t g = u >> 2;
+    u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+    if ((deal[g] | deal[n + g] | deal[2 * n + g] | deal[3 * n + g]) == 0) set = 0;      // an invalid deal row
+    on[u] = bid_list_on(contracts, pass_value, (set >> ((u32)u & 3u)) & 1u);
+}
+
+// Bids, the items: k_playout_bids_net_deal (VIEWER: _deal_value, PASS: _deal_value_pass) over the unit's live rows; the two
+// barriers per viewer stand outside every test of the seat set.
+template <bool VIEWER, bool PASS>
+__device__ __forceinline__ void playout_bids_net_list_deal_body(int64_t n, u32 bound, u64 pseed, u64 offset, u32 episode, u32 worlds, u32 lg,
+                                                                u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                                const u64 *__restrict__ deal, const u32 *__restrict__ on,
+                                                                const u32 *__restrict__ base, ulonglong2 *__restrict__ i01,
+                                                                ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
+    static_assert(VIEWER || !PASS, "the pass item carries its viewer");
+    __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS], world_ids[TK_PO_WORLD_SLOTS];
+    const PlayoutTeam t(lg, worlds);
+    const u32 L = t.L, lane = t.lane, slot0 = t.slot0;
+    const int64_t g = t.g;
+    u64 h0 = 0, h1 = 0, h2 = 0, h3 = 0, tal = 0;
+    u32 set = 0;
+    if (g < n) {
+        h0 = deal[g]; h1 = deal[n + g]; h2 = deal[2 * n + g]; h3 = deal[3 * n + g]; tal = deal[4 * n + g];
+        set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+        if ((h0 | h1 | h2 | h3) == 0) set = 0;           // an invalid deal row
+    }
+    const u64 ebase = (u64)episode << 28;
+#pragma unroll 1
+    for (u32 v = 0; v < 4; v++) {
+        const bool part = (set >> v) & 1u;
+        __syncthreads();                                 // the last viewer's items have read their worlds
+        if (part) {
+            for (u32 w = lane; w < worlds; w += L) {
+                u64 A, B, ids;
+                bid_world(h0, h1, h2, h3, tal, v, game_key(pseed, offset + (u64)g, (2ULL << 61) | ebase | ((u64)v << 6) | (u64)w), A, B, ids);
+                world_a[slot0 + w] = A; world_b[slot0 + w] = B; world_ids[slot0 + w] = ids;
+            }
+        }
+        __syncthreads();
+        if (part) {                                      // (part: g < n)
+            const u32 o = on[g * 4 + v], first = base[g * 4 + v];       // (bit 19 only under the PASS form: the launcher pairs them)
+            const u32 count = net_list_count(o, worlds);
+            for (u32 s = lane; s < count; s += L) {
+                const u32 q = s / worlds, w = s - q * worlds, r = kth_bit_word(o, 0u, q);
+                const u32 it = net_list_slot(first, q, worlds, w);
+                if (it >= bound) continue;
+                const u64 pkey = game_key(pseed, offset + (u64)g, (3ULL << 61) | ebase | ((u64)v << 26) | ((u64)r << 21) | ((u64)w << 15));
+                Game h;
+                if constexpr (PASS) {                    // (k_playout_bids_pass's one setup for both kinds of item)
+                    u32 ct = bid_row_contract(r), d = ct == TK_KLOP ? 0u : v, kg = bid_row_king(r);
+                    if (r == (u32)TK_BID_PASS_ROW) pass_round(pkey, v, ct, d, kg);
+                    bid_game_as(h, world_a[slot0 + w], world_b[slot0 + w], world_ids[slot0 + w], ct, d, kg);
+                } else {
+                    bid_game(h, world_a[slot0 + w], world_b[slot0 + w], world_ids[slot0 + w], r, v);
+                }
+                if (h.phase == TK_PHASE_EXCHANGE) bot_exchange(h, pkey);
+                u64 x0, x1, y0, y1;
+                pack(h, x0, x1, y0, y1);
+                i01[it] = make_ulonglong2(x0, x1);
+                i23[it] = make_ulonglong2(y0, y1);
+                ikey[it] = pkey;
+                ires[it] = VIEWER ? TK_PN_LIVE | (u64)v : TK_PN_LIVE;
+            }
+        }
+    }
+}
+
+#define TK_BIDS_NET_LIST_DEAL(NAME, VIEWER, PASS)                                                                                    \
+    TK_KERNEL(TK_BLOCK, 128) void NAME(int64_t n, u32 bound, u64 pseed /* seed ^ salt */, u64 offset, u32 episode, u32 worlds, u32 lg, \
+                                      u32 seats, const uint8_t *__restrict__ seat_sets, const u64 *__restrict__ deal,                 \
+                                      const u32 *__restrict__ on, const u32 *__restrict__ base, ulonglong2 *__restrict__ i01,         \
+                                      ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {                 \
+        TK_VGPR_TOP(128, 127);                                                                                                        \
+        playout_bids_net_list_deal_body<VIEWER, PASS>(n, bound, pseed, offset, episode, worlds, lg, seats, seat_sets, deal,            \
+                                                      on, base, i01, i23, ikey, ires);                                                \
+    }
+TK_BIDS_NET_LIST_DEAL(k_playout_bids_net_list_deal, false, false)
+TK_BIDS_NET_LIST_DEAL(k_playout_bids_net_list_deal_value, true, false)
+TK_BIDS_NET_LIST_DEAL(k_playout_bids_net_list_deal_value_pass, true, true)
+#undef TK_BIDS_NET_LIST_DEAL
+
+// Bids, the sums: one thread per (game, viewer, row); the VIEWER's 16 bits of the row's items, found through the unit's
+// word, summed over the worlds in integers.  A row whose bit is off gets 0: every row is written.
+TK_KERNEL(TK_BLOCK, 64) void k_playout_bids_net_list_sum(int64_t rows /* n * 4 * TAROK_BID_ROWS */, u32 bound, u32 worlds,
+                                                        const u32 *__restrict__ on, const u32 *__restrict__ base,
+                                                        const u64 *__restrict__ ires, int *__restrict__ sum_out) {
+    TK_VGPR_TOP(64, 63);
+    const int64_t i = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
+    if (i >= rows) return;
+    const int64_t u = i / TAROK_BID_ROWS;
+    const u32 r = (u32)(i - u * TAROK_BID_ROWS), v = (u32)(u & 3), o = on[u];
+    int s = 0;
+    if ((o >> r) & 1u) {
+        const u32 first = net_list_slot(base[u], (u32)__popc(o & ((1u << r) - 1u)), worlds, 0u);
+        for (u32 w = 0; w < worlds; w++) {
+            const u64 sc = first + w < bound ? ires[first + w] : 0ULL;
+            s += (int)(int16_t)(sc >> (16 * v));
+        }
+    }
+    sum_out[i] = s;
+}
+
+// ---------------------------------------------------------------------------
 // The reference agent's transition targets in its own form: what Nevronski_igralec.rezultat_stiha
 // builds per trick and rezultat_igre completes (Igralec.py:387-446), for every (trick, game, seat) of a recorded
 // rollout of whole tricks:  dy[54] = -70 on the cards that were not legal at the seat's decision (:392-393), on the
@@ -5487,6 +5745,131 @@ int tarok_playout_bids_net_value(tarok_env *e, uint32_t episode, const uint8_t *
     if (!value_args_ok(depth, TAROK_PLAYOUT_FRONT_MAX_DEPTH, value_scale) || pass_value < 0 || pass_value > 1) return TAROK_EINVAL;
     return launch_playout_bids_net(e, episode, deals, worlds, contracts, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3,
                                    scratch, scratch_bytes, sum_out, stream, depth, value_scale, pass_value);
+}
+
+extern "C++" {
+// A front list launch as the host sizes it: the units, the item bound, the scan's workgroups and the scratch —
+// 48 x bound (the four item arrays), `extra` bytes (the bids' deal), the units' on and base words, the scan's partials (a
+// word per TK_BLOCK units) and the total word, rounded up to 16.  false: a bound that reaches 2^31 items.
+struct FrontListPlan {
+    int64_t units = 0, bound = 0, blocks = 0, bytes = 0;
+};
+static bool front_list_plan(int64_t units, int64_t bound, int64_t extra, FrontListPlan &p) {
+    if (bound >= (1LL << 31)) return false;
+    p.units = units;
+    p.bound = bound;
+    p.blocks = (units + TK_BLOCK - 1) / TK_BLOCK;
+    p.bytes = (bound * TK_PN_ITEM_BYTES + extra + units * 8 + p.blocks * 4 + 4 + 15) & ~(int64_t)15;
+    return true;
+}
+static bool exchange_list_plan(const tarok_env *e, int worlds, int discard_sets, FrontListPlan &p) {
+    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || discard_sets < 1 || discard_sets > TAROK_EXCHANGE_MAX_SETS) return false;
+    return front_list_plan(e->n * 6, exchange_list_bound(e->n, (u32)discard_sets, (u32)worlds), 0, p);
+}
+static bool bid_list_plan(const tarok_env *e, int worlds, int contracts, int seats, int per_game_seats, int pass_value, FrontListPlan &p) {
+    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || contracts < 1 || contracts > TAROK_BID_ALL_CONTRACTS || seats < 0 ||
+        seats > 15 || per_game_seats < 0 || per_game_seats > 1 || pass_value < 0 || pass_value > 1)
+        return false;
+    return front_list_plan(e->n * 4, bid_list_bound(e->n, (u32)seats, per_game_seats != 0, (u32)contracts, (u32)pass_value, (u32)worlds),
+                           e->n * 5 * (int64_t)sizeof(u64), p);
+}
+// What the list launches take of depth and value_scale: 0 .. max_depth, finite and > 0.
+static inline bool list_value_args_ok(int depth, float value_scale) {
+    return depth >= 0 && depth <= TAROK_PLAYOUT_FRONT_MAX_DEPTH && value_scale > 0.f && !__builtin_isinf(value_scale);
+}
+// The list's prefix sum over the units' on words: base[u] and the total word.
+static inline void launch_front_list_scan(const FrontListPlan &p, int worlds, const u32 *on, u32 *base, u32 *part, u32 *total, hipStream_t s) {
+    hipLaunchKernelGGL(k_playout_net_list_totals, grid_for(p.units), dim3(TK_BLOCK), 0, s, p.units, (u32)worlds, on, part);
+    hipLaunchKernelGGL(k_playout_net_list_scan, dim3(1), dim3(TK_BLOCK), 0, s, (u32)p.blocks, part, total);
+    hipLaunchKernelGGL(k_playout_net_list_base, grid_for(p.units), dim3(TK_BLOCK), 0, s, p.units, (u32)worlds, on, part, base);
+}
+// The playouts over the list: the grid is the bound's (one workgroup where the bound is 0: it finds no row below the total).
+static inline void launch_front_list_play(const FrontListPlan &p, const u32 *total, int net_seats, const NetItems &it, const void *w1,
+                                          const float *b1, const void *w2, const float *b2, const void *w3, const float *b3, hipStream_t s,
+                                          int depth, float value_scale) {
+    const int64_t tiles = net_list_tiles(p.bound, PM_M);
+    const dim3 grid((unsigned)(tiles ? tiles : 1));
+    if (depth)
+        hipLaunchKernelGGL(k_playout_net_play_list_value, grid, dim3(TK_BLOCK), 0, s, total, (u32)net_seats, it.i01, it.i23, it.ikey, it.ires,
+                           (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3, (u32)depth, value_scale);
+    else
+        hipLaunchKernelGGL(k_playout_net_play_list, grid, dim3(TK_BLOCK), 0, s, total, (u32)net_seats, it.i01, it.i23, it.ikey, it.ires,
+                           (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3);
+}
+}
+
+int64_t tarok_playout_exchange_net_list_scratch(const tarok_env *e, int worlds, int discard_sets) {
+    FrontListPlan p;
+    return exchange_list_plan(e, worlds, discard_sets, p) ? p.bytes : (int64_t)TAROK_EINVAL;
+}
+
+// tarok_playout_exchange_net / _value on the compacted list: the on words, the scan, the items, the playouts, the sums and the
+// choice — seven launches on `stream`, nothing allocated, no host read.
+int tarok_playout_exchange_net_list(tarok_env *e, int worlds, int discard_sets, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                                    int net_seats, int depth, float value_scale, const void *w1, const float *b1, const void *w2,
+                                    const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
+                                    int32_t *sum_out, int8_t *choice_out, uint8_t *discards_out, void *stream) {
+    FrontListPlan p;
+    if (!playout_args_ok(e, worlds, 1, seats) || !exchange_list_plan(e, worlds, discard_sets, p) || !list_value_args_ok(depth, value_scale) ||
+        !net_args_ok(net_seats, w1, b1, w2, b2, w3, b3, scratch, scratch_bytes, p.bytes) || (!sum_out && !choice_out && !discards_out))
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const NetItems it(scratch, p.bound);
+    u32 *on = reinterpret_cast<u32 *>(it.ires + p.bound), *base = on + p.units, *part = base + p.units, *total = part + p.blocks;
+    const u64 pseed = e->seed ^ (u64)salt;
+    hipLaunchKernelGGL(k_playout_exchange_net_list_init, grid_for(p.units), dim3(TK_BLOCK), 0, s, p.units, (u32)discard_sets, (u32)seats,
+                       seats_per_game, e->s01, e->s23, on);
+    launch_front_list_scan(p, worlds, on, base, part, total, s);
+    const u32 lg = playout_lg(TK_PX_MIN_LG, worlds);     // tarok_playout_exchange's teams at samples = 1
+    hipLaunchKernelGGL(depth ? k_playout_exchange_net_list_deal_value : k_playout_exchange_net_list_deal, playout_grid(e, lg), dim3(TK_BLOCK),
+                       0, s, e->n, (u32)p.bound, pseed, e->offset, (u32)worlds, (u32)discard_sets, lg, (u32)seats, seats_per_game, e->s01,
+                       e->s23, e->cnt, on, base, it.i01, it.i23, it.ikey, it.ires);
+    launch_front_list_play(p, total, net_seats, it, w1, b1, w2, b2, w3, b3, s, depth, value_scale);
+    hipLaunchKernelGGL(k_playout_exchange_net_list_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, s, e->n, (u32)p.bound, pseed,
+                       e->offset, (u32)worlds, (u32)discard_sets, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, e->gkey, on, base,
+                       it.ires, reinterpret_cast<int4 *>(sum_out), choice_out, discards_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int64_t tarok_playout_bids_net_list_scratch(const tarok_env *e, int worlds, int contracts, int seats, int per_game_seats, int pass_value) {
+    FrontListPlan p;
+    return bid_list_plan(e, worlds, contracts, seats, per_game_seats, pass_value, p) ? p.bytes : (int64_t)TAROK_EINVAL;
+}
+
+// tarok_playout_bids_net / _value on the compacted list: the deal, the on words, the scan, the items, the playouts, the sums —
+// eight launches on `stream`, nothing allocated, no host read.  pass_value with depth 0: the _value launch at the depth that
+// never stops, which is the only launch that values a pass.
+int tarok_playout_bids_net_list(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int contracts, uint64_t salt, int seats,
+                                const uint8_t *seats_per_game, int net_seats, int depth, float value_scale, int pass_value, const void *w1,
+                                const float *b1, const void *w2, const float *b2, const void *w3, const float *b3, void *scratch,
+                                int64_t scratch_bytes, int32_t *sum_out, void *stream) {
+    FrontListPlan p;
+    if (!playout_args_ok(e, worlds, 1, seats) || !bid_list_plan(e, worlds, contracts, seats, seats_per_game != nullptr, pass_value, p) ||
+        !list_value_args_ok(depth, value_scale) || !net_args_ok(net_seats, w1, b1, w2, b2, w3, b3, scratch, scratch_bytes, p.bytes) ||
+        !sum_out)
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    if (pass_value && !depth) depth = TAROK_PLAYOUT_FRONT_MAX_DEPTH;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = e->n, rows = n * 4 * TAROK_BID_ROWS;
+    const NetItems it(scratch, p.bound);
+    u64 *deal = it.ires + p.bound;
+    u32 *on = reinterpret_cast<u32 *>(deal + n * 5), *base = on + p.units, *part = base + p.units, *total = part + p.blocks;
+    hipLaunchKernelGGL(k_bid_deal, grid_for(n), dim3(TK_BLOCK), 0, s, n, e->seed, e->offset, episode, deals, deal);
+    hipLaunchKernelGGL(k_playout_bids_net_list_init, grid_for(p.units), dim3(TK_BLOCK), 0, s, n, (u32)contracts, (u32)pass_value, (u32)seats,
+                       seats_per_game, deal, on);
+    launch_front_list_scan(p, worlds, on, base, part, total, s);
+    const u32 lg = playout_lg(TK_PB_MIN_LG, worlds);     // tarok_playout_bids' teams at samples = 1
+    hipLaunchKernelGGL(!depth ? k_playout_bids_net_list_deal : (pass_value ? k_playout_bids_net_list_deal_value_pass : k_playout_bids_net_list_deal_value),
+                       playout_grid(e, lg), dim3(TK_BLOCK), 0, s, n, (u32)p.bound, e->seed ^ (u64)salt, e->offset, episode, (u32)worlds, lg,
+                       (u32)seats, seats_per_game, deal, on, base, it.i01, it.i23, it.ikey, it.ires);
+    launch_front_list_play(p, total, net_seats, it, w1, b1, w2, b2, w3, b3, s, depth, value_scale);
+    hipLaunchKernelGGL(k_playout_bids_net_list_sum, grid_for(rows), dim3(TK_BLOCK), 0, s, rows, (u32)p.bound, (u32)worlds, on, base, it.ires,
+                       sum_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
 }
 
 extern "C++" {

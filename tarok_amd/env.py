@@ -651,6 +651,84 @@ class TarokVecEnv:
             raise ValueError("pass_value=True needs a depth: the plain net launch does not value the pass")
         return TarokVecEnv._bids_net(self, weights, episode, worlds, net_seats, contracts, deals, salt, seats, seats_per_game, sum_out, value)
 
+    @staticmethod
+    def _list_value(net_seats, depth, value_scale):
+        """The checks the two list launches share -> (depth, value_scale) as the ABI takes them (depth 0: to the end)."""
+        if not 0 <= int(net_seats) <= 15:
+            raise ValueError("net_seats: a 4-bit seat set, 0..15")
+        if depth is not None:
+            P.check_depth(depth, value_scale, max_depth=K.PLAYOUT_FRONT_MAX_DEPTH)
+        return (0 if depth is None else int(depth)), float(value_scale)
+
+    def playout_exchange_net_list_scratch(self, worlds, discard_sets=4):
+        """The scratch tensor of playout_exchange_net_list at (worlds, discard_sets) (uint8,
+        tarok_playout_exchange_net_list_scratch bytes: the dense launch's item arrays — the host cannot read the contracts,
+        so they do not shrink — plus 8 bytes per (game, group), the scan's partials and the total word), cached on the env
+        per shape: a caller that captures the launch asks for it BEFORE the capture."""
+        worlds, discard_sets = int(worlds), int(discard_sets)
+        if not 1 <= worlds <= K.PLAYOUT_MAX_WORLDS:
+            raise ValueError("worlds: 1..%d" % K.PLAYOUT_MAX_WORLDS)
+        if not 1 <= discard_sets <= K.EXCHANGE_MAX_SETS:
+            raise ValueError("discard_sets: 1..%d" % K.EXCHANGE_MAX_SETS)
+        return self._scratch(("exchange_list", worlds, discard_sets), self.L.tarok_playout_exchange_net_list_scratch, worlds, discard_sets)
+
+    def playout_exchange_net_list(self, weights, worlds, discard_sets=4, depth=None, value_scale=70.0, net_seats=15, salt=0, seats=15,
+                                  seats_per_game=None, sum_out=None, choice_out=None, discards_out=None):
+        """playout_exchange_net / playout_exchange_net_value on a compacted item list (tarok_playout_exchange_net_list): the
+        same three outputs to the byte, for any weights, with the items of Klop games, of games that do not take part and of
+        the groups a Tri or a Dve does not have left out of the play launch's forward rows.  depth=None or 13: to the last
+        card; 1..12: playout_exchange_net_value's stop at value_scale.  The scratch is
+        playout_exchange_net_list_scratch(worlds, discard_sets); the launch allocates nothing and reads nothing back."""
+        value = self._list_value(net_seats, depth, value_scale)
+        w = self.check_mlp_weights(weights)
+        scratch = self.playout_exchange_net_list_scratch(worlds, discard_sets)
+        with torch.cuda.device(self.device):
+            sum_out = self._empty(sum_out, (self.n, 6 * int(discard_sets), 4), torch.int32)
+            choice_out = self._empty(choice_out, self.n, torch.int8)
+            discards_out = self._empty(discards_out, (self.n, 3), torch.uint8)
+            _native.check(self.L.tarok_playout_exchange_net_list(
+                self._h, int(worlds), int(discard_sets), int(salt) & ((1 << 64) - 1), int(seats), self._p(self._seat_sets(seats_per_game)),
+                int(net_seats), *value, *[self._p(t) for t in w], self._p(scratch), scratch.numel(), self._p(sum_out), self._p(choice_out),
+                self._p(discards_out), self._stream()))
+        return sum_out, choice_out, discards_out
+
+    def playout_bids_net_list_scratch(self, worlds, contracts=K.BID_DEFAULT_CONTRACTS, seats=15, per_game=False, pass_value=False):
+        """The scratch tensor of playout_bids_net_list (uint8, tarok_playout_bids_net_list_scratch bytes): 48 bytes for every
+        item the seat set can hold — games x viewers in `seats` (4 with per_game=True, a seats_per_game launch) x the rows of
+        `contracts` (+ 1 with pass_value) x worlds — plus 72 bytes per game and the scan's words: 624 * worlds per game for
+        one viewer at the default contracts, against playout_bids_net_scratch's 3,840 * worlds.  Cached on the env per
+        shape: a caller that captures the launch asks for it BEFORE the capture."""
+        worlds, contracts, seats = int(worlds), int(contracts), int(seats)
+        if not 1 <= worlds <= K.PLAYOUT_MAX_WORLDS:
+            raise ValueError("worlds: 1..%d" % K.PLAYOUT_MAX_WORLDS)
+        if not 1 <= contracts <= K.BID_ALL_CONTRACTS:
+            raise ValueError("contracts: a bit set within 1..0x3FF")
+        if not 0 <= seats <= 15:
+            raise ValueError("seats: a 4-bit seat set, 0..15")
+        key = ("bids_list", worlds, contracts, 15 if per_game else seats, bool(per_game), bool(pass_value))
+        return self._scratch(key, self.L.tarok_playout_bids_net_list_scratch, worlds, contracts, seats, int(bool(per_game)),
+                             int(bool(pass_value)))
+
+    def playout_bids_net_list(self, weights, episode, worlds, depth=None, value_scale=70.0, pass_value=False, net_seats=15,
+                              contracts=K.BID_DEFAULT_CONTRACTS, deals=None, salt=0, seats=15, seats_per_game=None, sum_out=None):
+        """playout_bids_net / playout_bids_net_value on a compacted item list (tarok_playout_bids_net_list): the same sums to
+        the byte, for any weights, with the slots of rows outside `contracts`, of viewers outside the seat set and of
+        invalid deal rows neither allocated nor run through the play launch's forward.  depth=None or 13: to the last card;
+        1..12: playout_bids_net_value's stop at value_scale.  pass_value=True is taken at ANY depth: with depth=None it is
+        playout_bids_net_value(depth=13, pass_value=True).  The scratch is playout_bids_net_list_scratch(worlds, contracts,
+        seats, seats_per_game is not None, pass_value); the launch allocates nothing and reads nothing back."""
+        value = self._list_value(net_seats, depth, value_scale) + (int(bool(pass_value)),)
+        w = self.check_mlp_weights(weights)
+        scratch = self.playout_bids_net_list_scratch(worlds, contracts, seats, seats_per_game is not None, pass_value)
+        deals = self._dev(deals, torch.uint8, (self.n, 54))
+        with torch.cuda.device(self.device):
+            sum_out = self._empty(sum_out, (self.n, 4, K.BID_ROWS), torch.int32)
+            _native.check(self.L.tarok_playout_bids_net_list(
+                self._h, int(episode), self._p(deals), int(worlds), int(contracts), int(salt) & ((1 << 64) - 1), int(seats),
+                self._p(self._seat_sets(seats_per_game)), int(net_seats), *value, *[self._p(t) for t in w], self._p(scratch),
+                scratch.numel(), self._p(sum_out), self._stream()))
+        return sum_out
+
     def bid_round(self, episode, sums, playouts, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, seats=15, seats_per_game=None,
                   pass_value=False):
         """The bidding round of every game on the device (tarok_bid_round; Igra.licitacija's control flow): the seats of

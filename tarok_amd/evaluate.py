@@ -135,21 +135,24 @@ def _net_front_args(net, net_seats, samples, what, net_depth=None, net_value_sca
     return TarokVecEnv.check_mlp_weights(net), (lambda seats: seats if net_seats == "own" else net_seats)
 
 
-def _bid_net_front(net, net_seats, worlds, salt, threshold, contracts, net_depth=None, net_value_scale=70.0, pass_value=False):
+def _bid_net_front(net, net_seats, worlds, salt, threshold, contracts, net_depth=None, net_value_scale=70.0, pass_value=False,
+                   net_list=False):
     """_bid_front whose playouts the network plays: ONE tarok_playout_bids_net at `worlds` with the pass's seat set —
     net_seats inside the playouts, or the pass's own set for "own" — and ONE tarok_bid_round at playouts = worlds.
     net_depth: tarok_playout_bids_net_value in its place; pass_value (with net_depth only): its pass item, and
-    tarok_bid_round_pass with `threshold` the margin over the pass, as for the Bot teacher."""
+    tarok_bid_round_pass with `threshold` the margin over the pass, as for the Bot teacher.  net_list: the same arguments
+    to tarok_playout_bids_net_list in either launch's place."""
     def make(env):
         sums = _empty(env, (env.n, 4, K.BID_ROWS), torch.int32)
 
         def bid(env, episode, seats):
             if net_depth is None:
-                env.playout_bids_net(net, episode, worlds, net_seats=net_seats(seats), contracts=contracts, salt=salt, seats=seats, sum_out=sums)
+                (env.playout_bids_net_list if net_list else env.playout_bids_net)(net, episode, worlds, net_seats=net_seats(seats), contracts=contracts, salt=salt, seats=seats, sum_out=sums)
                 c, d, k = env.bid_round(episode, sums, int(worlds), threshold=threshold, contracts=contracts, seats=seats)
             else:
-                env.playout_bids_net_value(net, episode, worlds, net_depth, net_value_scale, pass_value=pass_value,
-                                           net_seats=net_seats(seats), contracts=contracts, salt=salt, seats=seats, sum_out=sums)
+                (env.playout_bids_net_list if net_list else env.playout_bids_net_value)(
+                    net, episode, worlds, net_depth, net_value_scale, pass_value=pass_value, net_seats=net_seats(seats), contracts=contracts,
+                    salt=salt, seats=seats, sum_out=sums)
                 c, d, k = env.bid_round(episode, sums, int(worlds), threshold=threshold, contracts=contracts, seats=seats,
                                         pass_value=pass_value)
             setup = dict(contract=c, declarer=d, king_suit=k)
@@ -194,21 +197,24 @@ def _exchange_front(worlds, samples, discard_sets, salt):
     return make
 
 
-def _exchange_net_front(net, net_seats, worlds, discard_sets, salt, net_depth=None, net_value_scale=70.0):
+def _exchange_net_front(net, net_seats, worlds, discard_sets, salt, net_depth=None, net_value_scale=70.0, net_list=False):
     """_exchange_front whose playouts the network plays: ONE tarok_playout_exchange_net at (worlds, discard_sets) with the
     pass's seat set — net_seats inside the playouts, or the pass's own set for "own" — and one tarok_exchange.  net_depth:
-    tarok_playout_exchange_net_value in its place."""
+    tarok_playout_exchange_net_value in its place.  net_list: the same arguments to tarok_playout_exchange_net_list in either
+    launch's place."""
     def make(env):
         sums = _empty(env, (env.n, 6 * int(discard_sets), 4), torch.int32)
         chosen = dict(choice=_empty(env, env.n, torch.int8), discards=_empty(env, (env.n, 3), torch.uint8))
 
         def exchange(env, seats):
             if net_depth is None:
-                env.playout_exchange_net(net, worlds, discard_sets, net_seats=net_seats(seats), salt=salt, seats=seats, sum_out=sums,
-                                         choice_out=chosen["choice"], discards_out=chosen["discards"])
+                (env.playout_exchange_net_list if net_list else env.playout_exchange_net)(
+                    net, worlds, discard_sets, net_seats=net_seats(seats), salt=salt, seats=seats, sum_out=sums, choice_out=chosen["choice"],
+                    discards_out=chosen["discards"])
             else:
-                env.playout_exchange_net_value(net, worlds, discard_sets, net_depth, net_value_scale, net_seats=net_seats(seats), salt=salt,
-                                               seats=seats, sum_out=sums, choice_out=chosen["choice"], discards_out=chosen["discards"])
+                (env.playout_exchange_net_list if net_list else env.playout_exchange_net_value)(
+                    net, worlds, discard_sets, net_depth, net_value_scale, net_seats=net_seats(seats), salt=salt, seats=seats, sum_out=sums,
+                    choice_out=chosen["choice"], discards_out=chosen["discards"])
             env.exchange(chosen["choice"], chosen["discards"])
             return dict(chosen, sums=sums)
         return exchange
@@ -494,7 +500,7 @@ def evaluate_exchange_vs_bot(worlds, samples, discard_sets, n_games, episodes, s
 
 
 def evaluate_exchange_net_vs_bot(net, worlds, discard_sets, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None,
-                                 net_seats=15, cards=None, net_depth=None, net_value_scale=70.0):
+                                 net_seats=15, cards=None, net_list=False, net_depth=None, net_value_scale=70.0):
     """evaluate_exchange_vs_bot with the playouts played by a network: net = policy_mlp's six tensors; in pass 1 + k the
     games seat k declared get their exchange from ONE tarok_playout_exchange_net at (worlds, discard_sets) — one playout
     per (candidate, world), the network's greedy card on the seats of net_seats (a 4-bit set of absolute seats; "own":
@@ -503,9 +509,12 @@ def evaluate_exchange_net_vs_bot(net, worlds, discard_sets, n_games, episodes, s
     Pass 0 is the Bot everywhere either way: evaluate_exchange_vs_bot's pass 0 on the same deals.  (A function of its own,
     not arguments of evaluate_exchange_vs_bot: that call's parameter list is pinned as it stands.)  net_depth: None, or
     1..13 — tarok_playout_exchange_net_value: the playouts stop at the declarer's net_depth-th decision and read the value
-    head of `net` there at net_value_scale points per unit."""
+    head of `net` there at net_value_scale points per unit.  net_list=True: the launch is tarok_playout_exchange_net_list
+    with the same arguments — the same numbers from a compacted item list."""
+    if net_list and net is None:
+        raise ValueError("net_list packs the network's playouts: it needs net=")
     exchange = _exchange_net_front(*_net_front_args(net, net_seats, None, "candidate", net_depth, net_value_scale), worlds, discard_sets,
-                                   salt, net_depth, net_value_scale)
+                                   salt, net_depth, net_value_scale, bool(net_list))
     front = _front(inspect is not None, exchange=exchange)
     return duplicate_advantage(_passes(n_games, episodes, front, _front_cards(cards), inspect, device=device, seed=seed, mix=mix))
 
@@ -523,7 +532,7 @@ def evaluate_exchangenet_vs_bot(weights, n_games, episodes, seed=0, mix=K.MIX_BO
 
 def evaluate_bidding_vs_bot(worlds, samples, n_games, episodes, seed=0, device=0, salt=0, threshold=0,
                             contracts=K.BID_DEFAULT_CONTRACTS, inspect=None, pass_value=False, net=None, net_seats=15, cards=None,
-                            net_depth=None, net_value_scale=70.0):
+                            net_list=False, net_depth=None, net_value_scale=70.0):
     """What is the bid alone worth?  The five duplicate passes on K.MIX_BOT's deals with the Bot making EVERY exchange and
     playing EVERY card; in pass 1 + k seat k bids by playouts — tarok_playout_bids at (worlds, samples) over `contracts`,
     then tarok_bid_round with `threshold` — against three Bot bidders, and calls its king by the same sums.  Pass 0 is the
@@ -538,17 +547,20 @@ def evaluate_bidding_vs_bot(worlds, samples, n_games, episodes, seed=0, device=0
     greedy card, in the Bot's place.  net_depth (with net): None, or 1..13 — tarok_playout_bids_net_value: the playouts stop
     at the viewer's net_depth-th decision and read the value head of `net` there at net_value_scale points per unit; then
     pass_value=True is allowed too — the launch plays the pass item, and tarok_bid_round_pass holds every bid against it as
-    for the Bot teacher.  With the defaults the call issues the launches it always did."""
+    for the Bot teacher.  net_list=True (with net): the launch is tarok_playout_bids_net_list with the same arguments — the
+    same numbers from a compacted item list.  With the defaults the call issues the launches it always did."""
     if net is None:
         if net_depth is not None:
             raise ValueError("net_depth stops the network's playouts: it needs net=")
+        if net_list:
+            raise ValueError("net_list packs the network's playouts: it needs net=")
         bid = _bid_front((worlds, samples), salt, threshold, contracts, pass_value)
     else:
         if pass_value and net_depth is None:
             raise ValueError("net= without net_depth does not value the pass: pass_value=True goes with the Bot's playouts or "
                              "with net_depth")
         bid = _bid_net_front(*_net_front_args(net, net_seats, samples, "option", net_depth, net_value_scale), worlds, salt, threshold,
-                             contracts, net_depth, net_value_scale, bool(pass_value))
+                             contracts, net_depth, net_value_scale, bool(pass_value), bool(net_list))
     front = _front(inspect is not None, bid=bid)
     return duplicate_advantage(_passes(n_games, episodes, front, _front_cards(cards), inspect, device=device, seed=seed, mix=K.MIX_BOT))
 

@@ -71,12 +71,15 @@ class ExchangeLearner:
     playout_exchange_net at (worlds, discard_sets) with the network's greedy card on the seats of net_seats inside the
     playouts, playouts = worlds; `samples` must be 1 or left unset.  net_depth: None, or 1..13 — the teacher is
     playout_exchange_net_value, whose playouts stop at the declarer's net_depth-th decision and read the value head of `net`
-    there at net_value_scale points per unit (13 never stops)."""
+    there at net_value_scale points per unit (13 never stops).  net_list=True (with net=): the one teacher launch is
+    playout_exchange_net_list, the same numbers from a compacted item list; nothing else changes."""
 
     def __init__(self, env, worlds=8, samples=None, discard_sets=4, lr=1e-3, reward_scale=1.0 / 70.0, seed=0, net=None, net_seats=15,
-                 net_depth=None, net_value_scale=70.0):
+                 net_list=False, net_depth=None, net_value_scale=70.0):
         if not reward_scale > 0:
             raise ValueError("reward_scale > 0")
+        if net_list and net is None:
+            raise ValueError("net_list packs the network's playouts: it needs net=")
         if net_depth is not None:
             if net is None:
                 raise ValueError("net_depth stops the network's playouts: it needs net=")
@@ -90,6 +93,7 @@ class ExchangeLearner:
         samples = (1 if net is not None else 2) if samples is None else samples
         self.net_weights, self.net_seats = net, int(net_seats)
         self.net_depth, self.net_value_scale = net_depth, float(net_value_scale)
+        self.net_list = bool(net_list)
         self.env = env
         self.device = env.device if env is not None else torch.device("cpu")
         self.worlds, self.samples, self.discard_sets = int(worlds), int(samples), int(discard_sets)
@@ -133,7 +137,10 @@ class ExchangeLearner:
         reset with the exchange deferred, the teacher's launch on every declarer, its candidates' discards and the head's
         launch for its input rows.  The games are left waiting for the exchange."""
         self.env.reset(episode=episode, defer_exchange=True)
-        if self.net_weights is not None:
+        if self.net_list:
+            sums, _, _ = self.env.playout_exchange_net_list(self.net_weights, self.worlds, self.discard_sets, self.net_depth,
+                                                            self.net_value_scale, net_seats=self.net_seats, salt=self.salt)
+        elif self.net_weights is not None:
             sums, _, _ = self.env.playout_exchange_net_value(self.net_weights, self.worlds, self.discard_sets, self.net_depth,
                                                              self.net_value_scale, net_seats=self.net_seats, salt=self.salt)
         else:
