@@ -138,14 +138,10 @@ class BidLearner:
     def collect(self, episode):
         """(feature_words [N,4,4] int64, sums [N,4,K.BID_ROWS] int32, playouts) of episode `episode`: the teacher's launch
         on every seat and the head's launch for its input rows."""
-        if self.net_list:
-            sums = self.env.playout_bids_net_list(self.net_weights, episode, self.worlds, self.net_depth, self.net_value_scale,
-                                                  pass_value=self.pass_value, net_seats=self.net_seats, contracts=self.contracts,
-                                                  salt=self.salt)
-        elif self.net_weights is not None:
-            sums = self.env.playout_bids_net_value(self.net_weights, episode, self.worlds, self.net_depth, self.net_value_scale,
-                                                   pass_value=self.pass_value, net_seats=self.net_seats, contracts=self.contracts,
-                                                   salt=self.salt)
+        if self.net_list or self.net_weights is not None:
+            launch = P.bids_net_launch(self.env, self.net_list, True)
+            sums = launch(self.net_weights, episode, self.worlds, self.net_depth, self.net_value_scale, pass_value=self.pass_value,
+                          net_seats=self.net_seats, contracts=self.contracts, salt=self.salt)
         else:
             sums = self.env.playout_bids(episode, self.worlds, self.samples, contracts=self.contracts, salt=self.salt,
                                          pass_value=self.pass_value)

@@ -35,6 +35,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <tuple>
 #include <type_traits>
 #include <utility>
 
@@ -3610,64 +3611,29 @@ __device__ __forceinline__ void playout_net_deal_body(int64_t n, u64 pseed, u64 
     }
 }
 
-// tarok_playout_cards_net: redeal_unseen's worlds.
-TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,
-                                                const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
-                                                const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
-                                                ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,
-                                                u64 *__restrict__ ires) {
-    TK_VGPR_TOP(128, 127);
-    playout_net_deal_body<DealUnseen>(n, pseed, offset, worlds, lg, seats, seat_sets, s01, s23, cnt, nullptr, i01, i23, ikey, ires);
-}
-
-// tarok_playout_cards_net_voids: the worlds honour shown voids (redeal_voids under voids[g], as k_playout_voids).
-TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal_voids(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,
-                                                      const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
-                                                      const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
-                                                      const u32 *__restrict__ voids, ulonglong2 *__restrict__ i01,
-                                                      ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
-    TK_VGPR_TOP(128, 127);
-    playout_net_deal_body<DealVoids>(n, pseed, offset, worlds, lg, seats, seat_sets, s01, s23, cnt, voids, i01, i23, ikey, ires);
-}
-
-// tarok_playout_cards_net_hidden: the worlds also re-deal Klop's talon and the declarer's discards (redeal_hidden under
-// played[g], as k_playout_hidden; WorldABCT slots: 36 bytes x TK_PO_WORLD_SLOTS = 2,304 bytes of LDS).
-TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal_hidden(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,
-                                                       const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
-                                                       const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
-                                                       const u64 *__restrict__ played_words, ulonglong2 *__restrict__ i01,
-                                                       ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
-    TK_VGPR_TOP(128, 127);
-    playout_net_deal_body<DealHidden>(n, pseed, offset, worlds, lg, seats, seat_sets, s01, s23, cnt, played_words, i01, i23, ikey, ires);
-}
-
-// tarok_playout_cards_net_value's first launches: the three above with the viewer in a live item's marker.
-TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal_value(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,
-                                                      const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
-                                                      const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
-                                                      ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,
-                                                      u64 *__restrict__ ires) {
-    TK_VGPR_TOP(128, 127);
-    playout_net_deal_body<DealUnseen, true>(n, pseed, offset, worlds, lg, seats, seat_sets, s01, s23, cnt, nullptr, i01, i23, ikey, ires);
-}
-
-TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal_value_voids(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,
-                                                            const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
-                                                            const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
-                                                            const u32 *__restrict__ voids, ulonglong2 *__restrict__ i01,
-                                                            ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
-    TK_VGPR_TOP(128, 127);
-    playout_net_deal_body<DealVoids, true>(n, pseed, offset, worlds, lg, seats, seat_sets, s01, s23, cnt, voids, i01, i23, ikey, ires);
-}
-
-TK_KERNEL(TK_BLOCK, 128) void k_playout_net_deal_value_hidden(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,
-                                                             const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
-                                                             const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
-                                                             const u64 *__restrict__ played_words, ulonglong2 *__restrict__ i01,
-                                                             ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
-    TK_VGPR_TOP(128, 127);
-    playout_net_deal_body<DealHidden, true>(n, pseed, offset, worlds, lg, seats, seat_sets, s01, s23, cnt, played_words, i01, i23, ikey, ires);
-}
+// The six first launches, one per dealer with and without the viewer in a live item's marker (tarok_playout_cards_net_value's).
+// WORDS: the body's words argument; after it the kernel's own words parameter, which a det kernel does not have.
+//   k_playout_net_deal         redeal_unseen's worlds
+//   k_playout_net_deal_voids   the worlds honour shown voids (redeal_voids under voids[g], as k_playout_voids)
+//   k_playout_net_deal_hidden  the worlds also re-deal Klop's talon and the declarer's discards (redeal_hidden under played[g],
+//                              as k_playout_hidden; WorldABCT slots: 36 bytes x TK_PO_WORLD_SLOTS = 2,304 bytes of LDS)
+#define TK_NET_DEAL(NAME, DEALER, VIEWER, WORDS, ...)                                                                              \
+    TK_KERNEL(TK_BLOCK, 128) void NAME(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,           \
+                                      const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,                    \
+                                      const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt, __VA_ARGS__             \
+                                      ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,           \
+                                      u64 *__restrict__ ires) {                                                                     \
+        TK_VGPR_TOP(128, 127);                                                                                                      \
+        playout_net_deal_body<DEALER, VIEWER>(n, pseed, offset, worlds, lg, seats, seat_sets, s01, s23, cnt, WORDS, i01, i23, ikey, \
+                                              ires);                                                                                \
+    }
+TK_NET_DEAL(k_playout_net_deal, DealUnseen, false, nullptr, )
+TK_NET_DEAL(k_playout_net_deal_voids, DealVoids, false, voids, const u32 *__restrict__ voids, )
+TK_NET_DEAL(k_playout_net_deal_hidden, DealHidden, false, played_words, const u64 *__restrict__ played_words, )
+TK_NET_DEAL(k_playout_net_deal_value, DealUnseen, true, nullptr, )
+TK_NET_DEAL(k_playout_net_deal_value_voids, DealVoids, true, voids, const u32 *__restrict__ voids, )
+TK_NET_DEAL(k_playout_net_deal_value_hidden, DealHidden, true, played_words, const u64 *__restrict__ played_words, )
+#undef TK_NET_DEAL
 
 // Second launch: the playouts.  A workgroup of 256 threads keeps one tile of PM_M = 128 items resident — their packed
 // states and keys in LDS, owned by threads 0..127 — and plays them card by card: feature words (policy_feature_words on
@@ -5329,29 +5295,257 @@ static int launch_playout_cards(Kernel kernel, tarok_env *e, int worlds, int sam
     return TAROK_OK;
 }
 
-// One halving launch: the schedule is read here and goes to the kernel as its cumulative ends, a byte a round; lg is the
-// card launches' at (all worlds) x samples, so the team's worlds fit its slots.  `words`: the dealer's per-game words (a
-// typed null for the det kind).
+// A halving schedule as the host reads it: the rounds' world counts, their cumulative ends — also packed a byte a round, as
+// the Bot-played kernels take them — and the total.
+struct HalvingSchedule {
+    int rounds = 0, worlds = 0;
+    int w[TAROK_PLAYOUT_MAX_ROUNDS] = {0, 0, 0, 0}, end[TAROK_PLAYOUT_MAX_ROUNDS] = {0, 0, 0, 0};
+    u32 ends = 0;
+};
+// false: rounds outside 1..TAROK_PLAYOUT_MAX_ROUNDS, a NULL schedule, a count < 1 or a sum above TAROK_PLAYOUT_MAX_WORLDS.
+static bool halving_schedule(int rounds, const int *round_worlds, HalvingSchedule &h) {
+    if (rounds < 1 || rounds > TAROK_PLAYOUT_MAX_ROUNDS || !round_worlds) return false;
+    h.rounds = rounds;
+    for (int r = 0; r < rounds; r++) {
+        if (round_worlds[r] < 1 || round_worlds[r] > TAROK_PLAYOUT_MAX_WORLDS - h.worlds) return false;
+        h.w[r] = round_worlds[r];
+        h.end[r] = h.worlds += round_worlds[r];
+        h.ends |= (u32)h.worlds << (8 * r);
+    }
+    return true;
+}
+
+// One halving launch: the schedule goes to the kernel as its cumulative ends, a byte a round; lg is the card launches' at
+// (all worlds) x samples, so the team's worlds fit its slots.  `words`: the dealer's per-game words (a typed null for the
+// det kind).
 template <class Kernel, class Word>
 static int launch_playout_halving(Kernel kernel, tarok_env *e, int rounds, const int *round_worlds, int samples, uint64_t salt, int seats,
                                   const uint8_t *seats_per_game, int32_t *sum_out, int32_t *count_out, uint8_t *action_out, void *stream,
                                   const Word *words) {
-    if (rounds < 1 || rounds > TAROK_PLAYOUT_MAX_ROUNDS || !round_worlds) return TAROK_EINVAL;
-    int worlds = 0;
-    u32 ends = 0;
-    for (int r = 0; r < rounds; r++) {
-        if (round_worlds[r] < 1 || round_worlds[r] > TAROK_PLAYOUT_MAX_WORLDS - worlds) return TAROK_EINVAL;
-        worlds += round_worlds[r];
-        ends |= (u32)worlds << (8 * r);
-    }
-    if (!playout_args_ok(e, worlds, samples, seats) || (!sum_out && !count_out && !action_out)) return TAROK_EINVAL;
+    HalvingSchedule h;
+    if (!halving_schedule(rounds, round_worlds, h) || !playout_args_ok(e, h.worlds, samples, seats) ||
+        (!sum_out && !count_out && !action_out))
+        return TAROK_EINVAL;
     HIPCHK(hipSetDevice(e->device));
-    const u32 lg = playout_lg(TK_PO_MIN_LG, worlds * samples);
-    hipLaunchKernelGGL(kernel, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset, ends,
+    const u32 lg = playout_lg(TK_PO_MIN_LG, h.worlds * samples);
+    hipLaunchKernelGGL(kernel, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset, h.ends,
                        (u32)samples, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, e->gkey, words,
                        reinterpret_cast<int4 *>(sum_out), reinterpret_cast<int4 *>(count_out), action_out);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
+}
+
+// The world kind of a launch that takes (kind, words): f(the kind as an integral constant, the words as the kind's type —
+// a typed null for DET, whose dealer reads none).  The caller has checked the kind's range and what it asks of `words`.
+template <class F>
+static int for_world_kind(int kind, const void *words, F f) {
+    if (kind == TAROK_NET_WORLDS_VOIDS) return f(std::integral_constant<int, TAROK_NET_WORLDS_VOIDS>{}, (const u32 *)words);
+    if (kind == TAROK_NET_WORLDS_HIDDEN) return f(std::integral_constant<int, TAROK_NET_WORLDS_HIDDEN>{}, (const u64 *)words);
+    return f(std::integral_constant<int, TAROK_NET_WORLDS_DET>{}, (const NoWord *)nullptr);
+}
+// A kernel family's member of for_world_kind's kind K: one row per family, in TAROK_NET_WORLDS_* order.
+#define TK_OF_KIND(K, DET, VOIDS, HIDDEN) std::get<decltype(K)::value>(std::make_tuple(DET, VOIDS, HIDDEN))
+static inline bool world_kind_ok(int kind) { return kind >= TAROK_NET_WORLDS_DET && kind <= TAROK_NET_WORLDS_HIDDEN; }
+
+// tarok_playout_bids and its _pass twin: the deal, then the playout kernel given
+template <class Kernel>
+static int launch_playout_bids(Kernel kernel, tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int samples, int contracts,
+                               uint64_t salt, int seats, const uint8_t *seats_per_game, int32_t *sum_out, void *stream) {
+    if (!playout_args_ok(e, worlds, samples, seats) || contracts < 1 || contracts > TAROK_BID_ALL_CONTRACTS) return TAROK_EINVAL;
+    if (!sum_out) return TAROK_OK;
+    HIPCHK(hipSetDevice(e->device));
+    if (!e->bid_deal) HIPCHK(hipMalloc((void **)&e->bid_deal, (size_t)e->n * 5 * sizeof(u64)));   // on the first call; tarok_destroy frees it
+    hipLaunchKernelGGL(k_bid_deal, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, episode, deals, e->bid_deal);
+    // 16 lanes per game or more, so a workgroup's at most 16 teams keep their 80 sums each in 5 KiB
+    static_assert(TAROK_BID_ROWS == TK_BID_ROWS && TAROK_BID_ROWS % 4 == 0, "a viewer's rows are whole 16-byte pieces");
+    static_assert(TAROK_BID_PASS_ROW == TK_BID_PASS_ROW && TK_BID_PASS_ROW == TK_BID_OPTIONS && TK_BID_PASS_ROW < 32, "row 19, in the key's five bits");
+    const u32 lg = playout_lg(TK_PB_MIN_LG, worlds * samples);
+    hipLaunchKernelGGL(kernel, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset, episode, (u32)worlds, (u32)samples, lg, (u32)contracts, (u32)seats, seats_per_game,
+                       e->bid_deal, reinterpret_cast<int4 *>(sum_out));
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+// ---- the net-played launches: what the dense and the list entries share
+#define TK_WEIGHTS(w1, b1, w2, b2, w3, b3) PolicyWeights{(const __bf16 *)(w1), b1, (const __bf16 *)(w2), b2, (const __bf16 *)(w3), b3}
+
+// The four item arrays of a net launch in its scratch (tarok_playout_cards_net's layout).
+struct NetItems {
+    ulonglong2 *i01, *i23;
+    u64 *ikey, *ires;
+    NetItems(void *scratch, int64_t items)
+        : i01(reinterpret_cast<ulonglong2 *>(scratch)), i23(i01 + items), ikey(reinterpret_cast<u64 *>(i23 + items)), ires(ikey + items) {}
+};
+static inline bool net_args_ok(int net_seats, const PolicyWeights &w, const void *scratch, int64_t scratch_bytes, int64_t need) {
+    return net_seats >= 0 && net_seats <= 15 && w.w1 && w.b1 && w.w2 && w.b2 && w.w3 && w.b3 && scratch && !((uintptr_t)scratch & 15) &&
+           need >= 0 && scratch_bytes >= need;
+}
+// What an entry takes of depth and value_scale: lo..hi — each entry point states its own range — and a finite value_scale > 0.
+static inline bool depth_args_ok(int depth, int lo, int hi, float value_scale) {
+    return depth >= lo && depth <= hi && value_scale > 0.f && !__builtin_isinf(value_scale);
+}
+
+// The play launch over a net launch's items, the one place that picks among the four play kernels.  total NULL: the dense
+// layout, `items` the host's count; else the compacted list, whose count is the device's total word and `items` the host's
+// bound: the grid is the bound's (one workgroup where the bound is 0: it finds no row below the total).  depth = 0: to the
+// last card; else the _value kernel, whose live items carry their viewers (the caller's item kernel is the _value form).
+static inline void launch_net_play(int64_t items, const u32 *total, int net_seats, const NetItems &it, const PolicyWeights &w,
+                                   hipStream_t s, int depth, float value_scale) {
+    const int64_t tiles = net_list_tiles(items, PM_M);
+    const dim3 grid((unsigned)(tiles ? tiles : 1));
+#define TK_LAUNCH_NET_PLAY(K, COUNT, ...)                                                                                          \
+    hipLaunchKernelGGL(K, grid, dim3(TK_BLOCK), 0, s, COUNT, (u32)net_seats, it.i01, it.i23, it.ikey, it.ires, w.w1, w.b1, w.w2, \
+                       w.b2, w.w3, w.b3, ##__VA_ARGS__)
+    if (total) {
+        if (depth) TK_LAUNCH_NET_PLAY(k_playout_net_play_list_value, total, (u32)depth, value_scale);
+        else TK_LAUNCH_NET_PLAY(k_playout_net_play_list, total);
+    } else {
+        if (depth) TK_LAUNCH_NET_PLAY(k_playout_net_play_value, items, (u32)depth, value_scale);
+        else TK_LAUNCH_NET_PLAY(k_playout_net_play, items);
+    }
+#undef TK_LAUNCH_NET_PLAY
+}
+
+// One net card launch: the items (`deal`, the dealer's kernel, with its per-game `words`: a typed null for a det kernel,
+// which takes none), the playouts, the sums — three launches on `stream`, nothing allocated.  depth = 0: the playouts run
+// to the last card; else (checked by tarok_playout_cards_net_value, the only caller that gives one) they stop at the
+// viewer's depth-th decision, and `deal` is a k_playout_net_deal_value*.
+template <class Kernel, class Word>
+static int launch_playout_cards_net(Kernel deal, tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                                    const Word *words, int net_seats, const PolicyWeights &w, void *scratch, int64_t scratch_bytes,
+                                    int32_t *sum_out, uint8_t *action_out, void *stream, int depth, float value_scale) {
+    constexpr bool has_words = !std::is_same<Word, NoWord>::value;
+    if (!playout_args_ok(e, worlds, 1, seats) || !net_args_ok(net_seats, w, scratch, scratch_bytes, tarok_playout_net_scratch(e, worlds)) ||
+        (!sum_out && !action_out) || (has_words && !words))
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    const int64_t items = e->n * TAROK_PLAYOUT_RANKS * (int64_t)worlds;
+    const NetItems it(scratch, items);
+    const u32 lg = playout_lg(TK_PO_MIN_LG, worlds);
+    auto launch_deal = [&](auto... kwords) {
+        hipLaunchKernelGGL(deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
+                           (u32)worlds, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, kwords..., it.i01, it.i23, it.ikey, it.ires);
+    };
+    if constexpr (has_words) launch_deal(words); else launch_deal();
+    launch_net_play(items, nullptr, net_seats, it, w, (hipStream_t)stream, depth, value_scale);
+    hipLaunchKernelGGL(k_playout_net_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, (u32)worlds,
+                       (u32)seats, seats_per_game, e->s01, e->s23, e->gkey, it.ires, reinterpret_cast<int4 *>(sum_out), action_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+// tarok_playout_exchange_net and its _value twin: the items, the playouts, the sums and the choice — three launches on `stream`,
+// nothing allocated.  depth = 0: the playouts run to the last card; else (checked by tarok_playout_exchange_net_value, the only
+// caller that gives one) they stop at the declarer's depth-th decision.
+static int launch_playout_exchange_net(tarok_env *e, int worlds, int discard_sets, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                                       int net_seats, const PolicyWeights &w, void *scratch, int64_t scratch_bytes, int32_t *sum_out,
+                                       int8_t *choice_out, uint8_t *discards_out, void *stream, int depth, float value_scale) {
+    if (!playout_args_ok(e, worlds, 1, seats) || discard_sets < 1 || discard_sets > TAROK_EXCHANGE_MAX_SETS ||
+        !net_args_ok(net_seats, w, scratch, scratch_bytes, tarok_playout_exchange_net_scratch(e, worlds, discard_sets)) ||
+        (!sum_out && !choice_out && !discards_out))
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    const int64_t items = e->n * 6 * (int64_t)discard_sets * (int64_t)worlds;
+    const NetItems it(scratch, items);
+    const u32 lg = playout_lg(TK_PX_MIN_LG, worlds);     // tarok_playout_exchange's teams at samples = 1
+    hipLaunchKernelGGL(depth ? k_playout_exchange_net_deal_value : k_playout_exchange_net_deal, playout_grid(e, lg), dim3(TK_BLOCK), 0,
+                       (hipStream_t)stream, e->n, items, e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)discard_sets, lg, (u32)seats,
+                       seats_per_game, e->s01, e->s23, e->cnt, it.i01, it.i23, it.ikey, it.ires);
+    launch_net_play(items, nullptr, net_seats, it, w, (hipStream_t)stream, depth, value_scale);
+    hipLaunchKernelGGL(k_playout_exchange_net_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, items,
+                       e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)discard_sets, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt,
+                       e->gkey, it.ires, reinterpret_cast<int4 *>(sum_out), choice_out, discards_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+// tarok_playout_bids_net and its _value twin: the deal, the items, the playouts, the sums — four launches on `stream`, nothing
+// allocated.  depth = 0: the playouts run to the last card and `pass` is 0; else (checked by tarok_playout_bids_net_value, the
+// only caller that gives one) they stop at the viewer's depth-th decision, and pass = 1 makes row 19's slots items.
+static int launch_playout_bids_net(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int contracts, uint64_t salt, int seats,
+                                   const uint8_t *seats_per_game, int net_seats, const PolicyWeights &w, void *scratch,
+                                   int64_t scratch_bytes, int32_t *sum_out, void *stream, int depth, float value_scale, int pass) {
+    if (!playout_args_ok(e, worlds, 1, seats) || contracts < 1 || contracts > TAROK_BID_ALL_CONTRACTS ||
+        !net_args_ok(net_seats, w, scratch, scratch_bytes, tarok_playout_bids_net_scratch(e, worlds)) || !sum_out)
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    const int64_t rows = e->n * 4 * TAROK_BID_ROWS, items = rows * (int64_t)worlds;
+    const NetItems it(scratch, items);
+    u64 *deal = it.ires + items;
+    hipLaunchKernelGGL(k_bid_deal, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, episode, deals, deal);
+    const u32 lg = playout_lg(TK_PB_MIN_LG, worlds);     // tarok_playout_bids' teams at samples = 1
+    hipLaunchKernelGGL(!depth ? k_playout_bids_net_deal : (pass ? k_playout_bids_net_deal_value_pass : k_playout_bids_net_deal_value),
+                       playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, items, e->seed ^ (u64)salt, e->offset, episode,
+                       (u32)worlds, lg, (u32)contracts, (u32)seats, seats_per_game, deal, it.i01, it.i23, it.ikey, it.ires);
+    launch_net_play(items, nullptr, net_seats, it, w, (hipStream_t)stream, depth, value_scale);
+    hipLaunchKernelGGL(k_playout_bids_net_sum, grid_for(rows), dim3(TK_BLOCK), 0, (hipStream_t)stream, rows, items, (u32)worlds, it.ires,
+                       sum_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+// The scratch of a list launch, layout and size from the same offsets: the four item arrays at the bound (NetItems), `extra`
+// bytes of the launch's own, per unit the on word and `more` further words (halving's alive), per unit the base word, the
+// scan's partials (a word per TK_BLOCK units) and the total word, rounded up to 16.
+struct ListArrays : NetItems {
+    char *extra;
+    u32 *on, *base, *part, *total;
+};
+struct ListScratch {
+    int64_t units = 0, bound = 0, blocks = 0, extra = 0, more = 0, bytes = 0;
+    int64_t on_at() const { return bound * TK_PN_ITEM_BYTES + extra; }
+    int64_t base_at() const { return on_at() + (1 + more) * units * 4; }
+    int64_t total_at() const { return base_at() + (units + blocks) * 4; }
+    // false: a bound that reaches 2^31 items (the list's slots are 32-bit words)
+    bool plan(int64_t units_, int64_t bound_, int64_t extra_, int64_t more_ = 0) {
+        if (bound_ >= (1LL << 31)) return false;
+        units = units_, bound = bound_, extra = extra_, more = more_;
+        blocks = (units + TK_BLOCK - 1) / TK_BLOCK;
+        bytes = (total_at() + 4 + 15) & ~(int64_t)15;
+        return true;
+    }
+    ListArrays carve(void *scratch) const {
+        char *s = reinterpret_cast<char *>(scratch);
+        u32 *base = reinterpret_cast<u32 *>(s + base_at());
+        return ListArrays{NetItems(scratch, bound), s + on_at() - extra, reinterpret_cast<u32 *>(s + on_at()), base, base + units,
+                          reinterpret_cast<u32 *>(s + total_at())};
+    }
+};
+// The list's prefix sum over the units' on words at `worlds` items each: base[u] and the total word.
+static inline void launch_list_scan(const ListScratch &p, const ListArrays &a, int worlds, hipStream_t s) {
+    hipLaunchKernelGGL(k_playout_net_list_totals, grid_for(p.units), dim3(TK_BLOCK), 0, s, p.units, (u32)worlds, a.on, a.part);
+    hipLaunchKernelGGL(k_playout_net_list_scan, dim3(1), dim3(TK_BLOCK), 0, s, (u32)p.blocks, a.part, a.total);
+    hipLaunchKernelGGL(k_playout_net_list_base, grid_for(p.units), dim3(TK_BLOCK), 0, s, p.units, (u32)worlds, a.on, a.part, a.base);
+}
+
+// A net halving launch as the host sizes it: the schedule, and the list at the largest round's bound over the games as units.
+// Its extension of the list's layout: a game's running sums (16 bytes a rank) and counts (4) are the extra bytes, its alive
+// word follows its on word.  false: a NULL env, a schedule halving_schedule refuses, or a round whose bound reaches 2^31.
+struct NetHalvingPlan {
+    HalvingSchedule h;
+    ListScratch list;
+};
+static bool net_halving_plan(const tarok_env *e, int rounds, const int *round_worlds, NetHalvingPlan &p) {
+    if (!e || !halving_schedule(rounds, round_worlds, p.h)) return false;
+    int64_t bound = 0;
+    for (int r = 0; r < rounds; r++) {
+        const int64_t b = net_list_bound(e->n, (u32)r, (u32)p.h.w[r]);
+        bound = b > bound ? b : bound;
+    }
+    return p.list.plan(e->n, bound, e->n * TAROK_PLAYOUT_RANKS * (int64_t)(sizeof(int4) + sizeof(int)), 1);
+}
+// The front list launches as the host sizes them: the exchange's units are (game, group), the bids' (game, viewer), whose
+// extra bytes are k_bid_deal's 40 per game.
+static bool exchange_list_plan(const tarok_env *e, int worlds, int discard_sets, ListScratch &p) {
+    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || discard_sets < 1 || discard_sets > TAROK_EXCHANGE_MAX_SETS) return false;
+    return p.plan(e->n * 6, exchange_list_bound(e->n, (u32)discard_sets, (u32)worlds), 0);
+}
+static bool bid_list_plan(const tarok_env *e, int worlds, int contracts, int seats, int per_game_seats, int pass_value, ListScratch &p) {
+    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || contracts < 1 || contracts > TAROK_BID_ALL_CONTRACTS || seats < 0 ||
+        seats > 15 || per_game_seats < 0 || per_game_seats > 1 || pass_value < 0 || pass_value > 1)
+        return false;
+    return p.plan(e->n * 4, bid_list_bound(e->n, (u32)seats, per_game_seats != 0, (u32)contracts, (u32)pass_value, (u32)worlds),
+                  e->n * 5 * (int64_t)sizeof(u64));
 }
 }
 
@@ -5370,100 +5564,42 @@ int64_t tarok_playout_net_scratch(const tarok_env *e, int worlds) {
     return e->n * TAROK_PLAYOUT_RANKS * (int64_t)worlds * TK_PN_ITEM_BYTES;
 }
 
-extern "C++" {
-// The four item arrays of a net launch in its scratch (tarok_playout_cards_net's layout).
-struct NetItems {
-    ulonglong2 *i01, *i23;
-    u64 *ikey, *ires;
-    NetItems(void *scratch, int64_t items)
-        : i01(reinterpret_cast<ulonglong2 *>(scratch)), i23(i01 + items), ikey(reinterpret_cast<u64 *>(i23 + items)), ires(ikey + items) {}
-};
-static inline bool net_args_ok(int net_seats, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
-                               const float *b3, const void *scratch, int64_t scratch_bytes, int64_t need) {
-    return net_seats >= 0 && net_seats <= 15 && w1 && b1 && w2 && b2 && w3 && b3 && scratch && !((uintptr_t)scratch & 15) && need >= 0 &&
-           scratch_bytes >= need;
-}
-// The play launch over a net launch's items.  depth = 0: k_playout_net_play, to the last card; else k_playout_net_play_value,
-// whose live items carry their viewers (the caller's item kernel is the _value form).
-static inline void launch_net_play(int64_t items, int net_seats, const NetItems &it, const void *w1, const float *b1, const void *w2,
-                                   const float *b2, const void *w3, const float *b3, void *stream, int depth = 0, float value_scale = 0.f) {
-    const dim3 grid((unsigned)((items + PM_M - 1) / PM_M));
-    if (depth)
-        hipLaunchKernelGGL(k_playout_net_play_value, grid, dim3(TK_BLOCK), 0, (hipStream_t)stream, items, (u32)net_seats, it.i01, it.i23,
-                           it.ikey, it.ires, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3, (u32)depth, value_scale);
-    else
-        hipLaunchKernelGGL(k_playout_net_play, grid, dim3(TK_BLOCK), 0, (hipStream_t)stream, items, (u32)net_seats, it.i01, it.i23, it.ikey,
-                           it.ires, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3);
-}
-// What the _value entries take more: a depth in 1..max_depth and a finite value_scale > 0.
-static inline bool value_args_ok(int depth, int max_depth, float value_scale) {
-    return depth >= 1 && depth <= max_depth && value_scale > 0.f && !__builtin_isinf(value_scale);
-}
-
-// One net card launch: the items (`deal`, the dealer's kernel, with its per-game `words` where it has any), the playouts,
-// the sums — three launches on `stream`, nothing allocated.  depth = 0: the playouts run to the last card; 1..12 (checked
-// by tarok_playout_cards_net_value, the only caller that gives one): they stop at the viewer's depth-th decision.
-template <class Kernel, class... Words>
-static int launch_playout_cards_net(Kernel deal, tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
-                                    int net_seats, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
-                                    const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out, uint8_t *action_out,
-                                    void *stream, int depth, float value_scale, Words... words) {
-    if (!playout_args_ok(e, worlds, 1, seats) ||
-        !net_args_ok(net_seats, w1, b1, w2, b2, w3, b3, scratch, scratch_bytes, tarok_playout_net_scratch(e, worlds)) ||
-        (!sum_out && !action_out) || (... || !words))
-        return TAROK_EINVAL;
-    HIPCHK(hipSetDevice(e->device));
-    const int64_t items = e->n * TAROK_PLAYOUT_RANKS * (int64_t)worlds;
-    const NetItems it(scratch, items);
-    const u32 lg = playout_lg(TK_PO_MIN_LG, worlds);
-    hipLaunchKernelGGL(deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
-                       (u32)worlds, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, words..., it.i01, it.i23, it.ikey, it.ires);
-    launch_net_play(items, net_seats, it, w1, b1, w2, b2, w3, b3, stream, depth, value_scale);   // (depth: `deal` is a k_playout_net_deal_value*)
-    hipLaunchKernelGGL(k_playout_net_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, (u32)worlds,
-                       (u32)seats, seats_per_game, e->s01, e->s23, e->gkey, it.ires, reinterpret_cast<int4 *>(sum_out), action_out);
-    HIPCHK(hipGetLastError());
-    return TAROK_OK;
-}
-}
-
+// (the plain dense entries take no depth and no value_scale: nothing of either is looked at)
 int tarok_playout_cards_net(tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game, int net_seats,
                             const void *w1, const float *b1, const void *w2, const float *b2, const void *w3, const float *b3,
                             void *scratch, int64_t scratch_bytes, int32_t *sum_out, uint8_t *action_out, void *stream) {
-    return launch_playout_cards_net(k_playout_net_deal, e, worlds, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3, scratch,
-                                    scratch_bytes, sum_out, action_out, stream, 0, 0.f);
+    return launch_playout_cards_net(k_playout_net_deal, e, worlds, salt, seats, seats_per_game, (const NoWord *)nullptr, net_seats,
+                                    TK_WEIGHTS(w1, b1, w2, b2, w3, b3), scratch, scratch_bytes, sum_out, action_out, stream, 0, 0.f);
 }
 
 int tarok_playout_cards_net_voids(tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
                                   const uint32_t *voids, int net_seats, const void *w1, const float *b1, const void *w2, const float *b2,
                                   const void *w3, const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out,
                                   uint8_t *action_out, void *stream) {
-    return launch_playout_cards_net(k_playout_net_deal_voids, e, worlds, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3,
-                                    scratch, scratch_bytes, sum_out, action_out, stream, 0, 0.f, voids);
+    return launch_playout_cards_net(k_playout_net_deal_voids, e, worlds, salt, seats, seats_per_game, voids, net_seats,
+                                    TK_WEIGHTS(w1, b1, w2, b2, w3, b3), scratch, scratch_bytes, sum_out, action_out, stream, 0, 0.f);
 }
 
 int tarok_playout_cards_net_hidden(tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
                                    const uint64_t *played, int net_seats, const void *w1, const float *b1, const void *w2,
                                    const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
                                    int32_t *sum_out, uint8_t *action_out, void *stream) {
-    return launch_playout_cards_net(k_playout_net_deal_hidden, e, worlds, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3,
-                                    scratch, scratch_bytes, sum_out, action_out, stream, 0, 0.f, (const u64 *)played);
+    return launch_playout_cards_net(k_playout_net_deal_hidden, e, worlds, salt, seats, seats_per_game, (const u64 *)played, net_seats,
+                                    TK_WEIGHTS(w1, b1, w2, b2, w3, b3), scratch, scratch_bytes, sum_out, action_out, stream, 0, 0.f);
 }
 
 int tarok_playout_cards_net_value(tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game, int kind,
                                   const void *words, int net_seats, int depth, float value_scale, const void *w1, const float *b1,
                                   const void *w2, const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
                                   int32_t *sum_out, uint8_t *action_out, void *stream) {
-    if (kind < TAROK_NET_WORLDS_DET || kind > TAROK_NET_WORLDS_HIDDEN || (kind == TAROK_NET_WORLDS_DET && words) || depth < 1 ||
-        depth > TAROK_PLAYOUT_MAX_DEPTH || !(value_scale > 0.f) || __builtin_isinf(value_scale))
+    // DET with words is refused here; VOIDS / HIDDEN without them by the launcher, as the plain entries of those kinds
+    if (!world_kind_ok(kind) || (kind == TAROK_NET_WORLDS_DET && words) || !depth_args_ok(depth, 1, TAROK_PLAYOUT_MAX_DEPTH, value_scale))
         return TAROK_EINVAL;
-    if (kind == TAROK_NET_WORLDS_VOIDS)
-        return launch_playout_cards_net(k_playout_net_deal_value_voids, e, worlds, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3,
-                                        b3, scratch, scratch_bytes, sum_out, action_out, stream, depth, value_scale, (const u32 *)words);
-    if (kind == TAROK_NET_WORLDS_HIDDEN)
-        return launch_playout_cards_net(k_playout_net_deal_value_hidden, e, worlds, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3,
-                                        b3, scratch, scratch_bytes, sum_out, action_out, stream, depth, value_scale, (const u64 *)words);
-    return launch_playout_cards_net(k_playout_net_deal_value, e, worlds, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3, scratch,
-                                    scratch_bytes, sum_out, action_out, stream, depth, value_scale);
+    return for_world_kind(kind, words, [&](auto k, auto *kwords) {
+        const auto deal = TK_OF_KIND(k, k_playout_net_deal_value, k_playout_net_deal_value_voids, k_playout_net_deal_value_hidden);
+        return launch_playout_cards_net(deal, e, worlds, salt, seats, seats_per_game, kwords, net_seats, TK_WEIGHTS(w1, b1, w2, b2, w3, b3),
+                                        scratch, scratch_bytes, sum_out, action_out, stream, depth, value_scale);
+    });
 }
 
 int tarok_playout_exchange(tarok_env *e, int worlds, int samples, int discard_sets, uint64_t salt, int seats,
@@ -5486,47 +5622,21 @@ int64_t tarok_playout_exchange_net_scratch(const tarok_env *e, int worlds, int d
     return e->n * 6 * (int64_t)discard_sets * (int64_t)worlds * TK_PN_ITEM_BYTES;
 }
 
-// tarok_playout_exchange_net and its _value twin: the items, the playouts, the sums and the choice — three launches on `stream`,
-// nothing allocated.  depth = 0: the playouts run to the last card; 1..13 (checked by tarok_playout_exchange_net_value, the only
-// caller that gives one): they stop at the declarer's depth-th decision.
-static int launch_playout_exchange_net(tarok_env *e, int worlds, int discard_sets, uint64_t salt, int seats, const uint8_t *seats_per_game,
-                                       int net_seats, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
-                                       const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out, int8_t *choice_out,
-                                       uint8_t *discards_out, void *stream, int depth, float value_scale) {
-    if (!playout_args_ok(e, worlds, 1, seats) || discard_sets < 1 || discard_sets > TAROK_EXCHANGE_MAX_SETS ||
-        !net_args_ok(net_seats, w1, b1, w2, b2, w3, b3, scratch, scratch_bytes, tarok_playout_exchange_net_scratch(e, worlds, discard_sets)) ||
-        (!sum_out && !choice_out && !discards_out))
-        return TAROK_EINVAL;
-    HIPCHK(hipSetDevice(e->device));
-    const int64_t items = e->n * 6 * (int64_t)discard_sets * (int64_t)worlds;
-    const NetItems it(scratch, items);
-    const u32 lg = playout_lg(TK_PX_MIN_LG, worlds);     // tarok_playout_exchange's teams at samples = 1
-    hipLaunchKernelGGL(depth ? k_playout_exchange_net_deal_value : k_playout_exchange_net_deal, playout_grid(e, lg), dim3(TK_BLOCK), 0,
-                       (hipStream_t)stream, e->n, items, e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)discard_sets, lg, (u32)seats,
-                       seats_per_game, e->s01, e->s23, e->cnt, it.i01, it.i23, it.ikey, it.ires);
-    launch_net_play(items, net_seats, it, w1, b1, w2, b2, w3, b3, stream, depth, value_scale);
-    hipLaunchKernelGGL(k_playout_exchange_net_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, items,
-                       e->seed ^ (u64)salt, e->offset, (u32)worlds, (u32)discard_sets, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt,
-                       e->gkey, it.ires, reinterpret_cast<int4 *>(sum_out), choice_out, discards_out);
-    HIPCHK(hipGetLastError());
-    return TAROK_OK;
-}
-
 int tarok_playout_exchange_net(tarok_env *e, int worlds, int discard_sets, uint64_t salt, int seats, const uint8_t *seats_per_game,
                                int net_seats, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
                                const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out, int8_t *choice_out,
                                uint8_t *discards_out, void *stream) {
-    return launch_playout_exchange_net(e, worlds, discard_sets, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3, scratch,
-                                       scratch_bytes, sum_out, choice_out, discards_out, stream, 0, 0.f);
+    return launch_playout_exchange_net(e, worlds, discard_sets, salt, seats, seats_per_game, net_seats, TK_WEIGHTS(w1, b1, w2, b2, w3, b3),
+                                       scratch, scratch_bytes, sum_out, choice_out, discards_out, stream, 0, 0.f);
 }
 
 int tarok_playout_exchange_net_value(tarok_env *e, int worlds, int discard_sets, uint64_t salt, int seats, const uint8_t *seats_per_game,
                                      int net_seats, int depth, float value_scale, const void *w1, const float *b1, const void *w2,
                                      const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
                                      int32_t *sum_out, int8_t *choice_out, uint8_t *discards_out, void *stream) {
-    if (!value_args_ok(depth, TAROK_PLAYOUT_FRONT_MAX_DEPTH, value_scale)) return TAROK_EINVAL;
-    return launch_playout_exchange_net(e, worlds, discard_sets, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3, scratch,
-                                       scratch_bytes, sum_out, choice_out, discards_out, stream, depth, value_scale);
+    if (!depth_args_ok(depth, 1, TAROK_PLAYOUT_FRONT_MAX_DEPTH, value_scale)) return TAROK_EINVAL;
+    return launch_playout_exchange_net(e, worlds, discard_sets, salt, seats, seats_per_game, net_seats, TK_WEIGHTS(w1, b1, w2, b2, w3, b3),
+                                       scratch, scratch_bytes, sum_out, choice_out, discards_out, stream, depth, value_scale);
 }
 
 int tarok_shown_voids(tarok_env *e, uint32_t *voids_out, void *stream) {
@@ -5560,58 +5670,16 @@ int tarok_playout_cards_hidden(tarok_env *e, int worlds, int samples, uint64_t s
 int tarok_playout_cards_halving(tarok_env *e, int kind, const void *words, int rounds, const int *round_worlds, int samples, uint64_t salt,
                                 int seats, const uint8_t *seats_per_game, int32_t *sum_out, int32_t *count_out, uint8_t *action_out,
                                 void *stream) {
-    if (kind < TAROK_NET_WORLDS_DET || kind > TAROK_NET_WORLDS_HIDDEN || (kind == TAROK_NET_WORLDS_DET) != !words) return TAROK_EINVAL;
-    if (kind == TAROK_NET_WORLDS_VOIDS)
-        return launch_playout_halving(k_playout_halving_voids, e, rounds, round_worlds, samples, salt, seats, seats_per_game, sum_out, count_out,
-                                      action_out, stream, (const u32 *)words);
-    if (kind == TAROK_NET_WORLDS_HIDDEN)
-        return launch_playout_halving(k_playout_halving_hidden, e, rounds, round_worlds, samples, salt, seats, seats_per_game, sum_out,
-                                      count_out, action_out, stream, (const u64 *)words);
-    return launch_playout_halving(k_playout_halving_det, e, rounds, round_worlds, samples, salt, seats, seats_per_game, sum_out, count_out,
-                                  action_out, stream, (const NoWord *)nullptr);
-}
-
-extern "C++" {
-// A net halving launch's schedule as the host reads it: the cumulative ends, the largest round's item bound and the scratch.
-struct NetHalvingPlan {
-    int rounds = 0, worlds = 0;
-    int w[TAROK_PLAYOUT_MAX_ROUNDS] = {0, 0, 0, 0}, end[TAROK_PLAYOUT_MAX_ROUNDS] = {0, 0, 0, 0};
-    int64_t bound = 0, blocks = 0, bytes = 0;            // max_r net_list_bound; the scan's workgroups; the scratch
-};
-// false: a NULL env, rounds outside 1..TAROK_PLAYOUT_MAX_ROUNDS, a NULL schedule, a count < 1, a sum above
-// TAROK_PLAYOUT_MAX_WORLDS, or a round whose bound reaches 2^31 items (the list's slots are 32-bit words).
-static bool net_halving_plan(const tarok_env *e, int rounds, const int *round_worlds, NetHalvingPlan &p) {
-    if (!e || rounds < 1 || rounds > TAROK_PLAYOUT_MAX_ROUNDS || !round_worlds) return false;
-    p.rounds = rounds;
-    for (int r = 0; r < rounds; r++) {
-        if (round_worlds[r] < 1 || round_worlds[r] > TAROK_PLAYOUT_MAX_WORLDS - p.worlds) return false;
-        p.w[r] = round_worlds[r];
-        p.worlds += round_worlds[r];
-        p.end[r] = p.worlds;
-        const int64_t b = net_list_bound(e->n, (u32)r, (u32)round_worlds[r]);
-        if (b >= (1LL << 31)) return false;
-        p.bound = b > p.bound ? b : p.bound;
-    }
-    p.blocks = (e->n + TK_BLOCK - 1) / TK_BLOCK;
-    const int64_t raw = p.bound * TK_PN_ITEM_BYTES + e->n * 252 + p.blocks * 4 + 4;
-    p.bytes = (raw + 15) & ~(int64_t)15;
-    return true;
-}
+    if (!world_kind_ok(kind) || (kind == TAROK_NET_WORLDS_DET) != !words) return TAROK_EINVAL;
+    return for_world_kind(kind, words, [&](auto k, auto *kwords) {
+        return launch_playout_halving(TK_OF_KIND(k, k_playout_halving_det, k_playout_halving_voids, k_playout_halving_hidden), e, rounds,
+                                      round_worlds, samples, salt, seats, seats_per_game, sum_out, count_out, action_out, stream, kwords);
+    });
 }
 
 int64_t tarok_playout_net_halving_scratch_bytes(const tarok_env *e, int rounds, const int *round_worlds) {
     NetHalvingPlan p;
-    return net_halving_plan(e, rounds, round_worlds, p) ? p.bytes : (int64_t)TAROK_EINVAL;
-}
-
-extern "C++" {
-template <class Kernel, class Word>
-static void launch_net_list_deal(Kernel deal, tarok_env *e, u64 pseed, int e0, int w, int seats, const uint8_t *seats_per_game,
-                                 const Word *words, const u32 *on, const u32 *base, const NetItems &it, hipStream_t s) {
-    const u32 lg = playout_lg(TK_PO_MIN_LG, w);
-    hipLaunchKernelGGL(deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, s, e->n, pseed, e->offset, (u32)e0, (u32)w, lg, (u32)seats,
-                       seats_per_game, e->s01, e->s23, e->cnt, words, on, base, it.i01, it.i23, it.ikey, it.ires);
-}
+    return net_halving_plan(e, rounds, round_worlds, p) ? p.list.bytes : (int64_t)TAROK_EINVAL;
 }
 
 int tarok_playout_cards_net_halving(tarok_env *e, int kind, const void *words, int rounds, const int *round_worlds, uint64_t salt,
@@ -5620,73 +5688,42 @@ int tarok_playout_cards_net_halving(tarok_env *e, int kind, const void *words, i
                                     void *scratch, int64_t scratch_bytes, int32_t *sum_out, int32_t *count_out, uint8_t *action_out,
                                     void *stream) {
     NetHalvingPlan p;
-    if (!e || kind < TAROK_NET_WORLDS_DET || kind > TAROK_NET_WORLDS_HIDDEN || (kind == TAROK_NET_WORLDS_DET) != !words ||
-        !net_halving_plan(e, rounds, round_worlds, p) || seats < 0 || seats > 15 ||
-        !net_args_ok(net_seats, w1, b1, w2, b2, w3, b3, scratch, scratch_bytes, p.bytes) || depth < 0 || depth > TAROK_PLAYOUT_MAX_DEPTH ||
-        !(value_scale > 0.f) || __builtin_isinf(value_scale) || (!sum_out && !count_out && !action_out))
+    const PolicyWeights w = TK_WEIGHTS(w1, b1, w2, b2, w3, b3);
+    // depth 0 is "to the last card", and a bad value_scale is refused there too
+    if (!e || !world_kind_ok(kind) || (kind == TAROK_NET_WORLDS_DET) != !words || !net_halving_plan(e, rounds, round_worlds, p) ||
+        seats < 0 || seats > 15 || !net_args_ok(net_seats, w, scratch, scratch_bytes, p.list.bytes) ||
+        !depth_args_ok(depth, 0, TAROK_PLAYOUT_MAX_DEPTH, value_scale) || (!sum_out && !count_out && !action_out))
         return TAROK_EINVAL;
     HIPCHK(hipSetDevice(e->device));
     if (depth == TAROK_PLAYOUT_MAX_DEPTH) depth = 0;     // never stops: the plain kernels' bytes (§8.18)
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = e->n;
-    const NetItems it(scratch, p.bound);
-    int4 *rsum = reinterpret_cast<int4 *>(it.ires + p.bound);
+    const ListArrays a = p.list.carve(scratch);
+    int4 *rsum = reinterpret_cast<int4 *>(a.extra);
     int *rcnt = reinterpret_cast<int *>(rsum + n * TAROK_PLAYOUT_RANKS);
-    u32 *on = reinterpret_cast<u32 *>(rcnt + n * TAROK_PLAYOUT_RANKS), *alive = on + n, *base = alive + n, *part = base + n,
-        *total = part + p.blocks;
+    u32 *alive = a.on + n;
     const u64 pseed = e->seed ^ (u64)salt;
-    const dim3 per_game = grid_for(n), per_16((unsigned)((n + 15) / 16));
-    hipLaunchKernelGGL(k_playout_net_list_init, per_16, dim3(TK_BLOCK), 0, s, n, (u32)seats, seats_per_game, e->s01, e->s23, on, alive, rsum,
-                       reinterpret_cast<int4 *>(rcnt));
-    for (int r = 0; r < p.rounds; r++) {
-        const int e0 = p.end[r] - p.w[r];
-        hipLaunchKernelGGL(k_playout_net_list_totals, per_game, dim3(TK_BLOCK), 0, s, n, (u32)p.w[r], on, part);
-        hipLaunchKernelGGL(k_playout_net_list_scan, dim3(1), dim3(TK_BLOCK), 0, s, (u32)p.blocks, part, total);
-        hipLaunchKernelGGL(k_playout_net_list_base, per_game, dim3(TK_BLOCK), 0, s, n, (u32)p.w[r], on, part, base);
-        if (kind == TAROK_NET_WORLDS_VOIDS) {
-            if (depth) launch_net_list_deal(k_playout_net_list_deal_value_voids, e, pseed, e0, p.w[r], seats, seats_per_game, (const u32 *)words, on, base, it, s);
-            else launch_net_list_deal(k_playout_net_list_deal_voids, e, pseed, e0, p.w[r], seats, seats_per_game, (const u32 *)words, on, base, it, s);
-        } else if (kind == TAROK_NET_WORLDS_HIDDEN) {
-            if (depth) launch_net_list_deal(k_playout_net_list_deal_value_hidden, e, pseed, e0, p.w[r], seats, seats_per_game, (const u64 *)words, on, base, it, s);
-            else launch_net_list_deal(k_playout_net_list_deal_hidden, e, pseed, e0, p.w[r], seats, seats_per_game, (const u64 *)words, on, base, it, s);
-        } else {
-            if (depth) launch_net_list_deal(k_playout_net_list_deal_value, e, pseed, e0, p.w[r], seats, seats_per_game, (const NoWord *)nullptr, on, base, it, s);
-            else launch_net_list_deal(k_playout_net_list_deal, e, pseed, e0, p.w[r], seats, seats_per_game, (const NoWord *)nullptr, on, base, it, s);
+    const dim3 per_16((unsigned)((n + 15) / 16));
+    hipLaunchKernelGGL(k_playout_net_list_init, per_16, dim3(TK_BLOCK), 0, s, n, (u32)seats, seats_per_game, e->s01, e->s23, a.on, alive,
+                       rsum, reinterpret_cast<int4 *>(rcnt));
+    return for_world_kind(kind, words, [&](auto k, auto *kwords) {
+        const auto deal = depth ? TK_OF_KIND(k, k_playout_net_list_deal_value, k_playout_net_list_deal_value_voids,
+                                             k_playout_net_list_deal_value_hidden)
+                                : TK_OF_KIND(k, k_playout_net_list_deal, k_playout_net_list_deal_voids, k_playout_net_list_deal_hidden);
+        for (int r = 0; r < p.h.rounds; r++) {
+            const int wr = p.h.w[r];
+            launch_list_scan(p.list, a, wr, s);
+            const u32 lg = playout_lg(TK_PO_MIN_LG, wr);
+            hipLaunchKernelGGL(deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, s, n, pseed, e->offset, (u32)(p.h.end[r] - wr), (u32)wr, lg,
+                               (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, kwords, a.on, a.base, a.i01, a.i23, a.ikey, a.ires);
+            launch_net_play(net_list_bound(n, (u32)r, (u32)wr), a.total, net_seats, a, w, s, depth, value_scale);
+            hipLaunchKernelGGL(k_playout_net_list_sum, per_16, dim3(TK_BLOCK), 0, s, n, (u32)p.h.end[r], (u32)wr,
+                               (u32)(r == p.h.rounds - 1), (u32)seats, seats_per_game, e->s01, e->s23, e->gkey, a.ires, a.on, alive, a.base,
+                               rsum, rcnt, reinterpret_cast<int4 *>(sum_out), reinterpret_cast<int4 *>(count_out), action_out);
         }
-        const int64_t tiles = net_list_tiles(net_list_bound(n, (u32)r, (u32)p.w[r]), PM_M);
-        if (depth)
-            hipLaunchKernelGGL(k_playout_net_play_list_value, dim3((unsigned)tiles), dim3(TK_BLOCK), 0, s, total, (u32)net_seats, it.i01, it.i23,
-                               it.ikey, it.ires, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3, (u32)depth, value_scale);
-        else
-            hipLaunchKernelGGL(k_playout_net_play_list, dim3((unsigned)tiles), dim3(TK_BLOCK), 0, s, total, (u32)net_seats, it.i01, it.i23, it.ikey,
-                               it.ires, (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3);
-        hipLaunchKernelGGL(k_playout_net_list_sum, per_16, dim3(TK_BLOCK), 0, s, n, (u32)p.end[r], (u32)p.w[r], (u32)(r == p.rounds - 1),
-                           (u32)seats, seats_per_game, e->s01, e->s23, e->gkey, it.ires, on, alive, base, rsum, rcnt,
-                           reinterpret_cast<int4 *>(sum_out), reinterpret_cast<int4 *>(count_out), action_out);
-    }
-    HIPCHK(hipGetLastError());
-    return TAROK_OK;
-}
-
-extern "C++" {
-// tarok_playout_bids and its _pass twin: the deal, then the playout kernel given
-template <class Kernel>
-static int launch_playout_bids(Kernel kernel, tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int samples, int contracts,
-                               uint64_t salt, int seats, const uint8_t *seats_per_game, int32_t *sum_out, void *stream) {
-    if (!playout_args_ok(e, worlds, samples, seats) || contracts < 1 || contracts > TAROK_BID_ALL_CONTRACTS) return TAROK_EINVAL;
-    if (!sum_out) return TAROK_OK;
-    HIPCHK(hipSetDevice(e->device));
-    if (!e->bid_deal) HIPCHK(hipMalloc((void **)&e->bid_deal, (size_t)e->n * 5 * sizeof(u64)));   // on the first call; tarok_destroy frees it
-    hipLaunchKernelGGL(k_bid_deal, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, episode, deals, e->bid_deal);
-    // 16 lanes per game or more, so a workgroup's at most 16 teams keep their 80 sums each in 5 KiB
-    static_assert(TAROK_BID_ROWS == TK_BID_ROWS && TAROK_BID_ROWS % 4 == 0, "a viewer's rows are whole 16-byte pieces");
-    static_assert(TAROK_BID_PASS_ROW == TK_BID_PASS_ROW && TK_BID_PASS_ROW == TK_BID_OPTIONS && TK_BID_PASS_ROW < 32, "row 19, in the key's five bits");
-    const u32 lg = playout_lg(TK_PB_MIN_LG, worlds * samples);
-    hipLaunchKernelGGL(kernel, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset, episode, (u32)worlds, (u32)samples, lg, (u32)contracts, (u32)seats, seats_per_game,
-                       e->bid_deal, reinterpret_cast<int4 *>(sum_out));
-    HIPCHK(hipGetLastError());
-    return TAROK_OK;
-}
+        HIPCHK(hipGetLastError());
+        return (int)TAROK_OK;
+    });
 }
 
 int tarok_playout_bids(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int samples, int contracts, uint64_t salt,
@@ -5705,101 +5742,24 @@ int64_t tarok_playout_bids_net_scratch(const tarok_env *e, int worlds) {
     return e->n * 4 * TAROK_BID_ROWS * (int64_t)worlds * TK_PN_ITEM_BYTES + e->n * 5 * (int64_t)sizeof(u64);
 }
 
-// tarok_playout_bids_net and its _value twin: the deal, the items, the playouts, the sums — four launches on `stream`, nothing
-// allocated.  depth = 0: the playouts run to the last card and `pass` is 0; 1..13 (checked by tarok_playout_bids_net_value, the only
-// caller that gives one): they stop at the viewer's depth-th decision, and pass = 1 makes row 19's slots items.
-static int launch_playout_bids_net(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int contracts, uint64_t salt, int seats,
-                                   const uint8_t *seats_per_game, int net_seats, const void *w1, const float *b1, const void *w2,
-                                   const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out,
-                                   void *stream, int depth, float value_scale, int pass) {
-    if (!playout_args_ok(e, worlds, 1, seats) || contracts < 1 || contracts > TAROK_BID_ALL_CONTRACTS ||
-        !net_args_ok(net_seats, w1, b1, w2, b2, w3, b3, scratch, scratch_bytes, tarok_playout_bids_net_scratch(e, worlds)) || !sum_out)
-        return TAROK_EINVAL;
-    HIPCHK(hipSetDevice(e->device));
-    const int64_t rows = e->n * 4 * TAROK_BID_ROWS, items = rows * (int64_t)worlds;
-    const NetItems it(scratch, items);
-    u64 *deal = it.ires + items;
-    hipLaunchKernelGGL(k_bid_deal, grid_for(e->n), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed, e->offset, episode, deals, deal);
-    const u32 lg = playout_lg(TK_PB_MIN_LG, worlds);     // tarok_playout_bids' teams at samples = 1
-    hipLaunchKernelGGL(!depth ? k_playout_bids_net_deal : (pass ? k_playout_bids_net_deal_value_pass : k_playout_bids_net_deal_value),
-                       playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, items, e->seed ^ (u64)salt, e->offset, episode,
-                       (u32)worlds, lg, (u32)contracts, (u32)seats, seats_per_game, deal, it.i01, it.i23, it.ikey, it.ires);
-    launch_net_play(items, net_seats, it, w1, b1, w2, b2, w3, b3, stream, depth, value_scale);
-    hipLaunchKernelGGL(k_playout_bids_net_sum, grid_for(rows), dim3(TK_BLOCK), 0, (hipStream_t)stream, rows, items, (u32)worlds, it.ires,
-                       sum_out);
-    HIPCHK(hipGetLastError());
-    return TAROK_OK;
-}
-
 int tarok_playout_bids_net(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int contracts, uint64_t salt, int seats,
                            const uint8_t *seats_per_game, int net_seats, const void *w1, const float *b1, const void *w2, const float *b2,
                            const void *w3, const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out, void *stream) {
-    return launch_playout_bids_net(e, episode, deals, worlds, contracts, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3,
-                                   scratch, scratch_bytes, sum_out, stream, 0, 0.f, 0);
+    return launch_playout_bids_net(e, episode, deals, worlds, contracts, salt, seats, seats_per_game, net_seats,
+                                   TK_WEIGHTS(w1, b1, w2, b2, w3, b3), scratch, scratch_bytes, sum_out, stream, 0, 0.f, 0);
 }
 
 int tarok_playout_bids_net_value(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int contracts, uint64_t salt, int seats,
                                  const uint8_t *seats_per_game, int net_seats, int depth, float value_scale, int pass_value, const void *w1,
                                  const float *b1, const void *w2, const float *b2, const void *w3, const float *b3, void *scratch,
                                  int64_t scratch_bytes, int32_t *sum_out, void *stream) {
-    if (!value_args_ok(depth, TAROK_PLAYOUT_FRONT_MAX_DEPTH, value_scale) || pass_value < 0 || pass_value > 1) return TAROK_EINVAL;
-    return launch_playout_bids_net(e, episode, deals, worlds, contracts, salt, seats, seats_per_game, net_seats, w1, b1, w2, b2, w3, b3,
-                                   scratch, scratch_bytes, sum_out, stream, depth, value_scale, pass_value);
-}
-
-extern "C++" {
-// A front list launch as the host sizes it: the units, the item bound, the scan's workgroups and the scratch —
-// 48 x bound (the four item arrays), `extra` bytes (the bids' deal), the units' on and base words, the scan's partials (a
-// word per TK_BLOCK units) and the total word, rounded up to 16.  false: a bound that reaches 2^31 items.
-struct FrontListPlan {
-    int64_t units = 0, bound = 0, blocks = 0, bytes = 0;
-};
-static bool front_list_plan(int64_t units, int64_t bound, int64_t extra, FrontListPlan &p) {
-    if (bound >= (1LL << 31)) return false;
-    p.units = units;
-    p.bound = bound;
-    p.blocks = (units + TK_BLOCK - 1) / TK_BLOCK;
-    p.bytes = (bound * TK_PN_ITEM_BYTES + extra + units * 8 + p.blocks * 4 + 4 + 15) & ~(int64_t)15;
-    return true;
-}
-static bool exchange_list_plan(const tarok_env *e, int worlds, int discard_sets, FrontListPlan &p) {
-    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || discard_sets < 1 || discard_sets > TAROK_EXCHANGE_MAX_SETS) return false;
-    return front_list_plan(e->n * 6, exchange_list_bound(e->n, (u32)discard_sets, (u32)worlds), 0, p);
-}
-static bool bid_list_plan(const tarok_env *e, int worlds, int contracts, int seats, int per_game_seats, int pass_value, FrontListPlan &p) {
-    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || contracts < 1 || contracts > TAROK_BID_ALL_CONTRACTS || seats < 0 ||
-        seats > 15 || per_game_seats < 0 || per_game_seats > 1 || pass_value < 0 || pass_value > 1)
-        return false;
-    return front_list_plan(e->n * 4, bid_list_bound(e->n, (u32)seats, per_game_seats != 0, (u32)contracts, (u32)pass_value, (u32)worlds),
-                           e->n * 5 * (int64_t)sizeof(u64), p);
-}
-// What the list launches take of depth and value_scale: 0 .. max_depth, finite and > 0.
-static inline bool list_value_args_ok(int depth, float value_scale) {
-    return depth >= 0 && depth <= TAROK_PLAYOUT_FRONT_MAX_DEPTH && value_scale > 0.f && !__builtin_isinf(value_scale);
-}
-// The list's prefix sum over the units' on words: base[u] and the total word.
-static inline void launch_front_list_scan(const FrontListPlan &p, int worlds, const u32 *on, u32 *base, u32 *part, u32 *total, hipStream_t s) {
-    hipLaunchKernelGGL(k_playout_net_list_totals, grid_for(p.units), dim3(TK_BLOCK), 0, s, p.units, (u32)worlds, on, part);
-    hipLaunchKernelGGL(k_playout_net_list_scan, dim3(1), dim3(TK_BLOCK), 0, s, (u32)p.blocks, part, total);
-    hipLaunchKernelGGL(k_playout_net_list_base, grid_for(p.units), dim3(TK_BLOCK), 0, s, p.units, (u32)worlds, on, part, base);
-}
-// The playouts over the list: the grid is the bound's (one workgroup where the bound is 0: it finds no row below the total).
-static inline void launch_front_list_play(const FrontListPlan &p, const u32 *total, int net_seats, const NetItems &it, const void *w1,
-                                          const float *b1, const void *w2, const float *b2, const void *w3, const float *b3, hipStream_t s,
-                                          int depth, float value_scale) {
-    const int64_t tiles = net_list_tiles(p.bound, PM_M);
-    const dim3 grid((unsigned)(tiles ? tiles : 1));
-    if (depth)
-        hipLaunchKernelGGL(k_playout_net_play_list_value, grid, dim3(TK_BLOCK), 0, s, total, (u32)net_seats, it.i01, it.i23, it.ikey, it.ires,
-                           (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3, (u32)depth, value_scale);
-    else
-        hipLaunchKernelGGL(k_playout_net_play_list, grid, dim3(TK_BLOCK), 0, s, total, (u32)net_seats, it.i01, it.i23, it.ikey, it.ires,
-                           (const __bf16 *)w1, b1, (const __bf16 *)w2, b2, (const __bf16 *)w3, b3);
-}
+    if (!depth_args_ok(depth, 1, TAROK_PLAYOUT_FRONT_MAX_DEPTH, value_scale) || pass_value < 0 || pass_value > 1) return TAROK_EINVAL;
+    return launch_playout_bids_net(e, episode, deals, worlds, contracts, salt, seats, seats_per_game, net_seats,
+                                   TK_WEIGHTS(w1, b1, w2, b2, w3, b3), scratch, scratch_bytes, sum_out, stream, depth, value_scale, pass_value);
 }
 
 int64_t tarok_playout_exchange_net_list_scratch(const tarok_env *e, int worlds, int discard_sets) {
-    FrontListPlan p;
+    ListScratch p;
     return exchange_list_plan(e, worlds, discard_sets, p) ? p.bytes : (int64_t)TAROK_EINVAL;
 }
 
@@ -5809,32 +5769,34 @@ int tarok_playout_exchange_net_list(tarok_env *e, int worlds, int discard_sets, 
                                     int net_seats, int depth, float value_scale, const void *w1, const float *b1, const void *w2,
                                     const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
                                     int32_t *sum_out, int8_t *choice_out, uint8_t *discards_out, void *stream) {
-    FrontListPlan p;
-    if (!playout_args_ok(e, worlds, 1, seats) || !exchange_list_plan(e, worlds, discard_sets, p) || !list_value_args_ok(depth, value_scale) ||
-        !net_args_ok(net_seats, w1, b1, w2, b2, w3, b3, scratch, scratch_bytes, p.bytes) || (!sum_out && !choice_out && !discards_out))
+    ListScratch p;
+    const PolicyWeights w = TK_WEIGHTS(w1, b1, w2, b2, w3, b3);
+    // depth 0 is "to the last card", and a bad value_scale is refused there too
+    if (!playout_args_ok(e, worlds, 1, seats) || !exchange_list_plan(e, worlds, discard_sets, p) ||
+        !depth_args_ok(depth, 0, TAROK_PLAYOUT_FRONT_MAX_DEPTH, value_scale) || !net_args_ok(net_seats, w, scratch, scratch_bytes, p.bytes) ||
+        (!sum_out && !choice_out && !discards_out))
         return TAROK_EINVAL;
     HIPCHK(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    const NetItems it(scratch, p.bound);
-    u32 *on = reinterpret_cast<u32 *>(it.ires + p.bound), *base = on + p.units, *part = base + p.units, *total = part + p.blocks;
+    const ListArrays a = p.carve(scratch);
     const u64 pseed = e->seed ^ (u64)salt;
     hipLaunchKernelGGL(k_playout_exchange_net_list_init, grid_for(p.units), dim3(TK_BLOCK), 0, s, p.units, (u32)discard_sets, (u32)seats,
-                       seats_per_game, e->s01, e->s23, on);
-    launch_front_list_scan(p, worlds, on, base, part, total, s);
+                       seats_per_game, e->s01, e->s23, a.on);
+    launch_list_scan(p, a, worlds, s);
     const u32 lg = playout_lg(TK_PX_MIN_LG, worlds);     // tarok_playout_exchange's teams at samples = 1
     hipLaunchKernelGGL(depth ? k_playout_exchange_net_list_deal_value : k_playout_exchange_net_list_deal, playout_grid(e, lg), dim3(TK_BLOCK),
                        0, s, e->n, (u32)p.bound, pseed, e->offset, (u32)worlds, (u32)discard_sets, lg, (u32)seats, seats_per_game, e->s01,
-                       e->s23, e->cnt, on, base, it.i01, it.i23, it.ikey, it.ires);
-    launch_front_list_play(p, total, net_seats, it, w1, b1, w2, b2, w3, b3, s, depth, value_scale);
+                       e->s23, e->cnt, a.on, a.base, a.i01, a.i23, a.ikey, a.ires);
+    launch_net_play(p.bound, a.total, net_seats, a, w, s, depth, value_scale);
     hipLaunchKernelGGL(k_playout_exchange_net_list_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, s, e->n, (u32)p.bound, pseed,
-                       e->offset, (u32)worlds, (u32)discard_sets, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, e->gkey, on, base,
-                       it.ires, reinterpret_cast<int4 *>(sum_out), choice_out, discards_out);
+                       e->offset, (u32)worlds, (u32)discard_sets, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, e->gkey, a.on, a.base,
+                       a.ires, reinterpret_cast<int4 *>(sum_out), choice_out, discards_out);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }
 
 int64_t tarok_playout_bids_net_list_scratch(const tarok_env *e, int worlds, int contracts, int seats, int per_game_seats, int pass_value) {
-    FrontListPlan p;
+    ListScratch p;
     return bid_list_plan(e, worlds, contracts, seats, per_game_seats, pass_value, p) ? p.bytes : (int64_t)TAROK_EINVAL;
 }
 
@@ -5845,29 +5807,31 @@ int tarok_playout_bids_net_list(tarok_env *e, uint32_t episode, const uint8_t *d
                                 const uint8_t *seats_per_game, int net_seats, int depth, float value_scale, int pass_value, const void *w1,
                                 const float *b1, const void *w2, const float *b2, const void *w3, const float *b3, void *scratch,
                                 int64_t scratch_bytes, int32_t *sum_out, void *stream) {
-    FrontListPlan p;
+    ListScratch p;
+    const PolicyWeights w = TK_WEIGHTS(w1, b1, w2, b2, w3, b3);
+    // depth 0 is "to the last card", and a bad value_scale is refused there too
     if (!playout_args_ok(e, worlds, 1, seats) || !bid_list_plan(e, worlds, contracts, seats, seats_per_game != nullptr, pass_value, p) ||
-        !list_value_args_ok(depth, value_scale) || !net_args_ok(net_seats, w1, b1, w2, b2, w3, b3, scratch, scratch_bytes, p.bytes) ||
+        !depth_args_ok(depth, 0, TAROK_PLAYOUT_FRONT_MAX_DEPTH, value_scale) || !net_args_ok(net_seats, w, scratch, scratch_bytes, p.bytes) ||
         !sum_out)
         return TAROK_EINVAL;
     HIPCHK(hipSetDevice(e->device));
     if (pass_value && !depth) depth = TAROK_PLAYOUT_FRONT_MAX_DEPTH;
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = e->n, rows = n * 4 * TAROK_BID_ROWS;
-    const NetItems it(scratch, p.bound);
-    u64 *deal = it.ires + p.bound;
-    u32 *on = reinterpret_cast<u32 *>(deal + n * 5), *base = on + p.units, *part = base + p.units, *total = part + p.blocks;
+    const ListArrays a = p.carve(scratch);
+    u64 *deal = reinterpret_cast<u64 *>(a.extra);
     hipLaunchKernelGGL(k_bid_deal, grid_for(n), dim3(TK_BLOCK), 0, s, n, e->seed, e->offset, episode, deals, deal);
     hipLaunchKernelGGL(k_playout_bids_net_list_init, grid_for(p.units), dim3(TK_BLOCK), 0, s, n, (u32)contracts, (u32)pass_value, (u32)seats,
-                       seats_per_game, deal, on);
-    launch_front_list_scan(p, worlds, on, base, part, total, s);
+                       seats_per_game, deal, a.on);
+    launch_list_scan(p, a, worlds, s);
     const u32 lg = playout_lg(TK_PB_MIN_LG, worlds);     // tarok_playout_bids' teams at samples = 1
-    hipLaunchKernelGGL(!depth ? k_playout_bids_net_list_deal : (pass_value ? k_playout_bids_net_list_deal_value_pass : k_playout_bids_net_list_deal_value),
+    hipLaunchKernelGGL(!depth ? k_playout_bids_net_list_deal
+                              : (pass_value ? k_playout_bids_net_list_deal_value_pass : k_playout_bids_net_list_deal_value),
                        playout_grid(e, lg), dim3(TK_BLOCK), 0, s, n, (u32)p.bound, e->seed ^ (u64)salt, e->offset, episode, (u32)worlds, lg,
-                       (u32)seats, seats_per_game, deal, on, base, it.i01, it.i23, it.ikey, it.ires);
-    launch_front_list_play(p, total, net_seats, it, w1, b1, w2, b2, w3, b3, s, depth, value_scale);
-    hipLaunchKernelGGL(k_playout_bids_net_list_sum, grid_for(rows), dim3(TK_BLOCK), 0, s, rows, (u32)p.bound, (u32)worlds, on, base, it.ires,
-                       sum_out);
+                       (u32)seats, seats_per_game, deal, a.on, a.base, a.i01, a.i23, a.ikey, a.ires);
+    launch_net_play(p.bound, a.total, net_seats, a, w, s, depth, value_scale);
+    hipLaunchKernelGGL(k_playout_bids_net_list_sum, grid_for(rows), dim3(TK_BLOCK), 0, s, rows, (u32)p.bound, (u32)worlds, a.on, a.base,
+                       a.ires, sum_out);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }
@@ -6212,7 +6176,6 @@ static int launch_policy_step(tarok_env *e, int kind, u32 seats, const uint8_t *
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }
-#define TK_WEIGHTS(w1, b1, w2, b2, w3, b3) PolicyWeights{(const __bf16 *)(w1), b1, (const __bf16 *)(w2), b2, (const __bf16 *)(w3), b3}
 
 int tarok_policy_step(tarok_env *e, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
                       const float *b3, const uint64_t *obs, uint8_t *action_out, float *logp_out, float *value_out,

@@ -23,6 +23,24 @@ def _u64(t):
     return t.detach().cpu().numpy().view(np.uint64)
 
 
+def _salt(salt):
+    """A salt as the ABI's uint64."""
+    return int(salt) & ((1 << 64) - 1)
+
+
+_SIZES = dict(worlds=(K.PLAYOUT_MAX_WORLDS, "worlds: 1..%d" % K.PLAYOUT_MAX_WORLDS),
+              discard_sets=(K.EXCHANGE_MAX_SETS, "discard_sets: 1..%d" % K.EXCHANGE_MAX_SETS),
+              contracts=(K.BID_ALL_CONTRACTS, "contracts: a bit set within 1..0x3FF"))
+
+
+def _sizes(**given):
+    """worlds=, discard_sets=, contracts= of a scratch method as ints, each within 1..its maximum (else a ValueError)."""
+    for name, value in given.items():
+        if not 1 <= int(value) <= _SIZES[name][0]:
+            raise ValueError(_SIZES[name][1])
+    return [int(value) for value in given.values()]
+
+
 class Obs:
     """Per-game observation words (include/tarok_env.h TAROK_OBS_*) as an int64
     device tensor with decoded views."""
@@ -320,34 +338,69 @@ class TarokVecEnv:
         new one); a tensor or an array in their place: the words themselves, which need no history — and of the player:
         net None (the Bot, `samples` playouts per card and world) or (weights, net_seats, depth, value_scale), samples None.
         Returns (sum_out, action_out), allocated where None."""
-        is_words = lambda x: x is not None and not isinstance(x, (bool, int))          # a tensor or an array
-        want_v, want_h = is_words(voids) or bool(voids), is_words(hidden) or bool(hidden)
-        P.one_world_kind(want_v, want_h)
-        kind = "open" if worlds is None else "voids" if want_v else "hidden" if want_h else "det"
-        given = voids if want_v else hidden
-        if kind in P.WORDS_DTYPE and not is_words(given) and not self.history:
-            raise ValueError("%s=True goes with the play history: TarokVecEnv(history=True)" % kind)
-        name = "tarok_playout_cards" + ("" if net is None else "_net") + ("" if kind == ("open" if net is None else "det") else "_" + kind)
+        kind, words = TarokVecEnv._world_words(self, worlds is not None, voids, hidden, words)
         if net is not None:
-            weights, net_seats, depth, value_scale = net
-            if not 0 <= int(net_seats) <= 15:
-                raise ValueError("net_seats: a 4-bit seat set, 0..15")
-            w, scratch = self.check_mlp_weights(weights), self.playout_net_scratch(worlds)
-        words = self._dev(given if is_words(given) else (self.shown_voids if want_v else self.played_cards)(words),
-                          P.WORDS_DTYPE[kind], (self.n,)) if kind in P.WORDS_DTYPE else None
+            net_seats, depth, value_scale, w = TarokVecEnv._net_args(self, *net)
+            scratch = self.playout_net_scratch(worlds)
+        words = words()
+        name = "tarok_playout_cards" + ("" if net is None else "_net") + ("" if kind == ("open" if net is None else "det") else "_" + kind)
         mid = [] if words is None else [self._p(words)]
         if net is not None:
-            mid.append(int(net_seats))
-            if depth is not None:
-                name, mid = "tarok_playout_cards_net_value", [P.WORLDS.index(kind), self._p(words), int(net_seats), int(depth), float(value_scale)]
-            mid += [self._p(t) for t in w] + [self._p(scratch), scratch.numel()]
+            mid.append(net_seats)
+            if net[2] is not None:
+                name, mid = "tarok_playout_cards_net_value", [P.WORLDS.index(kind), self._p(words), net_seats, depth, value_scale]
+            mid += w + [self._p(scratch), scratch.numel()]
         with torch.cuda.device(self.device):
-            sum_out = self._empty(sum_out, (self.n, K.PLAYOUT_RANKS, 4), torch.int32)
-            action_out = self._empty(action_out, self.n, torch.uint8)
-            _native.check(getattr(self.L, name)(self._h, *[int(c) for c in (worlds, samples) if c is not None], int(salt) & ((1 << 64) - 1),
+            sum_out, action_out = TarokVecEnv._card_outputs(self, sum_out, action_out)
+            _native.check(getattr(self.L, name)(self._h, *[int(c) for c in (worlds, samples) if c is not None], _salt(salt),
                                                 int(seats), self._p(self._seat_sets(seats_per_game)), *mid, self._p(sum_out),
                                                 self._p(action_out), self._stream()))
         return sum_out, action_out
+
+    def _world_words(self, fair, voids, hidden, words):
+        """(kind, words) of a card launch, `words` a call that makes its per-game words tensor (None for a kind without),
+        so that every refusal comes before the first launch.  fair False: "open", the true hands.  voids / hidden True: the
+        env's own words — which need the play history — written into the caller's `words` tensor (None: a new one); a
+        tensor or an array in their place: the words themselves, which need no history."""
+        is_words = lambda x: x is not None and not isinstance(x, (bool, int))          # a tensor or an array
+        want_v, want_h = is_words(voids) or bool(voids), is_words(hidden) or bool(hidden)
+        P.one_world_kind(want_v, want_h)
+        kind = "open" if not fair else "voids" if want_v else "hidden" if want_h else "det"
+        if kind not in P.WORDS_DTYPE:
+            return kind, lambda: None
+        given = voids if want_v else hidden
+        if is_words(given):
+            return kind, lambda: self._dev(given, P.WORDS_DTYPE[kind], (self.n,))
+        if not self.history:
+            raise ValueError("%s=True goes with the play history: TarokVecEnv(history=True)" % kind)
+        return kind, lambda: self._dev((self.shown_voids if want_v else self.played_cards)(words), P.WORDS_DTYPE[kind], (self.n,))
+
+    def _card_outputs(self, sum_out, action_out, count_out=False):
+        """A card launch's outputs — sum [N,12,4] int32, count [N,12] int32 unless False, action [N] uint8 — each the
+        caller's, or where it gave None a new tensor."""
+        counts = [] if count_out is False else [self._empty(count_out, (self.n, K.PLAYOUT_RANKS), torch.int32)]
+        return [self._empty(sum_out, (self.n, K.PLAYOUT_RANKS, 4), torch.int32)] + counts + [self._empty(action_out, self.n, torch.uint8)]
+
+    def _exchange_outputs(self, discard_sets, sum_out, choice_out, discards_out):
+        """An exchange launch's outputs (sum [N, 6 * discard_sets, 4] int32, choice [N] int8, discards [N,3] uint8)."""
+        return (self._empty(sum_out, (self.n, 6 * int(discard_sets), 4), torch.int32), self._empty(choice_out, self.n, torch.int8),
+                self._empty(discards_out, (self.n, 3), torch.uint8))
+
+    def _net_args(self, weights, net_seats, depth, value_scale, max_depth=K.PLAYOUT_MAX_DEPTH):
+        """What the net-played launches check and pass alike: (net_seats in 0..15, depth as the ABI's list and halving
+        entries take it — None becomes 0, to the last card; else checked within 1..max_depth with its value_scale —,
+        value_scale, the six weights' pointers)."""
+        depth, value_scale = TarokVecEnv._list_value(net_seats, depth, value_scale, max_depth)
+        return int(net_seats), depth, value_scale, [self._p(t) for t in self.check_mlp_weights(weights)]
+
+    @staticmethod
+    def _list_value(net_seats, depth, value_scale, max_depth=K.PLAYOUT_FRONT_MAX_DEPTH):
+        """_net_args' checks, which read nothing of an env -> (depth, value_scale) as the ABI takes them (depth 0: to the end)."""
+        if not 0 <= int(net_seats) <= 15:
+            raise ValueError("net_seats: a 4-bit seat set, 0..15")
+        if depth is not None:
+            P.check_depth(depth, value_scale, max_depth=max_depth)
+        return (0 if depth is None else int(depth)), float(value_scale)
 
     def playout_cards_fair(self, worlds, samples, *, voids=False, hidden=False, words=None, salt=0, seats=15, seats_per_game=None,
                            sum_out=None, action_out=None):
@@ -387,18 +440,13 @@ class TarokVecEnv:
         and the playouts' keys are that launch's, so round_worlds=(W,) gives its bytes.
         Returns (sum [N,12,4] int32, count [N,12] int32 — the playouts behind every row, 0 beyond the legal cards and for
         games that do not take part —, action [N] uint8: the first card at the maximum among the cards alive at the end)."""
-        P.one_world_kind(bool(voids), bool(hidden))
-        kind = "voids" if voids else "hidden" if hidden else "det"
         schedule = P.check_halving(round_worlds)
-        if kind in P.WORDS_DTYPE and not self.history:
-            raise ValueError("%s=True goes with the play history: TarokVecEnv(history=True)" % kind)
-        words = (self.shown_voids if voids else self.played_cards)(words) if kind in P.WORDS_DTYPE else None
+        kind, words = TarokVecEnv._world_words(self, True, voids, hidden, words)
+        words = words()
         with torch.cuda.device(self.device):
-            sum_out = self._empty(sum_out, (self.n, K.PLAYOUT_RANKS, 4), torch.int32)
-            count_out = self._empty(count_out, (self.n, K.PLAYOUT_RANKS), torch.int32)
-            action_out = self._empty(action_out, self.n, torch.uint8)
+            sum_out, count_out, action_out = TarokVecEnv._card_outputs(self, sum_out, action_out, count_out)
             _native.check(self.L.tarok_playout_cards_halving(self._h, P.WORLDS.index(kind), self._p(words), len(schedule),
-                                                             (C.c_int * len(schedule))(*schedule), int(samples), int(salt) & ((1 << 64) - 1),
+                                                             (C.c_int * len(schedule))(*schedule), int(samples), _salt(salt),
                                                              int(seats), self._p(self._seat_sets(seats_per_game)), self._p(sum_out),
                                                              self._p(count_out), self._p(action_out), self._stream()))
         return sum_out, count_out, action_out
@@ -425,35 +473,23 @@ class TarokVecEnv:
         caller's uint8 tensor of at least playout_net_halving_scratch(round_worlds).numel() bytes (None: that cached one).
         Returns (sum [N,12,4] int32, count [N,12] int32 — the worlds behind every row —, action [N] uint8: the first card
         at the maximum among the cards alive at the end)."""
-        P.one_world_kind(bool(voids), bool(hidden))
-        kind = "voids" if voids else "hidden" if hidden else "det"
         schedule = P.check_halving(round_worlds)
-        if not 0 <= int(net_seats) <= 15:
-            raise ValueError("net_seats: a 4-bit seat set, 0..15")
-        if depth is not None:
-            P.check_depth(depth, value_scale)
-        if kind in P.WORDS_DTYPE and not self.history:
-            raise ValueError("%s=True goes with the play history: TarokVecEnv(history=True)" % kind)
-        w = self.check_mlp_weights(weights)
+        kind, words = TarokVecEnv._world_words(self, True, voids, hidden, words)
+        net_seats, depth, value_scale, w = TarokVecEnv._net_args(self, weights, net_seats, depth, value_scale)
         scratch = self.playout_net_halving_scratch(schedule) if scratch is None else scratch
-        words = (self.shown_voids if voids else self.played_cards)(words) if kind in P.WORDS_DTYPE else None
+        words = words()
         with torch.cuda.device(self.device):
-            sum_out = self._empty(sum_out, (self.n, K.PLAYOUT_RANKS, 4), torch.int32)
-            count_out = self._empty(count_out, (self.n, K.PLAYOUT_RANKS), torch.int32)
-            action_out = self._empty(action_out, self.n, torch.uint8)
+            sum_out, count_out, action_out = TarokVecEnv._card_outputs(self, sum_out, action_out, count_out)
             _native.check(self.L.tarok_playout_cards_net_halving(
-                self._h, P.WORLDS.index(kind), self._p(words), len(schedule), (C.c_int * len(schedule))(*schedule),
-                int(salt) & ((1 << 64) - 1), int(seats), self._p(self._seat_sets(seats_per_game)), int(net_seats), *[self._p(t) for t in w],
-                0 if depth is None else int(depth), float(value_scale), self._p(scratch), scratch.numel(), self._p(sum_out),
-                self._p(count_out), self._p(action_out), self._stream()))
+                self._h, P.WORLDS.index(kind), self._p(words), len(schedule), (C.c_int * len(schedule))(*schedule), _salt(salt),
+                int(seats), self._p(self._seat_sets(seats_per_game)), net_seats, *w, depth, value_scale, self._p(scratch),
+                scratch.numel(), self._p(sum_out), self._p(count_out), self._p(action_out), self._stream()))
         return sum_out, count_out, action_out
 
     def playout_net_scratch(self, worlds):
         """The scratch tensor of playout_cards_net at `worlds` (uint8, tarok_playout_net_scratch bytes), cached on the env
         per `worlds`: a caller that captures the launch into a graph asks for it BEFORE the capture."""
-        worlds = int(worlds)
-        if not 1 <= worlds <= K.PLAYOUT_MAX_WORLDS:
-            raise ValueError("worlds: 1..%d" % K.PLAYOUT_MAX_WORLDS)
+        worlds, = _sizes(worlds=worlds)
         return self._scratch(("cards", worlds), self.L.tarok_playout_net_scratch, worlds)
 
     def playout_cards_net(self, weights, worlds, net_seats=15, salt=0, seats=15, seats_per_game=None, sum_out=None, action_out=None,
@@ -487,7 +523,7 @@ class TarokVecEnv:
         Everything else — worlds, voids= / hidden= / words=, the scratch, the outputs — is playout_cards_net's; depth=None
         IS playout_cards_net."""
         if depth is not None:
-            P.check_depth(depth, value_scale)
+            P.check_depth(depth, value_scale)         # (before anything of the env is read)
         return self._cards(worlds, None, salt, seats, seats_per_game, sum_out, action_out, voids, hidden, words,
                            (weights, net_seats, depth, value_scale))
 
@@ -503,11 +539,9 @@ class TarokVecEnv:
         with its declarer outside the set; -1 and 255s elsewhere).  exchange(choice, discards) applies them — a mixed
         table in one call.  Read-only on the env; `salt` varies the draws."""
         with torch.cuda.device(self.device):
-            sum_out = self._empty(sum_out, (self.n, 6 * int(discard_sets), 4), torch.int32)
-            choice_out = self._empty(choice_out, self.n, torch.int8)
-            discards_out = self._empty(discards_out, (self.n, 3), torch.uint8)
+            sum_out, choice_out, discards_out = TarokVecEnv._exchange_outputs(self, discard_sets, sum_out, choice_out, discards_out)
             _native.check(self.L.tarok_playout_exchange(self._h, int(worlds), int(samples), int(discard_sets),
-                                                        int(salt) & ((1 << 64) - 1), int(seats),
+                                                        _salt(salt), int(seats),
                                                         self._p(self._seat_sets(seats_per_game)), self._p(sum_out),
                                                         self._p(choice_out), self._p(discards_out), self._stream()))
         return sum_out, choice_out, discards_out
@@ -529,7 +563,7 @@ class TarokVecEnv:
         with torch.cuda.device(self.device):
             sum_out = self._empty(sum_out, (self.n, 4, K.BID_ROWS), torch.int32)
             _native.check(launch(self._h, int(episode), self._p(deals), int(worlds), int(samples), int(contracts),
-                                 int(salt) & ((1 << 64) - 1), int(seats),
+                                 _salt(salt), int(seats),
                                  self._p(self._seat_sets(seats_per_game)), self._p(sum_out), self._stream()))
         return sum_out
 
@@ -547,11 +581,7 @@ class TarokVecEnv:
     def playout_exchange_net_scratch(self, worlds, discard_sets=4):
         """The scratch tensor of playout_exchange_net at (worlds, discard_sets) (uint8, tarok_playout_exchange_net_scratch
         bytes), cached on the env per shape: a caller that captures the launch asks for it BEFORE the capture."""
-        worlds, discard_sets = int(worlds), int(discard_sets)
-        if not 1 <= worlds <= K.PLAYOUT_MAX_WORLDS:
-            raise ValueError("worlds: 1..%d" % K.PLAYOUT_MAX_WORLDS)
-        if not 1 <= discard_sets <= K.EXCHANGE_MAX_SETS:
-            raise ValueError("discard_sets: 1..%d" % K.EXCHANGE_MAX_SETS)
+        worlds, discard_sets = _sizes(worlds=worlds, discard_sets=discard_sets)
         return self._scratch(("exchange", worlds, discard_sets), self.L.tarok_playout_exchange_net_scratch, worlds, discard_sets)
 
     def playout_exchange_net(self, weights, worlds, discard_sets=4, net_seats=15, salt=0, seats=15, seats_per_game=None, sum_out=None,
@@ -562,25 +592,24 @@ class TarokVecEnv:
         playouts.  net_seats=0: playout_exchange(worlds, 1, discard_sets) to the byte.  Candidates, worlds, the three
         outputs, `seats` / `seats_per_game`, `salt` and the read-only contract: as for playout_exchange.  The scratch is
         playout_exchange_net_scratch(worlds, discard_sets)."""
-        return TarokVecEnv._exchange_net(self, weights, worlds, discard_sets, net_seats, salt, seats, seats_per_game, sum_out, choice_out,
-                                         discards_out)
+        return TarokVecEnv._exchange_net(self, "tarok_playout_exchange_net", weights, worlds, discard_sets, None, 0.0, net_seats, salt, seats, seats_per_game,
+                                         sum_out, choice_out, discards_out)
 
-    def _exchange_net(self, weights, worlds, discard_sets, net_seats, salt, seats, seats_per_game, sum_out, choice_out, discards_out,
-                      value=()):
-        """playout_exchange_net's call; value = (depth, value_scale): tarok_playout_exchange_net_value's."""
-        if not 0 <= int(net_seats) <= 15:
-            raise ValueError("net_seats: a 4-bit seat set, 0..15")
-        w = self.check_mlp_weights(weights)
-        scratch = self.playout_exchange_net_scratch(worlds, discard_sets)
-        launch = self.L.tarok_playout_exchange_net_value if value else self.L.tarok_playout_exchange_net
+    def _exchange_net(self, name, weights, worlds, discard_sets, depth, value_scale, net_seats, salt, seats, seats_per_game, sum_out,
+                      choice_out, discards_out):
+        """The call under playout_exchange_net, _net_value and _net_list.  name: the native function — the _list one takes
+        (depth, value_scale) at any depth (0: to the last card) and has its own scratch; the dense _value one is only
+        called with a depth."""
+        net_seats, d, value_scale, w = TarokVecEnv._net_args(self, weights, net_seats, depth, value_scale, K.PLAYOUT_FRONT_MAX_DEPTH)
+        is_list = name.endswith("_list")
+        value = (d, value_scale) if is_list or depth is not None else ()
+        scratch = (self.playout_exchange_net_list_scratch if is_list else self.playout_exchange_net_scratch)(worlds, discard_sets)
         with torch.cuda.device(self.device):
-            sum_out = self._empty(sum_out, (self.n, 6 * int(discard_sets), 4), torch.int32)
-            choice_out = self._empty(choice_out, self.n, torch.int8)
-            discards_out = self._empty(discards_out, (self.n, 3), torch.uint8)
-            _native.check(launch(self._h, int(worlds), int(discard_sets), int(salt) & ((1 << 64) - 1), int(seats),
-                                 self._p(self._seat_sets(seats_per_game)), int(net_seats), *value, *[self._p(t) for t in w],
-                                 self._p(scratch), scratch.numel(), self._p(sum_out), self._p(choice_out), self._p(discards_out),
-                                 self._stream()))
+            sum_out, choice_out, discards_out = TarokVecEnv._exchange_outputs(self, discard_sets, sum_out, choice_out, discards_out)
+            _native.check(getattr(self.L, name)(self._h, int(worlds), int(discard_sets), _salt(salt), int(seats),
+                                                self._p(self._seat_sets(seats_per_game)), net_seats, *value, *w, self._p(scratch),
+                                                scratch.numel(), self._p(sum_out), self._p(choice_out), self._p(discards_out),
+                                                self._stream()))
         return sum_out, choice_out, discards_out
 
     def playout_exchange_net_value(self, weights, worlds, discard_sets, depth, value_scale=70.0, net_seats=15, salt=0, seats=15,
@@ -593,19 +622,13 @@ class TarokVecEnv:
         last card, 1 runs at most 4 card rounds.  At depth 1 with the declarer on lead nothing is played and a candidate's
         number is the same in every world.  Everything else, the scratch included, is playout_exchange_net's; depth=None IS
         playout_exchange_net."""
-        value = ()
-        if depth is not None:
-            P.check_depth(depth, value_scale, max_depth=K.PLAYOUT_FRONT_MAX_DEPTH)
-            value = (int(depth), float(value_scale))
-        return TarokVecEnv._exchange_net(self, weights, worlds, discard_sets, net_seats, salt, seats, seats_per_game, sum_out, choice_out,
-                                         discards_out, value)
+        return TarokVecEnv._exchange_net(self, "tarok_playout_exchange_net" + ("" if depth is None else "_value"), weights, worlds, discard_sets, depth, value_scale, net_seats, salt, seats, seats_per_game,
+                                         sum_out, choice_out, discards_out)
 
     def playout_bids_net_scratch(self, worlds):
         """The scratch tensor of playout_bids_net at `worlds` (uint8, tarok_playout_bids_net_scratch bytes: 3,840 * worlds
         + 40 per game), cached on the env per `worlds`: a caller that captures the launch asks for it BEFORE the capture."""
-        worlds = int(worlds)
-        if not 1 <= worlds <= K.PLAYOUT_MAX_WORLDS:
-            raise ValueError("worlds: 1..%d" % K.PLAYOUT_MAX_WORLDS)
+        worlds, = _sizes(worlds=worlds)
         return self._scratch(("bids", worlds), self.L.tarok_playout_bids_net_scratch, worlds)
 
     def playout_bids_net(self, weights, episode, worlds, net_seats=15, contracts=K.BID_DEFAULT_CONTRACTS, deals=None, salt=0, seats=15,
@@ -616,21 +639,25 @@ class TarokVecEnv:
         net_seats=0: playout_bids(episode, worlds, 1) to the byte.  Row K.BID_PASS_ROW is 0: the pass is not valued here.
         Everything else as for playout_bids.  The scratch is playout_bids_net_scratch(worlds); nothing is allocated by
         the launch itself."""
-        return TarokVecEnv._bids_net(self, weights, episode, worlds, net_seats, contracts, deals, salt, seats, seats_per_game, sum_out)
+        return TarokVecEnv._bids_net(self, "tarok_playout_bids_net", weights, episode, worlds, None, 0.0, False, net_seats, contracts, deals, salt, seats,
+                                     seats_per_game, sum_out)
 
-    def _bids_net(self, weights, episode, worlds, net_seats, contracts, deals, salt, seats, seats_per_game, sum_out, value=()):
-        """playout_bids_net's call; value = (depth, value_scale, pass_value): tarok_playout_bids_net_value's."""
-        if not 0 <= int(net_seats) <= 15:
-            raise ValueError("net_seats: a 4-bit seat set, 0..15")
-        w = self.check_mlp_weights(weights)
-        scratch = self.playout_bids_net_scratch(worlds)
+    def _bids_net(self, name, weights, episode, worlds, depth, value_scale, pass_value, net_seats, contracts, deals, salt, seats,
+                  seats_per_game, sum_out):
+        """The call under playout_bids_net, _net_value and _net_list.  name: the native function — the _list one takes
+        (depth, value_scale, pass_value) at any depth (0: to the last card) and has its own scratch; the dense _value one
+        is only called with a depth."""
+        net_seats, d, value_scale, w = TarokVecEnv._net_args(self, weights, net_seats, depth, value_scale, K.PLAYOUT_FRONT_MAX_DEPTH)
+        is_list = name.endswith("_list")
+        value = (d, value_scale, int(bool(pass_value))) if is_list or depth is not None else ()
+        scratch = self.playout_bids_net_list_scratch(worlds, contracts, seats, seats_per_game is not None, pass_value) if is_list else \
+            self.playout_bids_net_scratch(worlds)
         deals = self._dev(deals, torch.uint8, (self.n, 54))
-        launch = self.L.tarok_playout_bids_net_value if value else self.L.tarok_playout_bids_net
         with torch.cuda.device(self.device):
             sum_out = self._empty(sum_out, (self.n, 4, K.BID_ROWS), torch.int32)
-            _native.check(launch(self._h, int(episode), self._p(deals), int(worlds), int(contracts), int(salt) & ((1 << 64) - 1),
-                                 int(seats), self._p(self._seat_sets(seats_per_game)), int(net_seats), *value,
-                                 *[self._p(t) for t in w], self._p(scratch), scratch.numel(), self._p(sum_out), self._stream()))
+            _native.check(getattr(self.L, name)(self._h, int(episode), self._p(deals), int(worlds), int(contracts), _salt(salt),
+                                                int(seats), self._p(self._seat_sets(seats_per_game)), net_seats, *value, *w,
+                                                self._p(scratch), scratch.numel(), self._p(sum_out), self._stream()))
         return sum_out
 
     def playout_bids_net_value(self, weights, episode, worlds, depth, value_scale=70.0, pass_value=False, net_seats=15,
@@ -643,33 +670,17 @@ class TarokVecEnv:
         of PASSING — playout_bids(pass_value=True)'s pass playout (three Bots bid with the viewer silent) at sample 0, played
         and stopped like every other row; bid_round(pass_value=True) takes the sums.  Without it row 19 is 0.  Everything
         else, the scratch included, is playout_bids_net's; depth=None IS playout_bids_net, where a pass is not valued."""
-        value = ()
-        if depth is not None:
-            P.check_depth(depth, value_scale, max_depth=K.PLAYOUT_FRONT_MAX_DEPTH)
-            value = (int(depth), float(value_scale), int(bool(pass_value)))
-        elif pass_value:
+        if depth is None and pass_value:
             raise ValueError("pass_value=True needs a depth: the plain net launch does not value the pass")
-        return TarokVecEnv._bids_net(self, weights, episode, worlds, net_seats, contracts, deals, salt, seats, seats_per_game, sum_out, value)
-
-    @staticmethod
-    def _list_value(net_seats, depth, value_scale):
-        """The checks the two list launches share -> (depth, value_scale) as the ABI takes them (depth 0: to the end)."""
-        if not 0 <= int(net_seats) <= 15:
-            raise ValueError("net_seats: a 4-bit seat set, 0..15")
-        if depth is not None:
-            P.check_depth(depth, value_scale, max_depth=K.PLAYOUT_FRONT_MAX_DEPTH)
-        return (0 if depth is None else int(depth)), float(value_scale)
+        return TarokVecEnv._bids_net(self, "tarok_playout_bids_net" + ("" if depth is None else "_value"), weights, episode, worlds, depth, value_scale, pass_value, net_seats, contracts, deals, salt, seats,
+                                     seats_per_game, sum_out)
 
     def playout_exchange_net_list_scratch(self, worlds, discard_sets=4):
         """The scratch tensor of playout_exchange_net_list at (worlds, discard_sets) (uint8,
         tarok_playout_exchange_net_list_scratch bytes: the dense launch's item arrays — the host cannot read the contracts,
         so they do not shrink — plus 8 bytes per (game, group), the scan's partials and the total word), cached on the env
         per shape: a caller that captures the launch asks for it BEFORE the capture."""
-        worlds, discard_sets = int(worlds), int(discard_sets)
-        if not 1 <= worlds <= K.PLAYOUT_MAX_WORLDS:
-            raise ValueError("worlds: 1..%d" % K.PLAYOUT_MAX_WORLDS)
-        if not 1 <= discard_sets <= K.EXCHANGE_MAX_SETS:
-            raise ValueError("discard_sets: 1..%d" % K.EXCHANGE_MAX_SETS)
+        worlds, discard_sets = _sizes(worlds=worlds, discard_sets=discard_sets)
         return self._scratch(("exchange_list", worlds, discard_sets), self.L.tarok_playout_exchange_net_list_scratch, worlds, discard_sets)
 
     def playout_exchange_net_list(self, weights, worlds, discard_sets=4, depth=None, value_scale=70.0, net_seats=15, salt=0, seats=15,
@@ -679,18 +690,8 @@ class TarokVecEnv:
         the groups a Tri or a Dve does not have left out of the play launch's forward rows.  depth=None or 13: to the last
         card; 1..12: playout_exchange_net_value's stop at value_scale.  The scratch is
         playout_exchange_net_list_scratch(worlds, discard_sets); the launch allocates nothing and reads nothing back."""
-        value = self._list_value(net_seats, depth, value_scale)
-        w = self.check_mlp_weights(weights)
-        scratch = self.playout_exchange_net_list_scratch(worlds, discard_sets)
-        with torch.cuda.device(self.device):
-            sum_out = self._empty(sum_out, (self.n, 6 * int(discard_sets), 4), torch.int32)
-            choice_out = self._empty(choice_out, self.n, torch.int8)
-            discards_out = self._empty(discards_out, (self.n, 3), torch.uint8)
-            _native.check(self.L.tarok_playout_exchange_net_list(
-                self._h, int(worlds), int(discard_sets), int(salt) & ((1 << 64) - 1), int(seats), self._p(self._seat_sets(seats_per_game)),
-                int(net_seats), *value, *[self._p(t) for t in w], self._p(scratch), scratch.numel(), self._p(sum_out), self._p(choice_out),
-                self._p(discards_out), self._stream()))
-        return sum_out, choice_out, discards_out
+        return TarokVecEnv._exchange_net(self, "tarok_playout_exchange_net_list", weights, worlds, discard_sets, depth, value_scale, net_seats, salt, seats, seats_per_game,
+                                         sum_out, choice_out, discards_out)
 
     def playout_bids_net_list_scratch(self, worlds, contracts=K.BID_DEFAULT_CONTRACTS, seats=15, per_game=False, pass_value=False):
         """The scratch tensor of playout_bids_net_list (uint8, tarok_playout_bids_net_list_scratch bytes): 48 bytes for every
@@ -698,11 +699,7 @@ class TarokVecEnv:
         `contracts` (+ 1 with pass_value) x worlds — plus 72 bytes per game and the scan's words: 624 * worlds per game for
         one viewer at the default contracts, against playout_bids_net_scratch's 3,840 * worlds.  Cached on the env per
         shape: a caller that captures the launch asks for it BEFORE the capture."""
-        worlds, contracts, seats = int(worlds), int(contracts), int(seats)
-        if not 1 <= worlds <= K.PLAYOUT_MAX_WORLDS:
-            raise ValueError("worlds: 1..%d" % K.PLAYOUT_MAX_WORLDS)
-        if not 1 <= contracts <= K.BID_ALL_CONTRACTS:
-            raise ValueError("contracts: a bit set within 1..0x3FF")
+        (worlds, contracts), seats = _sizes(worlds=worlds, contracts=contracts), int(seats)
         if not 0 <= seats <= 15:
             raise ValueError("seats: a 4-bit seat set, 0..15")
         key = ("bids_list", worlds, contracts, 15 if per_game else seats, bool(per_game), bool(pass_value))
@@ -717,17 +714,8 @@ class TarokVecEnv:
         1..12: playout_bids_net_value's stop at value_scale.  pass_value=True is taken at ANY depth: with depth=None it is
         playout_bids_net_value(depth=13, pass_value=True).  The scratch is playout_bids_net_list_scratch(worlds, contracts,
         seats, seats_per_game is not None, pass_value); the launch allocates nothing and reads nothing back."""
-        value = self._list_value(net_seats, depth, value_scale) + (int(bool(pass_value)),)
-        w = self.check_mlp_weights(weights)
-        scratch = self.playout_bids_net_list_scratch(worlds, contracts, seats, seats_per_game is not None, pass_value)
-        deals = self._dev(deals, torch.uint8, (self.n, 54))
-        with torch.cuda.device(self.device):
-            sum_out = self._empty(sum_out, (self.n, 4, K.BID_ROWS), torch.int32)
-            _native.check(self.L.tarok_playout_bids_net_list(
-                self._h, int(episode), self._p(deals), int(worlds), int(contracts), int(salt) & ((1 << 64) - 1), int(seats),
-                self._p(self._seat_sets(seats_per_game)), int(net_seats), *value, *[self._p(t) for t in w], self._p(scratch),
-                scratch.numel(), self._p(sum_out), self._stream()))
-        return sum_out
+        return TarokVecEnv._bids_net(self, "tarok_playout_bids_net_list", weights, episode, worlds, depth, value_scale, pass_value, net_seats, contracts, deals, salt, seats,
+                                     seats_per_game, sum_out)
 
     def bid_round(self, episode, sums, playouts, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, seats=15, seats_per_game=None,
                   pass_value=False):
@@ -870,7 +858,7 @@ class TarokVecEnv:
         Read-only on the env."""
         with torch.cuda.device(self.device):
             out = torch.empty((self.n, 6 * int(discard_sets), 3), dtype=torch.uint8, device=self.device)
-            _native.check(self.L.tarok_exchange_candidates(self._h, int(discard_sets), int(salt) & ((1 << 64) - 1), int(seats),
+            _native.check(self.L.tarok_exchange_candidates(self._h, int(discard_sets), _salt(salt), int(seats),
                                                            self._p(self._seat_sets(seats_per_game)), self._p(out), self._stream()))
         return out
 

@@ -147,10 +147,10 @@ def _bid_net_front(net, net_seats, worlds, salt, threshold, contracts, net_depth
 
         def bid(env, episode, seats):
             if net_depth is None:
-                (env.playout_bids_net_list if net_list else env.playout_bids_net)(net, episode, worlds, net_seats=net_seats(seats), contracts=contracts, salt=salt, seats=seats, sum_out=sums)
+                playout.bids_net_launch(env, net_list, False)(net, episode, worlds, net_seats=net_seats(seats), contracts=contracts, salt=salt, seats=seats, sum_out=sums)
                 c, d, k = env.bid_round(episode, sums, int(worlds), threshold=threshold, contracts=contracts, seats=seats)
             else:
-                (env.playout_bids_net_list if net_list else env.playout_bids_net_value)(
+                playout.bids_net_launch(env, net_list, True)(
                     net, episode, worlds, net_depth, net_value_scale, pass_value=pass_value, net_seats=net_seats(seats), contracts=contracts,
                     salt=salt, seats=seats, sum_out=sums)
                 c, d, k = env.bid_round(episode, sums, int(worlds), threshold=threshold, contracts=contracts, seats=seats,
@@ -208,11 +208,11 @@ def _exchange_net_front(net, net_seats, worlds, discard_sets, salt, net_depth=No
 
         def exchange(env, seats):
             if net_depth is None:
-                (env.playout_exchange_net_list if net_list else env.playout_exchange_net)(
+                playout.exchange_net_launch(env, net_list, False)(
                     net, worlds, discard_sets, net_seats=net_seats(seats), salt=salt, seats=seats, sum_out=sums, choice_out=chosen["choice"],
                     discards_out=chosen["discards"])
             else:
-                (env.playout_exchange_net_list if net_list else env.playout_exchange_net_value)(
+                playout.exchange_net_launch(env, net_list, True)(
                     net, worlds, discard_sets, net_depth, net_value_scale, net_seats=net_seats(seats), salt=salt, seats=seats, sum_out=sums,
                     choice_out=chosen["choice"], discards_out=chosen["discards"])
             env.exchange(chosen["choice"], chosen["discards"])

@@ -137,12 +137,10 @@ class ExchangeLearner:
         reset with the exchange deferred, the teacher's launch on every declarer, its candidates' discards and the head's
         launch for its input rows.  The games are left waiting for the exchange."""
         self.env.reset(episode=episode, defer_exchange=True)
-        if self.net_list:
-            sums, _, _ = self.env.playout_exchange_net_list(self.net_weights, self.worlds, self.discard_sets, self.net_depth,
-                                                            self.net_value_scale, net_seats=self.net_seats, salt=self.salt)
-        elif self.net_weights is not None:
-            sums, _, _ = self.env.playout_exchange_net_value(self.net_weights, self.worlds, self.discard_sets, self.net_depth,
-                                                             self.net_value_scale, net_seats=self.net_seats, salt=self.salt)
+        if self.net_list or self.net_weights is not None:
+            launch = P.exchange_net_launch(self.env, self.net_list, True)
+            sums, _, _ = launch(self.net_weights, self.worlds, self.discard_sets, self.net_depth, self.net_value_scale,
+                                net_seats=self.net_seats, salt=self.salt)
         else:
             sums, _, _ = self.env.playout_exchange(self.worlds, self.samples, self.discard_sets, salt=self.salt)
         cands = self.env.exchange_candidates(self.discard_sets, salt=self.salt)

@@ -23,6 +23,16 @@ def spelling(prefix="", pattern="%s", **other):
     return lambda text: prefix + text.format(**names)
 
 
+def exchange_net_launch(env, net_list, value):
+    """The env's net-played exchange launch: the compacted list's; else, `value`: the one that takes (depth, value_scale)."""
+    return env.playout_exchange_net_list if net_list else env.playout_exchange_net_value if value else env.playout_exchange_net
+
+
+def bids_net_launch(env, net_list, value):
+    """The env's net-played bid launch: the compacted list's; else, `value`: the one that takes (depth, value_scale, pass_value)."""
+    return env.playout_bids_net_list if net_list else env.playout_bids_net_value if value else env.playout_bids_net
+
+
 def one_world_kind(voids, hidden, say=spelling()):
     if voids and hidden:
         raise ValueError(say("{hidden}=True is not built together with {voids}=True: give one of the two"))
