@@ -1191,6 +1191,83 @@ int tarok_playout_bids_net_list(tarok_env *env, uint32_t episode, const uint8_t 
                                 const float *b2, const void *w3, const float *b3, void *scratch, int64_t scratch_bytes,
                                 int32_t *sum_out, void *stream);
 
+/* The two list launches above with SEQUENTIAL HALVING: later worlds are spent only on the leading candidates
+ * of a game, or the leading rows of a (game, viewer).  The arguments are the _net_list launches', with `rounds,
+ * round_worlds` in the place of `worlds`: round_worlds is a HOST array of `rounds` ints, read during the call, under
+ * tarok_playout_cards_net_halving's rules — rounds 1..TAROK_PLAYOUT_MAX_ROUNDS, every entry >= 1, W = their sum <=
+ * TAROK_PLAYOUT_MAX_WORLDS.  depth 0 or TAROK_PLAYOUT_FRONT_MAX_DEPTH: every item is played to the last card; 1..12: an
+ * item stops at the viewer's depth-th decision, as in the list launches.  value_scale finite and > 0.  pass_value (bids) 0
+ * or 1 at any depth.
+ *
+ * The existing launches' definition stays word for word: "waiting" and "takes part", the worlds (wkey), the candidates
+ * (ckey) and the rows, the playout keys with k = 0, the Bot's exchange inside a bid item and a pass item, the viewer, and
+ * net_seats.  No key depends on a launch size: world w is the world every existing launch deals under w.
+ *
+ * The rounds.  With e0 / e1 the cumulative world counts before / after round r, round r plays every ARM still alive once in
+ * each of the worlds e0 .. e1 - 1.
+ *   exchange   the arms of a game that takes part are its candidates r = i x D + d (i < its groups, d < D = discard_sets),
+ *              compared by the declarer's column of the running sums;
+ *   bids       the arms of a unit (g, v) are the rows of `contracts`, compared by the viewer's running sum;
+ *   the pass   with pass_value = 1 row 19 is NOT an arm: it is the bar every answer is held to, played in every round its
+ *              unit plays and never eliminated.
+ * The survivor rule, after a round that is not the last, with k arms alive and keep = max(1, ceil(k / 2)): arm j stays iff
+ * fewer than `keep` alive arms beat it, arm a beating j when S_a > S_j, or S_a = S_j and a < j (the highest sums stay, ties to
+ * the lower index: tarok_playout_cards_halving's rule).  A game or unit with one arm alive plays no further round, and
+ * neither does its pass item.
+ *
+ * Outputs: each optional, at least one given; EVERY row is written.
+ *   exchange   sum_out [N, 6 D, 4] i32 the running sums; count_out [N, 6 D] i32 the cumulative end e1 of the last round the
+ *              candidate played (0: none); choice_out [N] i8 / discards_out [N,3] u8: for a game that takes part the first
+ *              candidate at the maximum of the declarer's sum among the candidates alive at the end, with its discards; else
+ *              exactly the list launch's (the Bot's exchange for a waiting game outside the set; -1 / 255).
+ *   bids       sum_out [N,4,20] i32 (0 on the rows that are not played); count_out [N,4,20] i32 as above — row 19's is the end
+ *              of its unit's last round; value_out [N,4,20] i32: 0 where the count is 0, else the nearest integer to sum x W /
+ *              count, halves away from zero, in 64-bit integers — exactly sum x W / count where the count divides W.  value_out
+ *              stands in for sum_out as the `sums` of tarok_bid_round / tarok_bid_round_pass at playouts = W.
+ * Consequences: a one-round schedule (W) writes the _net_list launch's bytes at worlds = W, for every output, depth and
+ * pass_value, with value_out = sum_out and count W on the live rows; and for any schedule a row whose count is e equals that
+ * launch's row at worlds = e (all four columns, for the exchange).
+ *
+ * The launches (all on `stream`; no host read, no allocation, no synchronisation: capturable, the bids' first call
+ * included): for the bids the deal; one init kernel (the on and alive words, the running sums and counts zeroed); then per
+ * round the prefix sum over the units, the round's items — its worlds alone, under their true indices; every slot below the
+ * round's total and none at or above it —, the playouts over a grid sized by the round's bound, and the sums with the
+ * survivor rule, which writes the next on words (0 once one arm is left) and, on the last round, the outputs.
+ *
+ * The bounds, which the host computes without reading the env.  a_0 = 6 x D (exchange) or R = the rows of `contracts` (bids);
+ * a_{r+1} = ceil(a_r / 2);
+ *     exchange  B_r = n x a_r x W_r
+ *     bids      B_r = n x U x (a_r + pass_value) x W_r, U = popc(seats) without seats_per_game, else 4
+ * and B = max_r B_r sizes the four item arrays; the play grid of round r is B_r's.
+ * scratch: device memory, 16-byte aligned, contents undefined afterwards.  With units = 6 n / 4 n:
+ *     exchange  bytes = 48 x B + 20 x 6 n D + 12 x units + 4 x ceil(units / 256) + 4
+ *     bids      bytes = 48 x B + 8 x 80 n + 40 n + 12 x units + 4 x ceil(units / 256) + 4
+ * each rounded up to a multiple of 16 — the item arrays at B; a row's running sums and count; the bids' deal; the units' on,
+ * alive and base words; the scan's partials and the total word, in that order.
+ * tarok_playout_bids_net_halving_scratch_bytes takes the seat set the launch will get and per_game_seats = 1 where it will get
+ * a seats_per_game array.
+ * The _scratch_bytes entries return TAROK_EINVAL for a NULL env, a schedule outside the rules above, discard_sets outside
+ * 1..TAROK_EXCHANGE_MAX_SETS, contracts outside 1..TAROK_BID_ALL_CONTRACTS, seats outside 0..15, per_game_seats or
+ * pass_value outside 0..1, and a round bound that reaches 2^31 items.  The launches: TAROK_EINVAL (before any HIP call) for
+ * all of those, for everything the _net_list launches refuse (net_seats outside 0..15, a NULL weight array, depth outside
+ * 0..TAROK_PLAYOUT_FRONT_MAX_DEPTH, value_scale not finite or <= 0), a NULL or misaligned scratch, scratch_bytes below the
+ * size, and every output NULL. */
+int64_t tarok_playout_exchange_net_halving_scratch_bytes(const tarok_env *env, int rounds, const int *round_worlds,
+                                                         int discard_sets);
+int tarok_playout_exchange_net_halving(tarok_env *env, int rounds, const int *round_worlds, int discard_sets, uint64_t salt,
+                                       int seats, const uint8_t *seats_per_game, int net_seats, int depth, float value_scale,
+                                       const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
+                                       const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out,
+                                       int32_t *count_out, int8_t *choice_out, uint8_t *discards_out, void *stream);
+int64_t tarok_playout_bids_net_halving_scratch_bytes(const tarok_env *env, int rounds, const int *round_worlds, int contracts,
+                                                     int seats, int per_game_seats, int pass_value);
+int tarok_playout_bids_net_halving(tarok_env *env, uint32_t episode, const uint8_t *deals, int rounds, const int *round_worlds,
+                                   int contracts, uint64_t salt, int seats, const uint8_t *seats_per_game, int net_seats,
+                                   int depth, float value_scale, int pass_value, const void *w1, const float *b1,
+                                   const void *w2, const float *b2, const void *w3, const float *b3, void *scratch,
+                                   int64_t scratch_bytes, int32_t *sum_out, int32_t *count_out, int32_t *value_out,
+                                   void *stream);
+
 /* The learner's network input for a minibatch: features_out[j] [256] bf16 (0.0 / 1.0) = the bits
  * of feature_words[index[j]] (feature_words [M,4] u64 as written by feature_words_out; index
  * [n_samples] i64 sample numbers, or NULL for samples 0..n_samples-1).  Gather + expansion in one

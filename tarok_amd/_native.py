@@ -43,6 +43,8 @@ SYMBOLS = [
     "tarok_playout_net_halving_scratch_bytes", "tarok_playout_cards_net_halving",
     "tarok_playout_exchange_net_list_scratch", "tarok_playout_exchange_net_list",
     "tarok_playout_bids_net_list_scratch", "tarok_playout_bids_net_list",
+    "tarok_playout_exchange_net_halving_scratch_bytes", "tarok_playout_exchange_net_halving",
+    "tarok_playout_bids_net_halving_scratch_bytes", "tarok_playout_bids_net_halving",
 ]
 
 
@@ -224,6 +226,15 @@ def lib():
     L.tarok_playout_bids_net_list_scratch.argtypes = [vp, i32, i32, i32, i32, i32]
     L.tarok_playout_bids_net_list.restype = i32          # tarok_playout_bids_net_value's arguments; depth 0: to the last card
     L.tarok_playout_bids_net_list.argtypes = [vp, u32, vp, i32, i32, u64, i32, vp, i32, i32, f32, i32] + [vp] * 6 + [vp, i64, vp, vp]
+    # the _net_list launches' arguments with (rounds, round_worlds: a host int array) in the place of worlds, and the counts
+    L.tarok_playout_exchange_net_halving_scratch_bytes.restype = i64
+    L.tarok_playout_exchange_net_halving_scratch_bytes.argtypes = [vp, i32, vp, i32]
+    L.tarok_playout_exchange_net_halving.restype = i32
+    L.tarok_playout_exchange_net_halving.argtypes = [vp, i32, vp, i32, u64, i32, vp, i32, i32, f32] + [vp] * 6 + [vp, i64, vp, vp, vp, vp, vp]
+    L.tarok_playout_bids_net_halving_scratch_bytes.restype = i64   # (rounds, round_worlds, contracts, seats, per_game_seats, pass_value)
+    L.tarok_playout_bids_net_halving_scratch_bytes.argtypes = [vp, i32, vp, i32, i32, i32, i32]
+    L.tarok_playout_bids_net_halving.restype = i32
+    L.tarok_playout_bids_net_halving.argtypes = [vp, u32, vp, i32, vp, i32, u64, i32, vp, i32, i32, f32, i32] + [vp] * 6 + [vp, i64, vp, vp, vp, vp]
     L.tarok_learn_chain_distill.restype = i32
     L.tarok_learn_chain_distill.argtypes = [vp, i64] + [vp] * 4 + [f32] * 3 + [vp] * 17 + [vp, f32, vp, vp, vp, vp]
     L.tarok_front_lines_scratch_bytes.restype = i64; L.tarok_front_lines_scratch_bytes.argtypes = [i64]

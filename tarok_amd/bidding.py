@@ -31,7 +31,16 @@ def bid_loss(out, sums, playouts, reward_scale, contracts, pass_value=False):
     sums / playouts * reward_scale, Huber loss (delta 1) over the rows whose contract is in `contracts`, averaged over
     those entries.  The other columns enter neither the value nor the gradient.
     pass_value=True (out [M, >= 20], sums from playout_bids(pass_value=True)): row K.BID_PASS_ROW joins those rows — output
-    19 regresses on the value of a pass, same target, same loss."""
+    19 regresses on the value of a pass, same target, same loss.
+    playouts: a number, or a halving launch's counts [M, K.BID_ROWS] — a row's target is then its sum over its own count, and
+    a row with count 0 is not a target."""
+    if torch.is_tensor(playouts):
+        width = K.BID_ROWS if pass_value else BID_OPTIONS
+        rows = torch.cat([row_mask(contracts, out.device), torch.ones(1, dtype=torch.bool, device=out.device)])[:width]
+        count = playouts[:, :width]
+        on = rows.unsqueeze(0) & (count > 0)
+        target = sums[:, :width].to(torch.float32) * float(reward_scale) / count.clamp(min=1).to(torch.float32)
+        return F.huber_loss(out[:, :width].float()[on], target[on], reduction="mean", delta=1.0)
     if not pass_value:
         rows = row_mask(contracts, out.device)
         target = sums[:, :BID_OPTIONS].to(torch.float32) * (float(reward_scale) / float(playouts))
@@ -54,7 +63,8 @@ class BidLearner:
     """Regresses a PolicyNet on the playout teacher's bid values.
 
     env: a TarokVecEnv (never reset by the learner: both launches come before reset()), or None for a learner on the
-    CPU that is fed batches by hand (loss / step).  worlds, samples: the teacher's launch (playout_bids).  contracts: the
+    CPU that is fed batches by hand (loss / step).  worlds, samples: the teacher's launch (playout_bids).  worlds=None: 8, or with
+    net_halving= the schedule's sum.  contracts: the
     rows learned and bid.  playouts_equiv: the `playouts` bid_round() is told for the head's values, which are scaled to
     sums over that many playouts, so `threshold` stays in points per game as for the teacher.  pass_value=True: the teacher
     also values a pass (playout_bids(pass_value=True)), output 19 regresses on it, and round() holds every bid against the
@@ -66,11 +76,17 @@ class BidLearner:
     pass_value=True goes with net= only together with net_depth: the value launch plays the pass item too, and output 19
     regresses on its row 19; the plain net launch does not value the pass.  net_list=True (with net=): the one teacher
     launch is playout_bids_net_list, the same numbers from a compacted item list; it values the pass at any depth, so
-    pass_value=True then needs no net_depth.  Nothing else changes."""
+    pass_value=True then needs no net_depth.  Nothing else changes.
+    net_halving: a tuple of 1..4 positive world counts (with net=): the teacher is playout_bids_net_halving, which spends
+    later rounds' worlds on a viewer's leading rows only; it names the worlds itself (`worlds` None or their sum), goes with
+    net_depth and with pass_value at any depth, and collect() then returns the counts [N,4,20] in the place of the scalar
+    playouts."""
 
-    def __init__(self, env, worlds=8, samples=None, contracts=K.BID_DEFAULT_CONTRACTS, lr=1e-3, reward_scale=1.0 / 70.0,
-                 playouts_equiv=16, seed=0, pass_value=False, net=None, net_seats=15, net_list=False, net_depth=None,
+    def __init__(self, env, worlds=None, samples=None, contracts=K.BID_DEFAULT_CONTRACTS, lr=1e-3, reward_scale=1.0 / 70.0,
+                 playouts_equiv=16, seed=0, pass_value=False, net=None, net_seats=15, net_halving=None, net_list=False, net_depth=None,
                  net_value_scale=70.0):
+        self.net_halving = P.check_front_halving(net_halving, net, net_list, worlds, samples)
+        worlds = (8 if worlds is None else worlds) if self.net_halving is None else sum(self.net_halving)
         if net_list and net is None:
             raise ValueError("net_list packs the network's playouts: it needs net=")
         if net_depth is not None:
@@ -78,7 +94,7 @@ class BidLearner:
                 raise ValueError("net_depth stops the network's playouts: it needs net=")
             P.check_depth(net_depth, net_value_scale, P.spelling(), max_depth=K.PLAYOUT_FRONT_MAX_DEPTH)
         if net is not None:
-            if pass_value and net_depth is None and not net_list:
+            if pass_value and net_depth is None and not net_list and self.net_halving is None:
                 raise ValueError("net= without net_depth does not value the pass: pass_value=True goes with the Bot's playouts "
                                  "or with net_depth")
             if samples not in (None, 1):
@@ -118,6 +134,8 @@ class BidLearner:
 
     def loss(self, feature_words, sums, playouts):
         """bid_loss of the network on feature words [..., 4] and the teacher's sums [..., K.BID_ROWS] at `playouts`."""
+        if torch.is_tensor(playouts):
+            playouts = playouts.reshape(-1, K.BID_ROWS)
         return bid_loss(self.outputs(feature_words), sums.reshape(-1, K.BID_ROWS), playouts, self.reward_scale, self.contracts,
                         pass_value=self.pass_value)
 
@@ -138,7 +156,12 @@ class BidLearner:
     def collect(self, episode):
         """(feature_words [N,4,4] int64, sums [N,4,K.BID_ROWS] int32, playouts) of episode `episode`: the teacher's launch
         on every seat and the head's launch for its input rows."""
-        if self.net_list or self.net_weights is not None:
+        counts = None
+        if self.net_halving is not None:
+            sums, counts, _ = P.front_halving_launch(self.env, True)(self.net_weights, episode, self.net_halving, self.net_depth,
+                                                                     self.net_value_scale, pass_value=self.pass_value,
+                                                                     net_seats=self.net_seats, contracts=self.contracts, salt=self.salt)
+        elif self.net_list or self.net_weights is not None:
             launch = P.bids_net_launch(self.env, self.net_list, True)
             sums = launch(self.net_weights, episode, self.worlds, self.net_depth, self.net_value_scale, pass_value=self.pass_value,
                           net_seats=self.net_seats, contracts=self.contracts, salt=self.salt)
@@ -146,7 +169,7 @@ class BidLearner:
             sums = self.env.playout_bids(episode, self.worlds, self.samples, contracts=self.contracts, salt=self.salt,
                                          pass_value=self.pass_value)
         _, _, fw = self.env.bid_values(episode, self.weights(), self.scale, contracts=self.contracts, feature_words=True)
-        return fw, sums, self.worlds * self.samples
+        return fw, sums, self.worlds * self.samples if counts is None else counts
 
     def iterate(self):
         """collect() on a fresh episode and one step(); returns the loss before the step."""

@@ -1170,6 +1170,51 @@ TK_HOST_DEVICE __forceinline__ int64_t bid_list_bound(int64_t n, u32 seats, bool
     return n * (int64_t)viewers * (int64_t)__builtin_popcount(bid_list_rows(contracts, pass_value)) * (int64_t)worlds;
 }
 
+// Sequential halving over those lists (tarok_playout_exchange_net_halving / tarok_playout_bids_net_halving).
+// The ARMS are a game's candidates r = i * sets + d (up to 48) or a unit's rows of bid_row_mask (up to 19): bit j of a
+// 64-bit `alive` word.  The kernels, the host's bounds and tests/host_emu/front_halving_host.cpp share these statements.
+//   front_halving_keep    of k arms alive, max(1, ceil(k / 2)) stay
+//   front_halving_stays   the survivor rule as arm j's lane counts it: j stays iff fewer than `keep` alive arms beat it, arm a
+//                         beating j when S_a > S_j, or S_a = S_j and a < j — halve_alive's rule (highest sum, ties to the
+//                         lower index).  S_a = sums[a * stride]; the sums are re-read from memory (LDS in the kernels) in a
+//                         rolled loop over the alive bits: 48 sums are never held in registers (see halve_alive's comment).
+//   front_halving_alive   a_r: a_0 = arms, a_{r+1} = ceil(a_r / 2)
+//   exchange_halving_bound / bid_halving_bound   the round's item bound B_r
+//   front_halving_value   the nearest integer to sum * W / count, halves away from zero, in int64 (0 where count is 0)
+TK_HOST_DEVICE __forceinline__ u32 front_halving_keep(u32 k) { return k > 1u ? (k + 1u) >> 1 : 1u; }
+TK_HOST_DEVICE __forceinline__ bool front_halving_stays(const int *sums, u32 stride, u64 alive, u32 j) {
+    const u32 keep = front_halving_keep((u32)__builtin_popcountll(alive));
+    const int sj = sums[j * stride];
+    u32 beat = 0;
+#pragma nounroll
+    for (u64 rest = alive; rest; rest &= rest - 1ULL) {
+        const u32 a = (u32)__builtin_ctzll(rest);
+        const int sa = sums[a * stride];
+        beat += (sa > sj || (sa == sj && a < j)) ? 1u : 0u;
+    }
+    return beat < keep;
+}
+TK_HOST_DEVICE __forceinline__ u32 front_halving_alive(u32 arms, u32 round) {
+    u32 a = arms;
+    for (u32 r = 0; r < round; r++) a = (a + 1u) >> 1;
+    return a;
+}
+TK_HOST_DEVICE __forceinline__ int64_t exchange_halving_bound(int64_t n, u32 sets, u32 round, u32 round_worlds) {
+    return n * (int64_t)front_halving_alive(6u * sets, round) * (int64_t)round_worlds;
+}
+TK_HOST_DEVICE __forceinline__ int64_t bid_halving_bound(int64_t n, u32 seats, bool per_game, u32 contracts, u32 pass_value, u32 round,
+                                                        u32 round_worlds) {
+    const u32 viewers = per_game ? 4u : (u32)__builtin_popcount(seats & 15u);
+    const u32 arms = front_halving_alive((u32)__builtin_popcount(bid_row_mask(contracts)), round) + (pass_value ? 1u : 0u);
+    return n * (int64_t)viewers * (int64_t)arms * (int64_t)round_worlds;
+}
+TK_HOST_DEVICE __forceinline__ int front_halving_value(int sum, int worlds, int count) {
+    if (count <= 0) return 0;
+    const int64_t num = (int64_t)sum * (int64_t)worlds, mag = num < 0 ? -num : num;
+    const int64_t q = (2 * mag + (int64_t)count) / (2 * (int64_t)count);
+    return (int)(num < 0 ? -q : q);
+}
+
 // World wkey of a bidder: seat `viewer` holds its twelve cards and has seen nothing else, so the other 42 are dealt
 // again — redeal_hidden's four-capacity walk (12, 12, 12 and the talon's 6, then the talon's slot order) on the deal set
 // up as a Klop, where all six talon cards are un-owned.  The world is (A plane, B plane, talon ids); its C plane is the

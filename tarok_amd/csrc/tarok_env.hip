@@ -4685,6 +4685,352 @@ TK_KERNEL(TK_BLOCK, 64) void k_playout_bids_net_list_sum(int64_t rows /* n * 4 *
 }
 
 // ---------------------------------------------------------------------------
+// tarok_playout_exchange_net_halving / tarok_playout_bids_net_halving: sequential halving over the lists above.
+// Beside its `on` word a unit keeps an `alive` word (the arms still in the race; on = alive, plus the pass bit for the bids,
+// while the game or unit plays rounds, else 0), and every row a running sum and a count in the scratch.  A round is
+// tarok_playout_cards_net_halving's: the scan over the on words, the round's items in its worlds e0 .. e1 - 1 alone, under
+// their true indices, the playouts on the round's total, the sums and the survivor rule (front_halving_stays, one arm a lane).
+
+// Exchange, first launch: one thread a unit: the on and alive words, the unit's running sums and counts zeroed.
+TK_KERNEL(TK_BLOCK, 64) void k_playout_exchange_net_halving_init(int64_t units, u32 sets, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                                const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
+                                                                u32 *__restrict__ on, u32 *__restrict__ alive, int4 *__restrict__ rsum,
+                                                                int *__restrict__ rcnt) {
+    TK_VGPR_TOP(64, 63);
+    const int64_t u = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
+    if (u >= units) return;
+    const int64_t g = u / 6;
+    Game g0;
+    load_game(g0, s01, s23, g);
+    const ExchangePosition p = exchange_position(g0, seat_sets, seats, sets, g);
+    const u32 o = exchange_list_on(g0.contract, (u32)(u - g * 6), sets, p.takes_part);
+    on[u] = o;
+    alive[u] = o;
+    for (u32 d = 0; d < sets; d++) {
+        rsum[u * sets + d] = make_int4(0, 0, 0, 0);
+        rcnt[u * sets + d] = 0;
+    }
+}
+
+// Exchange, a round's items: playout_exchange_net_list_deal_body's team, barrier, keys and candidates; the team deals the
+// round's worlds e0 + lw, lw < round_worlds, into its world slots 0 .. round_worlds - 1, and row r = i * sets + d of a unit
+// whose bit d is on goes to the slot of the bit's rank in the word.  A game's items are popc(its on words) * round_worlds <=
+// a_r * round_worlds, so every slot written lies below the round's total and below the host's bound (tested all the same).
+template <bool VIEWER>
+__device__ __forceinline__ void playout_exchange_net_halving_deal_body(int64_t n, u32 bound, u64 pseed, u64 offset, u32 e0, u32 round_worlds,
+                                                                       u32 sets, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                                       const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
+                                                                       const Counters *__restrict__ cnt, const u32 *__restrict__ on,
+                                                                       const u32 *__restrict__ base, ulonglong2 *__restrict__ i01,
+                                                                       ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,
+                                                                       u64 *__restrict__ ires) {
+    __shared__ WorldAB world;
+    __shared__ u32 cand_dpk[(TK_BLOCK >> TK_PX_MIN_LG) * TK_PX_ROWS];
+    const PlayoutTeam t(lg, round_worlds);
+    const u32 L = t.L, lane = t.lane;
+    const int64_t g = t.g;
+    u32 *cand = cand_dpk + t.team * TK_PX_ROWS;
+    ulonglong2 a = {0, 0}, b = {0, 0};
+    u64 ebase = 0;
+    ExchangePosition p;
+    bool plays = false;
+    if (g < n) {
+        for (u32 i = 0; i < 6; i++) plays = plays || on[g * 6 + i] != 0u;      // (on: only games that take part)
+        if (plays) {
+            a = s01[g]; b = s23[g];
+            Game g0;
+            unpack(g0, a.x, a.y, b.x, b.y);
+            p = exchange_position(g0, seat_sets, seats, sets, g);
+            ebase = (u64)cnt[g].episode << 28;
+            for (u32 lw = lane; lw < round_worlds; lw += L) {
+                Game d = g0;
+                redeal_unseen(d, p.declarer, game_key(pseed, offset + (u64)g, (7ULL << 61) | ebase | (63ULL << 22) | (u64)(e0 + lw)));
+                world.store(t.slot0 + lw, d);
+            }
+            for (u32 r = lane; r < p.ncand; r += L) {
+                u32 i = r / sets, d = r - i * sets;
+                cand[r] = exchange_discards(g0, i, game_key(pseed, offset + (u64)g, (5ULL << 61) | ebase | ((u64)i << 6) | (u64)d));
+            }
+        }
+    }
+    __syncthreads();
+    if (!plays) return;
+    const u32 live = p.ncand * round_worlds;
+    for (u32 s = lane; s < live; s += L) {
+        const u32 r = s / round_worlds, lw = s - r * round_worlds, i = r / sets, d = r - i * sets;
+        const int64_t u = g * 6 + (int64_t)i;
+        const u32 o = on[u];
+        if (!((o >> d) & 1u)) continue;
+        const u32 it = net_list_slot(base[u], (u32)__popc(o & ((1u << d) - 1u)), round_worlds, lw);
+        if (it >= bound) continue;
+        Game h;
+        unpack(h, a.x, a.y, b.x, b.y);
+        world.load(t.slot0 + lw, h);
+        const u32 dpk = cand[r];
+        apply_exchange(h, i, dpk & 255, (dpk >> 8) & 255, (dpk >> 16) & 255);
+        u64 x0, x1, y0, y1;
+        pack(h, x0, x1, y0, y1);
+        i01[it] = make_ulonglong2(x0, x1);
+        i23[it] = make_ulonglong2(y0, y1);
+        ikey[it] = game_key(pseed, offset + (u64)g, (3ULL << 62) | ebase | (63ULL << 22) | ((u64)(8u * i + d) << 16) | ((u64)(e0 + lw) << 10));
+        ires[it] = VIEWER ? TK_PN_LIVE | (u64)p.declarer : TK_PN_LIVE;
+    }
+}
+
+#define TK_EXCHANGE_NET_HALVING_DEAL(NAME, VIEWER)                                                                                   \
+    TK_KERNEL(TK_BLOCK, 128) void NAME(int64_t n, u32 bound, u64 pseed /* seed ^ salt */, u64 offset, u32 e0, u32 round_worlds,       \
+                                      u32 sets, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,                             \
+                                      const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,                         \
+                                      const Counters *__restrict__ cnt, const u32 *__restrict__ on, const u32 *__restrict__ base,     \
+                                      ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,             \
+                                      u64 *__restrict__ ires) {                                                                       \
+        TK_VGPR_TOP(128, 127);                                                                                                        \
+        playout_exchange_net_halving_deal_body<VIEWER>(n, bound, pseed, offset, e0, round_worlds, sets, lg, seats, seat_sets, s01,    \
+                                                       s23, cnt, on, base, i01, i23, ikey, ires);                                     \
+    }
+TK_EXCHANGE_NET_HALVING_DEAL(k_playout_exchange_net_halving_deal, false)
+TK_EXCHANGE_NET_HALVING_DEAL(k_playout_exchange_net_halving_deal_value, true)
+#undef TK_EXCHANGE_NET_HALVING_DEAL
+
+// Exchange, a round's sums and the survivor rule: 16 lanes a game.  A lane takes the rows r = lane, lane + 16, lane + 32: a row
+// that played the round adds its round_worlds results, in integers, to its running sums and sets its count to the round's end
+// e1; the declarer's column of every row goes to the team's [48] ints in LDS.  After the barrier, not the last round: each
+// alive row's lane counts the arms that beat it (front_halving_stays) and ORs its bit into the team's six next words; after a
+// second barrier lanes 0..5 write the units' alive and on words — on = 0 once one arm is left.  The last round: every row's
+// sums and count are written, and the choice is the first row at the maximum of the declarer's sums among the rows alive.
+TK_KERNEL(TK_BLOCK, 64) void k_playout_exchange_net_halving_sum(int64_t n, u32 bound, u64 pseed /* seed ^ salt */, u64 offset, u32 e1,
+                                                               u32 round_worlds, u32 last, u32 sets, u32 seats,
+                                                               const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
+                                                               const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
+                                                               const u64 *__restrict__ gkey, const u64 *__restrict__ ires,
+                                                               u32 *__restrict__ on, u32 *__restrict__ alive, const u32 *__restrict__ base,
+                                                               int4 *__restrict__ rsum, int *__restrict__ rcnt, int4 *__restrict__ sum_out,
+                                                               int *__restrict__ count_out, int8_t *__restrict__ choice_out,
+                                                               uint8_t *__restrict__ discards_out) {
+    TK_VGPR_TOP(64, 63);
+    __shared__ int vals[(TK_BLOCK >> 4) * TK_PX_ROWS];
+    __shared__ u32 nexts[(TK_BLOCK >> 4) * 6];
+    const PlayoutTeam t(4);
+    const int64_t g = t.g;
+    int *val = vals + t.team * TK_PX_ROWS;
+    u32 *next = nexts + t.team * 6;
+    const u32 nrows = 6u * sets;
+    u64 al = 0;
+    ExchangePosition p;
+    Game g0;
+    if (t.lane < 6u) next[t.lane] = 0u;
+    if (g < n) {
+        load_game(g0, s01, s23, g);
+        p = exchange_position(g0, seat_sets, seats, sets, g);
+        for (u32 i = 0; i < 6; i++) al |= (u64)alive[g * 6 + i] << (i * sets);
+        for (u32 r = t.lane; r < nrows; r += t.L) {
+            const u32 i = r / sets, d = r - i * sets, o = on[g * 6 + i];
+            int4 s = rsum[g * nrows + r];
+            int c = rcnt[g * nrows + r];
+            if ((o >> d) & 1u) {
+                const u32 first = net_list_slot(base[g * 6 + i], (u32)__popc(o & ((1u << d) - 1u)), round_worlds, 0u);
+                for (u32 w = 0; w < round_worlds; w++) {
+                    const u64 sc = first + w < bound ? ires[first + w] : 0ULL;
+                    s.x += (int)(int16_t)sc; s.y += (int)(int16_t)(sc >> 16); s.z += (int)(int16_t)(sc >> 32); s.w += (int)(int16_t)(sc >> 48);
+                }
+                c = (int)e1;
+                rsum[g * nrows + r] = s;
+                rcnt[g * nrows + r] = c;
+            }
+            val[r] = p.declarer == 0 ? s.x : (p.declarer == 1 ? s.y : (p.declarer == 2 ? s.z : s.w));
+            if (last) {
+                if (sum_out) sum_out[g * nrows + r] = s;
+                if (count_out) count_out[g * nrows + r] = c;
+            }
+        }
+    }
+    __syncthreads();
+    if (!last) {
+        if (g < n)
+            for (u32 r = t.lane; r < nrows; r += t.L)
+                if (((al >> r) & 1ULL) && front_halving_stays(val, 1u, al, r)) atomicOr(next + r / sets, 1u << (r % sets));
+        __syncthreads();
+        if (g < n && t.lane < 6u) {
+            u32 left = 0;
+            for (u32 i = 0; i < 6; i++) left += (u32)__popc(next[i]);
+            alive[g * 6 + t.lane] = next[t.lane];
+            on[g * 6 + t.lane] = left > 1u ? next[t.lane] : 0u;      // a game down to one candidate plays no further round
+        }
+        return;
+    }
+    if (g >= n || t.lane != 0u || (!choice_out && !discards_out)) return;
+    int ch = -1;
+    u32 dpk = 0xFFFFFFu;
+    if (p.takes_part) {                                  // the first alive candidate at the maximum of the declarer's sums
+        u32 best = 0;
+        int top = 0;
+        bool none = true;
+#pragma nounroll
+        for (u64 rest = al; rest; rest &= rest - 1ULL) {
+            const u32 r = (u32)__builtin_ctzll(rest);
+            const int v = val[r];
+            if (none || v > top) { top = v; best = r; none = false; }
+        }
+        const u32 i = best / sets, d = best - i * sets;
+        ch = (int)i;
+        dpk = exchange_discards(g0, i, game_key(pseed, offset + (u64)g, (5ULL << 61) | ((u64)cnt[g].episode << 28) | ((u64)i << 6) | (u64)d));
+    } else if (p.waiting) {                              // the Bot's own exchange: group 0, its sampler under the game's key
+        ch = 0;
+        dpk = exchange_discards(g0, 0u, gkey[g]);
+    }
+    if (choice_out) choice_out[g] = (int8_t)ch;
+    if (discards_out) {
+        discards_out[g * 3 + 0] = (uint8_t)dpk; discards_out[g * 3 + 1] = (uint8_t)(dpk >> 8);
+        discards_out[g * 3 + 2] = (uint8_t)(dpk >> 16);
+    }
+}
+
+// Bids, second launch (after k_bid_deal): one thread a unit: the on word (the rows, and row 19 with pass_value), the alive word
+// (the rows alone: the pass is the bar, not an arm), the unit's running sums and counts zeroed.
+TK_KERNEL(TK_BLOCK, 64) void k_playout_bids_net_halving_init(int64_t n, u32 contracts, u32 pass_value, u32 seats,
+                                                            const uint8_t *__restrict__ seat_sets, const u64 *__restrict__ deal,
+                                                            u32 *__restrict__ on, u32 *__restrict__ alive, int4 *__restrict__ rsum,
+                                                            int4 *__restrict__ rcnt) {
+    TK_VGPR_TOP(64, 63);
+    const int64_t u = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x;
+    if (u >= n * 4) return;
+    const int64_t g = u >> 2;
+    u32 set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
+    if ((deal[g] | deal[n + g] | deal[2 * n + g] | deal[3 * n + g]) == 0) set = 0;      // an invalid deal row
+    const u32 o = bid_list_on(contracts, pass_value, (set >> ((u32)u & 3u)) & 1u);
+    on[u] = o;
+    alive[u] = o & ~(1u << TK_BID_PASS_ROW);
+    for (u32 q = 0; q < TAROK_BID_ROWS / 4; q++) {
+        rsum[u * (TAROK_BID_ROWS / 4) + q] = make_int4(0, 0, 0, 0);
+        rcnt[u * (TAROK_BID_ROWS / 4) + q] = make_int4(0, 0, 0, 0);
+    }
+}
+
+// Bids, a round's items: playout_bids_net_list_deal_body's team, barriers, keys and item setup, over the round's worlds
+// e0 + lw, lw < round_worlds, dealt into the team's world slots 0 .. round_worlds - 1.
+template <bool VIEWER, bool PASS>
+__device__ __forceinline__ void playout_bids_net_halving_deal_body(int64_t n, u32 bound, u64 pseed, u64 offset, u32 episode, u32 e0,
+                                                                   u32 round_worlds, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                                   const u64 *__restrict__ deal, const u32 *__restrict__ on,
+                                                                   const u32 *__restrict__ base, ulonglong2 *__restrict__ i01,
+                                                                   ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,
+                                                                   u64 *__restrict__ ires) {
+    static_assert(VIEWER || !PASS, "the pass item carries its viewer");
+    __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS], world_ids[TK_PO_WORLD_SLOTS];
+    const PlayoutTeam t(lg, round_worlds);
+    const u32 L = t.L, lane = t.lane, slot0 = t.slot0;
+    const int64_t g = t.g;
+    u64 h0 = 0, h1 = 0, h2 = 0, h3 = 0, tal = 0;
+    if (g < n) { h0 = deal[g]; h1 = deal[n + g]; h2 = deal[2 * n + g]; h3 = deal[3 * n + g]; tal = deal[4 * n + g]; }
+    const u64 ebase = (u64)episode << 28;
+#pragma unroll 1
+    for (u32 v = 0; v < 4; v++) {
+        const u32 o = g < n ? on[g * 4 + v] : 0u;        // (on: only viewers of the seat set with a valid deal row)
+        __syncthreads();                                 // the last viewer's items have read their worlds
+        if (o) {
+            for (u32 lw = lane; lw < round_worlds; lw += L) {
+                u64 A, B, ids;
+                bid_world(h0, h1, h2, h3, tal, v, game_key(pseed, offset + (u64)g, (2ULL << 61) | ebase | ((u64)v << 6) | (u64)(e0 + lw)), A, B, ids);
+                world_a[slot0 + lw] = A; world_b[slot0 + lw] = B; world_ids[slot0 + lw] = ids;
+            }
+        }
+        __syncthreads();
+        if (o) {
+            const u32 first = base[g * 4 + v];           // (bit 19 only under the PASS form: the launcher pairs them)
+            const u32 count = net_list_count(o, round_worlds);
+            for (u32 s = lane; s < count; s += L) {
+                const u32 q = s / round_worlds, lw = s - q * round_worlds, w = e0 + lw, r = kth_bit_word(o, 0u, q);
+                const u32 it = net_list_slot(first, q, round_worlds, lw);
+                if (it >= bound) continue;
+                const u64 pkey = game_key(pseed, offset + (u64)g, (3ULL << 61) | ebase | ((u64)v << 26) | ((u64)r << 21) | ((u64)w << 15));
+                Game h;
+                if constexpr (PASS) {                    // (k_playout_bids_pass's one setup for both kinds of item)
+                    u32 ct = bid_row_contract(r), d = ct == TK_KLOP ? 0u : v, kg = bid_row_king(r);
+                    if (r == (u32)TK_BID_PASS_ROW) pass_round(pkey, v, ct, d, kg);
+                    bid_game_as(h, world_a[slot0 + lw], world_b[slot0 + lw], world_ids[slot0 + lw], ct, d, kg);
+                } else {
+                    bid_game(h, world_a[slot0 + lw], world_b[slot0 + lw], world_ids[slot0 + lw], r, v);
+                }
+                if (h.phase == TK_PHASE_EXCHANGE) bot_exchange(h, pkey);
+                u64 x0, x1, y0, y1;
+                pack(h, x0, x1, y0, y1);
+                i01[it] = make_ulonglong2(x0, x1);
+                i23[it] = make_ulonglong2(y0, y1);
+                ikey[it] = pkey;
+                ires[it] = VIEWER ? TK_PN_LIVE | (u64)v : TK_PN_LIVE;
+            }
+        }
+    }
+}
+
+#define TK_BIDS_NET_HALVING_DEAL(NAME, VIEWER, PASS)                                                                                 \
+    TK_KERNEL(TK_BLOCK, 128) void NAME(int64_t n, u32 bound, u64 pseed /* seed ^ salt */, u64 offset, u32 episode, u32 e0,            \
+                                      u32 round_worlds, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,                     \
+                                      const u64 *__restrict__ deal, const u32 *__restrict__ on, const u32 *__restrict__ base,         \
+                                      ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,             \
+                                      u64 *__restrict__ ires) {                                                                       \
+        TK_VGPR_TOP(128, 127);                                                                                                        \
+        playout_bids_net_halving_deal_body<VIEWER, PASS>(n, bound, pseed, offset, episode, e0, round_worlds, lg, seats, seat_sets,    \
+                                                         deal, on, base, i01, i23, ikey, ires);                                       \
+    }
+TK_BIDS_NET_HALVING_DEAL(k_playout_bids_net_halving_deal, false, false)
+TK_BIDS_NET_HALVING_DEAL(k_playout_bids_net_halving_deal_value, true, false)
+TK_BIDS_NET_HALVING_DEAL(k_playout_bids_net_halving_deal_value_pass, true, true)
+#undef TK_BIDS_NET_HALVING_DEAL
+
+// Bids, a round's sums and the survivor rule: 32 lanes a unit, lane r < 20 its row r.  A row that played the round adds the
+// VIEWER's 16 bits of its round_worlds results to its running sum and sets its count to e1; the sums go to the team's [20]
+// ints in LDS.  After the barrier, not the last round: an alive row's lane counts the arms that beat it and ORs its bit into
+// the team's next word; after a second barrier lane 0 writes the unit's alive word and its on word — the survivors and the
+// pass bit the unit had, or 0 once one arm is left.  The last round: every row's sum, count and value are written.
+TK_KERNEL(TK_BLOCK, 64) void k_playout_bids_net_halving_sum(int64_t units, u32 bound, u32 e1, u32 round_worlds, u32 last, u32 worlds,
+                                                           const u64 *__restrict__ ires, u32 *__restrict__ on, u32 *__restrict__ alive,
+                                                           const u32 *__restrict__ base, int *__restrict__ rsum, int *__restrict__ rcnt,
+                                                           int *__restrict__ sum_out, int *__restrict__ count_out,
+                                                           int *__restrict__ value_out) {
+    TK_VGPR_TOP(64, 63);
+    __shared__ int vals[(TK_BLOCK >> 5) * 32];
+    __shared__ u32 nexts[TK_BLOCK >> 5];
+    const PlayoutTeam t(5);
+    const int64_t u = t.g;
+    const u32 r = t.lane, v = (u32)(u & 3);
+    int *val = vals + t.team * 32;
+    u32 o = 0, al = 0;
+    if (r == 0u) nexts[t.team] = 0u;
+    if (u < units) {
+        o = on[u]; al = alive[u];
+        if (r < (u32)TAROK_BID_ROWS) {
+            int s = rsum[u * TAROK_BID_ROWS + r], c = rcnt[u * TAROK_BID_ROWS + r];
+            if ((o >> r) & 1u) {
+                const u32 first = net_list_slot(base[u], (u32)__popc(o & ((1u << r) - 1u)), round_worlds, 0u);
+                for (u32 w = 0; w < round_worlds; w++) {
+                    const u64 sc = first + w < bound ? ires[first + w] : 0ULL;
+                    s += (int)(int16_t)(sc >> (16 * v));
+                }
+                c = (int)e1;
+                rsum[u * TAROK_BID_ROWS + r] = s;
+                rcnt[u * TAROK_BID_ROWS + r] = c;
+            }
+            val[r] = s;
+            if (last) {
+                if (sum_out) sum_out[u * TAROK_BID_ROWS + r] = s;
+                if (count_out) count_out[u * TAROK_BID_ROWS + r] = c;
+                if (value_out) value_out[u * TAROK_BID_ROWS + r] = front_halving_value(s, (int)worlds, c);
+            }
+        }
+    }
+    if (last) return;                                    // (launch-uniform)
+    __syncthreads();
+    if (u < units && ((al >> r) & 1u) && front_halving_stays(val, 1u, (u64)al, r)) atomicOr(nexts + t.team, 1u << r);
+    __syncthreads();
+    if (u < units && r == 0u) {
+        const u32 next = nexts[t.team];
+        alive[u] = next;
+        on[u] = (next & (next - 1u)) != 0u ? next | (o & (1u << TK_BID_PASS_ROW)) : 0u;     // one arm left: no further round
+    }
+}
+
+// ---------------------------------------------------------------------------
 // The reference agent's transition targets in its own form: what Nevronski_igralec.rezultat_stiha
 // builds per trick and rezultat_igre completes (Igralec.py:387-446), for every (trick, game, seat) of a recorded
 // rollout of whole tricks:  dy[54] = -70 on the cards that were not legal at the seat's decision (:392-393), on the
@@ -5547,6 +5893,38 @@ static bool bid_list_plan(const tarok_env *e, int worlds, int contracts, int sea
     return p.plan(e->n * 4, bid_list_bound(e->n, (u32)seats, per_game_seats != 0, (u32)contracts, (u32)pass_value, (u32)worlds),
                   e->n * 5 * (int64_t)sizeof(u64));
 }
+// The front halving launches as the host sizes them: the schedule, each round's bound B_r (the play grid's) and the list at
+// B = max B_r over the list launches' units, with an alive word after each on word.  The extra bytes: a row's running sums
+// and count — 16 + 4 bytes for each of the exchange's 6 D rows, 4 + 4 for each of the bids' 4 x 20 — and then the bids' deal.
+// false: what the list plans and halving_schedule refuse, or a round whose bound reaches 2^31.
+struct FrontHalvingPlan {
+    HalvingSchedule h;
+    ListScratch list;
+    int64_t round_bound[TAROK_PLAYOUT_MAX_ROUNDS] = {0, 0, 0, 0};
+    template <class Bound> bool plan(int64_t units, int64_t extra, Bound bound_of) {
+        int64_t bound = 0;
+        for (int r = 0; r < h.rounds; r++) {
+            round_bound[r] = bound_of((u32)r, (u32)h.w[r]);
+            if (round_bound[r] >= (1LL << 31)) return false;
+            bound = round_bound[r] > bound ? round_bound[r] : bound;
+        }
+        return list.plan(units, bound, extra, 1);
+    }
+};
+static bool exchange_halving_plan(const tarok_env *e, int rounds, const int *round_worlds, int discard_sets, FrontHalvingPlan &p) {
+    if (!e || !halving_schedule(rounds, round_worlds, p.h) || discard_sets < 1 || discard_sets > TAROK_EXCHANGE_MAX_SETS) return false;
+    return p.plan(e->n * 6, e->n * 6 * (int64_t)discard_sets * (int64_t)(sizeof(int4) + sizeof(int)),
+                  [&](u32 r, u32 wr) { return exchange_halving_bound(e->n, (u32)discard_sets, r, wr); });
+}
+static bool bid_halving_plan(const tarok_env *e, int rounds, const int *round_worlds, int contracts, int seats, int per_game_seats,
+                             int pass_value, FrontHalvingPlan &p) {
+    if (!e || !halving_schedule(rounds, round_worlds, p.h) || contracts < 1 || contracts > TAROK_BID_ALL_CONTRACTS || seats < 0 ||
+        seats > 15 || per_game_seats < 0 || per_game_seats > 1 || pass_value < 0 || pass_value > 1)
+        return false;
+    return p.plan(e->n * 4, e->n * 4 * TAROK_BID_ROWS * (int64_t)(2 * sizeof(int)) + e->n * 5 * (int64_t)sizeof(u64), [&](u32 r, u32 wr) {
+        return bid_halving_bound(e->n, (u32)seats, per_game_seats != 0, (u32)contracts, (u32)pass_value, r, wr);
+    });
+}
 }
 
 int tarok_playout_cards(tarok_env *e, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game, int32_t *sum_out,
@@ -5832,6 +6210,104 @@ int tarok_playout_bids_net_list(tarok_env *e, uint32_t episode, const uint8_t *d
     launch_net_play(p.bound, a.total, net_seats, a, w, s, depth, value_scale);
     hipLaunchKernelGGL(k_playout_bids_net_list_sum, grid_for(rows), dim3(TK_BLOCK), 0, s, rows, (u32)p.bound, (u32)worlds, a.on, a.base,
                        a.ires, sum_out);
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int64_t tarok_playout_exchange_net_halving_scratch_bytes(const tarok_env *e, int rounds, const int *round_worlds, int discard_sets) {
+    FrontHalvingPlan p;
+    return exchange_halving_plan(e, rounds, round_worlds, discard_sets, p) ? p.list.bytes : (int64_t)TAROK_EINVAL;
+}
+
+// tarok_playout_exchange_net_list with sequential halving over a game's candidates: the init, then per round the scan, the
+// round's items, the playouts and the sums with the survivor rule — 1 + 6 x rounds launches on `stream`, nothing allocated, no
+// host read.
+int tarok_playout_exchange_net_halving(tarok_env *e, int rounds, const int *round_worlds, int discard_sets, uint64_t salt, int seats,
+                                       const uint8_t *seats_per_game, int net_seats, int depth, float value_scale, const void *w1,
+                                       const float *b1, const void *w2, const float *b2, const void *w3, const float *b3, void *scratch,
+                                       int64_t scratch_bytes, int32_t *sum_out, int32_t *count_out, int8_t *choice_out,
+                                       uint8_t *discards_out, void *stream) {
+    FrontHalvingPlan p;
+    const PolicyWeights w = TK_WEIGHTS(w1, b1, w2, b2, w3, b3);
+    // depth 0 is "to the last card", and a bad value_scale is refused there too
+    if (!e || seats < 0 || seats > 15 || !exchange_halving_plan(e, rounds, round_worlds, discard_sets, p) ||
+        !depth_args_ok(depth, 0, TAROK_PLAYOUT_FRONT_MAX_DEPTH, value_scale) ||
+        !net_args_ok(net_seats, w, scratch, scratch_bytes, p.list.bytes) || (!sum_out && !count_out && !choice_out && !discards_out))
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = e->n;
+    const ListArrays a = p.list.carve(scratch);
+    int4 *rsum = reinterpret_cast<int4 *>(a.extra);
+    int *rcnt = reinterpret_cast<int *>(rsum + n * 6 * discard_sets);
+    u32 *alive = a.on + p.list.units;
+    const u64 pseed = e->seed ^ (u64)salt;
+    hipLaunchKernelGGL(k_playout_exchange_net_halving_init, grid_for(p.list.units), dim3(TK_BLOCK), 0, s, p.list.units, (u32)discard_sets,
+                       (u32)seats, seats_per_game, e->s01, e->s23, a.on, alive, rsum, rcnt);
+    for (int r = 0; r < p.h.rounds; r++) {
+        const int wr = p.h.w[r];
+        const u32 bound = (u32)p.round_bound[r];
+        launch_list_scan(p.list, a, wr, s);
+        const u32 lg = playout_lg(TK_PX_MIN_LG, wr);
+        hipLaunchKernelGGL(depth ? k_playout_exchange_net_halving_deal_value : k_playout_exchange_net_halving_deal, playout_grid(e, lg),
+                           dim3(TK_BLOCK), 0, s, n, bound, pseed, e->offset, (u32)(p.h.end[r] - wr), (u32)wr, (u32)discard_sets, lg,
+                           (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, a.on, a.base, a.i01, a.i23, a.ikey, a.ires);
+        launch_net_play(p.round_bound[r], a.total, net_seats, a, w, s, depth, value_scale);
+        hipLaunchKernelGGL(k_playout_exchange_net_halving_sum, dim3((unsigned)((n + 15) / 16)), dim3(TK_BLOCK), 0, s, n, bound, pseed,
+                           e->offset, (u32)p.h.end[r], (u32)wr, (u32)(r == p.h.rounds - 1), (u32)discard_sets, (u32)seats, seats_per_game,
+                           e->s01, e->s23, e->cnt, e->gkey, a.ires, a.on, alive, a.base, rsum, rcnt, reinterpret_cast<int4 *>(sum_out),
+                           count_out, choice_out, discards_out);
+    }
+    HIPCHK(hipGetLastError());
+    return TAROK_OK;
+}
+
+int64_t tarok_playout_bids_net_halving_scratch_bytes(const tarok_env *e, int rounds, const int *round_worlds, int contracts, int seats,
+                                                     int per_game_seats, int pass_value) {
+    FrontHalvingPlan p;
+    return bid_halving_plan(e, rounds, round_worlds, contracts, seats, per_game_seats, pass_value, p) ? p.list.bytes : (int64_t)TAROK_EINVAL;
+}
+
+// tarok_playout_bids_net_list with sequential halving over a unit's rows: the deal, the init, then per round the scan, the
+// round's items, the playouts and the sums with the survivor rule — 2 + 6 x rounds launches on `stream`, nothing allocated, no
+// host read.  pass_value with depth 0: the _value kernels at the depth that never stops, as the list launch.
+int tarok_playout_bids_net_halving(tarok_env *e, uint32_t episode, const uint8_t *deals, int rounds, const int *round_worlds, int contracts,
+                                   uint64_t salt, int seats, const uint8_t *seats_per_game, int net_seats, int depth, float value_scale,
+                                   int pass_value, const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
+                                   const float *b3, void *scratch, int64_t scratch_bytes, int32_t *sum_out, int32_t *count_out,
+                                   int32_t *value_out, void *stream) {
+    FrontHalvingPlan p;
+    const PolicyWeights w = TK_WEIGHTS(w1, b1, w2, b2, w3, b3);
+    if (!e || !bid_halving_plan(e, rounds, round_worlds, contracts, seats, seats_per_game != nullptr, pass_value, p) ||
+        !depth_args_ok(depth, 0, TAROK_PLAYOUT_FRONT_MAX_DEPTH, value_scale) ||
+        !net_args_ok(net_seats, w, scratch, scratch_bytes, p.list.bytes) || (!sum_out && !count_out && !value_out))
+        return TAROK_EINVAL;
+    HIPCHK(hipSetDevice(e->device));
+    if (pass_value && !depth) depth = TAROK_PLAYOUT_FRONT_MAX_DEPTH;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = e->n;
+    const ListArrays a = p.list.carve(scratch);
+    int *rsum = reinterpret_cast<int *>(a.extra);
+    int *rcnt = rsum + n * 4 * TAROK_BID_ROWS;
+    u64 *deal = reinterpret_cast<u64 *>(rcnt + n * 4 * TAROK_BID_ROWS);
+    u32 *alive = a.on + p.list.units;
+    hipLaunchKernelGGL(k_bid_deal, grid_for(n), dim3(TK_BLOCK), 0, s, n, e->seed, e->offset, episode, deals, deal);
+    hipLaunchKernelGGL(k_playout_bids_net_halving_init, grid_for(p.list.units), dim3(TK_BLOCK), 0, s, n, (u32)contracts, (u32)pass_value,
+                       (u32)seats, seats_per_game, deal, a.on, alive, reinterpret_cast<int4 *>(rsum), reinterpret_cast<int4 *>(rcnt));
+    const auto kdeal = !depth ? k_playout_bids_net_halving_deal
+                              : (pass_value ? k_playout_bids_net_halving_deal_value_pass : k_playout_bids_net_halving_deal_value);
+    for (int r = 0; r < p.h.rounds; r++) {
+        const int wr = p.h.w[r];
+        const u32 bound = (u32)p.round_bound[r];
+        launch_list_scan(p.list, a, wr, s);
+        const u32 lg = playout_lg(TK_PB_MIN_LG, wr);
+        hipLaunchKernelGGL(kdeal, playout_grid(e, lg), dim3(TK_BLOCK), 0, s, n, bound, e->seed ^ (u64)salt, e->offset, episode,
+                           (u32)(p.h.end[r] - wr), (u32)wr, lg, (u32)seats, seats_per_game, deal, a.on, a.base, a.i01, a.i23, a.ikey, a.ires);
+        launch_net_play(p.round_bound[r], a.total, net_seats, a, w, s, depth, value_scale);
+        hipLaunchKernelGGL(k_playout_bids_net_halving_sum, dim3((unsigned)((p.list.units + 7) / 8)), dim3(TK_BLOCK), 0, s, p.list.units,
+                           bound, (u32)p.h.end[r], (u32)wr, (u32)(r == p.h.rounds - 1), (u32)p.h.worlds, a.ires, a.on, alive, a.base, rsum,
+                           rcnt, sum_out, count_out, value_out);
+    }
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }

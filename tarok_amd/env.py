@@ -717,6 +717,72 @@ class TarokVecEnv:
         return TarokVecEnv._bids_net(self, "tarok_playout_bids_net_list", weights, episode, worlds, depth, value_scale, pass_value, net_seats, contracts, deals, salt, seats,
                                      seats_per_game, sum_out)
 
+    def playout_exchange_net_halving_scratch(self, round_worlds, discard_sets=4):
+        """The scratch tensor of playout_exchange_net_halving at (schedule, discard_sets) (uint8,
+        tarok_playout_exchange_net_halving_scratch_bytes: the largest round's item arrays at its bound, every row's running sums
+        and count, 12 bytes per (game, group), the scan's partials and the total word), cached on the env per shape: a caller
+        that captures the launch asks for it BEFORE the capture."""
+        schedule, (discard_sets,) = P.check_halving(round_worlds, option="round_worlds"), _sizes(discard_sets=discard_sets)
+        return self._scratch(("exchange_halving", schedule, discard_sets), self.L.tarok_playout_exchange_net_halving_scratch_bytes,
+                             len(schedule), (C.c_int * len(schedule))(*schedule), discard_sets)
+
+    def playout_exchange_net_halving(self, weights, round_worlds, discard_sets=4, depth=None, value_scale=70.0, net_seats=15, salt=0,
+                                     seats=15, seats_per_game=None, scratch=None, sum_out=None, count_out=None, choice_out=None,
+                                     discards_out=None):
+        """playout_exchange_net_list with sequential halving over a game's candidates (tarok_playout_exchange_net_halving):
+        round r plays the candidates still alive once in each of round_worlds[r] fresh worlds, and after every round but the
+        last the better half by the declarer's sum stays alive, ties to the lower row.  round_worlds=(W,) is
+        playout_exchange_net_list(weights, W) to the byte.  depth / value_scale / net_seats and everything else: the list
+        launch's.  scratch: the caller's uint8 tensor of at least playout_exchange_net_halving_scratch(round_worlds,
+        discard_sets).numel() bytes (None: that cached one).  Returns (sum [N, 6 * discard_sets, 4] int32, count [N, 6 *
+        discard_sets] int32 — the worlds behind every row —, choice [N] int8 and discards [N,3] uint8: the first candidate at
+        the maximum of the declarer's sums among the candidates alive at the end)."""
+        schedule = P.check_halving(round_worlds, option="round_worlds")
+        net_seats, d, value_scale, w = TarokVecEnv._net_args(self, weights, net_seats, depth, value_scale, K.PLAYOUT_FRONT_MAX_DEPTH)
+        scratch = self.playout_exchange_net_halving_scratch(schedule, discard_sets) if scratch is None else scratch
+        with torch.cuda.device(self.device):
+            sum_out, choice_out, discards_out = TarokVecEnv._exchange_outputs(self, discard_sets, sum_out, choice_out, discards_out)
+            count_out = self._empty(count_out, (self.n, 6 * int(discard_sets)), torch.int32)
+            _native.check(self.L.tarok_playout_exchange_net_halving(
+                self._h, len(schedule), (C.c_int * len(schedule))(*schedule), int(discard_sets), _salt(salt), int(seats),
+                self._p(self._seat_sets(seats_per_game)), net_seats, d, value_scale, *w, self._p(scratch), scratch.numel(),
+                self._p(sum_out), self._p(count_out), self._p(choice_out), self._p(discards_out), self._stream()))
+        return sum_out, count_out, choice_out, discards_out
+
+    def playout_bids_net_halving_scratch(self, round_worlds, contracts=K.BID_DEFAULT_CONTRACTS, seats=15, per_game=False, pass_value=False):
+        """The scratch tensor of playout_bids_net_halving (uint8, tarok_playout_bids_net_halving_scratch_bytes: the largest
+        round's item arrays at its bound, every row's running sum and count, the deal, 12 bytes per (game, viewer), the scan's
+        partials and the total word), cached on the env per shape as playout_bids_net_list_scratch caches its own: a caller
+        that captures the launch asks for it BEFORE the capture."""
+        schedule, (contracts,), seats = P.check_halving(round_worlds, option="round_worlds"), _sizes(contracts=contracts), int(seats)
+        if not 0 <= seats <= 15:
+            raise ValueError("seats: a 4-bit seat set, 0..15")
+        key = ("bids_halving", schedule, contracts, 15 if per_game else seats, bool(per_game), bool(pass_value))
+        return self._scratch(key, self.L.tarok_playout_bids_net_halving_scratch_bytes, len(schedule), (C.c_int * len(schedule))(*schedule),
+                             contracts, seats, int(bool(per_game)), int(bool(pass_value)))
+
+    def playout_bids_net_halving(self, weights, episode, round_worlds, depth=None, value_scale=70.0, pass_value=False, net_seats=15,
+                                 contracts=K.BID_DEFAULT_CONTRACTS, deals=None, salt=0, seats=15, seats_per_game=None, scratch=None,
+                                 sum_out=None, count_out=None, value_out=None):
+        """playout_bids_net_list with sequential halving over a viewer's rows (tarok_playout_bids_net_halving): round r plays
+        the rows still alive once in each of round_worlds[r] fresh worlds, and after every round but the last the better half
+        by the viewer's sum stays alive, ties to the lower row.  With pass_value=True row K.BID_PASS_ROW is not in the race: it
+        is played in every round its viewer plays.  round_worlds=(W,) is playout_bids_net_list(weights, episode, W) to the
+        byte.  Returns (sum [N,4,20] int32, count [N,4,20] int32 — the worlds behind every row —, value [N,4,20] int32: sum x W
+        / count to the nearest integer, which bid_round takes as its sums at playouts = W = sum(round_worlds))."""
+        schedule = P.check_halving(round_worlds, option="round_worlds")
+        net_seats, d, value_scale, w = TarokVecEnv._net_args(self, weights, net_seats, depth, value_scale, K.PLAYOUT_FRONT_MAX_DEPTH)
+        if scratch is None:
+            scratch = self.playout_bids_net_halving_scratch(schedule, contracts, seats, seats_per_game is not None, pass_value)
+        deals = self._dev(deals, torch.uint8, (self.n, 54))
+        with torch.cuda.device(self.device):
+            sum_out, count_out, value_out = (self._empty(t, (self.n, 4, K.BID_ROWS), torch.int32) for t in (sum_out, count_out, value_out))
+            _native.check(self.L.tarok_playout_bids_net_halving(
+                self._h, int(episode), self._p(deals), len(schedule), (C.c_int * len(schedule))(*schedule), int(contracts), _salt(salt),
+                int(seats), self._p(self._seat_sets(seats_per_game)), net_seats, d, value_scale, int(bool(pass_value)), *w,
+                self._p(scratch), scratch.numel(), self._p(sum_out), self._p(count_out), self._p(value_out), self._stream()))
+        return sum_out, count_out, value_out
+
     def bid_round(self, episode, sums, playouts, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, seats=15, seats_per_game=None,
                   pass_value=False):
         """The bidding round of every game on the device (tarok_bid_round; Igra.licitacija's control flow): the seats of

@@ -136,17 +136,25 @@ def _net_front_args(net, net_seats, samples, what, net_depth=None, net_value_sca
 
 
 def _bid_net_front(net, net_seats, worlds, salt, threshold, contracts, net_depth=None, net_value_scale=70.0, pass_value=False,
-                   net_list=False):
+                   net_list=False, net_halving=None):
     """_bid_front whose playouts the network plays: ONE tarok_playout_bids_net at `worlds` with the pass's seat set —
     net_seats inside the playouts, or the pass's own set for "own" — and ONE tarok_bid_round at playouts = worlds.
     net_depth: tarok_playout_bids_net_value in its place; pass_value (with net_depth only): its pass item, and
     tarok_bid_round_pass with `threshold` the margin over the pass, as for the Bot teacher.  net_list: the same arguments
-    to tarok_playout_bids_net_list in either launch's place."""
+    to tarok_playout_bids_net_list in either launch's place.  net_halving: ONE tarok_playout_bids_net_halving at that schedule
+    in the launch's place, whose value_out is the round's sums at playouts = W, the schedule's sum."""
     def make(env):
         sums = _empty(env, (env.n, 4, K.BID_ROWS), torch.int32)
+        raw, counts = ((_empty(env, (env.n, 4, K.BID_ROWS), torch.int32) for _ in range(2)) if net_halving is not None else (None, None))
 
         def bid(env, episode, seats):
-            if net_depth is None:
+            if net_halving is not None:                  # (sums holds value_out: what the round reads)
+                playout.front_halving_launch(env, True)(
+                    net, episode, net_halving, net_depth, net_value_scale, pass_value=pass_value, net_seats=net_seats(seats), contracts=contracts,
+                    salt=salt, seats=seats, sum_out=raw, count_out=counts, value_out=sums)
+                c, d, k = env.bid_round(episode, sums, sum(net_halving), threshold=threshold, contracts=contracts, seats=seats,
+                                        pass_value=pass_value)
+            elif net_depth is None:
                 playout.bids_net_launch(env, net_list, False)(net, episode, worlds, net_seats=net_seats(seats), contracts=contracts, salt=salt, seats=seats, sum_out=sums)
                 c, d, k = env.bid_round(episode, sums, int(worlds), threshold=threshold, contracts=contracts, seats=seats)
             else:
@@ -197,17 +205,24 @@ def _exchange_front(worlds, samples, discard_sets, salt):
     return make
 
 
-def _exchange_net_front(net, net_seats, worlds, discard_sets, salt, net_depth=None, net_value_scale=70.0, net_list=False):
+def _exchange_net_front(net, net_seats, worlds, discard_sets, salt, net_depth=None, net_value_scale=70.0, net_list=False,
+                        net_halving=None):
     """_exchange_front whose playouts the network plays: ONE tarok_playout_exchange_net at (worlds, discard_sets) with the
     pass's seat set — net_seats inside the playouts, or the pass's own set for "own" — and one tarok_exchange.  net_depth:
     tarok_playout_exchange_net_value in its place.  net_list: the same arguments to tarok_playout_exchange_net_list in either
-    launch's place."""
+    launch's place.  net_halving: ONE tarok_playout_exchange_net_halving at that schedule in the launch's place; its choice
+    and discards go to tarok_exchange."""
     def make(env):
         sums = _empty(env, (env.n, 6 * int(discard_sets), 4), torch.int32)
         chosen = dict(choice=_empty(env, env.n, torch.int8), discards=_empty(env, (env.n, 3), torch.uint8))
+        counts = _empty(env, (env.n, 6 * int(discard_sets)), torch.int32) if net_halving is not None else None
 
         def exchange(env, seats):
-            if net_depth is None:
+            if net_halving is not None:
+                playout.front_halving_launch(env, False)(
+                    net, net_halving, discard_sets, net_depth, net_value_scale, net_seats=net_seats(seats), salt=salt, seats=seats, sum_out=sums,
+                    count_out=counts, choice_out=chosen["choice"], discards_out=chosen["discards"])
+            elif net_depth is None:
                 playout.exchange_net_launch(env, net_list, False)(
                     net, worlds, discard_sets, net_seats=net_seats(seats), salt=salt, seats=seats, sum_out=sums, choice_out=chosen["choice"],
                     discards_out=chosen["discards"])
@@ -500,7 +515,7 @@ def evaluate_exchange_vs_bot(worlds, samples, discard_sets, n_games, episodes, s
 
 
 def evaluate_exchange_net_vs_bot(net, worlds, discard_sets, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None,
-                                 net_seats=15, cards=None, net_list=False, net_depth=None, net_value_scale=70.0):
+                                 net_seats=15, cards=None, net_halving=None, net_list=False, net_depth=None, net_value_scale=70.0):
     """evaluate_exchange_vs_bot with the playouts played by a network: net = policy_mlp's six tensors; in pass 1 + k the
     games seat k declared get their exchange from ONE tarok_playout_exchange_net at (worlds, discard_sets) — one playout
     per (candidate, world), the network's greedy card on the seats of net_seats (a 4-bit set of absolute seats; "own":
@@ -510,11 +525,14 @@ def evaluate_exchange_net_vs_bot(net, worlds, discard_sets, n_games, episodes, s
     not arguments of evaluate_exchange_vs_bot: that call's parameter list is pinned as it stands.)  net_depth: None, or
     1..13 — tarok_playout_exchange_net_value: the playouts stop at the declarer's net_depth-th decision and read the value
     head of `net` there at net_value_scale points per unit.  net_list=True: the launch is tarok_playout_exchange_net_list
-    with the same arguments — the same numbers from a compacted item list."""
+    with the same arguments — the same numbers from a compacted item list.  net_halving: a tuple of 1..4 positive world
+    counts — the launch is tarok_playout_exchange_net_halving, which spends later rounds' worlds on the leading candidates;
+    it names the worlds itself (`worlds` None or their sum), goes with net_depth and is not given with net_list=True."""
     if net_list and net is None:
         raise ValueError("net_list packs the network's playouts: it needs net=")
+    net_halving = playout.check_front_halving(net_halving, net, net_list, worlds, None)
     exchange = _exchange_net_front(*_net_front_args(net, net_seats, None, "candidate", net_depth, net_value_scale), worlds, discard_sets,
-                                   salt, net_depth, net_value_scale, bool(net_list))
+                                   salt, net_depth, net_value_scale, bool(net_list), net_halving)
     front = _front(inspect is not None, exchange=exchange)
     return duplicate_advantage(_passes(n_games, episodes, front, _front_cards(cards), inspect, device=device, seed=seed, mix=mix))
 
@@ -532,7 +550,7 @@ def evaluate_exchangenet_vs_bot(weights, n_games, episodes, seed=0, mix=K.MIX_BO
 
 def evaluate_bidding_vs_bot(worlds, samples, n_games, episodes, seed=0, device=0, salt=0, threshold=0,
                             contracts=K.BID_DEFAULT_CONTRACTS, inspect=None, pass_value=False, net=None, net_seats=15, cards=None,
-                            net_list=False, net_depth=None, net_value_scale=70.0):
+                            net_halving=None, net_list=False, net_depth=None, net_value_scale=70.0):
     """What is the bid alone worth?  The five duplicate passes on K.MIX_BOT's deals with the Bot making EVERY exchange and
     playing EVERY card; in pass 1 + k seat k bids by playouts — tarok_playout_bids at (worlds, samples) over `contracts`,
     then tarok_bid_round with `threshold` — against three Bot bidders, and calls its king by the same sums.  Pass 0 is the
@@ -548,7 +566,12 @@ def evaluate_bidding_vs_bot(worlds, samples, n_games, episodes, seed=0, device=0
     at the viewer's net_depth-th decision and read the value head of `net` there at net_value_scale points per unit; then
     pass_value=True is allowed too — the launch plays the pass item, and tarok_bid_round_pass holds every bid against it as
     for the Bot teacher.  net_list=True (with net): the launch is tarok_playout_bids_net_list with the same arguments — the
-    same numbers from a compacted item list.  With the defaults the call issues the launches it always did."""
+    same numbers from a compacted item list.  net_halving (with net): a tuple of 1..4 positive world counts — the launch is
+    tarok_playout_bids_net_halving, which spends later rounds' worlds on a viewer's leading rows; its value_out goes to the
+    round at playouts = the schedule's sum; it names the worlds itself (`worlds` None or their sum), goes with net_depth,
+    values the pass at any depth, and is not given with net_list=True.  With the defaults the call issues the launches it
+    always did."""
+    net_halving = playout.check_front_halving(net_halving, net, net_list, worlds, samples)
     if net is None:
         if net_depth is not None:
             raise ValueError("net_depth stops the network's playouts: it needs net=")
@@ -556,11 +579,11 @@ def evaluate_bidding_vs_bot(worlds, samples, n_games, episodes, seed=0, device=0
             raise ValueError("net_list packs the network's playouts: it needs net=")
         bid = _bid_front((worlds, samples), salt, threshold, contracts, pass_value)
     else:
-        if pass_value and net_depth is None:
+        if pass_value and net_depth is None and net_halving is None:
             raise ValueError("net= without net_depth does not value the pass: pass_value=True goes with the Bot's playouts or "
                              "with net_depth")
         bid = _bid_net_front(*_net_front_args(net, net_seats, samples, "option", net_depth, net_value_scale), worlds, salt, threshold,
-                             contracts, net_depth, net_value_scale, bool(pass_value), bool(net_list))
+                             contracts, net_depth, net_value_scale, bool(pass_value), bool(net_list), net_halving)
     front = _front(inspect is not None, bid=bid)
     return duplicate_advantage(_passes(n_games, episodes, front, _front_cards(cards), inspect, device=device, seed=seed, mix=K.MIX_BOT))
 

@@ -31,14 +31,21 @@ def exchange_targets(feature_words, sums, cands, playouts, reward_scale):
       value [N, 6] float32     mean over d of sums[i * D + d][declarer] / playouts * reward_scale
       score [N, 6, 54] float32 per card c: the mean of the scaled sums of the row's candidates that laid c down, minus value
       known [N, 6, 54] bool    live, and at least one of the row's D candidates laid c down
-    Entries outside live / known are zero."""
+    Entries outside live / known are zero.
+    playouts: a number, or a halving launch's counts [N, 6 * D] — each candidate's sum is then divided by its own count, and
+    a row with a candidate that was never played (count 0) is not live."""
     n = feature_words.shape[0]
     sets = sums.shape[1] // GROUPS
     w0 = feature_words[:, :GROUPS, 0]
     live = w0 != 0
     declarer = ((w0[:, 0] >> 55) & 1) + 2 * ((w0[:, 0] >> 56) & 1) + 3 * ((w0[:, 0] >> 57) & 1)        # one-hot bits 54..57
     own = sums.to(torch.float32).gather(2, declarer.view(n, 1, 1).expand(n, GROUPS * sets, 1)).view(n, GROUPS, sets)
-    scaled = own * (float(reward_scale) / float(playouts))
+    if torch.is_tensor(playouts):
+        count = playouts.view(n, GROUPS, sets)
+        scaled = own * float(reward_scale) / count.clamp(min=1).to(torch.float32)
+        live = live & (count > 0).all(dim=2)
+    else:
+        scaled = own * (float(reward_scale) / float(playouts))
     value = scaled.mean(dim=2) * live
     c = cands.view(n, GROUPS, sets, 3).long()
     laid = torch.zeros((n, GROUPS, sets, 55), dtype=torch.float32, device=sums.device)
@@ -67,17 +74,22 @@ class ExchangeLearner:
 
     env: a TarokVecEnv, which collect() RESETS with the exchange deferred (give the learner an env of its own), or None
     for a learner on the CPU that is fed batches by hand (loss / step).  worlds, samples, discard_sets: the teacher's
-    launch (playout_exchange).  net: six tensors (policy_mlp's weights, read live at every collect()) — the teacher is then
+    launch (playout_exchange).  worlds=None: 8, or with net_halving= the schedule's sum.  net: six tensors (policy_mlp's weights, read live at every collect()) — the teacher is then
     playout_exchange_net at (worlds, discard_sets) with the network's greedy card on the seats of net_seats inside the
     playouts, playouts = worlds; `samples` must be 1 or left unset.  net_depth: None, or 1..13 — the teacher is
     playout_exchange_net_value, whose playouts stop at the declarer's net_depth-th decision and read the value head of `net`
     there at net_value_scale points per unit (13 never stops).  net_list=True (with net=): the one teacher launch is
-    playout_exchange_net_list, the same numbers from a compacted item list; nothing else changes."""
+    playout_exchange_net_list, the same numbers from a compacted item list; nothing else changes.
+    net_halving: a tuple of 1..4 positive world counts (with net=): the teacher is playout_exchange_net_halving, which spends
+    later rounds' worlds on the leading candidates only; it names the worlds itself (`worlds` None or their sum), goes with
+    net_depth, and collect() then returns the counts [N, 6 * D] in the place of the scalar playouts."""
 
-    def __init__(self, env, worlds=8, samples=None, discard_sets=4, lr=1e-3, reward_scale=1.0 / 70.0, seed=0, net=None, net_seats=15,
-                 net_list=False, net_depth=None, net_value_scale=70.0):
+    def __init__(self, env, worlds=None, samples=None, discard_sets=4, lr=1e-3, reward_scale=1.0 / 70.0, seed=0, net=None, net_seats=15,
+                 net_halving=None, net_list=False, net_depth=None, net_value_scale=70.0):
         if not reward_scale > 0:
             raise ValueError("reward_scale > 0")
+        self.net_halving = P.check_front_halving(net_halving, net, net_list, worlds, samples)
+        worlds = (8 if worlds is None else worlds) if self.net_halving is None else sum(self.net_halving)
         if net_list and net is None:
             raise ValueError("net_list packs the network's playouts: it needs net=")
         if net_depth is not None:
@@ -137,7 +149,11 @@ class ExchangeLearner:
         reset with the exchange deferred, the teacher's launch on every declarer, its candidates' discards and the head's
         launch for its input rows.  The games are left waiting for the exchange."""
         self.env.reset(episode=episode, defer_exchange=True)
-        if self.net_list or self.net_weights is not None:
+        counts = None
+        if self.net_halving is not None:
+            sums, counts, _, _ = P.front_halving_launch(self.env, False)(self.net_weights, self.net_halving, self.discard_sets, self.net_depth,
+                                                                        self.net_value_scale, net_seats=self.net_seats, salt=self.salt)
+        elif self.net_list or self.net_weights is not None:
             launch = P.exchange_net_launch(self.env, self.net_list, True)
             sums, _, _ = launch(self.net_weights, self.worlds, self.discard_sets, self.net_depth, self.net_value_scale,
                                 net_seats=self.net_seats, salt=self.salt)
@@ -145,7 +161,7 @@ class ExchangeLearner:
             sums, _, _ = self.env.playout_exchange(self.worlds, self.samples, self.discard_sets, salt=self.salt)
         cands = self.env.exchange_candidates(self.discard_sets, salt=self.salt)
         _, _, _, fw = self.env.exchange_values(self.weights(), feature_words=True)
-        return fw, sums, cands, self.worlds * self.samples
+        return fw, sums, cands, self.worlds * self.samples if counts is None else counts
 
     def iterate(self):
         """collect() on a fresh episode and one step(); returns the loss before the step."""

@@ -33,6 +33,29 @@ def bids_net_launch(env, net_list, value):
     return env.playout_bids_net_list if net_list else env.playout_bids_net_value if value else env.playout_bids_net
 
 
+def front_halving_launch(env, bids):
+    """The env's sequential-halving launch over the net-played front lists: the bid launch's, else the exchange's."""
+    return env.playout_bids_net_halving if bids else env.playout_exchange_net_halving
+
+
+def check_front_halving(net_halving, net, net_list, worlds, samples, say=spelling()):
+    """net_halving= of the exchange and bid doors -> its schedule as a tuple (None stays None).  It needs {net}=, is itself a
+    list launch (no net_list=True beside it), names the worlds itself — `worlds` None or the schedule's sum — and runs one
+    playout per (arm, world): samples None or 1."""
+    if net_halving is None:
+        return None
+    schedule = check_halving(net_halving, say, "{net_halving}")
+    if net is None or net is False:
+        raise ValueError(say("{net_halving}= spends the worlds of the network's playouts: it goes with {net}="))
+    if net_list:
+        raise ValueError(say("{net_halving}= is already a list launch: leave net_list out"))
+    if worlds is not None and int(worlds) != sum(schedule):
+        raise ValueError(say("{net_halving}= names the worlds of every round: {worlds} is optional and must be their sum"))
+    if samples not in (None, 1):
+        raise ValueError(say("{net_halving}= runs one playout per (arm, world): {samples} is optional and must be 1"))
+    return schedule
+
+
 def one_world_kind(voids, hidden, say=spelling()):
     if voids and hidden:
         raise ValueError(say("{hidden}=True is not built together with {voids}=True: give one of the two"))
