@@ -4090,13 +4090,14 @@ __device__ __forceinline__ ExchangePosition exchange_position(const Game &g0, co
 // Exchange, first launch: the front half of k_playout_exchange — its team layout, worlds, candidates and keys — and, where
 // that kernel plays an item, the game after apply_exchange packed and written with the item's key (k = 0) and TK_PN_LIVE.
 // Item (g * 6 * sets + r) * worlds + w; a row at or beyond ncand, or a game that takes no part, gets result 0 and
-// nothing else.
-TK_KERNEL(TK_BLOCK, 128) void k_playout_exchange_net_deal(int64_t n, int64_t items, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds,
-                                                         u32 sets, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,
-                                                         const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
-                                                         const Counters *__restrict__ cnt, ulonglong2 *__restrict__ i01,
-                                                         ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
-    TK_VGPR_TOP(128, 127);
+// nothing else.  VIEWER (tarok_playout_exchange_net_value's first launch): a live item's marker also carries
+// the declarer, the seat the candidates are valued for, as playout_net_deal_body<Dealer, true> writes the mover.
+template <bool VIEWER>
+__device__ __forceinline__ void playout_exchange_net_deal_body(int64_t n, int64_t items, u64 pseed, u64 offset, u32 worlds, u32 sets, u32 lg,
+                                                               u32 seats, const uint8_t *__restrict__ seat_sets,
+                                                               const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
+                                                               const Counters *__restrict__ cnt, ulonglong2 *__restrict__ i01,
+                                                               ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
     __shared__ WorldAB world;
     __shared__ u32 cand_dpk[(TK_BLOCK >> TK_PX_MIN_LG) * TK_PX_ROWS];
     const PlayoutTeam t(lg, worlds);
@@ -4144,73 +4145,25 @@ TK_KERNEL(TK_BLOCK, 128) void k_playout_exchange_net_deal(int64_t n, int64_t ite
             i01[it] = make_ulonglong2(x0, x1);
             i23[it] = make_ulonglong2(y0, y1);
             ikey[it] = game_key(pseed, offset + (u64)g, (3ULL << 62) | ebase | (63ULL << 22) | ((u64)(8u * i + d) << 16) | ((u64)w << 10));
-            res = TK_PN_LIVE;
+            res = VIEWER ? TK_PN_LIVE | (u64)p.declarer : TK_PN_LIVE;
         }
         ires[it] = res;
     }
 }
 
-// tarok_playout_exchange_net_value's first launch: the kernel above with the VIEWER — the declarer, the seat the
-// candidates are valued for — in a live item's marker, as playout_net_deal_body<Dealer, true> writes the mover.  Text of its
-// own: as one templated body the kernel above compiled to other instructions than its parent's (seven operand orders).
-TK_KERNEL(TK_BLOCK, 128) void k_playout_exchange_net_deal_value(int64_t n, int64_t items, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds,
-                                                               u32 sets, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,
-                                                               const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
-                                                               const Counters *__restrict__ cnt, ulonglong2 *__restrict__ i01,
-                                                               ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
-    TK_VGPR_TOP(128, 127);
-    __shared__ WorldAB world;
-    __shared__ u32 cand_dpk[(TK_BLOCK >> TK_PX_MIN_LG) * TK_PX_ROWS];
-    const PlayoutTeam t(lg, worlds);
-    const u32 L = t.L, lane = t.lane;
-    const int64_t g = t.g;
-    u32 *cand = cand_dpk + t.team * TK_PX_ROWS;
-    ulonglong2 a = {0, 0}, b = {0, 0};
-    u64 ebase = 0;
-    ExchangePosition p;
-    if (g < n) {
-        a = s01[g]; b = s23[g];
-        Game g0;
-        unpack(g0, a.x, a.y, b.x, b.y);
-        p = exchange_position(g0, seat_sets, seats, sets, g);
-        if (p.takes_part) {
-            ebase = (u64)cnt[g].episode << 28;
-            for (u32 w = lane; w < worlds; w += L) {
-                Game d = g0;
-                redeal_unseen(d, p.declarer, game_key(pseed, offset + (u64)g, (7ULL << 61) | ebase | (63ULL << 22) | (u64)w));
-                world.store(t.slot0 + w, d);
-            }
-            for (u32 r = lane; r < p.ncand; r += L) {
-                u32 i = r / sets, d = r - i * sets;
-                cand[r] = exchange_discards(g0, i, game_key(pseed, offset + (u64)g, (5ULL << 61) | ebase | ((u64)i << 6) | (u64)d));
-            }
-        }
+#define TK_EXCHANGE_NET_DEAL(NAME, VIEWER)                                                                                            \
+    TK_KERNEL(TK_BLOCK, 128) void NAME(int64_t n, int64_t items, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 sets,       \
+                                      u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,   \
+                                      const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,                           \
+                                      ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,             \
+                                      u64 *__restrict__ ires) {                                                                       \
+        TK_VGPR_TOP(128, 127);                                                                                                        \
+        playout_exchange_net_deal_body<VIEWER>(n, items, pseed, offset, worlds, sets, lg, seats, seat_sets, s01, s23, cnt, i01, i23,  \
+                                               ikey, ires);                                                                           \
     }
-    __syncthreads();
-    if (g >= n) return;
-    const u32 slots = 6u * sets * worlds;
-    for (u32 s = lane; s < slots; s += L) {
-        const int64_t it = g * (int64_t)slots + s;
-        if (it >= items) break;
-        const u32 r = s / worlds, w = s - r * worlds;
-        u64 res = 0;
-        if (r < p.ncand) {                               // (ncand = 0 for a game that does not take part)
-            const u32 i = r / sets, d = r - i * sets;
-            Game h;
-            unpack(h, a.x, a.y, b.x, b.y);
-            world.load(t.slot0 + w, h);
-            const u32 dpk = cand[r];
-            apply_exchange(h, i, dpk & 255, (dpk >> 8) & 255, (dpk >> 16) & 255);
-            u64 x0, x1, y0, y1;
-            pack(h, x0, x1, y0, y1);
-            i01[it] = make_ulonglong2(x0, x1);
-            i23[it] = make_ulonglong2(y0, y1);
-            ikey[it] = game_key(pseed, offset + (u64)g, (3ULL << 62) | ebase | (63ULL << 22) | ((u64)(8u * i + d) << 16) | ((u64)w << 10));
-            res = TK_PN_LIVE | (u64)p.declarer;
-        }
-        ires[it] = res;
-    }
-}
+TK_EXCHANGE_NET_DEAL(k_playout_exchange_net_deal, false)
+TK_EXCHANGE_NET_DEAL(k_playout_exchange_net_deal_value, true)
+#undef TK_EXCHANGE_NET_DEAL
 
 // Exchange, third launch: 16 lanes per game; lane r, r + 16, r + 32 sum their rows' items over the worlds in integers,
 // then the tail of k_playout_exchange: 6 * sets 16-byte rows, and on lane 0 the choice — the first candidate at the
@@ -4432,7 +4385,9 @@ TK_KERNEL(TK_BLOCK, 64) void k_playout_bids_net_sum(int64_t rows /* n * 4 * TARO
 // rows (exchange_list_on / bid_list_on, tarok_device.h) and, from k_playout_net_list_totals / _scan / _base run over the
 // units, a first slot base[u]; the item of the q-th set bit in world w is net_list_slot(base[u], q, worlds, w).  The deal
 // kernels are the dense kernels' teams, worlds, candidates, barriers and keys looping over live rows only; every slot they
-// write is tested against the host's bound, and every slot below the list's total is written.
+// write is tested against the host's bound, and every slot below the list's total is written.  As k_playout_net_list_deal*
+// they take the first world e0 and the count round_worlds, and serve §8.23's rounds too: this launch is e0 = 0 over all its
+// worlds (launch_exchange_list_deal / launch_bids_list_deal pick the kernel for both).
 
 // Exchange, first launch: one thread a unit.
 TK_KERNEL(TK_BLOCK, 64) void k_playout_exchange_net_list_init(int64_t units, u32 sets, u32 seats, const uint8_t *__restrict__ seat_sets,
@@ -4448,35 +4403,44 @@ TK_KERNEL(TK_BLOCK, 64) void k_playout_exchange_net_list_init(int64_t units, u32
     on[u] = exchange_list_on(g0.contract, (u32)(u - g * 6), sets, p.takes_part);
 }
 
-// Exchange, the items: k_playout_exchange_net_deal (VIEWER: _deal_value) over the game's ncand * worlds live slots.  Row
-// r = i * sets + d is the d-th set bit of unit g * 6 + i, whose word is the low `sets` bits or 0.
+// Exchange, the items, for the list launch and for every halving round (§8.23): playout_exchange_net_deal_body's team, barrier,
+// keys and candidates (VIEWER: its marker) over live rows only.  The team deals the worlds e0 + lw, lw < round_worlds, into its
+// world slots 0 .. round_worlds - 1, and row r = i * sets + d of a unit whose bit d is on goes to the slot of the bit's rank in
+// the word.  A game's items are popc(its on words) * round_worlds, so every slot written lies below the launch's total and
+// below the host's bound (tested all the same).  The list launch is e0 = 0, round_worlds = worlds, on the init kernel's words:
+//  - a game plays if any of its six on words is non-zero; exchange_list_on makes that exchange_position's takes_part, since a
+//    game that takes part has ncand > 0 and so group 0 on;
+//  - a list word is the low `sets` bits or 0, so the rank of its bit d is d.
 template <bool VIEWER>
-__device__ __forceinline__ void playout_exchange_net_list_deal_body(int64_t n, u32 bound, u64 pseed, u64 offset, u32 worlds, u32 sets, u32 lg,
-                                                                    u32 seats, const uint8_t *__restrict__ seat_sets,
+__device__ __forceinline__ void playout_exchange_net_list_deal_body(int64_t n, u32 bound, u64 pseed, u64 offset, u32 e0, u32 round_worlds,
+                                                                    u32 sets, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,
                                                                     const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
                                                                     const Counters *__restrict__ cnt, const u32 *__restrict__ on,
                                                                     const u32 *__restrict__ base, ulonglong2 *__restrict__ i01,
-                                                                    ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
+                                                                    ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,
+                                                                    u64 *__restrict__ ires) {
     __shared__ WorldAB world;
     __shared__ u32 cand_dpk[(TK_BLOCK >> TK_PX_MIN_LG) * TK_PX_ROWS];
-    const PlayoutTeam t(lg, worlds);
+    const PlayoutTeam t(lg, round_worlds);
     const u32 L = t.L, lane = t.lane;
     const int64_t g = t.g;
     u32 *cand = cand_dpk + t.team * TK_PX_ROWS;
     ulonglong2 a = {0, 0}, b = {0, 0};
     u64 ebase = 0;
     ExchangePosition p;
+    bool plays = false;
     if (g < n) {
-        a = s01[g]; b = s23[g];
-        Game g0;
-        unpack(g0, a.x, a.y, b.x, b.y);
-        p = exchange_position(g0, seat_sets, seats, sets, g);
-        if (p.takes_part) {
+        for (u32 i = 0; i < 6; i++) plays = plays || on[g * 6 + i] != 0u;      // (on: only games that take part)
+        if (plays) {
+            a = s01[g]; b = s23[g];
+            Game g0;
+            unpack(g0, a.x, a.y, b.x, b.y);
+            p = exchange_position(g0, seat_sets, seats, sets, g);
             ebase = (u64)cnt[g].episode << 28;
-            for (u32 w = lane; w < worlds; w += L) {
+            for (u32 lw = lane; lw < round_worlds; lw += L) {
                 Game d = g0;
-                redeal_unseen(d, p.declarer, game_key(pseed, offset + (u64)g, (7ULL << 61) | ebase | (63ULL << 22) | (u64)w));
-                world.store(t.slot0 + w, d);
+                redeal_unseen(d, p.declarer, game_key(pseed, offset + (u64)g, (7ULL << 61) | ebase | (63ULL << 22) | (u64)(e0 + lw)));
+                world.store(t.slot0 + lw, d);
             }
             for (u32 r = lane; r < p.ncand; r += L) {
                 u32 i = r / sets, d = r - i * sets;
@@ -4485,37 +4449,39 @@ __device__ __forceinline__ void playout_exchange_net_list_deal_body(int64_t n, u
         }
     }
     __syncthreads();
-    if (g >= n) return;
-    const u32 live = p.ncand * worlds;                   // (ncand = 0 for a game that does not take part)
+    if (!plays) return;
+    const u32 live = p.ncand * round_worlds;
     for (u32 s = lane; s < live; s += L) {
-        const u32 r = s / worlds, w = s - r * worlds, i = r / sets, d = r - i * sets;
+        const u32 r = s / round_worlds, lw = s - r * round_worlds, i = r / sets, d = r - i * sets;
         const int64_t u = g * 6 + (int64_t)i;
-        if (!((on[u] >> d) & 1u)) continue;              // (never: the unit's word is the init kernel's, by the same statement)
-        const u32 it = net_list_slot(base[u], d, worlds, w);
+        const u32 o = on[u];
+        if (!((o >> d) & 1u)) continue;
+        const u32 it = net_list_slot(base[u], (u32)__popc(o & ((1u << d) - 1u)), round_worlds, lw);
         if (it >= bound) continue;
         Game h;
         unpack(h, a.x, a.y, b.x, b.y);
-        world.load(t.slot0 + w, h);
+        world.load(t.slot0 + lw, h);
         const u32 dpk = cand[r];
         apply_exchange(h, i, dpk & 255, (dpk >> 8) & 255, (dpk >> 16) & 255);
         u64 x0, x1, y0, y1;
         pack(h, x0, x1, y0, y1);
         i01[it] = make_ulonglong2(x0, x1);
         i23[it] = make_ulonglong2(y0, y1);
-        ikey[it] = game_key(pseed, offset + (u64)g, (3ULL << 62) | ebase | (63ULL << 22) | ((u64)(8u * i + d) << 16) | ((u64)w << 10));
+        ikey[it] = game_key(pseed, offset + (u64)g, (3ULL << 62) | ebase | (63ULL << 22) | ((u64)(8u * i + d) << 16) | ((u64)(e0 + lw) << 10));
         ires[it] = VIEWER ? TK_PN_LIVE | (u64)p.declarer : TK_PN_LIVE;
     }
 }
 
-#define TK_EXCHANGE_NET_LIST_DEAL(NAME, VIEWER)                                                                                      \
-    TK_KERNEL(TK_BLOCK, 128) void NAME(int64_t n, u32 bound, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 sets, u32 lg,    \
-                                      u32 seats, const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,           \
-                                      const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,                           \
-                                      const u32 *__restrict__ on, const u32 *__restrict__ base, ulonglong2 *__restrict__ i01,         \
-                                      ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {                 \
+#define TK_EXCHANGE_NET_LIST_DEAL(NAME, VIEWER)                                                                                       \
+    TK_KERNEL(TK_BLOCK, 128) void NAME(int64_t n, u32 bound, u64 pseed /* seed ^ salt */, u64 offset, u32 e0, u32 round_worlds,       \
+                                      u32 sets, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,                             \
+                                      const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,                         \
+                                      const Counters *__restrict__ cnt, const u32 *__restrict__ on, const u32 *__restrict__ base,     \
+                                      ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,             \
+                                      u64 *__restrict__ ires) {                                                                       \
         TK_VGPR_TOP(128, 127);                                                                                                        \
-        playout_exchange_net_list_deal_body<VIEWER>(n, bound, pseed, offset, worlds, sets, lg, seats, seat_sets, s01, s23, cnt, on,   \
-                                                    base, i01, i23, ikey, ires);                                                      \
+        playout_exchange_net_list_deal_body<VIEWER>(n, bound, pseed, offset, e0, round_worlds, sets, lg, seats, seat_sets, s01,       \
+                                                    s23, cnt, on, base, i01, i23, ikey, ires);                                        \
     }
 TK_EXCHANGE_NET_LIST_DEAL(k_playout_exchange_net_list_deal, false)
 TK_EXCHANGE_NET_LIST_DEAL(k_playout_exchange_net_list_deal_value, true)
@@ -4588,54 +4554,54 @@ TK_KERNEL(TK_BLOCK, 64) void k_playout_bids_net_list_init(int64_t n, u32 contrac
     on[u] = bid_list_on(contracts, pass_value, (set >> ((u32)u & 3u)) & 1u);
 }
 
-// Bids, the items: k_playout_bids_net_deal (VIEWER: _deal_value, PASS: _deal_value_pass) over the unit's live rows; the two
-// barriers per viewer stand outside every test of the seat set.
+// Bids, the items, for the list launch and for every halving round (§8.23): k_playout_bids_net_deal's team, keys and item setup
+// (VIEWER: _deal_value's marker, PASS: _deal_value_pass's pass item) over the unit's live rows, in the worlds e0 + lw, lw <
+// round_worlds, dealt into the team's world slots 0 .. round_worlds - 1; the two barriers per viewer stand outside every test
+// of the unit's word.  The list launch is e0 = 0, round_worlds = worlds, on the init kernel's words: a viewer takes part — its
+// seat bit with a valid deal row — exactly where its on word is non-zero, since bid_list_on is `part ? rows : 0` and rows is
+// never 0 for contracts >= 1.
 template <bool VIEWER, bool PASS>
-__device__ __forceinline__ void playout_bids_net_list_deal_body(int64_t n, u32 bound, u64 pseed, u64 offset, u32 episode, u32 worlds, u32 lg,
-                                                                u32 seats, const uint8_t *__restrict__ seat_sets,
+__device__ __forceinline__ void playout_bids_net_list_deal_body(int64_t n, u32 bound, u64 pseed, u64 offset, u32 episode, u32 e0,
+                                                                u32 round_worlds, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,
                                                                 const u64 *__restrict__ deal, const u32 *__restrict__ on,
                                                                 const u32 *__restrict__ base, ulonglong2 *__restrict__ i01,
-                                                                ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
+                                                                ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,
+                                                                u64 *__restrict__ ires) {
     static_assert(VIEWER || !PASS, "the pass item carries its viewer");
     __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS], world_ids[TK_PO_WORLD_SLOTS];
-    const PlayoutTeam t(lg, worlds);
+    const PlayoutTeam t(lg, round_worlds);
     const u32 L = t.L, lane = t.lane, slot0 = t.slot0;
     const int64_t g = t.g;
     u64 h0 = 0, h1 = 0, h2 = 0, h3 = 0, tal = 0;
-    u32 set = 0;
-    if (g < n) {
-        h0 = deal[g]; h1 = deal[n + g]; h2 = deal[2 * n + g]; h3 = deal[3 * n + g]; tal = deal[4 * n + g];
-        set = seat_sets ? (u32)seat_sets[g] & 15u : seats;
-        if ((h0 | h1 | h2 | h3) == 0) set = 0;           // an invalid deal row
-    }
+    if (g < n) { h0 = deal[g]; h1 = deal[n + g]; h2 = deal[2 * n + g]; h3 = deal[3 * n + g]; tal = deal[4 * n + g]; }
     const u64 ebase = (u64)episode << 28;
 #pragma unroll 1
     for (u32 v = 0; v < 4; v++) {
-        const bool part = (set >> v) & 1u;
+        const u32 o = g < n ? on[g * 4 + v] : 0u;        // (on: only viewers of the seat set with a valid deal row)
         __syncthreads();                                 // the last viewer's items have read their worlds
-        if (part) {
-            for (u32 w = lane; w < worlds; w += L) {
+        if (o) {
+            for (u32 lw = lane; lw < round_worlds; lw += L) {
                 u64 A, B, ids;
-                bid_world(h0, h1, h2, h3, tal, v, game_key(pseed, offset + (u64)g, (2ULL << 61) | ebase | ((u64)v << 6) | (u64)w), A, B, ids);
-                world_a[slot0 + w] = A; world_b[slot0 + w] = B; world_ids[slot0 + w] = ids;
+                bid_world(h0, h1, h2, h3, tal, v, game_key(pseed, offset + (u64)g, (2ULL << 61) | ebase | ((u64)v << 6) | (u64)(e0 + lw)), A, B, ids);
+                world_a[slot0 + lw] = A; world_b[slot0 + lw] = B; world_ids[slot0 + lw] = ids;
             }
         }
         __syncthreads();
-        if (part) {                                      // (part: g < n)
-            const u32 o = on[g * 4 + v], first = base[g * 4 + v];       // (bit 19 only under the PASS form: the launcher pairs them)
-            const u32 count = net_list_count(o, worlds);
+        if (o) {
+            const u32 first = base[g * 4 + v];           // (bit 19 only under the PASS form: the launcher pairs them)
+            const u32 count = net_list_count(o, round_worlds);
             for (u32 s = lane; s < count; s += L) {
-                const u32 q = s / worlds, w = s - q * worlds, r = kth_bit_word(o, 0u, q);
-                const u32 it = net_list_slot(first, q, worlds, w);
+                const u32 q = s / round_worlds, lw = s - q * round_worlds, w = e0 + lw, r = kth_bit_word(o, 0u, q);
+                const u32 it = net_list_slot(first, q, round_worlds, lw);
                 if (it >= bound) continue;
                 const u64 pkey = game_key(pseed, offset + (u64)g, (3ULL << 61) | ebase | ((u64)v << 26) | ((u64)r << 21) | ((u64)w << 15));
                 Game h;
                 if constexpr (PASS) {                    // (k_playout_bids_pass's one setup for both kinds of item)
                     u32 ct = bid_row_contract(r), d = ct == TK_KLOP ? 0u : v, kg = bid_row_king(r);
                     if (r == (u32)TK_BID_PASS_ROW) pass_round(pkey, v, ct, d, kg);
-                    bid_game_as(h, world_a[slot0 + w], world_b[slot0 + w], world_ids[slot0 + w], ct, d, kg);
+                    bid_game_as(h, world_a[slot0 + lw], world_b[slot0 + lw], world_ids[slot0 + lw], ct, d, kg);
                 } else {
-                    bid_game(h, world_a[slot0 + w], world_b[slot0 + w], world_ids[slot0 + w], r, v);
+                    bid_game(h, world_a[slot0 + lw], world_b[slot0 + lw], world_ids[slot0 + lw], r, v);
                 }
                 if (h.phase == TK_PHASE_EXCHANGE) bot_exchange(h, pkey);
                 u64 x0, x1, y0, y1;
@@ -4649,14 +4615,15 @@ __device__ __forceinline__ void playout_bids_net_list_deal_body(int64_t n, u32 b
     }
 }
 
-#define TK_BIDS_NET_LIST_DEAL(NAME, VIEWER, PASS)                                                                                    \
-    TK_KERNEL(TK_BLOCK, 128) void NAME(int64_t n, u32 bound, u64 pseed /* seed ^ salt */, u64 offset, u32 episode, u32 worlds, u32 lg, \
-                                      u32 seats, const uint8_t *__restrict__ seat_sets, const u64 *__restrict__ deal,                 \
-                                      const u32 *__restrict__ on, const u32 *__restrict__ base, ulonglong2 *__restrict__ i01,         \
-                                      ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {                 \
+#define TK_BIDS_NET_LIST_DEAL(NAME, VIEWER, PASS)                                                                                     \
+    TK_KERNEL(TK_BLOCK, 128) void NAME(int64_t n, u32 bound, u64 pseed /* seed ^ salt */, u64 offset, u32 episode, u32 e0,            \
+                                      u32 round_worlds, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,                     \
+                                      const u64 *__restrict__ deal, const u32 *__restrict__ on, const u32 *__restrict__ base,         \
+                                      ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,             \
+                                      u64 *__restrict__ ires) {                                                                       \
         TK_VGPR_TOP(128, 127);                                                                                                        \
-        playout_bids_net_list_deal_body<VIEWER, PASS>(n, bound, pseed, offset, episode, worlds, lg, seats, seat_sets, deal,            \
-                                                      on, base, i01, i23, ikey, ires);                                                \
+        playout_bids_net_list_deal_body<VIEWER, PASS>(n, bound, pseed, offset, episode, e0, round_worlds, lg, seats, seat_sets,       \
+                                                      deal, on, base, i01, i23, ikey, ires);                                          \
     }
 TK_BIDS_NET_LIST_DEAL(k_playout_bids_net_list_deal, false, false)
 TK_BIDS_NET_LIST_DEAL(k_playout_bids_net_list_deal_value, true, false)
@@ -4690,6 +4657,7 @@ TK_KERNEL(TK_BLOCK, 64) void k_playout_bids_net_list_sum(int64_t rows /* n * 4 *
 // while the game or unit plays rounds, else 0), and every row a running sum and a count in the scratch.  A round is
 // tarok_playout_cards_net_halving's: the scan over the on words, the round's items in its worlds e0 .. e1 - 1 alone, under
 // their true indices, the playouts on the round's total, the sums and the survivor rule (front_halving_stays, one arm a lane).
+// The round's items are §8.22's deal kernels at the round's e0, round_worlds and bound; this section adds the init and the sums.
 
 // Exchange, first launch: one thread a unit: the on and alive words, the unit's running sums and counts zeroed.
 TK_KERNEL(TK_BLOCK, 64) void k_playout_exchange_net_halving_init(int64_t units, u32 sets, u32 seats, const uint8_t *__restrict__ seat_sets,
@@ -4711,86 +4679,6 @@ TK_KERNEL(TK_BLOCK, 64) void k_playout_exchange_net_halving_init(int64_t units, 
         rcnt[u * sets + d] = 0;
     }
 }
-
-// Exchange, a round's items: playout_exchange_net_list_deal_body's team, barrier, keys and candidates; the team deals the
-// round's worlds e0 + lw, lw < round_worlds, into its world slots 0 .. round_worlds - 1, and row r = i * sets + d of a unit
-// whose bit d is on goes to the slot of the bit's rank in the word.  A game's items are popc(its on words) * round_worlds <=
-// a_r * round_worlds, so every slot written lies below the round's total and below the host's bound (tested all the same).
-template <bool VIEWER>
-__device__ __forceinline__ void playout_exchange_net_halving_deal_body(int64_t n, u32 bound, u64 pseed, u64 offset, u32 e0, u32 round_worlds,
-                                                                       u32 sets, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,
-                                                                       const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,
-                                                                       const Counters *__restrict__ cnt, const u32 *__restrict__ on,
-                                                                       const u32 *__restrict__ base, ulonglong2 *__restrict__ i01,
-                                                                       ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,
-                                                                       u64 *__restrict__ ires) {
-    __shared__ WorldAB world;
-    __shared__ u32 cand_dpk[(TK_BLOCK >> TK_PX_MIN_LG) * TK_PX_ROWS];
-    const PlayoutTeam t(lg, round_worlds);
-    const u32 L = t.L, lane = t.lane;
-    const int64_t g = t.g;
-    u32 *cand = cand_dpk + t.team * TK_PX_ROWS;
-    ulonglong2 a = {0, 0}, b = {0, 0};
-    u64 ebase = 0;
-    ExchangePosition p;
-    bool plays = false;
-    if (g < n) {
-        for (u32 i = 0; i < 6; i++) plays = plays || on[g * 6 + i] != 0u;      // (on: only games that take part)
-        if (plays) {
-            a = s01[g]; b = s23[g];
-            Game g0;
-            unpack(g0, a.x, a.y, b.x, b.y);
-            p = exchange_position(g0, seat_sets, seats, sets, g);
-            ebase = (u64)cnt[g].episode << 28;
-            for (u32 lw = lane; lw < round_worlds; lw += L) {
-                Game d = g0;
-                redeal_unseen(d, p.declarer, game_key(pseed, offset + (u64)g, (7ULL << 61) | ebase | (63ULL << 22) | (u64)(e0 + lw)));
-                world.store(t.slot0 + lw, d);
-            }
-            for (u32 r = lane; r < p.ncand; r += L) {
-                u32 i = r / sets, d = r - i * sets;
-                cand[r] = exchange_discards(g0, i, game_key(pseed, offset + (u64)g, (5ULL << 61) | ebase | ((u64)i << 6) | (u64)d));
-            }
-        }
-    }
-    __syncthreads();
-    if (!plays) return;
-    const u32 live = p.ncand * round_worlds;
-    for (u32 s = lane; s < live; s += L) {
-        const u32 r = s / round_worlds, lw = s - r * round_worlds, i = r / sets, d = r - i * sets;
-        const int64_t u = g * 6 + (int64_t)i;
-        const u32 o = on[u];
-        if (!((o >> d) & 1u)) continue;
-        const u32 it = net_list_slot(base[u], (u32)__popc(o & ((1u << d) - 1u)), round_worlds, lw);
-        if (it >= bound) continue;
-        Game h;
-        unpack(h, a.x, a.y, b.x, b.y);
-        world.load(t.slot0 + lw, h);
-        const u32 dpk = cand[r];
-        apply_exchange(h, i, dpk & 255, (dpk >> 8) & 255, (dpk >> 16) & 255);
-        u64 x0, x1, y0, y1;
-        pack(h, x0, x1, y0, y1);
-        i01[it] = make_ulonglong2(x0, x1);
-        i23[it] = make_ulonglong2(y0, y1);
-        ikey[it] = game_key(pseed, offset + (u64)g, (3ULL << 62) | ebase | (63ULL << 22) | ((u64)(8u * i + d) << 16) | ((u64)(e0 + lw) << 10));
-        ires[it] = VIEWER ? TK_PN_LIVE | (u64)p.declarer : TK_PN_LIVE;
-    }
-}
-
-#define TK_EXCHANGE_NET_HALVING_DEAL(NAME, VIEWER)                                                                                   \
-    TK_KERNEL(TK_BLOCK, 128) void NAME(int64_t n, u32 bound, u64 pseed /* seed ^ salt */, u64 offset, u32 e0, u32 round_worlds,       \
-                                      u32 sets, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,                             \
-                                      const ulonglong2 *__restrict__ s01, const ulonglong2 *__restrict__ s23,                         \
-                                      const Counters *__restrict__ cnt, const u32 *__restrict__ on, const u32 *__restrict__ base,     \
-                                      ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,             \
-                                      u64 *__restrict__ ires) {                                                                       \
-        TK_VGPR_TOP(128, 127);                                                                                                        \
-        playout_exchange_net_halving_deal_body<VIEWER>(n, bound, pseed, offset, e0, round_worlds, sets, lg, seats, seat_sets, s01,    \
-                                                       s23, cnt, on, base, i01, i23, ikey, ires);                                     \
-    }
-TK_EXCHANGE_NET_HALVING_DEAL(k_playout_exchange_net_halving_deal, false)
-TK_EXCHANGE_NET_HALVING_DEAL(k_playout_exchange_net_halving_deal_value, true)
-#undef TK_EXCHANGE_NET_HALVING_DEAL
 
 // Exchange, a round's sums and the survivor rule: 16 lanes a game.  A lane takes the rows r = lane, lane + 16, lane + 32: a row
 // that played the round adds its round_worlds results, in integers, to its running sums and sets its count to the round's end
@@ -4905,78 +4793,6 @@ TK_KERNEL(TK_BLOCK, 64) void k_playout_bids_net_halving_init(int64_t n, u32 cont
         rcnt[u * (TAROK_BID_ROWS / 4) + q] = make_int4(0, 0, 0, 0);
     }
 }
-
-// Bids, a round's items: playout_bids_net_list_deal_body's team, barriers, keys and item setup, over the round's worlds
-// e0 + lw, lw < round_worlds, dealt into the team's world slots 0 .. round_worlds - 1.
-template <bool VIEWER, bool PASS>
-__device__ __forceinline__ void playout_bids_net_halving_deal_body(int64_t n, u32 bound, u64 pseed, u64 offset, u32 episode, u32 e0,
-                                                                   u32 round_worlds, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,
-                                                                   const u64 *__restrict__ deal, const u32 *__restrict__ on,
-                                                                   const u32 *__restrict__ base, ulonglong2 *__restrict__ i01,
-                                                                   ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,
-                                                                   u64 *__restrict__ ires) {
-    static_assert(VIEWER || !PASS, "the pass item carries its viewer");
-    __shared__ u64 world_a[TK_PO_WORLD_SLOTS], world_b[TK_PO_WORLD_SLOTS], world_ids[TK_PO_WORLD_SLOTS];
-    const PlayoutTeam t(lg, round_worlds);
-    const u32 L = t.L, lane = t.lane, slot0 = t.slot0;
-    const int64_t g = t.g;
-    u64 h0 = 0, h1 = 0, h2 = 0, h3 = 0, tal = 0;
-    if (g < n) { h0 = deal[g]; h1 = deal[n + g]; h2 = deal[2 * n + g]; h3 = deal[3 * n + g]; tal = deal[4 * n + g]; }
-    const u64 ebase = (u64)episode << 28;
-#pragma unroll 1
-    for (u32 v = 0; v < 4; v++) {
-        const u32 o = g < n ? on[g * 4 + v] : 0u;        // (on: only viewers of the seat set with a valid deal row)
-        __syncthreads();                                 // the last viewer's items have read their worlds
-        if (o) {
-            for (u32 lw = lane; lw < round_worlds; lw += L) {
-                u64 A, B, ids;
-                bid_world(h0, h1, h2, h3, tal, v, game_key(pseed, offset + (u64)g, (2ULL << 61) | ebase | ((u64)v << 6) | (u64)(e0 + lw)), A, B, ids);
-                world_a[slot0 + lw] = A; world_b[slot0 + lw] = B; world_ids[slot0 + lw] = ids;
-            }
-        }
-        __syncthreads();
-        if (o) {
-            const u32 first = base[g * 4 + v];           // (bit 19 only under the PASS form: the launcher pairs them)
-            const u32 count = net_list_count(o, round_worlds);
-            for (u32 s = lane; s < count; s += L) {
-                const u32 q = s / round_worlds, lw = s - q * round_worlds, w = e0 + lw, r = kth_bit_word(o, 0u, q);
-                const u32 it = net_list_slot(first, q, round_worlds, lw);
-                if (it >= bound) continue;
-                const u64 pkey = game_key(pseed, offset + (u64)g, (3ULL << 61) | ebase | ((u64)v << 26) | ((u64)r << 21) | ((u64)w << 15));
-                Game h;
-                if constexpr (PASS) {                    // (k_playout_bids_pass's one setup for both kinds of item)
-                    u32 ct = bid_row_contract(r), d = ct == TK_KLOP ? 0u : v, kg = bid_row_king(r);
-                    if (r == (u32)TK_BID_PASS_ROW) pass_round(pkey, v, ct, d, kg);
-                    bid_game_as(h, world_a[slot0 + lw], world_b[slot0 + lw], world_ids[slot0 + lw], ct, d, kg);
-                } else {
-                    bid_game(h, world_a[slot0 + lw], world_b[slot0 + lw], world_ids[slot0 + lw], r, v);
-                }
-                if (h.phase == TK_PHASE_EXCHANGE) bot_exchange(h, pkey);
-                u64 x0, x1, y0, y1;
-                pack(h, x0, x1, y0, y1);
-                i01[it] = make_ulonglong2(x0, x1);
-                i23[it] = make_ulonglong2(y0, y1);
-                ikey[it] = pkey;
-                ires[it] = VIEWER ? TK_PN_LIVE | (u64)v : TK_PN_LIVE;
-            }
-        }
-    }
-}
-
-#define TK_BIDS_NET_HALVING_DEAL(NAME, VIEWER, PASS)                                                                                 \
-    TK_KERNEL(TK_BLOCK, 128) void NAME(int64_t n, u32 bound, u64 pseed /* seed ^ salt */, u64 offset, u32 episode, u32 e0,            \
-                                      u32 round_worlds, u32 lg, u32 seats, const uint8_t *__restrict__ seat_sets,                     \
-                                      const u64 *__restrict__ deal, const u32 *__restrict__ on, const u32 *__restrict__ base,         \
-                                      ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,             \
-                                      u64 *__restrict__ ires) {                                                                       \
-        TK_VGPR_TOP(128, 127);                                                                                                        \
-        playout_bids_net_halving_deal_body<VIEWER, PASS>(n, bound, pseed, offset, episode, e0, round_worlds, lg, seats, seat_sets,    \
-                                                         deal, on, base, i01, i23, ikey, ires);                                       \
-    }
-TK_BIDS_NET_HALVING_DEAL(k_playout_bids_net_halving_deal, false, false)
-TK_BIDS_NET_HALVING_DEAL(k_playout_bids_net_halving_deal_value, true, false)
-TK_BIDS_NET_HALVING_DEAL(k_playout_bids_net_halving_deal_value_pass, true, true)
-#undef TK_BIDS_NET_HALVING_DEAL
 
 // Bids, a round's sums and the survivor rule: 32 lanes a unit, lane r < 20 its row r.  A row that played the round adds the
 // VIEWER's 16 bits of its round_worlds results to its running sum and sets its count to e1; the sums go to the team's [20]
@@ -5863,6 +5679,24 @@ static inline void launch_list_scan(const ListScratch &p, const ListArrays &a, i
     hipLaunchKernelGGL(k_playout_net_list_scan, dim3(1), dim3(TK_BLOCK), 0, s, (u32)p.blocks, a.part, a.total);
     hipLaunchKernelGGL(k_playout_net_list_base, grid_for(p.units), dim3(TK_BLOCK), 0, s, p.units, (u32)worlds, a.on, a.part, a.base);
 }
+// The front lists' items in the worlds e0 .. e0 + round_worlds - 1, the one place per family that picks among the deal kernels:
+// the list entries' single launch is e0 = 0 over all their worlds at the list's bound, a halving round its own worlds and bound.
+static inline void launch_exchange_list_deal(tarok_env *e, const ListArrays &a, int64_t bound, u64 pseed, int e0, int round_worlds,
+                                             int discard_sets, int seats, const uint8_t *seats_per_game, int depth, hipStream_t s) {
+    const u32 lg = playout_lg(TK_PX_MIN_LG, round_worlds);      // tarok_playout_exchange's teams at samples = 1
+    hipLaunchKernelGGL(depth ? k_playout_exchange_net_list_deal_value : k_playout_exchange_net_list_deal, playout_grid(e, lg), dim3(TK_BLOCK),
+                       0, s, e->n, (u32)bound, pseed, e->offset, (u32)e0, (u32)round_worlds, (u32)discard_sets, lg, (u32)seats, seats_per_game,
+                       e->s01, e->s23, e->cnt, a.on, a.base, a.i01, a.i23, a.ikey, a.ires);
+}
+static inline void launch_bids_list_deal(tarok_env *e, const ListArrays &a, int64_t bound, u64 pseed, uint32_t episode, int e0,
+                                         int round_worlds, int seats, const uint8_t *seats_per_game, const u64 *deal, int depth,
+                                         int pass_value, hipStream_t s) {
+    const u32 lg = playout_lg(TK_PB_MIN_LG, round_worlds);      // tarok_playout_bids' teams at samples = 1
+    hipLaunchKernelGGL(!depth ? k_playout_bids_net_list_deal
+                              : (pass_value ? k_playout_bids_net_list_deal_value_pass : k_playout_bids_net_list_deal_value),
+                       playout_grid(e, lg), dim3(TK_BLOCK), 0, s, e->n, (u32)bound, pseed, e->offset, episode, (u32)e0, (u32)round_worlds, lg,
+                       (u32)seats, seats_per_game, deal, a.on, a.base, a.i01, a.i23, a.ikey, a.ires);
+}
 
 // A net halving launch as the host sizes it: the schedule, and the list at the largest round's bound over the games as units.
 // Its extension of the list's layout: a game's running sums (16 bytes a rank) and counts (4) are the extra bytes, its alive
@@ -6161,10 +5995,7 @@ int tarok_playout_exchange_net_list(tarok_env *e, int worlds, int discard_sets, 
     hipLaunchKernelGGL(k_playout_exchange_net_list_init, grid_for(p.units), dim3(TK_BLOCK), 0, s, p.units, (u32)discard_sets, (u32)seats,
                        seats_per_game, e->s01, e->s23, a.on);
     launch_list_scan(p, a, worlds, s);
-    const u32 lg = playout_lg(TK_PX_MIN_LG, worlds);     // tarok_playout_exchange's teams at samples = 1
-    hipLaunchKernelGGL(depth ? k_playout_exchange_net_list_deal_value : k_playout_exchange_net_list_deal, playout_grid(e, lg), dim3(TK_BLOCK),
-                       0, s, e->n, (u32)p.bound, pseed, e->offset, (u32)worlds, (u32)discard_sets, lg, (u32)seats, seats_per_game, e->s01,
-                       e->s23, e->cnt, a.on, a.base, a.i01, a.i23, a.ikey, a.ires);
+    launch_exchange_list_deal(e, a, p.bound, pseed, 0, worlds, discard_sets, seats, seats_per_game, depth, s);
     launch_net_play(p.bound, a.total, net_seats, a, w, s, depth, value_scale);
     hipLaunchKernelGGL(k_playout_exchange_net_list_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, s, e->n, (u32)p.bound, pseed,
                        e->offset, (u32)worlds, (u32)discard_sets, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, e->gkey, a.on, a.base,
@@ -6202,11 +6033,7 @@ int tarok_playout_bids_net_list(tarok_env *e, uint32_t episode, const uint8_t *d
     hipLaunchKernelGGL(k_playout_bids_net_list_init, grid_for(p.units), dim3(TK_BLOCK), 0, s, n, (u32)contracts, (u32)pass_value, (u32)seats,
                        seats_per_game, deal, a.on);
     launch_list_scan(p, a, worlds, s);
-    const u32 lg = playout_lg(TK_PB_MIN_LG, worlds);     // tarok_playout_bids' teams at samples = 1
-    hipLaunchKernelGGL(!depth ? k_playout_bids_net_list_deal
-                              : (pass_value ? k_playout_bids_net_list_deal_value_pass : k_playout_bids_net_list_deal_value),
-                       playout_grid(e, lg), dim3(TK_BLOCK), 0, s, n, (u32)p.bound, e->seed ^ (u64)salt, e->offset, episode, (u32)worlds, lg,
-                       (u32)seats, seats_per_game, deal, a.on, a.base, a.i01, a.i23, a.ikey, a.ires);
+    launch_bids_list_deal(e, a, p.bound, e->seed ^ (u64)salt, episode, 0, worlds, seats, seats_per_game, deal, depth, pass_value, s);
     launch_net_play(p.bound, a.total, net_seats, a, w, s, depth, value_scale);
     hipLaunchKernelGGL(k_playout_bids_net_list_sum, grid_for(rows), dim3(TK_BLOCK), 0, s, rows, (u32)p.bound, (u32)worlds, a.on, a.base,
                        a.ires, sum_out);
@@ -6248,10 +6075,7 @@ int tarok_playout_exchange_net_halving(tarok_env *e, int rounds, const int *roun
         const int wr = p.h.w[r];
         const u32 bound = (u32)p.round_bound[r];
         launch_list_scan(p.list, a, wr, s);
-        const u32 lg = playout_lg(TK_PX_MIN_LG, wr);
-        hipLaunchKernelGGL(depth ? k_playout_exchange_net_halving_deal_value : k_playout_exchange_net_halving_deal, playout_grid(e, lg),
-                           dim3(TK_BLOCK), 0, s, n, bound, pseed, e->offset, (u32)(p.h.end[r] - wr), (u32)wr, (u32)discard_sets, lg,
-                           (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, a.on, a.base, a.i01, a.i23, a.ikey, a.ires);
+        launch_exchange_list_deal(e, a, p.round_bound[r], pseed, p.h.end[r] - wr, wr, discard_sets, seats, seats_per_game, depth, s);
         launch_net_play(p.round_bound[r], a.total, net_seats, a, w, s, depth, value_scale);
         hipLaunchKernelGGL(k_playout_exchange_net_halving_sum, dim3((unsigned)((n + 15) / 16)), dim3(TK_BLOCK), 0, s, n, bound, pseed,
                            e->offset, (u32)p.h.end[r], (u32)wr, (u32)(r == p.h.rounds - 1), (u32)discard_sets, (u32)seats, seats_per_game,
@@ -6294,15 +6118,12 @@ int tarok_playout_bids_net_halving(tarok_env *e, uint32_t episode, const uint8_t
     hipLaunchKernelGGL(k_bid_deal, grid_for(n), dim3(TK_BLOCK), 0, s, n, e->seed, e->offset, episode, deals, deal);
     hipLaunchKernelGGL(k_playout_bids_net_halving_init, grid_for(p.list.units), dim3(TK_BLOCK), 0, s, n, (u32)contracts, (u32)pass_value,
                        (u32)seats, seats_per_game, deal, a.on, alive, reinterpret_cast<int4 *>(rsum), reinterpret_cast<int4 *>(rcnt));
-    const auto kdeal = !depth ? k_playout_bids_net_halving_deal
-                              : (pass_value ? k_playout_bids_net_halving_deal_value_pass : k_playout_bids_net_halving_deal_value);
     for (int r = 0; r < p.h.rounds; r++) {
         const int wr = p.h.w[r];
         const u32 bound = (u32)p.round_bound[r];
         launch_list_scan(p.list, a, wr, s);
-        const u32 lg = playout_lg(TK_PB_MIN_LG, wr);
-        hipLaunchKernelGGL(kdeal, playout_grid(e, lg), dim3(TK_BLOCK), 0, s, n, bound, e->seed ^ (u64)salt, e->offset, episode,
-                           (u32)(p.h.end[r] - wr), (u32)wr, lg, (u32)seats, seats_per_game, deal, a.on, a.base, a.i01, a.i23, a.ikey, a.ires);
+        launch_bids_list_deal(e, a, p.round_bound[r], e->seed ^ (u64)salt, episode, p.h.end[r] - wr, wr, seats, seats_per_game, deal, depth,
+                              pass_value, s);
         launch_net_play(p.round_bound[r], a.total, net_seats, a, w, s, depth, value_scale);
         hipLaunchKernelGGL(k_playout_bids_net_halving_sum, dim3((unsigned)((p.list.units + 7) / 8)), dim3(TK_BLOCK), 0, s, p.list.units,
                            bound, (u32)p.h.end[r], (u32)wr, (u32)(r == p.h.rounds - 1), (u32)p.h.worlds, a.ires, a.on, alive, a.base, rsum,
