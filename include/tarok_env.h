@@ -1067,6 +1067,55 @@ int tarok_playout_cards_net_halving(tarok_env *env, int kind, const void *words,
                                     float value_scale, void *scratch, int64_t scratch_bytes, int32_t *sum_out,
                                     int32_t *count_out, uint8_t *action_out, void *stream);
 
+/* Two-network net playouts with VIEWER-RELATIVE seats: tarok_playout_cards_net_value and
+ * tarok_playout_cards_net_halving whose playouts seat two networks, A (w1 .. b3) and B (v1 .. c3, in the same layouts), by
+ * where a seat sits relative to the item's viewer.  The VIEWER of an item is the seat to move in the env's position (the
+ * seat that plays the candidate card, the seat the playouts are for), as in tarok_playout_cards_net_value.  For an item
+ * whose viewer is v, the RELATIVE seat of absolute seat s is r = (s - v) & 3: r = 0 is the viewer, r = 1 the seat after
+ * it.  Two 4-bit sets over r give the roles:
+ *   own_rel   the relative seats that play network A;
+ *   opp_rel   the relative seats that play network B.
+ * Inside a playout, after the candidate card, the seat to move at relative seat r plays
+ *   - r in own_rel: A's GREEDY card — the lowest-numbered legal card at the maximum of the 54 card logits that
+ *     tarok_policy_mlp's forward gives (bit for bit) with A on the feature words of the playout's own position;
+ *   - r in opp_rel: B's greedy card, by the same rule with B;
+ *   - r in neither: the Bot's card policy_action(pkey, q, legal) at q cards played, as in tarok_playout_cards_det.
+ * own_rel & opp_rel != 0 is TAROK_EINVAL.  own_rel = 1, opp_rel = 14: A plays the viewer, B plays the table — the playouts
+ * of a best response to B, and of an opponent model.  One launch serves every game's own viewer.
+ * With depth > 0 an item stops at the viewer's depth-th decision exactly as in tarok_playout_cards_net_value; the value v is
+ * output 54 of the VIEWER'S OWN network on the stop position — B if bit 0 of opp_rel is set, else A, whether or not the
+ * viewer is in either set — and t = v * value_scale, NaN -> 0, the clamp to [-32767, 32767], V = (int)rintf(t) and "V in the
+ * viewer's column, 0 in the other three" are that launch's.  depth = 0 and depth = TAROK_PLAYOUT_MAX_DEPTH play to the last
+ * card; value_scale is then not read by the launches (it is still checked).
+ * Everything else is the existing launches': kind and words as tarok_playout_cards_net_value takes them; "takes part", the
+ * worlds and wkey, pkey, the item numbering, seats / seats_per_game, sum_out [N,12,4] i32, action_out [N] u8, count_out
+ * [N,12] i32, rounds and round_worlds, the survivor rule, the prefix-sum launches, the read-only env; the scratch sizes are
+ * tarok_playout_net_scratch(env, worlds) and tarok_playout_net_halving_scratch_bytes(env, rounds, round_worlds).  BOTH weight
+ * sets are read through the pointers when the launches RUN: a captured graph replays with whatever A and B hold then.
+ * Nothing is allocated, nothing is read by the host; three launches (the items, whose markers carry the viewer at every
+ * depth; the playouts; the sums), or the halving launch's per round.
+ * Consequences, byte for byte: (own_rel, opp_rel) = (15, 0) with any B (or none) is net_seats = 15 on A; (0, 15) is
+ * net_seats = 15 on B; any split of the four seats between equal A and B is net_seats = 15; (0, 0) is
+ * tarok_playout_cards_det / _voids / _hidden(worlds, 1); at seats = 1 << v, own_rel = an absolute set m rotated right by v
+ * (bit r of own_rel = bit (r + v) & 3 of m) with opp_rel = 0 is net_seats = m.
+ * B may be NULL (all six) when opp_rel = 0: it is not read.  The exchange and bid launches have no versus form.
+ * TAROK_EINVAL (before any HIP call) for everything tarok_playout_cards_net_value / tarok_playout_cards_net_halving refuse
+ * (net_seats aside: there is none), depth outside 0..TAROK_PLAYOUT_MAX_DEPTH, value_scale not finite or not > 0, own_rel or
+ * opp_rel outside 0..15, own_rel & opp_rel != 0, a missing array of B when opp_rel != 0. */
+int tarok_playout_cards_net_versus(tarok_env *env, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                                   int kind, const void *words, int own_rel, int opp_rel, int depth, float value_scale,
+                                   const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
+                                   const float *b3, const void *v1, const float *c1, const void *v2, const float *c2,
+                                   const void *v3, const float *c3, void *scratch, int64_t scratch_bytes, int32_t *sum_out,
+                                   uint8_t *action_out, void *stream);
+int tarok_playout_cards_net_versus_halving(tarok_env *env, int kind, const void *words, int rounds, const int *round_worlds,
+                                           uint64_t salt, int seats, const uint8_t *seats_per_game, int own_rel, int opp_rel,
+                                           const void *w1, const float *b1, const void *w2, const float *b2, const void *w3,
+                                           const float *b3, const void *v1, const float *c1, const void *v2, const float *c2,
+                                           const void *v3, const float *c3, int depth, float value_scale, void *scratch,
+                                           int64_t scratch_bytes, int32_t *sum_out, int32_t *count_out, uint8_t *action_out,
+                                           void *stream);
+
 /* Net-played playouts for the exchange and the bid: tarok_playout_exchange and tarok_playout_bids at ONE playout per
  * (candidate or option, world), played as tarok_playout_cards_net plays its playouts — the network's greedy card on the
  * absolute seats of net_seats (one launch-wide 4-bit set), the Bot's card policy_action(pkey, q, legal) on the others.

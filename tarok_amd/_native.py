@@ -45,6 +45,7 @@ SYMBOLS = [
     "tarok_playout_bids_net_list_scratch", "tarok_playout_bids_net_list",
     "tarok_playout_exchange_net_halving_scratch_bytes", "tarok_playout_exchange_net_halving",
     "tarok_playout_bids_net_halving_scratch_bytes", "tarok_playout_bids_net_halving",
+    "tarok_playout_cards_net_versus", "tarok_playout_cards_net_versus_halving",
 ]
 
 
@@ -219,6 +220,11 @@ def lib():
     L.tarok_playout_net_halving_scratch_bytes.restype = i64; L.tarok_playout_net_halving_scratch_bytes.argtypes = [vp, i32, vp]
     L.tarok_playout_cards_net_halving.restype = i32  # (kind, words, rounds, round_worlds), salt .. net_seats, w1 .. b3, (depth, value_scale)
     L.tarok_playout_cards_net_halving.argtypes = [vp, i32, vp, i32, vp, u64, i32, vp, i32] + [vp] * 6 + [i32, f32, vp, i64, vp, vp, vp, vp]
+    # tarok_playout_cards_net_value / _net_halving with (own_rel, opp_rel) for net_seats and network B's six arrays after A's
+    L.tarok_playout_cards_net_versus.restype = i32
+    L.tarok_playout_cards_net_versus.argtypes = [vp, i32, u64, i32, vp, i32, vp, i32, i32, i32, f32] + [vp] * 12 + [vp, i64, vp, vp, vp]
+    L.tarok_playout_cards_net_versus_halving.restype = i32
+    L.tarok_playout_cards_net_versus_halving.argtypes = [vp, i32, vp, i32, vp, u64, i32, vp, i32, i32] + [vp] * 12 + [i32, f32, vp, i64, vp, vp, vp, vp]
     L.tarok_playout_exchange_net_list_scratch.restype = i64; L.tarok_playout_exchange_net_list_scratch.argtypes = [vp, i32, i32]
     L.tarok_playout_exchange_net_list.restype = i32  # tarok_playout_exchange_net_value's arguments; depth 0: to the last card
     L.tarok_playout_exchange_net_list.argtypes = [vp, i32, i32, u64, i32, vp, i32, i32, f32] + [vp] * 6 + [vp, i64, vp, vp, vp, vp]

@@ -704,6 +704,21 @@ TK_HOST_DEVICE __forceinline__ int64_t net_list_bound(int64_t n, u32 round, u32 
 }
 TK_HOST_DEVICE __forceinline__ int64_t net_list_tiles(int64_t bound, u32 tile) { return (bound + (int64_t)tile - 1) / (int64_t)tile; }
 
+// The roles of tarok_playout_cards_net_versus (include/tarok_env.h): seats are named RELATIVE to an item's viewer,
+// r = (seat - viewer) & 3, and two disjoint 4-bit sets over r say who plays there.  The play kernels, the host's checks and
+// tests/host_emu/net_versus_host.cpp share these.
+//   net_versus_role        0: the Bot, 1: network A (r in own_rel), 2: network B (r in opp_rel) — the sets are disjoint
+//   net_versus_viewer_net  the network whose value head speaks for the viewer at a stop: B if the viewer (r = 0) plays B, else A
+//   net_versus_roles_ok    what the entries accept: both sets within 0..15 and no seat in both
+TK_HOST_DEVICE __forceinline__ u32 net_versus_role(u32 viewer, u32 mover, u32 own_rel, u32 opp_rel) {
+    const u32 r = (mover - viewer) & 3u;
+    return ((own_rel >> r) & 1u) | (((opp_rel >> r) & 1u) << 1);
+}
+TK_HOST_DEVICE __forceinline__ u32 net_versus_viewer_net(u32 opp_rel) { return (opp_rel & 1u) ? 2u : 1u; }
+TK_HOST_DEVICE __forceinline__ bool net_versus_roles_ok(int own_rel, int opp_rel) {
+    return own_rel >= 0 && own_rel <= 15 && opp_rel >= 0 && opp_rel <= 15 && !(own_rel & opp_rel);
+}
+
 // Determinization (tarok_playout_cards_det, include/tarok_env.h): one WORLD of the seat `mover` — the cards it cannot
 // see, P = the hands of the three other seats, are dealt afresh among those seats, uniformly over the deals that keep
 // the hand sizes.  The cards of P are walked in ascending card number; card i of the walk draws

@@ -3663,29 +3663,44 @@ TK_NET_DEAL(k_playout_net_deal_value_hidden, DealHidden, true, played_words, con
 //     half == 0 lane between the forward's last two barriers (512 bytes more LDS: 77,456 in all, still two per CU);
 //   - a stopping row is retired in its round whatever its legal mask holds; depth = TAROK_PLAYOUT_MAX_DEPTH never counts
 //     to 0 (a seat has at most 11 cards after its candidate), and every round is then the plain kernel's.
-template <bool VALUE>
+//
+// VERSUS (k_playout_net_play_versus*, tarok_playout_cards_net_versus): two networks, seated RELATIVE to each
+// item's viewer (net_versus_role, tarok_device.h); net_seats is not read.  A live item's marker always carries its viewer
+// (the caller's item kernel is the _value form also at depth 0).  What changes in the invariants above, and nothing else:
+//   - waves 0 and 1 write each row's role (0 Bot, 1 A, 2 B; bit 2: the row stops this round) to role_s[row], the second
+//     half of act_s, before the round's first barrier;
+//   - vote bit 2 means "some live row needs a pass of A", and a FOURTH bit (8) "some live row needs a pass of B": a row
+//     that plays a card needs its role's pass, a row that stops needs its viewer's network's pass alone.  Both are written
+//     with the first before the round's first barrier, so the pass tests are workgroup-uniform; the two parities stay;
+//   - the forward runs once per set pass bit — X re-expanded from ext each time, the third barrier of a pass keeps the
+//     next pass's expansion off the logits being read — and in pass P a row's half == 0 lane writes act_s only where the
+//     row's role is P, val_s only where the row stops and P is the viewer's network.  No barrier is in a divergent branch.
+template <bool VALUE, bool VERSUS = false>
 __device__ __forceinline__ void playout_net_play_body(int64_t items, u32 net_seats, u32 depth, float value_scale,
                                                       const ulonglong2 *__restrict__ i01, const ulonglong2 *__restrict__ i23,
                                                       const u64 *__restrict__ ikey, u64 *__restrict__ ires,
                                                       const __bf16 *__restrict__ w1, const float *__restrict__ b1,
                                                       const __bf16 *__restrict__ w2, const float *__restrict__ b2,
-                                                      const __bf16 *__restrict__ w3, const float *__restrict__ b3) {
+                                                      const __bf16 *__restrict__ w3, const float *__restrict__ b3,
+                                                      u32 own_rel = 0, u32 opp_rel = 0, const PolicyWeights &wb = PolicyWeights{}) {
+    constexpr bool MARKED = VALUE || VERSUS;             // a live item's marker carries its viewer
     __shared__ __attribute__((aligned(16))) __bf16 X[PM_M * PM_LD];
     __shared__ __attribute__((aligned(16))) u64 ext[PM_M][4];
     __shared__ __attribute__((aligned(16))) u64 st[PM_M][4];
     __shared__ u64 keys[PM_M];
-    __shared__ uint8_t act_s[PM_M];
+    __shared__ uint8_t act_s[VERSUS ? 2 * PM_M : PM_M];
     __shared__ u32 vote[2][2];
     __shared__ float val_s[VALUE ? PM_M : 1];
+    uint8_t *role_s = act_s + (VERSUS ? PM_M : 0);       // (VERSUS only)
     const u32 tid = threadIdx.x, wave = tid >> 6;
     const int64_t it = (int64_t)blockIdx.x * PM_M + tid;
     float *L = reinterpret_cast<float *>(X);
     bool live = false;
     u32 viewer = 0, left = depth;
     u64 mark = 0;
-    if (tid < PM_M && it < items && ((mark = ires[it]) & (VALUE ? ~3ULL : ~0ULL)) == TK_PN_LIVE) {
+    if (tid < PM_M && it < items && ((mark = ires[it]) & (MARKED ? ~3ULL : ~0ULL)) == TK_PN_LIVE) {
         live = true;
-        if constexpr (VALUE) viewer = (u32)mark & 3u;
+        if constexpr (MARKED) viewer = (u32)mark & 3u;
         const ulonglong2 a = i01[it], b = i23[it];
         st[tid][0] = a.x; st[tid][1] = a.y; st[tid][2] = b.x; st[tid][3] = b.y;
         keys[tid] = ikey[it];
@@ -3693,21 +3708,37 @@ __device__ __forceinline__ void playout_net_play_body(int64_t items, u32 net_sea
 #pragma unroll 1
     for (u32 round = 0; round < TK_PN_MAX_CARDS; round++) {
         bool stop = false;
+        u32 role = 0;                                      // (VERSUS only: the mover's, kept by the row's owner)
         if (tid < PM_M) {                                  // (waves 0 and 1, whole)
-            bool net = false;
+            bool net = false, net_b = false;               // (VERSUS: the row needs a pass of A / of B)
             if (live) {
                 Game h;
                 unpack(h, st[tid][0], st[tid][1], st[tid][2], st[tid][3]);
                 policy_feature_words(h, ext[tid]);
-                net = (net_seats >> ((h.leader + h.nt) & 3)) & 1u;
-                if constexpr (VALUE) {
-                    if (((h.leader + h.nt) & 3) == viewer) stop = --left == 0;
+                if constexpr (VERSUS) {
+                    const u32 mover = (h.leader + h.nt) & 3;
+                    role = net_versus_role(viewer, mover, own_rel, opp_rel);
+                    if constexpr (VALUE) {
+                        if (mover == viewer) stop = --left == 0;
+                    }
+                    const u32 need = stop ? net_versus_viewer_net(opp_rel) : role;
+                    net = need == 1u; net_b = need == 2u;
+                    role_s[tid] = (uint8_t)(role | (stop ? 4u : 0u));
+                } else {
+                    net = (net_seats >> ((h.leader + h.nt) & 3)) & 1u;
+                    if constexpr (VALUE) {
+                        if (((h.leader + h.nt) & 3) == viewer) stop = --left == 0;
+                    }
                 }
             } else {
                 ext[tid][0] = 0; ext[tid][1] = 0; ext[tid][2] = 0; ext[tid][3] = 0;
+                if constexpr (VERSUS) role_s[tid] = 0;
             }
             const u64 any_live = __ballot(live), any_net = __ballot(live && net);
-            if constexpr (VALUE) {
+            if constexpr (VERSUS) {
+                const u64 any_b = __ballot(live && net_b); // (every lane of the wave is here: tid < PM_M takes whole waves)
+                if (__lane_id() == 0) vote[round & 1][wave] = (any_live ? 1u : 0u) | (any_net ? 2u : 0u) | (any_b ? 8u : 0u);
+            } else if constexpr (VALUE) {
                 const u64 any_stop = __ballot(stop);       // (every lane of the wave is here: tid < PM_M takes whole waves)
                 if (__lane_id() == 0) vote[round & 1][wave] = (any_live ? 1u : 0u) | (any_net ? 2u : 0u) | (any_stop ? 4u : 0u);
             } else {
@@ -3717,7 +3748,39 @@ __device__ __forceinline__ void playout_net_play_body(int64_t items, u32 net_sea
         __syncthreads();
         const u32 v = vote[round & 1][0] | vote[round & 1][1];
         if (!(v & 1u)) break;
-        if (v & (VALUE ? 6u : 2u)) {
+        if constexpr (VERSUS) {
+            const u32 viewer_net = net_versus_viewer_net(opp_rel);
+#pragma unroll 1
+            for (u32 pass = 1; pass <= 2; pass++) {        // (v is the workgroup's: every thread runs the same passes)
+                if (!(v & (pass == 1 ? 2u : 8u))) continue;
+                const bool pa = pass == 1;
+                const __bf16 *p1 = pa ? w1 : wb.w1, *p2 = pa ? w2 : wb.w2, *p3 = pa ? w3 : wb.w3;
+                const float *c1 = pa ? b1 : wb.b1, *c2 = pa ? b2 : wb.b2, *c3 = pa ? b3 : wb.b3;
+                bf16x8 wq[4][2];
+                mlp_prefetch(wq, p1, wave * 2);
+                policy_expand(X, ext, tid);
+                __syncthreads();
+                mlp_hidden(X, p1, c1, wq, wave);
+                mlp_prefetch(wq, p2, wave * 2);
+                mlp_hidden(X, p2, c2, wq, wave);
+                mlp_head(X, L, p3, c3, wave, 0);
+                __syncthreads();
+                const u32 gi = tid >> 1, half = tid & 1;
+                PolicySampleIn in;
+                in.m = ext[gi][1] & TAROK_OBS_MASK;
+                in.o = in.m; in.key = 0; in.played = 0; in.last = 0;
+                in.mh = (u32)(in.m >> (27 * half)) & 0x7FFFFFFu;
+                const PolicyPick c = policy_sample<1>(L, gi, half, in, PlayMode{1.f, 1, 0u, 0.f});
+                if (half == 0) {
+                    const u32 rs = role_s[gi];
+                    if ((rs & 3u) == pass) act_s[gi] = (uint8_t)c.pk;
+                    if constexpr (VALUE) {
+                        if ((rs & 4u) && viewer_net == pass) val_s[gi] = c.v54;
+                    }
+                }
+                __syncthreads();
+            }
+        } else if (v & (VALUE ? 6u : 2u)) {
             bf16x8 wq[4][2];
             mlp_prefetch(wq, w1, wave * 2);
             policy_expand(X, ext, tid);
@@ -3756,7 +3819,8 @@ __device__ __forceinline__ void playout_net_play_body(int64_t items, u32 net_sea
                 ires[it] = 0;
             } else {
                 const u32 seat = (h.leader + h.nt) & 3, q = h.trick_no * 4 + h.nt;
-                const u32 c = ((net_seats >> seat) & 1u) ? (u32)act_s[tid] : policy_action(keys[tid], q, legal);
+                const bool by_net = VERSUS ? role != 0u : ((net_seats >> seat) & 1u) != 0u;
+                const u32 c = by_net ? (u32)act_s[tid] : policy_action(keys[tid], q, legal);
                 u64 scores = 0;
                 u32 ti;
                 if (apply_step<true>(h, c, scores, ti, false)) {
@@ -3787,6 +3851,26 @@ __global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net
     u32 depth, float value_scale) {
     TK_VGPR_TOP(256, 255);
     playout_net_play_body<true>(items, net_seats, depth, value_scale, i01, i23, ikey, ires, w1, b1, w2, b2, w3, b3);
+}
+
+// tarok_playout_cards_net_versus' second launch: the VERSUS body over the dense count, network A as the six arrays every
+// play kernel takes, then the two role sets and network B; the _value form stops at the viewer's depth-th decision.
+__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net_play_versus(
+    int64_t items, u32 own_rel, const ulonglong2 *__restrict__ i01, const ulonglong2 *__restrict__ i23,
+    const u64 *__restrict__ ikey, u64 *__restrict__ ires, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3, const float *__restrict__ b3,
+    u32 opp_rel, PolicyWeights wb) {
+    TK_VGPR_TOP(256, 255);
+    playout_net_play_body<false, true>(items, 0, 0, 0.f, i01, i23, ikey, ires, w1, b1, w2, b2, w3, b3, own_rel, opp_rel, wb);
+}
+
+__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net_play_versus_value(
+    int64_t items, u32 own_rel, const ulonglong2 *__restrict__ i01, const ulonglong2 *__restrict__ i23,
+    const u64 *__restrict__ ikey, u64 *__restrict__ ires, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3, const float *__restrict__ b3,
+    u32 opp_rel, PolicyWeights wb, u32 depth, float value_scale) {
+    TK_VGPR_TOP(256, 255);
+    playout_net_play_body<true, true>(items, 0, depth, value_scale, i01, i23, ikey, ires, w1, b1, w2, b2, w3, b3, own_rel, opp_rel, wb);
 }
 
 // Third launch: 16 lanes per game; lane r < 12 sums rank r's items over the worlds in integers, then card_epilogue's
@@ -3997,6 +4081,26 @@ __global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net
     u32 depth, float value_scale) {
     TK_VGPR_TOP(256, 255);
     playout_net_play_body<true>((int64_t)*total, net_seats, depth, value_scale, i01, i23, ikey, ires, w1, b1, w2, b2, w3, b3);
+}
+
+// tarok_playout_cards_net_versus_halving's playouts: the VERSUS body on the round's total.
+__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net_play_list_versus(
+    const u32 *__restrict__ total, u32 own_rel, const ulonglong2 *__restrict__ i01, const ulonglong2 *__restrict__ i23,
+    const u64 *__restrict__ ikey, u64 *__restrict__ ires, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3, const float *__restrict__ b3,
+    u32 opp_rel, PolicyWeights wb) {
+    TK_VGPR_TOP(256, 255);
+    playout_net_play_body<false, true>((int64_t)*total, 0, 0, 0.f, i01, i23, ikey, ires, w1, b1, w2, b2, w3, b3, own_rel, opp_rel, wb);
+}
+
+__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net_play_list_versus_value(
+    const u32 *__restrict__ total, u32 own_rel, const ulonglong2 *__restrict__ i01, const ulonglong2 *__restrict__ i23,
+    const u64 *__restrict__ ikey, u64 *__restrict__ ires, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3, const float *__restrict__ b3,
+    u32 opp_rel, PolicyWeights wb, u32 depth, float value_scale) {
+    TK_VGPR_TOP(256, 255);
+    playout_net_play_body<true, true>((int64_t)*total, 0, depth, value_scale, i01, i23, ikey, ires, w1, b1, w2, b2, w3, b3, own_rel, opp_rel,
+                                      wb);
 }
 
 // The round's sums and the survivor rule: 16 lanes a game, as k_playout_net_sum.  Lane j < 12 whose rank played the round adds
@@ -5551,14 +5655,27 @@ static inline bool depth_args_ok(int depth, int lo, int hi, float value_scale) {
 // layout, `items` the host's count; else the compacted list, whose count is the device's total word and `items` the host's
 // bound: the grid is the bound's (one workgroup where the bound is 0: it finds no row below the total).  depth = 0: to the
 // last card; else the _value kernel, whose live items carry their viewers (the caller's item kernel is the _value form).
+// b non-NULL: the VERSUS kernels (tarok_playout_cards_net_versus) — w is network A, *b network B, own_rel / opp_rel the role
+// sets over the seats relative to each item's viewer, net_seats is not read, and the caller's item kernel is the _value form
+// at every depth.
 static inline void launch_net_play(int64_t items, const u32 *total, int net_seats, const NetItems &it, const PolicyWeights &w,
-                                   hipStream_t s, int depth, float value_scale) {
+                                   hipStream_t s, int depth, float value_scale, const PolicyWeights *b = nullptr, int own_rel = 0,
+                                   int opp_rel = 0) {
     const int64_t tiles = net_list_tiles(items, PM_M);
     const dim3 grid((unsigned)(tiles ? tiles : 1));
 #define TK_LAUNCH_NET_PLAY(K, COUNT, ...)                                                                                          \
     hipLaunchKernelGGL(K, grid, dim3(TK_BLOCK), 0, s, COUNT, (u32)net_seats, it.i01, it.i23, it.ikey, it.ires, w.w1, w.b1, w.w2, \
                        w.b2, w.w3, w.b3, ##__VA_ARGS__)
-    if (total) {
+    if (b) {
+        net_seats = own_rel;                             // (the VERSUS kernels take own_rel where the others take net_seats)
+        if (total) {
+            if (depth) TK_LAUNCH_NET_PLAY(k_playout_net_play_list_versus_value, total, (u32)opp_rel, *b, (u32)depth, value_scale);
+            else TK_LAUNCH_NET_PLAY(k_playout_net_play_list_versus, total, (u32)opp_rel, *b);
+        } else {
+            if (depth) TK_LAUNCH_NET_PLAY(k_playout_net_play_versus_value, items, (u32)opp_rel, *b, (u32)depth, value_scale);
+            else TK_LAUNCH_NET_PLAY(k_playout_net_play_versus, items, (u32)opp_rel, *b);
+        }
+    } else if (total) {
         if (depth) TK_LAUNCH_NET_PLAY(k_playout_net_play_list_value, total, (u32)depth, value_scale);
         else TK_LAUNCH_NET_PLAY(k_playout_net_play_list, total);
     } else {
@@ -5571,11 +5688,13 @@ static inline void launch_net_play(int64_t items, const u32 *total, int net_seat
 // One net card launch: the items (`deal`, the dealer's kernel, with its per-game `words`: a typed null for a det kernel,
 // which takes none), the playouts, the sums — three launches on `stream`, nothing allocated.  depth = 0: the playouts run
 // to the last card; else (checked by tarok_playout_cards_net_value, the only caller that gives one) they stop at the
-// viewer's depth-th decision, and `deal` is a k_playout_net_deal_value*.
+// viewer's depth-th decision, and `deal` is a k_playout_net_deal_value*.  b non-NULL (tarok_playout_cards_net_versus, which has
+// checked the roles): launch_net_play's VERSUS form, `deal` a k_playout_net_deal_value* at every depth.
 template <class Kernel, class Word>
 static int launch_playout_cards_net(Kernel deal, tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
                                     const Word *words, int net_seats, const PolicyWeights &w, void *scratch, int64_t scratch_bytes,
-                                    int32_t *sum_out, uint8_t *action_out, void *stream, int depth, float value_scale) {
+                                    int32_t *sum_out, uint8_t *action_out, void *stream, int depth, float value_scale,
+                                    const PolicyWeights *b = nullptr, int own_rel = 0, int opp_rel = 0) {
     constexpr bool has_words = !std::is_same<Word, NoWord>::value;
     if (!playout_args_ok(e, worlds, 1, seats) || !net_args_ok(net_seats, w, scratch, scratch_bytes, tarok_playout_net_scratch(e, worlds)) ||
         (!sum_out && !action_out) || (has_words && !words))
@@ -5589,7 +5708,7 @@ static int launch_playout_cards_net(Kernel deal, tarok_env *e, int worlds, uint6
                            (u32)worlds, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, kwords..., it.i01, it.i23, it.ikey, it.ires);
     };
     if constexpr (has_words) launch_deal(words); else launch_deal();
-    launch_net_play(items, nullptr, net_seats, it, w, (hipStream_t)stream, depth, value_scale);
+    launch_net_play(items, nullptr, net_seats, it, w, (hipStream_t)stream, depth, value_scale, b, own_rel, opp_rel);
     hipLaunchKernelGGL(k_playout_net_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, (u32)worlds,
                        (u32)seats, seats_per_game, e->s01, e->s23, e->gkey, it.ires, reinterpret_cast<int4 *>(sum_out), action_out);
     HIPCHK(hipGetLastError());
@@ -5894,13 +6013,14 @@ int64_t tarok_playout_net_halving_scratch_bytes(const tarok_env *e, int rounds, 
     return net_halving_plan(e, rounds, round_worlds, p) ? p.list.bytes : (int64_t)TAROK_EINVAL;
 }
 
-int tarok_playout_cards_net_halving(tarok_env *e, int kind, const void *words, int rounds, const int *round_worlds, uint64_t salt,
-                                    int seats, const uint8_t *seats_per_game, int net_seats, const void *w1, const float *b1,
-                                    const void *w2, const float *b2, const void *w3, const float *b3, int depth, float value_scale,
-                                    void *scratch, int64_t scratch_bytes, int32_t *sum_out, int32_t *count_out, uint8_t *action_out,
-                                    void *stream) {
+// tarok_playout_cards_net_halving, and — b non-NULL, the roles checked by the caller — tarok_playout_cards_net_versus_halving: the
+// same rounds with launch_net_play's VERSUS form, whose items carry their viewers at every depth.
+static int launch_playout_cards_net_halving(tarok_env *e, int kind, const void *words, int rounds, const int *round_worlds, uint64_t salt,
+                                            int seats, const uint8_t *seats_per_game, int net_seats, const PolicyWeights &w, int depth,
+                                            float value_scale, void *scratch, int64_t scratch_bytes, int32_t *sum_out, int32_t *count_out,
+                                            uint8_t *action_out, void *stream, const PolicyWeights *b = nullptr, int own_rel = 0,
+                                            int opp_rel = 0) {
     NetHalvingPlan p;
-    const PolicyWeights w = TK_WEIGHTS(w1, b1, w2, b2, w3, b3);
     // depth 0 is "to the last card", and a bad value_scale is refused there too
     if (!e || !world_kind_ok(kind) || (kind == TAROK_NET_WORLDS_DET) != !words || !net_halving_plan(e, rounds, round_worlds, p) ||
         seats < 0 || seats > 15 || !net_args_ok(net_seats, w, scratch, scratch_bytes, p.list.bytes) ||
@@ -5919,16 +6039,16 @@ int tarok_playout_cards_net_halving(tarok_env *e, int kind, const void *words, i
     hipLaunchKernelGGL(k_playout_net_list_init, per_16, dim3(TK_BLOCK), 0, s, n, (u32)seats, seats_per_game, e->s01, e->s23, a.on, alive,
                        rsum, reinterpret_cast<int4 *>(rcnt));
     return for_world_kind(kind, words, [&](auto k, auto *kwords) {
-        const auto deal = depth ? TK_OF_KIND(k, k_playout_net_list_deal_value, k_playout_net_list_deal_value_voids,
-                                             k_playout_net_list_deal_value_hidden)
-                                : TK_OF_KIND(k, k_playout_net_list_deal, k_playout_net_list_deal_voids, k_playout_net_list_deal_hidden);
+        const auto deal = depth || b ? TK_OF_KIND(k, k_playout_net_list_deal_value, k_playout_net_list_deal_value_voids,
+                                                  k_playout_net_list_deal_value_hidden)
+                                     : TK_OF_KIND(k, k_playout_net_list_deal, k_playout_net_list_deal_voids, k_playout_net_list_deal_hidden);
         for (int r = 0; r < p.h.rounds; r++) {
             const int wr = p.h.w[r];
             launch_list_scan(p.list, a, wr, s);
             const u32 lg = playout_lg(TK_PO_MIN_LG, wr);
             hipLaunchKernelGGL(deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, s, n, pseed, e->offset, (u32)(p.h.end[r] - wr), (u32)wr, lg,
                                (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, kwords, a.on, a.base, a.i01, a.i23, a.ikey, a.ires);
-            launch_net_play(net_list_bound(n, (u32)r, (u32)wr), a.total, net_seats, a, w, s, depth, value_scale);
+            launch_net_play(net_list_bound(n, (u32)r, (u32)wr), a.total, net_seats, a, w, s, depth, value_scale, b, own_rel, opp_rel);
             hipLaunchKernelGGL(k_playout_net_list_sum, per_16, dim3(TK_BLOCK), 0, s, n, (u32)p.h.end[r], (u32)wr,
                                (u32)(r == p.h.rounds - 1), (u32)seats, seats_per_game, e->s01, e->s23, e->gkey, a.ires, a.on, alive, a.base,
                                rsum, rcnt, reinterpret_cast<int4 *>(sum_out), reinterpret_cast<int4 *>(count_out), action_out);
@@ -5936,6 +6056,56 @@ int tarok_playout_cards_net_halving(tarok_env *e, int kind, const void *words, i
         HIPCHK(hipGetLastError());
         return (int)TAROK_OK;
     });
+}
+
+int tarok_playout_cards_net_halving(tarok_env *e, int kind, const void *words, int rounds, const int *round_worlds, uint64_t salt,
+                                    int seats, const uint8_t *seats_per_game, int net_seats, const void *w1, const float *b1,
+                                    const void *w2, const float *b2, const void *w3, const float *b3, int depth, float value_scale,
+                                    void *scratch, int64_t scratch_bytes, int32_t *sum_out, int32_t *count_out, uint8_t *action_out,
+                                    void *stream) {
+    return launch_playout_cards_net_halving(e, kind, words, rounds, round_worlds, salt, seats, seats_per_game, net_seats,
+                                            TK_WEIGHTS(w1, b1, w2, b2, w3, b3), depth, value_scale, scratch, scratch_bytes, sum_out,
+                                            count_out, action_out, stream);
+}
+
+// The two versus entries' own refusals: the role sets, and network B where a seat plays it.  B may be absent when opp_rel = 0:
+// the kernels then get A in its place, and read neither.
+static bool versus_args_ok(int own_rel, int opp_rel, const PolicyWeights &a, PolicyWeights &b) {
+    if (!net_versus_roles_ok(own_rel, opp_rel)) return false;
+    if (!opp_rel) b = a;
+    return b.w1 && b.b1 && b.w2 && b.b2 && b.w3 && b.b3;
+}
+
+int tarok_playout_cards_net_versus(tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game, int kind,
+                                   const void *words, int own_rel, int opp_rel, int depth, float value_scale, const void *w1,
+                                   const float *b1, const void *w2, const float *b2, const void *w3, const float *b3, const void *v1,
+                                   const float *c1, const void *v2, const float *c2, const void *v3, const float *c3, void *scratch,
+                                   int64_t scratch_bytes, int32_t *sum_out, uint8_t *action_out, void *stream) {
+    const PolicyWeights a = TK_WEIGHTS(w1, b1, w2, b2, w3, b3);
+    PolicyWeights b = TK_WEIGHTS(v1, c1, v2, c2, v3, c3);
+    // DET with words is refused here; VOIDS / HIDDEN without them by the launcher, as tarok_playout_cards_net_value
+    if (!world_kind_ok(kind) || (kind == TAROK_NET_WORLDS_DET && words) || !depth_args_ok(depth, 0, TAROK_PLAYOUT_MAX_DEPTH, value_scale) ||
+        !versus_args_ok(own_rel, opp_rel, a, b))
+        return TAROK_EINVAL;
+    if (depth == TAROK_PLAYOUT_MAX_DEPTH) depth = 0;     // never stops (§8.18)
+    return for_world_kind(kind, words, [&](auto k, auto *kwords) {
+        const auto deal = TK_OF_KIND(k, k_playout_net_deal_value, k_playout_net_deal_value_voids, k_playout_net_deal_value_hidden);
+        return launch_playout_cards_net(deal, e, worlds, salt, seats, seats_per_game, kwords, 0, a, scratch, scratch_bytes, sum_out,
+                                        action_out, stream, depth, value_scale, &b, own_rel, opp_rel);
+    });
+}
+
+int tarok_playout_cards_net_versus_halving(tarok_env *e, int kind, const void *words, int rounds, const int *round_worlds, uint64_t salt,
+                                           int seats, const uint8_t *seats_per_game, int own_rel, int opp_rel, const void *w1,
+                                           const float *b1, const void *w2, const float *b2, const void *w3, const float *b3,
+                                           const void *v1, const float *c1, const void *v2, const float *c2, const void *v3,
+                                           const float *c3, int depth, float value_scale, void *scratch, int64_t scratch_bytes,
+                                           int32_t *sum_out, int32_t *count_out, uint8_t *action_out, void *stream) {
+    const PolicyWeights a = TK_WEIGHTS(w1, b1, w2, b2, w3, b3);
+    PolicyWeights b = TK_WEIGHTS(v1, c1, v2, c2, v3, c3);
+    if (!versus_args_ok(own_rel, opp_rel, a, b)) return TAROK_EINVAL;
+    return launch_playout_cards_net_halving(e, kind, words, rounds, round_worlds, salt, seats, seats_per_game, 0, a, depth, value_scale,
+                                            scratch, scratch_bytes, sum_out, count_out, action_out, stream, &b, own_rel, opp_rel);
 }
 
 int tarok_playout_bids(tarok_env *e, uint32_t episode, const uint8_t *deals, int worlds, int samples, int contracts, uint64_t salt,

@@ -527,6 +527,49 @@ class TarokVecEnv:
         return self._cards(worlds, None, salt, seats, seats_per_game, sum_out, action_out, voids, hidden, words,
                            (weights, net_seats, depth, value_scale))
 
+    def playout_cards_net_versus(self, weights, opponent, worlds, own_rel=1, opp_rel=14, depth=None, value_scale=70.0, voids=False,
+                                 hidden=False, words=None, halving=None, salt=0, seats=15, seats_per_game=None, sum_out=None,
+                                 action_out=None, count_out=None):
+        """playout_cards_net / playout_cards_net_value whose playouts seat TWO networks relative to each game's VIEWER — the
+        seat to move, the seat the playouts are for (tarok_playout_cards_net_versus).  own_rel / opp_rel: two
+        disjoint 4-bit sets over the relative seats r = (seat - viewer) & 3 (bit 0: the viewer itself); after the candidate
+        card the seats of own_rel play the greedy card of `weights`, those of opp_rel the greedy card of `opponent` (both
+        policy_mlp's six tensors, read when the launch runs), the rest the Bot's card.  The defaults (1, 14): `weights` plays
+        the viewer and `opponent` the table — the playouts of a best response to `opponent`, one launch for every game's own
+        viewer.  (15, 0) is playout_cards_net(weights, worlds) to the byte, (0, 15) the same on `opponent`, (0, 0)
+        playout_cards_det(worlds, 1); opponent may be None where opp_rel is 0.  depth / value_scale: playout_cards_net_value's
+        stop (None: to the last card), with the value head of the VIEWER'S OWN network — `opponent` if opp_rel holds bit 0,
+        else `weights`.  voids / hidden / words: the worlds' kind, as in playout_cards_net.  Returns (sum, action).
+        halving=(w0, w1, ..): the worlds are spent by sequential halving on a compacted item list
+        (tarok_playout_cards_net_versus_halving; `worlds` None or their sum), as in playout_cards_net_halving; returns (sum,
+        count, action), and count_out is taken.  The scratch is playout_net_scratch(worlds) or
+        playout_net_halving_scratch(halving)."""
+        own_rel, opp_rel = P.check_versus((own_rel, opp_rel), P.spelling(net_versus="(own_rel, opp_rel)"))
+        schedule = None if halving is None else P.check_halving(halving)
+        if schedule is not None and worlds and int(worlds) != sum(schedule):
+            raise ValueError("halving= names the worlds of every round: worlds is optional and must be their sum")
+        if schedule is None and count_out is not None:
+            raise ValueError("count_out holds the worlds behind every row of a halving launch: it goes with halving=")
+        kind, words = TarokVecEnv._world_words(self, True, voids, hidden, words)
+        _, depth, value_scale, a = TarokVecEnv._net_args(self, weights, 0, depth, value_scale)
+        if opponent is None and opp_rel:
+            raise ValueError("opp_rel seats the opponent's network: give its six tensors")
+        b = [None] * 6 if opponent is None else [self._p(t) for t in self.check_mlp_weights(opponent)]
+        scratch = self.playout_net_scratch(worlds) if schedule is None else self.playout_net_halving_scratch(schedule)
+        words = words()
+        with torch.cuda.device(self.device):
+            outs = TarokVecEnv._card_outputs(self, sum_out, action_out, False if schedule is None else count_out)
+            tail = [self._p(scratch), scratch.numel()] + [self._p(t) for t in outs] + [self._stream()]
+            sets = [_salt(salt), int(seats), self._p(self._seat_sets(seats_per_game))]
+            if schedule is None:
+                _native.check(self.L.tarok_playout_cards_net_versus(self._h, int(worlds), *sets, P.WORLDS.index(kind), self._p(words),
+                                                                    own_rel, opp_rel, depth, value_scale, *a, *b, *tail))
+            else:
+                _native.check(self.L.tarok_playout_cards_net_versus_halving(
+                    self._h, P.WORLDS.index(kind), self._p(words), len(schedule), (C.c_int * len(schedule))(*schedule), *sets, own_rel,
+                    opp_rel, *a, *b, depth, value_scale, *tail))
+        return tuple(outs)
+
     def playout_exchange(self, worlds, samples, discard_sets=4, salt=0, seats=15, seats_per_game=None, sum_out=None,
                          choice_out=None, discards_out=None):
         """The declarer's talon exchange valued by determinized playouts (tarok_playout_exchange), for the games that

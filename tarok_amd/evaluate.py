@@ -396,7 +396,8 @@ def _bid_args(bidding, mix):
 
 def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None, voids=False, exchange=None,
                     hidden=False, bidding=None, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None,
-                    net_seats=15, net_worlds="det", net_depth=None, net_value_scale=70.0, halving=None, net_halving=None):
+                    net_seats=15, net_worlds="det", net_depth=None, net_value_scale=70.0, halving=None, net_halving=None, net_versus=None,
+                    net_opponent=None):
     """_play_passes_mode with the Monte-Carlo player (TarokVecEnv.playout_cards) in the network's place: per lock-step
     one playout launch with the pass's seat set — tarok_playout_cards (open hands) for worlds=None,
     tarok_playout_cards_det (the fair player: `worlds` re-deals of the unseen cards) otherwise — whose action_out holds
@@ -421,20 +422,31 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     halving=(w0, ..): the launch is tarok_playout_cards_halving with that schedule, in the worlds voids / hidden name.
     net_halving=(w0, ..) (with net): the launch is tarok_playout_cards_net_halving with that schedule, in the worlds of
     net_worlds and at net_depth.
+    net_versus=(own_rel, opp_rel) (with net): the launch is playout_cards_net_versus — `net` on the relative seats of own_rel,
+    net_opponent (six tensors; required where opp_rel is not 0) on those of opp_rel, relative to the player's seat in every
+    game —, in the worlds of net_worlds, at net_depth and with net_halving's schedule where one is given.
     inspect: as in _play_passes_mode."""
     player = playout.card_player(samples, worlds, voids, hidden, net is not None, net_seats, net_worlds, net_depth, net_value_scale, salt,
                                  front=exchange is not None or bidding is not None, **({} if halving is None else dict(halving=halving)),
-                                 **({} if net_halving is None else dict(net_halving=net_halving)))
+                                 **({} if net_halving is None else dict(net_halving=net_halving)),
+                                 **({} if net_versus is None else dict(net_versus=net_versus)))
+    if net_opponent is not None and net_versus is None:
+        raise ValueError("net_opponent is the second network of net_versus=(own_rel, opp_rel): give that as well")
+    if net_versus is not None and player.versus[1] and net_opponent is None:
+        raise ValueError("net_versus seats an opponent's network on the seats of opp_rel: give net_opponent= (six tensors) as well")
     if net is not None:
         if samples is not None:
             raise ValueError("net= runs one playout per (card, world): samples is not taken (pass None)")
         net = TarokVecEnv.check_mlp_weights(net)
+    if net_opponent is not None:
+        net_opponent = TarokVecEnv.check_mlp_weights(net_opponent)
     if exchange is not None and worlds is None:
         raise ValueError("exchange=D is the fair player's front end: give worlds= as well")
     if bidding is not None and worlds is None:
         raise ValueError("bidding=(W, S) is the fair player's front end: give worlds= as well")
     bidding = _bid_args(bidding, mix)
-    cards = _playout_cards(lambda env, seats, words, sums, row, **more: player.launch(env, net, dict(seats=seats), words, sums, row, **more),
+    nets = (net,) if net_versus is None else (net, net_opponent)
+    cards = _playout_cards(lambda env, seats, words, sums, row, **more: player.launch(env, *nets, dict(seats=seats), words, sums, row, **more),
                            words_dtype=player.words_dtype, **({} if player.halving is None else dict(counts=True)))
     front = _front(inspect is not None, bid=None if bidding is None else _bid_front(bidding, salt, threshold, contracts, pass_value),
                    exchange=None if exchange is None else _exchange_front(worlds, samples, exchange, salt))
@@ -444,7 +456,7 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
 def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None,
                             voids=False, exchange=None, hidden=False, bidding=None, threshold=0,
                             contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None, net_seats=15, net_worlds="det",
-                            net_depth=None, net_value_scale=70.0, halving=None, net_halving=None):
+                            net_depth=None, net_value_scale=70.0, halving=None, net_halving=None, net_versus=None, net_opponent=None):
     """evaluate_vs_bot with the open-hand Monte-Carlo player in the network's place: a strong reference player that needs
     no training.  On its seat it plays, at every move, the legal card with the best summed score over `samples` Bot
     playouts of each legal card (tarok_playout_cards; `salt` varies their draws).  The playouts see the TRUE hidden
@@ -486,6 +498,11 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
     net_halving=(w0, w1, ..) (with net=weights; `worlds` None or their sum; with net_worlds and net_depth; not with exchange
     or bidding): the network's playouts are spent by sequential halving on a compacted item list
     (tarok_playout_cards_net_halving).  None (the default): the calls as they were.  halving= with net= keeps raising.
+    net_versus=(own_rel, opp_rel) with net_opponent=weights (with net=weights; net_seats left out; with net_worlds, net_depth and
+    net_halving): the playouts seat TWO networks relative to the player's seat (tarok_playout_cards_net_versus) — `net` on the
+    relative seats of own_rel, net_opponent on those of opp_rel, the Bot elsewhere; (1, 14): the player models the whole table
+    as net_opponent and plays `net` against it.  net_opponent may be left out where opp_rel is 0.  None (the default): the
+    calls as they were.
     The same five duplicate passes (PASS_SEATS) on an env of its own; returns duplicate_advantage's dict, `policy_mean`
     being the playout player's.  inspect (tests): a list that receives one dict per pass, as in _play_passes_mode."""
     return duplicate_advantage(_playout_passes(samples, n_games, episodes, seed, mix, device, salt=salt, inspect=inspect,
@@ -493,7 +510,9 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
                                                threshold=threshold, contracts=contracts, pass_value=pass_value, net=net,
                                                net_seats=net_seats, net_worlds=net_worlds, net_depth=net_depth,
                                                net_value_scale=net_value_scale, **({} if halving is None else dict(halving=halving)),
-                                               **({} if net_halving is None else dict(net_halving=net_halving))))
+                                               **({} if net_halving is None else dict(net_halving=net_halving)),
+                                               **({} if net_versus is None and net_opponent is None
+                                                  else dict(net_versus=net_versus, net_opponent=net_opponent))))
 
 
 def _front_cards(cards):

@@ -13,7 +13,7 @@ from . import karte as K
 WORLDS = ("det", "voids", "hidden")               # the fair world kinds; the position is tarok_playout_cards_net_value's `kind`
 WORDS_DTYPE = dict(voids=torch.int32, hidden=torch.int64)      # the per-game words a kind reads: shown_voids() / played_cards()
 OPTIONS = ("samples", "worlds", "voids", "hidden", "exchange", "bidding", "net", "net_seats", "net_worlds", "net_depth", "net_value_scale",
-           "halving", "net_halving")
+           "halving", "net_halving", "net_versus")
 
 
 def spelling(prefix="", pattern="%s", **other):
@@ -77,6 +77,16 @@ def check_halving(halving, say=spelling(), option="{halving}"):
     if not ok or sum(halving) > K.PLAYOUT_MAX_WORLDS:
         raise ValueError(say(option + ": 1..%d positive world counts, one per round, at most %d in all" % (K.PLAYOUT_MAX_ROUNDS, K.PLAYOUT_MAX_WORLDS)))
     return tuple(int(w) for w in halving)
+
+
+def check_versus(net_versus, say=spelling()):
+    """The roles of a two-network net playout as (own_rel, opp_rel): two disjoint 4-bit sets over the seats RELATIVE to the
+    viewer (bit r: the seat r places after the viewer; bit 0 the viewer itself) — network A's seats and network B's."""
+    ok = isinstance(net_versus, (tuple, list)) and len(net_versus) == 2 and \
+        all(isinstance(r, numbers.Integral) and not isinstance(r, bool) and 0 <= r <= 15 for r in net_versus)
+    if not ok or net_versus[0] & net_versus[1]:
+        raise ValueError(say("{net_versus}: (own_rel, opp_rel), two disjoint 4-bit sets (0..15) over the seats relative to the viewer"))
+    return int(net_versus[0]), int(net_versus[1])
 
 
 class CardPlayer(collections.namedtuple("CardPlayer", "kind worlds samples net net_seats depth value_scale salt")):
@@ -147,9 +157,35 @@ class NetHalvingPlayer(collections.namedtuple("NetHalvingPlayer", CardPlayer._fi
                                              action_out=action_out, **sets)
 
 
+class VersusPlayer(collections.namedtuple("VersusPlayer", CardPlayer._fields + ("halving", "versus"))):
+    """A CardPlayer of a fair kind whose playouts seat TWO networks relative to each game's viewer (tarok_playout_cards_net_versus,
+    DESIGN 8.24): versus = (own_rel, opp_rel), the relative seats of the player's own network and of the opponent's; net_seats is
+    not read.  halving: None, or the worlds of every round (tarok_playout_cards_net_versus_halving: the rows then have a count
+    per card, as a NetHalvingPlayer's)."""
+    __slots__ = ()
+
+    needs_history, words_dtype, playouts = CardPlayer.needs_history, CardPlayer.words_dtype, CardPlayer.playouts
+
+    def prepare(self, env):
+        """The launch's scratch, before the launch is captured into a graph."""
+        if self.halving is None:
+            env.playout_net_scratch(self.worlds)
+        else:
+            env.playout_net_halving_scratch(self.halving)
+
+    def launch(self, env, weights, opponent, sets, words, sum_out, action_out, count_out=None):
+        """As CardPlayer.launch, on the six tensors of the player's network and the six of the opponent's (None where opp_rel
+        is 0).  Returns (sum, action), or with a schedule (sum, count, action)."""
+        more = {} if self.halving is None else dict(count_out=count_out)
+        return env.playout_cards_net_versus(weights, opponent, self.worlds, self.versus[0], self.versus[1], depth=self.depth,
+                                            value_scale=self.value_scale, voids=self.kind == "voids", hidden=self.kind == "hidden",
+                                            words=words, halving=self.halving, salt=self.salt, sum_out=sum_out, action_out=action_out,
+                                            **more, **sets)
+
+
 def card_player(samples=None, worlds=None, voids=False, hidden=False, net=False, net_seats=15, net_worlds="det", net_depth=None,
                 net_value_scale=70.0, salt=0, front=False, fused=True, history=None, own=True, say=spelling(), halving=None,
-                net_halving=None):
+                net_halving=None, net_versus=None):
     """The one validator of a card player's options, in evaluate_playout_vs_bot's names: a CardPlayer, or a ValueError in
     the door's words (say: spelling()).  samples None: 1.  front: the door also asked for a playout-valued exchange or
     bidding.  fused: the door's policy is the fused one.  history: whether the env at hand keeps the play history (None:
@@ -159,7 +195,16 @@ def card_player(samples=None, worlds=None, voids=False, hidden=False, net=False,
     exchange, the bidding or open hands.
     net_halving: such a tuple for the NET-played launch (a NetHalvingPlayer, tarok_playout_cards_net_halving): it requires
     net=, names the worlds itself as halving does, goes with net_worlds and net_depth, and takes what net= takes — samples
-    None or 1, no exchange, no bidding.  halving= together with net= keeps raising."""
+    None or 1, no exchange, no bidding.  halving= together with net= keeps raising.
+    net_versus: (own_rel, opp_rel) — a VersusPlayer (tarok_playout_cards_net_versus): the playouts seat the player's network on
+    the relative seats of own_rel and an opponent's on those of opp_rel, relative to each game's viewer.  It requires net=, goes
+    with net_worlds, net_depth and net_halving, and seats the networks itself: net_seats stays at its default."""
+    if net_versus is not None:
+        net_versus = check_versus(net_versus, say)
+        if not net:
+            raise ValueError(say("{net_versus}= seats two networks inside the network's playouts: it goes with {net}="))
+        if net_seats != 15:
+            raise ValueError(say("{net_versus}= seats the networks itself, relative to the viewer: leave {net_seats} out"))
     if halving is not None:
         halving = check_halving(halving, say)
         if net or front:
@@ -205,6 +250,8 @@ def card_player(samples=None, worlds=None, voids=False, hidden=False, net=False,
     if kind in WORDS_DTYPE and history is not None and not history:
         raise ValueError(say("the %s worlds read the play history: TarokVecEnv(history=True)" % kind))
     player = CardPlayer(kind, worlds, samples, bool(net), net_seats, net_depth, float(net_value_scale), int(salt))
+    if net_versus is not None:
+        return VersusPlayer(*player, net_halving, net_versus)
     if net_halving is not None:
         return NetHalvingPlayer(*player, net_halving)
     return player if halving is None else HalvingPlayer(*player, halving)

@@ -304,6 +304,12 @@ class SelfPlay:
     compacted item list (tarok_playout_cards_net_halving, DESIGN 8.21: `worlds` omitted, None or their sum; with net_seats,
     net_worlds and depth as above) and the rows come from tarok_playout_targets_counts.  The launch's scratch and the counts
     buffer are allocated before capture; a replayed graph reads the live rollout weights.
+    teacher = dict(net=True, worlds=W, versus=(own_rel, opp_rel), ...) with opponent=<one snapshot>: the teacher's playouts seat
+    TWO networks relative to each game's mover (tarok_playout_cards_net_versus) — the learner's live rollout
+    weights on the relative seats of own_rel, the frozen opponent's tensors on those of opp_rel —, inside the captured rollout;
+    (1, 14) makes the targets a search against the opponent actually at the table, and set_opponent() is picked up without a
+    new capture.  It goes with net_worlds, depth and net_halving; net_seats is left out.  Without opponent=, or with a pool: a
+    ValueError.
 
     front = dict(bid=, exchange=, contracts=, margin=, pass_value=, every=1): the games auto-reset swaps in are bid and
     exchanged by the heads instead of the Bot (TarokVecEnv.front_lines).  bid / exchange: six tensors each
@@ -337,27 +343,33 @@ class SelfPlay:
         self.teacher, self._player, self.distill_coef = None, None, float(distill_coef)
         if teacher is not None:                       # the card player is playout.card_player's; tau and every are the teacher's own
             unknown = set(teacher) - {"worlds", "samples", "tau", "every", "salt", "voids", "hidden", "net", "net_seats", "net_worlds", "depth",
-                                      "halving", "net_halving"}
+                                      "halving", "net_halving", "versus"}
             net = bool(teacher.get("net", False))
             if unknown or ("samples" not in teacher and not net and "halving" not in teacher):
                 raise ValueError("teacher: dict(worlds=W, samples=S, tau=tau, every=k, salt=...) or dict(halving=(w0, ..), ...): samples "
                                  "required unless net=True or halving= is given; unknown keys %s" % sorted(unknown))
             if "net_seats" in teacher and not net:
                 raise ValueError("teacher: net_seats names the network's seats inside the playouts: it goes with net=True")
+            versus = teacher.get("versus")
+            if versus is not None and (opponent is None or pool):
+                raise ValueError("teacher: versus=(own_rel, opp_rel) seats the frozen opponent inside the teacher's playouts: it goes with "
+                                 "opponent= (ONE snapshot(), not a pool)")
             p = playout.card_player(int(teacher.get("samples", 1)), int(teacher.get("worlds") or 0), bool(teacher.get("voids", False)),
                                     bool(teacher.get("hidden", False)), net, int(teacher.get("net_seats", 15)), teacher.get("net_worlds", "det"),
                                     teacher.get("depth"), 1.0 / reward_scale if reward_scale else 0.0, int(teacher.get("salt", 0)),
                                     fused=(hidden == 256) if fused is None else bool(fused), history=getattr(env, "history", False), own=False,
                                     say=playout.spelling("teacher: ", net_depth="depth", net_value_scale="1 / reward_scale"),
                                     **({"halving": teacher["halving"]} if "halving" in teacher else {}),
-                                    **({"net_halving": teacher["net_halving"]} if teacher.get("net_halving") is not None else {}))
+                                    **({"net_halving": teacher["net_halving"]} if teacher.get("net_halving") is not None else {}),
+                                    **({} if versus is None else {"net_versus": versus}))
             tau, every = float(teacher.get("tau", 1.0)), int(teacher.get("every", 1))
             if not (every >= 1 and 0.0 <= tau < float("inf")):
                 raise ValueError("teacher: tau >= 0 and finite, every >= 1")
             self._player = p                          # self.teacher: the same player as the dict it has always been
             self.teacher = dict(worlds=p.worlds, samples=p.samples, tau=tau, every=every, salt=p.salt, voids=p.kind == "voids" and not net,
                                 hidden=p.kind == "hidden" and not net, net=net, net_seats=p.net_seats, net_worlds=p.kind if net else "det",
-                                **({} if p.depth is None else dict(depth=p.depth)), **({} if p.halving is None else {"net_halving" if net else "halving": p.halving}))
+                                **({} if p.depth is None else dict(depth=p.depth)), **({} if p.halving is None else {"net_halving" if net else "halving": p.halving}),
+                                **({} if versus is None else dict(versus=p.versus)))
         elif distill_coef:
             raise ValueError("distill_coef weighs the playout teacher's term: pass teacher= as well")
         self.env = env
@@ -715,14 +727,17 @@ class SelfPlay:
 
     def _teach(self, t):
         """The teacher's rows of lock-step t: one playout launch on the learner's seats from the env's current positions,
-        one tarok_playout_targets on the words of that lock-step.  Stream-ordered, read-only on the env, no allocation."""
+        one tarok_playout_targets on the words of that lock-step.  Stream-ordered, read-only on the env, no allocation.
+        A versus teacher's launch reads the live rollout weights as network A and the frozen opponent's own tensors (the ones
+        set_opponent writes in place) as network B."""
+        nets = (self._w, self._opp) if "versus" in self.teacher else (self._w,)
         if self._player.halving is not None:          # one halving launch, one tarok_playout_targets_counts on its counts
-            self._player.launch(self.env, self._w, dict(seats_per_game=self._seats), self._teach_words, self._teach_sums, self._teach_act,
+            self._player.launch(self.env, *nets, dict(seats_per_game=self._seats), self._teach_words, self._teach_sums, self._teach_act,
                                 count_out=self._teach_counts)
             self.env.playout_targets_counts(self._teach_sums, self._teach_counts, self._buf["words"][t], self.teacher["tau"],
                                             seats_per_game=self._seats, target_out=self._buf["teach"][t])
             return
-        self._player.launch(self.env, self._w, dict(seats_per_game=self._seats), self._teach_words, self._teach_sums, self._teach_act)
+        self._player.launch(self.env, *nets, dict(seats_per_game=self._seats), self._teach_words, self._teach_sums, self._teach_act)
         self.env.playout_targets(self._teach_sums, self._buf["words"][t], self._player.playouts, self.teacher["tau"], seats_per_game=self._seats,
                                  target_out=self._buf["teach"][t])
 
