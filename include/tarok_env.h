@@ -1116,6 +1116,49 @@ int tarok_playout_cards_net_versus_halving(tarok_env *env, int kind, const void 
                                            int64_t scratch_bytes, int32_t *sum_out, int32_t *count_out, uint8_t *action_out,
                                            void *stream);
 
+/* SAMPLED net playouts: tarok_playout_cards_net_versus (dense; the three world kinds; viewer-relative roles;
+ * the optional value stop) whose networks play as they play AT THE TABLE — each under a play mode of its own — and with
+ * `samples` playouts per (legal card, world).
+ * ITEMS.  One item per (game g, rank j, world w, sample k), samples in 1..TAROK_PLAYOUT_MAX_SAMPLES, numbered
+ *   item = ((g * 12 + j) * worlds + w) * samples + k.
+ * All samples of a world start from the same dealt position (the world is dealt once, under the launches' wkey).  Item k's key
+ * is the item key of the net launches with k in its ten low bits, which every other net item kernel leaves 0:
+ *   ikey = game_key(seed ^ salt, offset + g, 3 << 62 | episode << 28 | played << 22 | card << 16 | w << 10 | k),
+ * the pkey of tarok_playout_cards_det / _voids / _hidden(worlds, samples).
+ * PLAY MODES.  (temperature_a, epsilon_a) is network A's and (temperature_b, epsilon_b) network B's: the two arguments of
+ * tarok_set_play_mode, taken with its validation and its conversion (inv_t = 1 / temperature, greedy at temperature 0,
+ * thr = floor(epsilon * 2^24), eps = thr / 2^24).  Inside a playout, after the candidate card, the seat to move at q cards
+ * played, at relative seat r, plays
+ *   - r in own_rel: what the table's sampler gives on tarok_policy_mlp's 54 card logits of A (bit for bit) on the playout's
+ *     own position, with key = ikey, played = q and A's mode: the tempered inverse-CDF draw on spec RNG draw 192 + q (the
+ *     lowest-numbered legal card at the maximum at temperature 0) — unless A's coin, draw 256 + q, says explore
+ *     ((coin >> 8) < thr): then the Bot's card policy_action(ikey, q, legal);
+ *   - r in opp_rel: the same with B and B's mode;
+ *   - r in neither: the Bot's card policy_action(ikey, q, legal), as before.
+ * The three draws of a position use counters 128 + q, 192 + q and 256 + q of one key: they are independent.
+ * The value stop (depth > 0) reads output 54 of the viewer's own network exactly as tarok_playout_cards_net_versus does; no
+ * mode touches it.  The env's own play mode is neither read nor written.
+ * OUTPUTS.  sum_out [N,12,4] i32 is the sum over the worlds x samples items of a row; action_out [N] u8 follows
+ * card_epilogue's rule on it, as in every card launch.  Scratch: 48 bytes per item,
+ * tarok_playout_cards_net_sampled_scratch(env, worlds, samples); TAROK_EINVAL where worlds or samples are out of range or
+ * the count reaches 2^31 items.  Three launches (items, playouts, sums) on `stream`; nothing is allocated, nothing read by the
+ * host; both weight sets are read when the launches RUN.
+ * Consequences, byte for byte: samples = 1 with both temperatures 0 and both epsilons 0 is tarok_playout_cards_net_versus;
+ * (own_rel, opp_rel) = (0, 0) at any modes, and epsilon 1 on both networks at any roles, is tarok_playout_cards_det / _voids /
+ * _hidden(worlds, samples) (where nothing stops, depth 0 or 12; with a stop, the (0, 0) rows of the same depth); (15, 0) at temperature 0 and epsilon 0 with S samples gives S x the samples = 1 rows; equal A
+ * and B under equal modes give (15, 0)'s rows for any split of the four seats.
+ * TAROK_EINVAL (before any HIP call) for everything tarok_playout_cards_net_versus refuses, samples outside
+ * 1..TAROK_PLAYOUT_MAX_SAMPLES, an item count of 2^31 or more, and a temperature or epsilon tarok_set_play_mode refuses (NaN,
+ * epsilon outside [0, 1], temperature < 0, in (0, 1e-6) or > 1e6) — B's mode is checked also where opp_rel = 0. */
+int64_t tarok_playout_cards_net_sampled_scratch(const tarok_env *env, int worlds, int samples);
+int tarok_playout_cards_net_sampled(tarok_env *env, int worlds, int samples, uint64_t salt, int seats,
+                                    const uint8_t *seats_per_game, int kind, const void *words, int own_rel, int opp_rel,
+                                    int depth, float value_scale, float temperature_a, float epsilon_a, float temperature_b,
+                                    float epsilon_b, const void *w1, const float *b1, const void *w2, const float *b2,
+                                    const void *w3, const float *b3, const void *v1, const float *c1, const void *v2,
+                                    const float *c2, const void *v3, const float *c3, void *scratch, int64_t scratch_bytes,
+                                    int32_t *sum_out, uint8_t *action_out, void *stream);
+
 /* Net-played playouts for the exchange and the bid: tarok_playout_exchange and tarok_playout_bids at ONE playout per
  * (candidate or option, world), played as tarok_playout_cards_net plays its playouts — the network's greedy card on the
  * absolute seats of net_seats (one launch-wide 4-bit set), the Bot's card policy_action(pkey, q, legal) on the others.

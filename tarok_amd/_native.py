@@ -46,6 +46,7 @@ SYMBOLS = [
     "tarok_playout_exchange_net_halving_scratch_bytes", "tarok_playout_exchange_net_halving",
     "tarok_playout_bids_net_halving_scratch_bytes", "tarok_playout_bids_net_halving",
     "tarok_playout_cards_net_versus", "tarok_playout_cards_net_versus_halving",
+    "tarok_playout_cards_net_sampled_scratch", "tarok_playout_cards_net_sampled",
 ]
 
 
@@ -225,6 +226,10 @@ def lib():
     L.tarok_playout_cards_net_versus.argtypes = [vp, i32, u64, i32, vp, i32, vp, i32, i32, i32, f32] + [vp] * 12 + [vp, i64, vp, vp, vp]
     L.tarok_playout_cards_net_versus_halving.restype = i32
     L.tarok_playout_cards_net_versus_halving.argtypes = [vp, i32, vp, i32, vp, u64, i32, vp, i32, i32] + [vp] * 12 + [i32, f32, vp, i64, vp, vp, vp, vp]
+    # tarok_playout_cards_net_versus with samples after worlds and the two play modes (t_a, eps_a, t_b, eps_b) before A's arrays
+    L.tarok_playout_cards_net_sampled_scratch.restype = i64; L.tarok_playout_cards_net_sampled_scratch.argtypes = [vp, i32, i32]
+    L.tarok_playout_cards_net_sampled.restype = i32
+    L.tarok_playout_cards_net_sampled.argtypes = [vp, i32, i32, u64, i32, vp, i32, vp, i32, i32, i32, f32] + [f32] * 4 + [vp] * 12 + [vp, i64, vp, vp, vp]
     L.tarok_playout_exchange_net_list_scratch.restype = i64; L.tarok_playout_exchange_net_list_scratch.argtypes = [vp, i32, i32]
     L.tarok_playout_exchange_net_list.restype = i32  # tarok_playout_exchange_net_value's arguments; depth 0: to the last card
     L.tarok_playout_exchange_net_list.argtypes = [vp, i32, i32, u64, i32, vp, i32, i32, f32] + [vp] * 6 + [vp, i64, vp, vp, vp, vp]

@@ -719,6 +719,23 @@ TK_HOST_DEVICE __forceinline__ bool net_versus_roles_ok(int own_rel, int opp_rel
     return own_rel >= 0 && own_rel <= 15 && opp_rel >= 0 && opp_rel <= 15 && !(own_rel & opp_rel);
 }
 
+// The items of tarok_playout_cards_net_sampled (include/tarok_env.h): a game's slots are (rank j, world w, sample k), sample
+// fastest — slot = (j * worlds + w) * samples + k, item = g * slots + slot — so a row's worlds x samples results are
+// contiguous for the sum kernel.  The item kernels and tests/host_emu/net_sampled_host.cpp share these.
+TK_HOST_DEVICE __forceinline__ u32 net_sampled_slots(u32 worlds, u32 samples) { return 12u * worlds * samples; }
+TK_HOST_DEVICE __forceinline__ u32 net_sampled_slot(u32 j, u32 w, u32 k, u32 worlds, u32 samples) { return (j * worlds + w) * samples + k; }
+TK_HOST_DEVICE __forceinline__ void net_sampled_split(u32 slot, u32 worlds, u32 samples, u32 &j, u32 &w, u32 &k) {
+    const u32 jw = slot / samples;
+    k = slot - jw * samples;
+    j = jw / worlds;
+    w = jw - j * worlds;
+}
+// the dense item count, or -1 where it reaches 2^31 (the entry's TAROK_EINVAL)
+TK_HOST_DEVICE __forceinline__ int64_t net_sampled_items(int64_t n, u32 worlds, u32 samples) {
+    const int64_t items = n * (int64_t)net_sampled_slots(worlds, samples);
+    return items < (1LL << 31) ? items : -1;
+}
+
 // Determinization (tarok_playout_cards_det, include/tarok_env.h): one WORLD of the seat `mover` — the cards it cannot
 // see, P = the hands of the three other seats, are dealt afresh among those seats, uniformly over the deals that keep
 // the hand sizes.  The cards of P are walked in ascending card number; card i of the walk draws

@@ -3553,12 +3553,16 @@ __global__ __launch_bounds__(2 * TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_policy_
 // hidden world's item is the packed Game whose C plane and talon ids moved: the second launch unpacks all of it.
 // VIEWER (tarok_playout_cards_net_value): a live item's marker carries the viewer — the seat to move in the env's position —
 // in its two low bits (lane 0 is -32768 + viewer: no score is near).
-template <class Dealer, bool VIEWER = false>
+// SAMPLED (tarok_playout_cards_net_sampled): `samples` items per (rank, world), numbered by net_sampled_slot
+// (tarok_device.h); a world's samples load the same world slot — the team's layout stays sized by `worlds` — and sample k's
+// key is the item key with k in its ten low bits, the pkey of playout_cards_body.  Without it `samples` is not read.
+template <class Dealer, bool VIEWER = false, bool SAMPLED = false>
 __device__ __forceinline__ void playout_net_deal_body(int64_t n, u64 pseed, u64 offset, u32 worlds, u32 lg, u32 seats,
                                                       const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,
                                                       const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt,
                                                       const typename Dealer::Extra *__restrict__ extra, ulonglong2 *__restrict__ i01,
-                                                      ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires) {
+                                                      ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey, u64 *__restrict__ ires,
+                                                      u32 samples = 1) {
     __shared__ typename Dealer::Record world;
     const PlayoutTeam t(lg, worlds);
     const int64_t g = t.g;
@@ -3584,10 +3588,11 @@ __device__ __forceinline__ void playout_net_deal_body(int64_t n, u64 pseed, u64 
     }
     __syncthreads();
     if (g < n) {
-        const u32 slots = TAROK_PLAYOUT_RANKS * worlds;
+        const u32 slots = SAMPLED ? net_sampled_slots(worlds, samples) : TAROK_PLAYOUT_RANKS * worlds;
         for (u32 i = t.lane; i < slots; i += t.L) {
             const int64_t it = g * (int64_t)slots + i;
-            const u32 j = i / worlds, w = i - j * worlds;
+            u32 j = i / worlds, w = i - j * worlds, k = 0;
+            if constexpr (SAMPLED) net_sampled_split(i, worlds, samples, j, w, k);
             u64 res = 0;
             if (j < nlegal) {                            // (nlegal = 0 for a game that does not take part)
                 const u32 c = kth_bit(p.legal, j);
@@ -3603,7 +3608,7 @@ __device__ __forceinline__ void playout_net_deal_body(int64_t n, u64 pseed, u64 
                     pack(h, x0, x1, y0, y1);
                     i01[it] = make_ulonglong2(x0, x1);
                     i23[it] = make_ulonglong2(y0, y1);
-                    ikey[it] = game_key(pseed, offset + (u64)g, Dealer::item_tag | ebase | ((u64)c << 16) | ((u64)w << 10));
+                    ikey[it] = game_key(pseed, offset + (u64)g, Dealer::item_tag | ebase | ((u64)c << 16) | ((u64)w << 10) | (u64)k);
                 }
             }
             ires[it] = res;
@@ -3634,6 +3639,23 @@ TK_NET_DEAL(k_playout_net_deal_value, DealUnseen, true, nullptr, )
 TK_NET_DEAL(k_playout_net_deal_value_voids, DealVoids, true, voids, const u32 *__restrict__ voids, )
 TK_NET_DEAL(k_playout_net_deal_value_hidden, DealHidden, true, played_words, const u64 *__restrict__ played_words, )
 #undef TK_NET_DEAL
+
+// tarok_playout_cards_net_sampled's first launches: the three VIEWER dealers over (rank, world, sample) items; `samples` comes
+// last, after the item arrays.
+#define TK_NET_DEAL_SAMPLED(NAME, DEALER, WORDS, ...)                                                                              \
+    TK_KERNEL(TK_BLOCK, 128) void NAME(int64_t n, u64 pseed /* seed ^ salt */, u64 offset, u32 worlds, u32 lg, u32 seats,           \
+                                      const uint8_t *__restrict__ seat_sets, const ulonglong2 *__restrict__ s01,                    \
+                                      const ulonglong2 *__restrict__ s23, const Counters *__restrict__ cnt, __VA_ARGS__             \
+                                      ulonglong2 *__restrict__ i01, ulonglong2 *__restrict__ i23, u64 *__restrict__ ikey,           \
+                                      u64 *__restrict__ ires, u32 samples) {                                                        \
+        TK_VGPR_TOP(128, 127);                                                                                                      \
+        playout_net_deal_body<DEALER, true, true>(n, pseed, offset, worlds, lg, seats, seat_sets, s01, s23, cnt, WORDS, i01, i23,   \
+                                                  ikey, ires, samples);                                                             \
+    }
+TK_NET_DEAL_SAMPLED(k_playout_net_deal_sampled, DealUnseen, nullptr, )
+TK_NET_DEAL_SAMPLED(k_playout_net_deal_sampled_voids, DealVoids, voids, const u32 *__restrict__ voids, )
+TK_NET_DEAL_SAMPLED(k_playout_net_deal_sampled_hidden, DealHidden, played_words, const u64 *__restrict__ played_words, )
+#undef TK_NET_DEAL_SAMPLED
 
 // Second launch: the playouts.  A workgroup of 256 threads keeps one tile of PM_M = 128 items resident — their packed
 // states and keys in LDS, owned by threads 0..127 — and plays them card by card: feature words (policy_feature_words on
@@ -3675,23 +3697,39 @@ TK_NET_DEAL(k_playout_net_deal_value_hidden, DealHidden, true, played_words, con
 //   - the forward runs once per set pass bit — X re-expanded from ext each time, the third barrier of a pass keeps the
 //     next pass's expansion off the logits being read — and in pass P a row's half == 0 lane writes act_s only where the
 //     row's role is P, val_s only where the row stops and P is the viewer's network.  No barrier is in a divergent branch.
-template <bool VALUE, bool VERSUS = false>
+//
+// MODE = 1 (k_playout_net_play_sampled*, tarok_playout_cards_net_sampled; under VERSUS only): a network seat
+// plays what the table's sampler gives under ITS network's PlayMode — ma for role A, mb for role B — with the item's key and
+// the row's cards played q: the tempered draw (or the greedy card), and the Bot's card where the mode's coin says explore.
+// What changes in the invariants above, and nothing else:
+//   - waves 0 and 1 write each row's q to q_s[row], the third part of act_s, with its role, before the round's first
+//     barrier (0 for a dead row); the votes, the two parities, the 48 rounds and the pass tests are VERSUS';
+//   - in pass P the sampler runs with P's mode, picked by scalar selects on the pass number like the weight pointers, on
+//     in.key = keys[row], in.played = q_s[row] and in.last as policy_sample_inputs sets it.  EVERY thread runs it whatever
+//     its row's role: policy_sample's partner reads (pm_swap) — the greedy ones and MODE's — are all inside it, none
+//     in a select or a branch here;
+//   - the exploring card replaces the drawn one on the half == 0 lane, which holds the whole pick, before act_s is
+//     written; the value read for a stop is untouched by the mode.  No barrier is added.
+template <bool VALUE, bool VERSUS = false, int MODE = 0>
 __device__ __forceinline__ void playout_net_play_body(int64_t items, u32 net_seats, u32 depth, float value_scale,
                                                       const ulonglong2 *__restrict__ i01, const ulonglong2 *__restrict__ i23,
                                                       const u64 *__restrict__ ikey, u64 *__restrict__ ires,
                                                       const __bf16 *__restrict__ w1, const float *__restrict__ b1,
                                                       const __bf16 *__restrict__ w2, const float *__restrict__ b2,
                                                       const __bf16 *__restrict__ w3, const float *__restrict__ b3,
-                                                      u32 own_rel = 0, u32 opp_rel = 0, const PolicyWeights &wb = PolicyWeights{}) {
+                                                      u32 own_rel = 0, u32 opp_rel = 0, const PolicyWeights &wb = PolicyWeights{},
+                                                      const PlayMode &ma = PlayMode{}, const PlayMode &mb = PlayMode{}) {
+    static_assert(!MODE || VERSUS, "a play mode per network is the VERSUS body's");
     constexpr bool MARKED = VALUE || VERSUS;             // a live item's marker carries its viewer
     __shared__ __attribute__((aligned(16))) __bf16 X[PM_M * PM_LD];
     __shared__ __attribute__((aligned(16))) u64 ext[PM_M][4];
     __shared__ __attribute__((aligned(16))) u64 st[PM_M][4];
     __shared__ u64 keys[PM_M];
-    __shared__ uint8_t act_s[VERSUS ? 2 * PM_M : PM_M];
+    __shared__ uint8_t act_s[MODE ? 3 * PM_M : VERSUS ? 2 * PM_M : PM_M];
     __shared__ u32 vote[2][2];
     __shared__ float val_s[VALUE ? PM_M : 1];
     uint8_t *role_s = act_s + (VERSUS ? PM_M : 0);       // (VERSUS only)
+    uint8_t *q_s = act_s + (MODE ? 2 * PM_M : 0);        // (MODE only)
     const u32 tid = threadIdx.x, wave = tid >> 6;
     const int64_t it = (int64_t)blockIdx.x * PM_M + tid;
     float *L = reinterpret_cast<float *>(X);
@@ -3724,6 +3762,7 @@ __device__ __forceinline__ void playout_net_play_body(int64_t items, u32 net_sea
                     const u32 need = stop ? net_versus_viewer_net(opp_rel) : role;
                     net = need == 1u; net_b = need == 2u;
                     role_s[tid] = (uint8_t)(role | (stop ? 4u : 0u));
+                    if constexpr (MODE) q_s[tid] = (uint8_t)(h.trick_no * 4 + h.nt);
                 } else {
                     net = (net_seats >> ((h.leader + h.nt) & 3)) & 1u;
                     if constexpr (VALUE) {
@@ -3733,6 +3772,7 @@ __device__ __forceinline__ void playout_net_play_body(int64_t items, u32 net_sea
             } else {
                 ext[tid][0] = 0; ext[tid][1] = 0; ext[tid][2] = 0; ext[tid][3] = 0;
                 if constexpr (VERSUS) role_s[tid] = 0;
+                if constexpr (MODE) q_s[tid] = 0;
             }
             const u64 any_live = __ballot(live), any_net = __ballot(live && net);
             if constexpr (VERSUS) {
@@ -3770,9 +3810,18 @@ __device__ __forceinline__ void playout_net_play_body(int64_t items, u32 net_sea
                 in.m = ext[gi][1] & TAROK_OBS_MASK;
                 in.o = in.m; in.key = 0; in.played = 0; in.last = 0;
                 in.mh = (u32)(in.m >> (27 * half)) & 0x7FFFFFFu;
-                const PolicyPick c = policy_sample<1>(L, gi, half, in, PlayMode{1.f, 1, 0u, 0.f});
+                PlayMode pm = PlayMode{1.f, 1, 0u, 0.f};
+                if constexpr (MODE) {
+                    pm = PlayMode{pa ? ma.inv_t : mb.inv_t, pa ? ma.greedy : mb.greedy, pa ? ma.thr : mb.thr, pa ? ma.eps : mb.eps};
+                    in.key = keys[gi]; in.played = q_s[gi];
+                    in.last = in.m ? 63 - __clzll(in.m) : 0;
+                }
+                PolicyPick c = policy_sample<1>(L, gi, half, in, pm);
                 if (half == 0) {
                     const u32 rs = role_s[gi];
+                    if constexpr (MODE) {                  // the mode's coin: an exploring seat plays the Bot's card of the position
+                        if (in.m && pm.thr && (rng32(in.key, TK_DRAW_EXPLORE + in.played) >> 8) < pm.thr) c.pk = c.bc;
+                    }
                     if ((rs & 3u) == pass) act_s[gi] = (uint8_t)c.pk;
                     if constexpr (VALUE) {
                         if ((rs & 4u) && viewer_net == pass) val_s[gi] = c.v54;
@@ -3872,6 +3921,32 @@ __global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net
     TK_VGPR_TOP(256, 255);
     playout_net_play_body<true, true>(items, 0, depth, value_scale, i01, i23, ikey, ires, w1, b1, w2, b2, w3, b3, own_rel, opp_rel, wb);
 }
+
+// tarok_playout_cards_net_sampled's second launch: the VERSUS body under a play mode per network (MODE = 1); the two modes come
+// after network B, each as tarok_set_play_mode converts it.
+#define TK_PLAY_MODES_ARGS float inv_t_a, int greedy_a, u32 thr_a, float eps_a, float inv_t_b, int greedy_b, u32 thr_b, float eps_b
+#define TK_PLAY_MODES_NAMES PlayMode{inv_t_a, greedy_a, thr_a, eps_a}, PlayMode{inv_t_b, greedy_b, thr_b, eps_b}
+__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net_play_sampled(
+    int64_t items, u32 own_rel, const ulonglong2 *__restrict__ i01, const ulonglong2 *__restrict__ i23,
+    const u64 *__restrict__ ikey, u64 *__restrict__ ires, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3, const float *__restrict__ b3,
+    u32 opp_rel, PolicyWeights wb, TK_PLAY_MODES_ARGS) {
+    TK_VGPR_TOP(256, 255);
+    playout_net_play_body<false, true, 1>(items, 0, 0, 0.f, i01, i23, ikey, ires, w1, b1, w2, b2, w3, b3, own_rel, opp_rel, wb,
+                                          TK_PLAY_MODES_NAMES);
+}
+
+__global__ __launch_bounds__(TK_BLOCK, 2) TK_VGPR_BUDGET(256) void k_playout_net_play_sampled_value(
+    int64_t items, u32 own_rel, const ulonglong2 *__restrict__ i01, const ulonglong2 *__restrict__ i23,
+    const u64 *__restrict__ ikey, u64 *__restrict__ ires, const __bf16 *__restrict__ w1, const float *__restrict__ b1,
+    const __bf16 *__restrict__ w2, const float *__restrict__ b2, const __bf16 *__restrict__ w3, const float *__restrict__ b3,
+    u32 opp_rel, PolicyWeights wb, TK_PLAY_MODES_ARGS, u32 depth, float value_scale) {
+    TK_VGPR_TOP(256, 255);
+    playout_net_play_body<true, true, 1>(items, 0, depth, value_scale, i01, i23, ikey, ires, w1, b1, w2, b2, w3, b3, own_rel, opp_rel, wb,
+                                         TK_PLAY_MODES_NAMES);
+}
+#undef TK_PLAY_MODES_NAMES
+#undef TK_PLAY_MODES_ARGS
 
 // Third launch: 16 lanes per game; lane r < 12 sums rank r's items over the worlds in integers, then card_epilogue's
 // write-out on the game's position, as the det launch.
@@ -5657,10 +5732,11 @@ static inline bool depth_args_ok(int depth, int lo, int hi, float value_scale) {
 // last card; else the _value kernel, whose live items carry their viewers (the caller's item kernel is the _value form).
 // b non-NULL: the VERSUS kernels (tarok_playout_cards_net_versus) — w is network A, *b network B, own_rel / opp_rel the role
 // sets over the seats relative to each item's viewer, net_seats is not read, and the caller's item kernel is the _value form
-// at every depth.
+// at every depth.  modes non-NULL (with b, dense only: tarok_playout_cards_net_sampled): the SAMPLED kernels, modes[0] network A's
+// play mode and modes[1] network B's.
 static inline void launch_net_play(int64_t items, const u32 *total, int net_seats, const NetItems &it, const PolicyWeights &w,
                                    hipStream_t s, int depth, float value_scale, const PolicyWeights *b = nullptr, int own_rel = 0,
-                                   int opp_rel = 0) {
+                                   int opp_rel = 0, const PlayMode *modes = nullptr) {
     const int64_t tiles = net_list_tiles(items, PM_M);
     const dim3 grid((unsigned)(tiles ? tiles : 1));
 #define TK_LAUNCH_NET_PLAY(K, COUNT, ...)                                                                                          \
@@ -5668,7 +5744,12 @@ static inline void launch_net_play(int64_t items, const u32 *total, int net_seat
                        w.b2, w.w3, w.b3, ##__VA_ARGS__)
     if (b) {
         net_seats = own_rel;                             // (the VERSUS kernels take own_rel where the others take net_seats)
-        if (total) {
+        if (modes) {
+#define TK_MODES modes[0].inv_t, modes[0].greedy, modes[0].thr, modes[0].eps, modes[1].inv_t, modes[1].greedy, modes[1].thr, modes[1].eps
+            if (depth) TK_LAUNCH_NET_PLAY(k_playout_net_play_sampled_value, items, (u32)opp_rel, *b, TK_MODES, (u32)depth, value_scale);
+            else TK_LAUNCH_NET_PLAY(k_playout_net_play_sampled, items, (u32)opp_rel, *b, TK_MODES);
+#undef TK_MODES
+        } else if (total) {
             if (depth) TK_LAUNCH_NET_PLAY(k_playout_net_play_list_versus_value, total, (u32)opp_rel, *b, (u32)depth, value_scale);
             else TK_LAUNCH_NET_PLAY(k_playout_net_play_list_versus, total, (u32)opp_rel, *b);
         } else {
@@ -5690,27 +5771,41 @@ static inline void launch_net_play(int64_t items, const u32 *total, int net_seat
 // to the last card; else (checked by tarok_playout_cards_net_value, the only caller that gives one) they stop at the
 // viewer's depth-th decision, and `deal` is a k_playout_net_deal_value*.  b non-NULL (tarok_playout_cards_net_versus, which has
 // checked the roles): launch_net_play's VERSUS form, `deal` a k_playout_net_deal_value* at every depth.
-template <class Kernel, class Word>
+// SAMPLED (tarok_playout_cards_net_sampled, which has checked the roles and made the modes): `deal` is a
+// k_playout_net_deal_sampled*, which takes `samples` last; the items are (rank, world, sample), the scratch
+// tarok_playout_cards_net_sampled_scratch's, the play launch the SAMPLED kernels under modes[0..1], and k_playout_net_sum sums a
+// row's worlds x samples contiguous items.  The team layout (lg) stays the worlds'.
+template <bool SAMPLED = false, class Kernel, class Word>
 static int launch_playout_cards_net(Kernel deal, tarok_env *e, int worlds, uint64_t salt, int seats, const uint8_t *seats_per_game,
                                     const Word *words, int net_seats, const PolicyWeights &w, void *scratch, int64_t scratch_bytes,
                                     int32_t *sum_out, uint8_t *action_out, void *stream, int depth, float value_scale,
-                                    const PolicyWeights *b = nullptr, int own_rel = 0, int opp_rel = 0) {
+                                    const PolicyWeights *b = nullptr, int own_rel = 0, int opp_rel = 0, int samples = 1,
+                                    const PlayMode *modes = nullptr) {
     constexpr bool has_words = !std::is_same<Word, NoWord>::value;
-    if (!playout_args_ok(e, worlds, 1, seats) || !net_args_ok(net_seats, w, scratch, scratch_bytes, tarok_playout_net_scratch(e, worlds)) ||
+    if (!playout_args_ok(e, worlds, samples, seats) ||
+        !net_args_ok(net_seats, w, scratch, scratch_bytes,
+                     SAMPLED ? tarok_playout_cards_net_sampled_scratch(e, worlds, samples) : tarok_playout_net_scratch(e, worlds)) ||
         (!sum_out && !action_out) || (has_words && !words))
         return TAROK_EINVAL;
     HIPCHK(hipSetDevice(e->device));
-    const int64_t items = e->n * TAROK_PLAYOUT_RANKS * (int64_t)worlds;
+    const int64_t items = e->n * TAROK_PLAYOUT_RANKS * (int64_t)worlds * (int64_t)samples;
     const NetItems it(scratch, items);
     const u32 lg = playout_lg(TK_PO_MIN_LG, worlds);
     auto launch_deal = [&](auto... kwords) {
-        hipLaunchKernelGGL(deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
-                           (u32)worlds, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, kwords..., it.i01, it.i23, it.ikey, it.ires);
+        if constexpr (SAMPLED)
+            hipLaunchKernelGGL(deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
+                               (u32)worlds, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, kwords..., it.i01, it.i23, it.ikey,
+                               it.ires, (u32)samples);
+        else
+            hipLaunchKernelGGL(deal, playout_grid(e, lg), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, e->seed ^ (u64)salt, e->offset,
+                               (u32)worlds, lg, (u32)seats, seats_per_game, e->s01, e->s23, e->cnt, kwords..., it.i01, it.i23, it.ikey,
+                               it.ires);
     };
     if constexpr (has_words) launch_deal(words); else launch_deal();
-    launch_net_play(items, nullptr, net_seats, it, w, (hipStream_t)stream, depth, value_scale, b, own_rel, opp_rel);
-    hipLaunchKernelGGL(k_playout_net_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n, (u32)worlds,
-                       (u32)seats, seats_per_game, e->s01, e->s23, e->gkey, it.ires, reinterpret_cast<int4 *>(sum_out), action_out);
+    launch_net_play(items, nullptr, net_seats, it, w, (hipStream_t)stream, depth, value_scale, b, own_rel, opp_rel, SAMPLED ? modes : nullptr);
+    hipLaunchKernelGGL(k_playout_net_sum, dim3((unsigned)((e->n + 15) / 16)), dim3(TK_BLOCK), 0, (hipStream_t)stream, e->n,
+                       (u32)(worlds * samples), (u32)seats, seats_per_game, e->s01, e->s23, e->gkey, it.ires,
+                       reinterpret_cast<int4 *>(sum_out), action_out);
     HIPCHK(hipGetLastError());
     return TAROK_OK;
 }
@@ -6092,6 +6187,46 @@ int tarok_playout_cards_net_versus(tarok_env *e, int worlds, uint64_t salt, int 
         const auto deal = TK_OF_KIND(k, k_playout_net_deal_value, k_playout_net_deal_value_voids, k_playout_net_deal_value_hidden);
         return launch_playout_cards_net(deal, e, worlds, salt, seats, seats_per_game, kwords, 0, a, scratch, scratch_bytes, sum_out,
                                         action_out, stream, depth, value_scale, &b, own_rel, opp_rel);
+    });
+}
+
+int64_t tarok_playout_cards_net_sampled_scratch(const tarok_env *e, int worlds, int samples) {
+    if (!e || worlds < 1 || worlds > TAROK_PLAYOUT_MAX_WORLDS || samples < 1 || samples > TAROK_PLAYOUT_MAX_SAMPLES) return TAROK_EINVAL;
+    const int64_t items = net_sampled_items(e->n, (u32)worlds, (u32)samples);
+    return items < 0 ? (int64_t)TAROK_EINVAL : items * TK_PN_ITEM_BYTES;
+}
+
+// tarok_set_play_mode's checks and its conversion, for a mode that is an argument and not the env's.
+static bool play_mode_of(float temperature, float epsilon, PlayMode &pm) {
+    if (temperature != temperature || epsilon != epsilon) return false;
+    if (!(epsilon >= 0.f && epsilon <= 1.f)) return false;
+    if (temperature < 0.f || (temperature > 0.f && temperature < 1e-6f) || temperature > 1e6f) return false;
+    pm.greedy = temperature == 0.f;
+    pm.inv_t = pm.greedy ? 1.f : 1.0f / temperature;
+    pm.thr = (uint32_t)floor((double)epsilon * 16777216.0);
+    pm.eps = (float)pm.thr * (1.0f / 16777216.0f);
+    return true;
+}
+
+int tarok_playout_cards_net_sampled(tarok_env *e, int worlds, int samples, uint64_t salt, int seats, const uint8_t *seats_per_game,
+                                    int kind, const void *words, int own_rel, int opp_rel, int depth, float value_scale,
+                                    float temperature_a, float epsilon_a, float temperature_b, float epsilon_b, const void *w1,
+                                    const float *b1, const void *w2, const float *b2, const void *w3, const float *b3, const void *v1,
+                                    const float *c1, const void *v2, const float *c2, const void *v3, const float *c3, void *scratch,
+                                    int64_t scratch_bytes, int32_t *sum_out, uint8_t *action_out, void *stream) {
+    const PolicyWeights a = TK_WEIGHTS(w1, b1, w2, b2, w3, b3);
+    PolicyWeights b = TK_WEIGHTS(v1, c1, v2, c2, v3, c3);
+    PlayMode modes[2];
+    // (the scratch function refuses samples out of range and a count that reaches 2^31 items: the launcher's need is then < 0)
+    if (!world_kind_ok(kind) || (kind == TAROK_NET_WORLDS_DET && words) || !depth_args_ok(depth, 0, TAROK_PLAYOUT_MAX_DEPTH, value_scale) ||
+        !versus_args_ok(own_rel, opp_rel, a, b) || !play_mode_of(temperature_a, epsilon_a, modes[0]) ||
+        !play_mode_of(temperature_b, epsilon_b, modes[1]))
+        return TAROK_EINVAL;
+    if (depth == TAROK_PLAYOUT_MAX_DEPTH) depth = 0;     // never stops (§8.18)
+    return for_world_kind(kind, words, [&](auto k, auto *kwords) {
+        const auto deal = TK_OF_KIND(k, k_playout_net_deal_sampled, k_playout_net_deal_sampled_voids, k_playout_net_deal_sampled_hidden);
+        return launch_playout_cards_net<true>(deal, e, worlds, salt, seats, seats_per_game, kwords, 0, a, scratch, scratch_bytes, sum_out,
+                                              action_out, stream, depth, value_scale, &b, own_rel, opp_rel, samples, modes);
     });
 }
 

@@ -29,6 +29,7 @@ def _salt(salt):
 
 
 _SIZES = dict(worlds=(K.PLAYOUT_MAX_WORLDS, "worlds: 1..%d" % K.PLAYOUT_MAX_WORLDS),
+              samples=(K.PLAYOUT_MAX_SAMPLES, "samples: 1..%d" % K.PLAYOUT_MAX_SAMPLES),
               discard_sets=(K.EXCHANGE_MAX_SETS, "discard_sets: 1..%d" % K.EXCHANGE_MAX_SETS),
               contracts=(K.BID_ALL_CONTRACTS, "contracts: a bit set within 1..0x3FF"))
 
@@ -568,6 +569,43 @@ class TarokVecEnv:
                 _native.check(self.L.tarok_playout_cards_net_versus_halving(
                     self._h, P.WORLDS.index(kind), self._p(words), len(schedule), (C.c_int * len(schedule))(*schedule), *sets, own_rel,
                     opp_rel, *a, *b, depth, value_scale, *tail))
+        return tuple(outs)
+
+    def playout_net_sampled_scratch(self, worlds, samples):
+        """The scratch tensor of playout_cards_net_sampled at (worlds, samples) (uint8, tarok_playout_cards_net_sampled_scratch
+        bytes: 48 per item), cached on the env per shape: a caller that captures the launch asks for it BEFORE the capture."""
+        worlds, samples = _sizes(worlds=worlds, samples=samples)
+        return self._scratch(("cards_sampled", worlds, samples), self.L.tarok_playout_cards_net_sampled_scratch, worlds, samples)
+
+    def playout_cards_net_sampled(self, weights, opponent, worlds, samples, own_rel=15, opp_rel=0, temperature=1.0, epsilon=0.0,
+                                  opp_temperature=None, opp_epsilon=None, depth=None, value_scale=70.0, voids=False, hidden=False,
+                                  words=None, salt=0, seats=15, seats_per_game=None, sum_out=None, action_out=None):
+        """playout_cards_net_versus whose networks play as they play AT THE TABLE, `samples` playouts per (legal card, world)
+        (tarok_playout_cards_net_sampled).  The seats of own_rel play `weights` under the play mode (temperature,
+        epsilon), those of opp_rel play `opponent` under (opp_temperature, opp_epsilon) — each None: `weights`' value —, the
+        rest the Bot: set_play_mode's two numbers, with its checks — a draw from the softmax at the temperature (0: the greedy
+        card), and with probability epsilon the Bot's card instead —, on the draws of the item's own key, so a second sample of
+        a world is another playout.  The env's own play mode is neither read nor written.  All samples of a world start from
+        the same dealt position; the sums are over worlds * samples playouts (playout_values' divisor).  samples = 1 at
+        temperature 0 and epsilon 0 on both networks is playout_cards_net_versus to the byte; (0, 0), or epsilon 1 on both
+        networks, is playout_cards_det / _voids / _hidden(worlds, samples).  opponent may be None where opp_rel is 0.  depth /
+        value_scale, voids / hidden / words, seats / seats_per_game, salt and the outputs: as in playout_cards_net_versus; no
+        halving form.  The scratch is playout_net_sampled_scratch(worlds, samples).  Returns (sum, action)."""
+        own_rel, opp_rel = P.check_versus((own_rel, opp_rel), P.spelling(net_versus="(own_rel, opp_rel)"))
+        modes = P.check_play_modes(temperature, epsilon, opp_temperature, opp_epsilon)
+        kind, words = TarokVecEnv._world_words(self, True, voids, hidden, words)
+        _, depth, value_scale, a = TarokVecEnv._net_args(self, weights, 0, depth, value_scale)
+        if opponent is None and opp_rel:
+            raise ValueError("opp_rel seats the opponent's network: give its six tensors")
+        b = [None] * 6 if opponent is None else [self._p(t) for t in self.check_mlp_weights(opponent)]
+        scratch = self.playout_net_sampled_scratch(worlds, samples)
+        words = words()
+        with torch.cuda.device(self.device):
+            outs = TarokVecEnv._card_outputs(self, sum_out, action_out)
+            _native.check(self.L.tarok_playout_cards_net_sampled(
+                self._h, int(worlds), int(samples), _salt(salt), int(seats), self._p(self._seat_sets(seats_per_game)), P.WORLDS.index(kind),
+                self._p(words), own_rel, opp_rel, depth, value_scale, *modes, *a, *b, self._p(scratch), scratch.numel(),
+                *[self._p(t) for t in outs], self._stream()))
         return tuple(outs)
 
     def playout_exchange(self, worlds, samples, discard_sets=4, salt=0, seats=15, seats_per_game=None, sum_out=None,

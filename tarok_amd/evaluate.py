@@ -397,7 +397,7 @@ def _bid_args(bidding, mix):
 def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspect=None, worlds=None, voids=False, exchange=None,
                     hidden=False, bidding=None, threshold=0, contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None,
                     net_seats=15, net_worlds="det", net_depth=None, net_value_scale=70.0, halving=None, net_halving=None, net_versus=None,
-                    net_opponent=None):
+                    net_opponent=None, net_sampled=None):
     """_play_passes_mode with the Monte-Carlo player (TarokVecEnv.playout_cards) in the network's place: per lock-step
     one playout launch with the pass's seat set — tarok_playout_cards (open hands) for worlds=None,
     tarok_playout_cards_det (the fair player: `worlds` re-deals of the unseen cards) otherwise — whose action_out holds
@@ -425,11 +425,15 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     net_versus=(own_rel, opp_rel) (with net): the launch is playout_cards_net_versus — `net` on the relative seats of own_rel,
     net_opponent (six tensors; required where opp_rel is not 0) on those of opp_rel, relative to the player's seat in every
     game —, in the worlds of net_worlds, at net_depth and with net_halving's schedule where one is given.
+    net_sampled=dict(samples=, temperature=, epsilon=, opp_temperature=, opp_epsilon=) (with net, or with net and net_versus): the
+    launch is playout_cards_net_sampled — the networks play under those play modes, `samples` playouts per (card, world);
+    with net alone on the roles (15, 0).
     inspect: as in _play_passes_mode."""
     player = playout.card_player(samples, worlds, voids, hidden, net is not None, net_seats, net_worlds, net_depth, net_value_scale, salt,
                                  front=exchange is not None or bidding is not None, **({} if halving is None else dict(halving=halving)),
                                  **({} if net_halving is None else dict(net_halving=net_halving)),
-                                 **({} if net_versus is None else dict(net_versus=net_versus)))
+                                 **({} if net_versus is None else dict(net_versus=net_versus)),
+                                 **({} if net_sampled is None else dict(net_sampled=net_sampled)))
     if net_opponent is not None and net_versus is None:
         raise ValueError("net_opponent is the second network of net_versus=(own_rel, opp_rel): give that as well")
     if net_versus is not None and player.versus[1] and net_opponent is None:
@@ -445,7 +449,7 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     if bidding is not None and worlds is None:
         raise ValueError("bidding=(W, S) is the fair player's front end: give worlds= as well")
     bidding = _bid_args(bidding, mix)
-    nets = (net,) if net_versus is None else (net, net_opponent)
+    nets = (net,) if net_versus is None and net_sampled is None else (net, net_opponent)
     cards = _playout_cards(lambda env, seats, words, sums, row, **more: player.launch(env, *nets, dict(seats=seats), words, sums, row, **more),
                            words_dtype=player.words_dtype, **({} if player.halving is None else dict(counts=True)))
     front = _front(inspect is not None, bid=None if bidding is None else _bid_front(bidding, salt, threshold, contracts, pass_value),
@@ -456,7 +460,8 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
 def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, device=0, salt=0, inspect=None, worlds=None,
                             voids=False, exchange=None, hidden=False, bidding=None, threshold=0,
                             contracts=K.BID_DEFAULT_CONTRACTS, pass_value=False, net=None, net_seats=15, net_worlds="det",
-                            net_depth=None, net_value_scale=70.0, halving=None, net_halving=None, net_versus=None, net_opponent=None):
+                            net_depth=None, net_value_scale=70.0, halving=None, net_halving=None, net_versus=None, net_opponent=None,
+                            net_samples=None, net_temperature=None, net_epsilon=None, net_opp_temperature=None, net_opp_epsilon=None):
     """evaluate_vs_bot with the open-hand Monte-Carlo player in the network's place: a strong reference player that needs
     no training.  On its seat it plays, at every move, the legal card with the best summed score over `samples` Bot
     playouts of each legal card (tarok_playout_cards; `salt` varies their draws).  The playouts see the TRUE hidden
@@ -503,8 +508,15 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
     relative seats of own_rel, net_opponent on those of opp_rel, the Bot elsewhere; (1, 14): the player models the whole table
     as net_opponent and plays `net` against it.  net_opponent may be left out where opp_rel is 0.  None (the default): the
     calls as they were.
+    net_samples=S, net_temperature=t, net_epsilon=e [, net_opp_temperature=, net_opp_epsilon=] (with net=weights, alone or with
+    net_versus; any one of them given; not with net_seats, net_halving, exchange or bidding): the networks inside the playouts
+    play as at the table — a draw from the softmax at the temperature (default 1; 0: the greedy card), the Bot's card with
+    probability epsilon (default 0) — and every (card, world) gets S playouts (default 1) on draws of their own
+    (tarok_playout_cards_net_sampled); net_opponent's mode defaults to net's.  All None (the default): the calls as they were.
     The same five duplicate passes (PASS_SEATS) on an env of its own; returns duplicate_advantage's dict, `policy_mean`
     being the playout player's.  inspect (tests): a list that receives one dict per pass, as in _play_passes_mode."""
+    sampled = {k: v for k, v in dict(samples=net_samples, temperature=net_temperature, epsilon=net_epsilon,
+                                     opp_temperature=net_opp_temperature, opp_epsilon=net_opp_epsilon).items() if v is not None}
     return duplicate_advantage(_playout_passes(samples, n_games, episodes, seed, mix, device, salt=salt, inspect=inspect,
                                                worlds=worlds, voids=voids, exchange=exchange, hidden=hidden, bidding=bidding,
                                                threshold=threshold, contracts=contracts, pass_value=pass_value, net=net,
@@ -512,7 +524,8 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
                                                net_value_scale=net_value_scale, **({} if halving is None else dict(halving=halving)),
                                                **({} if net_halving is None else dict(net_halving=net_halving)),
                                                **({} if net_versus is None and net_opponent is None
-                                                  else dict(net_versus=net_versus, net_opponent=net_opponent))))
+                                                  else dict(net_versus=net_versus, net_opponent=net_opponent)),
+                                               **({} if not sampled else dict(net_sampled=sampled))))
 
 
 def _front_cards(cards):

@@ -13,7 +13,7 @@ from . import karte as K
 WORLDS = ("det", "voids", "hidden")               # the fair world kinds; the position is tarok_playout_cards_net_value's `kind`
 WORDS_DTYPE = dict(voids=torch.int32, hidden=torch.int64)      # the per-game words a kind reads: shown_voids() / played_cards()
 OPTIONS = ("samples", "worlds", "voids", "hidden", "exchange", "bidding", "net", "net_seats", "net_worlds", "net_depth", "net_value_scale",
-           "halving", "net_halving", "net_versus")
+           "halving", "net_halving", "net_versus", "net_sampled")
 
 
 def spelling(prefix="", pattern="%s", **other):
@@ -87,6 +87,38 @@ def check_versus(net_versus, say=spelling()):
     if not ok or net_versus[0] & net_versus[1]:
         raise ValueError(say("{net_versus}: (own_rel, opp_rel), two disjoint 4-bit sets (0..15) over the seats relative to the viewer"))
     return int(net_versus[0]), int(net_versus[1])
+
+
+def check_play_mode(temperature, epsilon, say=spelling(), names=("temperature", "epsilon")):
+    """A play mode as tarok_set_play_mode takes it: temperature 0 (greedy) or within [1e-6, 1e6], epsilon within [0, 1]."""
+    ok = all(isinstance(x, numbers.Real) and not isinstance(x, bool) and x == x for x in (temperature, epsilon))
+    if not ok or not (temperature == 0 or 1e-6 <= temperature <= 1e6) or not 0 <= epsilon <= 1:
+        raise ValueError(say("%s: 0 (greedy) or within 1e-6..1e6; %s: within 0..1" % names))
+    return float(temperature), float(epsilon)
+
+
+def check_play_modes(temperature, epsilon, opp_temperature=None, opp_epsilon=None, say=spelling()):
+    """The two play modes of a sampled net playout as (temperature, epsilon, opp_temperature, opp_epsilon): network A's, then
+    network B's, whose values default — each on its own — to A's."""
+    t, e = check_play_mode(temperature, epsilon, say)
+    return (t, e) + check_play_mode(t if opp_temperature is None else opp_temperature, e if opp_epsilon is None else opp_epsilon, say,
+                                    ("opp_temperature", "opp_epsilon"))
+
+
+SAMPLED_KEYS = ("samples", "temperature", "epsilon", "opp_temperature", "opp_epsilon")
+
+
+def check_sampled(net_sampled, say=spelling()):
+    """net_sampled=dict(samples=1, temperature=1.0, epsilon=0.0, opp_temperature=None, opp_epsilon=None) -> (samples, modes):
+    the playouts per (card, world) and check_play_modes' four numbers."""
+    if not isinstance(net_sampled, dict) or set(net_sampled) - set(SAMPLED_KEYS):
+        raise ValueError(say("{net_sampled}: a dict with keys among %s" % ", ".join(SAMPLED_KEYS)))
+    samples = net_sampled.get("samples", 1)
+    if not (isinstance(samples, numbers.Integral) and not isinstance(samples, bool) and 1 <= samples <= K.PLAYOUT_MAX_SAMPLES):
+        raise ValueError(say("{net_sampled}: samples 1..%d" % K.PLAYOUT_MAX_SAMPLES))
+    return int(samples), check_play_modes(net_sampled.get("temperature", 1.0), net_sampled.get("epsilon", 0.0),
+                                          net_sampled.get("opp_temperature"), net_sampled.get("opp_epsilon"),
+                                          lambda text: say("{net_sampled}: " + text))
 
 
 class CardPlayer(collections.namedtuple("CardPlayer", "kind worlds samples net net_seats depth value_scale salt")):
@@ -183,9 +215,31 @@ class VersusPlayer(collections.namedtuple("VersusPlayer", CardPlayer._fields + (
                                             **more, **sets)
 
 
+class SampledPlayer(collections.namedtuple("SampledPlayer", CardPlayer._fields + ("halving", "versus", "modes"))):
+    """A VersusPlayer whose networks play under a play mode each, `samples` playouts per (card, world)
+    (tarok_playout_cards_net_sampled): versus = (own_rel, opp_rel) — (15, 0) where the door gave net= alone —,
+    modes = (temperature, epsilon, opp_temperature, opp_epsilon), samples the playouts per (card, world); halving is None (no
+    such launch)."""
+    __slots__ = ()
+
+    needs_history, words_dtype, playouts = CardPlayer.needs_history, CardPlayer.words_dtype, CardPlayer.playouts
+
+    def prepare(self, env):
+        """The launch's scratch, before the launch is captured into a graph."""
+        env.playout_net_sampled_scratch(self.worlds, self.samples)
+
+    def launch(self, env, weights, opponent, sets, words, sum_out, action_out, modes=None):
+        """As VersusPlayer.launch.  modes: the four numbers in self.modes' place (a caller that fixes B's mode late)."""
+        t, e, ot, oe = self.modes if modes is None else modes
+        return env.playout_cards_net_sampled(weights, opponent, self.worlds, self.samples, self.versus[0], self.versus[1], temperature=t,
+                                             epsilon=e, opp_temperature=ot, opp_epsilon=oe, depth=self.depth, value_scale=self.value_scale,
+                                             voids=self.kind == "voids", hidden=self.kind == "hidden", words=words, salt=self.salt,
+                                             sum_out=sum_out, action_out=action_out, **sets)
+
+
 def card_player(samples=None, worlds=None, voids=False, hidden=False, net=False, net_seats=15, net_worlds="det", net_depth=None,
                 net_value_scale=70.0, salt=0, front=False, fused=True, history=None, own=True, say=spelling(), halving=None,
-                net_halving=None, net_versus=None):
+                net_halving=None, net_versus=None, net_sampled=None):
     """The one validator of a card player's options, in evaluate_playout_vs_bot's names: a CardPlayer, or a ValueError in
     the door's words (say: spelling()).  samples None: 1.  front: the door also asked for a playout-valued exchange or
     bidding.  fused: the door's policy is the fused one.  history: whether the env at hand keeps the play history (None:
@@ -198,7 +252,23 @@ def card_player(samples=None, worlds=None, voids=False, hidden=False, net=False,
     None or 1, no exchange, no bidding.  halving= together with net= keeps raising.
     net_versus: (own_rel, opp_rel) — a VersusPlayer (tarok_playout_cards_net_versus): the playouts seat the player's network on
     the relative seats of own_rel and an opponent's on those of opp_rel, relative to each game's viewer.  It requires net=, goes
-    with net_worlds, net_depth and net_halving, and seats the networks itself: net_seats stays at its default."""
+    with net_worlds, net_depth and net_halving, and seats the networks itself: net_seats stays at its default.
+    net_sampled: dict(samples=, temperature=, epsilon=, opp_temperature=, opp_epsilon=) on top of net= or net_versus= — a
+    SampledPlayer (tarok_playout_cards_net_sampled): the networks play under those play modes (the opponent's default to the
+    player's), `samples` playouts per (card, world).  With net= alone the network sits on all four seats, (own_rel, opp_rel) =
+    (15, 0): net_seats stays at its default.  Not built, and refused by name: net_halving, the exchange and the bidding."""
+    sampled = None
+    if net_sampled is not None:
+        sampled = check_sampled(net_sampled, say)
+        if not net:
+            raise ValueError(say("{net_sampled}= sets how the networks play inside the network's playouts: it goes with {net}="))
+        if net_halving is not None:
+            raise ValueError(say("{net_sampled}= is not built for {net_halving}: the sampled launch has no halving form"))
+        if front:
+            raise ValueError(say("{net_sampled}= is not built for the {exchange} and {bidding} launches: the card launch alone is sampled"))
+        if net_seats != 15:
+            raise ValueError(say("{net_sampled}= seats the network relative to the viewer, on all four seats or as {net_versus} says: "
+                                 "leave {net_seats} out"))
     if net_versus is not None:
         net_versus = check_versus(net_versus, say)
         if not net:
@@ -250,6 +320,8 @@ def card_player(samples=None, worlds=None, voids=False, hidden=False, net=False,
     if kind in WORDS_DTYPE and history is not None and not history:
         raise ValueError(say("the %s worlds read the play history: TarokVecEnv(history=True)" % kind))
     player = CardPlayer(kind, worlds, samples, bool(net), net_seats, net_depth, float(net_value_scale), int(salt))
+    if sampled is not None:
+        return SampledPlayer(*player._replace(samples=sampled[0]), None, (15, 0) if net_versus is None else net_versus, sampled[1])
     if net_versus is not None:
         return VersusPlayer(*player, net_halving, net_versus)
     if net_halving is not None:

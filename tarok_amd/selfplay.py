@@ -310,6 +310,15 @@ class SelfPlay:
     (1, 14) makes the targets a search against the opponent actually at the table, and set_opponent() is picked up without a
     new capture.  It goes with net_worlds, depth and net_halving; net_seats is left out.  Without opponent=, or with a pool: a
     ValueError.
+    teacher = dict(net=True, worlds=W, samples=S, temperature=t[, epsilon=e, versus=(1, 14), opp_temperature=, opp_epsilon=]): the
+    teacher's networks play as they play AT THE TABLE (tarok_playout_cards_net_sampled) — the learner's weights draw
+    from their softmax at temperature t (0: greedy), the Bot's card with probability e —, S playouts (default 1) per (card,
+    world) on draws of their own, so the rows value the policy that goes on playing and more samples cut their variance.  The
+    key `temperature` (or epsilon / opp_temperature / opp_epsilon) selects this launch: a dict without any of them is the
+    greedy launch as before, where samples above 1 keeps raising.  With versus and no opp_temperature (no opp_epsilon), the
+    frozen opponent's mode is the ENV'S CURRENT PLAY MODE (env.play_mode, read when the rollout is issued or captured): the
+    mode the opponent actually plays at the table, which is the point of the launch; without versus the network sits on all
+    four seats, (15, 0).  Inside the captured rollout, scratch allocated before capture.  Not with net_seats or net_halving.
 
     front = dict(bid=, exchange=, contracts=, margin=, pass_value=, every=1): the games auto-reset swaps in are bid and
     exchanged by the heads instead of the Bot (TarokVecEnv.front_lines).  bid / exchange: six tensors each
@@ -343,8 +352,15 @@ class SelfPlay:
         self.teacher, self._player, self.distill_coef = None, None, float(distill_coef)
         if teacher is not None:                       # the card player is playout.card_player's; tau and every are the teacher's own
             unknown = set(teacher) - {"worlds", "samples", "tau", "every", "salt", "voids", "hidden", "net", "net_seats", "net_worlds", "depth",
-                                      "halving", "net_halving", "versus"}
+                                      "halving", "net_halving", "versus"} - set(playout.SAMPLED_KEYS)
             net = bool(teacher.get("net", False))
+            # the sampled launch is asked for by a play-mode key; `samples` then is its playouts per (card, world)
+            sampled = {k: teacher[k] for k in playout.SAMPLED_KEYS[1:] if teacher.get(k) is not None}
+            if sampled and not net:
+                raise ValueError("teacher: temperature / epsilon / opp_temperature / opp_epsilon set how the NETWORK plays inside the "
+                                 "playouts: they go with net=True")
+            if sampled:
+                sampled["samples"] = teacher.get("samples", 1)
             if unknown or ("samples" not in teacher and not net and "halving" not in teacher):
                 raise ValueError("teacher: dict(worlds=W, samples=S, tau=tau, every=k, salt=...) or dict(halving=(w0, ..), ...): samples "
                                  "required unless net=True or halving= is given; unknown keys %s" % sorted(unknown))
@@ -354,14 +370,15 @@ class SelfPlay:
             if versus is not None and (opponent is None or pool):
                 raise ValueError("teacher: versus=(own_rel, opp_rel) seats the frozen opponent inside the teacher's playouts: it goes with "
                                  "opponent= (ONE snapshot(), not a pool)")
-            p = playout.card_player(int(teacher.get("samples", 1)), int(teacher.get("worlds") or 0), bool(teacher.get("voids", False)),
+            p = playout.card_player(1 if sampled else int(teacher.get("samples", 1)), int(teacher.get("worlds") or 0), bool(teacher.get("voids", False)),
                                     bool(teacher.get("hidden", False)), net, int(teacher.get("net_seats", 15)), teacher.get("net_worlds", "det"),
                                     teacher.get("depth"), 1.0 / reward_scale if reward_scale else 0.0, int(teacher.get("salt", 0)),
                                     fused=(hidden == 256) if fused is None else bool(fused), history=getattr(env, "history", False), own=False,
                                     say=playout.spelling("teacher: ", net_depth="depth", net_value_scale="1 / reward_scale"),
                                     **({"halving": teacher["halving"]} if "halving" in teacher else {}),
                                     **({"net_halving": teacher["net_halving"]} if teacher.get("net_halving") is not None else {}),
-                                    **({} if versus is None else {"net_versus": versus}))
+                                    **({} if versus is None else {"net_versus": versus}),
+                                    **({} if not sampled else {"net_sampled": sampled}))
             tau, every = float(teacher.get("tau", 1.0)), int(teacher.get("every", 1))
             if not (every >= 1 and 0.0 <= tau < float("inf")):
                 raise ValueError("teacher: tau >= 0 and finite, every >= 1")
@@ -369,7 +386,10 @@ class SelfPlay:
             self.teacher = dict(worlds=p.worlds, samples=p.samples, tau=tau, every=every, salt=p.salt, voids=p.kind == "voids" and not net,
                                 hidden=p.kind == "hidden" and not net, net=net, net_seats=p.net_seats, net_worlds=p.kind if net else "det",
                                 **({} if p.depth is None else dict(depth=p.depth)), **({} if p.halving is None else {"net_halving" if net else "halving": p.halving}),
-                                **({} if versus is None else dict(versus=p.versus)))
+                                **({} if versus is None else dict(versus=p.versus)),
+                                **({} if not sampled else dict(temperature=p.modes[0], epsilon=p.modes[1],
+                                                               opp_temperature=sampled.get("opp_temperature"),
+                                                               opp_epsilon=sampled.get("opp_epsilon"))))
         elif distill_coef:
             raise ValueError("distill_coef weighs the playout teacher's term: pass teacher= as well")
         self.env = env
@@ -610,7 +630,8 @@ class SelfPlay:
     def evaluate(self, n_games=4096, episodes=4, mix=K.MIX_BOT, opponent=None, greedy=False, temperature=None, epsilon=0.0,
                  versus_playout=None, playout_worlds=None, playout_voids=False, playout_exchange=None,
                  playout_hidden=False, playout_bidding=None, pass_value=False, playout_net=False, playout_net_seats=15,
-                 playout_net_worlds="det", playout_net_depth=None, playout_halving=None, playout_net_halving=None):
+                 playout_net_worlds="det", playout_net_depth=None, playout_halving=None, playout_net_halving=None,
+                 playout_net_samples=None, playout_net_temperature=None, playout_net_epsilon=None):
         """Points per game against the Bot on duplicate deals (evaluate.evaluate_vs_bot: its dict), with the current
         weights.  Played on an env of its own: the training env and the captured rollout are left alone.  Per rank,
         and on the SAME deals on every rank (seed 0, game offset 0, whatever the training env's are): the figures of
@@ -651,10 +672,18 @@ class SelfPlay:
         sequential halving (evaluate_playout_vs_bot(halving=...)).
         playout_net_halving=(w0, w1, ..) (with playout_net; playout_worlds None or their sum; with playout_net_worlds and
         playout_net_depth): the network's playouts are spent by sequential halving on a compacted item list
-        (evaluate_playout_vs_bot(net_halving=...)).  playout_halving with playout_net keeps raising."""
+        (evaluate_playout_vs_bot(net_halving=...)).  playout_halving with playout_net keeps raising.
+        playout_net_samples=S, playout_net_temperature=t, playout_net_epsilon=e (with playout_net; any one given; not with
+        playout_net_seats or playout_net_halving): inside those playouts the network plays as at the table — a draw from its
+        softmax at t (default 1; 0: greedy), the Bot's card with probability e (default 0) —, S playouts (default 1) per
+        (card, world) (evaluate_playout_vs_bot(net_samples=, net_temperature=, net_epsilon=)).  None: as before."""
         halving = {} if playout_halving is None else dict(halving=playout_halving)
         if playout_net_halving is not None:
             halving = dict(halving, net_halving=playout_net_halving)
+        sampled = {k: v for k, v in dict(samples=playout_net_samples, temperature=playout_net_temperature,
+                                         epsilon=playout_net_epsilon).items() if v is not None}
+        if sampled:
+            halving = dict(halving, net_sampled=sampled)
         playout.card_player(versus_playout, playout_worlds, playout_voids, playout_hidden, bool(playout_net), playout_net_seats,
                             playout_net_worlds, playout_net_depth, front=playout_exchange is not None or playout_bidding is not None,
                             say=playout.spelling(pattern="playout_%s", samples="versus_playout"), **halving)
@@ -694,7 +723,8 @@ class SelfPlay:
                                                 **({} if playout_net_worlds == "det" else dict(net_worlds=playout_net_worlds)),
                                                 **({} if playout_net_depth is None else
                                                    dict(net_depth=playout_net_depth, net_value_scale=1.0 / self.reward_scale)),
-                                                **({} if playout_net_halving is None else dict(net_halving=playout_net_halving)))
+                                                **({} if playout_net_halving is None else dict(net_halving=playout_net_halving)),
+                                                **{"net_" + k: v for k, v in sampled.items()})
         return own, evaluate_playout_vs_bot(int(versus_playout), n_games, episodes, mix=mix, device=self.env.device_index,
                                             worlds=playout_worlds, voids=bool(playout_voids), exchange=playout_exchange,
                                             hidden=bool(playout_hidden), bidding=playout_bidding,
@@ -725,12 +755,27 @@ class SelfPlay:
                 self._teach_counts = torch.empty((n, K.PLAYOUT_RANKS), dtype=torch.int32, device=dev)
         self._graph = None
 
+    def teacher_modes(self):
+        """(temperature, epsilon, opp_temperature, opp_epsilon) of a sampled teacher's next launch: the dict's own, and for a
+        versus teacher that left the opponent's open, the env's current play mode — what the opponent plays at the table."""
+        t, e = self.teacher["temperature"], self.teacher["epsilon"]
+        ot, oe = self.env.play_mode if "versus" in self.teacher else (t, e)
+        given_t, given_e = self.teacher["opp_temperature"], self.teacher["opp_epsilon"]
+        return t, e, ot if given_t is None else float(given_t), oe if given_e is None else float(given_e)
+
     def _teach(self, t):
         """The teacher's rows of lock-step t: one playout launch on the learner's seats from the env's current positions,
         one tarok_playout_targets on the words of that lock-step.  Stream-ordered, read-only on the env, no allocation.
         A versus teacher's launch reads the live rollout weights as network A and the frozen opponent's own tensors (the ones
         set_opponent writes in place) as network B."""
         nets = (self._w, self._opp) if "versus" in self.teacher else (self._w,)
+        if "temperature" in self.teacher:             # the sampled launch: B's mode, where the dict left it open, is the env's own
+            nets = (self._w, self._opp if "versus" in self.teacher else None)
+            self._player.launch(self.env, *nets, dict(seats_per_game=self._seats), self._teach_words, self._teach_sums, self._teach_act,
+                                modes=self.teacher_modes())
+            self.env.playout_targets(self._teach_sums, self._buf["words"][t], self._player.playouts, self.teacher["tau"],
+                                     seats_per_game=self._seats, target_out=self._buf["teach"][t])
+            return
         if self._player.halving is not None:          # one halving launch, one tarok_playout_targets_counts on its counts
             self._player.launch(self.env, *nets, dict(seats_per_game=self._seats), self._teach_words, self._teach_sums, self._teach_act,
                                 count_out=self._teach_counts)
