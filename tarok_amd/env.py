@@ -333,30 +333,48 @@ class TarokVecEnv:
                                                       self._p(out.get("actions")), self._stream()))
         return out
 
-    def _cards(self, worlds, samples, salt, seats, seats_per_game, sum_out, action_out, voids=False, hidden=False, words=None, net=None):
-        """The one card launch under the seven playout_cards* methods: picks the native entry point of the world kind —
-        worlds None: open hands; voids / hidden True: the env's own words, written into the caller's `words` tensor (None: a
-        new one); a tensor or an array in their place: the words themselves, which need no history — and of the player:
-        net None (the Bot, `samples` playouts per card and world) or (weights, net_seats, depth, value_scale), samples None.
-        Returns (sum_out, action_out), allocated where None."""
+    def _cards(self, worlds, samples, salt, seats, seats_per_game, sum_out, action_out, voids=False, hidden=False, words=None):
+        """The one card launch under the Bot-played playout_cards* methods (`samples` playouts per card and world): picks the
+        native entry point of the world kind — worlds None: open hands; voids / hidden True: the env's own words, written into
+        the caller's `words` tensor (None: a new one); a tensor or an array in their place: the words themselves, which need
+        no history.  Returns (sum_out, action_out), allocated where None."""
         kind, words = TarokVecEnv._world_words(self, worlds is not None, voids, hidden, words)
-        if net is not None:
-            net_seats, depth, value_scale, w = TarokVecEnv._net_args(self, *net)
-            scratch = self.playout_net_scratch(worlds)
         words = words()
-        name = "tarok_playout_cards" + ("" if net is None else "_net") + ("" if kind == ("open" if net is None else "det") else "_" + kind)
-        mid = [] if words is None else [self._p(words)]
-        if net is not None:
-            mid.append(net_seats)
-            if net[2] is not None:
-                name, mid = "tarok_playout_cards_net_value", [P.WORLDS.index(kind), self._p(words), net_seats, depth, value_scale]
-            mid += w + [self._p(scratch), scratch.numel()]
+        name = "tarok_playout_cards" + ("" if kind == "open" else "_" + kind)
         with torch.cuda.device(self.device):
             sum_out, action_out = TarokVecEnv._card_outputs(self, sum_out, action_out)
             _native.check(getattr(self.L, name)(self._h, *[int(c) for c in (worlds, samples) if c is not None], _salt(salt),
-                                                int(seats), self._p(self._seat_sets(seats_per_game)), *mid, self._p(sum_out),
-                                                self._p(action_out), self._stream()))
+                                                int(seats), self._p(self._seat_sets(seats_per_game)), *([] if words is None else [self._p(words)]),
+                                                self._p(sum_out), self._p(action_out), self._stream()))
         return sum_out, action_out
+
+    def _net_cards(self, name, order, sizes, given, scratch, weights, net_seats, depth, value_scale, voids, hidden, words, salt, seats,
+                   seats_per_game, sum_out, action_out, count_out=False, opponent=False, opp_rel=0):
+        """The one card launch under the five playout_cards_net* methods.  name: the native entry point ({kind}: "", "_voids" or
+        "_hidden", for the entries that have the world kind in their name); order: its arguments between the env and the
+        scratch, as the names of their groups — sizes (`sizes` as ints: worlds, samples), sets (salt, seats, the per-game
+        sets), kind (the kind's number and the words), words (the words alone, where there are any), net_seats, value (depth,
+        value_scale), nets (the six pointers of `weights`; then, with opponent other than False, the six of `opponent` — six
+        NULLs for None, which opp_rel 0 allows) and whatever `given` holds (roles, schedule, modes).  scratch: a call that makes
+        the launch's scratch tensor; count_out other than False: the launch writes a count per card.  voids / hidden / words:
+        as in _world_words.  Every refusal comes before the first launch.  Returns the outputs, allocated where None."""
+        kind, words = TarokVecEnv._world_words(self, True, voids, hidden, words)
+        net_seats, depth, value_scale, nets = TarokVecEnv._net_args(self, weights, net_seats, depth, value_scale)
+        if opponent is not False:
+            if opponent is None and opp_rel:
+                raise ValueError("opp_rel seats the opponent's network: give its six tensors")
+            nets = nets + ([None] * 6 if opponent is None else [self._p(t) for t in self.check_mlp_weights(opponent)])
+        scratch = scratch()
+        words = words()
+        with torch.cuda.device(self.device):
+            outs = TarokVecEnv._card_outputs(self, sum_out, action_out, count_out)
+            groups = dict(given, sizes=[int(c) for c in sizes], sets=[_salt(salt), int(seats), self._p(self._seat_sets(seats_per_game))],
+                          kind=[P.WORLDS.index(kind), self._p(words)], words=[] if words is None else [self._p(words)],
+                          net_seats=[net_seats], value=[depth, value_scale], nets=nets)
+            _native.check(getattr(self.L, name.format(kind="" if kind == "det" else "_" + kind))(
+                self._h, *[x for group in order.split() for x in groups[group]], self._p(scratch), scratch.numel(),
+                *[self._p(t) for t in outs], self._stream()))
+        return tuple(outs)
 
     def _world_words(self, fair, voids, hidden, words):
         """(kind, words) of a card launch, `words` a call that makes its per-game words tensor (None for a kind without),
@@ -475,17 +493,10 @@ class TarokVecEnv:
         Returns (sum [N,12,4] int32, count [N,12] int32 — the worlds behind every row —, action [N] uint8: the first card
         at the maximum among the cards alive at the end)."""
         schedule = P.check_halving(round_worlds)
-        kind, words = TarokVecEnv._world_words(self, True, voids, hidden, words)
-        net_seats, depth, value_scale, w = TarokVecEnv._net_args(self, weights, net_seats, depth, value_scale)
-        scratch = self.playout_net_halving_scratch(schedule) if scratch is None else scratch
-        words = words()
-        with torch.cuda.device(self.device):
-            sum_out, count_out, action_out = TarokVecEnv._card_outputs(self, sum_out, action_out, count_out)
-            _native.check(self.L.tarok_playout_cards_net_halving(
-                self._h, P.WORLDS.index(kind), self._p(words), len(schedule), (C.c_int * len(schedule))(*schedule), _salt(salt),
-                int(seats), self._p(self._seat_sets(seats_per_game)), net_seats, *w, depth, value_scale, self._p(scratch),
-                scratch.numel(), self._p(sum_out), self._p(count_out), self._p(action_out), self._stream()))
-        return sum_out, count_out, action_out
+        return TarokVecEnv._net_cards(self, "tarok_playout_cards_net_halving", "kind schedule sets net_seats nets value", (),
+                                      dict(schedule=[len(schedule), (C.c_int * len(schedule))(*schedule)]),
+                                      lambda: self.playout_net_halving_scratch(schedule) if scratch is None else scratch, weights, net_seats,
+                                      depth, value_scale, voids, hidden, words, salt, seats, seats_per_game, sum_out, action_out, count_out)
 
     def playout_net_scratch(self, worlds):
         """The scratch tensor of playout_cards_net at `worlds` (uint8, tarok_playout_net_scratch bytes), cached on the env
@@ -509,7 +520,8 @@ class TarokVecEnv:
         playout_cards_voids(voids=...) takes them, and needs no history.  words: the caller's scratch tensor for the
         env's own words (None: a new one per call), so that a captured launch allocates nothing.  Not both: the two
         kinds do not compose.  The defaults issue tarok_playout_cards_net."""
-        return self._cards(worlds, None, salt, seats, seats_per_game, sum_out, action_out, voids, hidden, words, (weights, net_seats, None, 0.0))
+        return TarokVecEnv.playout_cards_net_value(self, weights, worlds, None, 0.0, net_seats, salt, seats, seats_per_game, sum_out, action_out,
+                                                   voids, hidden, words)
 
     def playout_cards_net_value(self, weights, worlds, depth, value_scale=70.0, net_seats=15, salt=0, seats=15, seats_per_game=None,
                                 sum_out=None, action_out=None, voids=False, hidden=False, words=None):
@@ -525,8 +537,10 @@ class TarokVecEnv:
         IS playout_cards_net."""
         if depth is not None:
             P.check_depth(depth, value_scale)         # (before anything of the env is read)
-        return self._cards(worlds, None, salt, seats, seats_per_game, sum_out, action_out, voids, hidden, words,
-                           (weights, net_seats, depth, value_scale))
+        name, order = ("tarok_playout_cards_net{kind}", "sizes sets words net_seats nets") if depth is None else \
+            ("tarok_playout_cards_net_value", "sizes sets kind net_seats value nets")
+        return TarokVecEnv._net_cards(self, name, order, (worlds,), {}, lambda: self.playout_net_scratch(worlds), weights, net_seats, depth,
+                                      value_scale, voids, hidden, words, salt, seats, seats_per_game, sum_out, action_out)
 
     def playout_cards_net_versus(self, weights, opponent, worlds, own_rel=1, opp_rel=14, depth=None, value_scale=70.0, voids=False,
                                  hidden=False, words=None, halving=None, salt=0, seats=15, seats_per_game=None, sum_out=None,
@@ -551,25 +565,15 @@ class TarokVecEnv:
             raise ValueError("halving= names the worlds of every round: worlds is optional and must be their sum")
         if schedule is None and count_out is not None:
             raise ValueError("count_out holds the worlds behind every row of a halving launch: it goes with halving=")
-        kind, words = TarokVecEnv._world_words(self, True, voids, hidden, words)
-        _, depth, value_scale, a = TarokVecEnv._net_args(self, weights, 0, depth, value_scale)
-        if opponent is None and opp_rel:
-            raise ValueError("opp_rel seats the opponent's network: give its six tensors")
-        b = [None] * 6 if opponent is None else [self._p(t) for t in self.check_mlp_weights(opponent)]
-        scratch = self.playout_net_scratch(worlds) if schedule is None else self.playout_net_halving_scratch(schedule)
-        words = words()
-        with torch.cuda.device(self.device):
-            outs = TarokVecEnv._card_outputs(self, sum_out, action_out, False if schedule is None else count_out)
-            tail = [self._p(scratch), scratch.numel()] + [self._p(t) for t in outs] + [self._stream()]
-            sets = [_salt(salt), int(seats), self._p(self._seat_sets(seats_per_game))]
-            if schedule is None:
-                _native.check(self.L.tarok_playout_cards_net_versus(self._h, int(worlds), *sets, P.WORLDS.index(kind), self._p(words),
-                                                                    own_rel, opp_rel, depth, value_scale, *a, *b, *tail))
-            else:
-                _native.check(self.L.tarok_playout_cards_net_versus_halving(
-                    self._h, P.WORLDS.index(kind), self._p(words), len(schedule), (C.c_int * len(schedule))(*schedule), *sets, own_rel,
-                    opp_rel, *a, *b, depth, value_scale, *tail))
-        return tuple(outs)
+        roles = dict(roles=[own_rel, opp_rel])
+        if schedule is None:
+            return TarokVecEnv._net_cards(self, "tarok_playout_cards_net_versus", "sizes sets kind roles value nets", (worlds,), roles,
+                                          lambda: self.playout_net_scratch(worlds), weights, 0, depth, value_scale, voids, hidden, words, salt,
+                                          seats, seats_per_game, sum_out, action_out, opponent=opponent, opp_rel=opp_rel)
+        return TarokVecEnv._net_cards(self, "tarok_playout_cards_net_versus_halving", "kind schedule sets roles nets value", (),
+                                      dict(roles, schedule=[len(schedule), (C.c_int * len(schedule))(*schedule)]),
+                                      lambda: self.playout_net_halving_scratch(schedule), weights, 0, depth, value_scale, voids, hidden, words,
+                                      salt, seats, seats_per_game, sum_out, action_out, count_out, opponent, opp_rel)
 
     def playout_net_sampled_scratch(self, worlds, samples):
         """The scratch tensor of playout_cards_net_sampled at (worlds, samples) (uint8, tarok_playout_cards_net_sampled_scratch
@@ -593,20 +597,10 @@ class TarokVecEnv:
         halving form.  The scratch is playout_net_sampled_scratch(worlds, samples).  Returns (sum, action)."""
         own_rel, opp_rel = P.check_versus((own_rel, opp_rel), P.spelling(net_versus="(own_rel, opp_rel)"))
         modes = P.check_play_modes(temperature, epsilon, opp_temperature, opp_epsilon)
-        kind, words = TarokVecEnv._world_words(self, True, voids, hidden, words)
-        _, depth, value_scale, a = TarokVecEnv._net_args(self, weights, 0, depth, value_scale)
-        if opponent is None and opp_rel:
-            raise ValueError("opp_rel seats the opponent's network: give its six tensors")
-        b = [None] * 6 if opponent is None else [self._p(t) for t in self.check_mlp_weights(opponent)]
-        scratch = self.playout_net_sampled_scratch(worlds, samples)
-        words = words()
-        with torch.cuda.device(self.device):
-            outs = TarokVecEnv._card_outputs(self, sum_out, action_out)
-            _native.check(self.L.tarok_playout_cards_net_sampled(
-                self._h, int(worlds), int(samples), _salt(salt), int(seats), self._p(self._seat_sets(seats_per_game)), P.WORLDS.index(kind),
-                self._p(words), own_rel, opp_rel, depth, value_scale, *modes, *a, *b, self._p(scratch), scratch.numel(),
-                *[self._p(t) for t in outs], self._stream()))
-        return tuple(outs)
+        return TarokVecEnv._net_cards(self, "tarok_playout_cards_net_sampled", "sizes sets kind roles value modes nets", (worlds, samples),
+                                      dict(roles=[own_rel, opp_rel], modes=modes), lambda: self.playout_net_sampled_scratch(worlds, samples),
+                                      weights, 0, depth, value_scale, voids, hidden, words, salt, seats, seats_per_game, sum_out, action_out,
+                                      opponent=opponent, opp_rel=opp_rel)
 
     def playout_exchange(self, worlds, samples, discard_sets=4, salt=0, seats=15, seats_per_game=None, sum_out=None,
                          choice_out=None, discards_out=None):

@@ -430,10 +430,8 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     with net alone on the roles (15, 0).
     inspect: as in _play_passes_mode."""
     player = playout.card_player(samples, worlds, voids, hidden, net is not None, net_seats, net_worlds, net_depth, net_value_scale, salt,
-                                 front=exchange is not None or bidding is not None, **({} if halving is None else dict(halving=halving)),
-                                 **({} if net_halving is None else dict(net_halving=net_halving)),
-                                 **({} if net_versus is None else dict(net_versus=net_versus)),
-                                 **({} if net_sampled is None else dict(net_sampled=net_sampled)))
+                                 front=exchange is not None or bidding is not None, halving=halving, net_halving=net_halving,
+                                 net_versus=net_versus, net_sampled=net_sampled)
     if net_opponent is not None and net_versus is None:
         raise ValueError("net_opponent is the second network of net_versus=(own_rel, opp_rel): give that as well")
     if net_versus is not None and player.versus[1] and net_opponent is None:
@@ -449,9 +447,8 @@ def _playout_passes(samples, n_games, episodes, seed, mix, device, salt=0, inspe
     if bidding is not None and worlds is None:
         raise ValueError("bidding=(W, S) is the fair player's front end: give worlds= as well")
     bidding = _bid_args(bidding, mix)
-    nets = (net,) if net_versus is None and net_sampled is None else (net, net_opponent)
-    cards = _playout_cards(lambda env, seats, words, sums, row, **more: player.launch(env, *nets, dict(seats=seats), words, sums, row, **more),
-                           words_dtype=player.words_dtype, **({} if player.halving is None else dict(counts=True)))
+    cards = _playout_cards(lambda env, seats, words, sums, row, **more: player.launch(env, (net, net_opponent), dict(seats=seats), words, sums, row, **more),
+                           words_dtype=player.words_dtype, counts=player.counts)
     front = _front(inspect is not None, bid=None if bidding is None else _bid_front(bidding, salt, threshold, contracts, pass_value),
                    exchange=None if exchange is None else _exchange_front(worlds, samples, exchange, salt))
     return _passes(n_games, episodes, front, cards, inspect, device=device, seed=seed, mix=mix, history=player.needs_history)
@@ -521,11 +518,8 @@ def evaluate_playout_vs_bot(samples, n_games, episodes, seed=0, mix=K.MIX_BOT, d
                                                worlds=worlds, voids=voids, exchange=exchange, hidden=hidden, bidding=bidding,
                                                threshold=threshold, contracts=contracts, pass_value=pass_value, net=net,
                                                net_seats=net_seats, net_worlds=net_worlds, net_depth=net_depth,
-                                               net_value_scale=net_value_scale, **({} if halving is None else dict(halving=halving)),
-                                               **({} if net_halving is None else dict(net_halving=net_halving)),
-                                               **({} if net_versus is None and net_opponent is None
-                                                  else dict(net_versus=net_versus, net_opponent=net_opponent)),
-                                               **({} if not sampled else dict(net_sampled=sampled))))
+                                               net_value_scale=net_value_scale, halving=halving, net_halving=net_halving,
+                                               net_versus=net_versus, net_opponent=net_opponent, net_sampled=sampled or None))
 
 
 def _front_cards(cards):

@@ -1,8 +1,9 @@
 """The playout card player, described once: what SelfPlay(teacher=dict(...)), SelfPlay.evaluate(playout_*=...) and
 evaluate.evaluate_playout_vs_bot(...) each spell in their own words.  card_player() holds every rule of the options and
-returns a CardPlayer; the CardPlayer knows what its launch needs (history, the words tensor, the net scratch, the divisor
-of tarok_playout_targets) and issues it through the env's public method of its kind.  A door keeps only the rules that
-are its own (tau and every; versus_playout; exchange and bidding) and names the options its way through spelling()."""
+returns a CardPlayer — ONE class for every kind of launch, the options a kind does not have None —; the CardPlayer knows
+what its launch needs (history, the words tensor, the net scratch, the divisor of tarok_playout_targets or a count per
+card) and issues it, with one signature, through the env's public method of its launch_kind.  A door keeps only the rules
+that are its own (tau and every; versus_playout; exchange and bidding) and names the options its way through spelling()."""
 import collections
 import numbers
 
@@ -121,120 +122,74 @@ def check_sampled(net_sampled, say=spelling()):
                                           lambda text: say("{net_sampled}: " + text))
 
 
-class CardPlayer(collections.namedtuple("CardPlayer", "kind worlds samples net net_seats depth value_scale salt")):
+class CardPlayer(collections.namedtuple("CardPlayer", "kind worlds samples net net_seats depth value_scale salt halving versus modes",
+                                        defaults=(None, None, None))):
     """kind: "open" (the true hands) or one of WORLDS; worlds as the door gave it (None or 0 for "open"), samples per
     (card, world); net: the playouts are played by a network on net_seats (a set 0..15, or "own": the launch's own seats),
-    stopped at the viewer's depth-th decision (None: never) with the value head at value_scale points per unit."""
+    stopped at the viewer's depth-th decision (None: never) with the value head at value_scale points per unit.
+    halving: None, or the worlds of every round of sequential halving, worlds their sum — the Bot-played launch's, with net the
+    net-played one's.  versus: None, or (own_rel, opp_rel): the playouts seat TWO networks relative to each game's viewer, the
+    player's own and an opponent's; net_seats is then not read.  modes: None, or (temperature, epsilon,
+    opp_temperature, opp_epsilon): the networks play under a play mode each, `samples` playouts per (card, world) (DESIGN
+    8.25); versus is then (15, 0) where the door gave net= alone, and halving is None (no such launch)."""
     __slots__ = ()
-    halving = None                                    # (a HalvingPlayer's schedule)
 
     needs_history = property(lambda self: self.kind in WORDS_DTYPE)
     words_dtype = property(lambda self: WORDS_DTYPE.get(self.kind))
     playouts = property(lambda self: max(1, self.worlds or 0) * self.samples)       # tarok_playout_targets' divisor
+    # the rows have a count per card (count_out), not one divisor: the targets are tarok_playout_targets_counts'
+    counts = property(lambda self: self.halving is not None)
+
+    @property
+    def launch_kind(self):
+        """The env method of the launch: fair | halving | net | net_value | net_halving | versus | sampled."""
+        if self.modes is not None:
+            return "sampled"
+        if self.versus is not None:
+            return "versus"
+        if not self.net:
+            return "fair" if self.halving is None else "halving"
+        return "net_halving" if self.halving is not None else "net" if self.depth is None else "net_value"
 
     def prepare(self, env):
-        """What has to exist before the launch is captured into a graph: the net launch's scratch."""
-        if self.net:
+        """What has to exist before the launch is captured into a graph: a net-played launch's scratch."""
+        if self.modes is not None:
+            env.playout_net_sampled_scratch(self.worlds, self.samples)
+        elif self.net and self.halving is not None:
+            env.playout_net_halving_scratch(self.halving)
+        elif self.net:
             env.playout_net_scratch(self.worlds)
 
-    def launch(self, env, weights, sets, words, sum_out, action_out):
-        """The player's launch on `env`: sets = dict(seats=...) or dict(seats_per_game=...), words the caller's tensor of
-        words_dtype (None where there is none), weights the network's six tensors (net players only)."""
+    def launch(self, env, nets, sets, words, sum_out, action_out, count_out=None, modes=None):
+        """The player's launch on `env`, through the env's public method of its launch_kind; returns what that returns.
+        nets = (weights, opponent): the six tensors of the player's network and of the opponent's, each None where the kind
+        does not read it; sets = dict(seats=...) or dict(seats_per_game=...); words the caller's tensor of words_dtype (None
+        where there is none); count_out: the caller's [N,12] int32 tensor where the player `counts` (None: a new one per
+        call); modes: the four numbers in self.modes' place (a caller that fixes the opponent's mode late)."""
+        weights, opponent = nets
+        kind = self.launch_kind
+        world = dict(voids=self.kind == "voids", hidden=self.kind == "hidden", words=words)
         out = dict(salt=self.salt, sum_out=sum_out, action_out=action_out, **sets)
-        if not self.net:
-            return env.playout_cards_fair(self.worlds, self.samples, voids=self.kind == "voids", hidden=self.kind == "hidden", words=words, **out)
-        out.update(net_seats=sets["seats"] if self.net_seats == "own" else self.net_seats)
+        value = dict(depth=self.depth, value_scale=self.value_scale)
+        if kind == "fair":
+            return env.playout_cards_fair(self.worlds, self.samples, **world, **out)
+        if kind == "halving":
+            return env.playout_cards_halving(self.halving, self.samples, count_out=count_out, **world, **out)
+        if kind == "sampled":
+            t, e, ot, oe = self.modes if modes is None else modes
+            return env.playout_cards_net_sampled(weights, opponent, self.worlds, self.samples, *self.versus, temperature=t, epsilon=e,
+                                                 opp_temperature=ot, opp_epsilon=oe, **value, **world, **out)
+        if kind == "versus":
+            more = {} if self.halving is None else dict(count_out=count_out)
+            return env.playout_cards_net_versus(weights, opponent, self.worlds, *self.versus, halving=self.halving, **value, **world, **more, **out)
+        net_seats = sets["seats"] if self.net_seats == "own" else self.net_seats
+        if kind == "net_halving":
+            return env.playout_cards_net_halving(weights, self.halving, net_seats, count_out=count_out, **value, **world, **out)
         if self.needs_history:
             out.update({self.kind: True, "words": words})
-        if self.depth is None:
-            return env.playout_cards_net(weights, self.worlds, **out)
-        return env.playout_cards_net_value(weights, self.worlds, self.depth, self.value_scale, **out)
-
-
-class HalvingPlayer(collections.namedtuple("HalvingPlayer", CardPlayer._fields + ("halving",))):
-    """A CardPlayer of a fair kind played by the Bot whose launch is tarok_playout_cards_halving: halving = the worlds of
-    every round, worlds their sum.  Its rows have a count per card (count_out), not one divisor: the targets are
-    tarok_playout_targets_counts'."""
-    __slots__ = ()
-
-    needs_history, words_dtype = CardPlayer.needs_history, CardPlayer.words_dtype
-
-    def prepare(self, env):
-        pass
-
-    def launch(self, env, weights, sets, words, sum_out, action_out, count_out=None):
-        """As CardPlayer.launch; count_out: the caller's [N,12] int32 tensor (None: a new one per call).  Returns (sum,
-        count, action)."""
-        return env.playout_cards_halving(self.halving, self.samples, voids=self.kind == "voids", hidden=self.kind == "hidden", words=words,
-                                         salt=self.salt, sum_out=sum_out, count_out=count_out, action_out=action_out, **sets)
-
-
-class NetHalvingPlayer(collections.namedtuple("NetHalvingPlayer", CardPlayer._fields + ("halving",))):
-    """A CardPlayer of a fair kind played by the NETWORK whose launch is tarok_playout_cards_net_halving: halving = the worlds
-    of every round, worlds their sum, one playout per (card alive, world).  Its rows have a count per card, as a
-    HalvingPlayer's: the targets are tarok_playout_targets_counts'."""
-    __slots__ = ()
-
-    needs_history, words_dtype = CardPlayer.needs_history, CardPlayer.words_dtype
-
-    def prepare(self, env):
-        """The launch's scratch, before the launch is captured into a graph."""
-        env.playout_net_halving_scratch(self.halving)
-
-    def launch(self, env, weights, sets, words, sum_out, action_out, count_out=None):
-        """As HalvingPlayer.launch, on the network's six tensors.  Returns (sum, count, action)."""
-        return env.playout_cards_net_halving(weights, self.halving, sets["seats"] if self.net_seats == "own" else self.net_seats,
-                                             voids=self.kind == "voids", hidden=self.kind == "hidden", words=words, depth=self.depth,
-                                             value_scale=self.value_scale, salt=self.salt, sum_out=sum_out, count_out=count_out,
-                                             action_out=action_out, **sets)
-
-
-class VersusPlayer(collections.namedtuple("VersusPlayer", CardPlayer._fields + ("halving", "versus"))):
-    """A CardPlayer of a fair kind whose playouts seat TWO networks relative to each game's viewer (tarok_playout_cards_net_versus,
-    DESIGN 8.24): versus = (own_rel, opp_rel), the relative seats of the player's own network and of the opponent's; net_seats is
-    not read.  halving: None, or the worlds of every round (tarok_playout_cards_net_versus_halving: the rows then have a count
-    per card, as a NetHalvingPlayer's)."""
-    __slots__ = ()
-
-    needs_history, words_dtype, playouts = CardPlayer.needs_history, CardPlayer.words_dtype, CardPlayer.playouts
-
-    def prepare(self, env):
-        """The launch's scratch, before the launch is captured into a graph."""
-        if self.halving is None:
-            env.playout_net_scratch(self.worlds)
-        else:
-            env.playout_net_halving_scratch(self.halving)
-
-    def launch(self, env, weights, opponent, sets, words, sum_out, action_out, count_out=None):
-        """As CardPlayer.launch, on the six tensors of the player's network and the six of the opponent's (None where opp_rel
-        is 0).  Returns (sum, action), or with a schedule (sum, count, action)."""
-        more = {} if self.halving is None else dict(count_out=count_out)
-        return env.playout_cards_net_versus(weights, opponent, self.worlds, self.versus[0], self.versus[1], depth=self.depth,
-                                            value_scale=self.value_scale, voids=self.kind == "voids", hidden=self.kind == "hidden",
-                                            words=words, halving=self.halving, salt=self.salt, sum_out=sum_out, action_out=action_out,
-                                            **more, **sets)
-
-
-class SampledPlayer(collections.namedtuple("SampledPlayer", CardPlayer._fields + ("halving", "versus", "modes"))):
-    """A VersusPlayer whose networks play under a play mode each, `samples` playouts per (card, world)
-    (tarok_playout_cards_net_sampled): versus = (own_rel, opp_rel) — (15, 0) where the door gave net= alone —,
-    modes = (temperature, epsilon, opp_temperature, opp_epsilon), samples the playouts per (card, world); halving is None (no
-    such launch)."""
-    __slots__ = ()
-
-    needs_history, words_dtype, playouts = CardPlayer.needs_history, CardPlayer.words_dtype, CardPlayer.playouts
-
-    def prepare(self, env):
-        """The launch's scratch, before the launch is captured into a graph."""
-        env.playout_net_sampled_scratch(self.worlds, self.samples)
-
-    def launch(self, env, weights, opponent, sets, words, sum_out, action_out, modes=None):
-        """As VersusPlayer.launch.  modes: the four numbers in self.modes' place (a caller that fixes B's mode late)."""
-        t, e, ot, oe = self.modes if modes is None else modes
-        return env.playout_cards_net_sampled(weights, opponent, self.worlds, self.samples, self.versus[0], self.versus[1], temperature=t,
-                                             epsilon=e, opp_temperature=ot, opp_epsilon=oe, depth=self.depth, value_scale=self.value_scale,
-                                             voids=self.kind == "voids", hidden=self.kind == "hidden", words=words, salt=self.salt,
-                                             sum_out=sum_out, action_out=action_out, **sets)
+        if kind == "net":
+            return env.playout_cards_net(weights, self.worlds, net_seats=net_seats, **out)
+        return env.playout_cards_net_value(weights, self.worlds, self.depth, self.value_scale, net_seats=net_seats, **out)
 
 
 def card_player(samples=None, worlds=None, voids=False, hidden=False, net=False, net_seats=15, net_worlds="det", net_depth=None,
@@ -244,17 +199,17 @@ def card_player(samples=None, worlds=None, voids=False, hidden=False, net=False,
     the door's words (say: spelling()).  samples None: 1.  front: the door also asked for a playout-valued exchange or
     bidding.  fused: the door's policy is the fused one.  history: whether the env at hand keeps the play history (None:
     the door makes its env as needs_history says).  own: the door takes net_seats="own".
-    halving: a tuple of 1..4 positive world counts, one per round of sequential halving (a HalvingPlayer): it names the worlds
+    halving: a tuple of 1..4 positive world counts, one per round of sequential halving (tarok_playout_cards_halving): it names the worlds
     itself — `worlds` None (or 0) or their sum —, goes with voids / hidden as worlds does, and is not built for net=, the
     exchange, the bidding or open hands.
-    net_halving: such a tuple for the NET-played launch (a NetHalvingPlayer, tarok_playout_cards_net_halving): it requires
+    net_halving: such a tuple for the NET-played launch (tarok_playout_cards_net_halving; the player's `halving`): it requires
     net=, names the worlds itself as halving does, goes with net_worlds and net_depth, and takes what net= takes — samples
     None or 1, no exchange, no bidding.  halving= together with net= keeps raising.
-    net_versus: (own_rel, opp_rel) — a VersusPlayer (tarok_playout_cards_net_versus): the playouts seat the player's network on
+    net_versus: (own_rel, opp_rel) — the player's `versus` (tarok_playout_cards_net_versus): the playouts seat the player's network on
     the relative seats of own_rel and an opponent's on those of opp_rel, relative to each game's viewer.  It requires net=, goes
     with net_worlds, net_depth and net_halving, and seats the networks itself: net_seats stays at its default.
-    net_sampled: dict(samples=, temperature=, epsilon=, opp_temperature=, opp_epsilon=) on top of net= or net_versus= — a
-    SampledPlayer (tarok_playout_cards_net_sampled): the networks play under those play modes (the opponent's default to the
+    net_sampled: dict(samples=, temperature=, epsilon=, opp_temperature=, opp_epsilon=) on top of net= or net_versus= — the
+    player's `modes` (tarok_playout_cards_net_sampled): the networks play under those play modes (the opponent's default to the
     player's), `samples` playouts per (card, world).  With net= alone the network sits on all four seats, (own_rel, opp_rel) =
     (15, 0): net_seats stays at its default.  Not built, and refused by name: net_halving, the exchange and the bidding."""
     sampled = None
@@ -319,11 +274,8 @@ def card_player(samples=None, worlds=None, voids=False, hidden=False, net=False,
     kind = "open" if not worlds else "voids" if voids else "hidden" if hidden else net_worlds
     if kind in WORDS_DTYPE and history is not None and not history:
         raise ValueError(say("the %s worlds read the play history: TarokVecEnv(history=True)" % kind))
-    player = CardPlayer(kind, worlds, samples, bool(net), net_seats, net_depth, float(net_value_scale), int(salt))
-    if sampled is not None:
-        return SampledPlayer(*player._replace(samples=sampled[0]), None, (15, 0) if net_versus is None else net_versus, sampled[1])
-    if net_versus is not None:
-        return VersusPlayer(*player, net_halving, net_versus)
-    if net_halving is not None:
-        return NetHalvingPlayer(*player, net_halving)
-    return player if halving is None else HalvingPlayer(*player, halving)
+    samples, modes = (samples, None) if sampled is None else sampled
+    if modes is not None and net_versus is None:
+        net_versus = (15, 0)
+    return CardPlayer(kind, worlds, samples, bool(net), net_seats, net_depth, float(net_value_scale), int(salt),
+                      halving if net_halving is None else net_halving, net_versus, modes)

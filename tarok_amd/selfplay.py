@@ -370,26 +370,27 @@ class SelfPlay:
             if versus is not None and (opponent is None or pool):
                 raise ValueError("teacher: versus=(own_rel, opp_rel) seats the frozen opponent inside the teacher's playouts: it goes with "
                                  "opponent= (ONE snapshot(), not a pool)")
+            options = dict(halving=teacher.get("halving"), net_halving=teacher.get("net_halving"), net_versus=versus, net_sampled=sampled or None)
             p = playout.card_player(1 if sampled else int(teacher.get("samples", 1)), int(teacher.get("worlds") or 0), bool(teacher.get("voids", False)),
                                     bool(teacher.get("hidden", False)), net, int(teacher.get("net_seats", 15)), teacher.get("net_worlds", "det"),
                                     teacher.get("depth"), 1.0 / reward_scale if reward_scale else 0.0, int(teacher.get("salt", 0)),
                                     fused=(hidden == 256) if fused is None else bool(fused), history=getattr(env, "history", False), own=False,
-                                    say=playout.spelling("teacher: ", net_depth="depth", net_value_scale="1 / reward_scale"),
-                                    **({"halving": teacher["halving"]} if "halving" in teacher else {}),
-                                    **({"net_halving": teacher["net_halving"]} if teacher.get("net_halving") is not None else {}),
-                                    **({} if versus is None else {"net_versus": versus}),
-                                    **({} if not sampled else {"net_sampled": sampled}))
+                                    say=playout.spelling("teacher: ", net_depth="depth", net_value_scale="1 / reward_scale"), **options)
             tau, every = float(teacher.get("tau", 1.0)), int(teacher.get("every", 1))
             if not (every >= 1 and 0.0 <= tau < float("inf")):
                 raise ValueError("teacher: tau >= 0 and finite, every >= 1")
             self._player = p                          # self.teacher: the same player as the dict it has always been
             self.teacher = dict(worlds=p.worlds, samples=p.samples, tau=tau, every=every, salt=p.salt, voids=p.kind == "voids" and not net,
-                                hidden=p.kind == "hidden" and not net, net=net, net_seats=p.net_seats, net_worlds=p.kind if net else "det",
-                                **({} if p.depth is None else dict(depth=p.depth)), **({} if p.halving is None else {"net_halving" if net else "halving": p.halving}),
-                                **({} if versus is None else dict(versus=p.versus)),
-                                **({} if not sampled else dict(temperature=p.modes[0], epsilon=p.modes[1],
-                                                               opp_temperature=sampled.get("opp_temperature"),
-                                                               opp_epsilon=sampled.get("opp_epsilon"))))
+                                hidden=p.kind == "hidden" and not net, net=net, net_seats=p.net_seats, net_worlds=p.kind if net else "det")
+            if p.depth is not None:
+                self.teacher["depth"] = p.depth
+            if p.halving is not None:
+                self.teacher["net_halving" if net else "halving"] = p.halving
+            if versus is not None:
+                self.teacher["versus"] = p.versus
+            if sampled:
+                self.teacher.update(temperature=p.modes[0], epsilon=p.modes[1], opp_temperature=sampled.get("opp_temperature"),
+                                    opp_epsilon=sampled.get("opp_epsilon"))
         elif distill_coef:
             raise ValueError("distill_coef weighs the playout teacher's term: pass teacher= as well")
         self.env = env
@@ -677,16 +678,12 @@ class SelfPlay:
         playout_net_seats or playout_net_halving): inside those playouts the network plays as at the table — a draw from its
         softmax at t (default 1; 0: greedy), the Bot's card with probability e (default 0) —, S playouts (default 1) per
         (card, world) (evaluate_playout_vs_bot(net_samples=, net_temperature=, net_epsilon=)).  None: as before."""
-        halving = {} if playout_halving is None else dict(halving=playout_halving)
-        if playout_net_halving is not None:
-            halving = dict(halving, net_halving=playout_net_halving)
         sampled = {k: v for k, v in dict(samples=playout_net_samples, temperature=playout_net_temperature,
                                          epsilon=playout_net_epsilon).items() if v is not None}
-        if sampled:
-            halving = dict(halving, net_sampled=sampled)
         playout.card_player(versus_playout, playout_worlds, playout_voids, playout_hidden, bool(playout_net), playout_net_seats,
                             playout_net_worlds, playout_net_depth, front=playout_exchange is not None or playout_bidding is not None,
-                            say=playout.spelling(pattern="playout_%s", samples="versus_playout"), **halving)
+                            say=playout.spelling(pattern="playout_%s", samples="versus_playout"), halving=playout_halving,
+                            net_halving=playout_net_halving, net_sampled=sampled or None)
         if playout_halving is not None and versus_playout is None:
             raise ValueError("playout_halving goes with versus_playout=samples")
         if playout_bidding is not None and playout_worlds is None:
@@ -717,18 +714,16 @@ class SelfPlay:
         if versus_playout is None:
             return own
         from .evaluate import evaluate_playout_vs_bot
-        if playout_net:
+        if playout_net:                               # what was left at its default is left out: the calls as they were
+            more = dict({"net_" + k: v for k, v in sampled.items()}, net_worlds=None if playout_net_worlds == "det" else playout_net_worlds,
+                        net_depth=playout_net_depth, net_value_scale=None if playout_net_depth is None else 1.0 / self.reward_scale,
+                        net_halving=playout_net_halving)
             return own, evaluate_playout_vs_bot(None, n_games, episodes, mix=mix, device=self.env.device_index, worlds=playout_worlds,
-                                                net=self._w, net_seats=playout_net_seats,
-                                                **({} if playout_net_worlds == "det" else dict(net_worlds=playout_net_worlds)),
-                                                **({} if playout_net_depth is None else
-                                                   dict(net_depth=playout_net_depth, net_value_scale=1.0 / self.reward_scale)),
-                                                **({} if playout_net_halving is None else dict(net_halving=playout_net_halving)),
-                                                **{"net_" + k: v for k, v in sampled.items()})
+                                                net=self._w, net_seats=playout_net_seats, **{k: v for k, v in more.items() if v is not None})
         return own, evaluate_playout_vs_bot(int(versus_playout), n_games, episodes, mix=mix, device=self.env.device_index,
                                             worlds=playout_worlds, voids=bool(playout_voids), exchange=playout_exchange,
-                                            hidden=bool(playout_hidden), bidding=playout_bidding,
-                                            pass_value=pass_value, **halving)
+                                            hidden=bool(playout_hidden), bidding=playout_bidding, pass_value=pass_value,
+                                            **({} if playout_halving is None else dict(halving=playout_halving)))
 
     def _alloc(self, T):
         n, dev = self.env.n, self.device
@@ -751,7 +746,7 @@ class SelfPlay:
             dtype = self._player.words_dtype            # the voids / played words of the teacher's worlds
             self._teach_words = None if dtype is None else torch.empty(n, dtype=dtype, device=dev)
             self._player.prepare(self.env)            # the net launch's scratch: allocated here, before any capture
-            if self._player.halving is not None:      # a halving teacher's playouts per card: its targets' divisors
+            if self._player.counts:                   # a halving teacher's playouts per card: its targets' divisors
                 self._teach_counts = torch.empty((n, K.PLAYOUT_RANKS), dtype=torch.int32, device=dev)
         self._graph = None
 
@@ -768,23 +763,17 @@ class SelfPlay:
         one tarok_playout_targets on the words of that lock-step.  Stream-ordered, read-only on the env, no allocation.
         A versus teacher's launch reads the live rollout weights as network A and the frozen opponent's own tensors (the ones
         set_opponent writes in place) as network B."""
-        nets = (self._w, self._opp) if "versus" in self.teacher else (self._w,)
-        if "temperature" in self.teacher:             # the sampled launch: B's mode, where the dict left it open, is the env's own
-            nets = (self._w, self._opp if "versus" in self.teacher else None)
-            self._player.launch(self.env, *nets, dict(seats_per_game=self._seats), self._teach_words, self._teach_sums, self._teach_act,
-                                modes=self.teacher_modes())
-            self.env.playout_targets(self._teach_sums, self._buf["words"][t], self._player.playouts, self.teacher["tau"],
-                                     seats_per_game=self._seats, target_out=self._buf["teach"][t])
-            return
-        if self._player.halving is not None:          # one halving launch, one tarok_playout_targets_counts on its counts
-            self._player.launch(self.env, *nets, dict(seats_per_game=self._seats), self._teach_words, self._teach_sums, self._teach_act,
-                                count_out=self._teach_counts)
+        p, sets = self._player, dict(seats_per_game=self._seats)
+        more = dict(count_out=self._teach_counts) if p.counts else {}
+        if p.modes is not None:                       # B's mode, where the dict left it open, is the env's own
+            more["modes"] = self.teacher_modes()
+        p.launch(self.env, (self._w, self._opp if "versus" in self.teacher else None), sets, self._teach_words, self._teach_sums,
+                 self._teach_act, **more)
+        if p.counts:                                  # a halving launch: tarok_playout_targets_counts on its counts
             self.env.playout_targets_counts(self._teach_sums, self._teach_counts, self._buf["words"][t], self.teacher["tau"],
-                                            seats_per_game=self._seats, target_out=self._buf["teach"][t])
-            return
-        self._player.launch(self.env, *nets, dict(seats_per_game=self._seats), self._teach_words, self._teach_sums, self._teach_act)
-        self.env.playout_targets(self._teach_sums, self._buf["words"][t], self._player.playouts, self.teacher["tau"], seats_per_game=self._seats,
-                                 target_out=self._buf["teach"][t])
+                                            target_out=self._buf["teach"][t], **sets)
+        else:
+            self.env.playout_targets(self._teach_sums, self._buf["words"][t], p.playouts, self.teacher["tau"], target_out=self._buf["teach"][t], **sets)
 
     def _rollout_body(self, T):
         env, buf, w = self.env, self._buf, self._w

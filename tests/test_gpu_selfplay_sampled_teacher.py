@@ -52,11 +52,10 @@ def test_the_recorded_rows_are_the_eager_launch_and_captured_equals_eager(T, mod
     """mode: the env's play mode when the rollout is captured (None: a new env's (1, 0)); the teacher leaves B's mode open, so B
     plays that mode inside the playouts — and the rows differ from those of B at another mode and from the greedy launch's."""
     import torch
-    from tarok_amd import playout
     snap = snapshot_of(T, 3)
     ea, a = make(T, snap, True, mode=mode)
     eb, b = make(T, snap, False, mode=mode)
-    assert type(a._player) is playout.SampledPlayer and a._player.playouts == 4
+    assert a._player.launch_kind == "sampled" and a._player.playouts == 4
     with torch.no_grad():
         b._alloc(STEPS)
         b._collect_body(2)                               # (SelfPlay.collect warms up with two lock-steps before it captures)
@@ -94,10 +93,9 @@ def test_the_recorded_rows_are_the_eager_launch_and_captured_equals_eager(T, mod
 def test_a_teacher_without_the_new_keys_records_the_existing_launch(T):
     """teacher=dict(net=True, worlds=2, versus=(1, 14)) — no temperature, no samples: the greedy versus launch's rows, as before."""
     import torch
-    from tarok_amd import playout
     snap = snapshot_of(T, 3)
     ec, c = make(T, snap, False, dict(net=True, worlds=2, versus=(1, 14), tau=8, salt=11))
-    assert "temperature" not in c.teacher and type(c._player) is playout.VersusPlayer
+    assert "temperature" not in c.teacher and c._player.launch_kind == "versus" and c._player.modes is None
     buf = c.collect(STEPS)
     twin = T.TarokVecEnv(N, seed=6, mix=T.karte.MIX_BOT)
     twin.reset()

@@ -92,8 +92,7 @@ def test_a_teacher_without_versus_records_the_existing_launch(T):
     snap = snapshot_of(T, 3)
     plain = dict(net=True, worlds=2, tau=8, salt=11)
     ec, c = make(T, snap, False, plain)
-    from tarok_amd import playout
-    assert "versus" not in c.teacher and type(c._player) is playout.CardPlayer and playout.VersusPlayer is not type(c._player)
+    assert "versus" not in c.teacher and c._player.versus is None and c._player.launch_kind == "net"
     buf = c.collect(STEPS)
     twin = T.TarokVecEnv(N, seed=6, mix=T.karte.MIX_BOT)
     twin.reset()

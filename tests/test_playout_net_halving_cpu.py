@@ -150,10 +150,10 @@ def test_the_card_player_rules_and_the_surface():
     assert inspect.signature(EV.evaluate_playout_vs_bot).parameters["net_halving"].default is None
     assert inspect.signature(EV._playout_passes).parameters["net_halving"].default is None
     assert inspect.signature(SP.SelfPlay.evaluate).parameters["playout_net_halving"].default is None
-    assert P.CardPlayer._fields == ("kind", "worlds", "samples", "net", "net_seats", "depth", "value_scale", "salt")
-    assert P.NetHalvingPlayer._fields == P.CardPlayer._fields + ("halving",) == P.HalvingPlayer._fields
+    assert P.CardPlayer._fields[:8] == ("kind", "worlds", "samples", "net", "net_seats", "depth", "value_scale", "salt")
+    assert P.CardPlayer._fields[8:] == ("halving", "versus", "modes")          # one class: the schedule is a field of every player
     p = P.card_player(None, None, net=True, net_halving=(2, 2, 4, 8), net_worlds="hidden", net_depth=3, net_seats=5, salt=3)
-    assert isinstance(p, P.NetHalvingPlayer)
+    assert isinstance(p, P.CardPlayer) and p.launch_kind == "net_halving" and p.counts
     assert (p.kind, p.worlds, p.samples, p.net, p.net_seats, p.depth, p.halving, p.salt, p.needs_history) == \
         ("hidden", 16, 1, True, 5, 3, (2, 2, 4, 8), 3, True)
     assert P.card_player(1, 16, net=True, net_halving=[2, 2, 4, 8]).kind == "det" and P.card_player(None, 0, net=True, net_halving=(3,)).worlds == 3

@@ -174,15 +174,15 @@ def test_the_card_player_rules_and_the_surface():
     assert P.card_player(None, 3, net=True) == P.CardPlayer("det", 3, 1, True, 15, None, 70.0, 0)
     assert P.card_player(None, 3, net=True, net_sampled=None) == P.card_player(None, 3, net=True)
     p = P.card_player(None, 3, net=True, net_versus=(1, 14))
-    assert type(p) is P.VersusPlayer and p == ("det", 3, 1, True, 15, None, 70.0, 0, None, (1, 14))
-    assert P.VersusPlayer._fields == P.CardPlayer._fields + ("halving", "versus")
+    assert p.launch_kind == "versus" and p == ("det", 3, 1, True, 15, None, 70.0, 0, None, (1, 14), None)
+    assert P.CardPlayer._fields[8:] == ("halving", "versus", "modes") and len(P.CardPlayer._fields) == 11
     # with it
     p = P.card_player(None, 3, net=True, net_sampled=dict(samples=4, temperature=0.5))
-    assert type(p) is P.SampledPlayer and p == ("det", 3, 4, True, 15, None, 70.0, 0, None, (15, 0), (0.5, 0.0, 0.5, 0.0))
+    assert p.launch_kind == "sampled" and p == ("det", 3, 4, True, 15, None, 70.0, 0, None, (15, 0), (0.5, 0.0, 0.5, 0.0))
     assert p.playouts == 12 and p.halving is None and not p.needs_history
     p = P.card_player(None, 2, net=True, net_versus=(1, 14), net_worlds="hidden", net_depth=3, salt=7,
                       net_sampled=dict(epsilon=0.25, opp_temperature=2, opp_epsilon=0))
-    assert type(p) is P.SampledPlayer and p == ("hidden", 2, 1, True, 15, 3, 70.0, 7, None, (1, 14), (1.0, 0.25, 2.0, 0.0)) and p.needs_history
+    assert p.launch_kind == "sampled" and p == ("hidden", 2, 1, True, 15, 3, 70.0, 7, None, (1, 14), (1.0, 0.25, 2.0, 0.0)) and p.needs_history
     net = dict(net=True, worlds=3)
     for kw in (dict(worlds=3, samples=1, net_sampled=dict(samples=2)),                                   # requires net=
                dict(net, net_sampled=dict(samples=0)), dict(net, net_sampled=dict(samples=1025)), dict(net, net_sampled=dict(samples=2.0)),
@@ -223,7 +223,7 @@ def test_the_card_player_rules_and_the_surface():
 
 
 def test_the_doors_issue_the_launch():
-    """A SampledPlayer's launch and SelfPlay's teacher on stand-ins: playout_cards_net_sampled with A, then B, the sizes, the
+    """A sampled player's launch and SelfPlay's teacher on stand-ins: playout_cards_net_sampled with A, then B, the sizes, the
     roles and the modes; a versus teacher that leaves the opponent's mode open takes the env's play mode when it launches; a
     teacher dict without the new keys is the parent's."""
     import torch
@@ -236,7 +236,7 @@ def test_the_doors_issue_the_launch():
     p = P.card_player(None, 3, net=True, net_versus=(1, 14), net_worlds="hidden", net_depth=2, net_value_scale=35.0, salt=7,
                       net_sampled=dict(samples=4, temperature=0.5, opp_epsilon=0.25))
     p.prepare(env)
-    p.launch(env, "A", "B", dict(seats=4), "W", "S", "C")
+    p.launch(env, ("A", "B"), dict(seats=4), "W", "S", "C")
     assert env.calls == ["playout_net_sampled_scratch(3, 4)",
                          "playout_cards_net_sampled('A', 'B', 3, 4, 1, 14, action_out='C', depth=2, epsilon=0.0, hidden=True, opp_epsilon=0.25, "
                          "opp_temperature=0.5, salt=7, seats=4, sum_out='S', temperature=0.5, value_scale=35.0, voids=False, words='W')"], env.calls
@@ -249,11 +249,11 @@ def test_the_doors_issue_the_launch():
             pass
         return sp
     sp = teacher_of(dict(net=True, worlds=2, samples=3, temperature=1.0, versus=(1, 14), tau=8.0), opponent=weights())
-    assert type(sp._player) is P.SampledPlayer and sp._player.playouts == 6
+    assert sp._player.launch_kind == "sampled" and sp._player.playouts == 6
     assert sp.teacher == dict(worlds=2, samples=3, tau=8.0, every=1, salt=0, voids=False, hidden=False, net=True, net_seats=15, net_worlds="det",
                               versus=(1, 14), temperature=1.0, epsilon=0.0, opp_temperature=None, opp_epsilon=None)
     old = teacher_of(dict(net=True, worlds=2, tau=8.0, versus=(1, 14)), opponent=weights())
-    assert type(old._player) is P.VersusPlayer and "temperature" not in old.teacher                      # without the keys: as before
+    assert old._player.launch_kind == "versus" and old._player.modes is None and "temperature" not in old.teacher                      # without the keys: as before
     opp = [torch.zeros(1)] * 6
     sp.env, sp.device, sp.fused, sp._w, sp._opp, sp._seats, sp.reward_scale = Env(), torch.device("cpu"), True, weights(), opp, None, 0.25
     sp._alloc(3)

@@ -189,25 +189,24 @@ def test_the_card_player_rules_and_the_surface():
     for fn in (EV.evaluate_playout_vs_bot, EV._playout_passes):
         assert inspect.signature(fn).parameters["net_versus"].default is None and inspect.signature(fn).parameters["net_opponent"].default is None
     # what the call returns without the keyword: the parent's tuples, field for field
-    assert P.CardPlayer._fields == ("kind", "worlds", "samples", "net", "net_seats", "depth", "value_scale", "salt")
-    assert P.NetHalvingPlayer._fields == P.CardPlayer._fields + ("halving",) == P.HalvingPlayer._fields
-    assert P.VersusPlayer._fields == P.CardPlayer._fields + ("halving", "versus")
+    assert P.CardPlayer._fields[:8] == ("kind", "worlds", "samples", "net", "net_seats", "depth", "value_scale", "salt")
+    assert P.CardPlayer._fields[8:10] == ("halving", "versus") and P.CardPlayer._fields[10:] == ("modes",)      # one class holds them all
     assert P.card_player(4) == P.CardPlayer("open", None, 4, False, 15, None, 70.0, 0)
     assert P.card_player(2, 3, voids=True, salt=5) == P.CardPlayer("voids", 3, 2, False, 15, None, 70.0, 5)
     assert P.card_player(None, 3, net=True) == P.CardPlayer("det", 3, 1, True, 15, None, 70.0, 0)
     assert P.card_player(None, 3, net=True, net_versus=None) == P.card_player(None, 3, net=True)
     p = P.card_player(None, 3, net=True, net_seats="own", net_worlds="hidden", net_depth=2, net_value_scale=35.0)
-    assert type(p) is P.CardPlayer and p == ("hidden", 3, 1, True, "own", 2, 35.0, 0)
+    assert p.launch_kind == "net_value" and p == ("hidden", 3, 1, True, "own", 2, 35.0, 0, None, None, None)
     p = P.card_player(None, None, net=True, net_halving=(1, 2), net_seats=5)
-    assert type(p) is P.NetHalvingPlayer and p == ("det", 3, 1, True, 5, None, 70.0, 0, (1, 2))
+    assert p.launch_kind == "net_halving" and p == ("det", 3, 1, True, 5, None, 70.0, 0, (1, 2), None, None)
     p = P.card_player(2, None, halving=(1, 2), hidden=True)
-    assert type(p) is P.HalvingPlayer and p == ("hidden", 3, 2, False, 15, None, 70.0, 0, (1, 2))
+    assert p.launch_kind == "halving" and p == ("hidden", 3, 2, False, 15, None, 70.0, 0, (1, 2), None, None)
     # with it
     p = P.card_player(None, 3, net=True, net_versus=(1, 14), net_worlds="voids", net_depth=3, salt=7)
-    assert type(p) is P.VersusPlayer and p == ("voids", 3, 1, True, 15, 3, 70.0, 7, None, (1, 14))
+    assert p.launch_kind == "versus" and p == ("voids", 3, 1, True, 15, 3, 70.0, 7, None, (1, 14), None)
     assert p.needs_history and p.playouts == 3 and p.halving is None
     p = P.card_player(None, None, net=True, net_versus=[3, 8], net_halving=(1, 2))
-    assert type(p) is P.VersusPlayer and (p.worlds, p.halving, p.versus, p.kind) == (3, (1, 2), (3, 8), "det")
+    assert p.launch_kind == "versus" and p.counts and (p.worlds, p.halving, p.versus, p.kind) == (3, (1, 2), (3, 8), "det")
     net = dict(net=True, worlds=3)
     for kw in (dict(net_versus=(1, 14), worlds=3, samples=1),                                   # requires net=
                dict(net, net_versus=(1, 1)), dict(net, net_versus=(15, 8)), dict(net, net_versus=(16, 0)), dict(net, net_versus=(0, -1)),
@@ -300,7 +299,7 @@ def test_the_env_method_issues_the_launch():
 
 
 def test_the_doors_issue_the_launch():
-    """A VersusPlayer's launch, evaluate's wiring and SelfPlay's teacher on stand-ins: playout_cards_net_versus with A, then B,
+    """A versus player's launch, evaluate's wiring and SelfPlay's teacher on stand-ins: playout_cards_net_versus with A, then B,
     the roles, the kind and the schedule; the teacher reads the rollout weights as A and the opponent's own tensors as B."""
     import torch
     from tarok_amd import playout as P
@@ -311,14 +310,14 @@ def test_the_doors_issue_the_launch():
     env = Env()
     p = P.card_player(None, 3, net=True, net_versus=(1, 14), net_worlds="hidden", net_depth=2, net_value_scale=35.0, salt=7)
     p.prepare(env)
-    p.launch(env, "A", "B", dict(seats=4), "W", "S", "C")
+    p.launch(env, ("A", "B"), dict(seats=4), "W", "S", "C")
     assert env.calls == ["playout_net_scratch(3)",
                          "playout_cards_net_versus('A', 'B', 3, 1, 14, action_out='C', depth=2, halving=None, hidden=True, salt=7, seats=4, "
                          "sum_out='S', value_scale=35.0, voids=False, words='W')"], env.calls
     env = Env()
     p = P.card_player(None, None, net=True, net_versus=(3, 8), net_halving=(1, 2))
     p.prepare(env)
-    p.launch(env, "A", "B", dict(seats_per_game="G"), None, "S", "C", count_out="N")
+    p.launch(env, ("A", "B"), dict(seats_per_game="G"), None, "S", "C", count_out="N")
     assert env.calls == ["playout_net_halving_scratch((1, 2))",
                          "playout_cards_net_versus('A', 'B', 3, 3, 8, action_out='C', count_out='N', depth=None, halving=(1, 2), hidden=False, "
                          "salt=0, seats_per_game='G', sum_out='S', value_scale=70.0, voids=False, words=None)"], env.calls
@@ -335,7 +334,7 @@ def test_the_doors_issue_the_launch():
         sp2.__init__(WithHistory(), hidden=256, teacher=dict(net=True, worlds=2, tau=8.0), opponent=weights())
     except (AttributeError, TypeError):
         pass
-    assert "versus" not in sp2.teacher and type(sp2._player) is P.CardPlayer               # without the key: as before
+    assert "versus" not in sp2.teacher and sp2._player.versus is None and sp2._player.launch_kind == "net"      # without the key: as before
     opp = [torch.zeros(1)] * 6
     sp.env, sp.device, sp.fused, sp._w, sp._opp, sp._seats, sp.reward_scale = Env(), torch.device("cpu"), True, weights(), opp, None, 0.25
     sp._alloc(3)
